@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- RealSR x4 tiled inference on MI355X: BASELINE.json's metric on its config C2.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
         N = 1: runs in this process.  N > 1 without a torch.distributed environment: this script launches the N ranks
         itself (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...) and refuses to
         report anything but n_gpus == N.
@@ -18,10 +18,18 @@ load.  Weak scaling: every rank upsamples its own frame each step; value = total
 
 `value` is the HBM-resident rate (input and output images in device memory when the timed region starts -- the driver
 contract: a PCIe-inclusive rate is never `value`).  SURVEY.md 8(d) defines the end-user metric as host memory -> host
-memory: that run (rsr_process, the reference's RealSR::process boundary, H2D + network + D2H) is timed right behind it and
-reported in `host_to_host` (pinned buffers = what the CLI uses; pageable = a caller that hands over malloc'd memory).
+memory: under --full that run (rsr_process, the reference's RealSR::process boundary, H2D + network + D2H) is timed right behind
+it and reported in `host_to_host` (pinned buffers = what the CLI uses; pageable = a caller that hands over malloc'd memory).
 
-Prints ONE JSON line (rank 0).  The CPU oracle is used only for the cpu_baseline leg.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints it: `value`, `ms_per_step`, the
+config and an output checksum.  `--full` adds everything else: the hipEvent-profiled second pass and its `roofline` block,
+`host_to_host`, `other_configs` (C1 / C3 / C5), `precise_mode`, `cpu_baseline`, `group_mode` and `small_images`; the `--no-*`
+options trim that set.  The CPU oracle is used only for the cpu_baseline leg.
+
+--dump-outputs DIR: after the timed steps, every rank writes what its last timed step computed, for comparing two builds output
+for output: DIR/output.npy (rank r > 0: DIR/output_rank<r>.npy), float32 [n, 3], the RGB values of a fixed seeded sample of
+n ~ 2M / N pixels of the 7680x4320 uint8 output frame in row-major order (DUMP_PIXELS; 24 MB over all ranks).  The inputs are
+seeded (image seed 1235 + rank, weight seed 42), so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -46,6 +54,7 @@ _UP = 2 * 9 * (4 * 64 * 64 + 16 * 64 * 64 + 16 * 64 * 64 + 16 * 64 * 3)
 assert _LR + _UP == FLOP_PER_PADDED_LR_PX
 HBM_PEAK_TBPS = 8.0  # MI355X_MICROARCH.md: HBM3E spec (6.29 TB/s measured stream)
 RIDGE_FLOP_PER_BYTE = PEAK_F16_TFLOPS / HBM_PEAK_TBPS  # 312.5
+DUMP_PIXELS, DUMP_SEED = 1 << 21, 20240611  # --dump-outputs: sampled output pixels over all ranks, and the sample's seed
 
 
 def executed_lr_px(tw, th):
@@ -81,6 +90,17 @@ def padded_px(w, h, T, P=10):
         for x0 in range(0, w, T):
             n += (min(x0 + T, w) - x0 + 2 * P) * (min(y0 + T, h) - y0 + 2 * P)
     return n
+
+
+def dump_outputs(out_dir, d_out, rank, world):
+    """Write a fixed seeded sample of the uint8 HWC device frame d_out as float32 [n, 3] (see the module docstring)."""
+    import numpy as np
+    import torch
+    npx = d_out.shape[0] * d_out.shape[1]
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, npx, DUMP_PIXELS // world))
+    sample = d_out.reshape(npx, d_out.shape[2])[torch.from_numpy(idx).to(d_out.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "output.npy" if rank == 0 else "output_rank%d.npy" % rank), sample.astype(np.float32))
 
 
 def free_port():
@@ -371,6 +391,10 @@ def main():
     ap.add_argument("--frame-size", default="%dx%d" % (W_IN, H_IN), help="group mode: WxH of the frames (default the C2 / C4 frame)")
     ap.add_argument("--tile", type=int, default=TILE, help="group mode: tile size")
     ap.add_argument("--merge", type=int, default=None, help="group mode: rsr_set_option merge (1 = small images of concurrent calls are not merged)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiled pass, roofline, host->host, other configs, precise mode, CPU baseline and group legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's output frame as DIR/output.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--no-host", action="store_true", help="skip the host->host leg")
@@ -495,11 +519,13 @@ def main():
     if rank == 0 and os.environ.get("RSR_BENCH_MARKS"):  # tools/power_sampler.py: power / clock over exactly the timed region
         with open(os.environ["RSR_BENCH_MARKS"], "w") as f:
             f.write("%.6f %.6f\n" % (wall0, time.time()))
-    # Pass 2 -- the same steps again with hipEvents around every kernel launch on the engine's launch stream (~1 us per launch,
-    # 352 launches per frame): the per-kernel breakdown of the roofline block, and `ms_per_step_profiled` next to `ms_per_step`.
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, rank, world)
+    # Pass 2 (--full) -- the same steps again with hipEvents around every kernel launch on the engine's launch stream (~1 us per
+    # launch, 352 launches per frame): the per-kernel breakdown of the roofline block, and `ms_per_step_profiled` next to `ms_per_step`.
     prof = conv_ms = None
     dt_prof = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         sr.set_profiling(True)
         sr.get_profile(reset=True)
         sr.get_conv_times(reset=True)
@@ -520,9 +546,9 @@ def main():
         dt_prof = max_over_ranks(dt_prof)
     checksum = int(d_out[::97, ::89].to(torch.int64).sum().item())
 
-    # ---- host memory -> host memory: rsr_process incl. H2D / D2H, same frame, same step count ----
+    # ---- host memory -> host memory (--full): rsr_process incl. H2D / D2H, same frame, same step count ----
     host = None
-    if not args.no_host:
+    if args.full and not args.no_host:
         host = {}
         pin_in, pin_out = R.PinnedArray(img.shape), R.PinnedArray((H_IN * SCALE, W_IN * SCALE, 3))
         pin_in.array[:] = img
@@ -704,7 +730,7 @@ def main():
     del d_in, d_out, blob
     torch.cuda.empty_cache()
     kept = {}
-    if rank == 0 and world == 1 and not same_gpu and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not same_gpu and not args.no_other_configs:
         # the other single-GPU BASELINE configs, same definition as `value`.  C1 is the config the reference runs on its CPU path
         # (-g -1, one thread): its GPU side here, its CPU side in cpu_baseline.c1_single_thread; C4 needs 8 GPUs.
         res["other_configs"] = {}
@@ -731,12 +757,12 @@ def main():
         res["other_configs"]["C4"] = {"value": None, "status": "unmeasured: n_gpus = 1",
                                       "config": "64 x C2 frames over 8 GPUs, -j 4:8:4 (one process, rsr_create_group, proc threads on one shared queue)",
                                       "n1_anchor": "group_mode below: the same pipeline with ONE GPU, 16 frames, jobs_proc 2, host -> host"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline(pp, bp, gpu_c1=kept.get("C1"), gpu_c1_precise=kept.get("C1p"))
         except Exception as e:  # the oracle is optional here; never fail the GPU number on it
             res["cpu_baseline"] = {"value": None, "unit": "Mpix/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
-    if rank == 0 and world == 1 and not same_gpu and not args.no_group:
+    if args.full and rank == 0 and world == 1 and not same_gpu and not args.no_group:
         # The product's own multi-GPU pipeline (config C4: rsr_create_group + jobs_proc threads per GPU on one shared frame queue,
         # host memory -> host memory) with ONE GPU: the N = 1 anchor of a future scaling curve.  Child process with a deadline.
         cmd = [sys.executable, os.path.abspath(__file__), "--mode", "group", "--gpus", "1", "--frames", "16", "--jobs-proc", "2"]
@@ -765,7 +791,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and world > 1 and not args.no_group:
+    if args.full and rank == 0 and world > 1 and not args.no_group:
         # The product's own multi-GPU path (rsr_create_group: ncclCommInitAll + one ncclBroadcast inside ONE process, proc threads
         # on a shared queue = config C4) in a child process with a deadline, after every rank has released its GPU: a first-contact
         # failure there must not cost the rank-mode line.

@@ -2,6 +2,8 @@
 against (the reference ships none, SURVEY.md 8c -> "parity unpinned"), so it is pinned against
 independent constructions: numpy fp16, a PyTorch RRDBNet, a second tiling implementation written from
 realsr.cpp in numpy, and the committed golden outputs (drift guard)."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -11,7 +13,8 @@ import oracle
 from realsr_ncnn_vulkan_amd import synth
 from torch_ref import net_forward_np
 
-REF_PARAM = "/root/reference/models/models-DF2K/x4.param"
+# size + SHA-256 of the upstream project's models/models-DF2K{,_JPEG}/x4.param (not shipped here)
+REF_PARAM_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_param.json")
 
 
 def test_fp16_roundtrip_matches_numpy():
@@ -28,11 +31,13 @@ def test_fp16_roundtrip_matches_numpy():
 
 
 def test_param_generator_equals_reference_file():
-    if not os.path.exists(REF_PARAM):
-        pytest.skip("reference checkout not present on this box")
-    assert synth.param_text() == open(REF_PARAM).read()
+    with open(REF_PARAM_DIGESTS) as f:
+        ref = json.load(f)
+    df2k, jpeg = ref["models/models-DF2K/x4.param"], ref["models/models-DF2K_JPEG/x4.param"]
+    text = synth.param_text().encode()
+    assert (len(text), hashlib.sha256(text).hexdigest()) == (df2k["bytes"], df2k["sha256"])
     # both shipped model dirs carry the same graph
-    assert open(REF_PARAM).read() == open(REF_PARAM.replace("models-DF2K", "models-DF2K_JPEG")).read()
+    assert jpeg == df2k
 
 
 def test_bin_size_matches_ncnn_layout(model_dir):

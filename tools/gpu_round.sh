@@ -7,10 +7,10 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
+timeout 900 python $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
 # board power + sclk at 20 Hz over a longer timed region of the same command (bench.py writes its marks): profiles/<tag>_power_clock.txt
 timeout 300 python $R/tools/power_sampler.py --out $OUT/power_clock.txt --hz 20 -- python $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-host --no-other-configs --no-profile --no-group > $OUT/power.log 2>&1; echo "power rc=$?"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $R/bench.py --no-cpu-baseline --no-host --no-other-configs --no-group > $OUT/trace.log 2>&1; echo "trace rc=$?"
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $R/bench.py --full --no-cpu-baseline --no-host --no-other-configs --no-group > $OUT/trace.log 2>&1; echo "trace rc=$?"
 BA="--steps 1 --warmup 1 --no-cpu-baseline --no-profile --no-host --no-other-configs --no-group"
 i=0
 # separate --pmc passes, kernel-trace only (no other trace domain): FETCH_SIZE costs 3 TCC slots, WRITE_SIZE 2; SQ has 8 slots
