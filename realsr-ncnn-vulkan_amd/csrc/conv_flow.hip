@@ -544,8 +544,16 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
             if (EPI == 2 && has2)
             {
                 const half8 r2 = __builtin_bit_cast(half8, PRE2 ? r2q[PRE2 ? (rr & 1) : 0][n][p] : r2x[p]);
+                // v = fp16(fma(v, s2, r2)): the exact v*s2 + r2 rounded ONCE to fp32 (an explicit fma: what the contracted expression of
+                // rounds 1-6 compiled to in every instantiation), fenced like the product above so that it cannot be fused into the fp16
+                // conversion -- two roundings, fp32 then fp16, as tests/exact_conv.py epi2 restates them
 #pragma unroll
-                for (int e = 0; e < 8; e++) v[e] = (_Float16)((float)v[e] * a.s2 + (float)r2[e]);
+                for (int e = 0; e < 8; e++)
+                {
+                    float f = __builtin_fmaf((float)v[e], a.s2, (float)r2[e]);
+                    asm volatile("" : "+v"(f));
+                    v[e] = (_Float16)f;
+                }
             }
             const unsigned poff = unsigned(n * 2 + p) * pstride;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(ub, 0, o.live ? int(o.lim + poff) : 0, 0x00020000);
@@ -1340,7 +1348,9 @@ bool launch_conv_flow(const ConvArgs& a_in, int nt, int ncu, int flags, hipStrea
         if (epi >= 4 && !a.res1_kind) a.res1 = a.out16; // (conv_first: lo1_off == 0, the null resource is built on a valid base)
     }
     else if ((!a.out_planar3 && !a.out_u8) || a.out16.base || a.res1_kind || a.res2_kind) return false;
-    const bool ntw2 = (flags & 1) != 0, defer = !(flags & 2), res = !(flags & 4);
+    // (the deferred epilogue's block body is written out for half-stages 0..3 -- the hooks ride in them -- so it needs >= 4: a conv with
+    // cin <= 32, which the network does not have but rsr_conv3x3 accepts, runs the inline epilogue)
+    const bool ntw2 = (flags & 1) != 0, defer = !(flags & 2) && a.n0 + a.n1 >= 4, res = !(flags & 4);
     const int reserve = (flags & 16) ? 8192 : 0; // A/B aid: size the patch ring as if the rounds 1-3 transpose scratch (8 KB per n-tile) were still there
     if (nt == 1)
     {

@@ -49,7 +49,8 @@ def test_native_library_is_the_one_loaded(sr):
 @pytest.mark.parametrize("lrelu", [False, True])
 def test_conv3x3_layer_matches_oracle(sr, cin, cout, h, w, ups, lrelu):
     """fp16 inputs/weights, fp32 accumulate vs the oracle's fp32 conv on the same rounded operands:
-    only accumulation order + the final fp16 rounding differ -> |d| <= 2^-10 * |ref| + 1e-3."""
+    only accumulation order + the final fp16 rounding differ -> |d| <= 2^-10 * |ref| + 1e-3, and <= half an fp16 ulp of ref +
+    2^-20 * sum |x w| (the output's own rounding + the order noise)."""
     rng = np.random.default_rng(cin * 1000 + cout + h)
     x = rng.standard_normal((cin, h, w)).astype(np.float16)
     wt = (rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(cin * 9)).astype(np.float16).astype(np.float32)
@@ -58,6 +59,10 @@ def test_conv3x3_layer_matches_oracle(sr, cin, cout, h, w, ups, lrelu):
     if ups:
         xr = xr.repeat(2, axis=1).repeat(2, axis=2)
     ref = oracle.conv3x3(xr, wt, b, 2 if lrelu else 0, 0.2)
+    # the tighter bar, asserted as well: half an fp16 ulp of the reference (the output's own rounding) + the summation-order noise of
+    # the two fp32 sums, bounded by 2^-20 of the sum of the terms' magnitudes (exact operands: tests/test_gpu_exact.py)
+    mag = oracle.conv3x3(np.abs(xr), np.abs(wt), np.abs(b), 0, 0.2)
+    tight = np.spacing(np.abs(ref).astype(np.float16)).astype(np.float32) / 2 + mag * 2.0 ** -20
     try:
         # conv3x3_flow: 8 x 32 / 4 x 64 MFMA waves, with / without deferred epilogue, weights LDS-resident / streamed (flags 4),
         # rows below the tile skipped / computed
@@ -68,6 +73,7 @@ def test_conv3x3_layer_matches_oracle(sr, cin, cout, h, w, ups, lrelu):
             assert got.shape == ref.shape
             assert (np.abs(got - ref) <= np.abs(ref) * 2.0 ** -10 + 1e-3).all(), "flags=%d dbg=%d max err %g" % (
                 flags, dbg, np.abs(got - ref).max())
+            assert (np.abs(got - ref) <= tight).all(), "flags=%d dbg=%d max |d| / bound %g" % (flags, dbg, (np.abs(got - ref) / tight).max())
     finally:
         sr.set_option("flow_flags", 0)
         sr.set_option("dbg", 0)
