@@ -214,6 +214,40 @@ int rsr_conv3x3_res_precise(rsr_ctx* ctx, const uint16_t* in, const uint8_t* in_
                             const float* bias, float s1, int own_input_residual, const uint16_t* res, const uint8_t* res_lo, float s2,
                             uint16_t* out, uint8_t* out_lo);
 
+/* ---- model self-check (no reference counterpart) ----------------------------------------------------------------------- */
+/* Every feature map is stored as fp16, like the reference's GPU path (realsr.cpp:44-46); the bar is the reference's fp32 CPU path
+ * (realsr.cpp:525-838), +-1 per uint8.  Whether fp16 storage holds it depends on the weights.  rsr_selfcheck answers, on the
+ * device and in a few milliseconds: do the activations of the loaded model fit fp16, and how far does fp16 storage put the output
+ * from the fp32 result?  One tile walks the network in fp16 storage (a reduction behind every convolution reads what it stored) and
+ * again in precise mode (option "precise"); the two outputs are compared on the device.  storage_err = max |default - precise|
+ * estimates the default mode's true error e16 against fp32: e16 - eP <= storage_err <= e16 + eP with eP, precise mode's own error,
+ * about a third of e16 (profiles/selfcheck.txt has the estimate measured against the fp32 oracle). */
+typedef struct rsr_selfcheck_report
+{
+    int tile_w, tile_h;     /* the tile the check ran on */
+    float storage_err;      /* max |default - precise| of the network output before quantisation, [0,1] units */
+    float headroom;         /* (1/255) / storage_err  (FLT_MAX when storage_err == 0) */
+    int max_byte_diff;      /* max |q(default) - q(precise)|, q = the engine's uint8 conversion */
+    long long bytes_differ; /* output elements where q differs; of 3 * 16 * tile_w * tile_h */
+    float peak_abs;         /* largest finite |value| any convolution stored, default mode */
+    int peak_conv;          /* its index in x4.param order (0..350) */
+    long long nonfinite;    /* stored values that are inf / NaN, all convolutions, default mode */
+    int fp16_overflow;      /* nonfinite > 0 || peak_abs >= 65504 */
+    int recommend_precise;  /* headroom < 1.5 */
+    float elapsed_ms;       /* wall time of the check */
+} rsr_selfcheck_report;
+
+/* tile: planar fp16 [3][h][w] in [0,1] (host), or NULL = the built-in tile at w x h (w = h = 0: 148 x 148, the padded tile of a
+ * 256 x 256 image at tile 128).  RSR_E_STATE before load.  Works in either mode and leaves the context in the mode, with the plans
+ * and the output bytes it had; waits for the calls in flight on the context.  fp16_overflow is reported, not an error. */
+int rsr_selfcheck(rsr_ctx* ctx, const uint16_t* tile, int w, int h, rsr_selfcheck_report* out);
+/* Host-only (no GPU): the built-in tile, planar fp16 [3][h][w]: flat areas, ramps, hard edges and fine texture over 0 .. 1, every
+ * value k / 255 as the preprocessing produces it.  Integer arithmetic only: the same bytes everywhere. */
+int rsr_selfcheck_tile(uint16_t* dst, int w, int h);
+/* Per convolution (x4.param order, n <= 351 entries) of the context's last rsr_selfcheck: the largest finite |value| it stored and
+ * the number of inf / NaN it stored; either pointer may be NULL.  RSR_E_STATE when no self-check has run. */
+int rsr_selfcheck_ranges(rsr_ctx* ctx, float* peak, long long* nonfinite, int n);
+
 /* ---- measurement ------------------------------------------------------------------------- */
 typedef struct rsr_profile
 {
@@ -261,6 +295,10 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *                       between: half the distance to the reference's fp32 CPU path (realsr.cpp:525-838) that fp16 storage -- the
  *                       reference's own GPU path, realsr.cpp:44-46, and this engine's default (0) -- has; costs ~6 % more workspace
  *                       and the extra traffic of the residue planes in 71 of the 351 convolutions
+ *   "precise_auto"      1: "precise" is set by the model: on a loaded context rsr_selfcheck runs at once on the built-in tile and "precise"
+ *                       becomes its recommend_precise; on a context not yet loaded the same happens at the end of the next successful
+ *                       rsr_load / rsr_load_packed (which then returns the self-check's error, if it has one; the model stays loaded).
+ *                       0 [default]: off, "precise" stays where it is.  A later explicit "precise" still wins
  *   "merge"             small images of concurrent rsr_process / synchronous rsr_process_device calls walk the network as ONE tile batch, up
  *                       to this many per batch (default 16 = the most; 1 = off: the calls queue up on the compute stream).  An image is
  *                       small when its tiles are fewer than a quarter of "merge_target_items" (default 4096) 16 x 32 blocks -- 256 x 256
@@ -303,7 +341,10 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *   "lanes", "lane_in_mb", "lane_out_mb"   rsr_process lanes created so far and the device image buffers they hold (a member of
  *                       rsr_process_group allocates only the output rows of its tile range)
  *   "last_test_us"      HIP-event time of the last rsr_conv3x3 / rsr_conv3x3_res launch (with option "test_repeat" = N the
- *                       work items are repeated N times in that one launch: an L2-resident workload) */
+ *                       work items are repeated N times in that one launch: an L2-resident workload)
+ *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it)
+ *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
+ *                       "selfcheck_overflow" (-1 before the first run) */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);
 
 const char* rsr_last_error(const rsr_ctx* ctx); /* ctx may be NULL: last global (create/pack) error */

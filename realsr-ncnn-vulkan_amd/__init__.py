@@ -27,7 +27,10 @@ EXPORTS = [
     "rsr_set_progress_callback", "rsr_conv3x3_res", "rsr_create_group", "rsr_group_transport", "rsr_process_rows",
     "rsr_process_group", "rsr_device_memory", "rsr_process_tiles", "rsr_tile_partition", "rsr_rccl_probe", "rsr_get_stat",
     "rsr_net_forward_f32", "rsr_conv3x3_res_precise", "rsr_process_many",
+    "rsr_selfcheck", "rsr_selfcheck_tile", "rsr_selfcheck_ranges",
 ]
+
+NUM_CONVS = 351
 
 RSR_OK, RSR_E_ARG, RSR_E_IO, RSR_E_FORMAT, RSR_E_GRAPH, RSR_E_DEVICE, RSR_E_STATE, RSR_E_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 
@@ -37,6 +40,13 @@ class Profile(C.Structure):
                 ("pre_ms", C.c_double), ("post_ms", C.c_double), ("pre_bytes", C.c_double),
                 ("post_bytes", C.c_double), ("total_ms", C.c_double), ("tiles", C.c_longlong),
                 ("calls", C.c_longlong)]
+
+
+class SelfcheckReport(C.Structure):
+    _fields_ = [("tile_w", C.c_int), ("tile_h", C.c_int), ("storage_err", C.c_float), ("headroom", C.c_float),
+                ("max_byte_diff", C.c_int), ("bytes_differ", C.c_longlong), ("peak_abs", C.c_float), ("peak_conv", C.c_int),
+                ("nonfinite", C.c_longlong), ("fp16_overflow", C.c_int), ("recommend_precise", C.c_int),
+                ("elapsed_ms", C.c_float)]
 
 
 class RealSRError(RuntimeError):
@@ -103,6 +113,9 @@ def lib():
     L.rsr_process_many.argtypes = [vp, ip, C.POINTER(vp), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(vp), C.POINTER(ip)]
     L.rsr_net_forward_f32.argtypes = [vp, vp, ip, ip, vp]
     L.rsr_conv3x3_res_precise.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp, C.c_float, ip, vp, vp, C.c_float, vp, vp]
+    L.rsr_selfcheck.argtypes = [vp, vp, ip, ip, C.POINTER(SelfcheckReport)]
+    L.rsr_selfcheck_tile.argtypes = [vp, ip, ip]
+    L.rsr_selfcheck_ranges.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_longlong), ip]
     L.rsr_create_group.argtypes = [C.POINTER(vp), C.POINTER(ip), ip, ip, cp, cp]
     L.rsr_group_transport.restype = cp
     L.rsr_process_rows.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip]
@@ -299,6 +312,24 @@ class RealSR:
         self._ck(self._L.rsr_net_forward_f32(self._h, _p(x), w, h, _p(out)))
         return out
 
+    def selfcheck(self, tile=None, w=0, h=0):
+        """rsr_selfcheck: one tile through the network in fp16 storage and in precise mode, compared on the device.  tile: float16
+        planar (3,h,w) in [0,1], or None = the built-in tile at w x h (0, 0: 148 x 148).  Returns the report as a dict."""
+        if tile is not None:
+            tile = np.ascontiguousarray(tile, dtype=np.float16)
+            _, h, w = tile.shape
+        r = SelfcheckReport()
+        self._ck(self._L.rsr_selfcheck(self._h, _p(tile), int(w), int(h), C.byref(r)))
+        return {k: getattr(r, k) for k, _ in SelfcheckReport._fields_}
+
+    def selfcheck_ranges(self):
+        """rsr_selfcheck_ranges of the last selfcheck(): (peak float32[351], nonfinite int64[351]), x4.param order."""
+        peak = np.zeros(NUM_CONVS, dtype=np.float32)
+        bad = np.zeros(NUM_CONVS, dtype=np.int64)
+        self._ck(self._L.rsr_selfcheck_ranges(self._h, peak.ctypes.data_as(C.POINTER(C.c_float)),
+                                              bad.ctypes.data_as(C.POINTER(C.c_longlong)), NUM_CONVS))
+        return peak, bad
+
     def conv3x3_res_precise(self, x, weight, bias, s1, own_input_residual=False, x_lo=None, res=None, res_lo=None, s2=1.0, want_lo=True):
         """rsr_conv3x3_res_precise: the residual forms on the hi + lo / 2048 stream (hi float16, lo uint8 = bf8 bytes);
         returns (hi, lo), lo None unless want_lo."""
@@ -397,6 +428,17 @@ class RealSR:
         p = Profile()
         self._ck(self._L.rsr_get_profile(self._h, C.byref(p), int(bool(reset))))
         return {k: getattr(p, k) for k, _ in Profile._fields_}
+
+
+def selfcheck_tile(w=0, h=0):
+    """rsr_selfcheck_tile (host-only): the self-check's built-in tile, float16 planar (3,h,w); 0, 0 = 148 x 148."""
+    if w == 0 and h == 0:
+        w = h = 148
+    t = np.empty((3, int(h), int(w)), dtype=np.float16)
+    rc = lib().rsr_selfcheck_tile(_p(t), int(w), int(h))
+    if rc != RSR_OK:
+        raise RealSRError(rc, lib().rsr_last_error(None).decode())
+    return t
 
 
 def device_memory(gpuid=0):

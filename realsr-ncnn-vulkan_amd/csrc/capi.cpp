@@ -26,7 +26,7 @@ using namespace rsr;
 #pragma GCC visibility push(default)
 extern "C" {
 
-const char* rsr_version(void) { return "realsr-hip 0.3 (gfx950)"; }
+const char* rsr_version(void) { return "realsr-hip 0.4 (gfx950)"; }
 
 // Pinned host memory: images allocated here are copied to / from the GPU without the staging copy (the reference's
 // Vulkan path gets the same effect from its staging allocator, realsr.cpp:161-167).
@@ -101,7 +101,8 @@ int rsr_load(rsr_ctx* ctx, const char* parampath, const char* modelpath)
 {
     if (!ctx) return RSR_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->e.mu);
-    return ctx->e.load_files(parampath, modelpath);
+    const int rc = ctx->e.load_files(parampath, modelpath);
+    return (rc == RSR_OK && ctx->e.precise_auto) ? ctx->e.apply_precise_auto() : rc;
 }
 
 int rsr_set_params(rsr_ctx* ctx, int scale, int tilesize, int prepadding)
@@ -194,7 +195,8 @@ int rsr_load_packed(rsr_ctx* ctx, const void* blob, size_t bytes, int is_device)
 {
     if (!ctx || !blob) return RSR_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->e.mu);
-    return is_device ? ctx->e.load_blob_device(blob, bytes) : ctx->e.load_blob_host(blob, bytes);
+    const int rc = is_device ? ctx->e.load_blob_device(blob, bytes) : ctx->e.load_blob_host(blob, bytes);
+    return (rc == RSR_OK && ctx->e.precise_auto) ? ctx->e.apply_precise_auto() : rc;
 }
 
 int rsr_model_info(const char* parampath, const char* modelpath, int* n_layers, int* n_convs, long long* n_weights,
@@ -343,6 +345,31 @@ int rsr_net_forward_f32(rsr_ctx* ctx, const uint16_t* in, int w, int h, float* o
     return ctx->e.net_forward(in, w, h, nullptr, out);
 }
 
+int rsr_selfcheck(rsr_ctx* ctx, const uint16_t* tile, int w, int h, rsr_selfcheck_report* out)
+{
+    if (!ctx) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    return ctx->e.selfcheck(tile, w, h, out);
+}
+
+int rsr_selfcheck_tile(uint16_t* dst, int w, int h)
+{
+    if (!dst || w < 0 || h < 0 || (w == 0) != (h == 0)) return Engine::fail(RSR_E_ARG, "bad arguments");
+    if (w == 0) w = h = 148;
+    rsr::selfcheck_tile(dst, w, h);
+    return RSR_OK;
+}
+
+int rsr_selfcheck_ranges(rsr_ctx* ctx, float* peak, long long* nonfinite, int n)
+{
+    if (!ctx || n < 0 || n > kNumConvs) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    if (ctx->e.selfcheck_runs == 0) return ctx->e.fail(RSR_E_STATE, "no self-check has run on this context");
+    if (peak) std::memcpy(peak, ctx->e.sc_peak, size_t(n) * sizeof(float));
+    if (nonfinite) std::memcpy(nonfinite, ctx->e.sc_nonfinite, size_t(n) * sizeof(long long));
+    return RSR_OK;
+}
+
 int rsr_conv3x3(rsr_ctx* ctx, const uint16_t* in, int cin, int h, int w, int upsample2x, const float* weight, const float* bias,
                 int cout, int lrelu, uint16_t* out)
 {
@@ -446,6 +473,12 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "merged_images") *value = double(e.merged_images.load());
     else if (k == "merged_widest") *value = double(e.merged_widest.load());
     else if (k == "merged_mixed") *value = double(e.merged_mixed.load());
+    else if (k == "precise_active") *value = e.precise ? 1.0 : 0.0;
+    else if (k == "selfcheck_runs") *value = double(e.selfcheck_runs);
+    else if (k == "selfcheck_headroom") *value = e.selfcheck_runs ? double(e.sc_last.headroom) : -1.0;
+    else if (k == "selfcheck_peak_abs") *value = e.selfcheck_runs ? double(e.sc_last.peak_abs) : -1.0;
+    else if (k == "selfcheck_ms") *value = e.selfcheck_runs ? double(e.sc_last.elapsed_ms) : -1.0;
+    else if (k == "selfcheck_overflow") *value = e.selfcheck_runs ? double(e.sc_last.fp16_overflow) : -1.0;
     else return e.fail(RSR_E_ARG, "unknown stat " + k);
     return RSR_OK;
 }
@@ -482,6 +515,11 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     }
     else if (k == "precise")
         ctx->e.precise = value != 0; // plans are keyed by it (larger slots); the workspace grows on the next call
+    else if (k == "precise_auto")
+    { // the model decides: now when one is loaded, else at the end of the next load (rsr_load / rsr_load_packed)
+        ctx->e.precise_auto = value != 0;
+        if (ctx->e.precise_auto && ctx->e.loaded) return ctx->e.apply_precise_auto();
+    }
     else if (k == "flow_flags")
         ctx->e.flow_flags = int(value); // plans are keyed by bit 0 (it halves the largest tile the 32-bit plane offsets can address)
     else if (k == "max_lanes")

@@ -721,10 +721,13 @@ int Engine::launch(ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st)
 }
 
 int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fused_outs, int nimg, const int* fused_out_ws, int split_slot, hipEvent_t ev_half,
-                        hipEvent_t ev_mid, int mid_rdb, int nslots_used)
+                        hipEvent_t ev_mid, int mid_rdb, int nslots_used, const RangeProbe* probe)
 {
     const int nslots = (nslots_used > 0 && nslots_used < b.nslots) ? nslots_used : b.nslots;
     const long long cap = ws_cap_px;
+    // the probe reads whole planes: they must hold exactly the pixels of the one tile, all of them computed, in fp16 storage
+    if (probe && (b.nslots != 1 || b.dims.size() != 1 || cap != (long long)b.dims[0].h * b.dims[0].w || b.trim4 || precise || fused_outs))
+        return fail(RSR_E_STATE, "range probe on a plan that is not one untrimmed tile in fp16 storage");
     const int pc = plane_ch(), P32 = 32 / pc, P64 = 64 / pc;
     const long long ppx = pc * 2;
     const long long pb16 = cap * ppx + kGuard; // planes are guarded (see ensure_workspace)
@@ -774,6 +777,12 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fu
     };
     auto go = [&](ConvArgs& a) {
         if (rc == RSR_OK) rc = launch(a, ci, b, st);
+        if (rc == RSR_OK && probe)
+        { // what this convolution stored: its 2 * nt output planes of [H][W][16] halfs, or conv_last's planar [3][4h][4w] blob
+            const long long npx = ((long long)b.dims[0].h * b.dims[0].w) << (2 * a.lvl_out);
+            if (a.out_planar3) launch_range_probe(a.out_planar3, 0, 1, 3 * npx, probe->peak_bits + ci, probe->nonfinite + ci, st);
+            else launch_range_probe(a.out16.base, a.out16.plane_stride, 2 * int(convs[size_t(ci)].nt), npx * kPlaneCh, probe->peak_bits + ci, probe->nonfinite + ci, st);
+        }
         ci++;
     };
     const PlaneSrc fea = PS(b_fea, fea_pps, pb16, 0);
@@ -1782,6 +1791,158 @@ int Engine::net_forward(const uint16_t* in, int w, int h, uint16_t* out, float* 
     }
     cleanup();
     if (he != hipSuccess) return fail(RSR_E_DEVICE, std::string("net_forward: ") + hipGetErrorString(he));
+    return rc;
+}
+
+// ---- model self-check ---------------------------------------------------------------------------
+// The built-in tile: integer-only, so every build produces the same bytes.  The storage error depends on content, so the tile
+// has what a photograph has: a smooth field (value noise on an 8-pixel lattice, bilinear) under a ramp per channel, saturated
+// and black patches with hard edges, flat squares, and fine texture (per-pixel noise) on a checkerboard of 37-pixel cells -- the
+// other cells stay smooth.  Values are k / 255 as preproc_tiles produces them (float(k) * (1 / 255.f), rounded to fp16).
+static inline uint32_t sc_hash(uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t v = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
+    v ^= v >> 15; v *= 0x2C1B3C6Du; v ^= v >> 12; v *= 0x297A2D39u; v ^= v >> 15;
+    return v;
+}
+
+void selfcheck_tile(uint16_t* dst, int w, int h)
+{
+    uint16_t lut[256];
+    for (int k = 0; k < 256; k++)
+    {
+        const _Float16 v = (_Float16)(float(k) * (1 / 255.f));
+        std::memcpy(&lut[k], &v, 2);
+    }
+    for (int c = 0; c < 3; c++)
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++)
+            {
+                const int lx = x >> 3, ly = y >> 3, fx = x & 7, fy = y & 7;
+                const int n00 = int(sc_hash(lx, ly, c) & 255), n10 = int(sc_hash(lx + 1, ly, c) & 255), n01 = int(sc_hash(lx, ly + 1, c) & 255),
+                          n11 = int(sc_hash(lx + 1, ly + 1, c) & 255);
+                const int n = ((n00 * (8 - fx) + n10 * fx) * (8 - fy) + (n01 * (8 - fx) + n11 * fx) * fy + 32) >> 6;
+                const int g = (c & 1) ? (h > 1 ? y * 255 / (h - 1) : 0) : (w > 1 ? x * 255 / (w - 1) : 0);
+                int k = (166 * n + 89 * g + 127) / 255;
+                const int cx = x / 37, cy = y / 37;
+                if (((cx + cy) & 1) != 0) k += int(sc_hash(x, y, 16 + c) % 21) - 10;            // fine texture
+                else if (sc_hash(cx, cy, 32) % 3 == 0 && (x % 37) >= 8 && (x % 37) < 29 && (y % 37) >= 8 && (y % 37) < 29)
+                    k = int(sc_hash(cx, cy, 48 + c) & 255);                                       // a flat square
+                if ((x / 7 + y / 5 + c) % 11 == 0) k = 255;                                       // hard edges: saturated ...
+                if ((x / 5 + y / 9 + 2 * c) % 13 == 0) k = 0;                                     // ... and black patches
+                k = k < 0 ? 0 : (k > 255 ? 255 : k);
+                dst[(size_t(c) * h + y) * w + x] = lut[k];
+            }
+}
+
+// One tile through the network in fp16 storage (range probe behind every convolution) and in precise mode; the two results are compared
+// on the device.  `mu` held.  The context comes back in the mode it was in; the workspace is left marked "no layout", so the next call
+// lays its guards out afresh, exactly as after a net_forward of another tile size.  The plan cache is not touched.
+int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* out)
+{
+    if (!out) return fail(RSR_E_ARG, "null report");
+    if (!loaded) return fail(RSR_E_STATE, "selfcheck before load");
+    if (!tile && w == 0 && h == 0) w = h = 148; // C1's padded tile: the size of the storage measurements in profiles/
+    if (w < 1 || h < 1) return fail(RSR_E_ARG, "bad tile size");
+    const long long cap = (long long)w * h;
+    if (cap * 16 * 32 * ((flow_flags & 1) ? 4 : 2) + 4 * kGuard >= (1ll << 31)) return fail(RSR_E_ARG, "tile too large");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const size_t npx = size_t(cap), nout = npx * 16 * 3;
+    std::vector<uint16_t> own;
+    if (!tile)
+    {
+        own.resize(npx * 3);
+        selfcheck_tile(own.data(), w, h);
+        tile = own.data();
+    }
+    Plan::Batch b;
+    b.ntiles = 1;
+    b.nslots = 1;
+    b.dims.push_back(TileDim{h, w});
+    make_items(b, fold_cols);
+    // device side of the report: nonfinite[kNumConvs] | bytes_differ | peak_bits[kNumConvs] | storage_err bits, max_byte_diff
+    constexpr size_t kRep64 = kNumConvs + 1, kRep32 = kNumConvs + 2, kRepBytes = kRep64 * 8 + kRep32 * 4;
+    DevBuf tab, tmp, rep, out16;
+    const bool was_precise = precise, was_profiling = profiling;
+    auto finish = [&](int code) {
+        for (DevBuf* d : {&tab, &tmp, &rep, &out16})
+            if (d->p) (void)hipFree(d->p);
+        precise = was_precise;
+        profiling = was_profiling;
+        ws_cap_px = 0; // the workspace holds this walk's layout: the next call lays out its own
+        return code;
+    };
+    int rc;
+    if ((rc = ensure(tab, batch_table_bytes(b))) != RSR_OK || (rc = ensure(tmp, npx * 6)) != RSR_OK || (rc = ensure(rep, kRepBytes)) != RSR_OK ||
+        (rc = ensure(out16, nout * 2)) != RSR_OK)
+        return finish(rc);
+    char* d = static_cast<char*>(tab.p);
+    hipError_t he = upload_batch(b, d);
+    if (he == hipSuccess) he = hipMemcpy(tmp.p, tile, npx * 6, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemsetAsync(rep.p, 0, kRepBytes, stream);
+    if (he != hipSuccess) return finish(fail(RSR_E_DEVICE, std::string("selfcheck: ") + hipGetErrorString(he)));
+    unsigned long long* r64 = static_cast<unsigned long long*>(rep.p);
+    unsigned* r32 = reinterpret_cast<unsigned*>(r64 + kRep64);
+    RangeProbe probe;
+    probe.nonfinite = r64;
+    probe.peak_bits = r32;
+    profiling = false;
+    for (int pass = 0; pass < 2 && rc == RSR_OK; pass++)
+    {
+        precise = pass == 1;
+        if ((rc = ensure_workspace(1, cap, stream)) != RSR_OK) break; // (a change of layout zeroes b_in: the tile is written again)
+        launch_planar3_to_plane(static_cast<const uint16_t*>(tmp.p), w, h, static_cast<char*>(b_in.p) + kGuard, plane_ch(), stream);
+        rc = run_network(b, stream, nullptr, 1, nullptr, 0, nullptr, nullptr, -1, -1, pass == 0 ? &probe : nullptr);
+        if (rc != RSR_OK) break;
+        if (pass == 0) he = hipMemcpyAsync(out16.p, b_out3.p, nout * 2, hipMemcpyDeviceToDevice, stream);
+        else launch_output_compare(static_cast<const uint16_t*>(out16.p), static_cast<const float*>(b_out3.p), (long long)nout, r32 + kNumConvs, r64 + kNumConvs, stream);
+        if (he != hipSuccess) break;
+    }
+    if (rc != RSR_OK) return finish(rc);
+    std::vector<unsigned long long> h64(kRep64);
+    std::vector<unsigned> h32(kRep32);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpy(h64.data(), r64, kRep64 * 8, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(h32.data(), r32, kRep32 * 4, hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return finish(fail(RSR_E_DEVICE, std::string("selfcheck: ") + hipGetErrorString(he)));
+
+    rsr_selfcheck_report r;
+    std::memset(&r, 0, sizeof r);
+    r.tile_w = w;
+    r.tile_h = h;
+    std::memcpy(&r.storage_err, &h32[kNumConvs], 4);
+    r.headroom = r.storage_err > 0.f ? (1.f / 255.f) / r.storage_err : 3.402823466e+38f;
+    r.max_byte_diff = int(h32[kNumConvs + 1]);
+    r.bytes_differ = (long long)h64[kNumConvs];
+    r.peak_conv = 0;
+    for (int i = 0; i < kNumConvs; i++)
+    {
+        std::memcpy(&sc_peak[i], &h32[size_t(i)], 4);
+        sc_nonfinite[i] = (long long)h64[size_t(i)];
+        r.nonfinite += sc_nonfinite[i];
+        if (sc_peak[i] > r.peak_abs)
+        {
+            r.peak_abs = sc_peak[i];
+            r.peak_conv = i;
+        }
+    }
+    r.fp16_overflow = (r.nonfinite > 0 || r.peak_abs >= 65504.f) ? 1 : 0;
+    r.recommend_precise = r.headroom < 1.5f ? 1 : 0;
+    r.elapsed_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    sc_last = r;
+    selfcheck_runs++;
+    *out = r;
+    return finish(RSR_OK);
+}
+
+int Engine::apply_precise_auto()
+{
+    rsr_selfcheck_report r;
+    const int rc = selfcheck(nullptr, 0, 0, &r);
+    if (rc == RSR_OK) precise = r.recommend_precise != 0;
     return rc;
 }
 

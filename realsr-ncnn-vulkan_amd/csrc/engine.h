@@ -79,6 +79,13 @@ struct Plan
     void* d_tables = nullptr; // one allocation backing all device tables
 };
 
+// Device tables of the range probe (Engine::selfcheck): entry i receives what convolution i of x4.param stored.
+struct RangeProbe
+{
+    unsigned* peak_bits = nullptr;           // bits of the largest finite |value| as a float [kNumConvs]
+    unsigned long long* nonfinite = nullptr; // stored inf / NaN [kNumConvs]
+};
+
 // Helper threads for the staging copies of pageable images (pinned chunk <-> the caller's malloc'ed buffer): one core
 // moves ~10 GB/s, a 100 MB output would cost as much as a tenth of the network.  Started on first use.
 struct CopyPool
@@ -140,6 +147,14 @@ struct Engine
     // conv_last's fp32 result goes to the uint8 conversion unrounded.  Default off = the storage of the reference's Vulkan path
     // (fp16 everywhere, realsr.cpp:44-46); on = half the distance to its fp32 CPU path (realsr.cpp:525-838), the bar of the parity tests.
     bool precise = false;
+    // Model self-check (include/realsr_hip.h rsr_selfcheck): one tile through the network in both storages, compared on the device.
+    bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
+    long long selfcheck_runs = 0;
+    rsr_selfcheck_report sc_last{}; // of the last run
+    float sc_peak[kNumConvs] = {0};
+    long long sc_nonfinite[kNumConvs] = {0};
+    int selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* out); // mu held
+    int apply_precise_auto();                                                      // mu held, loaded: self-check on the built-in tile -> precise
     long long bytes_per_px() const; // workspace bytes per padded LR pixel of a slot
     int flow_flags = 0; // launch_conv_flow flags
     int num_cu = 256;
@@ -259,8 +274,10 @@ struct Engine
     // fused_outs: non-null = conv_last writes the uint8 images itself (one pointer per image of the batch)
     // ev_mid: recorded behind the middle RDB (a merged batch's throttle event)
     // mid_rdb >= 0: ev_mid is recorded behind that RDB.  nslots_used < b.nslots: only the first slots of the batch (a merged batch narrower than its plan)
+    // probe: non-null = every convolution is followed by a range-probe launch on what it stored (the self-check's one-tile batch in
+    // fp16 storage only; null everywhere else: the launch sequence is then exactly the one without it)
     int run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fused_outs = nullptr, int nimg = 1, const int* fused_out_ws = nullptr, int split_slot = 0,
-                    hipEvent_t ev_half = nullptr, hipEvent_t ev_mid = nullptr, int mid_rdb = -1, int nslots_used = -1);
+                    hipEvent_t ev_half = nullptr, hipEvent_t ev_mid = nullptr, int mid_rdb = -1, int nslots_used = -1, const RangeProbe* probe = nullptr);
     int launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int out_row0, const void* const* d_in, void* const* d_out, const int* ws,
                      const int* hs, int nimg, int c, int ntiles, hipStream_t st, int split_slot, hipEvent_t ev_half, hipEvent_t ev_mid);
     int enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid); // a merged batch of images of different sizes: tables built on the fly
@@ -285,6 +302,7 @@ struct Engine
     static int fail(int code, const std::string& msg);
 };
 
+void selfcheck_tile(uint16_t* dst, int w, int h); // host-only: the built-in tile of the self-check, planar fp16 [3][h][w]
 const char* last_error(); // message of the calling thread's last failure
 long long share_pool_stat(int what); // group.cpp: 0 = worker threads of rsr_process_group's pool, 1 = shares run inline because no worker could be started
 

@@ -190,4 +190,16 @@ void launch_planar3_to_plane(const uint16_t* planar, int w, int h, void* plane, 
 // zero the 64-byte guards of `count` planes, `stride` bytes apart
 void launch_zero_guards(void* first_guard, long long stride, long long count, hipStream_t st);
 
+// ---- model self-check (Engine::selfcheck): two reductions, results independent of scheduling ----
+// Range probe: what ONE convolution stored for ONE tile whose slot holds exactly the tile's pixels (capacity = h * w): `nplanes`
+// runs of `halfs_per_plane` fp16 values (a multiple of 8; 16-byte aligned), `plane_stride` bytes apart -- the [H][W][16] planes of
+// ConvArgs::out16 without their guards, or conv_last's planar blob as one run.  *peak_bits = max(*peak_bits, bits of the largest
+// finite |v| as a float) (atomicMax: the bit pattern of a non-negative float orders like the value), *nonfinite += inf / NaN count.
+void launch_range_probe(const void* base, long long plane_stride, int nplanes, long long halfs_per_plane, unsigned* peak_bits,
+                        unsigned long long* nonfinite, hipStream_t st);
+// Output compare: the network's result of fp16 storage (a) against precise mode's fp32 blob (b), n elements each (a multiple of 8).
+// res[0] = bits of max |a - b| (atomicMax as above), res[1] = max |q(a) - q(b)|, q = the uint8 conversion of postproc_tiles
+// (post_store(v * 255)); *ndiff = elements with q(a) != q(b).  The caller zeroes res[0..1] and *ndiff.
+void launch_output_compare(const uint16_t* a, const float* b, long long n, unsigned* res, unsigned long long* ndiff, hipStream_t st);
+
 } // namespace rsr

@@ -588,4 +588,101 @@ void launch_zero_guards(void* first_guard, long long stride, long long count, hi
     hipLaunchKernelGGL(zero_guards, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, st, static_cast<char*>(first_guard), stride, count);
 }
 
+// =============================================================================================
+// model self-check: range probe and output compare (Engine::selfcheck)
+// =============================================================================================
+constexpr int kCheckBlocks = 512; // grid-stride: at most this many workgroups of 256
+
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
+{
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned wave_sum_u32(unsigned v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+    return v;
+}
+
+// |fp16| as its 15-bit pattern orders like the value: the maximum is taken on the patterns, the one conversion to float at the end.
+__global__ __launch_bounds__(256) void range_probe(const char* base, long long plane_stride, int nplanes, long long vec_per_plane,
+                                                   unsigned* peak_bits, unsigned long long* nonfinite)
+{
+    unsigned peak = 0, bad = 0;
+    const long long total = vec_per_plane * nplanes, step = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += step)
+    {
+        const long long p = i / vec_per_plane, v = i - p * vec_per_plane;
+        const uint4 q = *reinterpret_cast<const uint4*>(base + p * plane_stride + v * 16);
+        const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const unsigned lo = w[k] & 0x7fffu, hi = (w[k] >> 16) & 0x7fffu;
+            if (lo >= 0x7c00u) bad++; else peak = max(peak, lo);
+            if (hi >= 0x7c00u) bad++; else peak = max(peak, hi);
+        }
+    }
+    peak = wave_max_u32(peak);
+    bad = wave_sum_u32(bad);
+    if ((threadIdx.x & 63) == 0)
+    {
+        const unsigned short hb = (unsigned short)peak;
+        _Float16 hv;
+        __builtin_memcpy(&hv, &hb, 2);
+        if (peak) atomicMax(peak_bits, __float_as_uint((float)hv));
+        if (bad) atomicAdd(nonfinite, (unsigned long long)bad);
+    }
+}
+
+void launch_range_probe(const void* base, long long plane_stride, int nplanes, long long halfs_per_plane, unsigned* peak_bits,
+                        unsigned long long* nonfinite, hipStream_t st)
+{
+    const long long vpp = halfs_per_plane / 8, total = vpp * nplanes;
+    if (total <= 0) return;
+    const unsigned grid = (unsigned)((total + 1023) / 1024 < kCheckBlocks ? (total + 1023) / 1024 : kCheckBlocks);
+    hipLaunchKernelGGL(range_probe, dim3(grid), dim3(256), 0, st, static_cast<const char*>(base), plane_stride, nplanes, vpp, peak_bits,
+                       nonfinite);
+}
+
+__global__ __launch_bounds__(256) void output_compare(const uint16_t* a, const float* b, long long nvec, unsigned* res, unsigned long long* ndiff)
+{
+    unsigned err = 0, qmax = 0, cnt = 0; // err: bits of a non-negative float
+    const long long step = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += step)
+    {
+        const half8 ha = *reinterpret_cast<const half8*>(a + i * 8);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(b + i * 8), b1 = *reinterpret_cast<const f32x4*>(b + i * 8 + 4);
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+        {
+            const float va = (float)ha[k], vb = k < 4 ? b0[k] : b1[k - 4];
+            const float d = fabsf(va - vb);
+            if (d == d) err = max(err, __float_as_uint(d)); // (+inf orders above every finite value; NaN is left out)
+            else err = max(err, 0x7f800000u);
+            const int qa = post_store(va * 255.f), qb = post_store(vb * 255.f);
+            const unsigned qd = (unsigned)(qa > qb ? qa - qb : qb - qa);
+            qmax = max(qmax, qd);
+            cnt += qd != 0;
+        }
+    }
+    err = wave_max_u32(err);
+    qmax = wave_max_u32(qmax);
+    cnt = wave_sum_u32(cnt);
+    if ((threadIdx.x & 63) == 0)
+    {
+        if (err) atomicMax(&res[0], err);
+        if (qmax) atomicMax(&res[1], qmax);
+        if (cnt) atomicAdd(ndiff, (unsigned long long)cnt);
+    }
+}
+
+void launch_output_compare(const uint16_t* a, const float* b, long long n, unsigned* res, unsigned long long* ndiff, hipStream_t st)
+{
+    const long long nvec = n / 8;
+    if (nvec <= 0) return;
+    const unsigned grid = (unsigned)((nvec + 1023) / 1024 < kCheckBlocks ? (nvec + 1023) / 1024 : kCheckBlocks);
+    hipLaunchKernelGGL(output_compare, dim3(grid), dim3(256), 0, st, a, b, nvec, res, ndiff);
+}
+
 } // namespace rsr

@@ -335,12 +335,52 @@ int main(int argc, char** argv)
         rsr_set_option(ctxs[size_t(i)], "max_lanes", std::max(16, std::min(64, jobs_proc[size_t(i)])));
         // no flag of the reference's surface is taken for it: RSR_PRECISE=1 keeps a byte of rounding residue per element of the residual
         // trunk (rsr_set_option "precise"; what tools/check_real_model.py recommends for weights with a wide output swing)
-        if (const char* pe = getenv("RSR_PRECISE"))
-            if (pe[0] && pe[0] != '0')
+        // RSR_PRECISE_AUTO=1: the loaded model decides (rsr_set_option "precise_auto": one built-in tile through both storages on the
+        // device, precise when fp16 storage leaves less than 1.5 x headroom to the +-1 bar).  RSR_PRECISE, when also set, wins.
+        const char* pa = getenv("RSR_PRECISE_AUTO");
+        const bool precise_auto = pa && pa[0] && pa[0] != '0';
+        const char* pe = getenv("RSR_PRECISE");
+        bool auto_ok = false;
+        if (precise_auto)
+        {
+            if (rsr_set_option(ctxs[size_t(i)], "precise_auto", 1) != RSR_OK)
+                fprintf(stderr, "gpu %d: model self-check failed: %s\n", gpuid[size_t(i)], rsr_last_error(ctxs[size_t(i)]));
+            else
+                auto_ok = true;
+            if (pe) rsr_set_option(ctxs[size_t(i)], "precise", (pe[0] && pe[0] != '0') ? 1 : 0);
+        }
+        else if (pe && pe[0] && pe[0] != '0')
+        {
+            rsr_set_option(ctxs[size_t(i)], "precise", 1);
+            if (verbose) fprintf(stderr, "gpu %d: precise residual trunk (RSR_PRECISE)\n", gpuid[size_t(i)]);
+        }
+        if (auto_ok)
+        {
+            double headroom = 0, peak = 0, overflow = 0, active = 0, ms = 0;
+            rsr_get_stat(ctxs[size_t(i)], "selfcheck_headroom", &headroom);
+            rsr_get_stat(ctxs[size_t(i)], "selfcheck_peak_abs", &peak);
+            rsr_get_stat(ctxs[size_t(i)], "selfcheck_overflow", &overflow);
+            rsr_get_stat(ctxs[size_t(i)], "selfcheck_ms", &ms);
+            rsr_get_stat(ctxs[size_t(i)], "precise_active", &active);
+            std::vector<float> pk(351, 0.f);
+            std::vector<long long> bad(351, 0);
+            rsr_selfcheck_ranges(ctxs[size_t(i)], pk.data(), bad.data(), 351);
+            int peak_conv = 0;
+            long long nonfinite = 0;
+            for (int k = 0; k < 351; k++)
             {
-                rsr_set_option(ctxs[size_t(i)], "precise", 1);
-                if (verbose) fprintf(stderr, "gpu %d: precise residual trunk (RSR_PRECISE)\n", gpuid[size_t(i)]);
+                nonfinite += bad[size_t(k)];
+                if (pk[size_t(k)] > pk[size_t(peak_conv)]) peak_conv = k;
             }
+            if (verbose)
+                fprintf(stderr, "gpu %d: self-check 148x148 tile: storage_err %.3e, headroom %.2f, peak |activation| %.4g at conv %d, %lld non-finite, %.1f ms -> %s%s%s\n",
+                        gpuid[size_t(i)], headroom > 0 ? (1.0 / 255.0) / headroom : 0.0, headroom, peak, peak_conv, nonfinite, ms,
+                        active != 0 ? "precise residual trunk" : "fp16 storage", pe ? " (RSR_PRECISE)" : "",
+                        overflow != 0 ? "; warning: activations overflow fp16, the output is not reliable" : "");
+            else if (overflow != 0)
+                fprintf(stderr, "gpu %d: warning: the model's activations overflow fp16 (peak %.4g, %lld non-finite values): the output is not reliable\n",
+                        gpuid[size_t(i)], peak, nonfinite);
+        }
         realsr.push_back(std::move(r));
     }
     // one image, several GPUs: every GPU takes a share of the tile rows

@@ -153,6 +153,13 @@ def gpu_checks(pp, bp, net, rep, bench):
     print("  network output before quantisation, fp16 storage (default), engine vs oracle on one 148x148 tile ([0,1] units): max %.3e  p99.9 %.3e  "
           "(tolerance 3.0e-3 / 1.5e-3); headroom of the +-1 uint8 bar = one step (3.92e-3) / max = %.2f" % (e.max(), np.quantile(e, 0.999), head16))
     ok16 = bool(np.isfinite(got).all() and e.max() <= 3.0e-3 and np.quantile(e, 0.999) <= 1.5e-3)
+    # The same question asked of the engine alone (rsr_selfcheck: fp16 storage against precise mode on the device, no oracle): what a
+    # user of the library sees.  Printed next to the oracle-measured figures; the decisions below stay with the oracle.
+    sc = sr.selfcheck(x)
+    rep["device_selfcheck"] = {k: (float(v) if isinstance(v, float) else int(v)) for k, v in sc.items()}
+    print("  device self-check on that tile (no oracle): storage_err %.3e (%.2f x the measured max), estimated headroom %.2f (measured %.2f); peak |activation| %.4g "
+          "at conv %d, %d non-finite; recommends %s; %.1f ms" % (sc["storage_err"], sc["storage_err"] / max(float(e.max()), 1e-12), sc["headroom"], head16, sc["peak_abs"],
+                                                               sc["peak_conv"], sc["nonfinite"], "precise" if sc["recommend_precise"] else "default", sc["elapsed_ms"]))
     # Is that error the engine's arithmetic or the fp16 STORAGE format (which the reference's Vulkan path shares, realsr.cpp:44-46)?
     # A PyTorch-CPU emulation of fp16 storage / fp32 arithmetic on the same tile must deviate from the fp32 oracle by the same amount.
     try:
