@@ -86,6 +86,30 @@ int rsr_process_many(rsr_ctx* ctx, int n, const uint8_t* const* in, const int* w
  * the work already on `stream` and in front of what the caller enqueues on it next. */
 int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void* d_out, void* stream);
 
+/* Pixel formats of device-resident images (no reference counterpart: the reference's images are uint8 HWC only). */
+#define RSR_FMT_U8_HWC 0  /* what rsr_process_device takes: uint8 [h][w][c], c in {3,4} */
+#define RSR_FMT_F16_CHW 1 /* planar fp16 [3][h][w], values in [0,1], tightly packed; c must be 3 */
+#define RSR_FMT_F32_CHW 2 /* planar fp32 [3][h][w], likewise */
+
+/* rsr_process_device with a pixel format per side: what a tensor pipeline holds (float CHW in [0,1]) goes in and comes out without a
+ * uint8 hop.  The two formats are independent; rsr_process_device(...) is exactly rsr_process_device_fmt(..., U8, ..., U8, ...).
+ * Same stream / ordering contract.  A planar format with c != 3 or an unknown format: RSR_E_ARG.  A call with a planar format on
+ * either side is never merged with concurrent calls (option "merge"); it is still safe next to them.
+ *   Input.   F16: the half IS the network input (the uint8 path feeds fp16(float(k) * (1/255.f)) for byte k: a caller who passes
+ *            exactly those halfs gets exactly the uint8 path's result).  F32: rounded to fp16, to nearest even.  Values are not
+ *            clamped.  The halo of a tile is filled by the same reflect-101 indexing as for uint8 images.
+ *   Output.  Let r be the fp32 value the uint8 conversion sees for a pixel in the context's current mode: the fp16-rounded conv_last
+ *            result (default), the fp32 mean of the eight fp16 values (TTA), conv_last's fp32 result or the fp32 mean of those
+ *            (option "precise").  F32 receives min(max(r, 0), 1); F16 that value rounded once to fp16 (lossless in the default
+ *            non-TTA mode).  Quantising it with floor(v * 255 + 0.5) reproduces the uint8 path's byte.
+ *   Option "bgr" swaps planes 0 and 2 the way it swaps bytes 0 and 2 of a uint8 pixel.
+ * Out of scope: RGBA in planar form, row pitches / strides, and a host-pointer variant (rsr_process stays uint8 HWC). */
+int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, int h, int c, void* d_out, int out_fmt, void* stream);
+
+/* Host-only: bytes of a w x h x c image in `fmt` (a negative RSR_E_ARG for a bad combination: unknown format, planar with c != 3,
+ * uint8 with c not in {3,4}, w or h < 1). */
+long long rsr_image_bytes(int fmt, int w, int h, int c);
+
 /* Pinned host memory for images.  rsr_process copies pinned buffers (these, hipHostMalloc'd or hipHostRegister'ed
  * memory) to / from the GPU directly; pageable memory goes through the call's pinned staging (the download in chunks,
  * the CPU copy of one chunk under the PCIe transfer of the next).  The reference gets the same from ncnn's Vulkan
@@ -336,7 +360,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *   "plan_items_lr" / "plan_items_2x" / "plan_items_4x"  work items (16 x 32 pixel blocks) of that plan per resolution level and image: what the
  *                       conv launches of a frame actually walk (blocks that only feed cropped pixels are left out, narrow last columns folded)
  *   "merged_batches" / "merged_images" / "merged_widest" / "merged_mixed"  tile batches that merged small images of concurrent calls, the
- *                       images they carried, the widest one, those whose images differed in size; "device_direct": rsr_process_device calls that ran on the caller's own stream
+ *                       images they carried, the widest one, those whose images differed in size; "device_direct": rsr_process_device[_fmt] calls that ran on the caller's own stream
  *   "workspace_mb"      device memory the workspace holds, "ws_clamp_mb" the bound a failed allocation left behind (-1 = none)
  *   "lanes", "lane_in_mb", "lane_out_mb"   rsr_process lanes created so far and the device image buffers they hold (a member of
  *                       rsr_process_group allocates only the output rows of its tile range)

@@ -28,11 +28,14 @@ EXPORTS = [
     "rsr_process_group", "rsr_device_memory", "rsr_process_tiles", "rsr_tile_partition", "rsr_rccl_probe", "rsr_get_stat",
     "rsr_net_forward_f32", "rsr_conv3x3_res_precise", "rsr_process_many",
     "rsr_selfcheck", "rsr_selfcheck_tile", "rsr_selfcheck_ranges",
+    "rsr_process_device_fmt", "rsr_image_bytes",
 ]
 
 NUM_CONVS = 351
 
 RSR_OK, RSR_E_ARG, RSR_E_IO, RSR_E_FORMAT, RSR_E_GRAPH, RSR_E_DEVICE, RSR_E_STATE, RSR_E_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
+# pixel formats of device-resident images (rsr_process_device_fmt): uint8 HWC, planar fp16 / fp32 [3][h][w] in [0, 1]
+RSR_FMT_U8_HWC, RSR_FMT_F16_CHW, RSR_FMT_F32_CHW = 0, 1, 2
 
 
 class Profile(C.Structure):
@@ -93,6 +96,9 @@ def lib():
     L.rsr_set_params.argtypes = [vp, ip, ip, ip]
     L.rsr_process.argtypes = [vp, vp, ip, ip, ip, vp]
     L.rsr_process_device.argtypes = [vp, vp, ip, ip, ip, vp, vp]
+    L.rsr_process_device_fmt.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, vp]
+    L.rsr_image_bytes.argtypes = [ip, ip, ip, ip]
+    L.rsr_image_bytes.restype = C.c_longlong
     L.rsr_model_pack.argtypes = [cp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_device_memory.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rsr_host_alloc.argtypes = [C.c_size_t]
@@ -207,6 +213,7 @@ class RealSR:
             if rc != 0:
                 raise RealSRError(rc, self._L.rsr_last_error(None).decode())
         self._h = h
+        self.gpuid = int(gpuid)
         self.scale, self.tilesize, self.prepadding = 4, 200, 10
         self.tta_mode = bool(tta_mode)
 
@@ -281,6 +288,13 @@ class RealSR:
         self._push_params()
         self._ck(self._L.rsr_process_device(self._h, C.c_void_p(int(d_in)), w, h, c, C.c_void_p(int(d_out)),
                                             C.c_void_p(int(stream)) if stream else None))
+
+    def process_device_fmt(self, d_in, in_fmt, w, h, c, d_out, out_fmt, stream=None):
+        """rsr_process_device_fmt: process_device with a pixel format (RSR_FMT_*) per side; the planar float formats need c == 3.
+        Buffer sizes: image_bytes(in_fmt, w, h, c) and image_bytes(out_fmt, 4 * w, 4 * h, c).  torch tensors: torch_io.upscale."""
+        self._push_params()
+        self._ck(self._L.rsr_process_device_fmt(self._h, C.c_void_p(int(d_in)), int(in_fmt), w, h, c, C.c_void_p(int(d_out)), int(out_fmt),
+                                                C.c_void_p(int(stream)) if stream else None))
 
     def process_rows(self, img, out, row0, row1):
         """Tile rows [row0, row1) of img's tile grid into the full-size `out` (see rsr_process_rows)."""
@@ -439,6 +453,14 @@ def selfcheck_tile(w=0, h=0):
     if rc != RSR_OK:
         raise RealSRError(rc, lib().rsr_last_error(None).decode())
     return t
+
+
+def image_bytes(fmt, w, h, c=3):
+    """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*)."""
+    n = lib().rsr_image_bytes(int(fmt), int(w), int(h), int(c))
+    if n < 0:
+        raise RealSRError(int(n), lib().rsr_last_error(None).decode())
+    return int(n)
 
 
 def device_memory(gpuid=0):

@@ -177,6 +177,22 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
     return ctx->e.process_device(d_in, w, h, c, d_out, static_cast<hipStream_t>(stream), stream == nullptr);
 }
 
+int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, int h, int c, void* d_out, int out_fmt, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    return ctx->e.process_device(d_in, w, h, c, d_out, static_cast<hipStream_t>(stream), stream == nullptr, in_fmt, out_fmt);
+}
+
+long long rsr_image_bytes(int fmt, int w, int h, int c)
+{
+    if (w < 1 || h < 1) return Engine::fail(RSR_E_ARG, "bad image size");
+    const long long px = (long long)w * h;
+    if (fmt == RSR_FMT_U8_HWC && (c == 3 || c == 4)) return px * c;
+    if (fmt == RSR_FMT_F16_CHW && c == 3) return px * 6;
+    if (fmt == RSR_FMT_F32_CHW && c == 3) return px * 12;
+    return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
+}
+
 int rsr_model_pack(const char* parampath, const char* modelpath, void* dst, size_t cap, size_t* need)
 {
     if (!parampath || !modelpath) return Engine::fail(RSR_E_ARG, "null path");

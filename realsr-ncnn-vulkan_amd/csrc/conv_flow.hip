@@ -156,6 +156,8 @@ __device__ __forceinline__ int pack_bf8_pair(float x, float y, int old, int hiwo
 //        (zeros, no memory access) and written into one: the epilogue is branch-free.
 //      6 / 7 = 3 / 0 in precise mode: conv_last's fp32 result goes to the uint8 conversion (or a planar fp32 blob) without the fp16
 //        rounding of the reference's `output` blob in between.
+//      8 / 9 / 10 / 11 = 3 / 6 / 0 / 7 writing the caller's PLANAR FLOAT image (ConvArgs::out_fmt: fp16 or fp32, chosen at run time) instead of
+//        the uint8 one -- instantiations of their own, so that the uint8 kernels keep their registers.
 // NTW: n-tiles (32 output channels) per MFMA wave; the workgroup has 4*NT/NTW MFMA waves + 4 loader waves.
 // DEFER: double-buffered accumulators, block r drained underneath block r+1 (NT == 1 only).
 // WRES: the conv's weight images stay RESIDENT in LDS for the whole launch (loaded once per workgroup; slot = plane index, the
@@ -173,9 +175,10 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
     constexpr int WB = C::WB;
     constexpr bool WDB = (NTW == 1); // double-buffered weight fragments (registers to spare with one n-tile per wave)
     static_assert(!DEFER || (NT == 1 && NTW == 1), "deferred epilogue needs the 256-VGPR budget of the 8-wave workgroup");
-    constexpr bool LAST3 = (EPI == 3 || EPI == 6); // conv_last with (dy, cout) in M
-    constexpr bool LASTG = (EPI == 0 || EPI == 7); // conv_last through the generic path
-    constexpr bool OUT32 = (EPI == 6 || EPI == 7); // ... in precise mode: its fp32 result is what is converted to uint8 / stored (planar fp32)
+    constexpr bool LAST3 = (EPI == 3 || EPI == 6 || EPI == 8 || EPI == 9);  // conv_last with (dy, cout) in M
+    constexpr bool LASTG = (EPI == 0 || EPI == 7 || EPI == 10 || EPI == 11); // conv_last through the generic path
+    constexpr bool OUT32 = (EPI == 6 || EPI == 7 || EPI == 9 || EPI == 11);  // ... in precise mode: its fp32 result is what is converted to uint8 / stored (planar fp32)
+    constexpr bool FIMG = EPI >= 8; // the fused image is planar fp16 / fp32 (ConvArgs::out_fmt), not uint8
     static_assert(!LAST3 || (NT == 1 && NTW == 1 && !UPS && !DEFER && WRES), "conv_last's (dy, cout) layout: 32 rows, resident aux image");
     static_assert((EPI != 4 && EPI != 5) || (NT == 2 && NTW == 1 && !UPS && !DEFER), "the precise residual epilogue exists for the 64-output-channel convs of the trunk");
     constexpr bool RESID = (EPI == 2 || EPI == 4 || EPI == 5); // residual forms
@@ -629,6 +632,32 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
             const int oim = pad2_img(it.pad2); // (a merged batch: the tile's own image and its row pitch)
             uint8_t* const oimg = a.out_u8s[oim];
             const int opitch = a.out_u8_ws[oim];
+            if constexpr (FIMG)
+            {
+                // planar fp16 / fp32 image [3][rows][opitch]: the value the uint8 conversion below sees, clamped to [0, 1] (fp16: rounded
+                // once -- a no-op unless OUT32).  Lanes run along x: a wave stores 32 contiguous elements per channel row.
+                const long long cstep = (long long)a.out_plane_rows[oim] * opitch;
+#pragma unroll
+                for (int rr = 0; rr < 4; rr++)
+                {
+                    const int y = yb + rr;
+                    const int rx = x - a.out_u8_crop, ry = y - a.out_u8_crop;
+                    if (rx >= 0 && rx < ow && ry >= 0 && ry < oh)
+                    {
+                        const long long pix = (long long)(it.pad1 + y) * opitch + ox;
+#pragma unroll
+                        for (int ch = 0; ch < 3; ch++)
+                        {
+                            float v = OUT32 ? val[rr][ch] : (float)(_Float16)val[rr][ch];
+                            v = fminf(fmaxf(v, 0.f), 1.f);
+                            const long long e = (a.out_u8_bgr ? 2 - ch : ch) * cstep + pix;
+                            if (a.out_fmt == kFmtF32) reinterpret_cast<float*>(oimg)[e] = v;
+                            else reinterpret_cast<_Float16*>(oimg)[e] = (_Float16)v;
+                        }
+                    }
+                }
+                return;
+            }
 #pragma unroll
             for (int rr = 0; rr < 4; rr++)
             {
@@ -1300,6 +1329,7 @@ static void flow_launch(const ConvArgs& a_in, int ncu, bool resident, int reserv
 // every instantiation the engine can reach, for the per-device opt-in to > 64 KiB of dynamic LDS
 #define RSR_FLOW_VARIANTS(F)                                                                                         \
     F(1, 1, false, 0, false) F(1, 1, false, 1, false) F(1, 1, false, 1, true) F(1, 1, false, 2, false) F(1, 1, false, 7, false) \
+    F(1, 1, false, 10, false) F(1, 1, false, 11, false)                                                              \
     F(1, 1, true, 1, false)                                                                                          \
     F(2, 1, false, 1, false) F(2, 1, false, 2, false) F(2, 1, true, 1, false) F(2, 1, false, 4, false) F(2, 1, false, 5, false) \
     F(2, 2, false, 1, false) F(2, 2, false, 2, false) F(2, 2, true, 1, false)
@@ -1310,6 +1340,10 @@ hipError_t flow_init_device()
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<1, 1, false, 6, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<1, 1, false, 8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<1, 1, false, 9, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
 #define RSR_F(NT, NTW, UPS, EPI, DEFER)                                                                              \
     if (e == hipSuccess) e = flow_attr<NT, NTW, UPS, EPI, DEFER>();
     RSR_FLOW_VARIANTS(RSR_F)
@@ -1366,9 +1400,14 @@ bool launch_conv_flow(const ConvArgs& a_in, int nt, int ncu, int flags, hipStrea
             int grid = ncu & ~7;
             const int per = (a.nitems + 7) / 8;
             if (per * 8 < grid) grid = per * 8;
-            if (a.precise) hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 6, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
+            const bool fimg = a.out_u8 && a.out_fmt != kFmtU8; // the fused image is planar fp16 / fp32
+            if (fimg && a.precise) hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 9, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
+            else if (fimg) hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 8, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
+            else if (a.precise) hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 6, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
             else hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 3, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
         }
+        else if (epi == 0 && !ups && a.out_u8 && a.out_fmt != kFmtU8 && a.precise) flow_launch<1, 1, false, 11, false>(a, ncu, res, reserve, st);
+        else if (epi == 0 && !ups && a.out_u8 && a.out_fmt != kFmtU8) flow_launch<1, 1, false, 10, false>(a, ncu, res, reserve, st);
         else if (epi == 0 && !ups && a.precise) flow_launch<1, 1, false, 7, false>(a, ncu, res, reserve, st);
         else if (epi == 0 && !ups) flow_launch<1, 1, false, 0, false>(a, ncu, res, reserve, st);
         else if (epi == 1 && !ups && defer) flow_launch<1, 1, false, 1, true>(a, ncu, res, reserve, st);

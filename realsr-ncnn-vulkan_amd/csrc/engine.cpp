@@ -721,7 +721,7 @@ int Engine::launch(ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st)
 }
 
 int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fused_outs, int nimg, const int* fused_out_ws, int split_slot, hipEvent_t ev_half,
-                        hipEvent_t ev_mid, int mid_rdb, int nslots_used, const RangeProbe* probe)
+                        hipEvent_t ev_mid, int mid_rdb, int nslots_used, const RangeProbe* probe, int out_fmt, const int* fused_out_hs)
 {
     const int nslots = (nslots_used > 0 && nslots_used < b.nslots) ? nslots_used : b.nslots;
     const long long cap = ws_cap_px;
@@ -891,7 +891,9 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fu
                 {
                     a.out_u8s[i] = fused_outs[i];
                     a.out_u8_ws[i] = fused_out_ws[i];
+                    a.out_plane_rows[i] = fused_out_hs ? fused_out_hs[i] : 0;
                 }
+                a.out_fmt = out_fmt;
                 a.out_u8_w = fused_out_ws[0];
                 a.out_u8_crop = prepadding * scale;
                 a.out_u8_bgr = bgr ? 1 : 0;
@@ -914,13 +916,13 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fu
 // ---- process ----------------------------------------------------------------------------------
 // enqueue preproc -> network -> postproc for every tile batch of one image on `st` (mu held)
 int Engine::enqueue_image(const void* d_in, int w, int h, int c, void* d_out, hipStream_t st, int tile0, int tile1, hipEvent_t ev_half,
-                          size_t* half_rows)
+                          size_t* half_rows, int in_fmt, int out_fmt)
 {
-    return enqueue_images(&d_in, &d_out, 1, w, h, c, st, tile0, tile1, ev_half, half_rows);
+    return enqueue_images(&d_in, &d_out, 1, w, h, c, st, tile0, tile1, ev_half, half_rows, nullptr, 0, in_fmt, out_fmt);
 }
 
 int Engine::enqueue_images(const void* const* d_in, void* const* d_out, int nimg, int w, int h, int c, hipStream_t st, int tile0, int tile1,
-                           hipEvent_t ev_half, size_t* half_rows, hipEvent_t ev_mid, int plan_nimg)
+                           hipEvent_t ev_half, size_t* half_rows, hipEvent_t ev_mid, int plan_nimg, int in_fmt, int out_fmt)
 {
     const bool merged = plan_nimg > 0; // (every caller of a merged batch reports the progress of its own image: process_host)
     if (plan_nimg < nimg) plan_nimg = nimg;
@@ -1011,7 +1013,7 @@ int Engine::enqueue_images(const void* const* d_in, void* const* d_out, int nimg
         }
         const bool last_batch = b.tile0 + b.ntiles >= tiles_wanted;
         rc = launch_batch(b, plan.cap_px, plan.max_tw, plan.max_th, plan.out_row0, d_in, d_out, ws, hs, nimg, c, ntiles, st, split_slot, ev_half,
-                          last_batch ? ev_mid : nullptr);
+                          last_batch ? ev_mid : nullptr, in_fmt, out_fmt);
         if (rc != RSR_OK) return rc;
         if (progress && !merged) // one call per TILE, like the reference's line per tile (realsr.cpp:481), issued when the tile's batch is enqueued
             for (int i = 1; i <= b.ntiles; i++) progress(done + i, total, progress_user); // (a merged batch: every caller reports its own image)
@@ -1030,7 +1032,8 @@ int Engine::enqueue_images(const void* const* d_in, void* const* d_out, int nimg
 // preproc -> network -> postproc of the first `ntiles` tiles of one tile batch on `st` (mu held; the workspace is laid out for cap_px).
 // The images of the batch may differ in size (ws / hs): every tile carries the index of its image.
 int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int out_row0, const void* const* d_in, void* const* d_out,
-                         const int* ws, const int* hs, int nimg, int c, int ntiles, hipStream_t st, int split_slot, hipEvent_t ev_half, hipEvent_t ev_mid)
+                         const int* ws, const int* hs, int nimg, int c, int ntiles, hipStream_t st, int split_slot, hipEvent_t ev_half, hipEvent_t ev_mid,
+                         int in_fmt, int out_fmt)
 {
     constexpr int pc = plane_ch();
     const int per = tta ? 8 : 1, nslots_used = ntiles * per;
@@ -1043,6 +1046,7 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
         pa.hs[i] = hs[i];
     }
     pa.nimgs = nimg;
+    pa.fmt = in_fmt;
     pa.c = c;
     pa.tiles = b.d_tiles;
     pa.ntiles = ntiles;
@@ -1053,20 +1057,23 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     pa.plane_ch = pc;
     pa.variant = (dbg & 32768) ? 1 : ((dbg & 65536) ? 2 : 0);
     launch_preproc_tiles(pa, max_tw, max_th, st);
-    mark(0, 0, b.px[0] / per * c + b.px[0] * 64, st);
+    // bytes of a pixel in the caller's image: c for uint8 HWC, 3 halfs / floats for the planar formats
+    auto px_bytes = [c](int fmt) { return fmt == RSR_FMT_F16_CHW ? 6.0 : (fmt == RSR_FMT_F32_CHW ? 12.0 : double(c)); };
+    mark(0, 0, b.px[0] / per * px_bytes(in_fmt) + b.px[0] * 64, st);
     // conv_last writes the uint8 image directly when no TTA merge / alpha channel needs the fp16 blob (dbg 8192: off)
     const bool fused = !tta && c == 3 && !(dbg & 8192);
     uint8_t* outs[kMaxMerge];
-    int out_ws[kMaxMerge];
+    int out_ws[kMaxMerge], out_hs[kMaxMerge];
     for (int i = 0; i < nimg; i++)
     {
         outs[i] = static_cast<uint8_t*>(d_out[i]);
         out_ws[i] = ws[i] * scale;
+        out_hs[i] = hs[i] * scale; // (the planar formats come with whole images only: process_device)
     }
     // the throttle event of a merged batch (Engine::submit_merged): behind the RDB that leaves about half an image's worth of network
     // ahead -- the time the next batch's launches take to enqueue
     int rc = run_network(b, st, fused ? outs : nullptr, nimg, out_ws, split_slot, ev_half, ev_mid, kNumRDB - 1 - std::max(2, kNumRDB / (2 * std::max(1, nimg))),
-                         nslots_used);
+                         nslots_used, nullptr, out_fmt, out_hs);
     if (rc != RSR_OK || fused) return rc;
     PostArgs po;
     std::memset(&po, 0, sizeof po);
@@ -1081,17 +1088,19 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     {
         po.outs[i] = outs[i];
         po.out_ws[i] = out_ws[i];
+        po.out_hs[i] = out_hs[i];
         po.in_imgs[i] = static_cast<const uint8_t*>(d_in[i]);
         po.in_ws[i] = ws[i];
     }
     po.nimgs = nimg;
+    po.out_fmt = out_fmt;
     po.c = c;
     po.out_row0 = out_row0;
     po.tilesize = tilesize;
     po.bgr = bgr ? 1 : 0;
     po.variant = (dbg & 32768) ? 1 : ((dbg & 65536) ? 2 : 0);
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
-    mark(2, 0, b.px[2] / per * (6.0 * per + c), st);
+    mark(2, 0, b.px[2] / per * (6.0 * per + px_bytes(out_fmt)), st);
     return RSR_OK;
 }
 
@@ -1155,11 +1164,17 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
     return RSR_OK;
 }
 
-int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync)
+int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync, int in_fmt, int out_fmt)
 {
     if (!d_in || !d_out || w < 1 || h < 1 || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
+    for (const int f : {in_fmt, out_fmt})
+    {
+        if (f != RSR_FMT_U8_HWC && f != RSR_FMT_F16_CHW && f != RSR_FMT_F32_CHW) return fail(RSR_E_ARG, "unknown pixel format");
+        if (f != RSR_FMT_U8_HWC && c != 3) return fail(RSR_E_ARG, "the planar float formats are RGB only (c == 3)");
+    }
+    const bool u8 = in_fmt == RSR_FMT_U8_HWC && out_fmt == RSR_FMT_U8_HWC;
     hipEvent_t done = nullptr;
-    if (!user_stream && sync)
+    if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
     { // a small image: merged with whatever other calls hand in meanwhile (Engine::submit_merged)
         int T = 0, width = 1;
         long long items = 0;
@@ -1199,7 +1214,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             // put on ITS caller's stream included: the compute stream was made to wait for it, below) -- so this call's kernels go
             // straight onto the caller's stream: no event hop into the compute stream and back.  Whatever is enqueued on the compute
             // stream later uses the same workspace and must come behind: it waits for this call's last kernel.
-            const int rc = enqueue_image(d_in, w, h, c, d_out, user_stream);
+            const int rc = enqueue_image(d_in, w, h, c, d_out, user_stream, 0, -1, nullptr, nullptr, in_fmt, out_fmt);
             hipEvent_t e = take_event();
             if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
             { // cannot order the compute stream behind it: fall back to waiting here
@@ -1220,7 +1235,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             HIP_TRY(hipStreamWaitEvent(stream, e, 0));
             give_event(e);
         }
-        const int rc = enqueue_image(d_in, w, h, c, d_out, stream);
+        const int rc = enqueue_image(d_in, w, h, c, d_out, stream, 0, -1, nullptr, nullptr, in_fmt, out_fmt);
         if (rc != RSR_OK) return rc;
         if (user_stream || sync)
         {

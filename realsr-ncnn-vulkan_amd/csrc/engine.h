@@ -251,7 +251,9 @@ struct Engine
     int load_blob_device(const void* blob, size_t bytes);
     // d_in/d_out on this device.  user_stream == nullptr: returns when the output is complete (sync) or enqueued (!sync);
     // otherwise ordered after / before the work of user_stream, asynchronous.
-    int process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync);
+    // in_fmt / out_fmt: RSR_FMT_* of the two images (the planar float formats need c == 3; such a call is never merged with others)
+    int process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync, int in_fmt = RSR_FMT_U8_HWC,
+                       int out_fmt = RSR_FMT_U8_HWC);
     // tile0/tile1: tiles [tile0, tile1) of the row-major tile grid only (tile1 < 0: all); `out` is always the full (4w x 4h x c) image,
     // only the output rectangles of
     // those tiles are written
@@ -271,24 +273,28 @@ struct Engine
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
-    // fused_outs: non-null = conv_last writes the uint8 images itself (one pointer per image of the batch)
+    // fused_outs: non-null = conv_last writes the images itself (one pointer per image of the batch): uint8 HWC, or -- out_fmt -- planar
+    // fp16 / fp32 of fused_out_hs[i] rows
     // ev_mid: recorded behind the middle RDB (a merged batch's throttle event)
     // mid_rdb >= 0: ev_mid is recorded behind that RDB.  nslots_used < b.nslots: only the first slots of the batch (a merged batch narrower than its plan)
     // probe: non-null = every convolution is followed by a range-probe launch on what it stored (the self-check's one-tile batch in
     // fp16 storage only; null everywhere else: the launch sequence is then exactly the one without it)
     int run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fused_outs = nullptr, int nimg = 1, const int* fused_out_ws = nullptr, int split_slot = 0,
-                    hipEvent_t ev_half = nullptr, hipEvent_t ev_mid = nullptr, int mid_rdb = -1, int nslots_used = -1, const RangeProbe* probe = nullptr);
+                    hipEvent_t ev_half = nullptr, hipEvent_t ev_mid = nullptr, int mid_rdb = -1, int nslots_used = -1, const RangeProbe* probe = nullptr,
+                    int out_fmt = RSR_FMT_U8_HWC, const int* fused_out_hs = nullptr);
     int launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int out_row0, const void* const* d_in, void* const* d_out, const int* ws,
-                     const int* hs, int nimg, int c, int ntiles, hipStream_t st, int split_slot, hipEvent_t ev_half, hipEvent_t ev_mid);
+                     const int* hs, int nimg, int c, int ntiles, hipStream_t st, int split_slot, hipEvent_t ev_half, hipEvent_t ev_mid,
+                     int in_fmt = RSR_FMT_U8_HWC, int out_fmt = RSR_FMT_U8_HWC);
     int enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid); // a merged batch of images of different sizes: tables built on the fly
     int launch(ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st);
     int enqueue_image(const void* d_in, int w, int h, int c, void* d_out, hipStream_t st, int tile0 = 0, int tile1 = -1,
-                      hipEvent_t ev_half = nullptr, size_t* half_rows = nullptr);
+                      hipEvent_t ev_half = nullptr, size_t* half_rows = nullptr, int in_fmt = RSR_FMT_U8_HWC, int out_fmt = RSR_FMT_U8_HWC);
     // nimg images of one geometry as ONE tile batch (nimg <= kMaxMerge; whole images only when nimg > 1)
     // plan_nimg >= nimg: the plan is the one of plan_nimg images and only the first nimg of them are launched (every width of a merged
     // batch shares ONE plan: slots, tiles and work items of an image are contiguous, so a narrower batch is a prefix of the tables)
     int enqueue_images(const void* const* d_in, void* const* d_out, int nimg, int w, int h, int c, hipStream_t st, int tile0 = 0, int tile1 = -1,
-                       hipEvent_t ev_half = nullptr, size_t* half_rows = nullptr, hipEvent_t ev_mid = nullptr, int plan_nimg = 0);
+                       hipEvent_t ev_half = nullptr, size_t* half_rows = nullptr, hipEvent_t ev_mid = nullptr, int plan_nimg = 0,
+                       int in_fmt = RSR_FMT_U8_HWC, int out_fmt = RSR_FMT_U8_HWC);
     void mark_begin(hipStream_t st);
     void mark(int cls, double flops, double bytes, hipStream_t st, int conv_index = -1);
     void collect_profile(hipStream_t st);

@@ -33,6 +33,10 @@ constexpr int kFoldMaxW = 14; // strip = left halo + <= 14 pixels + right halo =
 // them.  Every image keeps its own device buffers: the kernels that touch images get the pointers by value and the tile's image index.
 constexpr int kMaxMerge = 16;
 
+// Pixel formats of the caller's images (the RSR_FMT_* values of include/realsr_hip.h).  The planar formats are RGB only, tightly packed
+// [3][h][w], values in [0, 1]; they ride in the same pointer arrays as the uint8 images (PreArgs::imgs, PostArgs::outs, ConvArgs::out_u8s).
+constexpr int kFmtU8 = 0, kFmtF16 = 1, kFmtF32 = 2;
+
 struct WorkItem // 32 bytes: one aligned 2 x 16-byte fetch gives a workgroup everything about its block
 {
     int slot, y0, x0; // tile slot and block origin at this table's resolution level (x0 | kFoldBit: a folded block)
@@ -117,6 +121,10 @@ struct ConvArgs
     // differ in size); out_u8 == out_u8s[0] doubles as the mode flag
     uint8_t* out_u8s[kMaxMerge];
     int out_u8_ws[kMaxMerge];
+    // ... or, out_fmt != kFmtU8, planar fp16 / fp32 [3][out_plane_rows][out_u8_ws[i]] images behind the same pointers: min(max(r, 0), 1) of the
+    // value r the uint8 conversion sees (fp16: that rounded once), plane = 2 - ch under out_u8_bgr
+    int out_fmt;
+    int out_plane_rows[kMaxMerge];
 };
 
 // conv_flow.hip: half-stage ring on 16-channel planes.  flags: 1 = two n-tiles per MFMA wave for 64-cout convs, 2 = no deferred epilogue,
@@ -141,6 +149,7 @@ struct BaseTile
 struct PreArgs
 {
     const uint8_t* imgs[kMaxMerge]; // HWC u8, one per image of the batch (ws[i] x hs[i] x c); BaseTile::img selects
+    int fmt;                        // kFmtU8, or kFmtF16 / kFmtF32: the images are planar [3][hs[i]][ws[i]] of that type (c == 3)
     int ws[kMaxMerge], hs[kMaxMerge];
     int nimgs;
     int c;
@@ -151,7 +160,7 @@ struct PreArgs
     long long slot_stride;
     int bgr;
     int plane_ch;   // 16
-    int variant;    // 0 default (launch_preproc_tiles picks), 1 one thread per pixel (engine dbg 32768), 2 LDS-staged (dbg 65536)
+    int variant;    // 0 default (launch_preproc_tiles picks), 1 one thread per pixel (engine dbg 32768), 2 LDS-staged (dbg 65536; uint8 sources only)
 };
 void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t st);
 
@@ -165,6 +174,8 @@ struct PostArgs
     int tta;
     int crop;   // prepadding*scale
     uint8_t* outs[kMaxMerge]; // HWC u8 (4w x 4h x c), one per image of the batch
+    int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][out_hs[i]][out_ws[i]] of that type (c == 3; see ConvArgs::out_fmt)
+    int out_hs[kMaxMerge];    // rows of the buffers behind `outs` (planar formats: the plane stride is out_hs[i] * out_ws[i] elements)
     int out_ws[kMaxMerge];    // their row pitches in pixels (4w)
     int in_ws[kMaxMerge];     // ... and those of the source images (w)
     int nimgs;

@@ -1,7 +1,7 @@
 // kernels.hip -- gfx950 (CDNA4 / MI355X) pre/post kernels of the RealSR x4 hot path.
 //
-//   preproc_tiles[_lds]    realsr_preproc{,_tta}.comp equivalent, writes the network input planes
-//   postproc_tiles[_lds]   realsr_postproc{,_tta}.comp equivalent, writes the uint8 HWC image
+//   preproc_tiles[_lds]    realsr_preproc{,_tta}.comp equivalent, writes the network input planes (from uint8 HWC or planar fp16 / fp32 images)
+//   postproc_tiles[_lds]   realsr_postproc{,_tta}.comp equivalent, writes the uint8 HWC image (or a planar fp16 / fp32 one)
 //                          (_lds: rows staged in LDS, dword loads / 1-KiB stores, transposed TTA variants through an LDS tile;
 //                          chosen per launch by measurement: launch_*_tiles)
 //   *_shader               the same arithmetic in the shaders' own memory layout (parity tests)
@@ -37,6 +37,10 @@ __device__ __forceinline__ int reflect101(int v, int n)
 // One thread per padded-tile pixel; writes the 32-channel fp16 input plane(s) (channels 3..31 = 0).
 // The band-relative coordinates of the shader (crop_x/crop_y/pad) are folded into x_org/y_org:
 // reflecting against the band equals reflecting against the image (engine.cpp explains why).
+// SRC: what the caller's image is made of -- uint8_t (HWC), or _Float16 / float: planar [3][ih][iw] in [0, 1].  A half IS the network
+// input (the uint8 path makes fp16(float(k) * (1/255.f)) of byte k: those halfs give that path's input exactly); a float is rounded to
+// fp16, to nearest even.  Lanes run along x: the three plane reads of a wave are contiguous.
+template <typename SRC>
 __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -46,15 +50,26 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     const int im = __builtin_amdgcn_readfirstlane(t.img), iw = a.ws[im], ih = a.hs[im];
     const int x = reflect101(gx + t.x_org, iw);
     const int y = reflect101(gy + t.y_org, ih);
-    const uint8_t* p = a.imgs[im] + ((long long)y * iw + x) * a.c;
-    const float norm_val = 1 / 255.f;
     const int i0 = a.bgr ? 2 : 0, i2 = a.bgr ? 0 : 2;
     half8 v0;
 #pragma unroll
     for (int e = 0; e < 8; e++) v0[e] = (_Float16)0.f;
-    v0[0] = (_Float16)((float)p[i0] * norm_val);
-    v0[1] = (_Float16)((float)p[1] * norm_val);
-    v0[2] = (_Float16)((float)p[i2] * norm_val);
+    if constexpr (sizeof(SRC) == 1)
+    {
+        const uint8_t* p = a.imgs[im] + ((long long)y * iw + x) * a.c;
+        const float norm_val = 1 / 255.f;
+        v0[0] = (_Float16)((float)p[i0] * norm_val);
+        v0[1] = (_Float16)((float)p[1] * norm_val);
+        v0[2] = (_Float16)((float)p[i2] * norm_val);
+    }
+    else
+    {
+        const long long cstep = (long long)iw * ih;
+        const SRC* p = reinterpret_cast<const SRC*>(a.imgs[im]) + (long long)y * iw + x;
+        v0[0] = (_Float16)p[i0 * cstep];
+        v0[1] = (_Float16)p[cstep];
+        v0[2] = (_Float16)p[i2 * cstep];
+    }
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
     const int nv = a.tta ? 8 : 1;
     for (int k = 0; k < nv; k++)
@@ -191,10 +206,12 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
     // sectors: staging buys nothing here.  Default = the plain kernel; variant 2 forces the staged one (tests, A/B).
     bool aligned = true; // (the staged kernel reads the images in dwords)
     for (int i = 0; i < a.nimgs; i++) aligned = aligned && !(reinterpret_cast<uintptr_t>(a.imgs[i]) & 3);
-    if (a.variant != 2 || a.plane_ch != 16 || !aligned)
+    if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8) // (the staged kernel knows uint8 sources only)
     {
         const dim3 grid((max_tw + 31) / 32, (max_th + 7) / 8, a.ntiles), block(256);
-        hipLaunchKernelGGL(preproc_tiles, grid, block, 0, st, a);
+        if (a.fmt == kFmtF16) hipLaunchKernelGGL(preproc_tiles<_Float16>, grid, block, 0, st, a);
+        else if (a.fmt == kFmtF32) hipLaunchKernelGGL(preproc_tiles<float>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(preproc_tiles<uint8_t>, grid, block, 0, st, a);
         return;
     }
     const dim3 grid((max_tw + 31) / 32, (max_th + 31) / 32, a.ntiles), block(256);
@@ -208,6 +225,16 @@ __device__ __forceinline__ uint8_t post_store(float v)
     v = floorf(v + 0.5f);
     v = fminf(fmaxf(v, 0.f), 255.f);
     return (uint8_t)v;
+}
+
+// The planar float destinations (PostArgs::out_fmt): the value the uint8 conversion sees, clamped to [0, 1] -- so that
+// floor(v * 255 + 0.5) of it is post_store's byte -- as fp32, or rounded once to fp16.  o = element (y, x) of plane 0.
+template <typename TO>
+__device__ __forceinline__ void post_store_planar(TO* o, long long cstep, int bgr, const float (&v)[3])
+{
+    o[bgr ? 2 * cstep : 0] = (TO)fminf(fmaxf(v[0], 0.f), 1.f);
+    o[cstep] = (TO)fminf(fmaxf(v[1], 0.f), 1.f);
+    o[bgr ? 0 : 2 * cstep] = (TO)fminf(fmaxf(v[2], 0.f), 1.f);
 }
 
 // ncnn Interp bicubic coefficients (alpha channel only; realsr.cpp:128-140)
@@ -233,7 +260,9 @@ __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v > n 
 
 // realsr_postproc.comp:47-89 and realsr_postproc_tta.comp:54-110 for a batch of tiles.
 // One thread per output pixel of the tile's un-padded x4 rectangle.
-template <typename TP> // element type of the planar blob: _Float16 (the reference's `output` blob) or float (precise mode)
+// TP: element type of the planar blob: _Float16 (the reference's `output` blob) or float (precise mode)
+// TO: element type of the image: uint8_t (HWC), or _Float16 / float (planar [3][out_hs][out_ws], RGB only: post_store_planar)
+template <typename TP, typename TO>
 __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -244,7 +273,6 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
     const int w = t.tw * 4, h = t.th * 4;
     const long long cstep = (long long)w * h;
     const int sx = gx + a.crop, sy = gy + a.crop;
-    uint8_t* o = a.outs[im] + ((long long)(t.out_y - a.out_row0 + gy) * a.out_ws[im] + t.out_x + gx) * a.c;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     float v[3];
     if (!a.tta)
@@ -271,6 +299,13 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
             v[q] = (v0 + v1 + v2 + v3 + v4 + v5 + v6 + v7) * 0.125f;
         }
     }
+    if constexpr (sizeof(TO) != 1)
+    {
+        const long long pix = (long long)(t.out_y - a.out_row0 + gy) * a.out_ws[im] + t.out_x + gx;
+        post_store_planar(reinterpret_cast<TO*>(a.outs[im]) + pix, (long long)a.out_hs[im] * a.out_ws[im], a.bgr, v);
+        return;
+    }
+    uint8_t* o = a.outs[im] + ((long long)(t.out_y - a.out_row0 + gy) * a.out_ws[im] + t.out_x + gx) * a.c;
     const uint8_t r = post_store(v[0] * 255.f), g = post_store(v[1] * 255.f), bl = post_store(v[2] * 255.f);
     o[a.bgr ? 2 : 0] = r;
     o[1] = g;
@@ -306,7 +341,9 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
 // channel) block is read along ITS rows into an LDS tile and picked up transposed (34-half pitch: conflict-free).  The merge keeps
 // the shader's summation order (v0 + v1 + ... + v7) * 0.125.  The uint8 pixels are collected in LDS and leave as aligned dwords
 // (a 32-pixel row segment of the HWC image = 96 or 128 contiguous bytes).
-template <typename TP>
+// TO != uint8_t (planar float image): lanes run along x, so the values leave straight from the registers, 32 contiguous elements per
+// channel row, and the uint8 staging at the end is not needed.
+template <typename TP, typename TO>
 __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
 {
     __shared__ TP T[32][sizeof(TP) == 2 ? 34 : 33]; // pitch: conflict-free column reads for 2- and 4-byte elements
@@ -385,6 +422,12 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
         float v[3];
 #pragma unroll
         for (int q = 0; q < 3; q++) v[q] = a.tta ? acc[m][q] * 0.125f : acc[m][q];
+        if constexpr (sizeof(TO) != 1)
+        {
+            const long long pix = (long long)(t.out_y - a.out_row0 + gy0 + gyl) * a.out_ws[im] + t.out_x + gx0 + lx;
+            post_store_planar(reinterpret_cast<TO*>(a.outs[im]) + pix, (long long)a.out_hs[im] * a.out_ws[im], a.bgr, v);
+            continue;
+        }
         unsigned char* o = &ob[gyl][lx * a.c];
         o[a.bgr ? 2 : 0] = post_store(v[0] * 255.f);
         o[1] = post_store(v[1] * 255.f);
@@ -410,6 +453,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
             o[3] = post_store(rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3]);
         }
     }
+    if constexpr (sizeof(TO) != 1) return;
     __syncthreads();
     const int nd = nx * a.c / 4; // out_w, gx0 are multiples of 4: a row segment is whole dwords, 4-byte aligned in the image
     for (int i = tid; i < ny * nd; i += 256)
@@ -426,18 +470,26 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
     // Measured (profiles/r04_prepost.txt): the TTA gather 0.92 ms staged vs 2.42 ms per-pixel on the C5 frame (2.26 vs 0.86 TB/s: the
     // transposed variants), but 0.19 vs 0.12 ms for the plain single-variant conversion.  Default: staged under TTA, plain otherwise.
     const bool staged = a.variant == 2 || (a.variant == 0 && a.tta);
-    bool aligned = true; // (the staged kernel stores the image in dwords)
-    for (int i = 0; i < a.nimgs; i++) aligned = aligned && !(reinterpret_cast<uintptr_t>(a.outs[i]) & 3);
+    bool aligned = true; // (the staged kernel stores the uint8 image in dwords)
+    for (int i = 0; i < a.nimgs; i++) aligned = aligned && (a.out_fmt != kFmtU8 || !(reinterpret_cast<uintptr_t>(a.outs[i]) & 3));
+#define RSR_POST(K, TO)                                                                                              \
+    {                                                                                                                \
+        if (a.f32) hipLaunchKernelGGL((K<float, TO>), grid, block, 0, st, a);                                        \
+        else hipLaunchKernelGGL((K<_Float16, TO>), grid, block, 0, st, a);                                           \
+    }
     if (!staged || !aligned)
     {
         const dim3 grid((max_ow + 63) / 64, (max_oh + 3) / 4, a.ntiles), block(256);
-        if (a.f32) hipLaunchKernelGGL(postproc_tiles<float>, grid, block, 0, st, a);
-        else hipLaunchKernelGGL(postproc_tiles<_Float16>, grid, block, 0, st, a);
+        if (a.out_fmt == kFmtF16) RSR_POST(postproc_tiles, _Float16)
+        else if (a.out_fmt == kFmtF32) RSR_POST(postproc_tiles, float)
+        else RSR_POST(postproc_tiles, uint8_t)
         return;
     }
     const dim3 grid((max_ow + 31) / 32, (max_oh + 31) / 32, a.ntiles), block(256);
-    if (a.f32) hipLaunchKernelGGL(postproc_tiles_lds<float>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(postproc_tiles_lds<_Float16>, grid, block, 0, st, a);
+    if (a.out_fmt == kFmtF16) RSR_POST(postproc_tiles_lds, _Float16)
+    else if (a.out_fmt == kFmtF32) RSR_POST(postproc_tiles_lds, float)
+    else RSR_POST(postproc_tiles_lds, uint8_t)
+#undef RSR_POST
 }
 
 // ---- shader-shaped kernels: same arithmetic, the shaders' own buffer layouts -----------------
