@@ -454,6 +454,19 @@ static void image_tiles(int w, int h, int T, int P, int scale, int tile0, int ti
     }
 }
 
+// The kernels address a plane through 32-bit byte offsets (raw buffer resources, out-of-range sentinel 2^31): the
+// largest plane is the 4x level, 16 * cap pixels * 32 B, and an MFMA wave reaches the 2 planes of its n-tile (4 with two n-tiles
+// per wave, flow_flags bit 0) from one base; the stores' range limit is "end of the plane + the plane's offset" (conv_flow.hip
+// make_out), which must stay below the sentinel too.  Tiles beyond that (~1,400 px) must be split by the caller.
+int Engine::check_tile_px(long long cap_px) const
+{
+    const long long reach = (flow_flags & 1) ? 4 : 2; // planes an MFMA wave addresses from one base
+    if (cap_px * 16 * 32 * reach + 4 * kGuard < (1ll << 31)) return RSR_OK;
+    const long long max_px = ((1ll << 31) - 4 * kGuard - 1) / (16 * 32 * reach);
+    return fail(RSR_E_ARG, "tilesize too large: a padded tile may have at most " + std::to_string(max_px) + " pixels" +
+                               ((flow_flags & 1) ? " with flow_flags bit 0 (e.g. -t 1000)" : " (e.g. -t 1400)"));
+}
+
 int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*& out)
 {
     const long long kBytesPerPx = bytes_per_px();
@@ -478,25 +491,14 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
     // every merged batch -- of one geometry (this plan) or of several (enqueue_mixed) -- gives its slots the capacity of a full tile: the
     // workspace layout, hence its guards, then stays put from batch to batch whatever small images come
     if (nimg > 1) cap = std::max(cap, (long long)(T + 2 * P) * (T + 2 * P));
-    // The kernels address a plane through 32-bit byte offsets (raw buffer resources, out-of-range sentinel 2^31): the
-    // largest plane is the 4x level, 16 * cap pixels * 32 B, and an MFMA wave reaches the 2 planes of its n-tile (4 with two n-tiles
-    // per wave, flow_flags bit 0) from one base; the stores' range limit is "end of the plane + the plane's offset" (conv_flow.hip
-    // make_out), which must stay below the sentinel too.  Tiles beyond that (~1,400 px) must be split by the caller.
-    {
-        const long long reach = (flow_flags & 1) ? 4 : 2; // planes an MFMA wave addresses from one base
-        if (cap * 16 * 32 * reach + 4 * kGuard >= (1ll << 31))
-        {
-            const long long max_px = ((1ll << 31) - 4 * kGuard - 1) / (16 * 32 * reach);
-            return fail(RSR_E_ARG, "tilesize too large: a padded tile may have at most " + std::to_string(max_px) + " pixels" +
-                                       ((flow_flags & 1) ? " with flow_flags bit 0 (e.g. -t 1000)" : " (e.g. -t 1400)"));
-        }
-    }
+    int rc = check_tile_px(cap);
+    if (rc != RSR_OK) return rc;
     const int per = tta ? 8 : 1;
     const long long per_slot = cap * kBytesPerPx;
     // Memory policy (the reference bounds device memory through the tile size alone, main.cpp:761-774; here ALL tiles of an image
     // form one batch, so the batch is what must be bounded): the budget is max_workspace_mb, but never more than 90 % of what
     // the device can actually give this engine right now -- free memory + the workspace it already holds - the image buffers
-    // of its lanes -- and never more than a size that has already failed to allocate (ws_clamp_bytes, enqueue_image's retry).
+    // of its lanes -- and never more than a size that has already failed to allocate (ws_clamp_bytes, enqueue_images' retry).
     long long budget = max_workspace_mb * 1024 * 1024;
     {
         const long long avail = device_avail(w, h, c);
@@ -710,7 +712,7 @@ void Engine::collect_profile(hipStream_t st)
 //   UP1(P64 @2x)  UP2(P64 @4x)  HR(P64 @4x)  OUT3 (planar [3][4H][4W] fp16)
 // Concat never happens: conv k of a dense block reads planes [x | x1..x_{k-1}] in place and writes its
 // 32 channels as plane(s) x_k.  Eltwise/BinaryOp/Interp are epilogue or staging-address variants.
-int Engine::launch(ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st)
+int Engine::launch(const ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st)
 {
     const PackedConv& c = convs[size_t(ci)];
     if (!launch_conv_flow(a, int(c.nt), num_cu, flow_flags, st))
@@ -720,13 +722,17 @@ int Engine::launch(ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st)
     return RSR_OK;
 }
 
-int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fused_outs, int nimg, const int* fused_out_ws, int split_slot, hipEvent_t ev_half,
-                        hipEvent_t ev_mid, int mid_rdb, int nslots_used, const RangeProbe* probe, int out_fmt, const int* fused_out_hs)
+int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, const BatchIO* io, const RangeProbe* probe)
 {
-    const int nslots = (nslots_used > 0 && nslots_used < b.nslots) ? nslots_used : b.nslots;
+    const int nslots = std::min(nslots_used, b.nslots);
     const long long cap = ws_cap_px;
+    const bool fused = io && conv_last_writes_image(io->c); // conv_last writes the images of io itself, else the planar b_out3 blob
+    const int split_slot = io ? io->split_slot : 0;
+    // the throttle event of a merged batch (Engine::submit_merged): behind the RDB that leaves about half an image's worth of network
+    // ahead -- the time the next batch's launches take to enqueue
+    const int mid_rdb = (io && io->ev_mid) ? kNumRDB - 1 - std::max(2, kNumRDB / (2 * std::max(1, io->nimg))) : -1;
     // the probe reads whole planes: they must hold exactly the pixels of the one tile, all of them computed, in fp16 storage
-    if (probe && (b.nslots != 1 || b.dims.size() != 1 || cap != (long long)b.dims[0].h * b.dims[0].w || b.trim4 || precise || fused_outs))
+    if (probe && (b.nslots != 1 || b.dims.size() != 1 || cap != (long long)b.dims[0].h * b.dims[0].w || b.trim4 || precise || fused))
         return fail(RSR_E_STATE, "range probe on a plan that is not one untrimmed tile in fp16 storage");
     const int pc = plane_ch(), P32 = 32 / pc, P64 = 64 / pc;
     const long long ppx = pc * 2;
@@ -826,7 +832,7 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fu
         a.out16 = rdb_x((j + 1) % 3);
         a.out_lo_off = rdb_lo;
         go(a);
-        if (j == mid_rdb && ev_mid && rc == RSR_OK && hipEventRecord(ev_mid, st) != hipSuccess) rc = fail(RSR_E_DEVICE, "hipEventRecord failed");
+        if (j == mid_rdb && rc == RSR_OK && hipEventRecord(io->ev_mid, st) != hipSuccess) rc = fail(RSR_E_DEVICE, "hipEventRecord failed");
     }
     { // trunk_conv + global skip: fea + conv(trunk)   (x4.param:994-995)
         ConvArgs a = base_args(0, 0);
@@ -884,17 +890,18 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fu
         { // conv_last 64 -> 3   (x4.param:1001), planar fp16 output = the reference's `output` blob
             ConvArgs a = base_args(2, 2);
             a.src0 = hr; a.n0 = P64;
-            if (fused_outs)
-            { // non-TTA RGB with conv3x3_flow: conv_last applies realsr_postproc.comp itself and writes the image(s)
-                a.out_u8 = fused_outs[0];
-                for (int i = 0; i < nimg && i < kMaxMerge; i++)
+            if (fused)
+            { // non-TTA RGB with conv3x3_flow: conv_last applies realsr_postproc.comp itself and writes the image(s): uint8 HWC, or --
+              // out_fmt -- planar fp16 / fp32 of out_plane_rows[i] rows
+                for (int i = 0; i < io->nimg && i < kMaxMerge; i++)
                 {
-                    a.out_u8s[i] = fused_outs[i];
-                    a.out_u8_ws[i] = fused_out_ws[i];
-                    a.out_plane_rows[i] = fused_out_hs ? fused_out_hs[i] : 0;
+                    a.out_u8s[i] = static_cast<uint8_t*>(io->out[i]);
+                    a.out_u8_ws[i] = io->w[i] * scale;
+                    a.out_plane_rows[i] = io->h[i] * scale; // (the planar formats come with whole images only: process_device)
                 }
-                a.out_fmt = out_fmt;
-                a.out_u8_w = fused_out_ws[0];
+                a.out_u8 = a.out_u8s[0];
+                a.out_fmt = io->out_fmt;
+                a.out_u8_w = a.out_u8_ws[0];
                 a.out_u8_crop = prepadding * scale;
                 a.out_u8_bgr = bgr ? 1 : 0;
             }
@@ -906,7 +913,7 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fu
             sub(a, 2);
             go(a);
         }
-        if (s1 == split_slot && ev_half && rc == RSR_OK && hipEventRecord(ev_half, st) != hipSuccess)
+        if (s1 == split_slot && io->ev_half && rc == RSR_OK && hipEventRecord(io->ev_half, st) != hipSuccess)
             rc = fail(RSR_E_DEVICE, "hipEventRecord failed");
         s0 = s1;
     }
@@ -914,16 +921,10 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fu
 }
 
 // ---- process ----------------------------------------------------------------------------------
-// enqueue preproc -> network -> postproc for every tile batch of one image on `st` (mu held)
-int Engine::enqueue_image(const void* d_in, int w, int h, int c, void* d_out, hipStream_t st, int tile0, int tile1, hipEvent_t ev_half,
-                          size_t* half_rows, int in_fmt, int out_fmt)
+// enqueue preproc -> network -> postproc for every tile batch of the image(s) of io on `st` (mu held)
+int Engine::enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size_t* half_rows, hipStream_t st)
 {
-    return enqueue_images(&d_in, &d_out, 1, w, h, c, st, tile0, tile1, ev_half, half_rows, nullptr, 0, in_fmt, out_fmt);
-}
-
-int Engine::enqueue_images(const void* const* d_in, void* const* d_out, int nimg, int w, int h, int c, hipStream_t st, int tile0, int tile1,
-                           hipEvent_t ev_half, size_t* half_rows, hipEvent_t ev_mid, int plan_nimg, int in_fmt, int out_fmt)
-{
+    const int nimg = io.nimg, w = io.w[0], h = io.h[0], c = io.c;
     const bool merged = plan_nimg > 0; // (every caller of a merged batch reports the progress of its own image: process_host)
     if (plan_nimg < nimg) plan_nimg = nimg;
     const long long kBytesPerPx = bytes_per_px();
@@ -958,7 +959,6 @@ int Engine::enqueue_images(const void* const* d_in, void* const* d_out, int nimg
     {
         rc = get_plan(w, h, c, tile0, tile1, plan_nimg, planp);
         if (rc != RSR_OK) return rc;
-        // (a merged batch narrower than its plan needs the slots of its own images only)
         // (a merged batch narrower than its plan still gets the plan's workspace: growing it image by image as wider batches form
         // would re-allocate and clear gigabytes a dozen times)
         rc = ensure_workspace(planp->slots_per_batch, planp->cap_px, st);
@@ -993,27 +993,25 @@ int Engine::enqueue_images(const void* const* d_in, void* const* d_out, int nimg
     int done = 0, total = 0;
     for (const Plan::Batch& b : plan.batches) total += b.ntiles;
     const int tiles_wanted = (tile1 - tile0) * nimg; // the tiles of the first nimg images (all of the plan's unless the batch is narrower)
-    int ws[kMaxMerge], hs[kMaxMerge];
-    for (int i = 0; i < nimg; i++) { ws[i] = w; hs[i] = h; }
+    io.out_row0 = plan.out_row0;
+    const hipEvent_t ev_mid = io.ev_mid; // of the last batch
     for (const Plan::Batch& b : plan.batches)
     {
         const int ntiles = std::min(b.ntiles, tiles_wanted - b.tile0); // of this batch
         if (ntiles <= 0) break;
         // host calls: split the 4x tail at a tile-row boundary so that the first output rows can travel while the rest is computed
-        const bool fused = !tta && c == 3 && !(dbg & 8192);
-        int split_slot = 0;
-        if (fused && nimg == 1 && ev_half && half_rows && plan.batches.size() == 1 && !profiling && !(dbg & 16384))
+        io.split_slot = 0;
+        if (conv_last_writes_image(c) && nimg == 1 && io.ev_half && half_rows && plan.batches.size() == 1 && !profiling && !(dbg & 16384))
         {
             const int xt = xtiles, yt = b.ntiles / xt;
             if (yt >= 2 && b.ntiles == xt * yt && plan.tile0 % xt == 0)
             {
-                split_slot = xt * (yt / 2);
-                *half_rows = size_t(b.tiles[size_t(split_slot)].out_y - b.tiles[0].out_y); // output rows finished at ev_half
+                io.split_slot = xt * (yt / 2);
+                *half_rows = size_t(b.tiles[size_t(io.split_slot)].out_y - b.tiles[0].out_y); // output rows finished at ev_half
             }
         }
-        const bool last_batch = b.tile0 + b.ntiles >= tiles_wanted;
-        rc = launch_batch(b, plan.cap_px, plan.max_tw, plan.max_th, plan.out_row0, d_in, d_out, ws, hs, nimg, c, ntiles, st, split_slot, ev_half,
-                          last_batch ? ev_mid : nullptr, in_fmt, out_fmt);
+        io.ev_mid = b.tile0 + b.ntiles >= tiles_wanted ? ev_mid : nullptr;
+        rc = launch_batch(b, plan.cap_px, plan.max_tw, plan.max_th, ntiles, st, io);
         if (rc != RSR_OK) return rc;
         if (progress && !merged) // one call per TILE, like the reference's line per tile (realsr.cpp:481), issued when the tile's batch is enqueued
             for (int i = 1; i <= b.ntiles; i++) progress(done + i, total, progress_user); // (a merged batch: every caller reports its own image)
@@ -1030,23 +1028,27 @@ int Engine::enqueue_images(const void* const* d_in, void* const* d_out, int nimg
 }
 
 // preproc -> network -> postproc of the first `ntiles` tiles of one tile batch on `st` (mu held; the workspace is laid out for cap_px).
-// The images of the batch may differ in size (ws / hs): every tile carries the index of its image.
-int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int out_row0, const void* const* d_in, void* const* d_out,
-                         const int* ws, const int* hs, int nimg, int c, int ntiles, hipStream_t st, int split_slot, hipEvent_t ev_half, hipEvent_t ev_mid,
-                         int in_fmt, int out_fmt)
+// The images of the batch may differ in size (io.w / io.h): every tile carries the index of its image.
+int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io)
 {
     constexpr int pc = plane_ch();
-    const int per = tta ? 8 : 1, nslots_used = ntiles * per;
+    const int per = tta ? 8 : 1, c = io.c;
+    const int variant = (dbg & 32768) ? 1 : ((dbg & 65536) ? 2 : 0);
     PreArgs pa;
     std::memset(&pa, 0, sizeof pa);
-    for (int i = 0; i < nimg; i++)
+    PostArgs po;
+    std::memset(&po, 0, sizeof po);
+    for (int i = 0; i < io.nimg; i++)
     {
-        pa.imgs[i] = static_cast<const uint8_t*>(d_in[i]);
-        pa.ws[i] = ws[i];
-        pa.hs[i] = hs[i];
+        pa.imgs[i] = po.in_imgs[i] = static_cast<const uint8_t*>(io.in[i]);
+        pa.ws[i] = po.in_ws[i] = io.w[i];
+        pa.hs[i] = io.h[i];
+        po.outs[i] = static_cast<uint8_t*>(io.out[i]);
+        po.out_ws[i] = io.w[i] * scale;
+        po.out_hs[i] = io.h[i] * scale; // (the planar formats come with whole images only: process_device)
     }
-    pa.nimgs = nimg;
-    pa.fmt = in_fmt;
+    pa.nimgs = io.nimg;
+    pa.fmt = io.in_fmt;
     pa.c = c;
     pa.tiles = b.d_tiles;
     pa.ntiles = ntiles;
@@ -1055,28 +1057,13 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     pa.slot_stride = (32 / pc) * (cap_px * pc * 2 + kGuard);
     pa.bgr = bgr ? 1 : 0;
     pa.plane_ch = pc;
-    pa.variant = (dbg & 32768) ? 1 : ((dbg & 65536) ? 2 : 0);
+    pa.variant = variant;
     launch_preproc_tiles(pa, max_tw, max_th, st);
     // bytes of a pixel in the caller's image: c for uint8 HWC, 3 halfs / floats for the planar formats
     auto px_bytes = [c](int fmt) { return fmt == RSR_FMT_F16_CHW ? 6.0 : (fmt == RSR_FMT_F32_CHW ? 12.0 : double(c)); };
-    mark(0, 0, b.px[0] / per * px_bytes(in_fmt) + b.px[0] * 64, st);
-    // conv_last writes the uint8 image directly when no TTA merge / alpha channel needs the fp16 blob (dbg 8192: off)
-    const bool fused = !tta && c == 3 && !(dbg & 8192);
-    uint8_t* outs[kMaxMerge];
-    int out_ws[kMaxMerge], out_hs[kMaxMerge];
-    for (int i = 0; i < nimg; i++)
-    {
-        outs[i] = static_cast<uint8_t*>(d_out[i]);
-        out_ws[i] = ws[i] * scale;
-        out_hs[i] = hs[i] * scale; // (the planar formats come with whole images only: process_device)
-    }
-    // the throttle event of a merged batch (Engine::submit_merged): behind the RDB that leaves about half an image's worth of network
-    // ahead -- the time the next batch's launches take to enqueue
-    int rc = run_network(b, st, fused ? outs : nullptr, nimg, out_ws, split_slot, ev_half, ev_mid, kNumRDB - 1 - std::max(2, kNumRDB / (2 * std::max(1, nimg))),
-                         nslots_used, nullptr, out_fmt, out_hs);
-    if (rc != RSR_OK || fused) return rc;
-    PostArgs po;
-    std::memset(&po, 0, sizeof po);
+    mark(0, 0, b.px[0] / per * px_bytes(io.in_fmt) + b.px[0] * 64, st);
+    const int rc = run_network(b, st, ntiles * per, &io, nullptr);
+    if (rc != RSR_OK || conv_last_writes_image(c)) return rc;
     po.planar3 = b_out3.p;
     po.f32 = precise ? 1 : 0;
     po.slot_stride = cap_px * (precise ? 192 : 96);
@@ -1084,23 +1071,15 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     po.ntiles = ntiles;
     po.tta = tta;
     po.crop = prepadding * scale;
-    for (int i = 0; i < nimg; i++)
-    {
-        po.outs[i] = outs[i];
-        po.out_ws[i] = out_ws[i];
-        po.out_hs[i] = out_hs[i];
-        po.in_imgs[i] = static_cast<const uint8_t*>(d_in[i]);
-        po.in_ws[i] = ws[i];
-    }
-    po.nimgs = nimg;
-    po.out_fmt = out_fmt;
+    po.nimgs = io.nimg;
+    po.out_fmt = io.out_fmt;
     po.c = c;
-    po.out_row0 = out_row0;
+    po.out_row0 = io.out_row0;
     po.tilesize = tilesize;
     po.bgr = bgr ? 1 : 0;
-    po.variant = (dbg & 32768) ? 1 : ((dbg & 65536) ? 2 : 0);
+    po.variant = variant;
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
-    mark(2, 0, b.px[2] / per * (6.0 * per + px_bytes(out_fmt)), st);
+    mark(2, 0, b.px[2] / per * (6.0 * per + px_bytes(io.out_fmt)), st);
     return RSR_OK;
 }
 
@@ -1130,7 +1109,8 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
         t.slot0 = i * per;
         for (int k = 0; k < per; k++) b.dims.push_back(k < 4 ? TileDim{t.th, t.tw} : TileDim{t.tw, t.th}); // realsr.cpp:251-258
     }
-    if (cap * 16 * 32 * ((flow_flags & 1) ? 4 : 2) + 4 * kGuard >= (1ll << 31)) return fail(RSR_E_ARG, "tilesize too large");
+    int rc = check_tile_px(cap);
+    if (rc != RSR_OK) return rc;
     const long long need = (long long)b.nslots * cap * bytes_per_px();
     const long long avail = device_avail(g[0]->w, g[0]->h, c);
     if (need > max_workspace_mb * 1024 * 1024 || (avail >= 0 && need > avail)) return fail(RSR_E_NOMEM, "merged batch exceeds the workspace budget");
@@ -1139,23 +1119,14 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
     HIP_TRY(hipSetDevice(device));
     const int k = int(mix_seq++ % 3);
     if (mix_ev[k]) HIP_TRY(hipEventSynchronize(mix_ev[k])); // the batch that read this buffer last has finished
-    int rc;
     if ((rc = ensure(mix_tab[k], batch_table_bytes(b))) != RSR_OK) return rc;
     char* d = static_cast<char*>(mix_tab[k].p);
     const hipError_t e = upload_batch(b, d, false);
     if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("merged batch table upload: ") + hipGetErrorString(e));
     if ((rc = ensure_workspace(b.nslots, cap, st)) != RSR_OK) return rc;
-    const void* ins[kMaxMerge];
-    void* outs[kMaxMerge];
-    int ws[kMaxMerge], hs[kMaxMerge];
-    for (int i = 0; i < n; i++)
-    {
-        ins[i] = g[i]->d_in;
-        outs[i] = g[i]->d_out;
-        ws[i] = g[i]->w;
-        hs[i] = g[i]->h;
-    }
-    rc = launch_batch(b, cap, mtw, mth, 0, ins, outs, ws, hs, n, c, b.ntiles, st, 0, nullptr, ev_mid);
+    BatchIO io(g, n);
+    io.ev_mid = ev_mid;
+    rc = launch_batch(b, cap, mtw, mth, b.ntiles, st, io);
     if (rc != RSR_OK) return rc;
     if (!mix_ev[k] && hipEventCreateWithFlags(&mix_ev[k], hipEventDisableTiming) != hipSuccess) mix_ev[k] = nullptr;
     if (mix_ev[k]) HIP_TRY(hipEventRecord(mix_ev[k], st));
@@ -1214,7 +1185,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             // put on ITS caller's stream included: the compute stream was made to wait for it, below) -- so this call's kernels go
             // straight onto the caller's stream: no event hop into the compute stream and back.  Whatever is enqueued on the compute
             // stream later uses the same workspace and must come behind: it waits for this call's last kernel.
-            const int rc = enqueue_image(d_in, w, h, c, d_out, user_stream, 0, -1, nullptr, nullptr, in_fmt, out_fmt);
+            const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt), 0, -1, 0, nullptr, user_stream);
             hipEvent_t e = take_event();
             if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
             { // cannot order the compute stream behind it: fall back to waiting here
@@ -1235,7 +1206,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             HIP_TRY(hipStreamWaitEvent(stream, e, 0));
             give_event(e);
         }
-        const int rc = enqueue_image(d_in, w, h, c, d_out, stream, 0, -1, nullptr, nullptr, in_fmt, out_fmt);
+        const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt), 0, -1, 0, nullptr, stream);
         if (rc != RSR_OK) return rc;
         if (user_stream || sync)
         {
@@ -1300,21 +1271,20 @@ int Engine::run_group(MergeReq* const* g, int n)
     for (int i = 0; i < n; i++)
         if (g[i]->T != tilesize) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
     HIP_TRY(hipSetDevice(device));
-    const void* ins[kMaxMerge];
-    void* outs[kMaxMerge];
     for (int i = 0; i < n; i++)
-    {
-        ins[i] = g[i]->d_in;
-        outs[i] = g[i]->d_out;
         if (g[i]->ev_in) HIP_TRY(hipStreamWaitEvent(stream, g[i]->ev_in, 0));
-    }
     if (!merge_mid && hipEventCreateWithFlags(&merge_mid, hipEventDisableTiming) != hipSuccess) merge_mid = nullptr;
     merge_mid_used = false;
     bool same = true;
     for (int i = 1; i < n; i++) same = same && g[i]->w == g[0]->w && g[i]->h == g[0]->h;
     int rc;
-    if (same) // one geometry: the cached plan of merge_width images, launched in a prefix
-        rc = enqueue_images(ins, outs, n, g[0]->w, g[0]->h, g[0]->c, stream, 0, -1, nullptr, nullptr, merge_mid, merge_width(g[0]->w, g[0]->h, g[0]->c));
+    // all of one image, or of several of ONE geometry, under the plan of merge_width images; `mid`: the throttle event is recorded in this one
+    auto whole = [&](MergeReq* const* r, int k, bool mid) {
+        BatchIO io(r, k);
+        io.ev_mid = mid ? merge_mid : nullptr;
+        return enqueue_images(io, 0, -1, merge_width(r[0]->w, r[0]->h, r[0]->c), nullptr, stream);
+    };
+    if (same) rc = whole(g, n, true); // launched in a prefix of the cached plan
     else
     {
         rc = enqueue_mixed(g, n, stream, merge_mid);
@@ -1323,11 +1293,7 @@ int Engine::run_group(MergeReq* const* g, int n)
         { // the batch does not fit the workspace budget / the device right now: one image at a time (each call bounds and halves its own batch)
             (void)hipStreamSynchronize(stream);
             for (int i = 0; i < n; i++)
-            {
-                rc = enqueue_images(&ins[i], &outs[i], 1, g[i]->w, g[i]->h, g[i]->c, stream, 0, -1, nullptr, nullptr, i == n - 1 ? merge_mid : nullptr,
-                                    merge_width(g[i]->w, g[i]->h, g[i]->c));
-                if (rc != RSR_OK) break;
-            }
+                if ((rc = whole(g + i, 1, i == n - 1)) != RSR_OK) break;
         }
     }
     if (rc == RSR_OK)
@@ -1631,7 +1597,9 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
         if (!loaded || scale != 4 || tilesize != T)
             return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the guard drains the upload)
         HIP_TRY(hipStreamWaitEvent(stream, L->ev_in, 0));
-        rc = enqueue_image(L->d_in.p, w, h, c, dbase, stream, tile0, tile1, L->ev_half, &half_rows);
+        BatchIO io(L->d_in.p, dbase, w, h, c, RSR_FMT_U8_HWC, RSR_FMT_U8_HWC);
+        io.ev_half = L->ev_half;
+        rc = enqueue_images(io, tile0, tile1, 0, &half_rows, stream);
         if (rc != RSR_OK)
         {
             (void)hipStreamSynchronize(stream); // kernels of this call that did get enqueued use the lane buffers
@@ -1749,7 +1717,39 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
     return RSR_OK;
 }
 
-// one tile through the network only (layer-level parity hook)
+// The one-tile batch of the hooks below: one slot of exactly w x h pixels, nothing trimmed; its tables and the planar fp16
+// [3][h][w] host tile go to device scratch that lives as long as `t`.
+int Engine::one_tile_upload(OneTile& t, const uint16_t* tile, int w, int h)
+{
+    t.w = w;
+    t.h = h;
+    t.b.ntiles = t.b.nslots = 1;
+    t.b.dims.push_back(TileDim{h, w});
+    make_items(t.b, fold_cols);
+    const size_t tile_bytes = size_t(w) * h * 6;
+    int rc;
+    if ((rc = check_tile_px((long long)w * h)) != RSR_OK || (rc = ensure(t.tab, batch_table_bytes(t.b))) != RSR_OK || (rc = ensure(t.tile, tile_bytes)) != RSR_OK)
+        return rc;
+    char* d = static_cast<char*>(t.tab.p);
+    hipError_t he = upload_batch(t.b, d);
+    if (he == hipSuccess) he = hipMemcpy(t.tile.p, tile, tile_bytes, hipMemcpyHostToDevice);
+    if (he != hipSuccess) return fail(RSR_E_DEVICE, std::string("one-tile upload: ") + hipGetErrorString(he));
+    return RSR_OK;
+}
+
+int Engine::one_tile_walk(const OneTile& t, const RangeProbe* probe)
+{
+    int rc = ensure_workspace(1, (long long)t.w * t.h, stream); // (a change of layout zeroes b_in: the tile is written every time)
+    if (rc != RSR_OK) return rc;
+    launch_planar3_to_plane(static_cast<const uint16_t*>(t.tile.p), t.w, t.h, static_cast<char*>(b_in.p) + kGuard, plane_ch(), stream);
+    const bool was = profiling;
+    profiling = false;
+    rc = run_network(t.b, stream, 1, nullptr, probe);
+    profiling = was;
+    return rc;
+}
+
+// one tile through the network only (layer-level parity hook); the workspace keeps this tile's layout
 int Engine::net_forward(const uint16_t* in, int w, int h, uint16_t* out, float* out32)
 {
     if (!in || (!out && !out32) || w < 1 || h < 1) return fail(RSR_E_ARG, "bad arguments");
@@ -1757,54 +1757,29 @@ int Engine::net_forward(const uint16_t* in, int w, int h, uint16_t* out, float* 
     if (!loaded) return fail(RSR_E_STATE, "net_forward before load");
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamSynchronize(stream));
-    Plan::Batch b;
-    b.ntiles = 1;
-    b.nslots = 1;
-    b.dims.push_back(TileDim{h, w});
-    make_items(b, fold_cols);
-    const long long cap = (long long)w * h;
-    if (cap * 16 * 32 * ((flow_flags & 1) ? 4 : 2) + 4 * kGuard >= (1ll << 31)) return fail(RSR_E_ARG, "tile too large");
-    DevBuf tab, tmp;
-    auto cleanup = [&]() {
-        if (tab.p) (void)hipFree(tab.p);
-        if (tmp.p) (void)hipFree(tmp.p);
-    };
+    OneTile t;
     int rc;
-    if ((rc = ensure(tab, batch_table_bytes(b))) != RSR_OK) return rc;
-    char* d = static_cast<char*>(tab.p);
-    hipError_t he = upload_batch(b, d);
+    if ((rc = one_tile_upload(t, in, w, h)) != RSR_OK || (rc = one_tile_walk(t, nullptr)) != RSR_OK) return rc;
     const size_t npx = size_t(w) * h;
-    if (he == hipSuccess && (rc = ensure_workspace(1, cap, stream)) != RSR_OK) { cleanup(); return rc; }
-    if (he == hipSuccess && (rc = ensure(tmp, npx * 6)) != RSR_OK) { cleanup(); return rc; }
-    if (he == hipSuccess) he = hipMemcpy(tmp.p, in, npx * 6, hipMemcpyHostToDevice);
-    if (he == hipSuccess)
+    hipError_t he = hipStreamSynchronize(stream);
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he == hipSuccess && !precise)
     {
-        launch_planar3_to_plane(static_cast<const uint16_t*>(tmp.p), w, h, static_cast<char*>(b_in.p) + kGuard, plane_ch(), stream);
-        const bool was = profiling;
-        profiling = false;
-        rc = run_network(b, stream);
-        profiling = was;
-        he = hipStreamSynchronize(stream);
-        if (he == hipSuccess) he = hipGetLastError();
-        if (he == hipSuccess && rc == RSR_OK && !precise)
-        {
-            if (out) he = hipMemcpy(out, b_out3.p, npx * 16 * 6, hipMemcpyDeviceToHost);
-            if (out32) rc = fail(RSR_E_STATE, "the fp32 output blob exists in precise mode only (rsr_set_option precise 1)");
-        }
-        else if (he == hipSuccess && rc == RSR_OK)
-        { // precise mode: conv_last left fp32; the fp16 view of it is rounded here, on the host
-            std::vector<float> tmp32(out32 ? 0 : npx * 16 * 3);
-            float* dst = out32 ? out32 : tmp32.data();
-            he = hipMemcpy(dst, b_out3.p, npx * 16 * 12, hipMemcpyDeviceToHost);
-            if (he == hipSuccess && out)
-                for (size_t i = 0; i < npx * 16 * 3; i++)
-                {
-                    const _Float16 hv = (_Float16)dst[i];
-                    std::memcpy(&out[i], &hv, 2);
-                }
-        }
+        if (out) he = hipMemcpy(out, b_out3.p, npx * 16 * 6, hipMemcpyDeviceToHost);
+        if (out32) rc = fail(RSR_E_STATE, "the fp32 output blob exists in precise mode only (rsr_set_option precise 1)");
     }
-    cleanup();
+    else if (he == hipSuccess)
+    { // precise mode: conv_last left fp32; the fp16 view of it is rounded here, on the host
+        std::vector<float> tmp32(out32 ? 0 : npx * 16 * 3);
+        float* dst = out32 ? out32 : tmp32.data();
+        he = hipMemcpy(dst, b_out3.p, npx * 16 * 12, hipMemcpyDeviceToHost);
+        if (he == hipSuccess && out)
+            for (size_t i = 0; i < npx * 16 * 3; i++)
+            {
+                const _Float16 hv = (_Float16)dst[i];
+                std::memcpy(&out[i], &hv, 2);
+            }
+    }
     if (he != hipSuccess) return fail(RSR_E_DEVICE, std::string("net_forward: ") + hipGetErrorString(he));
     return rc;
 }
@@ -1859,12 +1834,10 @@ int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* 
     if (!loaded) return fail(RSR_E_STATE, "selfcheck before load");
     if (!tile && w == 0 && h == 0) w = h = 148; // C1's padded tile: the size of the storage measurements in profiles/
     if (w < 1 || h < 1) return fail(RSR_E_ARG, "bad tile size");
-    const long long cap = (long long)w * h;
-    if (cap * 16 * 32 * ((flow_flags & 1) ? 4 : 2) + 4 * kGuard >= (1ll << 31)) return fail(RSR_E_ARG, "tile too large");
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamSynchronize(stream));
-    const size_t npx = size_t(cap), nout = npx * 16 * 3;
+    const size_t npx = size_t(w) * h, nout = npx * 16 * 3;
     std::vector<uint16_t> own;
     if (!tile)
     {
@@ -1872,57 +1845,42 @@ int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* 
         selfcheck_tile(own.data(), w, h);
         tile = own.data();
     }
-    Plan::Batch b;
-    b.ntiles = 1;
-    b.nslots = 1;
-    b.dims.push_back(TileDim{h, w});
-    make_items(b, fold_cols);
     // device side of the report: nonfinite[kNumConvs] | bytes_differ | peak_bits[kNumConvs] | storage_err bits, max_byte_diff
     constexpr size_t kRep64 = kNumConvs + 1, kRep32 = kNumConvs + 2, kRepBytes = kRep64 * 8 + kRep32 * 4;
-    DevBuf tab, tmp, rep, out16;
-    const bool was_precise = precise, was_profiling = profiling;
-    auto finish = [&](int code) {
-        for (DevBuf* d : {&tab, &tmp, &rep, &out16})
-            if (d->p) (void)hipFree(d->p);
-        precise = was_precise;
-        profiling = was_profiling;
-        ws_cap_px = 0; // the workspace holds this walk's layout: the next call lays out its own
-        return code;
-    };
+    OneTile t;
+    ScratchBuf rep, out16;
     int rc;
-    if ((rc = ensure(tab, batch_table_bytes(b))) != RSR_OK || (rc = ensure(tmp, npx * 6)) != RSR_OK || (rc = ensure(rep, kRepBytes)) != RSR_OK ||
-        (rc = ensure(out16, nout * 2)) != RSR_OK)
-        return finish(rc);
-    char* d = static_cast<char*>(tab.p);
-    hipError_t he = upload_batch(b, d);
-    if (he == hipSuccess) he = hipMemcpy(tmp.p, tile, npx * 6, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemsetAsync(rep.p, 0, kRepBytes, stream);
-    if (he != hipSuccess) return finish(fail(RSR_E_DEVICE, std::string("selfcheck: ") + hipGetErrorString(he)));
+    if ((rc = one_tile_upload(t, tile, w, h)) != RSR_OK || (rc = ensure(rep, kRepBytes)) != RSR_OK || (rc = ensure(out16, nout * 2)) != RSR_OK) return rc;
+    hipError_t he = hipMemsetAsync(rep.p, 0, kRepBytes, stream);
     unsigned long long* r64 = static_cast<unsigned long long*>(rep.p);
     unsigned* r32 = reinterpret_cast<unsigned*>(r64 + kRep64);
     RangeProbe probe;
     probe.nonfinite = r64;
     probe.peak_bits = r32;
-    profiling = false;
-    for (int pass = 0; pass < 2 && rc == RSR_OK; pass++)
+    struct Restore // from here on, whatever way the call ends
+    {
+        Engine& e;
+        const bool was_precise;
+        ~Restore()
+        {
+            e.precise = was_precise;
+            e.ws_cap_px = 0; // the workspace holds this walk's layout: the next call lays out its own
+        }
+    } restore{*this, precise};
+    for (int pass = 0; pass < 2 && he == hipSuccess; pass++)
     {
         precise = pass == 1;
-        if ((rc = ensure_workspace(1, cap, stream)) != RSR_OK) break; // (a change of layout zeroes b_in: the tile is written again)
-        launch_planar3_to_plane(static_cast<const uint16_t*>(tmp.p), w, h, static_cast<char*>(b_in.p) + kGuard, plane_ch(), stream);
-        rc = run_network(b, stream, nullptr, 1, nullptr, 0, nullptr, nullptr, -1, -1, pass == 0 ? &probe : nullptr);
-        if (rc != RSR_OK) break;
+        if ((rc = one_tile_walk(t, pass == 0 ? &probe : nullptr)) != RSR_OK) return rc;
         if (pass == 0) he = hipMemcpyAsync(out16.p, b_out3.p, nout * 2, hipMemcpyDeviceToDevice, stream);
         else launch_output_compare(static_cast<const uint16_t*>(out16.p), static_cast<const float*>(b_out3.p), (long long)nout, r32 + kNumConvs, r64 + kNumConvs, stream);
-        if (he != hipSuccess) break;
     }
-    if (rc != RSR_OK) return finish(rc);
     std::vector<unsigned long long> h64(kRep64);
     std::vector<unsigned> h32(kRep32);
     if (he == hipSuccess) he = hipStreamSynchronize(stream);
     if (he == hipSuccess) he = hipGetLastError();
     if (he == hipSuccess) he = hipMemcpy(h64.data(), r64, kRep64 * 8, hipMemcpyDeviceToHost);
     if (he == hipSuccess) he = hipMemcpy(h32.data(), r32, kRep32 * 4, hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return finish(fail(RSR_E_DEVICE, std::string("selfcheck: ") + hipGetErrorString(he)));
+    if (he != hipSuccess) return fail(RSR_E_DEVICE, std::string("selfcheck: ") + hipGetErrorString(he));
 
     rsr_selfcheck_report r;
     std::memset(&r, 0, sizeof r);
@@ -1950,7 +1908,7 @@ int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* 
     sc_last = r;
     selfcheck_runs++;
     *out = r;
-    return finish(RSR_OK);
+    return RSR_OK;
 }
 
 int Engine::apply_precise_auto()
@@ -2014,24 +1972,17 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
             for (size_t p = 0; p < ipx; p++) hres[size_t(ch / pch) * ipl + kGuard / 2 + p * size_t(pch) + size_t(ch % pch)] = res[size_t(ch) * ipx + p];
         if (res_lo) put_lo(hres, size_t(npo) * ipl_b, res_lo);
     }
-    DevBuf d_w, d_in, d_out, d_tab, d_res;
+    ScratchBuf d_w, d_in, d_out, d_tab, d_res;
     std::vector<WorkItem> items;
     // test_repeat > 1 (measurement aid): the same blocks N times in ONE launch -- after the first pass every patch and every
     // output line is in the L2s, i.e. the launch shows what this conv costs when nothing goes to HBM (tools/l2_bound_probe.py)
     for (int rep = 0; rep < std::max(1, test_repeat); rep++)
         append_block_items(items, 0, H, W, 0, 0, 0, 0, 0, fold_cols);
     const TileDim td{h, w};
-    auto cleanup = [&]() {
-        for (DevBuf* b : {&d_w, &d_in, &d_out, &d_tab, &d_res})
-            if (b->p) (void)hipFree(b->p);
-    };
     if ((rc = ensure(d_w, pk.size())) != RSR_OK || (rc = ensure(d_in, hin.size() * 2)) != RSR_OK ||
         (rc = ensure(d_out, hout.size() * 2)) != RSR_OK || (rc = ensure(d_tab, 256 + items.size() * sizeof(WorkItem))) != RSR_OK ||
         (!hres.empty() && (rc = ensure(d_res, hres.size() * 2)) != RSR_OK))
-    {
-        cleanup();
         return rc;
-    }
     hipError_t he = hipMemcpy(d_w.p, pk.data(), pk.size(), hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(d_in.p, hin.data(), hin.size() * 2, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemsetAsync(d_out.p, 0, hout.size() * 2, stream);
@@ -2090,7 +2041,6 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
         if (he == hipSuccess) he = hipGetLastError();
         if (he == hipSuccess) he = hipMemcpy(hout.data(), d_out.p, hout.size() * 2, hipMemcpyDeviceToHost);
     }
-    cleanup();
     if (he != hipSuccess) return fail(RSR_E_DEVICE, std::string("conv_test: ") + hipGetErrorString(he));
     if (rc != RSR_OK) return rc;
     for (int ch = 0; ch < cout; ch++)

@@ -45,6 +45,18 @@ struct DevBuf
     size_t bytes = 0;
 };
 
+// A device buffer that lives as long as its scope (the scratch tables and tiles of the test hooks); filled by Engine::ensure.
+struct ScratchBuf : DevBuf
+{
+    ScratchBuf() = default;
+    ScratchBuf(const ScratchBuf&) = delete;
+    ScratchBuf& operator=(const ScratchBuf&) = delete;
+    ~ScratchBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+
 // geometry of one rsr_process call; cached per (w,h,c,T,P,tta,budget)
 struct Plan
 {
@@ -120,6 +132,29 @@ struct MergeReq
     int rc = RSR_OK;
     std::string err;
     bool done = false, lead = false; // under Engine::cq_mu
+};
+
+// What one tile batch is told about its caller (Engine::launch_batch, Engine::run_network): the images its tiles come from and go
+// to, and the events the caller wants recorded on the way.
+struct BatchIO
+{
+    int nimg = 0, c = 0;        // images of the batch (<= kMaxMerge; BaseTile::img selects) and their channel count
+    const void* in[kMaxMerge];  // per image: the device image, in_fmt, w[i] x h[i] ...
+    void* out[kMaxMerge];       // ... and its 4w[i] x 4h[i] result, out_fmt
+    int w[kMaxMerge], h[kMaxMerge];
+    int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float formats come with whole images of c == 3 only)
+    int out_row0 = 0;           // `out` points at this output row of the x4 image (a tile range's device buffer holds only its rows)
+    int split_slot = 0;         // > 0: the 4x tail is split in front of this slot and ...
+    hipEvent_t ev_half = nullptr; // ... this event recorded behind the first part (the caller starts downloading its output rows)
+    hipEvent_t ev_mid = nullptr;  // recorded behind the middle RDB (a merged batch's throttle event, Engine::submit_merged)
+    BatchIO(const void* d_in, void* d_out, int w0, int h0, int c0, int in_fmt0, int out_fmt0) : nimg(1), c(c0), in_fmt(in_fmt0), out_fmt(out_fmt0)
+    {
+        in[0] = d_in, out[0] = d_out, w[0] = w0, h[0] = h0;
+    }
+    BatchIO(MergeReq* const* g, int n) : nimg(n), c(g[0]->c) // the uint8 images of merged calls
+    {
+        for (int i = 0; i < n; i++) in[i] = g[i]->d_in, out[i] = g[i]->d_out, w[i] = g[i]->w, h[i] = g[i]->h;
+    }
 };
 
 // one in-flight rsr_process call (host API)
@@ -273,28 +308,32 @@ struct Engine
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
-    // fused_outs: non-null = conv_last writes the images itself (one pointer per image of the batch): uint8 HWC, or -- out_fmt -- planar
-    // fp16 / fp32 of fused_out_hs[i] rows
-    // ev_mid: recorded behind the middle RDB (a merged batch's throttle event)
-    // mid_rdb >= 0: ev_mid is recorded behind that RDB.  nslots_used < b.nslots: only the first slots of the batch (a merged batch narrower than its plan)
+    bool conv_last_writes_image(int c) const { return !tta && c == 3 && !(dbg & 8192); } // no TTA merge / alpha channel needs the planar blob (dbg 8192: off)
+    int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
+    // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
+    // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).
     // probe: non-null = every convolution is followed by a range-probe launch on what it stored (the self-check's one-tile batch in
     // fp16 storage only; null everywhere else: the launch sequence is then exactly the one without it)
-    int run_network(const Plan::Batch& b, hipStream_t st, uint8_t* const* fused_outs = nullptr, int nimg = 1, const int* fused_out_ws = nullptr, int split_slot = 0,
-                    hipEvent_t ev_half = nullptr, hipEvent_t ev_mid = nullptr, int mid_rdb = -1, int nslots_used = -1, const RangeProbe* probe = nullptr,
-                    int out_fmt = RSR_FMT_U8_HWC, const int* fused_out_hs = nullptr);
-    int launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int out_row0, const void* const* d_in, void* const* d_out, const int* ws,
-                     const int* hs, int nimg, int c, int ntiles, hipStream_t st, int split_slot, hipEvent_t ev_half, hipEvent_t ev_mid,
-                     int in_fmt = RSR_FMT_U8_HWC, int out_fmt = RSR_FMT_U8_HWC);
+    int run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, const BatchIO* io, const RangeProbe* probe);
+    int launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io);
     int enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid); // a merged batch of images of different sizes: tables built on the fly
-    int launch(ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st);
-    int enqueue_image(const void* d_in, int w, int h, int c, void* d_out, hipStream_t st, int tile0 = 0, int tile1 = -1,
-                      hipEvent_t ev_half = nullptr, size_t* half_rows = nullptr, int in_fmt = RSR_FMT_U8_HWC, int out_fmt = RSR_FMT_U8_HWC);
-    // nimg images of one geometry as ONE tile batch (nimg <= kMaxMerge; whole images only when nimg > 1)
-    // plan_nimg >= nimg: the plan is the one of plan_nimg images and only the first nimg of them are launched (every width of a merged
-    // batch shares ONE plan: slots, tiles and work items of an image are contiguous, so a narrower batch is a prefix of the tables)
-    int enqueue_images(const void* const* d_in, void* const* d_out, int nimg, int w, int h, int c, hipStream_t st, int tile0 = 0, int tile1 = -1,
-                       hipEvent_t ev_half = nullptr, size_t* half_rows = nullptr, hipEvent_t ev_mid = nullptr, int plan_nimg = 0,
-                       int in_fmt = RSR_FMT_U8_HWC, int out_fmt = RSR_FMT_U8_HWC);
+    int launch(const ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st);
+    // The images of io -- all of io.w[0] x io.h[0] -- as ONE tile batch per workspace-full: tiles [tile0, tile1) of the tile grid
+    // (tile1 < 0: all; whole images only when io.nimg > 1).  io.ev_half with half_rows: the engine may split the 4x tail and reports
+    // the output rows that are complete at ev_half.
+    // plan_nimg: 0 = the call of one caller; else a merged batch whose plan is the one of plan_nimg >= io.nimg images, of which only the
+    // first io.nimg are launched (every width of a merged batch shares ONE plan: slots, tiles and work items of an image are
+    // contiguous, so a narrower batch is a prefix of the tables)
+    int enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size_t* half_rows, hipStream_t st);
+    // The one-tile batch of net_forward and selfcheck: its tables and the caller's planar fp16 [3][h][w] tile in device scratch
+    struct OneTile
+    {
+        Plan::Batch b;
+        ScratchBuf tab, tile;
+        int w = 0, h = 0;
+    };
+    int one_tile_upload(OneTile& t, const uint16_t* tile, int w, int h);
+    int one_tile_walk(const OneTile& t, const RangeProbe* probe); // workspace of the current storage mode, tile -> b_in, the network (never profiled)
     void mark_begin(hipStream_t st);
     void mark(int cls, double flops, double bytes, hipStream_t st, int conv_index = -1);
     void collect_profile(hipStream_t st);
