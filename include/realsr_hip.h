@@ -88,7 +88,7 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
 
 /* Pixel formats of device-resident images (no reference counterpart: the reference's images are uint8 HWC only). */
 #define RSR_FMT_U8_HWC 0  /* what rsr_process_device takes: uint8 [h][w][c], c in {3,4} */
-#define RSR_FMT_F16_CHW 1 /* planar fp16 [3][h][w], values in [0,1], tightly packed; c must be 3 */
+#define RSR_FMT_F16_CHW 1 /* planar fp16 [3][h][w], values in [0,1]; c must be 3 (tightly packed unless described by an rsr_image) */
 #define RSR_FMT_F32_CHW 2 /* planar fp32 [3][h][w], likewise */
 
 /* rsr_process_device with a pixel format per side: what a tensor pipeline holds (float CHW in [0,1]) goes in and comes out without a
@@ -103,8 +103,46 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
  *            (option "precise").  F32 receives min(max(r, 0), 1); F16 that value rounded once to fp16 (lossless in the default
  *            non-TTA mode).  Quantising it with floor(v * 255 + 0.5) reproduces the uint8 path's byte.
  *   Option "bgr" swaps planes 0 and 2 the way it swaps bytes 0 and 2 of a uint8 pixel.
- * Out of scope: RGBA in planar form, row pitches / strides, and a host-pointer variant (rsr_process stays uint8 HWC). */
+ * This is rsr_process_device_batch (below) with n = 1 and tightly packed images.
+ * Out of scope: RGBA in planar form and a host-pointer variant (rsr_process stays uint8 HWC). */
 int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, int h, int c, void* d_out, int out_fmt, void* stream);
+
+/* A device image behind its own pointer and pitches: a whole tensor, a crop of a larger frame, a frame inside a padded decoder surface, a
+ * window of a canvas.  Pitches are in BYTES.  A uint8 row pitch need not be a multiple of the pixel size; for the planar formats both
+ * pitches and `data` must be multiples of the element size (2 / 4).  No further alignment is asked of `data`. */
+typedef struct rsr_image
+{
+    void* data;            /* device pointer to element (0,0) [of plane 0] */
+    long long row_pitch;   /* bytes from one row to the next; 0 = tightly packed */
+    long long plane_pitch; /* planar formats: bytes from one plane to the next; 0 = h * row pitch.  Ignored for uint8 HWC */
+} rsr_image;
+
+/* n images of ONE geometry (w x h x c, in_fmt -> out_fmt), each with its own pointer and pitches: what a tensor pipeline holds as an
+ * (N, 3, H, W) batch, or as views into larger tensors.  Image i receives exactly the bytes rsr_process_device_fmt(in[i] -> out[i]) writes
+ * for the same pixels in the context's current mode (default, TTA, "precise", "bgr"; uint8 with c 3 or 4, planar with c == 3); out[i]
+ * describes the 4w x 4h result and no byte outside that window is touched.
+ *   Batching.  The images are cut into groups of as many as one merged tile batch of this geometry takes (option "merge": up to 16 small
+ *            images; 1 for a frame that fills the chip by itself, for "merge" = 1 and while profiling is on); every group walks the
+ *            network as ONE tile batch, on the plan and workspace the merged host calls of that geometry use -- 16 images of 256 x 256
+ *            share 352 launches instead of paying for them 16 times.  n has no upper bound.  n == 1 with packed descriptors enqueues what
+ *            rsr_process_device_fmt enqueues.  Stats "batch_calls", "batch_images", "batch_groups".
+ *   Stream.  The contract of rsr_process_device: NULL = synchronous on the context's stream; otherwise asynchronous, on `stream` itself
+ *            when the context is idle (stat "device_direct"), else on the compute stream ordered around `stream` by events.  No host
+ *            waits inside an asynchronous call.  The call forms its own batches: it is never merged with concurrent calls and is safe
+ *            next to calls of every kind.
+ *   Errors.  All arguments are checked before anything is launched (RSR_E_ARG): n < 1, a null array or data pointer, an unknown format, a
+ *            planar format with c != 3, a negative pitch, a row pitch below the bytes of a row (or beyond 2^31 - 1), for planar formats a
+ *            pitch or data pointer that is not a multiple of the element size.  When a later group fails (RSR_E_NOMEM, say) the call
+ *            returns that error; the groups already enqueued complete.
+ *   Overlap between outputs, or between an output and an input, is the caller's responsibility: nothing here looks for it.
+ *   Progress callback: one call per tile, tiles_total = the tiles of all n images.
+ * Out of scope: images of different sizes in one call, RGBA in planar form, host pointers (rsr_process_many). */
+int rsr_process_device_batch(rsr_ctx* ctx, int n, const rsr_image* in, int in_fmt, int w, int h, int c,
+                             const rsr_image* out, int out_fmt, void* stream);
+
+/* Host-only: bytes from `data` to one past the last byte a w x h x c image in `fmt` with these pitches touches (0 = packed, as above: then
+ * rsr_image_bytes), or RSR_E_ARG for a combination rsr_process_device_batch refuses. */
+long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch);
 
 /* Host-only: bytes of a w x h x c image in `fmt` (a negative RSR_E_ARG for a bad combination: unknown format, planar with c != 3,
  * uint8 with c not in {3,4}, w or h < 1). */
@@ -360,7 +398,8 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *   "plan_items_lr" / "plan_items_2x" / "plan_items_4x"  work items (16 x 32 pixel blocks) of that plan per resolution level and image: what the
  *                       conv launches of a frame actually walk (blocks that only feed cropped pixels are left out, narrow last columns folded)
  *   "merged_batches" / "merged_images" / "merged_widest" / "merged_mixed"  tile batches that merged small images of concurrent calls, the
- *                       images they carried, the widest one, those whose images differed in size; "device_direct": rsr_process_device[_fmt] calls that ran on the caller's own stream
+ *                       images they carried, the widest one, those whose images differed in size; "device_direct": rsr_process_device[_fmt | _batch] calls that ran on the caller's own stream
+ *   "batch_calls" / "batch_images" / "batch_groups"  rsr_process_device_batch calls, the images they enqueued and the tile batches those went in (the merged_* stats count the cross-call combiner alone)
  *   "workspace_mb"      device memory the workspace holds, "ws_clamp_mb" the bound a failed allocation left behind (-1 = none)
  *   "lanes", "lane_in_mb", "lane_out_mb"   rsr_process lanes created so far and the device image buffers they hold (a member of
  *                       rsr_process_group allocates only the output rows of its tile range)

@@ -29,6 +29,7 @@ EXPORTS = [
     "rsr_net_forward_f32", "rsr_conv3x3_res_precise", "rsr_process_many",
     "rsr_selfcheck", "rsr_selfcheck_tile", "rsr_selfcheck_ranges",
     "rsr_process_device_fmt", "rsr_image_bytes",
+    "rsr_process_device_batch", "rsr_image_span",
 ]
 
 NUM_CONVS = 351
@@ -50,6 +51,11 @@ class SelfcheckReport(C.Structure):
                 ("max_byte_diff", C.c_int), ("bytes_differ", C.c_longlong), ("peak_abs", C.c_float), ("peak_conv", C.c_int),
                 ("nonfinite", C.c_longlong), ("fp16_overflow", C.c_int), ("recommend_precise", C.c_int),
                 ("elapsed_ms", C.c_float)]
+
+
+class Image(C.Structure):
+    """rsr_image: a device image behind its own pointer, row pitch and plane pitch (bytes; 0 = tightly packed)."""
+    _fields_ = [("data", C.c_void_p), ("row_pitch", C.c_longlong), ("plane_pitch", C.c_longlong)]
 
 
 class RealSRError(RuntimeError):
@@ -99,6 +105,9 @@ def lib():
     L.rsr_process_device_fmt.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, vp]
     L.rsr_image_bytes.argtypes = [ip, ip, ip, ip]
     L.rsr_image_bytes.restype = C.c_longlong
+    L.rsr_process_device_batch.argtypes = [vp, ip, C.POINTER(Image), ip, ip, ip, ip, C.POINTER(Image), ip, vp]
+    L.rsr_image_span.argtypes = [ip, ip, ip, ip, C.c_longlong, C.c_longlong]
+    L.rsr_image_span.restype = C.c_longlong
     L.rsr_model_pack.argtypes = [cp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_device_memory.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rsr_host_alloc.argtypes = [C.c_size_t]
@@ -296,6 +305,15 @@ class RealSR:
         self._ck(self._L.rsr_process_device_fmt(self._h, C.c_void_p(int(d_in)), int(in_fmt), w, h, c, C.c_void_p(int(d_out)), int(out_fmt),
                                                 C.c_void_p(int(stream)) if stream else None))
 
+    def process_device_batch(self, ins, in_fmt, w, h, c, outs, out_fmt, stream=None):
+        """rsr_process_device_batch: len(ins) images of one geometry as merged tile batches.  An entry of ins / outs is an integer device
+        pointer (tightly packed) or (ptr, row_pitch, plane_pitch) in bytes, 0 = packed; sizes: image_span()."""
+        if len(ins) != len(outs):
+            raise ValueError("process_device_batch: %d inputs for %d outputs" % (len(ins), len(outs)))
+        self._push_params()
+        self._ck(self._L.rsr_process_device_batch(self._h, len(ins), _images(ins), int(in_fmt), w, h, c, _images(outs), int(out_fmt),
+                                                  C.c_void_p(int(stream)) if stream else None))
+
     def process_rows(self, img, out, row0, row1):
         """Tile rows [row0, row1) of img's tile grid into the full-size `out` (see rsr_process_rows)."""
         h, w, c = img.shape
@@ -458,6 +476,23 @@ def selfcheck_tile(w=0, h=0):
 def image_bytes(fmt, w, h, c=3):
     """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*)."""
     n = lib().rsr_image_bytes(int(fmt), int(w), int(h), int(c))
+    if n < 0:
+        raise RealSRError(int(n), lib().rsr_last_error(None).decode())
+    return int(n)
+
+
+def _images(entries):
+    """A ctypes array of rsr_image from pointers or (ptr, row_pitch, plane_pitch) tuples."""
+    arr = (Image * max(len(entries), 1))()
+    for a, e in zip(arr, entries):
+        ptr, row, plane = e if isinstance(e, (tuple, list)) else (e, 0, 0)
+        a.data, a.row_pitch, a.plane_pitch = int(ptr), int(row), int(plane)
+    return arr
+
+
+def image_span(fmt, w, h, c=3, row_pitch=0, plane_pitch=0):
+    """rsr_image_span (host-only): bytes from the data pointer to one past the last byte of a w x h x c image with these pitches."""
+    n = lib().rsr_image_span(int(fmt), int(w), int(h), int(c), int(row_pitch), int(plane_pitch))
     if n < 0:
         raise RealSRError(int(n), lib().rsr_last_error(None).decode())
     return int(n)

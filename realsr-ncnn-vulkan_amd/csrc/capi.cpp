@@ -183,6 +183,28 @@ int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, in
     return ctx->e.process_device(d_in, w, h, c, d_out, static_cast<hipStream_t>(stream), stream == nullptr, in_fmt, out_fmt);
 }
 
+int rsr_process_device_batch(rsr_ctx* ctx, int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    try
+    {
+        return ctx->e.process_device_batch(n, in, in_fmt, w, h, c, out, out_fmt, static_cast<hipStream_t>(stream), stream == nullptr);
+    }
+    catch (const std::bad_alloc&) // (the per-image layout table) -- nothing crosses extern "C"
+    {
+        return Engine::fail(RSR_E_NOMEM, "rsr_process_device_batch: out of host memory");
+    }
+}
+
+long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch)
+{
+    long long row = 0, plane = 0;
+    const int rc = rsr::image_layout(fmt, w, h, c, row_pitch, plane_pitch, &row, &plane);
+    if (rc != RSR_OK) return rc;
+    // all pitches are positive: the last element of the last row of the last plane lies farthest from `data`
+    return (fmt == RSR_FMT_U8_HWC ? 0 : 2 * plane) + (long long)(h - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
+}
+
 long long rsr_image_bytes(int fmt, int w, int h, int c)
 {
     if (w < 1 || h < 1) return Engine::fail(RSR_E_ARG, "bad image size");
@@ -485,6 +507,9 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "lane_in_mb") *value = lanes_bytes(false) / 1048576.0;
     else if (k == "last_test_us") *value = e.last_test_us;
     else if (k == "device_direct") *value = double(e.device_direct);
+    else if (k == "batch_calls") *value = double(e.batch_calls);
+    else if (k == "batch_images") *value = double(e.batch_images);
+    else if (k == "batch_groups") *value = double(e.batch_groups);
     else if (k == "merged_batches") *value = double(e.merged_batches.load());
     else if (k == "merged_images") *value = double(e.merged_images.load());
     else if (k == "merged_widest") *value = double(e.merged_widest.load());

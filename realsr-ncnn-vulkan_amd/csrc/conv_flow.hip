@@ -629,14 +629,15 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
         if (a.out_u8)
         {
             const int ox = it.pad0 + x, ow = pad2_w(it.pad2), oh = pad2_h(it.pad2);
-            const int oim = pad2_img(it.pad2); // (a merged batch: the tile's own image and its row pitch)
+            const int oim = pad2_img(it.pad2); // (a merged batch: the tile's own image and its row pitch, in bytes)
             uint8_t* const oimg = a.out_u8s[oim];
-            const int opitch = a.out_u8_ws[oim];
+            const int opitch = a.out_pitch[oim];
             if constexpr (FIMG)
             {
-                // planar fp16 / fp32 image [3][rows][opitch]: the value the uint8 conversion below sees, clamped to [0, 1] (fp16: rounded
-                // once -- a no-op unless OUT32).  Lanes run along x: a wave stores 32 contiguous elements per channel row.
-                const long long cstep = (long long)a.out_plane_rows[oim] * opitch;
+                // planar fp16 / fp32 image, rows opitch and planes cstep BYTES apart: the value the uint8 conversion below sees, clamped to
+                // [0, 1] (fp16: rounded once -- a no-op unless OUT32).  Lanes run along x: a wave stores 32 contiguous elements per channel row.
+                const long long cstep = a.out_plane[oim];
+                const int esh = a.out_fmt == kFmtF32 ? 2 : 1; // log2 of the element size
 #pragma unroll
                 for (int rr = 0; rr < 4; rr++)
                 {
@@ -644,15 +645,15 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
                     const int rx = x - a.out_u8_crop, ry = y - a.out_u8_crop;
                     if (rx >= 0 && rx < ow && ry >= 0 && ry < oh)
                     {
-                        const long long pix = (long long)(it.pad1 + y) * opitch + ox;
+                        const long long pix = (long long)(it.pad1 + y) * opitch + ((long long)ox << esh);
 #pragma unroll
                         for (int ch = 0; ch < 3; ch++)
                         {
                             float v = OUT32 ? val[rr][ch] : (float)(_Float16)val[rr][ch];
                             v = fminf(fmaxf(v, 0.f), 1.f);
-                            const long long e = (a.out_u8_bgr ? 2 - ch : ch) * cstep + pix;
-                            if (a.out_fmt == kFmtF32) reinterpret_cast<float*>(oimg)[e] = v;
-                            else reinterpret_cast<_Float16*>(oimg)[e] = (_Float16)v;
+                            uint8_t* const e = oimg + (a.out_u8_bgr ? 2 - ch : ch) * cstep + pix;
+                            if (a.out_fmt == kFmtF32) *reinterpret_cast<float*>(e) = v;
+                            else *reinterpret_cast<_Float16*>(e) = (_Float16)v;
                         }
                     }
                 }
@@ -666,7 +667,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
                 const int rx = x - a.out_u8_crop, ry = y - a.out_u8_crop;
                 if (rx >= 0 && rx < ow && ry >= 0 && ry < oh)
                 {
-                    uint8_t* o = oimg + ((long long)(it.pad1 + y) * opitch + ox) * 3;
+                    uint8_t* o = oimg + (long long)(it.pad1 + y) * opitch + ox * 3;
 #pragma unroll
                     for (int ch = 0; ch < 3; ch++)
                     {

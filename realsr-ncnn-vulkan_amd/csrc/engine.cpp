@@ -892,16 +892,16 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
             a.src0 = hr; a.n0 = P64;
             if (fused)
             { // non-TTA RGB with conv3x3_flow: conv_last applies realsr_postproc.comp itself and writes the image(s): uint8 HWC, or --
-              // out_fmt -- planar fp16 / fp32 of out_plane_rows[i] rows
+              // out_fmt -- planar fp16 / fp32, through each image's row and plane pitch
                 for (int i = 0; i < io->nimg && i < kMaxMerge; i++)
                 {
                     a.out_u8s[i] = static_cast<uint8_t*>(io->out[i]);
-                    a.out_u8_ws[i] = io->w[i] * scale;
-                    a.out_plane_rows[i] = io->h[i] * scale; // (the planar formats come with whole images only: process_device)
+                    a.out_pitch[i] = int(io->out_pitch[i]);
+                    a.out_plane[i] = io->out_plane[i];
                 }
                 a.out_u8 = a.out_u8s[0];
                 a.out_fmt = io->out_fmt;
-                a.out_u8_w = a.out_u8_ws[0];
+                a.out_u8_w = io->w[0] * scale;
                 a.out_u8_crop = prepadding * scale;
                 a.out_u8_bgr = bgr ? 1 : 0;
             }
@@ -1041,11 +1041,13 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     for (int i = 0; i < io.nimg; i++)
     {
         pa.imgs[i] = po.in_imgs[i] = static_cast<const uint8_t*>(io.in[i]);
-        pa.ws[i] = po.in_ws[i] = io.w[i];
+        pa.ws[i] = io.w[i];
         pa.hs[i] = io.h[i];
+        pa.pitch[i] = po.in_pitch[i] = int(io.in_pitch[i]);
+        pa.plane[i] = io.in_plane[i];
         po.outs[i] = static_cast<uint8_t*>(io.out[i]);
-        po.out_ws[i] = io.w[i] * scale;
-        po.out_hs[i] = io.h[i] * scale; // (the planar formats come with whole images only: process_device)
+        po.out_pitch[i] = int(io.out_pitch[i]);
+        po.out_plane[i] = io.out_plane[i];
     }
     pa.nimgs = io.nimg;
     pa.fmt = io.in_fmt;
@@ -1229,6 +1231,127 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
         if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
     }
     return RSR_OK;
+}
+
+// ---- tensor batches: n images of one geometry behind descriptors (include/realsr_hip.h rsr_process_device_batch) ------------------
+int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane)
+{
+    if (w < 1 || h < 1) return Engine::fail(RSR_E_ARG, "bad image size");
+    if (fmt != RSR_FMT_U8_HWC && fmt != RSR_FMT_F16_CHW && fmt != RSR_FMT_F32_CHW) return Engine::fail(RSR_E_ARG, "unknown pixel format");
+    if (fmt == RSR_FMT_U8_HWC ? (c != 3 && c != 4) : c != 3) return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
+    if (row_pitch < 0 || plane_pitch < 0) return Engine::fail(RSR_E_ARG, "negative pitch");
+    const long long es = BatchIO::px_bytes(fmt, c), packed = w * es;
+    const long long rp = row_pitch ? row_pitch : packed;
+    if (rp < packed) return Engine::fail(RSR_E_ARG, "row pitch below the bytes of a row");
+    if (rp > 0x7fffffffll) return Engine::fail(RSR_E_ARG, "row pitch beyond 2^31 - 1 bytes");
+    long long pp = 0;
+    if (fmt != RSR_FMT_U8_HWC)
+    {
+        pp = plane_pitch ? plane_pitch : h * rp;
+        if (rp % es || pp % es) return Engine::fail(RSR_E_ARG, "pitch is not a multiple of the element size");
+    }
+    *row = rp;
+    *plane = pp;
+    return RSR_OK;
+}
+
+int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream,
+                                 bool sync)
+{
+    // everything is checked before anything is launched
+    if (n < 1 || !in || !out) return fail(RSR_E_ARG, "bad image arguments");
+    long long irow = 0, iplane = 0, orow = 0, oplane = 0;
+    std::vector<long long> lay(size_t(n) * 4);
+    for (int i = 0; i < n; i++)
+    {
+        if (!in[i].data || !out[i].data) return fail(RSR_E_ARG, "image " + std::to_string(i) + ": null data pointer");
+        int rc = image_layout(in_fmt, w, h, c, in[i].row_pitch, in[i].plane_pitch, &irow, &iplane);
+        if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
+        if (rc == RSR_OK) rc = image_layout(out_fmt, w * 4, h * 4, c, out[i].row_pitch, out[i].plane_pitch, &orow, &oplane);
+        if (rc != RSR_OK) return rc;
+        if (reinterpret_cast<uintptr_t>(in[i].data) % uintptr_t(in_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(in_fmt, c)) ||
+            reinterpret_cast<uintptr_t>(out[i].data) % uintptr_t(out_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(out_fmt, c)))
+            return fail(RSR_E_ARG, "image " + std::to_string(i) + ": data is not aligned to the element size");
+        lay[size_t(i) * 4] = irow, lay[size_t(i) * 4 + 1] = iplane, lay[size_t(i) * 4 + 2] = orow, lay[size_t(i) * 4 + 3] = oplane;
+    }
+    hipEvent_t done = nullptr;
+    int rc = RSR_OK;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!loaded) return fail(RSR_E_STATE, "process before load");
+        if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
+        HIP_TRY(hipSetDevice(device));
+        // As in process_device: an idle engine runs the call on the caller's own stream, a busy one on the compute stream between two events.
+        const bool direct = user_stream && hipStreamQuery(stream) == hipSuccess;
+        (void)hipGetLastError(); // (hipErrorNotReady is not an error)
+        hipStream_t st = direct ? user_stream : stream;
+        if (user_stream && !direct)
+        {
+            hipEvent_t e = take_event();
+            if (!e) return fail(RSR_E_DEVICE, "hipEventCreate failed");
+            HIP_TRY(hipEventRecord(e, user_stream));
+            HIP_TRY(hipStreamWaitEvent(stream, e, 0));
+            give_event(e);
+        }
+        // Groups of merge_width images, each ONE tile batch in (a prefix of) the merged plan of this geometry -- the plan and the workspace
+        // the merged host calls of that geometry use.  Width 1 (a large frame, "merge" 1, profiling): every image a batch of its own.
+        const int width = merge_width(w, h, c);
+        const int tiles_per_image = ((w + tilesize - 1) / tilesize) * ((h + tilesize - 1) / tilesize);
+        int enqueued = 0;
+        for (int g0 = 0; g0 < n && rc == RSR_OK; g0 += width)
+        {
+            const int k = std::min(width, n - g0);
+            BatchIO io(k, c, in_fmt, out_fmt);
+            for (int i = 0; i < k; i++)
+            {
+                const long long* l = &lay[size_t(g0 + i) * 4];
+                io.set(i, in[g0 + i].data, out[g0 + i].data, w, h);
+                io.in_pitch[i] = l[0], io.in_plane[i] = l[1], io.out_pitch[i] = l[2], io.out_plane[i] = l[3];
+            }
+            // (n == 1: plan_nimg 0, the very call process_device makes; otherwise the progress of all n images is reported here)
+            rc = enqueue_images(io, 0, -1, n == 1 ? 0 : width, nullptr, st);
+            if (rc != RSR_OK) break;
+            enqueued += k;
+            batch_groups++;
+            if (progress && n > 1)
+                for (int i = 1; i <= k * tiles_per_image; i++) progress(g0 * tiles_per_image + i, n * tiles_per_image, progress_user);
+        }
+        batch_calls++;
+        batch_images += enqueued;
+        // A later group that failed leaves the earlier ones enqueued: they complete, and the streams are ordered around them all the same.
+        if (direct)
+        { // whatever the compute stream gets next uses the same workspace: it waits for this call's last kernel
+            hipEvent_t e = take_event();
+            if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
+            {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(user_stream);
+            }
+            give_event(e);
+            if (rc == RSR_OK) device_direct++;
+            return rc;
+        }
+        if (enqueued && (user_stream || sync))
+        {
+            done = take_event();
+            if (!done) return fail(RSR_E_DEVICE, "hipEventCreate failed");
+            HIP_TRY(hipEventRecord(done, stream));
+            if (user_stream)
+            {
+                HIP_TRY(hipStreamWaitEvent(user_stream, done, 0));
+                give_event(done);
+                done = nullptr;
+            }
+        }
+    }
+    if (done)
+    { // wait outside the lock: other calls may enqueue behind this one meanwhile
+        const hipError_t e = hipEventSynchronize(done);
+        std::lock_guard<std::mutex> lk(mu);
+        give_event(done);
+        if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
+    }
+    return rc;
 }
 
 // ---- merging small images across calls (engine.h) ---------------------------------------------

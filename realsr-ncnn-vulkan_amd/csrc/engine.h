@@ -142,6 +142,9 @@ struct BatchIO
     const void* in[kMaxMerge];  // per image: the device image, in_fmt, w[i] x h[i] ...
     void* out[kMaxMerge];       // ... and its 4w[i] x 4h[i] result, out_fmt
     int w[kMaxMerge], h[kMaxMerge];
+    // Bytes from one row / one plane (planar formats) of an image to the next, resolved (never 0; rsr_image of the C ABI, image_layout).
+    // The constructors set the tightly packed values; Engine::process_device_batch overwrites them with the caller's.
+    long long in_pitch[kMaxMerge], in_plane[kMaxMerge], out_pitch[kMaxMerge], out_plane[kMaxMerge];
     int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float formats come with whole images of c == 3 only)
     int out_row0 = 0;           // `out` points at this output row of the x4 image (a tile range's device buffer holds only its rows)
     int split_slot = 0;         // > 0: the 4x tail is split in front of this slot and ...
@@ -149,11 +152,19 @@ struct BatchIO
     hipEvent_t ev_mid = nullptr;  // recorded behind the middle RDB (a merged batch's throttle event, Engine::submit_merged)
     BatchIO(const void* d_in, void* d_out, int w0, int h0, int c0, int in_fmt0, int out_fmt0) : nimg(1), c(c0), in_fmt(in_fmt0), out_fmt(out_fmt0)
     {
-        in[0] = d_in, out[0] = d_out, w[0] = w0, h[0] = h0;
+        set(0, d_in, d_out, w0, h0);
     }
     BatchIO(MergeReq* const* g, int n) : nimg(n), c(g[0]->c) // the uint8 images of merged calls
     {
-        for (int i = 0; i < n; i++) in[i] = g[i]->d_in, out[i] = g[i]->d_out, w[i] = g[i]->w, h[i] = g[i]->h;
+        for (int i = 0; i < n; i++) set(i, g[i]->d_in, g[i]->d_out, g[i]->w, g[i]->h);
+    }
+    BatchIO(int n, int c0, int in_fmt0, int out_fmt0) : nimg(n), c(c0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
+    static long long px_bytes(int fmt, int c) { return fmt == RSR_FMT_F16_CHW ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : c); } // of one element of a row
+    void set(int i, const void* d_in, void* d_out, int wi, int hi) // image i, tightly packed (the output is x4: Engine::scale is checked to be 4)
+    {
+        in[i] = d_in, out[i] = d_out, w[i] = wi, h[i] = hi;
+        in_pitch[i] = wi * px_bytes(in_fmt, c), in_plane[i] = hi * in_pitch[i];
+        out_pitch[i] = 4 * wi * px_bytes(out_fmt, c), out_plane[i] = 4 * hi * out_pitch[i];
     }
 };
 
@@ -250,6 +261,7 @@ struct Engine
     std::atomic<long long> merged_batches{0}, merged_images{0}, merged_widest{0}; // stats
     std::atomic<int> merge_inbound{0}; // calls with a small image that are on their way to submit_merged (uploading): a leader waits a moment for them
     long long device_direct = 0; // rsr_process_device calls that ran on the caller's own stream (the engine was idle), under mu
+    long long batch_calls = 0, batch_images = 0, batch_groups = 0; // rsr_process_device_batch: calls, their images, the tile batches they enqueued; under mu
     std::atomic<bool> merge_mixed{true}; // option "merge_mixed": a merged batch may hold images of different sizes (0: of one geometry only)
     DevBuf mix_tab[3];               // rotating device tables of such batches
     hipEvent_t mix_ev[3] = {nullptr, nullptr, nullptr};
@@ -289,6 +301,9 @@ struct Engine
     // in_fmt / out_fmt: RSR_FMT_* of the two images (the planar float formats need c == 3; such a call is never merged with others)
     int process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync, int in_fmt = RSR_FMT_U8_HWC,
                        int out_fmt = RSR_FMT_U8_HWC);
+    // n images of one geometry, each behind its own descriptor (pointer, row pitch, plane pitch), in groups of merge_width(w, h, c) images:
+    // every group ONE tile batch on the cached merged plan (include/realsr_hip.h rsr_process_device_batch).  Stream contract of process_device.
+    int process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream, bool sync);
     // tile0/tile1: tiles [tile0, tile1) of the row-major tile grid only (tile1 < 0: all); `out` is always the full (4w x 4h x c) image,
     // only the output rectangles of
     // those tiles are written
@@ -347,6 +362,9 @@ struct Engine
     static int fail(int code, const std::string& msg);
 };
 
+// Host-only: the resolved row and plane pitch (bytes) of a w x h x c image in `fmt` described with row_pitch / plane_pitch (0 = tightly
+// packed), or RSR_E_ARG (through Engine::fail) for a combination rsr_process_device_batch refuses.  plane = 0 for uint8 HWC.
+int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane);
 void selfcheck_tile(uint16_t* dst, int w, int h); // host-only: the built-in tile of the self-check, planar fp16 [3][h][w]
 const char* last_error(); // message of the calling thread's last failure
 long long share_pool_stat(int what); // group.cpp: 0 = worker threads of rsr_process_group's pool, 1 = shares run inline because no worker could be started

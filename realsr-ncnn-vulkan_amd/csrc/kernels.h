@@ -33,9 +33,13 @@ constexpr int kFoldMaxW = 14; // strip = left halo + <= 14 pixels + right halo =
 // them.  Every image keeps its own device buffers: the kernels that touch images get the pointers by value and the tile's image index.
 constexpr int kMaxMerge = 16;
 
-// Pixel formats of the caller's images (the RSR_FMT_* values of include/realsr_hip.h).  The planar formats are RGB only, tightly packed
-// [3][h][w], values in [0, 1]; they ride in the same pointer arrays as the uint8 images (PreArgs::imgs, PostArgs::outs, ConvArgs::out_u8s).
+// Pixel formats of the caller's images (the RSR_FMT_* values of include/realsr_hip.h).  The planar formats are RGB only, [3][h][w],
+// values in [0, 1]; they ride in the same pointer arrays as the uint8 images (PreArgs::imgs, PostArgs::outs, ConvArgs::out_u8s).
 constexpr int kFmtU8 = 0, kFmtF16 = 1, kFmtF32 = 2;
+// Every image is addressed through its own ROW PITCH and (planar formats) PLANE PITCH, both in BYTES (rsr_image of the C ABI): a crop of
+// a larger frame, a window of a canvas.  A uint8 pitch need not be a multiple of the pixel size and a base pointer is aligned to the
+// element only, so the image accesses are element-sized (the LDS-staged pre / post kernels, which move dwords, align by themselves or
+// are not chosen: launch_*_tiles).  Planar pitches are multiples of the element size.  Row pitches fit an int (the engine checks).
 
 struct WorkItem // 32 bytes: one aligned 2 x 16-byte fetch gives a workgroup everything about its block
 {
@@ -92,8 +96,8 @@ struct ConvArgs
     // conv_last: planar fp16 [3][H][W] per slot
     void* out_planar3;
     long long planar3_slot_stride; // bytes
-    // conv_last fused with realsr_postproc.comp (non-TTA RGB, conv3x3_flow): uint8 HWC image, row pitch out_u8_w pixels; the
-    // work items of the launch carry the tile's placement (WorkItem::pad0..2, see engine.cpp make_items)
+    // conv_last fused with realsr_postproc.comp (non-TTA RGB, conv3x3_flow): uint8 HWC image, out_u8_w pixels wide (row pitch:
+    // out_pitch below); the work items of the launch carry the tile's placement (WorkItem::pad0..2, see engine.cpp make_items)
     uint8_t* out_u8;
     int out_u8_w, out_u8_crop, out_u8_bgr; // crop = prepadding * scale; bgr: channel 0 <-> 2 on store
     // work
@@ -117,14 +121,14 @@ struct ConvArgs
     long long lo1_off;    // lo planes of res1 = res1 + lo1_off bytes
     long long lo2_off;    // lo planes of res2
     long long out_lo_off; // lo planes of the output = out16 + out_lo_off (0: not kept)
-    // fused conv_last: the uint8 image of every image of a (merged) batch and its row pitch in pixels (the images of a merged batch may
+    // fused conv_last: the uint8 image of every image of a (merged) batch and its row pitch in BYTES (the images of a merged batch may
     // differ in size); out_u8 == out_u8s[0] doubles as the mode flag
     uint8_t* out_u8s[kMaxMerge];
-    int out_u8_ws[kMaxMerge];
-    // ... or, out_fmt != kFmtU8, planar fp16 / fp32 [3][out_plane_rows][out_u8_ws[i]] images behind the same pointers: min(max(r, 0), 1) of the
-    // value r the uint8 conversion sees (fp16: that rounded once), plane = 2 - ch under out_u8_bgr
+    int out_pitch[kMaxMerge];
+    // ... or, out_fmt != kFmtU8, planar fp16 / fp32 images behind the same pointers, their planes out_plane[i] BYTES apart: min(max(r, 0), 1)
+    // of the value r the uint8 conversion sees (fp16: that rounded once), plane = 2 - ch under out_u8_bgr
     int out_fmt;
-    int out_plane_rows[kMaxMerge];
+    long long out_plane[kMaxMerge];
 };
 
 // conv_flow.hip: half-stage ring on 16-channel planes.  flags: 1 = two n-tiles per MFMA wave for 64-cout convs, 2 = no deferred epilogue,
@@ -151,6 +155,8 @@ struct PreArgs
     const uint8_t* imgs[kMaxMerge]; // HWC u8, one per image of the batch (ws[i] x hs[i] x c); BaseTile::img selects
     int fmt;                        // kFmtU8, or kFmtF16 / kFmtF32: the images are planar [3][hs[i]][ws[i]] of that type (c == 3)
     int ws[kMaxMerge], hs[kMaxMerge];
+    int pitch[kMaxMerge];           // bytes from one row of image i to the next (>= ws[i] * pixel size) ...
+    long long plane[kMaxMerge];     // ... and, planar formats, from one plane to the next
     int nimgs;
     int c;
     const BaseTile* tiles;
@@ -174,10 +180,10 @@ struct PostArgs
     int tta;
     int crop;   // prepadding*scale
     uint8_t* outs[kMaxMerge]; // HWC u8 (4w x 4h x c), one per image of the batch
-    int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][out_hs[i]][out_ws[i]] of that type (c == 3; see ConvArgs::out_fmt)
-    int out_hs[kMaxMerge];    // rows of the buffers behind `outs` (planar formats: the plane stride is out_hs[i] * out_ws[i] elements)
-    int out_ws[kMaxMerge];    // their row pitches in pixels (4w)
-    int in_ws[kMaxMerge];     // ... and those of the source images (w)
+    int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][4h][4w] of that type (c == 3; see ConvArgs::out_fmt)
+    long long out_plane[kMaxMerge]; // planar formats: bytes from one plane of `outs[i]` to the next
+    int out_pitch[kMaxMerge]; // row pitches of the outs in bytes
+    int in_pitch[kMaxMerge];  // ... and those of the source images
     int nimgs;
     int c;
     int out_row0; // the outs point at output row out_row0 of the x4 image (a tile range's device buffer holds only its rows)

@@ -39,7 +39,8 @@ __device__ __forceinline__ int reflect101(int v, int n)
 // reflecting against the band equals reflecting against the image (engine.cpp explains why).
 // SRC: what the caller's image is made of -- uint8_t (HWC), or _Float16 / float: planar [3][ih][iw] in [0, 1].  A half IS the network
 // input (the uint8 path makes fp16(float(k) * (1/255.f)) of byte k: those halfs give that path's input exactly); a float is rounded to
-// fp16, to nearest even.  Lanes run along x: the three plane reads of a wave are contiguous.
+// fp16, to nearest even.  Lanes run along x: the three plane reads of a wave are contiguous.  Rows are PreArgs::pitch bytes apart, planes
+// PreArgs::plane: the reflected (x, y) is an index into the image, never into the surface around it.
 template <typename SRC>
 __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
 {
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     for (int e = 0; e < 8; e++) v0[e] = (_Float16)0.f;
     if constexpr (sizeof(SRC) == 1)
     {
-        const uint8_t* p = a.imgs[im] + ((long long)y * iw + x) * a.c;
+        const uint8_t* p = a.imgs[im] + (long long)y * a.pitch[im] + x * a.c;
         const float norm_val = 1 / 255.f;
         v0[0] = (_Float16)((float)p[i0] * norm_val);
         v0[1] = (_Float16)((float)p[1] * norm_val);
@@ -64,11 +65,11 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     }
     else
     {
-        const long long cstep = (long long)iw * ih;
-        const SRC* p = reinterpret_cast<const SRC*>(a.imgs[im]) + (long long)y * iw + x;
-        v0[0] = (_Float16)p[i0 * cstep];
-        v0[1] = (_Float16)p[cstep];
-        v0[2] = (_Float16)p[i2 * cstep];
+        const long long cstep = a.plane[im]; // bytes, like the row pitch
+        const uint8_t* p = a.imgs[im] + (long long)y * a.pitch[im] + (long long)x * (int)sizeof(SRC);
+        v0[0] = (_Float16) * reinterpret_cast<const SRC*>(p + i0 * cstep);
+        v0[1] = (_Float16) * reinterpret_cast<const SRC*>(p + cstep);
+        v0[2] = (_Float16) * reinterpret_cast<const SRC*>(p + i2 * cstep);
     }
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
     const int nv = a.tta ? 8 : 1;
@@ -125,11 +126,12 @@ __global__ __launch_bounds__(256) void preproc_tiles_lds(const PreArgs a)
         lo = min(lo, __shfl_xor(lo, d));
         hi = max(hi, __shfl_xor(hi, d));
     }
-    const long long total = (long long)iw * ih * a.c;
+    const int pitch = a.pitch[im];
+    const long long total = (long long)(ih - 1) * pitch + (long long)iw * a.c; // one past the image's last byte
     for (int r = wave; r < ny; r += 4)
     {
         const int y = reflect101(gy0 + r + t.y_org, ih);
-        const long long b0 = ((long long)y * iw + lo) * a.c, b1 = ((long long)y * iw + hi + 1) * a.c;
+        const long long b0 = (long long)y * pitch + lo * a.c, b1 = (long long)y * pitch + (hi + 1) * a.c;
         const long long a0 = b0 & ~3ll;
         const int nd = int((b1 - a0 + 3) >> 2); // <= 33 dwords
         if (lane < nd)
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(256) void preproc_tiles_lds(const PreArgs a)
             uint32_t v;
             if (ad + 4 <= total) v = *reinterpret_cast<const uint32_t*>(img + ad);
             else
-            { // the last bytes of the image: never read past its end
+            { // the last bytes of the image: never read past its end (inside it, a dword may take in bytes of the row pitch's slack)
                 v = 0;
                 for (int e = 0; e < 4; e++)
                     if (ad + e < total) v |= (uint32_t)img[ad + e] << (8 * e);
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(256) void preproc_tiles_lds(const PreArgs a)
         {
             const int x = reflect101(gx0 + cx + t.x_org, iw);
             const int y = reflect101(gy0 + r + t.y_org, ih);
-            const int shift = int((((long long)y * iw + lo) * a.c) & 3);
+            const int shift = int(((long long)y * pitch + lo * a.c) & 3);
             const unsigned char* p = &raw[r][shift + (x - lo) * a.c];
             const _Float16 hr = (_Float16)((float)p[i0] * norm_val), hg = (_Float16)((float)p[1] * norm_val), hb = (_Float16)((float)p[i2] * norm_val);
             uint2 v;
@@ -204,7 +206,7 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
     // Measured (tools/prepost_perf.py, profiles/r04_prepost.txt): 0.042 ms LDS-staged vs 0.032 ms per-pixel on a 1080p frame, 0.145 vs
     // 0.150 ms with the 8 TTA scatters -- the byte loads of the plain kernel are served by the caches, its 32-byte stores are whole
     // sectors: staging buys nothing here.  Default = the plain kernel; variant 2 forces the staged one (tests, A/B).
-    bool aligned = true; // (the staged kernel reads the images in dwords)
+    bool aligned = true; // (the staged kernel reads the images in dwords, aligned down from any byte offset: only the base matters, not the pitch)
     for (int i = 0; i < a.nimgs; i++) aligned = aligned && !(reinterpret_cast<uintptr_t>(a.imgs[i]) & 3);
     if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8) // (the staged kernel knows uint8 sources only)
     {
@@ -228,13 +230,14 @@ __device__ __forceinline__ uint8_t post_store(float v)
 }
 
 // The planar float destinations (PostArgs::out_fmt): the value the uint8 conversion sees, clamped to [0, 1] -- so that
-// floor(v * 255 + 0.5) of it is post_store's byte -- as fp32, or rounded once to fp16.  o = element (y, x) of plane 0.
+// floor(v * 255 + 0.5) of it is post_store's byte -- as fp32, or rounded once to fp16.  o = element (y, x) of plane 0, the planes
+// `plane` bytes apart.
 template <typename TO>
-__device__ __forceinline__ void post_store_planar(TO* o, long long cstep, int bgr, const float (&v)[3])
+__device__ __forceinline__ void post_store_planar(uint8_t* o, long long plane, int bgr, const float (&v)[3])
 {
-    o[bgr ? 2 * cstep : 0] = (TO)fminf(fmaxf(v[0], 0.f), 1.f);
-    o[cstep] = (TO)fminf(fmaxf(v[1], 0.f), 1.f);
-    o[bgr ? 0 : 2 * cstep] = (TO)fminf(fmaxf(v[2], 0.f), 1.f);
+    *reinterpret_cast<TO*>(o + (bgr ? 2 * plane : 0)) = (TO)fminf(fmaxf(v[0], 0.f), 1.f);
+    *reinterpret_cast<TO*>(o + plane) = (TO)fminf(fmaxf(v[1], 0.f), 1.f);
+    *reinterpret_cast<TO*>(o + (bgr ? 0 : 2 * plane)) = (TO)fminf(fmaxf(v[2], 0.f), 1.f);
 }
 
 // ncnn Interp bicubic coefficients (alpha channel only; realsr.cpp:128-140)
@@ -301,11 +304,11 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
     }
     if constexpr (sizeof(TO) != 1)
     {
-        const long long pix = (long long)(t.out_y - a.out_row0 + gy) * a.out_ws[im] + t.out_x + gx;
-        post_store_planar(reinterpret_cast<TO*>(a.outs[im]) + pix, (long long)a.out_hs[im] * a.out_ws[im], a.bgr, v);
+        uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im] + (long long)(t.out_x + gx) * (int)sizeof(TO);
+        post_store_planar<TO>(o, a.out_plane[im], a.bgr, v);
         return;
     }
-    uint8_t* o = a.outs[im] + ((long long)(t.out_y - a.out_row0 + gy) * a.out_ws[im] + t.out_x + gx) * a.c;
+    uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im] + (t.out_x + gx) * a.c;
     const uint8_t r = post_store(v[0] * 255.f), g = post_store(v[1] * 255.f), bl = post_store(v[2] * 255.f);
     o[a.bgr ? 2 : 0] = r;
     o[1] = g;
@@ -325,7 +328,7 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
         for (int j = 0; j < 4; j++)
         {
             const int yy = ay0 + clampi(by - 1 + j, ah);
-            const uint8_t* rp = a.in_imgs[im] + ((long long)yy * a.in_ws[im] + ax0) * 4 + 3;
+            const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
             rows[j] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
                       (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
         }
@@ -424,8 +427,8 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
         for (int q = 0; q < 3; q++) v[q] = a.tta ? acc[m][q] * 0.125f : acc[m][q];
         if constexpr (sizeof(TO) != 1)
         {
-            const long long pix = (long long)(t.out_y - a.out_row0 + gy0 + gyl) * a.out_ws[im] + t.out_x + gx0 + lx;
-            post_store_planar(reinterpret_cast<TO*>(a.outs[im]) + pix, (long long)a.out_hs[im] * a.out_ws[im], a.bgr, v);
+            uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy0 + gyl) * a.out_pitch[im] + (long long)(t.out_x + gx0 + lx) * (int)sizeof(TO);
+            post_store_planar<TO>(o, a.out_plane[im], a.bgr, v);
             continue;
         }
         unsigned char* o = &ob[gyl][lx * a.c];
@@ -446,7 +449,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
             for (int j = 0; j < 4; j++)
             {
                 const int yy = ay0 + clampi(by - 1 + j, ah);
-                const uint8_t* rp = a.in_imgs[im] + ((long long)yy * a.in_ws[im] + ax0) * 4 + 3;
+                const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
                 rows[j] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
                           (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
             }
@@ -455,11 +458,11 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
     }
     if constexpr (sizeof(TO) != 1) return;
     __syncthreads();
-    const int nd = nx * a.c / 4; // out_w, gx0 are multiples of 4: a row segment is whole dwords, 4-byte aligned in the image
+    const int nd = nx * a.c / 4; // out_w, gx0 are multiples of 4: a row segment is whole dwords, 4-byte aligned in the image (base and pitch: launch_postproc_tiles)
     for (int i = tid; i < ny * nd; i += 256)
     {
         const int r = i / nd, d = i - r * nd;
-        uint8_t* o = a.outs[im] + ((long long)(t.out_y - a.out_row0 + gy0 + r) * a.out_ws[im] + t.out_x + gx0) * a.c;
+        uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy0 + r) * a.out_pitch[im] + (t.out_x + gx0) * a.c;
         reinterpret_cast<uint32_t*>(o)[d] = reinterpret_cast<const uint32_t*>(&ob[r][0])[d];
     }
 }
@@ -470,8 +473,8 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
     // Measured (profiles/r04_prepost.txt): the TTA gather 0.92 ms staged vs 2.42 ms per-pixel on the C5 frame (2.26 vs 0.86 TB/s: the
     // transposed variants), but 0.19 vs 0.12 ms for the plain single-variant conversion.  Default: staged under TTA, plain otherwise.
     const bool staged = a.variant == 2 || (a.variant == 0 && a.tta);
-    bool aligned = true; // (the staged kernel stores the uint8 image in dwords)
-    for (int i = 0; i < a.nimgs; i++) aligned = aligned && (a.out_fmt != kFmtU8 || !(reinterpret_cast<uintptr_t>(a.outs[i]) & 3));
+    bool aligned = true; // (the staged kernel stores the uint8 image in dwords: base and row pitch must be multiples of 4)
+    for (int i = 0; i < a.nimgs; i++) aligned = aligned && (a.out_fmt != kFmtU8 || !((reinterpret_cast<uintptr_t>(a.outs[i]) | (uintptr_t)a.out_pitch[i]) & 3));
 #define RSR_POST(K, TO)                                                                                              \
     {                                                                                                                \
         if (a.f32) hipLaunchKernelGGL((K<float, TO>), grid, block, 0, st, a);                                        \

@@ -3,10 +3,13 @@
     from realsr_ncnn_vulkan_amd import RealSR, torch_io
     sr = RealSR(0); sr.load(param, bin)
     y = torch_io.upscale(sr, x)        # x: (3, H, W) or (N, 3, H, W) float16 / float32 in [0, 1] on cuda:0  ->  (.., 3, 4H, 4W)
+    torch_io.upscale(sr, frame[..., y0:y1, x0:x1], out=canvas[..., 4 * y0:4 * y1, 4 * x0:4 * x1])   # views in, a window out: no copies
 
-The float tensors go through rsr_process_device_fmt as they are (planar fp16 / fp32, include/realsr_hip.h): no quantisation to
-uint8 on either side, no permute, no extra pass over the frame.  The work is enqueued on torch.cuda.current_stream() and nothing
-here waits for the GPU: the result is ordered on that stream like the output of any torch op.
+The float tensors go through rsr_process_device_fmt / rsr_process_device_batch as they are (planar fp16 / fp32, include/realsr_hip.h): no
+quantisation to uint8 on either side, no permute, no extra pass over the frame.  An (N, 3, H, W) batch is ONE call: small images share
+tile batches.  A view whose rows are contiguous (a crop, a slice of a batch, a frame inside a padded surface) is passed by pointer and
+pitches (describe()); anything else is made contiguous first.  The work is enqueued on torch.cuda.current_stream() and nothing here
+waits for the GPU: the result is ordered on that stream like the output of any torch op.
 """
 import torch
 
@@ -36,22 +39,71 @@ def _check(sr, x):
     return _FMT[x.dtype], x.dim() == 4
 
 
-def upscale(sr, x):
+def describe(x):
+    """The rsr_image descriptor of ONE image tensor -- float (3, H, W) or uint8 (H, W, c) -- as (data_ptr, row_pitch, plane_pitch) in bytes
+    (plane_pitch 0 for uint8), or None when the view does not fit one and must be copied.  Pure: looks at shape and strides only.
+      float:  stride(-1) == 1, stride(-2) >= W, stride(-3) > 0 (a crop, a slice along N, rows of a padded surface, planes stored apart)
+      uint8:  stride(2) == 1, stride(1) == c, stride(0) >= W * c
+    A dimension of size 1 has no stride to speak of.  Permuted views, stride 0 (expand) and steps along a row give None."""
+    if x.dim() != 3:
+        return None
+    es = x.element_size()
+    if x.dtype == torch.uint8:
+        h, w, c = x.shape
+        rs, ps, cs = x.stride()
+        if (c > 1 and cs != 1) or (w > 1 and ps != c):
+            return None
+        row, plane = (rs if h > 1 else w * c), 0
+        if row < w * c:
+            return None
+    else:
+        _, h, w = x.shape
+        plane, rs, cs = x.stride()
+        if (w > 1 and cs != 1) or plane <= 0:
+            return None
+        row = rs if h > 1 else w
+        if row < w:
+            return None
+    ptr = x.data_ptr()
+    if ptr % es:
+        return None
+    return ptr, row * es, plane * es
+
+
+def _packed(x, d):
+    """Is the descriptor d of the image tensor x the tightly packed one?"""
+    if x.dtype == torch.uint8:
+        return d[1] == x.shape[1] * x.shape[2]
+    return d[1] == x.shape[2] * x.element_size() and d[2] == x.shape[1] * d[1]
+
+
+def upscale(sr, x, out=None):
     """x4 of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
-    with values in [0, 1], or uint8 (H, W, 3 | 4).  Returns a new tensor of the same dtype and layout at 4x, enqueued on
-    torch.cuda.current_stream(); a batch is N calls on that stream.  Non-contiguous input is made contiguous first."""
+    with values in [0, 1], or uint8 (H, W, 3 | 4).  Returns a tensor of the same dtype and layout at 4x, enqueued on
+    torch.cuda.current_stream(); a batch is ONE rsr_process_device_batch call on that stream.  A view that fits a descriptor (describe)
+    is read in place; any other non-contiguous input is made contiguous first.
+    out: the tensor to write (and return) instead of a new one: the result's shape, dtype and device, and itself a view that fits a
+    descriptor -- a window of a larger canvas, say.  ValueError otherwise, before anything is launched.  It must not overlap x."""
     fmt, batched = _check(sr, x)
-    x = x.contiguous()
+    s = sr.scale
+    shape = tuple(x.shape[:-3]) + ((x.shape[0] * s, x.shape[1] * s, x.shape[2]) if fmt == RSR_FMT_U8_HWC else (3, x.shape[-2] * s, x.shape[-1] * s))
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError("upscale: out must be a %s tensor of shape %s on %s" % (x.dtype, shape, x.device))
+        if (batched and out.shape[0] > 1 and out.stride(0) == 0) or (out.numel() and describe(out[0] if batched else out) is None):
+            raise ValueError("upscale: out (strides %s) is not addressable by row and plane pitch" % (tuple(out.stride()),))
+    if x.numel() and describe(x[0] if batched else x) is None:
+        x = x.contiguous()
     cur = torch.cuda.current_stream(x.device)
     if cur.cuda_stream == 0:
         # torch's default stream is the null stream, and a null stream means "the context's own stream, synchronously" to the C call.
         # The work goes onto a side stream ordered behind and in front of the default stream by events: still nothing waits on the host.
         side = _side_stream(x.device)
         side.wait_stream(cur)
-        y = _enqueue(sr, x, fmt, batched, side.cuda_stream)
+        y = _enqueue(sr, x, fmt, batched, side.cuda_stream, out, shape)
         cur.wait_stream(side)  # (x and y are next touched by work behind this wait: the allocator may reuse them safely)
         return y
-    return _enqueue(sr, x, fmt, batched, cur.cuda_stream)
+    return _enqueue(sr, x, fmt, batched, cur.cuda_stream, out, shape)
 
 
 _side = {}
@@ -63,15 +115,22 @@ def _side_stream(device):
     return _side[device.index]
 
 
-def _enqueue(sr, x, fmt, batched, stream):
-    s = sr.scale
+def _enqueue(sr, x, fmt, batched, stream, out, shape):
+    y = out if out is not None else torch.empty(shape, dtype=x.dtype, device=x.device)
+    if x.numel() == 0:
+        return y
     if fmt == RSR_FMT_U8_HWC:
         h, w, c = x.shape
-        y = torch.empty((h * s, w * s, c), dtype=x.dtype, device=x.device)
-        sr.process_device_fmt(x.data_ptr(), fmt, w, h, c, y.data_ptr(), fmt, stream=stream)
-        return y
-    h, w = x.shape[-2], x.shape[-1]
-    y = torch.empty(tuple(x.shape[:-2]) + (h * s, w * s), dtype=x.dtype, device=x.device)
-    for xi, yi in zip(x, y) if batched else ((x, y),):
-        sr.process_device_fmt(xi.data_ptr(), fmt, w, h, 3, yi.data_ptr(), fmt, stream=stream)
+    else:
+        h, w, c = x.shape[-2], x.shape[-1], 3
+    dx, dy = describe(x[0] if batched else x), describe(y[0] if batched else y)
+    if batched:  # the batch stride only moves the per-image pointer
+        n, es = x.shape[0], x.element_size()
+        ins = [(dx[0] + i * x.stride(0) * es, dx[1], dx[2]) for i in range(n)]
+        outs = [(dy[0] + i * y.stride(0) * es, dy[1], dy[2]) for i in range(n)]
+        sr.process_device_batch(ins, fmt, w, h, c, outs, fmt, stream=stream)
+    elif _packed(x, dx) and _packed(y, dy):
+        sr.process_device_fmt(dx[0], fmt, w, h, c, dy[0], fmt, stream=stream)
+    else:
+        sr.process_device_batch([dx], fmt, w, h, c, [dy], fmt, stream=stream)
     return y
