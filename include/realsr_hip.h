@@ -69,13 +69,13 @@ int rsr_set_params(rsr_ctx* ctx, int scale, int tilesize, int prepadding);
 
 /* RealSR::process(const ncnn::Mat& in, ncnn::Mat& out) const   realsr.h:25, realsr.cpp:145-523.
  * `in`/`out` are HOST pointers (what ncnn::Mat::data is at main.cpp:275-276).  H2D, all tiles,
- * D2H; returns when `out` is complete. */
+ * D2H; returns when `out` is complete.  `out` is (w * out_scale) x (h * out_scale) x c (option "out_scale", default 4). */
 int rsr_process(rsr_ctx* ctx, const uint8_t* in, int w, int h, int c, uint8_t* out);
 
 /* n images in one call (no reference counterpart: main.cpp's proc threads call process() once per image, :311-331).  Every image is
  * what rsr_process would make of it; up to max_lanes of them are in flight at once on helper threads of the call, so that SMALL
  * images share tile batches (option "merge") without the host having to be multi-threaded.  rcs (may be NULL) receives the code of
- * every image; the return value is the first failure (0 = all ok). */
+ * every image; the return value is the first failure (0 = all ok).  out[i]: (w[i] * out_scale) x (h[i] * out_scale) x c[i]. */
 int rsr_process_many(rsr_ctx* ctx, int n, const uint8_t* const* in, const int* w, const int* h, const int* c, uint8_t* const* out, int* rcs);
 
 /* Same computation with both images already resident in this context's device memory
@@ -83,7 +83,8 @@ int rsr_process_many(rsr_ctx* ctx, int n, const uint8_t* const* in, const int* w
  * `stream` is a hipStream_t (NULL = the context's own stream).  Asynchronous when a stream is
  * given: the caller synchronises.  When nothing else is in flight on the context the kernels are
  * enqueued on `stream` itself; otherwise they run on the context's compute stream, ordered behind
- * the work already on `stream` and in front of what the caller enqueues on it next. */
+ * the work already on `stream` and in front of what the caller enqueues on it next.
+ * d_out: "4w x 4h" reads "(w * out_scale) x (h * out_scale)" (option "out_scale", default 4). */
 int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void* d_out, void* stream);
 
 /* Pixel formats of device-resident images (no reference counterpart: the reference's images are uint8 HWC only). */
@@ -103,6 +104,7 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
  *            (option "precise").  F32 receives min(max(r, 0), 1); F16 that value rounded once to fp16 (lossless in the default
  *            non-TTA mode).  Quantising it with floor(v * 255 + 0.5) reproduces the uint8 path's byte.
  *   Option "bgr" swaps planes 0 and 2 the way it swaps bytes 0 and 2 of a uint8 pixel.
+ *   Option "out_scale" 2 / 1: d_out is (w * out_scale) x (h * out_scale) and receives the box means of those values (rsr_set_option).
  * This is rsr_process_device_batch (below) with n = 1 and tightly packed images.
  * Out of scope: RGBA in planar form and a host-pointer variant (rsr_process stays uint8 HWC). */
 int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, int h, int c, void* d_out, int out_fmt, void* stream);
@@ -120,7 +122,7 @@ typedef struct rsr_image
 /* n images of ONE geometry (w x h x c, in_fmt -> out_fmt), each with its own pointer and pitches: what a tensor pipeline holds as an
  * (N, 3, H, W) batch, or as views into larger tensors.  Image i receives exactly the bytes rsr_process_device_fmt(in[i] -> out[i]) writes
  * for the same pixels in the context's current mode (default, TTA, "precise", "bgr"; uint8 with c 3 or 4, planar with c == 3); out[i]
- * describes the 4w x 4h result and no byte outside that window is touched.
+ * describes the 4w x 4h result -- (w * out_scale) x (h * out_scale) with option "out_scale" -- and no byte outside that window is touched.
  *   Batching.  The images are cut into groups of as many as one merged tile batch of this geometry takes (option "merge": up to 16 small
  *            images; 1 for a frame that fills the chip by itself, for "merge" = 1 and while profiling is on); every group walks the
  *            network as ONE tile batch, on the plan and workspace the merged host calls of that geometry use -- 16 images of 256 x 256
@@ -195,15 +197,16 @@ int rsr_rccl_probe(void);
 
 /* RealSR::process restricted to the tiles [tile_begin, tile_end) of the image's tile grid, counted row-major (tile (yi, xi) =
  * yi * ceil(w / tilesize) + xi; tiles are independent: realsr.cpp:377-380,458-459,490).  `in` is the whole image, `out` the
- * whole (4w x 4h x c) output; only the output rectangles of those tiles are written.  Disjoint ranges may run concurrently
- * on different contexts into the same `out`.  rsr_process_rows: the same for whole tile rows [tile_row_begin, tile_row_end). */
+ * whole (4w x 4h x c) output -- (w * out_scale) x (h * out_scale) x c with option "out_scale" --; only the output rectangles
+ * of those tiles are written.  Disjoint ranges may run concurrently on different contexts into the same `out`.  rsr_process_rows: the same for whole tile rows [tile_row_begin, tile_row_end). */
 int rsr_process_tiles(rsr_ctx* ctx, const uint8_t* in, int w, int h, int c, uint8_t* out, int tile_begin, int tile_end);
 int rsr_process_rows(rsr_ctx* ctx, const uint8_t* in, int w, int h, int c, uint8_t* out, int tile_row_begin, int tile_row_end);
 
 /* One image over n contexts (normally one per GPU): the TILES are dealt in contiguous row-major ranges of equal padded-pixel
  * load (within one tile; a 1080p frame at tile 200 = 60 tiles = 7-8 per GPU on 8 GPUs), every context runs its range on its
  * own thread and fetches the rectangles of its tiles into `out`; the call returns when `out` is complete.  All contexts must
- * carry the same tilesize / prepadding / scale / tta (checked: RSR_E_ARG otherwise). */
+ * carry the same tilesize / prepadding / scale / out_scale / tta (checked: RSR_E_ARG otherwise); `out` is
+ * (w * out_scale) x (h * out_scale) x c. */
 int rsr_process_group(rsr_ctx* const* ctx, int n, const uint8_t* in, int w, int h, int c, uint8_t* out);
 /* (rsr_process_group keeps its worker threads between calls: a process that has called it must not dlclose() the library.) */
 
@@ -357,6 +360,27 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *                       between: half the distance to the reference's fp32 CPU path (realsr.cpp:525-838) that fp16 storage -- the
  *                       reference's own GPU path, realsr.cpp:44-46, and this engine's default (0) -- has; costs ~6 % more workspace
  *                       and the extra traffic of the residue planes in 71 of the 351 convolutions
+ *   "out_scale"         4 [default]: the output is the network's x4 image.  2 / 1: that image box-reduced on the device, 2 x 2 / 4 x 4, to
+ *                       (2w) x (2h) / w x h -- 1080p -> 2160p, or a restoration model (models-DF2K_JPEG) at the image's own size -- without
+ *                       the x4 image ever leaving the library.  Any other value: RSR_E_ARG, the value in force stays (stat "out_scale").
+ *                       Takes effect for the next call, like "precise"; every rsr_process* entry point honours it, and wherever a
+ *                       comment below says "4w x 4h" read "(w * out_scale) x (h * out_scale)".  rsr_set_params is not concerned: its
+ *                       `scale` stays the network's 4.  rsr_image_bytes / rsr_image_span take the image's own w and h.  Definition,
+ *                       bit for bit, for output pixel (X, Y), channel q, k = 4 / out_scale:
+ *                         1. c(x, y) = min(max(r(x, y), 0), 1), r the fp32 value the uint8 conversion sees at x4 pixel (x, y) in the
+ *                            context's current mode (rsr_process_device_fmt, "Output": what RSR_FMT_F32_CHW holds at out_scale 4;
+ *                            under TTA the eight variants are merged first, (v0 + ... + v7) * 0.125f)
+ *                         2. d = the fp32 mean of c over x in [kX, kX + k), y in [kY, kY + k), in this order (c_yx):
+ *                            k = 2: ((c00 + c01) + (c10 + c11)) * 0.25f;  k = 4: s_j = ((c_j0 + c_j1) + (c_j2 + c_j3)), then
+ *                            ((s0 + s1) + (s2 + s3)) * 0.0625f.  Plain fp32 adds, one multiplication by a power of two
+ *                         3. RSR_FMT_F32_CHW stores d, RSR_FMT_F16_CHW d rounded once to fp16, RSR_FMT_U8_HWC floor(d * 255 + 0.5)
+ *                            clamped to 0 .. 255 (the conversion of the x4 path)
+ *                         4. alpha (uint8, c == 4): the bicubic x4 alpha value of the x4 path, clamped to [0, 255], averaged over the
+ *                            box in the same order and stored as floor(mean + 0.5)
+ *                         5. "bgr" swaps channels 0 and 2 on store as ever; "precise" changes only what r is.
+ *                       The clamp comes BEFORE the mean (the mean of the x4 image one would have got, not of the raw network output);
+ *                       a box never crosses a tile.  Below 4, conv_last leaves its planar blob and one more small launch
+ *                       (postproc_tiles_box) writes the image: the route RGBA and TTA take anyway
  *   "precise_auto"      1: "precise" is set by the model: on a loaded context rsr_selfcheck runs at once on the built-in tile and "precise"
  *                       becomes its recommend_precise; on a context not yet loaded the same happens at the end of the next successful
  *                       rsr_load / rsr_load_packed (which then returns the self-check's error, if it has one; the model stays loaded).
@@ -405,7 +429,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *                       rsr_process_group allocates only the output rows of its tile range)
  *   "last_test_us"      HIP-event time of the last rsr_conv3x3 / rsr_conv3x3_res launch (with option "test_repeat" = N the
  *                       work items are repeated N times in that one launch: an L2-resident workload)
- *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it)
+ *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force
  *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
  *                       "selfcheck_overflow" (-1 before the first run) */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);

@@ -226,6 +226,17 @@ class RealSR:
         self.scale, self.tilesize, self.prepadding = 4, 200, 10
         self.tta_mode = bool(tta_mode)
 
+    @property
+    def out_scale(self):
+        """Size of the output relative to the input: 4 (default) = the network's x4 image; 2 or 1 = that image box-reduced on the
+        device, 2 x 2 or 4 x 4 (option "out_scale", include/realsr_hip.h).  Takes effect for the next call.  Read from the engine, so
+        set_option("out_scale", s) and this property cannot disagree: every buffer below is sized with the value the engine will use."""
+        return int(self.get_stat("out_scale"))
+
+    @out_scale.setter
+    def out_scale(self, s):
+        self.set_option("out_scale", int(s))  # (anything but 1, 2 or 4 raises RealSRError(RSR_E_ARG) and leaves the value alone)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.rsr_destroy(self._h)
@@ -266,14 +277,15 @@ class RealSR:
         return v.value
 
     def process(self, img, out=None, push_params=True):
-        """out: optional preallocated (4h, 4w, c) uint8 array (e.g. PinnedArray(...).array)."""
+        """out: optional preallocated (h * out_scale, w * out_scale, c) uint8 array (e.g. PinnedArray(...).array)."""
         img = np.ascontiguousarray(img, dtype=np.uint8) if not (isinstance(img, np.ndarray) and img.flags.c_contiguous and img.dtype == np.uint8) else img
         h, w, c = img.shape
         if push_params:
             self._push_params()
+        s = self.out_scale
         if out is None:
-            out = np.empty((h * self.scale, w * self.scale, c), dtype=np.uint8)
-        assert out.shape == (h * self.scale, w * self.scale, c) and out.dtype == np.uint8 and out.flags.c_contiguous
+            out = np.empty((h * s, w * s, c), dtype=np.uint8)
+        assert out.shape == (h * s, w * s, c) and out.dtype == np.uint8 and out.flags.c_contiguous
         self._ck(self._L.rsr_process(self._h, _p(img), w, h, c, _p(out)))
         return out
 
@@ -281,7 +293,8 @@ class RealSR:
         """rsr_process_many: a list of uint8 HWC images in ONE call (small ones share tile batches); returns the list of outputs."""
         imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
         n = len(imgs)
-        outs = [np.empty((im.shape[0] * self.scale, im.shape[1] * self.scale, im.shape[2]), dtype=np.uint8) for im in imgs]
+        s = self.out_scale
+        outs = [np.empty((im.shape[0] * s, im.shape[1] * s, im.shape[2]), dtype=np.uint8) for im in imgs]
         self._push_params()
         ins_p = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
         outs_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
@@ -300,7 +313,7 @@ class RealSR:
 
     def process_device_fmt(self, d_in, in_fmt, w, h, c, d_out, out_fmt, stream=None):
         """rsr_process_device_fmt: process_device with a pixel format (RSR_FMT_*) per side; the planar float formats need c == 3.
-        Buffer sizes: image_bytes(in_fmt, w, h, c) and image_bytes(out_fmt, 4 * w, 4 * h, c).  torch tensors: torch_io.upscale."""
+        Buffer sizes: image_bytes(in_fmt, w, h, c) and image_bytes(out_fmt, w * out_scale, h * out_scale, c).  torch tensors: torch_io.upscale."""
         self._push_params()
         self._ck(self._L.rsr_process_device_fmt(self._h, C.c_void_p(int(d_in)), int(in_fmt), w, h, c, C.c_void_p(int(d_out)), int(out_fmt),
                                                 C.c_void_p(int(stream)) if stream else None))
@@ -314,9 +327,15 @@ class RealSR:
         self._ck(self._L.rsr_process_device_batch(self._h, len(ins), _images(ins), int(in_fmt), w, h, c, _images(outs), int(out_fmt),
                                                   C.c_void_p(int(stream)) if stream else None))
 
+    def _check_full_out(self, out, h, w, c):
+        s = self.out_scale
+        if out.shape != (h * s, w * s, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint8 array of shape %s (out_scale %d), not %s %s" % ((h * s, w * s, c), s, out.dtype, out.shape))
+
     def process_rows(self, img, out, row0, row1):
         """Tile rows [row0, row1) of img's tile grid into the full-size `out` (see rsr_process_rows)."""
         h, w, c = img.shape
+        self._check_full_out(out, h, w, c)
         self._push_params()
         self._ck(self._L.rsr_process_rows(self._h, _p(img), w, h, c, _p(out), int(row0), int(row1)))
         return out
@@ -324,6 +343,7 @@ class RealSR:
     def process_tiles(self, img, out, tile0, tile1):
         """Tiles [tile0, tile1) of img's row-major tile grid into the full-size `out` (see rsr_process_tiles)."""
         h, w, c = img.shape
+        self._check_full_out(out, h, w, c)
         self._push_params()
         self._ck(self._L.rsr_process_tiles(self._h, _p(img), w, h, c, _p(out), int(tile0), int(tile1)))
         return out
@@ -535,8 +555,11 @@ def process_group(srs, img, out=None):
     h, w, c = img.shape
     for s in srs:
         s._push_params()
+    os_ = srs[0].out_scale  # (members that disagree: RSR_E_ARG from the call)
     if out is None:
-        out = np.empty((h * 4, w * 4, c), dtype=np.uint8)
+        out = np.empty((h * os_, w * os_, c), dtype=np.uint8)
+    if out.shape != (h * os_, w * os_, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous uint8 array of shape %s (out_scale %d)" % ((h * os_, w * os_, c), os_))
     hs = (C.c_void_p * len(srs))(*[s._h for s in srs])
     rc = L.rsr_process_group(hs, len(srs), _p(img), w, h, c, _p(out))
     if rc != 0:

@@ -515,6 +515,7 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "merged_widest") *value = double(e.merged_widest.load());
     else if (k == "merged_mixed") *value = double(e.merged_mixed.load());
     else if (k == "precise_active") *value = e.precise ? 1.0 : 0.0;
+    else if (k == "out_scale") *value = double(e.out_scale);
     else if (k == "selfcheck_runs") *value = double(e.selfcheck_runs);
     else if (k == "selfcheck_headroom") *value = e.selfcheck_runs ? double(e.sc_last.headroom) : -1.0;
     else if (k == "selfcheck_peak_abs") *value = e.selfcheck_runs ? double(e.sc_last.peak_abs) : -1.0;
@@ -556,6 +557,11 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     }
     else if (k == "precise")
         ctx->e.precise = value != 0; // plans are keyed by it (larger slots); the workspace grows on the next call
+    else if (k == "out_scale")
+    { // the next call's output is (w * value) x (h * value): plans are keyed by it (below 4 conv_last leaves the planar blob to postproc_tiles_box)
+        if (value != 1 && value != 2 && value != 4) return ctx->e.fail(RSR_E_ARG, "out_scale must be 1, 2 or 4");
+        ctx->e.out_scale = int(value);
+    }
     else if (k == "precise_auto")
     { // the model decides: now when one is loaded, else at the end of the next load (rsr_load / rsr_load_packed)
         ctx->e.precise_auto = value != 0;

@@ -63,6 +63,7 @@ struct Plan
     int w = 0, h = 0, c = 0, T = 0, P = 0, tta = 0;
     int nimg = 1;         // images of this geometry merged into one tile batch (kernels.h kMaxMerge); their tiles follow each other image by image
     bool precise = false; // Engine::precise when the plan was built (the slots are larger: part of the cache key)
+    int out_scale = 4;    // Engine::out_scale when the plan was built (part of the cache key, though no field of a Plan depends on it today: the placement tables are built alike and below 4 merely go unused)
     bool ntw2 = false;    // flow_flags bit 0 when the plan was built (an MFMA wave then reaches 4 planes from one base: the tile-size bound halves)
     int tile0 = 0, tile1 = 0; // tiles [tile0, tile1) of the image's tile grid, row-major (multi-GPU tile sharding)
     long long budget_mb = 0;
@@ -124,6 +125,7 @@ struct MergeReq
     const void* d_in = nullptr;
     void* d_out = nullptr;
     int w = 0, h = 0, c = 0, T = 0;
+    int os = 4;                   // Engine::out_scale when the call came in: d_out is (w * os) x (h * os)
     long long items = 0;          // LR-level work items of the image (Engine::image_items)
     int width = 1;                // Engine::merge_width of its geometry when the call came in
     hipEvent_t ev_in = nullptr;   // the input is complete behind this event (null: it already is)
@@ -140,31 +142,32 @@ struct BatchIO
 {
     int nimg = 0, c = 0;        // images of the batch (<= kMaxMerge; BaseTile::img selects) and their channel count
     const void* in[kMaxMerge];  // per image: the device image, in_fmt, w[i] x h[i] ...
-    void* out[kMaxMerge];       // ... and its 4w[i] x 4h[i] result, out_fmt
+    void* out[kMaxMerge];       // ... and its (w[i] * os) x (h[i] * os) result, out_fmt
+    int os = 4;                 // Engine::out_scale of the call: 4, or 2 / 1 = the x4 result box-reduced (kernels.h PostArgs::box = 4 / os)
     int w[kMaxMerge], h[kMaxMerge];
     // Bytes from one row / one plane (planar formats) of an image to the next, resolved (never 0; rsr_image of the C ABI, image_layout).
     // The constructors set the tightly packed values; Engine::process_device_batch overwrites them with the caller's.
     long long in_pitch[kMaxMerge], in_plane[kMaxMerge], out_pitch[kMaxMerge], out_plane[kMaxMerge];
     int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float formats come with whole images of c == 3 only)
-    int out_row0 = 0;           // `out` points at this output row of the x4 image (a tile range's device buffer holds only its rows)
+    int out_row0 = 0;           // `out` points at output row out_row0 * os / 4 of the image; out_row0 counts x4 rows (a tile range's device buffer holds only its rows)
     int split_slot = 0;         // > 0: the 4x tail is split in front of this slot and ...
     hipEvent_t ev_half = nullptr; // ... this event recorded behind the first part (the caller starts downloading its output rows)
     hipEvent_t ev_mid = nullptr;  // recorded behind the middle RDB (a merged batch's throttle event, Engine::submit_merged)
-    BatchIO(const void* d_in, void* d_out, int w0, int h0, int c0, int in_fmt0, int out_fmt0) : nimg(1), c(c0), in_fmt(in_fmt0), out_fmt(out_fmt0)
+    BatchIO(const void* d_in, void* d_out, int w0, int h0, int c0, int in_fmt0, int out_fmt0, int os0) : nimg(1), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0)
     {
         set(0, d_in, d_out, w0, h0);
     }
-    BatchIO(MergeReq* const* g, int n) : nimg(n), c(g[0]->c) // the uint8 images of merged calls
+    BatchIO(MergeReq* const* g, int n) : nimg(n), c(g[0]->c), os(g[0]->os) // the uint8 images of merged calls (one out_scale: Engine::run_group)
     {
         for (int i = 0; i < n; i++) set(i, g[i]->d_in, g[i]->d_out, g[i]->w, g[i]->h);
     }
-    BatchIO(int n, int c0, int in_fmt0, int out_fmt0) : nimg(n), c(c0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
+    BatchIO(int n, int c0, int in_fmt0, int out_fmt0, int os0) : nimg(n), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
     static long long px_bytes(int fmt, int c) { return fmt == RSR_FMT_F16_CHW ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : c); } // of one element of a row
-    void set(int i, const void* d_in, void* d_out, int wi, int hi) // image i, tightly packed (the output is x4: Engine::scale is checked to be 4)
+    void set(int i, const void* d_in, void* d_out, int wi, int hi) // image i, tightly packed (the output is x os)
     {
         in[i] = d_in, out[i] = d_out, w[i] = wi, h[i] = hi;
         in_pitch[i] = wi * px_bytes(in_fmt, c), in_plane[i] = hi * in_pitch[i];
-        out_pitch[i] = 4 * wi * px_bytes(out_fmt, c), out_plane[i] = 4 * hi * out_pitch[i];
+        out_pitch[i] = os * wi * px_bytes(out_fmt, c), out_plane[i] = os * hi * out_pitch[i];
     }
 };
 
@@ -193,6 +196,10 @@ struct Engine
     // conv_last's fp32 result goes to the uint8 conversion unrounded.  Default off = the storage of the reference's Vulkan path
     // (fp16 everywhere, realsr.cpp:44-46); on = half the distance to its fp32 CPU path (realsr.cpp:525-838), the bar of the parity tests.
     bool precise = false;
+    // Output scale (option "out_scale"; include/realsr_hip.h): 4 = the network's x4 image; 2 / 1 = every 2 x 2 / 4 x 4 box of it, clamped to
+    // [0, 1] first, leaves as its fp32 mean.  A box never crosses a tile (a tile's x4 rectangle starts and ends on multiples of 4), so the
+    // reduction is the per-tile post-processing launch (kernels.hip postproc_tiles_box); conv_last then leaves the planar blob.
+    int out_scale = 4;
     // Model self-check (include/realsr_hip.h rsr_selfcheck): one tile through the network in both storages, compared on the device.
     bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
     long long selfcheck_runs = 0;
@@ -304,7 +311,7 @@ struct Engine
     // n images of one geometry, each behind its own descriptor (pointer, row pitch, plane pitch), in groups of merge_width(w, h, c) images:
     // every group ONE tile batch on the cached merged plan (include/realsr_hip.h rsr_process_device_batch).  Stream contract of process_device.
     int process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream, bool sync);
-    // tile0/tile1: tiles [tile0, tile1) of the row-major tile grid only (tile1 < 0: all); `out` is always the full (4w x 4h x c) image,
+    // tile0/tile1: tiles [tile0, tile1) of the row-major tile grid only (tile1 < 0: all); `out` is always the full (w * out_scale x h * out_scale x c) image,
     // only the output rectangles of
     // those tiles are written
     int process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, int tile0 = 0, int tile1 = -1);
@@ -323,7 +330,7 @@ struct Engine
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
-    bool conv_last_writes_image(int c) const { return !tta && c == 3 && !(dbg & 8192); } // no TTA merge / alpha channel needs the planar blob (dbg 8192: off)
+    bool conv_last_writes_image(int c) const { return !tta && c == 3 && out_scale == 4 && !(dbg & 8192); } // no TTA merge / alpha channel / box reduction needs the planar blob (dbg 8192: off)
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
     // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).

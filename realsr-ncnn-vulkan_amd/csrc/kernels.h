@@ -191,6 +191,10 @@ struct PostArgs
     int tilesize;
     int bgr;
     int variant; // 0 default (LDS-staged under TTA, else one thread per pixel), 1 per-pixel (engine dbg 32768), 2 LDS-staged (dbg 65536)
+    // Box-reduced output (engine option "out_scale"): 0 / 1 = the x4 image as above; 2 / 4 = every K x K box of x4 pixels, each clamped
+    // to [0, 1] first, leaves as ONE pixel, its fp32 mean (postproc_tiles_box): the outs are (4 / K)w x (4 / K)h.  Everything above stays in
+    // x4 units (BaseTile::out_*, out_row0, crop: all multiples of 4); the kernel divides by K.
+    int box;
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 

@@ -467,9 +467,194 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
     }
 }
 
+// ---- box-reduced output (engine option "out_scale" 2 / 1: PostArgs::box = K = 2 / 4) ----------------------------------------
+// K contiguous blob elements, K-element aligned: ONE 4- / 8-byte (fp16) or 8- / 16-byte (fp32) load.
+template <typename TP, int K>
+__device__ __forceinline__ void load_run(const TP* p, float (&o)[K])
+{
+    typedef TP vec __attribute__((ext_vector_type(K)));
+    const vec v = *reinterpret_cast<const vec*>(p);
+#pragma unroll
+    for (int i = 0; i < K; i++) o[i] = (float)v[i];
+}
+
+// The fp32 mean of a K x K box c[y][x] in the fixed order of include/realsr_hip.h ("out_scale"): pairs along x, then pairs of rows.
+// Plain adds and one multiplication by a power of two behind them: nothing a contraction could change.
+template <int K>
+__device__ __forceinline__ float box_mean(const float (&c)[K][K])
+{
+    if constexpr (K == 2) return ((c[0][0] + c[0][1]) + (c[1][0] + c[1][1])) * 0.25f;
+    else
+    {
+        float s[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) s[j] = (c[j][0] + c[j][1]) + (c[j][2] + c[j][3]);
+        return ((s[0] + s[1]) + (s[2] + s[3])) * 0.0625f;
+    }
+}
+
+// The box-reducing sibling of postproc_tiles: one thread makes ONE pixel of the (4 / K)x image -- the mean of the K x K box of x4
+// pixels min(max(r, 0), 1), r what postproc_tiles converts (TTA: the eight variants merged first, in the shader's order).  A tile's
+// kept x4 rectangle starts and ends on multiples of 4 (BaseTile::out_*), so no box crosses a tile; BaseTile stays in x4 units and is
+// divided by K here.  Lanes run along x.  The K elements a thread needs of a blob row are contiguous and K-aligned (crop, the row
+// length 4 * tw and the plane size are multiples of 4): one load each (load_run) -- also in the mirrored variants (the run is read
+// backwards) and in the TRANSPOSED ones, where a thread's run lies along y and it reads K of them.
+// ALPHA: the uint8 image is RGBA (PostArgs::c == 4; a kernel of its own: the bicubic's registers stay out of the RGB path).
+template <typename TP, typename TO, int K, bool ALPHA>
+__global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
+{
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= t.out_w / K || gy >= t.out_h / K) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const long long cstep = (long long)w * h;
+    const int sx = gx * K + a.crop, sy = gy * K + a.crop; // first x4 pixel of the box, in the blob
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    constexpr int es = sizeof(TO) == 1 ? 1 : (int)sizeof(TO);
+    uint8_t* const o = a.outs[im] + ((t.out_y - a.out_row0) / K + gy) * (long long)a.out_pitch[im] + (long long)(t.out_x / K + gx) * (sizeof(TO) == 1 ? a.c : es);
+#pragma unroll 1 // (one channel at a time: unrolled, the loads of all three are hoisted to the top and cost three times the registers)
+    for (int q = 0; q < 3; q++)
+    {
+        const TP* b = b0 + q * cstep;
+        float c[K][K], r[K];
+#pragma unroll
+        for (int j = 0; j < K; j++)
+        {
+            load_run<TP, K>(b + (long long)(sy + j) * w + sx, r);
+#pragma unroll
+            for (int i = 0; i < K; i++) c[j][i] = r[i];
+        }
+        if (a.tta)
+        { // realsr_postproc_tta.comp:76-85: (v0 + v1 + ... + v7) * 0.125f, in this order
+#pragma unroll
+            for (int j = 0; j < K; j++)
+            {
+                load_run<TP, K>(b + ss + (long long)(sy + j) * w + (w - K - sx), r);
+#pragma unroll
+                for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++)
+            {
+                load_run<TP, K>(b + 2 * ss + (long long)(h - 1 - sy - j) * w + (w - K - sx), r);
+#pragma unroll
+                for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++)
+            {
+                load_run<TP, K>(b + 3 * ss + (long long)(h - 1 - sy - j) * w + sx, r);
+#pragma unroll
+                for (int i = 0; i < K; i++) c[j][i] += r[i];
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++)
+            {
+                load_run<TP, K>(b + 4 * ss + (long long)(sx + i) * h + sy, r);
+#pragma unroll
+                for (int j = 0; j < K; j++) c[j][i] += r[j];
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++)
+            {
+                load_run<TP, K>(b + 5 * ss + (long long)(sx + i) * h + (h - K - sy), r);
+#pragma unroll
+                for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++)
+            {
+                load_run<TP, K>(b + 6 * ss + (long long)(w - 1 - sx - i) * h + (h - K - sy), r);
+#pragma unroll
+                for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++)
+            {
+                load_run<TP, K>(b + 7 * ss + (long long)(w - 1 - sx - i) * h + sy, r);
+#pragma unroll
+                for (int j = 0; j < K; j++) c[j][i] += r[j];
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++)
+#pragma unroll
+                for (int i = 0; i < K; i++) c[j][i] *= 0.125f;
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++)
+#pragma unroll
+            for (int i = 0; i < K; i++) c[j][i] = fminf(fmaxf(c[j][i], 0.f), 1.f);
+        const float d = box_mean<K>(c); // in [0, 1] like its sixteen / four terms
+        const int qo = a.bgr ? 2 - q : q;
+        if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)d;
+        else o[qo] = post_store(d * 255.f);
+    }
+    if constexpr (ALPHA)
+    { // alpha: the box mean of postproc_tiles' bicubic x4 value, each clamped to [0, 255] first; two box rows per turn: (s0 + s1) [+ (s2 + s3)]
+        const int aw = t.out_w / 4, ah = t.out_h / 4;
+        const int ax0 = t.out_x / 4, ay0 = t.out_y / 4;
+        float tot = 0.f;
+#pragma unroll 1
+        for (int p = 0; p < K / 2; p++)
+        {
+            float s2[2];
+#pragma unroll
+            for (int jj2 = 0; jj2 < 2; jj2++)
+            {
+                float al[K];
+                int by;
+                float cy[4];
+                cubic_coeffs(ah, t.out_h, gy * K + 2 * p + jj2, by, cy); // (of the row alone: once per box row, not per pixel)
+#pragma unroll
+                for (int i = 0; i < K; i++)
+                {
+                    int bx;
+                    float cx[4];
+                    cubic_coeffs(aw, t.out_w, gx * K + i, bx, cx);
+                    float rows[4];
+#pragma unroll
+                    for (int jj = 0; jj < 4; jj++)
+                    {
+                        const int yy = ay0 + clampi(by - 1 + jj, ah);
+                        const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
+                        rows[jj] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
+                                   (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
+                    }
+                    const float av = rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
+                    al[i] = fminf(fmaxf(av, 0.f), 255.f);
+                }
+                if constexpr (K == 2) s2[jj2] = al[0] + al[1];
+                else s2[jj2] = (al[0] + al[1]) + (al[2] + al[3]);
+            }
+            const float tp = s2[0] + s2[1];
+            tot = p == 0 ? tp : tot + tp;
+        }
+        o[3] = post_store(tot * (K == 2 ? 0.25f : 0.0625f));
+    }
+}
+
+template <typename TP, int K>
+static void launch_postproc_box(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    const dim3 grid((max_ow / K + 63) / 64, (max_oh / K + 3) / 4, a.ntiles), block(256);
+    if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_box<TP, _Float16, K, false>), grid, block, 0, st, a);
+    else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_box<TP, float, K, false>), grid, block, 0, st, a);
+    else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, false>), grid, block, 0, st, a);
+}
+
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
     if (a.ntiles <= 0) return;
+    if (a.box > 1)
+    { // out_scale 2 / 1: the box-reducing kernel (one thread per output pixel, with and without TTA)
+        if (a.box == 2) a.f32 ? launch_postproc_box<float, 2>(a, max_ow, max_oh, st) : launch_postproc_box<_Float16, 2>(a, max_ow, max_oh, st);
+        else a.f32 ? launch_postproc_box<float, 4>(a, max_ow, max_oh, st) : launch_postproc_box<_Float16, 4>(a, max_ow, max_oh, st);
+        return;
+    }
     // Measured (profiles/r04_prepost.txt): the TTA gather 0.92 ms staged vs 2.42 ms per-pixel on the C5 frame (2.26 vs 0.86 TB/s: the
     // transposed variants), but 0.19 vs 0.12 ms for the plain single-variant conversion.  Default: staged under TTA, plain otherwise.
     const bool staged = a.variant == 2 || (a.variant == 0 && a.tta);

@@ -191,6 +191,19 @@ int main(int argc, char** argv)
         fprintf(stderr, "invalid scale argument\n");
         return -1;
     }
+    // RSR_OUT_SCALE=1|2|4 (no flag of the reference's surface is taken for it; -s stays the MODEL's scale): the size of the output
+    // image relative to the input -- the x4 result box-reduced on the device (rsr_set_option "out_scale")
+    int out_scale = 4;
+    if (const char* oe = getenv("RSR_OUT_SCALE"))
+    {
+        const std::string v(oe);
+        if (v != "1" && v != "2" && v != "4")
+        {
+            fprintf(stderr, "invalid RSR_OUT_SCALE '%s' (1, 2 or 4)\n", oe);
+            return -1;
+        }
+        out_scale = v[0] - '0';
+    }
     if (gpuid.empty()) gpuid.push_back(0);
     const int ngpu = int(gpuid.size());
     for (int g : gpuid)
@@ -327,6 +340,8 @@ int main(int argc, char** argv)
         r->scale = scale;
         r->tilesize = tilesize[size_t(i)];
         r->prepadding = prepadding;
+        r->out_scale = out_scale;
+        if (verbose) fprintf(stderr, "gpu %d: output scale %d%s\n", gpuid[size_t(i)], out_scale, out_scale == 4 ? "" : " (RSR_OUT_SCALE: the x4 result box-reduced)");
         // the reference prints one line per tile, "%.2f%%" of (yi * xtiles + xi) / (ytiles * xtiles) (realsr.cpp:481): the same lines
         // here, one per tile of every batch (a batch of tiles runs at once, so they arrive in bursts)
         rsr_set_progress_callback(ctxs[size_t(i)], [](int done, int total, void*) { fprintf(stderr, "%.2f%%\n", total ? 100.f * float(done - 1) / float(total) : 0.f); }, nullptr);
@@ -425,7 +440,7 @@ int main(int argc, char** argv)
                     fprintf(stderr, "image %s has alpha channel ! %s will output %s\n", v->inpath.c_str(), v->inpath.c_str(), out2.c_str());
                     v->outpath = out2;
                 }
-                v->outimage.create(v->inimage.w * scale, v->inimage.h * scale, v->inimage.elempack, true);
+                v->outimage.create(v->inimage.w * out_scale, v->inimage.h * out_scale, v->inimage.elempack, true);
                 toproc.put(std::move(v));
             }
         });

@@ -73,13 +73,13 @@ private:
 class RealSR
 {
 public:
-    RealSR(int gpuid, bool tta_mode = false, int num_threads = 1) : scale(4), tilesize(200), prepadding(10), ctx(nullptr)
+    RealSR(int gpuid, bool tta_mode = false, int num_threads = 1) : scale(4), tilesize(200), prepadding(10), out_scale(4), ctx(nullptr)
     {
         const int rc = rsr_create(&ctx, gpuid, tta_mode ? 1 : 0, num_threads);
         if (rc != RSR_OK) std::fprintf(stderr, "RealSR: %s\n", rsr_last_error(nullptr));
     }
     // adopt a context created elsewhere (rsr_create_group: the model arrives by one RCCL broadcast instead of load())
-    explicit RealSR(rsr_ctx* adopted) : scale(4), tilesize(200), prepadding(10), ctx(adopted) {}
+    explicit RealSR(rsr_ctx* adopted) : scale(4), tilesize(200), prepadding(10), out_scale(4), ctx(adopted) {}
     ~RealSR() { rsr_destroy(ctx); }
     RealSR(const RealSR&) = delete;
     RealSR& operator=(const RealSR&) = delete;
@@ -106,10 +106,11 @@ public:
     {
         if (!ctx) return RSR_E_STATE;
         int rc = rsr_set_params(ctx, scale, tilesize, prepadding);
+        if (rc == RSR_OK) rc = rsr_set_option(ctx, "out_scale", out_scale);
         if (rc == RSR_OK)
         {
-            if (outimage.w != inimage.w * scale || outimage.h != inimage.h * scale || outimage.elempack != inimage.elempack)
-                outimage.create(inimage.w * scale, inimage.h * scale, inimage.elempack, true);
+            if (outimage.w != inimage.w * out_scale || outimage.h != inimage.h * out_scale || outimage.elempack != inimage.elempack)
+                outimage.create(inimage.w * out_scale, inimage.h * out_scale, inimage.elempack, true);
             rc = rsr_process(ctx, inimage.data(), inimage.w, inimage.h, inimage.elempack, outimage.data());
         }
         if (rc != RSR_OK) std::fprintf(stderr, "RealSR::process: %s\n", rsr_last_error(ctx));
@@ -128,12 +129,13 @@ public:
         {
             if (!r->ctx) return RSR_E_STATE;
             if (rc == RSR_OK) rc = rsr_set_params(r->ctx, r0.scale, r0.tilesize, r0.prepadding);
+            if (rc == RSR_OK) rc = rsr_set_option(r->ctx, "out_scale", r0.out_scale);
             ctxs.push_back(r->ctx);
         }
         if (rc == RSR_OK)
         {
-            if (outimage.w != inimage.w * r0.scale || outimage.h != inimage.h * r0.scale || outimage.elempack != inimage.elempack)
-                outimage.create(inimage.w * r0.scale, inimage.h * r0.scale, inimage.elempack, true);
+            if (outimage.w != inimage.w * r0.out_scale || outimage.h != inimage.h * r0.out_scale || outimage.elempack != inimage.elempack)
+                outimage.create(inimage.w * r0.out_scale, inimage.h * r0.out_scale, inimage.elempack, true);
             rc = rsr_process_group(ctxs.data(), int(ctxs.size()), inimage.data(), inimage.w, inimage.h, inimage.elempack, outimage.data());
         }
         if (rc != RSR_OK) std::fprintf(stderr, "RealSR::process_group: %s\n", rsr_last_error(nullptr));
@@ -145,6 +147,9 @@ public:
     int scale;
     int tilesize;
     int prepadding;
+    // size of the output image relative to the input: 4 = `scale`, the network's own; 2 / 1 = that result box-reduced on the device
+    // (rsr_set_option "out_scale"; no counterpart in the reference)
+    int out_scale;
 
 private:
     rsr_ctx* ctx;

@@ -78,14 +78,14 @@ def _packed(x, d):
 
 
 def upscale(sr, x, out=None):
-    """x4 of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
-    with values in [0, 1], or uint8 (H, W, 3 | 4).  Returns a tensor of the same dtype and layout at 4x, enqueued on
+    """x4 -- or, with sr.out_scale 2 / 1, that result box-reduced on the device to x2 / x1 -- of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
+    with values in [0, 1], or uint8 (H, W, 3 | 4).  Returns a tensor of the same dtype and layout at 4x (out_scale x), enqueued on
     torch.cuda.current_stream(); a batch is ONE rsr_process_device_batch call on that stream.  A view that fits a descriptor (describe)
     is read in place; any other non-contiguous input is made contiguous first.
     out: the tensor to write (and return) instead of a new one: the result's shape, dtype and device, and itself a view that fits a
     descriptor -- a window of a larger canvas, say.  ValueError otherwise, before anything is launched.  It must not overlap x."""
     fmt, batched = _check(sr, x)
-    s = sr.scale
+    s = getattr(sr, "out_scale", sr.scale)  # (the context's output scale: 4 unless option "out_scale" says 2 or 1)
     shape = tuple(x.shape[:-3]) + ((x.shape[0] * s, x.shape[1] * s, x.shape[2]) if fmt == RSR_FMT_U8_HWC else (3, x.shape[-2] * s, x.shape[-1] * s))
     if out is not None:
         if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != x.dtype or out.device != x.device:
