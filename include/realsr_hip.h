@@ -91,6 +91,9 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
 #define RSR_FMT_U8_HWC 0  /* what rsr_process_device takes: uint8 [h][w][c], c in {3,4} */
 #define RSR_FMT_F16_CHW 1 /* planar fp16 [3][h][w], values in [0,1]; c must be 3 (tightly packed unless described by an rsr_image) */
 #define RSR_FMT_F32_CHW 2 /* planar fp32 [3][h][w], likewise */
+/* YUV 4:2:0 surfaces: what a hardware video decoder hands over and an encoder takes (ids 3 and 7 stay unknown) */
+#define RSR_FMT_NV12 4  /* uint8  Y [h][w], then interleaved UV [h/2][w/2][2]; c must be 3 */
+#define RSR_FMT_P010 5  /* uint16 little-endian, the code in the HIGH 10 bits (code << 6), same layout */
 
 /* rsr_process_device with a pixel format per side: what a tensor pipeline holds (float CHW in [0,1]) goes in and comes out without a
  * uint8 hop.  The two formats are independent; rsr_process_device(...) is exactly rsr_process_device_fmt(..., U8, ..., U8, ...).
@@ -109,14 +112,50 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
  * Out of scope: RGBA in planar form and a host-pointer variant (rsr_process stays uint8 HWC). */
 int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, int h, int c, void* d_out, int out_fmt, void* stream);
 
+/* RSR_FMT_NV12 / RSR_FMT_P010 on either side of rsr_process_device_fmt / rsr_process_device_batch, independently of the other side (NV12 ->
+ * NV12, P010 -> P010, NV12 -> F16_CHW, U8_HWC -> NV12 ...): the YUV <-> RGB conversion and the chroma resampling happen inside the pre- and
+ * post-processing kernels, so no RGB frame exists outside the library -- a 1080p frame at x4 would be 199 MB of fp16 RGB for 50 MB of
+ * NV12 -- and a 10-bit source never passes through 8 bits.  Everything said of the planar float formats holds: the stream contract, no
+ * merging with concurrent calls, batches grouped alike, windows whose outside stays untouched, TTA, "precise", "out_scale" 4 / 2 / 1.
+ * Option "bgr" concerns RGB sides only.
+ *   Layout.  A surface is a plane of Y [h][w] and a plane of interleaved (U, V) pairs [h/2][w/2][2]: `data` is Y(0,0); the row pitch serves
+ *            both planes (a UV row has as many bytes as a Y row); the UV plane starts at data + plane_pitch, 0 = h * row pitch (tightly
+ *            packed: rsr_image_bytes = w*h*3/2 for NV12, 3*w*h for P010).  rsr_process_device_fmt takes packed surfaces.
+ *   Errors.  RSR_E_ARG before anything is launched: c != 3; an odd w or h of a YUV input; a YUV output whose w * out_scale, h * out_scale or
+ *            tilesize * out_scale is odd (out_scale 1 only: no 2 x 2 chroma quad may cross a tile); P010 with an odd data pointer or pitch.
+ *   Options. "yuv_matrix" 709 [default] / 601 / 2020 and "yuv_range" 0 = limited [default] / 1 = full (rsr_set_option).  Chroma is sited at
+ *            the CENTRE of its 2 x 2 luma quad in both directions (MPEG-1 / JPEG siting); other sitings are out of scope.
+ *   The definition, exact.  All arithmetic is fp32; every multiplication and every addition is rounded by itself, in the order written (no
+ *   contraction).  Constants are computed in double from Kr and Kb -- 0.2126 / 0.0722 (709), 0.299 / 0.114 (601), 0.2627 / 0.0593 (2020),
+ *   Kg = 1 - Kr - Kb -- and rounded once to fp32, written fp32(.) below; rsr_yuv_constants returns them.  b = 8 (NV12) or 10 (P010) bits,
+ *   k = 2^(b-8).  Limited range: yoff = 16k, ys = 1/(219k), cs = 1/(224k), yscale = 219k, cscale = 224k; full range: yoff = 0,
+ *   ys = cs = 1/(2^b - 1), yscale = cscale = 2^b - 1.  coff = 2^(b-1) always.
+ *   Decode, image pixel (x, y) (a halo pixel: the reflect-101 index is taken first, exactly as for uint8 images):
+ *            Y is the code at (x, y) (P010: word >> 6).  U and V come from the four nearest chroma samples with weights 3/4 and 1/4 per
+ *            axis, indices clamped at the image edge: horizontally first, (3 * c_near + c_far) * 0.25f, then vertically the same way
+ *            (exact for codes).  yn = (Y - yoff) * ys, cb = (U - coff) * cs, cr = (V - coff) * cs;
+ *            R = yn + fp32(2(1-Kr)) * cr;  G = (yn - fp32(2Kb(1-Kb)/Kg) * cb) - fp32(2Kr(1-Kr)/Kg) * cr;  B = yn + fp32(2(1-Kb)) * cb.
+ *            Each of R, G, B is clamped to [0, 1] and rounded to fp16, to nearest even: the network input.
+ *   Encode.  d(x, y, q) = what RSR_FMT_F32_CHW holds at the context's out_scale (clamped, TTA-merged, box-reduced as defined there).
+ *            Y' = (Kr * R + Kg * G) + Kb * B; Y code = floor(Y' * yscale + (yoff + 0.5f)) clamped to [0, 2^b - 1].  Chroma of a 2 x 2 quad:
+ *            per channel m = ((d00 + d01) + (d10 + d11)) * 0.25f, Ym from m as Y' from d, Cb = (Bm - Ym) * fp32(1/(2(1-Kb))),
+ *            Cr = (Rm - Ym) * fp32(1/(2(1-Kr))), code = floor(C * cscale + (coff + 0.5f)) clamped alike.  P010 stores code << 6.
+ * On the output side conv_last leaves its planar blob and one more small launch (postproc_tiles_yuv) writes the surface: the route RGBA, TTA
+ * and "out_scale" below 4 take anyway.  Out of scope: host pointers (rsr_process*) and the CLI, which stay uint8 RGB(A). */
+
+/* Host-only: the fp32 constants of the definition above for yuv_matrix `matrix`, yuv_range `range` and `bits` = 8 / 10, the first n of
+ * { yoff, ys, coff, cs, 2(1-Kr), 2Kb(1-Kb)/Kg, 2Kr(1-Kr)/Kg, 2(1-Kb), Kr, Kg, Kb, yscale, yoff + 0.5, cscale, coff + 0.5, 1/(2(1-Kb)),
+ * 1/(2(1-Kr)), 2^b - 1 } (18 values).  RSR_E_ARG for any other matrix, range or depth. */
+int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
+
 /* A device image behind its own pointer and pitches: a whole tensor, a crop of a larger frame, a frame inside a padded decoder surface, a
  * window of a canvas.  Pitches are in BYTES.  A uint8 row pitch need not be a multiple of the pixel size; for the planar formats both
  * pitches and `data` must be multiples of the element size (2 / 4).  No further alignment is asked of `data`. */
 typedef struct rsr_image
 {
-    void* data;            /* device pointer to element (0,0) [of plane 0] */
+    void* data;            /* device pointer to element (0,0) [of plane 0; NV12 / P010: Y(0,0)] */
     long long row_pitch;   /* bytes from one row to the next; 0 = tightly packed */
-    long long plane_pitch; /* planar formats: bytes from one plane to the next; 0 = h * row pitch.  Ignored for uint8 HWC */
+    long long plane_pitch; /* planar formats: bytes from one plane to the next (NV12 / P010: from `data` to the UV plane); 0 = h * row pitch.  Ignored for uint8 HWC */
 } rsr_image;
 
 /* n images of ONE geometry (w x h x c, in_fmt -> out_fmt), each with its own pointer and pitches: what a tensor pipeline holds as an
@@ -146,8 +185,8 @@ int rsr_process_device_batch(rsr_ctx* ctx, int n, const rsr_image* in, int in_fm
  * rsr_image_bytes), or RSR_E_ARG for a combination rsr_process_device_batch refuses. */
 long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch);
 
-/* Host-only: bytes of a w x h x c image in `fmt` (a negative RSR_E_ARG for a bad combination: unknown format, planar with c != 3,
- * uint8 with c not in {3,4}, w or h < 1). */
+/* Host-only: bytes of a w x h x c image in `fmt` (a negative RSR_E_ARG for a bad combination: unknown format, planar or YUV with c != 3,
+ * uint8 with c not in {3,4}, w or h < 1, YUV with an odd w or h).  NV12: w*h*3/2, P010: 3*w*h. */
 long long rsr_image_bytes(int fmt, int w, int h, int c);
 
 /* Pinned host memory for images.  rsr_process copies pinned buffers (these, hipHostMalloc'd or hipHostRegister'ed
@@ -381,6 +420,9 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *                       The clamp comes BEFORE the mean (the mean of the x4 image one would have got, not of the raw network output);
  *                       a box never crosses a tile.  Below 4, conv_last leaves its planar blob and one more small launch
  *                       (postproc_tiles_box) writes the image: the route RGBA and TTA take anyway
+ *   "yuv_matrix"        709 [default], 601 or 2020: Kr / Kb of the RSR_FMT_NV12 / RSR_FMT_P010 conversion; "yuv_range": 0 [default] = limited (16..235 /
+ *                       16..240 at 8 bits), 1 = full.  Any other value: RSR_E_ARG, the value in force stays (stats "yuv_matrix", "yuv_range").
+ *                       Both take effect for the next call, like "out_scale" (rsr_process_device_fmt has the definition)
  *   "precise_auto"      1: "precise" is set by the model: on a loaded context rsr_selfcheck runs at once on the built-in tile and "precise"
  *                       becomes its recommend_precise; on a context not yet loaded the same happens at the end of the next successful
  *                       rsr_load / rsr_load_packed (which then returns the self-check's error, if it has one; the model stays loaded).
@@ -429,7 +471,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *                       rsr_process_group allocates only the output rows of its tile range)
  *   "last_test_us"      HIP-event time of the last rsr_conv3x3 / rsr_conv3x3_res launch (with option "test_repeat" = N the
  *                       work items are repeated N times in that one launch: an L2-resident workload)
- *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force
+ *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force; "yuv_matrix" / "yuv_range": likewise
  *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
  *                       "selfcheck_overflow" (-1 before the first run) */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);

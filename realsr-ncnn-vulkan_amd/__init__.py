@@ -30,6 +30,7 @@ EXPORTS = [
     "rsr_selfcheck", "rsr_selfcheck_tile", "rsr_selfcheck_ranges",
     "rsr_process_device_fmt", "rsr_image_bytes",
     "rsr_process_device_batch", "rsr_image_span",
+    "rsr_yuv_constants",
 ]
 
 NUM_CONVS = 351
@@ -37,6 +38,8 @@ NUM_CONVS = 351
 RSR_OK, RSR_E_ARG, RSR_E_IO, RSR_E_FORMAT, RSR_E_GRAPH, RSR_E_DEVICE, RSR_E_STATE, RSR_E_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 # pixel formats of device-resident images (rsr_process_device_fmt): uint8 HWC, planar fp16 / fp32 [3][h][w] in [0, 1]
 RSR_FMT_U8_HWC, RSR_FMT_F16_CHW, RSR_FMT_F32_CHW = 0, 1, 2
+# YUV 4:2:0 surfaces: Y [h][w] then interleaved UV [h/2][w/2][2]; uint8, or uint16 with the 10-bit code in the high bits
+RSR_FMT_NV12, RSR_FMT_P010 = 4, 5
 
 
 class Profile(C.Structure):
@@ -108,6 +111,7 @@ def lib():
     L.rsr_process_device_batch.argtypes = [vp, ip, C.POINTER(Image), ip, ip, ip, ip, C.POINTER(Image), ip, vp]
     L.rsr_image_span.argtypes = [ip, ip, ip, ip, C.c_longlong, C.c_longlong]
     L.rsr_image_span.restype = C.c_longlong
+    L.rsr_yuv_constants.argtypes = [ip, ip, ip, C.POINTER(C.c_float), ip]
     L.rsr_model_pack.argtypes = [cp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_device_memory.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rsr_host_alloc.argtypes = [C.c_size_t]
@@ -494,11 +498,20 @@ def selfcheck_tile(w=0, h=0):
 
 
 def image_bytes(fmt, w, h, c=3):
-    """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*)."""
+    """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*; NV12: w*h*3/2, P010: 3*w*h)."""
     n = lib().rsr_image_bytes(int(fmt), int(w), int(h), int(c))
     if n < 0:
         raise RealSRError(int(n), lib().rsr_last_error(None).decode())
     return int(n)
+
+
+def yuv_constants(matrix=709, range_=0, bits=8):
+    """rsr_yuv_constants (host-only): the 18 float32 constants of the NV12 / P010 definition (include/realsr_hip.h) as an array."""
+    out = np.zeros(18, dtype=np.float32)
+    rc = lib().rsr_yuv_constants(int(matrix), int(range_), int(bits), out.ctypes.data_as(C.POINTER(C.c_float)), 18)
+    if rc != RSR_OK:
+        raise RealSRError(rc, lib().rsr_last_error(None).decode())
+    return out
 
 
 def _images(entries):

@@ -1,4 +1,5 @@
 // capi.cpp -- extern "C" entry points declared in include/realsr_hip.h.
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
@@ -202,6 +203,7 @@ long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long
     const int rc = rsr::image_layout(fmt, w, h, c, row_pitch, plane_pitch, &row, &plane);
     if (rc != RSR_OK) return rc;
     // all pitches are positive: the last element of the last row of the last plane lies farthest from `data`
+    if (rsr::fmt_is_yuv(fmt)) return plane + (long long)(h / 2 - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c); // (the UV plane: h / 2 rows as long as a Y row)
     return (fmt == RSR_FMT_U8_HWC ? 0 : 2 * plane) + (long long)(h - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
 }
 
@@ -212,7 +214,21 @@ long long rsr_image_bytes(int fmt, int w, int h, int c)
     if (fmt == RSR_FMT_U8_HWC && (c == 3 || c == 4)) return px * c;
     if (fmt == RSR_FMT_F16_CHW && c == 3) return px * 6;
     if (fmt == RSR_FMT_F32_CHW && c == 3) return px * 12;
+    if (rsr::fmt_is_yuv(fmt) && c == 3)
+    {
+        if ((w | h) & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
+        return fmt == RSR_FMT_NV12 ? px * 3 / 2 : px * 3;
+    }
     return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
+}
+
+int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n)
+{
+    rsr::YuvCoef c;
+    if (!out || n < 0 || !rsr::yuv_coef(matrix, range, bits, &c)) return Engine::fail(RSR_E_ARG, "rsr_yuv_constants: no such matrix / range / bit depth");
+    static_assert(sizeof c == rsr::kYuvCoefFloats * sizeof(float), "YuvCoef is an array of floats");
+    std::memcpy(out, &c, size_t(std::min(n, rsr::kYuvCoefFloats)) * sizeof(float));
+    return RSR_OK;
 }
 
 int rsr_model_pack(const char* parampath, const char* modelpath, void* dst, size_t cap, size_t* need)
@@ -516,6 +532,8 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "merged_mixed") *value = double(e.merged_mixed.load());
     else if (k == "precise_active") *value = e.precise ? 1.0 : 0.0;
     else if (k == "out_scale") *value = double(e.out_scale);
+    else if (k == "yuv_matrix") *value = double(e.yuv_matrix);
+    else if (k == "yuv_range") *value = double(e.yuv_range);
     else if (k == "selfcheck_runs") *value = double(e.selfcheck_runs);
     else if (k == "selfcheck_headroom") *value = e.selfcheck_runs ? double(e.sc_last.headroom) : -1.0;
     else if (k == "selfcheck_peak_abs") *value = e.selfcheck_runs ? double(e.sc_last.peak_abs) : -1.0;
@@ -561,6 +579,16 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     { // the next call's output is (w * value) x (h * value): plans are keyed by it (below 4 conv_last leaves the planar blob to postproc_tiles_box)
         if (value != 1 && value != 2 && value != 4) return ctx->e.fail(RSR_E_ARG, "out_scale must be 1, 2 or 4");
         ctx->e.out_scale = int(value);
+    }
+    else if (k == "yuv_matrix")
+    { // Kr / Kb of the NV12 / P010 formats; read when the next call is enqueued
+        if (value != 709 && value != 601 && value != 2020) return ctx->e.fail(RSR_E_ARG, "yuv_matrix must be 709, 601 or 2020");
+        ctx->e.yuv_matrix = int(value);
+    }
+    else if (k == "yuv_range")
+    {
+        if (value != 0 && value != 1) return ctx->e.fail(RSR_E_ARG, "yuv_range must be 0 (limited) or 1 (full)");
+        ctx->e.yuv_range = int(value);
     }
     else if (k == "precise_auto")
     { // the model decides: now when one is loaded, else at the end of the next load (rsr_load / rsr_load_packed)

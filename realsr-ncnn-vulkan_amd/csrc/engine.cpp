@@ -727,7 +727,7 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
 {
     const int nslots = std::min(nslots_used, b.nslots);
     const long long cap = ws_cap_px;
-    const bool fused = io && conv_last_writes_image(io->c); // conv_last writes the images of io itself, else the planar b_out3 blob
+    const bool fused = io && conv_last_writes_image(io->c, io->out_fmt); // conv_last writes the images of io itself, else the planar b_out3 blob
     const int split_slot = io ? io->split_slot : 0;
     // the throttle event of a merged batch (Engine::submit_merged): behind the RDB that leaves about half an image's worth of network
     // ahead -- the time the next batch's launches take to enqueue
@@ -1003,7 +1003,7 @@ int Engine::enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size
         if (ntiles <= 0) break;
         // host calls: split the 4x tail at a tile-row boundary so that the first output rows can travel while the rest is computed
         io.split_slot = 0;
-        if (conv_last_writes_image(c) && nimg == 1 && io.ev_half && half_rows && plan.batches.size() == 1 && !profiling && !(dbg & 16384))
+        if (conv_last_writes_image(c, io.out_fmt) && nimg == 1 && io.ev_half && half_rows && plan.batches.size() == 1 && !profiling && !(dbg & 16384))
         {
             const int xt = xtiles, yt = b.ntiles / xt;
             if (yt >= 2 && b.ntiles == xt * yt && plan.tile0 % xt == 0)
@@ -1062,12 +1062,16 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     pa.bgr = bgr ? 1 : 0;
     pa.plane_ch = pc;
     pa.variant = variant;
+    if (fmt_is_yuv(io.in_fmt) && !yuv_coef(yuv_matrix, yuv_range, io.in_fmt == RSR_FMT_P010 ? 10 : 8, &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
+    if (fmt_is_yuv(io.out_fmt) && !yuv_coef(yuv_matrix, yuv_range, io.out_fmt == RSR_FMT_P010 ? 10 : 8, &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     launch_preproc_tiles(pa, max_tw, max_th, st);
-    // bytes of a pixel in the caller's image: c for uint8 HWC, 3 halfs / floats for the planar formats
-    auto px_bytes = [c](int fmt) { return fmt == RSR_FMT_F16_CHW ? 6.0 : (fmt == RSR_FMT_F32_CHW ? 12.0 : double(c)); };
+    // bytes of a pixel in the caller's image: c for uint8 HWC, 3 halfs / floats for the planar formats, 1.5 samples for the 4:2:0 surfaces
+    auto px_bytes = [c](int fmt) {
+        return fmt == RSR_FMT_F16_CHW ? 6.0 : (fmt == RSR_FMT_F32_CHW ? 12.0 : (fmt == RSR_FMT_NV12 ? 1.5 : (fmt == RSR_FMT_P010 ? 3.0 : double(c))));
+    };
     mark(0, 0, b.px[0] / per * px_bytes(io.in_fmt) + b.px[0] * 64, st);
     const int rc = run_network(b, st, ntiles * per, &io, nullptr);
-    if (rc != RSR_OK || conv_last_writes_image(c)) return rc;
+    if (rc != RSR_OK || conv_last_writes_image(c, io.out_fmt)) return rc;
     po.planar3 = b_out3.p;
     po.f32 = precise ? 1 : 0;
     po.slot_stride = cap_px * (precise ? 192 : 96);
@@ -1145,9 +1149,12 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
     if (!d_in || !d_out || w < 1 || h < 1 || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
     for (const int f : {in_fmt, out_fmt})
     {
-        if (f != RSR_FMT_U8_HWC && f != RSR_FMT_F16_CHW && f != RSR_FMT_F32_CHW) return fail(RSR_E_ARG, "unknown pixel format");
-        if (f != RSR_FMT_U8_HWC && c != 3) return fail(RSR_E_ARG, "the planar float formats are RGB only (c == 3)");
+        if (f != RSR_FMT_U8_HWC && f != RSR_FMT_F16_CHW && f != RSR_FMT_F32_CHW && !fmt_is_yuv(f)) return fail(RSR_E_ARG, "unknown pixel format");
+        if (f != RSR_FMT_U8_HWC && c != 3) return fail(RSR_E_ARG, "the planar float and the YUV formats come with c == 3 only");
     }
+    if (fmt_is_yuv(in_fmt) && ((w | h) & 1)) return fail(RSR_E_ARG, "a YUV 4:2:0 input needs an even width and height");
+    if ((in_fmt == RSR_FMT_P010 && (reinterpret_cast<uintptr_t>(d_in) & 1)) || (out_fmt == RSR_FMT_P010 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
+        return fail(RSR_E_ARG, "P010 data is not aligned to its 16-bit samples");
     const bool u8 = in_fmt == RSR_FMT_U8_HWC && out_fmt == RSR_FMT_U8_HWC;
     hipEvent_t done = nullptr;
     if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
@@ -1185,6 +1192,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
         std::lock_guard<std::mutex> lk(mu);
         if (!loaded) return fail(RSR_E_STATE, "process before load");
         if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
+        if (const int rc = check_yuv_out(out_fmt, w, h, out_scale)) return rc;
         HIP_TRY(hipSetDevice(device));
         if (user_stream && hipStreamQuery(stream) == hipSuccess)
         {
@@ -1238,12 +1246,47 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
     return RSR_OK;
 }
 
+// ---- YUV 4:2:0 surfaces (RSR_FMT_NV12 / RSR_FMT_P010) ------------------------------------------------------------------------------
+// Every constant is computed in double from Kr and Kb and rounded ONCE to fp32 (include/realsr_hip.h "yuv_matrix"; tests/yuv_ref.py writes
+// the same expressions).
+bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
+{
+    double kr, kb;
+    if (matrix == 709) kr = 0.2126, kb = 0.0722;
+    else if (matrix == 601) kr = 0.299, kb = 0.114;
+    else if (matrix == 2020) kr = 0.2627, kb = 0.0593;
+    else return false;
+    if ((range != 0 && range != 1) || (bits != 8 && bits != 10)) return false;
+    const double kg = 1.0 - kr - kb, k = double(1 << (bits - 8)), top = double((1 << bits) - 1);
+    const double yoff = range ? 0.0 : 16.0 * k, coff = double(1 << (bits - 1));
+    const double yscale = range ? top : 219.0 * k, cscale = range ? top : 224.0 * k;
+    YuvCoef c;
+    c.yoff = float(yoff), c.ys = float(1.0 / yscale), c.coff = float(coff), c.cs = float(1.0 / cscale);
+    c.rv = float(2.0 * (1.0 - kr)), c.gu = float(2.0 * kb * (1.0 - kb) / kg), c.gv = float(2.0 * kr * (1.0 - kr) / kg), c.bu = float(2.0 * (1.0 - kb));
+    c.kr = float(kr), c.kg = float(kg), c.kb = float(kb);
+    c.yscale = float(yscale), c.yadd = float(yoff) + 0.5f, c.cscale = float(cscale), c.cadd = float(coff) + 0.5f;
+    c.icb = float(1.0 / (2.0 * (1.0 - kb))), c.icr = float(1.0 / (2.0 * (1.0 - kr))), c.maxcode = float(top);
+    *out = c;
+    return true;
+}
+
+// A YUV output is written one 2 x 2 luma quad per thread, tile by tile: the image and every tile's rectangle must start and end on even
+// output pixels (only out_scale 1 can break that).  mu held (tilesize).
+int Engine::check_yuv_out(int out_fmt, int w, int h, int os) const
+{
+    if (!fmt_is_yuv(out_fmt)) return RSR_OK;
+    if (((w * os) | (h * os) | (tilesize * os)) & 1)
+        return fail(RSR_E_ARG, "a YUV 4:2:0 output needs w * out_scale, h * out_scale and tilesize * out_scale even");
+    return RSR_OK;
+}
+
 // ---- tensor batches: n images of one geometry behind descriptors (include/realsr_hip.h rsr_process_device_batch) ------------------
 int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane)
 {
     if (w < 1 || h < 1) return Engine::fail(RSR_E_ARG, "bad image size");
-    if (fmt != RSR_FMT_U8_HWC && fmt != RSR_FMT_F16_CHW && fmt != RSR_FMT_F32_CHW) return Engine::fail(RSR_E_ARG, "unknown pixel format");
+    if (fmt != RSR_FMT_U8_HWC && fmt != RSR_FMT_F16_CHW && fmt != RSR_FMT_F32_CHW && !fmt_is_yuv(fmt)) return Engine::fail(RSR_E_ARG, "unknown pixel format");
     if (fmt == RSR_FMT_U8_HWC ? (c != 3 && c != 4) : c != 3) return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
+    if (fmt_is_yuv(fmt) && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
     if (row_pitch < 0 || plane_pitch < 0) return Engine::fail(RSR_E_ARG, "negative pitch");
     const long long es = BatchIO::px_bytes(fmt, c), packed = w * es;
     const long long rp = row_pitch ? row_pitch : packed;
@@ -1291,6 +1334,7 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
         if (!loaded) return fail(RSR_E_STATE, "process before load");
         if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
         if (out_scale != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
+        if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
         HIP_TRY(hipSetDevice(device));
         // As in process_device: an idle engine runs the call on the caller's own stream, a busy one on the compute stream between two events.
         const bool direct = user_stream && hipStreamQuery(stream) == hipSuccess;

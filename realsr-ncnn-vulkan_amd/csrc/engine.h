@@ -148,7 +148,8 @@ struct BatchIO
     // Bytes from one row / one plane (planar formats) of an image to the next, resolved (never 0; rsr_image of the C ABI, image_layout).
     // The constructors set the tightly packed values; Engine::process_device_batch overwrites them with the caller's.
     long long in_pitch[kMaxMerge], in_plane[kMaxMerge], out_pitch[kMaxMerge], out_plane[kMaxMerge];
-    int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float formats come with whole images of c == 3 only)
+    int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float and the YUV formats come with whole images of c == 3 only;
+                                                           // YUV: the plane pitch is the distance from Y(0,0) to the UV plane)
     int out_row0 = 0;           // `out` points at output row out_row0 * os / 4 of the image; out_row0 counts x4 rows (a tile range's device buffer holds only its rows)
     int split_slot = 0;         // > 0: the 4x tail is split in front of this slot and ...
     hipEvent_t ev_half = nullptr; // ... this event recorded behind the first part (the caller starts downloading its output rows)
@@ -162,7 +163,10 @@ struct BatchIO
         for (int i = 0; i < n; i++) set(i, g[i]->d_in, g[i]->d_out, g[i]->w, g[i]->h);
     }
     BatchIO(int n, int c0, int in_fmt0, int out_fmt0, int os0) : nimg(n), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
-    static long long px_bytes(int fmt, int c) { return fmt == RSR_FMT_F16_CHW ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : c); } // of one element of a row
+    static long long px_bytes(int fmt, int c) // of one element of a row (NV12 / P010: of one sample; a UV row has as many bytes as a Y row)
+    {
+        return fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_P010 ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : (fmt == RSR_FMT_NV12 ? 1 : c));
+    }
     void set(int i, const void* d_in, void* d_out, int wi, int hi) // image i, tightly packed (the output is x os)
     {
         in[i] = d_in, out[i] = d_out, w[i] = wi, h[i] = hi;
@@ -200,6 +204,9 @@ struct Engine
     // [0, 1] first, leaves as its fp32 mean.  A box never crosses a tile (a tile's x4 rectangle starts and ends on multiples of 4), so the
     // reduction is the per-tile post-processing launch (kernels.hip postproc_tiles_box); conv_last then leaves the planar blob.
     int out_scale = 4;
+    // YUV <-> RGB of the NV12 / P010 device formats (options "yuv_matrix", "yuv_range"; include/realsr_hip.h): Kr / Kb of BT.709, 601 or
+    // 2020, limited (0) or full (1) range.  Read when a call is enqueued: the constants travel with the launch (kernels.h YuvCoef).
+    int yuv_matrix = 709, yuv_range = 0;
     // Model self-check (include/realsr_hip.h rsr_selfcheck): one tile through the network in both storages, compared on the device.
     bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
     long long selfcheck_runs = 0;
@@ -330,7 +337,9 @@ struct Engine
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
-    bool conv_last_writes_image(int c) const { return !tta && c == 3 && out_scale == 4 && !(dbg & 8192); } // no TTA merge / alpha channel / box reduction needs the planar blob (dbg 8192: off)
+    // no TTA merge / alpha channel / box reduction / YUV 4:2:0 surface needs the planar blob (dbg 8192: off)
+    bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_scale == 4 && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
+    int check_yuv_out(int out_fmt, int w, int h, int os) const; // RSR_E_ARG when a 2 x 2 chroma quad of a YUV output would cross the image or a tile
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
     // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).
@@ -372,6 +381,9 @@ struct Engine
 // Host-only: the resolved row and plane pitch (bytes) of a w x h x c image in `fmt` described with row_pitch / plane_pitch (0 = tightly
 // packed), or RSR_E_ARG (through Engine::fail) for a combination rsr_process_device_batch refuses.  plane = 0 for uint8 HWC.
 int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane);
+// Host-only: the constants of the YUV definition for a matrix (709 / 601 / 2020), a range (0 limited, 1 full) and a bit depth (8 / 10);
+// false for any other combination.
+bool yuv_coef(int matrix, int range, int bits, YuvCoef* out);
 void selfcheck_tile(uint16_t* dst, int w, int h); // host-only: the built-in tile of the self-check, planar fp16 [3][h][w]
 const char* last_error(); // message of the calling thread's last failure
 long long share_pool_stat(int what); // group.cpp: 0 = worker threads of rsr_process_group's pool, 1 = shares run inline because no worker could be started

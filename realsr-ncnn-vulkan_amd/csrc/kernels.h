@@ -36,6 +36,11 @@ constexpr int kMaxMerge = 16;
 // Pixel formats of the caller's images (the RSR_FMT_* values of include/realsr_hip.h).  The planar formats are RGB only, [3][h][w],
 // values in [0, 1]; they ride in the same pointer arrays as the uint8 images (PreArgs::imgs, PostArgs::outs, ConvArgs::out_u8s).
 constexpr int kFmtU8 = 0, kFmtF16 = 1, kFmtF32 = 2;
+// YUV 4:2:0 surfaces, as a video decoder yields and an encoder takes them (RSR_FMT_NV12 / RSR_FMT_P010): a plane of Y [h][w], then --
+// `plane pitch` bytes behind Y(0,0) -- a plane of interleaved UV [h/2][w/2][2] whose rows are as many bytes apart as the Y rows.  uint8
+// codes, or uint16 words that hold a 10-bit code in their HIGH bits (code << 6).  w and h are even.
+constexpr int kFmtNV12 = 4, kFmtP010 = 5;
+constexpr bool fmt_is_yuv(int fmt) { return fmt == kFmtNV12 || fmt == kFmtP010; }
 // Every image is addressed through its own ROW PITCH and (planar formats) PLANE PITCH, both in BYTES (rsr_image of the C ABI): a crop of
 // a larger frame, a window of a canvas.  A uint8 pitch need not be a multiple of the pixel size and a base pointer is aligned to the
 // element only, so the image accesses are element-sized (the LDS-staged pre / post kernels, which move dwords, align by themselves or
@@ -140,6 +145,18 @@ hipError_t kernels_init_device();
 hipError_t flow_init_device();
 
 // ---- pre / post ------------------------------------------------------------------------------
+// The fp32 constants of the YUV <-> RGB definition of include/realsr_hip.h ("yuv_matrix"), each computed in double and rounded once
+// (engine.cpp yuv_coef): a function of the matrix, the range and the bit depth of the surface.  The kernels use them with one rounding per
+// operation, in the order the header writes (kernels.hip mul_rn / add_rn: nothing is contracted).
+struct YuvCoef
+{
+    // decode: yn = (Y - yoff) * ys, cb = (U - coff) * cs, cr = (V - coff) * cs; R = yn + rv * cr, G = (yn - gu * cb) - gv * cr, B = yn + bu * cb
+    float yoff, ys, coff, cs, rv, gu, gv, bu;
+    // encode: Y' = (kr * R + kg * G) + kb * B, code floor(Y' * yscale + yadd); Cb = (B - Y') * icb, Cr = (R - Y') * icr, code floor(C * cscale + cadd)
+    float kr, kg, kb, yscale, yadd, cscale, cadd, icb, icr, maxcode;
+};
+constexpr int kYuvCoefFloats = 18;
+
 struct BaseTile
 {
     int x_org, y_org; // image coords of padded-tile pixel (0,0)  (= xi*T - P, yi*T - P)
@@ -153,7 +170,8 @@ struct BaseTile
 struct PreArgs
 {
     const uint8_t* imgs[kMaxMerge]; // HWC u8, one per image of the batch (ws[i] x hs[i] x c); BaseTile::img selects
-    int fmt;                        // kFmtU8, or kFmtF16 / kFmtF32: the images are planar [3][hs[i]][ws[i]] of that type (c == 3)
+    int fmt;                        // kFmtU8, or kFmtF16 / kFmtF32: the images are planar [3][hs[i]][ws[i]] of that type (c == 3),
+                                    // or kFmtNV12 / kFmtP010: Y at imgs[i], UV plane[i] bytes behind it, decoded with `yuv`; bgr does not apply
     int ws[kMaxMerge], hs[kMaxMerge];
     int pitch[kMaxMerge];           // bytes from one row of image i to the next (>= ws[i] * pixel size) ...
     long long plane[kMaxMerge];     // ... and, planar formats, from one plane to the next
@@ -167,6 +185,7 @@ struct PreArgs
     int bgr;
     int plane_ch;   // 16
     int variant;    // 0 default (launch_preproc_tiles picks), 1 one thread per pixel (engine dbg 32768), 2 LDS-staged (dbg 65536; uint8 sources only)
+    YuvCoef yuv;    // fmt kFmtNV12 / kFmtP010 only
 };
 void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t st);
 
@@ -180,7 +199,8 @@ struct PostArgs
     int tta;
     int crop;   // prepadding*scale
     uint8_t* outs[kMaxMerge]; // HWC u8 (4w x 4h x c), one per image of the batch
-    int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][4h][4w] of that type (c == 3; see ConvArgs::out_fmt)
+    int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][4h][4w] of that type (c == 3; see ConvArgs::out_fmt),
+                              // or kFmtNV12 / kFmtP010: Y at outs[i], UV out_plane[i] bytes behind it (postproc_tiles_yuv; box 0 / 1, 2 and 4 alike)
     long long out_plane[kMaxMerge]; // planar formats: bytes from one plane of `outs[i]` to the next
     int out_pitch[kMaxMerge]; // row pitches of the outs in bytes
     int in_pitch[kMaxMerge];  // ... and those of the source images
@@ -195,6 +215,7 @@ struct PostArgs
     // to [0, 1] first, leaves as ONE pixel, its fp32 mean (postproc_tiles_box): the outs are (4 / K)w x (4 / K)h.  Everything above stays in
     // x4 units (BaseTile::out_*, out_row0, crop: all multiples of 4); the kernel divides by K.
     int box;
+    YuvCoef yuv; // out_fmt kFmtNV12 / kFmtP010 only
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 

@@ -2,6 +2,7 @@
 //
 //   preproc_tiles[_lds]    realsr_preproc{,_tta}.comp equivalent, writes the network input planes (from uint8 HWC or planar fp16 / fp32 images)
 //   postproc_tiles[_lds]   realsr_postproc{,_tta}.comp equivalent, writes the uint8 HWC image (or a planar fp16 / fp32 one)
+//   preproc_tiles<., true> / postproc_tiles_yuv   the same with an NV12 / P010 surface on that side (YUV <-> RGB inside the kernel)
 //                          (_lds: rows staged in LDS, dword loads / 1-KiB stores, transposed TTA variants through an LDS tile;
 //                          chosen per launch by measurement: launch_*_tiles)
 //   *_shader               the same arithmetic in the shaders' own memory layout (parity tests)
@@ -33,6 +34,82 @@ __device__ __forceinline__ int reflect101(int v, int n)
     return min(max(v, 0), n - 1);
 }
 
+// ---- YUV 4:2:0 sources (PreArgs::fmt kFmtNV12 / kFmtP010) -------------------------------------------------------------------------
+// ONE fp32 operation, rounded by itself.  HIP's __fmul_rn / __fadd_rn are the plain operators, which the compiler contracts with their
+// neighbours into an fma once they are inlined; an operation compiled with contraction off takes no part in that.
+__device__ __forceinline__ float mul_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// The (U, V) pair of chroma sample cx of a UV row: ONE 2-byte (NV12) or 4-byte (P010) load where the address allows it -- an NV12 surface
+// may start on any byte, a P010 surface on any even one.
+template <typename SRC>
+__device__ __forceinline__ void load_uv(const uint8_t* row, int cx, float& u, float& v)
+{
+    const uint8_t* p = row + (long long)cx * (2 * (int)sizeof(SRC));
+    if constexpr (sizeof(SRC) == 1)
+    {
+        unsigned w;
+        if (!(reinterpret_cast<uintptr_t>(p) & 1)) w = *reinterpret_cast<const unsigned short*>(p);
+        else w = (unsigned)p[0] | ((unsigned)p[1] << 8);
+        u = (float)(w & 0xffu);
+        v = (float)(w >> 8);
+    }
+    else
+    {
+        unsigned w;
+        if (!(reinterpret_cast<uintptr_t>(p) & 3)) w = *reinterpret_cast<const unsigned*>(p);
+        else w = (unsigned)reinterpret_cast<const unsigned short*>(p)[0] | ((unsigned)reinterpret_cast<const unsigned short*>(p)[1] << 16);
+        u = (float)((w & 0xffffu) >> 6);
+        v = (float)(w >> 22);
+    }
+}
+
+// RGB in [0, 1] of pixel (x, y) of a w x h surface (Y at img, rows `pitch` bytes apart; UV `plane` bytes behind Y(0,0), same pitch).
+// Chroma is sited at the centre of its 2 x 2 luma quad: a luma pixel takes 3/4 of the chroma sample of its own quad and 1/4 of the next
+// one on its side, per axis, indices clamped at the image edge -- horizontally first, (3 * near + far) * 0.25f, then vertically the same
+// way: exact for codes.  Lanes run along x: the Y loads of a wave are contiguous, a pair of neighbouring lanes shares its near chroma
+// column, and U and V always travel in one load.  Every product and sum below is rounded by itself (no contraction).
+template <typename SRC>
+__device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long long plane, int x, int y, int w, int h, const YuvCoef& k, float (&rgb)[3])
+{
+    const uint8_t* yp = img + (long long)y * pitch + (long long)x * (int)sizeof(SRC);
+    float Y;
+    if constexpr (sizeof(SRC) == 1) Y = (float)*yp;
+    else Y = (float)(*reinterpret_cast<const unsigned short*>(yp) >> 6);
+    const int cxn = x >> 1, cxf = min(max(cxn + ((x & 1) ? 1 : -1), 0), (w >> 1) - 1);
+    const int cyn = y >> 1, cyf = min(max(cyn + ((y & 1) ? 1 : -1), 0), (h >> 1) - 1);
+    const uint8_t* rn = img + plane + (long long)cyn * pitch;
+    const uint8_t* rf = img + plane + (long long)cyf * pitch;
+    float unn, vnn, unf, vnf, ufn, vfn, uff, vff; // (row, column): near / far
+    load_uv<SRC>(rn, cxn, unn, vnn);
+    load_uv<SRC>(rn, cxf, unf, vnf);
+    load_uv<SRC>(rf, cxn, ufn, vfn);
+    load_uv<SRC>(rf, cxf, uff, vff);
+    auto mix = [](float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); };
+    const float U = mix(mix(unn, unf), mix(ufn, uff)), V = mix(mix(vnn, vnf), mix(vfn, vff));
+    const float yn = mul_rn(sub_rn(Y, k.yoff), k.ys);
+    const float cb = mul_rn(sub_rn(U, k.coff), k.cs), cr = mul_rn(sub_rn(V, k.coff), k.cs);
+    const float r = add_rn(yn, mul_rn(k.rv, cr));
+    const float g = sub_rn(sub_rn(yn, mul_rn(k.gu, cb)), mul_rn(k.gv, cr));
+    const float b = add_rn(yn, mul_rn(k.bu, cb));
+    rgb[0] = fminf(fmaxf(r, 0.f), 1.f);
+    rgb[1] = fminf(fmaxf(g, 0.f), 1.f);
+    rgb[2] = fminf(fmaxf(b, 0.f), 1.f);
+}
+
 // realsr_preproc.comp:47-95 and realsr_preproc_tta.comp:54-113, for a batch of tiles.
 // One thread per padded-tile pixel; writes the 32-channel fp16 input plane(s) (channels 3..31 = 0).
 // The band-relative coordinates of the shader (crop_x/crop_y/pad) are folded into x_org/y_org:
@@ -41,7 +118,9 @@ __device__ __forceinline__ int reflect101(int v, int n)
 // input (the uint8 path makes fp16(float(k) * (1/255.f)) of byte k: those halfs give that path's input exactly); a float is rounded to
 // fp16, to nearest even.  Lanes run along x: the three plane reads of a wave are contiguous.  Rows are PreArgs::pitch bytes apart, planes
 // PreArgs::plane: the reflected (x, y) is an index into the image, never into the surface around it.
-template <typename SRC>
+// YUV = true: the image is a 4:2:0 surface, SRC its sample type -- uint8_t (NV12) or uint16_t (P010, the code in the high 10 bits).  Pixel
+// (x, y) -- reflected first, like every other source -- is decoded as include/realsr_hip.h ("yuv_matrix") defines, bit for bit: yuv_decode.
+template <typename SRC, bool YUV = false>
 __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -51,11 +130,19 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     const int im = __builtin_amdgcn_readfirstlane(t.img), iw = a.ws[im], ih = a.hs[im];
     const int x = reflect101(gx + t.x_org, iw);
     const int y = reflect101(gy + t.y_org, ih);
-    const int i0 = a.bgr ? 2 : 0, i2 = a.bgr ? 0 : 2;
+    [[maybe_unused]] const int i0 = a.bgr ? 2 : 0, i2 = a.bgr ? 0 : 2; // (a YUV source has no channel order to swap)
     half8 v0;
 #pragma unroll
     for (int e = 0; e < 8; e++) v0[e] = (_Float16)0.f;
-    if constexpr (sizeof(SRC) == 1)
+    if constexpr (YUV)
+    {
+        float rgb[3];
+        yuv_decode<SRC>(a.imgs[im], a.pitch[im], a.plane[im], x, y, iw, ih, a.yuv, rgb);
+        v0[0] = (_Float16)rgb[0];
+        v0[1] = (_Float16)rgb[1];
+        v0[2] = (_Float16)rgb[2];
+    }
+    else if constexpr (sizeof(SRC) == 1)
     {
         const uint8_t* p = a.imgs[im] + (long long)y * a.pitch[im] + x * a.c;
         const float norm_val = 1 / 255.f;
@@ -211,7 +298,9 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
     if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8) // (the staged kernel knows uint8 sources only)
     {
         const dim3 grid((max_tw + 31) / 32, (max_th + 7) / 8, a.ntiles), block(256);
-        if (a.fmt == kFmtF16) hipLaunchKernelGGL(preproc_tiles<_Float16>, grid, block, 0, st, a);
+        if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true>), grid, block, 0, st, a);
+        else if (a.fmt == kFmtP010) hipLaunchKernelGGL((preproc_tiles<uint16_t, true>), grid, block, 0, st, a);
+        else if (a.fmt == kFmtF16) hipLaunchKernelGGL(preproc_tiles<_Float16>, grid, block, 0, st, a);
         else if (a.fmt == kFmtF32) hipLaunchKernelGGL(preproc_tiles<float>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(preproc_tiles<uint8_t>, grid, block, 0, st, a);
         return;
@@ -646,9 +735,200 @@ static void launch_postproc_box(const PostArgs& a, int max_ow, int max_oh, hipSt
     else hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, false>), grid, block, 0, st, a);
 }
 
+// ---- YUV 4:2:0 output (PostArgs::out_fmt kFmtNV12 / kFmtP010) ----------------------------------------------------------------------
+// The K x K block of x4 pixels at (sx, sy) of one channel's blob, as postproc_tiles_box gathers it: the eight TTA variants merged in the
+// shader's order, then clamped to [0, 1].  sx and the row length are multiples of K: every run of K elements is ONE load.  (A copy of that
+// kernel's gather rather than a function shared with it: the box kernel stays, instruction for instruction, what it was measured as.)
+template <typename TP, int K>
+__device__ __forceinline__ void merged_block(const TP* b, long long ss, int w, int h, int sx, int sy, int tta, float (&c)[K][K])
+{
+    float r[K];
+#pragma unroll
+    for (int j = 0; j < K; j++)
+    {
+        load_run<TP, K>(b + (long long)(sy + j) * w + sx, r);
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] = r[i];
+    }
+    if (tta)
+    { // realsr_postproc_tta.comp:76-85: (v0 + v1 + ... + v7) * 0.125f, in this order
+#pragma unroll
+        for (int j = 0; j < K; j++)
+        {
+            load_run<TP, K>(b + ss + (long long)(sy + j) * w + (w - K - sx), r);
+#pragma unroll
+            for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++)
+        {
+            load_run<TP, K>(b + 2 * ss + (long long)(h - 1 - sy - j) * w + (w - K - sx), r);
+#pragma unroll
+            for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++)
+        {
+            load_run<TP, K>(b + 3 * ss + (long long)(h - 1 - sy - j) * w + sx, r);
+#pragma unroll
+            for (int i = 0; i < K; i++) c[j][i] += r[i];
+        }
+#pragma unroll
+        for (int i = 0; i < K; i++)
+        {
+            load_run<TP, K>(b + 4 * ss + (long long)(sx + i) * h + sy, r);
+#pragma unroll
+            for (int j = 0; j < K; j++) c[j][i] += r[j];
+        }
+#pragma unroll
+        for (int i = 0; i < K; i++)
+        {
+            load_run<TP, K>(b + 5 * ss + (long long)(sx + i) * h + (h - K - sy), r);
+#pragma unroll
+            for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
+        }
+#pragma unroll
+        for (int i = 0; i < K; i++)
+        {
+            load_run<TP, K>(b + 6 * ss + (long long)(w - 1 - sx - i) * h + (h - K - sy), r);
+#pragma unroll
+            for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
+        }
+#pragma unroll
+        for (int i = 0; i < K; i++)
+        {
+            load_run<TP, K>(b + 7 * ss + (long long)(w - 1 - sx - i) * h + sy, r);
+#pragma unroll
+            for (int j = 0; j < K; j++) c[j][i] += r[j];
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++)
+#pragma unroll
+            for (int i = 0; i < K; i++) c[j][i] *= 0.125f;
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++)
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] = fminf(fmaxf(c[j][i], 0.f), 1.f);
+}
+
+// code = floor(v * scale + add) clamped to [0, maxcode] (add = offset + 0.5f), as the sample type stores it: P010 keeps it in the high bits
+template <typename TO>
+__device__ __forceinline__ unsigned yuv_code(float v, float scale, float add, float maxcode)
+{
+    const float q = fminf(fmaxf(floorf(add_rn(mul_rn(v, scale), add)), 0.f), maxcode);
+    return sizeof(TO) == 1 ? (unsigned)q : (unsigned)q << 6;
+}
+
+// Two neighbouring samples of a surface row (lo in front) as ONE store of twice the sample size where the address allows it.
+template <typename TO>
+__device__ __forceinline__ void store_pair(uint8_t* o, unsigned lo, unsigned hi)
+{
+    if constexpr (sizeof(TO) == 1)
+    {
+        if (!(reinterpret_cast<uintptr_t>(o) & 1)) *reinterpret_cast<unsigned short*>(o) = (unsigned short)(lo | (hi << 8));
+        else { o[0] = (uint8_t)lo; o[1] = (uint8_t)hi; }
+    }
+    else
+    {
+        if (!(reinterpret_cast<uintptr_t>(o) & 3)) *reinterpret_cast<unsigned*>(o) = lo | (hi << 16);
+        else { reinterpret_cast<unsigned short*>(o)[0] = (unsigned short)lo; reinterpret_cast<unsigned short*>(o)[1] = (unsigned short)hi; }
+    }
+}
+
+// The YUV 4:2:0 sibling of postproc_tiles_box: one thread makes ONE 2 x 2 quad of luma samples and the (U, V) pair they share, at the
+// context's out_scale OS (4, 2 or 1: K = 4 / OS x4 pixels per output pixel and axis).  d, the RGB value of an output pixel, is what
+// RSR_FMT_F32_CHW holds for it -- x4 pixels TTA-merged, clamped and box-reduced exactly as in postproc_tiles / postproc_tiles_box --
+// and include/realsr_hip.h ("yuv_matrix") defines the rest: Y' = (kr R + kg G) + kb B per pixel; chroma from the mean m of the quad,
+// ((d00 + d01) + (d10 + d11)) * 0.25f per channel.  One channel at a time (the loads of three would cost three times the registers): Y'
+// is accumulated across the channel loop, 0 + kr R being kr R exactly (d >= 0).  A tile's rectangle starts and ends on even output pixels
+// (the engine refuses an out_scale 1 call where it would not), so no quad crosses a tile.  Lanes run along x.
+// TP: element type of the blob (_Float16, or float in precise mode); TO: sample type of the surface, uint8_t (NV12) or uint16_t (P010).
+template <typename TP, typename TO, int OS>
+__global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
+{
+    constexpr int K = 4 / OS, Q = 2 * K; // x4 pixels per output pixel / per quad, along an axis
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= t.out_w / Q || gy >= t.out_h / Q) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const long long cstep = (long long)w * h;
+    const int sx = gx * Q + a.crop, sy = gy * Q + a.crop; // first x4 pixel of the quad, in the blob
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    const YuvCoef& k = a.yuv;
+    float yq[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, ym = 0.f, rm = 0.f, bm = 0.f;
+#pragma unroll 1
+    for (int q = 0; q < 3; q++)
+    {
+        const TP* b = b0 + q * cstep;
+        float d[2][2];
+        if constexpr (OS == 4)
+            merged_block<TP, 2>(b, ss, w, h, sx, sy, a.tta, d);
+        else if constexpr (OS == 2)
+        {
+            float c[4][4];
+            merged_block<TP, 4>(b, ss, w, h, sx, sy, a.tta, c);
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+                    d[j][i] = mul_rn(add_rn(add_rn(c[2 * j][2 * i], c[2 * j][2 * i + 1]), add_rn(c[2 * j + 1][2 * i], c[2 * j + 1][2 * i + 1])), 0.25f);
+        }
+        else
+        {
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+                {
+                    float c[4][4];
+                    merged_block<TP, 4>(b, ss, w, h, sx + 4 * i, sy + 4 * j, a.tta, c);
+                    d[j][i] = box_mean<4>(c);
+                }
+        }
+        const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
+        const float m = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int i = 0; i < 2; i++) yq[j][i] = add_rn(yq[j][i], mul_rn(kq, d[j][i]));
+        ym = add_rn(ym, mul_rn(kq, m));
+        if (q == 0) rm = m;
+        if (q == 2) bm = m;
+    }
+    const long long pitch = a.out_pitch[im];
+    const int X = t.out_x / K + 2 * gx, Y = (t.out_y - a.out_row0) / K + 2 * gy; // the quad's first luma sample
+    uint8_t* const oy = a.outs[im] + Y * pitch + (long long)X * (int)sizeof(TO);
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+        store_pair<TO>(oy + j * pitch, yuv_code<TO>(yq[j][0], k.yscale, k.yadd, k.maxcode), yuv_code<TO>(yq[j][1], k.yscale, k.yadd, k.maxcode));
+    const float cb = mul_rn(sub_rn(bm, ym), k.icb), cr = mul_rn(sub_rn(rm, ym), k.icr);
+    uint8_t* const ouv = a.outs[im] + a.out_plane[im] + (Y >> 1) * pitch + (long long)X * (int)sizeof(TO);
+    store_pair<TO>(ouv, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
+}
+
+template <typename TP, typename TO>
+static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    const int q = a.box > 1 ? 2 * a.box : 2; // x4 pixels per quad and axis
+    const dim3 grid((max_ow / q + 63) / 64, (max_oh / q + 3) / 4, a.ntiles), block(256);
+    if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1>), grid, block, 0, st, a);
+    else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4>), grid, block, 0, st, a);
+}
+
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
     if (a.ntiles <= 0) return;
+    if (fmt_is_yuv(a.out_fmt))
+    { // a 4:2:0 surface: one thread per luma quad, at every out_scale, with and without TTA
+        if (a.out_fmt == kFmtNV12) a.f32 ? launch_postproc_yuv<float, uint8_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint8_t>(a, max_ow, max_oh, st);
+        else a.f32 ? launch_postproc_yuv<float, uint16_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint16_t>(a, max_ow, max_oh, st);
+        return;
+    }
     if (a.box > 1)
     { // out_scale 2 / 1: the box-reducing kernel (one thread per output pixel, with and without TTA)
         if (a.box == 2) a.f32 ? launch_postproc_box<float, 2>(a, max_ow, max_oh, st) : launch_postproc_box<_Float16, 2>(a, max_ow, max_oh, st);

@@ -5,6 +5,8 @@
     y = torch_io.upscale(sr, x)        # x: (3, H, W) or (N, 3, H, W) float16 / float32 in [0, 1] on cuda:0  ->  (.., 3, 4H, 4W)
     torch_io.upscale(sr, frame[..., y0:y1, x0:x1], out=canvas[..., 4 * y0:4 * y1, 4 * x0:4 * x1])   # views in, a window out: no copies
 
+    nv12 = torch_io.upscale_yuv(sr, surface)   # a decoder's (3H/2, W) uint8 NV12 or 16-bit P010 surface -> the same layout at out_scale
+
 The float tensors go through rsr_process_device_fmt / rsr_process_device_batch as they are (planar fp16 / fp32, include/realsr_hip.h): no
 quantisation to uint8 on either side, no permute, no extra pass over the frame.  An (N, 3, H, W) batch is ONE call: small images share
 tile batches.  A view whose rows are contiguous (a crop, a slice of a batch, a frame inside a padded surface) is passed by pointer and
@@ -13,7 +15,7 @@ waits for the GPU: the result is ordered on that stream like the output of any t
 """
 import torch
 
-from . import RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_U8_HWC
+from . import RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_P010, RSR_FMT_U8_HWC
 
 _FMT = {torch.float16: RSR_FMT_F16_CHW, torch.float32: RSR_FMT_F32_CHW}
 
@@ -104,6 +106,93 @@ def upscale(sr, x, out=None):
         cur.wait_stream(side)  # (x and y are next touched by work behind this wait: the allocator may reuse them safely)
         return y
     return _enqueue(sr, x, fmt, batched, cur.cuda_stream, out, shape)
+
+
+def _on_current_stream(device, enqueue):
+    """enqueue(stream handle) on torch's current stream, with nothing waiting on the host (see upscale)."""
+    cur = torch.cuda.current_stream(device)
+    if cur.cuda_stream != 0:
+        return enqueue(cur.cuda_stream)
+    side = _side_stream(device)
+    side.wait_stream(cur)
+    y = enqueue(side.cuda_stream)
+    cur.wait_stream(side)
+    return y
+
+
+# ---- YUV 4:2:0 surfaces: what a hardware decoder yields and an encoder takes ----------------------------------------------------------
+_YUV = {torch.uint8: RSR_FMT_NV12, torch.int16: RSR_FMT_P010}  # (P010 words as int16 too: torch's uint16 is a late and partial dtype)
+if hasattr(torch, "uint16"):
+    _YUV[torch.uint16] = RSR_FMT_P010
+
+
+def _planes(sr, s, what):
+    """The (y, uv) views of a surface -- a (3h / 2, w) tensor or a pair of planes -- validated; ValueError before anything is launched."""
+    if isinstance(s, (tuple, list)):
+        if len(s) != 2 or not all(isinstance(t, torch.Tensor) for t in s):
+            raise ValueError("upscale_yuv: %s must be a surface tensor or a (y, uv) pair of tensors" % what)
+        y, uv = s
+    else:
+        if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.shape[0] % 3 or s.shape[0] < 3:
+            raise ValueError("upscale_yuv: %s must be a (3h / 2, w) tensor: h rows of Y, then h / 2 rows of interleaved UV" % what)
+        h = s.shape[0] // 3 * 2
+        y, uv = s[:h], s[h:]
+    if y.dim() != 2 or uv.dim() != 2 or y.dtype != uv.dtype or y.device != uv.device:
+        raise ValueError("upscale_yuv: y and uv of %s must be 2-D tensors of one dtype on one device" % what)
+    if y.dtype not in _YUV:
+        raise ValueError("upscale_yuv: dtype %s is not supported (uint8 = NV12; uint16 / int16 = P010)" % y.dtype)
+    if y.device.type != "cuda" or y.device.index != sr.gpuid:
+        raise ValueError("upscale_yuv: %s is on %s, the context runs on cuda:%d" % (what, y.device, sr.gpuid))
+    h, w = y.shape
+    if h < 2 or w < 2 or h % 2 or w % 2 or tuple(uv.shape) != (h // 2, w):
+        raise ValueError("upscale_yuv: y %s with uv %s is not a 4:2:0 surface (even h and w, uv (h / 2, w))" % (tuple(y.shape), tuple(uv.shape)))
+    return y, uv
+
+
+def _describe_yuv(y, uv):
+    """(data_ptr, row_pitch, plane_pitch) in bytes of the surface behind the two views, or None when no rsr_image describes it: rows that
+    are not contiguous, two different row pitches, or a UV plane that does not lie above Y(0,0) in memory."""
+    es = y.element_size()
+    if y.stride(1) != 1 or uv.stride(1) != 1 or y.stride(0) < y.shape[1] or y.data_ptr() % es or uv.data_ptr() % es:
+        return None
+    if uv.shape[0] > 1 and uv.stride(0) != y.stride(0):
+        return None
+    plane = uv.data_ptr() - y.data_ptr()
+    return (y.data_ptr(), y.stride(0) * es, plane) if plane > 0 else None
+
+
+def upscale_yuv(sr, surface, out=None):
+    """upscale() for a YUV 4:2:0 surface on the context's GPU: the YUV <-> RGB conversion and the chroma resampling happen inside the
+    engine's pre- and post-processing kernels (RSR_FMT_NV12 / RSR_FMT_P010, include/realsr_hip.h; options "yuv_matrix", "yuv_range"), so no
+    RGB frame is materialised.  surface: a (3H / 2, W) tensor as a decoder yields it -- uint8 (NV12), or uint16 / int16 (P010: the 10-bit
+    code in the high bits) -- or a (y, uv) pair of views, y (H, W) and uv (H / 2, W).  A pair that no descriptor fits (a uv view that
+    lies below y in memory, say) is packed into one allocation first.  Returns the same layout at sr.out_scale: a (3H' / 2, W') tensor,
+    or for a pair the (y, uv) views of one.  out: the surface (or pair) to write and return instead.  Runs on torch.cuda.current_stream(),
+    with no host synchronisation inside."""
+    pair = isinstance(surface, (tuple, list))
+    y, uv = _planes(sr, surface, "surface")
+    fmt, (h, w) = _YUV[y.dtype], y.shape
+    s = getattr(sr, "out_scale", sr.scale)
+    if out is not None:
+        if isinstance(out, (tuple, list)) != pair:
+            raise ValueError("upscale_yuv: out must be a %s like the input" % ("(y, uv) pair" if pair else "surface tensor"))
+        oy, ouv = _planes(sr, out, "out")
+        if tuple(oy.shape) != (h * s, w * s) or oy.dtype != y.dtype or oy.device != y.device:
+            raise ValueError("upscale_yuv: out must be a %s surface of %d x %d on %s" % (y.dtype, w * s, h * s, y.device))
+        dout = _describe_yuv(oy, ouv)
+        if dout is None:
+            raise ValueError("upscale_yuv: out is not addressable by one row pitch and a plane pitch")
+    else:
+        o = y.new_empty((h * s * 3 // 2, w * s))
+        oy, ouv = o[:h * s], o[h * s:]
+        out = (oy, ouv) if pair else o
+        dout = _describe_yuv(oy, ouv)
+    din = _describe_yuv(y, uv)
+    if din is None:
+        packed = torch.cat([y, uv], dim=0)  # (kept alive by the stream ordering below, like any temporary of a torch op)
+        din = _describe_yuv(packed[:h], packed[h:])
+    _on_current_stream(y.device, lambda st: sr.process_device_batch([din], fmt, w, h, 3, [dout], fmt, stream=st))
+    return out
 
 
 _side = {}
