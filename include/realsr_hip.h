@@ -123,8 +123,9 @@ int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, in
  *            packed: rsr_image_bytes = w*h*3/2 for NV12, 3*w*h for P010).  rsr_process_device_fmt takes packed surfaces.
  *   Errors.  RSR_E_ARG before anything is launched: c != 3; an odd w or h of a YUV input; a YUV output whose w * out_scale, h * out_scale or
  *            tilesize * out_scale is odd (out_scale 1 only: no 2 x 2 chroma quad may cross a tile); P010 with an odd data pointer or pitch.
- *   Options. "yuv_matrix" 709 [default] / 601 / 2020 and "yuv_range" 0 = limited [default] / 1 = full (rsr_set_option).  Chroma is sited at
- *            the CENTRE of its 2 x 2 luma quad in both directions (MPEG-1 / JPEG siting); other sitings are out of scope.
+ *   Options. "yuv_matrix" 709 [default] / 601 / 2020 and "yuv_range" 0 = limited [default] / 1 = full (rsr_set_option).  "yuv_siting" says
+ *            where a chroma sample sits: 0 [default] = at the CENTRE of its 2 x 2 luma quad in both directions (MPEG-1 / JPEG siting), which
+ *            the definition below describes; 1 = left, 2 = top-left: "Chroma siting" behind it.
  *   The definition, exact.  All arithmetic is fp32; every multiplication and every addition is rounded by itself, in the order written (no
  *   contraction).  Constants are computed in double from Kr and Kb -- 0.2126 / 0.0722 (709), 0.299 / 0.114 (601), 0.2627 / 0.0593 (2020),
  *   Kg = 1 - Kr - Kb -- and rounded once to fp32, written fp32(.) below; rsr_yuv_constants returns them.  b = 8 (NV12) or 10 (P010) bits,
@@ -140,6 +141,24 @@ int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, in
  *            Y' = (Kr * R + Kg * G) + Kb * B; Y code = floor(Y' * yscale + (yoff + 0.5f)) clamped to [0, 2^b - 1].  Chroma of a 2 x 2 quad:
  *            per channel m = ((d00 + d01) + (d10 + d11)) * 0.25f, Ym from m as Y' from d, Cb = (Bm - Ym) * fp32(1/(2(1-Kb))),
  *            Cr = (Rm - Ym) * fp32(1/(2(1-Kr))), code = floor(C * cscale + (coff + 0.5f)) clamped alike.  P010 stores code << 6.
+ *   Chroma siting, exact ("yuv_siting" 1 / 2; it holds for both sides of a call).  1 = LEFT, the default of H.264, HEVC, AV1 and MPEG-2
+ *   (chroma_sample_loc_type 0): chroma is co-sited with the even luma columns and lies between the two luma rows.  2 = TOP-LEFT, BT.2020 /
+ *   UHD HEVC (chroma_sample_loc_type 2): chroma is co-sited with luma (2X, 2Y).  Call an axis on which chroma is co-sited with the even luma
+ *   index "cos": siting 1 is cos horizontally and centre vertically, siting 2 is cos on both axes.  Everything not said here is the
+ *   definition above: constants, luma, the RGB matrix, clamps, code rounding, reflect-101 first, every operation rounded by itself.
+ *   Decode.  Luma index i of an axis with N/2 chroma samples, n = i >> 1.  A centre axis: (3 * c_near + c_far) * 0.25f as above.  A cos axis:
+ *            c[n] for an even i, (c[n] + c[min(n + 1, N/2 - 1)]) * 0.5f for an odd one.  Horizontally first, then vertically (both rules are
+ *            exact in fp32 for 8- and 10-bit codes, so the order cannot show; it is fixed all the same).
+ *   Encode.  Luma is unchanged: the Y plane does not depend on the siting.  Chroma of quad (X, Y), per channel, d as above:
+ *            Hs(y) = (d(xl, y) + d(2X+1, y)) + (d(2X, y) + d(2X, y)) -- the [1 2 1] filter about the co-sited column, unnormalised -- with
+ *            xl = 2X - 1, but xl = 2X where column 2X is the first column of its TILE's output rectangle (the image's first column included).
+ *            Siting 1: m = (Hs(2Y) + Hs(2Y+1)) * 0.125f.  Siting 2: m = ((Hs(yu) + Hs(2Y+1)) + (Hs(2Y) + Hs(2Y))) * 0.0625f, yu = 2Y - 1, but
+ *            yu = 2Y on the first row of the tile's rectangle.  Ym, Cb, Cr and the codes follow from m as above.  A tile's rectangle starts
+ *            at multiples of tilesize * out_scale output pixels (even: see Errors).
+ *            Why the filter clamps at a tile's edge and does not take the neighbouring tile's column: that column is part of another tile's
+ *            network output, which may belong to another batch of the call; the tile's own halo there is not computed (the last convolutions
+ *            skip the margin nothing reads), and computing it would widen the hot convolution launches.  The price: one chroma column (row)
+ *            per tile edge -- every tilesize * out_scale output pixels, 800 at the defaults -- is filtered [0 3 1] / 4 instead of [1 2 1] / 4.
  * On the output side conv_last leaves its planar blob and one more small launch (postproc_tiles_yuv) writes the surface: the route RGBA, TTA
  * and "out_scale" below 4 take anyway.  Out of scope: host pointers (rsr_process*) and the CLI, which stay uint8 RGB(A). */
 
@@ -423,6 +442,9 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *   "yuv_matrix"        709 [default], 601 or 2020: Kr / Kb of the RSR_FMT_NV12 / RSR_FMT_P010 conversion; "yuv_range": 0 [default] = limited (16..235 /
  *                       16..240 at 8 bits), 1 = full.  Any other value: RSR_E_ARG, the value in force stays (stats "yuv_matrix", "yuv_range").
  *                       Both take effect for the next call, like "out_scale" (rsr_process_device_fmt has the definition)
+ *   "yuv_siting"        0 [default] = centre, 1 = left, 2 = top-left: where a chroma sample of an RSR_FMT_NV12 / RSR_FMT_P010 surface sits, on the
+ *                       input and the output side alike ("Chroma siting" above); takes effect for the next call.  Any other value: RSR_E_ARG,
+ *                       the value in force stays (stat "yuv_siting").  RGB formats, host pointers and the CLI are not concerned.
  *   "precise_auto"      1: "precise" is set by the model: on a loaded context rsr_selfcheck runs at once on the built-in tile and "precise"
  *                       becomes its recommend_precise; on a context not yet loaded the same happens at the end of the next successful
  *                       rsr_load / rsr_load_packed (which then returns the self-check's error, if it has one; the model stays loaded).
@@ -471,7 +493,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *                       rsr_process_group allocates only the output rows of its tile range)
  *   "last_test_us"      HIP-event time of the last rsr_conv3x3 / rsr_conv3x3_res launch (with option "test_repeat" = N the
  *                       work items are repeated N times in that one launch: an L2-resident workload)
- *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force; "yuv_matrix" / "yuv_range": likewise
+ *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force; "yuv_matrix" / "yuv_range" / "yuv_siting": likewise
  *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
  *                       "selfcheck_overflow" (-1 before the first run) */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);

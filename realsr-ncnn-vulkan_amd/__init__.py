@@ -241,6 +241,17 @@ class RealSR:
     def out_scale(self, s):
         self.set_option("out_scale", int(s))  # (anything but 1, 2 or 4 raises RealSRError(RSR_E_ARG) and leaves the value alone)
 
+    @property
+    def yuv_siting(self):
+        """Where a chroma sample of an NV12 / P010 surface sits, on both sides of a call: 0 (default) = the centre of its 2 x 2 luma
+        quad (JPEG, MPEG-1), 1 = left (H.264 / HEVC / AV1 / MPEG-2 default), 2 = top-left (BT.2020 / UHD HEVC) -- option "yuv_siting",
+        include/realsr_hip.h.  Takes effect for the next call.  Read from the engine, like out_scale."""
+        return int(self.get_stat("yuv_siting"))
+
+    @yuv_siting.setter
+    def yuv_siting(self, v):
+        self.set_option("yuv_siting", int(v))  # (anything but 0, 1 or 2 raises RealSRError(RSR_E_ARG) and leaves the value alone)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.rsr_destroy(self._h)

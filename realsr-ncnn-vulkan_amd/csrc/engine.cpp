@@ -1064,6 +1064,7 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     pa.variant = variant;
     if (fmt_is_yuv(io.in_fmt) && !yuv_coef(yuv_matrix, yuv_range, io.in_fmt == RSR_FMT_P010 ? 10 : 8, &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     if (fmt_is_yuv(io.out_fmt) && !yuv_coef(yuv_matrix, yuv_range, io.out_fmt == RSR_FMT_P010 ? 10 : 8, &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
+    pa.siting = po.siting = yuv_siting;
     launch_preproc_tiles(pa, max_tw, max_th, st);
     // bytes of a pixel in the caller's image: c for uint8 HWC, 3 halfs / floats for the planar formats, 1.5 samples for the 4:2:0 surfaces
     auto px_bytes = [c](int fmt) {

@@ -207,6 +207,10 @@ struct Engine
     // YUV <-> RGB of the NV12 / P010 device formats (options "yuv_matrix", "yuv_range"; include/realsr_hip.h): Kr / Kb of BT.709, 601 or
     // 2020, limited (0) or full (1) range.  Read when a call is enqueued: the constants travel with the launch (kernels.h YuvCoef).
     int yuv_matrix = 709, yuv_range = 0;
+    // Chroma siting of those surfaces (option "yuv_siting"; include/realsr_hip.h "Chroma siting"), on both sides of a call: 0 = centre of the
+    // 2 x 2 luma quad (JPEG, MPEG-1), 1 = left (H.264 / HEVC / AV1 / MPEG-2 default), 2 = top-left (BT.2020 / UHD HEVC).  Read when a call is
+    // enqueued, like the matrix; 1 and 2 launch kernels of their own (kernels.h PreArgs::siting / PostArgs::siting).
+    int yuv_siting = 0;
     // Model self-check (include/realsr_hip.h rsr_selfcheck): one tile through the network in both storages, compared on the device.
     bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
     long long selfcheck_runs = 0;

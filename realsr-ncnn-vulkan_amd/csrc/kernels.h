@@ -186,6 +186,7 @@ struct PreArgs
     int plane_ch;   // 16
     int variant;    // 0 default (launch_preproc_tiles picks), 1 one thread per pixel (engine dbg 32768), 2 LDS-staged (dbg 65536; uint8 sources only)
     YuvCoef yuv;    // fmt kFmtNV12 / kFmtP010 only
+    int siting;     // ... likewise: where a chroma sample sits in its luma quad (engine option "yuv_siting"): 0 centre, 1 left, 2 top-left
 };
 void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t st);
 
@@ -216,6 +217,9 @@ struct PostArgs
     // x4 units (BaseTile::out_*, out_row0, crop: all multiples of 4); the kernel divides by K.
     int box;
     YuvCoef yuv; // out_fmt kFmtNV12 / kFmtP010 only
+    // ... likewise: the chroma siting (engine option "yuv_siting": 0 centre, 1 left, 2 top-left).  The sited chroma filters clamp at the
+    // first column / row of a TILE's rectangle; that is quad column / row 0 of the tile's own grid (BaseTile::out_*), so nothing else travels.
+    int siting;
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 

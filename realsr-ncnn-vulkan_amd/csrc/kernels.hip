@@ -82,24 +82,55 @@ __device__ __forceinline__ void load_uv(const uint8_t* row, int cx, float& u, fl
 // one on its side, per axis, indices clamped at the image edge -- horizontally first, (3 * near + far) * 0.25f, then vertically the same
 // way: exact for codes.  Lanes run along x: the Y loads of a wave are contiguous, a pair of neighbouring lanes shares its near chroma
 // column, and U and V always travel in one load.  Every product and sum below is rounded by itself (no contraction).
-template <typename SRC>
+//
+// SITE (option "yuv_siting"; include/realsr_hip.h "Chroma siting"): 0 = the centre siting above, on both axes.  1 (left) / 2 (top-left):
+// chroma is CO-SITED with the even luma index horizontally / on both axes (yuv_decode_cos); a left-sited surface keeps the centre rule
+// vertically.  A co-sited axis takes c[n] for an even index i = 2n and (c[n] + c[min(n + 1, N/2 - 1)]) * 0.5f for an odd one: one chroma
+// column (row) for even pixels, two for odd ones, so the lanes of a pair still share their loads.  Exact for codes, like the centre rule.
+template <typename SRC, int SITE>
+__device__ __forceinline__ void yuv_decode_cos(const uint8_t* img, int pitch, long long plane, int x, int y, int w, int h, float& U, float& V)
+{
+    const int cx0 = x >> 1, cx1 = min(cx0 + (x & 1), (w >> 1) - 1); // an even x reads its column twice: (c + c) * 0.5f == c
+    int cy0 = y >> 1, cy1;
+    if constexpr (SITE == 2) cy1 = min(cy0 + (y & 1), (h >> 1) - 1);
+    else cy1 = min(max(cy0 + ((y & 1) ? 1 : -1), 0), (h >> 1) - 1); // centre rule: cy0 near, cy1 far
+    const uint8_t* r0 = img + plane + (long long)cy0 * pitch;
+    const uint8_t* r1 = img + plane + (long long)cy1 * pitch;
+    float u00, v00, u01, v01, u10, v10, u11, v11; // (row, column)
+    load_uv<SRC>(r0, cx0, u00, v00);
+    load_uv<SRC>(r0, cx1, u01, v01);
+    load_uv<SRC>(r1, cx0, u10, v10);
+    load_uv<SRC>(r1, cx1, u11, v11);
+    auto cos = [](float a, float b) { return mul_rn(add_rn(a, b), 0.5f); };
+    auto mix = [](float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); };
+    const float ua = cos(u00, u01), ub = cos(u10, u11), va = cos(v00, v01), vb = cos(v10, v11); // horizontally first
+    if constexpr (SITE == 2) { U = cos(ua, ub); V = cos(va, vb); }
+    else { U = mix(ua, ub); V = mix(va, vb); }
+}
+
+template <typename SRC, int SITE = 0>
 __device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long long plane, int x, int y, int w, int h, const YuvCoef& k, float (&rgb)[3])
 {
     const uint8_t* yp = img + (long long)y * pitch + (long long)x * (int)sizeof(SRC);
     float Y;
     if constexpr (sizeof(SRC) == 1) Y = (float)*yp;
     else Y = (float)(*reinterpret_cast<const unsigned short*>(yp) >> 6);
-    const int cxn = x >> 1, cxf = min(max(cxn + ((x & 1) ? 1 : -1), 0), (w >> 1) - 1);
-    const int cyn = y >> 1, cyf = min(max(cyn + ((y & 1) ? 1 : -1), 0), (h >> 1) - 1);
-    const uint8_t* rn = img + plane + (long long)cyn * pitch;
-    const uint8_t* rf = img + plane + (long long)cyf * pitch;
-    float unn, vnn, unf, vnf, ufn, vfn, uff, vff; // (row, column): near / far
-    load_uv<SRC>(rn, cxn, unn, vnn);
-    load_uv<SRC>(rn, cxf, unf, vnf);
-    load_uv<SRC>(rf, cxn, ufn, vfn);
-    load_uv<SRC>(rf, cxf, uff, vff);
-    auto mix = [](float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); };
-    const float U = mix(mix(unn, unf), mix(ufn, uff)), V = mix(mix(vnn, vnf), mix(vfn, vff));
+    float U, V;
+    if constexpr (SITE != 0) yuv_decode_cos<SRC, SITE>(img, pitch, plane, x, y, w, h, U, V);
+    else
+    {
+        const int cxn = x >> 1, cxf = min(max(cxn + ((x & 1) ? 1 : -1), 0), (w >> 1) - 1);
+        const int cyn = y >> 1, cyf = min(max(cyn + ((y & 1) ? 1 : -1), 0), (h >> 1) - 1);
+        const uint8_t* rn = img + plane + (long long)cyn * pitch;
+        const uint8_t* rf = img + plane + (long long)cyf * pitch;
+        float unn, vnn, unf, vnf, ufn, vfn, uff, vff; // (row, column): near / far
+        load_uv<SRC>(rn, cxn, unn, vnn);
+        load_uv<SRC>(rn, cxf, unf, vnf);
+        load_uv<SRC>(rf, cxn, ufn, vfn);
+        load_uv<SRC>(rf, cxf, uff, vff);
+        auto mix = [](float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); };
+        U = mix(mix(unn, unf), mix(ufn, uff)), V = mix(mix(vnn, vnf), mix(vfn, vff));
+    }
     const float yn = mul_rn(sub_rn(Y, k.yoff), k.ys);
     const float cb = mul_rn(sub_rn(U, k.coff), k.cs), cr = mul_rn(sub_rn(V, k.coff), k.cs);
     const float r = add_rn(yn, mul_rn(k.rv, cr));
@@ -119,8 +150,9 @@ __device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long l
 // fp16, to nearest even.  Lanes run along x: the three plane reads of a wave are contiguous.  Rows are PreArgs::pitch bytes apart, planes
 // PreArgs::plane: the reflected (x, y) is an index into the image, never into the surface around it.
 // YUV = true: the image is a 4:2:0 surface, SRC its sample type -- uint8_t (NV12) or uint16_t (P010, the code in the high 10 bits).  Pixel
-// (x, y) -- reflected first, like every other source -- is decoded as include/realsr_hip.h ("yuv_matrix") defines, bit for bit: yuv_decode.
-template <typename SRC, bool YUV = false>
+// (x, y) -- reflected first, like every other source -- is decoded as include/realsr_hip.h ("yuv_matrix") defines, bit for bit: yuv_decode;
+// SITE is the chroma siting (PreArgs::siting: a kernel per siting, the centre-sited one is what it was before the others existed).
+template <typename SRC, bool YUV = false, int SITE = 0>
 __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -137,7 +169,7 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     if constexpr (YUV)
     {
         float rgb[3];
-        yuv_decode<SRC>(a.imgs[im], a.pitch[im], a.plane[im], x, y, iw, ih, a.yuv, rgb);
+        yuv_decode<SRC, SITE>(a.imgs[im], a.pitch[im], a.plane[im], x, y, iw, ih, a.yuv, rgb);
         v0[0] = (_Float16)rgb[0];
         v0[1] = (_Float16)rgb[1];
         v0[2] = (_Float16)rgb[2];
@@ -298,7 +330,17 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
     if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8) // (the staged kernel knows uint8 sources only)
     {
         const dim3 grid((max_tw + 31) / 32, (max_th + 7) / 8, a.ntiles), block(256);
-        if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true>), grid, block, 0, st, a);
+        if (fmt_is_yuv(a.fmt) && a.siting == 1)
+        {
+            if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true, 1>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((preproc_tiles<uint16_t, true, 1>), grid, block, 0, st, a);
+        }
+        else if (fmt_is_yuv(a.fmt) && a.siting == 2)
+        {
+            if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true, 2>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((preproc_tiles<uint16_t, true, 2>), grid, block, 0, st, a);
+        }
+        else if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true>), grid, block, 0, st, a);
         else if (a.fmt == kFmtP010) hipLaunchKernelGGL((preproc_tiles<uint16_t, true>), grid, block, 0, st, a);
         else if (a.fmt == kFmtF16) hipLaunchKernelGGL(preproc_tiles<_Float16>, grid, block, 0, st, a);
         else if (a.fmt == kFmtF32) hipLaunchKernelGGL(preproc_tiles<float>, grid, block, 0, st, a);
@@ -836,6 +878,19 @@ __device__ __forceinline__ void store_pair(uint8_t* o, unsigned lo, unsigned hi)
     }
 }
 
+// ONE pixel d of the context's out_scale image (K = 4 / out_scale x4 pixels per axis; (px, py) its first x4 pixel in the blob, K-aligned):
+// the K x K block gathered by merged_block and box-reduced in the order of include/realsr_hip.h ("out_scale") -- the value the quad
+// kernel below computes for the pixels of its own quad, for the neighbours the sited chroma filters need.
+template <typename TP, int K>
+__device__ __forceinline__ float out_pixel(const TP* b, long long ss, int w, int h, int px, int py, int tta)
+{
+    float c[K][K];
+    merged_block<TP, K>(b, ss, w, h, px, py, tta, c);
+    if constexpr (K == 1) return c[0][0];
+    else if constexpr (K == 2) return mul_rn(add_rn(add_rn(c[0][0], c[0][1]), add_rn(c[1][0], c[1][1])), 0.25f);
+    else return box_mean<4>(c);
+}
+
 // The YUV 4:2:0 sibling of postproc_tiles_box: one thread makes ONE 2 x 2 quad of luma samples and the (U, V) pair they share, at the
 // context's out_scale OS (4, 2 or 1: K = 4 / OS x4 pixels per output pixel and axis).  d, the RGB value of an output pixel, is what
 // RSR_FMT_F32_CHW holds for it -- x4 pixels TTA-merged, clamped and box-reduced exactly as in postproc_tiles / postproc_tiles_box --
@@ -844,7 +899,17 @@ __device__ __forceinline__ void store_pair(uint8_t* o, unsigned lo, unsigned hi)
 // is accumulated across the channel loop, 0 + kr R being kr R exactly (d >= 0).  A tile's rectangle starts and ends on even output pixels
 // (the engine refuses an out_scale 1 call where it would not), so no quad crosses a tile.  Lanes run along x.
 // TP: element type of the blob (_Float16, or float in precise mode); TO: sample type of the surface, uint8_t (NV12) or uint16_t (P010).
-template <typename TP, typename TO, int OS>
+//
+// SITE (PostArgs::siting, option "yuv_siting"): 0 = chroma at the centre of the quad, as above.  1 (left) / 2 (top-left): chroma co-sited
+// with the quad's first column / first pixel -- include/realsr_hip.h "Chroma siting": per channel Hs(y) = (d(xl, y) + d(2X+1, y)) +
+// (d(2X, y) + d(2X, y)), the unnormalised [1 2 1] filter about column 2X, and m = (Hs(2Y) + Hs(2Y+1)) * 0.125f (left) or ((Hs(yu) +
+// Hs(2Y+1)) + (Hs(2Y) + Hs(2Y))) * 0.0625f (top-left), xl = 2X - 1 and yu = 2Y - 1 -- or 2X / 2Y in the first quad column / row of the
+// TILE's rectangle (gx == 0 / gy == 0): the pixel beyond belongs to another tile's blob.  Luma does not change.  The neighbours d(2X-1, .)
+// and d(., 2Y-1) are pixels of this tile's own kept rectangle, gathered like every other d -- merged_block<TP, K> at (sx - K, .) /
+// (., sy - K), K-aligned like sx and sy -- by the thread itself: redundant with the lane beside it / the wave above it, served by the
+// caches, and free of any cross-lane dependence on threads that have returned.  At a tile-first column / row the address is the pixel's
+// own (lx == sx): the same loads, the same arithmetic, hence bitwise d(2X, .) / d(., 2Y) with no divergent branch.
+template <typename TP, typename TO, int OS, int SITE = 0>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
 {
     constexpr int K = 4 / OS, Q = 2 * K; // x4 pixels per output pixel / per quad, along an axis
@@ -890,7 +955,23 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
                 }
         }
         const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
-        const float m = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
+        float m;
+        if constexpr (SITE == 0) m = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
+        else
+        {
+            const int lx = sx - (gx ? K : 0), uy = sy - (gy ? K : 0); // x4 position of output column xl / row yu
+            float hs[2];
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+                hs[j] = add_rn(add_rn(out_pixel<TP, K>(b, ss, w, h, lx, sy + K * j, a.tta), d[j][1]), add_rn(d[j][0], d[j][0]));
+            if constexpr (SITE == 1) m = mul_rn(add_rn(hs[0], hs[1]), 0.125f);
+            else
+            {
+                const float u0 = out_pixel<TP, K>(b, ss, w, h, sx, uy, a.tta);
+                const float hu = add_rn(add_rn(out_pixel<TP, K>(b, ss, w, h, lx, uy, a.tta), out_pixel<TP, K>(b, ss, w, h, sx + K, uy, a.tta)), add_rn(u0, u0));
+                m = mul_rn(add_rn(add_rn(hu, hs[1]), add_rn(hs[0], hs[0])), 0.0625f);
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -915,9 +996,16 @@ static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipSt
 {
     const int q = a.box > 1 ? 2 * a.box : 2; // x4 pixels per quad and axis
     const dim3 grid((max_ow / q + 63) / 64, (max_oh / q + 3) / 4, a.ntiles), block(256);
-    if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1>), grid, block, 0, st, a);
-    else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4>), grid, block, 0, st, a);
+#define RSR_POST_YUV(SITE)                                                                                           \
+    {                                                                                                                \
+        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1, SITE>), grid, block, 0, st, a);            \
+        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2, SITE>), grid, block, 0, st, a);       \
+        else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4, SITE>), grid, block, 0, st, a);                       \
+    }
+    if (a.siting == 1) RSR_POST_YUV(1)
+    else if (a.siting == 2) RSR_POST_YUV(2)
+    else RSR_POST_YUV(0)
+#undef RSR_POST_YUV
 }
 
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)

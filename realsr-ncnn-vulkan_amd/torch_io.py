@@ -164,7 +164,8 @@ def _describe_yuv(y, uv):
 def upscale_yuv(sr, surface, out=None):
     """upscale() for a YUV 4:2:0 surface on the context's GPU: the YUV <-> RGB conversion and the chroma resampling happen inside the
     engine's pre- and post-processing kernels (RSR_FMT_NV12 / RSR_FMT_P010, include/realsr_hip.h; options "yuv_matrix", "yuv_range"), so no
-    RGB frame is materialised.  surface: a (3H / 2, W) tensor as a decoder yields it -- uint8 (NV12), or uint16 / int16 (P010: the 10-bit
+    RGB frame is materialised.  Where the chroma samples sit is the context's option "yuv_siting" (sr.yuv_siting: 0 centre, 1 left -- what
+    an H.264 / HEVC / AV1 decoder yields by default --, 2 top-left -- BT.2020 / UHD); it holds for the surface read and the one written.  surface: a (3H / 2, W) tensor as a decoder yields it -- uint8 (NV12), or uint16 / int16 (P010: the 10-bit
     code in the high bits) -- or a (y, uv) pair of views, y (H, W) and uv (H / 2, W).  A pair that no descriptor fits (a uv view that
     lies below y in memory, say) is packed into one allocation first.  Returns the same layout at sr.out_scale: a (3H' / 2, W') tensor,
     or for a pair the (y, uv) views of one.  out: the surface (or pair) to write and return instead.  Runs on torch.cuda.current_stream(),

@@ -10,6 +10,15 @@ caller needed before the NV12 / P010 formats existed:
 All variants alternate inside every repetition, on ONE torch stream, each timed with HIP events around `frames` back-to-back frames.  The
 gate is printed per line: the native path must not be slower than its detour by more than the detour's own spread over the repetitions.
     python tools/yuv_perf.py [reps=5] [frames=4] [out=profiles/yuv_io.txt] [option=value ...]
+
+siting=1 measures the chroma sitings instead (option "yuv_siting"; profiles/yuv_siting.txt):
+    nv12->nv12 / p010->p010 at out_scale 4 and 2, siting 1 (left) and 2 (top-left) against siting 0 (centre) in the same run, alternating;
+    the expectation, printed per line: the frame time stays within siting 0's own spread over the repetitions.  post_ms of each from one
+    profiled frame.  Then the size of the tile-edge effect (the sited chroma filters clamp at the first column / row of every tile's
+    rectangle): the C2 golden frame's input as uint8, F32 out at x4 and x2, tests/yuv_siting_ref.encode with the tile grid against
+    the same without it -- how many chroma samples differ and by how many codes, for NV12 and P010.  Reported, not gated.
+    python tools/yuv_perf.py siting=1 [reps=5] [frames=4] [out=profiles/yuv_siting.txt]
+The numpy restatement is the tests' (tests/yuv_siting_ref.py, on top of tests/yuv_ref.py): this mode puts tests/ on sys.path to import it.
 """
 import os
 import sys
@@ -22,7 +31,7 @@ import torch.nn.functional as F  # noqa: E402
 import realsr_ncnn_vulkan_amd as R  # noqa: E402
 from realsr_ncnn_vulkan_amd import synth, torch_io  # noqa: E402
 
-reps, frames, out_path, opts = 5, 4, None, []
+reps, frames, out_path, opts, siting_mode = 5, 4, None, [], False
 for kv in sys.argv[1:]:
     k, v = kv.split("=")
     if k == "reps":
@@ -31,6 +40,8 @@ for kv in sys.argv[1:]:
         frames = int(v)
     elif k == "out":
         out_path = v
+    elif k == "siting":
+        siting_mode = bool(int(v))
     else:
         opts.append((k, int(v)))
 
@@ -87,29 +98,110 @@ def at(scale, f):
     return g
 
 
+def finish(text):
+    print(text)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(text + "\n")
+    sr.close()
+
+
+def alternate(variants):
+    """Every variant once per repetition, `frames` back-to-back frames between two HIP events: ms per frame, per repetition; and what each
+    variant returned in the first warm-up pass."""
+    times = {n: [] for n, _ in variants}
+    with torch.cuda.stream(st):
+        outs = {n: f() for n, f in variants}  # warm-up: plans, workspace, torch's kernels and allocator
+        for n, f in variants:
+            f()
+        st.synchronize()
+        for rep in range(reps):
+            for n, f in variants:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(frames):
+                    y = f()
+                e1.record(st)
+                e1.synchronize()
+                del y
+                times[n].append(e0.elapsed_time(e1) / frames)
+    st.synchronize()
+    return times, outs
+
+
+def siting_report():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import yuv_siting_ref as ref  # noqa: E402
+
+    def sited(scale, k, bits):
+        def g():
+            sr.out_scale, sr.yuv_siting = scale, k
+            return torch_io.upscale_yuv(sr, surf[bits])
+        return g
+
+    cases = [(s_, bits, name) for s_ in (4, 2) for bits, name in ((8, "nv12"), (10, "p010"))]
+    variants = [("%s->%s x%d siting %d" % (name, name, s_, k), sited(s_, k, bits)) for s_, bits, name in cases for k in (0, 1, 2)]
+    times = alternate(variants)[0]
+    post = {}
+    sr.set_profiling(True)
+    with torch.cuda.stream(st):
+        for n, f in variants:  # one profiled frame each
+            sr.get_profile(reset=True)
+            f()
+            st.synchronize()
+            post[n] = sr.get_profile(reset=True)
+    sr.set_profiling(False)
+    lines = ["C2 frame 1920 x 1080, tile 200, device-resident, BT.709 limited, %d repetitions x %d frames per variant, alternating, HIP events on one stream"
+             % (reps, frames), "device: %s" % torch.cuda.get_device_name(0),
+             "%-26s %9s %9s %9s %8s %8s   %s" % ("variant", "median ms", "min ms", "max ms", "pre_ms", "post_ms", "per repetition")]
+    for n, _ in variants:
+        t = times[n]
+        line = "%-26s %9.2f %9.2f %9.2f %8.3f %8.3f   %s" % (n, np.median(t), min(t), max(t), post[n]["pre_ms"], post[n]["post_ms"], " ".join("%.2f" % v for v in t))
+        if not n.endswith("siting 0"):
+            t0 = times[n[:-1] + "0"]
+            spread, over = max(t0) - min(t0), np.median(t) - np.median(t0)
+            line += "   vs siting 0: %+.2f ms (%+.2f %%), its spread %.2f ms: %s" % (
+                over, over / np.median(t0) * 100, spread, "within" if over <= spread else "OUTSIDE by %.2f ms" % (over - spread))
+        lines.append(line)
+    # the tile-edge effect
+    sr.yuv_siting = 0
+    src = torch.from_numpy(synth.make_image(1235, w, h)).cuda()
+    lines += ["", "Tile-edge effect: input of the C2 golden frame (uint8, 1920 x 1080, tile 200), F32 out; encode(d, siting, tilesize * out_scale) against",
+              "encode(d, siting, 0) in numpy (tests/yuv_siting_ref.py): chroma samples that differ / all chroma samples, largest code difference"]
+    for s_ in (4, 2):
+        sr.out_scale = s_
+        dst = torch.empty((3, h * s_, w * s_), dtype=torch.float32, device="cuda")
+        sr.process_device_fmt(src.data_ptr(), R.RSR_FMT_U8_HWC, w, h, 3, dst.data_ptr(), R.RSR_FMT_F32_CHW)
+        torch.cuda.synchronize()
+        dd = dst.cpu().numpy()
+        del dst
+        for k in (1, 2):
+            for bits, name in ((8, "nv12"), (10, "p010")):
+                grid, free = ref.encode(dd, k, 200 * s_, 709, 0, bits)[1], ref.encode(dd, k, 0, 709, 0, bits)[1]
+                diff = np.abs(grid - free)
+                dm, step = diff.any(axis=2), 100 * s_
+                first = np.zeros_like(dm)
+                first[:, ::step] = True
+                if k == 2:
+                    first[::step, :] = True
+                on_edges = not (dm & ~first).any()
+                lines.append("x%d siting %d %s: %d of %d samples differ (%.4f %%), max %d codes, mean of the differing %.2f; all on tile-first chroma columns%s: %s" % (
+                    s_, k, name, int((diff > 0).sum()), diff.size, 100.0 * (diff > 0).mean(), int(diff.max()),
+                    float(diff[diff > 0].mean()) if (diff > 0).any() else 0.0, " / rows" if k == 2 else "", on_edges))
+    finish("\n".join(lines))
+
+
+if siting_mode:
+    siting_report()
+    sys.exit(0)
+
 variants = []
 for s_ in (4, 2):
     for bits, name in ((8, "nv12"), (10, "p010")):
         variants.append(("%s->%s x%d" % (name, name, s_), at(s_, lambda b=bits: torch_io.upscale_yuv(sr, surf[b]))))
         variants.append(("detour %s x%d" % (name, s_), at(s_, lambda b=bits: to_yuv(torch_io.upscale(sr, to_rgb(surf[b], b)), b))))
     variants.append(("u8->u8 x%d" % s_, at(s_, lambda: torch_io.upscale(sr, x8))))
-times = {n: [] for n, _ in variants}
-with torch.cuda.stream(st):
-    outs = {n: f() for n, f in variants}  # warm-up: plans, workspace, torch's kernels and allocator
-    for n, f in variants:
-        f()
-    st.synchronize()
-    for rep in range(reps):
-        for n, f in variants:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            for _ in range(frames):
-                y = f()
-            e1.record(st)
-            e1.synchronize()
-            del y
-            times[n].append(e0.elapsed_time(e1) / frames)
-st.synchronize()
+times, outs = alternate(variants)
 
 lines = ["C2 frame 1920 x 1080, tile 200, device-resident, BT.709 limited, %d repetitions x %d frames per variant, alternating, HIP events on one stream%s"
          % (reps, frames, "".join(" %s=%d" % kv for kv in opts)),
@@ -128,9 +220,4 @@ for n, _ in variants:
         line += "   gate: <= detour %.2f + its spread %.2f ms: %s (%+.2f %%); max code difference to the detour %d" % (
             np.median(dt), spread, "PASS" if ok else "FAIL", (np.median(t) / np.median(dt) - 1) * 100, diff)
     lines.append(line)
-text = "\n".join(lines)
-print(text)
-if out_path:
-    with open(out_path, "w") as fh:
-        fh.write(text + "\n")
-sr.close()
+finish("\n".join(lines))
