@@ -167,6 +167,50 @@ int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, in
  * 1/(2(1-Kr)), 2^b - 1 } (18 values).  RSR_E_ARG for any other matrix, range or depth. */
 int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
 
+/* ---- rational output scales: x3, x3/2, x4/3, x9/4 ... area-averaged on the device (no reference counterpart) --------------------------
+ * Option "out_scale" (rsr_set_option) takes the x4 image down to x2 or x1 inside the library.  rsr_set_out_ratio generalises it to the
+ * scales real resize jobs ask for -- 720p -> 1080p is 3/2, 1080p -> 1440p 4/3, 480p -> 1080p 9/4, 720p -> 2160p 3/1 -- so that the x4
+ * frame (199 MB of fp16 for a 1080p source) never leaves the library to be resampled outside.
+ *   num / den is reduced by its gcd; after that den must be 1, 2, 3 or 4 and 1 <= num / den <= 4:
+ *            d = 1: 1, 2, 3, 4;  d = 2: 3/2, 5/2, 7/2;  d = 3: 4/3, 5/3, 7/3, 8/3, 10/3, 11/3;  d = 4: 5/4, 7/4, 9/4, 11/4, 13/4, 15/4.
+ *            Anything else: RSR_E_ARG, the ratio in force stays.  A new ratio takes effect for the next call, like "out_scale".
+ *   4/1, 2/1 and 1/1 ARE option "out_scale" 4 / 2 / 1: the same kernels, launches and bytes.  rsr_set_option("out_scale", v) keeps its
+ *            exact behaviour (v = 3 is still RSR_E_ARG: x3 is rsr_set_out_ratio(ctx, 3, 1)) and leaves a fractional ratio again.
+ *   Stats    "out_num" / "out_den": the ratio in force, in lowest terms; "out_scale" reads 4 / 2 / 1 as ever and 0 while any other ratio
+ *            is in force.
+ *   Sizes.   The output is (w * n / d) x (h * n / d) (rsr_out_size).  Every rsr_process* entry point honours the ratio -- host, device,
+ *            _fmt, _batch with windows, _tiles / _rows, _many, _group (whose members must agree on it), merged concurrent calls -- and
+ *            wherever a comment says "(w * out_scale) x (h * out_scale)" read "(w * n / d) x (h * n / d)".  Row pitches and windows are
+ *            checked against that size.
+ *   Errors.  RSR_E_ARG at call time, before anything is launched: w * n, h * n or tilesize * n not divisible by d (reduced terms).  The
+ *            tile condition is what keeps an averaging footprint inside its tile: every tile's output rectangle then starts on a whole
+ *            output pixel (tile 200 serves d = 2 and 4; tile 198 or 201 serves d = 3), and the reduction stays one small per-tile launch
+ *            behind conv_last (postproc_tiles_area) -- no whole-frame pass, no materialised x4 image.
+ *   Formats. Outputs RSR_FMT_U8_HWC (c 3 and 4), RSR_FMT_F16_CHW, RSR_FMT_F32_CHW.  The input side is independent: a YUV input works at
+ *            any ratio.
+ *   The definition, exact.  Scale n / d in lowest terms, L = 4 d.  Along one axis, on the integer grid where x4 pixel i covers
+ *   [i n, (i + 1) n), output pixel X covers [X L, (X + 1) L): its taps are i = floor(X L / n) .. floor(((X + 1) L - 1) / n), with the
+ *   integer weights g_i = min((X + 1) L, (i + 1) n) - max(X L, i n), each in 1 .. n, summing to L; at most 4 taps per axis for the
+ *   permitted ratios.  Coordinates are the image's (they equal the tile's own: tiles start on whole output pixels).
+ *            1. c(x, y) = min(max(r(x, y), 0), 1), r the fp32 value the uint8 conversion sees at x4 pixel (x, y) in the context's current
+ *               mode, as for "out_scale" (what RSR_FMT_F32_CHW holds at out_scale 4; under TTA the eight variants are merged first, in
+ *               the existing order)
+ *            2. horizontally first: for every source row, H = g_i0 * c_i0, then H = H + g_i * c_i in ascending i.  The weights are
+ *               converted to fp32; every multiplication and every addition is rounded by itself (no contraction)
+ *            3. then vertically the same way over the H of the tap rows: V = g_j0 * H_j0, then V = V + g_j * H_j in ascending j
+ *            4. m = min(V * fp32(1 / (16 d^2)), 1), the constant computed in double and rounded once
+ *            5. RSR_FMT_F32_CHW stores m, RSR_FMT_F16_CHW m rounded once to fp16, RSR_FMT_U8_HWC floor(m * 255 + 0.5) clamped to 0 .. 255
+ *            6. alpha (uint8, c == 4): the bicubic x4 alpha value of the x4 path, clamped to [0, 255], under the same weights, order and
+ *               constant, stored as floor(mean + 0.5)
+ *            7. "bgr" swaps channels 0 and 2 on store as ever; "precise" changes only what r is.
+ *   (For 2/1 the definition gives the bits of "out_scale" 2 -- weights 2, 2 and 1/16 against plain adds and 1/4 -- but 2/1 takes the box
+ *   kernel all the same.)
+ * Out of scope: a YUV OUTPUT (RSR_FMT_NV12 / RSR_FMT_P010) at a ratio other than 4 / 2 / 1: RSR_E_ARG. */
+int rsr_set_out_ratio(rsr_ctx* ctx, int num, int den);
+/* Host-only (no GPU): *ow = w * n / d, *oh = h * n / d for n / d = num / den reduced (either pointer may be NULL), or RSR_E_ARG for a ratio
+ * outside the set above, or when w * n, h * n or tilesize * n is not divisible by d: what a call at that ratio and tile size refuses. */
+int rsr_out_size(int num, int den, int tilesize, int w, int h, int* ow, int* oh);
+
 /* A device image behind its own pointer and pitches: a whole tensor, a crop of a larger frame, a frame inside a padded decoder surface, a
  * window of a canvas.  Pitches are in BYTES.  A uint8 row pitch need not be a multiple of the pixel size; for the planar formats both
  * pitches and `data` must be multiples of the element size (2 / 4).  No further alignment is asked of `data`. */
@@ -438,7 +482,8 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *                         5. "bgr" swaps channels 0 and 2 on store as ever; "precise" changes only what r is.
  *                       The clamp comes BEFORE the mean (the mean of the x4 image one would have got, not of the raw network output);
  *                       a box never crosses a tile.  Below 4, conv_last leaves its planar blob and one more small launch
- *                       (postproc_tiles_box) writes the image: the route RGBA and TTA take anyway
+ *                       (postproc_tiles_box) writes the image: the route RGBA and TTA take anyway.  Other scales (3, 3/2, 4/3 ...):
+                       rsr_set_out_ratio; setting "out_scale" leaves such a ratio again
  *   "yuv_matrix"        709 [default], 601 or 2020: Kr / Kb of the RSR_FMT_NV12 / RSR_FMT_P010 conversion; "yuv_range": 0 [default] = limited (16..235 /
  *                       16..240 at 8 bits), 1 = full.  Any other value: RSR_E_ARG, the value in force stays (stats "yuv_matrix", "yuv_range").
  *                       Both take effect for the next call, like "out_scale" (rsr_process_device_fmt has the definition)
@@ -493,7 +538,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *                       rsr_process_group allocates only the output rows of its tile range)
  *   "last_test_us"      HIP-event time of the last rsr_conv3x3 / rsr_conv3x3_res launch (with option "test_repeat" = N the
  *                       work items are repeated N times in that one launch: an L2-resident workload)
- *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force; "yuv_matrix" / "yuv_range" / "yuv_siting": likewise
+ *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force (0: a ratio other than 4 / 2 / 1, "out_num" / "out_den": rsr_set_out_ratio); "yuv_matrix" / "yuv_range" / "yuv_siting": likewise
  *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
  *                       "selfcheck_overflow" (-1 before the first run) */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);

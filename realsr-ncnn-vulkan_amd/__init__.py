@@ -9,6 +9,7 @@ creating a `RealSR` without a gfx950 device raises.  The directory name carries 
 reference's name + `_amd`); import it through the repo-root shim `realsr_ncnn_vulkan_amd.py`.
 """
 import ctypes as C
+import fractions
 import os
 import subprocess
 
@@ -31,6 +32,7 @@ EXPORTS = [
     "rsr_process_device_fmt", "rsr_image_bytes",
     "rsr_process_device_batch", "rsr_image_span",
     "rsr_yuv_constants",
+    "rsr_set_out_ratio", "rsr_out_size",
 ]
 
 NUM_CONVS = 351
@@ -112,6 +114,8 @@ def lib():
     L.rsr_image_span.argtypes = [ip, ip, ip, ip, C.c_longlong, C.c_longlong]
     L.rsr_image_span.restype = C.c_longlong
     L.rsr_yuv_constants.argtypes = [ip, ip, ip, C.POINTER(C.c_float), ip]
+    L.rsr_set_out_ratio.argtypes = [vp, ip, ip]
+    L.rsr_out_size.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_model_pack.argtypes = [cp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_device_memory.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rsr_host_alloc.argtypes = [C.c_size_t]
@@ -242,6 +246,37 @@ class RealSR:
         self.set_option("out_scale", int(s))  # (anything but 1, 2 or 4 raises RealSRError(RSR_E_ARG) and leaves the value alone)
 
     @property
+    def out_ratio(self):
+        """Size of the output relative to the input as a fractions.Fraction: out_scale generalised to n / d with d in 1..4 and
+        1 <= n / d <= 4 (3, 3/2, 4/3, 9/4 ...: rsr_set_out_ratio, include/realsr_hip.h), area-averaged on the device.  Set it with a
+        Fraction, an (n, d) pair or an int; 4, 2 and 1 ARE out_scale 4 / 2 / 1.  Takes effect for the next call.  Read from the engine."""
+        s = int(self.get_stat("out_scale"))
+        if s:
+            return fractions.Fraction(s)
+        return fractions.Fraction(int(self.get_stat("out_num")), int(self.get_stat("out_den")))
+
+    @out_ratio.setter
+    def out_ratio(self, r):
+        if isinstance(r, (tuple, list)):
+            n, d = int(r[0]), int(r[1])  # (as given: the engine reduces it, and refuses a zero denominator)
+        else:
+            r = fractions.Fraction(r)
+            n, d = r.numerator, r.denominator
+        self._ck(self._L.rsr_set_out_ratio(self._h, n, d))  # (a ratio outside the set raises RealSRError(RSR_E_ARG) and leaves the value alone)
+
+    def out_size(self, w, h):
+        """(ow, oh) of the output the next call writes for a w x h image: (w * n / d, h * n / d) at the ratio and tile size in force.
+        ValueError where the engine would refuse the call: w, h or tilesize times n is no multiple of d (rsr_out_size)."""
+        r = self.out_ratio
+        if r.denominator == 1:
+            return w * r.numerator, h * r.numerator
+        ow, oh = C.c_int(0), C.c_int(0)
+        if self._L.rsr_out_size(r.numerator, r.denominator, int(self.tilesize), int(w), int(h), C.byref(ow), C.byref(oh)) != 0:
+            raise ValueError("output ratio %s: %d x %d at tile %d: w, h and tilesize times %d must be multiples of %d"
+                             % (r, w, h, self.tilesize, r.numerator, r.denominator))
+        return ow.value, oh.value
+
+    @property
     def yuv_siting(self):
         """Where a chroma sample of an NV12 / P010 surface sits, on both sides of a call: 0 (default) = the centre of its 2 x 2 luma
         quad (JPEG, MPEG-1), 1 = left (H.264 / HEVC / AV1 / MPEG-2 default), 2 = top-left (BT.2020 / UHD HEVC) -- option "yuv_siting",
@@ -292,15 +327,15 @@ class RealSR:
         return v.value
 
     def process(self, img, out=None, push_params=True):
-        """out: optional preallocated (h * out_scale, w * out_scale, c) uint8 array (e.g. PinnedArray(...).array)."""
+        """out: optional preallocated (oh, ow, c) uint8 array, (ow, oh) = out_size(w, h) (e.g. PinnedArray(...).array)."""
         img = np.ascontiguousarray(img, dtype=np.uint8) if not (isinstance(img, np.ndarray) and img.flags.c_contiguous and img.dtype == np.uint8) else img
         h, w, c = img.shape
         if push_params:
             self._push_params()
-        s = self.out_scale
+        ow, oh = self.out_size(w, h)
         if out is None:
-            out = np.empty((h * s, w * s, c), dtype=np.uint8)
-        assert out.shape == (h * s, w * s, c) and out.dtype == np.uint8 and out.flags.c_contiguous
+            out = np.empty((oh, ow, c), dtype=np.uint8)
+        assert out.shape == (oh, ow, c) and out.dtype == np.uint8 and out.flags.c_contiguous
         self._ck(self._L.rsr_process(self._h, _p(img), w, h, c, _p(out)))
         return out
 
@@ -308,8 +343,8 @@ class RealSR:
         """rsr_process_many: a list of uint8 HWC images in ONE call (small ones share tile batches); returns the list of outputs."""
         imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
         n = len(imgs)
-        s = self.out_scale
-        outs = [np.empty((im.shape[0] * s, im.shape[1] * s, im.shape[2]), dtype=np.uint8) for im in imgs]
+        sizes = [self.out_size(im.shape[1], im.shape[0]) for im in imgs]
+        outs = [np.empty((oh, ow, im.shape[2]), dtype=np.uint8) for im, (ow, oh) in zip(imgs, sizes)]
         self._push_params()
         ins_p = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
         outs_p = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
@@ -328,7 +363,7 @@ class RealSR:
 
     def process_device_fmt(self, d_in, in_fmt, w, h, c, d_out, out_fmt, stream=None):
         """rsr_process_device_fmt: process_device with a pixel format (RSR_FMT_*) per side; the planar float formats need c == 3.
-        Buffer sizes: image_bytes(in_fmt, w, h, c) and image_bytes(out_fmt, w * out_scale, h * out_scale, c).  torch tensors: torch_io.upscale."""
+        Buffer sizes: image_bytes(in_fmt, w, h, c) and image_bytes(out_fmt, *out_size(w, h), c).  torch tensors: torch_io.upscale."""
         self._push_params()
         self._ck(self._L.rsr_process_device_fmt(self._h, C.c_void_p(int(d_in)), int(in_fmt), w, h, c, C.c_void_p(int(d_out)), int(out_fmt),
                                                 C.c_void_p(int(stream)) if stream else None))
@@ -343,9 +378,9 @@ class RealSR:
                                                   C.c_void_p(int(stream)) if stream else None))
 
     def _check_full_out(self, out, h, w, c):
-        s = self.out_scale
-        if out.shape != (h * s, w * s, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous uint8 array of shape %s (out_scale %d), not %s %s" % ((h * s, w * s, c), s, out.dtype, out.shape))
+        ow, oh = self.out_size(w, h)
+        if out.shape != (oh, ow, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint8 array of shape %s (output ratio %s), not %s %s" % ((oh, ow, c), self.out_ratio, out.dtype, out.shape))
 
     def process_rows(self, img, out, row0, row1):
         """Tile rows [row0, row1) of img's tile grid into the full-size `out` (see rsr_process_rows)."""
@@ -579,11 +614,11 @@ def process_group(srs, img, out=None):
     h, w, c = img.shape
     for s in srs:
         s._push_params()
-    os_ = srs[0].out_scale  # (members that disagree: RSR_E_ARG from the call)
+    ow, oh = srs[0].out_size(w, h)  # (members that disagree: RSR_E_ARG from the call)
     if out is None:
-        out = np.empty((h * os_, w * os_, c), dtype=np.uint8)
-    if out.shape != (h * os_, w * os_, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
-        raise ValueError("out must be a contiguous uint8 array of shape %s (out_scale %d)" % ((h * os_, w * os_, c), os_))
+        out = np.empty((oh, ow, c), dtype=np.uint8)
+    if out.shape != (oh, ow, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous uint8 array of shape %s (output ratio %s)" % ((oh, ow, c), srs[0].out_ratio))
     hs = (C.c_void_p * len(srs))(*[s._h for s in srs])
     rc = L.rsr_process_group(hs, len(srs), _p(img), w, h, c, _p(out))
     if rc != 0:

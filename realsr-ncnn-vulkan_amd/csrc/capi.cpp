@@ -222,6 +222,29 @@ long long rsr_image_bytes(int fmt, int w, int h, int c)
     return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
 }
 
+int rsr_set_out_ratio(rsr_ctx* ctx, int num, int den)
+{
+    if (!ctx) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    rsr::OutRatio r;
+    if (!rsr::out_ratio_reduce(num, den, &r)) return ctx->e.fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
+    ctx->e.out_ratio = r; // the next call's output is (w * n / d) x (h * n / d): plans are keyed by it; 4 / 1, 2 / 1, 1 / 1 ARE option "out_scale"
+    return RSR_OK;
+}
+
+int rsr_out_size(int num, int den, int tilesize, int w, int h, int* ow, int* oh)
+{
+    rsr::OutRatio r;
+    if (!rsr::out_ratio_reduce(num, den, &r)) return Engine::fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
+    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
+    if (!r.divides(w) || !r.divides(h) || !r.divides(tilesize))
+        return Engine::fail(RSR_E_ARG, "output ratio " + std::to_string(r.n) + "/" + std::to_string(r.d) + ": w, h and tilesize times " + std::to_string(r.n) +
+                                           " must be multiples of " + std::to_string(r.d));
+    if (ow) *ow = int(r.of(w));
+    if (oh) *oh = int(r.of(h));
+    return RSR_OK;
+}
+
 int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n)
 {
     rsr::YuvCoef c;
@@ -531,7 +554,9 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "merged_widest") *value = double(e.merged_widest.load());
     else if (k == "merged_mixed") *value = double(e.merged_mixed.load());
     else if (k == "precise_active") *value = e.precise ? 1.0 : 0.0;
-    else if (k == "out_scale") *value = double(e.out_scale);
+    else if (k == "out_scale") *value = double(e.out_ratio.out_scale()); // (0 while a ratio other than 4, 2 or 1 is in force: rsr_set_out_ratio)
+    else if (k == "out_num") *value = double(e.out_ratio.n);
+    else if (k == "out_den") *value = double(e.out_ratio.d);
     else if (k == "yuv_matrix") *value = double(e.yuv_matrix);
     else if (k == "yuv_range") *value = double(e.yuv_range);
     else if (k == "yuv_siting") *value = double(e.yuv_siting);
@@ -579,7 +604,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     else if (k == "out_scale")
     { // the next call's output is (w * value) x (h * value): plans are keyed by it (below 4 conv_last leaves the planar blob to postproc_tiles_box)
         if (value != 1 && value != 2 && value != 4) return ctx->e.fail(RSR_E_ARG, "out_scale must be 1, 2 or 4");
-        ctx->e.out_scale = int(value);
+        ctx->e.out_ratio = rsr::OutRatio{int(value), 1}; // (leaves a fractional ratio, rsr_set_out_ratio, again)
     }
     else if (k == "yuv_matrix")
     { // Kr / Kb of the NV12 / P010 formats; read when the next call is enqueued

@@ -471,7 +471,7 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
 {
     const long long kBytesPerPx = bytes_per_px();
     for (auto it = plans.begin(); it != plans.end(); ++it)
-        if (it->w == w && it->h == h && it->c == c && it->T == tilesize && it->P == prepadding && it->tta == tta && it->nimg == nimg && it->precise == precise && it->out_scale == out_scale && it->ntw2 == ((flow_flags & 1) != 0) &&
+        if (it->w == w && it->h == h && it->c == c && it->T == tilesize && it->P == prepadding && it->tta == tta && it->nimg == nimg && it->precise == precise && it->ratio == out_ratio && it->ntw2 == ((flow_flags & 1) != 0) &&
             it->tile0 == tile0 && it->tile1 == tile1 && it->budget_mb == max_workspace_mb && it->trim == trim_tail && it->xcd_order == xcd_order && it->fold == fold_cols &&
             it->clamp == ws_clamp_bytes)
         {
@@ -515,7 +515,7 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
     plan.w = w; plan.h = h; plan.c = c; plan.T = T; plan.P = P; plan.tta = tta;
     plan.nimg = nimg;
     plan.precise = precise;
-    plan.out_scale = out_scale;
+    plan.ratio = out_ratio;
     plan.ntw2 = (flow_flags & 1) != 0;
     plan.tile0 = tile0; plan.tile1 = tile1;
     plan.budget_mb = max_workspace_mb;
@@ -926,7 +926,7 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
 int Engine::enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size_t* half_rows, hipStream_t st)
 {
     const int nimg = io.nimg, w = io.w[0], h = io.h[0], c = io.c;
-    if (io.os != out_scale) return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the images of io are sized for io.os)
+    if (io.os != out_ratio) return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the images of io are sized for io.os)
     const bool merged = plan_nimg > 0; // (every caller of a merged batch reports the progress of its own image: process_host)
     if (plan_nimg < nimg) plan_nimg = nimg;
     const long long kBytesPerPx = bytes_per_px();
@@ -1084,12 +1084,15 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     po.out_fmt = io.out_fmt;
     po.c = c;
     po.out_row0 = io.out_row0;
-    po.box = 4 / io.os;
+    po.box = io.os.is_box() ? 4 / io.os.n : 1;
+    po.num = io.os.n;
+    po.den = io.os.d;
+    po.area_norm = float(1.0 / (16.0 * io.os.d * io.os.d));
     po.tilesize = tilesize;
     po.bgr = bgr ? 1 : 0;
     po.variant = variant;
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
-    mark(2, 0, b.px[2] / per * (6.0 * per + px_bytes(io.out_fmt) * io.os * io.os / 16.0), st);
+    mark(2, 0, b.px[2] / per * (6.0 * per + px_bytes(io.out_fmt) * io.os.n * io.os.n / (16.0 * io.os.d * io.os.d)), st);
     return RSR_OK;
 }
 
@@ -1160,14 +1163,16 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
     hipEvent_t done = nullptr;
     if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
     { // a small image: merged with whatever other calls hand in meanwhile (Engine::submit_merged)
-        int T = 0, width = 1, os = 4;
+        int T = 0, width = 1;
+        OutRatio os;
         long long items = 0;
         { // (the engine's settings are read under its lock: another thread may be in rsr_set_params / rsr_set_option)
             std::lock_guard<std::mutex> lk(mu);
             if (!loaded) return fail(RSR_E_STATE, "process before load");
             if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
             T = tilesize;
-            os = out_scale;
+            os = out_ratio;
+            if (const int rc = check_ratio_out(out_fmt, w, h, T, os)) return rc;
             width = merge_width(w, h, c);
             if (width > 1) items = image_items(w, h, merge_target_items);
         }
@@ -1193,7 +1198,8 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
         std::lock_guard<std::mutex> lk(mu);
         if (!loaded) return fail(RSR_E_STATE, "process before load");
         if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
-        if (const int rc = check_yuv_out(out_fmt, w, h, out_scale)) return rc;
+        if (const int rc = check_ratio_out(out_fmt, w, h, tilesize, out_ratio)) return rc;
+        if (const int rc = check_yuv_out(out_fmt, w, h, out_ratio)) return rc;
         HIP_TRY(hipSetDevice(device));
         if (user_stream && hipStreamQuery(stream) == hipSuccess)
         {
@@ -1201,7 +1207,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             // put on ITS caller's stream included: the compute stream was made to wait for it, below) -- so this call's kernels go
             // straight onto the caller's stream: no event hop into the compute stream and back.  Whatever is enqueued on the compute
             // stream later uses the same workspace and must come behind: it waits for this call's last kernel.
-            const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt, out_scale), 0, -1, 0, nullptr, user_stream);
+            const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt, out_ratio), 0, -1, 0, nullptr, user_stream);
             hipEvent_t e = take_event();
             if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
             { // cannot order the compute stream behind it: fall back to waiting here
@@ -1222,7 +1228,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             HIP_TRY(hipStreamWaitEvent(stream, e, 0));
             give_event(e);
         }
-        const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt, out_scale), 0, -1, 0, nullptr, stream);
+        const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt, out_ratio), 0, -1, 0, nullptr, stream);
         if (rc != RSR_OK) return rc;
         if (user_stream || sync)
         {
@@ -1273,11 +1279,37 @@ bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
 
 // A YUV output is written one 2 x 2 luma quad per thread, tile by tile: the image and every tile's rectangle must start and end on even
 // output pixels (only out_scale 1 can break that).  mu held (tilesize).
-int Engine::check_yuv_out(int out_fmt, int w, int h, int os) const
+int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
 {
     if (!fmt_is_yuv(out_fmt)) return RSR_OK;
+    const int os = ratio.out_scale(); // (check_ratio_out has refused a YUV output at any other ratio)
     if (((w * os) | (h * os) | (tilesize * os)) & 1)
         return fail(RSR_E_ARG, "a YUV 4:2:0 output needs w * out_scale, h * out_scale and tilesize * out_scale even");
+    return RSR_OK;
+}
+
+// ---- rational output scales (rsr_set_out_ratio) -----------------------------------------------------------------------------------------
+bool out_ratio_reduce(int num, int den, OutRatio* out)
+{
+    if (num < 1 || den < 1) return false;
+    int a = num, b = den;
+    while (b) { const int t = a % b; a = b; b = t; }
+    const int n = num / a, d = den / a;
+    if (d > 4 || n < d || n > 4 * d) return false;
+    out->n = n, out->d = d;
+    return true;
+}
+
+// An output pixel of scale n / d is a whole number of them only where the image's sides times n are multiples of d; and only where the
+// tile size times n is one too does every tile's rectangle start on a whole output pixel, so that no averaging footprint crosses a tile
+// (postproc_tiles_area is a per-tile launch).  Always true for 4, 2 and 1.  Checked before anything is launched.
+int Engine::check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const
+{
+    if (os.is_box()) return RSR_OK;
+    if (fmt_is_yuv(out_fmt)) return fail(RSR_E_ARG, "a YUV 4:2:0 output takes out_scale 4, 2 or 1 only: no other output ratio (rsr_set_out_ratio)");
+    if (!os.divides(w) || !os.divides(h) || !os.divides(T))
+        return fail(RSR_E_ARG, "output ratio " + std::to_string(os.n) + "/" + std::to_string(os.d) + ": w, h and tilesize times " + std::to_string(os.n) +
+                                   " must be multiples of " + std::to_string(os.d) + " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
     return RSR_OK;
 }
 
@@ -1311,17 +1343,19 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
     if (n < 1 || !in || !out) return fail(RSR_E_ARG, "bad image arguments");
     long long irow = 0, iplane = 0, orow = 0, oplane = 0;
     std::vector<long long> lay(size_t(n) * 4);
-    int os = 4; // the output windows are checked against the out_scale in force now; should it change before the launch: RSR_E_STATE
+    OutRatio os; // the output windows are checked against the output ratio in force now; should it change before the launch: RSR_E_STATE
     {
         std::lock_guard<std::mutex> lk(mu);
-        os = out_scale;
+        os = out_ratio;
+        if (n >= 1 && w >= 1 && h >= 1)
+            if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
     }
     for (int i = 0; i < n; i++)
     {
         if (!in[i].data || !out[i].data) return fail(RSR_E_ARG, "image " + std::to_string(i) + ": null data pointer");
         int rc = image_layout(in_fmt, w, h, c, in[i].row_pitch, in[i].plane_pitch, &irow, &iplane);
         if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
-        if (rc == RSR_OK) rc = image_layout(out_fmt, w * os, h * os, c, out[i].row_pitch, out[i].plane_pitch, &orow, &oplane);
+        if (rc == RSR_OK) rc = image_layout(out_fmt, int(os.of(w)), int(os.of(h)), c, out[i].row_pitch, out[i].plane_pitch, &orow, &oplane);
         if (rc != RSR_OK) return rc;
         if (reinterpret_cast<uintptr_t>(in[i].data) % uintptr_t(in_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(in_fmt, c)) ||
             reinterpret_cast<uintptr_t>(out[i].data) % uintptr_t(out_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(out_fmt, c)))
@@ -1334,7 +1368,8 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
         std::lock_guard<std::mutex> lk(mu);
         if (!loaded) return fail(RSR_E_STATE, "process before load");
         if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
-        if (out_scale != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
+        if (out_ratio != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
+        if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
         if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
         HIP_TRY(hipSetDevice(device));
         // As in process_device: an idle engine runs the call on the caller's own stream, a busy one on the compute stream between two events.
@@ -1448,7 +1483,7 @@ int Engine::run_group(MergeReq* const* g, int n)
     std::lock_guard<std::mutex> lk(mu);
     if (!loaded || scale != 4) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
     for (int i = 0; i < n; i++)
-        if (g[i]->T != tilesize || g[i]->os != out_scale) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
+        if (g[i]->T != tilesize || g[i]->os != out_ratio) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
     HIP_TRY(hipSetDevice(device));
     for (int i = 0; i < n; i++)
         if (g[i]->ev_in) HIP_TRY(hipStreamWaitEvent(stream, g[i]->ev_in, 0));
@@ -1665,18 +1700,20 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
 {
     if (!in || !out || w < 1 || h < 1 || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
     const size_t nin = size_t(w) * h * c;
-    int T = 0, mwidth = 1, os = 4; // os: the out_scale in force when the call came in (the size of `out`)
+    int T = 0, mwidth = 1;
+    OutRatio os; // the output ratio in force when the call came in (the size of `out`)
     long long mitems = 0;
     { // state checks BEFORE anything is enqueued on behalf of this call (and the engine's settings read under its lock)
         std::lock_guard<std::mutex> lk(mu);
         if (!loaded) return fail(RSR_E_STATE, "process before load");
         if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
         T = tilesize;
-        os = out_scale;
+        os = out_ratio;
+        if (const int rrc = check_ratio_out(RSR_FMT_U8_HWC, w, h, T, os)) return rrc;
         mwidth = merge_width(w, h, c);
         if (mwidth > 1) mitems = image_items(w, h, merge_target_items);
     }
-    const size_t nout_full = nin * size_t(os) * os;
+    const size_t nout_full = size_t(os.of(w)) * size_t(os.of(h)) * c;
     const int xtiles = (w + T - 1) / T, ytiles = (h + T - 1) / T;
     if (tile1 < 0) tile1 = xtiles * ytiles;
     if (tile0 < 0 || tile1 > xtiles * ytiles || tile0 >= tile1) return fail(RSR_E_ARG, "tile range outside the image");
@@ -1724,16 +1761,16 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
     // The device output holds only the output ROWS of this call's tile range (a member of rsr_process_group running an eighth
     // of a 4K frame does not allocate 398 MB for it): the kernels get the address row 0 would have and only ever write
     // inside the rectangles of the range's tiles (conv_last / postproc_tiles place by tile), i.e. inside the allocation.
-    const size_t rowbytes = size_t(w) * os * c; // one output row
-    auto yof = [&](int tr) { return size_t(std::min(tr * T, h)) * os; };  // first output row of tile row tr
-    auto xof = [&](int tc) { return size_t(std::min(tc * T, w)) * os * c; }; // byte column of tile column tc
+    const size_t rowbytes = size_t(os.of(w)) * c; // one output row
+    auto yof = [&](int tr) { return size_t(os.of(std::min(tr * T, h))); };  // first output row of tile row tr (whole: check_ratio_out)
+    auto xof = [&](int tc) { return size_t(os.of(std::min(tc * T, w))) * c; }; // byte column of tile column tc
     const int r0 = tile0 / xtiles, c0 = tile0 % xtiles, r1 = (tile1 - 1) / xtiles, c1 = (tile1 - 1) % xtiles + 1; // last tile = (r1, c1 - 1)
     const size_t base_off = yof(r0) * rowbytes;
     if ((rc = ensure(L->d_out, (yof(r1 + 1) - yof(r0)) * rowbytes)) != RSR_OK) return rc;
     L->in_bytes.store(L->d_in.bytes, std::memory_order_relaxed); // what device_avail() / rsr_get_stat read (they do not hold this lane)
     L->out_bytes.store(L->d_out.bytes, std::memory_order_relaxed);
     // the kernels get the REAL base of the allocation: the plan of a tile range places its tiles relative to the range's first
-    // output row (Plan::out_row0, in x4 rows, is yof(r0) * 4 / os: get_plan); dev(off) = device address of byte `off` of the full-size image
+    // output row (Plan::out_row0, in x4 rows, is the x4 row of yof(r0): get_plan); dev(off) = device address of byte `off` of the full-size image
     char* const dbase = static_cast<char*>(L->d_out.p);
     auto dev = [&](size_t off) { return dbase + (off - base_off); };
 
@@ -1776,7 +1813,7 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
     else
     {
         std::lock_guard<std::mutex> lk(mu);
-        if (!loaded || scale != 4 || tilesize != T || out_scale != os)
+        if (!loaded || scale != 4 || tilesize != T || out_ratio != os)
             return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the guard drains the upload)
         HIP_TRY(hipStreamWaitEvent(stream, L->ev_in, 0));
         BatchIO io(L->d_in.p, dbase, w, h, c, RSR_FMT_U8_HWC, RSR_FMT_U8_HWC, os);

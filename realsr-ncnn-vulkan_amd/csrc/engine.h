@@ -39,6 +39,21 @@
 
 namespace rsr {
 
+// The size of the output relative to the input, n / d in lowest terms (include/realsr_hip.h rsr_set_out_ratio).  4 / 1, 2 / 1 and 1 / 1 are
+// option "out_scale" 4 / 2 / 1 and take its kernels; every other permitted ratio is area-averaged by postproc_tiles_area.
+struct OutRatio
+{
+    int n = 4, d = 1;
+    bool operator==(const OutRatio& o) const { return n == o.n && d == o.d; }
+    bool operator!=(const OutRatio& o) const { return !(*this == o); }
+    bool is_box() const { return d == 1 && (n == 4 || n == 2 || n == 1); }
+    int out_scale() const { return is_box() ? n : 0; }                 // what stat "out_scale" reads
+    long long of(long long x) const { return x * n / d; }              // an input length in output pixels (exact where the call was admitted)
+    bool divides(long long x) const { return x * n % d == 0; }
+};
+// Host-only: num / den reduced to lowest terms when it is one of the permitted ratios (d in 1..4, 1 <= n / d <= 4), else false.
+bool out_ratio_reduce(int num, int den, OutRatio* out);
+
 struct DevBuf
 {
     void* p = nullptr;
@@ -63,7 +78,7 @@ struct Plan
     int w = 0, h = 0, c = 0, T = 0, P = 0, tta = 0;
     int nimg = 1;         // images of this geometry merged into one tile batch (kernels.h kMaxMerge); their tiles follow each other image by image
     bool precise = false; // Engine::precise when the plan was built (the slots are larger: part of the cache key)
-    int out_scale = 4;    // Engine::out_scale when the plan was built (part of the cache key, though no field of a Plan depends on it today: the placement tables are built alike and below 4 merely go unused)
+    OutRatio ratio;       // Engine::out_ratio when the plan was built (part of the cache key, though no field of a Plan depends on it today: the placement tables are built alike and below 4 merely go unused)
     bool ntw2 = false;    // flow_flags bit 0 when the plan was built (an MFMA wave then reaches 4 planes from one base: the tile-size bound halves)
     int tile0 = 0, tile1 = 0; // tiles [tile0, tile1) of the image's tile grid, row-major (multi-GPU tile sharding)
     long long budget_mb = 0;
@@ -125,7 +140,7 @@ struct MergeReq
     const void* d_in = nullptr;
     void* d_out = nullptr;
     int w = 0, h = 0, c = 0, T = 0;
-    int os = 4;                   // Engine::out_scale when the call came in: d_out is (w * os) x (h * os)
+    OutRatio os;                  // Engine::out_ratio when the call came in: d_out is os.of(w) x os.of(h)
     long long items = 0;          // LR-level work items of the image (Engine::image_items)
     int width = 1;                // Engine::merge_width of its geometry when the call came in
     hipEvent_t ev_in = nullptr;   // the input is complete behind this event (null: it already is)
@@ -142,19 +157,19 @@ struct BatchIO
 {
     int nimg = 0, c = 0;        // images of the batch (<= kMaxMerge; BaseTile::img selects) and their channel count
     const void* in[kMaxMerge];  // per image: the device image, in_fmt, w[i] x h[i] ...
-    void* out[kMaxMerge];       // ... and its (w[i] * os) x (h[i] * os) result, out_fmt
-    int os = 4;                 // Engine::out_scale of the call: 4, or 2 / 1 = the x4 result box-reduced (kernels.h PostArgs::box = 4 / os)
+    void* out[kMaxMerge];       // ... and its os.of(w[i]) x os.of(h[i]) result, out_fmt
+    OutRatio os;                // Engine::out_ratio of the call: 4, or 2 / 1 = the x4 result box-reduced (kernels.h PostArgs::box = 4 / os), or another ratio = area-averaged (PostArgs::num / den)
     int w[kMaxMerge], h[kMaxMerge];
     // Bytes from one row / one plane (planar formats) of an image to the next, resolved (never 0; rsr_image of the C ABI, image_layout).
     // The constructors set the tightly packed values; Engine::process_device_batch overwrites them with the caller's.
     long long in_pitch[kMaxMerge], in_plane[kMaxMerge], out_pitch[kMaxMerge], out_plane[kMaxMerge];
     int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float and the YUV formats come with whole images of c == 3 only;
                                                            // YUV: the plane pitch is the distance from Y(0,0) to the UV plane)
-    int out_row0 = 0;           // `out` points at output row out_row0 * os / 4 of the image; out_row0 counts x4 rows (a tile range's device buffer holds only its rows)
+    int out_row0 = 0;           // `out` points at output row os.of(out_row0) / 4 of the image; out_row0 counts x4 rows (a tile range's device buffer holds only its rows)
     int split_slot = 0;         // > 0: the 4x tail is split in front of this slot and ...
     hipEvent_t ev_half = nullptr; // ... this event recorded behind the first part (the caller starts downloading its output rows)
     hipEvent_t ev_mid = nullptr;  // recorded behind the middle RDB (a merged batch's throttle event, Engine::submit_merged)
-    BatchIO(const void* d_in, void* d_out, int w0, int h0, int c0, int in_fmt0, int out_fmt0, int os0) : nimg(1), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0)
+    BatchIO(const void* d_in, void* d_out, int w0, int h0, int c0, int in_fmt0, int out_fmt0, OutRatio os0) : nimg(1), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0)
     {
         set(0, d_in, d_out, w0, h0);
     }
@@ -162,7 +177,7 @@ struct BatchIO
     {
         for (int i = 0; i < n; i++) set(i, g[i]->d_in, g[i]->d_out, g[i]->w, g[i]->h);
     }
-    BatchIO(int n, int c0, int in_fmt0, int out_fmt0, int os0) : nimg(n), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
+    BatchIO(int n, int c0, int in_fmt0, int out_fmt0, OutRatio os0) : nimg(n), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
     static long long px_bytes(int fmt, int c) // of one element of a row (NV12 / P010: of one sample; a UV row has as many bytes as a Y row)
     {
         return fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_P010 ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : (fmt == RSR_FMT_NV12 ? 1 : c));
@@ -171,7 +186,7 @@ struct BatchIO
     {
         in[i] = d_in, out[i] = d_out, w[i] = wi, h[i] = hi;
         in_pitch[i] = wi * px_bytes(in_fmt, c), in_plane[i] = hi * in_pitch[i];
-        out_pitch[i] = os * wi * px_bytes(out_fmt, c), out_plane[i] = os * hi * out_pitch[i];
+        out_pitch[i] = os.of(wi) * px_bytes(out_fmt, c), out_plane[i] = os.of(hi) * out_pitch[i];
     }
 };
 
@@ -203,7 +218,10 @@ struct Engine
     // Output scale (option "out_scale"; include/realsr_hip.h): 4 = the network's x4 image; 2 / 1 = every 2 x 2 / 4 x 4 box of it, clamped to
     // [0, 1] first, leaves as its fp32 mean.  A box never crosses a tile (a tile's x4 rectangle starts and ends on multiples of 4), so the
     // reduction is the per-tile post-processing launch (kernels.hip postproc_tiles_box); conv_last then leaves the planar blob.
-    int out_scale = 4;
+    // out_ratio generalises it (rsr_set_out_ratio): n / d with d in 1..4 and 1 <= n / d <= 4.  For a scale that is not 4, 2 or 1 the footprint of
+    // an output pixel is up to 4 x 4 x4 pixels with integer weights; whenever tilesize * n is a multiple of d a tile's rectangle starts on a
+    // whole output pixel, no footprint crosses a tile, and the reduction is still ONE per-tile launch (postproc_tiles_area).
+    OutRatio out_ratio;
     // YUV <-> RGB of the NV12 / P010 device formats (options "yuv_matrix", "yuv_range"; include/realsr_hip.h): Kr / Kb of BT.709, 601 or
     // 2020, limited (0) or full (1) range.  Read when a call is enqueued: the constants travel with the launch (kernels.h YuvCoef).
     int yuv_matrix = 709, yuv_range = 0;
@@ -342,8 +360,9 @@ struct Engine
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
     // no TTA merge / alpha channel / box reduction / YUV 4:2:0 surface needs the planar blob (dbg 8192: off)
-    bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_scale == 4 && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
-    int check_yuv_out(int out_fmt, int w, int h, int os) const; // RSR_E_ARG when a 2 x 2 chroma quad of a YUV output would cross the image or a tile
+    bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
+    int check_yuv_out(int out_fmt, int w, int h, OutRatio os) const; // RSR_E_ARG when a 2 x 2 chroma quad of a YUV output would cross the image or a tile
+    int check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const; // RSR_E_ARG when w, h or the tile size T times os is no whole number of pixels, or for a YUV output at a ratio other than 4 / 2 / 1 (no lock needed)
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
     // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).

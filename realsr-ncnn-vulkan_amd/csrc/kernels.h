@@ -216,6 +216,12 @@ struct PostArgs
     // to [0, 1] first, leaves as ONE pixel, its fp32 mean (postproc_tiles_box): the outs are (4 / K)w x (4 / K)h.  Everything above stays in
     // x4 units (BaseTile::out_*, out_row0, crop: all multiples of 4); the kernel divides by K.
     int box;
+    // Area-averaged output at a rational scale num / den in lowest terms (rsr_set_out_ratio; den in 1..4, 1 <= num / den <= 4) that is not
+    // 4, 2 or 1 -- those are `box` above, and num = 0 / 4 with box <= 1 is the x4 image --: postproc_tiles_area, the outs are
+    // (w * num / den) x (h * num / den).  Everything above stays in x4 units; the kernel converts with * num / (4 * den), exact because the
+    // engine refuses a call whose image or tile size times num is not a multiple of den.  area_norm = fp32(1 / (16 * den * den)).
+    int num, den;
+    float area_norm;
     YuvCoef yuv; // out_fmt kFmtNV12 / kFmtP010 only
     // ... likewise: the chroma siting (engine option "yuv_siting": 0 centre, 1 left, 2 top-left).  The sited chroma filters clamp at the
     // first column / row of a TILE's rectangle; that is quad column / row 0 of the tile's own grid (BaseTile::out_*), so nothing else travels.

@@ -991,6 +991,109 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
     store_pair<TO>(ouv, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
 }
 
+// ---- area-averaged output at a rational scale (rsr_set_out_ratio: PostArgs::num / den, e.g. 3/2, 4/3, 9/4, 3/1) -------------------------
+// The sibling of postproc_tiles_box for the scales n / d that are not 4, 2 or 1: one thread makes ONE output pixel (X, Y) of the tile's
+// rectangle.  On the integer grid where x4 pixel i covers [i n, (i + 1) n) and output pixel X covers [X L, (X + 1) L), L = 4 d, its taps
+// along an axis are i = floor(X L / n) .. floor(((X + 1) L - 1) / n) -- at most 4 -- with the integer weights g_i = the overlap, which sum
+// to L.  A tile's kept x4 rectangle starts on a multiple of L grid units (the engine refuses the call otherwise: tilesize * n is a multiple
+// of d), so the tile's own coordinates are the image's and no footprint crosses a tile.  include/realsr_hip.h (rsr_set_out_ratio) fixes the
+// arithmetic: every tap clamped to [0, 1] (TTA: the eight variants merged first), horizontally H = g c, H = H + g c in ascending i, then
+// vertically the same over the rows' H, every product and sum rounded by itself; m = min(V * fp32(1 / (16 d^2)), 1).
+// The ratio is a runtime argument: the tap loops have no arrays to index, so nothing is gained by unrolling them per ratio.  Taps are
+// fetched one at a time through merged_block<TP, 1>; lanes run along x, so a wave's loads of one tap row fall into a few cache lines.
+// One channel at a time, as in the box kernel.  ALPHA: PostArgs::c == 4, the bicubic x4 alpha under the same weights.
+template <typename TP, typename TO, bool ALPHA>
+__global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
+{
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int n = a.num, L = 4 * a.den;
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= t.out_w * n / L || gy >= t.out_h * n / L) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const long long cstep = (long long)w * h;
+    const int x0 = gx * L, x1 = x0 + L, y0 = gy * L, y1 = y0 + L;              // the pixel's footprint on the grid
+    const int ix0 = x0 / n, ix1 = (x1 - 1) / n, iy0 = y0 / n, iy1 = (y1 - 1) / n; // its taps: x4 pixels of the tile's kept rectangle
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    constexpr int es = sizeof(TO) == 1 ? 1 : (int)sizeof(TO);
+    uint8_t* const o = a.outs[im] + ((long long)(t.out_y - a.out_row0) * n / L + gy) * (long long)a.out_pitch[im] +
+                       ((long long)t.out_x * n / L + gx) * (sizeof(TO) == 1 ? a.c : es);
+#pragma unroll 1
+    for (int q = 0; q < 3; q++)
+    {
+        const TP* b = b0 + q * cstep;
+        float V = 0.f;
+#pragma unroll 1
+        for (int j = iy0; j <= iy1; j++)
+        {
+            float H = 0.f;
+#pragma unroll 1
+            for (int i = ix0; i <= ix1; i++)
+            {
+                float c[1][1];
+                merged_block<TP, 1>(b, ss, w, h, i + a.crop, j + a.crop, a.tta, c);
+                const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), c[0][0]);
+                H = i == ix0 ? p : add_rn(H, p);
+            }
+            const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
+            V = j == iy0 ? p : add_rn(V, p);
+        }
+        const float m = fminf(mul_rn(V, a.area_norm), 1.f);
+        const int qo = a.bgr ? 2 - q : q;
+        if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)m;
+        else o[qo] = post_store(m * 255.f);
+    }
+    if constexpr (ALPHA)
+    { // alpha: postproc_tiles' bicubic x4 value at every tap, clamped to [0, 255], under the same weights, order and constant
+        const int aw = t.out_w / 4, ah = t.out_h / 4;
+        const int ax0 = t.out_x / 4, ay0 = t.out_y / 4;
+        float V = 0.f;
+#pragma unroll 1
+        for (int j = iy0; j <= iy1; j++)
+        {
+            int by;
+            float cy[4];
+            cubic_coeffs(ah, t.out_h, j, by, cy);
+            float H = 0.f;
+#pragma unroll 1
+            for (int i = ix0; i <= ix1; i++)
+            {
+                int bx;
+                float cx[4];
+                cubic_coeffs(aw, t.out_w, i, bx, cx);
+                float rows[4];
+#pragma unroll
+                for (int jj = 0; jj < 4; jj++)
+                {
+                    const int yy = ay0 + clampi(by - 1 + jj, ah);
+                    const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
+                    rows[jj] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
+                               (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
+                }
+                const float av = rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
+                const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), fminf(fmaxf(av, 0.f), 255.f));
+                H = i == ix0 ? p : add_rn(H, p);
+            }
+            const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
+            V = j == iy0 ? p : add_rn(V, p);
+        }
+        o[3] = post_store(mul_rn(V, a.area_norm));
+    }
+}
+
+template <typename TP>
+static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    const int L = 4 * a.den;
+    const dim3 grid((max_ow * a.num / L + 63) / 64, (max_oh * a.num / L + 3) / 4, a.ntiles), block(256);
+    if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_area<TP, _Float16, false>), grid, block, 0, st, a);
+    else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_area<TP, float, false>), grid, block, 0, st, a);
+    else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
+}
+
 template <typename TP, typename TO>
 static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
@@ -1015,6 +1118,11 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
     { // a 4:2:0 surface: one thread per luma quad, at every out_scale, with and without TTA
         if (a.out_fmt == kFmtNV12) a.f32 ? launch_postproc_yuv<float, uint8_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint8_t>(a, max_ow, max_oh, st);
         else a.f32 ? launch_postproc_yuv<float, uint16_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint16_t>(a, max_ow, max_oh, st);
+        return;
+    }
+    if (a.num > 0 && !(a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1)))
+    { // a rational scale other than 4 / 2 / 1 (rsr_set_out_ratio): the area-averaging kernel (one thread per output pixel, with and without TTA)
+        a.f32 ? launch_postproc_area<float>(a, max_ow, max_oh, st) : launch_postproc_area<_Float16>(a, max_ow, max_oh, st);
         return;
     }
     if (a.box > 1)

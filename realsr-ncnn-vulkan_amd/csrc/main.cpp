@@ -192,17 +192,26 @@ int main(int argc, char** argv)
         return -1;
     }
     // RSR_OUT_SCALE=1|2|4 (no flag of the reference's surface is taken for it; -s stays the MODEL's scale): the size of the output
-    // image relative to the input -- the x4 result box-reduced on the device (rsr_set_option "out_scale")
-    int out_scale = 4;
+    // image relative to the input -- the x4 result box-reduced on the device (rsr_set_option "out_scale") --, or n/d (3/2, 4/3, 9/4,
+    // 3/1 ...: rsr_set_out_ratio, area-averaged on the device).  A single number other than 1, 2 and 4 stays refused: x3 is written 3/1.
+    int out_scale = 4, out_num = 4, out_den = 1;
     if (const char* oe = getenv("RSR_OUT_SCALE"))
     {
         const std::string v(oe);
-        if (v != "1" && v != "2" && v != "4")
+        int n = 0, d = 0, ow = 0, oh = 0;
+        char tail = 0;
+        if (v == "1" || v == "2" || v == "4") out_num = out_scale = v[0] - '0';
+        else if (v.find('/') != std::string::npos && v.find_first_not_of("0123456789/") == std::string::npos && sscanf(oe, "%d/%d%c", &n, &d, &tail) == 2 &&
+                 rsr_out_size(n, d, 12, 12, 12, &ow, &oh) == RSR_OK) // (12: every permitted d divides it, so the ratio alone is judged)
         {
-            fprintf(stderr, "invalid RSR_OUT_SCALE '%s' (1, 2 or 4)\n", oe);
+            out_num = n, out_den = d;
+            out_scale = (n == 4 * d || n == 2 * d || n == d) ? n / d : 0; // 4/1, 2/1, 1/1 are the box scales; 0 = another ratio
+        }
+        else
+        {
+            fprintf(stderr, "invalid RSR_OUT_SCALE '%s' (1, 2 or 4, or n/d with d in 1..4 and 1 <= n/d <= 4)\n", oe);
             return -1;
         }
-        out_scale = v[0] - '0';
     }
     if (gpuid.empty()) gpuid.push_back(0);
     const int ngpu = int(gpuid.size());
@@ -340,8 +349,10 @@ int main(int argc, char** argv)
         r->scale = scale;
         r->tilesize = tilesize[size_t(i)];
         r->prepadding = prepadding;
-        r->out_scale = out_scale;
-        if (verbose) fprintf(stderr, "gpu %d: output scale %d%s\n", gpuid[size_t(i)], out_scale, out_scale == 4 ? "" : " (RSR_OUT_SCALE: the x4 result box-reduced)");
+        r->out_scale = out_scale ? out_scale : 4;
+        if (!out_scale) r->out_num = out_num, r->out_den = out_den;
+        if (verbose && out_scale) fprintf(stderr, "gpu %d: output scale %d%s\n", gpuid[size_t(i)], out_scale, out_scale == 4 ? "" : " (RSR_OUT_SCALE: the x4 result box-reduced)");
+        if (verbose && !out_scale) fprintf(stderr, "gpu %d: output scale %d/%d (RSR_OUT_SCALE: the x4 result area-averaged)\n", gpuid[size_t(i)], out_num, out_den);
         // the reference prints one line per tile, "%.2f%%" of (yi * xtiles + xi) / (ytiles * xtiles) (realsr.cpp:481): the same lines
         // here, one per tile of every batch (a batch of tiles runs at once, so they arrive in bursts)
         rsr_set_progress_callback(ctxs[size_t(i)], [](int done, int total, void*) { fprintf(stderr, "%.2f%%\n", total ? 100.f * float(done - 1) / float(total) : 0.f); }, nullptr);
@@ -440,7 +451,8 @@ int main(int argc, char** argv)
                     fprintf(stderr, "image %s has alpha channel ! %s will output %s\n", v->inpath.c_str(), v->inpath.c_str(), out2.c_str());
                     v->outpath = out2;
                 }
-                v->outimage.create(v->inimage.w * out_scale, v->inimage.h * out_scale, v->inimage.elempack, true);
+                // (a size the ratio does not divide is refused by RealSR::process, which sizes the image through rsr_out_size)
+                v->outimage.create(std::max(1, v->inimage.w * out_num / out_den), std::max(1, v->inimage.h * out_num / out_den), v->inimage.elempack, true);
                 toproc.put(std::move(v));
             }
         });

@@ -73,13 +73,13 @@ private:
 class RealSR
 {
 public:
-    RealSR(int gpuid, bool tta_mode = false, int num_threads = 1) : scale(4), tilesize(200), prepadding(10), out_scale(4), ctx(nullptr)
+    RealSR(int gpuid, bool tta_mode = false, int num_threads = 1) : scale(4), tilesize(200), prepadding(10), out_scale(4), out_num(0), out_den(0), ctx(nullptr)
     {
         const int rc = rsr_create(&ctx, gpuid, tta_mode ? 1 : 0, num_threads);
         if (rc != RSR_OK) std::fprintf(stderr, "RealSR: %s\n", rsr_last_error(nullptr));
     }
     // adopt a context created elsewhere (rsr_create_group: the model arrives by one RCCL broadcast instead of load())
-    explicit RealSR(rsr_ctx* adopted) : scale(4), tilesize(200), prepadding(10), out_scale(4), ctx(adopted) {}
+    explicit RealSR(rsr_ctx* adopted) : scale(4), tilesize(200), prepadding(10), out_scale(4), out_num(0), out_den(0), ctx(adopted) {}
     ~RealSR() { rsr_destroy(ctx); }
     RealSR(const RealSR&) = delete;
     RealSR& operator=(const RealSR&) = delete;
@@ -106,14 +106,16 @@ public:
     {
         if (!ctx) return RSR_E_STATE;
         int rc = rsr_set_params(ctx, scale, tilesize, prepadding);
-        if (rc == RSR_OK) rc = rsr_set_option(ctx, "out_scale", out_scale);
+        int ow = 0, oh = 0;
+        if (rc == RSR_OK) rc = rsr_set_out_ratio(ctx, ratio_num(), ratio_den());
+        if (rc == RSR_OK) rc = rsr_out_size(ratio_num(), ratio_den(), tilesize, inimage.w, inimage.h, &ow, &oh);
         if (rc == RSR_OK)
         {
-            if (outimage.w != inimage.w * out_scale || outimage.h != inimage.h * out_scale || outimage.elempack != inimage.elempack)
-                outimage.create(inimage.w * out_scale, inimage.h * out_scale, inimage.elempack, true);
+            if (outimage.w != ow || outimage.h != oh || outimage.elempack != inimage.elempack)
+                outimage.create(ow, oh, inimage.elempack, true);
             rc = rsr_process(ctx, inimage.data(), inimage.w, inimage.h, inimage.elempack, outimage.data());
         }
-        if (rc != RSR_OK) std::fprintf(stderr, "RealSR::process: %s\n", rsr_last_error(ctx));
+        if (rc != RSR_OK) std::fprintf(stderr, "RealSR::process: %s\n", rsr_last_error(ctx)); // (rsr_out_size reports on the calling thread, as every call does)
         return rc;
     }
 
@@ -129,13 +131,15 @@ public:
         {
             if (!r->ctx) return RSR_E_STATE;
             if (rc == RSR_OK) rc = rsr_set_params(r->ctx, r0.scale, r0.tilesize, r0.prepadding);
-            if (rc == RSR_OK) rc = rsr_set_option(r->ctx, "out_scale", r0.out_scale);
+            if (rc == RSR_OK) rc = rsr_set_out_ratio(r->ctx, r0.ratio_num(), r0.ratio_den());
             ctxs.push_back(r->ctx);
         }
+        int ow = 0, oh = 0;
+        if (rc == RSR_OK) rc = rsr_out_size(r0.ratio_num(), r0.ratio_den(), r0.tilesize, inimage.w, inimage.h, &ow, &oh);
         if (rc == RSR_OK)
         {
-            if (outimage.w != inimage.w * r0.out_scale || outimage.h != inimage.h * r0.out_scale || outimage.elempack != inimage.elempack)
-                outimage.create(inimage.w * r0.out_scale, inimage.h * r0.out_scale, inimage.elempack, true);
+            if (outimage.w != ow || outimage.h != oh || outimage.elempack != inimage.elempack)
+                outimage.create(ow, oh, inimage.elempack, true);
             rc = rsr_process_group(ctxs.data(), int(ctxs.size()), inimage.data(), inimage.w, inimage.h, inimage.elempack, outimage.data());
         }
         if (rc != RSR_OK) std::fprintf(stderr, "RealSR::process_group: %s\n", rsr_last_error(nullptr));
@@ -150,6 +154,10 @@ public:
     // size of the output image relative to the input: 4 = `scale`, the network's own; 2 / 1 = that result box-reduced on the device
     // (rsr_set_option "out_scale"; no counterpart in the reference)
     int out_scale;
+    // ... or a ratio out_num / out_den such as 3/2, 4/3, 9/4, 3/1, area-averaged on the device (rsr_set_out_ratio); out_den 0 [default] = out_scale
+    int out_num, out_den;
+    int ratio_num() const { return out_den ? out_num : out_scale; }
+    int ratio_den() const { return out_den ? out_den : 1; }
 
 private:
     rsr_ctx* ctx;

@@ -79,16 +79,30 @@ def _packed(x, d):
     return d[1] == x.shape[2] * x.element_size() and d[2] == x.shape[1] * d[1]
 
 
+def _out_size(sr, w, h):
+    """(ow, oh) of the context's output for a w x h image: sr.out_size where the context has it (out_scale 4 / 2 / 1, or a ratio such as
+    3/2: ValueError where w, h or the tile size does not take it), else w and h times its out_scale, else times its scale."""
+    if hasattr(sr, "out_size"):
+        return sr.out_size(w, h)
+    s = getattr(sr, "out_scale", sr.scale)
+    return w * s, h * s
+
+
 def upscale(sr, x, out=None):
-    """x4 -- or, with sr.out_scale 2 / 1, that result box-reduced on the device to x2 / x1 -- of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
+    """x4 -- or, with sr.out_scale 2 / 1, that result box-reduced on the device to x2 / x1, or with sr.out_ratio 3/2, 4/3, 3 ... area-averaged to that scale -- of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
     with values in [0, 1], or uint8 (H, W, 3 | 4).  Returns a tensor of the same dtype and layout at 4x (out_scale x), enqueued on
     torch.cuda.current_stream(); a batch is ONE rsr_process_device_batch call on that stream.  A view that fits a descriptor (describe)
     is read in place; any other non-contiguous input is made contiguous first.
     out: the tensor to write (and return) instead of a new one: the result's shape, dtype and device, and itself a view that fits a
     descriptor -- a window of a larger canvas, say.  ValueError otherwise, before anything is launched.  It must not overlap x."""
     fmt, batched = _check(sr, x)
-    s = getattr(sr, "out_scale", sr.scale)  # (the context's output scale: 4 unless option "out_scale" says 2 or 1)
-    shape = tuple(x.shape[:-3]) + ((x.shape[0] * s, x.shape[1] * s, x.shape[2]) if fmt == RSR_FMT_U8_HWC else (3, x.shape[-2] * s, x.shape[-1] * s))
+    # (the context's output size: x4 unless option "out_scale" says 2 or 1, or out_ratio another scale)
+    if fmt == RSR_FMT_U8_HWC:
+        ow, oh = _out_size(sr, x.shape[1], x.shape[0])
+        shape = (oh, ow, x.shape[2])
+    else:
+        ow, oh = _out_size(sr, x.shape[-1], x.shape[-2])
+        shape = tuple(x.shape[:-3]) + (3, oh, ow)
     if out is not None:
         if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != x.dtype or out.device != x.device:
             raise ValueError("upscale: out must be a %s tensor of shape %s on %s" % (x.dtype, shape, x.device))
@@ -174,6 +188,8 @@ def upscale_yuv(sr, surface, out=None):
     y, uv = _planes(sr, surface, "surface")
     fmt, (h, w) = _YUV[y.dtype], y.shape
     s = getattr(sr, "out_scale", sr.scale)
+    if not s:  # (a ratio other than 4 / 2 / 1 is in force: sr.out_ratio)
+        raise ValueError("upscale_yuv: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (getattr(sr, "out_ratio", "in force"),))
     if out is not None:
         if isinstance(out, (tuple, list)) != pair:
             raise ValueError("upscale_yuv: out must be a %s like the input" % ("(y, uv) pair" if pair else "surface tensor"))
