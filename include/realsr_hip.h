@@ -244,6 +244,69 @@ typedef struct rsr_image
 int rsr_process_device_batch(rsr_ctx* ctx, int n, const rsr_image* in, int in_fmt, int w, int h, int c,
                              const rsr_image* out, int out_fmt, void* stream);
 
+/* ---- masked tiles and a device frame diff: run only what changed (no reference counterpart) ----------------------------------------------
+ * Decoded video repeats itself: skip blocks, letterbox bars, static backgrounds, screen recordings, held frames are bit-identical to the
+ * previous frame over large areas.  Tiles are independent (realsr.cpp:377-380,458-459,490): a tile's output rectangle is a function of its
+ * padded source rectangle and of nothing else, so where that rectangle is unchanged the bytes already in the previous output ARE the answer.
+ * rsr_diff_tiles finds the tiles whose source changed, on the device; rsr_process_device_masked runs exactly those.
+ *
+ * Host-only geometry (no GPU).  The tile grid of a w x h image is nx x ny = ceil(w / tilesize) x ceil(h / tilesize); tiles are counted
+ * row-major, tile = yi * nx + xi, as rsr_process_tiles counts them.  Either pointer may be NULL.  RSR_E_ARG for w, h or tilesize < 1 or
+ * above 2^24. */
+int rsr_tile_count(int w, int h, int tilesize, int* nx, int* ny);
+/* The SOURCE RECTANGLE of tile (yi, xi), half-open [x0, x1) x [y0, y1):
+ *            sx0 = max(xi * T - P, 0),  sx1 = min(min((xi + 1) * T, w) + P, w), and likewise in y  (T = tilesize, P = prepadding).
+ * It is the clipped image of what the preprocessing reads: padded pixel gx samples reflect101(xi * T - P + gx), and a reflected index always
+ * lands inside the clipped rectangle (an index d <= P outside an edge reflects to d inside it, within the P pixels of halo on that side or,
+ * where the tile is narrower than that, onto the clamped last pixel).  Any pointer may be NULL.  RSR_E_ARG for bad sizes (as above), a
+ * prepadding that is negative or above 2^24, or a tile outside the grid. */
+int rsr_tile_source_rect(int w, int h, int tilesize, int prepadding, int tile, int* x0, int* y0, int* x1, int* y1);
+
+/* Which tiles changed.  a and b are two device images of ONE format and geometry (fmt, w x h x c), each behind its own pointer and pitches as in
+ * rsr_process_device_batch; the grid and the rectangles are those of the context's current tilesize and prepadding.  d_mask: DEVICE memory, nx * ny
+ * bytes.  mask[t] = 1 if any COMPARED BYTE of tile t's source rectangle differs between a and b, else 0.  Every mask byte is written, 0 as
+ * well as 1: the caller does not clear the buffer.  The compared bytes, exactly:
+ *   RSR_FMT_U8_HWC                     bytes [sx0 * c, sx1 * c) of rows sy0 .. sy1 - 1.  Alpha is included.
+ *   RSR_FMT_F16_CHW / RSR_FMT_F32_CHW  the rectangle's elements in each of the three planes.  Bytes are compared, not values: -0.0 against 0.0
+ *                                      counts as changed, a NaN equals itself.  That is conservative.
+ *   RSR_FMT_NV12 / RSR_FMT_P010        the Y samples of the rectangle, and the (U, V) pairs of chroma columns
+ *                                      max((sx0 >> 1) - 1, 0) .. min(((sx1 - 1) >> 1) + 1, w / 2 - 1) inclusive, rows likewise with sy and h: the
+ *                                      decode of every siting reads one chroma sample beyond its own.  P010 compares whole 16-bit words, the low
+ *                                      6 bits included.
+ * A tile whose mask byte is 0 would get, from rsr_process_device* on b, the bytes it got from a -- in every mode and at every option that is the
+ * same for both calls.
+ *   Stream.  Asynchronous on `stream` with the contract of rsr_process_device (NULL = the context's stream, and the call waits).  One memset and
+ *            one kernel launch; no host wait inside; the kernel uses none of the context's workspace and is safe next to calls of every kind.
+ *   Errors.  RSR_E_ARG before anything is launched, as rsr_process_device_batch checks one image: unknown format, format with c, pitches,
+ *            alignment of the planar formats and P010 to their elements, an odd w or h of a YUV surface, a null pointer. */
+int rsr_diff_tiles(rsr_ctx* ctx, const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, void* stream);
+
+/* rsr_process_device_batch with n = 1, restricted to the tiles t with mask[t] != 0.  mask is a HOST array of nmask = nx * ny bytes: the grid
+ * size of every launch depends on it, so it is the caller who makes the one round trip (rsr_diff_tiles, a copy, one synchronisation), explicitly.
+ * The marked tiles walk the network and exactly their output rectangles are written: no other byte of `out` is touched.  For every written
+ * rectangle the bytes are those rsr_process_device_batch writes with n = 1 for the same image in the context's current mode -- every format
+ * pair, c 3 and 4, TTA, "precise", "bgr", "out_scale" 4 / 2 / 1 and every output ratio (with their admission checks), the YUV matrices, ranges
+ * and sitings, pitched images and windows.
+ *   No tile set:    RSR_OK, nothing is launched.
+ *   Every tile set: the call IS rsr_process_device_batch with n = 1: the same path, launches and bytes.
+ *   Batches.  The tables of the selected tiles are built per call (no plan is cached for a mask) and cut into as many tile batches as the
+ *            workspace budget requires ("max_workspace_mb", free device memory).  The slots have the capacity of the FRAME's largest tile,
+ *            whatever is selected, so plain and masked calls on one geometry share one workspace layout.  A workspace that cannot be allocated
+ *            halves the batches of this call and leaves no bound behind for later calls.
+ *   Stream.  The contract of rsr_process_device_batch: on `stream` itself when the context is idle (stat "device_direct"), else on the compute
+ *            stream ordered around `stream` by events.  The call forms its own batches and is never merged with concurrent calls.  A host wait
+ *            occurs only when all three rotating table buffers still belong to earlier masked calls in flight: the tables travel from pinned
+ *            memory with one asynchronous copy on the stream the launches go to, so no other stream is involved, blocking or not.
+ *   Progress callback: one call per selected tile.  rsr_profile.tiles counts the slots actually run.
+ *   Errors.  RSR_E_ARG before anything is launched: nmask != nx * ny, a null mask, and everything rsr_process_device_batch refuses.
+ *   Stats    "masked_calls", "masked_tiles_run", "masked_tiles_skipped" (counted once a call is enqueued, or returns with no tile set: a call that
+ *            fails counts nothing), "masked_batches" (the tile batches built for partial masks; a call
+ *            with every tile set runs the plain plan and adds none), "masked_table_us" (host time spent building and uploading those
+ *            tables, accumulated).  A masked call that launches counts in "batch_calls" too.
+ * Out of scope: n > 1, host-pointer images, groups of GPUs, the CLI, merging with concurrent calls. */
+int rsr_process_device_masked(rsr_ctx* ctx, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt,
+                              const uint8_t* mask /* HOST, nmask bytes */, int nmask, void* stream);
+
 /* Host-only: bytes from `data` to one past the last byte a w x h x c image in `fmt` with these pitches touches (0 = packed, as above: then
  * rsr_image_bytes), or RSR_E_ARG for a combination rsr_process_device_batch refuses. */
 long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch);

@@ -33,6 +33,7 @@ EXPORTS = [
     "rsr_process_device_batch", "rsr_image_span",
     "rsr_yuv_constants",
     "rsr_set_out_ratio", "rsr_out_size",
+    "rsr_tile_count", "rsr_tile_source_rect", "rsr_diff_tiles", "rsr_process_device_masked",
 ]
 
 NUM_CONVS = 351
@@ -116,6 +117,10 @@ def lib():
     L.rsr_yuv_constants.argtypes = [ip, ip, ip, C.POINTER(C.c_float), ip]
     L.rsr_set_out_ratio.argtypes = [vp, ip, ip]
     L.rsr_out_size.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_tile_count.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_tile_source_rect.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_diff_tiles.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), ip, ip, ip, ip, vp, vp]
+    L.rsr_process_device_masked.argtypes = [vp, C.POINTER(Image), ip, ip, ip, ip, C.POINTER(Image), ip, vp, ip, vp]
     L.rsr_model_pack.argtypes = [cp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_device_memory.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rsr_host_alloc.argtypes = [C.c_size_t]
@@ -377,6 +382,37 @@ class RealSR:
         self._ck(self._L.rsr_process_device_batch(self._h, len(ins), _images(ins), int(in_fmt), w, h, c, _images(outs), int(out_fmt),
                                                   C.c_void_p(int(stream)) if stream else None))
 
+    def tile_count(self, w, h):
+        """(nx, ny) of the tile grid of a w x h image at the context's tilesize (rsr_tile_count); tiles count row-major."""
+        return tile_count(w, h, self.tilesize, _L=self._L)
+
+    def tile_source_rect(self, w, h, tile):
+        """(x0, y0, x1, y1), half-open: the image pixels tile `tile` reads at the context's tilesize and prepadding (rsr_tile_source_rect)."""
+        return tile_source_rect(w, h, self.tilesize, self.prepadding, tile, _L=self._L)
+
+    def diff_tiles(self, a, b, fmt, w, h, c, d_mask, stream=None):
+        """rsr_diff_tiles: d_mask[t] (device pointer, nx * ny bytes) = 1 where the device images a and b -- an integer pointer or
+        (ptr, row_pitch, plane_pitch), as for process_device_batch -- differ inside tile t's source rectangle, else 0.  Asynchronous on
+        `stream`; None = the context's stream, synchronously."""
+        self._push_params()
+        self._ck(self._L.rsr_diff_tiles(self._h, _images([a]), _images([b]), int(fmt), w, h, c, C.c_void_p(int(d_mask)),
+                                        C.c_void_p(int(stream)) if stream else None))
+
+    def process_device_masked(self, src, in_fmt, w, h, c, dst, out_fmt, mask, stream=None):
+        """rsr_process_device_masked: process_device_batch for ONE image, restricted to the tiles t with mask[t] != 0.  mask: a HOST uint8
+        array (or bytes) of nx * ny entries, or an integer address of that many bytes with the count as (address, nmask).  Only the
+        output rectangles of those tiles are written; every tile set is the plain call, none set launches nothing."""
+        if isinstance(mask, tuple):
+            mp, nmask = C.c_void_p(int(mask[0]) or None), int(mask[1])
+        elif mask is None:
+            mp, nmask = None, 0
+        else:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+            mp, nmask = _p(mask), mask.size
+        self._push_params()
+        self._ck(self._L.rsr_process_device_masked(self._h, _images([src]), int(in_fmt), w, h, c, _images([dst]), int(out_fmt), mp, nmask,
+                                                   C.c_void_p(int(stream)) if stream else None))
+
     def _check_full_out(self, out, h, w, c):
         ow, oh = self.out_size(w, h)
         if out.shape != (oh, ow, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
@@ -558,6 +594,26 @@ def yuv_constants(matrix=709, range_=0, bits=8):
     if rc != RSR_OK:
         raise RealSRError(rc, lib().rsr_last_error(None).decode())
     return out
+
+
+def tile_count(w, h, tilesize, _L=None):
+    """rsr_tile_count (host-only): (nx, ny) = (ceil(w / tilesize), ceil(h / tilesize)); tiles are counted row-major."""
+    L = _L or lib()
+    nx, ny = C.c_int(0), C.c_int(0)
+    rc = L.rsr_tile_count(int(w), int(h), int(tilesize), C.byref(nx), C.byref(ny))
+    if rc != RSR_OK:
+        raise RealSRError(rc, L.rsr_last_error(None).decode())
+    return nx.value, ny.value
+
+
+def tile_source_rect(w, h, tilesize, prepadding, tile, _L=None):
+    """rsr_tile_source_rect (host-only): (x0, y0, x1, y1), half-open, the image pixels the padded tile reads (include/realsr_hip.h)."""
+    L = _L or lib()
+    r = [C.c_int(0) for _ in range(4)]
+    rc = L.rsr_tile_source_rect(int(w), int(h), int(tilesize), int(prepadding), int(tile), *[C.byref(v) for v in r])
+    if rc != RSR_OK:
+        raise RealSRError(rc, L.rsr_last_error(None).decode())
+    return tuple(v.value for v in r)
 
 
 def _images(entries):

@@ -197,6 +197,51 @@ int rsr_process_device_batch(rsr_ctx* ctx, int n, const rsr_image* in, int in_fm
     }
 }
 
+int rsr_process_device_masked(rsr_ctx* ctx, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, const uint8_t* mask,
+                              int nmask, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    if (!mask) return ctx->e.fail(RSR_E_ARG, "null mask");
+    try
+    {
+        return ctx->e.process_device_batch(1, in, in_fmt, w, h, c, out, out_fmt, static_cast<hipStream_t>(stream), stream == nullptr, mask, nmask);
+    }
+    catch (const std::bad_alloc&) // (the tile tables of the call) -- nothing crosses extern "C"
+    {
+        return Engine::fail(RSR_E_NOMEM, "rsr_process_device_masked: out of host memory");
+    }
+}
+
+int rsr_diff_tiles(rsr_ctx* ctx, const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    return ctx->e.diff_tiles(a, b, fmt, w, h, c, d_mask, static_cast<hipStream_t>(stream));
+}
+
+int rsr_tile_count(int w, int h, int tilesize, int* nx, int* ny)
+{
+    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
+    const int x = (w + tilesize - 1) / tilesize, y = (h + tilesize - 1) / tilesize;
+    if (nx) *nx = x;
+    if (ny) *ny = y;
+    return RSR_OK;
+}
+
+int rsr_tile_source_rect(int w, int h, int tilesize, int prepadding, int tile, int* x0, int* y0, int* x1, int* y1)
+{
+    int nx = 0, ny = 0;
+    if (const int rc = rsr_tile_count(w, h, tilesize, &nx, &ny)) return rc;
+    if (prepadding < 0 || prepadding > (1 << 24)) return Engine::fail(RSR_E_ARG, "prepadding out of range");
+    if (tile < 0 || tile >= (long long)nx * ny) return Engine::fail(RSR_E_ARG, "tile outside the grid");
+    int r[4];
+    rsr::tile_source_rect(w, h, tilesize, prepadding, tile % nx, tile / nx, r);
+    if (x0) *x0 = r[0];
+    if (y0) *y0 = r[1];
+    if (x1) *x1 = r[2];
+    if (y1) *y1 = r[3];
+    return RSR_OK;
+}
+
 long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch)
 {
     long long row = 0, plane = 0;
@@ -549,6 +594,11 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "batch_calls") *value = double(e.batch_calls);
     else if (k == "batch_images") *value = double(e.batch_images);
     else if (k == "batch_groups") *value = double(e.batch_groups);
+    else if (k == "masked_calls") *value = double(e.masked_calls);
+    else if (k == "masked_tiles_run") *value = double(e.masked_tiles_run);
+    else if (k == "masked_tiles_skipped") *value = double(e.masked_tiles_skipped);
+    else if (k == "masked_batches") *value = double(e.masked_batches);
+    else if (k == "masked_table_us") *value = e.masked_table_us;
     else if (k == "merged_batches") *value = double(e.merged_batches.load());
     else if (k == "merged_images") *value = double(e.merged_images.load());
     else if (k == "merged_widest") *value = double(e.merged_widest.load());

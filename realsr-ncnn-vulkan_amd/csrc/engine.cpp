@@ -102,6 +102,9 @@ Engine::~Engine()
     {
         if (mix_ev[k]) (void)hipEventDestroy(mix_ev[k]);
         if (mix_tab[k].p) (void)hipFree(mix_tab[k].p);
+        if (mask_ev[k]) (void)hipEventDestroy(mask_ev[k]);
+        if (mask_tab[k].p) (void)hipFree(mask_tab[k].p);
+        if (mask_stage[k]) (void)hipHostFree(mask_stage[k]);
     }
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -360,13 +363,19 @@ static size_t batch_table_bytes(const Plan::Batch& b)
     return n;
 }
 
-// upload one batch's tables behind `d`; every copy is checked
-static hipError_t upload_batch(Plan::Batch& b, char*& d, bool xcd_order = true)
+// upload one batch's tables behind `d`; every copy is checked.  stage: non-null = the tables are only laid out, behind *stage on the host,
+// as they will lie behind `d`; the caller copies the whole stage with one hipMemcpy (a masked call: several batches per call, every call)
+static hipError_t upload_batch(Plan::Batch& b, char*& d, bool xcd_order = true, char** stage = nullptr)
 {
     hipError_t err = hipSuccess;
     auto put = [&](const void* src, size_t bytes) -> void* {
         void* at = d;
-        if (bytes && err == hipSuccess) err = hipMemcpy(at, src, bytes, hipMemcpyHostToDevice);
+        if (stage)
+        {
+            if (bytes) std::memcpy(*stage, src, bytes);
+            *stage += al256(bytes);
+        }
+        else if (bytes && err == hipSuccess) err = hipMemcpy(at, src, bytes, hipMemcpyHostToDevice);
         d += al256(bytes);
         return at;
     };
@@ -467,9 +476,27 @@ int Engine::check_tile_px(long long cap_px) const
                                ((flow_flags & 1) ? " with flow_flags bit 0 (e.g. -t 1000)" : " (e.g. -t 1400)"));
 }
 
+// Memory policy (the reference bounds device memory through the tile size alone, main.cpp:761-774; here ALL tiles of an image
+// form one batch, so the batch is what must be bounded): the budget is max_workspace_mb, but never more than 90 % of what
+// the device can actually give this engine right now -- free memory + the workspace it already holds - the image buffers
+// of its lanes -- and never more than a size that has already failed to allocate (ws_clamp_bytes, enqueue_images' retry).
+// Returns the slots of cap_px LR pixels a batch may have: a whole number of tiles (x8 under TTA), at least one.
+long long Engine::budget_slots(long long cap_px, int w, int h, int c)
+{
+    const int per = tta ? 8 : 1;
+    const long long per_slot = cap_px * bytes_per_px();
+    long long budget = max_workspace_mb * 1024 * 1024;
+    {
+        const long long avail = device_avail(w, h, c);
+        if (avail >= 0) budget = std::min(budget, std::max<long long>(avail, per_slot * per));
+    }
+    if (ws_clamp_bytes >= 0) budget = std::min(budget, std::max<long long>(ws_clamp_bytes, per_slot * per));
+    const long long slots = budget / std::max<long long>(per_slot, 1);
+    return std::max<long long>(per, slots / per * per);
+}
+
 int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*& out)
 {
-    const long long kBytesPerPx = bytes_per_px();
     for (auto it = plans.begin(); it != plans.end(); ++it)
         if (it->w == w && it->h == h && it->c == c && it->T == tilesize && it->P == prepadding && it->tta == tta && it->nimg == nimg && it->precise == precise && it->ratio == out_ratio && it->ntw2 == ((flow_flags & 1) != 0) &&
             it->tile0 == tile0 && it->tile1 == tile1 && it->budget_mb == max_workspace_mb && it->trim == trim_tail && it->xcd_order == xcd_order && it->fold == fold_cols &&
@@ -494,21 +521,8 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
     int rc = check_tile_px(cap);
     if (rc != RSR_OK) return rc;
     const int per = tta ? 8 : 1;
-    const long long per_slot = cap * kBytesPerPx;
-    // Memory policy (the reference bounds device memory through the tile size alone, main.cpp:761-774; here ALL tiles of an image
-    // form one batch, so the batch is what must be bounded): the budget is max_workspace_mb, but never more than 90 % of what
-    // the device can actually give this engine right now -- free memory + the workspace it already holds - the image buffers
-    // of its lanes -- and never more than a size that has already failed to allocate (ws_clamp_bytes, enqueue_images' retry).
-    long long budget = max_workspace_mb * 1024 * 1024;
-    {
-        const long long avail = device_avail(w, h, c);
-        if (avail >= 0) budget = std::min(budget, std::max<long long>(avail, per_slot * per));
-    }
-    if (ws_clamp_bytes >= 0) budget = std::min(budget, std::max<long long>(ws_clamp_bytes, per_slot * per));
-    long long budget_slots = budget / std::max<long long>(per_slot, 1);
-    budget_slots = std::max<long long>(per, budget_slots / per * per);
     const long long total_slots = (long long)all.size() * per;
-    const int spb = int(std::min<long long>(total_slots, budget_slots));
+    const int spb = int(std::min<long long>(total_slots, budget_slots(cap, w, h, c)));
     const int tiles_per_batch = spb / per;
 
     Plan plan;
@@ -1148,6 +1162,106 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
     return RSR_OK;
 }
 
+// The tiles `sel` of the one image of io -- a masked call (include/realsr_hip.h rsr_process_device_masked) -- as tile batches built here, the way
+// enqueue_mixed builds its batch: no cached plan serves an arbitrary tile list.  Every BaseTile keeps the image's own out_x / out_y, so exactly
+// the rectangles of the selected tiles are written.  The slots get the capacity of the FRAME's largest tile, whatever is selected: the plan of
+// the plain call (get_plan, nimg == 1) lays the workspace out for that capacity too, so plain and masked calls on one geometry alternate
+// without moving a guard.  The selected tiles are cut into batches by get_plan's budget arithmetic; an allocation that fails all the same
+// halves the batch of THIS call and leaves no clamp behind (the next plain call plans as if nothing had happened: if the memory is still
+// short it finds out, and clamps, for itself).  All tables of the call go into one of three rotating device buffers, each guarded by the
+// event behind the last launch that reads it: the host waits only when the call three masked calls back is still in flight.  The tables
+// travel from a pinned image of the same rotation with one asynchronous copy on `st`.  mu held.
+int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t st)
+{
+    const int T = tilesize, P = prepadding, per = tta ? 8 : 1, w = io.w[0], h = io.h[0], c = io.c;
+    const int total = ((w + T - 1) / T) * ((h + T - 1) / T), nsel = int(sel.size());
+    std::vector<BaseTile> all;
+    long long cap = 0;
+    int mtw = 0, mth = 0;
+    image_tiles(w, h, T, P, scale, 0, total, 0, all, cap, mtw, mth);
+    int rc = check_tile_px(cap);
+    if (rc != RSR_OK) return rc;
+    int tiles_per_batch = int(std::min<long long>((long long)nsel * per, budget_slots(cap, w, h, c))) / per;
+    HIP_TRY(hipSetDevice(device));
+    while ((rc = ensure_workspace(tiles_per_batch * per, cap, st)) == RSR_E_NOMEM && tiles_per_batch > 1)
+    {
+        free_workspace(st); // partly grown buffers go back first
+        tiles_per_batch /= 2;
+    }
+    if (rc != RSR_OK) return rc;
+    const auto t_tab = std::chrono::steady_clock::now();
+    std::vector<Plan::Batch> batches;
+    size_t table_bytes = 0;
+    mtw = mth = 0; // of the selected tiles: the grids of the pre- and post-processing launches
+    for (int t0 = 0; t0 < nsel; t0 += tiles_per_batch)
+    {
+        Plan::Batch b;
+        b.tile0 = t0;
+        b.ntiles = std::min(nsel - t0, tiles_per_batch);
+        b.nslots = b.ntiles * per;
+        for (int i = 0; i < b.ntiles; i++)
+        {
+            BaseTile t = all[size_t(sel[size_t(t0 + i)])];
+            t.slot0 = i * per;
+            b.tiles.push_back(t);
+            for (int k = 0; k < per; k++) b.dims.push_back(k < 4 ? TileDim{t.th, t.tw} : TileDim{t.tw, t.th}); // realsr.cpp:251-258
+            mtw = std::max(mtw, t.tw), mth = std::max(mth, t.th);
+        }
+        b.trim4 = trim_tail ? P * scale : 0;
+        make_items(b, fold_cols, tta ? -1 : P * scale, b.trim4, 0);
+        table_bytes += batch_table_bytes(b);
+        batches.push_back(std::move(b));
+    }
+    const int k = int(mask_seq++ % 3);
+    if (mask_ev[k]) HIP_TRY(hipEventSynchronize(mask_ev[k])); // the call that read this buffer last has finished
+    if ((rc = ensure(mask_tab[k], table_bytes)) != RSR_OK) return rc;
+    if (mask_stage_bytes[k] < table_bytes)
+    { // (the copy that read the old image has finished: the event above)
+        if (mask_stage[k]) (void)hipHostFree(mask_stage[k]);
+        mask_stage[k] = nullptr, mask_stage_bytes[k] = 0;
+        if (hipHostMalloc(&mask_stage[k], table_bytes, hipHostMallocDefault) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            mask_stage[k] = nullptr;
+            return fail(RSR_E_NOMEM, "hipHostMalloc(" + std::to_string(table_bytes) + ") for the tile tables failed");
+        }
+        mask_stage_bytes[k] = table_bytes;
+    }
+    char *d = static_cast<char*>(mask_tab[k].p), *hs = static_cast<char*>(mask_stage[k]);
+    for (Plan::Batch& b : batches) (void)upload_batch(b, d, xcd_order, &hs);
+    // on the call's own stream, in front of its launches: no other stream is involved, whatever kind the caller's is
+    HIP_TRY(hipMemcpyAsync(mask_tab[k].p, mask_stage[k], table_bytes, hipMemcpyHostToDevice, st));
+    masked_table_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_tab).count();
+    mark_begin(st);
+    io.out_row0 = 0;
+    io.split_slot = 0;
+    io.ev_mid = nullptr;
+    int done = 0;
+    long long slots = 0;
+    for (const Plan::Batch& b : batches)
+    {
+        rc = launch_batch(b, cap, mtw, mth, b.ntiles, st, io);
+        if (rc != RSR_OK) break;
+        if (progress)
+            for (int i = 1; i <= b.ntiles; i++) progress(done + i, nsel, progress_user);
+        done += b.ntiles;
+        slots += b.nslots;
+        masked_batches++;
+    }
+    // (also behind a batch that failed to launch: the copy and the batches in front of it read the buffers)
+    if (!mask_ev[k] && hipEventCreateWithFlags(&mask_ev[k], hipEventDisableTiming) != hipSuccess) mask_ev[k] = nullptr;
+    if (!mask_ev[k] || hipEventRecord(mask_ev[k], st) != hipSuccess) (void)hipStreamSynchronize(st);
+    if (rc != RSR_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    if (profiling)
+    {
+        collect_profile(st);
+        prof.calls++;
+        prof.tiles += slots;
+    }
+    return RSR_OK;
+}
+
 int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync, int in_fmt, int out_fmt)
 {
     if (!d_in || !d_out || w < 1 || h < 1 || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
@@ -1337,10 +1451,12 @@ int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long pl
 }
 
 int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream,
-                                 bool sync)
+                                 bool sync, const uint8_t* mask, int nmask)
 {
     // everything is checked before anything is launched
-    if (n < 1 || !in || !out) return fail(RSR_E_ARG, "bad image arguments");
+    if (n < 1 || !in || !out || (mask && n != 1)) return fail(RSR_E_ARG, "bad image arguments");
+    std::vector<int> sel; // a masked call: the tiles to run
+    bool masked = false;  // ... and that it is one (mask is dropped where every tile is set)
     long long irow = 0, iplane = 0, orow = 0, oplane = 0;
     std::vector<long long> lay(size_t(n) * 4);
     OutRatio os; // the output windows are checked against the output ratio in force now; should it change before the launch: RSR_E_STATE
@@ -1371,6 +1487,21 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
         if (out_ratio != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
         if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
         if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
+        if (mask)
+        {
+            const int ntiles = ((w + tilesize - 1) / tilesize) * ((h + tilesize - 1) / tilesize);
+            if (nmask != ntiles) return fail(RSR_E_ARG, "the mask has " + std::to_string(nmask) + " bytes, the tile grid " + std::to_string(ntiles) + " tiles");
+            for (int t = 0; t < ntiles; t++)
+                if (mask[t]) sel.push_back(t);
+            if (sel.empty())
+            { // nothing changed: nothing is launched
+                masked_calls++;
+                masked_tiles_skipped += ntiles;
+                return RSR_OK;
+            }
+            masked = true;
+            if (int(sel.size()) == ntiles) mask = nullptr; // every tile: the plain call, on its cached plan
+        }
         HIP_TRY(hipSetDevice(device));
         // As in process_device: an idle engine runs the call on the caller's own stream, a busy one on the compute stream between two events.
         const bool direct = user_stream && hipStreamQuery(stream) == hipSuccess;
@@ -1400,8 +1531,14 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
                 io.in_pitch[i] = l[0], io.in_plane[i] = l[1], io.out_pitch[i] = l[2], io.out_plane[i] = l[3];
             }
             // (n == 1: plan_nimg 0, the very call process_device makes; otherwise the progress of all n images is reported here)
-            rc = enqueue_images(io, 0, -1, n == 1 ? 0 : width, nullptr, st);
+            rc = mask ? enqueue_masked(io, sel, st) : enqueue_images(io, 0, -1, n == 1 ? 0 : width, nullptr, st);
             if (rc != RSR_OK) break;
+            if (masked)
+            { // counted once the call is enqueued: a call that fails has run nothing
+                masked_calls++;
+                masked_tiles_run += (long long)sel.size();
+                masked_tiles_skipped += tiles_per_image - (long long)sel.size();
+            }
             enqueued += k;
             batch_groups++;
             if (progress && n > 1)
@@ -1443,6 +1580,34 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
         if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
     }
     return rc;
+}
+
+// ---- which tiles changed (include/realsr_hip.h rsr_diff_tiles) ---------------------------------------------------------------------------
+// One memset and one launch on the caller's stream: the kernel touches neither the workspace nor anything of the calls in flight, so it needs
+// no ordering against the compute stream.  A null stream: the context's own, and the call waits.
+int Engine::diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, hipStream_t user_stream)
+{
+    if (!a || !b || !a->data || !b->data || !d_mask) return fail(RSR_E_ARG, "bad image arguments");
+    DiffArgs da;
+    std::memset(&da, 0, sizeof da);
+    int rc = image_layout(fmt, w, h, c, a->row_pitch, a->plane_pitch, &da.pitch_a, &da.plane_a);
+    if (rc == RSR_OK) rc = image_layout(fmt, w, h, c, b->row_pitch, b->plane_pitch, &da.pitch_b, &da.plane_b);
+    if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
+    if (rc != RSR_OK) return rc;
+    const uintptr_t es = uintptr_t(fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(fmt, c));
+    if (reinterpret_cast<uintptr_t>(a->data) % es || reinterpret_cast<uintptr_t>(b->data) % es) return fail(RSR_E_ARG, "data is not aligned to the element size");
+    da.a = static_cast<const uint8_t*>(a->data), da.b = static_cast<const uint8_t*>(b->data);
+    da.fmt = fmt, da.w = w, da.h = h, da.c = c;
+    da.mask = d_mask;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        da.T = tilesize, da.P = prepadding;
+        da.nx = (w + da.T - 1) / da.T, da.ny = (h + da.T - 1) / da.T;
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_diff_tiles(da, user_stream ? user_stream : stream));
+    }
+    if (!user_stream) HIP_TRY(hipStreamSynchronize(stream));
+    return RSR_OK;
 }
 
 // ---- merging small images across calls (engine.h) ---------------------------------------------

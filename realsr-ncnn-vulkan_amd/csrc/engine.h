@@ -303,6 +303,14 @@ struct Engine
     hipEvent_t mix_ev[3] = {nullptr, nullptr, nullptr};
     unsigned long long mix_seq = 0;
     std::atomic<long long> merged_mixed{0}; // stat: merged batches whose images differed in size
+    // masked calls (rsr_process_device_masked): the tables of the selected tiles, built per call, in rotating device buffers of their own
+    DevBuf mask_tab[3];
+    hipEvent_t mask_ev[3] = {nullptr, nullptr, nullptr}; // recorded behind the last launch that reads mask_tab[k]
+    unsigned long long mask_seq = 0;
+    void* mask_stage[3] = {nullptr, nullptr, nullptr}; // ... and their pinned host images: the tables of a call are laid out here and go to the
+    size_t mask_stage_bytes[3] = {0, 0, 0};            // device with ONE asynchronous copy on the call's stream (same event guard)
+    long long masked_calls = 0, masked_tiles_run = 0, masked_tiles_skipped = 0, masked_batches = 0; // stats, under mu
+    double masked_table_us = 0; // stat: host time spent building and uploading those tables
     long long image_items(int w, int h, long long limit) const;
     int merge_width(int w, int h, int c) const; // images of this geometry one batch may take (1: not a small image / merging off)
     int submit_merged(MergeReq& r);             // returns when r's batch has been ENQUEUED (r.ev_done recorded) or failed
@@ -339,7 +347,12 @@ struct Engine
                        int out_fmt = RSR_FMT_U8_HWC);
     // n images of one geometry, each behind its own descriptor (pointer, row pitch, plane pitch), in groups of merge_width(w, h, c) images:
     // every group ONE tile batch on the cached merged plan (include/realsr_hip.h rsr_process_device_batch).  Stream contract of process_device.
-    int process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream, bool sync);
+    // mask (n == 1 only; include/realsr_hip.h rsr_process_device_masked): nmask bytes, one per tile of the row-major grid; only the tiles with
+    // a non-zero byte run (enqueue_masked).  No tile set: nothing is launched; every tile set: the call without a mask.
+    int process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream, bool sync,
+                             const uint8_t* mask = nullptr, int nmask = 0);
+    // mask[t] = do the images a and b differ inside tile t's source rectangle (include/realsr_hip.h rsr_diff_tiles); d_mask: device, one byte per tile
+    int diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, hipStream_t user_stream);
     // tile0/tile1: tiles [tile0, tile1) of the row-major tile grid only (tile1 < 0: all); `out` is always the full (w * out_scale x h * out_scale x c) image,
     // only the output rectangles of
     // those tiles are written
@@ -356,6 +369,7 @@ struct Engine
     int ensure(DevBuf& b, size_t bytes);
     int ensure_planes(DevBuf& b, size_t bytes, long long plane_bytes, bool layout_changed, bool zero_all, hipStream_t st);
     int get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*& out);
+    long long budget_slots(long long cap_px, int w, int h, int c); // slots of cap_px LR pixels one tile batch may have: the memory policy of get_plan and enqueue_masked
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
@@ -371,6 +385,7 @@ struct Engine
     int run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, const BatchIO* io, const RangeProbe* probe);
     int launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io);
     int enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid); // a merged batch of images of different sizes: tables built on the fly
+    int enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t st);     // the tiles `sel` (ascending) of the ONE image of io: tables built on the fly
     int launch(const ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st);
     // The images of io -- all of io.w[0] x io.h[0] -- as ONE tile batch per workspace-full: tiles [tile0, tile1) of the tile grid
     // (tile1 < 0: all; whole images only when io.nimg > 1).  io.ev_half with half_rows: the engine may split the 4x tail and reports

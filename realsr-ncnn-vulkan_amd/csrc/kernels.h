@@ -229,6 +229,31 @@ struct PostArgs
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 
+// ---- frame diff per tile (rsr_diff_tiles) -----------------------------------------------------
+// The SOURCE RECTANGLE of tile (yi, xi) of a w x h image at tile size T and prepadding P: the image pixels its padded tile reads, i.e. the
+// padded rectangle clipped to the image (reflect-101 never leaves it: the reflection of an index less than P outside an edge lies less
+// than P + 1 inside it).  Half-open, r = {x0, y0, x1, y1}.
+__host__ __device__ inline void tile_source_rect(int w, int h, int T, int P, int xi, int yi, int r[4])
+{
+    const int ex = (xi + 1) * T < w ? (xi + 1) * T : w, ey = (yi + 1) * T < h ? (yi + 1) * T : h;
+    r[0] = xi * T - P > 0 ? xi * T - P : 0;
+    r[1] = yi * T - P > 0 ? yi * T - P : 0;
+    r[2] = ex + P < w ? ex + P : w;
+    r[3] = ey + P < h ? ey + P : h;
+}
+// mask[t] = 1 when any compared byte of tile t's source rectangle differs between the images a and b (one format and geometry, their own
+// pitches), else 0; include/realsr_hip.h rsr_diff_tiles says which bytes are compared.
+struct DiffArgs
+{
+    const uint8_t* a;
+    const uint8_t* b;
+    long long pitch_a, plane_a, pitch_b, plane_b; // bytes, resolved (plane: planar formats plane to plane; NV12 / P010: Y(0,0) to the UV plane)
+    int fmt, w, h, c;
+    int T, P, nx, ny; // tile size, prepadding, tile grid
+    uint8_t* mask;    // [ny * nx]
+};
+hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st); // the error of the memset or of the launch
+
 // shader-shaped standalone kernels (parity tests): device pointers
 void launch_preproc_shader(const uint8_t* bottom, int w, int h, int channels, uint16_t* const top[8], int ntop, int outw,
                            int outh, int outcstep, int pad_top, int pad_left, int crop_x, int crop_y, uint16_t* alpha,

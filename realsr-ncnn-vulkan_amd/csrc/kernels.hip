@@ -1305,6 +1305,101 @@ void launch_zero_guards(void* first_guard, long long stride, long long count, hi
 }
 
 // =============================================================================================
+// frame diff per tile (rsr_diff_tiles): which tiles' source rectangles differ between two frames
+// =============================================================================================
+constexpr int kDiffRows = 16; // rows of a rectangle per workgroup and step: 4 per wave, so that a 220-row tile spreads over 14 workgroups
+
+__device__ __forceinline__ bool differ(uint4 x, uint4 y) { return ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) != 0; }
+__device__ __forceinline__ bool differ(uint32_t x, uint32_t y) { return x != y; }
+__device__ __forceinline__ bool differ(uint8_t x, uint8_t y) { return x != y; }
+
+// Do the n bytes behind pa and pb differ?  One wave, lanes along the row.  TV is the widest access both rows allow: their addresses agree
+// modulo sizeof(TV), so one head of 0 .. 15 bytes brings both to that boundary.  Head and tail are compared byte by byte (lanes 0 .. 15 and
+// 16 .. 31), the body in aligned pieces, 64 per step (a 220-pixel row of fp32 is 55 pieces of 16 bytes; a wider one loops).  No byte
+// outside [pa, pa + n) and [pb, pb + n) is read: a crop's neighbours may belong to someone else.
+template <typename TV>
+__device__ __forceinline__ bool row_differs(const uint8_t* pa, const uint8_t* pb, int n, int lane)
+{
+    constexpr int V = int(sizeof(TV));
+    const int head = min(n, int((0 - reinterpret_cast<uintptr_t>(pa)) & uintptr_t(V - 1)));
+    const int nvec = (n - head) / V, tail = n - head - nvec * V;
+    bool d = false;
+    if (V > 1)
+    {
+        int e = -1;
+        if (lane < 16) e = lane < head ? lane : -1;
+        else if (lane < 32) e = lane - 16 < tail ? n - tail + lane - 16 : -1;
+        if (e >= 0) d = pa[e] != pb[e];
+    }
+    const TV* const va = reinterpret_cast<const TV*>(pa + head);
+    const TV* const vb = reinterpret_cast<const TV*>(pb + head);
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = lane; i < nvec; i += 64) d |= differ(va[i], vb[i]);
+    return d;
+}
+
+// A wave's rows of a rectangle: y = ys, ys + 4, ... inside every chunk of kDiffRows rows, the chunks `step` rows apart.
+template <typename TV>
+__device__ __forceinline__ bool rows_differ(const uint8_t* pa, long long pitch_a, const uint8_t* pb, long long pitch_b, int n, int ys, int y1, int step, int lane)
+{
+    bool d = false;
+#pragma unroll 1
+    for (; ys < y1; ys += step)
+#pragma unroll 1
+        for (int y = ys; y < min(ys + kDiffRows, y1); y += 4) d |= row_differs<TV>(pa + (long long)y * pitch_a, pb + (long long)y * pitch_b, n, lane);
+    return d;
+}
+
+// grid (tile, row chunk, rectangle): the compared bytes of a tile are 1 (uint8 HWC), 3 (the planes of a planar image) or 2 (Y, UV) byte
+// rectangles.  A workgroup that finds a difference stores the 1; the launch function zeroes the mask in front of the kernel.
+__global__ __launch_bounds__(256) void diff_tiles(const DiffArgs a)
+{
+    const int tile = blockIdx.x, yi = tile / a.nx, xi = tile - yi * a.nx;
+    int r[4];
+    tile_source_rect(a.w, a.h, a.T, a.P, xi, yi, r);
+    const int rect = blockIdx.z;
+    const int es = a.fmt == kFmtF32 ? 4 : ((a.fmt == kFmtF16 || a.fmt == kFmtP010) ? 2 : (a.fmt == kFmtU8 ? a.c : 1));
+    int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
+    long long off_a = 0, off_b = 0;
+    if (fmt_is_yuv(a.fmt))
+    {
+        if (rect == 1)
+        { // the (U, V) pairs the decode of this rectangle reads: one chroma sample beyond its own, at every siting
+            const int cx0 = max((r[0] >> 1) - 1, 0), cx1 = min(((r[2] - 1) >> 1) + 1, a.w / 2 - 1);
+            bx0 = cx0 * 2 * es, bx1 = (cx1 + 1) * 2 * es;
+            y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1;
+            off_a = a.plane_a, off_b = a.plane_b;
+        }
+    }
+    else if (a.fmt != kFmtU8) off_a = rect * a.plane_a, off_b = rect * a.plane_b;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint8_t* const pa = a.a + off_a + bx0;
+    const uint8_t* const pb = a.b + off_b + bx0;
+    // the widest access EVERY row of the rectangle allows: both images' rows then reach its boundary after the same head
+    const unsigned mis = unsigned(reinterpret_cast<uintptr_t>(pa) ^ reinterpret_cast<uintptr_t>(pb)) | unsigned(a.pitch_a ^ a.pitch_b);
+    const int n = bx1 - bx0, ys = y0 + blockIdx.y * kDiffRows + wave, step = gridDim.y * kDiffRows;
+    bool d;
+    if (!(mis & 15)) d = rows_differ<uint4>(pa, a.pitch_a, pb, a.pitch_b, n, ys, y1, step, lane);
+    else if (!(mis & 3)) d = rows_differ<uint32_t>(pa, a.pitch_a, pb, a.pitch_b, n, ys, y1, step, lane);
+    else d = rows_differ<uint8_t>(pa, a.pitch_a, pb, a.pitch_b, n, ys, y1, step, lane);
+    if (__any(d) && lane == 0) a.mask[tile] = 1;
+}
+
+hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st)
+{
+    const int ntiles = a.nx * a.ny;
+    if (ntiles <= 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(a.mask, 0, size_t(ntiles), st); // every byte is written: the kernel only ever stores ones
+    if (e != hipSuccess) return e;
+    const long long padded = (long long)a.T + 2 * a.P; // rows of the tallest rectangle
+    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_yuv(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
+    const int chunks = (rows + kDiffRows - 1) / kDiffRows;
+    const dim3 grid(ntiles, chunks < 1024 ? chunks : 1024, nrect), block(256); // (taller rectangles: the kernel strides over the chunks)
+    hipLaunchKernelGGL(diff_tiles, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+// =============================================================================================
 // model self-check: range probe and output compare (Engine::selfcheck)
 // =============================================================================================
 constexpr int kCheckBlocks = 512; // grid-stride: at most this many workgroups of 256

@@ -7,12 +7,17 @@
 
     nv12 = torch_io.upscale_yuv(sr, surface)   # a decoder's (3H/2, W) uint8 NV12 or 16-bit P010 surface -> the same layout at out_scale
 
+    y, n = torch_io.upscale_delta(sr, frame, prev_frame, y)   # video: only the tiles whose source changed run again, y is updated in place
+
 The float tensors go through rsr_process_device_fmt / rsr_process_device_batch as they are (planar fp16 / fp32, include/realsr_hip.h): no
 quantisation to uint8 on either side, no permute, no extra pass over the frame.  An (N, 3, H, W) batch is ONE call: small images share
 tile batches.  A view whose rows are contiguous (a crop, a slice of a batch, a frame inside a padded surface) is passed by pointer and
 pitches (describe()); anything else is made contiguous first.  The work is enqueued on torch.cuda.current_stream() and nothing here
 waits for the GPU: the result is ordered on that stream like the output of any torch op.
 """
+import contextlib
+
+import numpy as np
 import torch
 
 from . import RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_P010, RSR_FMT_U8_HWC
@@ -210,6 +215,111 @@ def upscale_yuv(sr, surface, out=None):
         din = _describe_yuv(packed[:h], packed[h:])
     _on_current_stream(y.device, lambda st: sr.process_device_batch([din], fmt, w, h, 3, [dout], fmt, stream=st))
     return out
+
+
+# ---- video: run only the tiles that changed -----------------------------------------------------------------------------------------------
+def _pinned_u8(n):
+    """n bytes of pinned host memory as a uint8 tensor (the mask's landing place: a copy into it can be asynchronous)."""
+    return torch.empty(n, dtype=torch.uint8, pin_memory=True)
+
+
+def _image_desc(sr, t, what):
+    """(fmt, w, h, c, descriptor or None) of ONE image as upscale (a single uint8 / float image) or upscale_yuv (a surface or a (y, uv)
+    pair) takes it; ValueError before anything is launched."""
+    if isinstance(t, (tuple, list)) or (isinstance(t, torch.Tensor) and t.dim() == 2):
+        y, uv = _planes(sr, t, what)
+        return _YUV[y.dtype], y.shape[1], y.shape[0], 3, _describe_yuv(y, uv)
+    fmt, batched = _check(sr, t)
+    if batched:
+        raise ValueError("upscale_delta: %s must be ONE image, not a batch %s" % (what, tuple(t.shape)))
+    h, w, c = t.shape if fmt == RSR_FMT_U8_HWC else (t.shape[1], t.shape[2], 3)
+    return fmt, w, h, c, describe(t)
+
+
+def _desc_or_packed(sr, t, what):
+    """(descriptor, keep) of the image t: its own where one fits (_image_desc), else that of a packed copy `keep` (kept alive by the
+    stream ordering, like any temporary of a torch op)."""
+    d = _image_desc(sr, t, what)[4]
+    if d is not None:
+        return d, None
+    if isinstance(t, torch.Tensor) and t.dim() == 3:
+        keep = t.contiguous()
+        return describe(keep), keep
+    y, uv = _planes(sr, t, what)
+    keep = torch.cat([y, uv], dim=0)
+    return _describe_yuv(keep[:y.shape[0]], keep[y.shape[0]:]), keep
+
+
+def _same_layout(a, b):
+    """Do two images (tensors or (y, uv) pairs) agree in kind, shape, dtype and device?"""
+    if isinstance(a, (tuple, list)) != isinstance(b, (tuple, list)):
+        return False
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same_layout(p, q) for p, q in zip(a, b))
+    return isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.shape == b.shape and a.dtype == b.dtype and a.device == b.device
+
+
+def upscale_delta(sr, x, prev_x, prev_y, out=None):
+    """upscale() / upscale_yuv() of the video frame x, given the previous frame prev_x and its result prev_y: only the tiles whose SOURCE
+    RECTANGLE differs between prev_x and x walk the network (rsr_diff_tiles + rsr_process_device_masked, include/realsr_hip.h); every
+    other tile's output rectangle is a function of bytes that did not change, so what prev_y holds there is the answer, bit for bit.
+    x and prev_x: one layout and dtype -- anything upscale takes for a SINGLE image (uint8 (H, W, 3 | 4), float (3, H, W)) or a surface
+    as upscale_yuv takes it ((3H / 2, W) tensor or (y, uv) pair); views go through the same descriptors (describe).  prev_y: the result
+    for prev_x, in the layout upscale / upscale_yuv returns, computed at the context's CURRENT options.
+    out: None = prev_y is updated in place and returned; another tensor (or pair) of prev_y's layout first receives prev_y through copy_.
+    Returns (out, tiles_run).  prev_x=None: every tile runs (the first frame, a scene cut) and prev_y only provides the memory.
+    Steps, all on torch.cuda.current_stream(): the diff; a copy of the mask into pinned memory; ONE stream synchronisation -- the grid of
+    every launch depends on the mask, so the host has to see it: this is the only host wait, and it is what the skipped tiles are paid
+    with --; the masked call."""
+    fmt, w, h, c, _ = _image_desc(sr, x, "x")
+    if prev_x is not None and not _same_layout(x, prev_x):
+        raise ValueError("upscale_delta: prev_x must have x's layout, shape, dtype and device")
+    yuv = fmt in (RSR_FMT_NV12, RSR_FMT_P010)
+    if yuv:
+        s = getattr(sr, "out_scale", sr.scale)
+        if not s:
+            raise ValueError("upscale_delta: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (getattr(sr, "out_ratio", "in force"),))
+        ow, oh = w * s, h * s
+    else:
+        ow, oh = _out_size(sr, w, h)
+    for t, what in ((prev_y, "prev_y"),) + (((out, "out"),) if out is not None else ()):
+        if isinstance(t, (tuple, list)) != isinstance(x, (tuple, list)):
+            raise ValueError("upscale_delta: %s must be a %s like x" % (what, "(y, uv) pair" if isinstance(x, (tuple, list)) else "tensor"))
+        f2, w2, h2, c2, d2 = _image_desc(sr, t, what)
+        if (f2, w2, h2, c2) != (fmt, ow, oh, c):
+            raise ValueError("upscale_delta: %s must hold the %d x %d result for x (%d x %d) in x's format" % (what, ow, oh, w, h))
+        if d2 is None:
+            raise ValueError("upscale_delta: %s is not addressable by row and plane pitch" % what)
+    if out is None:
+        out = prev_y
+    else:
+        for dst, src in (zip(out, prev_y) if isinstance(out, (tuple, list)) else ((out, prev_y),)):
+            dst.copy_(src)
+    dout = _image_desc(sr, out, "out")[4]
+    first = x[0] if isinstance(x, (tuple, list)) else x
+    # A view no descriptor fits is packed first -- BOTH frames here, in front of the wait below: the packing runs on torch's current
+    # stream, and the side stream (where the diff reads the copies) is ordered behind that stream only up to the wait.
+    dx, keep_x = _desc_or_packed(sr, x, "x")
+    dp, keep_p = _desc_or_packed(sr, prev_x, "prev_x") if prev_x is not None else (None, None)
+    nx, ny = sr.tile_count(w, h)
+    cur = torch.cuda.current_stream(first.device)
+    st = cur if cur.cuda_stream != 0 else _side_stream(first.device)  # (the null stream means "synchronously" to the C calls: see upscale)
+    if st is not cur:
+        st.wait_stream(cur)
+    if prev_x is None:
+        mask = np.ones(nx * ny, dtype=np.uint8)
+    else:
+        d_mask = first.new_empty(nx * ny, dtype=torch.uint8)
+        host = _pinned_u8(nx * ny)
+        with (torch.cuda.stream(st) if st is not cur else contextlib.nullcontext()):  # (the copy below goes where torch's current stream is)
+            sr.diff_tiles(dp, dx, fmt, w, h, c, d_mask.data_ptr(), stream=st.cuda_stream)
+            host.copy_(d_mask, non_blocking=True)
+        st.synchronize()  # the ONE host wait
+        mask = host.numpy()
+    sr.process_device_masked(dx, fmt, w, h, c, dout, fmt, mask, stream=st.cuda_stream)
+    if st is not cur:
+        cur.wait_stream(st)
+    return out, int(np.count_nonzero(mask))
 
 
 _side = {}

@@ -1,0 +1,78 @@
+"""numpy restatement of the tile geometry and of rsr_diff_tiles (include/realsr_hip.h "masked tiles and a device frame diff"): the tile
+grid, a tile's source rectangle, and, for every pixel format, the mask of tiles whose compared bytes differ between two frames.  Plain
+loops over tiles; nothing here shares code with the library."""
+import numpy as np
+
+U8, F16, F32, NV12, P010 = 0, 1, 2, 4, 5
+NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16}
+
+
+def tile_count(w, h, T):
+    return -(-w // T), -(-h // T)
+
+
+def source_rect(w, h, T, P, tile):
+    """(x0, y0, x1, y1), half-open: the padded rectangle of tile `tile` (row-major) clipped to the image."""
+    nx, ny = tile_count(w, h, T)
+    assert 0 <= tile < nx * ny
+    yi, xi = divmod(tile, nx)
+    return (max(xi * T - P, 0), max(yi * T - P, 0), min(min((xi + 1) * T, w) + P, w), min(min((yi + 1) * T, h) + P, h))
+
+
+def reflect101(v, n):
+    """The index the preprocessing reads for position v of an axis of n pixels: one reflection about either edge, then the clamp for
+    images narrower than the halo (oracle/realsr_oracle.c reflect_pad, kernels.hip reflect101)."""
+    v = np.abs(np.asarray(v))
+    v = np.where(v > n - 1, (n - 1) - (v - (n - 1)), v)
+    return np.clip(v, 0, n - 1)
+
+
+def sampled(w, h, T, P, tile):
+    """The sets of image columns and rows the padded tile samples."""
+    nx, _ = tile_count(w, h, T)
+    yi, xi = divmod(tile, nx)
+    tw, th = min((xi + 1) * T, w) - xi * T + 2 * P, min((yi + 1) * T, h) - yi * T + 2 * P
+    return set(reflect101(xi * T - P + np.arange(tw), w).tolist()), set(reflect101(yi * T - P + np.arange(th), h).tolist())
+
+
+def chroma_span(s0, s1, n):
+    """Chroma indices [c0, c1] inclusive a luma span [s0, s1) of an axis of n luma samples compares: its own and one beyond."""
+    return max((s0 >> 1) - 1, 0), min(((s1 - 1) >> 1) + 1, n // 2 - 1)
+
+
+def compared(fmt, w, h, T, P, tile, a, b):
+    """The pairs of arrays rsr_diff_tiles compares for one tile of the frames a and b (numpy images in the library's layouts: uint8
+    (h, w, c); float (3, h, w); surfaces (3h / 2, w))."""
+    x0, y0, x1, y1 = source_rect(w, h, T, P, tile)
+    if fmt == U8:
+        return [(a[y0:y1, x0:x1, :], b[y0:y1, x0:x1, :])]
+    if fmt in (F16, F32):
+        return [(a[:, y0:y1, x0:x1], b[:, y0:y1, x0:x1])]
+    cx0, cx1 = chroma_span(x0, x1, w)
+    cy0, cy1 = chroma_span(y0, y1, h)
+    return [(a[y0:y1, x0:x1], b[y0:y1, x0:x1]), (a[h + cy0:h + cy1 + 1, 2 * cx0:2 * cx1 + 2], b[h + cy0:h + cy1 + 1, 2 * cx0:2 * cx1 + 2])]
+
+
+def diff_mask(fmt, a, b, T, P):
+    """mask[t] = 1 where any compared BYTE of tile t differs between a and b, else 0 (uint8, nx * ny)."""
+    assert a.shape == b.shape and a.dtype == b.dtype == NP[fmt]
+    if fmt == U8:
+        h, w = a.shape[:2]
+    elif fmt in (F16, F32):
+        h, w = a.shape[1:]
+    else:
+        h, w = a.shape[0] * 2 // 3, a.shape[1]
+    nx, ny = tile_count(w, h, T)
+    mask = np.zeros(nx * ny, dtype=np.uint8)
+    for t in range(nx * ny):
+        for pa, pb in compared(fmt, w, h, T, P, t, a, b):
+            if not np.array_equal(np.ascontiguousarray(pa).view(np.uint8), np.ascontiguousarray(pb).view(np.uint8)):
+                mask[t] = 1
+    return mask
+
+
+def out_rect(w, h, T, tile, num=4, den=1):
+    """(x0, y0, x1, y1) of the tile's output rectangle at output ratio num / den."""
+    nx, _ = tile_count(w, h, T)
+    yi, xi = divmod(tile, nx)
+    return (xi * T * num // den, yi * T * num // den, min((xi + 1) * T, w) * num // den, min((yi + 1) * T, h) * num // den)
