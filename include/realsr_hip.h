@@ -307,6 +307,62 @@ int rsr_diff_tiles(rsr_ctx* ctx, const rsr_image* a, const rsr_image* b, int fmt
 int rsr_process_device_masked(rsr_ctx* ctx, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt,
                               const uint8_t* mask /* HOST, nmask bytes */, int nmask, void* stream);
 
+/* ---- frame sequences: N video frames share one diff and one tile batch (no reference counterpart) -----------------------------------------
+ * A masked call pays its fixed cost -- 352 launches, one host round trip -- per frame, however few tiles changed.  A caller who knows the next
+ * N decoded frames (an offline transcode, a player's look-ahead) pays it once per window: one launch diffs every consecutive pair, one round
+ * trip brings N masks to the host, the changed tiles of all N frames walk the network as shared tile batches, and one memory-bound launch
+ * fills every output rectangle that was not computed from the frame that computed it last.
+ *
+ * Definitions.  All frames of a call have ONE format and geometry; the tile grid (nx x ny, ntiles = nx * ny, row-major) and a tile's source
+ * and output rectangles are those of the masked section above, at the context's current tilesize, prepadding and output ratio.  masks is a
+ * row-major [n][ntiles] byte array; any non-zero byte is "set".  The SOURCE of output tile t of frame k is
+ *            src[k * ntiles + t] = k                                      where masks[k][t] != 0,
+ *                                = the largest j < k with masks[j][t] != 0  otherwise,
+ *                                = -1, the previous output,                 where there is no such j.
+ * rsr_sequence_sources computes exactly this (host-only, no GPU): the one definition of where every output rectangle comes from.
+ * RSR_E_ARG for n < 1, n > RSR_SEQ_MAX, ntiles < 1, a null pointer, or a -1 that would be needed while has_prev == 0. */
+#define RSR_SEQ_MAX 16 /* frames per call: the images one tile batch can address */
+int rsr_sequence_sources(int n, int ntiles, const uint8_t* masks, int has_prev, int* src /* n * ntiles */);
+
+/* The masks of n consecutive frames.  Row k of d_masks (DEVICE memory, n * nx * ny bytes, every byte written) is what
+ * rsr_diff_tiles(frames[k - 1], frames[k]) writes: the same compared bytes, the same tile grid.  Row 0 compares prev with frames[0]; with
+ * prev == NULL it is all ones (a first frame, a scene cut).
+ *   Stream.  The contract of rsr_diff_tiles.  One memset and ONE kernel launch for all pairs; no host wait inside.
+ *   Errors.  RSR_E_ARG before anything is launched: n outside 1 .. RSR_SEQ_MAX, a null pointer (frames, d_masks, any data), and for every
+ *            descriptor what rsr_diff_tiles refuses. */
+int rsr_diff_tiles_sequence(rsr_ctx* ctx, int n, const rsr_image* frames, const rsr_image* prev /* may be NULL */, int fmt, int w, int h, int c,
+                            uint8_t* d_masks /* DEVICE, n * nx * ny */, void* stream);
+
+/* n frames in[k] -> out[k] in one call.  masks (HOST, nmask = n * nx * ny bytes) alone define it -- any bytes, not necessarily a diff; as in
+ * the masked call it is the caller who makes the one round trip (rsr_diff_tiles_sequence, a copy, one synchronisation), because the grid of
+ * every launch depends on the masks.  With src = rsr_sequence_sources(n, ntiles, masks, prev_out != NULL):
+ *   src == k:   tile t of in[k] walks the network; its output rectangle in out[k] receives the bytes rsr_process_device_batch with n = 1 writes
+ *               there, in the context's current mode.
+ *   otherwise:  the rectangle in out[k] receives the bytes of the same rectangle of out[src], or of prev_out for src == -1.
+ * Every byte of every out[k] window is therefore written, and no byte outside a window is touched.
+ *   Supported.  Everything the masked call supports: every format pair, NV12 and P010 on either side included; c 3 and 4; TTA, "precise",
+ *            "bgr"; "out_scale" 4 / 2 / 1 and every output ratio, with their admission checks; the YUV matrices, ranges and sitings; pitched
+ *            images and windows.  The copies move bytes at any alignment: prev_out and the out[k] may sit at different offsets modulo 16, a
+ *            uint8 pitch need not be a multiple of 3.
+ *   Aliasing.  prev_out may be out[0] itself (the same data and pitches): frame 0 is then updated in place and its source -1 rectangles are
+ *            skipped.  That is safe: a tile computed in frame 0 is never anybody's source -1.  Any other overlap between prev_out, the in[k]
+ *            and the out[k] is the caller's responsibility.
+ *   Ordering.  The changed tiles of all frames, in frame-major order, are cut into tile batches as in the masked call (slots of the frame's
+ *            largest tile; a refused workspace halves the batches of this call and leaves no bound behind).  The copies are ONE launch behind
+ *            the last tile batch: every source is a computed rectangle or prev_out, so no copy depends on another copy.  With no tile set
+ *            anywhere only the copy launch runs; with n == 1 and prev_out == out[0] in addition, nothing is launched.
+ *   Stream.  The contract of rsr_process_device_masked, the copy launch included; the tables of the tiles and of the copies travel in the
+ *            rotating buffers of the masked calls with the same single asynchronous copy.
+ *   Errors.  RSR_E_ARG before anything is launched: n outside 1 .. RSR_SEQ_MAX, nmask != n * nx * ny, a null pointer, prev_out == NULL
+ *            while row 0 has a zero byte, a prev_out that fails the checks of an output image, and everything rsr_process_device_batch refuses.
+ *   Progress callback: one call per computed tile.
+ *   Stats    "seq_calls", "seq_frames", "seq_tiles_run" (computed), "seq_tiles_copied" (tiles whose rectangles the copy launch moved: the
+ *            ones skipped in place are not counted), "seq_batches"; counted once the call is enqueued, like the masked stats.  A call that
+ *            launches counts in "batch_calls" too.  The "masked_*" stats are not touched.
+ * Out of scope: host-pointer images, groups of GPUs, the CLI, merging with concurrent calls, frames of different geometry in one call. */
+int rsr_process_device_sequence(rsr_ctx* ctx, int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt,
+                                const rsr_image* prev_out /* may be NULL */, const uint8_t* masks /* HOST, nmask bytes */, int nmask, void* stream);
+
 /* Host-only: bytes from `data` to one past the last byte a w x h x c image in `fmt` with these pitches touches (0 = packed, as above: then
  * rsr_image_bytes), or RSR_E_ARG for a combination rsr_process_device_batch refuses. */
 long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch);

@@ -34,6 +34,7 @@ EXPORTS = [
     "rsr_yuv_constants",
     "rsr_set_out_ratio", "rsr_out_size",
     "rsr_tile_count", "rsr_tile_source_rect", "rsr_diff_tiles", "rsr_process_device_masked",
+    "rsr_sequence_sources", "rsr_diff_tiles_sequence", "rsr_process_device_sequence",
 ]
 
 NUM_CONVS = 351
@@ -43,6 +44,7 @@ RSR_OK, RSR_E_ARG, RSR_E_IO, RSR_E_FORMAT, RSR_E_GRAPH, RSR_E_DEVICE, RSR_E_STAT
 RSR_FMT_U8_HWC, RSR_FMT_F16_CHW, RSR_FMT_F32_CHW = 0, 1, 2
 # YUV 4:2:0 surfaces: Y [h][w] then interleaved UV [h/2][w/2][2]; uint8, or uint16 with the 10-bit code in the high bits
 RSR_FMT_NV12, RSR_FMT_P010 = 4, 5
+RSR_SEQ_MAX = 16  # frames per rsr_process_device_sequence call
 
 
 class Profile(C.Structure):
@@ -121,6 +123,9 @@ def lib():
     L.rsr_tile_source_rect.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
     L.rsr_diff_tiles.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), ip, ip, ip, ip, vp, vp]
     L.rsr_process_device_masked.argtypes = [vp, C.POINTER(Image), ip, ip, ip, ip, C.POINTER(Image), ip, vp, ip, vp]
+    L.rsr_sequence_sources.argtypes = [ip, ip, vp, ip, C.POINTER(ip)]
+    L.rsr_diff_tiles_sequence.argtypes = [vp, ip, C.POINTER(Image), C.POINTER(Image), ip, ip, ip, ip, vp, vp]
+    L.rsr_process_device_sequence.argtypes = [vp, ip, C.POINTER(Image), ip, ip, ip, ip, C.POINTER(Image), ip, C.POINTER(Image), vp, ip, vp]
     L.rsr_model_pack.argtypes = [cp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_device_memory.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rsr_host_alloc.argtypes = [C.c_size_t]
@@ -413,6 +418,32 @@ class RealSR:
         self._ck(self._L.rsr_process_device_masked(self._h, _images([src]), int(in_fmt), w, h, c, _images([dst]), int(out_fmt), mp, nmask,
                                                    C.c_void_p(int(stream)) if stream else None))
 
+    def diff_tiles_sequence(self, frames, prev, fmt, w, h, c, d_masks, stream=None):
+        """rsr_diff_tiles_sequence: row k of d_masks (device pointer, len(frames) * nx * ny bytes) is what diff_tiles(frames[k - 1], frames[k])
+        writes; row 0 compares prev with frames[0], prev=None marks every tile of it.  One launch for all pairs.  frames: pointers or
+        (ptr, row_pitch, plane_pitch) descriptors, as for process_device_batch."""
+        self._push_params()
+        self._ck(self._L.rsr_diff_tiles_sequence(self._h, len(frames), _images(frames), _images([prev]) if prev is not None else None, int(fmt), w, h, c,
+                                                 C.c_void_p(int(d_masks)), C.c_void_p(int(stream)) if stream else None))
+
+    def process_device_sequence(self, srcs, in_fmt, w, h, c, dsts, out_fmt, masks, prev_out=None, stream=None):
+        """rsr_process_device_sequence: the frames srcs[k] -> dsts[k] (at most RSR_SEQ_MAX) in one call.  masks: a HOST uint8 array of
+        len(srcs) * nx * ny entries, row k the tiles of frame k that walk the network (or (address, nmask)); every other output rectangle
+        is copied from the frame that computed it last, or from prev_out (a descriptor; it may be dsts[0] itself: frame 0 in place)."""
+        if len(srcs) != len(dsts):
+            raise ValueError("process_device_sequence: %d inputs, %d outputs" % (len(srcs), len(dsts)))
+        if isinstance(masks, tuple):
+            mp, nmask = C.c_void_p(int(masks[0]) or None), int(masks[1])
+        elif masks is None:
+            mp, nmask = None, 0
+        else:
+            masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+            mp, nmask = _p(masks), masks.size
+        self._push_params()
+        self._ck(self._L.rsr_process_device_sequence(self._h, len(srcs), _images(srcs), int(in_fmt), w, h, c, _images(dsts), int(out_fmt),
+                                                     _images([prev_out]) if prev_out is not None else None, mp, nmask,
+                                                     C.c_void_p(int(stream)) if stream else None))
+
     def _check_full_out(self, out, h, w, c):
         ow, oh = self.out_size(w, h)
         if out.shape != (oh, ow, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
@@ -614,6 +645,20 @@ def tile_source_rect(w, h, tilesize, prepadding, tile, _L=None):
     if rc != RSR_OK:
         raise RealSRError(rc, L.rsr_last_error(None).decode())
     return tuple(v.value for v in r)
+
+
+def sequence_sources(masks, has_prev, _L=None):
+    """rsr_sequence_sources (host-only): masks is an (n, ntiles) array; returns the int32 (n, ntiles) array src with src[k, t] = k where
+    masks[k, t] is set, else the last j < k with masks[j, t] set, else -1 (the previous output: RealSRError unless has_prev)."""
+    L = _L or lib()
+    m = np.ascontiguousarray(masks, dtype=np.uint8)
+    if m.ndim != 2:
+        raise ValueError("sequence_sources: masks must be (n, ntiles), not %s" % (m.shape,))
+    src = np.zeros(m.shape, dtype=np.int32)
+    rc = L.rsr_sequence_sources(m.shape[0], m.shape[1], _p(m), int(bool(has_prev)), src.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != RSR_OK:
+        raise RealSRError(rc, L.rsr_last_error(None).decode())
+    return src
 
 
 def _images(entries):

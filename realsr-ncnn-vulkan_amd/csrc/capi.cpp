@@ -218,6 +218,28 @@ int rsr_diff_tiles(rsr_ctx* ctx, const rsr_image* a, const rsr_image* b, int fmt
     return ctx->e.diff_tiles(a, b, fmt, w, h, c, d_mask, static_cast<hipStream_t>(stream));
 }
 
+int rsr_sequence_sources(int n, int ntiles, const uint8_t* masks, int has_prev, int* src) { return rsr::sequence_sources(n, ntiles, masks, has_prev, src); }
+
+int rsr_diff_tiles_sequence(rsr_ctx* ctx, int n, const rsr_image* frames, const rsr_image* prev, int fmt, int w, int h, int c, uint8_t* d_masks, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    return ctx->e.diff_tiles_sequence(n, frames, prev, fmt, w, h, c, d_masks, static_cast<hipStream_t>(stream));
+}
+
+int rsr_process_device_sequence(rsr_ctx* ctx, int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt,
+                                const rsr_image* prev_out, const uint8_t* masks, int nmask, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    try
+    {
+        return ctx->e.process_device_sequence(n, in, in_fmt, w, h, c, out, out_fmt, prev_out, masks, nmask, static_cast<hipStream_t>(stream), stream == nullptr);
+    }
+    catch (const std::bad_alloc&) // (the tables of the call) -- nothing crosses extern "C"
+    {
+        return Engine::fail(RSR_E_NOMEM, "rsr_process_device_sequence: out of host memory");
+    }
+}
+
 int rsr_tile_count(int w, int h, int tilesize, int* nx, int* ny)
 {
     if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
@@ -599,6 +621,11 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "masked_tiles_skipped") *value = double(e.masked_tiles_skipped);
     else if (k == "masked_batches") *value = double(e.masked_batches);
     else if (k == "masked_table_us") *value = e.masked_table_us;
+    else if (k == "seq_calls") *value = double(e.seq_calls);
+    else if (k == "seq_frames") *value = double(e.seq_frames);
+    else if (k == "seq_tiles_run") *value = double(e.seq_tiles_run);
+    else if (k == "seq_tiles_copied") *value = double(e.seq_tiles_copied);
+    else if (k == "seq_batches") *value = double(e.seq_batches);
     else if (k == "merged_batches") *value = double(e.merged_batches.load());
     else if (k == "merged_images") *value = double(e.merged_images.load());
     else if (k == "merged_widest") *value = double(e.merged_widest.load());

@@ -1173,6 +1173,18 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
 // travel from a pinned image of the same rotation with one asynchronous copy on `st`.  mu held.
 int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t st)
 {
+    return enqueue_sequence(io, sel, std::vector<PropRect>(), st, masked_batches, &masked_table_us);
+}
+
+// The general form (include/realsr_hip.h rsr_process_device_sequence): the io.nimg <= kMaxMerge images have ONE geometry, and sel names
+// (image, tile) pairs, frame-major, as image * tiles_per_image + tile.  BaseTile::img carries the image into the pre- and post-processing
+// launches and, through item_pad2, into conv_last where it writes the image itself, as in enqueue_mixed; nothing else of the tables knows
+// how many images there are, so with one image this IS the masked call.  `rects`, when there are any, are copied by ONE launch of
+// propagate_rects behind the last batch: their table rides behind the tile tables in the same buffer and the same asynchronous copy, and
+// the event that guards the buffer is recorded behind that launch.  sel may be empty (nothing changed in any frame): then no workspace is
+// touched and only the copy runs.  batches_stat / table_us: the counters of the caller's kind of call.
+int Engine::enqueue_sequence(BatchIO io, const std::vector<int>& sel, const std::vector<PropRect>& rects, hipStream_t st, long long& batches_stat, double* table_us)
+{
     const int T = tilesize, P = prepadding, per = tta ? 8 : 1, w = io.w[0], h = io.h[0], c = io.c;
     const int total = ((w + T - 1) / T) * ((h + T - 1) / T), nsel = int(sel.size());
     std::vector<BaseTile> all;
@@ -1181,9 +1193,9 @@ int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t 
     image_tiles(w, h, T, P, scale, 0, total, 0, all, cap, mtw, mth);
     int rc = check_tile_px(cap);
     if (rc != RSR_OK) return rc;
-    int tiles_per_batch = int(std::min<long long>((long long)nsel * per, budget_slots(cap, w, h, c))) / per;
+    int tiles_per_batch = std::max(1, int(std::min<long long>((long long)nsel * per, budget_slots(cap, w, h, c))) / per);
     HIP_TRY(hipSetDevice(device));
-    while ((rc = ensure_workspace(tiles_per_batch * per, cap, st)) == RSR_E_NOMEM && tiles_per_batch > 1)
+    while (nsel && (rc = ensure_workspace(tiles_per_batch * per, cap, st)) == RSR_E_NOMEM && tiles_per_batch > 1)
     {
         free_workspace(st); // partly grown buffers go back first
         tiles_per_batch /= 2;
@@ -1201,7 +1213,8 @@ int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t 
         b.nslots = b.ntiles * per;
         for (int i = 0; i < b.ntiles; i++)
         {
-            BaseTile t = all[size_t(sel[size_t(t0 + i)])];
+            BaseTile t = all[size_t(sel[size_t(t0 + i)] % total)];
+            t.img = sel[size_t(t0 + i)] / total;
             t.slot0 = i * per;
             b.tiles.push_back(t);
             for (int k = 0; k < per; k++) b.dims.push_back(k < 4 ? TileDim{t.th, t.tw} : TileDim{t.tw, t.th}); // realsr.cpp:251-258
@@ -1212,6 +1225,8 @@ int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t 
         table_bytes += batch_table_bytes(b);
         batches.push_back(std::move(b));
     }
+    const size_t rect_at = table_bytes, rect_bytes = rects.size() * sizeof(PropRect);
+    table_bytes += al256(rect_bytes);
     const int k = int(mask_seq++ % 3);
     if (mask_ev[k]) HIP_TRY(hipEventSynchronize(mask_ev[k])); // the call that read this buffer last has finished
     if ((rc = ensure(mask_tab[k], table_bytes)) != RSR_OK) return rc;
@@ -1229,9 +1244,10 @@ int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t 
     }
     char *d = static_cast<char*>(mask_tab[k].p), *hs = static_cast<char*>(mask_stage[k]);
     for (Plan::Batch& b : batches) (void)upload_batch(b, d, xcd_order, &hs);
+    if (rect_bytes) std::memcpy(static_cast<char*>(mask_stage[k]) + rect_at, rects.data(), rect_bytes);
     // on the call's own stream, in front of its launches: no other stream is involved, whatever kind the caller's is
     HIP_TRY(hipMemcpyAsync(mask_tab[k].p, mask_stage[k], table_bytes, hipMemcpyHostToDevice, st));
-    masked_table_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_tab).count();
+    if (table_us) *table_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_tab).count();
     mark_begin(st);
     io.out_row0 = 0;
     io.split_slot = 0;
@@ -1246,7 +1262,19 @@ int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t 
             for (int i = 1; i <= b.ntiles; i++) progress(done + i, nsel, progress_user);
         done += b.ntiles;
         slots += b.nslots;
-        masked_batches++;
+        batches_stat++;
+    }
+    // The copies: every source is a rectangle some batch above computed, or the previous output, never another copy's destination, so
+    // one launch in any order does.  Also behind a LATER batch that failed to launch (what ran is then propagated as usual); not when
+    // the first one failed: nothing was computed, and nothing is written.
+    if (rect_bytes && (done > 0 || nsel == 0))
+    {
+        int max_rows = 0;
+        double bytes = 0;
+        for (const PropRect& r : rects) max_rows = std::max(max_rows, r.rows), bytes += double(r.width) * r.rows;
+        const hipError_t e = launch_propagate_rects(reinterpret_cast<const PropRect*>(static_cast<char*>(mask_tab[k].p) + rect_at), int(rects.size()), max_rows, st);
+        if (e != hipSuccess && rc == RSR_OK) rc = fail(RSR_E_DEVICE, std::string("propagate_rects: ") + hipGetErrorString(e));
+        mark(2, 0, 2 * bytes, st);
     }
     // (also behind a batch that failed to launch: the copy and the batches in front of it read the buffers)
     if (!mask_ev[k] && hipEventCreateWithFlags(&mask_ev[k], hipEventDisableTiming) != hipSuccess) mask_ev[k] = nullptr;
@@ -1608,6 +1636,219 @@ int Engine::diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, i
     }
     if (!user_stream) HIP_TRY(hipStreamSynchronize(stream));
     return RSR_OK;
+}
+
+// ---- frame sequences (include/realsr_hip.h "frame sequences") ------------------------------------------------------------------------------
+int sequence_sources(int n, int ntiles, const uint8_t* masks, int has_prev, int* src)
+{
+    if (n < 1 || n > kMaxMerge || ntiles < 1 || !masks || !src) return Engine::fail(RSR_E_ARG, "bad sequence arguments");
+    for (int t = 0; t < ntiles; t++)
+    {
+        int last = -1;
+        for (int k = 0; k < n; k++)
+        {
+            if (masks[size_t(k) * ntiles + t]) last = k;
+            if (last < 0 && !has_prev)
+                return Engine::fail(RSR_E_ARG, "tile " + std::to_string(t) + " of frame " + std::to_string(k) + " is not set and there is no previous output to take it from");
+            src[size_t(k) * ntiles + t] = last;
+        }
+    }
+    return RSR_OK;
+}
+
+// diff_tiles for the n consecutive pairs (prev, frames[0]), (frames[0], frames[1]), ...: every descriptor is checked as diff_tiles checks
+// its two, then one memset and one launch.
+int Engine::diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image* prev, int fmt, int w, int h, int c, uint8_t* d_masks, hipStream_t user_stream)
+{
+    if (n < 1 || n > kMaxMerge || !frames || !d_masks || (prev && !prev->data)) return fail(RSR_E_ARG, "bad image arguments");
+    DiffSeqArgs da;
+    std::memset(&da, 0, sizeof da);
+    const uintptr_t es = uintptr_t(fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(fmt, c));
+    for (int k = -1; k < n; k++)
+    {
+        const rsr_image* im = k < 0 ? prev : &frames[k];
+        if (!im) continue; // (no predecessor: pair 0 keeps its null `a`)
+        if (!im->data) return fail(RSR_E_ARG, "image " + std::to_string(k) + ": null data pointer");
+        long long row = 0, plane = 0;
+        int rc = image_layout(fmt, w, h, c, im->row_pitch, im->plane_pitch, &row, &plane);
+        if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
+        if (rc != RSR_OK) return rc;
+        if (reinterpret_cast<uintptr_t>(im->data) % es) return fail(RSR_E_ARG, "data is not aligned to the element size");
+        if (k >= 0)
+        { // frame k is the `b` of pair k ...
+            DiffPair& p = da.pair[k];
+            p.b = static_cast<const uint8_t*>(im->data), p.pitch_b = row, p.plane_b = plane;
+        }
+        if (k + 1 < n)
+        { // ... and the `a` of pair k + 1
+            DiffPair& p = da.pair[k + 1];
+            p.a = static_cast<const uint8_t*>(im->data), p.pitch_a = row, p.plane_a = plane;
+        }
+    }
+    da.n = n, da.fmt = fmt, da.w = w, da.h = h, da.c = c;
+    da.mask = d_masks;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        da.T = tilesize, da.P = prepadding;
+        da.nx = (w + da.T - 1) / da.T, da.ny = (h + da.T - 1) / da.T;
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_diff_tiles_seq(da, user_stream ? user_stream : stream));
+    }
+    if (!user_stream) HIP_TRY(hipStreamSynchronize(stream));
+    return RSR_OK;
+}
+
+// The byte rectangles of output tile `tile` of an os.of(w) x os.of(h) image in out_fmt, from (sb, sp, spl) to (db, dp, dpl) (base, row pitch,
+// plane pitch): one for uint8 HWC, three for the planar formats, Y and UV for the surfaces (the UV rectangle has the byte columns of the Y
+// rectangle and half its rows; check_yuv_out has made its edges even).
+static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, int tile, uint8_t* db, long long dp, long long dpl, const uint8_t* sb, long long sp,
+                         long long spl, std::vector<PropRect>& out)
+{
+    const int nx = (w + T - 1) / T, yi = tile / nx, xi = tile - yi * nx;
+    const long long es = BatchIO::px_bytes(out_fmt, c);
+    const long long x0 = os.of((long long)xi * T), y0 = os.of((long long)yi * T), x1 = os.of(std::min((xi + 1) * T, w)), y1 = os.of(std::min((yi + 1) * T, h));
+    const int width = int((x1 - x0) * es), rows = int(y1 - y0);
+    const int nplanes = out_fmt == RSR_FMT_U8_HWC || fmt_is_yuv(out_fmt) ? 1 : 3;
+    for (int q = 0; q < nplanes; q++)
+        out.push_back(PropRect{db + q * dpl + y0 * dp + x0 * es, sb + q * spl + y0 * sp + x0 * es, dp, sp, width, rows});
+    if (fmt_is_yuv(out_fmt)) out.push_back(PropRect{db + dpl + y0 / 2 * dp + x0 * es, sb + spl + y0 / 2 * sp + x0 * es, dp, sp, width, rows / 2});
+}
+
+int Engine::process_device_sequence(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, const rsr_image* prev_out,
+                                    const uint8_t* masks, int nmask, hipStream_t user_stream, bool sync)
+{
+    // everything is checked before anything is launched
+    if (n < 1 || n > kMaxMerge || !in || !out || !masks) return fail(RSR_E_ARG, "bad sequence arguments");
+    long long irow = 0, iplane = 0, orow = 0, oplane = 0, prow = 0, pplane = 0;
+    std::vector<long long> lay(size_t(n) * 4);
+    OutRatio os;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        os = out_ratio;
+        if (w >= 1 && h >= 1)
+            if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
+    }
+    const uintptr_t ies = uintptr_t(in_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(in_fmt, c)), oes = uintptr_t(out_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(out_fmt, c));
+    for (int i = 0; i < n; i++)
+    {
+        if (!in[i].data || !out[i].data) return fail(RSR_E_ARG, "image " + std::to_string(i) + ": null data pointer");
+        int rc = image_layout(in_fmt, w, h, c, in[i].row_pitch, in[i].plane_pitch, &irow, &iplane);
+        if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
+        if (rc == RSR_OK) rc = image_layout(out_fmt, int(os.of(w)), int(os.of(h)), c, out[i].row_pitch, out[i].plane_pitch, &orow, &oplane);
+        if (rc != RSR_OK) return rc;
+        if (reinterpret_cast<uintptr_t>(in[i].data) % ies || reinterpret_cast<uintptr_t>(out[i].data) % oes)
+            return fail(RSR_E_ARG, "image " + std::to_string(i) + ": data is not aligned to the element size");
+        lay[size_t(i) * 4] = irow, lay[size_t(i) * 4 + 1] = iplane, lay[size_t(i) * 4 + 2] = orow, lay[size_t(i) * 4 + 3] = oplane;
+    }
+    if (prev_out)
+    { // an output image like the others
+        if (!prev_out->data) return fail(RSR_E_ARG, "previous output: null data pointer");
+        if (const int rc = image_layout(out_fmt, int(os.of(w)), int(os.of(h)), c, prev_out->row_pitch, prev_out->plane_pitch, &prow, &pplane)) return rc;
+        if (reinterpret_cast<uintptr_t>(prev_out->data) % oes) return fail(RSR_E_ARG, "previous output: data is not aligned to the element size");
+    }
+    // frame 0 updated in place: its own rectangles of the previous output are already where they belong
+    const bool in_place = prev_out && prev_out->data == out[0].data && prow == lay[2] && pplane == lay[3];
+    hipEvent_t done = nullptr;
+    int rc = RSR_OK;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!loaded) return fail(RSR_E_STATE, "process before load");
+        if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
+        if (out_ratio != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
+        if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
+        if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
+        const int ntiles = ((w + tilesize - 1) / tilesize) * ((h + tilesize - 1) / tilesize);
+        if (nmask != (long long)n * ntiles)
+            return fail(RSR_E_ARG, "the masks have " + std::to_string(nmask) + " bytes, " + std::to_string(n) + " frames of " + std::to_string(ntiles) + " tiles each");
+        std::vector<int> src(static_cast<size_t>(nmask));
+        if (const int src_rc = sequence_sources(n, ntiles, masks, prev_out != nullptr, src.data())) return src_rc;
+        std::vector<int> sel; // (frame, tile) pairs that walk the network, frame-major
+        std::vector<PropRect> rects;
+        long long copied = 0;
+        for (int k = 0; k < n; k++)
+            for (int t = 0; t < ntiles; t++)
+            {
+                const int s = src[size_t(k) * ntiles + t];
+                if (s == k) sel.push_back(k * ntiles + t);
+                else if (!(s < 0 && k == 0 && in_place))
+                {
+                    const uint8_t* sb = static_cast<const uint8_t*>(s < 0 ? prev_out->data : out[s].data);
+                    output_rects(out_fmt, w, h, c, tilesize, os, t, static_cast<uint8_t*>(out[k].data), lay[size_t(k) * 4 + 2], lay[size_t(k) * 4 + 3], sb,
+                                 s < 0 ? prow : lay[size_t(s) * 4 + 2], s < 0 ? pplane : lay[size_t(s) * 4 + 3], rects);
+                    copied++;
+                }
+            }
+        auto count = [&]() { // once the call is enqueued (or has nothing to do): a call that fails counts nothing
+            seq_calls++;
+            seq_frames += n;
+            seq_tiles_run += (long long)sel.size();
+            seq_tiles_copied += copied;
+        };
+        if (sel.empty() && rects.empty())
+        { // nothing changed and everything is in place: nothing is launched
+            count();
+            return RSR_OK;
+        }
+        HIP_TRY(hipSetDevice(device));
+        // As in process_device_batch: an idle engine runs the call on the caller's own stream, a busy one on the compute stream between two events.
+        const bool direct = user_stream && hipStreamQuery(stream) == hipSuccess;
+        (void)hipGetLastError(); // (hipErrorNotReady is not an error)
+        hipStream_t st = direct ? user_stream : stream;
+        if (user_stream && !direct)
+        {
+            hipEvent_t e = take_event();
+            if (!e) return fail(RSR_E_DEVICE, "hipEventCreate failed");
+            HIP_TRY(hipEventRecord(e, user_stream));
+            HIP_TRY(hipStreamWaitEvent(stream, e, 0));
+            give_event(e);
+        }
+        BatchIO io(n, c, in_fmt, out_fmt, os);
+        for (int i = 0; i < n; i++)
+        {
+            const long long* l = &lay[size_t(i) * 4];
+            io.set(i, in[i].data, out[i].data, w, h);
+            io.in_pitch[i] = l[0], io.in_plane[i] = l[1], io.out_pitch[i] = l[2], io.out_plane[i] = l[3];
+        }
+        rc = enqueue_sequence(io, sel, rects, st, seq_batches, nullptr);
+        if (rc == RSR_OK)
+        {
+            count();
+            batch_calls++;
+        }
+        // A later batch that failed leaves the earlier ones enqueued: they complete, and the streams are ordered around them all the same.
+        if (direct)
+        { // whatever the compute stream gets next uses the same workspace: it waits for this call's last kernel
+            hipEvent_t e = take_event();
+            if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
+            {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(user_stream);
+            }
+            give_event(e);
+            if (rc == RSR_OK) device_direct++;
+            return rc;
+        }
+        if (user_stream || sync)
+        {
+            done = take_event();
+            if (!done) return fail(RSR_E_DEVICE, "hipEventCreate failed");
+            HIP_TRY(hipEventRecord(done, stream));
+            if (user_stream)
+            {
+                HIP_TRY(hipStreamWaitEvent(user_stream, done, 0));
+                give_event(done);
+                done = nullptr;
+            }
+        }
+    }
+    if (done)
+    { // wait outside the lock: other calls may enqueue behind this one meanwhile
+        const hipError_t e = hipEventSynchronize(done);
+        std::lock_guard<std::mutex> lk(mu);
+        give_event(done);
+        if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
+    }
+    return rc;
 }
 
 // ---- merging small images across calls (engine.h) ---------------------------------------------

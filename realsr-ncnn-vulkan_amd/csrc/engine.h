@@ -311,6 +311,8 @@ struct Engine
     size_t mask_stage_bytes[3] = {0, 0, 0};            // device with ONE asynchronous copy on the call's stream (same event guard)
     long long masked_calls = 0, masked_tiles_run = 0, masked_tiles_skipped = 0, masked_batches = 0; // stats, under mu
     double masked_table_us = 0; // stat: host time spent building and uploading those tables
+    // frame sequences (rsr_process_device_sequence); their tables travel in the rotating buffers of the masked calls
+    long long seq_calls = 0, seq_frames = 0, seq_tiles_run = 0, seq_tiles_copied = 0, seq_batches = 0; // stats, under mu
     long long image_items(int w, int h, long long limit) const;
     int merge_width(int w, int h, int c) const; // images of this geometry one batch may take (1: not a small image / merging off)
     int submit_merged(MergeReq& r);             // returns when r's batch has been ENQUEUED (r.ev_done recorded) or failed
@@ -353,6 +355,13 @@ struct Engine
                              const uint8_t* mask = nullptr, int nmask = 0);
     // mask[t] = do the images a and b differ inside tile t's source rectangle (include/realsr_hip.h rsr_diff_tiles); d_mask: device, one byte per tile
     int diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, hipStream_t user_stream);
+    // Frame sequences (include/realsr_hip.h "frame sequences").  diff_tiles_sequence: row k of d_masks = diff_tiles(frames[k - 1], frames[k]), row 0
+    // against prev (null: all ones); one memset, one launch.  process_device_sequence: the tiles of in[k] whose mask byte is set walk the
+    // network as shared tile batches (enqueue_sequence); every other output rectangle is copied from the frame that computed it last, or
+    // from prev_out, by one launch behind the last batch.
+    int diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image* prev, int fmt, int w, int h, int c, uint8_t* d_masks, hipStream_t user_stream);
+    int process_device_sequence(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, const rsr_image* prev_out,
+                                const uint8_t* masks, int nmask, hipStream_t user_stream, bool sync);
     // tile0/tile1: tiles [tile0, tile1) of the row-major tile grid only (tile1 < 0: all); `out` is always the full (w * out_scale x h * out_scale x c) image,
     // only the output rectangles of
     // those tiles are written
@@ -386,6 +395,10 @@ struct Engine
     int launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io);
     int enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid); // a merged batch of images of different sizes: tables built on the fly
     int enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t st);     // the tiles `sel` (ascending) of the ONE image of io: tables built on the fly
+    // The (image, tile) pairs `sel` (frame-major, tile = image * tiles_per_image + tile of the grid) of the io.nimg images of ONE geometry:
+    // tables built on the fly, then the copies `rects` in one launch behind the last batch (either may be empty).  enqueue_masked is this with
+    // one image and no copies.  batches_stat / table_us (may be null): the stats of the caller's kind of call
+    int enqueue_sequence(BatchIO io, const std::vector<int>& sel, const std::vector<PropRect>& rects, hipStream_t st, long long& batches_stat, double* table_us);
     int launch(const ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st);
     // The images of io -- all of io.w[0] x io.h[0] -- as ONE tile batch per workspace-full: tiles [tile0, tile1) of the tile grid
     // (tile1 < 0: all; whole images only when io.nimg > 1).  io.ev_half with half_rows: the engine may split the 4x tail and reports
@@ -419,6 +432,10 @@ struct Engine
 // Host-only: the resolved row and plane pitch (bytes) of a w x h x c image in `fmt` described with row_pitch / plane_pitch (0 = tightly
 // packed), or RSR_E_ARG (through Engine::fail) for a combination rsr_process_device_batch refuses.  plane = 0 for uint8 HWC.
 int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane);
+// Host-only (include/realsr_hip.h rsr_sequence_sources): src[k * ntiles + t] = the frame whose computed rectangle output tile t of frame k
+// shows -- k itself where masks[k][t] != 0, else the last j < k with masks[j][t] != 0, else -1 = the previous output.  RSR_E_ARG (through
+// Engine::fail) for n outside 1 .. kMaxMerge, ntiles < 1, a null pointer, or a -1 while has_prev == 0.
+int sequence_sources(int n, int ntiles, const uint8_t* masks, int has_prev, int* src);
 // Host-only: the constants of the YUV definition for a matrix (709 / 601 / 2020), a range (0 limited, 1 full) and a bit depth (8 / 10);
 // false for any other combination.
 bool yuv_coef(int matrix, int range, int bits, YuvCoef* out);

@@ -254,6 +254,38 @@ struct DiffArgs
 };
 hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st); // the error of the memset or of the launch
 
+// ---- frame sequences (rsr_diff_tiles_sequence, rsr_process_device_sequence) --------------------
+// n pairs of images of ONE format and geometry in one launch: row k of mask [n][ny * nx] is what diff_tiles writes for pair k.  The pair
+// index travels in the grid; every pair brings its own two descriptors, by value.  A pair without an `a` (the first frame of a stream that
+// has no predecessor) marks every tile.
+struct DiffPair
+{
+    const uint8_t* a; // null: every tile of this pair is marked
+    const uint8_t* b;
+    long long pitch_a, plane_a, pitch_b, plane_b; // as DiffArgs
+};
+struct DiffSeqArgs
+{
+    DiffPair pair[kMaxMerge];
+    int n;
+    int fmt, w, h, c;
+    int T, P, nx, ny;
+    uint8_t* mask; // [n][ny * nx]
+};
+hipError_t launch_diff_tiles_seq(const DiffSeqArgs& a, hipStream_t st); // the error of the memset or of the launch
+
+// One rectangle of bytes to move: `rows` rows of `width` bytes, from src to dst, each with its own pitch, at any alignment.  The rectangles
+// of one launch never overlap one another's destinations, and no source is another rectangle's destination.
+struct PropRect
+{
+    uint8_t* dst;
+    const uint8_t* src;
+    long long dst_pitch, src_pitch;
+    int width, rows;
+};
+// d_rects: DEVICE table of nrects entries; max_rows: the tallest of them (sizes the grid)
+hipError_t launch_propagate_rects(const PropRect* d_rects, int nrects, int max_rows, hipStream_t st);
+
 // shader-shaped standalone kernels (parity tests): device pointers
 void launch_preproc_shader(const uint8_t* bottom, int w, int h, int channels, uint16_t* const top[8], int ntop, int outw,
                            int outh, int outcstep, int pad_top, int pad_left, int crop_x, int crop_y, uint16_t* alpha,

@@ -1400,6 +1400,137 @@ hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st)
 }
 
 // =============================================================================================
+// frame sequences: the diff of n pairs in one launch, and the copy of the rectangles nobody computed
+// =============================================================================================
+// diff_tiles for n pairs at once: grid (tile, row chunk, pair * nrect + rectangle).  Row `pair` of the mask gets what diff_tiles writes
+// for that pair: the same rectangles, the same compared bytes (include/realsr_hip.h rsr_diff_tiles), the same choice of access width.
+__global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
+{
+    const int nrect = fmt_is_yuv(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
+    const int pair = blockIdx.z / nrect, rect = blockIdx.z - pair * nrect;
+    const int tile = blockIdx.x, yi = tile / a.nx, xi = tile - yi * a.nx;
+    const DiffPair& p = a.pair[pair];
+    uint8_t* const mask = a.mask + (long long)pair * a.nx * a.ny;
+    if (!p.a)
+    { // no predecessor: every tile of this frame is marked
+        if (rect == 0 && blockIdx.y == 0 && threadIdx.x == 0) mask[tile] = 1;
+        return;
+    }
+    int r[4];
+    tile_source_rect(a.w, a.h, a.T, a.P, xi, yi, r);
+    const int es = a.fmt == kFmtF32 ? 4 : ((a.fmt == kFmtF16 || a.fmt == kFmtP010) ? 2 : (a.fmt == kFmtU8 ? a.c : 1));
+    int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
+    long long off_a = 0, off_b = 0;
+    if (fmt_is_yuv(a.fmt))
+    {
+        if (rect == 1)
+        { // the (U, V) pairs the decode of this rectangle reads (diff_tiles)
+            const int cx0 = max((r[0] >> 1) - 1, 0), cx1 = min(((r[2] - 1) >> 1) + 1, a.w / 2 - 1);
+            bx0 = cx0 * 2 * es, bx1 = (cx1 + 1) * 2 * es;
+            y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1;
+            off_a = p.plane_a, off_b = p.plane_b;
+        }
+    }
+    else if (a.fmt != kFmtU8) off_a = rect * p.plane_a, off_b = rect * p.plane_b;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint8_t* const pa = p.a + off_a + bx0;
+    const uint8_t* const pb = p.b + off_b + bx0;
+    const unsigned mis = unsigned(reinterpret_cast<uintptr_t>(pa) ^ reinterpret_cast<uintptr_t>(pb)) | unsigned(p.pitch_a ^ p.pitch_b);
+    const int n = bx1 - bx0, ys = y0 + blockIdx.y * kDiffRows + wave, step = gridDim.y * kDiffRows;
+    bool d;
+    if (!(mis & 15)) d = rows_differ<uint4>(pa, p.pitch_a, pb, p.pitch_b, n, ys, y1, step, lane);
+    else if (!(mis & 3)) d = rows_differ<uint32_t>(pa, p.pitch_a, pb, p.pitch_b, n, ys, y1, step, lane);
+    else d = rows_differ<uint8_t>(pa, p.pitch_a, pb, p.pitch_b, n, ys, y1, step, lane);
+    if (__any(d) && lane == 0) mask[tile] = 1;
+}
+
+hipError_t launch_diff_tiles_seq(const DiffSeqArgs& a, hipStream_t st)
+{
+    const int ntiles = a.nx * a.ny;
+    if (ntiles <= 0 || a.n <= 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(a.mask, 0, size_t(ntiles) * size_t(a.n), st); // every byte is written: the kernel only ever stores ones
+    if (e != hipSuccess) return e;
+    const long long padded = (long long)a.T + 2 * a.P;
+    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_yuv(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
+    const int chunks = (rows + kDiffRows - 1) / kDiffRows;
+    const dim3 grid(ntiles, chunks < 1024 ? chunks : 1024, a.n * nrect), block(256);
+    hipLaunchKernelGGL(diff_tiles_seq, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+// Rows of a rectangle per workgroup and step: 4 per wave.  An 800-row rectangle spreads over 50 workgroups, the 60 of a 1080p frame at x4
+// over 3000: a dozen per CU, enough in flight for a pass that only waits for memory.
+constexpr int kPropRows = 16;
+
+// n bytes from ps to pd, one wave, lanes along the row; TV is the widest access the two addresses allow (they agree modulo sizeof(TV)).
+// The head up to pd's boundary and the tail behind the last whole piece go byte by byte (lanes 0 .. 15 and 16 .. 31), the body in aligned
+// pieces, 64 per step.  No byte outside [ps, ps + n) is read and none outside [pd, pd + n) written: the neighbours belong to someone else.
+template <typename TV>
+__device__ __forceinline__ void copy_row(uint8_t* pd, const uint8_t* ps, int n, int lane)
+{
+    constexpr int V = int(sizeof(TV));
+    const int head = min(n, int((0 - reinterpret_cast<uintptr_t>(pd)) & uintptr_t(V - 1)));
+    const int nvec = (n - head) / V, tail = n - head - nvec * V;
+    if (V > 1)
+    {
+        int e = -1;
+        if (lane < 16) e = lane < head ? lane : -1;
+        else if (lane < 32) e = lane - 16 < tail ? n - tail + lane - 16 : -1;
+        if (e >= 0) pd[e] = ps[e];
+    }
+    TV* const vd = reinterpret_cast<TV*>(pd + head);
+    const TV* const vs = reinterpret_cast<const TV*>(ps + head);
+    // four pieces per lane and step, all loads in front of the stores: a 2400-byte row (an 800-pixel uint8 rectangle) is in flight at once
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = lane; i < nvec; i += 256)
+    {
+        const bool b1 = i + 64 < nvec, b2 = i + 128 < nvec, b3 = i + 192 < nvec;
+        const TV v0 = vs[i];
+        TV v1 = v0, v2 = v0, v3 = v0;
+        if (b1) v1 = vs[i + 64];
+        if (b2) v2 = vs[i + 128];
+        if (b3) v3 = vs[i + 192];
+        vd[i] = v0;
+        if (b1) vd[i + 64] = v1;
+        if (b2) vd[i + 128] = v2;
+        if (b3) vd[i + 192] = v3;
+    }
+}
+
+// grid (rectangle, row chunk): wave w of a workgroup moves rows w, w + 4, ... of its chunks.  The access width is chosen per row, uniformly
+// for the wave: 16 bytes where source and destination of the row are co-aligned (a window at the same offset in equally pitched surfaces;
+// every row of it when the pitches agree modulo 16), 4 where they agree modulo 4, single bytes otherwise.
+__global__ __launch_bounds__(256) void propagate_rects(const PropRect* __restrict__ rects)
+{
+    const PropRect r = rects[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int step = gridDim.y * kPropRows;
+#pragma unroll 1
+    for (int ys = blockIdx.y * kPropRows + wave; ys < r.rows; ys += step)
+#pragma unroll 1
+        for (int y = ys; y < min(ys - wave + kPropRows, r.rows); y += 4)
+        {
+            uint8_t* const pd = r.dst + (long long)y * r.dst_pitch;
+            const uint8_t* const ps = r.src + (long long)y * r.src_pitch;
+            const unsigned mis = __builtin_amdgcn_readfirstlane(unsigned(reinterpret_cast<uintptr_t>(pd) ^ reinterpret_cast<uintptr_t>(ps)));
+            if (!(mis & 15)) copy_row<uint4>(pd, ps, r.width, lane);
+            else if (!(mis & 3)) copy_row<uint32_t>(pd, ps, r.width, lane);
+            else copy_row<uint8_t>(pd, ps, r.width, lane);
+        }
+}
+
+hipError_t launch_propagate_rects(const PropRect* d_rects, int nrects, int max_rows, hipStream_t st)
+{
+    if (nrects <= 0 || max_rows <= 0) return hipSuccess;
+    const int chunks = (max_rows + kPropRows - 1) / kPropRows;
+    // (a table of many rectangles: the workgroups stride over the chunks rather than the grid growing beyond what the device keeps in flight)
+    const int cap = nrects >= 8192 ? 1 : 8192 / nrects;
+    const dim3 grid(nrects, chunks < cap ? chunks : cap), block(256);
+    hipLaunchKernelGGL(propagate_rects, grid, block, 0, st, d_rects);
+    return hipGetLastError();
+}
+
+// =============================================================================================
 // model self-check: range probe and output compare (Engine::selfcheck)
 // =============================================================================================
 constexpr int kCheckBlocks = 512; // grid-stride: at most this many workgroups of 256

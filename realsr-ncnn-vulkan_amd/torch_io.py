@@ -9,6 +9,8 @@
 
     y, n = torch_io.upscale_delta(sr, frame, prev_frame, y)   # video: only the tiles whose source changed run again, y is updated in place
 
+    ys, n = torch_io.upscale_sequence(sr, frames)   # video, N frames known in advance: one diff, one host wait and shared launches per 16
+
 The float tensors go through rsr_process_device_fmt / rsr_process_device_batch as they are (planar fp16 / fp32, include/realsr_hip.h): no
 quantisation to uint8 on either side, no permute, no extra pass over the frame.  An (N, 3, H, W) batch is ONE call: small images share
 tile batches.  A view whose rows are contiguous (a crop, a slice of a batch, a frame inside a padded surface) is passed by pointer and
@@ -320,6 +322,113 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None):
     if st is not cur:
         cur.wait_stream(st)
     return out, int(np.count_nonzero(mask))
+
+
+# ---- video: a window of frames shares one diff, one round trip and one walk through the network ------------------------------------------
+SEQ_MAX = 16  # frames per rsr_process_device_sequence call (RSR_SEQ_MAX)
+
+
+def _new_like_result(x, ow, oh):
+    """An uninitialised result for the single image x (a tensor or a (y, uv) pair) at ow x oh, of x's kind."""
+    if isinstance(x, (tuple, list)):
+        o = x[0].new_empty((oh * 3 // 2, ow))
+        return (o[:oh], o[oh:])
+    if x.dim() == 2:
+        return x.new_empty((oh * 3 // 2, ow))
+    return x.new_empty((oh, ow, x.shape[2]) if x.dtype == torch.uint8 else (3, oh, ow))
+
+
+def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
+    """upscale() / upscale_yuv() of N consecutive video frames: returns (ys, tiles_run), ys[k] bit for bit what upscale(frames[k]) returns.
+    Only the tiles whose source rectangle differs from the frame before walk the network, and the changed tiles of up to 16 frames share
+    their launches (rsr_diff_tiles_sequence + rsr_process_device_sequence, include/realsr_hip.h); every other rectangle of ys[k] is copied
+    from the frame that computed it last.
+    frames: a stacked tensor -- (N, 3, H, W) float or (N, H, W, 3 | 4) uint8 -- or a list of single images of ONE layout, each anything
+    upscale_delta takes for x (YUV surfaces and (y, uv) pairs come as a list only: a stacked 3-D uint8 tensor would be ambiguous).
+    prev_x, prev_y: the frame in front of frames[0] and its result at the context's current options; without them every tile of
+    frames[0] runs.  out: None = the results are allocated (torch.empty: every byte is written); else a stacked tensor or a list like
+    the result, each image addressable by row and plane pitch.  The result has the kind the input had.
+    Windows of at most 16 frames; window g + 1 takes the last frame and output of window g as its prev.  Per window, all on
+    torch.cuda.current_stream() (the side stream for the null stream, as in upscale_delta): the diff of all pairs, ONE asynchronous copy
+    of the masks into pinned memory, ONE stream synchronisation, the sequence call."""
+    stacked = isinstance(frames, torch.Tensor)
+    if stacked:
+        if frames.dim() != 4 or frames.shape[0] < 1:
+            raise ValueError("upscale_sequence: a stacked tensor must be (N, 3, H, W) float or (N, H, W, 3 | 4) uint8, not %s" % (tuple(frames.shape),))
+        xs = [frames[i] for i in range(frames.shape[0])]
+    else:
+        xs = list(frames) if isinstance(frames, (tuple, list)) else []
+        if not xs:
+            raise ValueError("upscale_sequence: frames must be a stacked tensor or a non-empty list of images")
+    n = len(xs)
+    fmt, w, h, c, _ = _image_desc(sr, xs[0], "frames[0]")
+    for i, x in enumerate(xs[1:], 1):
+        if not _same_layout(xs[0], x):
+            raise ValueError("upscale_sequence: mixed layouts: frames[%d] differs from frames[0] in kind, shape, dtype or device" % i)
+    if prev_x is not None and prev_y is None:
+        raise ValueError("upscale_sequence: a prev_x needs its result prev_y")
+    if prev_x is not None and not _same_layout(xs[0], prev_x):
+        raise ValueError("upscale_sequence: prev_x must have the frames' layout, shape, dtype and device")
+    if prev_x is None:
+        prev_y = None  # (nothing of it would be used: every tile of frames[0] runs)
+    pair = isinstance(xs[0], (tuple, list))
+    if fmt in (RSR_FMT_NV12, RSR_FMT_P010):
+        s = getattr(sr, "out_scale", sr.scale)
+        if not s:
+            raise ValueError("upscale_sequence: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (getattr(sr, "out_ratio", "in force"),))
+        ow, oh = w * s, h * s
+    else:
+        ow, oh = _out_size(sr, w, h)
+
+    def result_desc(t, what):
+        if isinstance(t, (tuple, list)) != pair:
+            raise ValueError("upscale_sequence: %s must be a %s like the frames" % (what, "(y, uv) pair" if pair else "tensor"))
+        f2, w2, h2, c2, d2 = _image_desc(sr, t, what)
+        if (f2, w2, h2, c2) != (fmt, ow, oh, c):
+            raise ValueError("upscale_sequence: %s must hold the %d x %d result of a %d x %d frame in the frames' format" % (what, ow, oh, w, h))
+        if d2 is None:
+            raise ValueError("upscale_sequence: %s is not addressable by row and plane pitch" % what)
+        return d2
+
+    dprev_y = result_desc(prev_y, "prev_y") if prev_y is not None else None
+    first = xs[0][0] if pair else xs[0]
+    if out is None:
+        if stacked:
+            out = first.new_empty((n, oh, ow, c) if fmt == RSR_FMT_U8_HWC else (n, 3, oh, ow))
+            ys = [out[i] for i in range(n)]
+        else:
+            out = ys = [_new_like_result(x, ow, oh) for x in xs]
+    else:
+        if stacked != isinstance(out, torch.Tensor) or (stacked and out.dim() != 4) or len(out) != n:
+            raise ValueError("upscale_sequence: out must be a %s of %d results like the frames" % ("stacked tensor" if stacked else "list", n))
+        ys = [out[i] for i in range(n)]
+    douts = [result_desc(y, "out[%d]" % i) for i, y in enumerate(ys)]
+    # Views no descriptor fits are packed first -- all of them here, in front of the wait below (see upscale_delta).
+    packed = [_desc_or_packed(sr, x, "frames[%d]" % i) for i, x in enumerate(xs)]
+    dxs = [p[0] for p in packed]
+    dprev_x, keep_p = _desc_or_packed(sr, prev_x, "prev_x") if prev_x is not None else (None, None)
+    nx, ny = sr.tile_count(w, h)
+    nt = nx * ny
+    cur = torch.cuda.current_stream(first.device)
+    st = cur if cur.cuda_stream != 0 else _side_stream(first.device)  # (the null stream means "synchronously" to the C calls: see upscale)
+    if st is not cur:
+        st.wait_stream(cur)
+    tiles_run = 0
+    for g in range(0, n, SEQ_MAX):
+        k = min(SEQ_MAX, n - g)
+        px, py = (dprev_x, dprev_y) if g == 0 else (dxs[g - 1], douts[g - 1])
+        d_masks = first.new_empty(k * nt, dtype=torch.uint8)
+        host = _pinned_u8(k * nt)
+        with (torch.cuda.stream(st) if st is not cur else contextlib.nullcontext()):  # (the copy below goes where torch's current stream is)
+            sr.diff_tiles_sequence(dxs[g:g + k], px, fmt, w, h, c, d_masks.data_ptr(), stream=st.cuda_stream)
+            host.copy_(d_masks, non_blocking=True)
+        st.synchronize()  # the ONE host wait of the window
+        masks = host.numpy()
+        sr.process_device_sequence(dxs[g:g + k], fmt, w, h, c, douts[g:g + k], fmt, masks, prev_out=py, stream=st.cuda_stream)
+        tiles_run += int(np.count_nonzero(masks))
+    if st is not cur:
+        cur.wait_stream(st)
+    return out, tiles_run
 
 
 _side = {}
