@@ -188,6 +188,7 @@ int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
  *            behind conv_last (postproc_tiles_area) -- no whole-frame pass, no materialised x4 image.
  *   Formats. Outputs RSR_FMT_U8_HWC (c 3 and 4), RSR_FMT_F16_CHW, RSR_FMT_F32_CHW.  The input side is independent: a YUV input works at
  *            any ratio.
+ *            (RSR_FMT_NV12 / RSR_FMT_P010 outputs: "YUV output at a ratio" below.)
  *   The definition, exact.  Scale n / d in lowest terms, L = 4 d.  Along one axis, on the integer grid where x4 pixel i covers
  *   [i n, (i + 1) n), output pixel X covers [X L, (X + 1) L): its taps are i = floor(X L / n) .. floor(((X + 1) L - 1) / n), with the
  *   integer weights g_i = min((X + 1) L, (i + 1) n) - max(X L, i n), each in 1 .. n, summing to L; at most 4 taps per axis for the
@@ -205,11 +206,32 @@ int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
  *            7. "bgr" swaps channels 0 and 2 on store as ever; "precise" changes only what r is.
  *   (For 2/1 the definition gives the bits of "out_scale" 2 -- weights 2, 2 and 1/16 against plain adds and 1/4 -- but 2/1 takes the box
  *   kernel all the same.)
- * Out of scope: a YUV OUTPUT (RSR_FMT_NV12 / RSR_FMT_P010) at a ratio other than 4 / 2 / 1: RSR_E_ARG. */
+ * Out of scope: a YUV OUTPUT (RSR_FMT_NV12 / RSR_FMT_P010) whose w * n / d, h * n / d or tilesize * n / d is odd: RSR_E_ARG ("YUV output at
+ * a ratio" below says what is admitted).
+ *
+ * YUV output at a ratio.  RSR_FMT_NV12 / RSR_FMT_P010 on the OUTPUT side at any permitted n / d -- 720p NV12 -> 1080p NV12 is one call at
+ * 3/2 -- through every device entry point that honours ratios and YUV formats: rsr_process_device_fmt, _batch (windows and pitched
+ * surfaces included), _masked and _sequence (whose propagated rectangles are the reduced ones).  A YUV input stays independent of it.
+ *   Admission.  The ratio rule above (w * n, h * n and tilesize * n divisible by d), and w * n / d, h * n / d and tilesize * n / d EVEN, so
+ *            that no 2 x 2 chroma quad crosses a tile or the image's edge: 1280 x 720 at 3/2 and tile 200 (tile rectangle 300), 1920 x 1080
+ *            at 4/3 and tile 198 (264) or 201 (268), 720 x 480 at 9/4 and tile 200 (450), any even size at 3/1 and tile 200 (600); not tile
+ *            30 at 3/2 (45, odd).  Anything else: RSR_E_ARG before anything is launched, with "YUV" in rsr_last_error (rsr_out_size_yuv).
+ *   The definition, exact.  d(X, Y, q) = what RSR_FMT_F32_CHW holds for output pixel (X, Y) at the context's ratio n / d: steps 1 to 4
+ *            above, unchanged.  The surface is "Encode" of the YUV section applied to those d: luma per pixel, chroma from the quad mean
+ *            at "yuv_siting" 0 and from the [1 2 1] filters of "Chroma siting" at 1 and 2, with the same clamp at the first column / row of
+ *            every TILE's output rectangle -- which now starts at multiples of tilesize * n / d output pixels.  TTA and "precise" change
+ *            only what r is, as ever.
+ *   One more small launch behind conv_last writes the surface (postproc_tiles_yuv_area: one thread per 2 x 2 quad, every output pixel
+ *   gathered tap by tap as postproc_tiles_area gathers it); 4/1, 2/1 and 1/1 keep postproc_tiles_yuv, the same launches and bytes.
+ *   Host pointers, groups of GPUs and the CLI stay uint8 RGB(A), as before. */
 int rsr_set_out_ratio(rsr_ctx* ctx, int num, int den);
 /* Host-only (no GPU): *ow = w * n / d, *oh = h * n / d for n / d = num / den reduced (either pointer may be NULL), or RSR_E_ARG for a ratio
  * outside the set above, or when w * n, h * n or tilesize * n is not divisible by d: what a call at that ratio and tile size refuses. */
 int rsr_out_size(int num, int den, int tilesize, int w, int h, int* ow, int* oh);
+/* Host-only (no GPU): rsr_out_size for a YUV 4:2:0 OUTPUT (RSR_FMT_NV12 / RSR_FMT_P010) -- the same results and conventions, and RSR_E_ARG
+ * also for an odd w or h, or when w * n / d, h * n / d or tilesize * n / d is odd: what a call with a YUV output at that ratio and tile size
+ * refuses.  For 4/1, 2/1 and 1/1 that is the rule of the YUV section ("Errors": tilesize * out_scale even). */
+int rsr_out_size_yuv(int num, int den, int tilesize, int w, int h, int* ow, int* oh);
 
 /* A device image behind its own pointer and pitches: a whole tensor, a crop of a larger frame, a frame inside a padded decoder surface, a
  * window of a canvas.  Pitches are in BYTES.  A uint8 row pitch need not be a multiple of the pixel size; for the planar formats both

@@ -32,7 +32,7 @@ EXPORTS = [
     "rsr_process_device_fmt", "rsr_image_bytes",
     "rsr_process_device_batch", "rsr_image_span",
     "rsr_yuv_constants",
-    "rsr_set_out_ratio", "rsr_out_size",
+    "rsr_set_out_ratio", "rsr_out_size", "rsr_out_size_yuv",
     "rsr_tile_count", "rsr_tile_source_rect", "rsr_diff_tiles", "rsr_process_device_masked",
     "rsr_sequence_sources", "rsr_diff_tiles_sequence", "rsr_process_device_sequence",
 ]
@@ -119,6 +119,7 @@ def lib():
     L.rsr_yuv_constants.argtypes = [ip, ip, ip, C.POINTER(C.c_float), ip]
     L.rsr_set_out_ratio.argtypes = [vp, ip, ip]
     L.rsr_out_size.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_out_size_yuv.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_tile_count.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_tile_source_rect.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
     L.rsr_diff_tiles.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), ip, ip, ip, ip, vp, vp]
@@ -284,6 +285,17 @@ class RealSR:
         if self._L.rsr_out_size(r.numerator, r.denominator, int(self.tilesize), int(w), int(h), C.byref(ow), C.byref(oh)) != 0:
             raise ValueError("output ratio %s: %d x %d at tile %d: w, h and tilesize times %d must be multiples of %d"
                              % (r, w, h, self.tilesize, r.numerator, r.denominator))
+        return ow.value, oh.value
+
+    def out_size_yuv(self, w, h):
+        """out_size for a YUV 4:2:0 OUTPUT (RSR_FMT_NV12 / RSR_FMT_P010): (w * n / d, h * n / d) at the ratio and tile size in force.
+        ValueError where the engine would refuse the call: an odd w or h, w, h or tilesize times n no multiple of d, or one of
+        w * n / d, h * n / d and tilesize * n / d odd -- a 2 x 2 chroma quad would cross a tile or the image's edge (rsr_out_size_yuv)."""
+        r = self.out_ratio
+        ow, oh = C.c_int(0), C.c_int(0)
+        if self._L.rsr_out_size_yuv(r.numerator, r.denominator, int(self.tilesize), int(w), int(h), C.byref(ow), C.byref(oh)) != 0:
+            raise ValueError("a YUV output at ratio %s: %d x %d at tile %d: w and h must be even, w, h and tilesize times %d multiples of %d, and "
+                             "w, h and tilesize times %s even" % (r, w, h, self.tilesize, r.numerator, r.denominator, r))
         return ow.value, oh.value
 
     @property

@@ -312,6 +312,22 @@ int rsr_out_size(int num, int den, int tilesize, int w, int h, int* ow, int* oh)
     return RSR_OK;
 }
 
+int rsr_out_size_yuv(int num, int den, int tilesize, int w, int h, int* ow, int* oh)
+{
+    rsr::OutRatio r;
+    if (!rsr::out_ratio_reduce(num, den, &r)) return Engine::fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
+    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
+    if ((w | h) & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
+    const std::string what = "a YUV 4:2:0 output at ratio " + std::to_string(r.n) + "/" + std::to_string(r.d);
+    if (!r.divides(w) || !r.divides(h) || !r.divides(tilesize))
+        return Engine::fail(RSR_E_ARG, what + ": w, h and tilesize times " + std::to_string(r.n) + " must be multiples of " + std::to_string(r.d));
+    if (!rsr::yuv_out_even(r, w, h, tilesize))
+        return Engine::fail(RSR_E_ARG, what + " needs w, h and tilesize times " + std::to_string(r.n) + "/" + std::to_string(r.d) + " even");
+    if (ow) *ow = int(r.of(w));
+    if (oh) *oh = int(r.of(h));
+    return RSR_OK;
+}
+
 int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n)
 {
     rsr::YuvCoef c;

@@ -1420,15 +1420,26 @@ bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
 }
 
 // A YUV output is written one 2 x 2 luma quad per thread, tile by tile: the image and every tile's rectangle must start and end on even
-// output pixels (only out_scale 1 can break that).  mu held (tilesize).
+// output pixels (only out_scale 1 can break that).  At a ratio n / d other than 4 / 2 / 1 (check_ratio_out has made w n / d, h n / d and
+// tilesize n / d whole) the same rule reads: those three are even (yuv_out_even, what rsr_out_size_yuv states).  mu held (tilesize).
 int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
 {
     if (!fmt_is_yuv(out_fmt)) return RSR_OK;
-    const int os = ratio.out_scale(); // (check_ratio_out has refused a YUV output at any other ratio)
-    if (((w * os) | (h * os) | (tilesize * os)) & 1)
-        return fail(RSR_E_ARG, "a YUV 4:2:0 output needs w * out_scale, h * out_scale and tilesize * out_scale even");
+    if (ratio.is_box())
+    {
+        const int os = ratio.out_scale();
+        if (((w * os) | (h * os) | (tilesize * os)) & 1)
+            return fail(RSR_E_ARG, "a YUV 4:2:0 output needs w * out_scale, h * out_scale and tilesize * out_scale even");
+        return RSR_OK;
+    }
+    if (!yuv_out_even(ratio, w, h, tilesize))
+        return fail(RSR_E_ARG, "a YUV 4:2:0 output at ratio " + std::to_string(ratio.n) + "/" + std::to_string(ratio.d) + " needs w, h and tilesize times " +
+                                   std::to_string(ratio.n) + "/" + std::to_string(ratio.d) + " even (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " +
+                                   std::to_string(tilesize) + ")");
     return RSR_OK;
 }
+
+bool yuv_out_even(OutRatio r, long long w, long long h, long long T) { return !((r.of(w) | r.of(h) | r.of(T)) & 1); }
 
 // ---- rational output scales (rsr_set_out_ratio) -----------------------------------------------------------------------------------------
 bool out_ratio_reduce(int num, int den, OutRatio* out)
@@ -1448,9 +1459,8 @@ bool out_ratio_reduce(int num, int den, OutRatio* out)
 int Engine::check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const
 {
     if (os.is_box()) return RSR_OK;
-    if (fmt_is_yuv(out_fmt)) return fail(RSR_E_ARG, "a YUV 4:2:0 output takes out_scale 4, 2 or 1 only: no other output ratio (rsr_set_out_ratio)");
-    if (!os.divides(w) || !os.divides(h) || !os.divides(T))
-        return fail(RSR_E_ARG, "output ratio " + std::to_string(os.n) + "/" + std::to_string(os.d) + ": w, h and tilesize times " + std::to_string(os.n) +
+    if (!os.divides(w) || !os.divides(h) || !os.divides(T)) // (a YUV output: check_yuv_out then asks for even quotients as well)
+        return fail(RSR_E_ARG, std::string(fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "") + "output ratio " + std::to_string(os.n) + "/" + std::to_string(os.d) + ": w, h and tilesize times " + std::to_string(os.n) +
                                    " must be multiples of " + std::to_string(os.d) + " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
     return RSR_OK;
 }
@@ -1492,7 +1502,10 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
         std::lock_guard<std::mutex> lk(mu);
         os = out_ratio;
         if (n >= 1 && w >= 1 && h >= 1)
+        {
             if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
+            if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
+        }
     }
     for (int i = 0; i < n; i++)
     {
@@ -1726,7 +1739,10 @@ int Engine::process_device_sequence(int n, const rsr_image* in, int in_fmt, int 
         std::lock_guard<std::mutex> lk(mu);
         os = out_ratio;
         if (w >= 1 && h >= 1)
+        {
             if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
+            if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
+        }
     }
     const uintptr_t ies = uintptr_t(in_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(in_fmt, c)), oes = uintptr_t(out_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(out_fmt, c));
     for (int i = 0; i < n; i++)

@@ -53,6 +53,8 @@ struct OutRatio
 };
 // Host-only: num / den reduced to lowest terms when it is one of the permitted ratios (d in 1..4, 1 <= n / d <= 4), else false.
 bool out_ratio_reduce(int num, int den, OutRatio* out);
+// Host-only: are w n / d, h n / d and T n / d (whole: OutRatio::divides) all even -- what a YUV 4:2:0 output asks of image and tile size?
+bool yuv_out_even(OutRatio r, long long w, long long h, long long T);
 
 struct DevBuf
 {
@@ -385,7 +387,7 @@ struct Engine
     // no TTA merge / alpha channel / box reduction / YUV 4:2:0 surface needs the planar blob (dbg 8192: off)
     bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
     int check_yuv_out(int out_fmt, int w, int h, OutRatio os) const; // RSR_E_ARG when a 2 x 2 chroma quad of a YUV output would cross the image or a tile
-    int check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const; // RSR_E_ARG when w, h or the tile size T times os is no whole number of pixels, or for a YUV output at a ratio other than 4 / 2 / 1 (no lock needed)
+    int check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const; // RSR_E_ARG when w, h or the tile size T times os is no whole number of pixels (no lock needed)
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
     // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).

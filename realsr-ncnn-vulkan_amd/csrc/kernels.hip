@@ -3,6 +3,7 @@
 //   preproc_tiles[_lds]    realsr_preproc{,_tta}.comp equivalent, writes the network input planes (from uint8 HWC or planar fp16 / fp32 images)
 //   postproc_tiles[_lds]   realsr_postproc{,_tta}.comp equivalent, writes the uint8 HWC image (or a planar fp16 / fp32 one)
 //   preproc_tiles<., true> / postproc_tiles_yuv   the same with an NV12 / P010 surface on that side (YUV <-> RGB inside the kernel)
+//   postproc_tiles_yuv_area                        ... written at an output ratio other than 4 / 2 / 1 (rsr_set_out_ratio)
 //                          (_lds: rows staged in LDS, dword loads / 1-KiB stores, transposed TTA variants through an LDS tile;
 //                          chosen per launch by measurement: launch_*_tiles)
 //   *_shader               the same arithmetic in the shaders' own memory layout (parity tests)
@@ -1094,6 +1095,116 @@ static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipS
     else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
 }
 
+// ---- YUV 4:2:0 output at a rational scale (a surface format under rsr_set_out_ratio) -----------------------------------------------------
+// ONE pixel d(X, Y) of a tile's output rectangle at the scale n / d, L = 4 d, of one channel's blob: the value postproc_tiles_area stores
+// for RSR_FMT_F32_CHW -- the same taps, integer weights, order and constant (include/realsr_hip.h, rsr_set_out_ratio, steps 1 to 4), every
+// tap through merged_block<TP, 1>.  (X, Y) are the tile's own coordinates, which are the image's.  (A copy of that kernel's loop nest rather
+// than a function shared with it: the area kernel stays, instruction for instruction, what it was measured as.)
+template <typename TP>
+__device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, int h, int crop, int tta, int n, int L, float norm, int X, int Y)
+{
+    const int x0 = X * L, x1 = x0 + L, y0 = Y * L, y1 = y0 + L;                   // the pixel's footprint on the grid
+    const int ix0 = x0 / n, ix1 = (x1 - 1) / n, iy0 = y0 / n, iy1 = (y1 - 1) / n; // its taps: x4 pixels of the tile's kept rectangle
+    float V = 0.f;
+#pragma unroll 1
+    for (int j = iy0; j <= iy1; j++)
+    {
+        float H = 0.f;
+#pragma unroll 1
+        for (int i = ix0; i <= ix1; i++)
+        {
+            float c[1][1];
+            merged_block<TP, 1>(b, ss, w, h, i + crop, j + crop, tta, c);
+            const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), c[0][0]);
+            H = i == ix0 ? p : add_rn(H, p);
+        }
+        const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
+        V = j == iy0 ? p : add_rn(V, p);
+    }
+    return fminf(mul_rn(V, norm), 1.f);
+}
+
+// The sibling of postproc_tiles_yuv for the scales n / d that are not 4, 2 or 1: one thread makes ONE 2 x 2 quad of luma samples and the
+// (U, V) pair they share; d, the RGB value of an output pixel, is area_pixel -- what RSR_FMT_F32_CHW holds at that ratio -- and everything
+// behind d is postproc_tiles_yuv's: Y' accumulated across the channel loop, chroma from the quad mean (SITE 0) or the [1 2 1] filters about
+// the co-sited column / row (SITE 1 / 2), whose neighbours d(2X-1, .) / d(., 2Y-1) the thread gathers itself; in the first quad column / row
+// of the TILE's rectangle the neighbour's coordinate is the pixel's own (a select, no divergent branch), hence bitwise d(2X, .) / d(., 2Y).
+// A tile's rectangle is tilesize * n / d output pixels and starts at its multiples; the engine admits the call only where that, w * n / d
+// and h * n / d are even (check_yuv_out), so no quad crosses a tile or the image's edge.  Every tap index stays inside the tile's kept
+// rectangle as in postproc_tiles_area: X < out_w n / L gives ((X + 1) L - 1) / n <= out_w - 1.  Lanes run along x.
+template <typename TP, typename TO, int SITE>
+__global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
+{
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int n = a.num, L = 4 * a.den;
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= t.out_w * n / L / 2 || gy >= t.out_h * n / L / 2) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const long long cstep = (long long)w * h;
+    const int px = 2 * gx, py = 2 * gy; // the quad's first output pixel, in the tile's rectangle
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    const YuvCoef& k = a.yuv;
+    float yq[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, ym = 0.f, rm = 0.f, bm = 0.f;
+#pragma unroll 1
+    for (int q = 0; q < 3; q++)
+    {
+        const TP* b = b0 + q * cstep;
+        float d[2][2];
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int i = 0; i < 2; i++) d[j][i] = area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, px + i, py + j);
+        const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
+        float m;
+        if constexpr (SITE == 0) m = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
+        else
+        {
+            const int lx = px - (gx ? 1 : 0), uy = py - (gy ? 1 : 0); // output column xl / row yu
+            float hs[2];
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+                hs[j] = add_rn(add_rn(area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, lx, py + j), d[j][1]), add_rn(d[j][0], d[j][0]));
+            if constexpr (SITE == 1) m = mul_rn(add_rn(hs[0], hs[1]), 0.125f);
+            else
+            {
+                const float u0 = area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, px, uy);
+                const float hu = add_rn(add_rn(area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, lx, uy),
+                                               area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, px + 1, uy)), add_rn(u0, u0));
+                m = mul_rn(add_rn(add_rn(hu, hs[1]), add_rn(hs[0], hs[0])), 0.0625f);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int i = 0; i < 2; i++) yq[j][i] = add_rn(yq[j][i], mul_rn(kq, d[j][i]));
+        ym = add_rn(ym, mul_rn(kq, m));
+        if (q == 0) rm = m;
+        if (q == 2) bm = m;
+    }
+    const long long pitch = a.out_pitch[im];
+    const int X = t.out_x * n / L + px, Y = (t.out_y - a.out_row0) * n / L + py; // the quad's first luma sample
+    uint8_t* const oy = a.outs[im] + Y * pitch + (long long)X * (int)sizeof(TO);
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+        store_pair<TO>(oy + j * pitch, yuv_code<TO>(yq[j][0], k.yscale, k.yadd, k.maxcode), yuv_code<TO>(yq[j][1], k.yscale, k.yadd, k.maxcode));
+    const float cb = mul_rn(sub_rn(bm, ym), k.icb), cr = mul_rn(sub_rn(rm, ym), k.icr);
+    uint8_t* const ouv = a.outs[im] + a.out_plane[im] + (Y >> 1) * pitch + (long long)X * (int)sizeof(TO);
+    store_pair<TO>(ouv, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
+}
+
+template <typename TP, typename TO>
+static void launch_postproc_yuv_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    const int L = 4 * a.den; // (ow_tile / 2) x (oh_tile / 2) quads per tile
+    const dim3 grid((max_ow * a.num / L / 2 + 63) / 64, (max_oh * a.num / L / 2 + 3) / 4, a.ntiles), block(256);
+    if (a.siting == 1) hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, 1>), grid, block, 0, st, a);
+    else if (a.siting == 2) hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, 2>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, 0>), grid, block, 0, st, a);
+}
+
 template <typename TP, typename TO>
 static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
@@ -1116,6 +1227,12 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
     if (a.ntiles <= 0) return;
     if (fmt_is_yuv(a.out_fmt))
     { // a 4:2:0 surface: one thread per luma quad, at every out_scale, with and without TTA
+        if (a.num > 0 && !(a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1)))
+        { // ... and at every other ratio (rsr_set_out_ratio): the quad kernel over area-averaged pixels
+            if (a.out_fmt == kFmtNV12) a.f32 ? launch_postproc_yuv_area<float, uint8_t>(a, max_ow, max_oh, st) : launch_postproc_yuv_area<_Float16, uint8_t>(a, max_ow, max_oh, st);
+            else a.f32 ? launch_postproc_yuv_area<float, uint16_t>(a, max_ow, max_oh, st) : launch_postproc_yuv_area<_Float16, uint16_t>(a, max_ow, max_oh, st);
+            return;
+        }
         if (a.out_fmt == kFmtNV12) a.f32 ? launch_postproc_yuv<float, uint8_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint8_t>(a, max_ow, max_oh, st);
         else a.f32 ? launch_postproc_yuv<float, uint16_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint16_t>(a, max_ow, max_oh, st);
         return;

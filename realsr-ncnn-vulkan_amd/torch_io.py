@@ -6,6 +6,7 @@
     torch_io.upscale(sr, frame[..., y0:y1, x0:x1], out=canvas[..., 4 * y0:4 * y1, 4 * x0:4 * x1])   # views in, a window out: no copies
 
     nv12 = torch_io.upscale_yuv(sr, surface)   # a decoder's (3H/2, W) uint8 NV12 or 16-bit P010 surface -> the same layout at out_scale
+    sr.tilesize = 200; sr.out_ratio = Fraction(3, 2); nv12_1080 = torch_io.upscale_yuv(sr, nv12_720)   # ... or at a ratio: 720p -> 1080p
 
     y, n = torch_io.upscale_delta(sr, frame, prev_frame, y)   # video: only the tiles whose source changed run again, y is updated in place
 
@@ -182,33 +183,51 @@ def _describe_yuv(y, uv):
     return (y.data_ptr(), y.stride(0) * es, plane) if plane > 0 else None
 
 
+def _out_size_yuv(sr, w, h, who):
+    """(ow, oh) of the YUV output for a w x h surface: w and h times the context's out_scale 4 / 2 / 1, or, while another ratio is in force
+    (sr.out_ratio: out_scale reads 0), sr.out_size_yuv -- ValueError where w, h or the tile size does not take a YUV output at that ratio,
+    and for a context that has no out_size_yuv."""
+    s = getattr(sr, "out_scale", sr.scale)
+    if s:
+        return w * s, h * s
+    if not hasattr(sr, "out_size_yuv"):
+        raise ValueError("%s: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (who, getattr(sr, "out_ratio", "in force"),))
+    return sr.out_size_yuv(w, h)
+
+
+def _yuv_ratio_note(sr):
+    """What a size refusal adds while a YUV surface is written at a ratio other than 4 / 2 / 1 (else nothing)."""
+    if getattr(sr, "out_scale", sr.scale):
+        return ""
+    return " (a YUV surface at the output ratio %s)" % (getattr(sr, "out_ratio", "in force"),)
+
+
 def upscale_yuv(sr, surface, out=None):
     """upscale() for a YUV 4:2:0 surface on the context's GPU: the YUV <-> RGB conversion and the chroma resampling happen inside the
     engine's pre- and post-processing kernels (RSR_FMT_NV12 / RSR_FMT_P010, include/realsr_hip.h; options "yuv_matrix", "yuv_range"), so no
     RGB frame is materialised.  Where the chroma samples sit is the context's option "yuv_siting" (sr.yuv_siting: 0 centre, 1 left -- what
     an H.264 / HEVC / AV1 decoder yields by default --, 2 top-left -- BT.2020 / UHD); it holds for the surface read and the one written.  surface: a (3H / 2, W) tensor as a decoder yields it -- uint8 (NV12), or uint16 / int16 (P010: the 10-bit
     code in the high bits) -- or a (y, uv) pair of views, y (H, W) and uv (H / 2, W).  A pair that no descriptor fits (a uv view that
-    lies below y in memory, say) is packed into one allocation first.  Returns the same layout at sr.out_scale: a (3H' / 2, W') tensor,
+    lies below y in memory, say) is packed into one allocation first.  Returns the same layout at sr.out_scale -- or at sr.out_ratio (3/2, 4/3,
+    9/4, 3 ...) where sr.out_size_yuv admits the size --: a (3H' / 2, W') tensor,
     or for a pair the (y, uv) views of one.  out: the surface (or pair) to write and return instead.  Runs on torch.cuda.current_stream(),
     with no host synchronisation inside."""
     pair = isinstance(surface, (tuple, list))
     y, uv = _planes(sr, surface, "surface")
     fmt, (h, w) = _YUV[y.dtype], y.shape
-    s = getattr(sr, "out_scale", sr.scale)
-    if not s:  # (a ratio other than 4 / 2 / 1 is in force: sr.out_ratio)
-        raise ValueError("upscale_yuv: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (getattr(sr, "out_ratio", "in force"),))
+    ow, oh = _out_size_yuv(sr, w, h, "upscale_yuv")  # (out_scale 4 / 2 / 1, or a ratio such as 3/2: sr.out_ratio)
     if out is not None:
         if isinstance(out, (tuple, list)) != pair:
             raise ValueError("upscale_yuv: out must be a %s like the input" % ("(y, uv) pair" if pair else "surface tensor"))
         oy, ouv = _planes(sr, out, "out")
-        if tuple(oy.shape) != (h * s, w * s) or oy.dtype != y.dtype or oy.device != y.device:
-            raise ValueError("upscale_yuv: out must be a %s surface of %d x %d on %s" % (y.dtype, w * s, h * s, y.device))
+        if tuple(oy.shape) != (oh, ow) or oy.dtype != y.dtype or oy.device != y.device:
+            raise ValueError("upscale_yuv: out must be a %s YUV surface of %d x %d on %s" % (y.dtype, ow, oh, y.device))
         dout = _describe_yuv(oy, ouv)
         if dout is None:
             raise ValueError("upscale_yuv: out is not addressable by one row pitch and a plane pitch")
     else:
-        o = y.new_empty((h * s * 3 // 2, w * s))
-        oy, ouv = o[:h * s], o[h * s:]
+        o = y.new_empty((oh * 3 // 2, ow))
+        oy, ouv = o[:oh], o[oh:]
         out = (oy, ouv) if pair else o
         dout = _describe_yuv(oy, ouv)
     din = _describe_yuv(y, uv)
@@ -278,18 +297,16 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None):
         raise ValueError("upscale_delta: prev_x must have x's layout, shape, dtype and device")
     yuv = fmt in (RSR_FMT_NV12, RSR_FMT_P010)
     if yuv:
-        s = getattr(sr, "out_scale", sr.scale)
-        if not s:
-            raise ValueError("upscale_delta: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (getattr(sr, "out_ratio", "in force"),))
-        ow, oh = w * s, h * s
+        ow, oh = _out_size_yuv(sr, w, h, "upscale_delta")
     else:
         ow, oh = _out_size(sr, w, h)
+    note = _yuv_ratio_note(sr) if yuv else ""
     for t, what in ((prev_y, "prev_y"),) + (((out, "out"),) if out is not None else ()):
         if isinstance(t, (tuple, list)) != isinstance(x, (tuple, list)):
             raise ValueError("upscale_delta: %s must be a %s like x" % (what, "(y, uv) pair" if isinstance(x, (tuple, list)) else "tensor"))
         f2, w2, h2, c2, d2 = _image_desc(sr, t, what)
         if (f2, w2, h2, c2) != (fmt, ow, oh, c):
-            raise ValueError("upscale_delta: %s must hold the %d x %d result for x (%d x %d) in x's format" % (what, ow, oh, w, h))
+            raise ValueError("upscale_delta: %s must hold the %d x %d result for x (%d x %d) in x's format%s" % (what, ow, oh, w, h, note))
         if d2 is None:
             raise ValueError("upscale_delta: %s is not addressable by row and plane pitch" % what)
     if out is None:
@@ -372,11 +389,10 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
     if prev_x is None:
         prev_y = None  # (nothing of it would be used: every tile of frames[0] runs)
     pair = isinstance(xs[0], (tuple, list))
+    note = ""
     if fmt in (RSR_FMT_NV12, RSR_FMT_P010):
-        s = getattr(sr, "out_scale", sr.scale)
-        if not s:
-            raise ValueError("upscale_sequence: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (getattr(sr, "out_ratio", "in force"),))
-        ow, oh = w * s, h * s
+        ow, oh = _out_size_yuv(sr, w, h, "upscale_sequence")
+        note = _yuv_ratio_note(sr)
     else:
         ow, oh = _out_size(sr, w, h)
 
@@ -385,7 +401,7 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
             raise ValueError("upscale_sequence: %s must be a %s like the frames" % (what, "(y, uv) pair" if pair else "tensor"))
         f2, w2, h2, c2, d2 = _image_desc(sr, t, what)
         if (f2, w2, h2, c2) != (fmt, ow, oh, c):
-            raise ValueError("upscale_sequence: %s must hold the %d x %d result of a %d x %d frame in the frames' format" % (what, ow, oh, w, h))
+            raise ValueError("upscale_sequence: %s must hold the %d x %d result of a %d x %d frame in the frames' format%s" % (what, ow, oh, w, h, note))
         if d2 is None:
             raise ValueError("upscale_sequence: %s is not addressable by row and plane pitch" % what)
         return d2
