@@ -92,6 +92,39 @@ def test_accumulator_and_fp16_conversion_round_to_nearest_even(sr):
         assert not msg, (c, msg)
 
 
+def test_fp16_subnormals_are_kept_on_both_sides(sr):
+    """The whole-network mirror (tests/exact_net.py) stores a few thousand fp16 SUBNORMAL activations per tile and keeps them, as numpy
+    does.  Here: fp16-subnormal inputs (and the smallest normal ones) times weights 1.0 / 2.0 / 0.5, one tap per output channel, plus a
+    bias far below fp16's subnormal spacing -- every accumulator is exact in fp32, and its fp16 result is subnormal or just above, with
+    and without LeakyReLU.  A kernel that flushed subnormal MFMA inputs, or whose fp32 -> fp16 conversion flushed subnormal results, would
+    differ from numpy; the message says which."""
+    cin, cout, h, w = 32, 32, 9, 40
+    rng = np.random.default_rng(2411)
+    k = rng.integers(1, 1024, (cin, h, w))                                     # subnormals: k * 2^-24
+    k = np.where(rng.integers(0, 3, (cin, h, w)) == 0, (1024 + k) << rng.integers(0, 3, (cin, h, w)), k)   # a third: [2^-14, 2^-11)
+    x = (np.where(rng.integers(0, 2, k.shape) == 1, -k, k) * 2.0 ** -24).astype(np.float16)
+    assert (np.abs(x.astype(np.float64)) < X.F16_MIN_NORMAL).mean() > 0.5 and (x != 0).all()
+    wt = np.zeros((cout, cin, 3, 3), np.float32)
+    for o in range(cout):
+        wt[o, (o * 7) % cin, o % 3, (o // 3) % 3] = (1.0, 2.0, 0.5)[o % 3] * (-1.0 if o & 4 else 1.0)
+    m = rng.integers(0, 64, cout) * 2 + 1
+    b = (np.where(rng.integers(0, 2, cout) == 1, -m, m) * 2.0 ** -27).astype(np.float32)   # odd multiples of 2^-27, |b| < 2^-20
+    acc = X.conv_sum(x, wt, b)                                                  # (asserts that the sums are exact in fp32)
+    flushed_in = X.conv_sum(np.where(np.abs(x.astype(np.float64)) < X.F16_MIN_NORMAL, 0, x).astype(np.float16), wt, b)
+    for lrelu in (False, True):
+        want = X.epi1(acc, lrelu)
+        sub = (np.abs(want.astype(np.float64)) < X.F16_MIN_NORMAL) & (want != 0)
+        assert sub.mean() > 0.3                                                 # subnormal results, and normal ones next to them
+        flushed_out = np.where(sub, np.float16(0) * want, want).astype(np.float16)
+        for c in combos(sr, LAYER_COMBOS[:2]):
+            got = sr.conv3x3(x, wt, b, lrelu=lrelu)
+            msg = same16(got, want)
+            if msg:
+                msg += " | equals subnormal inputs flushed: %s, subnormal results flushed (ignoring the sign of zero): %s" % (
+                    np.array_equal(got.view(np.uint16), X.epi1(flushed_in, lrelu).view(np.uint16)), np.array_equal(got, flushed_out))
+            assert not msg, (c, lrelu, msg)
+
+
 # ---- EPI 1 (conv + bias [+ LeakyReLU] -> fp16), every conv shape of the network ------------------------------------
 SHAPES = [(64, 32, 20, 40, False), (96, 32, 17, 33, False), (128, 32, 16, 32, False), (160, 32, 33, 65, False), (192, 64, 16, 32, False),
           (3, 64, 9, 70, False), (64, 3, 33, 31, False), (64, 64, 10, 21, True), (64, 64, 1, 1, False),

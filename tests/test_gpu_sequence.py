@@ -281,6 +281,7 @@ def test_diff_rows_equal_the_reference_and_the_single_diff(ctx, name, fmt, c):
             keep.append(d), descs.append(desc)
     for with_prev in (True, False):
         d_m = torch.full((8 * NT + 16,), 0xCD, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()  # (the fill runs on torch's null stream, the diff on the context's non-blocking one: without this wait the fill may land behind the diff's memset)
         s.diff_tiles_sequence(descs[1:], descs[0] if with_prev else None, fmt, W, H, c, d_m.data_ptr())
         got = d_m.cpu().numpy()
         assert (got[8 * NT:] == 0xCD).all()
@@ -291,10 +292,12 @@ def test_diff_rows_equal_the_reference_and_the_single_diff(ctx, name, fmt, c):
     # ... and what rsr_diff_tiles writes for every pair
     for k in range(8):
         d_1 = torch.full((NT,), 0xCD, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
         s.diff_tiles(descs[k], descs[k + 1], fmt, W, H, c, d_1.data_ptr())
         assert d_1.cpu().numpy().tolist() == want[k].tolist(), k
     # sixteen pairs in one launch
     d_m = torch.full((16 * NT,), 0xCD, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
     s.diff_tiles_sequence([descs[1 + k % 8] for k in range(16)], None, fmt, W, H, c, d_m.data_ptr())
     got = d_m.cpu().numpy().reshape(16, NT)
     assert got[0].tolist() == ONE and got[8].tolist() == ref.diff_mask(fmt, frames[8], frames[1], T, P).tolist()

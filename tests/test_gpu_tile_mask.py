@@ -282,6 +282,7 @@ def gpu_mask(s, a, b, fmt, w, h, c=3, place_b=None):
         d_b = torch.from_numpy(host).cuda()
         desc_b = (d_b.data_ptr() + off, row, plane)
     d_m = torch.full((nx * ny,), 0xCD, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()  # (the fill runs on torch's null stream, the diff on the context's non-blocking one: without this wait the fill may land behind the diff's memset)
     s.diff_tiles(d_a.data_ptr(), desc_b, fmt, w, h, c, d_m.data_ptr())
     m = d_m.cpu().numpy()
     assert set(m.tolist()) <= {0, 1}, m
