@@ -2,14 +2,25 @@
 //
 //   preproc_tiles[_lds]    realsr_preproc{,_tta}.comp equivalent, writes the network input planes (from uint8 HWC or planar fp16 / fp32 images)
 //   postproc_tiles[_lds]   realsr_postproc{,_tta}.comp equivalent, writes the uint8 HWC image (or a planar fp16 / fp32 one)
-//   preproc_tiles<., true> / postproc_tiles_yuv   the same with an NV12 / P010 surface on that side (YUV <-> RGB inside the kernel)
-//   postproc_tiles_yuv_area                        ... written at an output ratio other than 4 / 2 / 1 (rsr_set_out_ratio)
 //                          (_lds: rows staged in LDS, dword loads / 1-KiB stores, transposed TTA variants through an LDS tile;
 //                          chosen per launch by measurement: launch_*_tiles)
-//   *_shader               the same arithmetic in the shaders' own memory layout (parity tests)
+//   postproc_tiles_box     the image box-reduced to x2 / x1 (out_scale)
+//   postproc_tiles_area    the image area-averaged to any other ratio (rsr_set_out_ratio)
+//   preproc_tiles<., true> an NV12 / P010 surface as the source (YUV -> RGB inside the kernel)
+//   postproc_tiles_yuv[_area]   an NV12 / P010 surface as the destination, at out_scale 4 / 2 / 1 [at any other ratio]
+//   *_shader               the same arithmetic in the shaders' own memory layout (parity tests; independent of everything below)
+//
+// Every rule the header (include/realsr_hip.h) fixes bit for bit is written ONCE, as a __device__ __forceinline__ function the kernels share:
+//   tta_dest               where pixel (gx, gy) of a tile goes in TTA variant k                    preproc_tiles, preproc_tiles_lds
+//   tta_gather / merged_block   the eight TTA variants of a K x K block merged in the shader's order [and clamped]
+//                                                                                                    every post kernel but postproc_tiles_lds
+//   alpha_bicubic          the bicubic x4 alpha value                                               every post kernel that writes RGBA
+//   area_sum / area_pixel  the area-average loop nest over a tap source                            postproc_tiles_area, postproc_tiles_yuv_area
+//   yuv_quad               a luma quad and its (U, V) pair from a source of pixels d               postproc_tiles_yuv, postproc_tiles_yuv_area
 //
 // The 351 convolutions live in conv_flow.hip (conv3x3_flow).  Written for gfx950 only.
 #include "kernels.h"
+#include <type_traits>
 
 namespace rsr {
 
@@ -88,6 +99,9 @@ __device__ __forceinline__ void load_uv(const uint8_t* row, int cx, float& u, fl
 // chroma is CO-SITED with the even luma index horizontally / on both axes (yuv_decode_cos); a left-sited surface keeps the centre rule
 // vertically.  A co-sited axis takes c[n] for an even index i = 2n and (c[n] + c[min(n + 1, N/2 - 1)]) * 0.5f for an odd one: one chroma
 // column (row) for even pixels, two for odd ones, so the lanes of a pair still share their loads.  Exact for codes, like the centre rule.
+// The centre rule along one axis: 3/4 of the near chroma sample, 1/4 of the far one (yuv_decode, yuv_decode_cos).
+__device__ __forceinline__ float chroma_mix(float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); }
+
 template <typename SRC, int SITE>
 __device__ __forceinline__ void yuv_decode_cos(const uint8_t* img, int pitch, long long plane, int x, int y, int w, int h, float& U, float& V)
 {
@@ -103,10 +117,9 @@ __device__ __forceinline__ void yuv_decode_cos(const uint8_t* img, int pitch, lo
     load_uv<SRC>(r1, cx0, u10, v10);
     load_uv<SRC>(r1, cx1, u11, v11);
     auto cos = [](float a, float b) { return mul_rn(add_rn(a, b), 0.5f); };
-    auto mix = [](float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); };
     const float ua = cos(u00, u01), ub = cos(u10, u11), va = cos(v00, v01), vb = cos(v10, v11); // horizontally first
     if constexpr (SITE == 2) { U = cos(ua, ub); V = cos(va, vb); }
-    else { U = mix(ua, ub); V = mix(va, vb); }
+    else { U = chroma_mix(ua, ub); V = chroma_mix(va, vb); }
 }
 
 template <typename SRC, int SITE = 0>
@@ -129,8 +142,7 @@ __device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long l
         load_uv<SRC>(rn, cxf, unf, vnf);
         load_uv<SRC>(rf, cxn, ufn, vfn);
         load_uv<SRC>(rf, cxf, uff, vff);
-        auto mix = [](float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); };
-        U = mix(mix(unn, unf), mix(ufn, uff)), V = mix(mix(vnn, vnf), mix(vfn, vff));
+        U = chroma_mix(chroma_mix(unn, unf), chroma_mix(ufn, uff)), V = chroma_mix(chroma_mix(vnn, vnf), chroma_mix(vfn, vff));
     }
     const float yn = mul_rn(sub_rn(Y, k.yoff), k.ys);
     const float cb = mul_rn(sub_rn(U, k.coff), k.cs), cr = mul_rn(sub_rn(V, k.coff), k.cs);
@@ -140,6 +152,23 @@ __device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long l
     rgb[0] = fminf(fmaxf(r, 0.f), 1.f);
     rgb[1] = fminf(fmaxf(g, 0.f), 1.f);
     rgb[2] = fminf(fmaxf(b, 0.f), 1.f);
+}
+
+// realsr_preproc_tta.comp:104-111: pixel (gx, gy) of a tw x th tile lands at (ox, oy) of TTA variant k, whose rows are ow long
+// (preproc_tiles, preproc_tiles_lds).
+__device__ __forceinline__ void tta_dest(int k, int gx, int gy, int tw, int th, int& oy, int& ox, int& ow)
+{
+    switch (k)
+    {
+    default: oy = gy; ox = gx; ow = tw; break;
+    case 1: oy = gy; ox = tw - 1 - gx; ow = tw; break;
+    case 2: oy = th - 1 - gy; ox = tw - 1 - gx; ow = tw; break;
+    case 3: oy = th - 1 - gy; ox = gx; ow = tw; break;
+    case 4: oy = gx; ox = gy; ow = th; break;
+    case 5: oy = gx; ox = th - 1 - gy; ow = th; break;
+    case 6: oy = tw - 1 - gx; ox = th - 1 - gy; ow = th; break;
+    case 7: oy = tw - 1 - gx; ox = gy; ow = th; break;
+    }
 }
 
 // realsr_preproc.comp:47-95 and realsr_preproc_tta.comp:54-113, for a batch of tiles.
@@ -196,17 +225,7 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     for (int k = 0; k < nv; k++)
     {
         int oy, ox, ow;
-        switch (k)
-        { // realsr_preproc_tta.comp:104-111
-        default: oy = gy; ox = gx; ow = t.tw; break;
-        case 1: oy = gy; ox = t.tw - 1 - gx; ow = t.tw; break;
-        case 2: oy = t.th - 1 - gy; ox = t.tw - 1 - gx; ow = t.tw; break;
-        case 3: oy = t.th - 1 - gy; ox = gx; ow = t.tw; break;
-        case 4: oy = gx; ox = gy; ow = t.th; break;
-        case 5: oy = gx; ox = t.th - 1 - gy; ow = t.th; break;
-        case 6: oy = t.tw - 1 - gx; ox = t.th - 1 - gy; ow = t.th; break;
-        case 7: oy = t.tw - 1 - gx; ox = gy; ow = t.th; break;
-        }
+        tta_dest(k, gx, gy, t.tw, t.th, oy, ox, ow);
         char* dst = static_cast<char*>(a.in_plane) + (long long)(t.slot0 + k) * a.slot_stride + ((long long)oy * ow + ox) * (a.plane_ch * 2);
         *reinterpret_cast<half8*>(dst) = v0;
         *reinterpret_cast<uint4*>(dst + 16) = z;
@@ -302,22 +321,43 @@ __global__ __launch_bounds__(256) void preproc_tiles_lds(const PreArgs a)
             const int r = tr ? pi : ro, cx = tr ? ro : pi;
             const int gx = gx0 + cx, gy = gy0 + r;
             int oy, ox, ow;
-            switch (k)
-            { // realsr_preproc_tta.comp:104-111
-            default: oy = gy; ox = gx; ow = t.tw; break;
-            case 1: oy = gy; ox = t.tw - 1 - gx; ow = t.tw; break;
-            case 2: oy = t.th - 1 - gy; ox = t.tw - 1 - gx; ow = t.tw; break;
-            case 3: oy = t.th - 1 - gy; ox = gx; ow = t.tw; break;
-            case 4: oy = gx; ox = gy; ow = t.th; break;
-            case 5: oy = gx; ox = t.th - 1 - gy; ow = t.th; break;
-            case 6: oy = t.tw - 1 - gx; ox = t.th - 1 - gy; ow = t.th; break;
-            case 7: oy = t.tw - 1 - gx; ox = gy; ow = t.th; break;
-            }
+            tta_dest(k, gx, gy, t.tw, t.th, oy, ox, ow);
             const uint2 v = px[r][cx];
             const uint4 o = half ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(v.x, v.y, 0u, 0u);
             *reinterpret_cast<uint4*>(base + ((long long)oy * ow + ox) * 32 + half * 16) = o;
         }
     }
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------------
+// f(T{}) with T = the blob's element type (PostArgs::f32), a surface's sample type, an image's element type; f(integral_constant) with
+// the chroma siting: how the launchers below pick these template arguments.  (launch_postproc_box and launch_postproc_area keep a ladder
+// of their own: their ALPHA argument exists for the uint8 image only.)
+template <typename F>
+static void with_blob_type(const PostArgs& a, F f)
+{
+    if (a.f32) f(float{});
+    else f(_Float16{});
+}
+template <typename F>
+static void with_sample_type(int fmt, F f)
+{
+    if (fmt == kFmtNV12) f(uint8_t{});
+    else f(uint16_t{});
+}
+template <typename F>
+static void with_image_type(int fmt, F f)
+{
+    if (fmt == kFmtF16) f(_Float16{});
+    else if (fmt == kFmtF32) f(float{});
+    else f(uint8_t{});
+}
+template <typename F>
+static void with_siting(int siting, F f)
+{
+    if (siting == 1) f(std::integral_constant<int, 1>{});
+    else if (siting == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 0>{});
 }
 
 void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t st)
@@ -331,18 +371,10 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
     if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8) // (the staged kernel knows uint8 sources only)
     {
         const dim3 grid((max_tw + 31) / 32, (max_th + 7) / 8, a.ntiles), block(256);
-        if (fmt_is_yuv(a.fmt) && a.siting == 1)
-        {
-            if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true, 1>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((preproc_tiles<uint16_t, true, 1>), grid, block, 0, st, a);
-        }
-        else if (fmt_is_yuv(a.fmt) && a.siting == 2)
-        {
-            if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true, 2>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((preproc_tiles<uint16_t, true, 2>), grid, block, 0, st, a);
-        }
-        else if (a.fmt == kFmtNV12) hipLaunchKernelGGL((preproc_tiles<uint8_t, true>), grid, block, 0, st, a);
-        else if (a.fmt == kFmtP010) hipLaunchKernelGGL((preproc_tiles<uint16_t, true>), grid, block, 0, st, a);
+        if (fmt_is_yuv(a.fmt))
+            with_sample_type(a.fmt, [&](auto src) {
+                with_siting(a.siting, [&](auto site) { hipLaunchKernelGGL((preproc_tiles<decltype(src), true, decltype(site)::value>), grid, block, 0, st, a); });
+            });
         else if (a.fmt == kFmtF16) hipLaunchKernelGGL(preproc_tiles<_Float16>, grid, block, 0, st, a);
         else if (a.fmt == kFmtF32) hipLaunchKernelGGL(preproc_tiles<float>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(preproc_tiles<uint8_t>, grid, block, 0, st, a);
@@ -393,6 +425,120 @@ __device__ __forceinline__ void cubic_coeffs(int w, int outw, int dx, int& sx, f
 
 __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
+// The bicubic x4 alpha value (0..255 units, not clamped) of a tile's kept rectangle -- realsr.cpp:431-442, realsr_preproc.comp:79-88 (crop),
+// realsr_postproc.comp:58-61 -- from the coefficient sets cubic_coeffs made for its column (bx, cx) and row (by, cy): four rows of four
+// taps of the RGBA source image, indices clamped to the rectangle.  postproc_tiles, postproc_tiles_lds, postproc_tiles_box and
+// postproc_tiles_area; a kernel that needs one row's coefficients for several pixels makes them once, at its call site.
+__device__ __forceinline__ float alpha_bicubic(const PostArgs& a, const BaseTile& t, int im, int bx, const float (&cx)[4], int by, const float (&cy)[4])
+{
+    const int aw = t.out_w / 4, ah = t.out_h / 4;
+    const int ax0 = t.out_x / 4, ay0 = t.out_y / 4;
+    float rows[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+    {
+        const int yy = ay0 + clampi(by - 1 + j, ah);
+        const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
+        rows[j] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
+                  (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
+    }
+    return rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
+}
+
+// K contiguous blob elements, K-element aligned: ONE 4- / 8-byte (fp16) or 8- / 16-byte (fp32) load.
+template <typename TP, int K>
+__device__ __forceinline__ void load_run(const TP* p, float (&o)[K])
+{
+    typedef TP vec __attribute__((ext_vector_type(K)));
+    const vec v = *reinterpret_cast<const vec*>(p);
+#pragma unroll
+    for (int i = 0; i < K; i++) o[i] = (float)v[i];
+}
+
+// The K x K block of x4 pixels at (sx, sy) of one channel's blob b (w x h, the TTA variants ss elements apart): under TTA the eight
+// variants merged as realsr_postproc_tta.comp:76-85 does, (v0 + v1 + ... + v7) * 0.125f in this order.  The only place that knows the
+// eight source addresses.  sx and the row length are multiples of K: every run of K elements is ONE load (load_run) -- also in the
+// mirrored variants (the run is read backwards) and in the TRANSPOSED ones, where a run lies along y.  postproc_tiles (K = 1), and
+// through merged_block every box, area and YUV kernel; postproc_tiles_lds stages the transposed variants in LDS instead.
+template <typename TP, int K>
+__device__ __forceinline__ void tta_gather(const TP* b, long long ss, int w, int h, int sx, int sy, int tta, float (&c)[K][K])
+{
+    float r[K];
+#pragma unroll
+    for (int j = 0; j < K; j++)
+    {
+        load_run<TP, K>(b + (long long)(sy + j) * w + sx, r);
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] = r[i];
+    }
+    if (!tta) return;
+#pragma unroll
+    for (int j = 0; j < K; j++)
+    {
+        load_run<TP, K>(b + ss + (long long)(sy + j) * w + (w - K - sx), r);
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++)
+    {
+        load_run<TP, K>(b + 2 * ss + (long long)(h - 1 - sy - j) * w + (w - K - sx), r);
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++)
+    {
+        load_run<TP, K>(b + 3 * ss + (long long)(h - 1 - sy - j) * w + sx, r);
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] += r[i];
+    }
+#pragma unroll
+    for (int i = 0; i < K; i++)
+    {
+        load_run<TP, K>(b + 4 * ss + (long long)(sx + i) * h + sy, r);
+#pragma unroll
+        for (int j = 0; j < K; j++) c[j][i] += r[j];
+    }
+#pragma unroll
+    for (int i = 0; i < K; i++)
+    {
+        load_run<TP, K>(b + 5 * ss + (long long)(sx + i) * h + (h - K - sy), r);
+#pragma unroll
+        for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
+    }
+#pragma unroll
+    for (int i = 0; i < K; i++)
+    {
+        load_run<TP, K>(b + 6 * ss + (long long)(w - 1 - sx - i) * h + (h - K - sy), r);
+#pragma unroll
+        for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
+    }
+#pragma unroll
+    for (int i = 0; i < K; i++)
+    {
+        load_run<TP, K>(b + 7 * ss + (long long)(w - 1 - sx - i) * h + sy, r);
+#pragma unroll
+        for (int j = 0; j < K; j++) c[j][i] += r[j];
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++)
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] *= 0.125f;
+}
+
+// tta_gather's block clamped to [0, 1]: the x4 pixels every reduced output is made of (postproc_tiles_box, postproc_tiles_area through
+// area_pixel, and the two YUV kernels).
+template <typename TP, int K>
+__device__ __forceinline__ void merged_block(const TP* b, long long ss, int w, int h, int sx, int sy, int tta, float (&c)[K][K])
+{
+    tta_gather<TP, K>(b, ss, w, h, sx, sy, tta, c);
+#pragma unroll
+    for (int j = 0; j < K; j++)
+#pragma unroll
+        for (int i = 0; i < K; i++) c[j][i] = fminf(fmaxf(c[j][i], 0.f), 1.f);
+}
+
 // realsr_postproc.comp:47-89 and realsr_postproc_tta.comp:54-110 for a batch of tiles.
 // One thread per output pixel of the tile's un-padded x4 rectangle.
 // TP: element type of the planar blob: _Float16 (the reference's `output` blob) or float (precise mode)
@@ -407,31 +553,23 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
     if (gx >= t.out_w || gy >= t.out_h) return;
     const int w = t.tw * 4, h = t.th * 4;
     const long long cstep = (long long)w * h;
-    const int sx = gx + a.crop, sy = gy + a.crop;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    const int sx = gx + a.crop, sy = gy + a.crop;
     float v[3];
     if (!a.tta)
-    {
+    { // (a branch of its own: the three loads leave together, with no test of a.tta between them)
 #pragma unroll
         for (int q = 0; q < 3; q++) v[q] = (float)b0[q * cstep + (long long)sy * w + sx];
     }
     else
     {
-        const long long ss = a.slot_stride / (long long)sizeof(TP);
 #pragma unroll
         for (int q = 0; q < 3; q++)
         {
-            const TP* b = b0 + q * cstep;
-            // realsr_postproc_tta.comp:76-85
-            const float v0 = (float)b[(long long)sy * w + sx];
-            const float v1 = (float)b[ss + (long long)sy * w + (w - 1 - sx)];
-            const float v2 = (float)b[2 * ss + (long long)(h - 1 - sy) * w + (w - 1 - sx)];
-            const float v3 = (float)b[3 * ss + (long long)(h - 1 - sy) * w + sx];
-            const float v4 = (float)b[4 * ss + (long long)sx * h + sy];
-            const float v5 = (float)b[5 * ss + (long long)sx * h + (h - 1 - sy)];
-            const float v6 = (float)b[6 * ss + (long long)(w - 1 - sx) * h + (h - 1 - sy)];
-            const float v7 = (float)b[7 * ss + (long long)(w - 1 - sx) * h + sy];
-            v[q] = (v0 + v1 + v2 + v3 + v4 + v5 + v6 + v7) * 0.125f;
+            float c[1][1];
+            tta_gather<TP, 1>(b0 + q * cstep, ss, w, h, sx, sy, 1, c);
+            v[q] = c[0][0];
         }
     }
     if constexpr (sizeof(TO) != 1)
@@ -447,25 +585,11 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
     o[a.bgr ? 0 : 2] = bl;
     if (a.c == 4)
     {
-        // alpha: bicubic x4 of the un-padded tile's alpha (0..255 units), realsr.cpp:431-442,
-        // realsr_preproc.comp:79-88 (crop), realsr_postproc.comp:58-61
-        const int aw = t.out_w / 4, ah = t.out_h / 4;
-        const int ax0 = t.out_x / 4, ay0 = t.out_y / 4;
         int bx, by;
         float cx[4], cy[4];
-        cubic_coeffs(aw, t.out_w, gx, bx, cx);
-        cubic_coeffs(ah, t.out_h, gy, by, cy);
-        float rows[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-        {
-            const int yy = ay0 + clampi(by - 1 + j, ah);
-            const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
-            rows[j] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
-                      (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
-        }
-        const float av = rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
-        o[3] = post_store(av);
+        cubic_coeffs(t.out_w / 4, t.out_w, gx, bx, cx);
+        cubic_coeffs(t.out_h / 4, t.out_h, gy, by, cy);
+        o[3] = post_store(alpha_bicubic(a, t, im, bx, cx, by, cy));
     }
 }
 
@@ -568,24 +692,12 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
         o[1] = post_store(v[1] * 255.f);
         o[a.bgr ? 0 : 2] = post_store(v[2] * 255.f);
         if (a.c == 4)
-        { // alpha: bicubic x4 of the un-padded tile's alpha, exactly as in postproc_tiles
-            const int gx = gx0 + lx, gy = gy0 + gyl;
-            const int aw = t.out_w / 4, ah = t.out_h / 4;
-            const int ax0 = t.out_x / 4, ay0 = t.out_y / 4;
+        {
             int bx, by;
             float cx[4], cy[4];
-            cubic_coeffs(aw, t.out_w, gx, bx, cx);
-            cubic_coeffs(ah, t.out_h, gy, by, cy);
-            float rows[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-            {
-                const int yy = ay0 + clampi(by - 1 + j, ah);
-                const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
-                rows[j] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
-                          (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
-            }
-            o[3] = post_store(rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3]);
+            cubic_coeffs(t.out_w / 4, t.out_w, gx0 + lx, bx, cx);
+            cubic_coeffs(t.out_h / 4, t.out_h, gy0 + gyl, by, cy);
+            o[3] = post_store(alpha_bicubic(a, t, im, bx, cx, by, cy));
         }
     }
     if constexpr (sizeof(TO) != 1) return;
@@ -600,16 +712,6 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
 }
 
 // ---- box-reduced output (engine option "out_scale" 2 / 1: PostArgs::box = K = 2 / 4) ----------------------------------------
-// K contiguous blob elements, K-element aligned: ONE 4- / 8-byte (fp16) or 8- / 16-byte (fp32) load.
-template <typename TP, int K>
-__device__ __forceinline__ void load_run(const TP* p, float (&o)[K])
-{
-    typedef TP vec __attribute__((ext_vector_type(K)));
-    const vec v = *reinterpret_cast<const vec*>(p);
-#pragma unroll
-    for (int i = 0; i < K; i++) o[i] = (float)v[i];
-}
-
 // The fp32 mean of a K x K box c[y][x] in the fixed order of include/realsr_hip.h ("out_scale"): pairs along x, then pairs of rows.
 // Plain adds and one multiplication by a power of two behind them: nothing a contraction could change.
 template <int K>
@@ -629,8 +731,7 @@ __device__ __forceinline__ float box_mean(const float (&c)[K][K])
 // pixels min(max(r, 0), 1), r what postproc_tiles converts (TTA: the eight variants merged first, in the shader's order).  A tile's
 // kept x4 rectangle starts and ends on multiples of 4 (BaseTile::out_*), so no box crosses a tile; BaseTile stays in x4 units and is
 // divided by K here.  Lanes run along x.  The K elements a thread needs of a blob row are contiguous and K-aligned (crop, the row
-// length 4 * tw and the plane size are multiples of 4): one load each (load_run) -- also in the mirrored variants (the run is read
-// backwards) and in the TRANSPOSED ones, where a thread's run lies along y and it reads K of them.
+// length 4 * tw and the plane size are multiples of 4): merged_block fetches each run with one load.
 // ALPHA: the uint8 image is RGBA (PostArgs::c == 4; a kernel of its own: the bicubic's registers stay out of the RGB path).
 template <typename TP, typename TO, int K, bool ALPHA>
 __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
@@ -650,75 +751,8 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
 #pragma unroll 1 // (one channel at a time: unrolled, the loads of all three are hoisted to the top and cost three times the registers)
     for (int q = 0; q < 3; q++)
     {
-        const TP* b = b0 + q * cstep;
-        float c[K][K], r[K];
-#pragma unroll
-        for (int j = 0; j < K; j++)
-        {
-            load_run<TP, K>(b + (long long)(sy + j) * w + sx, r);
-#pragma unroll
-            for (int i = 0; i < K; i++) c[j][i] = r[i];
-        }
-        if (a.tta)
-        { // realsr_postproc_tta.comp:76-85: (v0 + v1 + ... + v7) * 0.125f, in this order
-#pragma unroll
-            for (int j = 0; j < K; j++)
-            {
-                load_run<TP, K>(b + ss + (long long)(sy + j) * w + (w - K - sx), r);
-#pragma unroll
-                for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
-            }
-#pragma unroll
-            for (int j = 0; j < K; j++)
-            {
-                load_run<TP, K>(b + 2 * ss + (long long)(h - 1 - sy - j) * w + (w - K - sx), r);
-#pragma unroll
-                for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
-            }
-#pragma unroll
-            for (int j = 0; j < K; j++)
-            {
-                load_run<TP, K>(b + 3 * ss + (long long)(h - 1 - sy - j) * w + sx, r);
-#pragma unroll
-                for (int i = 0; i < K; i++) c[j][i] += r[i];
-            }
-#pragma unroll
-            for (int i = 0; i < K; i++)
-            {
-                load_run<TP, K>(b + 4 * ss + (long long)(sx + i) * h + sy, r);
-#pragma unroll
-                for (int j = 0; j < K; j++) c[j][i] += r[j];
-            }
-#pragma unroll
-            for (int i = 0; i < K; i++)
-            {
-                load_run<TP, K>(b + 5 * ss + (long long)(sx + i) * h + (h - K - sy), r);
-#pragma unroll
-                for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
-            }
-#pragma unroll
-            for (int i = 0; i < K; i++)
-            {
-                load_run<TP, K>(b + 6 * ss + (long long)(w - 1 - sx - i) * h + (h - K - sy), r);
-#pragma unroll
-                for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
-            }
-#pragma unroll
-            for (int i = 0; i < K; i++)
-            {
-                load_run<TP, K>(b + 7 * ss + (long long)(w - 1 - sx - i) * h + sy, r);
-#pragma unroll
-                for (int j = 0; j < K; j++) c[j][i] += r[j];
-            }
-#pragma unroll
-            for (int j = 0; j < K; j++)
-#pragma unroll
-                for (int i = 0; i < K; i++) c[j][i] *= 0.125f;
-        }
-#pragma unroll
-        for (int j = 0; j < K; j++)
-#pragma unroll
-            for (int i = 0; i < K; i++) c[j][i] = fminf(fmaxf(c[j][i], 0.f), 1.f);
+        float c[K][K];
+        merged_block<TP, K>(b0 + q * cstep, ss, w, h, sx, sy, a.tta, c);
         const float d = box_mean<K>(c); // in [0, 1] like its sixteen / four terms
         const int qo = a.bgr ? 2 - q : q;
         if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)d;
@@ -726,8 +760,6 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
     }
     if constexpr (ALPHA)
     { // alpha: the box mean of postproc_tiles' bicubic x4 value, each clamped to [0, 255] first; two box rows per turn: (s0 + s1) [+ (s2 + s3)]
-        const int aw = t.out_w / 4, ah = t.out_h / 4;
-        const int ax0 = t.out_x / 4, ay0 = t.out_y / 4;
         float tot = 0.f;
 #pragma unroll 1
         for (int p = 0; p < K / 2; p++)
@@ -739,23 +771,14 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
                 float al[K];
                 int by;
                 float cy[4];
-                cubic_coeffs(ah, t.out_h, gy * K + 2 * p + jj2, by, cy); // (of the row alone: once per box row, not per pixel)
+                cubic_coeffs(t.out_h / 4, t.out_h, gy * K + 2 * p + jj2, by, cy); // (of the row alone: once per box row, not per pixel)
 #pragma unroll
                 for (int i = 0; i < K; i++)
                 {
                     int bx;
                     float cx[4];
-                    cubic_coeffs(aw, t.out_w, gx * K + i, bx, cx);
-                    float rows[4];
-#pragma unroll
-                    for (int jj = 0; jj < 4; jj++)
-                    {
-                        const int yy = ay0 + clampi(by - 1 + jj, ah);
-                        const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
-                        rows[jj] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
-                                   (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
-                    }
-                    const float av = rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
+                    cubic_coeffs(t.out_w / 4, t.out_w, gx * K + i, bx, cx);
+                    const float av = alpha_bicubic(a, t, im, bx, cx, by, cy);
                     al[i] = fminf(fmaxf(av, 0.f), 255.f);
                 }
                 if constexpr (K == 2) s2[jj2] = al[0] + al[1];
@@ -778,83 +801,112 @@ static void launch_postproc_box(const PostArgs& a, int max_ow, int max_oh, hipSt
     else hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, false>), grid, block, 0, st, a);
 }
 
-// ---- YUV 4:2:0 output (PostArgs::out_fmt kFmtNV12 / kFmtP010) ----------------------------------------------------------------------
-// The K x K block of x4 pixels at (sx, sy) of one channel's blob, as postproc_tiles_box gathers it: the eight TTA variants merged in the
-// shader's order, then clamped to [0, 1].  sx and the row length are multiples of K: every run of K elements is ONE load.  (A copy of that
-// kernel's gather rather than a function shared with it: the box kernel stays, instruction for instruction, what it was measured as.)
-template <typename TP, int K>
-__device__ __forceinline__ void merged_block(const TP* b, long long ss, int w, int h, int sx, int sy, int tta, float (&c)[K][K])
+// ---- area-averaged output at a rational scale (rsr_set_out_ratio: PostArgs::num / den, e.g. 3/2, 4/3, 9/4, 3/1) -------------------------
+// The area-average loop nest of output pixel (X, Y) of a tile's rectangle at the scale n / d, L = 4 d.  On the integer grid where x4
+// pixel i covers [i n, (i + 1) n) and output pixel X covers [X L, (X + 1) L), its taps along an axis are i = floor(X L / n) ..
+// floor(((X + 1) L - 1) / n) -- at most 4 -- with the integer weights g_i = the overlap, which sum to L.  include/realsr_hip.h
+// (rsr_set_out_ratio) fixes the arithmetic: horizontally H = g c, H = H + g c in ascending i, then vertically the same over the rows' H,
+// every product and sum rounded by itself.  row(j), called once per tap row, returns that row's tap function: tap(i) is the value c of
+// x4 pixel (i, j) of the tile's kept rectangle.  The caller multiplies the sum V it gets by fp32(1 / (16 d^2)).
+// The ratio is a runtime argument: the tap loops have no arrays to index, so nothing is gained by unrolling them per ratio.
+// Used by area_pixel (colour) and by postproc_tiles_area's alpha.
+template <typename ROW>
+__device__ __forceinline__ float area_sum(int n, int L, int X, int Y, ROW row)
 {
-    float r[K];
-#pragma unroll
-    for (int j = 0; j < K; j++)
+    const int x0 = X * L, x1 = x0 + L, y0 = Y * L, y1 = y0 + L;                   // the pixel's footprint on the grid
+    const int ix0 = x0 / n, ix1 = (x1 - 1) / n, iy0 = y0 / n, iy1 = (y1 - 1) / n; // its taps
+    float V = 0.f;
+#pragma unroll 1
+    for (int j = iy0; j <= iy1; j++)
     {
-        load_run<TP, K>(b + (long long)(sy + j) * w + sx, r);
-#pragma unroll
-        for (int i = 0; i < K; i++) c[j][i] = r[i];
+        const auto tap = row(j);
+        float H = 0.f;
+#pragma unroll 1
+        for (int i = ix0; i <= ix1; i++)
+        {
+            const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), tap(i));
+            H = i == ix0 ? p : add_rn(H, p);
+        }
+        const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
+        V = j == iy0 ? p : add_rn(V, p);
     }
-    if (tta)
-    { // realsr_postproc_tta.comp:76-85: (v0 + v1 + ... + v7) * 0.125f, in this order
-#pragma unroll
-        for (int j = 0; j < K; j++)
-        {
-            load_run<TP, K>(b + ss + (long long)(sy + j) * w + (w - K - sx), r);
-#pragma unroll
-            for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
-        }
-#pragma unroll
-        for (int j = 0; j < K; j++)
-        {
-            load_run<TP, K>(b + 2 * ss + (long long)(h - 1 - sy - j) * w + (w - K - sx), r);
-#pragma unroll
-            for (int i = 0; i < K; i++) c[j][i] += r[K - 1 - i];
-        }
-#pragma unroll
-        for (int j = 0; j < K; j++)
-        {
-            load_run<TP, K>(b + 3 * ss + (long long)(h - 1 - sy - j) * w + sx, r);
-#pragma unroll
-            for (int i = 0; i < K; i++) c[j][i] += r[i];
-        }
-#pragma unroll
-        for (int i = 0; i < K; i++)
-        {
-            load_run<TP, K>(b + 4 * ss + (long long)(sx + i) * h + sy, r);
-#pragma unroll
-            for (int j = 0; j < K; j++) c[j][i] += r[j];
-        }
-#pragma unroll
-        for (int i = 0; i < K; i++)
-        {
-            load_run<TP, K>(b + 5 * ss + (long long)(sx + i) * h + (h - K - sy), r);
-#pragma unroll
-            for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
-        }
-#pragma unroll
-        for (int i = 0; i < K; i++)
-        {
-            load_run<TP, K>(b + 6 * ss + (long long)(w - 1 - sx - i) * h + (h - K - sy), r);
-#pragma unroll
-            for (int j = 0; j < K; j++) c[j][i] += r[K - 1 - j];
-        }
-#pragma unroll
-        for (int i = 0; i < K; i++)
-        {
-            load_run<TP, K>(b + 7 * ss + (long long)(w - 1 - sx - i) * h + sy, r);
-#pragma unroll
-            for (int j = 0; j < K; j++) c[j][i] += r[j];
-        }
-#pragma unroll
-        for (int j = 0; j < K; j++)
-#pragma unroll
-            for (int i = 0; i < K; i++) c[j][i] *= 0.125f;
-    }
-#pragma unroll
-    for (int j = 0; j < K; j++)
-#pragma unroll
-        for (int i = 0; i < K; i++) c[j][i] = fminf(fmaxf(c[j][i], 0.f), 1.f);
+    return V;
 }
 
+// ONE pixel d(X, Y) of a tile's output rectangle at the scale n / d of one channel's blob -- what RSR_FMT_F32_CHW holds for it: every tap
+// clamped to [0, 1] (TTA: the eight variants merged first), fetched one at a time through merged_block<TP, 1>, and m = min(V * norm, 1).
+// (X, Y) are the tile's own coordinates, which are the image's.  postproc_tiles_area and postproc_tiles_yuv_area.
+template <typename TP>
+__device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, int h, int crop, int tta, int n, int L, float norm, int X, int Y)
+{
+    const float V = area_sum(n, L, X, Y, [&](int j) {
+        return [&, j](int i) {
+            float c[1][1];
+            merged_block<TP, 1>(b, ss, w, h, i + crop, j + crop, tta, c);
+            return c[0][0];
+        };
+    });
+    return fminf(mul_rn(V, norm), 1.f);
+}
+
+// The sibling of postproc_tiles_box for the scales n / d that are not 4, 2 or 1: one thread makes ONE output pixel (X, Y) of the tile's
+// rectangle, area_pixel per channel.  A tile's kept x4 rectangle starts on a multiple of L grid units (the engine refuses the call
+// otherwise: tilesize * n is a multiple of d), so the tile's own coordinates are the image's and no footprint crosses a tile.  Lanes run
+// along x, so a wave's loads of one tap row fall into a few cache lines.  One channel at a time, as in the box kernel.
+// ALPHA: PostArgs::c == 4, the bicubic x4 alpha, clamped to [0, 255], under the same weights, order and constant.
+template <typename TP, typename TO, bool ALPHA>
+__global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
+{
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int n = a.num, L = 4 * a.den;
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= t.out_w * n / L || gy >= t.out_h * n / L) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const long long cstep = (long long)w * h;
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    constexpr int es = sizeof(TO) == 1 ? 1 : (int)sizeof(TO);
+    uint8_t* const o = a.outs[im] + ((long long)(t.out_y - a.out_row0) * n / L + gy) * (long long)a.out_pitch[im] +
+                       ((long long)t.out_x * n / L + gx) * (sizeof(TO) == 1 ? a.c : es);
+#pragma unroll 1
+    for (int q = 0; q < 3; q++)
+    {
+        const float m = area_pixel<TP>(b0 + q * cstep, ss, w, h, a.crop, a.tta, n, L, a.area_norm, gx, gy);
+        const int qo = a.bgr ? 2 - q : q;
+        if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)m;
+        else o[qo] = post_store(m * 255.f);
+    }
+    if constexpr (ALPHA)
+    {
+        const float V = area_sum(n, L, gx, gy, [&](int j) {
+            int by;
+            float cy[4];
+            cubic_coeffs(t.out_h / 4, t.out_h, j, by, cy);
+            return [&, by, cy](int i) {
+                int bx;
+                float cx[4];
+                cubic_coeffs(t.out_w / 4, t.out_w, i, bx, cx);
+                return fminf(fmaxf(alpha_bicubic(a, t, im, bx, cx, by, cy), 0.f), 255.f);
+            };
+        });
+        o[3] = post_store(mul_rn(V, a.area_norm));
+    }
+}
+
+template <typename TP>
+static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    const int L = 4 * a.den;
+    const dim3 grid((max_ow * a.num / L + 63) / 64, (max_oh * a.num / L + 3) / 4, a.ntiles), block(256);
+    if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_area<TP, _Float16, false>), grid, block, 0, st, a);
+    else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_area<TP, float, false>), grid, block, 0, st, a);
+    else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
+}
+
+// ---- YUV 4:2:0 output (PostArgs::out_fmt kFmtNV12 / kFmtP010) ----------------------------------------------------------------------
 // code = floor(v * scale + add) clamped to [0, maxcode] (add = offset + 0.5f), as the sample type stores it: P010 keeps it in the high bits
 template <typename TO>
 __device__ __forceinline__ unsigned yuv_code(float v, float scale, float add, float maxcode)
@@ -880,8 +932,8 @@ __device__ __forceinline__ void store_pair(uint8_t* o, unsigned lo, unsigned hi)
 }
 
 // ONE pixel d of the context's out_scale image (K = 4 / out_scale x4 pixels per axis; (px, py) its first x4 pixel in the blob, K-aligned):
-// the K x K block gathered by merged_block and box-reduced in the order of include/realsr_hip.h ("out_scale") -- the value the quad
-// kernel below computes for the pixels of its own quad, for the neighbours the sited chroma filters need.
+// the K x K block gathered by merged_block and box-reduced in the order of include/realsr_hip.h ("out_scale") -- what RSR_FMT_F32_CHW
+// holds for it.  QuadBox::at.
 template <typename TP, int K>
 __device__ __forceinline__ float out_pixel(const TP* b, long long ss, int w, int h, int px, int py, int tta)
 {
@@ -892,51 +944,26 @@ __device__ __forceinline__ float out_pixel(const TP* b, long long ss, int w, int
     else return box_mean<4>(c);
 }
 
-// The YUV 4:2:0 sibling of postproc_tiles_box: one thread makes ONE 2 x 2 quad of luma samples and the (U, V) pair they share, at the
-// context's out_scale OS (4, 2 or 1: K = 4 / OS x4 pixels per output pixel and axis).  d, the RGB value of an output pixel, is what
-// RSR_FMT_F32_CHW holds for it -- x4 pixels TTA-merged, clamped and box-reduced exactly as in postproc_tiles / postproc_tiles_box --
-// and include/realsr_hip.h ("yuv_matrix") defines the rest: Y' = (kr R + kg G) + kb B per pixel; chroma from the mean m of the quad,
-// ((d00 + d01) + (d10 + d11)) * 0.25f per channel.  One channel at a time (the loads of three would cost three times the registers): Y'
-// is accumulated across the channel loop, 0 + kr R being kr R exactly (d >= 0).  A tile's rectangle starts and ends on even output pixels
-// (the engine refuses an out_scale 1 call where it would not), so no quad crosses a tile.  Lanes run along x.
-// TP: element type of the blob (_Float16, or float in precise mode); TO: sample type of the surface, uint8_t (NV12) or uint16_t (P010).
-//
-// SITE (PostArgs::siting, option "yuv_siting"): 0 = chroma at the centre of the quad, as above.  1 (left) / 2 (top-left): chroma co-sited
-// with the quad's first column / first pixel -- include/realsr_hip.h "Chroma siting": per channel Hs(y) = (d(xl, y) + d(2X+1, y)) +
-// (d(2X, y) + d(2X, y)), the unnormalised [1 2 1] filter about column 2X, and m = (Hs(2Y) + Hs(2Y+1)) * 0.125f (left) or ((Hs(yu) +
-// Hs(2Y+1)) + (Hs(2Y) + Hs(2Y))) * 0.0625f (top-left), xl = 2X - 1 and yu = 2Y - 1 -- or 2X / 2Y in the first quad column / row of the
-// TILE's rectangle (gx == 0 / gy == 0): the pixel beyond belongs to another tile's blob.  Luma does not change.  The neighbours d(2X-1, .)
-// and d(., 2Y-1) are pixels of this tile's own kept rectangle, gathered like every other d -- merged_block<TP, K> at (sx - K, .) /
-// (., sy - K), K-aligned like sx and sy -- by the thread itself: redundant with the lane beside it / the wave above it, served by the
-// caches, and free of any cross-lane dependence on threads that have returned.  At a tile-first column / row the address is the pixel's
-// own (lx == sx): the same loads, the same arithmetic, hence bitwise d(2X, .) / d(., 2Y) with no divergent branch.
-template <typename TP, typename TO, int OS, int SITE = 0>
-__global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
+// Where yuv_quad takes the RGB value d of an output pixel from, b the channel's blob -- what RSR_FMT_F32_CHW holds for that pixel: quad(b, d)
+// = the four d of the thread's 2 x 2 quad, at(b, ox, oy) = ONE d, ox / oy output pixels beside the quad's first; out(v) = a length v of the
+// x4 image in output pixels.
+// QuadBox: out_scale OS = 4, 2 or 1 (K = 4 / OS x4 pixels per output pixel and axis; (sx, sy) the quad's first x4 pixel in the blob).
+// The quad is the 2K x 2K block in one or four merged_block fetches; a neighbour is out_pixel at (sx + K ox, sy + K oy), K-aligned like
+// sx and sy.
+template <typename TP, int OS>
+struct QuadBox
 {
-    constexpr int K = 4 / OS, Q = 2 * K; // x4 pixels per output pixel / per quad, along an axis
-    const BaseTile t = a.tiles[blockIdx.z];
-    const int im = __builtin_amdgcn_readfirstlane(t.img);
-    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (gx >= t.out_w / Q || gy >= t.out_h / Q) return;
-    const int w = t.tw * 4, h = t.th * 4;
-    const long long cstep = (long long)w * h;
-    const int sx = gx * Q + a.crop, sy = gy * Q + a.crop; // first x4 pixel of the quad, in the blob
-    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
-    const long long ss = a.slot_stride / (long long)sizeof(TP);
-    const YuvCoef& k = a.yuv;
-    float yq[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, ym = 0.f, rm = 0.f, bm = 0.f;
-#pragma unroll 1
-    for (int q = 0; q < 3; q++)
+    static constexpr int K = 4 / OS;
+    long long ss;
+    int w, h, sx, sy, tta;
+    __device__ __forceinline__ void quad(const TP* b, float (&d)[2][2]) const
     {
-        const TP* b = b0 + q * cstep;
-        float d[2][2];
         if constexpr (OS == 4)
-            merged_block<TP, 2>(b, ss, w, h, sx, sy, a.tta, d);
+            merged_block<TP, 2>(b, ss, w, h, sx, sy, tta, d);
         else if constexpr (OS == 2)
         {
             float c[4][4];
-            merged_block<TP, 4>(b, ss, w, h, sx, sy, a.tta, c);
+            merged_block<TP, 4>(b, ss, w, h, sx, sy, tta, c);
 #pragma unroll
             for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -951,25 +978,76 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
                 for (int i = 0; i < 2; i++)
                 {
                     float c[4][4];
-                    merged_block<TP, 4>(b, ss, w, h, sx + 4 * i, sy + 4 * j, a.tta, c);
+                    merged_block<TP, 4>(b, ss, w, h, sx + 4 * i, sy + 4 * j, tta, c);
                     d[j][i] = box_mean<4>(c);
                 }
         }
+    }
+    __device__ __forceinline__ float at(const TP* b, int ox, int oy) const { return out_pixel<TP, K>(b, ss, w, h, sx + K * ox, sy + K * oy, tta); }
+    __device__ __forceinline__ int out(int v) const { return v / K; }
+};
+
+// QuadArea: any other ratio n / d (rsr_set_out_ratio); (px, py) the quad's first output pixel in the tile's rectangle.  Every d is
+// area_pixel.  Every tap index stays inside the tile's kept rectangle as in postproc_tiles_area: X < out_w n / L gives
+// ((X + 1) L - 1) / n <= out_w - 1.
+template <typename TP>
+struct QuadArea
+{
+    long long ss;
+    int w, h, crop, tta, n, L;
+    float norm;
+    int px, py;
+    __device__ __forceinline__ void quad(const TP* b, float (&d)[2][2]) const
+    {
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int i = 0; i < 2; i++) d[j][i] = at(b, i, j);
+    }
+    __device__ __forceinline__ float at(const TP* b, int ox, int oy) const { return area_pixel<TP>(b, ss, w, h, crop, tta, n, L, norm, px + ox, py + oy); }
+    __device__ __forceinline__ int out(int v) const { return v * n / L; }
+};
+
+// ONE 2 x 2 quad of luma samples and the (U, V) pair they share, quad (gx, gy) of tile t's rectangle: what a thread of
+// postproc_tiles_yuv and postproc_tiles_yuv_area does behind its source `src` of RGB values d (QuadBox / QuadArea; b0 the blob of
+// channel 0, the channels cstep elements apart).  include/realsr_hip.h ("yuv_matrix") defines it: Y' = (kr R + kg G) + kb B per pixel;
+// chroma from the mean m of the quad, ((d00 + d01) + (d10 + d11)) * 0.25f per channel.  One channel at a time (the loads of three would
+// cost three times the registers): Y' is accumulated across the channel loop, 0 + kr R being kr R exactly (d >= 0).
+//
+// SITE (PostArgs::siting, option "yuv_siting"): 0 = chroma at the centre of the quad, as above.  1 (left) / 2 (top-left): chroma co-sited
+// with the quad's first column / first pixel -- include/realsr_hip.h "Chroma siting": per channel Hs(y) = (d(xl, y) + d(2X+1, y)) +
+// (d(2X, y) + d(2X, y)), the unnormalised [1 2 1] filter about column 2X, and m = (Hs(2Y) + Hs(2Y+1)) * 0.125f (left) or ((Hs(yu) +
+// Hs(2Y+1)) + (Hs(2Y) + Hs(2Y))) * 0.0625f (top-left), xl = 2X - 1 and yu = 2Y - 1 -- or 2X / 2Y in the first quad column / row of the
+// TILE's rectangle (gx == 0 / gy == 0): the pixel beyond belongs to another tile's blob.  Luma does not change.  The neighbours
+// d(2X-1, .) and d(., 2Y-1) are pixels of this tile's own kept rectangle, gathered like every other d by the thread itself: redundant with
+// the lane beside it / the wave above it, served by the caches, and free of any cross-lane dependence on threads that have returned.  At
+// a tile-first column / row the offset is 0, the pixel's own: the same loads, the same arithmetic, hence bitwise d(2X, .) / d(., 2Y) with
+// no divergent branch.
+template <typename TO, int SITE, typename SRC, typename TP>
+__device__ __forceinline__ void yuv_quad(const PostArgs& a, const BaseTile& t, int im, int gx, int gy, const SRC& src, const TP* b0, long long cstep)
+{
+    const YuvCoef& k = a.yuv;
+    float yq[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, ym = 0.f, rm = 0.f, bm = 0.f;
+#pragma unroll 1
+    for (int q = 0; q < 3; q++)
+    {
+        const TP* b = b0 + q * cstep;
+        float d[2][2];
+        src.quad(b, d);
         const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
         float m;
         if constexpr (SITE == 0) m = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
         else
         {
-            const int lx = sx - (gx ? K : 0), uy = sy - (gy ? K : 0); // x4 position of output column xl / row yu
+            const int xl = gx ? -1 : 0, yu = gy ? -1 : 0; // output column xl / row yu, relative to the quad's first pixel
             float hs[2];
 #pragma unroll
-            for (int j = 0; j < 2; j++)
-                hs[j] = add_rn(add_rn(out_pixel<TP, K>(b, ss, w, h, lx, sy + K * j, a.tta), d[j][1]), add_rn(d[j][0], d[j][0]));
+            for (int j = 0; j < 2; j++) hs[j] = add_rn(add_rn(src.at(b, xl, j), d[j][1]), add_rn(d[j][0], d[j][0]));
             if constexpr (SITE == 1) m = mul_rn(add_rn(hs[0], hs[1]), 0.125f);
             else
             {
-                const float u0 = out_pixel<TP, K>(b, ss, w, h, sx, uy, a.tta);
-                const float hu = add_rn(add_rn(out_pixel<TP, K>(b, ss, w, h, lx, uy, a.tta), out_pixel<TP, K>(b, ss, w, h, sx + K, uy, a.tta)), add_rn(u0, u0));
+                const float u0 = src.at(b, 0, yu);
+                const float hu = add_rn(add_rn(src.at(b, xl, yu), src.at(b, 1, yu)), add_rn(u0, u0));
                 m = mul_rn(add_rn(add_rn(hu, hs[1]), add_rn(hs[0], hs[0])), 0.0625f);
             }
         }
@@ -982,7 +1060,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
         if (q == 2) bm = m;
     }
     const long long pitch = a.out_pitch[im];
-    const int X = t.out_x / K + 2 * gx, Y = (t.out_y - a.out_row0) / K + 2 * gy; // the quad's first luma sample
+    const int X = src.out(t.out_x) + 2 * gx, Y = src.out(t.out_y - a.out_row0) + 2 * gy; // the quad's first luma sample
     uint8_t* const oy = a.outs[im] + Y * pitch + (long long)X * (int)sizeof(TO);
 #pragma unroll
     for (int j = 0; j < 2; j++)
@@ -992,146 +1070,28 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
     store_pair<TO>(ouv, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
 }
 
-// ---- area-averaged output at a rational scale (rsr_set_out_ratio: PostArgs::num / den, e.g. 3/2, 4/3, 9/4, 3/1) -------------------------
-// The sibling of postproc_tiles_box for the scales n / d that are not 4, 2 or 1: one thread makes ONE output pixel (X, Y) of the tile's
-// rectangle.  On the integer grid where x4 pixel i covers [i n, (i + 1) n) and output pixel X covers [X L, (X + 1) L), L = 4 d, its taps
-// along an axis are i = floor(X L / n) .. floor(((X + 1) L - 1) / n) -- at most 4 -- with the integer weights g_i = the overlap, which sum
-// to L.  A tile's kept x4 rectangle starts on a multiple of L grid units (the engine refuses the call otherwise: tilesize * n is a multiple
-// of d), so the tile's own coordinates are the image's and no footprint crosses a tile.  include/realsr_hip.h (rsr_set_out_ratio) fixes the
-// arithmetic: every tap clamped to [0, 1] (TTA: the eight variants merged first), horizontally H = g c, H = H + g c in ascending i, then
-// vertically the same over the rows' H, every product and sum rounded by itself; m = min(V * fp32(1 / (16 d^2)), 1).
-// The ratio is a runtime argument: the tap loops have no arrays to index, so nothing is gained by unrolling them per ratio.  Taps are
-// fetched one at a time through merged_block<TP, 1>; lanes run along x, so a wave's loads of one tap row fall into a few cache lines.
-// One channel at a time, as in the box kernel.  ALPHA: PostArgs::c == 4, the bicubic x4 alpha under the same weights.
-template <typename TP, typename TO, bool ALPHA>
-__global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
+// The YUV 4:2:0 sibling of postproc_tiles_box: one thread makes ONE quad (yuv_quad over QuadBox) at the context's out_scale OS (4, 2 or
+// 1).  A tile's rectangle starts and ends on even output pixels (the engine refuses an out_scale 1 call where it would not), so no quad
+// crosses a tile.  Lanes run along x.
+// TP: element type of the blob (_Float16, or float in precise mode); TO: sample type of the surface, uint8_t (NV12) or uint16_t (P010).
+template <typename TP, typename TO, int OS, int SITE = 0>
+__global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
 {
+    constexpr int K = 4 / OS, Q = 2 * K; // x4 pixels per output pixel / per quad, along an axis
     const BaseTile t = a.tiles[blockIdx.z];
     const int im = __builtin_amdgcn_readfirstlane(t.img);
-    const int n = a.num, L = 4 * a.den;
     const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (gx >= t.out_w * n / L || gy >= t.out_h * n / L) return;
+    if (gx >= t.out_w / Q || gy >= t.out_h / Q) return;
     const int w = t.tw * 4, h = t.th * 4;
-    const long long cstep = (long long)w * h;
-    const int x0 = gx * L, x1 = x0 + L, y0 = gy * L, y1 = y0 + L;              // the pixel's footprint on the grid
-    const int ix0 = x0 / n, ix1 = (x1 - 1) / n, iy0 = y0 / n, iy1 = (y1 - 1) / n; // its taps: x4 pixels of the tile's kept rectangle
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
-    const long long ss = a.slot_stride / (long long)sizeof(TP);
-    constexpr int es = sizeof(TO) == 1 ? 1 : (int)sizeof(TO);
-    uint8_t* const o = a.outs[im] + ((long long)(t.out_y - a.out_row0) * n / L + gy) * (long long)a.out_pitch[im] +
-                       ((long long)t.out_x * n / L + gx) * (sizeof(TO) == 1 ? a.c : es);
-#pragma unroll 1
-    for (int q = 0; q < 3; q++)
-    {
-        const TP* b = b0 + q * cstep;
-        float V = 0.f;
-#pragma unroll 1
-        for (int j = iy0; j <= iy1; j++)
-        {
-            float H = 0.f;
-#pragma unroll 1
-            for (int i = ix0; i <= ix1; i++)
-            {
-                float c[1][1];
-                merged_block<TP, 1>(b, ss, w, h, i + a.crop, j + a.crop, a.tta, c);
-                const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), c[0][0]);
-                H = i == ix0 ? p : add_rn(H, p);
-            }
-            const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
-            V = j == iy0 ? p : add_rn(V, p);
-        }
-        const float m = fminf(mul_rn(V, a.area_norm), 1.f);
-        const int qo = a.bgr ? 2 - q : q;
-        if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)m;
-        else o[qo] = post_store(m * 255.f);
-    }
-    if constexpr (ALPHA)
-    { // alpha: postproc_tiles' bicubic x4 value at every tap, clamped to [0, 255], under the same weights, order and constant
-        const int aw = t.out_w / 4, ah = t.out_h / 4;
-        const int ax0 = t.out_x / 4, ay0 = t.out_y / 4;
-        float V = 0.f;
-#pragma unroll 1
-        for (int j = iy0; j <= iy1; j++)
-        {
-            int by;
-            float cy[4];
-            cubic_coeffs(ah, t.out_h, j, by, cy);
-            float H = 0.f;
-#pragma unroll 1
-            for (int i = ix0; i <= ix1; i++)
-            {
-                int bx;
-                float cx[4];
-                cubic_coeffs(aw, t.out_w, i, bx, cx);
-                float rows[4];
-#pragma unroll
-                for (int jj = 0; jj < 4; jj++)
-                {
-                    const int yy = ay0 + clampi(by - 1 + jj, ah);
-                    const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
-                    rows[jj] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
-                               (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
-                }
-                const float av = rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
-                const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), fminf(fmaxf(av, 0.f), 255.f));
-                H = i == ix0 ? p : add_rn(H, p);
-            }
-            const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
-            V = j == iy0 ? p : add_rn(V, p);
-        }
-        o[3] = post_store(mul_rn(V, a.area_norm));
-    }
+    const QuadBox<TP, OS> src{a.slot_stride / (long long)sizeof(TP), w, h, gx * Q + a.crop, gy * Q + a.crop, a.tta};
+    yuv_quad<TO, SITE>(a, t, im, gx, gy, src, b0, (long long)w * h);
 }
 
-template <typename TP>
-static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
-{
-    const int L = 4 * a.den;
-    const dim3 grid((max_ow * a.num / L + 63) / 64, (max_oh * a.num / L + 3) / 4, a.ntiles), block(256);
-    if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_area<TP, _Float16, false>), grid, block, 0, st, a);
-    else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_area<TP, float, false>), grid, block, 0, st, a);
-    else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
-}
-
-// ---- YUV 4:2:0 output at a rational scale (a surface format under rsr_set_out_ratio) -----------------------------------------------------
-// ONE pixel d(X, Y) of a tile's output rectangle at the scale n / d, L = 4 d, of one channel's blob: the value postproc_tiles_area stores
-// for RSR_FMT_F32_CHW -- the same taps, integer weights, order and constant (include/realsr_hip.h, rsr_set_out_ratio, steps 1 to 4), every
-// tap through merged_block<TP, 1>.  (X, Y) are the tile's own coordinates, which are the image's.  (A copy of that kernel's loop nest rather
-// than a function shared with it: the area kernel stays, instruction for instruction, what it was measured as.)
-template <typename TP>
-__device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, int h, int crop, int tta, int n, int L, float norm, int X, int Y)
-{
-    const int x0 = X * L, x1 = x0 + L, y0 = Y * L, y1 = y0 + L;                   // the pixel's footprint on the grid
-    const int ix0 = x0 / n, ix1 = (x1 - 1) / n, iy0 = y0 / n, iy1 = (y1 - 1) / n; // its taps: x4 pixels of the tile's kept rectangle
-    float V = 0.f;
-#pragma unroll 1
-    for (int j = iy0; j <= iy1; j++)
-    {
-        float H = 0.f;
-#pragma unroll 1
-        for (int i = ix0; i <= ix1; i++)
-        {
-            float c[1][1];
-            merged_block<TP, 1>(b, ss, w, h, i + crop, j + crop, tta, c);
-            const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), c[0][0]);
-            H = i == ix0 ? p : add_rn(H, p);
-        }
-        const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
-        V = j == iy0 ? p : add_rn(V, p);
-    }
-    return fminf(mul_rn(V, norm), 1.f);
-}
-
-// The sibling of postproc_tiles_yuv for the scales n / d that are not 4, 2 or 1: one thread makes ONE 2 x 2 quad of luma samples and the
-// (U, V) pair they share; d, the RGB value of an output pixel, is area_pixel -- what RSR_FMT_F32_CHW holds at that ratio -- and everything
-// behind d is postproc_tiles_yuv's: Y' accumulated across the channel loop, chroma from the quad mean (SITE 0) or the [1 2 1] filters about
-// the co-sited column / row (SITE 1 / 2), whose neighbours d(2X-1, .) / d(., 2Y-1) the thread gathers itself; in the first quad column / row
-// of the TILE's rectangle the neighbour's coordinate is the pixel's own (a select, no divergent branch), hence bitwise d(2X, .) / d(., 2Y).
-// A tile's rectangle is tilesize * n / d output pixels and starts at its multiples; the engine admits the call only where that, w * n / d
-// and h * n / d are even (check_yuv_out), so no quad crosses a tile or the image's edge.  Every tap index stays inside the tile's kept
-// rectangle as in postproc_tiles_area: X < out_w n / L gives ((X + 1) L - 1) / n <= out_w - 1.  Lanes run along x.
+// The sibling of postproc_tiles_yuv for the scales n / d that are not 4, 2 or 1: yuv_quad over QuadArea.  A tile's rectangle is
+// tilesize * n / d output pixels and starts at its multiples; the engine admits the call only where that, w * n / d and h * n / d are
+// even (check_yuv_out), so no quad crosses a tile or the image's edge.  Lanes run along x.
 template <typename TP, typename TO, int SITE>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
 {
@@ -1142,57 +1102,9 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
     const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (gx >= t.out_w * n / L / 2 || gy >= t.out_h * n / L / 2) return;
     const int w = t.tw * 4, h = t.th * 4;
-    const long long cstep = (long long)w * h;
-    const int px = 2 * gx, py = 2 * gy; // the quad's first output pixel, in the tile's rectangle
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
-    const long long ss = a.slot_stride / (long long)sizeof(TP);
-    const YuvCoef& k = a.yuv;
-    float yq[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, ym = 0.f, rm = 0.f, bm = 0.f;
-#pragma unroll 1
-    for (int q = 0; q < 3; q++)
-    {
-        const TP* b = b0 + q * cstep;
-        float d[2][2];
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int i = 0; i < 2; i++) d[j][i] = area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, px + i, py + j);
-        const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
-        float m;
-        if constexpr (SITE == 0) m = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
-        else
-        {
-            const int lx = px - (gx ? 1 : 0), uy = py - (gy ? 1 : 0); // output column xl / row yu
-            float hs[2];
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-                hs[j] = add_rn(add_rn(area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, lx, py + j), d[j][1]), add_rn(d[j][0], d[j][0]));
-            if constexpr (SITE == 1) m = mul_rn(add_rn(hs[0], hs[1]), 0.125f);
-            else
-            {
-                const float u0 = area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, px, uy);
-                const float hu = add_rn(add_rn(area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, lx, uy),
-                                               area_pixel<TP>(b, ss, w, h, a.crop, a.tta, n, L, a.area_norm, px + 1, uy)), add_rn(u0, u0));
-                m = mul_rn(add_rn(add_rn(hu, hs[1]), add_rn(hs[0], hs[0])), 0.0625f);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int i = 0; i < 2; i++) yq[j][i] = add_rn(yq[j][i], mul_rn(kq, d[j][i]));
-        ym = add_rn(ym, mul_rn(kq, m));
-        if (q == 0) rm = m;
-        if (q == 2) bm = m;
-    }
-    const long long pitch = a.out_pitch[im];
-    const int X = t.out_x * n / L + px, Y = (t.out_y - a.out_row0) * n / L + py; // the quad's first luma sample
-    uint8_t* const oy = a.outs[im] + Y * pitch + (long long)X * (int)sizeof(TO);
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-        store_pair<TO>(oy + j * pitch, yuv_code<TO>(yq[j][0], k.yscale, k.yadd, k.maxcode), yuv_code<TO>(yq[j][1], k.yscale, k.yadd, k.maxcode));
-    const float cb = mul_rn(sub_rn(bm, ym), k.icb), cr = mul_rn(sub_rn(rm, ym), k.icr);
-    uint8_t* const ouv = a.outs[im] + a.out_plane[im] + (Y >> 1) * pitch + (long long)X * (int)sizeof(TO);
-    store_pair<TO>(ouv, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
+    const QuadArea<TP> src{a.slot_stride / (long long)sizeof(TP), w, h, a.crop, a.tta, n, L, a.area_norm, 2 * gx, 2 * gy};
+    yuv_quad<TO, SITE>(a, t, im, gx, gy, src, b0, (long long)w * h);
 }
 
 template <typename TP, typename TO>
@@ -1200,9 +1112,7 @@ static void launch_postproc_yuv_area(const PostArgs& a, int max_ow, int max_oh, 
 {
     const int L = 4 * a.den; // (ow_tile / 2) x (oh_tile / 2) quads per tile
     const dim3 grid((max_ow * a.num / L / 2 + 63) / 64, (max_oh * a.num / L / 2 + 3) / 4, a.ntiles), block(256);
-    if (a.siting == 1) hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, 1>), grid, block, 0, st, a);
-    else if (a.siting == 2) hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, 2>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, 0>), grid, block, 0, st, a);
+    with_siting(a.siting, [&](auto site) { hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, decltype(site)::value>), grid, block, 0, st, a); });
 }
 
 template <typename TP, typename TO>
@@ -1210,67 +1120,47 @@ static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipSt
 {
     const int q = a.box > 1 ? 2 * a.box : 2; // x4 pixels per quad and axis
     const dim3 grid((max_ow / q + 63) / 64, (max_oh / q + 3) / 4, a.ntiles), block(256);
-#define RSR_POST_YUV(SITE)                                                                                           \
-    {                                                                                                                \
-        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1, SITE>), grid, block, 0, st, a);            \
-        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2, SITE>), grid, block, 0, st, a);       \
-        else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4, SITE>), grid, block, 0, st, a);                       \
-    }
-    if (a.siting == 1) RSR_POST_YUV(1)
-    else if (a.siting == 2) RSR_POST_YUV(2)
-    else RSR_POST_YUV(0)
-#undef RSR_POST_YUV
+    with_siting(a.siting, [&](auto site) {
+        constexpr int SITE = decltype(site)::value;
+        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1, SITE>), grid, block, 0, st, a);
+        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2, SITE>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4, SITE>), grid, block, 0, st, a);
+    });
 }
+
+// A rational scale other than 4 / 2 / 1 (rsr_set_out_ratio)?
+static bool generic_ratio(const PostArgs& a) { return a.num > 0 && !(a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1)); }
 
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
     if (a.ntiles <= 0) return;
-    if (fmt_is_yuv(a.out_fmt))
-    { // a 4:2:0 surface: one thread per luma quad, at every out_scale, with and without TTA
-        if (a.num > 0 && !(a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1)))
-        { // ... and at every other ratio (rsr_set_out_ratio): the quad kernel over area-averaged pixels
-            if (a.out_fmt == kFmtNV12) a.f32 ? launch_postproc_yuv_area<float, uint8_t>(a, max_ow, max_oh, st) : launch_postproc_yuv_area<_Float16, uint8_t>(a, max_ow, max_oh, st);
-            else a.f32 ? launch_postproc_yuv_area<float, uint16_t>(a, max_ow, max_oh, st) : launch_postproc_yuv_area<_Float16, uint16_t>(a, max_ow, max_oh, st);
+    with_blob_type(a, [&](auto tp) {
+        using TP = decltype(tp);
+        if (fmt_is_yuv(a.out_fmt))
+        { // a 4:2:0 surface: one thread per luma quad, at every out_scale or ratio, with and without TTA
+            with_sample_type(a.out_fmt, [&](auto to) {
+                using TO = decltype(to);
+                if (generic_ratio(a)) launch_postproc_yuv_area<TP, TO>(a, max_ow, max_oh, st);
+                else launch_postproc_yuv<TP, TO>(a, max_ow, max_oh, st);
+            });
             return;
         }
-        if (a.out_fmt == kFmtNV12) a.f32 ? launch_postproc_yuv<float, uint8_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint8_t>(a, max_ow, max_oh, st);
-        else a.f32 ? launch_postproc_yuv<float, uint16_t>(a, max_ow, max_oh, st) : launch_postproc_yuv<_Float16, uint16_t>(a, max_ow, max_oh, st);
-        return;
-    }
-    if (a.num > 0 && !(a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1)))
-    { // a rational scale other than 4 / 2 / 1 (rsr_set_out_ratio): the area-averaging kernel (one thread per output pixel, with and without TTA)
-        a.f32 ? launch_postproc_area<float>(a, max_ow, max_oh, st) : launch_postproc_area<_Float16>(a, max_ow, max_oh, st);
-        return;
-    }
-    if (a.box > 1)
-    { // out_scale 2 / 1: the box-reducing kernel (one thread per output pixel, with and without TTA)
-        if (a.box == 2) a.f32 ? launch_postproc_box<float, 2>(a, max_ow, max_oh, st) : launch_postproc_box<_Float16, 2>(a, max_ow, max_oh, st);
-        else a.f32 ? launch_postproc_box<float, 4>(a, max_ow, max_oh, st) : launch_postproc_box<_Float16, 4>(a, max_ow, max_oh, st);
-        return;
-    }
-    // Measured (profiles/r04_prepost.txt): the TTA gather 0.92 ms staged vs 2.42 ms per-pixel on the C5 frame (2.26 vs 0.86 TB/s: the
-    // transposed variants), but 0.19 vs 0.12 ms for the plain single-variant conversion.  Default: staged under TTA, plain otherwise.
-    const bool staged = a.variant == 2 || (a.variant == 0 && a.tta);
-    bool aligned = true; // (the staged kernel stores the uint8 image in dwords: base and row pitch must be multiples of 4)
-    for (int i = 0; i < a.nimgs; i++) aligned = aligned && (a.out_fmt != kFmtU8 || !((reinterpret_cast<uintptr_t>(a.outs[i]) | (uintptr_t)a.out_pitch[i]) & 3));
-#define RSR_POST(K, TO)                                                                                              \
-    {                                                                                                                \
-        if (a.f32) hipLaunchKernelGGL((K<float, TO>), grid, block, 0, st, a);                                        \
-        else hipLaunchKernelGGL((K<_Float16, TO>), grid, block, 0, st, a);                                           \
-    }
-    if (!staged || !aligned)
-    {
-        const dim3 grid((max_ow + 63) / 64, (max_oh + 3) / 4, a.ntiles), block(256);
-        if (a.out_fmt == kFmtF16) RSR_POST(postproc_tiles, _Float16)
-        else if (a.out_fmt == kFmtF32) RSR_POST(postproc_tiles, float)
-        else RSR_POST(postproc_tiles, uint8_t)
-        return;
-    }
-    const dim3 grid((max_ow + 31) / 32, (max_oh + 31) / 32, a.ntiles), block(256);
-    if (a.out_fmt == kFmtF16) RSR_POST(postproc_tiles_lds, _Float16)
-    else if (a.out_fmt == kFmtF32) RSR_POST(postproc_tiles_lds, float)
-    else RSR_POST(postproc_tiles_lds, uint8_t)
-#undef RSR_POST
+        // one thread per output pixel, with and without TTA: the area-averaging kernel, or at out_scale 2 / 1 the box-reducing one
+        if (generic_ratio(a)) return launch_postproc_area<TP>(a, max_ow, max_oh, st);
+        if (a.box == 2) return launch_postproc_box<TP, 2>(a, max_ow, max_oh, st);
+        if (a.box > 1) return launch_postproc_box<TP, 4>(a, max_ow, max_oh, st);
+        // Measured on the C5 frame: the TTA gather 0.92 ms staged vs 1.72 ms per-pixel (profiles/post_dedupe.txt; 2.42 ms before the per-pixel
+        // kernel took its value through tta_gather, profiles/r04_prepost.txt: the transposed variants), but 0.19 vs 0.12 ms for the plain
+        // single-variant conversion.  Default: staged under TTA, plain otherwise.
+        const bool staged = a.variant == 2 || (a.variant == 0 && a.tta);
+        bool aligned = true; // (the staged kernel stores the uint8 image in dwords: base and row pitch must be multiples of 4)
+        for (int i = 0; i < a.nimgs; i++) aligned = aligned && (a.out_fmt != kFmtU8 || !((reinterpret_cast<uintptr_t>(a.outs[i]) | (uintptr_t)a.out_pitch[i]) & 3));
+        with_image_type(a.out_fmt, [&](auto to) {
+            using TO = decltype(to);
+            if (staged && aligned) hipLaunchKernelGGL((postproc_tiles_lds<TP, TO>), dim3((max_ow + 31) / 32, (max_oh + 31) / 32, a.ntiles), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((postproc_tiles<TP, TO>), dim3((max_ow + 63) / 64, (max_oh + 3) / 4, a.ntiles), dim3(256), 0, st, a);
+        });
+    });
 }
 
 // ---- shader-shaped kernels: same arithmetic, the shaders' own buffer layouts -----------------

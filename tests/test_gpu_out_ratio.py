@@ -161,8 +161,8 @@ def test_longest_and_shortest_footprint(ctxs, nd, tta):
 
 
 # ---- 3. alpha, bgr -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tta", [False, True], ids=["plain", "tta"])
-def test_alpha_is_the_area_mean_of_the_x4_alpha(ctxs, tta):
+@pytest.mark.parametrize("tta,precise", [(False, 0), (True, 0), (False, 1)], ids=["plain", "tta", "precise"])
+def test_alpha_is_the_area_mean_of_the_x4_alpha(ctxs, tta, precise):
     """Alpha at 3/2: the reference applied to the x4 path's alpha -- the bicubic x4 of every tile's un-padded alpha rectangle
     (oracle.bicubic, the arithmetic behind the x4 path's alpha byte), clamped to [0, 255] -- and stored as floor(mean + 0.5): +-0 outside
     the elements whose mean + 0.5 lies within 2^-10 of an integer, +-1 there.  The band: a 4 x 4-tap bicubic value of bytes <= 255 with
@@ -171,6 +171,7 @@ def test_alpha_is_the_area_mean_of_the_x4_alpha(ctxs, tta):
     w, h, T = 62, 46, 32
     s = ctxs[tta]
     s.tilesize = T
+    s.set_option("precise", precise)  # (the blob is fp32 then: the kernels' <float, uint8_t, ., true> instances)
     img = image(7400, w, h, 4)
     full = run(s, img, U8, U8, 4)
     a4 = np.empty((4 * h, 4 * w), dtype=np.float32)

@@ -148,11 +148,12 @@ def test_bgr_swaps_channels_of_the_reduced_image(ctxs, tta):
 
 
 # ---- 4. alpha ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tta", [False, True], ids=["plain", "tta"])
-def test_alpha_is_the_box_mean_of_the_x4_alpha(ctxs, tta):
+@pytest.mark.parametrize("tta,precise", [(False, 0), (True, 0), (False, 1)], ids=["plain", "tta", "precise"])
+def test_alpha_is_the_box_mean_of_the_x4_alpha(ctxs, tta, precise):
     w, h, T = 53, 47, 32
     s = ctxs[tta]
     s.tilesize = T
+    s.set_option("precise", precise)  # (the blob is fp32 then: the kernels' <float, uint8_t, ., true> instances)
     img = image(9300, w, h, 4)
     full = run(s, img, U8, U8, 4)
     for scale in (2, 1):
