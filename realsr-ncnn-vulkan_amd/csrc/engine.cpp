@@ -16,7 +16,7 @@ const char* last_error() { return tl_err.c_str(); }
     do                                                                                             \
     {                                                                                              \
         hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(RSR_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return Engine::fail(RSR_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
 int Engine::fail(int code, const std::string& msg)
@@ -98,15 +98,44 @@ Engine::~Engine()
     for (hipEvent_t e : sync_events) (void)hipEventDestroy(e);
     if (merge_mid) (void)hipEventDestroy(merge_mid);
     if (merge_done) (void)hipEventDestroy(merge_done);
-    for (int k = 0; k < 3; k++)
-    {
-        if (mix_ev[k]) (void)hipEventDestroy(mix_ev[k]);
-        if (mix_tab[k].p) (void)hipFree(mix_tab[k].p);
-        if (mask_ev[k]) (void)hipEventDestroy(mask_ev[k]);
-        if (mask_tab[k].p) (void)hipFree(mask_tab[k].p);
-        if (mask_stage[k]) (void)hipHostFree(mask_stage[k]);
-    }
+    mix_ring.free();
+    mask_ring.free();
     if (stream) (void)hipStreamDestroy(stream);
+}
+
+int TableRing::acquire(size_t bytes, bool want_stage)
+{
+    k = int(seq++ % 3);
+    if (ev[k]) HIP_TRY(hipEventSynchronize(ev[k])); // the call that read this slot last has finished (its copy from the pinned image too)
+    if (const int rc = Engine::ensure(tab[k], bytes)) return rc;
+    if (!want_stage || stage_bytes[k] >= bytes) return RSR_OK;
+    if (stage[k]) (void)hipHostFree(stage[k]);
+    stage[k] = nullptr, stage_bytes[k] = 0;
+    if (hipHostMalloc(&stage[k], bytes, hipHostMallocDefault) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        stage[k] = nullptr;
+        return Engine::fail(RSR_E_NOMEM, "hipHostMalloc(" + std::to_string(bytes) + ") for the tile tables failed");
+    }
+    stage_bytes[k] = bytes;
+    return RSR_OK;
+}
+
+void TableRing::release(hipStream_t st)
+{
+    if (!ev[k] && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) != hipSuccess) ev[k] = nullptr;
+    if (!ev[k] || hipEventRecord(ev[k], st) != hipSuccess) (void)hipStreamSynchronize(st);
+}
+
+void TableRing::free()
+{
+    for (int i = 0; i < 3; i++)
+    {
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+        if (tab[i].p) (void)hipFree(tab[i].p);
+        if (stage[i]) (void)hipHostFree(stage[i]);
+        ev[i] = nullptr, tab[i] = DevBuf(), stage[i] = nullptr, stage_bytes[i] = 0;
+    }
 }
 
 int Engine::init(int gpuid, int tta_mode)
@@ -363,6 +392,28 @@ static size_t batch_table_bytes(const Plan::Batch& b)
     return n;
 }
 
+// Makes b the tile batch of the `count` tiles tile_at(0 .. count) (each with the index of its image in BaseTile::img), the tile0-th of its
+// call onwards: every tile gets its slots (eight orientations under TTA, realsr.cpp:251-258; else one), then the work-item tables.  crop4 =
+// prepadding * scale; out_row0: make_items.  Returns the bytes of the batch's device tables.
+template <class TileAt>
+static size_t fill_batch(Plan::Batch& b, int tile0, int count, TileAt tile_at, bool tta, int crop4, bool trim, bool fold, int out_row0)
+{
+    const int per = tta ? 8 : 1;
+    b.tile0 = tile0;
+    b.ntiles = count;
+    b.nslots = count * per;
+    for (int i = 0; i < count; i++)
+    {
+        BaseTile t = tile_at(i);
+        t.slot0 = i * per;
+        b.tiles.push_back(t);
+        for (int k = 0; k < per; k++) b.dims.push_back(k < 4 ? TileDim{t.th, t.tw} : TileDim{t.tw, t.th});
+    }
+    b.trim4 = trim ? crop4 : 0;
+    make_items(b, fold, tta ? -1 : crop4, b.trim4, out_row0);
+    return batch_table_bytes(b);
+}
+
 // upload one batch's tables behind `d`; every copy is checked.  stage: non-null = the tables are only laid out, behind *stage on the host,
 // as they will lie behind `d`; the caller copies the whole stage with one hipMemcpy (a masked call: several batches per call, every call)
 static hipError_t upload_batch(Plan::Batch& b, char*& d, bool xcd_order = true, char** stage = nullptr)
@@ -508,12 +559,13 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
         }
     const int T = tilesize, P = prepadding;
     // tile grid: realsr.cpp:170-171; tile geometry: realsr.cpp:178-181,237,246-249
-    const int xtiles = (w + T - 1) / T, ytiles = (h + T - 1) / T;
+    int xtiles = 0;
+    const int ntiles = tile_count(w, h, &xtiles);
     std::vector<BaseTile> all;
     long long cap = 0;
     int mtw = 0, mth = 0;
-    if (tile0 < 0 || tile1 > xtiles * ytiles || tile0 >= tile1) return fail(RSR_E_ARG, "tile range outside the image");
-    if (nimg < 1 || nimg > kMaxMerge || (nimg > 1 && (tile0 != 0 || tile1 != xtiles * ytiles))) return fail(RSR_E_ARG, "merged batches take whole images");
+    if (tile0 < 0 || tile1 > ntiles || tile0 >= tile1) return fail(RSR_E_ARG, "tile range outside the image");
+    if (nimg < 1 || nimg > kMaxMerge || (nimg > 1 && (tile0 != 0 || tile1 != ntiles))) return fail(RSR_E_ARG, "merged batches take whole images");
     for (int im = 0; im < nimg; im++) image_tiles(w, h, T, P, scale, tile0, tile1, im, all, cap, mtw, mth);
     // every merged batch -- of one geometry (this plan) or of several (enqueue_mixed) -- gives its slots the capacity of a full tile: the
     // workspace layout, hence its guards, then stays put from batch to batch whatever small images come
@@ -546,20 +598,8 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
     for (size_t t0 = 0; t0 < all.size(); t0 += size_t(tiles_per_batch))
     {
         Plan::Batch b;
-        b.tile0 = int(t0);
-        b.ntiles = int(std::min(all.size() - t0, size_t(tiles_per_batch)));
-        b.nslots = b.ntiles * per;
-        for (int i = 0; i < b.ntiles; i++)
-        {
-            BaseTile t = all[t0 + size_t(i)];
-            t.slot0 = i * per;
-            b.tiles.push_back(t);
-            for (int k = 0; k < per; k++)
-                b.dims.push_back(k < 4 ? TileDim{t.th, t.tw} : TileDim{t.tw, t.th}); // realsr.cpp:251-258
-        }
-        b.trim4 = trim_tail ? P * scale : 0;
-        make_items(b, fold_cols, tta ? -1 : P * scale, b.trim4, plan.out_row0);
-        table_bytes += batch_table_bytes(b);
+        table_bytes += fill_batch(b, int(t0), int(std::min(all.size() - t0, size_t(tiles_per_batch))), [&](int i) { return all[t0 + size_t(i)]; }, tta != 0, P * scale,
+                                  trim_tail, fold_cols, plan.out_row0);
         plan.batches.push_back(std::move(b));
     }
     if (plans.size() >= kMaxPlans)
@@ -946,8 +986,9 @@ int Engine::enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size
     const long long kBytesPerPx = bytes_per_px();
     if (half_rows) *half_rows = 0;
     Plan* planp = nullptr;
-    const int xtiles = (w + tilesize - 1) / tilesize;
-    if (tile1 < 0) tile1 = xtiles * ((h + tilesize - 1) / tilesize);
+    int xtiles = 0;
+    const int all_tiles = tile_count(w, h, &xtiles);
+    if (tile1 < 0) tile1 = all_tiles;
     int rc;
     // A clamp left behind by a transient allocation failure (another process held the memory for a moment) must not halve the
     // batches for ever: a NEW call that finds the device able to give twice the clamped size again plans without it (never inside
@@ -1080,11 +1121,7 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     if (fmt_is_yuv(io.out_fmt) && !yuv_coef(yuv_matrix, yuv_range, io.out_fmt == RSR_FMT_P010 ? 10 : 8, &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     pa.siting = po.siting = yuv_siting;
     launch_preproc_tiles(pa, max_tw, max_th, st);
-    // bytes of a pixel in the caller's image: c for uint8 HWC, 3 halfs / floats for the planar formats, 1.5 samples for the 4:2:0 surfaces
-    auto px_bytes = [c](int fmt) {
-        return fmt == RSR_FMT_F16_CHW ? 6.0 : (fmt == RSR_FMT_F32_CHW ? 12.0 : (fmt == RSR_FMT_NV12 ? 1.5 : (fmt == RSR_FMT_P010 ? 3.0 : double(c))));
-    };
-    mark(0, 0, b.px[0] / per * px_bytes(io.in_fmt) + b.px[0] * 64, st);
+    mark(0, 0, b.px[0] / per * BatchIO::image_px_bytes(io.in_fmt, c) + b.px[0] * 64, st);
     const int rc = run_network(b, st, ntiles * per, &io, nullptr);
     if (rc != RSR_OK || conv_last_writes_image(c, io.out_fmt)) return rc;
     po.planar3 = b_out3.p;
@@ -1106,7 +1143,7 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     po.bgr = bgr ? 1 : 0;
     po.variant = variant;
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
-    mark(2, 0, b.px[2] / per * (6.0 * per + px_bytes(io.out_fmt) * io.os.n * io.os.n / (16.0 * io.os.d * io.os.d)), st);
+    mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) * io.os.n * io.os.n / (16.0 * io.os.d * io.os.d)), st);
     return RSR_OK;
 }
 
@@ -1117,37 +1154,22 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
 // change from batch to batch.  mu held.
 int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid)
 {
-    const int T = tilesize, P = prepadding, per = tta ? 8 : 1, c = g[0]->c;
-    Plan::Batch b;
+    const int T = tilesize, P = prepadding, c = g[0]->c;
+    std::vector<BaseTile> all;
     long long cap = 0;
     int mtw = 0, mth = 0;
-    for (int i = 0; i < n; i++)
-    {
-        const int xt = (g[i]->w + T - 1) / T, yt = (g[i]->h + T - 1) / T;
-        image_tiles(g[i]->w, g[i]->h, T, P, scale, 0, xt * yt, i, b.tiles, cap, mtw, mth);
-    }
+    for (int i = 0; i < n; i++) image_tiles(g[i]->w, g[i]->h, T, P, scale, 0, tile_count(g[i]->w, g[i]->h), i, all, cap, mtw, mth);
     cap = (long long)(T + 2 * P) * (T + 2 * P);
-    b.tile0 = 0;
-    b.ntiles = int(b.tiles.size());
-    b.nslots = b.ntiles * per;
-    for (int i = 0; i < b.ntiles; i++)
-    {
-        BaseTile& t = b.tiles[size_t(i)];
-        t.slot0 = i * per;
-        for (int k = 0; k < per; k++) b.dims.push_back(k < 4 ? TileDim{t.th, t.tw} : TileDim{t.tw, t.th}); // realsr.cpp:251-258
-    }
     int rc = check_tile_px(cap);
     if (rc != RSR_OK) return rc;
-    const long long need = (long long)b.nslots * cap * bytes_per_px();
+    const long long need = (long long)all.size() * (tta ? 8 : 1) * cap * bytes_per_px();
     const long long avail = device_avail(g[0]->w, g[0]->h, c);
     if (need > max_workspace_mb * 1024 * 1024 || (avail >= 0 && need > avail)) return fail(RSR_E_NOMEM, "merged batch exceeds the workspace budget");
-    b.trim4 = trim_tail ? P * scale : 0;
-    make_items(b, fold_cols, tta ? -1 : P * scale, b.trim4, 0);
+    Plan::Batch b;
+    const size_t table_bytes = fill_batch(b, 0, int(all.size()), [&](int i) { return all[size_t(i)]; }, tta != 0, P * scale, trim_tail, fold_cols, 0);
     HIP_TRY(hipSetDevice(device));
-    const int k = int(mix_seq++ % 3);
-    if (mix_ev[k]) HIP_TRY(hipEventSynchronize(mix_ev[k])); // the batch that read this buffer last has finished
-    if ((rc = ensure(mix_tab[k], batch_table_bytes(b))) != RSR_OK) return rc;
-    char* d = static_cast<char*>(mix_tab[k].p);
+    if ((rc = mix_ring.acquire(table_bytes, false)) != RSR_OK) return rc;
+    char* d = mix_ring.dev();
     const hipError_t e = upload_batch(b, d, false);
     if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("merged batch table upload: ") + hipGetErrorString(e));
     if ((rc = ensure_workspace(b.nslots, cap, st)) != RSR_OK) return rc;
@@ -1155,9 +1177,7 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
     io.ev_mid = ev_mid;
     rc = launch_batch(b, cap, mtw, mth, b.ntiles, st, io);
     if (rc != RSR_OK) return rc;
-    if (!mix_ev[k] && hipEventCreateWithFlags(&mix_ev[k], hipEventDisableTiming) != hipSuccess) mix_ev[k] = nullptr;
-    if (mix_ev[k]) HIP_TRY(hipEventRecord(mix_ev[k], st));
-    else HIP_TRY(hipStreamSynchronize(st));
+    mix_ring.release(st);
     HIP_TRY(hipGetLastError());
     return RSR_OK;
 }
@@ -1186,7 +1206,7 @@ int Engine::enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t 
 int Engine::enqueue_sequence(BatchIO io, const std::vector<int>& sel, const std::vector<PropRect>& rects, hipStream_t st, long long& batches_stat, double* table_us)
 {
     const int T = tilesize, P = prepadding, per = tta ? 8 : 1, w = io.w[0], h = io.h[0], c = io.c;
-    const int total = ((w + T - 1) / T) * ((h + T - 1) / T), nsel = int(sel.size());
+    const int total = tile_count(w, h), nsel = int(sel.size());
     std::vector<BaseTile> all;
     long long cap = 0;
     int mtw = 0, mth = 0;
@@ -1208,45 +1228,23 @@ int Engine::enqueue_sequence(BatchIO io, const std::vector<int>& sel, const std:
     for (int t0 = 0; t0 < nsel; t0 += tiles_per_batch)
     {
         Plan::Batch b;
-        b.tile0 = t0;
-        b.ntiles = std::min(nsel - t0, tiles_per_batch);
-        b.nslots = b.ntiles * per;
-        for (int i = 0; i < b.ntiles; i++)
-        {
+        auto tile_at = [&](int i) {
             BaseTile t = all[size_t(sel[size_t(t0 + i)] % total)];
             t.img = sel[size_t(t0 + i)] / total;
-            t.slot0 = i * per;
-            b.tiles.push_back(t);
-            for (int k = 0; k < per; k++) b.dims.push_back(k < 4 ? TileDim{t.th, t.tw} : TileDim{t.tw, t.th}); // realsr.cpp:251-258
             mtw = std::max(mtw, t.tw), mth = std::max(mth, t.th);
-        }
-        b.trim4 = trim_tail ? P * scale : 0;
-        make_items(b, fold_cols, tta ? -1 : P * scale, b.trim4, 0);
-        table_bytes += batch_table_bytes(b);
+            return t;
+        };
+        table_bytes += fill_batch(b, t0, std::min(nsel - t0, tiles_per_batch), tile_at, tta != 0, P * scale, trim_tail, fold_cols, 0);
         batches.push_back(std::move(b));
     }
     const size_t rect_at = table_bytes, rect_bytes = rects.size() * sizeof(PropRect);
     table_bytes += al256(rect_bytes);
-    const int k = int(mask_seq++ % 3);
-    if (mask_ev[k]) HIP_TRY(hipEventSynchronize(mask_ev[k])); // the call that read this buffer last has finished
-    if ((rc = ensure(mask_tab[k], table_bytes)) != RSR_OK) return rc;
-    if (mask_stage_bytes[k] < table_bytes)
-    { // (the copy that read the old image has finished: the event above)
-        if (mask_stage[k]) (void)hipHostFree(mask_stage[k]);
-        mask_stage[k] = nullptr, mask_stage_bytes[k] = 0;
-        if (hipHostMalloc(&mask_stage[k], table_bytes, hipHostMallocDefault) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            mask_stage[k] = nullptr;
-            return fail(RSR_E_NOMEM, "hipHostMalloc(" + std::to_string(table_bytes) + ") for the tile tables failed");
-        }
-        mask_stage_bytes[k] = table_bytes;
-    }
-    char *d = static_cast<char*>(mask_tab[k].p), *hs = static_cast<char*>(mask_stage[k]);
+    if ((rc = mask_ring.acquire(table_bytes, true)) != RSR_OK) return rc;
+    char *d = mask_ring.dev(), *hs = mask_ring.host();
     for (Plan::Batch& b : batches) (void)upload_batch(b, d, xcd_order, &hs);
-    if (rect_bytes) std::memcpy(static_cast<char*>(mask_stage[k]) + rect_at, rects.data(), rect_bytes);
+    if (rect_bytes) std::memcpy(mask_ring.host() + rect_at, rects.data(), rect_bytes);
     // on the call's own stream, in front of its launches: no other stream is involved, whatever kind the caller's is
-    HIP_TRY(hipMemcpyAsync(mask_tab[k].p, mask_stage[k], table_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(mask_ring.dev(), mask_ring.host(), table_bytes, hipMemcpyHostToDevice, st));
     if (table_us) *table_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_tab).count();
     mark_begin(st);
     io.out_row0 = 0;
@@ -1272,13 +1270,12 @@ int Engine::enqueue_sequence(BatchIO io, const std::vector<int>& sel, const std:
         int max_rows = 0;
         double bytes = 0;
         for (const PropRect& r : rects) max_rows = std::max(max_rows, r.rows), bytes += double(r.width) * r.rows;
-        const hipError_t e = launch_propagate_rects(reinterpret_cast<const PropRect*>(static_cast<char*>(mask_tab[k].p) + rect_at), int(rects.size()), max_rows, st);
+        const hipError_t e = launch_propagate_rects(reinterpret_cast<const PropRect*>(mask_ring.dev() + rect_at), int(rects.size()), max_rows, st);
         if (e != hipSuccess && rc == RSR_OK) rc = fail(RSR_E_DEVICE, std::string("propagate_rects: ") + hipGetErrorString(e));
         mark(2, 0, 2 * bytes, st);
     }
     // (also behind a batch that failed to launch: the copy and the batches in front of it read the buffers)
-    if (!mask_ev[k] && hipEventCreateWithFlags(&mask_ev[k], hipEventDisableTiming) != hipSuccess) mask_ev[k] = nullptr;
-    if (!mask_ev[k] || hipEventRecord(mask_ev[k], st) != hipSuccess) (void)hipStreamSynchronize(st);
+    mask_ring.release(st);
     if (rc != RSR_OK) return rc;
     HIP_TRY(hipGetLastError());
     if (profiling)
@@ -1288,6 +1285,66 @@ int Engine::enqueue_sequence(BatchIO io, const std::vector<int>& sel, const std:
         prof.tiles += slots;
     }
     return RSR_OK;
+}
+
+// ---- the call skeleton of the device entry points (engine.h) ------------------------------------------------------------------
+int Engine::admit(int out_fmt, int w, int h, OutRatio os, bool enter) const
+{
+    if (enter)
+    {
+        if (!loaded) return fail(RSR_E_STATE, "process before load");
+        if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
+        if (out_ratio != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
+    }
+    if (w < 1 || h < 1) return RSR_OK;
+    if (const int rc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rc;
+    return check_yuv_out(out_fmt, w, h, os);
+}
+
+template <class Body> int Engine::on_stream(std::unique_lock<std::mutex>& lk, hipStream_t user_stream, bool sync, Body body)
+{
+    HIP_TRY(hipSetDevice(device));
+    // Idle: nothing of any earlier call is pending on the compute stream -- work an earlier direct call put on ITS caller's stream included:
+    // the compute stream was made to wait for it, below.  All other network kernels run on the compute stream (there is one workspace).
+    const bool direct = user_stream && hipStreamQuery(stream) == hipSuccess;
+    (void)hipGetLastError(); // (hipErrorNotReady is not an error)
+    if (user_stream && !direct)
+    {
+        hipEvent_t e = take_event();
+        if (!e) return fail(RSR_E_DEVICE, "hipEventCreate failed");
+        HIP_TRY(hipEventRecord(e, user_stream));
+        HIP_TRY(hipStreamWaitEvent(stream, e, 0));
+        give_event(e);
+    }
+    bool enqueued = false;
+    const int rc = body(direct ? user_stream : stream, enqueued);
+    if (direct)
+    { // whatever the compute stream gets next uses the same workspace: it waits for this call's last kernel
+        hipEvent_t e = take_event();
+        if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
+        { // cannot order the compute stream behind it: fall back to waiting here
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(user_stream);
+        }
+        give_event(e);
+        if (rc == RSR_OK) device_direct++;
+        return rc;
+    }
+    if (!enqueued || !(user_stream || sync)) return rc;
+    hipEvent_t done = take_event();
+    if (!done) return fail(RSR_E_DEVICE, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(done, stream));
+    if (user_stream) HIP_TRY(hipStreamWaitEvent(user_stream, done, 0));
+    hipError_t e = hipSuccess;
+    if (!user_stream)
+    { // wait outside the lock: other calls may enqueue behind this one meanwhile
+        lk.unlock();
+        e = hipEventSynchronize(done);
+        lk.lock();
+    }
+    give_event(done);
+    if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
+    return rc;
 }
 
 int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync, int in_fmt, int out_fmt)
@@ -1302,7 +1359,6 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
     if ((in_fmt == RSR_FMT_P010 && (reinterpret_cast<uintptr_t>(d_in) & 1)) || (out_fmt == RSR_FMT_P010 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
         return fail(RSR_E_ARG, "P010 data is not aligned to its 16-bit samples");
     const bool u8 = in_fmt == RSR_FMT_U8_HWC && out_fmt == RSR_FMT_U8_HWC;
-    hipEvent_t done = nullptr;
     if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
     { // a small image: merged with whatever other calls hand in meanwhile (Engine::submit_merged)
         int T = 0, width = 1;
@@ -1336,63 +1392,12 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             return RSR_OK;
         }
     }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!loaded) return fail(RSR_E_STATE, "process before load");
-        if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
-        if (const int rc = check_ratio_out(out_fmt, w, h, tilesize, out_ratio)) return rc;
-        if (const int rc = check_yuv_out(out_fmt, w, h, out_ratio)) return rc;
-        HIP_TRY(hipSetDevice(device));
-        if (user_stream && hipStreamQuery(stream) == hipSuccess)
-        {
-            // The engine is idle -- nothing of any earlier call is pending on the compute stream (work an earlier call of this kind
-            // put on ITS caller's stream included: the compute stream was made to wait for it, below) -- so this call's kernels go
-            // straight onto the caller's stream: no event hop into the compute stream and back.  Whatever is enqueued on the compute
-            // stream later uses the same workspace and must come behind: it waits for this call's last kernel.
-            const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt, out_ratio), 0, -1, 0, nullptr, user_stream);
-            hipEvent_t e = take_event();
-            if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
-            { // cannot order the compute stream behind it: fall back to waiting here
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(user_stream);
-            }
-            give_event(e);
-            if (rc == RSR_OK) device_direct++;
-            return rc;
-        }
-        (void)hipGetLastError(); // (hipErrorNotReady is not an error)
-        // All network kernels run on the engine's compute stream (one workspace); a caller stream is ordered around them.
-        if (user_stream)
-        {
-            hipEvent_t e = take_event();
-            if (!e) return fail(RSR_E_DEVICE, "hipEventCreate failed");
-            HIP_TRY(hipEventRecord(e, user_stream));
-            HIP_TRY(hipStreamWaitEvent(stream, e, 0));
-            give_event(e);
-        }
-        const int rc = enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt, out_ratio), 0, -1, 0, nullptr, stream);
-        if (rc != RSR_OK) return rc;
-        if (user_stream || sync)
-        {
-            done = take_event();
-            if (!done) return fail(RSR_E_DEVICE, "hipEventCreate failed");
-            HIP_TRY(hipEventRecord(done, stream));
-            if (user_stream)
-            {
-                HIP_TRY(hipStreamWaitEvent(user_stream, done, 0));
-                give_event(done);
-                done = nullptr;
-            }
-        }
-    }
-    if (done)
-    { // wait outside the lock: other calls may enqueue behind this one meanwhile
-        const hipError_t e = hipEventSynchronize(done);
-        std::lock_guard<std::mutex> lk(mu);
-        give_event(done);
-        if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
-    }
-    return RSR_OK;
+    std::unique_lock<std::mutex> lk(mu);
+    if (const int rc = admit(out_fmt, w, h, out_ratio, true)) return rc;
+    return on_stream(lk, user_stream, sync, [&](hipStream_t st, bool& enqueued) {
+        enqueued = true; // (enqueue_images does not say how far it got: a failing call is ordered behind whatever it did enqueue)
+        return enqueue_images(BatchIO(d_in, d_out, w, h, c, in_fmt, out_fmt, out_ratio), 0, -1, 0, nullptr, st);
+    });
 }
 
 // ---- YUV 4:2:0 surfaces (RSR_FMT_NV12 / RSR_FMT_P010) ------------------------------------------------------------------------------
@@ -1488,6 +1493,38 @@ int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long pl
     return RSR_OK;
 }
 
+int image_refs(int n, const rsr_image* im, int fmt, int w, int h, int c, const OutRatio* os, const char* what, int index0, ImageRef* out)
+{
+    const int iw = os ? int(os->of(w)) : w, ih = os ? int(os->of(h)) : h;
+    for (int i = 0; i < n; i++)
+    {
+        const char* why = nullptr;
+        int rc = RSR_OK;
+        if (!im[i].data) why = "null data pointer";
+        else if ((rc = image_layout(fmt, iw, ih, c, im[i].row_pitch, im[i].plane_pitch, &out[i].row, &out[i].plane)) != RSR_OK) why = last_error();
+        else if (w > (1 << 24) || h > (1 << 24)) why = "bad image size";
+        else if (reinterpret_cast<uintptr_t>(im[i].data) % uintptr_t(BatchIO::elem_bytes(fmt, c))) why = "data is not aligned to the element size";
+        if (why) return Engine::fail(RSR_E_ARG, what + (index0 >= 0 ? " " + std::to_string(index0 + i) : std::string()) + ": " + why);
+        out[i].data = im[i].data;
+    }
+    return RSR_OK;
+}
+
+int Engine::check_pairs(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, OutRatio* os, ImageRef* src, ImageRef* dst)
+{
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        *os = out_ratio;
+        if (const int rc = admit(out_fmt, w, h, *os, false)) return rc;
+    }
+    for (int i = 0; i < n; i++)
+    {
+        if (const int rc = image_refs(1, &in[i], in_fmt, w, h, c, nullptr, "image", i, &src[i])) return rc;
+        if (const int rc = image_refs(1, &out[i], out_fmt, w, h, c, os, "image", i, &dst[i])) return rc;
+    }
+    return RSR_OK;
+}
+
 int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream,
                                  bool sync, const uint8_t* mask, int nmask)
 {
@@ -1495,82 +1532,37 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
     if (n < 1 || !in || !out || (mask && n != 1)) return fail(RSR_E_ARG, "bad image arguments");
     std::vector<int> sel; // a masked call: the tiles to run
     bool masked = false;  // ... and that it is one (mask is dropped where every tile is set)
-    long long irow = 0, iplane = 0, orow = 0, oplane = 0;
-    std::vector<long long> lay(size_t(n) * 4);
+    std::vector<ImageRef> refs(size_t(n) * 2);
+    ImageRef *const src = refs.data(), *const dst = src + n;
     OutRatio os; // the output windows are checked against the output ratio in force now; should it change before the launch: RSR_E_STATE
+    if (const int rc = check_pairs(n, in, in_fmt, w, h, c, out, out_fmt, &os, src, dst)) return rc;
+    std::unique_lock<std::mutex> lk(mu);
+    if (const int rc = admit(out_fmt, w, h, os, true)) return rc;
+    const int ntiles = tile_count(w, h);
+    if (mask)
     {
-        std::lock_guard<std::mutex> lk(mu);
-        os = out_ratio;
-        if (n >= 1 && w >= 1 && h >= 1)
-        {
-            if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
-            if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
+        if (nmask != ntiles) return fail(RSR_E_ARG, "the mask has " + std::to_string(nmask) + " bytes, the tile grid " + std::to_string(ntiles) + " tiles");
+        for (int t = 0; t < ntiles; t++)
+            if (mask[t]) sel.push_back(t);
+        if (sel.empty())
+        { // nothing changed: nothing is launched
+            masked_calls++;
+            masked_tiles_skipped += ntiles;
+            return RSR_OK;
         }
+        masked = true;
+        if (int(sel.size()) == ntiles) mask = nullptr; // every tile: the plain call, on its cached plan
     }
-    for (int i = 0; i < n; i++)
-    {
-        if (!in[i].data || !out[i].data) return fail(RSR_E_ARG, "image " + std::to_string(i) + ": null data pointer");
-        int rc = image_layout(in_fmt, w, h, c, in[i].row_pitch, in[i].plane_pitch, &irow, &iplane);
-        if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
-        if (rc == RSR_OK) rc = image_layout(out_fmt, int(os.of(w)), int(os.of(h)), c, out[i].row_pitch, out[i].plane_pitch, &orow, &oplane);
-        if (rc != RSR_OK) return rc;
-        if (reinterpret_cast<uintptr_t>(in[i].data) % uintptr_t(in_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(in_fmt, c)) ||
-            reinterpret_cast<uintptr_t>(out[i].data) % uintptr_t(out_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(out_fmt, c)))
-            return fail(RSR_E_ARG, "image " + std::to_string(i) + ": data is not aligned to the element size");
-        lay[size_t(i) * 4] = irow, lay[size_t(i) * 4 + 1] = iplane, lay[size_t(i) * 4 + 2] = orow, lay[size_t(i) * 4 + 3] = oplane;
-    }
-    hipEvent_t done = nullptr;
-    int rc = RSR_OK;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!loaded) return fail(RSR_E_STATE, "process before load");
-        if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
-        if (out_ratio != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
-        if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
-        if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
-        if (mask)
-        {
-            const int ntiles = ((w + tilesize - 1) / tilesize) * ((h + tilesize - 1) / tilesize);
-            if (nmask != ntiles) return fail(RSR_E_ARG, "the mask has " + std::to_string(nmask) + " bytes, the tile grid " + std::to_string(ntiles) + " tiles");
-            for (int t = 0; t < ntiles; t++)
-                if (mask[t]) sel.push_back(t);
-            if (sel.empty())
-            { // nothing changed: nothing is launched
-                masked_calls++;
-                masked_tiles_skipped += ntiles;
-                return RSR_OK;
-            }
-            masked = true;
-            if (int(sel.size()) == ntiles) mask = nullptr; // every tile: the plain call, on its cached plan
-        }
-        HIP_TRY(hipSetDevice(device));
-        // As in process_device: an idle engine runs the call on the caller's own stream, a busy one on the compute stream between two events.
-        const bool direct = user_stream && hipStreamQuery(stream) == hipSuccess;
-        (void)hipGetLastError(); // (hipErrorNotReady is not an error)
-        hipStream_t st = direct ? user_stream : stream;
-        if (user_stream && !direct)
-        {
-            hipEvent_t e = take_event();
-            if (!e) return fail(RSR_E_DEVICE, "hipEventCreate failed");
-            HIP_TRY(hipEventRecord(e, user_stream));
-            HIP_TRY(hipStreamWaitEvent(stream, e, 0));
-            give_event(e);
-        }
+    return on_stream(lk, user_stream, sync, [&](hipStream_t st, bool& any) {
         // Groups of merge_width images, each ONE tile batch in (a prefix of) the merged plan of this geometry -- the plan and the workspace
         // the merged host calls of that geometry use.  Width 1 (a large frame, "merge" 1, profiling): every image a batch of its own.
         const int width = merge_width(w, h, c);
-        const int tiles_per_image = ((w + tilesize - 1) / tilesize) * ((h + tilesize - 1) / tilesize);
-        int enqueued = 0;
-        for (int g0 = 0; g0 < n && rc == RSR_OK; g0 += width)
+        int rc = RSR_OK, enqueued = 0;
+        for (int g0 = 0; g0 < n; g0 += width)
         {
             const int k = std::min(width, n - g0);
             BatchIO io(k, c, in_fmt, out_fmt, os);
-            for (int i = 0; i < k; i++)
-            {
-                const long long* l = &lay[size_t(g0 + i) * 4];
-                io.set(i, in[g0 + i].data, out[g0 + i].data, w, h);
-                io.in_pitch[i] = l[0], io.in_plane[i] = l[1], io.out_pitch[i] = l[2], io.out_plane[i] = l[3];
-            }
+            for (int i = 0; i < k; i++) io.set(i, src[g0 + i], dst[g0 + i], w, h);
             // (n == 1: plan_nimg 0, the very call process_device makes; otherwise the progress of all n images is reported here)
             rc = mask ? enqueue_masked(io, sel, st) : enqueue_images(io, 0, -1, n == 1 ? 0 : width, nullptr, st);
             if (rc != RSR_OK) break;
@@ -1578,49 +1570,18 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
             { // counted once the call is enqueued: a call that fails has run nothing
                 masked_calls++;
                 masked_tiles_run += (long long)sel.size();
-                masked_tiles_skipped += tiles_per_image - (long long)sel.size();
+                masked_tiles_skipped += ntiles - (long long)sel.size();
             }
             enqueued += k;
             batch_groups++;
             if (progress && n > 1)
-                for (int i = 1; i <= k * tiles_per_image; i++) progress(g0 * tiles_per_image + i, n * tiles_per_image, progress_user);
+                for (int i = 1; i <= k * ntiles; i++) progress(g0 * ntiles + i, n * ntiles, progress_user);
         }
         batch_calls++;
         batch_images += enqueued;
-        // A later group that failed leaves the earlier ones enqueued: they complete, and the streams are ordered around them all the same.
-        if (direct)
-        { // whatever the compute stream gets next uses the same workspace: it waits for this call's last kernel
-            hipEvent_t e = take_event();
-            if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
-            {
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(user_stream);
-            }
-            give_event(e);
-            if (rc == RSR_OK) device_direct++;
-            return rc;
-        }
-        if (enqueued && (user_stream || sync))
-        {
-            done = take_event();
-            if (!done) return fail(RSR_E_DEVICE, "hipEventCreate failed");
-            HIP_TRY(hipEventRecord(done, stream));
-            if (user_stream)
-            {
-                HIP_TRY(hipStreamWaitEvent(user_stream, done, 0));
-                give_event(done);
-                done = nullptr;
-            }
-        }
-    }
-    if (done)
-    { // wait outside the lock: other calls may enqueue behind this one meanwhile
-        const hipError_t e = hipEventSynchronize(done);
-        std::lock_guard<std::mutex> lk(mu);
-        give_event(done);
-        if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
-    }
-    return rc;
+        any = enqueued > 0; // a later group that failed leaves the earlier ones enqueued: they complete, and the streams are ordered around them
+        return rc;
+    });
 }
 
 // ---- which tiles changed (include/realsr_hip.h rsr_diff_tiles) ---------------------------------------------------------------------------
@@ -1628,16 +1589,14 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
 // no ordering against the compute stream.  A null stream: the context's own, and the call waits.
 int Engine::diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, hipStream_t user_stream)
 {
-    if (!a || !b || !a->data || !b->data || !d_mask) return fail(RSR_E_ARG, "bad image arguments");
+    if (!a || !b || !d_mask) return fail(RSR_E_ARG, "bad image arguments");
+    ImageRef ra, rb;
+    if (const int rc = image_refs(1, a, fmt, w, h, c, nullptr, "image a", -1, &ra)) return rc;
+    if (const int rc = image_refs(1, b, fmt, w, h, c, nullptr, "image b", -1, &rb)) return rc;
     DiffArgs da;
     std::memset(&da, 0, sizeof da);
-    int rc = image_layout(fmt, w, h, c, a->row_pitch, a->plane_pitch, &da.pitch_a, &da.plane_a);
-    if (rc == RSR_OK) rc = image_layout(fmt, w, h, c, b->row_pitch, b->plane_pitch, &da.pitch_b, &da.plane_b);
-    if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
-    if (rc != RSR_OK) return rc;
-    const uintptr_t es = uintptr_t(fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(fmt, c));
-    if (reinterpret_cast<uintptr_t>(a->data) % es || reinterpret_cast<uintptr_t>(b->data) % es) return fail(RSR_E_ARG, "data is not aligned to the element size");
-    da.a = static_cast<const uint8_t*>(a->data), da.b = static_cast<const uint8_t*>(b->data);
+    da.a = static_cast<const uint8_t*>(ra.data), da.pitch_a = ra.row, da.plane_a = ra.plane;
+    da.b = static_cast<const uint8_t*>(rb.data), da.pitch_b = rb.row, da.plane_b = rb.plane;
     da.fmt = fmt, da.w = w, da.h = h, da.c = c;
     da.mask = d_mask;
     {
@@ -1673,30 +1632,18 @@ int sequence_sources(int n, int ntiles, const uint8_t* masks, int has_prev, int*
 // its two, then one memset and one launch.
 int Engine::diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image* prev, int fmt, int w, int h, int c, uint8_t* d_masks, hipStream_t user_stream)
 {
-    if (n < 1 || n > kMaxMerge || !frames || !d_masks || (prev && !prev->data)) return fail(RSR_E_ARG, "bad image arguments");
+    if (n < 1 || n > kMaxMerge || !frames || !d_masks) return fail(RSR_E_ARG, "bad image arguments");
+    ImageRef r[kMaxMerge + 1]; // r[0]: prev (no predecessor: pair 0 keeps its null `a`), r[k + 1]: frame k
+    if (prev)
+        if (const int rc = image_refs(1, prev, fmt, w, h, c, nullptr, "previous frame", -1, &r[0])) return rc;
+    if (const int rc = image_refs(n, frames, fmt, w, h, c, nullptr, "image", 0, &r[1])) return rc;
     DiffSeqArgs da;
     std::memset(&da, 0, sizeof da);
-    const uintptr_t es = uintptr_t(fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(fmt, c));
-    for (int k = -1; k < n; k++)
-    {
-        const rsr_image* im = k < 0 ? prev : &frames[k];
-        if (!im) continue; // (no predecessor: pair 0 keeps its null `a`)
-        if (!im->data) return fail(RSR_E_ARG, "image " + std::to_string(k) + ": null data pointer");
-        long long row = 0, plane = 0;
-        int rc = image_layout(fmt, w, h, c, im->row_pitch, im->plane_pitch, &row, &plane);
-        if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
-        if (rc != RSR_OK) return rc;
-        if (reinterpret_cast<uintptr_t>(im->data) % es) return fail(RSR_E_ARG, "data is not aligned to the element size");
-        if (k >= 0)
-        { // frame k is the `b` of pair k ...
-            DiffPair& p = da.pair[k];
-            p.b = static_cast<const uint8_t*>(im->data), p.pitch_b = row, p.plane_b = plane;
-        }
-        if (k + 1 < n)
-        { // ... and the `a` of pair k + 1
-            DiffPair& p = da.pair[k + 1];
-            p.a = static_cast<const uint8_t*>(im->data), p.pitch_a = row, p.plane_a = plane;
-        }
+    for (int k = 0; k < n; k++)
+    { // pair k: (frame k - 1 or prev, frame k)
+        DiffPair& p = da.pair[k];
+        p.a = static_cast<const uint8_t*>(r[k].data), p.pitch_a = r[k].row, p.plane_a = r[k].plane;
+        p.b = static_cast<const uint8_t*>(r[k + 1].data), p.pitch_b = r[k + 1].row, p.plane_b = r[k + 1].plane;
     }
     da.n = n, da.fmt = fmt, da.w = w, da.h = h, da.c = c;
     da.mask = d_masks;
@@ -1711,12 +1658,14 @@ int Engine::diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image*
     return RSR_OK;
 }
 
-// The byte rectangles of output tile `tile` of an os.of(w) x os.of(h) image in out_fmt, from (sb, sp, spl) to (db, dp, dpl) (base, row pitch,
-// plane pitch): one for uint8 HWC, three for the planar formats, Y and UV for the surfaces (the UV rectangle has the byte columns of the Y
-// rectangle and half its rows; check_yuv_out has made its edges even).
-static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, int tile, uint8_t* db, long long dp, long long dpl, const uint8_t* sb, long long sp,
-                         long long spl, std::vector<PropRect>& out)
+// The byte rectangles of output tile `tile` of an os.of(w) x os.of(h) image in out_fmt, from the image `src` to the image `dst`: one for
+// uint8 HWC, three for the planar formats, Y and UV for the surfaces (the UV rectangle has the byte columns of the Y rectangle and half its
+// rows; check_yuv_out has made its edges even).
+static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, int tile, const ImageRef& dst, const ImageRef& src, std::vector<PropRect>& out)
 {
+    uint8_t* const db = static_cast<uint8_t*>(const_cast<void*>(dst.data));
+    const uint8_t* const sb = static_cast<const uint8_t*>(src.data);
+    const long long dp = dst.row, dpl = dst.plane, sp = src.row, spl = src.plane;
     const int nx = (w + T - 1) / T, yi = tile / nx, xi = tile - yi * nx;
     const long long es = BatchIO::px_bytes(out_fmt, c);
     const long long x0 = os.of((long long)xi * T), y0 = os.of((long long)yi * T), x1 = os.of(std::min((xi + 1) * T, w)), y1 = os.of(std::min((yi + 1) * T, h));
@@ -1732,139 +1681,57 @@ int Engine::process_device_sequence(int n, const rsr_image* in, int in_fmt, int 
 {
     // everything is checked before anything is launched
     if (n < 1 || n > kMaxMerge || !in || !out || !masks) return fail(RSR_E_ARG, "bad sequence arguments");
-    long long irow = 0, iplane = 0, orow = 0, oplane = 0, prow = 0, pplane = 0;
-    std::vector<long long> lay(size_t(n) * 4);
+    ImageRef src[kMaxMerge], dst[kMaxMerge], prev;
     OutRatio os;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        os = out_ratio;
-        if (w >= 1 && h >= 1)
-        {
-            if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
-            if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
-        }
-    }
-    const uintptr_t ies = uintptr_t(in_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(in_fmt, c)), oes = uintptr_t(out_fmt == RSR_FMT_U8_HWC ? 1 : BatchIO::px_bytes(out_fmt, c));
-    for (int i = 0; i < n; i++)
-    {
-        if (!in[i].data || !out[i].data) return fail(RSR_E_ARG, "image " + std::to_string(i) + ": null data pointer");
-        int rc = image_layout(in_fmt, w, h, c, in[i].row_pitch, in[i].plane_pitch, &irow, &iplane);
-        if (rc == RSR_OK && (w > (1 << 24) || h > (1 << 24))) rc = fail(RSR_E_ARG, "bad image size");
-        if (rc == RSR_OK) rc = image_layout(out_fmt, int(os.of(w)), int(os.of(h)), c, out[i].row_pitch, out[i].plane_pitch, &orow, &oplane);
-        if (rc != RSR_OK) return rc;
-        if (reinterpret_cast<uintptr_t>(in[i].data) % ies || reinterpret_cast<uintptr_t>(out[i].data) % oes)
-            return fail(RSR_E_ARG, "image " + std::to_string(i) + ": data is not aligned to the element size");
-        lay[size_t(i) * 4] = irow, lay[size_t(i) * 4 + 1] = iplane, lay[size_t(i) * 4 + 2] = orow, lay[size_t(i) * 4 + 3] = oplane;
-    }
-    if (prev_out)
-    { // an output image like the others
-        if (!prev_out->data) return fail(RSR_E_ARG, "previous output: null data pointer");
-        if (const int rc = image_layout(out_fmt, int(os.of(w)), int(os.of(h)), c, prev_out->row_pitch, prev_out->plane_pitch, &prow, &pplane)) return rc;
-        if (reinterpret_cast<uintptr_t>(prev_out->data) % oes) return fail(RSR_E_ARG, "previous output: data is not aligned to the element size");
-    }
+    if (const int rc = check_pairs(n, in, in_fmt, w, h, c, out, out_fmt, &os, src, dst)) return rc;
+    if (prev_out) // an output image like the others
+        if (const int rc = image_refs(1, prev_out, out_fmt, w, h, c, &os, "previous output", -1, &prev)) return rc;
     // frame 0 updated in place: its own rectangles of the previous output are already where they belong
-    const bool in_place = prev_out && prev_out->data == out[0].data && prow == lay[2] && pplane == lay[3];
-    hipEvent_t done = nullptr;
-    int rc = RSR_OK;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!loaded) return fail(RSR_E_STATE, "process before load");
-        if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
-        if (out_ratio != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
-        if (const int rrc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rrc;
-        if (const int yrc = check_yuv_out(out_fmt, w, h, os)) return yrc;
-        const int ntiles = ((w + tilesize - 1) / tilesize) * ((h + tilesize - 1) / tilesize);
-        if (nmask != (long long)n * ntiles)
-            return fail(RSR_E_ARG, "the masks have " + std::to_string(nmask) + " bytes, " + std::to_string(n) + " frames of " + std::to_string(ntiles) + " tiles each");
-        std::vector<int> src(static_cast<size_t>(nmask));
-        if (const int src_rc = sequence_sources(n, ntiles, masks, prev_out != nullptr, src.data())) return src_rc;
-        std::vector<int> sel; // (frame, tile) pairs that walk the network, frame-major
-        std::vector<PropRect> rects;
-        long long copied = 0;
-        for (int k = 0; k < n; k++)
-            for (int t = 0; t < ntiles; t++)
+    const bool in_place = prev_out && prev.data == dst[0].data && prev.row == dst[0].row && prev.plane == dst[0].plane;
+    std::unique_lock<std::mutex> lk(mu);
+    if (const int rc = admit(out_fmt, w, h, os, true)) return rc;
+    const int ntiles = tile_count(w, h);
+    if (nmask != (long long)n * ntiles)
+        return fail(RSR_E_ARG, "the masks have " + std::to_string(nmask) + " bytes, " + std::to_string(n) + " frames of " + std::to_string(ntiles) + " tiles each");
+    std::vector<int> from(static_cast<size_t>(nmask));
+    if (const int rc = sequence_sources(n, ntiles, masks, prev_out != nullptr, from.data())) return rc;
+    std::vector<int> sel; // (frame, tile) pairs that walk the network, frame-major
+    std::vector<PropRect> rects;
+    long long copied = 0;
+    for (int k = 0; k < n; k++)
+        for (int t = 0; t < ntiles; t++)
+        {
+            const int s = from[size_t(k) * ntiles + t];
+            if (s == k) sel.push_back(k * ntiles + t);
+            else if (!(s < 0 && k == 0 && in_place))
             {
-                const int s = src[size_t(k) * ntiles + t];
-                if (s == k) sel.push_back(k * ntiles + t);
-                else if (!(s < 0 && k == 0 && in_place))
-                {
-                    const uint8_t* sb = static_cast<const uint8_t*>(s < 0 ? prev_out->data : out[s].data);
-                    output_rects(out_fmt, w, h, c, tilesize, os, t, static_cast<uint8_t*>(out[k].data), lay[size_t(k) * 4 + 2], lay[size_t(k) * 4 + 3], sb,
-                                 s < 0 ? prow : lay[size_t(s) * 4 + 2], s < 0 ? pplane : lay[size_t(s) * 4 + 3], rects);
-                    copied++;
-                }
+                output_rects(out_fmt, w, h, c, tilesize, os, t, dst[k], s < 0 ? prev : dst[s], rects);
+                copied++;
             }
-        auto count = [&]() { // once the call is enqueued (or has nothing to do): a call that fails counts nothing
-            seq_calls++;
-            seq_frames += n;
-            seq_tiles_run += (long long)sel.size();
-            seq_tiles_copied += copied;
-        };
-        if (sel.empty() && rects.empty())
-        { // nothing changed and everything is in place: nothing is launched
-            count();
-            return RSR_OK;
         }
-        HIP_TRY(hipSetDevice(device));
-        // As in process_device_batch: an idle engine runs the call on the caller's own stream, a busy one on the compute stream between two events.
-        const bool direct = user_stream && hipStreamQuery(stream) == hipSuccess;
-        (void)hipGetLastError(); // (hipErrorNotReady is not an error)
-        hipStream_t st = direct ? user_stream : stream;
-        if (user_stream && !direct)
-        {
-            hipEvent_t e = take_event();
-            if (!e) return fail(RSR_E_DEVICE, "hipEventCreate failed");
-            HIP_TRY(hipEventRecord(e, user_stream));
-            HIP_TRY(hipStreamWaitEvent(stream, e, 0));
-            give_event(e);
-        }
+    auto count = [&]() { // once the call is enqueued (or has nothing to do): a call that fails counts nothing
+        seq_calls++;
+        seq_frames += n;
+        seq_tiles_run += (long long)sel.size();
+        seq_tiles_copied += copied;
+    };
+    if (sel.empty() && rects.empty())
+    { // nothing changed and everything is in place: nothing is launched
+        count();
+        return RSR_OK;
+    }
+    return on_stream(lk, user_stream, sync, [&](hipStream_t st, bool& any) {
         BatchIO io(n, c, in_fmt, out_fmt, os);
-        for (int i = 0; i < n; i++)
-        {
-            const long long* l = &lay[size_t(i) * 4];
-            io.set(i, in[i].data, out[i].data, w, h);
-            io.in_pitch[i] = l[0], io.in_plane[i] = l[1], io.out_pitch[i] = l[2], io.out_plane[i] = l[3];
-        }
-        rc = enqueue_sequence(io, sel, rects, st, seq_batches, nullptr);
+        for (int i = 0; i < n; i++) io.set(i, src[i], dst[i], w, h);
+        const int rc = enqueue_sequence(io, sel, rects, st, seq_batches, nullptr);
         if (rc == RSR_OK)
         {
             count();
             batch_calls++;
         }
-        // A later batch that failed leaves the earlier ones enqueued: they complete, and the streams are ordered around them all the same.
-        if (direct)
-        { // whatever the compute stream gets next uses the same workspace: it waits for this call's last kernel
-            hipEvent_t e = take_event();
-            if (!e || hipEventRecord(e, user_stream) != hipSuccess || hipStreamWaitEvent(stream, e, 0) != hipSuccess)
-            {
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(user_stream);
-            }
-            give_event(e);
-            if (rc == RSR_OK) device_direct++;
-            return rc;
-        }
-        if (user_stream || sync)
-        {
-            done = take_event();
-            if (!done) return fail(RSR_E_DEVICE, "hipEventCreate failed");
-            HIP_TRY(hipEventRecord(done, stream));
-            if (user_stream)
-            {
-                HIP_TRY(hipStreamWaitEvent(user_stream, done, 0));
-                give_event(done);
-                done = nullptr;
-            }
-        }
-    }
-    if (done)
-    { // wait outside the lock: other calls may enqueue behind this one meanwhile
-        const hipError_t e = hipEventSynchronize(done);
-        std::lock_guard<std::mutex> lk(mu);
-        give_event(done);
-        if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
-    }
-    return rc;
+        any = true; // (a later batch that failed leaves the earlier ones enqueued: they complete, and the streams are ordered around them)
+        return rc;
+    });
 }
 
 // ---- merging small images across calls (engine.h) ---------------------------------------------

@@ -153,6 +153,32 @@ struct MergeReq
     bool done = false, lead = false; // under Engine::cq_mu
 };
 
+// One device image as a call addresses it: its base and the bytes from one row / one plane to the next, resolved (0 = "tightly packed"
+// has been replaced by the packed value; plane stays 0 for uint8 HWC behind a descriptor, which has no planes).
+struct ImageRef
+{
+    const void* data = nullptr;
+    long long row = 0, plane = 0;
+};
+
+// Three rotating device buffers for tile tables that are built per call (Engine::enqueue_mixed, Engine::enqueue_sequence), each guarded by
+// an event recorded behind the last launch that reads it: the host waits only when the call three turns back is still in flight.  With
+// want_stage a slot has a pinned host image of the same size, from which the tables travel in one asynchronous copy.  Engine::mu held.
+struct TableRing
+{
+    DevBuf tab[3];
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    void* stage[3] = {nullptr, nullptr, nullptr};
+    size_t stage_bytes[3] = {0, 0, 0};
+    unsigned long long seq = 0;
+    int k = 0;                                   // the slot in use
+    int acquire(size_t bytes, bool want_stage);  // the next slot: waits for its event, grows its buffer(s) to `bytes`; RSR_*
+    char* dev() const { return static_cast<char*>(tab[k].p); }
+    char* host() const { return static_cast<char*>(stage[k]); }
+    void release(hipStream_t st);                // records the slot's event behind what `st` holds (no event to be had: waits for `st`)
+    void free();
+};
+
 // What one tile batch is told about its caller (Engine::launch_batch, Engine::run_network): the images its tiles come from and go
 // to, and the events the caller wants recorded on the way.
 struct BatchIO
@@ -163,7 +189,7 @@ struct BatchIO
     OutRatio os;                // Engine::out_ratio of the call: 4, or 2 / 1 = the x4 result box-reduced (kernels.h PostArgs::box = 4 / os), or another ratio = area-averaged (PostArgs::num / den)
     int w[kMaxMerge], h[kMaxMerge];
     // Bytes from one row / one plane (planar formats) of an image to the next, resolved (never 0; rsr_image of the C ABI, image_layout).
-    // The constructors set the tightly packed values; Engine::process_device_batch overwrites them with the caller's.
+    // set() takes them from two ImageRefs (what image_refs made of the caller's descriptors), or packs them tightly itself.
     long long in_pitch[kMaxMerge], in_plane[kMaxMerge], out_pitch[kMaxMerge], out_plane[kMaxMerge];
     int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float and the YUV formats come with whole images of c == 3 only;
                                                            // YUV: the plane pitch is the distance from Y(0,0) to the UV plane)
@@ -184,11 +210,24 @@ struct BatchIO
     {
         return fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_P010 ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : (fmt == RSR_FMT_NV12 ? 1 : c));
     }
-    void set(int i, const void* d_in, void* d_out, int wi, int hi) // image i, tightly packed (the output is x os)
+    static long long elem_bytes(int fmt, int c) { return fmt == RSR_FMT_U8_HWC ? 1 : px_bytes(fmt, c); } // what `data` and the pitches of a descriptor must be multiples of
+    static double image_px_bytes(int fmt, int c) // bytes of one PIXEL of a whole image: c for uint8 HWC, 3 halfs / floats, 1.5 samples of a 4:2:0 surface
     {
-        in[i] = d_in, out[i] = d_out, w[i] = wi, h[i] = hi;
-        in_pitch[i] = wi * px_bytes(in_fmt, c), in_plane[i] = hi * in_pitch[i];
-        out_pitch[i] = os.of(wi) * px_bytes(out_fmt, c), out_plane[i] = os.of(hi) * out_pitch[i];
+        return double(px_bytes(fmt, c)) * (fmt_is_yuv(fmt) ? 1.5 : (fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_F32_CHW ? 3.0 : 1.0));
+    }
+    static ImageRef packed(const void* data, int fmt, long long wi, long long hi, int c) // a tightly packed wi x hi image
+    {
+        const long long row = wi * px_bytes(fmt, c);
+        return ImageRef{data, row, hi * row};
+    }
+    void set(int i, const ImageRef& src, const ImageRef& dst, int wi, int hi) // image i: wi x hi behind src, its x os result behind dst
+    {
+        in[i] = src.data, out[i] = const_cast<void*>(dst.data), w[i] = wi, h[i] = hi;
+        in_pitch[i] = src.row, in_plane[i] = src.plane, out_pitch[i] = dst.row, out_plane[i] = dst.plane;
+    }
+    void set(int i, const void* d_in, void* d_out, int wi, int hi) // ... both tightly packed
+    {
+        set(i, packed(d_in, in_fmt, wi, hi, c), packed(d_out, out_fmt, os.of(wi), os.of(hi), c), wi, hi);
     }
 };
 
@@ -301,16 +340,11 @@ struct Engine
     long long device_direct = 0; // rsr_process_device calls that ran on the caller's own stream (the engine was idle), under mu
     long long batch_calls = 0, batch_images = 0, batch_groups = 0; // rsr_process_device_batch: calls, their images, the tile batches they enqueued; under mu
     std::atomic<bool> merge_mixed{true}; // option "merge_mixed": a merged batch may hold images of different sizes (0: of one geometry only)
-    DevBuf mix_tab[3];               // rotating device tables of such batches
-    hipEvent_t mix_ev[3] = {nullptr, nullptr, nullptr};
-    unsigned long long mix_seq = 0;
+    TableRing mix_ring;              // the device tables of such batches (uploaded table by table: no pinned images)
     std::atomic<long long> merged_mixed{0}; // stat: merged batches whose images differed in size
-    // masked calls (rsr_process_device_masked): the tables of the selected tiles, built per call, in rotating device buffers of their own
-    DevBuf mask_tab[3];
-    hipEvent_t mask_ev[3] = {nullptr, nullptr, nullptr}; // recorded behind the last launch that reads mask_tab[k]
-    unsigned long long mask_seq = 0;
-    void* mask_stage[3] = {nullptr, nullptr, nullptr}; // ... and their pinned host images: the tables of a call are laid out here and go to the
-    size_t mask_stage_bytes[3] = {0, 0, 0};            // device with ONE asynchronous copy on the call's stream (same event guard)
+    // masked calls (rsr_process_device_masked): the tables of the selected tiles, built per call, in a ring of their own; they are laid out
+    // in the slot's pinned image and go to the device with ONE asynchronous copy on the call's stream
+    TableRing mask_ring;
     long long masked_calls = 0, masked_tiles_run = 0, masked_tiles_skipped = 0, masked_batches = 0; // stats, under mu
     double masked_table_us = 0; // stat: host time spent building and uploading those tables
     // frame sequences (rsr_process_device_sequence); their tables travel in the rotating buffers of the masked calls
@@ -350,7 +384,7 @@ struct Engine
     int process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync, int in_fmt = RSR_FMT_U8_HWC,
                        int out_fmt = RSR_FMT_U8_HWC);
     // n images of one geometry, each behind its own descriptor (pointer, row pitch, plane pitch), in groups of merge_width(w, h, c) images:
-    // every group ONE tile batch on the cached merged plan (include/realsr_hip.h rsr_process_device_batch).  Stream contract of process_device.
+    // every group ONE tile batch on the cached merged plan (include/realsr_hip.h rsr_process_device_batch).  Stream contract: on_stream.
     // mask (n == 1 only; include/realsr_hip.h rsr_process_device_masked): nmask bytes, one per tile of the row-major grid; only the tiles with
     // a non-zero byte run (enqueue_masked).  No tile set: nothing is launched; every tile set: the call without a mask.
     int process_device_batch(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, hipStream_t user_stream, bool sync,
@@ -377,7 +411,22 @@ struct Engine
 
     // ---- internals (call with `mu` held unless noted) ----
     static constexpr int plane_ch() { return kPlaneCh; }
-    int ensure(DevBuf& b, size_t bytes);
+    // The call skeleton of the device entry points (DESIGN.md "The call skeleton of a device entry point"): image_refs, admit, on_stream.
+    // admit: may a w x h image leave in out_fmt at output ratio os -- check_ratio_out, check_yuv_out (a w or h below 1 is left to the
+    // descriptor check) --; with `enter`, the call is about to enqueue: before those, is a model loaded, the scale 4, and os still the
+    // ratio in force (the descriptors were checked against os in front of the lock).
+    int admit(int out_fmt, int w, int h, OutRatio os, bool enter) const;
+    // In FRONT of the lock (mu is taken inside, for a moment): *os = the ratio in force and admit(.., false) -- a ratio the images do not
+    // take is refused before any descriptor is looked at --, then image_refs of in[i] and of out[i], image by image.
+    int check_pairs(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, OutRatio* os, ImageRef* src, ImageRef* dst);
+    // The stream protocol.  lk holds mu.  An idle engine (nothing pending on the compute stream) with a caller's stream runs body on that
+    // stream -- no event hop -- and makes the compute stream wait behind it; a call that ends so with RSR_OK counts in device_direct.
+    // Otherwise body runs on the compute stream, behind what the caller's stream holds, and the caller's stream is ordered behind it (or,
+    // without one, a sync call waits for it, lk released meanwhile).  body(st, enqueued) enqueues on st and returns RSR_*; it sets
+    // `enqueued` when it put anything on st: then the ordering behind it happens also where body failed later on.
+    template <class Body> int on_stream(std::unique_lock<std::mutex>& lk, hipStream_t user_stream, bool sync, Body body);
+    int tile_count(int w, int h, int* nx = nullptr) const { const int x = (w + tilesize - 1) / tilesize; if (nx) *nx = x; return x * ((h + tilesize - 1) / tilesize); } // tiles of the grid (realsr.cpp:170-171)
+    static int ensure(DevBuf& b, size_t bytes);
     int ensure_planes(DevBuf& b, size_t bytes, long long plane_bytes, bool layout_changed, bool zero_all, hipStream_t st);
     int get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*& out);
     long long budget_slots(long long cap_px, int w, int h, int c); // slots of cap_px LR pixels one tile batch may have: the memory policy of get_plan and enqueue_masked
@@ -434,6 +483,11 @@ struct Engine
 // Host-only: the resolved row and plane pitch (bytes) of a w x h x c image in `fmt` described with row_pitch / plane_pitch (0 = tightly
 // packed), or RSR_E_ARG (through Engine::fail) for a combination rsr_process_device_batch refuses.  plane = 0 for uint8 HWC.
 int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane);
+// Host-only: THE descriptor check of the device entry points.  im[0 .. n) describe images of one format and geometry: w x h x c, or with
+// os the os->of(w) x os->of(h) results of such images.  Per descriptor, in this order: a null `data`, image_layout, w or h beyond 2^24 (of
+// the input geometry: what the kernels' tile coordinates hold), `data` no multiple of BatchIO::elem_bytes.  out[i] receives the resolved
+// image; a refusal is RSR_E_ARG (through Engine::fail), its message led by `what` (+ " <index0 + i>" where index0 >= 0).
+int image_refs(int n, const rsr_image* im, int fmt, int w, int h, int c, const OutRatio* os, const char* what, int index0, ImageRef* out);
 // Host-only (include/realsr_hip.h rsr_sequence_sources): src[k * ntiles + t] = the frame whose computed rectangle output tile t of frame k
 // shows -- k itself where masks[k][t] != 0, else the last j < k with masks[j][t] != 0, else -1 = the previous output.  RSR_E_ARG (through
 // Engine::fail) for n outside 1 .. kMaxMerge, ntiles < 1, a null pointer, or a -1 while has_prev == 0.

@@ -1,0 +1,120 @@
+// descriptor_check.cpp -- the pure host code of the device entry points under AddressSanitizer + UBSan: no GPU, no Python.
+//
+// Includes engine.cpp itself (so the file-static table builder is in reach) and links the kernel objects of the library build; nothing
+// here initialises HIP.  `make -C realsr-ncnn-vulkan_amd/csrc host_check` builds and runs it.
+//   1. image_refs: the refusal table of tests/test_gpu_device_refusals.py (every row RSR_E_ARG, no ImageRef written past its slot) and
+//      valid layouts: packed, strided, n = 16.
+//   2. fill_batch: batches of 1, 7 and 60 tiles with and without TTA; every table entry is read back and range-checked.
+#include "../../realsr-ncnn-vulkan_amd/csrc/engine.cpp"
+
+#include <cinttypes>
+
+using namespace rsr;
+
+static int failures = 0;
+#define CHECK(cond)                                                              \
+    do                                                                           \
+    {                                                                            \
+        if (!(cond))                                                             \
+        {                                                                        \
+            std::fprintf(stderr, "%s:%d: %s failed (last error: %s)\n", __FILE__, __LINE__, #cond, last_error()); \
+            failures++;                                                          \
+        }                                                                        \
+    } while (0)
+
+static void descriptors()
+{
+    const int W = 40, H = 36;
+    alignas(16) static unsigned char mem[64];
+    void* p = mem;
+    const OutRatio x4;
+    struct Row
+    {
+        const char* name;
+        int fmt, w, c;
+        rsr_image im;
+    };
+    const Row bad[] = {
+        {"null data", RSR_FMT_U8_HWC, W, 3, {nullptr, 0, 0}},
+        {"row pitch one below packed", RSR_FMT_U8_HWC, W, 3, {p, 3 * W - 1, 0}},
+        {"negative plane pitch", RSR_FMT_F32_CHW, W, 3, {p, 0, -1}},
+        {"f16 at an odd address", RSR_FMT_F16_CHW, W, 3, {mem + 1, 0, 0}},
+        {"pitch no element multiple", RSR_FMT_F16_CHW, W, 3, {p, 2 * W + 1, 0}},
+        {"odd w with NV12", RSR_FMT_NV12, W + 1, 3, {p, 0, 0}},
+        {"w beyond 2^24", RSR_FMT_U8_HWC, (1 << 24) + 1, 3, {p, 0, 0}},
+        {"unknown format", 7, W, 3, {p, 0, 0}},
+        {"planar with c == 4", RSR_FMT_F16_CHW, W, 4, {p, 0, 0}},
+    };
+    for (const Row& r : bad)
+        for (const OutRatio* os : {static_cast<const OutRatio*>(nullptr), &x4})
+            for (int at : {0, 2})
+            { // the bad descriptor first and last of three; the slots behind it must stay untouched
+                rsr_image im[3] = {{p, 0, 0}, {p, 0, 0}, {p, 0, 0}};
+                if (os && r.fmt == RSR_FMT_NV12) continue; // (x4 of an odd width is even: it is the input descriptor that refuses this call)
+                im[at] = r.im;
+                std::vector<ImageRef> out(3); // exactly three: a write past the array is ASan's to report
+                const int rc = image_refs(3, im, r.fmt, r.w, H, r.c, os, "image", 0, out.data());
+                CHECK(rc == RSR_E_ARG);
+                CHECK(std::strstr(last_error(), at == 0 || r.w != W || r.fmt == 7 || r.c == 4 ? "image 0: " : "image 2: ") == last_error());
+                if (rc != RSR_E_ARG) std::fprintf(stderr, "  (%s, bad descriptor %d)\n", r.name, at);
+            }
+    // valid layouts
+    {
+        ImageRef out;
+        const rsr_image packed = {p, 0, 0};
+        CHECK(image_refs(1, &packed, RSR_FMT_U8_HWC, W, H, 3, nullptr, "image", 0, &out) == RSR_OK && out.data == p && out.row == 3 * W && out.plane == 0);
+        CHECK(image_refs(1, &packed, RSR_FMT_U8_HWC, W, H, 3, &x4, "image", 0, &out) == RSR_OK && out.row == 12 * W);
+        CHECK(image_refs(1, &packed, RSR_FMT_F32_CHW, W, H, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == 4 * W && out.plane == 4ll * W * H);
+        CHECK(image_refs(1, &packed, RSR_FMT_NV12, W, H, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == W && out.plane == (long long)W * H);
+        const rsr_image strided = {mem + 4, 4 * W + 20, (4 * W + 20) * (H + 3ll)};
+        CHECK(image_refs(1, &strided, RSR_FMT_F32_CHW, W, H, 3, nullptr, "previous output", -1, &out) == RSR_OK && out.data == mem + 4 && out.row == 4 * W + 20 &&
+              out.plane == (4 * W + 20) * (H + 3ll));
+        const rsr_image odd_u8 = {mem + 1, 3 * W + 1, 0};
+        CHECK(image_refs(1, &odd_u8, RSR_FMT_U8_HWC, W, H, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == 3 * W + 1);
+        const rsr_image far_row = {p, 0x7fffffffll, 0};
+        CHECK(image_refs(1, &far_row, RSR_FMT_U8_HWC, W, 3, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == 0x7fffffffll);
+        std::vector<rsr_image> many(16, packed);
+        std::vector<ImageRef> outs(16);
+        CHECK(image_refs(16, many.data(), RSR_FMT_F16_CHW, W, H, 3, nullptr, "image", 0, outs.data()) == RSR_OK && outs[15].row == 2 * W && outs[15].plane == 2ll * W * H);
+    }
+}
+
+static void batches()
+{
+    const int T = 200, P = 10, scale = 4;
+    std::vector<BaseTile> all;
+    long long cap = 0;
+    int mtw = 0, mth = 0;
+    image_tiles(1920, 1080, T, P, scale, 0, 60, 0, all, cap, mtw, mth);
+    CHECK(all.size() == 60 && mtw == T + 2 * P && cap == (long long)(T + 2 * P) * (T + 2 * P));
+    for (const bool tta : {false, true})
+        for (const int count : {1, 7, 60})
+            for (const bool fold : {false, true})
+            {
+                Plan::Batch b;
+                const int per = tta ? 8 : 1;
+                const size_t bytes = fill_batch(b, 3, count, [&](int i) { BaseTile t = all[size_t((i * 7) % 60)]; t.img = i % 3; return t; }, tta, P * scale, true, fold, 0);
+                CHECK(b.tile0 == 3 && b.ntiles == count && b.nslots == count * per && int(b.tiles.size()) == count && int(b.dims.size()) == count * per);
+                CHECK(b.trim4 == P * scale && bytes == batch_table_bytes(b) && bytes % 256 == 0);
+                for (int i = 0; i < count; i++) CHECK(b.tiles[size_t(i)].slot0 == i * per && b.tiles[size_t(i)].img == i % 3);
+                for (int lvl = 0; lvl < 3; lvl++)
+                {
+                    CHECK(int(b.item_start[lvl].size()) == b.nslots + 1 && b.item_start[lvl].back() == int(b.items[lvl].size()));
+                    for (const WorkItem& it : b.items[lvl])
+                    {
+                        CHECK(it.slot >= 0 && it.slot < b.nslots);
+                        const TileDim& d = b.dims[size_t(it.slot)];
+                        CHECK(it.H == d.h << lvl && it.W == d.w << lvl && it.y0 >= 0 && it.y0 < it.H && (it.x0 & ~kFoldBit) >= 0 && (it.x0 & ~kFoldBit) < it.W);
+                    }
+                }
+            }
+}
+
+int main()
+{
+    descriptors();
+    batches();
+    if (failures) return std::fprintf(stderr, "%d check(s) failed\n", failures), 1;
+    std::puts("descriptor_check ok");
+    return 0;
+}
