@@ -233,6 +233,45 @@ int rsr_out_size(int num, int den, int tilesize, int w, int h, int* ow, int* oh)
  * refuses.  For 4/1, 2/1 and 1/1 that is the rule of the YUV section ("Errors": tilesize * out_scale even). */
 int rsr_out_size_yuv(int num, int den, int tilesize, int w, int h, int* ow, int* oh);
 
+/* ---- a ratio per axis: DVD and HDV frames to square-pixel sizes (no reference counterpart) -------------------------------------------
+ * Frames whose pixels are not square need a different ratio along x and along y: NTSC DVD 720 x 480 -> 1920 x 1080 is 8/3 along x and 9/4
+ * along y, PAL DVD 720 x 576 -> 1920 x 1080 is 8/3 and 15/8, HDV / XDCAM 1440 x 1080 -> 1920 x 1080 is 4/3 and 1 (-> 3840 x 2160: 8/3 and
+ * 2), DVCPRO-HD 1280 x 1080 -> 1920 x 1080 is 3/2 and 1.  rsr_set_out_ratio_xy sets the pair; the area average is separable, so nothing
+ * but the two axes' taps and weights differ from rsr_set_out_ratio.
+ *   Each axis is reduced by its gcd; after that it needs 1 <= den <= 8 and 1 <= num / den <= 4: 67 ratios per axis (the 19 above; d = 5:
+ *            6/5 .. 19/5; d = 6: 7/6 .. 23/6; d = 7: 8/7 .. 27/7; d = 8: 9/8 .. 31/8 -- the eighths are what PAL needs).  A footprint then
+ *            has at most 5 taps per axis; the 19 ratios of rsr_set_out_ratio keep at most 4.  Anything else: RSR_E_ARG, the ratio in force
+ *            stays.  rsr_set_out_ratio, rsr_out_size, rsr_out_size_yuv and option "out_scale" keep their exact behaviour, every refusal
+ *            included (d <= 4 there; a lone 3 is no out_scale).
+ *   Equal axes.  rsr_set_out_ratio_xy(ctx, n, d, n, d) with n / d one of the 19 IS rsr_set_out_ratio(ctx, n, d): the same kernels,
+ *            launches, bytes and stats -- so 4/1, 2/1 and 1/1 on both axes are option "out_scale".  Any other pair is area-averaged, 4/1 x
+ *            2/1 and 15/8 x 15/8 included.  rsr_set_out_ratio and option "out_scale" afterwards set both axes again.
+ *   Stats    "out_num_x" / "out_den_x" / "out_num_y" / "out_den_y": the pair in force, always valid.  "out_num" / "out_den" read the common
+ *            reduced ratio while the axes agree and 0 / 0 while they differ; "out_scale" is as ever (4 / 2 / 1, else 0).
+ *   Sizes.   The output is (w * nx / dx) x (h * ny / dy) (rsr_out_size_xy).  Every entry point that honours a ratio honours the pair:
+ *            rsr_process, _many, _tiles, _rows, _group (whose members must agree on both axes), merged concurrent calls, _device, _fmt,
+ *            _batch with windows and pitches, _masked and _sequence (whose output rectangles and propagated rectangles are the per-axis
+ *            reduced ones).
+ *   Errors.  RSR_E_ARG at call time, before anything is launched, unless w * nx and tilesize * nx are multiples of dx, and h * ny and
+ *            tilesize * ny are multiples of dy.  No footprint then crosses a tile, and the reduction stays one per-tile launch.  A YUV
+ *            output (RSR_FMT_NV12 / RSR_FMT_P010) additionally needs w * nx / dx, tilesize * nx / dx, h * ny / dy and tilesize * ny / dy
+ *            EVEN, with "YUV" in rsr_last_error (rsr_out_size_yuv_xy).
+ *            720 x 480 at (8/3, 9/4) and tile 192: tile rectangle 512 x 432, output 1920 x 1080.  720 x 576 at (8/3, 15/8) and tile 192:
+ *            512 x 360.  1440 x 1080 at (4/3, 1) and tile 198: 264 x 198.  720 x 480 at (8/3, 9/4) and tile 200 is refused (200 * 8 is no
+ *            multiple of 3).
+ *   The definition, exact.  Steps 1 to 7 of rsr_set_out_ratio, with n, d, L per axis: the horizontal taps and weights (step 2) come from
+ *            (nx, Lx = 4 dx), the vertical ones (step 3) from (ny, Ly = 4 dy).  Step 4 reads m = min(V * fp32(1 / (16 dx dy)), 1), the
+ *            constant computed in double and rounded once; for dx = dy it is the constant above.  Alpha (step 6) uses the same per-axis
+ *            weights.  A YUV output is "Encode" applied to those pixels; the sited chroma filters clamp at the first column of every tile
+ *            rectangle (multiples of tilesize * nx / dx) and at its first row (multiples of tilesize * ny / dy). */
+int rsr_set_out_ratio_xy(rsr_ctx* ctx, int num_x, int den_x, int num_y, int den_y);
+/* Host-only (no GPU): *ow = w * nx / dx, *oh = h * ny / dy for the pair reduced per axis (either pointer may be NULL), or RSR_E_ARG for a
+ * pair outside the set above, or when the call-time rule above refuses w, h or tilesize. */
+int rsr_out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh);
+/* Host-only (no GPU): rsr_out_size_xy for a YUV 4:2:0 OUTPUT: RSR_E_ARG also for an odd w or h, or when one of the four quotients above is
+ * odd. */
+int rsr_out_size_yuv_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh);
+
 /* A device image behind its own pointer and pitches: a whole tensor, a crop of a larger frame, a frame inside a padded decoder surface, a
  * window of a canvas.  Pitches are in BYTES.  A uint8 row pitch need not be a multiple of the pixel size; for the planar formats both
  * pitches and `data` must be multiples of the element size (2 / 4).  No further alignment is asked of `data`. */
@@ -679,7 +718,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *                       rsr_process_group allocates only the output rows of its tile range)
  *   "last_test_us"      HIP-event time of the last rsr_conv3x3 / rsr_conv3x3_res launch (with option "test_repeat" = N the
  *                       work items are repeated N times in that one launch: an L2-resident workload)
- *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force (0: a ratio other than 4 / 2 / 1, "out_num" / "out_den": rsr_set_out_ratio); "yuv_matrix" / "yuv_range" / "yuv_siting": likewise
+ *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force (0: a ratio other than 4 / 2 / 1, "out_num" / "out_den": rsr_set_out_ratio; 0 / 0 while the axes differ, "out_num_x" / "out_den_x" / "out_num_y" / "out_den_y": rsr_set_out_ratio_xy); "yuv_matrix" / "yuv_range" / "yuv_siting": likewise
  *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
  *                       "selfcheck_overflow" (-1 before the first run) */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);

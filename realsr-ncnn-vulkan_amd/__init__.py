@@ -33,6 +33,7 @@ EXPORTS = [
     "rsr_process_device_batch", "rsr_image_span",
     "rsr_yuv_constants",
     "rsr_set_out_ratio", "rsr_out_size", "rsr_out_size_yuv",
+    "rsr_set_out_ratio_xy", "rsr_out_size_xy", "rsr_out_size_yuv_xy",
     "rsr_tile_count", "rsr_tile_source_rect", "rsr_diff_tiles", "rsr_process_device_masked",
     "rsr_sequence_sources", "rsr_diff_tiles_sequence", "rsr_process_device_sequence",
 ]
@@ -120,6 +121,9 @@ def lib():
     L.rsr_set_out_ratio.argtypes = [vp, ip, ip]
     L.rsr_out_size.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_out_size_yuv.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_set_out_ratio_xy.argtypes = [vp, ip, ip, ip, ip]
+    L.rsr_out_size_xy.argtypes = [ip, ip, ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_out_size_yuv_xy.argtypes = [ip, ip, ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_tile_count.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_tile_source_rect.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
     L.rsr_diff_tiles.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), ip, ip, ip, ip, vp, vp]
@@ -264,21 +268,70 @@ class RealSR:
         s = int(self.get_stat("out_scale"))
         if s:
             return fractions.Fraction(s)
-        return fractions.Fraction(int(self.get_stat("out_num")), int(self.get_stat("out_den")))
+        n, d = int(self.get_stat("out_num")), int(self.get_stat("out_den"))
+        if d == 0:  # the axes differ (rsr_set_out_ratio_xy): no single ratio describes the output
+            raise ValueError("the output ratio differs per axis (%s along x, %s along y): read out_ratio_xy" % self._ratio_pair())
+        return fractions.Fraction(n, d)
+
+    @staticmethod
+    def _nd(r):
+        if isinstance(r, (tuple, list)):
+            return int(r[0]), int(r[1])  # (as given: the engine reduces it, and refuses a zero denominator)
+        r = fractions.Fraction(r)
+        return r.numerator, r.denominator
 
     @out_ratio.setter
     def out_ratio(self, r):
-        if isinstance(r, (tuple, list)):
-            n, d = int(r[0]), int(r[1])  # (as given: the engine reduces it, and refuses a zero denominator)
-        else:
-            r = fractions.Fraction(r)
-            n, d = r.numerator, r.denominator
+        n, d = self._nd(r)
         self._ck(self._L.rsr_set_out_ratio(self._h, n, d))  # (a ratio outside the set raises RealSRError(RSR_E_ARG) and leaves the value alone)
 
+    @property
+    def out_ratio_xy(self):
+        """Size of the output relative to the input per axis, a pair of fractions.Fraction (x, y): DVD and HDV frames to square-pixel
+        sizes -- 720 x 480 -> 1920 x 1080 is (8/3, 9/4), 720 x 576 -> 1920 x 1080 (8/3, 15/8), 1440 x 1080 -> 1920 x 1080 (4/3, 1)
+        (rsr_set_out_ratio_xy, include/realsr_hip.h: each axis n / d with d in 1..8 and 1 <= n / d <= 4).  Set it with a pair whose
+        members are a Fraction, an (n, d) pair or an int.  Equal members among the ratios of out_ratio ARE out_ratio; setting out_ratio
+        or out_scale sets both axes again.  Takes effect for the next call.  Read from the engine."""
+        r, pair = self._ratio_or_pair()
+        return (r, r) if pair is None else pair
+
+    def _ratio_pair(self):  # the pair while the axes differ (stats of their own: out_num / out_den read 0 then)
+        return (fractions.Fraction(int(self.get_stat("out_num_x")), int(self.get_stat("out_den_x"))),
+                fractions.Fraction(int(self.get_stat("out_num_y")), int(self.get_stat("out_den_y"))))
+
+    @out_ratio_xy.setter
+    def out_ratio_xy(self, r):
+        if not isinstance(r, (tuple, list)) or len(r) != 2:
+            raise ValueError("out_ratio_xy takes a pair (x ratio, y ratio)")
+        (nx, dx), (ny, dy) = self._nd(r[0]), self._nd(r[1])
+        self._ck(self._L.rsr_set_out_ratio_xy(self._h, nx, dx, ny, dy))  # (a pair outside the set raises RealSRError(RSR_E_ARG) and leaves the value alone)
+
+    def _ratio_or_pair(self):
+        """(r, None) while one ratio of rsr_set_out_ratio serves both axes -- the engine calls the methods below have always made --,
+        else (None, (rx, ry)): the _xy stats and functions are consulted only then."""
+        s = int(self.get_stat("out_scale"))
+        if s:
+            return fractions.Fraction(s), None
+        n, d = int(self.get_stat("out_num")), int(self.get_stat("out_den"))
+        if d == 0:
+            return None, self._ratio_pair()
+        r = fractions.Fraction(n, d)
+        return (r, None) if r.denominator <= 4 else (None, (r, r))
+
+    def _out_size_xy(self, fn, pair, w, h, what):
+        rx, ry = pair
+        ow, oh = C.c_int(0), C.c_int(0)
+        if fn(rx.numerator, rx.denominator, ry.numerator, ry.denominator, int(self.tilesize), int(w), int(h), C.byref(ow), C.byref(oh)) != 0:
+            raise ValueError("%s %s x %s: %d x %d at tile %d: %s" % (what, rx, ry, w, h, self.tilesize, self._L.rsr_last_error(None).decode()))
+        return ow.value, oh.value
+
     def out_size(self, w, h):
-        """(ow, oh) of the output the next call writes for a w x h image: (w * n / d, h * n / d) at the ratio and tile size in force.
-        ValueError where the engine would refuse the call: w, h or tilesize times n is no multiple of d (rsr_out_size)."""
-        r = self.out_ratio
+        """(ow, oh) of the output the next call writes for a w x h image: (w * n / d, h * n / d) at the ratio and tile size in force --
+        (w * nx / dx, h * ny / dy) while out_ratio_xy holds a pair.  ValueError where the engine would refuse the call: w, h or tilesize
+        times n is no multiple of d, each axis with its own n / d (rsr_out_size, rsr_out_size_xy)."""
+        r, pair = self._ratio_or_pair()
+        if pair is not None:
+            return self._out_size_xy(self._L.rsr_out_size_xy, pair, w, h, "output ratios")
         if r.denominator == 1:
             return w * r.numerator, h * r.numerator
         ow, oh = C.c_int(0), C.c_int(0)
@@ -290,13 +343,20 @@ class RealSR:
     def out_size_yuv(self, w, h):
         """out_size for a YUV 4:2:0 OUTPUT (RSR_FMT_NV12 / RSR_FMT_P010): (w * n / d, h * n / d) at the ratio and tile size in force.
         ValueError where the engine would refuse the call: an odd w or h, w, h or tilesize times n no multiple of d, or one of
-        w * n / d, h * n / d and tilesize * n / d odd -- a 2 x 2 chroma quad would cross a tile or the image's edge (rsr_out_size_yuv)."""
-        r = self.out_ratio
+        w * n / d, h * n / d and tilesize * n / d odd -- a 2 x 2 chroma quad would cross a tile or the image's edge (rsr_out_size_yuv;
+        per axis while out_ratio_xy holds a pair: rsr_out_size_yuv_xy)."""
+        r, pair = self._ratio_or_pair()
+        if pair is not None:
+            return self._out_size_xy(self._L.rsr_out_size_yuv_xy, pair, w, h, "a YUV output at ratios")
         ow, oh = C.c_int(0), C.c_int(0)
         if self._L.rsr_out_size_yuv(r.numerator, r.denominator, int(self.tilesize), int(w), int(h), C.byref(ow), C.byref(oh)) != 0:
             raise ValueError("a YUV output at ratio %s: %d x %d at tile %d: w and h must be even, w, h and tilesize times %d multiples of %d, and "
                              "w, h and tilesize times %s even" % (r, w, h, self.tilesize, r.numerator, r.denominator, r))
         return ow.value, oh.value
+
+    def _ratio_text(self):  # for error texts: one ratio, or "rx x ry"
+        r, pair = self._ratio_or_pair()
+        return str(r) if pair is None else "%s x %s" % pair
 
     @property
     def yuv_siting(self):
@@ -459,7 +519,7 @@ class RealSR:
     def _check_full_out(self, out, h, w, c):
         ow, oh = self.out_size(w, h)
         if out.shape != (oh, ow, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous uint8 array of shape %s (output ratio %s), not %s %s" % ((oh, ow, c), self.out_ratio, out.dtype, out.shape))
+            raise ValueError("out must be a contiguous uint8 array of shape %s (output ratio %s), not %s %s" % ((oh, ow, c), self._ratio_text(), out.dtype, out.shape))
 
     def process_rows(self, img, out, row0, row1):
         """Tile rows [row0, row1) of img's tile grid into the full-size `out` (see rsr_process_rows)."""
@@ -731,7 +791,7 @@ def process_group(srs, img, out=None):
     if out is None:
         out = np.empty((oh, ow, c), dtype=np.uint8)
     if out.shape != (oh, ow, c) or out.dtype != np.uint8 or not out.flags.c_contiguous:
-        raise ValueError("out must be a contiguous uint8 array of shape %s (output ratio %s)" % ((oh, ow, c), srs[0].out_ratio))
+        raise ValueError("out must be a contiguous uint8 array of shape %s (output ratio %s)" % ((oh, ow, c), srs[0]._ratio_text()))
     hs = (C.c_void_p * len(srs))(*[s._h for s in srs])
     rc = L.rsr_process_group(hs, len(srs), _p(img), w, h, c, _p(out))
     if rc != 0:

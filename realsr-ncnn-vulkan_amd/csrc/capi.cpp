@@ -304,11 +304,11 @@ int rsr_out_size(int num, int den, int tilesize, int w, int h, int* ow, int* oh)
     rsr::OutRatio r;
     if (!rsr::out_ratio_reduce(num, den, &r)) return Engine::fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
     if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
-    if (!r.divides(w) || !r.divides(h) || !r.divides(tilesize))
-        return Engine::fail(RSR_E_ARG, "output ratio " + std::to_string(r.n) + "/" + std::to_string(r.d) + ": w, h and tilesize times " + std::to_string(r.n) +
-                                           " must be multiples of " + std::to_string(r.d));
-    if (ow) *ow = int(r.of(w));
-    if (oh) *oh = int(r.of(h));
+    if (!r.divides_x(w) || !r.divides_y(h) || !r.divides_x(tilesize))
+        return Engine::fail(RSR_E_ARG, "output ratio " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + ": w, h and tilesize times " + std::to_string(r.nx) +
+                                           " must be multiples of " + std::to_string(r.dx));
+    if (ow) *ow = int(r.of_x(w));
+    if (oh) *oh = int(r.of_y(h));
     return RSR_OK;
 }
 
@@ -318,14 +318,56 @@ int rsr_out_size_yuv(int num, int den, int tilesize, int w, int h, int* ow, int*
     if (!rsr::out_ratio_reduce(num, den, &r)) return Engine::fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
     if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
     if ((w | h) & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
-    const std::string what = "a YUV 4:2:0 output at ratio " + std::to_string(r.n) + "/" + std::to_string(r.d);
-    if (!r.divides(w) || !r.divides(h) || !r.divides(tilesize))
-        return Engine::fail(RSR_E_ARG, what + ": w, h and tilesize times " + std::to_string(r.n) + " must be multiples of " + std::to_string(r.d));
+    const std::string what = "a YUV 4:2:0 output at ratio " + std::to_string(r.nx) + "/" + std::to_string(r.dx);
+    if (!r.divides_x(w) || !r.divides_y(h) || !r.divides_x(tilesize))
+        return Engine::fail(RSR_E_ARG, what + ": w, h and tilesize times " + std::to_string(r.nx) + " must be multiples of " + std::to_string(r.dx));
     if (!rsr::yuv_out_even(r, w, h, tilesize))
-        return Engine::fail(RSR_E_ARG, what + " needs w, h and tilesize times " + std::to_string(r.n) + "/" + std::to_string(r.d) + " even");
-    if (ow) *ow = int(r.of(w));
-    if (oh) *oh = int(r.of(h));
+        return Engine::fail(RSR_E_ARG, what + " needs w, h and tilesize times " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + " even");
+    if (ow) *ow = int(r.of_x(w));
+    if (oh) *oh = int(r.of_y(h));
     return RSR_OK;
+}
+
+// ---- a ratio per axis (rsr_set_out_ratio_xy) ----------------------------------------------------------------------------------------
+static const char* const kBadRatioXY = "output ratios must reduce per axis to n / d with d in 1 .. 8 and 1 <= n / d <= 4";
+
+int rsr_set_out_ratio_xy(rsr_ctx* ctx, int num_x, int den_x, int num_y, int den_y)
+{
+    if (!ctx) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    rsr::OutRatio r;
+    if (!rsr::out_ratio_reduce_xy(num_x, den_x, num_y, den_y, &r)) return ctx->e.fail(RSR_E_ARG, kBadRatioXY);
+    ctx->e.out_ratio = r; // the next call's output is (w * nx / dx) x (h * ny / dy); equal axes ARE rsr_set_out_ratio (one state, one set of kernels)
+    return RSR_OK;
+}
+
+// The admission rule of a pair, shared by the two size functions: RSR_OK and the reduced pair, or the refusal.
+static int out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, bool yuv, int* ow, int* oh)
+{
+    rsr::OutRatio r;
+    if (!rsr::out_ratio_reduce_xy(num_x, den_x, num_y, den_y, &r)) return Engine::fail(RSR_E_ARG, kBadRatioXY);
+    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
+    if (yuv && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
+    const std::string what = std::string(yuv ? "a YUV 4:2:0 output at " : "") + "output ratios " + r.str();
+    if (!r.divides_x(w) || !r.divides_x(tilesize) || !r.divides_y(h) || !r.divides_y(tilesize))
+        return Engine::fail(RSR_E_ARG, what + ": w and tilesize times " + std::to_string(r.nx) + " must be multiples of " + std::to_string(r.dx) + ", h and tilesize times " +
+                                           std::to_string(r.ny) + " multiples of " + std::to_string(r.dy));
+    if (yuv && !rsr::yuv_out_even(r, w, h, tilesize))
+        return Engine::fail(RSR_E_ARG, what + " needs w and tilesize times " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + " and h and tilesize times " +
+                                           std::to_string(r.ny) + "/" + std::to_string(r.dy) + " even");
+    if (ow) *ow = int(r.of_x(w));
+    if (oh) *oh = int(r.of_y(h));
+    return RSR_OK;
+}
+
+int rsr_out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
+{
+    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, false, ow, oh);
+}
+
+int rsr_out_size_yuv_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
+{
+    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, true, ow, oh);
 }
 
 int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n)
@@ -648,8 +690,12 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "merged_mixed") *value = double(e.merged_mixed.load());
     else if (k == "precise_active") *value = e.precise ? 1.0 : 0.0;
     else if (k == "out_scale") *value = double(e.out_ratio.out_scale()); // (0 while a ratio other than 4, 2 or 1 is in force: rsr_set_out_ratio)
-    else if (k == "out_num") *value = double(e.out_ratio.n);
-    else if (k == "out_den") *value = double(e.out_ratio.d);
+    else if (k == "out_num") *value = double(e.out_ratio.same() ? e.out_ratio.nx : 0); // (0 / 0 while the axes differ: rsr_set_out_ratio_xy)
+    else if (k == "out_den") *value = double(e.out_ratio.same() ? e.out_ratio.dx : 0);
+    else if (k == "out_num_x") *value = double(e.out_ratio.nx);
+    else if (k == "out_den_x") *value = double(e.out_ratio.dx);
+    else if (k == "out_num_y") *value = double(e.out_ratio.ny);
+    else if (k == "out_den_y") *value = double(e.out_ratio.dy);
     else if (k == "yuv_matrix") *value = double(e.yuv_matrix);
     else if (k == "yuv_range") *value = double(e.yuv_range);
     else if (k == "yuv_siting") *value = double(e.yuv_siting);
@@ -697,7 +743,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     else if (k == "out_scale")
     { // the next call's output is (w * value) x (h * value): plans are keyed by it (below 4 conv_last leaves the planar blob to postproc_tiles_box)
         if (value != 1 && value != 2 && value != 4) return ctx->e.fail(RSR_E_ARG, "out_scale must be 1, 2 or 4");
-        ctx->e.out_ratio = rsr::OutRatio{int(value), 1}; // (leaves a fractional ratio, rsr_set_out_ratio, again)
+        ctx->e.out_ratio = rsr::OutRatio(int(value), 1); // (leaves a fractional ratio or a pair, rsr_set_out_ratio / _xy, again)
     }
     else if (k == "yuv_matrix")
     { // Kr / Kb of the NV12 / P010 formats; read when the next call is enqueued

@@ -1135,15 +1135,17 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     po.out_fmt = io.out_fmt;
     po.c = c;
     po.out_row0 = io.out_row0;
-    po.box = io.os.is_box() ? 4 / io.os.n : 1;
-    po.num = io.os.n;
-    po.den = io.os.d;
-    po.area_norm = float(1.0 / (16.0 * io.os.d * io.os.d));
+    po.box = io.os.is_box() ? 4 / io.os.nx : 1;
+    po.num = io.os.nx;
+    po.den = io.os.dx;
+    po.num_y = io.os.ny;
+    po.den_y = io.os.dy;
+    po.area_norm = float(1.0 / (16.0 * io.os.dx * io.os.dy));
     po.tilesize = tilesize;
     po.bgr = bgr ? 1 : 0;
     po.variant = variant;
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
-    mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) * io.os.n * io.os.n / (16.0 * io.os.d * io.os.d)), st);
+    mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) * io.os.nx * io.os.ny / (16.0 * io.os.dx * io.os.dy)), st);
     return RSR_OK;
 }
 
@@ -1426,7 +1428,8 @@ bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
 
 // A YUV output is written one 2 x 2 luma quad per thread, tile by tile: the image and every tile's rectangle must start and end on even
 // output pixels (only out_scale 1 can break that).  At a ratio n / d other than 4 / 2 / 1 (check_ratio_out has made w n / d, h n / d and
-// tilesize n / d whole) the same rule reads: those three are even (yuv_out_even, what rsr_out_size_yuv states).  mu held (tilesize).
+// tilesize n / d whole) the same rule reads: those three are even (yuv_out_even, what rsr_out_size_yuv states) -- per axis where the axes
+// differ: w nx / dx, tilesize nx / dx, h ny / dy and tilesize ny / dy (rsr_out_size_yuv_xy).  mu held (tilesize).
 int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
 {
     if (!fmt_is_yuv(out_fmt)) return RSR_OK;
@@ -1438,35 +1441,65 @@ int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
         return RSR_OK;
     }
     if (!yuv_out_even(ratio, w, h, tilesize))
-        return fail(RSR_E_ARG, "a YUV 4:2:0 output at ratio " + std::to_string(ratio.n) + "/" + std::to_string(ratio.d) + " needs w, h and tilesize times " +
-                                   std::to_string(ratio.n) + "/" + std::to_string(ratio.d) + " even (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " +
+    {
+        if (!ratio.same())
+            return fail(RSR_E_ARG, "a YUV 4:2:0 output at ratios " + ratio.str() + " needs w and tilesize times " + std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) +
+                                       " and h and tilesize times " + std::to_string(ratio.ny) + "/" + std::to_string(ratio.dy) + " even (" + std::to_string(w) + " x " +
+                                       std::to_string(h) + " at tile " + std::to_string(tilesize) + ")");
+        return fail(RSR_E_ARG, "a YUV 4:2:0 output at ratio " + std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) + " needs w, h and tilesize times " +
+                                   std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) + " even (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " +
                                    std::to_string(tilesize) + ")");
+    }
     return RSR_OK;
 }
 
-bool yuv_out_even(OutRatio r, long long w, long long h, long long T) { return !((r.of(w) | r.of(h) | r.of(T)) & 1); }
+bool yuv_out_even(OutRatio r, long long w, long long h, long long T) { return !((r.of_x(w) | r.of_y(h) | r.of_x(T) | r.of_y(T)) & 1); }
 
-// ---- rational output scales (rsr_set_out_ratio) -----------------------------------------------------------------------------------------
-bool out_ratio_reduce(int num, int den, OutRatio* out)
+// ---- rational output scales (rsr_set_out_ratio, rsr_set_out_ratio_xy) ---------------------------------------------------------------------
+// num / den in lowest terms when den <= max_den and 1 <= num / den <= 4
+static bool axis_reduce(int num, int den, int max_den, int* n_out, int* d_out)
 {
     if (num < 1 || den < 1) return false;
     int a = num, b = den;
     while (b) { const int t = a % b; a = b; b = t; }
     const int n = num / a, d = den / a;
-    if (d > 4 || n < d || n > 4 * d) return false;
-    out->n = n, out->d = d;
+    if (d > max_den || n < d || n > 4 * d) return false;
+    *n_out = n, *d_out = d;
+    return true;
+}
+
+bool out_ratio_reduce(int num, int den, OutRatio* out)
+{
+    int n, d;
+    if (!axis_reduce(num, den, 4, &n, &d)) return false;
+    *out = OutRatio(n, d);
+    return true;
+}
+
+bool out_ratio_reduce_xy(int num_x, int den_x, int num_y, int den_y, OutRatio* out)
+{
+    int nx, dx, ny, dy;
+    if (!axis_reduce(num_x, den_x, 8, &nx, &dx) || !axis_reduce(num_y, den_y, 8, &ny, &dy)) return false;
+    *out = OutRatio(nx, dx, ny, dy);
     return true;
 }
 
 // An output pixel of scale n / d is a whole number of them only where the image's sides times n are multiples of d; and only where the
 // tile size times n is one too does every tile's rectangle start on a whole output pixel, so that no averaging footprint crosses a tile
-// (postproc_tiles_area is a per-tile launch).  Always true for 4, 2 and 1.  Checked before anything is launched.
+// (postproc_tiles_area is a per-tile launch).  Always true for 4, 2 and 1.  Checked before anything is launched.  With a ratio per axis
+// (rsr_set_out_ratio_xy) w and the tile size answer to the x ratio, h and the tile size to the y ratio.
 int Engine::check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const
 {
     if (os.is_box()) return RSR_OK;
-    if (!os.divides(w) || !os.divides(h) || !os.divides(T)) // (a YUV output: check_yuv_out then asks for even quotients as well)
-        return fail(RSR_E_ARG, std::string(fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "") + "output ratio " + std::to_string(os.n) + "/" + std::to_string(os.d) + ": w, h and tilesize times " + std::to_string(os.n) +
-                                   " must be multiples of " + std::to_string(os.d) + " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
+    if (!os.divides_x(w) || !os.divides_y(h) || !os.divides_x(T) || !os.divides_y(T)) // (a YUV output: check_yuv_out then asks for even quotients as well)
+    {
+        if (!os.same())
+            return fail(RSR_E_ARG, std::string(fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "") + "output ratios " + os.str() + ": w and tilesize times " + std::to_string(os.nx) +
+                                       " must be multiples of " + std::to_string(os.dx) + ", h and tilesize times " + std::to_string(os.ny) + " multiples of " + std::to_string(os.dy) +
+                                       " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
+        return fail(RSR_E_ARG, std::string(fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "") + "output ratio " + std::to_string(os.nx) + "/" + std::to_string(os.dx) + ": w, h and tilesize times " + std::to_string(os.nx) +
+                                   " must be multiples of " + std::to_string(os.dx) + " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
+    }
     return RSR_OK;
 }
 
@@ -1495,7 +1528,7 @@ int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long pl
 
 int image_refs(int n, const rsr_image* im, int fmt, int w, int h, int c, const OutRatio* os, const char* what, int index0, ImageRef* out)
 {
-    const int iw = os ? int(os->of(w)) : w, ih = os ? int(os->of(h)) : h;
+    const int iw = os ? int(os->of_x(w)) : w, ih = os ? int(os->of_y(h)) : h;
     for (int i = 0; i < n; i++)
     {
         const char* why = nullptr;
@@ -1658,7 +1691,7 @@ int Engine::diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image*
     return RSR_OK;
 }
 
-// The byte rectangles of output tile `tile` of an os.of(w) x os.of(h) image in out_fmt, from the image `src` to the image `dst`: one for
+// The byte rectangles of output tile `tile` of an os.of_x(w) x os.of_y(h) image in out_fmt, from the image `src` to the image `dst`: one for
 // uint8 HWC, three for the planar formats, Y and UV for the surfaces (the UV rectangle has the byte columns of the Y rectangle and half its
 // rows; check_yuv_out has made its edges even).
 static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, int tile, const ImageRef& dst, const ImageRef& src, std::vector<PropRect>& out)
@@ -1668,7 +1701,7 @@ static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, i
     const long long dp = dst.row, dpl = dst.plane, sp = src.row, spl = src.plane;
     const int nx = (w + T - 1) / T, yi = tile / nx, xi = tile - yi * nx;
     const long long es = BatchIO::px_bytes(out_fmt, c);
-    const long long x0 = os.of((long long)xi * T), y0 = os.of((long long)yi * T), x1 = os.of(std::min((xi + 1) * T, w)), y1 = os.of(std::min((yi + 1) * T, h));
+    const long long x0 = os.of_x((long long)xi * T), y0 = os.of_y((long long)yi * T), x1 = os.of_x(std::min((xi + 1) * T, w)), y1 = os.of_y(std::min((yi + 1) * T, h));
     const int width = int((x1 - x0) * es), rows = int(y1 - y0);
     const int nplanes = out_fmt == RSR_FMT_U8_HWC || fmt_is_yuv(out_fmt) ? 1 : 3;
     for (int q = 0; q < nplanes; q++)
@@ -2002,7 +2035,7 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
         mwidth = merge_width(w, h, c);
         if (mwidth > 1) mitems = image_items(w, h, merge_target_items);
     }
-    const size_t nout_full = size_t(os.of(w)) * size_t(os.of(h)) * c;
+    const size_t nout_full = size_t(os.of_x(w)) * size_t(os.of_y(h)) * c;
     const int xtiles = (w + T - 1) / T, ytiles = (h + T - 1) / T;
     if (tile1 < 0) tile1 = xtiles * ytiles;
     if (tile0 < 0 || tile1 > xtiles * ytiles || tile0 >= tile1) return fail(RSR_E_ARG, "tile range outside the image");
@@ -2050,9 +2083,9 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
     // The device output holds only the output ROWS of this call's tile range (a member of rsr_process_group running an eighth
     // of a 4K frame does not allocate 398 MB for it): the kernels get the address row 0 would have and only ever write
     // inside the rectangles of the range's tiles (conv_last / postproc_tiles place by tile), i.e. inside the allocation.
-    const size_t rowbytes = size_t(os.of(w)) * c; // one output row
-    auto yof = [&](int tr) { return size_t(os.of(std::min(tr * T, h))); };  // first output row of tile row tr (whole: check_ratio_out)
-    auto xof = [&](int tc) { return size_t(os.of(std::min(tc * T, w))) * c; }; // byte column of tile column tc
+    const size_t rowbytes = size_t(os.of_x(w)) * c; // one output row
+    auto yof = [&](int tr) { return size_t(os.of_y(std::min(tr * T, h))); };  // first output row of tile row tr (whole: check_ratio_out)
+    auto xof = [&](int tc) { return size_t(os.of_x(std::min(tc * T, w))) * c; }; // byte column of tile column tc
     const int r0 = tile0 / xtiles, c0 = tile0 % xtiles, r1 = (tile1 - 1) / xtiles, c1 = (tile1 - 1) % xtiles + 1; // last tile = (r1, c1 - 1)
     const size_t base_off = yof(r0) * rowbytes;
     if ((rc = ensure(L->d_out, (yof(r1 + 1) - yof(r0)) * rowbytes)) != RSR_OK) return rc;

@@ -39,21 +39,33 @@
 
 namespace rsr {
 
-// The size of the output relative to the input, n / d in lowest terms (include/realsr_hip.h rsr_set_out_ratio).  4 / 1, 2 / 1 and 1 / 1 are
-// option "out_scale" 4 / 2 / 1 and take its kernels; every other permitted ratio is area-averaged by postproc_tiles_area.
+// The size of the output relative to the input, per axis: nx / dx along x and ny / dy along y, each in lowest terms
+// (include/realsr_hip.h rsr_set_out_ratio, rsr_set_out_ratio_xy).  4 / 1, 2 / 1 and 1 / 1 on BOTH axes are option "out_scale" 4 / 2 / 1
+// and take its kernels; every other permitted pair is area-averaged by postproc_tiles_area.
 struct OutRatio
 {
-    int n = 4, d = 1;
-    bool operator==(const OutRatio& o) const { return n == o.n && d == o.d; }
+    int nx = 4, dx = 1, ny = 4, dy = 1;
+    OutRatio() = default;
+    OutRatio(int n, int d) : nx(n), dx(d), ny(n), dy(d) {} // one ratio on both axes
+    OutRatio(int nx0, int dx0, int ny0, int dy0) : nx(nx0), dx(dx0), ny(ny0), dy(dy0) {}
+    bool operator==(const OutRatio& o) const { return nx == o.nx && dx == o.dx && ny == o.ny && dy == o.dy; }
     bool operator!=(const OutRatio& o) const { return !(*this == o); }
-    bool is_box() const { return d == 1 && (n == 4 || n == 2 || n == 1); }
-    int out_scale() const { return is_box() ? n : 0; }                 // what stat "out_scale" reads
-    long long of(long long x) const { return x * n / d; }              // an input length in output pixels (exact where the call was admitted)
-    bool divides(long long x) const { return x * n % d == 0; }
+    bool same() const { return nx == ny && dx == dy; }                      // one ratio on both axes (what stats "out_num" / "out_den" can read)
+    bool is_box() const { return same() && dx == 1 && (nx == 4 || nx == 2 || nx == 1); }
+    int out_scale() const { return is_box() ? nx : 0; }                     // what stat "out_scale" reads
+    long long of_x(long long x) const { return x * nx / dx; }               // an input length in output pixels (exact where the call was admitted)
+    long long of_y(long long y) const { return y * ny / dy; }
+    bool divides_x(long long x) const { return x * nx % dx == 0; }
+    bool divides_y(long long y) const { return y * ny % dy == 0; }
+    std::string str() const { return same() ? std::to_string(nx) + "/" + std::to_string(dx) : std::to_string(nx) + "/" + std::to_string(dx) + " x " + std::to_string(ny) + "/" + std::to_string(dy); }
 };
-// Host-only: num / den reduced to lowest terms when it is one of the permitted ratios (d in 1..4, 1 <= n / d <= 4), else false.
+// Host-only: num / den reduced to lowest terms on both axes when it is one of the permitted ratios of rsr_set_out_ratio (d in 1..4,
+// 1 <= n / d <= 4), else false.
 bool out_ratio_reduce(int num, int den, OutRatio* out);
-// Host-only: are w n / d, h n / d and T n / d (whole: OutRatio::divides) all even -- what a YUV 4:2:0 output asks of image and tile size?
+// Host-only: the pair reduced per axis when each axis is one of the permitted ratios of rsr_set_out_ratio_xy (d in 1..8, 1 <= n / d <= 4).
+bool out_ratio_reduce_xy(int num_x, int den_x, int num_y, int den_y, OutRatio* out);
+// Host-only: are w nx / dx, T nx / dx, h ny / dy and T ny / dy (whole: OutRatio::divides_*) all even -- what a YUV 4:2:0 output asks of
+// image and tile size?
 bool yuv_out_even(OutRatio r, long long w, long long h, long long T);
 
 struct DevBuf
@@ -142,7 +154,7 @@ struct MergeReq
     const void* d_in = nullptr;
     void* d_out = nullptr;
     int w = 0, h = 0, c = 0, T = 0;
-    OutRatio os;                  // Engine::out_ratio when the call came in: d_out is os.of(w) x os.of(h)
+    OutRatio os;                  // Engine::out_ratio when the call came in: d_out is os.of_x(w) x os.of_y(h)
     long long items = 0;          // LR-level work items of the image (Engine::image_items)
     int width = 1;                // Engine::merge_width of its geometry when the call came in
     hipEvent_t ev_in = nullptr;   // the input is complete behind this event (null: it already is)
@@ -185,15 +197,15 @@ struct BatchIO
 {
     int nimg = 0, c = 0;        // images of the batch (<= kMaxMerge; BaseTile::img selects) and their channel count
     const void* in[kMaxMerge];  // per image: the device image, in_fmt, w[i] x h[i] ...
-    void* out[kMaxMerge];       // ... and its os.of(w[i]) x os.of(h[i]) result, out_fmt
-    OutRatio os;                // Engine::out_ratio of the call: 4, or 2 / 1 = the x4 result box-reduced (kernels.h PostArgs::box = 4 / os), or another ratio = area-averaged (PostArgs::num / den)
+    void* out[kMaxMerge];       // ... and its os.of_x(w[i]) x os.of_y(h[i]) result, out_fmt
+    OutRatio os;                // Engine::out_ratio of the call: 4, or 2 / 1 = the x4 result box-reduced (kernels.h PostArgs::box = 4 / os), or another ratio or pair = area-averaged (PostArgs::num / den per axis)
     int w[kMaxMerge], h[kMaxMerge];
     // Bytes from one row / one plane (planar formats) of an image to the next, resolved (never 0; rsr_image of the C ABI, image_layout).
     // set() takes them from two ImageRefs (what image_refs made of the caller's descriptors), or packs them tightly itself.
     long long in_pitch[kMaxMerge], in_plane[kMaxMerge], out_pitch[kMaxMerge], out_plane[kMaxMerge];
     int in_fmt = RSR_FMT_U8_HWC, out_fmt = RSR_FMT_U8_HWC; // RSR_FMT_* (the planar float and the YUV formats come with whole images of c == 3 only;
                                                            // YUV: the plane pitch is the distance from Y(0,0) to the UV plane)
-    int out_row0 = 0;           // `out` points at output row os.of(out_row0) / 4 of the image; out_row0 counts x4 rows (a tile range's device buffer holds only its rows)
+    int out_row0 = 0;           // `out` points at output row os.of_y(out_row0) / 4 of the image; out_row0 counts x4 rows (a tile range's device buffer holds only its rows)
     int split_slot = 0;         // > 0: the 4x tail is split in front of this slot and ...
     hipEvent_t ev_half = nullptr; // ... this event recorded behind the first part (the caller starts downloading its output rows)
     hipEvent_t ev_mid = nullptr;  // recorded behind the middle RDB (a merged batch's throttle event, Engine::submit_merged)
@@ -227,7 +239,7 @@ struct BatchIO
     }
     void set(int i, const void* d_in, void* d_out, int wi, int hi) // ... both tightly packed
     {
-        set(i, packed(d_in, in_fmt, wi, hi, c), packed(d_out, out_fmt, os.of(wi), os.of(hi), c), wi, hi);
+        set(i, packed(d_in, in_fmt, wi, hi, c), packed(d_out, out_fmt, os.of_x(wi), os.of_y(hi), c), wi, hi);
     }
 };
 
@@ -262,6 +274,7 @@ struct Engine
     // out_ratio generalises it (rsr_set_out_ratio): n / d with d in 1..4 and 1 <= n / d <= 4.  For a scale that is not 4, 2 or 1 the footprint of
     // an output pixel is up to 4 x 4 x4 pixels with integer weights; whenever tilesize * n is a multiple of d a tile's rectangle starts on a
     // whole output pixel, no footprint crosses a tile, and the reduction is still ONE per-tile launch (postproc_tiles_area).
+    // rsr_set_out_ratio_xy gives each axis a ratio of its own (d in 1..8: up to 5 taps per axis); the rule above then holds per axis.
     OutRatio out_ratio;
     // YUV <-> RGB of the NV12 / P010 device formats (options "yuv_matrix", "yuv_range"; include/realsr_hip.h): Kr / Kb of BT.709, 601 or
     // 2020, limited (0) or full (1) range.  Read when a call is enqueued: the constants travel with the launch (kernels.h YuvCoef).

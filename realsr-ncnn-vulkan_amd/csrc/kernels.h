@@ -219,8 +219,13 @@ struct PostArgs
     // Area-averaged output at a rational scale num / den in lowest terms (rsr_set_out_ratio; den in 1..4, 1 <= num / den <= 4) that is not
     // 4, 2 or 1 -- those are `box` above, and num = 0 / 4 with box <= 1 is the x4 image --: postproc_tiles_area, the outs are
     // (w * num / den) x (h * num / den).  Everything above stays in x4 units; the kernel converts with * num / (4 * den), exact because the
-    // engine refuses a call whose image or tile size times num is not a multiple of den.  area_norm = fp32(1 / (16 * den * den)).
+    // engine refuses a call whose image or tile size times num is not a multiple of den.
+    // num / den is the ratio along x; num_y / den_y the one along y (rsr_set_out_ratio_xy; den up to 8 there, so a footprint has up to 5
+    // taps per axis) -- equal to num / den wherever one ratio serves both axes.  The outs are (w * num / den) x (h * num_y / den_y), columns
+    // convert with * num / (4 * den), rows with * num_y / (4 * den_y); a pair that differs is never `box`, whatever its two ratios.
+    // area_norm = fp32(1 / (16 * den * den_y)).
     int num, den;
+    int num_y, den_y;
     float area_norm;
     YuvCoef yuv; // out_fmt kFmtNV12 / kFmtP010 only
     // ... likewise: the chroma siting (engine option "yuv_siting": 0 centre, 1 left, 2 top-left).  The sited chroma filters clamp at the

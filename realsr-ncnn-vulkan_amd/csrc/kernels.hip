@@ -5,7 +5,7 @@
 //                          (_lds: rows staged in LDS, dword loads / 1-KiB stores, transposed TTA variants through an LDS tile;
 //                          chosen per launch by measurement: launch_*_tiles)
 //   postproc_tiles_box     the image box-reduced to x2 / x1 (out_scale)
-//   postproc_tiles_area    the image area-averaged to any other ratio (rsr_set_out_ratio)
+//   postproc_tiles_area    the image area-averaged to any other ratio, or to a ratio per axis (rsr_set_out_ratio, rsr_set_out_ratio_xy)
 //   preproc_tiles<., true> an NV12 / P010 surface as the source (YUV -> RGB inside the kernel)
 //   postproc_tiles_yuv[_area]   an NV12 / P010 surface as the destination, at out_scale 4 / 2 / 1 [at any other ratio]
 //   *_shader               the same arithmetic in the shaders' own memory layout (parity tests; independent of everything below)
@@ -802,19 +802,20 @@ static void launch_postproc_box(const PostArgs& a, int max_ow, int max_oh, hipSt
 }
 
 // ---- area-averaged output at a rational scale (rsr_set_out_ratio: PostArgs::num / den, e.g. 3/2, 4/3, 9/4, 3/1) -------------------------
-// The area-average loop nest of output pixel (X, Y) of a tile's rectangle at the scale n / d, L = 4 d.  On the integer grid where x4
+// The area-average loop nest of output pixel (X, Y) of a tile's rectangle at the scale n / d, L = 4 d -- per axis: (nx, Lx) along x,
+// (ny, Ly) along y (rsr_set_out_ratio_xy; one ratio on both axes passes it twice).  On the integer grid where x4
 // pixel i covers [i n, (i + 1) n) and output pixel X covers [X L, (X + 1) L), its taps along an axis are i = floor(X L / n) ..
-// floor(((X + 1) L - 1) / n) -- at most 4 -- with the integer weights g_i = the overlap, which sum to L.  include/realsr_hip.h
+// floor(((X + 1) L - 1) / n) -- at most 4 (d <= 4) or 5 (d <= 8) -- with the integer weights g_i = the overlap, which sum to L.  include/realsr_hip.h
 // (rsr_set_out_ratio) fixes the arithmetic: horizontally H = g c, H = H + g c in ascending i, then vertically the same over the rows' H,
 // every product and sum rounded by itself.  row(j), called once per tap row, returns that row's tap function: tap(i) is the value c of
-// x4 pixel (i, j) of the tile's kept rectangle.  The caller multiplies the sum V it gets by fp32(1 / (16 d^2)).
+// x4 pixel (i, j) of the tile's kept rectangle.  The caller multiplies the sum V it gets by fp32(1 / (16 dx dy)).
 // The ratio is a runtime argument: the tap loops have no arrays to index, so nothing is gained by unrolling them per ratio.
 // Used by area_pixel (colour) and by postproc_tiles_area's alpha.
 template <typename ROW>
-__device__ __forceinline__ float area_sum(int n, int L, int X, int Y, ROW row)
+__device__ __forceinline__ float area_sum(int nx, int Lx, int ny, int Ly, int X, int Y, ROW row)
 {
-    const int x0 = X * L, x1 = x0 + L, y0 = Y * L, y1 = y0 + L;                   // the pixel's footprint on the grid
-    const int ix0 = x0 / n, ix1 = (x1 - 1) / n, iy0 = y0 / n, iy1 = (y1 - 1) / n; // its taps
+    const int x0 = X * Lx, x1 = x0 + Lx, y0 = Y * Ly, y1 = y0 + Ly;                   // the pixel's footprint on the two grids
+    const int ix0 = x0 / nx, ix1 = (x1 - 1) / nx, iy0 = y0 / ny, iy1 = (y1 - 1) / ny; // its taps
     float V = 0.f;
 #pragma unroll 1
     for (int j = iy0; j <= iy1; j++)
@@ -824,22 +825,22 @@ __device__ __forceinline__ float area_sum(int n, int L, int X, int Y, ROW row)
 #pragma unroll 1
         for (int i = ix0; i <= ix1; i++)
         {
-            const float p = mul_rn((float)(min(x1, (i + 1) * n) - max(x0, i * n)), tap(i));
+            const float p = mul_rn((float)(min(x1, (i + 1) * nx) - max(x0, i * nx)), tap(i));
             H = i == ix0 ? p : add_rn(H, p);
         }
-        const float p = mul_rn((float)(min(y1, (j + 1) * n) - max(y0, j * n)), H);
+        const float p = mul_rn((float)(min(y1, (j + 1) * ny) - max(y0, j * ny)), H);
         V = j == iy0 ? p : add_rn(V, p);
     }
     return V;
 }
 
-// ONE pixel d(X, Y) of a tile's output rectangle at the scale n / d of one channel's blob -- what RSR_FMT_F32_CHW holds for it: every tap
+// ONE pixel d(X, Y) of a tile's output rectangle at the scales nx / dx, ny / dy of one channel's blob -- what RSR_FMT_F32_CHW holds for it: every tap
 // clamped to [0, 1] (TTA: the eight variants merged first), fetched one at a time through merged_block<TP, 1>, and m = min(V * norm, 1).
 // (X, Y) are the tile's own coordinates, which are the image's.  postproc_tiles_area and postproc_tiles_yuv_area.
 template <typename TP>
-__device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, int h, int crop, int tta, int n, int L, float norm, int X, int Y)
+__device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, int h, int crop, int tta, int nx, int Lx, int ny, int Ly, float norm, int X, int Y)
 {
-    const float V = area_sum(n, L, X, Y, [&](int j) {
+    const float V = area_sum(nx, Lx, ny, Ly, X, Y, [&](int j) {
         return [&, j](int i) {
             float c[1][1];
             merged_block<TP, 1>(b, ss, w, h, i + crop, j + crop, tta, c);
@@ -851,7 +852,7 @@ __device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, in
 
 // The sibling of postproc_tiles_box for the scales n / d that are not 4, 2 or 1: one thread makes ONE output pixel (X, Y) of the tile's
 // rectangle, area_pixel per channel.  A tile's kept x4 rectangle starts on a multiple of L grid units (the engine refuses the call
-// otherwise: tilesize * n is a multiple of d), so the tile's own coordinates are the image's and no footprint crosses a tile.  Lanes run
+// otherwise: tilesize * n is a multiple of d, on each axis with its own n / d), so the tile's own coordinates are the image's and no footprint crosses a tile.  Lanes run
 // along x, so a wave's loads of one tap row fall into a few cache lines.  One channel at a time, as in the box kernel.
 // ALPHA: PostArgs::c == 4, the bicubic x4 alpha, clamped to [0, 255], under the same weights, order and constant.
 template <typename TP, typename TO, bool ALPHA>
@@ -859,28 +860,28 @@ __global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
     const int im = __builtin_amdgcn_readfirstlane(t.img);
-    const int n = a.num, L = 4 * a.den;
+    const int nx = a.num, Lx = 4 * a.den, ny = a.num_y, Ly = 4 * a.den_y;
     const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (gx >= t.out_w * n / L || gy >= t.out_h * n / L) return;
+    if (gx >= t.out_w * nx / Lx || gy >= t.out_h * ny / Ly) return;
     const int w = t.tw * 4, h = t.th * 4;
     const long long cstep = (long long)w * h;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const long long ss = a.slot_stride / (long long)sizeof(TP);
     constexpr int es = sizeof(TO) == 1 ? 1 : (int)sizeof(TO);
-    uint8_t* const o = a.outs[im] + ((long long)(t.out_y - a.out_row0) * n / L + gy) * (long long)a.out_pitch[im] +
-                       ((long long)t.out_x * n / L + gx) * (sizeof(TO) == 1 ? a.c : es);
+    uint8_t* const o = a.outs[im] + ((long long)(t.out_y - a.out_row0) * ny / Ly + gy) * (long long)a.out_pitch[im] +
+                       ((long long)t.out_x * nx / Lx + gx) * (sizeof(TO) == 1 ? a.c : es);
 #pragma unroll 1
     for (int q = 0; q < 3; q++)
     {
-        const float m = area_pixel<TP>(b0 + q * cstep, ss, w, h, a.crop, a.tta, n, L, a.area_norm, gx, gy);
+        const float m = area_pixel<TP>(b0 + q * cstep, ss, w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, gx, gy);
         const int qo = a.bgr ? 2 - q : q;
         if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)m;
         else o[qo] = post_store(m * 255.f);
     }
     if constexpr (ALPHA)
     {
-        const float V = area_sum(n, L, gx, gy, [&](int j) {
+        const float V = area_sum(nx, Lx, ny, Ly, gx, gy, [&](int j) {
             int by;
             float cy[4];
             cubic_coeffs(t.out_h / 4, t.out_h, j, by, cy);
@@ -898,8 +899,8 @@ __global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
 template <typename TP>
 static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
-    const int L = 4 * a.den;
-    const dim3 grid((max_ow * a.num / L + 63) / 64, (max_oh * a.num / L + 3) / 4, a.ntiles), block(256);
+    const int Lx = 4 * a.den, Ly = 4 * a.den_y;
+    const dim3 grid((max_ow * a.num / Lx + 63) / 64, (max_oh * a.num_y / Ly + 3) / 4, a.ntiles), block(256);
     if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_area<TP, _Float16, false>), grid, block, 0, st, a);
     else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_area<TP, float, false>), grid, block, 0, st, a);
     else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true>), grid, block, 0, st, a);
@@ -945,8 +946,8 @@ __device__ __forceinline__ float out_pixel(const TP* b, long long ss, int w, int
 }
 
 // Where yuv_quad takes the RGB value d of an output pixel from, b the channel's blob -- what RSR_FMT_F32_CHW holds for that pixel: quad(b, d)
-// = the four d of the thread's 2 x 2 quad, at(b, ox, oy) = ONE d, ox / oy output pixels beside the quad's first; out(v) = a length v of the
-// x4 image in output pixels.
+// = the four d of the thread's 2 x 2 quad, at(b, ox, oy) = ONE d, ox / oy output pixels beside the quad's first; out_x(v) / out_y(v) = a
+// length v of the x4 image in output columns / rows.
 // QuadBox: out_scale OS = 4, 2 or 1 (K = 4 / OS x4 pixels per output pixel and axis; (sx, sy) the quad's first x4 pixel in the blob).
 // The quad is the 2K x 2K block in one or four merged_block fetches; a neighbour is out_pixel at (sx + K ox, sy + K oy), K-aligned like
 // sx and sy.
@@ -984,17 +985,19 @@ struct QuadBox
         }
     }
     __device__ __forceinline__ float at(const TP* b, int ox, int oy) const { return out_pixel<TP, K>(b, ss, w, h, sx + K * ox, sy + K * oy, tta); }
-    __device__ __forceinline__ int out(int v) const { return v / K; }
+    __device__ __forceinline__ int out_x(int v) const { return v / K; }
+    __device__ __forceinline__ int out_y(int v) const { return v / K; }
 };
 
-// QuadArea: any other ratio n / d (rsr_set_out_ratio); (px, py) the quad's first output pixel in the tile's rectangle.  Every d is
-// area_pixel.  Every tap index stays inside the tile's kept rectangle as in postproc_tiles_area: X < out_w n / L gives
-// ((X + 1) L - 1) / n <= out_w - 1.
+// QuadArea: any other ratio n / d or pair of ratios (rsr_set_out_ratio, rsr_set_out_ratio_xy); (px, py) the quad's first output pixel in
+// the tile's rectangle.  Every d is area_pixel.  Every tap index stays inside the tile's kept rectangle as in postproc_tiles_area:
+// X < out_w nx / Lx gives ((X + 1) Lx - 1) / nx <= out_w - 1, and the rows likewise.  out_x(v) / out_y(v) = a length v of the x4 image in
+// output columns / rows.
 template <typename TP>
 struct QuadArea
 {
     long long ss;
-    int w, h, crop, tta, n, L;
+    int w, h, crop, tta, nx, Lx, ny, Ly;
     float norm;
     int px, py;
     __device__ __forceinline__ void quad(const TP* b, float (&d)[2][2]) const
@@ -1004,8 +1007,9 @@ struct QuadArea
 #pragma unroll
             for (int i = 0; i < 2; i++) d[j][i] = at(b, i, j);
     }
-    __device__ __forceinline__ float at(const TP* b, int ox, int oy) const { return area_pixel<TP>(b, ss, w, h, crop, tta, n, L, norm, px + ox, py + oy); }
-    __device__ __forceinline__ int out(int v) const { return v * n / L; }
+    __device__ __forceinline__ float at(const TP* b, int ox, int oy) const { return area_pixel<TP>(b, ss, w, h, crop, tta, nx, Lx, ny, Ly, norm, px + ox, py + oy); }
+    __device__ __forceinline__ int out_x(int v) const { return v * nx / Lx; }
+    __device__ __forceinline__ int out_y(int v) const { return v * ny / Ly; }
 };
 
 // ONE 2 x 2 quad of luma samples and the (U, V) pair they share, quad (gx, gy) of tile t's rectangle: what a thread of
@@ -1060,7 +1064,7 @@ __device__ __forceinline__ void yuv_quad(const PostArgs& a, const BaseTile& t, i
         if (q == 2) bm = m;
     }
     const long long pitch = a.out_pitch[im];
-    const int X = src.out(t.out_x) + 2 * gx, Y = src.out(t.out_y - a.out_row0) + 2 * gy; // the quad's first luma sample
+    const int X = src.out_x(t.out_x) + 2 * gx, Y = src.out_y(t.out_y - a.out_row0) + 2 * gy; // the quad's first luma sample
     uint8_t* const oy = a.outs[im] + Y * pitch + (long long)X * (int)sizeof(TO);
 #pragma unroll
     for (int j = 0; j < 2; j++)
@@ -1090,28 +1094,29 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
 }
 
 // The sibling of postproc_tiles_yuv for the scales n / d that are not 4, 2 or 1: yuv_quad over QuadArea.  A tile's rectangle is
-// tilesize * n / d output pixels and starts at its multiples; the engine admits the call only where that, w * n / d and h * n / d are
-// even (check_yuv_out), so no quad crosses a tile or the image's edge.  Lanes run along x.
+// tilesize * n / d output pixels and starts at its multiples (per axis: tilesize * nx / dx columns, tilesize * ny / dy rows); the engine
+// admits the call only where those, w * nx / dx and h * ny / dy are even (check_yuv_out), so no quad crosses a tile or the image's edge.
+// Lanes run along x.
 template <typename TP, typename TO, int SITE>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
     const int im = __builtin_amdgcn_readfirstlane(t.img);
-    const int n = a.num, L = 4 * a.den;
+    const int nx = a.num, Lx = 4 * a.den, ny = a.num_y, Ly = 4 * a.den_y;
     const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (gx >= t.out_w * n / L / 2 || gy >= t.out_h * n / L / 2) return;
+    if (gx >= t.out_w * nx / Lx / 2 || gy >= t.out_h * ny / Ly / 2) return;
     const int w = t.tw * 4, h = t.th * 4;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
-    const QuadArea<TP> src{a.slot_stride / (long long)sizeof(TP), w, h, a.crop, a.tta, n, L, a.area_norm, 2 * gx, 2 * gy};
+    const QuadArea<TP> src{a.slot_stride / (long long)sizeof(TP), w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, 2 * gx, 2 * gy};
     yuv_quad<TO, SITE>(a, t, im, gx, gy, src, b0, (long long)w * h);
 }
 
 template <typename TP, typename TO>
 static void launch_postproc_yuv_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
-    const int L = 4 * a.den; // (ow_tile / 2) x (oh_tile / 2) quads per tile
-    const dim3 grid((max_ow * a.num / L / 2 + 63) / 64, (max_oh * a.num / L / 2 + 3) / 4, a.ntiles), block(256);
+    const int Lx = 4 * a.den, Ly = 4 * a.den_y; // (ow_tile / 2) x (oh_tile / 2) quads per tile
+    const dim3 grid((max_ow * a.num / Lx / 2 + 63) / 64, (max_oh * a.num_y / Ly / 2 + 3) / 4, a.ntiles), block(256);
     with_siting(a.siting, [&](auto site) { hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, decltype(site)::value>), grid, block, 0, st, a); });
 }
 
@@ -1128,8 +1133,12 @@ static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipSt
     });
 }
 
-// A rational scale other than 4 / 2 / 1 (rsr_set_out_ratio)?
-static bool generic_ratio(const PostArgs& a) { return a.num > 0 && !(a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1)); }
+// A rational scale other than 4 / 2 / 1 on both axes (rsr_set_out_ratio, rsr_set_out_ratio_xy)?
+static bool generic_ratio(const PostArgs& a)
+{
+    const bool same = a.num_y == a.num && a.den_y == a.den;
+    return a.num > 0 && !(same && a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1));
+}
 
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {

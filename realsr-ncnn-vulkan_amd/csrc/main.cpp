@@ -194,13 +194,37 @@ int main(int argc, char** argv)
     // RSR_OUT_SCALE=1|2|4 (no flag of the reference's surface is taken for it; -s stays the MODEL's scale): the size of the output
     // image relative to the input -- the x4 result box-reduced on the device (rsr_set_option "out_scale") --, or n/d (3/2, 4/3, 9/4,
     // 3/1 ...: rsr_set_out_ratio, area-averaged on the device).  A single number other than 1, 2 and 4 stays refused: x3 is written 3/1.
-    int out_scale = 4, out_num = 4, out_den = 1;
+    // RSR_OUT_SCALE=8/3,9/4 gives a ratio per axis, x then y (rsr_set_out_ratio_xy: 720 x 480 -> 1920 x 1080), each member n/d or a whole
+    // number, d in 1..8; a value without a comma is parsed exactly as above.
+    int out_scale = 4, out_num = 4, out_den = 1, out_num_y = 0, out_den_y = 0; // out_den_y 0: one ratio on both axes
     if (const char* oe = getenv("RSR_OUT_SCALE"))
     {
         const std::string v(oe);
         int n = 0, d = 0, ow = 0, oh = 0;
         char tail = 0;
-        if (v == "1" || v == "2" || v == "4") out_num = out_scale = v[0] - '0';
+        const size_t comma = v.find(',');
+        auto member = [](const std::string& m, int* mn, int* md) { // "n/d" or "n", digits only
+            char t = 0;
+            if (m.empty() || m.size() > 9 || m.find_first_not_of("0123456789/") != std::string::npos) return false;
+            if (m.find('/') == std::string::npos) { *md = 1; return sscanf(m.c_str(), "%d%c", mn, &t) == 1; }
+            return sscanf(m.c_str(), "%d/%d%c", mn, md, &t) == 2;
+        };
+        if (comma != std::string::npos)
+        {
+            int ny = 0, dy = 0;
+            if (v.find(',', comma + 1) == std::string::npos && member(v.substr(0, comma), &n, &d) && member(v.substr(comma + 1), &ny, &dy) &&
+                rsr_out_size_xy(n, d, ny, dy, 840, 840, 840, &ow, &oh) == RSR_OK) // (840: every permitted d divides it, so the pair alone is judged)
+            {
+                out_num = n, out_den = d, out_num_y = ny, out_den_y = dy;
+                out_scale = 0; // the library itself takes equal box members back to out_scale
+            }
+            else
+            {
+                fprintf(stderr, "invalid RSR_OUT_SCALE '%s' (x,y: each n/d or n with d in 1..8 and 1 <= n/d <= 4)\n", oe);
+                return -1;
+            }
+        }
+        else if (v == "1" || v == "2" || v == "4") out_num = out_scale = v[0] - '0';
         else if (v.find('/') != std::string::npos && v.find_first_not_of("0123456789/") == std::string::npos && sscanf(oe, "%d/%d%c", &n, &d, &tail) == 2 &&
                  rsr_out_size(n, d, 12, 12, 12, &ow, &oh) == RSR_OK) // (12: every permitted d divides it, so the ratio alone is judged)
         {
@@ -350,9 +374,10 @@ int main(int argc, char** argv)
         r->tilesize = tilesize[size_t(i)];
         r->prepadding = prepadding;
         r->out_scale = out_scale ? out_scale : 4;
-        if (!out_scale) r->out_num = out_num, r->out_den = out_den;
+        if (!out_scale) r->out_num = out_num, r->out_den = out_den, r->out_num_y = out_num_y, r->out_den_y = out_den_y;
         if (verbose && out_scale) fprintf(stderr, "gpu %d: output scale %d%s\n", gpuid[size_t(i)], out_scale, out_scale == 4 ? "" : " (RSR_OUT_SCALE: the x4 result box-reduced)");
-        if (verbose && !out_scale) fprintf(stderr, "gpu %d: output scale %d/%d (RSR_OUT_SCALE: the x4 result area-averaged)\n", gpuid[size_t(i)], out_num, out_den);
+        if (verbose && !out_scale && !out_den_y) fprintf(stderr, "gpu %d: output scale %d/%d (RSR_OUT_SCALE: the x4 result area-averaged)\n", gpuid[size_t(i)], out_num, out_den);
+        if (verbose && out_den_y) fprintf(stderr, "gpu %d: output scale %d/%d along x, %d/%d along y (RSR_OUT_SCALE: the x4 result area-averaged)\n", gpuid[size_t(i)], out_num, out_den, out_num_y, out_den_y);
         // the reference prints one line per tile, "%.2f%%" of (yi * xtiles + xi) / (ytiles * xtiles) (realsr.cpp:481): the same lines
         // here, one per tile of every batch (a batch of tiles runs at once, so they arrive in bursts)
         rsr_set_progress_callback(ctxs[size_t(i)], [](int done, int total, void*) { fprintf(stderr, "%.2f%%\n", total ? 100.f * float(done - 1) / float(total) : 0.f); }, nullptr);
@@ -452,7 +477,7 @@ int main(int argc, char** argv)
                     v->outpath = out2;
                 }
                 // (a size the ratio does not divide is refused by RealSR::process, which sizes the image through rsr_out_size)
-                v->outimage.create(std::max(1, v->inimage.w * out_num / out_den), std::max(1, v->inimage.h * out_num / out_den), v->inimage.elempack, true);
+                v->outimage.create(std::max(1, v->inimage.w * out_num / out_den), std::max(1, out_den_y ? v->inimage.h * out_num_y / out_den_y : v->inimage.h * out_num / out_den), v->inimage.elempack, true);
                 toproc.put(std::move(v));
             }
         });

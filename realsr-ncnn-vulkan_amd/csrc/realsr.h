@@ -73,13 +73,13 @@ private:
 class RealSR
 {
 public:
-    RealSR(int gpuid, bool tta_mode = false, int num_threads = 1) : scale(4), tilesize(200), prepadding(10), out_scale(4), out_num(0), out_den(0), ctx(nullptr)
+    RealSR(int gpuid, bool tta_mode = false, int num_threads = 1) : scale(4), tilesize(200), prepadding(10), out_scale(4), out_num(0), out_den(0), out_num_y(0), out_den_y(0), ctx(nullptr)
     {
         const int rc = rsr_create(&ctx, gpuid, tta_mode ? 1 : 0, num_threads);
         if (rc != RSR_OK) std::fprintf(stderr, "RealSR: %s\n", rsr_last_error(nullptr));
     }
     // adopt a context created elsewhere (rsr_create_group: the model arrives by one RCCL broadcast instead of load())
-    explicit RealSR(rsr_ctx* adopted) : scale(4), tilesize(200), prepadding(10), out_scale(4), out_num(0), out_den(0), ctx(adopted) {}
+    explicit RealSR(rsr_ctx* adopted) : scale(4), tilesize(200), prepadding(10), out_scale(4), out_num(0), out_den(0), out_num_y(0), out_den_y(0), ctx(adopted) {}
     ~RealSR() { rsr_destroy(ctx); }
     RealSR(const RealSR&) = delete;
     RealSR& operator=(const RealSR&) = delete;
@@ -107,8 +107,8 @@ public:
         if (!ctx) return RSR_E_STATE;
         int rc = rsr_set_params(ctx, scale, tilesize, prepadding);
         int ow = 0, oh = 0;
-        if (rc == RSR_OK) rc = rsr_set_out_ratio(ctx, ratio_num(), ratio_den());
-        if (rc == RSR_OK) rc = rsr_out_size(ratio_num(), ratio_den(), tilesize, inimage.w, inimage.h, &ow, &oh);
+        if (rc == RSR_OK) rc = set_ratio(ctx);
+        if (rc == RSR_OK) rc = out_size(inimage.w, inimage.h, &ow, &oh);
         if (rc == RSR_OK)
         {
             if (outimage.w != ow || outimage.h != oh || outimage.elempack != inimage.elempack)
@@ -131,11 +131,11 @@ public:
         {
             if (!r->ctx) return RSR_E_STATE;
             if (rc == RSR_OK) rc = rsr_set_params(r->ctx, r0.scale, r0.tilesize, r0.prepadding);
-            if (rc == RSR_OK) rc = rsr_set_out_ratio(r->ctx, r0.ratio_num(), r0.ratio_den());
+            if (rc == RSR_OK) rc = r0.set_ratio(r->ctx);
             ctxs.push_back(r->ctx);
         }
         int ow = 0, oh = 0;
-        if (rc == RSR_OK) rc = rsr_out_size(r0.ratio_num(), r0.ratio_den(), r0.tilesize, inimage.w, inimage.h, &ow, &oh);
+        if (rc == RSR_OK) rc = r0.out_size(inimage.w, inimage.h, &ow, &oh);
         if (rc == RSR_OK)
         {
             if (outimage.w != ow || outimage.h != oh || outimage.elempack != inimage.elempack)
@@ -158,6 +158,17 @@ public:
     int out_num, out_den;
     int ratio_num() const { return out_den ? out_num : out_scale; }
     int ratio_den() const { return out_den ? out_den : 1; }
+    // ... and a ratio of its own along y, out_num_y / out_den_y (rsr_set_out_ratio_xy: 720 x 480 -> 1920 x 1080 is 8/3 along x, 9/4 along
+    // y); out_den_y 0 [default] = the ratio above on both axes
+    int out_num_y, out_den_y;
+    int set_ratio(rsr_ctx* c) const
+    {
+        return out_den_y ? rsr_set_out_ratio_xy(c, ratio_num(), ratio_den(), out_num_y, out_den_y) : rsr_set_out_ratio(c, ratio_num(), ratio_den());
+    }
+    int out_size(int w, int h, int* ow, int* oh) const
+    {
+        return out_den_y ? rsr_out_size_xy(ratio_num(), ratio_den(), out_num_y, out_den_y, tilesize, w, h, ow, oh) : rsr_out_size(ratio_num(), ratio_den(), tilesize, w, h, ow, oh);
+    }
 
 private:
     rsr_ctx* ctx;

@@ -7,6 +7,7 @@
 
     nv12 = torch_io.upscale_yuv(sr, surface)   # a decoder's (3H/2, W) uint8 NV12 or 16-bit P010 surface -> the same layout at out_scale
     sr.tilesize = 200; sr.out_ratio = Fraction(3, 2); nv12_1080 = torch_io.upscale_yuv(sr, nv12_720)   # ... or at a ratio: 720p -> 1080p
+    sr.tilesize = 192; sr.out_ratio_xy = (Fraction(8, 3), Fraction(9, 4)); nv12_1080 = torch_io.upscale_yuv(sr, nv12_dvd)   # ... or one per axis: 720 x 480 -> 1920 x 1080
 
     y, n = torch_io.upscale_delta(sr, frame, prev_frame, y)   # video: only the tiles whose source changed run again, y is updated in place
 
@@ -88,8 +89,8 @@ def _packed(x, d):
 
 
 def _out_size(sr, w, h):
-    """(ow, oh) of the context's output for a w x h image: sr.out_size where the context has it (out_scale 4 / 2 / 1, or a ratio such as
-    3/2: ValueError where w, h or the tile size does not take it), else w and h times its out_scale, else times its scale."""
+    """(ow, oh) of the context's output for a w x h image: sr.out_size where the context has it (out_scale 4 / 2 / 1, a ratio such as
+    3/2, or a ratio per axis, sr.out_ratio_xy, such as (8/3, 9/4): ValueError where w, h or the tile size does not take it), else w and h times its out_scale, else times its scale."""
     if hasattr(sr, "out_size"):
         return sr.out_size(w, h)
     s = getattr(sr, "out_scale", sr.scale)
@@ -97,7 +98,7 @@ def _out_size(sr, w, h):
 
 
 def upscale(sr, x, out=None):
-    """x4 -- or, with sr.out_scale 2 / 1, that result box-reduced on the device to x2 / x1, or with sr.out_ratio 3/2, 4/3, 3 ... area-averaged to that scale -- of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
+    """x4 -- or, with sr.out_scale 2 / 1, that result box-reduced on the device to x2 / x1, or with sr.out_ratio 3/2, 4/3, 3 ... area-averaged to that scale, or with sr.out_ratio_xy = (8/3, 9/4) ... to a scale per axis (720 x 480 -> 1920 x 1080) -- of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
     with values in [0, 1], or uint8 (H, W, 3 | 4).  Returns a tensor of the same dtype and layout at 4x (out_scale x), enqueued on
     torch.cuda.current_stream(); a batch is ONE rsr_process_device_batch call on that stream.  A view that fits a descriptor (describe)
     is read in place; any other non-contiguous input is made contiguous first.
@@ -183,15 +184,25 @@ def _describe_yuv(y, uv):
     return (y.data_ptr(), y.stride(0) * es, plane) if plane > 0 else None
 
 
+def _ratio_text(sr):
+    """The context's output ratio for an error text: its out_ratio, or, while that raises because the axes differ (out_ratio_xy), the pair
+    as "rx x ry"; "in force" for a context that has neither."""
+    try:
+        return str(getattr(sr, "out_ratio", "in force"))
+    except ValueError:
+        pair = getattr(sr, "out_ratio_xy", None)
+        return "%s x %s" % tuple(pair) if pair else "in force"
+
+
 def _out_size_yuv(sr, w, h, who):
     """(ow, oh) of the YUV output for a w x h surface: w and h times the context's out_scale 4 / 2 / 1, or, while another ratio is in force
-    (sr.out_ratio: out_scale reads 0), sr.out_size_yuv -- ValueError where w, h or the tile size does not take a YUV output at that ratio,
+    (sr.out_ratio, or a pair sr.out_ratio_xy: out_scale reads 0), sr.out_size_yuv -- ValueError where w, h or the tile size does not take a YUV output at that ratio,
     and for a context that has no out_size_yuv."""
     s = getattr(sr, "out_scale", sr.scale)
     if s:
         return w * s, h * s
     if not hasattr(sr, "out_size_yuv"):
-        raise ValueError("%s: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (who, getattr(sr, "out_ratio", "in force"),))
+        raise ValueError("%s: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (who, _ratio_text(sr)))
     return sr.out_size_yuv(w, h)
 
 
@@ -199,7 +210,7 @@ def _yuv_ratio_note(sr):
     """What a size refusal adds while a YUV surface is written at a ratio other than 4 / 2 / 1 (else nothing)."""
     if getattr(sr, "out_scale", sr.scale):
         return ""
-    return " (a YUV surface at the output ratio %s)" % (getattr(sr, "out_ratio", "in force"),)
+    return " (a YUV surface at the output ratio %s)" % (_ratio_text(sr),)
 
 
 def upscale_yuv(sr, surface, out=None):
