@@ -94,6 +94,9 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
 /* YUV 4:2:0 surfaces: what a hardware video decoder hands over and an encoder takes (ids 3 and 7 stay unknown) */
 #define RSR_FMT_NV12 4  /* uint8  Y [h][w], then interleaved UV [h/2][w/2][2]; c must be 3 */
 #define RSR_FMT_P010 5  /* uint16 little-endian, the code in the HIGH 10 bits (code << 6), same layout */
+/* YUV 4:2:2 surfaces: what broadcast and archive codecs hold -- chroma halved horizontally only ("YUV 4:2:2" below; id 6 stays unknown too) */
+#define RSR_FMT_NV16 8  /* uint8  Y [h][w], then interleaved UV [h][w/2][2]; c must be 3 */
+#define RSR_FMT_P210 9  /* uint16 little-endian, the code in the HIGH 10 bits (code << 6), same layout */
 
 /* rsr_process_device with a pixel format per side: what a tensor pipeline holds (float CHW in [0,1]) goes in and comes out without a
  * uint8 hop.  The two formats are independent; rsr_process_device(...) is exactly rsr_process_device_fmt(..., U8, ..., U8, ...).
@@ -166,6 +169,47 @@ int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, in
  * { yoff, ys, coff, cs, 2(1-Kr), 2Kb(1-Kb)/Kg, 2Kr(1-Kr)/Kg, 2(1-Kb), Kr, Kg, Kb, yscale, yoff + 0.5, cscale, coff + 0.5, 1/(2(1-Kb)),
  * 1/(2(1-Kr)), 2^b - 1 } (18 values).  RSR_E_ARG for any other matrix, range or depth. */
 int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
+
+/* ---- YUV 4:2:2: RSR_FMT_NV16 / RSR_FMT_P210 in and out (no reference counterpart) -------------------------------------------------------
+ * DVCPRO-HD, Digital Betacam, ProRes 422, DNxHD, XDCAM HD422, MPEG-2 4:2:2 profile and uncompressed broadcast captures hold chroma halved
+ * HORIZONTALLY only.  Such a surface goes in and comes out as it is -- no chroma row is thrown away to make NV12 of it, and no RGB frame
+ * exists outside the library.  Either side of a call, independently of the other (NV16 -> NV16, P210 -> P210, NV16 -> NV12, P210 -> F16_CHW,
+ * U8_HWC -> NV16 ...), through every entry point that takes NV12 / P010: rsr_process_device_fmt, _batch (windows, pitched surfaces), _masked,
+ * _sequence, rsr_diff_tiles, rsr_diff_tiles_sequence; in every mode: TTA, "precise", every "yuv_matrix" / "yuv_range", "out_scale" 4 / 2 / 1,
+ * rsr_set_out_ratio, rsr_set_out_ratio_xy.
+ *   Layout.  The rsr_image conventions of NV12 / P010: `data` is Y(0,0); one row pitch serves both planes (a UV row [w/2][2] has as many
+ *            bytes as a Y row); the UV plane starts at data + plane_pitch, 0 = h * row pitch, and has h rows.  Tightly packed:
+ *            rsr_image_bytes = 2*w*h for NV16, 4*w*h for P210; rsr_image_span follows, the UV plane's last row at plane + (h - 1) * row.
+ *   Admission.  Every check is RSR_E_ARG before anything is launched; c must be 3; P210 refuses an odd data pointer or pitch, as P010 does.
+ *            A 4:2:2 INPUT needs an even w; any h >= 1 is taken, odd heights included.  A 4:2:2 OUTPUT needs the ratio rule (w * nx and
+ *            tilesize * nx divisible by dx, h * ny and tilesize * ny divisible by dy) and w * nx / dx and tilesize * nx / dx EVEN, so that no
+ *            2 x 1 chroma pair crosses a tile or the image's edge, with "YUV" in rsr_last_error where only this parity refuses; the two row
+ *            quotients carry no parity rule.  1280 x 1080 at (3/2, 1) and tile 200 is taken (1920 x 1080, tile rectangle 300 x 200); 36 x 26
+ *            at 3/2 and tile 16 gives 54 x 39, taken here and refused for NV12; tile 30 at 3/2 (45 columns) and "out_scale" 1 at an odd tile
+ *            size stay refused.  rsr_out_size_fmt states the rule of any output format.
+ *   The definition, exact.  Everything not said here is the NV12 / P010 definition above: the constants of rsr_yuv_constants (b = 8 for NV16,
+ *   10 for P210), luma, the matrix, clamps, code rounding, reflect-101 first, fp32 throughout, every operation rounded by itself (no contraction).
+ *   Decode, image pixel (x, y).  The chroma row is y itself: there is no vertical filter.  Horizontally, with w/2 chroma columns:
+ *            "yuv_siting" 0 (centre): (3 * c_near + c_far) * 0.25f, c_near = c[x >> 1], the far index +-1 by the parity of x, clamped to
+ *            [0, w/2 - 1].  "yuv_siting" 1 (left): the co-sited rule, c[n] for x = 2n, (c[n] + c[min(n + 1, w/2 - 1)]) * 0.5f for x = 2n + 1.
+ *            "yuv_siting" 2 (top-left) has no vertical meaning at 4:2:2 and IS siting 1: the same kernels, the same bytes.
+ *   Encode, output row y, chroma pair X, per channel; d = what RSR_FMT_F32_CHW holds at the context's scale or ratio.
+ *            Siting 0: m = (d(2X, y) + d(2X+1, y)) * 0.5f.  Siting 1 / 2: m = Hs(y) * 0.25f, Hs(y) = (d(xl, y) + d(2X+1, y)) + (d(2X, y) +
+ *            d(2X, y)), xl = 2X - 1, but xl = 2X where column 2X is the first column of its TILE's output rectangle: the tile-first clamp of
+ *            the 4:2:0 sitings, for the reason given there.  Ym, Cb, Cr and the codes follow from m as for 4:2:0; the (U, V) pair lands at
+ *            UV row y, pair X.  Luma is per pixel and independent of the siting.  P210 stores code << 6.
+ *   Diff.    rsr_diff_tiles / rsr_diff_tiles_sequence compare the Y samples of the tile's source rectangle and the (U, V) pairs of chroma
+ *            columns max((sx0 >> 1) - 1, 0) .. min(((sx1 - 1) >> 1) + 1, w/2 - 1) on rows sy0 .. sy1 - 1; P210 compares whole words.
+ *   Sequences.  The propagated UV rectangle of a tile has the tile's own rows.
+ * One more small launch behind conv_last writes the surface, as for NV12 / P010: postproc_tiles_yuv / postproc_tiles_yuv_area with two stacked
+ * 2 x 1 pairs per thread.  rsr_out_size_yuv and rsr_out_size_yuv_xy keep their exact 4:2:0 behaviour.
+ * Out of scope: three-plane layouts (yuv422p: interleave the two chroma planes first), 4:4:4, 4:1:1, a siting per side, host pointers
+ * (rsr_process*), groups of GPUs and the CLI, which stay uint8 RGB(A). */
+
+/* Host-only (no GPU): the admission rule and the size of an output in `out_fmt` at the pair of ratios and the tile size given -- *ow = w *
+ * nx / dx, *oh = h * ny / dy (either pointer may be NULL).  RSR_FMT_U8_HWC / F16_CHW / F32_CHW: exactly rsr_out_size_xy.  RSR_FMT_NV12 /
+ * P010: exactly rsr_out_size_yuv_xy.  RSR_FMT_NV16 / P210: the 4:2:2 rule above.  RSR_E_ARG for an unknown format. */
+int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh);
 
 /* ---- rational output scales: x3, x3/2, x4/3, x9/4 ... area-averaged on the device (no reference counterpart) --------------------------
  * Option "out_scale" (rsr_set_option) takes the x4 image down to x2 or x1 inside the library.  rsr_set_out_ratio generalises it to the
@@ -334,6 +378,8 @@ int rsr_tile_source_rect(int w, int h, int tilesize, int prepadding, int tile, i
  *                                      max((sx0 >> 1) - 1, 0) .. min(((sx1 - 1) >> 1) + 1, w / 2 - 1) inclusive, rows likewise with sy and h: the
  *                                      decode of every siting reads one chroma sample beyond its own.  P010 compares whole 16-bit words, the low
  *                                      6 bits included.
+ *   RSR_FMT_NV16 / RSR_FMT_P210        the Y samples of the rectangle, and the (U, V) pairs of the same chroma columns on rows sy0 .. sy1 - 1
+ *                                      ("YUV 4:2:2": a chroma row per luma row).  P210 compares whole words.
  * A tile whose mask byte is 0 would get, from rsr_process_device* on b, the bytes it got from a -- in every mode and at every option that is the
  * same for both calls.
  *   Stream.  Asynchronous on `stream` with the contract of rsr_process_device (NULL = the context's stream, and the call waits).  One memset and

@@ -36,6 +36,7 @@ EXPORTS = [
     "rsr_set_out_ratio_xy", "rsr_out_size_xy", "rsr_out_size_yuv_xy",
     "rsr_tile_count", "rsr_tile_source_rect", "rsr_diff_tiles", "rsr_process_device_masked",
     "rsr_sequence_sources", "rsr_diff_tiles_sequence", "rsr_process_device_sequence",
+    "rsr_out_size_fmt",
 ]
 
 NUM_CONVS = 351
@@ -45,6 +46,8 @@ RSR_OK, RSR_E_ARG, RSR_E_IO, RSR_E_FORMAT, RSR_E_GRAPH, RSR_E_DEVICE, RSR_E_STAT
 RSR_FMT_U8_HWC, RSR_FMT_F16_CHW, RSR_FMT_F32_CHW = 0, 1, 2
 # YUV 4:2:0 surfaces: Y [h][w] then interleaved UV [h/2][w/2][2]; uint8, or uint16 with the 10-bit code in the high bits
 RSR_FMT_NV12, RSR_FMT_P010 = 4, 5
+# YUV 4:2:2 surfaces: Y [h][w] then interleaved UV [h][w/2][2] -- chroma halved horizontally only; uint8, or uint16 with the code in the high bits
+RSR_FMT_NV16, RSR_FMT_P210 = 8, 9
 RSR_SEQ_MAX = 16  # frames per rsr_process_device_sequence call
 
 
@@ -124,6 +127,7 @@ def lib():
     L.rsr_set_out_ratio_xy.argtypes = [vp, ip, ip, ip, ip]
     L.rsr_out_size_xy.argtypes = [ip, ip, ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_out_size_yuv_xy.argtypes = [ip, ip, ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_out_size_fmt.argtypes = [ip, ip, ip, ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_tile_count.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.rsr_tile_source_rect.argtypes = [ip, ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
     L.rsr_diff_tiles.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), ip, ip, ip, ip, vp, vp]
@@ -352,6 +356,18 @@ class RealSR:
         if self._L.rsr_out_size_yuv(r.numerator, r.denominator, int(self.tilesize), int(w), int(h), C.byref(ow), C.byref(oh)) != 0:
             raise ValueError("a YUV output at ratio %s: %d x %d at tile %d: w and h must be even, w, h and tilesize times %d multiples of %d, and "
                              "w, h and tilesize times %s even" % (r, w, h, self.tilesize, r.numerator, r.denominator, r))
+        return ow.value, oh.value
+
+    def out_size_fmt(self, fmt, w, h):
+        """out_size for an output in pixel format `fmt` (RSR_FMT_*) at the ratio, or pair, and tile size in force: the rule of out_size for
+        the RGB formats, of out_size_yuv for NV12 / P010, and for NV16 / P210 the 4:2:2 rule -- the ratio rule, and w * nx / dx and
+        tilesize * nx / dx even; the rows carry no parity rule (rsr_out_size_fmt).  ValueError where the engine would refuse the call."""
+        r, pair = self._ratio_or_pair()
+        rx, ry = (r, r) if pair is None else pair
+        ow, oh = C.c_int(0), C.c_int(0)
+        if self._L.rsr_out_size_fmt(int(fmt), rx.numerator, rx.denominator, ry.numerator, ry.denominator, int(self.tilesize), int(w), int(h),
+                                    C.byref(ow), C.byref(oh)) != 0:
+            raise ValueError("format %d at %s x %s: %d x %d at tile %d: %s" % (fmt, rx, ry, w, h, self.tilesize, self._L.rsr_last_error(None).decode()))
         return ow.value, oh.value
 
     def _ratio_text(self):  # for error texts: one ratio, or "rx x ry"
@@ -683,7 +699,8 @@ def selfcheck_tile(w=0, h=0):
 
 
 def image_bytes(fmt, w, h, c=3):
-    """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*; NV12: w*h*3/2, P010: 3*w*h)."""
+    """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*; NV12: w*h*3/2, P010: 3*w*h,
+    NV16: 2*w*h, P210: 4*w*h)."""
     n = lib().rsr_image_bytes(int(fmt), int(w), int(h), int(c))
     if n < 0:
         raise RealSRError(int(n), lib().rsr_last_error(None).decode())

@@ -270,7 +270,8 @@ long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long
     const int rc = rsr::image_layout(fmt, w, h, c, row_pitch, plane_pitch, &row, &plane);
     if (rc != RSR_OK) return rc;
     // all pitches are positive: the last element of the last row of the last plane lies farthest from `data`
-    if (rsr::fmt_is_yuv(fmt)) return plane + (long long)(h / 2 - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c); // (the UV plane: h / 2 rows as long as a Y row)
+    if (rsr::fmt_is_yuv(fmt)) // (the UV plane: h / 2 rows as long as a Y row, h of them at 4:2:2)
+        return plane + (long long)((rsr::fmt_is_422(fmt) ? h : h / 2) - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
     return (fmt == RSR_FMT_U8_HWC ? 0 : 2 * plane) + (long long)(h - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
 }
 
@@ -281,6 +282,11 @@ long long rsr_image_bytes(int fmt, int w, int h, int c)
     if (fmt == RSR_FMT_U8_HWC && (c == 3 || c == 4)) return px * c;
     if (fmt == RSR_FMT_F16_CHW && c == 3) return px * 6;
     if (fmt == RSR_FMT_F32_CHW && c == 3) return px * 12;
+    if (rsr::fmt_is_422(fmt) && c == 3)
+    {
+        if (w & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:2 surface needs an even width");
+        return fmt == RSR_FMT_NV16 ? px * 2 : px * 4;
+    }
     if (rsr::fmt_is_yuv(fmt) && c == 3)
     {
         if ((w | h) & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
@@ -342,17 +348,21 @@ int rsr_set_out_ratio_xy(rsr_ctx* ctx, int num_x, int den_x, int num_y, int den_
 }
 
 // The admission rule of a pair, shared by the two size functions: RSR_OK and the reduced pair, or the refusal.
-static int out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, bool yuv, int* ow, int* oh)
+// yuv: 0 = an RGB output, 1 = a YUV 4:2:0 output, 2 = a YUV 4:2:2 output (whose columns alone answer to a parity rule; its input may be any format,
+// so w and h themselves are not asked to be even).
+static int out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int yuv, int* ow, int* oh)
 {
     rsr::OutRatio r;
     if (!rsr::out_ratio_reduce_xy(num_x, den_x, num_y, den_y, &r)) return Engine::fail(RSR_E_ARG, kBadRatioXY);
     if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
-    if (yuv && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
-    const std::string what = std::string(yuv ? "a YUV 4:2:0 output at " : "") + "output ratios " + r.str();
+    if (yuv == 1 && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
+    const std::string what = std::string(yuv == 1 ? "a YUV 4:2:0 output at " : (yuv == 2 ? "a YUV 4:2:2 output at " : "")) + "output ratios " + r.str();
     if (!r.divides_x(w) || !r.divides_x(tilesize) || !r.divides_y(h) || !r.divides_y(tilesize))
         return Engine::fail(RSR_E_ARG, what + ": w and tilesize times " + std::to_string(r.nx) + " must be multiples of " + std::to_string(r.dx) + ", h and tilesize times " +
                                            std::to_string(r.ny) + " multiples of " + std::to_string(r.dy));
-    if (yuv && !rsr::yuv_out_even(r, w, h, tilesize))
+    if (yuv == 2 && !rsr::yuv422_out_even(r, w, tilesize))
+        return Engine::fail(RSR_E_ARG, what + " needs w and tilesize times " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + " even");
+    if (yuv == 1 && !rsr::yuv_out_even(r, w, h, tilesize))
         return Engine::fail(RSR_E_ARG, what + " needs w and tilesize times " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + " and h and tilesize times " +
                                            std::to_string(r.ny) + "/" + std::to_string(r.dy) + " even");
     if (ow) *ow = int(r.of_x(w));
@@ -362,12 +372,19 @@ static int out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize,
 
 int rsr_out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
 {
-    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, false, ow, oh);
+    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 0, ow, oh);
 }
 
 int rsr_out_size_yuv_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
 {
-    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, true, ow, oh);
+    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 1, ow, oh);
+}
+
+int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
+{
+    if (out_fmt == RSR_FMT_U8_HWC || out_fmt == RSR_FMT_F16_CHW || out_fmt == RSR_FMT_F32_CHW) return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 0, ow, oh);
+    if (!rsr::fmt_is_yuv(out_fmt)) return Engine::fail(RSR_E_ARG, "unknown pixel format");
+    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, rsr::fmt_is_422(out_fmt) ? 2 : 1, ow, oh);
 }
 
 int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n)

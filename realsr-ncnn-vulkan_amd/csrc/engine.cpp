@@ -1117,8 +1117,8 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     pa.bgr = bgr ? 1 : 0;
     pa.plane_ch = pc;
     pa.variant = variant;
-    if (fmt_is_yuv(io.in_fmt) && !yuv_coef(yuv_matrix, yuv_range, io.in_fmt == RSR_FMT_P010 ? 10 : 8, &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
-    if (fmt_is_yuv(io.out_fmt) && !yuv_coef(yuv_matrix, yuv_range, io.out_fmt == RSR_FMT_P010 ? 10 : 8, &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
+    if (fmt_is_yuv(io.in_fmt) && !yuv_coef(yuv_matrix, yuv_range, fmt_yuv_bits(io.in_fmt), &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
+    if (fmt_is_yuv(io.out_fmt) && !yuv_coef(yuv_matrix, yuv_range, fmt_yuv_bits(io.out_fmt), &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     pa.siting = po.siting = yuv_siting;
     launch_preproc_tiles(pa, max_tw, max_th, st);
     mark(0, 0, b.px[0] / per * BatchIO::image_px_bytes(io.in_fmt, c) + b.px[0] * 64, st);
@@ -1357,9 +1357,11 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
         if (f != RSR_FMT_U8_HWC && f != RSR_FMT_F16_CHW && f != RSR_FMT_F32_CHW && !fmt_is_yuv(f)) return fail(RSR_E_ARG, "unknown pixel format");
         if (f != RSR_FMT_U8_HWC && c != 3) return fail(RSR_E_ARG, "the planar float and the YUV formats come with c == 3 only");
     }
-    if (fmt_is_yuv(in_fmt) && ((w | h) & 1)) return fail(RSR_E_ARG, "a YUV 4:2:0 input needs an even width and height");
-    if ((in_fmt == RSR_FMT_P010 && (reinterpret_cast<uintptr_t>(d_in) & 1)) || (out_fmt == RSR_FMT_P010 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
-        return fail(RSR_E_ARG, "P010 data is not aligned to its 16-bit samples");
+    if (fmt_is_422(in_fmt) && (w & 1)) return fail(RSR_E_ARG, "a YUV 4:2:2 input needs an even width");
+    if (fmt_is_yuv(in_fmt) && !fmt_is_422(in_fmt) && ((w | h) & 1)) return fail(RSR_E_ARG, "a YUV 4:2:0 input needs an even width and height");
+    if ((fmt_is_yuv(in_fmt) && fmt_yuv_bits(in_fmt) > 8 && (reinterpret_cast<uintptr_t>(d_in) & 1)) ||
+        (fmt_is_yuv(out_fmt) && fmt_yuv_bits(out_fmt) > 8 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
+        return fail(RSR_E_ARG, "P010 / P210 data is not aligned to its 16-bit samples");
     const bool u8 = in_fmt == RSR_FMT_U8_HWC && out_fmt == RSR_FMT_U8_HWC;
     if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
     { // a small image: merged with whatever other calls hand in meanwhile (Engine::submit_merged)
@@ -1402,7 +1404,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
     });
 }
 
-// ---- YUV 4:2:0 surfaces (RSR_FMT_NV12 / RSR_FMT_P010) ------------------------------------------------------------------------------
+// ---- YUV 4:2:0 and 4:2:2 surfaces (RSR_FMT_NV12 / RSR_FMT_P010, RSR_FMT_NV16 / RSR_FMT_P210) -------------------------------------
 // Every constant is computed in double from Kr and Kb and rounded ONCE to fp32 (include/realsr_hip.h "yuv_matrix"; tests/yuv_ref.py writes
 // the same expressions).
 bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
@@ -1430,9 +1432,24 @@ bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
 // output pixels (only out_scale 1 can break that).  At a ratio n / d other than 4 / 2 / 1 (check_ratio_out has made w n / d, h n / d and
 // tilesize n / d whole) the same rule reads: those three are even (yuv_out_even, what rsr_out_size_yuv states) -- per axis where the axes
 // differ: w nx / dx, tilesize nx / dx, h ny / dy and tilesize ny / dy (rsr_out_size_yuv_xy).  mu held (tilesize).
+// A 4:2:2 output is written one 2 x 1 luma pair and its (U, V) at a time: the same rule for the COLUMNS alone -- w nx / dx and tilesize nx / dx
+// even -- and none for the rows (rsr_out_size_fmt).
 int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
 {
     if (!fmt_is_yuv(out_fmt)) return RSR_OK;
+    if (fmt_is_422(out_fmt))
+    {
+        if (ratio.is_box())
+        {
+            const int os = ratio.out_scale();
+            if (((w * os) | (tilesize * os)) & 1) return fail(RSR_E_ARG, "a YUV 4:2:2 output needs w * out_scale and tilesize * out_scale even");
+            return RSR_OK;
+        }
+        if (!yuv422_out_even(ratio, w, tilesize))
+            return fail(RSR_E_ARG, "a YUV 4:2:2 output at ratios " + ratio.str() + " needs w and tilesize times " + std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) +
+                                       " even (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(tilesize) + ")");
+        return RSR_OK;
+    }
     if (ratio.is_box())
     {
         const int os = ratio.out_scale();
@@ -1454,6 +1471,7 @@ int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
 }
 
 bool yuv_out_even(OutRatio r, long long w, long long h, long long T) { return !((r.of_x(w) | r.of_y(h) | r.of_x(T) | r.of_y(T)) & 1); }
+bool yuv422_out_even(OutRatio r, long long w, long long T) { return !((r.of_x(w) | r.of_x(T)) & 1); }
 
 // ---- rational output scales (rsr_set_out_ratio, rsr_set_out_ratio_xy) ---------------------------------------------------------------------
 // num / den in lowest terms when den <= max_den and 1 <= num / den <= 4
@@ -1494,10 +1512,10 @@ int Engine::check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const
     if (!os.divides_x(w) || !os.divides_y(h) || !os.divides_x(T) || !os.divides_y(T)) // (a YUV output: check_yuv_out then asks for even quotients as well)
     {
         if (!os.same())
-            return fail(RSR_E_ARG, std::string(fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "") + "output ratios " + os.str() + ": w and tilesize times " + std::to_string(os.nx) +
+            return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratios " + os.str() + ": w and tilesize times " + std::to_string(os.nx) +
                                        " must be multiples of " + std::to_string(os.dx) + ", h and tilesize times " + std::to_string(os.ny) + " multiples of " + std::to_string(os.dy) +
                                        " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
-        return fail(RSR_E_ARG, std::string(fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "") + "output ratio " + std::to_string(os.nx) + "/" + std::to_string(os.dx) + ": w, h and tilesize times " + std::to_string(os.nx) +
+        return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratio " + std::to_string(os.nx) + "/" + std::to_string(os.dx) + ": w, h and tilesize times " + std::to_string(os.nx) +
                                    " must be multiples of " + std::to_string(os.dx) + " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
     }
     return RSR_OK;
@@ -1509,7 +1527,8 @@ int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long pl
     if (w < 1 || h < 1) return Engine::fail(RSR_E_ARG, "bad image size");
     if (fmt != RSR_FMT_U8_HWC && fmt != RSR_FMT_F16_CHW && fmt != RSR_FMT_F32_CHW && !fmt_is_yuv(fmt)) return Engine::fail(RSR_E_ARG, "unknown pixel format");
     if (fmt == RSR_FMT_U8_HWC ? (c != 3 && c != 4) : c != 3) return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
-    if (fmt_is_yuv(fmt) && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
+    if (fmt_is_422(fmt) && (w & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:2 surface needs an even width");
+    if (fmt_is_yuv(fmt) && !fmt_is_422(fmt) && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
     if (row_pitch < 0 || plane_pitch < 0) return Engine::fail(RSR_E_ARG, "negative pitch");
     const long long es = BatchIO::px_bytes(fmt, c), packed = w * es;
     const long long rp = row_pitch ? row_pitch : packed;
@@ -1693,7 +1712,7 @@ int Engine::diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image*
 
 // The byte rectangles of output tile `tile` of an os.of_x(w) x os.of_y(h) image in out_fmt, from the image `src` to the image `dst`: one for
 // uint8 HWC, three for the planar formats, Y and UV for the surfaces (the UV rectangle has the byte columns of the Y rectangle and half its
-// rows; check_yuv_out has made its edges even).
+// rows; check_yuv_out has made its edges even -- a 4:2:2 surface: the tile's own rows, and only its columns are even).
 static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, int tile, const ImageRef& dst, const ImageRef& src, std::vector<PropRect>& out)
 {
     uint8_t* const db = static_cast<uint8_t*>(const_cast<void*>(dst.data));
@@ -1706,7 +1725,8 @@ static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, i
     const int nplanes = out_fmt == RSR_FMT_U8_HWC || fmt_is_yuv(out_fmt) ? 1 : 3;
     for (int q = 0; q < nplanes; q++)
         out.push_back(PropRect{db + q * dpl + y0 * dp + x0 * es, sb + q * spl + y0 * sp + x0 * es, dp, sp, width, rows});
-    if (fmt_is_yuv(out_fmt)) out.push_back(PropRect{db + dpl + y0 / 2 * dp + x0 * es, sb + spl + y0 / 2 * sp + x0 * es, dp, sp, width, rows / 2});
+    if (fmt_is_422(out_fmt)) out.push_back(PropRect{db + dpl + y0 * dp + x0 * es, sb + spl + y0 * sp + x0 * es, dp, sp, width, rows});
+    else if (fmt_is_yuv(out_fmt)) out.push_back(PropRect{db + dpl + y0 / 2 * dp + x0 * es, sb + spl + y0 / 2 * sp + x0 * es, dp, sp, width, rows / 2});
 }
 
 int Engine::process_device_sequence(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, const rsr_image* prev_out,

@@ -67,6 +67,8 @@ bool out_ratio_reduce_xy(int num_x, int den_x, int num_y, int den_y, OutRatio* o
 // Host-only: are w nx / dx, T nx / dx, h ny / dy and T ny / dy (whole: OutRatio::divides_*) all even -- what a YUV 4:2:0 output asks of
 // image and tile size?
 bool yuv_out_even(OutRatio r, long long w, long long h, long long T);
+// ... and what a 4:2:2 output asks: w nx / dx and T nx / dx even (its chroma is halved along x only: the two row quotients are any).
+bool yuv422_out_even(OutRatio r, long long w, long long T);
 
 struct DevBuf
 {
@@ -218,14 +220,14 @@ struct BatchIO
         for (int i = 0; i < n; i++) set(i, g[i]->d_in, g[i]->d_out, g[i]->w, g[i]->h);
     }
     BatchIO(int n, int c0, int in_fmt0, int out_fmt0, OutRatio os0) : nimg(n), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
-    static long long px_bytes(int fmt, int c) // of one element of a row (NV12 / P010: of one sample; a UV row has as many bytes as a Y row)
+    static long long px_bytes(int fmt, int c) // of one element of a row (a YUV surface: of one sample; a UV row has as many bytes as a Y row)
     {
-        return fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_P010 ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : (fmt == RSR_FMT_NV12 ? 1 : c));
+        return fmt == RSR_FMT_F16_CHW ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : (fmt_is_yuv(fmt) ? (fmt_yuv_bits(fmt) + 7) / 8 : c));
     }
     static long long elem_bytes(int fmt, int c) { return fmt == RSR_FMT_U8_HWC ? 1 : px_bytes(fmt, c); } // what `data` and the pitches of a descriptor must be multiples of
-    static double image_px_bytes(int fmt, int c) // bytes of one PIXEL of a whole image: c for uint8 HWC, 3 halfs / floats, 1.5 samples of a 4:2:0 surface
+    static double image_px_bytes(int fmt, int c) // bytes of one PIXEL of a whole image: c for uint8 HWC, 3 halfs / floats, 1.5 samples of a 4:2:0 surface, 2 of a 4:2:2 one
     {
-        return double(px_bytes(fmt, c)) * (fmt_is_yuv(fmt) ? 1.5 : (fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_F32_CHW ? 3.0 : 1.0));
+        return double(px_bytes(fmt, c)) * (fmt_is_422(fmt) ? 2.0 : (fmt_is_yuv(fmt) ? 1.5 : (fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_F32_CHW ? 3.0 : 1.0)));
     }
     static ImageRef packed(const void* data, int fmt, long long wi, long long hi, int c) // a tightly packed wi x hi image
     {
@@ -448,7 +450,7 @@ struct Engine
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
     // no TTA merge / alpha channel / box reduction / YUV 4:2:0 surface needs the planar blob (dbg 8192: off)
     bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
-    int check_yuv_out(int out_fmt, int w, int h, OutRatio os) const; // RSR_E_ARG when a 2 x 2 chroma quad of a YUV output would cross the image or a tile
+    int check_yuv_out(int out_fmt, int w, int h, OutRatio os) const; // RSR_E_ARG when a chroma quad (4:2:0) / pair (4:2:2) of a YUV output would cross the image or a tile
     int check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const; // RSR_E_ARG when w, h or the tile size T times os is no whole number of pixels (no lock needed)
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).

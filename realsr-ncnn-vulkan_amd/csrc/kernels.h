@@ -40,7 +40,12 @@ constexpr int kFmtU8 = 0, kFmtF16 = 1, kFmtF32 = 2;
 // `plane pitch` bytes behind Y(0,0) -- a plane of interleaved UV [h/2][w/2][2] whose rows are as many bytes apart as the Y rows.  uint8
 // codes, or uint16 words that hold a 10-bit code in their HIGH bits (code << 6).  w and h are even.
 constexpr int kFmtNV12 = 4, kFmtP010 = 5;
-constexpr bool fmt_is_yuv(int fmt) { return fmt == kFmtNV12 || fmt == kFmtP010; }
+// YUV 4:2:2 surfaces, what broadcast and archive codecs hold (RSR_FMT_NV16 / RSR_FMT_P210): the same two planes, but chroma is halved
+// horizontally only -- the UV plane is [h][w/2][2], one UV row per Y row.  w is even; h is any.
+constexpr int kFmtNV16 = 8, kFmtP210 = 9;
+constexpr bool fmt_is_422(int fmt) { return fmt == kFmtNV16 || fmt == kFmtP210; }
+constexpr bool fmt_is_yuv(int fmt) { return fmt == kFmtNV12 || fmt == kFmtP010 || fmt_is_422(fmt); }
+constexpr int fmt_yuv_bits(int fmt) { return fmt == kFmtP010 || fmt == kFmtP210 ? 10 : 8; } // of a YUV format: the code's bits (10: uint16 words, code << 6)
 // Every image is addressed through its own ROW PITCH and (planar formats) PLANE PITCH, both in BYTES (rsr_image of the C ABI): a crop of
 // a larger frame, a window of a canvas.  A uint8 pitch need not be a multiple of the pixel size and a base pointer is aligned to the
 // element only, so the image accesses are element-sized (the LDS-staged pre / post kernels, which move dwords, align by themselves or
@@ -171,7 +176,7 @@ struct PreArgs
 {
     const uint8_t* imgs[kMaxMerge]; // HWC u8, one per image of the batch (ws[i] x hs[i] x c); BaseTile::img selects
     int fmt;                        // kFmtU8, or kFmtF16 / kFmtF32: the images are planar [3][hs[i]][ws[i]] of that type (c == 3),
-                                    // or kFmtNV12 / kFmtP010: Y at imgs[i], UV plane[i] bytes behind it, decoded with `yuv`; bgr does not apply
+                                    // or a YUV surface (fmt_is_yuv): Y at imgs[i], UV plane[i] bytes behind it, decoded with `yuv`; bgr does not apply
     int ws[kMaxMerge], hs[kMaxMerge];
     int pitch[kMaxMerge];           // bytes from one row of image i to the next (>= ws[i] * pixel size) ...
     long long plane[kMaxMerge];     // ... and, planar formats, from one plane to the next
@@ -185,8 +190,9 @@ struct PreArgs
     int bgr;
     int plane_ch;   // 16
     int variant;    // 0 default (launch_preproc_tiles picks), 1 one thread per pixel (engine dbg 32768), 2 LDS-staged (dbg 65536; uint8 sources only)
-    YuvCoef yuv;    // fmt kFmtNV12 / kFmtP010 only
+    YuvCoef yuv;    // YUV formats only
     int siting;     // ... likewise: where a chroma sample sits in its luma quad (engine option "yuv_siting"): 0 centre, 1 left, 2 top-left
+                    // (a 4:2:2 surface has no vertical siting: 2 is 1 there)
 };
 void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t st);
 
@@ -201,7 +207,7 @@ struct PostArgs
     int crop;   // prepadding*scale
     uint8_t* outs[kMaxMerge]; // HWC u8 (4w x 4h x c), one per image of the batch
     int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][4h][4w] of that type (c == 3; see ConvArgs::out_fmt),
-                              // or kFmtNV12 / kFmtP010: Y at outs[i], UV out_plane[i] bytes behind it (postproc_tiles_yuv; box 0 / 1, 2 and 4 alike)
+                              // or a YUV surface (fmt_is_yuv): Y at outs[i], UV out_plane[i] bytes behind it (postproc_tiles_yuv; box 0 / 1, 2 and 4 alike)
     long long out_plane[kMaxMerge]; // planar formats: bytes from one plane of `outs[i]` to the next
     int out_pitch[kMaxMerge]; // row pitches of the outs in bytes
     int in_pitch[kMaxMerge];  // ... and those of the source images
@@ -227,7 +233,7 @@ struct PostArgs
     int num, den;
     int num_y, den_y;
     float area_norm;
-    YuvCoef yuv; // out_fmt kFmtNV12 / kFmtP010 only
+    YuvCoef yuv; // YUV out_fmt only
     // ... likewise: the chroma siting (engine option "yuv_siting": 0 centre, 1 left, 2 top-left).  The sited chroma filters clamp at the
     // first column / row of a TILE's rectangle; that is quad column / row 0 of the tile's own grid (BaseTile::out_*), so nothing else travels.
     int siting;

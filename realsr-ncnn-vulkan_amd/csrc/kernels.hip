@@ -6,8 +6,8 @@
 //                          chosen per launch by measurement: launch_*_tiles)
 //   postproc_tiles_box     the image box-reduced to x2 / x1 (out_scale)
 //   postproc_tiles_area    the image area-averaged to any other ratio, or to a ratio per axis (rsr_set_out_ratio, rsr_set_out_ratio_xy)
-//   preproc_tiles<., true> an NV12 / P010 surface as the source (YUV -> RGB inside the kernel)
-//   postproc_tiles_yuv[_area]   an NV12 / P010 surface as the destination, at out_scale 4 / 2 / 1 [at any other ratio]
+//   preproc_tiles<., true> an NV12 / P010 (4:2:0) or NV16 / P210 (4:2:2) surface as the source (YUV -> RGB inside the kernel)
+//   postproc_tiles_yuv[_area]   such a surface as the destination, at out_scale 4 / 2 / 1 [at any other ratio]
 //   *_shader               the same arithmetic in the shaders' own memory layout (parity tests; independent of everything below)
 //
 // Every rule the header (include/realsr_hip.h) fixes bit for bit is written ONCE, as a __device__ __forceinline__ function the kernels share:
@@ -16,7 +16,7 @@
 //                                                                                                    every post kernel but postproc_tiles_lds
 //   alpha_bicubic          the bicubic x4 alpha value                                               every post kernel that writes RGBA
 //   area_sum / area_pixel  the area-average loop nest over a tap source                            postproc_tiles_area, postproc_tiles_yuv_area
-//   yuv_quad               a luma quad and its (U, V) pair from a source of pixels d               postproc_tiles_yuv, postproc_tiles_yuv_area
+//   yuv_quad               a luma quad and its (U, V) pair(s) from a source of pixels d              postproc_tiles_yuv, postproc_tiles_yuv_area
 //
 // The 351 convolutions live in conv_flow.hip (conv3x3_flow).  Written for gfx950 only.
 #include "kernels.h"
@@ -46,7 +46,7 @@ __device__ __forceinline__ int reflect101(int v, int n)
     return min(max(v, 0), n - 1);
 }
 
-// ---- YUV 4:2:0 sources (PreArgs::fmt kFmtNV12 / kFmtP010) -------------------------------------------------------------------------
+// ---- YUV 4:2:0 and 4:2:2 sources (PreArgs::fmt kFmtNV12 / kFmtP010, kFmtNV16 / kFmtP210) ----------------------------------------
 // ONE fp32 operation, rounded by itself.  HIP's __fmul_rn / __fadd_rn are the plain operators, which the compiler contracts with their
 // neighbours into an fma once they are inlined; an operation compiled with contraction off takes no part in that.
 __device__ __forceinline__ float mul_rn(float a, float b)
@@ -102,10 +102,22 @@ __device__ __forceinline__ void load_uv(const uint8_t* row, int cx, float& u, fl
 // The centre rule along one axis: 3/4 of the near chroma sample, 1/4 of the far one (yuv_decode, yuv_decode_cos).
 __device__ __forceinline__ float chroma_mix(float near, float far) { return mul_rn(add_rn(mul_rn(3.f, near), far), 0.25f); }
 
-template <typename SRC, int SITE>
+// VS (the surface's vertical chroma shift): 1 = 4:2:0, everything above.  0 = 4:2:2 (kFmtNV16 / kFmtP210; include/realsr_hip.h "YUV 4:2:2"): the
+// chroma row of pixel (x, y) is row y itself, so only the horizontal half of either rule applies -- two load_uv per pixel instead of four --
+// and SITE is 0 or 1 (top-left has no vertical meaning there: launch_preproc_tiles runs it as 1).
+template <typename SRC, int SITE, int VS = 1>
 __device__ __forceinline__ void yuv_decode_cos(const uint8_t* img, int pitch, long long plane, int x, int y, int w, int h, float& U, float& V)
 {
     const int cx0 = x >> 1, cx1 = min(cx0 + (x & 1), (w >> 1) - 1); // an even x reads its column twice: (c + c) * 0.5f == c
+    if constexpr (VS == 0)
+    {
+        const uint8_t* r = img + plane + (long long)y * pitch;
+        float u0, v0, u1, v1;
+        load_uv<SRC>(r, cx0, u0, v0);
+        load_uv<SRC>(r, cx1, u1, v1);
+        U = mul_rn(add_rn(u0, u1), 0.5f), V = mul_rn(add_rn(v0, v1), 0.5f);
+        return;
+    }
     int cy0 = y >> 1, cy1;
     if constexpr (SITE == 2) cy1 = min(cy0 + (y & 1), (h >> 1) - 1);
     else cy1 = min(max(cy0 + ((y & 1) ? 1 : -1), 0), (h >> 1) - 1); // centre rule: cy0 near, cy1 far
@@ -122,7 +134,7 @@ __device__ __forceinline__ void yuv_decode_cos(const uint8_t* img, int pitch, lo
     else { U = chroma_mix(ua, ub); V = chroma_mix(va, vb); }
 }
 
-template <typename SRC, int SITE = 0>
+template <typename SRC, int SITE = 0, int VS = 1>
 __device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long long plane, int x, int y, int w, int h, const YuvCoef& k, float (&rgb)[3])
 {
     const uint8_t* yp = img + (long long)y * pitch + (long long)x * (int)sizeof(SRC);
@@ -130,7 +142,16 @@ __device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long l
     if constexpr (sizeof(SRC) == 1) Y = (float)*yp;
     else Y = (float)(*reinterpret_cast<const unsigned short*>(yp) >> 6);
     float U, V;
-    if constexpr (SITE != 0) yuv_decode_cos<SRC, SITE>(img, pitch, plane, x, y, w, h, U, V);
+    if constexpr (SITE != 0) yuv_decode_cos<SRC, SITE, VS>(img, pitch, plane, x, y, w, h, U, V);
+    else if constexpr (VS == 0)
+    { // 4:2:2, centre: the horizontal rule on the pixel's own chroma row
+        const int cxn = x >> 1, cxf = min(max(cxn + ((x & 1) ? 1 : -1), 0), (w >> 1) - 1);
+        const uint8_t* r = img + plane + (long long)y * pitch;
+        float un, vn, uf, vf;
+        load_uv<SRC>(r, cxn, un, vn);
+        load_uv<SRC>(r, cxf, uf, vf);
+        U = chroma_mix(un, uf), V = chroma_mix(vn, vf);
+    }
     else
     {
         const int cxn = x >> 1, cxf = min(max(cxn + ((x & 1) ? 1 : -1), 0), (w >> 1) - 1);
@@ -182,7 +203,8 @@ __device__ __forceinline__ void tta_dest(int k, int gx, int gy, int tw, int th, 
 // YUV = true: the image is a 4:2:0 surface, SRC its sample type -- uint8_t (NV12) or uint16_t (P010, the code in the high 10 bits).  Pixel
 // (x, y) -- reflected first, like every other source -- is decoded as include/realsr_hip.h ("yuv_matrix") defines, bit for bit: yuv_decode;
 // SITE is the chroma siting (PreArgs::siting: a kernel per siting, the centre-sited one is what it was before the others existed).
-template <typename SRC, bool YUV = false, int SITE = 0>
+// VS = 0: a 4:2:2 surface (kFmtNV16 / kFmtP210), SRC its sample type likewise; the chroma row of a pixel is its own (yuv_decode).
+template <typename SRC, bool YUV = false, int SITE = 0, int VS = 1>
 __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -199,7 +221,7 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     if constexpr (YUV)
     {
         float rgb[3];
-        yuv_decode<SRC, SITE>(a.imgs[im], a.pitch[im], a.plane[im], x, y, iw, ih, a.yuv, rgb);
+        yuv_decode<SRC, SITE, VS>(a.imgs[im], a.pitch[im], a.plane[im], x, y, iw, ih, a.yuv, rgb);
         v0[0] = (_Float16)rgb[0];
         v0[1] = (_Float16)rgb[1];
         v0[2] = (_Float16)rgb[2];
@@ -342,7 +364,7 @@ static void with_blob_type(const PostArgs& a, F f)
 template <typename F>
 static void with_sample_type(int fmt, F f)
 {
-    if (fmt == kFmtNV12) f(uint8_t{});
+    if (fmt_yuv_bits(fmt) == 8) f(uint8_t{});
     else f(uint16_t{});
 }
 template <typename F>
@@ -359,6 +381,15 @@ static void with_siting(int siting, F f)
     else if (siting == 2) f(std::integral_constant<int, 2>{});
     else f(std::integral_constant<int, 0>{});
 }
+// f(siting, vertical chroma shift VS) of a YUV surface: VS 1 = 4:2:0 with its three sitings; VS 0 = 4:2:2, left or centre -- top-left has no
+// vertical meaning there and IS left (the same kernels, the same bytes).
+template <typename F>
+static void with_chroma(int fmt, int siting, F f)
+{
+    if (!fmt_is_422(fmt)) with_siting(siting, [&](auto site) { f(site, std::integral_constant<int, 1>{}); });
+    else if (siting != 0) f(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
+    else f(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+}
 
 void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t st)
 {
@@ -373,7 +404,9 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
         const dim3 grid((max_tw + 31) / 32, (max_th + 7) / 8, a.ntiles), block(256);
         if (fmt_is_yuv(a.fmt))
             with_sample_type(a.fmt, [&](auto src) {
-                with_siting(a.siting, [&](auto site) { hipLaunchKernelGGL((preproc_tiles<decltype(src), true, decltype(site)::value>), grid, block, 0, st, a); });
+                with_chroma(a.fmt, a.siting, [&](auto site, auto vs) {
+                    hipLaunchKernelGGL((preproc_tiles<decltype(src), true, decltype(site)::value, decltype(vs)::value>), grid, block, 0, st, a);
+                });
             });
         else if (a.fmt == kFmtF16) hipLaunchKernelGGL(preproc_tiles<_Float16>, grid, block, 0, st, a);
         else if (a.fmt == kFmtF32) hipLaunchKernelGGL(preproc_tiles<float>, grid, block, 0, st, a);
@@ -907,7 +940,7 @@ static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipS
     else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
 }
 
-// ---- YUV 4:2:0 output (PostArgs::out_fmt kFmtNV12 / kFmtP010) ----------------------------------------------------------------------
+// ---- YUV 4:2:0 and 4:2:2 output (PostArgs::out_fmt kFmtNV12 / kFmtP010, kFmtNV16 / kFmtP210) ------------------------------------
 // code = floor(v * scale + add) clamped to [0, maxcode] (add = offset + 0.5f), as the sample type stores it: P010 keeps it in the high bits
 template <typename TO>
 __device__ __forceinline__ unsigned yuv_code(float v, float scale, float add, float maxcode)
@@ -951,10 +984,13 @@ __device__ __forceinline__ float out_pixel(const TP* b, long long ss, int w, int
 // QuadBox: out_scale OS = 4, 2 or 1 (K = 4 / OS x4 pixels per output pixel and axis; (sx, sy) the quad's first x4 pixel in the blob).
 // The quad is the 2K x 2K block in one or four merged_block fetches; a neighbour is out_pixel at (sx + K ox, sy + K oy), K-aligned like
 // sx and sy.
+// whole_quads: both rows of every quad exist whatever the surface (a tile's rectangle has an even number of rows) -- what a 4:2:2 surface,
+// whose rectangles may end on an odd row, needs to know (yuv_quad).
 template <typename TP, int OS>
 struct QuadBox
 {
     static constexpr int K = 4 / OS;
+    static constexpr bool whole_quads = OS != 1; // (4 th rows of x4 pixels: even at out_scale 4 and 2, th of them at out_scale 1)
     long long ss;
     int w, h, sx, sy, tta;
     __device__ __forceinline__ void quad(const TP* b, float (&d)[2][2]) const
@@ -996,6 +1032,7 @@ struct QuadBox
 template <typename TP>
 struct QuadArea
 {
+    static constexpr bool whole_quads = false;
     long long ss;
     int w, h, crop, tta, nx, Lx, ny, Ly;
     float norm;
@@ -1027,58 +1064,92 @@ struct QuadArea
 // the lane beside it / the wave above it, served by the caches, and free of any cross-lane dependence on threads that have returned.  At
 // a tile-first column / row the offset is 0, the pixel's own: the same loads, the same arithmetic, hence bitwise d(2X, .) / d(., 2Y) with
 // no divergent branch.
-template <typename TO, int SITE, typename SRC, typename TP>
-__device__ __forceinline__ void yuv_quad(const PostArgs& a, const BaseTile& t, int im, int gx, int gy, const SRC& src, const TP* b0, long long cstep)
+//
+// VS (the surface's vertical chroma shift): 1 = 4:2:0, the above.  0 = 4:2:2 (kFmtNV16 / kFmtP210; include/realsr_hip.h "YUV 4:2:2"): the unit
+// is a 2 x 1 luma pair and its (U, V), and the thread makes the two stacked pairs of its quad -- one gather of the same 2 x 2 block, two UV
+// stores.  Per row j and channel, m_j = (d(2X, j) + d(2X+1, j)) * 0.5f (SITE 0) or Hs(j) * 0.25f (SITE 1; top-left is left here); nothing
+// is filtered vertically, so no row clamp exists.  rows = the luma rows of this quad that exist: 2, or 1 where the tile's rectangle ends on
+// an odd row (no parity rule holds for a 4:2:2 surface's rows) -- then nothing of row 1 is gathered (unless SRC::whole_quads says it cannot
+// happen) or stored.
+template <typename TO, int SITE, int VS, typename SRC, typename TP>
+__device__ __forceinline__ void yuv_quad(const PostArgs& a, const BaseTile& t, int im, int gx, int gy, const SRC& src, const TP* b0, long long cstep, int rows = 2)
 {
+    constexpr int NC = VS ? 1 : 2; // chroma rows of the quad
     const YuvCoef& k = a.yuv;
-    float yq[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, ym = 0.f, rm = 0.f, bm = 0.f;
+    float yq[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, ym[NC], rm[NC], bm[NC];
+#pragma unroll
+    for (int n = 0; n < NC; n++) ym[n] = rm[n] = bm[n] = 0.f;
+    [[maybe_unused]] const int xl = gx ? -1 : 0, yu = gy ? -1 : 0; // output column xl / row yu, relative to the quad's first pixel
 #pragma unroll 1
     for (int q = 0; q < 3; q++)
     {
         const TP* b = b0 + q * cstep;
         float d[2][2];
-        src.quad(b, d);
-        const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
-        float m;
-        if constexpr (SITE == 0) m = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
+        if (VS || SRC::whole_quads || rows == 2) src.quad(b, d);
         else
         {
-            const int xl = gx ? -1 : 0, yu = gy ? -1 : 0; // output column xl / row yu, relative to the quad's first pixel
+            d[0][0] = src.at(b, 0, 0), d[0][1] = src.at(b, 1, 0);
+            d[1][0] = d[0][0], d[1][1] = d[0][1]; // (carried along, never stored)
+        }
+        const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
+        float m[NC];
+        if constexpr (VS == 0)
+        {
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+                if constexpr (SITE == 0) m[j] = mul_rn(add_rn(d[j][0], d[j][1]), 0.5f);
+                else m[j] = mul_rn(add_rn(add_rn(src.at(b, xl, min(j, rows - 1)), d[j][1]), add_rn(d[j][0], d[j][0])), 0.25f);
+        }
+        else if constexpr (SITE == 0) m[0] = mul_rn(add_rn(add_rn(d[0][0], d[0][1]), add_rn(d[1][0], d[1][1])), 0.25f);
+        else
+        {
             float hs[2];
 #pragma unroll
             for (int j = 0; j < 2; j++) hs[j] = add_rn(add_rn(src.at(b, xl, j), d[j][1]), add_rn(d[j][0], d[j][0]));
-            if constexpr (SITE == 1) m = mul_rn(add_rn(hs[0], hs[1]), 0.125f);
+            if constexpr (SITE == 1) m[0] = mul_rn(add_rn(hs[0], hs[1]), 0.125f);
             else
             {
                 const float u0 = src.at(b, 0, yu);
                 const float hu = add_rn(add_rn(src.at(b, xl, yu), src.at(b, 1, yu)), add_rn(u0, u0));
-                m = mul_rn(add_rn(add_rn(hu, hs[1]), add_rn(hs[0], hs[0])), 0.0625f);
+                m[0] = mul_rn(add_rn(add_rn(hu, hs[1]), add_rn(hs[0], hs[0])), 0.0625f);
             }
         }
 #pragma unroll
         for (int j = 0; j < 2; j++)
 #pragma unroll
             for (int i = 0; i < 2; i++) yq[j][i] = add_rn(yq[j][i], mul_rn(kq, d[j][i]));
-        ym = add_rn(ym, mul_rn(kq, m));
-        if (q == 0) rm = m;
-        if (q == 2) bm = m;
+#pragma unroll
+        for (int n = 0; n < NC; n++)
+        {
+            ym[n] = add_rn(ym[n], mul_rn(kq, m[n]));
+            if (q == 0) rm[n] = m[n];
+            if (q == 2) bm[n] = m[n];
+        }
     }
     const long long pitch = a.out_pitch[im];
     const int X = src.out_x(t.out_x) + 2 * gx, Y = src.out_y(t.out_y - a.out_row0) + 2 * gy; // the quad's first luma sample
     uint8_t* const oy = a.outs[im] + Y * pitch + (long long)X * (int)sizeof(TO);
 #pragma unroll
     for (int j = 0; j < 2; j++)
-        store_pair<TO>(oy + j * pitch, yuv_code<TO>(yq[j][0], k.yscale, k.yadd, k.maxcode), yuv_code<TO>(yq[j][1], k.yscale, k.yadd, k.maxcode));
-    const float cb = mul_rn(sub_rn(bm, ym), k.icb), cr = mul_rn(sub_rn(rm, ym), k.icr);
-    uint8_t* const ouv = a.outs[im] + a.out_plane[im] + (Y >> 1) * pitch + (long long)X * (int)sizeof(TO);
-    store_pair<TO>(ouv, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
+        if (VS || j < rows)
+            store_pair<TO>(oy + j * pitch, yuv_code<TO>(yq[j][0], k.yscale, k.yadd, k.maxcode), yuv_code<TO>(yq[j][1], k.yscale, k.yadd, k.maxcode));
+    // the (U, V) pairs: a UV row is as long as a Y row, a pair as wide as two luma samples; 4:2:0 has one for the quad, on UV row Y / 2
+    uint8_t* const ouv = a.outs[im] + a.out_plane[im] + (VS ? Y >> 1 : Y) * pitch + (long long)X * (int)sizeof(TO);
+#pragma unroll
+    for (int n = 0; n < NC; n++)
+    {
+        const float cb = mul_rn(sub_rn(bm[n], ym[n]), k.icb), cr = mul_rn(sub_rn(rm[n], ym[n]), k.icr);
+        if (VS || n < rows) store_pair<TO>(ouv + n * pitch, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
+    }
 }
 
 // The YUV 4:2:0 sibling of postproc_tiles_box: one thread makes ONE quad (yuv_quad over QuadBox) at the context's out_scale OS (4, 2 or
 // 1).  A tile's rectangle starts and ends on even output pixels (the engine refuses an out_scale 1 call where it would not), so no quad
 // crosses a tile.  Lanes run along x.
 // TP: element type of the blob (_Float16, or float in precise mode); TO: sample type of the surface, uint8_t (NV12) or uint16_t (P010).
-template <typename TP, typename TO, int OS, int SITE = 0>
+// VS = 0: a 4:2:2 surface (TO: uint8_t NV16, uint16_t P210), two stacked luma pairs per thread.  Its rectangles start and end on even
+// COLUMNS only; where one has an odd number of rows (out_scale 1) the threads of its last quad row make one pair (yuv_quad, rows).
+template <typename TP, typename TO, int OS, int SITE = 0, int VS = 1>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
 {
     constexpr int K = 4 / OS, Q = 2 * K; // x4 pixels per output pixel / per quad, along an axis
@@ -1086,18 +1157,20 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
     const int im = __builtin_amdgcn_readfirstlane(t.img);
     const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (gx >= t.out_w / Q || gy >= t.out_h / Q) return;
+    const int oh = t.out_h / K; // output rows of the rectangle (4:2:0: even)
+    if (gx >= t.out_w / Q || 2 * gy >= oh) return;
     const int w = t.tw * 4, h = t.th * 4;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const QuadBox<TP, OS> src{a.slot_stride / (long long)sizeof(TP), w, h, gx * Q + a.crop, gy * Q + a.crop, a.tta};
-    yuv_quad<TO, SITE>(a, t, im, gx, gy, src, b0, (long long)w * h);
+    yuv_quad<TO, SITE, VS>(a, t, im, gx, gy, src, b0, (long long)w * h, min(2, oh - 2 * gy));
 }
 
 // The sibling of postproc_tiles_yuv for the scales n / d that are not 4, 2 or 1: yuv_quad over QuadArea.  A tile's rectangle is
 // tilesize * n / d output pixels and starts at its multiples (per axis: tilesize * nx / dx columns, tilesize * ny / dy rows); the engine
 // admits the call only where those, w * nx / dx and h * ny / dy are even (check_yuv_out), so no quad crosses a tile or the image's edge.
 // Lanes run along x.
-template <typename TP, typename TO, int SITE>
+// VS = 0: a 4:2:2 surface -- w * nx / dx and tilesize * nx / dx are even, the two row counts are any (yuv_quad, rows).
+template <typename TP, typename TO, int SITE, int VS = 1>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -1105,31 +1178,34 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
     const int nx = a.num, Lx = 4 * a.den, ny = a.num_y, Ly = 4 * a.den_y;
     const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (gx >= t.out_w * nx / Lx / 2 || gy >= t.out_h * ny / Ly / 2) return;
+    const int oh = t.out_h * ny / Ly; // output rows of the rectangle (4:2:0: even)
+    if (gx >= t.out_w * nx / Lx / 2 || 2 * gy >= oh) return;
     const int w = t.tw * 4, h = t.th * 4;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const QuadArea<TP> src{a.slot_stride / (long long)sizeof(TP), w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, 2 * gx, 2 * gy};
-    yuv_quad<TO, SITE>(a, t, im, gx, gy, src, b0, (long long)w * h);
+    yuv_quad<TO, SITE, VS>(a, t, im, gx, gy, src, b0, (long long)w * h, min(2, oh - 2 * gy));
 }
 
 template <typename TP, typename TO>
 static void launch_postproc_yuv_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
-    const int Lx = 4 * a.den, Ly = 4 * a.den_y; // (ow_tile / 2) x (oh_tile / 2) quads per tile
-    const dim3 grid((max_ow * a.num / Lx / 2 + 63) / 64, (max_oh * a.num_y / Ly / 2 + 3) / 4, a.ntiles), block(256);
-    with_siting(a.siting, [&](auto site) { hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, decltype(site)::value>), grid, block, 0, st, a); });
+    const int Lx = 4 * a.den, Ly = 4 * a.den_y; // (ow_tile / 2) x (oh_tile / 2) quads per tile (4:2:2: the last quad row may be half a quad)
+    const dim3 grid((max_ow * a.num / Lx / 2 + 63) / 64, ((max_oh * a.num_y / Ly + 1) / 2 + 3) / 4, a.ntiles), block(256);
+    with_chroma(a.out_fmt, a.siting, [&](auto site, auto vs) {
+        hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, decltype(site)::value, decltype(vs)::value>), grid, block, 0, st, a);
+    });
 }
 
 template <typename TP, typename TO>
 static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
     const int q = a.box > 1 ? 2 * a.box : 2; // x4 pixels per quad and axis
-    const dim3 grid((max_ow / q + 63) / 64, (max_oh / q + 3) / 4, a.ntiles), block(256);
-    with_siting(a.siting, [&](auto site) {
-        constexpr int SITE = decltype(site)::value;
-        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1, SITE>), grid, block, 0, st, a);
-        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2, SITE>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4, SITE>), grid, block, 0, st, a);
+    const dim3 grid((max_ow / q + 63) / 64, ((max_oh / (q / 2) + 1) / 2 + 3) / 4, a.ntiles), block(256); // (4:2:2: the last quad row may be half a quad)
+    with_chroma(a.out_fmt, a.siting, [&](auto site, auto vs) {
+        constexpr int SITE = decltype(site)::value, VS = decltype(vs)::value;
+        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1, SITE, VS>), grid, block, 0, st, a);
+        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2, SITE, VS>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4, SITE, VS>), grid, block, 0, st, a);
     });
 }
 
@@ -1146,7 +1222,7 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
     with_blob_type(a, [&](auto tp) {
         using TP = decltype(tp);
         if (fmt_is_yuv(a.out_fmt))
-        { // a 4:2:0 surface: one thread per luma quad, at every out_scale or ratio, with and without TTA
+        { // a 4:2:0 or 4:2:2 surface: one thread per luma quad, at every out_scale or ratio, with and without TTA
             with_sample_type(a.out_fmt, [&](auto to) {
                 using TO = decltype(to);
                 if (generic_ratio(a)) launch_postproc_yuv_area<TP, TO>(a, max_ow, max_oh, st);
@@ -1374,7 +1450,7 @@ __global__ __launch_bounds__(256) void diff_tiles(const DiffArgs a)
     int r[4];
     tile_source_rect(a.w, a.h, a.T, a.P, xi, yi, r);
     const int rect = blockIdx.z;
-    const int es = a.fmt == kFmtF32 ? 4 : ((a.fmt == kFmtF16 || a.fmt == kFmtP010) ? 2 : (a.fmt == kFmtU8 ? a.c : 1));
+    const int es = a.fmt == kFmtF32 ? 4 : (a.fmt == kFmtF16 ? 2 : (a.fmt == kFmtU8 ? a.c : (fmt_yuv_bits(a.fmt) + 7) / 8)); // (a YUV surface: of one sample)
     int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
     long long off_a = 0, off_b = 0;
     if (fmt_is_yuv(a.fmt))
@@ -1383,7 +1459,7 @@ __global__ __launch_bounds__(256) void diff_tiles(const DiffArgs a)
         { // the (U, V) pairs the decode of this rectangle reads: one chroma sample beyond its own, at every siting
             const int cx0 = max((r[0] >> 1) - 1, 0), cx1 = min(((r[2] - 1) >> 1) + 1, a.w / 2 - 1);
             bx0 = cx0 * 2 * es, bx1 = (cx1 + 1) * 2 * es;
-            y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1;
+            if (!fmt_is_422(a.fmt)) y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1; // (4:2:2: the rectangle's own rows)
             off_a = a.plane_a, off_b = a.plane_b;
         }
     }
@@ -1434,7 +1510,7 @@ __global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
     }
     int r[4];
     tile_source_rect(a.w, a.h, a.T, a.P, xi, yi, r);
-    const int es = a.fmt == kFmtF32 ? 4 : ((a.fmt == kFmtF16 || a.fmt == kFmtP010) ? 2 : (a.fmt == kFmtU8 ? a.c : 1));
+    const int es = a.fmt == kFmtF32 ? 4 : (a.fmt == kFmtF16 ? 2 : (a.fmt == kFmtU8 ? a.c : (fmt_yuv_bits(a.fmt) + 7) / 8)); // (a YUV surface: of one sample)
     int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
     long long off_a = 0, off_b = 0;
     if (fmt_is_yuv(a.fmt))
@@ -1443,7 +1519,7 @@ __global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
         { // the (U, V) pairs the decode of this rectangle reads (diff_tiles)
             const int cx0 = max((r[0] >> 1) - 1, 0), cx1 = min(((r[2] - 1) >> 1) + 1, a.w / 2 - 1);
             bx0 = cx0 * 2 * es, bx1 = (cx1 + 1) * 2 * es;
-            y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1;
+            if (!fmt_is_422(a.fmt)) y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1;
             off_a = p.plane_a, off_b = p.plane_b;
         }
     }

@@ -24,7 +24,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_P010, RSR_FMT_U8_HWC
+from . import RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_NV16, RSR_FMT_P010, RSR_FMT_P210, RSR_FMT_U8_HWC
 
 _FMT = {torch.float16: RSR_FMT_F16_CHW, torch.float32: RSR_FMT_F32_CHW}
 
@@ -143,14 +143,52 @@ def _on_current_stream(device, enqueue):
     return y
 
 
-# ---- YUV 4:2:0 surfaces: what a hardware decoder yields and an encoder takes ----------------------------------------------------------
+# ---- YUV 4:2:0 (and, chroma=422, 4:2:2) surfaces: what a hardware decoder yields and an encoder takes ----------------------------------------------------------
 _YUV = {torch.uint8: RSR_FMT_NV12, torch.int16: RSR_FMT_P010}  # (P010 words as int16 too: torch's uint16 is a late and partial dtype)
 if hasattr(torch, "uint16"):
     _YUV[torch.uint16] = RSR_FMT_P010
+# ... and 4:2:2 surfaces (keyword chroma=422): what broadcast and archive codecs hold -- a UV row per Y row
+_YUV422 = {t: {RSR_FMT_NV12: RSR_FMT_NV16, RSR_FMT_P010: RSR_FMT_P210}[f] for t, f in _YUV.items()}
+_YUV_FMTS = (RSR_FMT_NV12, RSR_FMT_P010, RSR_FMT_NV16, RSR_FMT_P210)
 
 
-def _planes(sr, s, what):
-    """The (y, uv) views of a surface -- a (3h / 2, w) tensor or a pair of planes -- validated; ValueError before anything is launched."""
+def _yuv_fmt(dtype, chroma):
+    return (_YUV422 if chroma == 422 else _YUV)[dtype]
+
+
+def _check_chroma(chroma, who):
+    if chroma not in (420, 422):
+        raise ValueError("%s: chroma must be 420 or 422 (YUV 4:2:0 / 4:2:2 surfaces), not %r" % (who, chroma))
+
+
+def _planes422(sr, s, what):
+    """_planes for a 4:2:2 surface: a (2h, w) tensor -- h rows of Y, then h rows of interleaved UV -- or a (y, uv) pair, uv (h, w)."""
+    if isinstance(s, (tuple, list)):
+        if len(s) != 2 or not all(isinstance(t, torch.Tensor) for t in s):
+            raise ValueError("upscale_yuv: %s must be a surface tensor or a (y, uv) pair of tensors" % what)
+        y, uv = s
+    else:
+        if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.shape[0] % 2 or s.shape[0] < 2:
+            raise ValueError("upscale_yuv: %s must be a (2h, w) tensor: h rows of Y, then h rows of interleaved UV (a YUV 4:2:2 surface)" % what)
+        h = s.shape[0] // 2
+        y, uv = s[:h], s[h:]
+    if y.dim() != 2 or uv.dim() != 2 or y.dtype != uv.dtype or y.device != uv.device:
+        raise ValueError("upscale_yuv: y and uv of %s must be 2-D tensors of one dtype on one device" % what)
+    if y.dtype not in _YUV422:
+        raise ValueError("upscale_yuv: dtype %s is not supported (uint8 = NV16; uint16 / int16 = P210)" % y.dtype)
+    if y.device.type != "cuda" or y.device.index != sr.gpuid:
+        raise ValueError("upscale_yuv: %s is on %s, the context runs on cuda:%d" % (what, y.device, sr.gpuid))
+    h, w = y.shape
+    if h < 1 or w < 2 or w % 2 or tuple(uv.shape) != (h, w):
+        raise ValueError("upscale_yuv: y %s with uv %s is not a YUV 4:2:2 surface (even w, uv (h, w))" % (tuple(y.shape), tuple(uv.shape)))
+    return y, uv
+
+
+def _planes(sr, s, what, chroma=420):
+    """The (y, uv) views of a surface -- a (3h / 2, w) tensor or a pair of planes -- validated; ValueError before anything is launched.
+    chroma=422: a (2h, w) tensor or a pair with uv (h, w) (_planes422)."""
+    if chroma == 422:
+        return _planes422(sr, s, what)
     if isinstance(s, (tuple, list)):
         if len(s) != 2 or not all(isinstance(t, torch.Tensor) for t in s):
             raise ValueError("upscale_yuv: %s must be a surface tensor or a (y, uv) pair of tensors" % what)
@@ -206,6 +244,14 @@ def _out_size_yuv(sr, w, h, who):
     return sr.out_size_yuv(w, h)
 
 
+def _out_size_yuv422(sr, fmt, w, h, who):
+    """(ow, oh) of the 4:2:2 output for a w x h surface: sr.out_size_fmt at every out_scale, ratio or pair -- ValueError with "YUV" in it where
+    the engine would refuse the call (an odd tile rectangle or image width), and for a context that has no out_size_fmt."""
+    if not hasattr(sr, "out_size_fmt"):
+        raise ValueError("%s: this context writes no YUV 4:2:2 surfaces (no out_size_fmt)" % who)
+    return sr.out_size_fmt(fmt, w, h)
+
+
 def _yuv_ratio_note(sr):
     """What a size refusal adds while a YUV surface is written at a ratio other than 4 / 2 / 1 (else nothing)."""
     if getattr(sr, "out_scale", sr.scale):
@@ -213,7 +259,7 @@ def _yuv_ratio_note(sr):
     return " (a YUV surface at the output ratio %s)" % (_ratio_text(sr),)
 
 
-def upscale_yuv(sr, surface, out=None):
+def upscale_yuv(sr, surface, out=None, chroma=420):
     """upscale() for a YUV 4:2:0 surface on the context's GPU: the YUV <-> RGB conversion and the chroma resampling happen inside the
     engine's pre- and post-processing kernels (RSR_FMT_NV12 / RSR_FMT_P010, include/realsr_hip.h; options "yuv_matrix", "yuv_range"), so no
     RGB frame is materialised.  Where the chroma samples sit is the context's option "yuv_siting" (sr.yuv_siting: 0 centre, 1 left -- what
@@ -222,22 +268,30 @@ def upscale_yuv(sr, surface, out=None):
     lies below y in memory, say) is packed into one allocation first.  Returns the same layout at sr.out_scale -- or at sr.out_ratio (3/2, 4/3,
     9/4, 3 ...) where sr.out_size_yuv admits the size --: a (3H' / 2, W') tensor,
     or for a pair the (y, uv) views of one.  out: the surface (or pair) to write and return instead.  Runs on torch.cuda.current_stream(),
-    with no host synchronisation inside."""
+    with no host synchronisation inside.
+    chroma=422: a YUV 4:2:2 surface (RSR_FMT_NV16 / RSR_FMT_P210: chroma halved horizontally only, what DVCPRO-HD, ProRes 422, XDCAM HD422
+    hold) -- a (2H, W) tensor, H rows of Y and H rows of interleaved UV, or a (y, uv) pair with uv (H, W); uint8 is NV16, uint16 / int16
+    P210.  Any H >= 1 is taken.  The result has the same layout, sized by sr.out_size_fmt: ValueError with "YUV" in it where the engine would
+    refuse (w or tilesize times the x ratio odd)."""
+    _check_chroma(chroma, "upscale_yuv")
     pair = isinstance(surface, (tuple, list))
-    y, uv = _planes(sr, surface, "surface")
-    fmt, (h, w) = _YUV[y.dtype], y.shape
-    ow, oh = _out_size_yuv(sr, w, h, "upscale_yuv")  # (out_scale 4 / 2 / 1, or a ratio such as 3/2: sr.out_ratio)
+    y, uv = _planes(sr, surface, "surface", chroma)
+    fmt, (h, w) = _yuv_fmt(y.dtype, chroma), y.shape
+    if chroma == 422:
+        ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_yuv")
+    else:
+        ow, oh = _out_size_yuv(sr, w, h, "upscale_yuv")  # (out_scale 4 / 2 / 1, or a ratio such as 3/2: sr.out_ratio)
     if out is not None:
         if isinstance(out, (tuple, list)) != pair:
             raise ValueError("upscale_yuv: out must be a %s like the input" % ("(y, uv) pair" if pair else "surface tensor"))
-        oy, ouv = _planes(sr, out, "out")
+        oy, ouv = _planes(sr, out, "out", chroma)
         if tuple(oy.shape) != (oh, ow) or oy.dtype != y.dtype or oy.device != y.device:
             raise ValueError("upscale_yuv: out must be a %s YUV surface of %d x %d on %s" % (y.dtype, ow, oh, y.device))
         dout = _describe_yuv(oy, ouv)
         if dout is None:
             raise ValueError("upscale_yuv: out is not addressable by one row pitch and a plane pitch")
     else:
-        o = y.new_empty((oh * 3 // 2, ow))
+        o = y.new_empty((oh * 2 if chroma == 422 else oh * 3 // 2, ow))
         oy, ouv = o[:oh], o[oh:]
         out = (oy, ouv) if pair else o
         dout = _describe_yuv(oy, ouv)
@@ -255,12 +309,12 @@ def _pinned_u8(n):
     return torch.empty(n, dtype=torch.uint8, pin_memory=True)
 
 
-def _image_desc(sr, t, what):
+def _image_desc(sr, t, what, chroma=420):
     """(fmt, w, h, c, descriptor or None) of ONE image as upscale (a single uint8 / float image) or upscale_yuv (a surface or a (y, uv)
-    pair) takes it; ValueError before anything is launched."""
+    pair; chroma: its subsampling) takes it; ValueError before anything is launched."""
     if isinstance(t, (tuple, list)) or (isinstance(t, torch.Tensor) and t.dim() == 2):
-        y, uv = _planes(sr, t, what)
-        return _YUV[y.dtype], y.shape[1], y.shape[0], 3, _describe_yuv(y, uv)
+        y, uv = _planes(sr, t, what, chroma)
+        return _yuv_fmt(y.dtype, chroma), y.shape[1], y.shape[0], 3, _describe_yuv(y, uv)
     fmt, batched = _check(sr, t)
     if batched:
         raise ValueError("upscale_delta: %s must be ONE image, not a batch %s" % (what, tuple(t.shape)))
@@ -268,16 +322,16 @@ def _image_desc(sr, t, what):
     return fmt, w, h, c, describe(t)
 
 
-def _desc_or_packed(sr, t, what):
+def _desc_or_packed(sr, t, what, chroma=420):
     """(descriptor, keep) of the image t: its own where one fits (_image_desc), else that of a packed copy `keep` (kept alive by the
     stream ordering, like any temporary of a torch op)."""
-    d = _image_desc(sr, t, what)[4]
+    d = _image_desc(sr, t, what, chroma)[4]
     if d is not None:
         return d, None
     if isinstance(t, torch.Tensor) and t.dim() == 3:
         keep = t.contiguous()
         return describe(keep), keep
-    y, uv = _planes(sr, t, what)
+    y, uv = _planes(sr, t, what, chroma)
     keep = torch.cat([y, uv], dim=0)
     return _describe_yuv(keep[:y.shape[0]], keep[y.shape[0]:]), keep
 
@@ -291,7 +345,7 @@ def _same_layout(a, b):
     return isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.shape == b.shape and a.dtype == b.dtype and a.device == b.device
 
 
-def upscale_delta(sr, x, prev_x, prev_y, out=None):
+def upscale_delta(sr, x, prev_x, prev_y, out=None, chroma=420):
     """upscale() / upscale_yuv() of the video frame x, given the previous frame prev_x and its result prev_y: only the tiles whose SOURCE
     RECTANGLE differs between prev_x and x walk the network (rsr_diff_tiles + rsr_process_device_masked, include/realsr_hip.h); every
     other tile's output rectangle is a function of bytes that did not change, so what prev_y holds there is the answer, bit for bit.
@@ -302,12 +356,16 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None):
     Returns (out, tiles_run).  prev_x=None: every tile runs (the first frame, a scene cut) and prev_y only provides the memory.
     Steps, all on torch.cuda.current_stream(): the diff; a copy of the mask into pinned memory; ONE stream synchronisation -- the grid of
     every launch depends on the mask, so the host has to see it: this is the only host wait, and it is what the skipped tiles are paid
-    with --; the masked call."""
-    fmt, w, h, c, _ = _image_desc(sr, x, "x")
+    with --; the masked call.
+    chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them."""
+    _check_chroma(chroma, "upscale_delta")
+    fmt, w, h, c, _ = _image_desc(sr, x, "x", chroma)
     if prev_x is not None and not _same_layout(x, prev_x):
         raise ValueError("upscale_delta: prev_x must have x's layout, shape, dtype and device")
-    yuv = fmt in (RSR_FMT_NV12, RSR_FMT_P010)
-    if yuv:
+    yuv = fmt in _YUV_FMTS
+    if yuv and chroma == 422:
+        ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_delta")
+    elif yuv:
         ow, oh = _out_size_yuv(sr, w, h, "upscale_delta")
     else:
         ow, oh = _out_size(sr, w, h)
@@ -315,7 +373,7 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None):
     for t, what in ((prev_y, "prev_y"),) + (((out, "out"),) if out is not None else ()):
         if isinstance(t, (tuple, list)) != isinstance(x, (tuple, list)):
             raise ValueError("upscale_delta: %s must be a %s like x" % (what, "(y, uv) pair" if isinstance(x, (tuple, list)) else "tensor"))
-        f2, w2, h2, c2, d2 = _image_desc(sr, t, what)
+        f2, w2, h2, c2, d2 = _image_desc(sr, t, what, chroma)
         if (f2, w2, h2, c2) != (fmt, ow, oh, c):
             raise ValueError("upscale_delta: %s must hold the %d x %d result for x (%d x %d) in x's format%s" % (what, ow, oh, w, h, note))
         if d2 is None:
@@ -325,12 +383,12 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None):
     else:
         for dst, src in (zip(out, prev_y) if isinstance(out, (tuple, list)) else ((out, prev_y),)):
             dst.copy_(src)
-    dout = _image_desc(sr, out, "out")[4]
+    dout = _image_desc(sr, out, "out", chroma)[4]
     first = x[0] if isinstance(x, (tuple, list)) else x
     # A view no descriptor fits is packed first -- BOTH frames here, in front of the wait below: the packing runs on torch's current
     # stream, and the side stream (where the diff reads the copies) is ordered behind that stream only up to the wait.
-    dx, keep_x = _desc_or_packed(sr, x, "x")
-    dp, keep_p = _desc_or_packed(sr, prev_x, "prev_x") if prev_x is not None else (None, None)
+    dx, keep_x = _desc_or_packed(sr, x, "x", chroma)
+    dp, keep_p = _desc_or_packed(sr, prev_x, "prev_x", chroma) if prev_x is not None else (None, None)
     nx, ny = sr.tile_count(w, h)
     cur = torch.cuda.current_stream(first.device)
     st = cur if cur.cuda_stream != 0 else _side_stream(first.device)  # (the null stream means "synchronously" to the C calls: see upscale)
@@ -356,17 +414,18 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None):
 SEQ_MAX = 16  # frames per rsr_process_device_sequence call (RSR_SEQ_MAX)
 
 
-def _new_like_result(x, ow, oh):
-    """An uninitialised result for the single image x (a tensor or a (y, uv) pair) at ow x oh, of x's kind."""
+def _new_like_result(x, ow, oh, chroma=420):
+    """An uninitialised result for the single image x (a tensor or a (y, uv) pair; chroma: a surface's subsampling) at ow x oh, of x's kind."""
+    rows = oh * 2 if chroma == 422 else oh * 3 // 2
     if isinstance(x, (tuple, list)):
-        o = x[0].new_empty((oh * 3 // 2, ow))
+        o = x[0].new_empty((rows, ow))
         return (o[:oh], o[oh:])
     if x.dim() == 2:
-        return x.new_empty((oh * 3 // 2, ow))
+        return x.new_empty((rows, ow))
     return x.new_empty((oh, ow, x.shape[2]) if x.dtype == torch.uint8 else (3, oh, ow))
 
 
-def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
+def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420):
     """upscale() / upscale_yuv() of N consecutive video frames: returns (ys, tiles_run), ys[k] bit for bit what upscale(frames[k]) returns.
     Only the tiles whose source rectangle differs from the frame before walk the network, and the changed tiles of up to 16 frames share
     their launches (rsr_diff_tiles_sequence + rsr_process_device_sequence, include/realsr_hip.h); every other rectangle of ys[k] is copied
@@ -378,7 +437,9 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
     the result, each image addressable by row and plane pitch.  The result has the kind the input had.
     Windows of at most 16 frames; window g + 1 takes the last frame and output of window g as its prev.  Per window, all on
     torch.cuda.current_stream() (the side stream for the null stream, as in upscale_delta): the diff of all pairs, ONE asynchronous copy
-    of the masks into pinned memory, ONE stream synchronisation, the sequence call."""
+    of the masks into pinned memory, ONE stream synchronisation, the sequence call.
+    chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them."""
+    _check_chroma(chroma, "upscale_sequence")
     stacked = isinstance(frames, torch.Tensor)
     if stacked:
         if frames.dim() != 4 or frames.shape[0] < 1:
@@ -389,7 +450,7 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
         if not xs:
             raise ValueError("upscale_sequence: frames must be a stacked tensor or a non-empty list of images")
     n = len(xs)
-    fmt, w, h, c, _ = _image_desc(sr, xs[0], "frames[0]")
+    fmt, w, h, c, _ = _image_desc(sr, xs[0], "frames[0]", chroma)
     for i, x in enumerate(xs[1:], 1):
         if not _same_layout(xs[0], x):
             raise ValueError("upscale_sequence: mixed layouts: frames[%d] differs from frames[0] in kind, shape, dtype or device" % i)
@@ -401,7 +462,9 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
         prev_y = None  # (nothing of it would be used: every tile of frames[0] runs)
     pair = isinstance(xs[0], (tuple, list))
     note = ""
-    if fmt in (RSR_FMT_NV12, RSR_FMT_P010):
+    if fmt in _YUV_FMTS and chroma == 422:
+        ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_sequence")
+    elif fmt in _YUV_FMTS:
         ow, oh = _out_size_yuv(sr, w, h, "upscale_sequence")
         note = _yuv_ratio_note(sr)
     else:
@@ -410,7 +473,7 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
     def result_desc(t, what):
         if isinstance(t, (tuple, list)) != pair:
             raise ValueError("upscale_sequence: %s must be a %s like the frames" % (what, "(y, uv) pair" if pair else "tensor"))
-        f2, w2, h2, c2, d2 = _image_desc(sr, t, what)
+        f2, w2, h2, c2, d2 = _image_desc(sr, t, what, chroma)
         if (f2, w2, h2, c2) != (fmt, ow, oh, c):
             raise ValueError("upscale_sequence: %s must hold the %d x %d result of a %d x %d frame in the frames' format%s" % (what, ow, oh, w, h, note))
         if d2 is None:
@@ -424,16 +487,16 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None):
             out = first.new_empty((n, oh, ow, c) if fmt == RSR_FMT_U8_HWC else (n, 3, oh, ow))
             ys = [out[i] for i in range(n)]
         else:
-            out = ys = [_new_like_result(x, ow, oh) for x in xs]
+            out = ys = [_new_like_result(x, ow, oh, chroma) for x in xs]
     else:
         if stacked != isinstance(out, torch.Tensor) or (stacked and out.dim() != 4) or len(out) != n:
             raise ValueError("upscale_sequence: out must be a %s of %d results like the frames" % ("stacked tensor" if stacked else "list", n))
         ys = [out[i] for i in range(n)]
     douts = [result_desc(y, "out[%d]" % i) for i, y in enumerate(ys)]
     # Views no descriptor fits are packed first -- all of them here, in front of the wait below (see upscale_delta).
-    packed = [_desc_or_packed(sr, x, "frames[%d]" % i) for i, x in enumerate(xs)]
+    packed = [_desc_or_packed(sr, x, "frames[%d]" % i, chroma) for i, x in enumerate(xs)]
     dxs = [p[0] for p in packed]
-    dprev_x, keep_p = _desc_or_packed(sr, prev_x, "prev_x") if prev_x is not None else (None, None)
+    dprev_x, keep_p = _desc_or_packed(sr, prev_x, "prev_x", chroma) if prev_x is not None else (None, None)
     nx, ny = sr.tile_count(w, h)
     nt = nx * ny
     cur = torch.cuda.current_stream(first.device)
