@@ -97,6 +97,10 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
 /* YUV 4:2:2 surfaces: what broadcast and archive codecs hold -- chroma halved horizontally only ("YUV 4:2:2" below; id 6 stays unknown too) */
 #define RSR_FMT_NV16 8  /* uint8  Y [h][w], then interleaved UV [h][w/2][2]; c must be 3 */
 #define RSR_FMT_P210 9  /* uint16 little-endian, the code in the HIGH 10 bits (code << 6), same layout */
+/* Planar YUV 4:4:4: what screen recordings, mezzanine masters and software video frameworks hold ("YUV 4:4:4" below; ids 10 and 11 stay unknown) */
+#define RSR_FMT_YUV444P   12  /* uint8  planes Y, U, V, each [h][w]; c must be 3 */
+#define RSR_FMT_YUV444P10 13  /* uint16 little-endian, the code in the LOW 10 bits (yuv444p10le), same layout */
+/* (Mind the contrast: P010 / P210 hold code << 6, as hardware decoders write it; YUV444P10 holds the code itself, as every producer of planar 4:4:4 does.) */
 
 /* rsr_process_device with a pixel format per side: what a tensor pipeline holds (float CHW in [0,1]) goes in and comes out without a
  * uint8 hop.  The two formats are independent; rsr_process_device(...) is exactly rsr_process_device_fmt(..., U8, ..., U8, ...).
@@ -203,13 +207,55 @@ int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
  *   Sequences.  The propagated UV rectangle of a tile has the tile's own rows.
  * One more small launch behind conv_last writes the surface, as for NV12 / P010: postproc_tiles_yuv / postproc_tiles_yuv_area with two stacked
  * 2 x 1 pairs per thread.  rsr_out_size_yuv and rsr_out_size_yuv_xy keep their exact 4:2:0 behaviour.
- * Out of scope: three-plane layouts (yuv422p: interleave the two chroma planes first), 4:4:4, 4:1:1, a siting per side, host pointers
+ * Out of scope: three-plane SUBSAMPLED layouts (yuv422p: interleave the two chroma planes first; "YUV 4:4:4" below says why rsr_image cannot
+ * describe them -- planar 4:4:4 itself is RSR_FMT_YUV444P / YUV444P10), 4:1:1, a siting per side, host pointers
  * (rsr_process*), groups of GPUs and the CLI, which stay uint8 RGB(A). */
 
 /* Host-only (no GPU): the admission rule and the size of an output in `out_fmt` at the pair of ratios and the tile size given -- *ow = w *
  * nx / dx, *oh = h * ny / dy (either pointer may be NULL).  RSR_FMT_U8_HWC / F16_CHW / F32_CHW: exactly rsr_out_size_xy.  RSR_FMT_NV12 /
- * P010: exactly rsr_out_size_yuv_xy.  RSR_FMT_NV16 / P210: the 4:2:2 rule above.  RSR_E_ARG for an unknown format. */
+ * P010: exactly rsr_out_size_yuv_xy.  RSR_FMT_NV16 / P210: the 4:2:2 rule above.  RSR_FMT_YUV444P / YUV444P10: exactly rsr_out_size_xy (a
+ * 4:4:4 surface has no parity rule).  RSR_E_ARG for an unknown format. */
 int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh);
+
+/* ---- YUV 4:4:4: RSR_FMT_YUV444P / RSR_FMT_YUV444P10 in and out (no reference counterpart) -------------------------------------------------
+ * Screen recordings (H.264 Hi444PP, HEVC RExt, AV1 4:4:4, lossless x264 / FFV1: subsampled chroma smears coloured text), ProRes 4444 and
+ * DNxHR 444 masters, and whatever was ever RGB inside libavfilter, VapourSynth or an encoder's input hold three FULL planes of integer codes:
+ * yuv444p / yuv444p10le.  Such a surface goes in and comes out as it is -- no chroma is halved to make NV16 of it, a 10-bit source never
+ * passes through 8 bits, and no RGB frame exists outside the library.  Either side of a call, independently of the other (YUV444P -> YUV444P,
+ * YUV444P10 -> NV12, P010 -> YUV444P10, U8_HWC -> YUV444P, YUV444P -> F16_CHW ...), through every entry point that takes NV16 / P210:
+ * rsr_process_device_fmt, _batch (windows, pitched surfaces), _masked, _sequence, rsr_diff_tiles, rsr_diff_tiles_sequence; in every mode: TTA,
+ * "precise", every "yuv_matrix" / "yuv_range", "out_scale" 4 / 2 / 1, rsr_set_out_ratio, rsr_set_out_ratio_xy.
+ *   Layout.  The rsr_image conventions of the planar float formats: `data` is Y(0,0); one row pitch serves all three planes, 0 = tightly packed;
+ *            plane q (0 = Y, 1 = U, 2 = V) starts at data + q * plane_pitch, 0 = h * row pitch.  Tightly packed: rsr_image_bytes = 3*w*h for
+ *            YUV444P, 6*w*h for YUV444P10; rsr_image_span follows.  YUV444P takes any byte pointer and any byte pitches; YUV444P10 refuses an
+ *            odd data pointer, row pitch or plane pitch, as the planar float formats refuse non-multiples of their element size.
+ *            The 10-bit code sits in the LOW bits of its word (P010 / P210: code << 6).  On input the bits above bit 9 are ignored (word &
+ *            1023); on output they are written 0.
+ *   Admission.  Every check is RSR_E_ARG before anything is launched; c must be 3; w, h >= 1.  There is NO PARITY RULE on either side: a 4:4:4
+ *            surface has no chroma pairs and no quads, so nothing can cross a tile or the image's edge.  Any w, any h, any tile size and any
+ *            admitted ratio is taken, exactly as for the RGB outputs: a 4:4:4 output needs the ratio rule and nothing else, and
+ *            rsr_out_size_fmt(RSR_FMT_YUV444P*, ...) is exactly rsr_out_size_xy.  35 x 25 at tile 16 is taken at x4, x2, x1 and 3/2 alike.
+ *   Options.  "yuv_matrix" and "yuv_range" apply.  "yuv_siting" has no meaning -- every chroma sample sits on its luma sample -- and 0, 1 and 2
+ *            give the same kernels and the same bytes.  "bgr" concerns RGB sides only.
+ *   The definition, exact.  Everything not said here is the NV12 / P010 definition above: the constants of rsr_yuv_constants (b = 8 for
+ *   YUV444P, 10 for YUV444P10), the matrix, clamps, code rounding, reflect-101 first, fp32 throughout, every operation rounded by itself.
+ *   Decode, image pixel (x, y).  Y, U, V are the codes at (x, y) of planes 0, 1, 2 (YUV444P10: word & 1023).  There is no chroma filter.
+ *            yn = (Y - yoff) * ys, cb = (U - coff) * cs, cr = (V - coff) * cs; then the matrix, the clamp to [0, 1] and the rounding to fp16
+ *            word for word as for NV12.
+ *   Encode, output pixel (x, y); d = what RSR_FMT_F32_CHW holds there at the context's scale, ratio or pair.  Y' = (Kr * R + Kg * G) + Kb * B;
+ *            Y code = floor(Y' * yscale + (yoff + 0.5f)) clamped to [0, 2^b - 1]; Cb = (B - Y') * fp32(1/(2(1-Kb))), Cr = (R - Y') *
+ *            fp32(1/(2(1-Kr))), codes floor(C * cscale + (coff + 0.5f)) clamped alike -- the 4:2:0 rule with m = d.  Nothing is filtered, so
+ *            no tile-first clamp exists.  Codes are stored as they are; the high six bits of a YUV444P10 word are 0.
+ *   Diff.    rsr_diff_tiles / rsr_diff_tiles_sequence compare the three planes over the tile's source rectangle and nothing beyond it;
+ *            YUV444P10 compares whole words.
+ *   Sequences.  The propagated rectangle is the tile's output rectangle in each of the three planes.
+ * One more small launch behind conv_last writes the surface, as for every YUV output: postproc_tiles_yuv444 / postproc_tiles_yuv444_area, one
+ * output pixel per thread and three plane stores.
+ * Out of scope: the three-plane SUBSAMPLED layouts (yuv420p, yuv422p and their 10-bit forms) -- rsr_image cannot express them: its one
+ * plane_pitch is the distance Y -> U AND U -> V.  Their chroma planes are smaller than the luma plane, so the two distances differ, and a
+ * window of such a canvas needs a U -> V distance (and a chroma row pitch) of its own, for which the descriptor has no field -- interleave the
+ * chroma planes to NV12 / NV16 first; semi-planar or packed 4:4:4 (NV24, P410, Y410, AYUV); 12- and 16-bit codes (rsr_yuv_constants keeps refusing them);
+ * 4:1:1; planar RGB (GBRP); a siting per side; host pointers (rsr_process*), groups of GPUs and the CLI, which stay uint8 RGB(A). */
 
 /* ---- rational output scales: x3, x3/2, x4/3, x9/4 ... area-averaged on the device (no reference counterpart) --------------------------
  * Option "out_scale" (rsr_set_option) takes the x4 image down to x2 or x1 inside the library.  rsr_set_out_ratio generalises it to the
@@ -380,6 +426,8 @@ int rsr_tile_source_rect(int w, int h, int tilesize, int prepadding, int tile, i
  *                                      6 bits included.
  *   RSR_FMT_NV16 / RSR_FMT_P210        the Y samples of the rectangle, and the (U, V) pairs of the same chroma columns on rows sy0 .. sy1 - 1
  *                                      ("YUV 4:2:2": a chroma row per luma row).  P210 compares whole words.
+ *   RSR_FMT_YUV444P / RSR_FMT_YUV444P10  the samples of the rectangle in each of the three planes, nothing beyond it ("YUV 4:4:4").  YUV444P10
+ *                                      compares whole words, the bits above bit 9 included.
  * A tile whose mask byte is 0 would get, from rsr_process_device* on b, the bytes it got from a -- in every mode and at every option that is the
  * same for both calls.
  *   Stream.  Asynchronous on `stream` with the contract of rsr_process_device (NULL = the context's stream, and the call waits).  One memset and

@@ -48,6 +48,8 @@ RSR_FMT_U8_HWC, RSR_FMT_F16_CHW, RSR_FMT_F32_CHW = 0, 1, 2
 RSR_FMT_NV12, RSR_FMT_P010 = 4, 5
 # YUV 4:2:2 surfaces: Y [h][w] then interleaved UV [h][w/2][2] -- chroma halved horizontally only; uint8, or uint16 with the code in the high bits
 RSR_FMT_NV16, RSR_FMT_P210 = 8, 9
+# planar YUV 4:4:4: the planes Y, U, V [h][w] one plane pitch apart; uint8, or uint16 with the 10-bit code in the LOW bits (yuv444p10le)
+RSR_FMT_YUV444P, RSR_FMT_YUV444P10 = 12, 13
 RSR_SEQ_MAX = 16  # frames per rsr_process_device_sequence call
 
 
@@ -361,7 +363,8 @@ class RealSR:
     def out_size_fmt(self, fmt, w, h):
         """out_size for an output in pixel format `fmt` (RSR_FMT_*) at the ratio, or pair, and tile size in force: the rule of out_size for
         the RGB formats, of out_size_yuv for NV12 / P010, and for NV16 / P210 the 4:2:2 rule -- the ratio rule, and w * nx / dx and
-        tilesize * nx / dx even; the rows carry no parity rule (rsr_out_size_fmt).  ValueError where the engine would refuse the call."""
+        tilesize * nx / dx even; the rows carry no parity rule (rsr_out_size_fmt).  YUV444P / YUV444P10: the rule of out_size, no parity at
+        all.  ValueError where the engine would refuse the call."""
         r, pair = self._ratio_or_pair()
         rx, ry = (r, r) if pair is None else pair
         ow, oh = C.c_int(0), C.c_int(0)
@@ -700,7 +703,7 @@ def selfcheck_tile(w=0, h=0):
 
 def image_bytes(fmt, w, h, c=3):
     """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*; NV12: w*h*3/2, P010: 3*w*h,
-    NV16: 2*w*h, P210: 4*w*h)."""
+    NV16: 2*w*h, P210: 4*w*h, YUV444P: 3*w*h, YUV444P10: 6*w*h)."""
     n = lib().rsr_image_bytes(int(fmt), int(w), int(h), int(c))
     if n < 0:
         raise RealSRError(int(n), lib().rsr_last_error(None).decode())

@@ -270,7 +270,7 @@ long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long
     const int rc = rsr::image_layout(fmt, w, h, c, row_pitch, plane_pitch, &row, &plane);
     if (rc != RSR_OK) return rc;
     // all pitches are positive: the last element of the last row of the last plane lies farthest from `data`
-    if (rsr::fmt_is_yuv(fmt)) // (the UV plane: h / 2 rows as long as a Y row, h of them at 4:2:2)
+    if (rsr::fmt_is_semiplanar(fmt)) // (the UV plane: h / 2 rows as long as a Y row, h of them at 4:2:2; planar 4:4:4: three planes, below)
         return plane + (long long)((rsr::fmt_is_422(fmt) ? h : h / 2) - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
     return (fmt == RSR_FMT_U8_HWC ? 0 : 2 * plane) + (long long)(h - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
 }
@@ -282,12 +282,13 @@ long long rsr_image_bytes(int fmt, int w, int h, int c)
     if (fmt == RSR_FMT_U8_HWC && (c == 3 || c == 4)) return px * c;
     if (fmt == RSR_FMT_F16_CHW && c == 3) return px * 6;
     if (fmt == RSR_FMT_F32_CHW && c == 3) return px * 12;
+    if (rsr::fmt_is_444(fmt) && c == 3) return fmt == RSR_FMT_YUV444P ? px * 3 : px * 6;
     if (rsr::fmt_is_422(fmt) && c == 3)
     {
         if (w & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:2 surface needs an even width");
         return fmt == RSR_FMT_NV16 ? px * 2 : px * 4;
     }
-    if (rsr::fmt_is_yuv(fmt) && c == 3)
+    if (rsr::fmt_is_semiplanar(fmt) && c == 3)
     {
         if ((w | h) & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
         return fmt == RSR_FMT_NV12 ? px * 3 / 2 : px * 3;
@@ -382,7 +383,8 @@ int rsr_out_size_yuv_xy(int num_x, int den_x, int num_y, int den_y, int tilesize
 
 int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
 {
-    if (out_fmt == RSR_FMT_U8_HWC || out_fmt == RSR_FMT_F16_CHW || out_fmt == RSR_FMT_F32_CHW) return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 0, ow, oh);
+    if (out_fmt == RSR_FMT_U8_HWC || out_fmt == RSR_FMT_F16_CHW || out_fmt == RSR_FMT_F32_CHW || rsr::fmt_is_444(out_fmt)) // (4:4:4: no pairs, no quads, no parity)
+        return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 0, ow, oh);
     if (!rsr::fmt_is_yuv(out_fmt)) return Engine::fail(RSR_E_ARG, "unknown pixel format");
     return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, rsr::fmt_is_422(out_fmt) ? 2 : 1, ow, oh);
 }

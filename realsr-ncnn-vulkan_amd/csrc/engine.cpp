@@ -1358,10 +1358,10 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
         if (f != RSR_FMT_U8_HWC && c != 3) return fail(RSR_E_ARG, "the planar float and the YUV formats come with c == 3 only");
     }
     if (fmt_is_422(in_fmt) && (w & 1)) return fail(RSR_E_ARG, "a YUV 4:2:2 input needs an even width");
-    if (fmt_is_yuv(in_fmt) && !fmt_is_422(in_fmt) && ((w | h) & 1)) return fail(RSR_E_ARG, "a YUV 4:2:0 input needs an even width and height");
+    if (fmt_is_semiplanar(in_fmt) && !fmt_is_422(in_fmt) && ((w | h) & 1)) return fail(RSR_E_ARG, "a YUV 4:2:0 input needs an even width and height");
     if ((fmt_is_yuv(in_fmt) && fmt_yuv_bits(in_fmt) > 8 && (reinterpret_cast<uintptr_t>(d_in) & 1)) ||
         (fmt_is_yuv(out_fmt) && fmt_yuv_bits(out_fmt) > 8 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
-        return fail(RSR_E_ARG, "P010 / P210 data is not aligned to its 16-bit samples");
+        return fail(RSR_E_ARG, "P010 / P210 / YUV444P10 data is not aligned to its 16-bit samples");
     const bool u8 = in_fmt == RSR_FMT_U8_HWC && out_fmt == RSR_FMT_U8_HWC;
     if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
     { // a small image: merged with whatever other calls hand in meanwhile (Engine::submit_merged)
@@ -1404,7 +1404,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
     });
 }
 
-// ---- YUV 4:2:0 and 4:2:2 surfaces (RSR_FMT_NV12 / RSR_FMT_P010, RSR_FMT_NV16 / RSR_FMT_P210) -------------------------------------
+// ---- YUV surfaces: 4:2:0 and 4:2:2 semi-planar (RSR_FMT_NV12 / P010, NV16 / P210), 4:4:4 planar (RSR_FMT_YUV444P / YUV444P10) ------
 // Every constant is computed in double from Kr and Kb and rounded ONCE to fp32 (include/realsr_hip.h "yuv_matrix"; tests/yuv_ref.py writes
 // the same expressions).
 bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
@@ -1433,10 +1433,10 @@ bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
 // tilesize n / d whole) the same rule reads: those three are even (yuv_out_even, what rsr_out_size_yuv states) -- per axis where the axes
 // differ: w nx / dx, tilesize nx / dx, h ny / dy and tilesize ny / dy (rsr_out_size_yuv_xy).  mu held (tilesize).
 // A 4:2:2 output is written one 2 x 1 luma pair and its (U, V) at a time: the same rule for the COLUMNS alone -- w nx / dx and tilesize nx / dx
-// even -- and none for the rows (rsr_out_size_fmt).
+// even -- and none for the rows (rsr_out_size_fmt).  A planar 4:4:4 output has no pairs and no quads, hence no rule here at all.
 int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
 {
-    if (!fmt_is_yuv(out_fmt)) return RSR_OK;
+    if (!fmt_is_semiplanar(out_fmt)) return RSR_OK;
     if (fmt_is_422(out_fmt))
     {
         if (ratio.is_box())
@@ -1512,10 +1512,10 @@ int Engine::check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const
     if (!os.divides_x(w) || !os.divides_y(h) || !os.divides_x(T) || !os.divides_y(T)) // (a YUV output: check_yuv_out then asks for even quotients as well)
     {
         if (!os.same())
-            return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratios " + os.str() + ": w and tilesize times " + std::to_string(os.nx) +
+            return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_semiplanar(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratios " + os.str() + ": w and tilesize times " + std::to_string(os.nx) +
                                        " must be multiples of " + std::to_string(os.dx) + ", h and tilesize times " + std::to_string(os.ny) + " multiples of " + std::to_string(os.dy) +
                                        " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
-        return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_yuv(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratio " + std::to_string(os.nx) + "/" + std::to_string(os.dx) + ": w, h and tilesize times " + std::to_string(os.nx) +
+        return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_semiplanar(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratio " + std::to_string(os.nx) + "/" + std::to_string(os.dx) + ": w, h and tilesize times " + std::to_string(os.nx) +
                                    " must be multiples of " + std::to_string(os.dx) + " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
     }
     return RSR_OK;
@@ -1528,7 +1528,7 @@ int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long pl
     if (fmt != RSR_FMT_U8_HWC && fmt != RSR_FMT_F16_CHW && fmt != RSR_FMT_F32_CHW && !fmt_is_yuv(fmt)) return Engine::fail(RSR_E_ARG, "unknown pixel format");
     if (fmt == RSR_FMT_U8_HWC ? (c != 3 && c != 4) : c != 3) return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
     if (fmt_is_422(fmt) && (w & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:2 surface needs an even width");
-    if (fmt_is_yuv(fmt) && !fmt_is_422(fmt) && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
+    if (fmt_is_semiplanar(fmt) && !fmt_is_422(fmt) && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
     if (row_pitch < 0 || plane_pitch < 0) return Engine::fail(RSR_E_ARG, "negative pitch");
     const long long es = BatchIO::px_bytes(fmt, c), packed = w * es;
     const long long rp = row_pitch ? row_pitch : packed;
@@ -1712,7 +1712,8 @@ int Engine::diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image*
 
 // The byte rectangles of output tile `tile` of an os.of_x(w) x os.of_y(h) image in out_fmt, from the image `src` to the image `dst`: one for
 // uint8 HWC, three for the planar formats, Y and UV for the surfaces (the UV rectangle has the byte columns of the Y rectangle and half its
-// rows; check_yuv_out has made its edges even -- a 4:2:2 surface: the tile's own rows, and only its columns are even).
+// rows; check_yuv_out has made its edges even -- a 4:2:2 surface: the tile's own rows, and only its columns are even).  A planar 4:4:4
+// surface is three planes like the planar float formats.
 static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, int tile, const ImageRef& dst, const ImageRef& src, std::vector<PropRect>& out)
 {
     uint8_t* const db = static_cast<uint8_t*>(const_cast<void*>(dst.data));
@@ -1722,11 +1723,11 @@ static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, i
     const long long es = BatchIO::px_bytes(out_fmt, c);
     const long long x0 = os.of_x((long long)xi * T), y0 = os.of_y((long long)yi * T), x1 = os.of_x(std::min((xi + 1) * T, w)), y1 = os.of_y(std::min((yi + 1) * T, h));
     const int width = int((x1 - x0) * es), rows = int(y1 - y0);
-    const int nplanes = out_fmt == RSR_FMT_U8_HWC || fmt_is_yuv(out_fmt) ? 1 : 3;
+    const int nplanes = out_fmt == RSR_FMT_U8_HWC || fmt_is_semiplanar(out_fmt) ? 1 : 3;
     for (int q = 0; q < nplanes; q++)
         out.push_back(PropRect{db + q * dpl + y0 * dp + x0 * es, sb + q * spl + y0 * sp + x0 * es, dp, sp, width, rows});
     if (fmt_is_422(out_fmt)) out.push_back(PropRect{db + dpl + y0 * dp + x0 * es, sb + spl + y0 * sp + x0 * es, dp, sp, width, rows});
-    else if (fmt_is_yuv(out_fmt)) out.push_back(PropRect{db + dpl + y0 / 2 * dp + x0 * es, sb + spl + y0 / 2 * sp + x0 * es, dp, sp, width, rows / 2});
+    else if (fmt_is_semiplanar(out_fmt)) out.push_back(PropRect{db + dpl + y0 / 2 * dp + x0 * es, sb + spl + y0 / 2 * sp + x0 * es, dp, sp, width, rows / 2});
 }
 
 int Engine::process_device_sequence(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, const rsr_image* prev_out,

@@ -225,9 +225,9 @@ struct BatchIO
         return fmt == RSR_FMT_F16_CHW ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : (fmt_is_yuv(fmt) ? (fmt_yuv_bits(fmt) + 7) / 8 : c));
     }
     static long long elem_bytes(int fmt, int c) { return fmt == RSR_FMT_U8_HWC ? 1 : px_bytes(fmt, c); } // what `data` and the pitches of a descriptor must be multiples of
-    static double image_px_bytes(int fmt, int c) // bytes of one PIXEL of a whole image: c for uint8 HWC, 3 halfs / floats, 1.5 samples of a 4:2:0 surface, 2 of a 4:2:2 one
+    static double image_px_bytes(int fmt, int c) // bytes of one PIXEL of a whole image: c for uint8 HWC, 3 halfs / floats, 1.5 samples of a 4:2:0 surface, 2 of a 4:2:2, 3 of a 4:4:4 one
     {
-        return double(px_bytes(fmt, c)) * (fmt_is_422(fmt) ? 2.0 : (fmt_is_yuv(fmt) ? 1.5 : (fmt == RSR_FMT_F16_CHW || fmt == RSR_FMT_F32_CHW ? 3.0 : 1.0)));
+        return double(px_bytes(fmt, c)) * (fmt_is_422(fmt) ? 2.0 : (fmt_is_semiplanar(fmt) ? 1.5 : (fmt == RSR_FMT_U8_HWC ? 1.0 : 3.0)));
     }
     static ImageRef packed(const void* data, int fmt, long long wi, long long hi, int c) // a tightly packed wi x hi image
     {
@@ -448,7 +448,7 @@ struct Engine
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
-    // no TTA merge / alpha channel / box reduction / YUV 4:2:0 surface needs the planar blob (dbg 8192: off)
+    // no TTA merge / alpha channel / box reduction / YUV surface needs the planar blob (dbg 8192: off)
     bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
     int check_yuv_out(int out_fmt, int w, int h, OutRatio os) const; // RSR_E_ARG when a chroma quad (4:2:0) / pair (4:2:2) of a YUV output would cross the image or a tile
     int check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const; // RSR_E_ARG when w, h or the tile size T times os is no whole number of pixels (no lock needed)

@@ -44,8 +44,18 @@ constexpr int kFmtNV12 = 4, kFmtP010 = 5;
 // horizontally only -- the UV plane is [h][w/2][2], one UV row per Y row.  w is even; h is any.
 constexpr int kFmtNV16 = 8, kFmtP210 = 9;
 constexpr bool fmt_is_422(int fmt) { return fmt == kFmtNV16 || fmt == kFmtP210; }
-constexpr bool fmt_is_yuv(int fmt) { return fmt == kFmtNV12 || fmt == kFmtP010 || fmt_is_422(fmt); }
-constexpr int fmt_yuv_bits(int fmt) { return fmt == kFmtP010 || fmt == kFmtP210 ? 10 : 8; } // of a YUV format: the code's bits (10: uint16 words, code << 6)
+// Planar YUV 4:4:4, what screen recordings, mezzanine masters and software video frameworks hold (RSR_FMT_YUV444P / RSR_FMT_YUV444P10,
+// yuv444p / yuv444p10le): three full planes Y, U, V [h][w] one plane pitch apart -- the LAYOUT of the planar float formats with a YUV
+// colour model.  uint8 codes, or uint16 words that hold a 10-bit code in their LOW bits.  No pairs, no quads: w and h are any.
+constexpr int kFmtYUV444P = 12, kFmtYUV444P10 = 13;
+constexpr bool fmt_is_444(int fmt) { return fmt == kFmtYUV444P || fmt == kFmtYUV444P10; }
+// Two questions that had one answer until 4:4:4 came.  fmt_is_semiplanar: is it a Y plane followed by ONE plane of interleaved, subsampled
+// (U, V) pairs -- the geometry behind the pair / quad units, the parity rules and the second rectangle of the diff and of the sequence copy?
+// fmt_is_yuv: does it hold Y'CbCr codes -- the colour model: YuvCoef, the decode in front of the network, the encode behind conv_last?
+constexpr bool fmt_is_semiplanar(int fmt) { return fmt == kFmtNV12 || fmt == kFmtP010 || fmt_is_422(fmt); }
+constexpr bool fmt_is_yuv(int fmt) { return fmt_is_semiplanar(fmt) || fmt_is_444(fmt); }
+// of a YUV format: the code's bits (10: uint16 words -- code << 6 in a semi-planar surface, the plain code in a planar 4:4:4 one)
+constexpr int fmt_yuv_bits(int fmt) { return fmt == kFmtP010 || fmt == kFmtP210 || fmt == kFmtYUV444P10 ? 10 : 8; }
 // Every image is addressed through its own ROW PITCH and (planar formats) PLANE PITCH, both in BYTES (rsr_image of the C ABI): a crop of
 // a larger frame, a window of a canvas.  A uint8 pitch need not be a multiple of the pixel size and a base pointer is aligned to the
 // element only, so the image accesses are element-sized (the LDS-staged pre / post kernels, which move dwords, align by themselves or
@@ -176,7 +186,8 @@ struct PreArgs
 {
     const uint8_t* imgs[kMaxMerge]; // HWC u8, one per image of the batch (ws[i] x hs[i] x c); BaseTile::img selects
     int fmt;                        // kFmtU8, or kFmtF16 / kFmtF32: the images are planar [3][hs[i]][ws[i]] of that type (c == 3),
-                                    // or a YUV surface (fmt_is_yuv): Y at imgs[i], UV plane[i] bytes behind it, decoded with `yuv`; bgr does not apply
+                                    // or a YUV surface (fmt_is_yuv): Y at imgs[i], UV plane[i] bytes behind it (planar 4:4:4: U, then V another
+                                    // plane[i] behind), decoded with `yuv`; bgr does not apply
     int ws[kMaxMerge], hs[kMaxMerge];
     int pitch[kMaxMerge];           // bytes from one row of image i to the next (>= ws[i] * pixel size) ...
     long long plane[kMaxMerge];     // ... and, planar formats, from one plane to the next
@@ -207,7 +218,8 @@ struct PostArgs
     int crop;   // prepadding*scale
     uint8_t* outs[kMaxMerge]; // HWC u8 (4w x 4h x c), one per image of the batch
     int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][4h][4w] of that type (c == 3; see ConvArgs::out_fmt),
-                              // or a YUV surface (fmt_is_yuv): Y at outs[i], UV out_plane[i] bytes behind it (postproc_tiles_yuv; box 0 / 1, 2 and 4 alike)
+                              // or a YUV surface (fmt_is_yuv): Y at outs[i], UV out_plane[i] bytes behind it (postproc_tiles_yuv; box 0 / 1, 2 and 4 alike;
+                              // planar 4:4:4: the planes Y, U, V out_plane[i] apart, postproc_tiles_yuv444)
     long long out_plane[kMaxMerge]; // planar formats: bytes from one plane of `outs[i]` to the next
     int out_pitch[kMaxMerge]; // row pitches of the outs in bytes
     int in_pitch[kMaxMerge];  // ... and those of the source images
@@ -218,6 +230,8 @@ struct PostArgs
     int tilesize;
     int bgr;
     int variant; // 0 default (LDS-staged under TTA, else one thread per pixel), 1 per-pixel (engine dbg 32768), 2 LDS-staged (dbg 65536)
+                 // (a planar 4:4:4 surface: 1 one pixel per thread, 2 two neighbouring pixels, 0 two at out_scale 4 and one elsewhere --
+                 // with_pixels_per_thread)
     // Box-reduced output (engine option "out_scale"): 0 / 1 = the x4 image as above; 2 / 4 = every K x K box of x4 pixels, each clamped
     // to [0, 1] first, leaves as ONE pixel, its fp32 mean (postproc_tiles_box): the outs are (4 / K)w x (4 / K)h.  Everything above stays in
     // x4 units (BaseTile::out_*, out_row0, crop: all multiples of 4); the kernel divides by K.

@@ -8,6 +8,7 @@
 //   postproc_tiles_area    the image area-averaged to any other ratio, or to a ratio per axis (rsr_set_out_ratio, rsr_set_out_ratio_xy)
 //   preproc_tiles<., true> an NV12 / P010 (4:2:0) or NV16 / P210 (4:2:2) surface as the source (YUV -> RGB inside the kernel)
 //   postproc_tiles_yuv[_area]   such a surface as the destination, at out_scale 4 / 2 / 1 [at any other ratio]
+//   preproc_tiles<., true, 0, kVs444> / postproc_tiles_yuv444[_area]   a planar 4:4:4 surface (kFmtYUV444P / kFmtYUV444P10) as the source / destination
 //   *_shader               the same arithmetic in the shaders' own memory layout (parity tests; independent of everything below)
 //
 // Every rule the header (include/realsr_hip.h) fixes bit for bit is written ONCE, as a __device__ __forceinline__ function the kernels share:
@@ -17,6 +18,8 @@
 //   alpha_bicubic          the bicubic x4 alpha value                                               every post kernel that writes RGBA
 //   area_sum / area_pixel  the area-average loop nest over a tap source                            postproc_tiles_area, postproc_tiles_yuv_area
 //   yuv_quad               a luma quad and its (U, V) pair(s) from a source of pixels d              postproc_tiles_yuv, postproc_tiles_yuv_area
+//   yuv_pixels             one or two pixels' Y, U and V codes from the same sources (4:4:4)        postproc_tiles_yuv444, postproc_tiles_yuv444_area
+//   yuv_sample             the code of one sample of a surface: word >> 6, or word & 1023 (4:4:4)  yuv_decode
 //
 // The 351 convolutions live in conv_flow.hip (conv3x3_flow).  Written for gfx950 only.
 #include "kernels.h"
@@ -63,6 +66,20 @@ __device__ __forceinline__ float sub_rn(float a, float b)
 {
 #pragma clang fp contract(off)
     return a - b;
+}
+
+// The vertical-chroma-shift argument VS of the YUV templates below: 1 = 4:2:0, 0 = 4:2:2, kVs444 = a planar 4:4:4 surface, which has no
+// chroma shift on either axis and a plane of its own per component.
+constexpr int kVs444 = -1;
+
+// The code of the sample at p as a float: a byte; or a 16-bit word that holds its 10-bit code in the HIGH bits (P010 / P210: word >> 6) or,
+// LOW = true, in the low ones (yuv444p10le: word & 1023 -- whatever a producer left above bit 9 is not part of the sample).
+template <typename SRC, bool LOW>
+__device__ __forceinline__ float yuv_sample(const uint8_t* p)
+{
+    if constexpr (sizeof(SRC) == 1) return (float)*p;
+    else if constexpr (LOW) return (float)(*reinterpret_cast<const unsigned short*>(p) & 1023u);
+    else return (float)(*reinterpret_cast<const unsigned short*>(p) >> 6);
 }
 
 // The (U, V) pair of chroma sample cx of a UV row: ONE 2-byte (NV12) or 4-byte (P010) load where the address allows it -- an NV12 surface
@@ -138,11 +155,13 @@ template <typename SRC, int SITE = 0, int VS = 1>
 __device__ __forceinline__ void yuv_decode(const uint8_t* img, int pitch, long long plane, int x, int y, int w, int h, const YuvCoef& k, float (&rgb)[3])
 {
     const uint8_t* yp = img + (long long)y * pitch + (long long)x * (int)sizeof(SRC);
-    float Y;
-    if constexpr (sizeof(SRC) == 1) Y = (float)*yp;
-    else Y = (float)(*reinterpret_cast<const unsigned short*>(yp) >> 6);
+    const float Y = yuv_sample<SRC, VS == kVs444>(yp);
     float U, V;
-    if constexpr (SITE != 0) yuv_decode_cos<SRC, SITE, VS>(img, pitch, plane, x, y, w, h, U, V);
+    if constexpr (VS == kVs444)
+    { // planar 4:4:4 (include/realsr_hip.h "YUV 4:4:4"): the pixel's own sample of planes 1 and 2 -- no chroma filter, no siting
+        U = yuv_sample<SRC, true>(yp + plane), V = yuv_sample<SRC, true>(yp + 2 * plane);
+    }
+    else if constexpr (SITE != 0) yuv_decode_cos<SRC, SITE, VS>(img, pitch, plane, x, y, w, h, U, V);
     else if constexpr (VS == 0)
     { // 4:2:2, centre: the horizontal rule on the pixel's own chroma row
         const int cxn = x >> 1, cxf = min(max(cxn + ((x & 1) ? 1 : -1), 0), (w >> 1) - 1);
@@ -204,6 +223,8 @@ __device__ __forceinline__ void tta_dest(int k, int gx, int gy, int tw, int th, 
 // (x, y) -- reflected first, like every other source -- is decoded as include/realsr_hip.h ("yuv_matrix") defines, bit for bit: yuv_decode;
 // SITE is the chroma siting (PreArgs::siting: a kernel per siting, the centre-sited one is what it was before the others existed).
 // VS = 0: a 4:2:2 surface (kFmtNV16 / kFmtP210), SRC its sample type likewise; the chroma row of a pixel is its own (yuv_decode).
+// VS = kVs444: a planar 4:4:4 surface (kFmtYUV444P / kFmtYUV444P10; a uint16_t holds its code in the LOW 10 bits): three plane reads at
+// the pixel's own (x, y), each contiguous over the lanes of a wave like those of the planar float sources; SITE is 0.
 template <typename SRC, bool YUV = false, int SITE = 0, int VS = 1>
 __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
 {
@@ -382,7 +403,7 @@ static void with_siting(int siting, F f)
     else f(std::integral_constant<int, 0>{});
 }
 // f(siting, vertical chroma shift VS) of a YUV surface: VS 1 = 4:2:0 with its three sitings; VS 0 = 4:2:2, left or centre -- top-left has no
-// vertical meaning there and IS left (the same kernels, the same bytes).
+// vertical meaning there and IS left (the same kernels, the same bytes).  (Semi-planar surfaces: a planar 4:4:4 one has nothing to site.)
 template <typename F>
 static void with_chroma(int fmt, int siting, F f)
 {
@@ -402,7 +423,9 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
     if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8) // (the staged kernel knows uint8 sources only)
     {
         const dim3 grid((max_tw + 31) / 32, (max_th + 7) / 8, a.ntiles), block(256);
-        if (fmt_is_yuv(a.fmt))
+        if (fmt_is_444(a.fmt)) // nothing is sited: one kernel per sample type whatever "yuv_siting" says
+            with_sample_type(a.fmt, [&](auto src) { hipLaunchKernelGGL((preproc_tiles<decltype(src), true, 0, kVs444>), grid, block, 0, st, a); });
+        else if (fmt_is_yuv(a.fmt))
             with_sample_type(a.fmt, [&](auto src) {
                 with_chroma(a.fmt, a.siting, [&](auto site, auto vs) {
                     hipLaunchKernelGGL((preproc_tiles<decltype(src), true, decltype(site)::value, decltype(vs)::value>), grid, block, 0, st, a);
@@ -941,12 +964,13 @@ static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipS
 }
 
 // ---- YUV 4:2:0 and 4:2:2 output (PostArgs::out_fmt kFmtNV12 / kFmtP010, kFmtNV16 / kFmtP210) ------------------------------------
-// code = floor(v * scale + add) clamped to [0, maxcode] (add = offset + 0.5f), as the sample type stores it: P010 keeps it in the high bits
-template <typename TO>
+// code = floor(v * scale + add) clamped to [0, maxcode] (add = offset + 0.5f), as the sample type stores it: P010 / P210 keep it in the
+// high bits; LOW = true (planar 4:4:4) stores the code itself, the six bits above it 0
+template <typename TO, bool LOW = false>
 __device__ __forceinline__ unsigned yuv_code(float v, float scale, float add, float maxcode)
 {
     const float q = fminf(fmaxf(floorf(add_rn(mul_rn(v, scale), add)), 0.f), maxcode);
-    return sizeof(TO) == 1 ? (unsigned)q : (unsigned)q << 6;
+    return sizeof(TO) == 1 || LOW ? (unsigned)q : (unsigned)q << 6;
 }
 
 // Two neighbouring samples of a surface row (lo in front) as ONE store of twice the sample size where the address allows it.
@@ -1209,6 +1233,133 @@ static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipSt
     });
 }
 
+// ---- planar YUV 4:4:4 output (PostArgs::out_fmt kFmtYUV444P / kFmtYUV444P10; include/realsr_hip.h "YUV 4:4:4") -----------------------------
+// NP (1 or 2) neighbouring pixels of ONE output row, the first at column gx * NP of tile t's rectangle, row gy: the per-pixel sibling of
+// yuv_quad, behind the same sources of RGB values d (QuadBox / QuadArea, whose origin is the first of these pixels: d = src.at(b, i, 0)).
+// This is the 4:2:0 rule with m = d: Y' = (kr R + kg G) + kb B, accumulated across the channel loop as in yuv_quad (one channel's gather
+// at a time: the three never hold registers together), Cb = (B - Y') * icb, Cr = (R - Y') * icr; nothing is filtered, so no siting and no
+// tile-first clamp exist.  Three plane stores finish it, the planes out_plane apart; a 10-bit code is stored as it is (the high six bits
+// 0).  n = how many of the NP pixels exist: a rectangle may have an odd width, and nothing of a pixel beyond it is gathered or stored.
+template <typename TO, int NP, typename SRC, typename TP>
+__device__ __forceinline__ void yuv_pixels(const PostArgs& a, const BaseTile& t, int im, int gx, int gy, const SRC& src, const TP* b0, long long cstep, int n)
+{
+    const YuvCoef& k = a.yuv;
+    float y[NP], r[NP], bl[NP];
+#pragma unroll
+    for (int i = 0; i < NP; i++) y[i] = r[i] = bl[i] = 0.f;
+#pragma unroll 1
+    for (int q = 0; q < 3; q++)
+    {
+        const TP* b = b0 + q * cstep;
+        const float kq = q == 0 ? k.kr : (q == 1 ? k.kg : k.kb);
+#pragma unroll
+        for (int i = 0; i < NP; i++)
+        {
+            const float d = src.at(b, i < n ? i : 0, 0); // (a pixel beyond the rectangle: the first one again, carried along, never stored)
+            y[i] = add_rn(y[i], mul_rn(kq, d));
+            if (q == 0) r[i] = d;
+            if (q == 2) bl[i] = d;
+        }
+    }
+    unsigned cy[NP], cu[NP], cv[NP];
+#pragma unroll
+    for (int i = 0; i < NP; i++)
+    {
+        cy[i] = yuv_code<TO, true>(y[i], k.yscale, k.yadd, k.maxcode);
+        cu[i] = yuv_code<TO, true>(mul_rn(sub_rn(bl[i], y[i]), k.icb), k.cscale, k.cadd, k.maxcode);
+        cv[i] = yuv_code<TO, true>(mul_rn(sub_rn(r[i], y[i]), k.icr), k.cscale, k.cadd, k.maxcode);
+    }
+    const int X = src.out_x(t.out_x) + NP * gx, Y = src.out_y(t.out_y - a.out_row0) + gy;
+    uint8_t* const o = a.outs[im] + Y * (long long)a.out_pitch[im] + (long long)X * (int)sizeof(TO);
+    const long long plane = a.out_plane[im];
+    if constexpr (NP == 2)
+    {
+        if (n == 2)
+        { // (store_pair falls back to two sample stores where the address is odd: a window starts at any byte)
+            store_pair<TO>(o, cy[0], cy[1]);
+            store_pair<TO>(o + plane, cu[0], cu[1]);
+            store_pair<TO>(o + 2 * plane, cv[0], cv[1]);
+            return;
+        }
+    }
+    *reinterpret_cast<TO*>(o) = (TO)cy[0];
+    *reinterpret_cast<TO*>(o + plane) = (TO)cu[0];
+    *reinterpret_cast<TO*>(o + 2 * plane) = (TO)cv[0];
+}
+
+// The 4:4:4 sibling of postproc_tiles_yuv: one thread makes NP pixels of one row (yuv_pixels over QuadBox) at the context's out_scale OS (4,
+// 2 or 1).  The rectangle of a tile is out_w / K x out_h / K output pixels, of any parity.  Lanes run along x: every plane store of a wave
+// is one contiguous run.  TP: element type of the blob; TO: uint8_t (YUV444P) or uint16_t (YUV444P10).
+template <typename TP, typename TO, int OS, int NP>
+__global__ __launch_bounds__(256) void postproc_tiles_yuv444(const PostArgs a)
+{
+    constexpr int K = 4 / OS; // x4 pixels per output pixel, along an axis
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int ow = t.out_w / K, oh = t.out_h / K;
+    if (NP * gx >= ow || gy >= oh) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const QuadBox<TP, OS> src{a.slot_stride / (long long)sizeof(TP), w, h, NP * gx * K + a.crop, gy * K + a.crop, a.tta};
+    yuv_pixels<TO, NP>(a, t, im, gx, gy, src, b0, (long long)w * h, min(NP, ow - NP * gx));
+}
+
+// ... and of postproc_tiles_yuv_area, for every other ratio or pair: yuv_pixels over QuadArea.  The engine admits the call where the ratio
+// rule holds (w, h and tilesize times the ratios whole); the quotients may be odd.
+template <typename TP, typename TO, int NP>
+__global__ __launch_bounds__(256) void postproc_tiles_yuv444_area(const PostArgs a)
+{
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int nx = a.num, Lx = 4 * a.den, ny = a.num_y, Ly = 4 * a.den_y;
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int ow = t.out_w * nx / Lx, oh = t.out_h * ny / Ly;
+    if (NP * gx >= ow || gy >= oh) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const QuadArea<TP> src{a.slot_stride / (long long)sizeof(TP), w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, NP * gx, gy};
+    yuv_pixels<TO, NP>(a, t, im, gx, gy, src, b0, (long long)w * h, min(NP, ow - NP * gx));
+}
+
+// f(integral_constant NP): pixels per thread of the 4:4:4 kernels.  Chosen by the compiler's resource report and by measurement (DESIGN.md
+// 4.8, profiles/yuv444.txt): two at out_scale 4 -- 50 VGPRs against 42 at the same occupancy 8, stores twice as wide, post_ms 0.19 - 0.21
+// against 0.22 - 0.23 ms on a 1080p frame -- and one everywhere else: a second pixel costs out_scale 2 a third of its occupancy (116
+// VGPRs against 80; 0.13 against 0.08 ms), takes out_scale 1 to 256 VGPRs and occupancy 1 (140 and 3) and the area kernel from
+// occupancy 8 to 6.  PostArgs::variant forces a shape (tests, A/B): 1 = one pixel, 2 = two.
+template <typename F>
+static void with_pixels_per_thread(const PostArgs& a, bool x4, F f)
+{
+    if (a.variant == 2 || (a.variant == 0 && x4)) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+}
+
+template <typename TP, typename TO>
+static void launch_postproc_yuv444_area(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    const int ow = max_ow * a.num / (4 * a.den), oh = max_oh * a.num_y / (4 * a.den_y); // output pixels of the largest tile rectangle
+    with_pixels_per_thread(a, false, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        const dim3 grid(((ow + NP - 1) / NP + 63) / 64, (oh + 3) / 4, a.ntiles), block(256);
+        hipLaunchKernelGGL((postproc_tiles_yuv444_area<TP, TO, NP>), grid, block, 0, st, a);
+    });
+}
+
+template <typename TP, typename TO>
+static void launch_postproc_yuv444(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    const int K = a.box > 1 ? a.box : 1, ow = max_ow / K, oh = max_oh / K;
+    with_pixels_per_thread(a, K == 1, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        const dim3 grid(((ow + NP - 1) / NP + 63) / 64, (oh + 3) / 4, a.ntiles), block(256);
+        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 1, NP>), grid, block, 0, st, a);
+        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 2, NP>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 4, NP>), grid, block, 0, st, a);
+    });
+}
+
 // A rational scale other than 4 / 2 / 1 on both axes (rsr_set_out_ratio, rsr_set_out_ratio_xy)?
 static bool generic_ratio(const PostArgs& a)
 {
@@ -1221,6 +1372,15 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
     if (a.ntiles <= 0) return;
     with_blob_type(a, [&](auto tp) {
         using TP = decltype(tp);
+        if (fmt_is_444(a.out_fmt))
+        { // a planar 4:4:4 surface: one thread per pixel (or two), at every out_scale or ratio, with and without TTA
+            with_sample_type(a.out_fmt, [&](auto to) {
+                using TO = decltype(to);
+                if (generic_ratio(a)) launch_postproc_yuv444_area<TP, TO>(a, max_ow, max_oh, st);
+                else launch_postproc_yuv444<TP, TO>(a, max_ow, max_oh, st);
+            });
+            return;
+        }
         if (fmt_is_yuv(a.out_fmt))
         { // a 4:2:0 or 4:2:2 surface: one thread per luma quad, at every out_scale or ratio, with and without TTA
             with_sample_type(a.out_fmt, [&](auto to) {
@@ -1453,7 +1613,7 @@ __global__ __launch_bounds__(256) void diff_tiles(const DiffArgs a)
     const int es = a.fmt == kFmtF32 ? 4 : (a.fmt == kFmtF16 ? 2 : (a.fmt == kFmtU8 ? a.c : (fmt_yuv_bits(a.fmt) + 7) / 8)); // (a YUV surface: of one sample)
     int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
     long long off_a = 0, off_b = 0;
-    if (fmt_is_yuv(a.fmt))
+    if (fmt_is_semiplanar(a.fmt)) // (a planar 4:4:4 surface: three planes like the planar float formats, below)
     {
         if (rect == 1)
         { // the (U, V) pairs the decode of this rectangle reads: one chroma sample beyond its own, at every siting
@@ -1484,7 +1644,7 @@ hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st)
     const hipError_t e = hipMemsetAsync(a.mask, 0, size_t(ntiles), st); // every byte is written: the kernel only ever stores ones
     if (e != hipSuccess) return e;
     const long long padded = (long long)a.T + 2 * a.P; // rows of the tallest rectangle
-    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_yuv(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
+    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_semiplanar(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
     const int chunks = (rows + kDiffRows - 1) / kDiffRows;
     const dim3 grid(ntiles, chunks < 1024 ? chunks : 1024, nrect), block(256); // (taller rectangles: the kernel strides over the chunks)
     hipLaunchKernelGGL(diff_tiles, grid, block, 0, st, a);
@@ -1498,7 +1658,7 @@ hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st)
 // for that pair: the same rectangles, the same compared bytes (include/realsr_hip.h rsr_diff_tiles), the same choice of access width.
 __global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
 {
-    const int nrect = fmt_is_yuv(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
+    const int nrect = fmt_is_semiplanar(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
     const int pair = blockIdx.z / nrect, rect = blockIdx.z - pair * nrect;
     const int tile = blockIdx.x, yi = tile / a.nx, xi = tile - yi * a.nx;
     const DiffPair& p = a.pair[pair];
@@ -1513,7 +1673,7 @@ __global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
     const int es = a.fmt == kFmtF32 ? 4 : (a.fmt == kFmtF16 ? 2 : (a.fmt == kFmtU8 ? a.c : (fmt_yuv_bits(a.fmt) + 7) / 8)); // (a YUV surface: of one sample)
     int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
     long long off_a = 0, off_b = 0;
-    if (fmt_is_yuv(a.fmt))
+    if (fmt_is_semiplanar(a.fmt)) // (a planar 4:4:4 surface: three planes like the planar float formats, below)
     {
         if (rect == 1)
         { // the (U, V) pairs the decode of this rectangle reads (diff_tiles)
@@ -1543,7 +1703,7 @@ hipError_t launch_diff_tiles_seq(const DiffSeqArgs& a, hipStream_t st)
     const hipError_t e = hipMemsetAsync(a.mask, 0, size_t(ntiles) * size_t(a.n), st); // every byte is written: the kernel only ever stores ones
     if (e != hipSuccess) return e;
     const long long padded = (long long)a.T + 2 * a.P;
-    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_yuv(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
+    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_semiplanar(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
     const int chunks = (rows + kDiffRows - 1) / kDiffRows;
     const dim3 grid(ntiles, chunks < 1024 ? chunks : 1024, a.n * nrect), block(256);
     hipLaunchKernelGGL(diff_tiles_seq, grid, block, 0, st, a);

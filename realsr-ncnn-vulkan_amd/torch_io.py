@@ -5,6 +5,7 @@
     y = torch_io.upscale(sr, x)        # x: (3, H, W) or (N, 3, H, W) float16 / float32 in [0, 1] on cuda:0  ->  (.., 3, 4H, 4W)
     torch_io.upscale(sr, frame[..., y0:y1, x0:x1], out=canvas[..., 4 * y0:4 * y1, 4 * x0:4 * x1])   # views in, a window out: no copies
 
+    yuv444 = torch_io.upscale_yuv(sr, planes, chroma=444)   # a (3, H, W) uint8 / int16 yuv444p / yuv444p10le frame -> (3, H', W'), any H and W
     nv12 = torch_io.upscale_yuv(sr, surface)   # a decoder's (3H/2, W) uint8 NV12 or 16-bit P010 surface -> the same layout at out_scale
     sr.tilesize = 200; sr.out_ratio = Fraction(3, 2); nv12_1080 = torch_io.upscale_yuv(sr, nv12_720)   # ... or at a ratio: 720p -> 1080p
     sr.tilesize = 192; sr.out_ratio_xy = (Fraction(8, 3), Fraction(9, 4)); nv12_1080 = torch_io.upscale_yuv(sr, nv12_dvd)   # ... or one per axis: 720 x 480 -> 1920 x 1080
@@ -24,7 +25,8 @@ import contextlib
 import numpy as np
 import torch
 
-from . import RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_NV16, RSR_FMT_P010, RSR_FMT_P210, RSR_FMT_U8_HWC
+from . import (RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_NV16, RSR_FMT_P010, RSR_FMT_P210, RSR_FMT_U8_HWC, RSR_FMT_YUV444P,
+               RSR_FMT_YUV444P10)
 
 _FMT = {torch.float16: RSR_FMT_F16_CHW, torch.float32: RSR_FMT_F32_CHW}
 
@@ -150,6 +152,8 @@ if hasattr(torch, "uint16"):
 # ... and 4:2:2 surfaces (keyword chroma=422): what broadcast and archive codecs hold -- a UV row per Y row
 _YUV422 = {t: {RSR_FMT_NV12: RSR_FMT_NV16, RSR_FMT_P010: RSR_FMT_P210}[f] for t, f in _YUV.items()}
 _YUV_FMTS = (RSR_FMT_NV12, RSR_FMT_P010, RSR_FMT_NV16, RSR_FMT_P210)
+# ... and planar 4:4:4 (keyword chroma=444): three full planes (3, H, W); 16-bit words hold the 10-bit code in their LOW bits (yuv444p10le)
+_YUV444 = {t: {RSR_FMT_NV12: RSR_FMT_YUV444P, RSR_FMT_P010: RSR_FMT_YUV444P10}[f] for t, f in _YUV.items()}
 
 
 def _yuv_fmt(dtype, chroma):
@@ -157,8 +161,89 @@ def _yuv_fmt(dtype, chroma):
 
 
 def _check_chroma(chroma, who):
-    if chroma not in (420, 422):
-        raise ValueError("%s: chroma must be 420 or 422 (YUV 4:2:0 / 4:2:2 surfaces), not %r" % (who, chroma))
+    if chroma not in (420, 422, 444):
+        raise ValueError("%s: chroma must be 420, 422 or 444 (YUV 4:2:0 / 4:2:2 surfaces, planar 4:4:4), not %r" % (who, chroma))
+
+
+def _planes444(sr, s, what):
+    """The three (H, W) plane views Y, U, V of a planar 4:4:4 image -- a (3, H, W) tensor, or a (y, u, v) triple of 2-D views -- validated;
+    ValueError before anything is launched."""
+    if isinstance(s, (tuple, list)):
+        if len(s) != 3 or not all(isinstance(t, torch.Tensor) and t.dim() == 2 for t in s):
+            raise ValueError("upscale_yuv: %s must be a (3, H, W) tensor or a (y, u, v) triple of (H, W) tensors (planar YUV 4:4:4)" % what)
+        planes = list(s)
+    else:
+        if not isinstance(s, torch.Tensor) or s.dim() != 3 or s.shape[0] != 3:
+            raise ValueError("upscale_yuv: %s must be a (3, H, W) tensor: the planes Y, U, V (planar YUV 4:4:4)" % what)
+        planes = [s[0], s[1], s[2]]
+    y = planes[0]
+    if any(t.dtype != y.dtype or t.device != y.device or t.shape != y.shape for t in planes):
+        raise ValueError("upscale_yuv: the planes of %s must have one shape and dtype, on one device" % what)
+    if y.dtype not in _YUV444:
+        raise ValueError("upscale_yuv: dtype %s is not supported (uint8 = yuv444p; uint16 / int16 = yuv444p10le)" % y.dtype)
+    if y.device.type != "cuda" or y.device.index != sr.gpuid:
+        raise ValueError("upscale_yuv: %s is on %s, the context runs on cuda:%d" % (what, y.device, sr.gpuid))
+    if y.shape[0] < 1 or y.shape[1] < 1:
+        raise ValueError("upscale_yuv: empty image %s" % (tuple(y.shape),))
+    return planes
+
+
+def _describe444(planes):
+    """(data_ptr, row_pitch, plane_pitch) in bytes of the image behind three plane views, or None when no rsr_image describes it: a step
+    along W, planes with different row strides, or planes that are not equally spaced upwards in memory."""
+    y = planes[0]
+    es, (h, w) = y.element_size(), y.shape
+    if any((w > 1 and t.stride(1) != 1) or t.data_ptr() % es for t in planes):
+        return None
+    row = y.stride(0) if h > 1 else w
+    if row < w or (h > 1 and any(t.stride(0) != row for t in planes)):
+        return None
+    plane = planes[1].data_ptr() - y.data_ptr()
+    if plane <= 0 or planes[2].data_ptr() - planes[1].data_ptr() != plane:
+        return None
+    return y.data_ptr(), row * es, plane
+
+
+def _desc444(sr, s, what):
+    """(fmt, w, h, descriptor) of a planar 4:4:4 image; ValueError where it is none or no rsr_image describes it -- a 4:4:4 view is taken
+    in place or not at all."""
+    planes = _planes444(sr, s, what)
+    d = _describe444(planes)
+    if d is None:
+        raise ValueError("upscale_yuv: %s is not addressable by one row pitch and one plane pitch (stride 1 along W, one row stride for all "
+                         "three planes, the planes equally spaced)" % what)
+    return _YUV444[planes[0].dtype], planes[0].shape[1], planes[0].shape[0], d
+
+
+def _out_size_yuv444(sr, fmt, w, h, who):
+    """(ow, oh) of the 4:4:4 output for a w x h image: sr.out_size_fmt -- the rule of the RGB outputs, no parity anywhere."""
+    if not hasattr(sr, "out_size_fmt"):
+        raise ValueError("%s: this context writes no YUV 4:4:4 images (no out_size_fmt)" % who)
+    return sr.out_size_fmt(fmt, w, h)
+
+
+def _new444(like, ow, oh):
+    """An uninitialised ow x oh 4:4:4 result of the kind of `like`: a (3, oh, ow) tensor, or the (y, u, v) views of one."""
+    first = like[0] if isinstance(like, (tuple, list)) else like
+    o = first.new_empty((3, oh, ow))
+    return (o[0], o[1], o[2]) if isinstance(like, (tuple, list)) else o
+
+
+def _upscale_yuv444(sr, surface, out):
+    fmt, w, h, din = _desc444(sr, surface, "surface")
+    ow, oh = _out_size_yuv444(sr, fmt, w, h, "upscale_yuv")
+    first = surface[0] if isinstance(surface, (tuple, list)) else surface
+    if out is not None:
+        if isinstance(out, (tuple, list)) != isinstance(surface, (tuple, list)):
+            raise ValueError("upscale_yuv: out must be a %s like the input" % ("(y, u, v) triple" if isinstance(surface, (tuple, list)) else "(3, H, W) tensor"))
+        ofmt, w2, h2, dout = _desc444(sr, out, "out")
+        if (ofmt, w2, h2) != (fmt, ow, oh):
+            raise ValueError("upscale_yuv: out must be a %s YUV 4:4:4 image of %d x %d on %s" % (first.dtype, ow, oh, first.device))
+    else:
+        out = _new444(surface, ow, oh)
+        dout = _desc444(sr, out, "out")[3]
+    _on_current_stream(first.device, lambda st: sr.process_device_batch([din], fmt, w, h, 3, [dout], fmt, stream=st))
+    return out
 
 
 def _planes422(sr, s, what):
@@ -272,8 +357,15 @@ def upscale_yuv(sr, surface, out=None, chroma=420):
     chroma=422: a YUV 4:2:2 surface (RSR_FMT_NV16 / RSR_FMT_P210: chroma halved horizontally only, what DVCPRO-HD, ProRes 422, XDCAM HD422
     hold) -- a (2H, W) tensor, H rows of Y and H rows of interleaved UV, or a (y, uv) pair with uv (H, W); uint8 is NV16, uint16 / int16
     P210.  Any H >= 1 is taken.  The result has the same layout, sized by sr.out_size_fmt: ValueError with "YUV" in it where the engine would
-    refuse (w or tilesize times the x ratio odd)."""
+    refuse (w or tilesize times the x ratio odd).
+    chroma=444: planar YUV 4:4:4 (RSR_FMT_YUV444P / RSR_FMT_YUV444P10: what screen recordings, ProRes 4444 and software video frameworks
+    hold) -- a (3, H, W) tensor of the planes Y, U, V, uint8 or uint16 / int16 with the 10-bit code in the LOW bits (yuv444p10le), or a
+    (y, u, v) triple of (H, W) views.  Any H and W >= 1, odd ones included: no parity rule exists.  The view needs stride 1 along W, one row
+    stride for all planes and equally spaced planes -- a crop, a window of a canvas -- and is then taken without a copy; ValueError
+    otherwise.  The result is (3, H', W') of the same dtype (or a triple), sized by sr.out_size_fmt; out= takes a window."""
     _check_chroma(chroma, "upscale_yuv")
+    if chroma == 444:
+        return _upscale_yuv444(sr, surface, out)
     pair = isinstance(surface, (tuple, list))
     y, uv = _planes(sr, surface, "surface", chroma)
     fmt, (h, w) = _yuv_fmt(y.dtype, chroma), y.shape
@@ -311,7 +403,10 @@ def _pinned_u8(n):
 
 def _image_desc(sr, t, what, chroma=420):
     """(fmt, w, h, c, descriptor or None) of ONE image as upscale (a single uint8 / float image) or upscale_yuv (a surface or a (y, uv)
-    pair; chroma: its subsampling) takes it; ValueError before anything is launched."""
+    pair; chroma: its subsampling) takes it; ValueError before anything is launched.  chroma=444: every image is a planar 4:4:4 one."""
+    if chroma == 444:
+        fmt, w, h, d = _desc444(sr, t, what)
+        return fmt, w, h, 3, d
     if isinstance(t, (tuple, list)) or (isinstance(t, torch.Tensor) and t.dim() == 2):
         y, uv = _planes(sr, t, what, chroma)
         return _yuv_fmt(y.dtype, chroma), y.shape[1], y.shape[0], 3, _describe_yuv(y, uv)
@@ -357,13 +452,16 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None, chroma=420):
     Steps, all on torch.cuda.current_stream(): the diff; a copy of the mask into pinned memory; ONE stream synchronisation -- the grid of
     every launch depends on the mask, so the host has to see it: this is the only host wait, and it is what the skipped tiles are paid
     with --; the masked call.
-    chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them."""
+    chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them.  chroma=444: x, prev_x, prev_y and out are
+    planar 4:4:4 images as upscale_yuv(..., chroma=444) takes them."""
     _check_chroma(chroma, "upscale_delta")
     fmt, w, h, c, _ = _image_desc(sr, x, "x", chroma)
     if prev_x is not None and not _same_layout(x, prev_x):
         raise ValueError("upscale_delta: prev_x must have x's layout, shape, dtype and device")
     yuv = fmt in _YUV_FMTS
-    if yuv and chroma == 422:
+    if chroma == 444:
+        ow, oh = _out_size_yuv444(sr, fmt, w, h, "upscale_delta")
+    elif yuv and chroma == 422:
         ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_delta")
     elif yuv:
         ow, oh = _out_size_yuv(sr, w, h, "upscale_delta")
@@ -416,6 +514,8 @@ SEQ_MAX = 16  # frames per rsr_process_device_sequence call (RSR_SEQ_MAX)
 
 def _new_like_result(x, ow, oh, chroma=420):
     """An uninitialised result for the single image x (a tensor or a (y, uv) pair; chroma: a surface's subsampling) at ow x oh, of x's kind."""
+    if chroma == 444:
+        return _new444(x, ow, oh)
     rows = oh * 2 if chroma == 422 else oh * 3 // 2
     if isinstance(x, (tuple, list)):
         o = x[0].new_empty((rows, ow))
@@ -438,7 +538,8 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420)
     Windows of at most 16 frames; window g + 1 takes the last frame and output of window g as its prev.  Per window, all on
     torch.cuda.current_stream() (the side stream for the null stream, as in upscale_delta): the diff of all pairs, ONE asynchronous copy
     of the masks into pinned memory, ONE stream synchronisation, the sequence call.
-    chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them."""
+    chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them.  chroma=444: every frame is a planar 4:4:4
+    image as upscale_yuv(..., chroma=444) takes it -- a list of them, or a stacked (N, 3, H, W) uint8 / int16 tensor."""
     _check_chroma(chroma, "upscale_sequence")
     stacked = isinstance(frames, torch.Tensor)
     if stacked:
@@ -462,7 +563,9 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420)
         prev_y = None  # (nothing of it would be used: every tile of frames[0] runs)
     pair = isinstance(xs[0], (tuple, list))
     note = ""
-    if fmt in _YUV_FMTS and chroma == 422:
+    if chroma == 444:
+        ow, oh = _out_size_yuv444(sr, fmt, w, h, "upscale_sequence")
+    elif fmt in _YUV_FMTS and chroma == 422:
         ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_sequence")
     elif fmt in _YUV_FMTS:
         ow, oh = _out_size_yuv(sr, w, h, "upscale_sequence")
