@@ -37,10 +37,15 @@ extern "C" {
 #define RSR_E_ARG (-1)      /* bad argument */
 #define RSR_E_IO (-2)       /* cannot open / truncated file */
 #define RSR_E_FORMAT (-3)   /* .param/.bin not parseable */
-#define RSR_E_GRAPH (-4)    /* parsed graph is not the RRDBNet(3,3,64,23,32) x4.param describes */
+#define RSR_E_GRAPH (-4)    /* parsed graph is not the RRDBNet(3,3,64,nb,32) x4.param describes, for any nb in 1..RSR_MAX_RRDB */
 #define RSR_E_DEVICE (-5)   /* HIP error / no such device */
 #define RSR_E_STATE (-6)    /* call order (e.g. process before load) */
 #define RSR_E_NOMEM (-7)
+
+/* The deepest RRDBNet a context loads: RRDB blocks of the x4 graph (x4.param of the reference's model directories has 23; the anime
+ * networks 6, "lite" trainings 16).  A model of nb blocks has 15 nb + 6 convolutions, 966 at this bound -- which is what bounds the
+ * conv table a packed blob's header may announce and the `n` of rsr_selfcheck_ranges / rsr_get_conv_times. */
+#define RSR_MAX_RRDB 64
 
 typedef struct rsr_ctx rsr_ctx;
 
@@ -56,7 +61,15 @@ void rsr_destroy(rsr_ctx* ctx);
 
 /* RealSR::load(parampath, modelpath)   realsr.h:19-23, realsr.cpp:37-143.
  * Parses the ncnn text graph and tagged weight stream (fp16-tagged or raw fp32), checks that the
- * DAG is exactly the x4.param RRDBNet, packs the weights for the MFMA kernels and uploads them. */
+ * DAG is exactly the x4.param RRDBNet, packs the weights for the MFMA kernels and uploads them.
+ * Depth: the graph may have any number nb of RRDB blocks in 1..RSR_MAX_RRDB (23 in the reference's files); the depth is derived from
+ * the node count and everything else -- operator types and parameters (never names), nf 64, gc 32, three RDBs per RRDB, the 0.2 / 1
+ * Eltwise residuals, two nearest x2 Interp stages -- must equal the canonical graph of that depth, else RSR_E_GRAPH with a message that
+ * names the depth found or the first node that differs.  Stats "model_blocks" / "model_convs" read what was loaded.  A context that
+ * already ran may load a model of another depth: plans and workspace stay, the self-check report, what option "precise_auto" made of
+ * it, and the per-convolution times of the old model are dropped.
+ * Out of scope: another nf / gc, x2 / x1 / x8 networks, pixel-unshuffle inputs, SRVGG-style compact networks (they need other
+ * epilogues and a second reference), and other operator spellings of the same network (a residual written as two BinaryOps ...). */
 int rsr_load(rsr_ctx* ctx, const char* parampath, const char* modelpath);
 
 /* The public mutable fields `scale`, `tilesize`, `prepadding` assigned after load()
@@ -548,7 +561,8 @@ int rsr_set_progress_callback(rsr_ctx* ctx, void (*cb)(int tiles_done, int tiles
  * torch.distributed.broadcast with backend nccl), and every rank loads it with rsr_load_packed. */
 
 /* Host-only: parse + validate + pack into `dst` (capacity `cap` bytes).  *need receives the blob
- * size (33.5 MB for x4.param); call with dst=NULL to query.  No GPU required. */
+ * size (33.5 MB for the 23-block x4.param; 1.44 MB per RRDB block + 0.38 MB for the six other convolutions: 9.0 MB at 6 blocks); call with dst=NULL to query.  The header's
+ * conv count, 15 nb + 6, carries the depth; the layout is the same at every depth.  No GPU required. */
 int rsr_model_pack(const char* parampath, const char* modelpath, void* dst, size_t cap, size_t* need);
 
 /* Load a blob produced by rsr_model_pack.  `blob` may be a host pointer (is_device=0) or a device
@@ -685,8 +699,10 @@ int rsr_selfcheck(rsr_ctx* ctx, const uint16_t* tile, int w, int h, rsr_selfchec
 /* Host-only (no GPU): the built-in tile, planar fp16 [3][h][w]: flat areas, ramps, hard edges and fine texture over 0 .. 1, every
  * value k / 255 as the preprocessing produces it.  Integer arithmetic only: the same bytes everywhere. */
 int rsr_selfcheck_tile(uint16_t* dst, int w, int h);
-/* Per convolution (x4.param order, n <= 351 entries) of the context's last rsr_selfcheck: the largest finite |value| it stored and
- * the number of inf / NaN it stored; either pointer may be NULL.  RSR_E_STATE when no self-check has run. */
+/* Per convolution (x4.param order) of the context's last rsr_selfcheck: the largest finite |value| it stored and the number of
+ * inf / NaN it stored; either pointer may be NULL.  n: entries of the caller's arrays, 0 .. 15 RSR_MAX_RRDB + 6 = 966 (else RSR_E_ARG);
+ * entries [0, min(n, model_convs)) are written and the rest of the n are zeroed (351 convolutions at 23 blocks: stat "model_convs").
+ * RSR_E_STATE when no self-check has run since the model was loaded. */
 int rsr_selfcheck_ranges(rsr_ctx* ctx, float* peak, long long* nonfinite, int n);
 
 /* ---- measurement ------------------------------------------------------------------------- */
@@ -707,8 +723,8 @@ typedef struct rsr_profile
 int rsr_set_profiling(rsr_ctx* ctx, int enable);
 int rsr_get_profile(rsr_ctx* ctx, rsr_profile* out, int reset);
 
-/* Accumulated HIP-event time per convolution of x4.param (index = order in the file, 351 entries),
- * over the profiled calls since the last reset. */
+/* Accumulated HIP-event time per convolution of x4.param (index = order in the file; stat "model_convs" entries, 351 at 23 blocks),
+ * over the profiled calls since the last reset or load.  n as in rsr_selfcheck_ranges: 0 .. 966, entries beyond the model's zeroed. */
 int rsr_get_conv_times(rsr_ctx* ctx, double* ms, int n, int reset);
 
 /* Profiling aid: after rsr_set_option("trace_conv", i) the launch of convolution i records, for workgroup 0 /
@@ -814,7 +830,8 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *                       work items are repeated N times in that one launch: an L2-resident workload)
  *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force (0: a ratio other than 4 / 2 / 1, "out_num" / "out_den": rsr_set_out_ratio; 0 / 0 while the axes differ, "out_num_x" / "out_den_x" / "out_num_y" / "out_den_y": rsr_set_out_ratio_xy); "yuv_matrix" / "yuv_range" / "yuv_siting": likewise
  *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
- *                       "selfcheck_overflow" (-1 before the first run) */
+ *                       "selfcheck_overflow" (-1 before the first run)
+ *   "model_blocks" / "model_convs"  RRDB blocks and convolutions (15 blocks + 6) of the loaded model; 0 before a load */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);
 
 const char* rsr_last_error(const rsr_ctx* ctx); /* ctx may be NULL: last global (create/pack) error */

@@ -39,7 +39,8 @@ EXPORTS = [
     "rsr_out_size_fmt",
 ]
 
-NUM_CONVS = 351
+NUM_CONVS = 351  # convolutions of the default-depth model (23 RRDB blocks); a loaded model's own count is RealSR.num_convs
+MAX_RRDB = 64    # RSR_MAX_RRDB: the deepest model rsr_load takes (15 * 64 + 6 = 966 convolutions)
 
 RSR_OK, RSR_E_ARG, RSR_E_IO, RSR_E_FORMAT, RSR_E_GRAPH, RSR_E_DEVICE, RSR_E_STATE, RSR_E_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 # pixel formats of device-resident images (rsr_process_device_fmt): uint8 HWC, planar fp16 / fp32 [3][h][w] in [0, 1]
@@ -196,7 +197,7 @@ def model_info(param_path, bin_path):
 
 
 def model_pack(param_path, bin_path):
-    """Host-only: parse, validate and pack the model into one relocatable blob (np.uint8 array, 33.5 MB): what rsr_load
+    """Host-only: parse, validate and pack the model into one relocatable blob (np.uint8 array; 33.5 MB at 23 blocks, 9.0 MB at 6): what rsr_load
     uploads and what the multi-GPU broadcast carries."""
     L = lib()
     need = C.c_size_t()
@@ -415,6 +416,16 @@ class RealSR:
             blob = np.ascontiguousarray(blob, dtype=np.uint8)
             self._ck(self._L.rsr_load_packed(self._h, _p(blob), blob.size, 0))
 
+    @property
+    def num_blocks(self):
+        """RRDB blocks of the loaded model (stat "model_blocks"): 23 for the reference's x4.param, 1 .. MAX_RRDB accepted; 0 before a load."""
+        return int(self.get_stat("model_blocks"))
+
+    @property
+    def num_convs(self):
+        """Convolutions of the loaded model, 15 * num_blocks + 6 (stat "model_convs"); 0 before a load."""
+        return int(self.get_stat("model_convs"))
+
     def _push_params(self):
         self._ck(self._L.rsr_set_params(self._h, int(self.scale), int(self.tilesize), int(self.prepadding)))
 
@@ -583,11 +594,13 @@ class RealSR:
         return {k: getattr(r, k) for k, _ in SelfcheckReport._fields_}
 
     def selfcheck_ranges(self):
-        """rsr_selfcheck_ranges of the last selfcheck(): (peak float32[351], nonfinite int64[351]), x4.param order."""
-        peak = np.zeros(NUM_CONVS, dtype=np.float32)
-        bad = np.zeros(NUM_CONVS, dtype=np.int64)
+        """rsr_selfcheck_ranges of the last selfcheck(): (peak float32[num_convs], nonfinite int64[num_convs]), x4.param order
+        (351 entries for the default 23-block model)."""
+        n = self.num_convs or NUM_CONVS
+        peak = np.zeros(n, dtype=np.float32)
+        bad = np.zeros(n, dtype=np.int64)
         self._ck(self._L.rsr_selfcheck_ranges(self._h, peak.ctypes.data_as(C.POINTER(C.c_float)),
-                                              bad.ctypes.data_as(C.POINTER(C.c_longlong)), NUM_CONVS))
+                                              bad.ctypes.data_as(C.POINTER(C.c_longlong)), n))
         return peak, bad
 
     def conv3x3_res_precise(self, x, weight, bias, s1, own_input_residual=False, x_lo=None, res=None, res_lo=None, s2=1.0, want_lo=True):
@@ -675,9 +688,13 @@ class RealSR:
         self._ck(self._L.rsr_set_profiling(self._h, int(bool(on))))
 
     def get_conv_times(self, reset=True):
-        arr = (C.c_double * 351)()
-        self._ck(self._L.rsr_get_conv_times(self._h, arr, 351, int(bool(reset))))
+        """rsr_get_conv_times: accumulated ms per convolution of the loaded model, num_convs entries (351 for the default model)."""
+        n = self.num_convs or NUM_CONVS
+        arr = (C.c_double * n)()
+        self._ck(self._L.rsr_get_conv_times(self._h, arr, n, int(bool(reset))))
         return np.array(arr[:])
+
+    conv_times = get_conv_times
 
     def get_trace(self, n=1024):
         arr = (C.c_ulonglong * n)()

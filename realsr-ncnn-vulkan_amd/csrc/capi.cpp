@@ -583,11 +583,21 @@ int rsr_selfcheck_tile(uint16_t* dst, int w, int h)
 
 int rsr_selfcheck_ranges(rsr_ctx* ctx, float* peak, long long* nonfinite, int n)
 {
-    if (!ctx || n < 0 || n > kNumConvs) return RSR_E_ARG;
+    if (!ctx || n < 0 || n > kMaxConvs) return RSR_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->e.mu);
-    if (ctx->e.selfcheck_runs == 0) return ctx->e.fail(RSR_E_STATE, "no self-check has run on this context");
-    if (peak) std::memcpy(peak, ctx->e.sc_peak, size_t(n) * sizeof(float));
-    if (nonfinite) std::memcpy(nonfinite, ctx->e.sc_nonfinite, size_t(n) * sizeof(long long));
+    if (!ctx->e.sc_have) return ctx->e.fail(RSR_E_STATE, "no self-check has run on this context's model");
+    // entries [0, min(n, nconv)) are the model's; what is left of the caller's n is zeroed
+    const size_t have = std::min(size_t(n), ctx->e.sc_peak.size());
+    if (peak)
+    {
+        std::memcpy(peak, ctx->e.sc_peak.data(), have * sizeof(float));
+        std::fill(peak + have, peak + n, 0.f);
+    }
+    if (nonfinite)
+    {
+        std::memcpy(nonfinite, ctx->e.sc_nonfinite.data(), have * sizeof(long long));
+        std::fill(nonfinite + have, nonfinite + n, 0LL);
+    }
     return RSR_OK;
 }
 
@@ -633,10 +643,13 @@ int rsr_get_profile(rsr_ctx* ctx, rsr_profile* out, int reset)
 
 int rsr_get_conv_times(rsr_ctx* ctx, double* ms, int n, int reset)
 {
-    if (!ctx || !ms || n < 0) return RSR_E_ARG;
+    if (!ctx || !ms || n < 0 || n > kMaxConvs) return RSR_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->e.mu);
-    for (int i = 0; i < n && i < kNumConvs; i++) ms[i] = ctx->e.conv_ms_by_index[i];
-    if (reset) std::memset(ctx->e.conv_ms_by_index, 0, sizeof ctx->e.conv_ms_by_index);
+    std::vector<double>& t = ctx->e.conv_ms_by_index; // [nconv]; empty before a load
+    const size_t have = std::min(size_t(n), t.size());
+    std::copy(t.begin(), t.begin() + std::ptrdiff_t(have), ms);
+    std::fill(ms + have, ms + n, 0.0);
+    if (reset) std::fill(t.begin(), t.end(), 0.0);
     return RSR_OK;
 }
 
@@ -719,10 +732,12 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "yuv_range") *value = double(e.yuv_range);
     else if (k == "yuv_siting") *value = double(e.yuv_siting);
     else if (k == "selfcheck_runs") *value = double(e.selfcheck_runs);
-    else if (k == "selfcheck_headroom") *value = e.selfcheck_runs ? double(e.sc_last.headroom) : -1.0;
-    else if (k == "selfcheck_peak_abs") *value = e.selfcheck_runs ? double(e.sc_last.peak_abs) : -1.0;
-    else if (k == "selfcheck_ms") *value = e.selfcheck_runs ? double(e.sc_last.elapsed_ms) : -1.0;
-    else if (k == "selfcheck_overflow") *value = e.selfcheck_runs ? double(e.sc_last.fp16_overflow) : -1.0;
+    else if (k == "selfcheck_headroom") *value = e.sc_have ? double(e.sc_last.headroom) : -1.0;
+    else if (k == "selfcheck_peak_abs") *value = e.sc_have ? double(e.sc_last.peak_abs) : -1.0;
+    else if (k == "selfcheck_ms") *value = e.sc_have ? double(e.sc_last.elapsed_ms) : -1.0;
+    else if (k == "selfcheck_overflow") *value = e.sc_have ? double(e.sc_last.fp16_overflow) : -1.0;
+    else if (k == "model_blocks") *value = double(e.nb);
+    else if (k == "model_convs") *value = double(e.nconv);
     else return e.fail(RSR_E_ARG, "unknown stat " + k);
     return RSR_OK;
 }
@@ -758,7 +773,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
         ctx->e.merge_target_items = int(value);
     }
     else if (k == "precise")
-        ctx->e.precise = value != 0; // plans are keyed by it (larger slots); the workspace grows on the next call
+        ctx->e.precise = value != 0, ctx->e.precise_by_auto = false; // plans are keyed by it (larger slots); the workspace grows on the next call
     else if (k == "out_scale")
     { // the next call's output is (w * value) x (h * value): plans are keyed by it (below 4 conv_last leaves the planar blob to postproc_tiles_box)
         if (value != 1 && value != 2 && value != 4) return ctx->e.fail(RSR_E_ARG, "out_scale must be 1, 2 or 4");

@@ -209,19 +209,41 @@ void Engine::give_event(hipEvent_t e)
 }
 
 // ---- model --------------------------------------------------------------------------------
-int Engine::adopt_table(const unsigned char* head, size_t bytes)
+int Engine::adopt_table(const unsigned char* head, size_t head_bytes, size_t bytes)
 {
     std::string e;
-    const int rc = check_packed(head, packed_table_bytes(), bytes, e);
+    const int rc = check_packed(head, head_bytes, bytes, e);
     if (rc != RSR_OK) return fail(rc, e);
     return RSR_OK;
 }
 
+// The model changes hands.  Plans and workspace do not depend on the depth (tile tables, slot layout and the margins of tail_margin are
+// those of the convs behind the trunk, which every depth has), so they stay.  What described the OLD model goes: the self-check's
+// report and ranges, a `precise` that its recommendation switched on, and the per-convolution times.
+void Engine::adopt_model(const unsigned char* head)
+{
+    PackedHeader H;
+    std::memcpy(&H, head, sizeof H);
+    const PackedConv* T = reinterpret_cast<const PackedConv*>(head + sizeof(PackedHeader));
+    convs.assign(T, T + H.nconv);
+    nconv = int(H.nconv);
+    nb = depth_of_convs(H.nconv);
+    nrdb = 3 * nb;
+    sc_peak.assign(size_t(nconv), 0.f);
+    sc_nonfinite.assign(size_t(nconv), 0);
+    conv_ms_by_index.assign(size_t(nconv), 0.0);
+    std::memset(&sc_last, 0, sizeof sc_last);
+    sc_have = false;
+    if (precise_by_auto) precise = false;
+    precise_by_auto = false;
+    loaded = true;
+}
+
 int Engine::load_blob_host(const void* data, size_t bytes)
 {
-    if (!data || bytes < packed_table_bytes()) return fail(RSR_E_FORMAT, "packed blob too small");
+    if (!data || bytes < sizeof(PackedHeader)) return fail(RSR_E_FORMAT, "packed blob too small");
     // validate BEFORE touching engine state: a failed load leaves a previously loaded model intact
-    int rc = adopt_table(static_cast<const unsigned char*>(data), bytes);
+    int rc = adopt_table(static_cast<const unsigned char*>(data), bytes, bytes);
     if (rc != RSR_OK) return rc;
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -235,21 +257,22 @@ int Engine::load_blob_host(const void* data, size_t bytes)
     }
     if (blob.p) (void)hipFree(blob.p);
     blob = fresh;
-    const PackedHeader* H = static_cast<const PackedHeader*>(data);
-    const PackedConv* T = reinterpret_cast<const PackedConv*>(static_cast<const unsigned char*>(data) + sizeof(PackedHeader));
-    convs.assign(T, T + H->nconv);
-    loaded = true;
+    adopt_model(static_cast<const unsigned char*>(data));
     return RSR_OK;
 }
 
 int Engine::load_blob_device(const void* data, size_t bytes)
 {
-    // header + table are small: fetch them to the host for validation, keep the payload on device
-    if (!data || bytes < packed_table_bytes()) return fail(RSR_E_FORMAT, "packed blob too small");
+    // header + table are small: fetch them to the host for validation, keep the payload on device.  The header first: it says how
+    // long the table is (nconv, bounded by kMaxConvs before it sizes anything); never more than `bytes` is copied.
+    if (!data || bytes < sizeof(PackedHeader)) return fail(RSR_E_FORMAT, "packed blob too small");
     HIP_TRY(hipSetDevice(device));
-    std::vector<unsigned char> head(packed_table_bytes());
+    PackedHeader H;
+    HIP_TRY(hipMemcpy(&H, data, sizeof H, hipMemcpyDeviceToHost));
+    if (depth_of_convs(H.nconv) == 0 || packed_table_bytes(H.nconv) > bytes) return fail(RSR_E_FORMAT, "packed blob header mismatch (conv count / size)");
+    std::vector<unsigned char> head(packed_table_bytes(H.nconv));
     HIP_TRY(hipMemcpy(head.data(), data, head.size(), hipMemcpyDeviceToHost));
-    int rc = adopt_table(head.data(), bytes);
+    int rc = adopt_table(head.data(), head.size(), bytes);
     if (rc != RSR_OK) return rc;
     HIP_TRY(hipStreamSynchronize(stream));
     DevBuf fresh;
@@ -262,10 +285,7 @@ int Engine::load_blob_device(const void* data, size_t bytes)
     }
     if (blob.p) (void)hipFree(blob.p);
     blob = fresh;
-    const PackedHeader* H = reinterpret_cast<const PackedHeader*>(head.data());
-    const PackedConv* T = reinterpret_cast<const PackedConv*>(head.data() + sizeof(PackedHeader));
-    convs.assign(T, T + H->nconv);
-    loaded = true;
+    adopt_model(head.data());
     return RSR_OK;
 }
 
@@ -311,7 +331,7 @@ static int tail_margin(int crop4, int which) // which: 0 conv_last, 1 HRconv, 2 
         if (which >= 4)
         {
             m = (m - 1) >> 1;  // trunk_conv: read by upconv1 through the nearest-x2 gather
-            m -= (which - 4);  // RDB 69 conv5, conv4, ... each one ring further out
+            m -= (which - 4);  // the last RDB's conv5, conv4, ... each one ring further out
         }
     }
     return m > 0 ? m : 0;
@@ -749,7 +769,7 @@ void Engine::collect_profile(hipStream_t st)
             prof.conv_ms += ms;
             prof.conv_flops += s.flops;
             prof.conv_launches++;
-            if (s.conv_index >= 0 && s.conv_index < kNumConvs) conv_ms_by_index[s.conv_index] += ms;
+            if (s.conv_index >= 0 && size_t(s.conv_index) < conv_ms_by_index.size()) conv_ms_by_index[size_t(s.conv_index)] += ms;
         }
         else if (s.cls == 0) { prof.pre_ms += ms; prof.pre_bytes += s.bytes; }
         else if (s.cls == 2) { prof.post_ms += ms; prof.post_bytes += s.bytes; }
@@ -785,7 +805,8 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
     const int split_slot = io ? io->split_slot : 0;
     // the throttle event of a merged batch (Engine::submit_merged): behind the RDB that leaves about half an image's worth of network
     // ahead -- the time the next batch's launches take to enqueue
-    const int mid_rdb = (io && io->ev_mid) ? kNumRDB - 1 - std::max(2, kNumRDB / (2 * std::max(1, io->nimg))) : -1;
+    // (a one-block model has three RDBs: the formula gives RDB 0 there; the clamp keeps it inside the loop at every depth)
+    const int mid_rdb = (io && io->ev_mid) ? std::min(nrdb - 1, std::max(0, nrdb - 1 - std::max(2, nrdb / (2 * std::max(1, io->nimg))))) : -1;
     // the probe reads whole planes: they must hold exactly the pixels of the one tile, all of them computed, in fp16 storage
     if (probe && (b.nslots != 1 || b.dims.size() != 1 || cap != (long long)b.dims[0].h * b.dims[0].w || b.trim4 || precise || fused))
         return fail(RSR_E_STATE, "range probe on a plan that is not one untrimmed tile in fp16 storage");
@@ -831,8 +852,8 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
         a.trace = (trace_conv == ci) ? static_cast<unsigned long long*>(trace_buf.p) : nullptr;
         a.s1 = a.s2 = 1.f;
         a.precise = precise ? 1 : 0;
-        // x4.param order: ... RDB 69 | trunk_conv kNumConvs-5 | upconv1 -4 | upconv2 -3 | HRconv -2 | conv_last kNumConvs-1
-        constexpr int kLast = kNumConvs - 1, kUp1 = kNumConvs - 4;
+        // x4.param order: ... RDB nrdb | trunk_conv nconv-5 | upconv1 -4 | upconv2 -3 | HRconv -2 | conv_last nconv-1
+        const int kLast = nconv - 1, kUp1 = nconv - 4;
         a.margin = tail_margin(b.trim4, ci >= kUp1 ? kLast - ci : 4 + (kUp1 - 1 - ci));
         return a;
     };
@@ -858,7 +879,7 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
         a.out_lo_off = fea_lo; // the stream starts here: fea keeps its rounding residue too
         go(a);
     }
-    for (int j = 0; j < kNumRDB; j++)
+    for (int j = 0; j < nrdb; j++)
     {
         const int bi = j % 3;
         const PlaneSrc xs = (j == 0) ? fea : rdb_x(bi);
@@ -891,7 +912,7 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
     }
     { // trunk_conv + global skip: fea + conv(trunk)   (x4.param:994-995)
         ConvArgs a = base_args(0, 0);
-        a.src0 = rdb_x(kNumRDB % 3); a.n0 = P64;
+        a.src0 = rdb_x(nrdb % 3); a.n0 = P64; // (nrdb = 3 nb: always rdb_x(0), where the last RDB of an RRDB leaves its result)
         a.res1 = fea; a.res1_kind = 1; a.s1 = 1.f;
         a.lo1_off = fea_lo;
         a.out16 = rdb_x(1); // (only upconv1 reads it: no lo planes)
@@ -2407,8 +2428,8 @@ int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* 
         selfcheck_tile(own.data(), w, h);
         tile = own.data();
     }
-    // device side of the report: nonfinite[kNumConvs] | bytes_differ | peak_bits[kNumConvs] | storage_err bits, max_byte_diff
-    constexpr size_t kRep64 = kNumConvs + 1, kRep32 = kNumConvs + 2, kRepBytes = kRep64 * 8 + kRep32 * 4;
+    // device side of the report: nonfinite[nconv] | bytes_differ | peak_bits[nconv] | storage_err bits, max_byte_diff
+    const size_t nc = size_t(nconv), kRep64 = nc + 1, kRep32 = nc + 2, kRepBytes = kRep64 * 8 + kRep32 * 4;
     OneTile t;
     ScratchBuf rep, out16;
     int rc;
@@ -2434,7 +2455,7 @@ int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* 
         precise = pass == 1;
         if ((rc = one_tile_walk(t, pass == 0 ? &probe : nullptr)) != RSR_OK) return rc;
         if (pass == 0) he = hipMemcpyAsync(out16.p, b_out3.p, nout * 2, hipMemcpyDeviceToDevice, stream);
-        else launch_output_compare(static_cast<const uint16_t*>(out16.p), static_cast<const float*>(b_out3.p), (long long)nout, r32 + kNumConvs, r64 + kNumConvs, stream);
+        else launch_output_compare(static_cast<const uint16_t*>(out16.p), static_cast<const float*>(b_out3.p), (long long)nout, r32 + nc, r64 + nc, stream);
     }
     std::vector<unsigned long long> h64(kRep64);
     std::vector<unsigned> h32(kRep32);
@@ -2448,26 +2469,27 @@ int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* 
     std::memset(&r, 0, sizeof r);
     r.tile_w = w;
     r.tile_h = h;
-    std::memcpy(&r.storage_err, &h32[kNumConvs], 4);
+    std::memcpy(&r.storage_err, &h32[nc], 4);
     r.headroom = r.storage_err > 0.f ? (1.f / 255.f) / r.storage_err : 3.402823466e+38f;
-    r.max_byte_diff = int(h32[kNumConvs + 1]);
-    r.bytes_differ = (long long)h64[kNumConvs];
+    r.max_byte_diff = int(h32[nc + 1]);
+    r.bytes_differ = (long long)h64[nc];
     r.peak_conv = 0;
-    for (int i = 0; i < kNumConvs; i++)
+    for (size_t i = 0; i < nc; i++)
     {
-        std::memcpy(&sc_peak[i], &h32[size_t(i)], 4);
-        sc_nonfinite[i] = (long long)h64[size_t(i)];
+        std::memcpy(&sc_peak[i], &h32[i], 4);
+        sc_nonfinite[i] = (long long)h64[i];
         r.nonfinite += sc_nonfinite[i];
         if (sc_peak[i] > r.peak_abs)
         {
             r.peak_abs = sc_peak[i];
-            r.peak_conv = i;
+            r.peak_conv = int(i);
         }
     }
     r.fp16_overflow = (r.nonfinite > 0 || r.peak_abs >= 65504.f) ? 1 : 0;
     r.recommend_precise = r.headroom < 1.5f ? 1 : 0;
     r.elapsed_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     sc_last = r;
+    sc_have = true;
     selfcheck_runs++;
     *out = r;
     return RSR_OK;
@@ -2477,7 +2499,7 @@ int Engine::apply_precise_auto()
 {
     rsr_selfcheck_report r;
     const int rc = selfcheck(nullptr, 0, 0, &r);
-    if (rc == RSR_OK) precise = r.recommend_precise != 0;
+    if (rc == RSR_OK) precise = precise_by_auto = r.recommend_precise != 0;
     return rc;
 }
 

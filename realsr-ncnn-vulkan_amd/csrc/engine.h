@@ -2,7 +2,7 @@
 //
 // Replaces RealSR::process (/root/reference/src/realsr.cpp:145-523): instead of a row-band loop with
 // one Vulkan submit_and_wait per tile and >= 722 dispatches per tile, ALL tiles of an image (x8 under
-// TTA) are laid out as "slots" of one batch and walk the 351 convolutions together: one kernel launch
+// TTA) are laid out as "slots" of one batch and walk the model's convolutions (351 at 23 RRDB blocks) together: one kernel launch
 // per network layer per batch, no host synchronisation inside a call.
 //
 // Concurrency (the reference calls RealSR::process from several proc threads on one object, main.cpp:811-828,
@@ -126,8 +126,8 @@ struct Plan
 // Device tables of the range probe (Engine::selfcheck): entry i receives what convolution i of x4.param stored.
 struct RangeProbe
 {
-    unsigned* peak_bits = nullptr;           // bits of the largest finite |value| as a float [kNumConvs]
-    unsigned long long* nonfinite = nullptr; // stored inf / NaN [kNumConvs]
+    unsigned* peak_bits = nullptr;           // bits of the largest finite |value| as a float [Engine::nconv]
+    unsigned long long* nonfinite = nullptr; // stored inf / NaN [Engine::nconv]
 };
 
 // Helper threads for the staging copies of pageable images (pinned chunk <-> the caller's malloc'ed buffer): one core
@@ -289,8 +289,10 @@ struct Engine
     bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
     long long selfcheck_runs = 0;
     rsr_selfcheck_report sc_last{}; // of the last run
-    float sc_peak[kNumConvs] = {0};
-    long long sc_nonfinite[kNumConvs] = {0};
+    bool sc_have = false;           // sc_last / sc_peak / sc_nonfinite describe the loaded model (a load drops them)
+    bool precise_by_auto = false;   // `precise` is on because a self-check of the loaded model recommended it (a load drops that too)
+    std::vector<float> sc_peak;     // [nconv], resized and zeroed on every load (adopt_model)
+    std::vector<long long> sc_nonfinite;
     int selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* out); // mu held
     int apply_precise_auto();                                                      // mu held, loaded: self-check on the built-in tile -> precise
     long long bytes_per_px() const; // workspace bytes per padded LR pixel of a slot
@@ -321,7 +323,8 @@ struct Engine
     CopyPool pool;
     hipStream_t stream = nullptr;          // the compute stream
 
-    // model
+    // model: depth of the loaded RRDBNet (0 before a load) -- nb RRDB blocks, nrdb = 3 nb dense blocks, nconv = 15 nb + 6 convolutions
+    int nb = 0, nrdb = 0, nconv = 0;
     std::vector<PackedConv> convs;
     DevBuf blob; // packed weights on device
     DevBuf zeros;
@@ -381,7 +384,7 @@ struct Engine
         double flops, bytes;
         int conv_index;
     };
-    double conv_ms_by_index[kNumConvs] = {0};
+    std::vector<double> conv_ms_by_index; // [nconv], resized and zeroed on every load
     std::vector<Seg> segs;
     size_t ev_used = 0;
     rsr_profile prof{};
@@ -491,7 +494,8 @@ struct Engine
     void give_event(hipEvent_t e);
     Lane* acquire_lane(); // lane_mu inside
     void release_lane(Lane* l);
-    int adopt_table(const unsigned char* head, size_t bytes); // validated header -> convs
+    int adopt_table(const unsigned char* head, size_t head_bytes, size_t bytes); // check_packed of a header + table that came from anywhere
+    void adopt_model(const unsigned char* head);             // a validated header + table -> convs, nb / nrdb / nconv; drops what belonged to the old model
     static int fail(int code, const std::string& msg);
 };
 

@@ -374,6 +374,11 @@ int main(int argc, char** argv)
         r->tilesize = tilesize[size_t(i)];
         r->prepadding = prepadding;
         r->out_scale = out_scale ? out_scale : 4;
+        double model_blocks = 0, model_convs = 0; // the depth of the model that was loaded (stats "model_blocks" / "model_convs")
+        rsr_get_stat(ctxs[size_t(i)], "model_blocks", &model_blocks);
+        rsr_get_stat(ctxs[size_t(i)], "model_convs", &model_convs);
+        const int nconv = int(model_convs);
+        if (verbose) fprintf(stderr, "gpu %d: model: %d blocks, %d convolutions\n", gpuid[size_t(i)], int(model_blocks), nconv);
         if (!out_scale) r->out_num = out_num, r->out_den = out_den, r->out_num_y = out_num_y, r->out_den_y = out_den_y;
         if (verbose && out_scale) fprintf(stderr, "gpu %d: output scale %d%s\n", gpuid[size_t(i)], out_scale, out_scale == 4 ? "" : " (RSR_OUT_SCALE: the x4 result box-reduced)");
         if (verbose && !out_scale && !out_den_y) fprintf(stderr, "gpu %d: output scale %d/%d (RSR_OUT_SCALE: the x4 result area-averaged)\n", gpuid[size_t(i)], out_num, out_den);
@@ -413,12 +418,12 @@ int main(int argc, char** argv)
             rsr_get_stat(ctxs[size_t(i)], "selfcheck_overflow", &overflow);
             rsr_get_stat(ctxs[size_t(i)], "selfcheck_ms", &ms);
             rsr_get_stat(ctxs[size_t(i)], "precise_active", &active);
-            std::vector<float> pk(351, 0.f);
-            std::vector<long long> bad(351, 0);
-            rsr_selfcheck_ranges(ctxs[size_t(i)], pk.data(), bad.data(), 351);
+            std::vector<float> pk(size_t(std::max(1, nconv)), 0.f);
+            std::vector<long long> bad(pk.size(), 0);
+            rsr_selfcheck_ranges(ctxs[size_t(i)], pk.data(), bad.data(), nconv);
             int peak_conv = 0;
             long long nonfinite = 0;
-            for (int k = 0; k < 351; k++)
+            for (int k = 0; k < nconv; k++)
             {
                 nonfinite += bad[size_t(k)];
                 if (pk[size_t(k)] > pk[size_t(peak_conv)]) peak_conv = k;

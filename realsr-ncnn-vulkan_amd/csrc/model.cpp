@@ -1,6 +1,7 @@
 // model.cpp -- see model.h.  Host-only C++ (no HIP).
 #include "model.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -256,7 +257,7 @@ int flatten(const Model& m, std::vector<VNode>& out, std::string& err)
     return RSR_OK;
 }
 
-void canonical(std::vector<VNode>& g)
+void canonical(std::vector<VNode>& g, int nb)
 {
     auto add = [&](const std::string& type, const std::string& sig, std::vector<int> ins) {
         g.push_back(VNode{type, sig, std::move(ins)});
@@ -271,7 +272,7 @@ void canonical(std::vector<VNode>& g)
     const int data = add("Input", "", {});
     const int fea = conv(data, 3, kNF, false);
     int cur = fea;
-    for (int i = 0; i < kNumRRDB; i++)
+    for (int i = 0; i < nb; i++)
     {
         const int rin = cur;
         for (int j = 0; j < 3; j++)
@@ -300,25 +301,44 @@ void canonical(std::vector<VNode>& g)
 }
 } // namespace
 
-int validate_graph(const Model& m, std::string& err)
+// Compute nodes of the canonical graph at depth nb: Input, conv_first | per RRDB 3 x (5 convs + 4 Concats + 1 Eltwise) + 1 Eltwise |
+// trunk_conv, BinaryOp, 2 x (Interp + conv), HRconv, conv_last.
+constexpr int kNodesPerRRDB = 3 * 10 + 1, kNodesFixed = 10;
+
+int validate_graph(const Model& m, std::string& err, int* nb_out)
 {
     std::vector<VNode> got, want;
     int rc = flatten(m, got, err);
     if (rc != RSR_OK) return rc;
-    canonical(want);
-    if (got.size() != want.size())
+    // The depth is what the node count says; everything else about the graph must then equal the canonical one of that depth.  A count
+    // that fits no depth (an RDB or an Eltwise missing, a stage too many) is compared with the nearest depth, so that the message names
+    // the first node that differs.
+    const long long body = (long long)got.size() - kNodesFixed;
+    const long long found = body < 0 ? 0 : (body + kNodesPerRRDB / 2) / kNodesPerRRDB;
+    const bool whole = body >= 0 && body % kNodesPerRRDB == 0;
+    if (whole && (found < 1 || found > kMaxRRDB))
     {
-        err = "graph is not RRDBNet(3,3,64,23,32): " + std::to_string(got.size()) + " compute nodes, expected " +
-              std::to_string(want.size());
+        err = "graph has the " + std::to_string(got.size()) + " compute nodes of an RRDBNet with " + std::to_string(found) +
+              " RRDB blocks: the depth must be 1.." + std::to_string(kMaxRRDB);
         return RSR_E_GRAPH;
     }
-    for (size_t i = 0; i < got.size(); i++)
+    const int nb = int(std::min<long long>(std::max<long long>(found, 1), kMaxRRDB));
+    canonical(want, nb);
+    const std::string name = "RRDBNet(3,3,64," + std::to_string(nb) + ",32)";
+    for (size_t i = 0; i < got.size() && i < want.size(); i++)
         if (!(got[i] == want[i]))
         {
-            err = "graph differs from RRDBNet(3,3,64,23,32) at compute node " + std::to_string(i) + " (" + got[i].type +
+            err = "graph differs from " + name + " at compute node " + std::to_string(i) + " (" + got[i].type +
                   " " + got[i].sig + " vs " + want[i].type + " " + want[i].sig + ")";
             return RSR_E_GRAPH;
         }
+    if (got.size() != want.size())
+    {
+        err = "graph is not " + name + ": " + std::to_string(got.size()) + " compute nodes, expected " +
+              std::to_string(want.size()) + " (no depth 1.." + std::to_string(kMaxRRDB) + " has that many)";
+        return RSR_E_GRAPH;
+    }
+    if (nb_out) *nb_out = nb;
     return RSR_OK;
 }
 
@@ -420,13 +440,13 @@ int load_model(const std::string& param, const std::string& bin, Model& m, std::
 {
     int rc = parse_param(param, m, err);
     if (rc != RSR_OK) return rc;
-    rc = validate_graph(m, err);
+    rc = validate_graph(m, err, &m.nb);
     if (rc != RSR_OK) return rc;
     rc = read_bin(bin, m, err);
     if (rc != RSR_OK) return rc;
-    if (int(m.convs.size()) != kNumConvs)
+    if (int(m.convs.size()) != num_convs(m.nb))
     {
-        err = "expected 351 convolutions";
+        err = "expected " + std::to_string(num_convs(m.nb)) + " convolutions";
         return RSR_E_GRAPH;
     }
     return RSR_OK;
@@ -531,13 +551,14 @@ int pack_model(const Model& m, void* dst, size_t cap, std::string& err)
     return RSR_OK;
 }
 
-void canonical_conv(int index, int& cin, int& cout, int& act)
+void canonical_conv(int nb, int index, int& cin, int& cout, int& act)
 {
-    // x4.param order: conv_first | 69 x {64->32, 96->32, 128->32, 160->32 (LeakyReLU), 192->64} | trunk_conv |
+    // x4.param order: conv_first | 3 nb x {64->32, 96->32, 128->32, 160->32 (LeakyReLU), 192->64} | trunk_conv |
     // upconv1, upconv2, HRconv (LeakyReLU) | conv_last
+    const int nrdb = 3 * nb;
     act = 0;
     if (index == 0) { cin = 3; cout = kNF; return; }
-    if (index <= kNumRDB * 5)
+    if (index <= nrdb * 5)
     {
         const int k = (index - 1) % 5;
         cin = kNF + k * kGC;
@@ -545,36 +566,48 @@ void canonical_conv(int index, int& cin, int& cout, int& act)
         act = k < 4 ? 2 : 0;
         return;
     }
-    const int t = index - 1 - kNumRDB * 5; // 0 trunk, 1 up1, 2 up2, 3 HR, 4 last
+    const int t = index - 1 - nrdb * 5; // 0 trunk, 1 up1, 2 up2, 3 HR, 4 last
     cin = kNF;
     cout = t == 4 ? 3 : kNF;
     act = (t >= 1 && t <= 3) ? 2 : 0;
 }
 
-size_t packed_table_bytes() { return sizeof(PackedHeader) + size_t(kNumConvs) * sizeof(PackedConv); }
+void canonical_conv(int index, int& cin, int& cout, int& act) { canonical_conv(kNumRRDB, index, cin, cout, act); }
+
+size_t packed_table_bytes(uint32_t nconv) { return sizeof(PackedHeader) + size_t(nconv) * sizeof(PackedConv); }
+size_t packed_table_bytes() { return packed_table_bytes(uint32_t(kNumConvs)); }
 
 int check_packed(const void* head, size_t head_bytes, size_t total_bytes, std::string& err)
 {
-    if (!head || head_bytes < packed_table_bytes() || total_bytes < head_bytes)
+    if (!head || head_bytes < sizeof(PackedHeader) || total_bytes < head_bytes)
     {
         err = "packed blob too small";
         return RSR_E_FORMAT;
     }
-    const PackedHeader* H = static_cast<const PackedHeader*>(head);
-    if (H->magic != kPackedMagic || H->version != kPackedVersion || H->nconv != uint32_t(kNumConvs) || H->total_bytes != total_bytes || H->flags != 0u)
+    PackedHeader H; // (a copy: `head` may be any byte buffer)
+    std::memcpy(&H, head, sizeof H);
+    const int nb = depth_of_convs(H.nconv);
+    if (H.magic != kPackedMagic || H.version != kPackedVersion || nb == 0 || H.total_bytes != total_bytes || H.flags != 0u)
     {
         err = "packed blob header mismatch (magic / version / conv count / size)";
         return RSR_E_FORMAT;
     }
-    const PackedConv* T = reinterpret_cast<const PackedConv*>(static_cast<const unsigned char*>(head) + sizeof(PackedHeader));
-    for (int i = 0; i < kNumConvs; i++)
+    const size_t table = packed_table_bytes(H.nconv); // <= 16 + 966 * 48: nconv was bounded above
+    if (head_bytes < table)
     {
-        const PackedConv& c = T[i];
+        err = "packed blob too small for its table of " + std::to_string(H.nconv) + " convolutions";
+        return RSR_E_FORMAT;
+    }
+    const unsigned char* tab = static_cast<const unsigned char*>(head) + sizeof(PackedHeader);
+    for (int i = 0; i < int(H.nconv); i++)
+    {
+        PackedConv c;
+        std::memcpy(&c, tab + size_t(i) * sizeof(PackedConv), sizeof c);
         int cin, cout, act;
-        canonical_conv(i, cin, cout, act);
+        canonical_conv(nb, i, cin, cout, act);
         const uint64_t np = uint64_t((cin + 31) / 32), nt = uint64_t((cout + 31) / 32);
         bool ok = int(c.cin) == cin && int(c.cout) == cout && int(c.act) == act && c.nplanes == np && c.nt == nt;
-        auto inside = [&](uint64_t off, uint64_t size) { return off >= packed_table_bytes() && (off & 255) == 0 && off <= total_bytes && size <= total_bytes - off; };
+        auto inside = [&](uint64_t off, uint64_t size) { return off >= table && (off & 255) == 0 && off <= total_bytes && size <= total_bytes - off; };
         ok = ok && inside(c.b_off, nt * 32 * 4) && inside(c.w16_off, 2 * np * 9 * nt * 32 * 32);
         ok = ok && (cout <= 4 ? inside(c.aux_off, 2 * np * 3 * 32 * 32) : c.aux_off == 0);
         if (!ok)

@@ -2,7 +2,8 @@
 //
 // Replaces what the reference gets from ncnn::Net::load_param / load_model
 // (/root/reference/src/realsr.cpp:75-76) for the one graph it ships:
-// models/models-DF2K*/x4.param = ESRGAN RRDBNet(in 3, out 3, nf 64, nb 23, gc 32), 999 layers.
+// models/models-DF2K*/x4.param = ESRGAN RRDBNet(in 3, out 3, nf 64, nb 23, gc 32), 999 layers -- and the same graph at any
+// other depth nb in 1..RSR_MAX_RRDB (the 6-block anime networks, 16-block "lite" trainings): 15 nb + 6 convolutions.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -37,19 +38,26 @@ struct Model
     int n_layers = 0, n_blobs = 0;
     std::vector<ParamLayer> layers;
     std::vector<ConvRec> convs; // file order == canonical RRDBNet order (validated)
+    int nb = 0;                 // RRDB blocks of the validated graph (validate_graph); convs.size() == num_convs(nb) after load_model
     int bin_encoding = -1;      // 1 fp16-tagged, 0 raw fp32, 2 mixed/table
     long long n_weights = 0, n_biases = 0;
 };
 
-// Network constants of the validated graph
+// Network constants of the validated graph at the DEFAULT depth (x4.param of the reference's model directories).  The depth a
+// model really has is Model::nb / PackedHeader::nconv; these size nothing that a loaded model is held in.
 constexpr int kNumRRDB = 23;
 constexpr int kNumRDB = kNumRRDB * 3; // 69
 constexpr int kNumConvs = 1 + kNumRDB * 5 + 5; // 351
 constexpr int kNF = 64, kGC = 32;
+constexpr int kMaxRRDB = 64;                        // == RSR_MAX_RRDB (include/realsr_hip.h): bounds a table size read from a blob header
+constexpr int num_convs(int nb) { return 15 * nb + 6; } // conv_first + 3 nb RDBs of 5 + trunk_conv, upconv1, upconv2, HRconv, conv_last
+constexpr int kMaxConvs = num_convs(kMaxRRDB);      // 966
+// the depth with num_convs(nb) == nconv, or 0 when there is none in 1..kMaxRRDB
+constexpr int depth_of_convs(uint32_t nconv) { return (nconv >= 21u && nconv <= uint32_t(kMaxConvs) && (nconv - 6u) % 15u == 0u) ? int((nconv - 6u) / 15u) : 0; }
 
 // Error codes match include/realsr_hip.h
 int parse_param(const std::string& path, Model& m, std::string& err);
-int validate_graph(const Model& m, std::string& err); // checks DAG == canonical RRDBNet, fills nothing
+int validate_graph(const Model& m, std::string& err, int* nb = nullptr); // checks DAG == canonical RRDBNet of some depth 1..kMaxRRDB (*nb), fills nothing else
 int read_bin(const std::string& path, Model& m, std::string& err);
 int load_model(const std::string& param, const std::string& bin, Model& m, std::string& err);
 
@@ -64,8 +72,8 @@ int load_model(const std::string& param, const std::string& bin, Model& m, std::
 struct PackedHeader
 {
     uint32_t magic;   // 'RSRP'
-    uint32_t version; // 5
-    uint32_t nconv;
+    uint32_t version; // kPackedVersion
+    uint32_t nconv;   // 15 nb + 6: the depth of the model (depth_of_convs)
     uint32_t flags;   // 0 (version 3 carried the 32-channel images of the round-1 kernels behind bit 0)
     uint64_t total_bytes;
 };
@@ -93,12 +101,16 @@ constexpr uint32_t kPackedMagic = 0x50525352u; // "RSRP"
 size_t packed_size(const Model& m);
 int pack_model(const Model& m, void* dst, size_t cap, std::string& err);
 // Full validation of a blob that may come from anywhere (a broadcast, a file): header, every offset + extent inside the
-// blob, and the conv table equal to the canonical RRDBNet schedule (cin/cout/act per index) the engine hard-wires.
-// Only the header + table (first packed_table_bytes() bytes) are dereferenced.
+// blob, and the conv table equal to the canonical RRDBNet schedule (cin/cout/act per index) of the depth the header names.
+// The header is read first (head_bytes >= sizeof(PackedHeader)); its nconv must be num_convs(nb) for some nb in 1..kMaxRRDB and
+// head_bytes at least packed_table_bytes(nconv) before any table entry is looked at.  Only those bytes are dereferenced.
 int check_packed(const void* head, size_t head_bytes, size_t total_bytes, std::string& err);
-size_t packed_table_bytes();
-// cin / cout of convolution `index` (0..350) in x4.param order
+size_t packed_table_bytes();               // header + table of the default depth (kNumConvs entries)
+size_t packed_table_bytes(uint32_t nconv); // ... of nconv entries
+// cin / cout of convolution `index` (0..350) in x4.param order at the default depth ...
 void canonical_conv(int index, int& cin, int& cout, int& act);
+// ... and at depth nb (index 0 .. num_convs(nb) - 1)
+void canonical_conv(int nb, int index, int& cin, int& cout, int& act);
 
 uint16_t f32_to_f16(float f);
 float f16_to_f32(uint16_t h);

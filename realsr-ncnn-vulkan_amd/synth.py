@@ -8,6 +8,8 @@ everything the tests and the bench need is generated here, deterministically fro
                        exactly as `models/models-DF2K/x4.param` spells it (tests/test_model_io.py
                        checks byte equality against the reference file when it is present).
 * `make_weights()`  -- seeded, fp16-representable conv weights/biases (351 convs, OIHW).
+                       Both, `conv_specs()` and `make_model_dir()` take a depth `nb` (RRDB blocks, 1..64): the same
+                       graph with another trip count of its block loop, 15 * nb + 6 convs.  None = NB, the default depth.
 * `write_bin()`     -- ncnn `.bin` in either encoding ncnn can read for a type-0 blob
                        (fp16-tagged 0x01306B47, or raw fp32 tag 0) -- SURVEY.md Appendix A.2.
 * `make_image()`    -- seeded RGB/RGBA uint8 test image (low-pass noise + gradients + hard edges).
@@ -25,10 +27,14 @@ GC = 32
 FP16_TAG = 0x01306B47
 
 
-def conv_specs():
-    """(cin, cout, act) of the 351 convs in .param/.bin order (act: 0 none, 2 leakyrelu 0.2)."""
+def _depth(nb):
+    return NB if nb is None else int(nb)
+
+
+def conv_specs(nb=None):
+    """(cin, cout, act) of the 15 * nb + 6 convs (351 at the default depth) in .param/.bin order (act: 0 none, 2 leakyrelu 0.2)."""
     specs = [(3, NF, 0)]
-    for _ in range(NB * 3):
+    for _ in range(_depth(nb) * 3):
         for k in range(4):
             specs.append((NF + k * GC, GC, 2))
         specs.append((NF + 4 * GC, NF, 0))
@@ -43,7 +49,7 @@ def conv_specs():
 # --------------------------------------------------------------------------------------------
 # .param writer
 # --------------------------------------------------------------------------------------------
-def _param_layers():
+def _param_layers(nb):
     """Layer list before Split insertion: (type, name, [in blobs], out blob, params string)."""
     layers = []
     node = [0]
@@ -85,7 +91,7 @@ def _param_layers():
     layers.append(("Input", "input.1", [], "data", ""))
     fea = conv("data", 3, NF, False)
     cur = fea
-    for _ in range(NB):
+    for _ in range(nb):
         rrdb_in = cur
         for _ in range(3):
             x = cur
@@ -113,8 +119,8 @@ def _param_layers():
     return layers
 
 
-def param_text():
-    layers = _param_layers()
+def param_text(nb=None):
+    layers = _param_layers(_depth(nb))
     # consumers per blob, in layer order
     consumers = {}
     for li, (_, _, ins, _, _) in enumerate(layers):
@@ -148,15 +154,15 @@ def param_text():
     return "\n".join(lines) + "\n"
 
 
-def write_param(path):
+def write_param(path, nb=None):
     with open(path, "w") as f:
-        f.write(param_text())
+        f.write(param_text(nb))
 
 
 # --------------------------------------------------------------------------------------------
 # weights
 # --------------------------------------------------------------------------------------------
-def make_weights(seed, rdb_gain=0.6, io_gain=1.0, trunk_gain=0.02, last_gain=0.12, bias_std=0.02, round_fp16=True, hot=1.0, chan_sigma=0.0):
+def make_weights(seed, rdb_gain=0.6, io_gain=1.0, trunk_gain=0.02, last_gain=0.12, bias_std=0.02, round_fp16=True, hot=1.0, chan_sigma=0.0, nb=None):
     """Seeded synthetic weights, rounded to fp16-representable fp32.
 
     He-normal (fan_in, leaky slope 0.2) scaled by `rdb_gain` inside the dense blocks (ESRGAN initialises
@@ -174,15 +180,22 @@ def make_weights(seed, rdb_gain=0.6, io_gain=1.0, trunk_gain=0.02, last_gain=0.1
     `chan_sigma` > 0: every conv's OUTPUT channels get log-normal gains exp(sigma * N(0,1)), normalised to unit RMS per conv -- the
     channel-to-channel spread trained ESRGAN weights show (a few loud channels, many quiet ones) instead of i.i.d. filters; sigma = 1
     spreads the channel scales over ~50x.
+
+    `nb`: the depth (None = NB).  `trunk_gain` is stated for the default depth.  The trunk grows ~1.2x per RRDB, so at depth nb
+    trunk_conv is scaled by trunk_gain * 1.2 ** (23 - nb) instead: 1.2 ** nb * that = the same 1.2 ** 23 * trunk_gain at every depth --
+    the trunk's contribution next to `fea`, and so at the output, is comparable across depths.  At nb = 23 the factor is exactly 1.
     """
+    nb = _depth(nb)
     rng = np.random.default_rng(seed)
     ws = []
-    specs = conv_specs()
+    specs = conv_specs(nb)
+    if nb != 23:
+        trunk_gain = trunk_gain * 1.2 ** (23 - nb)
     for i, (cin, cout, act) in enumerate(specs):
         he = np.sqrt(2.0 / ((1 + 0.2 ** 2) * cin * 9))
-        in_rdb = 1 <= i <= NB * 15
+        in_rdb = 1 <= i <= nb * 15
         gain = rdb_gain if in_rdb else io_gain
-        if i == NB * 15 + 1:
+        if i == nb * 15 + 1:
             gain = trunk_gain
         if i == len(specs) - 1:
             gain = last_gain
@@ -222,8 +235,14 @@ def write_bin(path, weights, encoding="fp16"):
             f.write(b.astype(np.float32).tobytes())
 
 
-def make_model_dir(root, name="models-DF2K", seed=42, encoding="fp16", **kw):
-    """Create <root>/<name>/x4.param + x4.bin; returns the directory.  Reuses an existing one."""
+def make_model_dir(root, name="models-DF2K", seed=42, encoding="fp16", nb=None, **kw):
+    """Create <root>/<name>/x4.param + x4.bin; returns the directory.  Reuses an existing one.
+    nb: the depth (None = NB).  A model of another depth than 23 goes to <name>-nb<depth>: a cache directory shared with the
+    default-depth models is never overwritten."""
+    nb = _depth(nb)
+    if nb != 23:
+        name = "%s-nb%d" % (name, nb)
+        kw = dict(kw, nb=nb)
     d = os.path.join(root, name)
     os.makedirs(d, exist_ok=True)
     pp, bp = os.path.join(d, "x4.param"), os.path.join(d, "x4.bin")
@@ -231,7 +250,7 @@ def make_model_dir(root, name="models-DF2K", seed=42, encoding="fp16", **kw):
     tag = "%d %s %r" % (seed, encoding, sorted(kw.items()))
     if os.path.exists(stamp) and open(stamp).read() == tag and os.path.exists(pp) and os.path.exists(bp):
         return d
-    write_param(pp)
+    write_param(pp, nb)
     write_bin(bp, make_weights(seed, **kw), encoding)
     with open(stamp, "w") as f:
         f.write(tag)

@@ -5,8 +5,9 @@ checkout ships x4.param without x4.bin (/root/reference/.MISSING_LARGE_BLOBS).  
     python tools/check_real_model.py <dir with x4.param + x4.bin>  [--no-gpu] [--no-bench] [--json out.json]
     python tools/check_real_model.py                # looks in $RSR_REAL_MODELS, ./models/models-DF2K, ./models/models-DF2K_JPEG
 
-It (1) identifies the .bin encoding by its size -- 33,424,520 B = fp16-tagged (flag 0x01306B47 per conv), 66,793,352 B = raw
-fp32 (SURVEY a-7; what ncnn::Net::load_model reads, realsr.cpp:75-76) -- and cross-checks with the parser; (2) host-only:
+It (1) identifies the .bin encoding by its size -- at 23 blocks 33,424,520 B = fp16-tagged (flag 0x01306B47 per conv), 66,793,352 B = raw
+fp32 (SURVEY a-7; what ncnn::Net::load_model reads, realsr.cpp:75-76); at another depth (rsr_load takes 1 .. 64 RRDB blocks) the two
+sizes that depth's graph gives -- and cross-checks with the parser; (2) host-only:
 parses, validates the graph, packs the blob, reports weight statistics (max |w|, how many weights are not fp16-representable);
 (3) walks the network in fp32 on the CPU oracle over a real-image-like tile and reports the ACTIVATION RANGE per RDB -- the
 engine stores every feature map as fp16 (max 65504): the overflow guard for weights nobody has run through it before; (4) on
@@ -30,7 +31,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-SIZE_FP16_TAGGED, SIZE_RAW_FP32 = 33424520, 66793352  # 351 tags + fp16 weights + fp32 biases | fp32 everything
+SIZE_FP16_TAGGED, SIZE_RAW_FP32 = 33424520, 66793352  # 351 tags + fp16 weights + fp32 biases | fp32 everything (23 blocks)
 FP16_MAX = 65504.0
 
 
@@ -44,12 +45,23 @@ def find_model_dir(arg):
     return None
 
 
-def encoding_by_size(n):
-    if n == SIZE_FP16_TAGGED:
+def sizes_of(info):
+    """(fp16-tagged, raw fp32) .bin sizes of the graph model_info describes: a 4-byte tag per conv, 2 or 4 bytes per weight (every
+    conv of the graph has an even weight count: no padding), fp32 biases.  23 blocks: the two constants above."""
+    return tuple(4 * info["n_convs"] + k * info["n_weights"] + 4 * info["n_biases"] for k in (2, 4))
+
+
+def encoding_by_size(n, sizes=(SIZE_FP16_TAGGED, SIZE_RAW_FP32)):
+    if n == sizes[0]:
         return "fp16-tagged"
-    if n == SIZE_RAW_FP32:
+    if n == sizes[1]:
         return "raw-fp32"
     return None
+
+
+def flop_per_px(nb):
+    """Algorithmic FLOPs per padded LR pixel of the nb-block network: 35,853,696 at 23 blocks."""
+    return 18 * (3 * 64 + 3 * nb * (64 + 96 + 128 + 160 + 2 * 192) * 32 + 64 * 64 + 4 * 64 * 64 + 16 * (2 * 64 * 64 + 64 * 3))
 
 
 def host_checks(pp, bp, rep):
@@ -58,14 +70,18 @@ def host_checks(pp, bp, rep):
     ok = True
     size = os.path.getsize(bp)
     rep["bin_bytes"] = size
-    rep["encoding_by_size"] = encoding_by_size(size)
-    info = R.model_info(pp, bp)  # parses + validates the DAG against RRDBNet(3,3,64,23,32); raises on anything else
+    info = R.model_info(pp, bp)  # parses + validates the DAG against RRDBNet(3,3,64,nb,32) for the nb in 1..64 its node count gives; raises on anything else
     rep["model_info"] = info
+    rep["blocks"] = (info["n_convs"] - 6) // 15
+    size_f16, size_f32 = sizes_of(info)
+    assert rep["blocks"] != 23 or (size_f16, size_f32) == (SIZE_FP16_TAGGED, SIZE_RAW_FP32)
+    rep["encoding_by_size"] = encoding_by_size(size, (size_f16, size_f32))
+    print("  %d RRDB blocks, %d convolutions" % (rep["blocks"], info["n_convs"]))
     enc_names = {1: "fp16-tagged", 0: "raw-fp32", 2: "mixed/table"}
     rep["encoding_by_parser"] = enc_names.get(info["bin_encoding"], str(info["bin_encoding"]))
     if rep["encoding_by_size"] is None:
         print("  NOTE: %d bytes is neither %d (fp16-tagged) nor %d (raw fp32): per-conv mixed encoding; the parser says %s" % (
-            size, SIZE_FP16_TAGGED, SIZE_RAW_FP32, rep["encoding_by_parser"]))
+            size, size_f16, size_f32, rep["encoding_by_parser"]))
     elif rep["encoding_by_size"] != rep["encoding_by_parser"]:
         print("  FAIL: size says %s, parser says %s" % (rep["encoding_by_size"], rep["encoding_by_parser"]))
         ok = False
@@ -105,7 +121,7 @@ def activation_ranges(net, tile):
     fea = conv(tile, False)
     peaks.append(("conv_first", float(np.abs(fea).max())))
     x = fea
-    for b in range(23):
+    for b in range((net.num_convs - 6) // 15):
         rrdb_in = x
         for j in range(3):
             feats = [x]
@@ -224,9 +240,10 @@ def gpu_checks(pp, bp, net, rep, bench):
             sr.process_device(d_in.data_ptr(), w, h, 3, d_out.data_ptr())
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t) / n
-        rep["c2_bench"] = {"ms_per_frame": dt * 1e3, "mpix_per_s": 33.1776 / dt, "frac_of_peak": 2544000 * 35853696 / dt / 2.5e15}
-        print("  C2 (1920x1080, tile 200, device-resident, %d steps): %.2f ms/frame = %.1f Mpix/s = %.1f %% of 2.5 PFLOP/s" % (
-            n, dt * 1e3, 33.1776 / dt, 100 * 2544000 * 35853696 / dt / 2.5e15))
+        flops = 2544000 * flop_per_px(sr.num_blocks)  # (2,544,000 padded LR pixels per C2 frame)
+        rep["c2_bench"] = {"ms_per_frame": dt * 1e3, "mpix_per_s": 33.1776 / dt, "frac_of_peak": flops / dt / 2.5e15}
+        print("  C2 (1920x1080, tile 200, device-resident, %d steps, %d blocks): %.2f ms/frame = %.1f Mpix/s = %.1f %% of 2.5 PFLOP/s" % (
+            n, sr.num_blocks, dt * 1e3, 33.1776 / dt, 100 * flops / dt / 2.5e15))
     sr.close()
     return ok
 
