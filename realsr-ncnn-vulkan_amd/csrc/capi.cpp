@@ -269,75 +269,63 @@ long long rsr_image_span(int fmt, int w, int h, int c, long long row_pitch, long
     long long row = 0, plane = 0;
     const int rc = rsr::image_layout(fmt, w, h, c, row_pitch, plane_pitch, &row, &plane);
     if (rc != RSR_OK) return rc;
-    // all pitches are positive: the last element of the last row of the last plane lies farthest from `data`
-    if (rsr::fmt_is_semiplanar(fmt)) // (the UV plane: h / 2 rows as long as a Y row, h of them at 4:2:2; planar 4:4:4: three planes, below)
-        return plane + (long long)((rsr::fmt_is_422(fmt) ? h : h / 2) - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
-    return (fmt == RSR_FMT_U8_HWC ? 0 : 2 * plane) + (long long)(h - 1) * row + (long long)w * rsr::BatchIO::px_bytes(fmt, c);
+    // all pitches are positive: the last element of the last row of the last plane lies farthest from `data` (a chroma plane has h >> csy rows)
+    const rsr::PixFmt f = rsr::pix_fmt(fmt, c);
+    return (f.planes - 1) * plane + (long long)((h >> f.csy) - 1) * row + (long long)w * f.es;
 }
 
 long long rsr_image_bytes(int fmt, int w, int h, int c)
 {
     if (w < 1 || h < 1) return Engine::fail(RSR_E_ARG, "bad image size");
-    const long long px = (long long)w * h;
-    if (fmt == RSR_FMT_U8_HWC && (c == 3 || c == 4)) return px * c;
-    if (fmt == RSR_FMT_F16_CHW && c == 3) return px * 6;
-    if (fmt == RSR_FMT_F32_CHW && c == 3) return px * 12;
-    if (rsr::fmt_is_444(fmt) && c == 3) return fmt == RSR_FMT_YUV444P ? px * 3 : px * 6;
-    if (rsr::fmt_is_422(fmt) && c == 3)
-    {
-        if (w & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:2 surface needs an even width");
-        return fmt == RSR_FMT_NV16 ? px * 2 : px * 4;
-    }
-    if (rsr::fmt_is_semiplanar(fmt) && c == 3)
-    {
-        if ((w | h) & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
-        return fmt == RSR_FMT_NV12 ? px * 3 / 2 : px * 3;
-    }
-    return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
+    const rsr::PixFmt f = rsr::pix_fmt(fmt, c);
+    if (!f.takes(c)) return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
+    if (const int rc = rsr::parity_check(f, w, h, "surface")) return rc;
+    return f.rows(h) * w * f.es;
 }
+
+static const char* const kBadRatio = "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4";
+static const char* const kBadRatioXY = "output ratios must reduce per axis to n / d with d in 1 .. 8 and 1 <= n / d <= 4";
 
 int rsr_set_out_ratio(rsr_ctx* ctx, int num, int den)
 {
     if (!ctx) return RSR_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->e.mu);
     rsr::OutRatio r;
-    if (!rsr::out_ratio_reduce(num, den, &r)) return ctx->e.fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
+    if (!rsr::out_ratio_reduce(num, den, &r)) return ctx->e.fail(RSR_E_ARG, kBadRatio);
     ctx->e.out_ratio = r; // the next call's output is (w * n / d) x (h * n / d): plans are keyed by it; 4 / 1, 2 / 1, 1 / 1 ARE option "out_scale"
+    return RSR_OK;
+}
+
+// What the size functions share behind the reduction of their ratio (`reduced`: it is a permitted one, else bad_ratio is the refusal):
+// the size limits, then out_admit in format f.  Two things differ between them and stay as they are:
+//   * rsr_out_size and rsr_out_size_yuv take denominators up to 4 (out_ratio_reduce), the _xy and _fmt forms up to 8 (out_ratio_reduce_xy);
+//   * a 4:2:0 output (rsr_out_size_yuv*, NV12 / P010 of rsr_out_size_fmt) also refuses an odd INPUT w or h: its input is a 4:2:0 surface
+//     too.  A 4:2:2 output does not ask for an even input w: its input may be any format.
+static int out_size(bool reduced, const char* bad_ratio, const rsr::PixFmt& f, const rsr::OutRatio& r, rsr::OutWho who, int tilesize, int w, int h, int* ow, int* oh)
+{
+    if (!reduced) return Engine::fail(RSR_E_ARG, bad_ratio);
+    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
+    if (f.csy)
+        if (const int rc = rsr::parity_check(f, w, h, "surface")) return rc;
+    if (const int rc = rsr::out_admit(f, w, h, tilesize, r, who)) return rc;
+    if (ow) *ow = int(r.of_x(w));
+    if (oh) *oh = int(r.of_y(h));
     return RSR_OK;
 }
 
 int rsr_out_size(int num, int den, int tilesize, int w, int h, int* ow, int* oh)
 {
     rsr::OutRatio r;
-    if (!rsr::out_ratio_reduce(num, den, &r)) return Engine::fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
-    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
-    if (!r.divides_x(w) || !r.divides_y(h) || !r.divides_x(tilesize))
-        return Engine::fail(RSR_E_ARG, "output ratio " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + ": w, h and tilesize times " + std::to_string(r.nx) +
-                                           " must be multiples of " + std::to_string(r.dx));
-    if (ow) *ow = int(r.of_x(w));
-    if (oh) *oh = int(r.of_y(h));
-    return RSR_OK;
+    return out_size(rsr::out_ratio_reduce(num, den, &r), kBadRatio, rsr::pix_fmt(RSR_FMT_U8_HWC), r, rsr::kWhoOutSize, tilesize, w, h, ow, oh);
 }
 
 int rsr_out_size_yuv(int num, int den, int tilesize, int w, int h, int* ow, int* oh)
 {
     rsr::OutRatio r;
-    if (!rsr::out_ratio_reduce(num, den, &r)) return Engine::fail(RSR_E_ARG, "output ratio must reduce to n / d with d in 1 .. 4 and 1 <= n / d <= 4");
-    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
-    if ((w | h) & 1) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
-    const std::string what = "a YUV 4:2:0 output at ratio " + std::to_string(r.nx) + "/" + std::to_string(r.dx);
-    if (!r.divides_x(w) || !r.divides_y(h) || !r.divides_x(tilesize))
-        return Engine::fail(RSR_E_ARG, what + ": w, h and tilesize times " + std::to_string(r.nx) + " must be multiples of " + std::to_string(r.dx));
-    if (!rsr::yuv_out_even(r, w, h, tilesize))
-        return Engine::fail(RSR_E_ARG, what + " needs w, h and tilesize times " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + " even");
-    if (ow) *ow = int(r.of_x(w));
-    if (oh) *oh = int(r.of_y(h));
-    return RSR_OK;
+    return out_size(rsr::out_ratio_reduce(num, den, &r), kBadRatio, rsr::pix_fmt(RSR_FMT_NV12), r, rsr::kWhoOutSize, tilesize, w, h, ow, oh);
 }
 
 // ---- a ratio per axis (rsr_set_out_ratio_xy) ----------------------------------------------------------------------------------------
-static const char* const kBadRatioXY = "output ratios must reduce per axis to n / d with d in 1 .. 8 and 1 <= n / d <= 4";
-
 int rsr_set_out_ratio_xy(rsr_ctx* ctx, int num_x, int den_x, int num_y, int den_y)
 {
     if (!ctx) return RSR_E_ARG;
@@ -348,45 +336,22 @@ int rsr_set_out_ratio_xy(rsr_ctx* ctx, int num_x, int den_x, int num_y, int den_
     return RSR_OK;
 }
 
-// The admission rule of a pair, shared by the two size functions: RSR_OK and the reduced pair, or the refusal.
-// yuv: 0 = an RGB output, 1 = a YUV 4:2:0 output, 2 = a YUV 4:2:2 output (whose columns alone answer to a parity rule; its input may be any format,
-// so w and h themselves are not asked to be even).
-static int out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int yuv, int* ow, int* oh)
+int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
 {
+    const rsr::PixFmt f = rsr::pix_fmt(out_fmt);
+    if (!f.known()) return Engine::fail(RSR_E_ARG, "unknown pixel format");
     rsr::OutRatio r;
-    if (!rsr::out_ratio_reduce_xy(num_x, den_x, num_y, den_y, &r)) return Engine::fail(RSR_E_ARG, kBadRatioXY);
-    if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
-    if (yuv == 1 && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
-    const std::string what = std::string(yuv == 1 ? "a YUV 4:2:0 output at " : (yuv == 2 ? "a YUV 4:2:2 output at " : "")) + "output ratios " + r.str();
-    if (!r.divides_x(w) || !r.divides_x(tilesize) || !r.divides_y(h) || !r.divides_y(tilesize))
-        return Engine::fail(RSR_E_ARG, what + ": w and tilesize times " + std::to_string(r.nx) + " must be multiples of " + std::to_string(r.dx) + ", h and tilesize times " +
-                                           std::to_string(r.ny) + " multiples of " + std::to_string(r.dy));
-    if (yuv == 2 && !rsr::yuv422_out_even(r, w, tilesize))
-        return Engine::fail(RSR_E_ARG, what + " needs w and tilesize times " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + " even");
-    if (yuv == 1 && !rsr::yuv_out_even(r, w, h, tilesize))
-        return Engine::fail(RSR_E_ARG, what + " needs w and tilesize times " + std::to_string(r.nx) + "/" + std::to_string(r.dx) + " and h and tilesize times " +
-                                           std::to_string(r.ny) + "/" + std::to_string(r.dy) + " even");
-    if (ow) *ow = int(r.of_x(w));
-    if (oh) *oh = int(r.of_y(h));
-    return RSR_OK;
+    return out_size(rsr::out_ratio_reduce_xy(num_x, den_x, num_y, den_y, &r), kBadRatioXY, f, r, rsr::kWhoOutSizeXY, tilesize, w, h, ow, oh);
 }
 
 int rsr_out_size_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
 {
-    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 0, ow, oh);
+    return rsr_out_size_fmt(RSR_FMT_U8_HWC, num_x, den_x, num_y, den_y, tilesize, w, h, ow, oh);
 }
 
 int rsr_out_size_yuv_xy(int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
 {
-    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 1, ow, oh);
-}
-
-int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh)
-{
-    if (out_fmt == RSR_FMT_U8_HWC || out_fmt == RSR_FMT_F16_CHW || out_fmt == RSR_FMT_F32_CHW || rsr::fmt_is_444(out_fmt)) // (4:4:4: no pairs, no quads, no parity)
-        return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, 0, ow, oh);
-    if (!rsr::fmt_is_yuv(out_fmt)) return Engine::fail(RSR_E_ARG, "unknown pixel format");
-    return out_size_xy(num_x, den_x, num_y, den_y, tilesize, w, h, rsr::fmt_is_422(out_fmt) ? 2 : 1, ow, oh);
+    return rsr_out_size_fmt(RSR_FMT_NV12, num_x, den_x, num_y, den_y, tilesize, w, h, ow, oh);
 }
 
 int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n)

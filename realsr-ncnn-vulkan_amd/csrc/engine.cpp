@@ -1138,8 +1138,8 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     pa.bgr = bgr ? 1 : 0;
     pa.plane_ch = pc;
     pa.variant = variant;
-    if (fmt_is_yuv(io.in_fmt) && !yuv_coef(yuv_matrix, yuv_range, fmt_yuv_bits(io.in_fmt), &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
-    if (fmt_is_yuv(io.out_fmt) && !yuv_coef(yuv_matrix, yuv_range, fmt_yuv_bits(io.out_fmt), &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
+    if (const int bits = pix_fmt(io.in_fmt).bits; bits && !yuv_coef(yuv_matrix, yuv_range, bits, &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
+    if (const int bits = pix_fmt(io.out_fmt).bits; bits && !yuv_coef(yuv_matrix, yuv_range, bits, &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     pa.siting = po.siting = yuv_siting;
     launch_preproc_tiles(pa, max_tw, max_th, st);
     mark(0, 0, b.px[0] / per * BatchIO::image_px_bytes(io.in_fmt, c) + b.px[0] * 64, st);
@@ -1320,8 +1320,7 @@ int Engine::admit(int out_fmt, int w, int h, OutRatio os, bool enter) const
         if (out_ratio != os) return fail(RSR_E_STATE, "context parameters changed while the call was in flight");
     }
     if (w < 1 || h < 1) return RSR_OK;
-    if (const int rc = check_ratio_out(out_fmt, w, h, tilesize, os)) return rc;
-    return check_yuv_out(out_fmt, w, h, os);
+    return out_admit(pix_fmt(out_fmt), w, h, tilesize, os, kWhoEngine);
 }
 
 template <class Body> int Engine::on_stream(std::unique_lock<std::mutex>& lk, hipStream_t user_stream, bool sync, Body body)
@@ -1373,15 +1372,11 @@ template <class Body> int Engine::on_stream(std::unique_lock<std::mutex>& lk, hi
 int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, hipStream_t user_stream, bool sync, int in_fmt, int out_fmt)
 {
     if (!d_in || !d_out || w < 1 || h < 1 || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
-    for (const int f : {in_fmt, out_fmt})
-    {
-        if (f != RSR_FMT_U8_HWC && f != RSR_FMT_F16_CHW && f != RSR_FMT_F32_CHW && !fmt_is_yuv(f)) return fail(RSR_E_ARG, "unknown pixel format");
-        if (f != RSR_FMT_U8_HWC && c != 3) return fail(RSR_E_ARG, "the planar float and the YUV formats come with c == 3 only");
-    }
-    if (fmt_is_422(in_fmt) && (w & 1)) return fail(RSR_E_ARG, "a YUV 4:2:2 input needs an even width");
-    if (fmt_is_semiplanar(in_fmt) && !fmt_is_422(in_fmt) && ((w | h) & 1)) return fail(RSR_E_ARG, "a YUV 4:2:0 input needs an even width and height");
-    if ((fmt_is_yuv(in_fmt) && fmt_yuv_bits(in_fmt) > 8 && (reinterpret_cast<uintptr_t>(d_in) & 1)) ||
-        (fmt_is_yuv(out_fmt) && fmt_yuv_bits(out_fmt) > 8 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
+    const PixFmt fin = pix_fmt(in_fmt, c), fout = pix_fmt(out_fmt, c);
+    for (const PixFmt* f : {&fin, &fout})
+        if (const int rc = fmt_check(*f, c, "the planar float and the YUV formats come with c == 3 only")) return rc;
+    if (const int rc = parity_check(fin, w, h, "input")) return rc;
+    if ((fin.bits > 8 && (reinterpret_cast<uintptr_t>(d_in) & 1)) || (fout.bits > 8 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
         return fail(RSR_E_ARG, "P010 / P210 / YUV444P10 data is not aligned to its 16-bit samples");
     const bool u8 = in_fmt == RSR_FMT_U8_HWC && out_fmt == RSR_FMT_U8_HWC;
     if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
@@ -1395,7 +1390,7 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
             if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
             T = tilesize;
             os = out_ratio;
-            if (const int rc = check_ratio_out(out_fmt, w, h, T, os)) return rc;
+            if (const int rc = out_admit(fout, w, h, T, os, kWhoEngine)) return rc;
             width = merge_width(w, h, c);
             if (width > 1) items = image_items(w, h, merge_target_items);
         }
@@ -1449,51 +1444,6 @@ bool yuv_coef(int matrix, int range, int bits, YuvCoef* out)
     return true;
 }
 
-// A YUV output is written one 2 x 2 luma quad per thread, tile by tile: the image and every tile's rectangle must start and end on even
-// output pixels (only out_scale 1 can break that).  At a ratio n / d other than 4 / 2 / 1 (check_ratio_out has made w n / d, h n / d and
-// tilesize n / d whole) the same rule reads: those three are even (yuv_out_even, what rsr_out_size_yuv states) -- per axis where the axes
-// differ: w nx / dx, tilesize nx / dx, h ny / dy and tilesize ny / dy (rsr_out_size_yuv_xy).  mu held (tilesize).
-// A 4:2:2 output is written one 2 x 1 luma pair and its (U, V) at a time: the same rule for the COLUMNS alone -- w nx / dx and tilesize nx / dx
-// even -- and none for the rows (rsr_out_size_fmt).  A planar 4:4:4 output has no pairs and no quads, hence no rule here at all.
-int Engine::check_yuv_out(int out_fmt, int w, int h, OutRatio ratio) const
-{
-    if (!fmt_is_semiplanar(out_fmt)) return RSR_OK;
-    if (fmt_is_422(out_fmt))
-    {
-        if (ratio.is_box())
-        {
-            const int os = ratio.out_scale();
-            if (((w * os) | (tilesize * os)) & 1) return fail(RSR_E_ARG, "a YUV 4:2:2 output needs w * out_scale and tilesize * out_scale even");
-            return RSR_OK;
-        }
-        if (!yuv422_out_even(ratio, w, tilesize))
-            return fail(RSR_E_ARG, "a YUV 4:2:2 output at ratios " + ratio.str() + " needs w and tilesize times " + std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) +
-                                       " even (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(tilesize) + ")");
-        return RSR_OK;
-    }
-    if (ratio.is_box())
-    {
-        const int os = ratio.out_scale();
-        if (((w * os) | (h * os) | (tilesize * os)) & 1)
-            return fail(RSR_E_ARG, "a YUV 4:2:0 output needs w * out_scale, h * out_scale and tilesize * out_scale even");
-        return RSR_OK;
-    }
-    if (!yuv_out_even(ratio, w, h, tilesize))
-    {
-        if (!ratio.same())
-            return fail(RSR_E_ARG, "a YUV 4:2:0 output at ratios " + ratio.str() + " needs w and tilesize times " + std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) +
-                                       " and h and tilesize times " + std::to_string(ratio.ny) + "/" + std::to_string(ratio.dy) + " even (" + std::to_string(w) + " x " +
-                                       std::to_string(h) + " at tile " + std::to_string(tilesize) + ")");
-        return fail(RSR_E_ARG, "a YUV 4:2:0 output at ratio " + std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) + " needs w, h and tilesize times " +
-                                   std::to_string(ratio.nx) + "/" + std::to_string(ratio.dx) + " even (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " +
-                                   std::to_string(tilesize) + ")");
-    }
-    return RSR_OK;
-}
-
-bool yuv_out_even(OutRatio r, long long w, long long h, long long T) { return !((r.of_x(w) | r.of_y(h) | r.of_x(T) | r.of_y(T)) & 1); }
-bool yuv422_out_even(OutRatio r, long long w, long long T) { return !((r.of_x(w) | r.of_x(T)) & 1); }
-
 // ---- rational output scales (rsr_set_out_ratio, rsr_set_out_ratio_xy) ---------------------------------------------------------------------
 // num / den in lowest terms when den <= max_den and 1 <= num / den <= 4
 static bool axis_reduce(int num, int den, int max_den, int* n_out, int* d_out)
@@ -1523,40 +1473,62 @@ bool out_ratio_reduce_xy(int num_x, int den_x, int num_y, int den_y, OutRatio* o
     return true;
 }
 
-// An output pixel of scale n / d is a whole number of them only where the image's sides times n are multiples of d; and only where the
-// tile size times n is one too does every tile's rectangle start on a whole output pixel, so that no averaging footprint crosses a tile
-// (postproc_tiles_area is a per-tile launch).  Always true for 4, 2 and 1.  Checked before anything is launched.  With a ratio per axis
-// (rsr_set_out_ratio_xy) w and the tile size answer to the x ratio, h and the tile size to the y ratio.
-int Engine::check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const
+// ---- the rules of a pixel format (engine.h; kernels.h PixFmt) ----------------------------------------------------------------------------
+int fmt_check(const PixFmt& f, int c, const char* c_text)
 {
-    if (os.is_box()) return RSR_OK;
-    if (!os.divides_x(w) || !os.divides_y(h) || !os.divides_x(T) || !os.divides_y(T)) // (a YUV output: check_yuv_out then asks for even quotients as well)
-    {
-        if (!os.same())
-            return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_semiplanar(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratios " + os.str() + ": w and tilesize times " + std::to_string(os.nx) +
-                                       " must be multiples of " + std::to_string(os.dx) + ", h and tilesize times " + std::to_string(os.ny) + " multiples of " + std::to_string(os.dy) +
-                                       " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
-        return fail(RSR_E_ARG, std::string(fmt_is_422(out_fmt) ? "YUV 4:2:2 output at " : (fmt_is_semiplanar(out_fmt) ? "YUV 4:2:0 output at " : "")) + "output ratio " + std::to_string(os.nx) + "/" + std::to_string(os.dx) + ": w, h and tilesize times " + std::to_string(os.nx) +
-                                   " must be multiples of " + std::to_string(os.dx) + " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")");
-    }
-    return RSR_OK;
+    if (!f.known()) return Engine::fail(RSR_E_ARG, "unknown pixel format");
+    return f.takes(c) ? RSR_OK : Engine::fail(RSR_E_ARG, c_text);
+}
+
+int parity_check(const PixFmt& f, int w, int h, const char* noun)
+{
+    if (!f.odd(w, h)) return RSR_OK;
+    return Engine::fail(RSR_E_ARG, std::string("a ") + f.family + " " + noun + " needs an even width" + (f.csy ? " and height" : ""));
+}
+
+// The refusals of out_admit, worded as each caller always has.  One ratio on both axes reads "ratio n/d" and names w, h and tilesize
+// together; a pair -- and everything the _xy / _fmt size functions say, and the engine's word on 4:2:2 columns -- reads "ratios" and names
+// the axes apart.  The engine alone adds the sizes it was asked about.
+static std::string out_refusal(const PixFmt& f, int w, int h, int T, OutRatio r, OutWho who, bool parity)
+{
+    const std::string rx = std::to_string(r.nx) + "/" + std::to_string(r.dx), ry = std::to_string(r.ny) + "/" + std::to_string(r.dy), fam = f.family;
+    if (parity && who == kWhoEngine && r.is_box())
+        return "a " + fam + " output needs w * out_scale" + (f.csy ? ", h * out_scale" : "") + " and tilesize * out_scale even";
+    const bool axes = who == kWhoOutSizeXY || !r.same() || (parity && !f.csy);
+    std::string s = fam.empty() ? "" : (parity || who != kWhoEngine ? "a " : "") + fam + " output at ";
+    if (who == kWhoOutSizeXY || (!parity && (who == kWhoEngine || fam.empty()))) s += "output ";
+    s += axes ? "ratios " + r.str() : "ratio " + rx;
+    if (!parity)
+        s += axes ? ": w and tilesize times " + std::to_string(r.nx) + " must be multiples of " + std::to_string(r.dx) + ", h and tilesize times " + std::to_string(r.ny) +
+                        " multiples of " + std::to_string(r.dy)
+                  : ": w, h and tilesize times " + std::to_string(r.nx) + " must be multiples of " + std::to_string(r.dx);
+    else if (!f.csy) s += " needs w and tilesize times " + rx + " even";
+    else s += axes ? " needs w and tilesize times " + rx + " and h and tilesize times " + ry + " even" : " needs w, h and tilesize times " + rx + " even";
+    if (who == kWhoEngine) s += " (" + std::to_string(w) + " x " + std::to_string(h) + " at tile " + std::to_string(T) + ")";
+    return s;
+}
+
+int out_admit(const PixFmt& f, int w, int h, int T, OutRatio r, OutWho who)
+{
+    if (!r.divides_x(w) || !r.divides_y(h) || !r.divides_x(T) || !r.divides_y(T)) return Engine::fail(RSR_E_ARG, out_refusal(f, w, h, T, r, who, false));
+    const long long quotients = (f.csx ? r.of_x(w) | r.of_x(T) : 0) | (f.csy ? r.of_y(h) | r.of_y(T) : 0); // of the subsampled axes
+    return quotients & 1 ? Engine::fail(RSR_E_ARG, out_refusal(f, w, h, T, r, who, true)) : RSR_OK;
 }
 
 // ---- tensor batches: n images of one geometry behind descriptors (include/realsr_hip.h rsr_process_device_batch) ------------------
 int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane)
 {
     if (w < 1 || h < 1) return Engine::fail(RSR_E_ARG, "bad image size");
-    if (fmt != RSR_FMT_U8_HWC && fmt != RSR_FMT_F16_CHW && fmt != RSR_FMT_F32_CHW && !fmt_is_yuv(fmt)) return Engine::fail(RSR_E_ARG, "unknown pixel format");
-    if (fmt == RSR_FMT_U8_HWC ? (c != 3 && c != 4) : c != 3) return Engine::fail(RSR_E_ARG, "no such pixel format / channel count");
-    if (fmt_is_422(fmt) && (w & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:2 surface needs an even width");
-    if (fmt_is_semiplanar(fmt) && !fmt_is_422(fmt) && ((w | h) & 1)) return Engine::fail(RSR_E_ARG, "a YUV 4:2:0 surface needs an even width and height");
+    const PixFmt f = pix_fmt(fmt, c);
+    if (const int rc = fmt_check(f, c)) return rc;
+    if (const int rc = parity_check(f, w, h, "surface")) return rc;
     if (row_pitch < 0 || plane_pitch < 0) return Engine::fail(RSR_E_ARG, "negative pitch");
-    const long long es = BatchIO::px_bytes(fmt, c), packed = w * es;
+    const long long es = f.es, packed = w * es;
     const long long rp = row_pitch ? row_pitch : packed;
     if (rp < packed) return Engine::fail(RSR_E_ARG, "row pitch below the bytes of a row");
     if (rp > 0x7fffffffll) return Engine::fail(RSR_E_ARG, "row pitch beyond 2^31 - 1 bytes");
     long long pp = 0;
-    if (fmt != RSR_FMT_U8_HWC)
+    if (f.planes > 1)
     {
         pp = plane_pitch ? plane_pitch : h * rp;
         if (rp % es || pp % es) return Engine::fail(RSR_E_ARG, "pitch is not a multiple of the element size");
@@ -1576,7 +1548,7 @@ int image_refs(int n, const rsr_image* im, int fmt, int w, int h, int c, const O
         if (!im[i].data) why = "null data pointer";
         else if ((rc = image_layout(fmt, iw, ih, c, im[i].row_pitch, im[i].plane_pitch, &out[i].row, &out[i].plane)) != RSR_OK) why = last_error();
         else if (w > (1 << 24) || h > (1 << 24)) why = "bad image size";
-        else if (reinterpret_cast<uintptr_t>(im[i].data) % uintptr_t(BatchIO::elem_bytes(fmt, c))) why = "data is not aligned to the element size";
+        else if (reinterpret_cast<uintptr_t>(im[i].data) % uintptr_t(pix_fmt(fmt, c).align())) why = "data is not aligned to the element size";
         if (why) return Engine::fail(RSR_E_ARG, what + (index0 >= 0 ? " " + std::to_string(index0 + i) : std::string()) + ": " + why);
         out[i].data = im[i].data;
     }
@@ -1657,30 +1629,47 @@ int Engine::process_device_batch(int n, const rsr_image* in, int in_fmt, int w, 
     });
 }
 
-// ---- which tiles changed (include/realsr_hip.h rsr_diff_tiles) ---------------------------------------------------------------------------
-// One memset and one launch on the caller's stream: the kernel touches neither the workspace nor anything of the calls in flight, so it needs
-// no ordering against the compute stream.  A null stream: the context's own, and the call waits.
-int Engine::diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, hipStream_t user_stream)
+// ---- which tiles changed (include/realsr_hip.h rsr_diff_tiles, rsr_diff_tiles_sequence) -------------------------------------------------
+// The n pairs (r[0], r[1]), (r[1], r[2]), ... of checked images (an r[0] without data: pair 0 has no predecessor and marks every tile):
+// one memset and one launch on the caller's stream -- the kernel touches neither the workspace nor anything of the calls in flight, so it
+// needs no ordering against the compute stream.  A null stream: the context's own, and the call waits.
+template <int N> static hipError_t diff_launch(int n, const ImageRef* r, int fmt, int w, int h, int c, int T, int P, uint8_t* d_masks, hipStream_t st)
 {
-    if (!a || !b || !d_mask) return fail(RSR_E_ARG, "bad image arguments");
-    ImageRef ra, rb;
-    if (const int rc = image_refs(1, a, fmt, w, h, c, nullptr, "image a", -1, &ra)) return rc;
-    if (const int rc = image_refs(1, b, fmt, w, h, c, nullptr, "image b", -1, &rb)) return rc;
-    DiffArgs da;
+    DiffArgs<N> da;
     std::memset(&da, 0, sizeof da);
-    da.a = static_cast<const uint8_t*>(ra.data), da.pitch_a = ra.row, da.plane_a = ra.plane;
-    da.b = static_cast<const uint8_t*>(rb.data), da.pitch_b = rb.row, da.plane_b = rb.plane;
-    da.fmt = fmt, da.w = w, da.h = h, da.c = c;
-    da.mask = d_mask;
+    for (int k = 0; k < n; k++)
+    {
+        DiffPair& p = da.pair[k];
+        p.a = static_cast<const uint8_t*>(r[k].data), p.pitch_a = r[k].row, p.plane_a = r[k].plane;
+        p.b = static_cast<const uint8_t*>(r[k + 1].data), p.pitch_b = r[k + 1].row, p.plane_b = r[k + 1].plane;
+    }
+    da.n = n, da.fmt = fmt, da.w = w, da.h = h, da.c = c;
+    da.T = T, da.P = P, da.nx = (w + T - 1) / T, da.ny = (h + T - 1) / T;
+    da.mask = d_masks;
+    return launch_diff_tiles(da, st);
+}
+
+int Engine::diff_pairs(int n, const ImageRef* r, int fmt, int w, int h, int c, uint8_t* d_masks, hipStream_t user_stream)
+{
     {
         std::lock_guard<std::mutex> lk(mu);
-        da.T = tilesize, da.P = prepadding;
-        da.nx = (w + da.T - 1) / da.T, da.ny = (h + da.T - 1) / da.T;
+        hipStream_t st = user_stream ? user_stream : stream;
         HIP_TRY(hipSetDevice(device));
-        HIP_TRY(launch_diff_tiles(da, user_stream ? user_stream : stream));
+        HIP_TRY(n == 1 ? diff_launch<1>(n, r, fmt, w, h, c, tilesize, prepadding, d_masks, st) // (one pair: the small argument block)
+                       : diff_launch<kMaxMerge>(n, r, fmt, w, h, c, tilesize, prepadding, d_masks, st));
     }
     if (!user_stream) HIP_TRY(hipStreamSynchronize(stream));
     return RSR_OK;
+}
+
+// rsr_diff_tiles is the sequence of one pair, with `a` as the predecessor.
+int Engine::diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, hipStream_t user_stream)
+{
+    if (!a || !b || !d_mask) return fail(RSR_E_ARG, "bad image arguments");
+    ImageRef r[2];
+    if (const int rc = image_refs(1, a, fmt, w, h, c, nullptr, "image a", -1, &r[0])) return rc;
+    if (const int rc = image_refs(1, b, fmt, w, h, c, nullptr, "image b", -1, &r[1])) return rc;
+    return diff_pairs(1, r, fmt, w, h, c, d_mask, user_stream);
 }
 
 // ---- frame sequences (include/realsr_hip.h "frame sequences") ------------------------------------------------------------------------------
@@ -1702,53 +1691,33 @@ int sequence_sources(int n, int ntiles, const uint8_t* masks, int has_prev, int*
 }
 
 // diff_tiles for the n consecutive pairs (prev, frames[0]), (frames[0], frames[1]), ...: every descriptor is checked as diff_tiles checks
-// its two, then one memset and one launch.
+// its two.
 int Engine::diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image* prev, int fmt, int w, int h, int c, uint8_t* d_masks, hipStream_t user_stream)
 {
     if (n < 1 || n > kMaxMerge || !frames || !d_masks) return fail(RSR_E_ARG, "bad image arguments");
-    ImageRef r[kMaxMerge + 1]; // r[0]: prev (no predecessor: pair 0 keeps its null `a`), r[k + 1]: frame k
+    ImageRef r[kMaxMerge + 1]; // r[0]: prev (none: it stays without data), r[k + 1]: frame k
     if (prev)
         if (const int rc = image_refs(1, prev, fmt, w, h, c, nullptr, "previous frame", -1, &r[0])) return rc;
     if (const int rc = image_refs(n, frames, fmt, w, h, c, nullptr, "image", 0, &r[1])) return rc;
-    DiffSeqArgs da;
-    std::memset(&da, 0, sizeof da);
-    for (int k = 0; k < n; k++)
-    { // pair k: (frame k - 1 or prev, frame k)
-        DiffPair& p = da.pair[k];
-        p.a = static_cast<const uint8_t*>(r[k].data), p.pitch_a = r[k].row, p.plane_a = r[k].plane;
-        p.b = static_cast<const uint8_t*>(r[k + 1].data), p.pitch_b = r[k + 1].row, p.plane_b = r[k + 1].plane;
-    }
-    da.n = n, da.fmt = fmt, da.w = w, da.h = h, da.c = c;
-    da.mask = d_masks;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        da.T = tilesize, da.P = prepadding;
-        da.nx = (w + da.T - 1) / da.T, da.ny = (h + da.T - 1) / da.T;
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(launch_diff_tiles_seq(da, user_stream ? user_stream : stream));
-    }
-    if (!user_stream) HIP_TRY(hipStreamSynchronize(stream));
-    return RSR_OK;
+    return diff_pairs(n, r, fmt, w, h, c, d_masks, user_stream);
 }
 
-// The byte rectangles of output tile `tile` of an os.of_x(w) x os.of_y(h) image in out_fmt, from the image `src` to the image `dst`: one for
-// uint8 HWC, three for the planar formats, Y and UV for the surfaces (the UV rectangle has the byte columns of the Y rectangle and half its
-// rows; check_yuv_out has made its edges even -- a 4:2:2 surface: the tile's own rows, and only its columns are even).  A planar 4:4:4
-// surface is three planes like the planar float formats.
+// The byte rectangles of output tile `tile` of an os.of_x(w) x os.of_y(h) image in out_fmt, from the image `src` to the image `dst`: one per
+// plane of the format, plane q at q * plane pitch, all with the byte columns of the first; a subsampled chroma plane (the UV plane of a
+// 4:2:0 surface) has half the rows -- out_admit has made the tile's edges even on that axis.
 static void output_rects(int out_fmt, int w, int h, int c, int T, OutRatio os, int tile, const ImageRef& dst, const ImageRef& src, std::vector<PropRect>& out)
 {
     uint8_t* const db = static_cast<uint8_t*>(const_cast<void*>(dst.data));
     const uint8_t* const sb = static_cast<const uint8_t*>(src.data);
-    const long long dp = dst.row, dpl = dst.plane, sp = src.row, spl = src.plane;
+    const PixFmt f = pix_fmt(out_fmt, c);
     const int nx = (w + T - 1) / T, yi = tile / nx, xi = tile - yi * nx;
-    const long long es = BatchIO::px_bytes(out_fmt, c);
     const long long x0 = os.of_x((long long)xi * T), y0 = os.of_y((long long)yi * T), x1 = os.of_x(std::min((xi + 1) * T, w)), y1 = os.of_y(std::min((yi + 1) * T, h));
-    const int width = int((x1 - x0) * es), rows = int(y1 - y0);
-    const int nplanes = out_fmt == RSR_FMT_U8_HWC || fmt_is_semiplanar(out_fmt) ? 1 : 3;
-    for (int q = 0; q < nplanes; q++)
-        out.push_back(PropRect{db + q * dpl + y0 * dp + x0 * es, sb + q * spl + y0 * sp + x0 * es, dp, sp, width, rows});
-    if (fmt_is_422(out_fmt)) out.push_back(PropRect{db + dpl + y0 * dp + x0 * es, sb + spl + y0 * sp + x0 * es, dp, sp, width, rows});
-    else if (fmt_is_semiplanar(out_fmt)) out.push_back(PropRect{db + dpl + y0 / 2 * dp + x0 * es, sb + spl + y0 / 2 * sp + x0 * es, dp, sp, width, rows / 2});
+    const int width = int((x1 - x0) * f.es), rows = int(y1 - y0);
+    for (int q = 0; q < f.planes; q++)
+    {
+        const int cs = q ? f.csy : 0;
+        out.push_back(PropRect{db + q * dst.plane + (y0 >> cs) * dst.row + x0 * f.es, sb + q * src.plane + (y0 >> cs) * src.row + x0 * f.es, dst.row, src.row, width, rows >> cs});
+    }
 }
 
 int Engine::process_device_sequence(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, const rsr_image* prev_out,
@@ -2073,7 +2042,7 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
         if (scale != 4) return fail(RSR_E_ARG, "only scale 4 is supported (main.cpp:533-537)");
         T = tilesize;
         os = out_ratio;
-        if (const int rrc = check_ratio_out(RSR_FMT_U8_HWC, w, h, T, os)) return rrc;
+        if (const int rrc = out_admit(pix_fmt(RSR_FMT_U8_HWC), w, h, T, os, kWhoEngine)) return rrc;
         mwidth = merge_width(w, h, c);
         if (mwidth > 1) mitems = image_items(w, h, merge_target_items);
     }
@@ -2126,7 +2095,7 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
     // of a 4K frame does not allocate 398 MB for it): the kernels get the address row 0 would have and only ever write
     // inside the rectangles of the range's tiles (conv_last / postproc_tiles place by tile), i.e. inside the allocation.
     const size_t rowbytes = size_t(os.of_x(w)) * c; // one output row
-    auto yof = [&](int tr) { return size_t(os.of_y(std::min(tr * T, h))); };  // first output row of tile row tr (whole: check_ratio_out)
+    auto yof = [&](int tr) { return size_t(os.of_y(std::min(tr * T, h))); };  // first output row of tile row tr (whole: out_admit)
     auto xof = [&](int tc) { return size_t(os.of_x(std::min(tc * T, w))) * c; }; // byte column of tile column tc
     const int r0 = tile0 / xtiles, c0 = tile0 % xtiles, r1 = (tile1 - 1) / xtiles, c1 = (tile1 - 1) % xtiles + 1; // last tile = (r1, c1 - 1)
     const size_t base_off = yof(r0) * rowbytes;

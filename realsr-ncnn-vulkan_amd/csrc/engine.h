@@ -64,11 +64,20 @@ struct OutRatio
 bool out_ratio_reduce(int num, int den, OutRatio* out);
 // Host-only: the pair reduced per axis when each axis is one of the permitted ratios of rsr_set_out_ratio_xy (d in 1..8, 1 <= n / d <= 4).
 bool out_ratio_reduce_xy(int num_x, int den_x, int num_y, int den_y, OutRatio* out);
-// Host-only: are w nx / dx, T nx / dx, h ny / dy and T ny / dy (whole: OutRatio::divides_*) all even -- what a YUV 4:2:0 output asks of
-// image and tile size?
-bool yuv_out_even(OutRatio r, long long w, long long h, long long T);
-// ... and what a 4:2:2 output asks: w nx / dx and T nx / dx even (its chroma is halved along x only: the two row quotients are any).
-bool yuv422_out_even(OutRatio r, long long w, long long T);
+// Host-only, the rules of a pixel format (kernels.h PixFmt), each RSR_OK or RSR_E_ARG through Engine::fail.
+// fmt_check: is it a format at all ("unknown pixel format"), and does it come with c channels (c_text)?
+int fmt_check(const PixFmt& f, int c, const char* c_text = "no such pixel format / channel count");
+// parity_check: w (h) of a surface is even on every axis its chroma is subsampled on; `noun`: what the message calls the image.
+int parity_check(const PixFmt& f, int w, int h, const char* noun);
+// out_admit, THE output admission rule: may a w x h image at tile size T leave in format f at ratio r?  The ratio rule: w and T times
+// nx / dx, h and T times ny / dy are whole -- an output pixel is a whole number of them only where the image's sides times n are multiples
+// of d, and only where the tile size times n is one too does every tile's rectangle start on a whole output pixel, so that no averaging
+// footprint crosses a tile (postproc_tiles_area is a per-tile launch); always true at 4, 2 and 1.  On every axis the format's chroma is
+// subsampled on, the parity rule on top: those quotients are even -- a YUV output is written one 2 x 2 luma quad (4:2:0) or one 2 x 1 pair
+// (4:2:2: the columns alone answer to it) per thread, tile by tile, so the image and every tile's rectangle start and end on even output
+// pixels; at out_scale 4 / 2 / 1 that reads w * os, h * os and T * os even.  `who` words the refusal as its caller always has.
+enum OutWho { kWhoOutSize, kWhoOutSizeXY, kWhoEngine }; // rsr_out_size / _yuv; the _xy and _fmt size functions; the engine (adds "(w x h at tile T)")
+int out_admit(const PixFmt& f, int w, int h, int T, OutRatio r, OutWho who);
 
 struct DevBuf
 {
@@ -220,18 +229,14 @@ struct BatchIO
         for (int i = 0; i < n; i++) set(i, g[i]->d_in, g[i]->d_out, g[i]->w, g[i]->h);
     }
     BatchIO(int n, int c0, int in_fmt0, int out_fmt0, OutRatio os0) : nimg(n), c(c0), os(os0), in_fmt(in_fmt0), out_fmt(out_fmt0) {} // the caller calls set() n times
-    static long long px_bytes(int fmt, int c) // of one element of a row (a YUV surface: of one sample; a UV row has as many bytes as a Y row)
-    {
-        return fmt == RSR_FMT_F16_CHW ? 2 : (fmt == RSR_FMT_F32_CHW ? 4 : (fmt_is_yuv(fmt) ? (fmt_yuv_bits(fmt) + 7) / 8 : c));
-    }
-    static long long elem_bytes(int fmt, int c) { return fmt == RSR_FMT_U8_HWC ? 1 : px_bytes(fmt, c); } // what `data` and the pitches of a descriptor must be multiples of
     static double image_px_bytes(int fmt, int c) // bytes of one PIXEL of a whole image: c for uint8 HWC, 3 halfs / floats, 1.5 samples of a 4:2:0 surface, 2 of a 4:2:2, 3 of a 4:4:4 one
     {
-        return double(px_bytes(fmt, c)) * (fmt_is_422(fmt) ? 2.0 : (fmt_is_semiplanar(fmt) ? 1.5 : (fmt == RSR_FMT_U8_HWC ? 1.0 : 3.0)));
+        const PixFmt f = pix_fmt(fmt, c);
+        return double(f.rows(2) * f.es) / 2; // (two rows: the smallest height every format takes)
     }
     static ImageRef packed(const void* data, int fmt, long long wi, long long hi, int c) // a tightly packed wi x hi image
     {
-        const long long row = wi * px_bytes(fmt, c);
+        const long long row = wi * pix_fmt(fmt, c).es; // (a UV row has as many bytes as a Y row)
         return ImageRef{data, row, hi * row};
     }
     void set(int i, const ImageRef& src, const ImageRef& dst, int wi, int hi) // image i: wi x hi behind src, its x os result behind dst
@@ -409,6 +414,7 @@ struct Engine
                              const uint8_t* mask = nullptr, int nmask = 0);
     // mask[t] = do the images a and b differ inside tile t's source rectangle (include/realsr_hip.h rsr_diff_tiles); d_mask: device, one byte per tile
     int diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, int h, int c, uint8_t* d_mask, hipStream_t user_stream);
+    int diff_pairs(int n, const ImageRef* r, int fmt, int w, int h, int c, uint8_t* d_masks, hipStream_t user_stream); // what the two diffs share: the launch for checked images r[0 .. n]
     // Frame sequences (include/realsr_hip.h "frame sequences").  diff_tiles_sequence: row k of d_masks = diff_tiles(frames[k - 1], frames[k]), row 0
     // against prev (null: all ones); one memset, one launch.  process_device_sequence: the tiles of in[k] whose mask byte is set walk the
     // network as shared tile batches (enqueue_sequence); every other output rectangle is copied from the frame that computed it last, or
@@ -430,7 +436,7 @@ struct Engine
     // ---- internals (call with `mu` held unless noted) ----
     static constexpr int plane_ch() { return kPlaneCh; }
     // The call skeleton of the device entry points (DESIGN.md "The call skeleton of a device entry point"): image_refs, admit, on_stream.
-    // admit: may a w x h image leave in out_fmt at output ratio os -- check_ratio_out, check_yuv_out (a w or h below 1 is left to the
+    // admit: may a w x h image leave in out_fmt at output ratio os -- out_admit (a w or h below 1 is left to the
     // descriptor check) --; with `enter`, the call is about to enqueue: before those, is a model loaded, the scale 4, and os still the
     // ratio in force (the descriptors were checked against os in front of the lock).
     int admit(int out_fmt, int w, int h, OutRatio os, bool enter) const;
@@ -453,8 +459,6 @@ struct Engine
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
     // no TTA merge / alpha channel / box reduction / YUV surface needs the planar blob (dbg 8192: off)
     bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
-    int check_yuv_out(int out_fmt, int w, int h, OutRatio os) const; // RSR_E_ARG when a chroma quad (4:2:0) / pair (4:2:2) of a YUV output would cross the image or a tile
-    int check_ratio_out(int out_fmt, int w, int h, int T, OutRatio os) const; // RSR_E_ARG when w, h or the tile size T times os is no whole number of pixels (no lock needed)
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
     // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).
@@ -504,7 +508,7 @@ struct Engine
 int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long plane_pitch, long long* row, long long* plane);
 // Host-only: THE descriptor check of the device entry points.  im[0 .. n) describe images of one format and geometry: w x h x c, or with
 // os the os->of(w) x os->of(h) results of such images.  Per descriptor, in this order: a null `data`, image_layout, w or h beyond 2^24 (of
-// the input geometry: what the kernels' tile coordinates hold), `data` no multiple of BatchIO::elem_bytes.  out[i] receives the resolved
+// the input geometry: what the kernels' tile coordinates hold), `data` no multiple of PixFmt::align.  out[i] receives the resolved
 // image; a refusal is RSR_E_ARG (through Engine::fail), its message led by `what` (+ " <index0 + i>" where index0 >= 0).
 int image_refs(int n, const rsr_image* im, int fmt, int w, int h, int c, const OutRatio* os, const char* what, int index0, ImageRef* out);
 // Host-only (include/realsr_hip.h rsr_sequence_sources): src[k * ntiles + t] = the frame whose computed rectangle output tile t of frame k

@@ -407,7 +407,7 @@ int rsr_process_group(rsr_ctx* const* ctx, int n, const uint8_t* in, int w, int 
         else if (e.nb != NB) // the shares of one image must come from one network
             return Engine::fail(RSR_E_ARG, "group members hold models of different depth (" + std::to_string(NB) + " and " + std::to_string(e.nb) + " RRDB blocks)");
     }
-    if (const int rrc = ctx[0]->e.check_ratio_out(RSR_FMT_U8_HWC, w, h, T, OS)) return rrc; // (before any share has written a rectangle)
+    if (const int rrc = out_admit(pix_fmt(RSR_FMT_U8_HWC), w, h, T, OS, kWhoEngine)) return rrc; // (before any share has written a rectangle)
     const int xtiles = (w + T - 1) / T, ytiles = (h + T - 1) / T, ntiles = xtiles * ytiles;
     const int parts = std::min(n, ntiles);
     if (parts == 1) return ctx[0]->e.process_host(in, w, h, c, out);

@@ -43,19 +43,50 @@ constexpr int kFmtNV12 = 4, kFmtP010 = 5;
 // YUV 4:2:2 surfaces, what broadcast and archive codecs hold (RSR_FMT_NV16 / RSR_FMT_P210): the same two planes, but chroma is halved
 // horizontally only -- the UV plane is [h][w/2][2], one UV row per Y row.  w is even; h is any.
 constexpr int kFmtNV16 = 8, kFmtP210 = 9;
-constexpr bool fmt_is_422(int fmt) { return fmt == kFmtNV16 || fmt == kFmtP210; }
 // Planar YUV 4:4:4, what screen recordings, mezzanine masters and software video frameworks hold (RSR_FMT_YUV444P / RSR_FMT_YUV444P10,
 // yuv444p / yuv444p10le): three full planes Y, U, V [h][w] one plane pitch apart -- the LAYOUT of the planar float formats with a YUV
 // colour model.  uint8 codes, or uint16 words that hold a 10-bit code in their LOW bits.  No pairs, no quads: w and h are any.
 constexpr int kFmtYUV444P = 12, kFmtYUV444P10 = 13;
-constexpr bool fmt_is_444(int fmt) { return fmt == kFmtYUV444P || fmt == kFmtYUV444P10; }
-// Two questions that had one answer until 4:4:4 came.  fmt_is_semiplanar: is it a Y plane followed by ONE plane of interleaved, subsampled
-// (U, V) pairs -- the geometry behind the pair / quad units, the parity rules and the second rectangle of the diff and of the sequence copy?
-// fmt_is_yuv: does it hold Y'CbCr codes -- the colour model: YuvCoef, the decode in front of the network, the encode behind conv_last?
-constexpr bool fmt_is_semiplanar(int fmt) { return fmt == kFmtNV12 || fmt == kFmtP010 || fmt_is_422(fmt); }
-constexpr bool fmt_is_yuv(int fmt) { return fmt_is_semiplanar(fmt) || fmt_is_444(fmt); }
-// of a YUV format: the code's bits (10: uint16 words -- code << 6 in a semi-planar surface, the plain code in a planar 4:4:4 one)
-constexpr int fmt_yuv_bits(int fmt) { return fmt == kFmtP010 || fmt == kFmtP210 || fmt == kFmtYUV444P10 ? 10 : 8; }
+
+// What a pixel format IS, said once: sizes, parity rules, admission rules and byte rectangles on the host, the rectangle selection of the
+// diff kernel on the device, all read these fields.  A new format is one more case of pix_fmt.
+struct PixFmt
+{
+    int es;             // bytes of one element of a row: c for uint8 HWC, elsewhere of one sample / half / float; 0 = no such format
+    int planes;         // planes addressed through the plane pitch: 1 (uint8 HWC), 2 (Y, then UV) or 3
+    bool pairs;         // plane 1 holds interleaved (U, V) pairs (the semi-planar surfaces: the geometry behind the pair / quad units) ...
+    int csx, csy;       // ... the chroma shift of that plane along x and y: 1, 1 at 4:2:0; 1, 0 at 4:2:2; 0, 0 everywhere else
+    int bits;           // of a Y'CbCr code (the colour model: YuvCoef, the decode in front of the network, the encode behind conv_last); 0 = RGB
+    bool high;          // a 10-bit code sits in the HIGH bits of its 16-bit word (code << 6), not in the low ones
+    int cmax;           // channel counts admitted: 3 .. cmax
+    const char* family; // as the messages name it: "YUV 4:2:0", "YUV 4:2:2", else ""
+    constexpr bool known() const { return es != 0; }
+    constexpr bool takes(int c) const { return c >= 3 && c <= cmax; }
+    constexpr int align() const { return planes == 1 ? 1 : es; }                            // what `data` and the pitches of a descriptor must be multiples of
+    constexpr long long rows(long long h) const { return h + (planes - 1) * (h >> csy); } // rows of all planes of an image h rows high, each w * es bytes
+    constexpr bool odd(long long w, long long h) const { return ((w & csx) | (h & csy)) != 0; } // w or h breaks the parity rule of a subsampled axis
+};
+constexpr __host__ __device__ PixFmt pix_fmt(int fmt, int c = 3)
+{
+    switch (fmt)
+    {
+    case kFmtU8: return {c, 1, false, 0, 0, 0, false, 4, ""};
+    case kFmtF16: return {2, 3, false, 0, 0, 0, false, 3, ""};
+    case kFmtF32: return {4, 3, false, 0, 0, 0, false, 3, ""};
+    case kFmtNV12: return {1, 2, true, 1, 1, 8, false, 3, "YUV 4:2:0"};
+    case kFmtP010: return {2, 2, true, 1, 1, 10, true, 3, "YUV 4:2:0"};
+    case kFmtNV16: return {1, 2, true, 1, 0, 8, false, 3, "YUV 4:2:2"};
+    case kFmtP210: return {2, 2, true, 1, 0, 10, true, 3, "YUV 4:2:2"};
+    case kFmtYUV444P: return {1, 3, false, 0, 0, 8, false, 3, ""};
+    case kFmtYUV444P10: return {2, 3, false, 0, 0, 10, false, 3, ""};
+    default: return {0, 0, false, 0, 0, 0, false, 0, ""};
+    }
+}
+// readers of it, where a name reads better than a field (the template dispatch of launch_preproc_tiles / launch_postproc_tiles)
+constexpr bool fmt_is_422(int fmt) { return pix_fmt(fmt).csx && !pix_fmt(fmt).csy; }
+constexpr bool fmt_is_444(int fmt) { return pix_fmt(fmt).bits && !pix_fmt(fmt).pairs; }
+constexpr bool fmt_is_yuv(int fmt) { return pix_fmt(fmt).bits != 0; }
+constexpr int fmt_yuv_bits(int fmt) { return pix_fmt(fmt).bits; }
 // Every image is addressed through its own ROW PITCH and (planar formats) PLANE PITCH, both in BYTES (rsr_image of the C ABI): a crop of
 // a larger frame, a window of a canvas.  A uint8 pitch need not be a multiple of the pixel size and a base pointer is aligned to the
 // element only, so the image accesses are element-sized (the LDS-staged pre / post kernels, which move dwords, align by themselves or
@@ -186,7 +217,7 @@ struct PreArgs
 {
     const uint8_t* imgs[kMaxMerge]; // HWC u8, one per image of the batch (ws[i] x hs[i] x c); BaseTile::img selects
     int fmt;                        // kFmtU8, or kFmtF16 / kFmtF32: the images are planar [3][hs[i]][ws[i]] of that type (c == 3),
-                                    // or a YUV surface (fmt_is_yuv): Y at imgs[i], UV plane[i] bytes behind it (planar 4:4:4: U, then V another
+                                    // or a YUV surface (PixFmt::bits): Y at imgs[i], UV plane[i] bytes behind it (planar 4:4:4: U, then V another
                                     // plane[i] behind), decoded with `yuv`; bgr does not apply
     int ws[kMaxMerge], hs[kMaxMerge];
     int pitch[kMaxMerge];           // bytes from one row of image i to the next (>= ws[i] * pixel size) ...
@@ -218,7 +249,7 @@ struct PostArgs
     int crop;   // prepadding*scale
     uint8_t* outs[kMaxMerge]; // HWC u8 (4w x 4h x c), one per image of the batch
     int out_fmt;              // kFmtU8, or kFmtF16 / kFmtF32: the outs are planar [3][4h][4w] of that type (c == 3; see ConvArgs::out_fmt),
-                              // or a YUV surface (fmt_is_yuv): Y at outs[i], UV out_plane[i] bytes behind it (postproc_tiles_yuv; box 0 / 1, 2 and 4 alike;
+                              // or a YUV surface (PixFmt::bits): Y at outs[i], UV out_plane[i] bytes behind it (postproc_tiles_yuv; box 0 / 1, 2 and 4 alike;
                               // planar 4:4:4: the planes Y, U, V out_plane[i] apart, postproc_tiles_yuv444)
     long long out_plane[kMaxMerge]; // planar formats: bytes from one plane of `outs[i]` to the next
     int out_pitch[kMaxMerge]; // row pitches of the outs in bytes
@@ -254,7 +285,7 @@ struct PostArgs
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 
-// ---- frame diff per tile (rsr_diff_tiles) -----------------------------------------------------
+// ---- frame diff per tile, frame sequences (rsr_diff_tiles, rsr_diff_tiles_sequence, rsr_process_device_sequence) --------------------
 // The SOURCE RECTANGLE of tile (yi, xi) of a w x h image at tile size T and prepadding P: the image pixels its padded tile reads, i.e. the
 // padded rectangle clipped to the image (reflect-101 never leaves it: the reflection of an index less than P outside an edge lies less
 // than P + 1 inside it).  Half-open, r = {x0, y0, x1, y1}.
@@ -266,38 +297,26 @@ __host__ __device__ inline void tile_source_rect(int w, int h, int T, int P, int
     r[2] = ex + P < w ? ex + P : w;
     r[3] = ey + P < h ? ey + P : h;
 }
-// mask[t] = 1 when any compared byte of tile t's source rectangle differs between the images a and b (one format and geometry, their own
-// pitches), else 0; include/realsr_hip.h rsr_diff_tiles says which bytes are compared.
-struct DiffArgs
-{
-    const uint8_t* a;
-    const uint8_t* b;
-    long long pitch_a, plane_a, pitch_b, plane_b; // bytes, resolved (plane: planar formats plane to plane; NV12 / P010: Y(0,0) to the UV plane)
-    int fmt, w, h, c;
-    int T, P, nx, ny; // tile size, prepadding, tile grid
-    uint8_t* mask;    // [ny * nx]
-};
-hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st); // the error of the memset or of the launch
-
-// ---- frame sequences (rsr_diff_tiles_sequence, rsr_process_device_sequence) --------------------
-// n pairs of images of ONE format and geometry in one launch: row k of mask [n][ny * nx] is what diff_tiles writes for pair k.  The pair
-// index travels in the grid; every pair brings its own two descriptors, by value.  A pair without an `a` (the first frame of a stream that
-// has no predecessor) marks every tile.
+// n pairs of images of ONE format and geometry in one launch.  mask[k][t] = 1 when any compared byte of tile t's source rectangle differs
+// between the images a and b of pair k (their own pitches), else 0; include/realsr_hip.h rsr_diff_tiles says which bytes are compared.  The
+// pair index travels in the grid; every pair brings its own two descriptors, by value.  A pair without an `a` (the first frame of a stream
+// that has no predecessor) marks every tile.  One kernel body for two sizes of its argument block: room for kMaxMerge pairs, and for ONE
+// (rsr_diff_tiles) -- a 10 us call pays measurably for 720 bytes of arguments it does not use (profiles/format_table.txt).
 struct DiffPair
 {
     const uint8_t* a; // null: every tile of this pair is marked
     const uint8_t* b;
-    long long pitch_a, plane_a, pitch_b, plane_b; // as DiffArgs
+    long long pitch_a, plane_a, pitch_b, plane_b; // bytes, resolved (plane: from one plane to the next; a surface: Y(0,0) to the UV plane)
 };
-struct DiffSeqArgs
+template <int N> struct DiffArgs // N: 1 or kMaxMerge
 {
-    DiffPair pair[kMaxMerge];
-    int n;
+    DiffPair pair[N];
+    int n;            // <= N
     int fmt, w, h, c;
-    int T, P, nx, ny;
-    uint8_t* mask; // [n][ny * nx]
+    int T, P, nx, ny; // tile size, prepadding, tile grid
+    uint8_t* mask;    // [n][ny * nx]
 };
-hipError_t launch_diff_tiles_seq(const DiffSeqArgs& a, hipStream_t st); // the error of the memset or of the launch
+template <int N> hipError_t launch_diff_tiles(const DiffArgs<N>& a, hipStream_t st); // the error of the memset or of the launch
 
 // One rectangle of bytes to move: `rows` rows of `width` bytes, from src to dst, each with its own pitch, at any alignment.  The rectangles
 // of one launch never overlap one another's destinations, and no source is another rectangle's destination.

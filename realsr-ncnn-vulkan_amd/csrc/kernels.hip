@@ -1191,7 +1191,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
 
 // The sibling of postproc_tiles_yuv for the scales n / d that are not 4, 2 or 1: yuv_quad over QuadArea.  A tile's rectangle is
 // tilesize * n / d output pixels and starts at its multiples (per axis: tilesize * nx / dx columns, tilesize * ny / dy rows); the engine
-// admits the call only where those, w * nx / dx and h * ny / dy are even (check_yuv_out), so no quad crosses a tile or the image's edge.
+// admits the call only where those, w * nx / dx and h * ny / dy are even (out_admit), so no quad crosses a tile or the image's edge.
 // Lanes run along x.
 // VS = 0: a 4:2:2 surface -- w * nx / dx and tilesize * nx / dx are even, the two row counts are any (yuv_quad, rows).
 template <typename TP, typename TO, int SITE, int VS = 1>
@@ -1557,7 +1557,7 @@ void launch_zero_guards(void* first_guard, long long stride, long long count, hi
 }
 
 // =============================================================================================
-// frame diff per tile (rsr_diff_tiles): which tiles' source rectangles differ between two frames
+// frame diff per tile (rsr_diff_tiles, rsr_diff_tiles_sequence): which tiles' source rectangles differ between two frames
 // =============================================================================================
 constexpr int kDiffRows = 16; // rows of a rectangle per workgroup and step: 4 per wave, so that a 220-row tile spreads over 14 workgroups
 
@@ -1602,64 +1602,14 @@ __device__ __forceinline__ bool rows_differ(const uint8_t* pa, long long pitch_a
     return d;
 }
 
-// grid (tile, row chunk, rectangle): the compared bytes of a tile are 1 (uint8 HWC), 3 (the planes of a planar image) or 2 (Y, UV) byte
-// rectangles.  A workgroup that finds a difference stores the 1; the launch function zeroes the mask in front of the kernel.
-__global__ __launch_bounds__(256) void diff_tiles(const DiffArgs a)
+// n pairs of images at once (DiffArgs<1>: the one of rsr_diff_tiles), grid (tile, row chunk, pair * planes + plane): the compared bytes of a tile are one byte
+// rectangle per plane of the format (PixFmt::planes: uint8 HWC one, a surface Y and UV, a planar image three), the same columns and rows
+// in every plane but the UV plane of a surface.  A workgroup that finds a difference stores the 1 into row `pair` of the mask; the launch
+// function zeroes the mask in front of the kernel.
+template <int N> __global__ __launch_bounds__(256) void diff_tiles(const DiffArgs<N> a)
 {
-    const int tile = blockIdx.x, yi = tile / a.nx, xi = tile - yi * a.nx;
-    int r[4];
-    tile_source_rect(a.w, a.h, a.T, a.P, xi, yi, r);
-    const int rect = blockIdx.z;
-    const int es = a.fmt == kFmtF32 ? 4 : (a.fmt == kFmtF16 ? 2 : (a.fmt == kFmtU8 ? a.c : (fmt_yuv_bits(a.fmt) + 7) / 8)); // (a YUV surface: of one sample)
-    int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
-    long long off_a = 0, off_b = 0;
-    if (fmt_is_semiplanar(a.fmt)) // (a planar 4:4:4 surface: three planes like the planar float formats, below)
-    {
-        if (rect == 1)
-        { // the (U, V) pairs the decode of this rectangle reads: one chroma sample beyond its own, at every siting
-            const int cx0 = max((r[0] >> 1) - 1, 0), cx1 = min(((r[2] - 1) >> 1) + 1, a.w / 2 - 1);
-            bx0 = cx0 * 2 * es, bx1 = (cx1 + 1) * 2 * es;
-            if (!fmt_is_422(a.fmt)) y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1; // (4:2:2: the rectangle's own rows)
-            off_a = a.plane_a, off_b = a.plane_b;
-        }
-    }
-    else if (a.fmt != kFmtU8) off_a = rect * a.plane_a, off_b = rect * a.plane_b;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint8_t* const pa = a.a + off_a + bx0;
-    const uint8_t* const pb = a.b + off_b + bx0;
-    // the widest access EVERY row of the rectangle allows: both images' rows then reach its boundary after the same head
-    const unsigned mis = unsigned(reinterpret_cast<uintptr_t>(pa) ^ reinterpret_cast<uintptr_t>(pb)) | unsigned(a.pitch_a ^ a.pitch_b);
-    const int n = bx1 - bx0, ys = y0 + blockIdx.y * kDiffRows + wave, step = gridDim.y * kDiffRows;
-    bool d;
-    if (!(mis & 15)) d = rows_differ<uint4>(pa, a.pitch_a, pb, a.pitch_b, n, ys, y1, step, lane);
-    else if (!(mis & 3)) d = rows_differ<uint32_t>(pa, a.pitch_a, pb, a.pitch_b, n, ys, y1, step, lane);
-    else d = rows_differ<uint8_t>(pa, a.pitch_a, pb, a.pitch_b, n, ys, y1, step, lane);
-    if (__any(d) && lane == 0) a.mask[tile] = 1;
-}
-
-hipError_t launch_diff_tiles(const DiffArgs& a, hipStream_t st)
-{
-    const int ntiles = a.nx * a.ny;
-    if (ntiles <= 0) return hipSuccess;
-    const hipError_t e = hipMemsetAsync(a.mask, 0, size_t(ntiles), st); // every byte is written: the kernel only ever stores ones
-    if (e != hipSuccess) return e;
-    const long long padded = (long long)a.T + 2 * a.P; // rows of the tallest rectangle
-    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_semiplanar(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
-    const int chunks = (rows + kDiffRows - 1) / kDiffRows;
-    const dim3 grid(ntiles, chunks < 1024 ? chunks : 1024, nrect), block(256); // (taller rectangles: the kernel strides over the chunks)
-    hipLaunchKernelGGL(diff_tiles, grid, block, 0, st, a);
-    return hipGetLastError();
-}
-
-// =============================================================================================
-// frame sequences: the diff of n pairs in one launch, and the copy of the rectangles nobody computed
-// =============================================================================================
-// diff_tiles for n pairs at once: grid (tile, row chunk, pair * nrect + rectangle).  Row `pair` of the mask gets what diff_tiles writes
-// for that pair: the same rectangles, the same compared bytes (include/realsr_hip.h rsr_diff_tiles), the same choice of access width.
-__global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
-{
-    const int nrect = fmt_is_semiplanar(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
-    const int pair = blockIdx.z / nrect, rect = blockIdx.z - pair * nrect;
+    const PixFmt f = pix_fmt(a.fmt, a.c);
+    const int pair = N == 1 ? 0 : blockIdx.z / f.planes, rect = blockIdx.z - pair * f.planes; // (one pair: no division per workgroup)
     const int tile = blockIdx.x, yi = tile / a.nx, xi = tile - yi * a.nx;
     const DiffPair& p = a.pair[pair];
     uint8_t* const mask = a.mask + (long long)pair * a.nx * a.ny;
@@ -1670,23 +1620,17 @@ __global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
     }
     int r[4];
     tile_source_rect(a.w, a.h, a.T, a.P, xi, yi, r);
-    const int es = a.fmt == kFmtF32 ? 4 : (a.fmt == kFmtF16 ? 2 : (a.fmt == kFmtU8 ? a.c : (fmt_yuv_bits(a.fmt) + 7) / 8)); // (a YUV surface: of one sample)
-    int bx0 = r[0] * es, bx1 = r[2] * es, y0 = r[1], y1 = r[3];
-    long long off_a = 0, off_b = 0;
-    if (fmt_is_semiplanar(a.fmt)) // (a planar 4:4:4 surface: three planes like the planar float formats, below)
-    {
-        if (rect == 1)
-        { // the (U, V) pairs the decode of this rectangle reads (diff_tiles)
-            const int cx0 = max((r[0] >> 1) - 1, 0), cx1 = min(((r[2] - 1) >> 1) + 1, a.w / 2 - 1);
-            bx0 = cx0 * 2 * es, bx1 = (cx1 + 1) * 2 * es;
-            if (!fmt_is_422(a.fmt)) y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1;
-            off_a = p.plane_a, off_b = p.plane_b;
-        }
+    int bx0 = r[0] * f.es, bx1 = r[2] * f.es, y0 = r[1], y1 = r[3];
+    if (f.pairs && rect == 1)
+    { // the (U, V) pairs the decode of this rectangle reads: one chroma sample beyond its own, at every siting
+        const int cx0 = max((r[0] >> 1) - 1, 0), cx1 = min(((r[2] - 1) >> 1) + 1, a.w / 2 - 1);
+        bx0 = cx0 * 2 * f.es, bx1 = (cx1 + 1) * 2 * f.es;
+        if (f.csy) y0 = max((r[1] >> 1) - 1, 0), y1 = min(((r[3] - 1) >> 1) + 1, a.h / 2 - 1) + 1; // (4:2:2: the rectangle's own rows)
     }
-    else if (a.fmt != kFmtU8) off_a = rect * p.plane_a, off_b = rect * p.plane_b;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint8_t* const pa = p.a + off_a + bx0;
-    const uint8_t* const pb = p.b + off_b + bx0;
+    const uint8_t* const pa = p.a + rect * p.plane_a + bx0;
+    const uint8_t* const pb = p.b + rect * p.plane_b + bx0;
+    // the widest access EVERY row of the rectangle allows: both images' rows then reach its boundary after the same head
     const unsigned mis = unsigned(reinterpret_cast<uintptr_t>(pa) ^ reinterpret_cast<uintptr_t>(pb)) | unsigned(p.pitch_a ^ p.pitch_b);
     const int n = bx1 - bx0, ys = y0 + blockIdx.y * kDiffRows + wave, step = gridDim.y * kDiffRows;
     bool d;
@@ -1696,20 +1640,24 @@ __global__ __launch_bounds__(256) void diff_tiles_seq(const DiffSeqArgs a)
     if (__any(d) && lane == 0) mask[tile] = 1;
 }
 
-hipError_t launch_diff_tiles_seq(const DiffSeqArgs& a, hipStream_t st)
+template <int N> hipError_t launch_diff_tiles(const DiffArgs<N>& a, hipStream_t st)
 {
     const int ntiles = a.nx * a.ny;
     if (ntiles <= 0 || a.n <= 0) return hipSuccess;
     const hipError_t e = hipMemsetAsync(a.mask, 0, size_t(ntiles) * size_t(a.n), st); // every byte is written: the kernel only ever stores ones
     if (e != hipSuccess) return e;
-    const long long padded = (long long)a.T + 2 * a.P;
-    const int rows = padded < a.h ? int(padded) : a.h, nrect = fmt_is_semiplanar(a.fmt) ? 2 : (a.fmt == kFmtU8 ? 1 : 3);
-    const int chunks = (rows + kDiffRows - 1) / kDiffRows;
-    const dim3 grid(ntiles, chunks < 1024 ? chunks : 1024, a.n * nrect), block(256);
-    hipLaunchKernelGGL(diff_tiles_seq, grid, block, 0, st, a);
+    const long long padded = (long long)a.T + 2 * a.P; // rows of the tallest rectangle
+    const int rows = padded < a.h ? int(padded) : a.h, chunks = (rows + kDiffRows - 1) / kDiffRows;
+    const dim3 grid(ntiles, chunks < 1024 ? chunks : 1024, a.n * pix_fmt(a.fmt).planes), block(256); // (taller rectangles: the kernel strides over the chunks)
+    hipLaunchKernelGGL(diff_tiles<N>, grid, block, 0, st, a);
     return hipGetLastError();
 }
+template hipError_t launch_diff_tiles<1>(const DiffArgs<1>&, hipStream_t);
+template hipError_t launch_diff_tiles<kMaxMerge>(const DiffArgs<kMaxMerge>&, hipStream_t);
 
+// =============================================================================================
+// frame sequences: the copy of the rectangles nobody computed
+// =============================================================================================
 // Rows of a rectangle per workgroup and step: 4 per wave.  An 800-row rectangle spreads over 50 workgroups, the 60 of a 1080p frame at x4
 // over 3000: a dozen per CU, enough in flight for a pass that only waits for memory.
 constexpr int kPropRows = 16;

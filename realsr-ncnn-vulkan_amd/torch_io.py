@@ -21,6 +21,7 @@ pitches (describe()); anything else is made contiguous first.  The work is enque
 waits for the GPU: the result is ordered on that stream like the output of any torch op.
 """
 import contextlib
+import types
 
 import numpy as np
 import torch
@@ -145,19 +146,29 @@ def _on_current_stream(device, enqueue):
     return y
 
 
-# ---- YUV 4:2:0 (and, chroma=422, 4:2:2) surfaces: what a hardware decoder yields and an encoder takes ----------------------------------------------------------
-_YUV = {torch.uint8: RSR_FMT_NV12, torch.int16: RSR_FMT_P010}  # (P010 words as int16 too: torch's uint16 is a late and partial dtype)
-if hasattr(torch, "uint16"):
-    _YUV[torch.uint16] = RSR_FMT_P010
-# ... and 4:2:2 surfaces (keyword chroma=422): what broadcast and archive codecs hold -- a UV row per Y row
-_YUV422 = {t: {RSR_FMT_NV12: RSR_FMT_NV16, RSR_FMT_P010: RSR_FMT_P210}[f] for t, f in _YUV.items()}
-_YUV_FMTS = (RSR_FMT_NV12, RSR_FMT_P010, RSR_FMT_NV16, RSR_FMT_P210)
-# ... and planar 4:4:4 (keyword chroma=444): three full planes (3, H, W); 16-bit words hold the 10-bit code in their LOW bits (yuv444p10le)
-_YUV444 = {t: {RSR_FMT_NV12: RSR_FMT_YUV444P, RSR_FMT_P010: RSR_FMT_YUV444P10}[f] for t, f in _YUV.items()}
+# ---- YUV images, keyword chroma: what each subsampling is to this module -------------------------------------------------------------------
+def _chroma(fmt8, fmt16, names, unit=0, yrows=1, tensor="", surface="", family=""):
+    """One row of _CHROMA.  fmt: dtype -> format (16-bit words as int16 too: torch's uint16 is a late and partial dtype); names: the dtype
+    refusal's list.  A surface (420, 422) is `unit` rows per `yrows` rows of Y -- (3h / 2, w) or (2h, w), uv (h / yrows, w), h a multiple of
+    yrows --; unit 0: three full planes (3, h, w).  tensor, surface, family: the texts that differ."""
+    fmt = {torch.uint8: fmt8, torch.int16: fmt16}
+    if hasattr(torch, "uint16"):
+        fmt[torch.uint16] = fmt16
+    return types.SimpleNamespace(fmt=fmt, names=names, unit=unit, yrows=yrows, tensor=tensor, surface=surface, family=family)
 
 
-def _yuv_fmt(dtype, chroma):
-    return (_YUV422 if chroma == 422 else _YUV)[dtype]
+_CHROMA = {
+    # what a hardware decoder yields and an encoder takes; P010: the 10-bit code in the high bits
+    420: _chroma(RSR_FMT_NV12, RSR_FMT_P010, "uint8 = NV12; uint16 / int16 = P010", 3, 2,
+                 "a (3h / 2, w) tensor: h rows of Y, then h / 2 rows of interleaved UV", "a 4:2:0 surface (even h and w, uv (h / 2, w))"),
+    # what broadcast and archive codecs hold: a UV row per Y row
+    422: _chroma(RSR_FMT_NV16, RSR_FMT_P210, "uint8 = NV16; uint16 / int16 = P210", 2, 1,
+                 "a (2h, w) tensor: h rows of Y, then h rows of interleaved UV (a YUV 4:2:2 surface)", "a YUV 4:2:2 surface (even w, uv (h, w))",
+                 "YUV 4:2:2 surfaces"),
+    # planar: three full planes (3, H, W); 16-bit words hold the 10-bit code in their LOW bits (yuv444p10le)
+    444: _chroma(RSR_FMT_YUV444P, RSR_FMT_YUV444P10, "uint8 = yuv444p; uint16 / int16 = yuv444p10le", family="YUV 4:4:4 images"),
+}
+_CHROMA_OF = {f: c for c, k in _CHROMA.items() for f in k.fmt.values()}  # format -> chroma (an RGB format: in no row)
 
 
 def _check_chroma(chroma, who):
@@ -179,8 +190,8 @@ def _planes444(sr, s, what):
     y = planes[0]
     if any(t.dtype != y.dtype or t.device != y.device or t.shape != y.shape for t in planes):
         raise ValueError("upscale_yuv: the planes of %s must have one shape and dtype, on one device" % what)
-    if y.dtype not in _YUV444:
-        raise ValueError("upscale_yuv: dtype %s is not supported (uint8 = yuv444p; uint16 / int16 = yuv444p10le)" % y.dtype)
+    if y.dtype not in _CHROMA[444].fmt:
+        raise ValueError("upscale_yuv: dtype %s is not supported (%s)" % (y.dtype, _CHROMA[444].names))
     if y.device.type != "cuda" or y.device.index != sr.gpuid:
         raise ValueError("upscale_yuv: %s is on %s, the context runs on cuda:%d" % (what, y.device, sr.gpuid))
     if y.shape[0] < 1 or y.shape[1] < 1:
@@ -212,26 +223,24 @@ def _desc444(sr, s, what):
     if d is None:
         raise ValueError("upscale_yuv: %s is not addressable by one row pitch and one plane pitch (stride 1 along W, one row stride for all "
                          "three planes, the planes equally spaced)" % what)
-    return _YUV444[planes[0].dtype], planes[0].shape[1], planes[0].shape[0], d
+    return _CHROMA[444].fmt[planes[0].dtype], planes[0].shape[1], planes[0].shape[0], d
 
 
-def _out_size_yuv444(sr, fmt, w, h, who):
-    """(ow, oh) of the 4:4:4 output for a w x h image: sr.out_size_fmt -- the rule of the RGB outputs, no parity anywhere."""
-    if not hasattr(sr, "out_size_fmt"):
-        raise ValueError("%s: this context writes no YUV 4:4:4 images (no out_size_fmt)" % who)
-    return sr.out_size_fmt(fmt, w, h)
-
-
-def _new444(like, ow, oh):
-    """An uninitialised ow x oh 4:4:4 result of the kind of `like`: a (3, oh, ow) tensor, or the (y, u, v) views of one."""
-    first = like[0] if isinstance(like, (tuple, list)) else like
-    o = first.new_empty((3, oh, ow))
-    return (o[0], o[1], o[2]) if isinstance(like, (tuple, list)) else o
+def _new_yuv(like, ow, oh, chroma):
+    """An uninitialised ow x oh YUV result of the kind of `like`: a surface tensor of the chroma's rows or a (3, oh, ow) tensor -- or, for
+    a pair or triple, the plane views of one."""
+    seq = isinstance(like, (tuple, list))
+    first, k = like[0] if seq else like, _CHROMA[chroma]
+    if not k.unit:
+        o = first.new_empty((3, oh, ow))
+        return (o[0], o[1], o[2]) if seq else o
+    o = first.new_empty((oh * k.unit // k.yrows, ow))
+    return (o[:oh], o[oh:]) if seq else o
 
 
 def _upscale_yuv444(sr, surface, out):
     fmt, w, h, din = _desc444(sr, surface, "surface")
-    ow, oh = _out_size_yuv444(sr, fmt, w, h, "upscale_yuv")
+    ow, oh = _out_size_for(sr, fmt, w, h, "upscale_yuv")
     first = surface[0] if isinstance(surface, (tuple, list)) else surface
     if out is not None:
         if isinstance(out, (tuple, list)) != isinstance(surface, (tuple, list)):
@@ -240,58 +249,34 @@ def _upscale_yuv444(sr, surface, out):
         if (ofmt, w2, h2) != (fmt, ow, oh):
             raise ValueError("upscale_yuv: out must be a %s YUV 4:4:4 image of %d x %d on %s" % (first.dtype, ow, oh, first.device))
     else:
-        out = _new444(surface, ow, oh)
+        out = _new_yuv(surface, ow, oh, 444)
         dout = _desc444(sr, out, "out")[3]
     _on_current_stream(first.device, lambda st: sr.process_device_batch([din], fmt, w, h, 3, [dout], fmt, stream=st))
     return out
 
 
-def _planes422(sr, s, what):
-    """_planes for a 4:2:2 surface: a (2h, w) tensor -- h rows of Y, then h rows of interleaved UV -- or a (y, uv) pair, uv (h, w)."""
-    if isinstance(s, (tuple, list)):
-        if len(s) != 2 or not all(isinstance(t, torch.Tensor) for t in s):
-            raise ValueError("upscale_yuv: %s must be a surface tensor or a (y, uv) pair of tensors" % what)
-        y, uv = s
-    else:
-        if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.shape[0] % 2 or s.shape[0] < 2:
-            raise ValueError("upscale_yuv: %s must be a (2h, w) tensor: h rows of Y, then h rows of interleaved UV (a YUV 4:2:2 surface)" % what)
-        h = s.shape[0] // 2
-        y, uv = s[:h], s[h:]
-    if y.dim() != 2 or uv.dim() != 2 or y.dtype != uv.dtype or y.device != uv.device:
-        raise ValueError("upscale_yuv: y and uv of %s must be 2-D tensors of one dtype on one device" % what)
-    if y.dtype not in _YUV422:
-        raise ValueError("upscale_yuv: dtype %s is not supported (uint8 = NV16; uint16 / int16 = P210)" % y.dtype)
-    if y.device.type != "cuda" or y.device.index != sr.gpuid:
-        raise ValueError("upscale_yuv: %s is on %s, the context runs on cuda:%d" % (what, y.device, sr.gpuid))
-    h, w = y.shape
-    if h < 1 or w < 2 or w % 2 or tuple(uv.shape) != (h, w):
-        raise ValueError("upscale_yuv: y %s with uv %s is not a YUV 4:2:2 surface (even w, uv (h, w))" % (tuple(y.shape), tuple(uv.shape)))
-    return y, uv
-
-
 def _planes(sr, s, what, chroma=420):
-    """The (y, uv) views of a surface -- a (3h / 2, w) tensor or a pair of planes -- validated; ValueError before anything is launched.
-    chroma=422: a (2h, w) tensor or a pair with uv (h, w) (_planes422)."""
-    if chroma == 422:
-        return _planes422(sr, s, what)
+    """The (y, uv) views of a surface -- a (3h / 2, w) tensor (chroma=422: (2h, w)) or a pair of planes, uv (h / 2, w) ((h, w)) --
+    validated; ValueError before anything is launched."""
+    k = _CHROMA[chroma]
     if isinstance(s, (tuple, list)):
         if len(s) != 2 or not all(isinstance(t, torch.Tensor) for t in s):
             raise ValueError("upscale_yuv: %s must be a surface tensor or a (y, uv) pair of tensors" % what)
         y, uv = s
     else:
-        if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.shape[0] % 3 or s.shape[0] < 3:
-            raise ValueError("upscale_yuv: %s must be a (3h / 2, w) tensor: h rows of Y, then h / 2 rows of interleaved UV" % what)
-        h = s.shape[0] // 3 * 2
+        if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.shape[0] % k.unit or s.shape[0] < k.unit:
+            raise ValueError("upscale_yuv: %s must be %s" % (what, k.tensor))
+        h = s.shape[0] // k.unit * k.yrows
         y, uv = s[:h], s[h:]
     if y.dim() != 2 or uv.dim() != 2 or y.dtype != uv.dtype or y.device != uv.device:
         raise ValueError("upscale_yuv: y and uv of %s must be 2-D tensors of one dtype on one device" % what)
-    if y.dtype not in _YUV:
-        raise ValueError("upscale_yuv: dtype %s is not supported (uint8 = NV12; uint16 / int16 = P010)" % y.dtype)
+    if y.dtype not in k.fmt:
+        raise ValueError("upscale_yuv: dtype %s is not supported (%s)" % (y.dtype, k.names))
     if y.device.type != "cuda" or y.device.index != sr.gpuid:
         raise ValueError("upscale_yuv: %s is on %s, the context runs on cuda:%d" % (what, y.device, sr.gpuid))
     h, w = y.shape
-    if h < 2 or w < 2 or h % 2 or w % 2 or tuple(uv.shape) != (h // 2, w):
-        raise ValueError("upscale_yuv: y %s with uv %s is not a 4:2:0 surface (even h and w, uv (h / 2, w))" % (tuple(y.shape), tuple(uv.shape)))
+    if h < k.yrows or w < 2 or h % k.yrows or w % 2 or tuple(uv.shape) != (h // k.yrows, w):
+        raise ValueError("upscale_yuv: y %s with uv %s is not %s" % (tuple(y.shape), tuple(uv.shape), k.surface))
     return y, uv
 
 
@@ -317,23 +302,24 @@ def _ratio_text(sr):
         return "%s x %s" % tuple(pair) if pair else "in force"
 
 
-def _out_size_yuv(sr, w, h, who):
-    """(ow, oh) of the YUV output for a w x h surface: w and h times the context's out_scale 4 / 2 / 1, or, while another ratio is in force
-    (sr.out_ratio, or a pair sr.out_ratio_xy: out_scale reads 0), sr.out_size_yuv -- ValueError where w, h or the tile size does not take a YUV output at that ratio,
-    and for a context that has no out_size_yuv."""
-    s = getattr(sr, "out_scale", sr.scale)
-    if s:
-        return w * s, h * s
-    if not hasattr(sr, "out_size_yuv"):
-        raise ValueError("%s: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (who, _ratio_text(sr)))
-    return sr.out_size_yuv(w, h)
-
-
-def _out_size_yuv422(sr, fmt, w, h, who):
-    """(ow, oh) of the 4:2:2 output for a w x h surface: sr.out_size_fmt at every out_scale, ratio or pair -- ValueError with "YUV" in it where
-    the engine would refuse the call (an odd tile rectangle or image width), and for a context that has no out_size_fmt."""
+def _out_size_for(sr, fmt, w, h, who):
+    """(ow, oh) of the context's output for a w x h image in fmt; ValueError where w, h or the tile size does not take it.  RGB: _out_size.
+    A 4:2:0 surface: w and h times the context's out_scale 4 / 2 / 1, or, while another ratio is in force (sr.out_ratio, or a pair
+    sr.out_ratio_xy: out_scale reads 0), sr.out_size_yuv -- ValueError for a context that has none.  4:2:2 and 4:4:4: sr.out_size_fmt at
+    every out_scale, ratio or pair -- ValueError with "YUV" in it where the engine would refuse the call (4:2:2: an odd tile rectangle or
+    image width; 4:4:4 has the rule of the RGB outputs, no parity anywhere), and for a context that has no out_size_fmt."""
+    chroma = _CHROMA_OF.get(fmt)
+    if chroma is None:
+        return _out_size(sr, w, h)
+    if chroma == 420:
+        s = getattr(sr, "out_scale", sr.scale)
+        if s:
+            return w * s, h * s
+        if not hasattr(sr, "out_size_yuv"):
+            raise ValueError("%s: a YUV output takes out_scale 4, 2 or 1 only, not the output ratio %s" % (who, _ratio_text(sr)))
+        return sr.out_size_yuv(w, h)
     if not hasattr(sr, "out_size_fmt"):
-        raise ValueError("%s: this context writes no YUV 4:2:2 surfaces (no out_size_fmt)" % who)
+        raise ValueError("%s: this context writes no %s (no out_size_fmt)" % (who, _CHROMA[chroma].family))
     return sr.out_size_fmt(fmt, w, h)
 
 
@@ -368,11 +354,8 @@ def upscale_yuv(sr, surface, out=None, chroma=420):
         return _upscale_yuv444(sr, surface, out)
     pair = isinstance(surface, (tuple, list))
     y, uv = _planes(sr, surface, "surface", chroma)
-    fmt, (h, w) = _yuv_fmt(y.dtype, chroma), y.shape
-    if chroma == 422:
-        ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_yuv")
-    else:
-        ow, oh = _out_size_yuv(sr, w, h, "upscale_yuv")  # (out_scale 4 / 2 / 1, or a ratio such as 3/2: sr.out_ratio)
+    fmt, (h, w) = _CHROMA[chroma].fmt[y.dtype], y.shape
+    ow, oh = _out_size_for(sr, fmt, w, h, "upscale_yuv")  # (out_scale 4 / 2 / 1, or a ratio such as 3/2: sr.out_ratio)
     if out is not None:
         if isinstance(out, (tuple, list)) != pair:
             raise ValueError("upscale_yuv: out must be a %s like the input" % ("(y, uv) pair" if pair else "surface tensor"))
@@ -383,10 +366,8 @@ def upscale_yuv(sr, surface, out=None, chroma=420):
         if dout is None:
             raise ValueError("upscale_yuv: out is not addressable by one row pitch and a plane pitch")
     else:
-        o = y.new_empty((oh * 2 if chroma == 422 else oh * 3 // 2, ow))
-        oy, ouv = o[:oh], o[oh:]
-        out = (oy, ouv) if pair else o
-        dout = _describe_yuv(oy, ouv)
+        out = _new_yuv(surface, ow, oh, chroma)
+        dout = _describe_yuv(*(out if pair else (out[:oh], out[oh:])))
     din = _describe_yuv(y, uv)
     if din is None:
         packed = torch.cat([y, uv], dim=0)  # (kept alive by the stream ordering below, like any temporary of a torch op)
@@ -409,7 +390,7 @@ def _image_desc(sr, t, what, chroma=420):
         return fmt, w, h, 3, d
     if isinstance(t, (tuple, list)) or (isinstance(t, torch.Tensor) and t.dim() == 2):
         y, uv = _planes(sr, t, what, chroma)
-        return _yuv_fmt(y.dtype, chroma), y.shape[1], y.shape[0], 3, _describe_yuv(y, uv)
+        return _CHROMA[chroma].fmt[y.dtype], y.shape[1], y.shape[0], 3, _describe_yuv(y, uv)
     fmt, batched = _check(sr, t)
     if batched:
         raise ValueError("upscale_delta: %s must be ONE image, not a batch %s" % (what, tuple(t.shape)))
@@ -458,16 +439,8 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None, chroma=420):
     fmt, w, h, c, _ = _image_desc(sr, x, "x", chroma)
     if prev_x is not None and not _same_layout(x, prev_x):
         raise ValueError("upscale_delta: prev_x must have x's layout, shape, dtype and device")
-    yuv = fmt in _YUV_FMTS
-    if chroma == 444:
-        ow, oh = _out_size_yuv444(sr, fmt, w, h, "upscale_delta")
-    elif yuv and chroma == 422:
-        ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_delta")
-    elif yuv:
-        ow, oh = _out_size_yuv(sr, w, h, "upscale_delta")
-    else:
-        ow, oh = _out_size(sr, w, h)
-    note = _yuv_ratio_note(sr) if yuv else ""
+    ow, oh = _out_size_for(sr, fmt, w, h, "upscale_delta")
+    note = _yuv_ratio_note(sr) if _CHROMA_OF.get(fmt) in (420, 422) else ""
     for t, what in ((prev_y, "prev_y"),) + (((out, "out"),) if out is not None else ()):
         if isinstance(t, (tuple, list)) != isinstance(x, (tuple, list)):
             raise ValueError("upscale_delta: %s must be a %s like x" % (what, "(y, uv) pair" if isinstance(x, (tuple, list)) else "tensor"))
@@ -514,14 +487,8 @@ SEQ_MAX = 16  # frames per rsr_process_device_sequence call (RSR_SEQ_MAX)
 
 def _new_like_result(x, ow, oh, chroma=420):
     """An uninitialised result for the single image x (a tensor or a (y, uv) pair; chroma: a surface's subsampling) at ow x oh, of x's kind."""
-    if chroma == 444:
-        return _new444(x, ow, oh)
-    rows = oh * 2 if chroma == 422 else oh * 3 // 2
-    if isinstance(x, (tuple, list)):
-        o = x[0].new_empty((rows, ow))
-        return (o[:oh], o[oh:])
-    if x.dim() == 2:
-        return x.new_empty((rows, ow))
+    if chroma == 444 or isinstance(x, (tuple, list)) or x.dim() == 2:
+        return _new_yuv(x, ow, oh, chroma)
     return x.new_empty((oh, ow, x.shape[2]) if x.dtype == torch.uint8 else (3, oh, ow))
 
 
@@ -562,16 +529,8 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420)
     if prev_x is None:
         prev_y = None  # (nothing of it would be used: every tile of frames[0] runs)
     pair = isinstance(xs[0], (tuple, list))
-    note = ""
-    if chroma == 444:
-        ow, oh = _out_size_yuv444(sr, fmt, w, h, "upscale_sequence")
-    elif fmt in _YUV_FMTS and chroma == 422:
-        ow, oh = _out_size_yuv422(sr, fmt, w, h, "upscale_sequence")
-    elif fmt in _YUV_FMTS:
-        ow, oh = _out_size_yuv(sr, w, h, "upscale_sequence")
-        note = _yuv_ratio_note(sr)
-    else:
-        ow, oh = _out_size(sr, w, h)
+    ow, oh = _out_size_for(sr, fmt, w, h, "upscale_sequence")
+    note = _yuv_ratio_note(sr) if _CHROMA_OF.get(fmt) == 420 else ""
 
     def result_desc(t, what):
         if isinstance(t, (tuple, list)) != pair:

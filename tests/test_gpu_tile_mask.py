@@ -20,6 +20,8 @@ import tile_diff_ref as ref
 
 pytestmark = pytest.mark.gpu
 U8, F16, F32, NV12, P010 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW, R.RSR_FMT_NV12, R.RSR_FMT_P010
+NV16, P210, YUV444P, YUV444P10 = R.RSR_FMT_NV16, R.RSR_FMT_P210, R.RSR_FMT_YUV444P, R.RSR_FMT_YUV444P10
+S420, S422, P444 = (NV12, P010), (NV16, P210), (YUV444P, YUV444P10)  # surfaces (3h / 2, w) and (2h, w); planar (3, h, w) like the float formats
 NP = ref.NP
 W, H, T, P = 70, 50, 32, 10
 NT = 6
@@ -63,7 +65,7 @@ def ctx(ctxs):
 
 
 def shape_of(fmt, w, h, c=3):
-    return (h, w, c) if fmt == U8 else ((h * 3 // 2, w) if fmt in (NV12, P010) else (3, h, w))
+    return (h, w, c) if fmt == U8 else ((h * 3 // 2, w) if fmt in S420 else ((h * 2, w) if fmt in S422 else (3, h, w)))
 
 
 def image(seed, fmt, w=W, h=H, c=3):
@@ -72,8 +74,8 @@ def image(seed, fmt, w=W, h=H, c=3):
         return rng.integers(0, 256, size=(h, w, c), dtype=np.uint8)
     if fmt in (F16, F32):
         return rng.uniform(0, 1, size=(3, h, w)).astype(NP[fmt])
-    codes = rng.integers(0, 256 if fmt == NV12 else 1024, size=(h * 3 // 2, w))
-    return codes.astype(np.uint8) if fmt == NV12 else (codes << 6).astype(np.uint16)
+    codes = rng.integers(0, 256 if NP[fmt] == np.uint8 else 1024, size=shape_of(fmt, w, h))
+    return codes.astype(np.uint8) if NP[fmt] == np.uint8 else (codes << (0 if fmt in P444 else 6)).astype(np.uint16)  # (4:4:4: the code in the LOW bits)
 
 
 def dev(x):
@@ -269,14 +271,15 @@ def gpu_mask(s, a, b, fmt, w, h, c=3, place_b=None):
         off, row, plane = place_b
         es = b.dtype.itemsize
         rowbytes = w * es * (c if fmt == U8 else 1)
+        planar = fmt in (F16, F32) + P444
         host = np.random.default_rng(3).integers(0, 256, size=off + R.image_span(fmt, w, h, c, row, plane) + 64, dtype=np.uint8)
         raw = np.ascontiguousarray(b).view(np.uint8).reshape(-1, rowbytes)  # rows of every plane, in order
         if fmt == U8:
             starts = [off + y * row for y in range(h)]
-        elif fmt in (F16, F32):
+        elif planar:
             starts = [off + q * plane + y * row for q in range(3) for y in range(h)]
         else:
-            starts = [off + y * row for y in range(h)] + [off + plane + y * row for y in range(h // 2)]
+            starts = [off + y * row for y in range(h)] + [off + plane + y * row for y in range(h if fmt in S422 else h // 2)]
         for r_, st in zip(raw, starts):
             host[st:st + rowbytes] = r_
         d_b = torch.from_numpy(host).cuda()
@@ -286,16 +289,21 @@ def gpu_mask(s, a, b, fmt, w, h, c=3, place_b=None):
     s.diff_tiles(d_a.data_ptr(), desc_b, fmt, w, h, c, d_m.data_ptr())
     m = d_m.cpu().numpy()
     assert set(m.tolist()) <= {0, 1}, m
+    # rsr_diff_tiles IS the sequence of the one pair (prev = a, frames = [b]): row 0 of its masks
+    d_m.fill_(0xCD)
+    torch.cuda.synchronize()
+    s.diff_tiles_sequence([desc_b], d_a.data_ptr(), fmt, w, h, c, d_m.data_ptr())
+    assert d_m.cpu().numpy().tolist() == m.tolist()
     return m
 
 
 def poke(fmt, x, px, py, ch=0, chroma=None, h=H):
     """x with ONE sample changed by one bit: luma / element (px, py) of channel ch, or, chroma = 0 / 1, the U / V of chroma pair (px, py)."""
     y = x.copy()
-    v = y.view(np.uint8) if fmt == NV12 else (y.view(np.uint16) if fmt in (F16, P010) else (y.view(np.uint32) if fmt == F32 else y))
+    v = y.view({1: np.uint8, 2: np.uint16, 4: np.uint32}[y.dtype.itemsize])
     if fmt == U8:
         v[py, px, ch] ^= 1
-    elif fmt in (F16, F32):
+    elif fmt in (F16, F32) + P444:
         v[ch, py, px] ^= 1
     elif chroma is None:
         v[py, px] ^= 1  # (P010: one of the low 6 bits)
@@ -305,68 +313,91 @@ def poke(fmt, x, px, py, ch=0, chroma=None, h=H):
 
 
 DIFF_FORMATS = [("u8c3", U8, 3), ("u8c4", U8, 4), ("f16", F16, 3), ("f32", F32, 3), ("nv12", NV12, 3), ("p010", P010, 3)]
+# (id, fmt, c, w, h, tile): the families the feature came with on the base case; the later ones at 35 x 25 (4:4:4) and 36 x 26 (4:2:2) with
+# tile 16 -- a 3 x 2 grid again, the smallest with an interior tile, an edge tile, an odd chroma boundary and a clipped halo
+DIFF_CASES = [f + (W, H, T) for f in DIFF_FORMATS] + [("nv16", NV16, 3, 36, 26, 16), ("p210", P210, 3, 36, 26, 16), ("yuv444p", YUV444P, 3, 35, 25, 16),
+                                                      ("yuv444p10", YUV444P10, 3, 35, 25, 16)]
+DIFF_IDS = [f[0] for f in DIFF_CASES]
 
 
-@pytest.mark.parametrize("name,fmt,c", DIFF_FORMATS, ids=[f[0] for f in DIFF_FORMATS])
-def test_diff_against_the_reference(ctx, name, fmt, c):
+@pytest.mark.parametrize("name,fmt,c,w,h,tile", DIFF_CASES, ids=DIFF_IDS)
+def test_diff_against_the_reference(ctx, name, fmt, c, w, h, tile):
     s = ctx[False]
-    a = image(21, fmt, c=c)
-    assert gpu_mask(s, a, a, fmt, W, H, c).tolist() == [0] * NT
+    s.tilesize = tile
+    base = (w, h, tile) == (W, H, T)
+    a = image(21, fmt, w, h, c)
+    assert gpu_mask(s, a, a, fmt, w, h, c).tolist() == [0] * NT
     last = c - 1 if fmt == U8 else 2  # (c == 4: the alpha byte)
     for t in (0, 4):
-        x0, y0, x1, y1 = ref.source_rect(W, H, T, P, t)
+        x0, y0, x1, y1 = ref.source_rect(w, h, tile, P, t)
         inside = [(x0, y0), (x1 - 1, y0), (x0, y1 - 1), (x1 - 1, y1 - 1)]
         outside = [(x0 - 1, y0), (x1, y0), (x0, y0 - 1), (x0, y1), (x1, y1 - 1)]
-        for px, py in inside + [q for q in outside if 0 <= q[0] < W and 0 <= q[1] < H]:
-            b = poke(fmt, a, px, py, ch=last)
-            want = ref.diff_mask(fmt, a, b, T, P)
+        for px, py in inside + [q for q in outside if 0 <= q[0] < w and 0 <= q[1] < h]:
+            b = poke(fmt, a, px, py, ch=last, h=h)
+            want = ref.diff_mask(fmt, a, b, tile, P)
             assert want[t] == int((px, py) in inside) and want.any()
-            assert gpu_mask(s, a, b, fmt, W, H, c).tolist() == want.tolist(), (t, px, py)
-    # column 41 is inside tile 0's [0, 42) and tile 1's [22, 70); column 42 in tile 1's only
-    assert gpu_mask(s, a, poke(fmt, a, 41, 5, ch=last), fmt, W, H, c).tolist() == [1, 1, 0, 0, 0, 0]
-    assert gpu_mask(s, a, poke(fmt, a, 42, 5, ch=last), fmt, W, H, c).tolist() == [0, 1, 0, 0, 0, 0]
-    if fmt in (NV12, P010):
-        # chroma pair 21 lies one sample beyond tile 0's luma columns [0, 42) (its own pairs are 0 .. 20): compared all the same; pair 22 not
-        for cx, want0 in ((21, 1), (22, 0)):
+            assert gpu_mask(s, a, b, fmt, w, h, c).tolist() == want.tolist(), (t, px, py)
+    # the last column of tile 0's rectangle lies in its right neighbours' too, the one behind it in theirs only (the base case: column 41
+    # is inside tile 0's [0, 42) and tile 1's [22, 70); column 42 in tile 1's only)
+    x1 = ref.source_rect(w, h, tile, P, 0)[2]
+    for px, want0 in ((x1 - 1, 1), (x1, 0)):
+        b = poke(fmt, a, px, 5, ch=last, h=h)
+        want = ref.diff_mask(fmt, a, b, tile, P).tolist()
+        assert want[0] == want0 and want[1] == 1 and want[3:] == [0, 0, 0] and (not base or (px, want) == (42 - want0, [want0, 1, 0, 0, 0, 0]))
+        assert gpu_mask(s, a, b, fmt, w, h, c).tolist() == want
+    if fmt in S420 + S422:
+        # the chroma pair one sample beyond tile 0's luma columns [0, x1) (its own pairs are 0 .. x1 / 2 - 1) is compared all the same; the
+        # next one not (the base case: pairs 21 and 22)
+        for cx, want0 in ((x1 // 2, 1), (x1 // 2 + 1, 0)):
             for uv in (0, 1):
-                b = poke(fmt, a, cx, 3, chroma=uv)
-                want = ref.diff_mask(fmt, a, b, T, P)
-                assert want[0] == want0 and gpu_mask(s, a, b, fmt, W, H, c).tolist() == want.tolist(), (cx, uv)
+                b = poke(fmt, a, cx, 3, chroma=uv, h=h)
+                want = ref.diff_mask(fmt, a, b, tile, P)
+                assert want[0] == want0 and gpu_mask(s, a, b, fmt, w, h, c).tolist() == want.tolist(), (cx, uv)
+    if fmt in S420:
         # chroma row 21 against tile 0's luma rows [0, 42), likewise
-        b = poke(fmt, a, 2, 21, chroma=1)
-        want = ref.diff_mask(fmt, a, b, T, P)
-        assert want.tolist() == [1, 0, 0, 1, 0, 0] and gpu_mask(s, a, b, fmt, W, H, c).tolist() == want.tolist()
+        b = poke(fmt, a, 2, 21, chroma=1, h=h)
+        want = ref.diff_mask(fmt, a, b, tile, P)
+        assert want.tolist() == [1, 0, 0, 1, 0, 0] and gpu_mask(s, a, b, fmt, w, h, c).tolist() == want.tolist()
+    if fmt in S422:
+        # a UV row per Y row, nothing beyond: tile row 1 reads rows [6, 26), so chroma row 5 is tile row 0's alone and row 6 both rows'
+        # (pair 0: of the tiles of a row, only the first reads it)
+        for cy, want3 in ((5, 0), (6, 1)):
+            b = poke(fmt, a, 0, cy, chroma=1, h=h)
+            want = ref.diff_mask(fmt, a, b, tile, P)
+            assert want.tolist() == [1, 0, 0, want3, 0, 0] and gpu_mask(s, a, b, fmt, w, h, c).tolist() == want.tolist()
     if fmt == F32:
         z = a.copy()
         z[1, 30, 30] = 0.0
         n = z.copy()
         n[1, 30, 30] = -0.0
         assert z[1, 30, 30] == n[1, 30, 30]
-        want = ref.diff_mask(fmt, z, n, T, P)
-        assert want.tolist() == [1, 1, 0, 1, 1, 0] and gpu_mask(s, z, n, fmt, W, H, c).tolist() == want.tolist()
+        want = ref.diff_mask(fmt, z, n, tile, P)
+        assert want.tolist() == [1, 1, 0, 1, 1, 0] and gpu_mask(s, z, n, fmt, w, h, c).tolist() == want.tolist()
 
 
-@pytest.mark.parametrize("name,fmt,c", DIFF_FORMATS, ids=[f[0] for f in DIFF_FORMATS])
-def test_diff_of_pitched_against_packed_operands(ctx, name, fmt, c):
+@pytest.mark.parametrize("name,fmt,c,w,h,tile", DIFF_CASES, ids=DIFF_IDS)
+def test_diff_of_pitched_against_packed_operands(ctx, name, fmt, c, w, h, tile):
     """b inside a larger allocation: at offsets and pitches that agree with the packed a modulo 16, modulo 4 only, and not at all (uint8
-    and NV12; the wider elements as far as their alignment lets them)."""
+    and the 8-bit surfaces; the wider elements as far as their alignment lets them)."""
     s = ctx[False]
-    a = image(22, fmt, c=c)
+    s.tilesize = tile
+    a = image(22, fmt, w, h, c)
     es = a.dtype.itemsize
-    rowbytes = W * es * (c if fmt == U8 else 1)
-    rows = H if fmt != U8 else 0
+    rowbytes = w * es * (c if fmt == U8 else 1)
+    rows = h if fmt != U8 else 0
     for off, pad in ((0, 0), (16, 32), (4, 12), (8 if es == 4 else 2, 4 if es == 4 else 6)) + (((3, 7), (1, 0)) if es == 1 else ()):
         row = rowbytes + pad
         plane = (rows + 3) * row if fmt != U8 else 0
-        for b in (a, poke(fmt, a, 41, 41, ch=1), poke(fmt, a, W - 1, H - 1, ch=2), poke(fmt, a, 0, 0)):
-            want = ref.diff_mask(fmt, a, b, T, P)
-            assert gpu_mask(s, a, b, fmt, W, H, c, place_b=(off, row, plane)).tolist() == want.tolist(), (off, pad)
+        for b in (a, poke(fmt, a, min(41, w - 2), min(41, h - 2), ch=1, h=h), poke(fmt, a, w - 1, h - 1, ch=2, h=h), poke(fmt, a, 0, 0, h=h)):
+            want = ref.diff_mask(fmt, a, b, tile, P)
+            assert gpu_mask(s, a, b, fmt, w, h, c, place_b=(off, row, plane)).tolist() == want.tolist(), (off, pad)
 
 
-@pytest.mark.parametrize("name,fmt,c", [("u8c4", U8, 4), ("f32", F32, 3), ("nv12", NV12, 3)])
+@pytest.mark.parametrize("name,fmt,c", [f[:3] for f in DIFF_CASES])
 def test_diff_of_a_row_longer_than_a_workgroup_pass(ctx, name, fmt, c):
     """230 x 36 at tile 200: tile 0's rectangle is 210 pixels wide -- 840 bytes of RGBA or fp32, 210 of luma --, more than 64 lanes cover in
-    one step of 4-byte or 1-byte pieces; the change sits at the far end of the row."""
+    one step of 4-byte or 1-byte pieces; the change sits at the far end of the row.  Every family at this one geometry: a row this long
+    is what the test is about."""
     s = ctx[False]
     s.tilesize = 200
     w, h = 230, 36

@@ -4,7 +4,8 @@ loops over tiles; nothing here shares code with the library."""
 import numpy as np
 
 U8, F16, F32, NV12, P010 = 0, 1, 2, 4, 5
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16}
+NV16, P210, YUV444P, YUV444P10 = 8, 9, 12, 13
+NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16, NV16: np.uint8, P210: np.uint16, YUV444P: np.uint8, YUV444P10: np.uint16}
 
 
 def tile_count(w, h, T):
@@ -42,13 +43,15 @@ def chroma_span(s0, s1, n):
 
 def compared(fmt, w, h, T, P, tile, a, b):
     """The pairs of arrays rsr_diff_tiles compares for one tile of the frames a and b (numpy images in the library's layouts: uint8
-    (h, w, c); float (3, h, w); surfaces (3h / 2, w))."""
+    (h, w, c); float and planar 4:4:4 (3, h, w); 4:2:0 surfaces (3h / 2, w); 4:2:2 surfaces (2h, w))."""
     x0, y0, x1, y1 = source_rect(w, h, T, P, tile)
     if fmt == U8:
         return [(a[y0:y1, x0:x1, :], b[y0:y1, x0:x1, :])]
-    if fmt in (F16, F32):
+    if fmt in (F16, F32, YUV444P, YUV444P10):
         return [(a[:, y0:y1, x0:x1], b[:, y0:y1, x0:x1])]
     cx0, cx1 = chroma_span(x0, x1, w)
+    if fmt in (NV16, P210):  # a UV row per Y row: the rectangle's own rows
+        return [(a[y0:y1, x0:x1], b[y0:y1, x0:x1]), (a[h + y0:h + y1, 2 * cx0:2 * cx1 + 2], b[h + y0:h + y1, 2 * cx0:2 * cx1 + 2])]
     cy0, cy1 = chroma_span(y0, y1, h)
     return [(a[y0:y1, x0:x1], b[y0:y1, x0:x1]), (a[h + cy0:h + cy1 + 1, 2 * cx0:2 * cx1 + 2], b[h + cy0:h + cy1 + 1, 2 * cx0:2 * cx1 + 2])]
 
@@ -58,8 +61,10 @@ def diff_mask(fmt, a, b, T, P):
     assert a.shape == b.shape and a.dtype == b.dtype == NP[fmt]
     if fmt == U8:
         h, w = a.shape[:2]
-    elif fmt in (F16, F32):
+    elif fmt in (F16, F32, YUV444P, YUV444P10):
         h, w = a.shape[1:]
+    elif fmt in (NV16, P210):
+        h, w = a.shape[0] // 2, a.shape[1]
     else:
         h, w = a.shape[0] * 2 // 3, a.shape[1]
     nx, ny = tile_count(w, h, T)

@@ -3,7 +3,8 @@
 // Includes engine.cpp itself (so the file-static table builder is in reach) and links the kernel objects of the library build; nothing
 // here initialises HIP.  `make -C realsr-ncnn-vulkan_amd/csrc host_check` builds and runs it.
 //   1. image_refs: the refusal table of tests/test_gpu_device_refusals.py (every row RSR_E_ARG, no ImageRef written past its slot) and
-//      valid layouts: packed, strided, n = 16.
+//      valid layouts: packed, strided, n = 16 -- one format of every family (uint8 HWC, planar float, YUV 4:2:0, 4:2:2, 4:4:4).
+//   1b. out_admit: the engine's wording of every kind of refusal, and the sizes each family takes.
 //   2. fill_batch: batches of 1, 7 and 60 tiles with and without TTA; every table entry is read back and range-checked.
 #include "../../realsr-ncnn-vulkan_amd/csrc/engine.cpp"
 
@@ -41,6 +42,11 @@ static void descriptors()
         {"f16 at an odd address", RSR_FMT_F16_CHW, W, 3, {mem + 1, 0, 0}},
         {"pitch no element multiple", RSR_FMT_F16_CHW, W, 3, {p, 2 * W + 1, 0}},
         {"odd w with NV12", RSR_FMT_NV12, W + 1, 3, {p, 0, 0}},
+        {"odd w with P210", RSR_FMT_P210, W + 1, 3, {p, 0, 0}},
+        {"NV16 row pitch below packed", RSR_FMT_NV16, W, 3, {p, W - 1, 0}},
+        {"YUV444P10 at an odd address", RSR_FMT_YUV444P10, W, 3, {mem + 1, 0, 0}},
+        {"YUV444P10 plane pitch no element multiple", RSR_FMT_YUV444P10, W, 3, {p, 0, 2ll * W * H + 1}},
+        {"YUV444P with c == 4", RSR_FMT_YUV444P, W, 4, {p, 0, 0}},
         {"w beyond 2^24", RSR_FMT_U8_HWC, (1 << 24) + 1, 3, {p, 0, 0}},
         {"unknown format", 7, W, 3, {p, 0, 0}},
         {"planar with c == 4", RSR_FMT_F16_CHW, W, 4, {p, 0, 0}},
@@ -50,7 +56,7 @@ static void descriptors()
             for (int at : {0, 2})
             { // the bad descriptor first and last of three; the slots behind it must stay untouched
                 rsr_image im[3] = {{p, 0, 0}, {p, 0, 0}, {p, 0, 0}};
-                if (os && r.fmt == RSR_FMT_NV12) continue; // (x4 of an odd width is even: it is the input descriptor that refuses this call)
+                if (os && r.w != W && (r.fmt == RSR_FMT_NV12 || r.fmt == RSR_FMT_P210)) continue; // (x4 of an odd width is even: it is the input descriptor that refuses this call)
                 im[at] = r.im;
                 std::vector<ImageRef> out(3); // exactly three: a write past the array is ASan's to report
                 const int rc = image_refs(3, im, r.fmt, r.w, H, r.c, os, "image", 0, out.data());
@@ -73,10 +79,58 @@ static void descriptors()
         CHECK(image_refs(1, &odd_u8, RSR_FMT_U8_HWC, W, H, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == 3 * W + 1);
         const rsr_image far_row = {p, 0x7fffffffll, 0};
         CHECK(image_refs(1, &far_row, RSR_FMT_U8_HWC, W, 3, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == 0x7fffffffll);
+        CHECK(image_refs(1, &packed, RSR_FMT_P010, W, H, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == 2 * W && out.plane == 2ll * W * H);
+        CHECK(image_refs(1, &packed, RSR_FMT_NV16, W, H + 1, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == W && out.plane == W * (H + 1ll)); // (4:2:2: any h)
+        CHECK(image_refs(1, &packed, RSR_FMT_P210, W, H, 3, &x4, "image", 0, &out) == RSR_OK && out.row == 8 * W && out.plane == 32ll * W * H);
+        CHECK(image_refs(1, &packed, RSR_FMT_YUV444P, W + 1, H + 1, 3, nullptr, "image", 0, &out) == RSR_OK && out.row == W + 1 && out.plane == (W + 1ll) * (H + 1)); // (4:4:4: any w and h)
+        const rsr_image strided444 = {mem + 2, 2 * W + 6, (2 * W + 6) * (H + 1ll)};
+        CHECK(image_refs(1, &strided444, RSR_FMT_YUV444P10, W, H, 3, nullptr, "image", 0, &out) == RSR_OK && out.data == mem + 2 && out.row == 2 * W + 6 && out.plane == (2 * W + 6) * (H + 1ll));
+        long long row = 0, plane = 0;
+        CHECK(image_layout(RSR_FMT_NV16, W, H, 3, W + 4, 0, &row, &plane) == RSR_OK && row == W + 4 && plane == (W + 4ll) * H);
+        CHECK(image_layout(RSR_FMT_NV12, W, H + 1, 3, 0, 0, &row, &plane) == RSR_E_ARG && !std::strcmp(last_error(), "a YUV 4:2:0 surface needs an even width and height"));
+        CHECK(image_layout(RSR_FMT_NV16, W + 1, H, 3, 0, 0, &row, &plane) == RSR_E_ARG && !std::strcmp(last_error(), "a YUV 4:2:2 surface needs an even width"));
         std::vector<rsr_image> many(16, packed);
         std::vector<ImageRef> outs(16);
         CHECK(image_refs(16, many.data(), RSR_FMT_F16_CHW, W, H, 3, nullptr, "image", 0, outs.data()) == RSR_OK && outs[15].row == 2 * W && outs[15].plane == 2ll * W * H);
     }
+}
+
+// out_admit as the engine asks it: what each family takes, and the engine's wording of every kind of refusal
+static void admission()
+{
+    struct Row
+    {
+        int fmt, w, h, T;
+        OutRatio r;
+        const char* text; // null: admitted
+    };
+    const Row rows[] = {
+        {RSR_FMT_U8_HWC, 35, 25, 16, OutRatio(1, 1), nullptr},
+        {RSR_FMT_F16_CHW, 35, 25, 16, OutRatio(3, 2), "output ratio 3/2: w, h and tilesize times 3 must be multiples of 2 (35 x 25 at tile 16)"},
+        {RSR_FMT_F32_CHW, 36, 26, 16, OutRatio(3, 2), nullptr},
+        {RSR_FMT_YUV444P, 35, 25, 16, OutRatio(1, 1), nullptr},
+        {RSR_FMT_YUV444P10, 35, 25, 16, OutRatio(3, 2, 1, 1), "output ratios 3/2 x 1/1: w and tilesize times 3 must be multiples of 2, h and tilesize times 1 multiples of 1 (35 x 25 at tile 16)"},
+        {RSR_FMT_NV12, 36, 26, 16, OutRatio(1, 1), nullptr},
+        {RSR_FMT_NV12, 35, 26, 16, OutRatio(1, 1), "a YUV 4:2:0 output needs w * out_scale, h * out_scale and tilesize * out_scale even"},
+        {RSR_FMT_P010, 35, 25, 3, OutRatio(2, 1), nullptr},
+        {RSR_FMT_NV12, 35, 26, 16, OutRatio(3, 2), "YUV 4:2:0 output at output ratio 3/2: w, h and tilesize times 3 must be multiples of 2 (35 x 26 at tile 16)"},
+        {RSR_FMT_P010, 36, 26, 6, OutRatio(3, 2), "a YUV 4:2:0 output at ratio 3/2 needs w, h and tilesize times 3/2 even (36 x 26 at tile 6)"},
+        {RSR_FMT_NV12, 36, 26, 16, OutRatio(3, 2, 1, 1), nullptr},
+        {RSR_FMT_NV12, 36, 25, 16, OutRatio(3, 2, 1, 1), "a YUV 4:2:0 output at ratios 3/2 x 1/1 needs w and tilesize times 3/2 and h and tilesize times 1/1 even (36 x 25 at tile 16)"},
+        {RSR_FMT_NV16, 36, 25, 16, OutRatio(1, 1), nullptr},
+        {RSR_FMT_NV16, 35, 25, 16, OutRatio(1, 1), "a YUV 4:2:2 output needs w * out_scale and tilesize * out_scale even"},
+        {RSR_FMT_P210, 36, 26, 6, OutRatio(3, 2), "a YUV 4:2:2 output at ratios 3/2 needs w and tilesize times 3/2 even (36 x 26 at tile 6)"},
+        {RSR_FMT_P210, 36, 25, 16, OutRatio(3, 2, 1, 1), nullptr},
+        {RSR_FMT_NV16, 35, 25, 16, OutRatio(8, 3, 9, 4),
+         "YUV 4:2:2 output at output ratios 8/3 x 9/4: w and tilesize times 8 must be multiples of 3, h and tilesize times 9 multiples of 4 (35 x 25 at tile 16)"},
+    };
+    for (const Row& r : rows)
+    {
+        const int rc = out_admit(pix_fmt(r.fmt), r.w, r.h, r.T, r.r, kWhoEngine);
+        CHECK(rc == (r.text ? RSR_E_ARG : RSR_OK));
+        if (r.text) CHECK(!std::strcmp(last_error(), r.text));
+    }
+    CHECK(pix_fmt(7).known() == false && fmt_check(pix_fmt(7), 3) == RSR_E_ARG && fmt_check(pix_fmt(RSR_FMT_U8_HWC, 4), 4) == RSR_OK && fmt_check(pix_fmt(RSR_FMT_NV16), 4) == RSR_E_ARG);
 }
 
 static void batches()
@@ -113,6 +167,7 @@ static void batches()
 int main()
 {
     descriptors();
+    admission();
     batches();
     if (failures) return std::fprintf(stderr, "%d check(s) failed\n", failures), 1;
     std::puts("descriptor_check ok");
