@@ -133,7 +133,10 @@ def forward(model, x16, slow=False, stats=None, fault=None, precise=False):
     precise: option "precise" = 1 -- the trunk's 64-channel tensors (conv_first, every RDB output) are kept as hi + lo / 2048 and rounded
     once per conv (exact_conv.epi_precise, conv_flow.hip EPI 4 / 5); the convs read the hi planes; conv_last's accumulator is what is
     converted (no fp16 rounding in between).
-    stats: a dict that receives peak |activation|, the non-finite count and the fp16-subnormal count of the stored activations.
+    stats: a dict that receives peak |activation|, the non-finite count and the fp16-subnormal count of the stored activations, and per
+    convolution, in .bin order, "conv_peak" (the largest finite |stored fp16|; conv_last's entry is that of fp16(acc)) and
+    "conv_nonfinite" (the stored values that are not finite) -- what the self-check's range probe reports; over several calls with one
+    dict the lists hold the element-wise maximum and sum.
     fault: None, or a deliberate defect of the MIRROR (tests/test_exact_net.py shows that each one is seen):
       "slope16" the LeakyReLU slope held as fp16, "tap_x" the taps of ONE dense conv mirrored in x, "res_rrdb" one conv5's identity tap
       read from the RRDB's input instead of the RDB's."""
@@ -142,10 +145,17 @@ def forward(model, x16, slow=False, stats=None, fault=None, precise=False):
     if single:
         x16 = x16[None]
     it = iter(enumerate(model))
+    conv_peak, conv_bad = [], []
+
+    def per_conv(a):
+        fin = np.isfinite(a)
+        conv_peak.append(float(a[fin].max()) if fin.any() else 0.0)
+        conv_bad.append(int((~fin).sum()))
 
     def keep(v16):
         if stats is not None:
             a = np.abs(v16.astype(np.float64))
+            per_conv(a)
             stats["peak"] = max(stats.get("peak", 0.0), float(a.max()))
             stats["nonfinite"] = stats.get("nonfinite", 0) + int((~np.isfinite(a)).sum())
             stats["subnormal"] = stats.get("subnormal", 0) + int(((a > 0) & (a < X.F16_MIN_NORMAL)).sum())
@@ -196,6 +206,12 @@ def forward(model, x16, slow=False, stats=None, fault=None, precise=False):
     s = keep(act(conv(s)))
     acc = conv(s)
     assert next(it, None) is None
+    if stats is not None:
+        with np.errstate(over="ignore"):   # (a model made to overflow: the cast to fp16 gives the infinities the engine stores)
+            per_conv(np.abs(X.f16(acc).astype(np.float64)))
+        assert len(conv_peak) == len(model)
+        stats["conv_peak"] = [max(p) for p in zip(stats.get("conv_peak", conv_peak), conv_peak)]
+        stats["conv_nonfinite"] = [a + b for a, b in zip(stats.get("conv_nonfinite", [0] * len(model)), conv_bad)]
     return acc[0] if single else acc
 
 
@@ -214,10 +230,21 @@ def tile_grid(w, h, T):
     return [(x0, y0, min(x0 + T, w) - x0, min(y0 + T, h) - y0) for y0 in range(0, h, T) for x0 in range(0, w, T)]
 
 
+def reflect101(v, n):
+    """The engine's halo index (kernels.hip reflect101, after realsr_preproc.comp:59-62): ONE reflection at each end of 0 .. n - 1, then
+    clamped -- where the halo is wider than the image (n <= P) the shader's single bounce leaves the image, and the engine and the
+    oracle clamp.  numpy's "reflect" bounces as often as needed instead: the two agree while |v| and v - (n - 1) stay below n."""
+    v = np.abs(np.asarray(v))
+    v = (n - 1) - np.abs(v - (n - 1))
+    return np.clip(v, 0, n - 1)
+
+
 def padded_tile(x16, x0, y0, tw, th, P=10):
-    """The padded network input of the tile at (x0, y0): reflect-101 at the image border, real neighbours elsewhere."""
-    big = np.pad(x16, ((0, 0), (P, P), (P, P)), mode="reflect")
-    return big[:, y0:y0 + th + 2 * P, x0:x0 + tw + 2 * P]
+    """The padded network input of the tile at (x0, y0): reflect101 at the image border, real neighbours elsewhere."""
+    _, h, w = x16.shape
+    ys = reflect101(np.arange(y0 - P, y0 + th + P), h)
+    xs = reflect101(np.arange(x0 - P, x0 + tw + P), w)
+    return x16[:, ys[:, None], xs[None, :]]
 
 
 def tta_variants(t):
@@ -247,16 +274,17 @@ def tta_merge(b):
     return s * F32(0.125)
 
 
-def image_x4(model, x16, T, P=10, tta=False, precise=False, **kw):
+def image_x4(model, x16, T, P=10, tta=False, precise=False, pad=None, **kw):
     """The x4 image [3][4h][4w] as fp32, BEFORE the clamp and the conversion to the output format, for the fp16 image x16 [3][h][w] at
     tile size T: per tile the padded tile through forward(), the halo cropped.  Default: the fp16-rounded value; tta: the fp32 mean
-    of the eight fp16 outputs; precise: conv_last's fp32 accumulator itself."""
+    of the eight fp16 outputs; precise: conv_last's fp32 accumulator itself.  pad: another halo rule than padded_tile, same signature
+    (tests/test_exact_geometry.py shows that a wrong one changes kept bytes)."""
     out_of = (lambda a: np.asarray(a, F32)) if precise else half_out
     kw["precise"] = precise
     _, h, w = x16.shape
     out = np.empty((3, 4 * h, 4 * w), F32)
     for x0, y0, tw, th in tile_grid(w, h, T):
-        t = padded_tile(x16, x0, y0, tw, th, P)
+        t = (pad or padded_tile)(x16, x0, y0, tw, th, P)
         if tta:
             vs = tta_variants(t)
             y = [out_of(a) for k in (0, 4) for a in forward(model, np.stack(vs[k:k + 4]), **kw)]
