@@ -808,7 +808,6 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *   "fold"              1 [default]: a tile's last block column, when it is only 1..14 pixels wide, is computed by FOLDED work items
  *                       (two block rows of that narrow column per 16 x 32 block: C3's 420-wide tiles 13.5 instead of 14 block
  *                       columns); 0: one plain block column more.  Output bytes unchanged (kernels.h: kFoldBit)
- *   "flow_flags" bit 4  size the patch ring as if the rounds 1-3 LDS transpose scratch were still reserved (A/B aid)
  *   "dbg"               A-B bits of ConvArgs::dbg, profiling only (bits 1 / 4 / 64 / 128 act only in -DRSR_EXPERIMENT builds of conv_flow.hip):
  *                         1 skip LDS-DMA (64: weights only, 128: patches only), 4 skip epilogue stores, 32 MFMA waves do not skip rows
  *                         outside the tile / inside the unread frame, 8192 conv_last never writes the uint8 image itself, 16384 no split tail for early download,

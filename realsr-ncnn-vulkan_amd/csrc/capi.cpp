@@ -765,7 +765,7 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
         if (ctx->e.precise_auto && ctx->e.loaded) return ctx->e.apply_precise_auto();
     }
     else if (k == "flow_flags")
-        ctx->e.flow_flags = int(value); // plans are keyed by bit 0 (it halves the largest tile the 32-bit plane offsets can address)
+        ctx->e.flow_flags = int(value); // kFlow* bits of kernels.h; plans are keyed by kFlowNtw2 (it halves the largest tile the 32-bit plane offsets can address)
     else if (k == "max_lanes")
     {
         if (value < 1 || value > 64) return ctx->e.fail(RSR_E_ARG, "max_lanes out of range");

@@ -145,19 +145,7 @@ __device__ __forceinline__ int pack_bf8_pair(float x, float y, int old, int hiwo
 
 } // namespace
 
-// EPI: 0 generic (conv_last: planar fp16 [3][H][W] output)      1 v = act(acc)  -> fp16 planes      3 conv_last with (dy, cout) in M
-//      2 v = s1*acc (the conv's own input rides in the accumulator as an identity tap) [, v = s2*v + r2] -> fp16 planes
-//      4 / 5 the PRECISE forms of 2 without / with the second residual (engine option "precise"; 64 output channels): the residual
-//        stream is kept as hi + lo / 2048, hi an fp16 plane as ever and lo ONE BYTE per element (bf8 = e5m2: the upper byte of an
-//        fp16; kernels.h ConvArgs::precise) -- v = s1*acc + lo1/2048 [, v = s2*v + r2 + lo2/2048] in fp32, then ONE rounding:
-//        hi = fp16(v) -> out16 (what the next convs read), lo = bf8((v - hi) * 2048) -> the output's lo planes (16 B per pixel).  The reference's GPU path rounds the trunk 92 times on its way
-//        through the 23 RRDBs (fp16 storage, realsr.cpp:44-46); this halves the engine's distance to the fp32 CPU path
-//        (realsr.cpp:525-838; profiles/r06_storage_emulation.txt).  Absent lo planes are read through a null buffer resource
-//        (zeros, no memory access) and written into one: the epilogue is branch-free.
-//      6 / 7 = 3 / 0 in precise mode: conv_last's fp32 result goes to the uint8 conversion (or a planar fp32 blob) without the fp16
-//        rounding of the reference's `output` blob in between.
-//      8 / 9 / 10 / 11 = 3 / 6 / 0 / 7 writing the caller's PLANAR FLOAT image (ConvArgs::out_fmt: fp16 or fp32, chosen at run time) instead of
-//        the uint8 one -- instantiations of their own, so that the uint8 kernels keep their registers.
+// EPI: the epilogue, a FlowEpi of kernels.h (which describes the twelve of them); the body asks epi_desc(EPI) for its properties.
 // NTW: n-tiles (32 output channels) per MFMA wave; the workgroup has 4*NT/NTW MFMA waves + 4 loader waves.
 // DEFER: double-buffered accumulators, block r drained underneath block r+1 (NT == 1 only).
 // WRES: the conv's weight images stay RESIDENT in LDS for the whole launch (loaded once per workgroup; slot = plane index, the
@@ -175,14 +163,15 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
     constexpr int WB = C::WB;
     constexpr bool WDB = (NTW == 1); // double-buffered weight fragments (registers to spare with one n-tile per wave)
     static_assert(!DEFER || (NT == 1 && NTW == 1), "deferred epilogue needs the 256-VGPR budget of the 8-wave workgroup");
-    constexpr bool LAST3 = (EPI == 3 || EPI == 6 || EPI == 8 || EPI == 9);  // conv_last with (dy, cout) in M
-    constexpr bool LASTG = (EPI == 0 || EPI == 7 || EPI == 10 || EPI == 11); // conv_last through the generic path
-    constexpr bool OUT32 = (EPI == 6 || EPI == 7 || EPI == 9 || EPI == 11);  // ... in precise mode: its fp32 result is what is converted to uint8 / stored (planar fp32)
-    constexpr bool FIMG = EPI >= 8; // the fused image is planar fp16 / fp32 (ConvArgs::out_fmt), not uint8
+    constexpr EpiDesc kEpi = epi_desc(EPI);
+    constexpr bool LAST3 = kEpi.last3(); // conv_last with (dy, cout) in M
+    constexpr bool LASTG = kEpi.lastg(); // conv_last through the generic path
+    constexpr bool OUT32 = kEpi.out32;   // ... in precise mode: its fp32 result is what is converted to uint8 / stored (planar fp32)
+    constexpr bool FIMG = kEpi.fimg;     // the fused image is planar fp16 / fp32 (ConvArgs::out_fmt), not uint8
     static_assert(!LAST3 || (NT == 1 && NTW == 1 && !UPS && !DEFER && WRES), "conv_last's (dy, cout) layout: 32 rows, resident aux image");
-    static_assert((EPI != 4 && EPI != 5) || (NT == 2 && NTW == 1 && !UPS && !DEFER), "the precise residual epilogue exists for the 64-output-channel convs of the trunk");
-    constexpr bool RESID = (EPI == 2 || EPI == 4 || EPI == 5); // residual forms
-    constexpr bool PREC = (EPI == 4 || EPI == 5);              // ... with the hi + lo residual stream
+    static_assert(!kEpi.prec() || (NT == 2 && NTW == 1 && !UPS && !DEFER), "the precise residual epilogue exists for the 64-output-channel convs of the trunk");
+    constexpr bool RESID = kEpi.resid(); // residual forms
+    constexpr bool PREC = kEpi.prec();   // ... with the hi + lo residual stream
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -386,8 +375,8 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
     // accumulator -> ds_write_b64 x4 -> ds_read_b128 x2 -> store per row; the 64 lanes of a store cover the same 1 KiB either
     // way, and the (pixel, half) lane order stores as fast as the pixel-pair order: tools/ubench/store_pattern.hip).
     const float slope = a.lrelu ? 0.2f : 1.f;
-    const bool idt = RESID && a.res1_in_acc; // a fetched first residual arrives as res2 with s2 = 1 (launch_conv_flow)
-    const bool has2 = EPI == 5 || ((EPI == 2) && a.res2_kind == 1);
+    const bool idt = RESID && a.res1_in_acc; // a fetched first residual arrives as res2 with s2 = 1 (choose_conv_flow)
+    const bool has2 = EPI == kEpiPrec2 || ((EPI == kEpiRes) && a.res2_kind == 1);
 #ifdef RSR_FLOW_TRACE // experiment builds only: an s_memtime in the loop forces every lgkmcnt wait to 0 (SMEM returns out of order)
     const bool tracing = a.trace && blockIdx.x == 0 && wave == 0;
 #else
@@ -433,7 +422,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
             for (int e = 0; e < 8; e++)
             {
                 float v = acc[p * 8 + e];
-                if (EPI == 2)
+                if (EPI == kEpiRes)
                 {
                     v = v * a.s1;
                     asm volatile("" : "+v"(v)); // see row_emit
@@ -448,12 +437,12 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
     // The second residual (the RRDB input, every third conv5) is fetched ahead of its use when the registers allow it (one
     // n-tile per wave) -- rows 0-1 one half-stage before the epilogue, rows 2-3 into the same registers once the
     // epilogue is through with rows 0-1: four dependent HBM round trips per block otherwise.
-    constexpr bool PRE2 = (EPI == 2 || EPI == 4) && NTW == 1; // (EPI 5 fetches lo rows at the start of its epilogue anyway: nothing to gain, 16 VGPRs to lose)
+    constexpr bool PRE2 = (EPI == kEpiRes || EPI == kEpiPrec) && NTW == 1; // (EPI 5 fetches lo rows at the start of its epilogue anyway: nothing to gain, 16 VGPRs to lose)
     u32x4 r2q[PRE2 ? 2 : 1][NTW][2]; // rows 0-1, then rows 2-3
 #ifndef RSR_PREC_PRE
 #define RSR_PREC_PRE 1 // EPI 4: lo rows of residual 1 fetched one half-stage ahead of the epilogue (the rest at its start).  1: no spill; 2 spills two dwords and measures the same, 3 / 4 spill a row (profiles/r06_precise_cost.txt)
 #endif
-    u32x4 l1q[EPI == 4 ? 4 : 1];     // EPI 4: the four lo rows of residual 1
+    u32x4 l1q[EPI == kEpiPrec ? 4 : 1];     // EPI 4: the four lo rows of residual 1
     // Out-of-image lanes / rows read zeros through the buffer range check, like row_store drops them.
     auto res2_row = [&](u32x4 (&dst)[2], const OutDesc& o, int rr, int n) {
         const int y = o.y0 + rr;
@@ -481,13 +470,13 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
     };
     auto res2_prefetch = [&](const WorkItem& w, int row0) { // rows row0, row0 + 1
         if (!PRE2) return;
-        if (EPI == 4)
+        if (EPI == kEpiPrec)
         { // no second residual: the prefetch brings ALL FOUR rows of the first residual's lo planes (16 VGPRs, what rows 0-1 of a second
           // residual cost EPI 2)
             if (row0 != 0) return;
             const OutDesc o = make_out(w, true);
 #pragma unroll
-            for (int rr = 0; rr < RSR_PREC_PRE; rr++) lo_row(a.res1, a.lo1_off, l1q[EPI == 4 ? rr : 0], o, rr, 0);
+            for (int rr = 0; rr < RSR_PREC_PRE; rr++) lo_row(a.res1, a.lo1_off, l1q[EPI == kEpiPrec ? rr : 0], o, rr, 0);
             __builtin_amdgcn_sched_barrier(0);
             return;
         }
@@ -524,7 +513,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
         char* ub = uniform_ptr(o.base);
         const unsigned pstride = unsigned(a.out16.plane_stride);
         u32x4 r2x[2];
-        if (EPI == 2 && has2 && !PRE2) res2_row(r2x, o, rr, n);
+        if (EPI == kEpiRes && has2 && !PRE2) res2_row(r2x, o, rr, n);
 #pragma unroll
         for (int p = 0; p < 2; p++)
         {
@@ -533,7 +522,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
             for (int e = 0; e < 8; e++)
             {
                 float f = acc[p * 8 + e];
-                if (EPI == 2)
+                if (EPI == kEpiRes)
                 {
                     f = f * a.s1;
                     // the product is rounded to fp32 BEFORE it becomes an fp16 (as in rounds 1-3): left visible, the compiler fuses
@@ -544,7 +533,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
                 else f = __builtin_amdgcn_fmed3f(f, f * slope, pinf0);
                 v[e] = (_Float16)f;
             }
-            if (EPI == 2 && has2)
+            if (EPI == kEpiRes && has2)
             {
                 const half8 r2 = __builtin_bit_cast(half8, PRE2 ? r2q[PRE2 ? (rr & 1) : 0][n][p] : r2x[p]);
                 // v = fp16(fma(v, s2, r2)): the exact v*s2 + r2 rounded ONCE to fp32 (an explicit fma: what the contracted expression of
@@ -564,7 +553,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
             __builtin_amdgcn_sched_barrier(0); // one plane at a time: interleaved, the two planes' temporaries do not fit the 168-VGPR kernels
         }
     };
-    // EPI 4 / 5, one row of one n-tile: everything in fp32, one rounding (see the template comment).  l1 / r2h / r2l: this lane's 16
+    // EPI 4 / 5, one row of one n-tile: everything in fp32, one rounding (kernels.h FlowEpi).  l1 / r2h / r2l: this lane's 16
     // bytes per plane of residual 1's lo planes, of residual 2 and of residual 2's lo planes (the latter two: EPI 5 only).
     constexpr float kLoScale = 2048.f, kLoInv = 1.f / 2048.f;
     auto row_emit4 = [&](const f32x16& acc, const OutDesc& o, int rr, int n, const u32x4& l1, const u32x4 (&r2h)[2], const u32x4& r2l) {
@@ -594,7 +583,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
                     const f32x2 av = {acc[c0], acc[c0 + 1]};
                     const f32x2 kinv = {kLoInv, kLoInv}, s1v = {a.s1, a.s1};
                     f32x2 f = __builtin_elementwise_fma(bf8_pair(l1[p * 2 + k], e2), kinv, av * s1v);
-                    if (EPI == 5)
+                    if (EPI == kEpiPrec2)
                     {
                         const f32x2 rv = {(float)r[k * 4 + e2 * 2], (float)r[k * 4 + e2 * 2 + 1]}, s2v = {a.s2, a.s2};
                         f = __builtin_elementwise_fma(bf8_pair(r2l[p * 2 + k], e2), kinv, __builtin_elementwise_fma(f, s2v, rv));
@@ -920,7 +909,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
         // strip whenever they hit the first, and the tables never fold a pair of block rows that reaches into the top margin
         // (engine.cpp append_block_items) -- so this expression, whose exact shape the register allocation of every instantiation
         // hangs on (+90 VGPRs and spills for a second pair of compares here, round 5), stays as it was.
-        return (y >= w.H - a.margin || y + 4 <= a.margin) && !(a.dbg & 32);
+        return (y >= w.H - a.margin || y + 4 <= a.margin) && !(a.dbg & kDbgAllRows);
     };
     auto skip_block = [&]() {
         {
@@ -1121,17 +1110,17 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
                 // residual 2 and of both residuals' lo planes are fetched here, rows 2-3 into the same registers once rows 0-1 are
                 // through: two exposed round trips per block, in 24 of the 352 launches.
                 const OutDesc o = make_out(it, true);
-                if (EPI == 4)
+                if (EPI == kEpiPrec)
                 {
                     const u32x4 (&nor)[2] = r2q[0][0]; // (not read)
 #pragma unroll
-                    for (int rr = RSR_PREC_PRE; rr < 4; rr++) lo_row(a.res1, a.lo1_off, l1q[EPI == 4 ? rr : 0], o, rr, 0);
+                    for (int rr = RSR_PREC_PRE; rr < 4; rr++) lo_row(a.res1, a.lo1_off, l1q[EPI == kEpiPrec ? rr : 0], o, rr, 0);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int rr = 0; rr < 4; rr++)
                     {
                         if (rr == 3) refill();
-                        row_emit4(accA[rr][0], o, rr, 0, l1q[EPI == 4 ? rr : 0], nor, l1q[0]);
+                        row_emit4(accA[rr][0], o, rr, 0, l1q[EPI == kEpiPrec ? rr : 0], nor, l1q[0]);
                     }
                 }
                 else
@@ -1164,7 +1153,7 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
                     if (rr == 3) refill();
 #pragma unroll
                     for (int n = 0; n < NTW; n++) row_emit(accA[rr][n], o, rr, n);
-                    if (EPI == 2 && rr == 1) res2_prefetch(it, 2);
+                    if (EPI == kEpiRes && rr == 1) res2_prefetch(it, 2);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1288,154 +1277,146 @@ __global__ __launch_bounds__((4 * NT / NTW + 4) * 64, (4 * NT / NTW + 4) / 4) vo
 // ---- launch ------------------------------------------------------------------------------------
 constexpr int kLdsMax = 160 * 1024;
 
-template <int NT, int NTW, bool UPS, int EPI, bool DEFER>
-static hipError_t flow_attr()
+// EVERY instantiation there is, listed ONCE: the per-device opt-in to > 64 KiB of dynamic LDS, the launch and flow_variant_exists all
+// read this list.  F(NT, NTW, UPS, EPI, DEFER, STREAMED) -- STREAMED: the WRES = false kernel exists next to the resident one (the
+// (dy, cout) conv_last is resident only: its 3-KiB-per-plane aux image always fits).
+#define RSR_FLOW_VARIANTS(F)                                                                                                        \
+    F(1, 1, false, kEpiLast3, false, false) F(1, 1, false, kEpiLast3F32, false, false) F(1, 1, false, kEpiLast3Img, false, false)    \
+    F(1, 1, false, kEpiLast3ImgF32, false, false)                                                                                    \
+    F(1, 1, false, kEpiLastG, false, true) F(1, 1, false, kEpiPlain, false, true) F(1, 1, false, kEpiPlain, true, true)              \
+    F(1, 1, false, kEpiRes, false, true) F(1, 1, false, kEpiLastGF32, false, true) F(1, 1, false, kEpiLastGImg, false, true)         \
+    F(1, 1, false, kEpiLastGImgF32, false, true)                                                                                     \
+    F(1, 1, true, kEpiPlain, false, true)                                                                                            \
+    F(2, 1, false, kEpiPlain, false, true) F(2, 1, false, kEpiRes, false, true) F(2, 1, true, kEpiPlain, false, true)                \
+    F(2, 1, false, kEpiPrec, false, true) F(2, 1, false, kEpiPrec2, false, true)                                                     \
+    F(2, 2, false, kEpiPlain, false, true) F(2, 2, false, kEpiRes, false, true) F(2, 2, true, kEpiPlain, false, true)
+
+template <int NT, int NTW, bool UPS, int EPI, bool DEFER, bool WRES, bool EXISTS>
+static const void* flow_fn()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<NT, NTW, UPS, EPI, DEFER, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, FlowCfg<NT>::TOTAL);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<NT, NTW, UPS, EPI, DEFER, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-    return e;
+    if constexpr (EXISTS) return reinterpret_cast<const void*>(&conv3x3_flow<NT, NTW, UPS, EPI, DEFER, WRES>);
+    else return nullptr;
 }
 
-// patch ring depth a resident-weight launch can afford (0: the weights do not fit next to 3 patches)
-template <int NT>
-static int resident_ring(int nst, int reserve)
+struct FlowVariant
 {
-    const int rest = kLdsMax - nst * FlowCfg<NT>::WB - reserve - NT * 128;
-    const int pr = rest / kFPatch;
-    return pr < 3 ? 0 : (pr > 6 ? 6 : pr);
-}
+    int nt, ntw;
+    bool ups;
+    int epi;
+    bool defer;
+    const void* fn[2]; // [WRES]; null: there is no such kernel
+};
+static const FlowVariant kFlowVariants[] = {
+#define RSR_F(NT, NTW, UPS, EPI, DEFER, STREAMED)                                                                                   \
+    {NT, NTW, UPS, EPI, DEFER, {flow_fn<NT, NTW, UPS, EPI, DEFER, false, STREAMED>(), flow_fn<NT, NTW, UPS, EPI, DEFER, true, true>()}},
+    RSR_FLOW_VARIANTS(RSR_F)
+#undef RSR_F
+};
 
-template <int NT, int NTW, bool UPS, int EPI, bool DEFER>
-static void flow_launch(const ConvArgs& a_in, int ncu, bool resident, int reserve, hipStream_t st)
+static const void* flow_kernel(int nt, int ntw, bool ups, int epi, bool defer, bool wres)
 {
-    int grid = ncu & ~7;
-    const int per = (a_in.nitems + 7) / 8;
-    if (per * 8 < grid) grid = per * 8;
-    const int nst = a_in.n0 + a_in.n1;
-    const int pr = resident ? resident_ring<NT>(nst, reserve * NT) : 0; // (measured: a ring of 3 is as fast as one of 5 -- depth is not a limit)
-    if (pr)
-    {
-        ConvArgs a = a_in;
-        a.pr = pr;
-        const int lds = pr * kFPatch + nst * FlowCfg<NT>::WB + NT * 128;
-        hipLaunchKernelGGL((conv3x3_flow<NT, NTW, UPS, EPI, DEFER, true>), dim3(grid), dim3((4 * NT / NTW + 4) * 64), lds, st, a);
-    }
-    else
-        hipLaunchKernelGGL((conv3x3_flow<NT, NTW, UPS, EPI, DEFER, false>), dim3(grid), dim3((4 * NT / NTW + 4) * 64), FlowCfg<NT>::TOTAL, st, a_in);
+    for (const FlowVariant& v : kFlowVariants)
+        if (v.nt == nt && v.ntw == ntw && v.ups == ups && v.epi == epi && v.defer == defer) return v.fn[wres];
+    return nullptr;
 }
+bool flow_variant_exists(int nt, int ntw, bool ups, int epi, bool defer, bool wres) { return flow_kernel(nt, ntw, ups, epi, defer, wres) != nullptr; }
 
-// every instantiation the engine can reach, for the per-device opt-in to > 64 KiB of dynamic LDS
-#define RSR_FLOW_VARIANTS(F)                                                                                         \
-    F(1, 1, false, 0, false) F(1, 1, false, 1, false) F(1, 1, false, 1, true) F(1, 1, false, 2, false) F(1, 1, false, 7, false) \
-    F(1, 1, false, 10, false) F(1, 1, false, 11, false)                                                              \
-    F(1, 1, true, 1, false)                                                                                          \
-    F(2, 1, false, 1, false) F(2, 1, false, 2, false) F(2, 1, true, 1, false) F(2, 1, false, 4, false) F(2, 1, false, 5, false) \
-    F(2, 2, false, 1, false) F(2, 2, false, 2, false) F(2, 2, true, 1, false)
+static int flow_wb(int nt) { return nt == 1 ? FlowCfg<1>::WB : FlowCfg<2>::WB; }                 // bytes of one weight image
+static int flow_streamed_lds(int nt) { return nt == 1 ? FlowCfg<1>::TOTAL : FlowCfg<2>::TOTAL; } // LDS of a streamed-weight launch
 
 hipError_t flow_init_device()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<1, 1, false, 3, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<1, 1, false, 6, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<1, 1, false, 8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_flow<1, 1, false, 9, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-#define RSR_F(NT, NTW, UPS, EPI, DEFER)                                                                              \
-    if (e == hipSuccess) e = flow_attr<NT, NTW, UPS, EPI, DEFER>();
-    RSR_FLOW_VARIANTS(RSR_F)
-#undef RSR_F
+    hipError_t e = hipSuccess;
+    for (const FlowVariant& v : kFlowVariants)
+        for (int wres = 0; wres < 2; wres++)
+            if (e == hipSuccess && v.fn[wres])
+                e = hipFuncSetAttribute(v.fn[wres], hipFuncAttributeMaxDynamicSharedMemorySize, wres ? kLdsMax : flow_streamed_lds(v.nt));
     return e;
 }
 
-// flags: bit 0 = two n-tiles per MFMA wave for the 64-output-channel convs (4 MFMA waves), bit 1 = no deferred epilogue,
-//        bit 2 = weights re-streamed per block even where they would fit in LDS for the whole launch,
-//        bit 3 = conv_last through the generic 32-output-channel path (9 taps x 32 padded couts) instead of (dy, cout) in M
-bool launch_conv_flow(const ConvArgs& a_in, int nt, int ncu, int flags, hipStream_t st)
+// patch ring depth a resident-weight launch can afford next to nst resident images of plane_bytes each (0: they do not fit next to
+// 3 patches).  (measured: a ring of 3 is as fast as one of 5 -- depth is not a limit)
+static int resident_ring(int nst, int plane_bytes, int nt)
 {
-    if (a_in.nitems <= 0) return true;
-    ConvArgs a = a_in;
+    const int pr = (kLdsMax - nst * plane_bytes - nt * 128) / kFPatch;
+    return pr < 3 ? 0 : (pr > 6 ? 6 : pr);
+}
+
+// Which kernel runs a ConvArgs, and how: the epilogue is read off the outputs and residuals that are set, the rest off `flags` (kFlow*
+// of kernels.h).  No HIP call in here.
+FlowChoice choose_conv_flow(const ConvArgs& a_in, int nt, int ncu, int flags, FlowPlan& p)
+{
+    if (a_in.nitems <= 0) return kFlowNothing;
+    ConvArgs& a = p.args;
+    a = a_in;
     if (a.res1_kind == 1 && !a.res1_in_acc)
     {
         // a first residual that is not this conv's own input (trunk_conv: fea + trunk) is fetched through the second
         // residual's slot: fp16(s1*acc)*1 + r rounds exactly like fp16(s1*acc) + r
-        if (a.res2_kind) return false;
+        if (a.res2_kind) return kFlowNotCovered;
         a.res2 = a.res1;
         a.lo2_off = a.lo1_off;
         a.lo1_off = 0;
         a.res2_kind = 1;
         a.s2 = 1.f;
     }
-    if (((a.n0 + a.n1) & 1) || !a.wpk16) return false;
-    const bool ups = a.lvl_out != a.lvl_in;
-    int epi = 0;
+    const int nst = a.n0 + a.n1;
+    if ((nst & 1) || !a.wpk16 || (nt != 1 && nt != 2)) return kFlowNotCovered;
+    p.nt = nt;
+    p.ups = a.lvl_out != a.lvl_in;
+    EpiDesc d = {kFormLast, false, false, false};
     if (a.out16.base && !a.out_planar3 && !a.out_u8)
     {
-        if (a.res1_kind == 0 && a.res2_kind == 0) epi = 1;
-        else if (a.res1_kind == 1 && (a.res2_kind == 0 || a.res2_kind == 1)) epi = 2;
-        else return false;
+        if (a.res1_kind == 0 && a.res2_kind == 0) d.form = kFormPlain;
+        else if (a.res1_kind == 1 && (a.res2_kind == 0 || a.res2_kind == 1)) d.form = kFormRes;
+        else return kFlowNotCovered;
         // the precise residual stream: every residual form, and a plain conv that starts the stream (conv_first: its lo planes are kept)
-        if (a.precise && (epi == 2 || (epi == 1 && a.out_lo_off && !a.lrelu && !ups))) epi = a.res2_kind ? 5 : 4;
-        if (epi >= 4 && !a.res1_kind) a.res1 = a.out16; // (conv_first: lo1_off == 0, the null resource is built on a valid base)
+        if (a.precise && (d.form == kFormRes || (d.form == kFormPlain && a.out_lo_off && !a.lrelu && !p.ups))) d.form = a.res2_kind ? kFormPrec2 : kFormPrec;
+        if (d.prec() && !a.res1_kind) a.res1 = a.out16; // (conv_first: lo1_off == 0, the null resource is built on a valid base)
     }
-    else if ((!a.out_planar3 && !a.out_u8) || a.out16.base || a.res1_kind || a.res2_kind) return false;
+    else if ((!a.out_planar3 && !a.out_u8) || a.out16.base || a.res1_kind || a.res2_kind) return kFlowNotCovered;
+    else
+    { // conv_last: into the planar blob, or fused with the post-processing into the caller's image
+        d.dycout = a.waux && !(flags & kFlowLastGeneric);
+        d.out32 = a.precise != 0;
+        d.fimg = a.out_u8 && a.out_fmt != kFmtU8;
+    }
+    p.epi = epi_of(d);
+    // (the precise residual forms exist in the 8 x 32 wave layout only: their epilogue needs its SGPRs)
+    p.ntw = (nt == 2 && (flags & kFlowNtw2) && !d.prec()) ? 2 : 1;
     // (the deferred epilogue's block body is written out for half-stages 0..3 -- the hooks ride in them -- so it needs >= 4: a conv with
     // cin <= 32, which the network does not have but rsr_conv3x3 accepts, runs the inline epilogue)
-    const bool ntw2 = (flags & 1) != 0, defer = !(flags & 2) && a.n0 + a.n1 >= 4, res = !(flags & 4);
-    const int reserve = (flags & 16) ? 8192 : 0; // A/B aid: size the patch ring as if the rounds 1-3 transpose scratch (8 KB per n-tile) were still there
-    if (nt == 1)
-    {
-        if (epi == 0 && !ups && a.waux && !(flags & 8))
-        { // conv_last with (dy, cout) in the MFMA's M dimension: the 3-KB-per-plane aux image, always resident
-            const int nst = a.n0 + a.n1;
-            int pr = (kLdsMax - nst * 3072 - 128) / kFPatch;
-            pr = pr > 6 ? 6 : pr;
-            if (pr < 3) return false;
-            a.wpk16 = a.waux;
-            a.wpieces = 3;
-            a.pr = pr;
-            int grid = ncu & ~7;
-            const int per = (a.nitems + 7) / 8;
-            if (per * 8 < grid) grid = per * 8;
-            const bool fimg = a.out_u8 && a.out_fmt != kFmtU8; // the fused image is planar fp16 / fp32
-            if (fimg && a.precise) hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 9, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
-            else if (fimg) hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 8, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
-            else if (a.precise) hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 6, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
-            else hipLaunchKernelGGL((conv3x3_flow<1, 1, false, 3, false, true>), dim3(grid), dim3(512), pr * kFPatch + nst * 3072 + 128, st, a);
-        }
-        else if (epi == 0 && !ups && a.out_u8 && a.out_fmt != kFmtU8 && a.precise) flow_launch<1, 1, false, 11, false>(a, ncu, res, reserve, st);
-        else if (epi == 0 && !ups && a.out_u8 && a.out_fmt != kFmtU8) flow_launch<1, 1, false, 10, false>(a, ncu, res, reserve, st);
-        else if (epi == 0 && !ups && a.precise) flow_launch<1, 1, false, 7, false>(a, ncu, res, reserve, st);
-        else if (epi == 0 && !ups) flow_launch<1, 1, false, 0, false>(a, ncu, res, reserve, st);
-        else if (epi == 1 && !ups && defer) flow_launch<1, 1, false, 1, true>(a, ncu, res, reserve, st);
-        else if (epi == 1 && !ups) flow_launch<1, 1, false, 1, false>(a, ncu, res, reserve, st);
-        else if (epi == 1) flow_launch<1, 1, true, 1, false>(a, ncu, res, reserve, st);
-        else if (epi == 2 && !ups) flow_launch<1, 1, false, 2, false>(a, ncu, res, reserve, st);
-        else return false;
-        return true;
+    p.defer = nt == 1 && d.form == kFormPlain && !p.ups && !(flags & kFlowInlineEpi) && nst >= 4;
+    int plane_bytes = flow_wb(nt);
+    bool resident = !(flags & kFlowStreamW);
+    if (d.last3())
+    { // (dy, cout) in the MFMA's M dimension: the 3-KiB-per-plane aux image, always resident
+        a.wpk16 = a.waux;
+        a.wpieces = 3;
+        plane_bytes = a.wpieces * 1024;
+        resident = true;
     }
-    if (nt != 2 || epi == 0) return false;
-    if (ntw2 && epi < 4) // (the precise residual forms exist in the 8 x 32 wave layout only: their epilogue needs its SGPRs)
-    {
-        if (epi == 1 && !ups) flow_launch<2, 2, false, 1, false>(a, ncu, res, reserve, st);
-        else if (epi == 1) flow_launch<2, 2, true, 1, false>(a, ncu, res, reserve, st);
-        else if (epi == 2 && !ups) flow_launch<2, 2, false, 2, false>(a, ncu, res, reserve, st);
-        else return false;
-    }
-    else
-    {
-        if (epi == 1 && !ups) flow_launch<2, 1, false, 1, false>(a, ncu, res, reserve, st);
-        else if (epi == 1) flow_launch<2, 1, true, 1, false>(a, ncu, res, reserve, st);
-        else if (epi == 4 && !ups) flow_launch<2, 1, false, 4, false>(a, ncu, res, reserve, st);
-        else if (epi == 5 && !ups) flow_launch<2, 1, false, 5, false>(a, ncu, res, reserve, st);
-        else if (epi == 2 && !ups) flow_launch<2, 1, false, 2, false>(a, ncu, res, reserve, st);
-        else return false;
-    }
+    p.pr = resident ? resident_ring(nst, plane_bytes, nt) : 0;
+    if (d.last3() && !p.pr) return kFlowNotCovered;
+    p.wres = p.pr != 0; // weights that do not fit next to 3 patches are streamed
+    if (p.wres) a.pr = p.pr;
+    p.lds = p.wres ? p.pr * kFPatch + nst * plane_bytes + nt * 128 : flow_streamed_lds(nt);
+    p.grid = ncu & ~7;
+    const int per = (a.nitems + 7) / 8;
+    if (per * 8 < p.grid) p.grid = per * 8;
+    p.block = (4 * nt / p.ntw + 4) * 64;
+    return flow_variant_exists(nt, p.ntw, p.ups, p.epi, p.defer, p.wres) ? kFlowLaunch : kFlowNotCovered;
+}
+
+bool launch_conv_flow(const ConvArgs& a, int nt, int ncu, int flags, hipStream_t st)
+{
+    FlowPlan p;
+    const FlowChoice c = choose_conv_flow(a, nt, ncu, flags, p);
+    if (c != kFlowLaunch) return c == kFlowNothing;
+    void* args[] = {&p.args};
+    (void)hipLaunchKernel(flow_kernel(p.nt, p.ntw, p.ups, p.epi, p.defer, p.wres), dim3(p.grid), dim3(p.block), args, size_t(p.lds), st);
     return true;
 }
 
 } // namespace rsr
+

@@ -540,11 +540,11 @@ static void image_tiles(int w, int h, int T, int P, int scale, int tile0, int ti
 // make_out), which must stay below the sentinel too.  Tiles beyond that (~1,400 px) must be split by the caller.
 int Engine::check_tile_px(long long cap_px) const
 {
-    const long long reach = (flow_flags & 1) ? 4 : 2; // planes an MFMA wave addresses from one base
+    const long long reach = (flow_flags & kFlowNtw2) ? 4 : 2; // planes an MFMA wave addresses from one base
     if (cap_px * 16 * 32 * reach + 4 * kGuard < (1ll << 31)) return RSR_OK;
     const long long max_px = ((1ll << 31) - 4 * kGuard - 1) / (16 * 32 * reach);
     return fail(RSR_E_ARG, "tilesize too large: a padded tile may have at most " + std::to_string(max_px) + " pixels" +
-                               ((flow_flags & 1) ? " with flow_flags bit 0 (e.g. -t 1000)" : " (e.g. -t 1400)"));
+                               ((flow_flags & kFlowNtw2) ? " with flow_flags bit 0 (e.g. -t 1000)" : " (e.g. -t 1400)"));
 }
 
 // Memory policy (the reference bounds device memory through the tile size alone, main.cpp:761-774; here ALL tiles of an image
@@ -569,7 +569,7 @@ long long Engine::budget_slots(long long cap_px, int w, int h, int c)
 int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*& out)
 {
     for (auto it = plans.begin(); it != plans.end(); ++it)
-        if (it->w == w && it->h == h && it->c == c && it->T == tilesize && it->P == prepadding && it->tta == tta && it->nimg == nimg && it->precise == precise && it->ratio == out_ratio && it->ntw2 == ((flow_flags & 1) != 0) &&
+        if (it->w == w && it->h == h && it->c == c && it->T == tilesize && it->P == prepadding && it->tta == tta && it->nimg == nimg && it->precise == precise && it->ratio == out_ratio && it->ntw2 == ((flow_flags & kFlowNtw2) != 0) &&
             it->tile0 == tile0 && it->tile1 == tile1 && it->budget_mb == max_workspace_mb && it->trim == trim_tail && it->xcd_order == xcd_order && it->fold == fold_cols &&
             it->clamp == ws_clamp_bytes)
         {
@@ -602,7 +602,7 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
     plan.nimg = nimg;
     plan.precise = precise;
     plan.ratio = out_ratio;
-    plan.ntw2 = (flow_flags & 1) != 0;
+    plan.ntw2 = (flow_flags & kFlowNtw2) != 0;
     plan.tile0 = tile0; plan.tile1 = tile1;
     plan.budget_mb = max_workspace_mb;
     plan.trim = trim_tail;
@@ -1079,7 +1079,7 @@ int Engine::enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size
         if (ntiles <= 0) break;
         // host calls: split the 4x tail at a tile-row boundary so that the first output rows can travel while the rest is computed
         io.split_slot = 0;
-        if (conv_last_writes_image(c, io.out_fmt) && nimg == 1 && io.ev_half && half_rows && plan.batches.size() == 1 && !profiling && !(dbg & 16384))
+        if (conv_last_writes_image(c, io.out_fmt) && nimg == 1 && io.ev_half && half_rows && plan.batches.size() == 1 && !profiling && !(dbg & kDbgNoSplitTail))
         {
             const int xt = xtiles, yt = b.ntiles / xt;
             if (yt >= 2 && b.ntiles == xt * yt && plan.tile0 % xt == 0)
@@ -1111,7 +1111,7 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
 {
     constexpr int pc = plane_ch();
     const int per = tta ? 8 : 1, c = io.c;
-    const int variant = (dbg & 32768) ? 1 : ((dbg & 65536) ? 2 : 0);
+    const int variant = (dbg & kDbgPrePostVar1) ? 1 : ((dbg & kDbgPrePostVar2) ? 2 : 0);
     PreArgs pa;
     std::memset(&pa, 0, sizeof pa);
     PostArgs po;

@@ -104,7 +104,7 @@ struct Plan
     int nimg = 1;         // images of this geometry merged into one tile batch (kernels.h kMaxMerge); their tiles follow each other image by image
     bool precise = false; // Engine::precise when the plan was built (the slots are larger: part of the cache key)
     OutRatio ratio;       // Engine::out_ratio when the plan was built (part of the cache key, though no field of a Plan depends on it today: the placement tables are built alike and below 4 merely go unused)
-    bool ntw2 = false;    // flow_flags bit 0 when the plan was built (an MFMA wave then reaches 4 planes from one base: the tile-size bound halves)
+    bool ntw2 = false;    // flow_flags has kFlowNtw2 when the plan was built (an MFMA wave then reaches 4 planes from one base: the tile-size bound halves)
     int tile0 = 0, tile1 = 0; // tiles [tile0, tile1) of the image's tile grid, row-major (multi-GPU tile sharding)
     long long budget_mb = 0;
     bool trim = true, xcd_order = true, fold = true;
@@ -301,7 +301,7 @@ struct Engine
     int selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* out); // mu held
     int apply_precise_auto();                                                      // mu held, loaded: self-check on the built-in tile -> precise
     long long bytes_per_px() const; // workspace bytes per padded LR pixel of a slot
-    int flow_flags = 0; // launch_conv_flow flags
+    int flow_flags = 0; // kFlow* bits of kernels.h
     int num_cu = 256;
     int dbg = 0; // ConvArgs::dbg ablation bits (profiling only)
     bool trim_tail = true; // leave out the blocks / rows behind the trunk that only feed cropped output pixels (engine.cpp: tail_margin)
@@ -457,8 +457,8 @@ struct Engine
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
-    // no TTA merge / alpha channel / box reduction / YUV surface needs the planar blob (dbg 8192: off)
-    bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & 8192); }
+    // no TTA merge / alpha channel / box reduction / YUV surface needs the planar blob (kDbgNoFusedLast: off)
+    bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & kDbgNoFusedLast); }
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
     // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).

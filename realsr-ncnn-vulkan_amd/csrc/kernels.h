@@ -128,14 +128,14 @@ struct ConvArgs
     // weights: packed LDS images [plane of 16 cin][9 taps][NT*32 cout][16 cin]; bias fp32 [NT*32]
     const void* wpk16;
     const void* waux; // conv_last only: [plane of 16 cin][dx 0..2][row = dy*8 + cout][16 cin] (PackedConv::aux_off), or null
-    int wpieces;      // 1-KiB pieces per plane of the resident image (set by launch_conv_flow)
+    int wpieces;      // 1-KiB pieces per plane of the resident image (set by choose_conv_flow)
     const float* bias;
     int lrelu; // LeakyReLU(0.2) on (acc + bias)
     // Output pixels closer than `margin` to the tile border (at this conv's output level) are never read by anything that
     // reaches the cropped output rectangle (engine.cpp: tail_margins): MFMA waves whose four rows lie wholly inside that frame
     // skip their block like rows below the tile.  0 = every pixel is needed.
     int margin;
-    int pr; // patch ring depth of a resident-weight launch (set by launch_conv_flow)
+    int pr; // patch ring depth of a resident-weight launch (set by choose_conv_flow)
     // residual stages: v = v*s + r  (r = fp16 planes)
     PlaneSrc res1, res2;
     int res1_kind, res2_kind; // 0 none, 1 fp16 planes
@@ -182,8 +182,100 @@ struct ConvArgs
     long long out_plane[kMaxMerge];
 };
 
-// conv_flow.hip: half-stage ring on 16-channel planes.  flags: 1 = two n-tiles per MFMA wave for 64-cout convs, 2 = no deferred epilogue,
-// 4 = weights always streamed (never LDS-resident), 8 = conv_last through the generic path.
+// ---- conv3x3_flow (conv_flow.hip: half-stage ring on 16-channel planes) -------------------------------------------------------------
+// The bits of the engine option "flow_flags" (include/realsr_hip.h has the user's wording; the values are public) ...
+constexpr int kFlowNtw2 = 1;        // two n-tiles per MFMA wave for the 64-output-channel convs: 4 MFMA waves x 64 channels, not 8 x 32
+constexpr int kFlowInlineEpi = 2;   // no deferred epilogue for the 32-output-channel convs
+constexpr int kFlowStreamW = 4;     // weights re-streamed per block even where they would fit in LDS for the whole launch
+constexpr int kFlowLastGeneric = 8; // conv_last through the generic 32-output-channel path instead of (dy, cout) in M
+// ... and those of the engine option "dbg" that exist in the product build (the ablation bits 1 / 4 / 64 / 128 of ConvArgs::dbg act in
+// -DRSR_EXPERIMENT builds only: conv_flow.hip RSR_ABL)
+constexpr int kDbgAllRows = 32;          // MFMA waves compute the rows they would skip (a test hook: results unchanged)
+constexpr int kDbgNoFusedLast = 8192;    // conv_last never writes the caller's image itself
+constexpr int kDbgNoSplitTail = 16384;   // no split tail for the early download
+constexpr int kDbgPrePostVar1 = 32768, kDbgPrePostVar2 = 65536; // force variant 1 / 2 of the pre and post kernels (PreArgs::variant)
+
+// The EPILOGUES of conv3x3_flow: the values of its template parameter EPI.  EPI stays an int (the numbers are part of the kernels'
+// symbol names, which profiles/, tools/ and bench.py's report quote; DESIGN.md, README.md and the tests speak of "EPI 4 / 5"), but
+// nothing outside this definition writes a number for one.
+//   kEpiPlain (1)            v = act(acc) -> fp16 planes
+//   kEpiRes (2)              v = s1*acc (the conv's own input rides in the accumulator as an identity tap) [, v = s2*v + r2] -> fp16 planes
+//   kEpiPrec / kEpiPrec2 (4 / 5)  the PRECISE forms of kEpiRes without / with the second residual (engine option "precise"; 64 output
+//        channels): the residual stream is kept as hi + lo / 2048, hi an fp16 plane as ever and lo ONE BYTE per element (bf8 = e5m2: the
+//        upper byte of an fp16; ConvArgs::precise) -- v = s1*acc + lo1/2048 [, v = s2*v + r2 + lo2/2048] in fp32, then ONE rounding:
+//        hi = fp16(v) -> out16 (what the next convs read), lo = bf8((v - hi) * 2048) -> the output's lo planes (16 B per pixel).  The
+//        reference's GPU path rounds the trunk 92 times on its way through the 23 RRDBs (fp16 storage, realsr.cpp:44-46); this halves the
+//        engine's distance to the fp32 CPU path (realsr.cpp:525-838; profiles/r06_storage_emulation.txt).  Absent lo planes are read
+//        through a null buffer resource (zeros, no memory access) and written into one: the epilogue is branch-free.
+//   kEpiLast* (0, 3, 6 .. 11)  conv_last, eight of them = 2 layouts x fp32 kept or not x 2 kinds of output:
+//        layout: "3" = (dy, cout) in the MFMA's M dimension (3 / 6 / 8 / 9), "G" = the generic 32-output-channel path (0 / 7 / 10 / 11);
+//        F32 (6 / 7 / 9 / 11; precise mode): conv_last's fp32 result goes to the uint8 conversion (or a planar fp32 blob) without the fp16
+//        rounding of the reference's `output` blob in between;
+//        Img (8 .. 11): the fused image is the caller's PLANAR FLOAT one (ConvArgs::out_fmt: fp16 or fp32, chosen at run time), not the
+//        uint8 one / the planar blob -- instantiations of their own, so that the uint8 kernels keep their registers.
+enum FlowEpi : int
+{
+    kEpiLastG = 0, kEpiPlain = 1, kEpiRes = 2, kEpiLast3 = 3, kEpiPrec = 4, kEpiPrec2 = 5, kEpiLast3F32 = 6, kEpiLastGF32 = 7,
+    kEpiLast3Img = 8, kEpiLast3ImgF32 = 9, kEpiLastGImg = 10, kEpiLastGImgF32 = 11, kEpiCount = 12
+};
+enum FlowEpiForm : int { kFormPlain, kFormRes, kFormPrec, kFormPrec2, kFormLast };
+struct EpiDesc
+{
+    int form;    // FlowEpiForm
+    bool dycout; // conv_last's layout: (dy, cout) in M; false: generic
+    bool out32;  // conv_last: the fp32 result is kept (converted / stored without an fp16 rounding in between)
+    bool fimg;   // conv_last: the output is a planar float image
+    constexpr bool last3() const { return form == kFormLast && dycout; }
+    constexpr bool lastg() const { return form == kFormLast && !dycout; }
+    constexpr bool resid() const { return form == kFormRes || form == kFormPrec || form == kFormPrec2; } // residual forms
+    constexpr bool prec() const { return form == kFormPrec || form == kFormPrec2; }                       // ... with the hi + lo residual stream
+    constexpr bool operator==(const EpiDesc& o) const { return form == o.form && dycout == o.dycout && out32 == o.out32 && fimg == o.fimg; }
+};
+constexpr __host__ __device__ EpiDesc epi_desc(int epi)
+{
+    switch (epi)
+    {
+    case kEpiPlain: return {kFormPlain, false, false, false};
+    case kEpiRes: return {kFormRes, false, false, false};
+    case kEpiPrec: return {kFormPrec, false, false, false};
+    case kEpiPrec2: return {kFormPrec2, false, false, false};
+    case kEpiLast3: return {kFormLast, true, false, false};
+    case kEpiLast3F32: return {kFormLast, true, true, false};
+    case kEpiLast3Img: return {kFormLast, true, false, true};
+    case kEpiLast3ImgF32: return {kFormLast, true, true, true};
+    case kEpiLastG: return {kFormLast, false, false, false};
+    case kEpiLastGF32: return {kFormLast, false, true, false};
+    case kEpiLastGImg: return {kFormLast, false, false, true};
+    default: return {kFormLast, false, true, true}; // kEpiLastGImgF32
+    }
+}
+// the epilogue that IS this description
+constexpr int epi_of(const EpiDesc& d)
+{
+    for (int e = 0; e < kEpiCount; e++)
+        if (epi_desc(e) == d) return e;
+    return -1;
+}
+
+// What launch_conv_flow launches for a ConvArgs: the kernel (a row of conv_flow.hip's variant list), its launch geometry and its
+// argument.  Pure host arithmetic -- choose_conv_flow makes no HIP call (tools/host_check runs it without a GPU).
+struct FlowPlan
+{
+    int nt, ntw;      // conv3x3_flow<nt, ntw, ups, epi, defer, wres>
+    bool ups;
+    int epi;          // FlowEpi
+    bool defer, wres;
+    int pr;           // patch ring depth of a resident-weight launch (= args.pr), 0 when the weights are streamed
+    int lds;          // dynamic LDS bytes
+    int grid, block;
+    // the ConvArgs as the kernel gets them: a first residual that is not the conv's own input moved into the second residual's slot
+    // (trunk_conv), res1 = out16 for the precise conv_first, wpk16 = waux with wpieces = 3 for the (dy, cout) conv_last, pr
+    ConvArgs args;
+};
+enum FlowChoice : int { kFlowNothing, kFlowLaunch, kFlowNotCovered }; // kFlowNothing: no work items, nothing to launch (a success)
+// flags: kFlow* above.  nt: n-tiles (32 output channels) of the conv, ncu: the persistent grid's size
+FlowChoice choose_conv_flow(const ConvArgs& a, int nt, int ncu, int flags, FlowPlan& plan);
+bool flow_variant_exists(int nt, int ntw, bool ups, int epi, bool defer, bool wres); // a row of the variant list with this WRES
 // false = this combination of outputs / residuals is not covered (the engine then reports an error)
 bool launch_conv_flow(const ConvArgs& a, int nt, int ncu, int flags, hipStream_t st);
 // Opt-in to > 64 KiB of dynamic LDS for every kernel instantiation, on the CURRENT device (call once per device).
@@ -231,7 +323,7 @@ struct PreArgs
     long long slot_stride;
     int bgr;
     int plane_ch;   // 16
-    int variant;    // 0 default (launch_preproc_tiles picks), 1 one thread per pixel (engine dbg 32768), 2 LDS-staged (dbg 65536; uint8 sources only)
+    int variant;    // 0 default (launch_preproc_tiles picks), 1 one thread per pixel (engine dbg kDbgPrePostVar1), 2 LDS-staged (kDbgPrePostVar2; uint8 sources only)
     YuvCoef yuv;    // YUV formats only
     int siting;     // ... likewise: where a chroma sample sits in its luma quad (engine option "yuv_siting"): 0 centre, 1 left, 2 top-left
                     // (a 4:2:2 surface has no vertical siting: 2 is 1 there)
@@ -260,7 +352,7 @@ struct PostArgs
     const uint8_t* in_imgs[kMaxMerge]; // for alpha (c==4): the source images (w x h x 4)
     int tilesize;
     int bgr;
-    int variant; // 0 default (LDS-staged under TTA, else one thread per pixel), 1 per-pixel (engine dbg 32768), 2 LDS-staged (dbg 65536)
+    int variant; // 0 default (LDS-staged under TTA, else one thread per pixel), 1 per-pixel (engine dbg kDbgPrePostVar1), 2 LDS-staged (kDbgPrePostVar2)
                  // (a planar 4:4:4 surface: 1 one pixel per thread, 2 two neighbouring pixels, 0 two at out_scale 4 and one elsewhere --
                  // with_pixels_per_thread)
     // Box-reduced output (engine option "out_scale"): 0 / 1 = the x4 image as above; 2 / 4 = every K x K box of x4 pixels, each clamped

@@ -6,6 +6,8 @@
 //      valid layouts: packed, strided, n = 16 -- one format of every family (uint8 HWC, planar float, YUV 4:2:0, 4:2:2, 4:4:4).
 //   1b. out_admit: the engine's wording of every kind of refusal, and the sizes each family takes.
 //   2. fill_batch: batches of 1, 7 and 60 tiles with and without TTA; every table entry is read back and range-checked.
+//   3. choose_conv_flow: which conv3x3_flow kernel, patch ring, LDS size and grid every convolution of the network and of rsr_conv3x3 gets
+//      under flow_flags 1 / 2 / 4 / 8 and in precise mode, against rows written out by hand; every plan names a row of the variant list.
 #include "../../realsr-ncnn-vulkan_amd/csrc/engine.cpp"
 
 #include <cinttypes>
@@ -164,11 +166,174 @@ static void batches()
             }
 }
 
+// choose_conv_flow: ConvArgs as Engine::run_network and Engine::conv_test fill them, against rows written out by hand
+static unsigned char flow_mem[64];
+static ConvArgs flow_conv(int n0, int n1, int lrelu = 0, int precise = 0)
+{
+    ConvArgs a{};
+    a.n0 = n0;
+    a.n1 = n1;
+    a.wpk16 = flow_mem;
+    a.out16.base = flow_mem + 1;
+    a.lrelu = lrelu;
+    a.precise = precise;
+    a.nitems = 1000;
+    a.pr = -7; // (a streamed launch leaves it alone)
+    return a;
+}
+static ConvArgs flow_residual(int n1, bool own_input, bool second, int precise)
+{
+    ConvArgs a = flow_conv(4, n1, 0, precise);
+    a.res1_kind = 1;
+    a.res1_in_acc = own_input;
+    a.res1.base = flow_mem + 2;
+    a.s1 = 0.2f;
+    a.lo1_off = precise ? 4096 : 0;
+    a.out_lo_off = precise ? 8192 : 0;
+    if (second)
+    {
+        a.res2_kind = 1;
+        a.res2.base = flow_mem + 3;
+        a.s2 = 0.2f;
+    }
+    return a;
+}
+static ConvArgs flow_last(int n0, int kind, int precise) // kind 0: the planar blob, 1: the uint8 image, 2: a planar float image
+{
+    ConvArgs a = flow_conv(n0, 0, 0, precise);
+    a.out16.base = nullptr;
+    a.waux = flow_mem + 4;
+    if (kind == 0) a.out_planar3 = flow_mem + 5;
+    else a.out_u8 = flow_mem + 6;
+    a.out_fmt = kind == 2 ? kFmtF32 : kFmtU8;
+    return a;
+}
+// the plan of (a, nt, flags) is conv3x3_flow<nt, ntw, ups, epi, defer, wres> with this ring, LDS and block size
+static FlowPlan flow_expect(int line, const ConvArgs& a, int nt, int flags, int ntw, bool ups, int epi, bool defer, bool wres, int pr, int lds, int block)
+{
+    FlowPlan p{};
+    const FlowChoice c = choose_conv_flow(a, nt, 256, flags, p);
+    const bool ok = c == kFlowLaunch && p.nt == nt && p.ntw == ntw && p.ups == ups && p.epi == epi && p.defer == defer && p.wres == wres && p.pr == pr &&
+                    p.lds == lds && p.block == block && p.grid == 256 && p.args.pr == (wres ? pr : -7) && flow_variant_exists(p.nt, p.ntw, p.ups, p.epi, p.defer, p.wres);
+    if (!ok)
+    {
+        std::fprintf(stderr, "%s:%d: plan <%d,%d,%d,%d,%d,%d> ring %d lds %d block %d grid %d (choice %d)\n", __FILE__, line, p.nt, p.ntw, p.ups, p.epi, p.defer, p.wres, p.pr,
+                     p.lds, p.block, p.grid, int(c));
+        failures++;
+    }
+    return p;
+}
+#define FLOW(...) flow_expect(__LINE__, __VA_ARGS__)
+static void flow_choice()
+{
+    FlowPlan p;
+    // LDS bytes, written out: resident = ring * 20480 + planes * bytes per plane + nt * 128; streamed = FlowCfg<NT>::TOTAL
+    const int kTotal1 = 150656, kTotal2 = 137472, kLast3 = 6 * 20480 + 4 * 3072 + 128;
+    for (const int precise : {0, 1})
+    {
+        // conv_first: 3 channels in two planes; in precise mode its lo planes are kept and it starts the stream
+        ConvArgs first = flow_conv(2, 0, 0, precise);
+        first.out_lo_off = precise ? 8192 : 0;
+        p = FLOW(first, 2, 0, 1, false, precise ? kEpiPrec : kEpiPlain, false, true, 6, 160000, 768);
+        CHECK(p.args.res1.base == (precise ? first.out16.base : nullptr) && p.args.res1_kind == 0);
+        FLOW(first, 2, kFlowNtw2, precise ? 1 : 2, false, precise ? kEpiPrec : kEpiPlain, false, true, 6, 160000, precise ? 768 : 512);
+        FLOW(first, 2, kFlowStreamW, 1, false, precise ? kEpiPrec : kEpiPlain, false, false, 0, kTotal2, 768);
+        // the dense convs of an RDB: x + k grown planes
+        const int ring[4] = {6, 5, 4, 3}, lds[4] = {159872, 157824, 155776, 153728};
+        for (int k = 0; k < 4; k++)
+        {
+            const ConvArgs dense = flow_conv(4, 2 * k, 1, precise);
+            FLOW(dense, 1, 0, 1, false, kEpiPlain, true, true, ring[k], lds[k], 512);
+            FLOW(dense, 1, kFlowNtw2, 1, false, kEpiPlain, true, true, ring[k], lds[k], 512);
+            FLOW(dense, 1, kFlowInlineEpi, 1, false, kEpiPlain, false, true, ring[k], lds[k], 512);
+            FLOW(dense, 1, kFlowStreamW, 1, false, kEpiPlain, true, false, 0, kTotal1, 512);
+            FLOW(dense, 1, kFlowNtw2 | kFlowInlineEpi, 1, false, kEpiPlain, false, true, ring[k], lds[k], 512);
+        }
+        // conv5: 12 planes of 18 KiB do not fit, streamed whatever the flags say
+        for (const bool second : {false, true})
+        {
+            const ConvArgs conv5 = flow_residual(8, true, second, precise);
+            const int epi = precise ? (second ? kEpiPrec2 : kEpiPrec) : kEpiRes;
+            p = FLOW(conv5, 2, 0, 1, false, epi, false, false, 0, kTotal2, 768);
+            CHECK(p.args.res1.base == conv5.res1.base && p.args.res2_kind == (second ? 1 : 0) && p.args.lo1_off == conv5.lo1_off);
+            FLOW(conv5, 2, kFlowNtw2, precise ? 1 : 2, false, epi, false, false, 0, kTotal2, precise ? 768 : 512);
+            FLOW(conv5, 2, kFlowStreamW, 1, false, epi, false, false, 0, kTotal2, 768);
+        }
+        // trunk_conv: fea is not its own input and moves into the second residual's slot
+        const ConvArgs trunk = flow_residual(0, false, false, precise);
+        p = FLOW(trunk, 2, 0, 1, false, precise ? kEpiPrec2 : kEpiRes, false, true, 4, 155904, 768);
+        CHECK(p.args.res2.base == trunk.res1.base && p.args.res2_kind == 1 && p.args.s2 == 1.f && p.args.lo2_off == trunk.lo1_off && p.args.lo1_off == 0 && p.args.res1_kind == 1);
+        FLOW(trunk, 2, kFlowNtw2, precise ? 1 : 2, false, precise ? kEpiPrec2 : kEpiRes, false, true, 4, 155904, precise ? 768 : 512);
+        FLOW(trunk, 2, kFlowStreamW, 1, false, precise ? kEpiPrec2 : kEpiRes, false, false, 0, kTotal2, 768);
+        // upconv1 / upconv2 (nearest x2 in front) and HRconv: plain in either mode
+        ConvArgs up = flow_conv(4, 0, 1, precise);
+        up.lvl_out = 1;
+        FLOW(up, 2, 0, 1, true, kEpiPlain, false, true, 4, 155904, 768);
+        FLOW(up, 2, kFlowNtw2, 2, true, kEpiPlain, false, true, 4, 155904, 512);
+        FLOW(up, 2, kFlowStreamW | kFlowInlineEpi, 1, true, kEpiPlain, false, false, 0, kTotal2, 768);
+        ConvArgs hr = flow_conv(4, 0, 1, precise);
+        hr.lvl_in = hr.lvl_out = 2;
+        FLOW(hr, 2, 0, 1, false, kEpiPlain, false, true, 4, 155904, 768);
+        FLOW(hr, 2, kFlowNtw2, 2, false, kEpiPlain, false, true, 4, 155904, 512);
+        FLOW(hr, 2, kFlowStreamW, 1, false, kEpiPlain, false, false, 0, kTotal2, 768);
+        // conv_last: the planar blob and the uint8 image run one kernel, a planar float image another
+        const int last3[3] = {precise ? kEpiLast3F32 : kEpiLast3, precise ? kEpiLast3F32 : kEpiLast3, precise ? kEpiLast3ImgF32 : kEpiLast3Img};
+        const int lastg[3] = {precise ? kEpiLastGF32 : kEpiLastG, precise ? kEpiLastGF32 : kEpiLastG, precise ? kEpiLastGImgF32 : kEpiLastGImg};
+        for (int kind = 0; kind < 3; kind++)
+        {
+            ConvArgs last = flow_last(4, kind, precise);
+            last.lvl_in = last.lvl_out = 2;
+            for (const int flags : {0, int(kFlowStreamW), kFlowNtw2 | kFlowInlineEpi})
+            {
+                p = FLOW(last, 1, flags, 1, false, last3[kind], false, true, 6, kLast3, 512);
+                CHECK(p.args.wpk16 == last.waux && p.args.wpieces == 3);
+            }
+            p = FLOW(last, 1, kFlowLastGeneric, 1, false, lastg[kind], false, true, 6, 159872, 512);
+            CHECK(p.args.wpk16 == last.wpk16);
+            FLOW(last, 1, kFlowLastGeneric | kFlowStreamW, 1, false, lastg[kind], false, false, 0, kTotal1, 512);
+            last.waux = nullptr; // a model without the aux image
+            FLOW(last, 1, 0, 1, false, lastg[kind], false, true, 6, 159872, 512);
+            CHECK(choose_conv_flow(last, 2, 256, 0, p) == kFlowNotCovered); // 64 output channels and conv_last's epilogue
+            CHECK(choose_conv_flow(flow_last(34, kind, precise), 1, 256, 0, p) == kFlowNotCovered); // (dy, cout): 34 planes leave 2 ring slots
+            FLOW(flow_last(32, kind, precise), 1, 0, 1, false, last3[kind], false, true, 3, 3 * 20480 + 32 * 3072 + 128, 512);
+        }
+    }
+    // rsr_conv3x3 / rsr_conv3x3_res (Engine::conv_test): 32 output channels with upsampling, with a residual, with few input planes
+    ConvArgs t = flow_conv(4, 0, 1);
+    t.lvl_out = 1;
+    FLOW(t, 1, 0, 1, true, kEpiPlain, false, true, 6, 159872, 512);
+    FLOW(flow_residual(0, true, false, 0), 1, 0, 1, false, kEpiRes, false, true, 6, 159872, 512);
+    FLOW(flow_residual(0, true, true, 0), 1, kFlowNtw2, 1, false, kEpiRes, false, true, 6, 159872, 512);
+    FLOW(flow_conv(2, 0, 1), 1, 0, 1, false, kEpiPlain, false, true, 6, 6 * 20480 + 2 * 9216 + 128, 512); // fewer than 4 planes never defer
+    // the grid: whole groups of 8 workgroups, no more than the work items need
+    t = flow_conv(4, 0, 1);
+    t.nitems = 9;
+    CHECK(choose_conv_flow(t, 1, 256, 0, p) == kFlowLaunch && p.grid == 16);
+    CHECK(choose_conv_flow(t, 1, 13, 0, p) == kFlowLaunch && p.grid == 8);
+    // nothing to launch
+    t.nitems = 0;
+    CHECK(choose_conv_flow(t, 1, 256, 0, p) == kFlowNothing);
+    // not covered
+    CHECK(choose_conv_flow(flow_conv(3, 0, 1), 1, 256, 0, p) == kFlowNotCovered);                     // an odd plane count
+    CHECK(choose_conv_flow(flow_residual(0, false, true, 0), 2, 256, 0, p) == kFlowNotCovered);      // a fetched first residual and a second one
+    CHECK(choose_conv_flow(flow_residual(0, true, false, 1), 1, 256, 0, p) == kFlowNotCovered);      // the precise forms have 64 output channels
+    t = flow_residual(0, true, false, 0);
+    t.lvl_out = 1;
+    CHECK(choose_conv_flow(t, 2, 256, 0, p) == kFlowNotCovered);                                     // a residual behind the upsampling
+    t = flow_conv(4, 0);
+    t.wpk16 = nullptr;
+    CHECK(choose_conv_flow(t, 1, 256, 0, p) == kFlowNotCovered);
+    CHECK(choose_conv_flow(flow_conv(4, 0), 3, 256, 0, p) == kFlowNotCovered);
+    // the description of the epilogues names each of them once
+    for (int e = 0; e < kEpiCount; e++) CHECK(epi_of(epi_desc(e)) == e);
+}
+
 int main()
 {
     descriptors();
     admission();
     batches();
+    flow_choice();
     if (failures) return std::fprintf(stderr, "%d check(s) failed\n", failures), 1;
     std::puts("descriptor_check ok");
     return 0;
