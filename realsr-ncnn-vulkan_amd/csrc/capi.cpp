@@ -650,7 +650,7 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
         double n = 0;
         if (!e.plans.empty())
             for (const auto& b : e.plans.front().batches) n += double(b.items[lvl].size());
-        *value = e.plans.empty() ? 0.0 : n / double(e.plans.front().nimg); // (a merged plan holds the tables of `nimg` images: per image)
+        *value = e.plans.empty() ? 0.0 : n / double(e.plans.front().key.nimg); // (a merged plan holds the tables of `nimg` images: per image)
     }
     else if (k == "ws_clamp_mb") *value = e.ws_clamp_bytes < 0 ? -1.0 : double(e.ws_clamp_bytes) / 1048576.0;
     else if (k == "ws_failures") *value = double(e.ws_failures);
@@ -660,7 +660,7 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "workspace_mb")
     {
         double n = 0;
-        for (const rsr::DevBuf* wb : {&e.b_in, &e.b_fea, &e.b_rdb[0], &e.b_rdb[1], &e.b_rdb[2], &e.b_up1, &e.b_up2, &e.b_hr, &e.b_out3}) n += double(wb->bytes);
+        for (const rsr::DevBuf& wb : e.ws) n += double(wb.bytes);
         *value = n / 1048576.0;
     }
     else if (k == "lanes") { std::lock_guard<std::mutex> ll(e.lane_mu); *value = double(e.lanes.size()); }

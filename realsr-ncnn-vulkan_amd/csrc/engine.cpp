@@ -91,9 +91,10 @@ Engine::~Engine()
         if (l->copy) (void)hipStreamDestroy(l->copy);
     }
     free_plans();
-    DevBuf* all[] = {&blob, &zeros, &b_in, &b_fea, &b_rdb[0], &b_rdb[1], &b_rdb[2], &b_up1, &b_up2, &b_hr, &b_out3, &trace_buf};
-    for (DevBuf* b : all)
+    for (DevBuf* b : {&blob, &zeros, &trace_buf})
         if (b->p) (void)hipFree(b->p);
+    for (DevBuf& b : ws)
+        if (b.p) (void)hipFree(b.p);
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : sync_events) (void)hipEventDestroy(e);
     if (merge_mid) (void)hipEventDestroy(merge_mid);
@@ -475,9 +476,6 @@ static hipError_t upload_batch(Plan::Batch& b, char*& d, bool xcd_order = true, 
     return err;
 }
 
-// per-slot workspace bytes per LR pixel: IN 64, FEA 128, 3 x RDB 384, UP1 4*128, UP2 16*128, HR 16*128, OUT3 16*6;
-// precise mode: + the one-byte lo planes of FEA and of the three RDB x tensors (4 x 64), OUT3 in fp32 (16*12)
-long long Engine::bytes_per_px() const { return 64 + 128 + 3 * 384 + 512 + 2048 + 2048 + 96 + (precise ? 4 * 64 + 96 : 0); }
 static constexpr size_t kMaxPlans = 8;
 
 // What the device can give this engine's workspace right now: 90 % of (free memory + the workspace it already holds) minus the
@@ -491,7 +489,7 @@ long long Engine::device_avail(int w, int h, int c)
         return -1;
     }
     long long held = 0;
-    for (const DevBuf* wb : {&b_in, &b_fea, &b_rdb[0], &b_rdb[1], &b_rdb[2], &b_up1, &b_up2, &b_hr, &b_out3}) held += (long long)wb->bytes;
+    for (const DevBuf& wb : ws) held += (long long)wb.bytes;
     long long lanes_have = 0;
     {
         std::lock_guard<std::mutex> ll(lane_mu);
@@ -535,14 +533,15 @@ static void image_tiles(int w, int h, int T, int P, int scale, int tile0, int ti
 }
 
 // The kernels address a plane through 32-bit byte offsets (raw buffer resources, out-of-range sentinel 2^31): the
-// largest plane is the 4x level, 16 * cap pixels * 32 B, and an MFMA wave reaches the 2 planes of its n-tile (4 with two n-tiles
-// per wave, flow_flags bit 0) from one base; the stores' range limit is "end of the plane + the plane's offset" (conv_flow.hip
-// make_out), which must stay below the sentinel too.  Tiles beyond that (~1,400 px) must be split by the caller.
+// largest plane is the 4x level, 16 * cap pixels * 32 B (workspace.h), and an MFMA wave reaches the 2 planes of its n-tile (4 with
+// two n-tiles per wave, flow_flags bit 0) from one base; the stores' range limit is "end of the plane + the plane's offset"
+// (conv_flow.hip make_out), which must stay below the sentinel too.  Tiles beyond that (~1,400 px) must be split by the caller.
 int Engine::check_tile_px(long long cap_px) const
 {
     const long long reach = (flow_flags & kFlowNtw2) ? 4 : 2; // planes an MFMA wave addresses from one base
-    if (cap_px * 16 * 32 * reach + 4 * kGuard < (1ll << 31)) return RSR_OK;
-    const long long max_px = ((1ll << 31) - 4 * kGuard - 1) / (16 * 32 * reach);
+    constexpr long long plane_px = WsLayout::max_plane_px_bytes();
+    if (cap_px * plane_px * reach + 4 * kGuard < (1ll << 31)) return RSR_OK;
+    const long long max_px = ((1ll << 31) - 4 * kGuard - 1) / (plane_px * reach);
     return fail(RSR_E_ARG, "tilesize too large: a padded tile may have at most " + std::to_string(max_px) + " pixels" +
                                ((flow_flags & kFlowNtw2) ? " with flow_flags bit 0 (e.g. -t 1000)" : " (e.g. -t 1400)"));
 }
@@ -568,10 +567,10 @@ long long Engine::budget_slots(long long cap_px, int w, int h, int c)
 
 int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*& out)
 {
+    const PlanKey key{w, h, c, tilesize, prepadding, tta, nimg, precise, out_ratio, (flow_flags & kFlowNtw2) != 0, tile0, tile1, max_workspace_mb,
+                      trim_tail, xcd_order, fold_cols, ws_clamp_bytes}; // (in the order of its fields)
     for (auto it = plans.begin(); it != plans.end(); ++it)
-        if (it->w == w && it->h == h && it->c == c && it->T == tilesize && it->P == prepadding && it->tta == tta && it->nimg == nimg && it->precise == precise && it->ratio == out_ratio && it->ntw2 == ((flow_flags & kFlowNtw2) != 0) &&
-            it->tile0 == tile0 && it->tile1 == tile1 && it->budget_mb == max_workspace_mb && it->trim == trim_tail && it->xcd_order == xcd_order && it->fold == fold_cols &&
-            it->clamp == ws_clamp_bytes)
+        if (it->key == key)
         {
             plans.splice(plans.begin(), plans, it); // most recently used first
             out = &plans.front();
@@ -587,33 +586,17 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
     if (tile0 < 0 || tile1 > ntiles || tile0 >= tile1) return fail(RSR_E_ARG, "tile range outside the image");
     if (nimg < 1 || nimg > kMaxMerge || (nimg > 1 && (tile0 != 0 || tile1 != ntiles))) return fail(RSR_E_ARG, "merged batches take whole images");
     for (int im = 0; im < nimg; im++) image_tiles(w, h, T, P, scale, tile0, tile1, im, all, cap, mtw, mth);
-    // every merged batch -- of one geometry (this plan) or of several (enqueue_mixed) -- gives its slots the capacity of a full tile: the
-    // workspace layout, hence its guards, then stays put from batch to batch whatever small images come
-    if (nimg > 1) cap = std::max(cap, (long long)(T + 2 * P) * (T + 2 * P));
-    int rc = check_tile_px(cap);
-    if (rc != RSR_OK) return rc;
+    if (nimg > 1) cap = std::max(cap, merged_cap_px());
+    if (const int rc = check_tile_px(cap)) return rc;
     const int per = tta ? 8 : 1;
     const long long total_slots = (long long)all.size() * per;
     const int spb = int(std::min<long long>(total_slots, budget_slots(cap, w, h, c)));
     const int tiles_per_batch = spb / per;
 
     Plan plan;
-    plan.w = w; plan.h = h; plan.c = c; plan.T = T; plan.P = P; plan.tta = tta;
-    plan.nimg = nimg;
-    plan.precise = precise;
-    plan.ratio = out_ratio;
-    plan.ntw2 = (flow_flags & kFlowNtw2) != 0;
-    plan.tile0 = tile0; plan.tile1 = tile1;
-    plan.budget_mb = max_workspace_mb;
-    plan.trim = trim_tail;
-    plan.xcd_order = xcd_order;
-    plan.fold = fold_cols;
+    plan.key = key;
     plan.out_row0 = std::min((tile0 / xtiles) * T, h) * scale; // first output row of the range's first tile row
-    plan.clamp = ws_clamp_bytes;
-    plan.cap_px = cap;
-    plan.max_tw = mtw;
-    plan.max_th = mth;
-    plan.slots_per_batch = spb;
+    plan.cap_px = cap; plan.max_tw = mtw; plan.max_th = mth; plan.slots_per_batch = spb;
     size_t table_bytes = 0;
     for (size_t t0 = 0; t0 < all.size(); t0 += size_t(tiles_per_batch))
     {
@@ -654,72 +637,40 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
 int Engine::ensure_planes(DevBuf& b, size_t bytes, long long plane_bytes, bool layout_changed, bool zero_all, hipStream_t st)
 {
     const bool grow = !(b.bytes >= bytes && b.p);
-    if (grow)
-    {
-        const int rc = ensure(b, bytes);
-        if (rc != RSR_OK) return rc;
-        HIP_TRY(hipMemsetAsync(b.p, 0, b.bytes, st)); // same stream as the kernels that follow
-    }
-    else if (layout_changed)
-    {
-        if (zero_all) HIP_TRY(hipMemsetAsync(b.p, 0, b.bytes, st));
-        else launch_zero_guards(b.p, plane_bytes, (long long)(b.bytes / size_t(plane_bytes)), st);
-    }
+    if (const int rc = ensure(b, bytes)) return rc; // (does nothing unless the buffer grows)
+    if (grow || (layout_changed && zero_all)) HIP_TRY(hipMemsetAsync(b.p, 0, b.bytes, st)); // same stream as the kernels that follow
+    else if (layout_changed) launch_zero_guards(b.p, plane_bytes, (long long)(b.bytes / size_t(plane_bytes)), st);
     return RSR_OK;
 }
 
 int Engine::ensure_workspace(int nslots, long long cap, hipStream_t st)
 {
-    constexpr int pc = plane_ch();
-    const size_t n = size_t(nslots), c = size_t(cap), G = size_t(kGuard), ppx = size_t(pc) * 2;
-    const size_t p32 = size_t(32 / pc), p64 = size_t(64 / pc);
-    // the plane stride (hence the guard positions) depends on the slot capacity; precise mode moves the planes of a slot (its one-byte
-    // lo planes sit at half strides and run across plane boundaries: where they lay, the other layout has guards)
-    const bool lc = cap != ws_cap_px || precise != ws_precise;
-    // precise mode: FEA and the RDB buffers carry the lo planes of their 64-channel trunk tensor behind the hi / dense planes
-    // (one byte per element: the four lo planes of a tensor take the room of two hi planes)
-    const size_t fea_pps = p64 + (precise ? p64 / 2 : 0), rdb_pps = 3 * p64 + (precise ? p64 / 2 : 0);
-    const size_t need[] = {n * p32 * (c * ppx + G), n * fea_pps * (c * ppx + G), n * rdb_pps * (c * ppx + G), n * p64 * (c * 4 * ppx + G),
-                           n * p64 * (c * 16 * ppx + G), n * c * (precise ? 192 : 96)};
-    DevBuf* const bufs[] = {&b_in, &b_fea, &b_rdb[0], &b_up1, &b_up2, &b_out3};
+    const WsLayout lay{cap, precise};
+    // The guard positions of a buffer are a function of the slot capacity only: every plane, the lo pair planes of precise mode included
+    // (conv_flow.hip lo_row), starts a whole number of plane_bytes behind the buffer's start, and plane_bytes does not depend on `precise`
+    // (workspace.h; tools/host_check checks both).  So a change of `precise` alone moves no guard: nothing is zeroed for it.
+    const bool lc = cap != ws_cap_px;
     bool any_grow = false;
-    for (int i = 0; i < 6; i++)
-        if (need[i] && !(bufs[i]->bytes >= need[i] && bufs[i]->p)) any_grow = true;
-    if (ws_fail_above_bytes >= 0)
+    for (int i = 0; i < kWsCount; i++)
+        if (const size_t need = size_t(lay.bytes(i, nslots)); need && !(ws[i].bytes >= need && ws[i].p)) any_grow = true;
+    if (const long long total = (long long)nslots * cap * bytes_per_px(); ws_fail_above_bytes >= 0 && total > ws_fail_above_bytes)
     { // test hook (option "ws_fail_above_mb"): a device on which workspaces above this size persistently fail to allocate
-        const long long total = (long long)nslots * cap * bytes_per_px();
-        if (total > ws_fail_above_bytes)
-        {
-            ws_failures++;
-            return fail(RSR_E_NOMEM, "workspace of " + std::to_string(total >> 20) + " MiB refused (ws_fail_above_mb test hook)");
-        }
+        ws_failures++;
+        return fail(RSR_E_NOMEM, "workspace of " + std::to_string(total >> 20) + " MiB refused (ws_fail_above_mb test hook)");
     }
     if (any_grow || lc) HIP_TRY(hipStreamSynchronize(st)); // nothing in flight may use a buffer that is freed / re-laid-out
-    int rc;
-    // b_in: its second plane (channels 16..31 of the padded 3-channel input) must stay zero
-    if ((rc = ensure_planes(b_in, need[0], long(c * ppx + G), lc, true, st)) != RSR_OK) return rc;
-    if ((rc = ensure_planes(b_fea, need[1], long(c * ppx + G), lc, false, st)) != RSR_OK) return rc;
-    for (int i = 0; i < 3; i++)
-        if ((rc = ensure_planes(b_rdb[i], need[2], long(c * ppx + G), lc, false, st)) != RSR_OK) return rc;
-    if ((rc = ensure_planes(b_up1, need[3], long(c * 4 * ppx + G), lc, false, st)) != RSR_OK) return rc;
-    if ((rc = ensure_planes(b_up2, need[4], long(c * 16 * ppx + G), lc, false, st)) != RSR_OK) return rc;
-    if ((rc = ensure_planes(b_hr, need[4], long(c * 16 * ppx + G), lc, false, st)) != RSR_OK) return rc;
-    if ((rc = ensure(b_out3, need[5])) != RSR_OK) return rc;
+    for (int i = 0; i < kWsCount; i++)
+        if (const size_t need = size_t(lay.bytes(i, nslots)); const int rc = WsLayout::guarded(i) ? ensure_planes(ws[i], need, lay.plane_bytes(i), lc, kWsTable[i].zero_all, st) : ensure(ws[i], need))
+            return rc;
     HIP_TRY(hipGetLastError());
     ws_cap_px = cap;
-    ws_precise = precise;
     return RSR_OK;
 }
 
 void Engine::free_workspace(hipStream_t st)
 {
     (void)hipStreamSynchronize(st);
-    for (DevBuf* wb : {&b_in, &b_fea, &b_rdb[0], &b_rdb[1], &b_rdb[2], &b_up1, &b_up2, &b_hr, &b_out3})
-    {
-        if (wb->p) (void)hipFree(wb->p);
-        wb->p = nullptr;
-        wb->bytes = 0;
-    }
+    for (DevBuf& wb : ws) (void)hipFree(wb.p), wb = DevBuf(); // (freeing a null pointer does nothing)
     ws_cap_px = 0;
 }
 
@@ -781,10 +732,10 @@ void Engine::collect_profile(hipStream_t st)
 }
 
 // ---- the network schedule ---------------------------------------------------------------------
-// x4.param as a fused schedule.  Buffers per slot, in planes of plane_ch() channels (P32 = planes
-// per 32 channels, P64 per 64):
-//   IN(P32; channels 3.. zero)  FEA(P64)  RDB[3] x {x(P64) + dense x1..x4 (4 x P32)}  T32/R32 (fp32 trunk, kernels 1-3)
-//   UP1(P64 @2x)  UP2(P64 @4x)  HR(P64 @4x)  OUT3 (planar [3][4H][4W] fp16)
+// x4.param as a fused schedule.  Buffers per slot (workspace.h kWsTable), in planes of plane_ch() channels
+// (P32 = planes per 32 channels, P64 per 64):
+//   IN(P32; channels 3.. zero)  FEA(P64)  RDB[3] x {x(P64) + dense x1..x4 (4 x P32)}
+//   UP1(P64 @2x)  UP2(P64 @4x)  HR(P64 @4x)  OUT3 (planar [3][4H][4W] fp16; precise mode: fp32, and lo pair planes behind FEA's and RDB's)
 // Concat never happens: conv k of a dense block reads planes [x | x1..x_{k-1}] in place and writes its
 // 32 channels as plane(s) x_k.  Eltwise/BinaryOp/Interp are epilogue or staging-address variants.
 int Engine::launch(const ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t st)
@@ -800,29 +751,18 @@ int Engine::launch(const ConvArgs& a, int ci, const Plan::Batch& b, hipStream_t 
 int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, const BatchIO* io, const RangeProbe* probe)
 {
     const int nslots = std::min(nslots_used, b.nslots);
-    const long long cap = ws_cap_px;
-    const bool fused = io && conv_last_writes_image(io->c, io->out_fmt); // conv_last writes the images of io itself, else the planar b_out3 blob
+    const bool fused = io && conv_last_writes_image(io->c, io->out_fmt); // conv_last writes the images of io itself, else the planar OUT3 blob
     const int split_slot = io ? io->split_slot : 0;
     // the throttle event of a merged batch (Engine::submit_merged): behind the RDB that leaves about half an image's worth of network
     // ahead -- the time the next batch's launches take to enqueue
     // (a one-block model has three RDBs: the formula gives RDB 0 there; the clamp keeps it inside the loop at every depth)
     const int mid_rdb = (io && io->ev_mid) ? std::min(nrdb - 1, std::max(0, nrdb - 1 - std::max(2, nrdb / (2 * std::max(1, io->nimg))))) : -1;
     // the probe reads whole planes: they must hold exactly the pixels of the one tile, all of them computed, in fp16 storage
-    if (probe && (b.nslots != 1 || b.dims.size() != 1 || cap != (long long)b.dims[0].h * b.dims[0].w || b.trim4 || precise || fused))
+    if (probe && (b.nslots != 1 || b.dims.size() != 1 || ws_cap_px != (long long)b.dims[0].h * b.dims[0].w || b.trim4 || precise || fused))
         return fail(RSR_E_STATE, "range probe on a plan that is not one untrimmed tile in fp16 storage");
     const int pc = plane_ch(), P32 = 32 / pc, P64 = 64 / pc;
-    const long long ppx = pc * 2;
-    const long long pb16 = cap * ppx + kGuard; // planes are guarded (see ensure_workspace)
     // precise mode (ConvArgs::precise): the lo planes of a trunk tensor sit behind the hi / dense planes of its slot
-    const int fea_pps = P64 + (precise ? P64 / 2 : 0), rdb_pps = 3 * P64 + (precise ? P64 / 2 : 0);
-    const long long fea_lo = precise ? P64 * pb16 : 0, rdb_lo = precise ? 3 * P64 * pb16 : 0;
-    auto PS = [](const DevBuf& buf, long long planes_per_slot, long long plane_bytes, int plane_off) {
-        PlaneSrc s; // base = pixel 0 of plane `plane_off` of slot 0
-        s.base = static_cast<const char*>(buf.p) + (long long)plane_off * plane_bytes + kGuard;
-        s.slot_stride = planes_per_slot * plane_bytes;
-        s.plane_stride = plane_bytes;
-        return s;
-    };
+    const long long fea_lo = layout().lo_off(kWsFea), rdb_lo = layout().lo_off(kWsRdb0);
     const char* blobp = static_cast<const char*>(blob.p);
     int ci = 0, rc = RSR_OK;
     auto base_args = [&](int lvl_in, int lvl_out) {
@@ -867,13 +807,13 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
         }
         ci++;
     };
-    const PlaneSrc fea = PS(b_fea, fea_pps, pb16, 0);
-    auto rdb_x = [&](int i) { return PS(b_rdb[i], rdb_pps, pb16, 0); };
-    auto rdb_d = [&](int i, int k) { return PS(b_rdb[i], rdb_pps, pb16, P64 + k * P32); };
+    const PlaneSrc fea = ws_planes(kWsFea);
+    auto rdb_x = [&](int i) { return ws_planes(kWsRdb0 + i); };
+    auto rdb_d = [&](int i, int k) { return ws_planes(kWsRdb0 + i, P64 + k * P32); };
 
     { // conv_first (x4.param:4): IN -> FEA
         ConvArgs a = base_args(0, 0);
-        a.src0 = PS(b_in, P32, pb16, 0);
+        a.src0 = ws_planes(kWsIn);
         a.n0 = P32;
         a.out16 = fea;
         a.out_lo_off = fea_lo; // the stream starts here: fea keeps its rounding residue too
@@ -918,8 +858,7 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
         a.out16 = rdb_x(1); // (only upconv1 reads it: no lo planes)
         go(a);
     }
-    const PlaneSrc up1 = PS(b_up1, P64, cap * 4 * ppx + kGuard, 0), up2 = PS(b_up2, P64, cap * 16 * ppx + kGuard, 0),
-                   hr = PS(b_hr, P64, cap * 16 * ppx + kGuard, 0);
+    const PlaneSrc up1 = ws_planes(kWsUp1), up2 = ws_planes(kWsUp2), hr = ws_planes(kWsHr);
     // The convs behind the trunk (upconv1 @2x, upconv2 / HRconv / conv_last @4x: ~11 % of the frame) can run per GROUP of
     // `tail_group_slots` slots (0 = the whole batch): a tile has 4x / 16x the blocks up there, so a few tiles fill the chip for
     // > 100 us per launch, and their 2 x 99 MB per tile of 4x intermediates are then read back from the 256 MB Infinity Cache
@@ -983,8 +922,8 @@ int Engine::run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, c
             }
             else
             {
-                a.out_planar3 = b_out3.p;
-                a.planar3_slot_stride = cap * (precise ? 192 : 96);
+                a.out_planar3 = ws[kWsOut3].p;
+                a.planar3_slot_stride = layout().slot_stride(kWsOut3);
             }
             sub(a, 2);
             go(a);
@@ -1082,14 +1021,14 @@ int Engine::enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size
         if (conv_last_writes_image(c, io.out_fmt) && nimg == 1 && io.ev_half && half_rows && plan.batches.size() == 1 && !profiling && !(dbg & kDbgNoSplitTail))
         {
             const int xt = xtiles, yt = b.ntiles / xt;
-            if (yt >= 2 && b.ntiles == xt * yt && plan.tile0 % xt == 0)
+            if (yt >= 2 && b.ntiles == xt * yt && plan.key.tile0 % xt == 0)
             {
                 io.split_slot = xt * (yt / 2);
                 *half_rows = size_t(b.tiles[size_t(io.split_slot)].out_y - b.tiles[0].out_y); // output rows finished at ev_half
             }
         }
         io.ev_mid = b.tile0 + b.ntiles >= tiles_wanted ? ev_mid : nullptr;
-        rc = launch_batch(b, plan.cap_px, plan.max_tw, plan.max_th, ntiles, st, io);
+        rc = launch_batch(b, plan.max_tw, plan.max_th, ntiles, st, io);
         if (rc != RSR_OK) return rc;
         if (progress && !merged) // one call per TILE, like the reference's line per tile (realsr.cpp:481), issued when the tile's batch is enqueued
             for (int i = 1; i <= b.ntiles; i++) progress(done + i, total, progress_user); // (a merged batch: every caller reports its own image)
@@ -1105,11 +1044,10 @@ int Engine::enqueue_images(BatchIO io, int tile0, int tile1, int plan_nimg, size
     return RSR_OK;
 }
 
-// preproc -> network -> postproc of the first `ntiles` tiles of one tile batch on `st` (mu held; the workspace is laid out for cap_px).
-// The images of the batch may differ in size (io.w / io.h): every tile carries the index of its image.
-int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io)
+// preproc -> network -> postproc of the first `ntiles` tiles of one tile batch on `st` (mu held; the workspace is laid out for the batch's
+// slots).  The images of the batch may differ in size (io.w / io.h): every tile carries the index of its image.
+int Engine::launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io)
 {
-    constexpr int pc = plane_ch();
     const int per = tta ? 8 : 1, c = io.c;
     const int variant = (dbg & kDbgPrePostVar1) ? 1 : ((dbg & kDbgPrePostVar2) ? 2 : 0);
     PreArgs pa;
@@ -1133,10 +1071,10 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     pa.tiles = b.d_tiles;
     pa.ntiles = ntiles;
     pa.tta = tta;
-    pa.in_plane = static_cast<char*>(b_in.p) + kGuard;
-    pa.slot_stride = (32 / pc) * (cap_px * pc * 2 + kGuard);
+    pa.in_plane = const_cast<void*>(ws_planes(kWsIn).base);
+    pa.slot_stride = ws_planes(kWsIn).slot_stride;
     pa.bgr = bgr ? 1 : 0;
-    pa.plane_ch = pc;
+    pa.plane_ch = plane_ch();
     pa.variant = variant;
     if (const int bits = pix_fmt(io.in_fmt).bits; bits && !yuv_coef(yuv_matrix, yuv_range, bits, &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     if (const int bits = pix_fmt(io.out_fmt).bits; bits && !yuv_coef(yuv_matrix, yuv_range, bits, &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
@@ -1145,9 +1083,9 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
     mark(0, 0, b.px[0] / per * BatchIO::image_px_bytes(io.in_fmt, c) + b.px[0] * 64, st);
     const int rc = run_network(b, st, ntiles * per, &io, nullptr);
     if (rc != RSR_OK || conv_last_writes_image(c, io.out_fmt)) return rc;
-    po.planar3 = b_out3.p;
+    po.planar3 = ws[kWsOut3].p;
     po.f32 = precise ? 1 : 0;
-    po.slot_stride = cap_px * (precise ? 192 : 96);
+    po.slot_stride = layout().slot_stride(kWsOut3);
     po.tiles = b.d_tiles;
     po.ntiles = ntiles;
     po.tta = tta;
@@ -1173,8 +1111,7 @@ int Engine::launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int
 // A merged batch of images that DIFFER in size (a directory of thumbnails, sprites, crops ...): no cached plan can serve it -- the
 // tile and work-item tables are built here, for exactly these images, and uploaded into one of three rotating device buffers (the
 // throttle of submit_merged leaves at most the previous batch in flight when the next one is formed; the buffer's event makes sure).
-// All slots get the capacity of a full tile, (T + 2P)^2, whatever the images: the workspace layout (hence its guards) then does not
-// change from batch to batch.  mu held.
+// All slots get the capacity of a full tile (merged_cap_px), whatever the images.  mu held.
 int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid)
 {
     const int T = tilesize, P = prepadding, c = g[0]->c;
@@ -1182,7 +1119,7 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
     long long cap = 0;
     int mtw = 0, mth = 0;
     for (int i = 0; i < n; i++) image_tiles(g[i]->w, g[i]->h, T, P, scale, 0, tile_count(g[i]->w, g[i]->h), i, all, cap, mtw, mth);
-    cap = (long long)(T + 2 * P) * (T + 2 * P);
+    cap = merged_cap_px();
     int rc = check_tile_px(cap);
     if (rc != RSR_OK) return rc;
     const long long need = (long long)all.size() * (tta ? 8 : 1) * cap * bytes_per_px();
@@ -1198,7 +1135,7 @@ int Engine::enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t 
     if ((rc = ensure_workspace(b.nslots, cap, st)) != RSR_OK) return rc;
     BatchIO io(g, n);
     io.ev_mid = ev_mid;
-    rc = launch_batch(b, cap, mtw, mth, b.ntiles, st, io);
+    rc = launch_batch(b, mtw, mth, b.ntiles, st, io);
     if (rc != RSR_OK) return rc;
     mix_ring.release(st);
     HIP_TRY(hipGetLastError());
@@ -1277,7 +1214,7 @@ int Engine::enqueue_sequence(BatchIO io, const std::vector<int>& sel, const std:
     long long slots = 0;
     for (const Plan::Batch& b : batches)
     {
-        rc = launch_batch(b, cap, mtw, mth, b.ntiles, st, io);
+        rc = launch_batch(b, mtw, mth, b.ntiles, st, io);
         if (rc != RSR_OK) break;
         if (progress)
             for (int i = 1; i <= b.ntiles; i++) progress(done + i, nsel, progress_user);
@@ -2291,9 +2228,9 @@ int Engine::one_tile_upload(OneTile& t, const uint16_t* tile, int w, int h)
 
 int Engine::one_tile_walk(const OneTile& t, const RangeProbe* probe)
 {
-    int rc = ensure_workspace(1, (long long)t.w * t.h, stream); // (a change of layout zeroes b_in: the tile is written every time)
+    int rc = ensure_workspace(1, (long long)t.w * t.h, stream); // (a change of layout zeroes IN: the tile is written every time)
     if (rc != RSR_OK) return rc;
-    launch_planar3_to_plane(static_cast<const uint16_t*>(t.tile.p), t.w, t.h, static_cast<char*>(b_in.p) + kGuard, plane_ch(), stream);
+    launch_planar3_to_plane(static_cast<const uint16_t*>(t.tile.p), t.w, t.h, const_cast<void*>(ws_planes(kWsIn).base), plane_ch(), stream);
     const bool was = profiling;
     profiling = false;
     rc = run_network(t.b, stream, 1, nullptr, probe);
@@ -2317,14 +2254,14 @@ int Engine::net_forward(const uint16_t* in, int w, int h, uint16_t* out, float* 
     if (he == hipSuccess) he = hipGetLastError();
     if (he == hipSuccess && !precise)
     {
-        if (out) he = hipMemcpy(out, b_out3.p, npx * 16 * 6, hipMemcpyDeviceToHost);
+        if (out) he = hipMemcpy(out, ws[kWsOut3].p, npx * 16 * 6, hipMemcpyDeviceToHost);
         if (out32) rc = fail(RSR_E_STATE, "the fp32 output blob exists in precise mode only (rsr_set_option precise 1)");
     }
     else if (he == hipSuccess)
     { // precise mode: conv_last left fp32; the fp16 view of it is rounded here, on the host
         std::vector<float> tmp32(out32 ? 0 : npx * 16 * 3);
         float* dst = out32 ? out32 : tmp32.data();
-        he = hipMemcpy(dst, b_out3.p, npx * 16 * 12, hipMemcpyDeviceToHost);
+        he = hipMemcpy(dst, ws[kWsOut3].p, npx * 16 * 12, hipMemcpyDeviceToHost);
         if (he == hipSuccess && out)
             for (size_t i = 0; i < npx * 16 * 3; i++)
             {
@@ -2423,8 +2360,8 @@ int Engine::selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* 
     {
         precise = pass == 1;
         if ((rc = one_tile_walk(t, pass == 0 ? &probe : nullptr)) != RSR_OK) return rc;
-        if (pass == 0) he = hipMemcpyAsync(out16.p, b_out3.p, nout * 2, hipMemcpyDeviceToDevice, stream);
-        else launch_output_compare(static_cast<const uint16_t*>(out16.p), static_cast<const float*>(b_out3.p), (long long)nout, r32 + nc, r64 + nc, stream);
+        if (pass == 0) he = hipMemcpyAsync(out16.p, ws[kWsOut3].p, nout * 2, hipMemcpyDeviceToDevice, stream);
+        else launch_output_compare(static_cast<const uint16_t*>(out16.p), static_cast<const float*>(ws[kWsOut3].p), (long long)nout, r32 + nc, r64 + nc, stream);
     }
     std::vector<unsigned long long> h64(kRep64);
     std::vector<unsigned> h32(kRep32);
@@ -2500,10 +2437,9 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
     const int H = ups ? 2 * h : h, W = ups ? 2 * w : w;
     const size_t ipx = size_t(h) * w, opx = size_t(H) * W;
     // planar [cin][h][w] -> guarded planes [np][h][w][pch]
-    const size_t ipl = ipx * size_t(pch) + kGuard / 2; // halfs per guarded input plane
-    // precise form: the one-byte lo planes of a tensor (plane stride / 2) follow its hi planes in the same allocation, `lo_off` bytes
-    // behind pixel 0 of plane 0 (kernels.h ConvArgs::lo1_off)
-    const size_t ipl_b = ipl * 2, opl_b = opx * size_t(pch) * 2; // bytes per (guarded) input plane / per output plane
+    const size_t ipl_b = size_t(WsLayout::guarded_plane((long long)ipx)), ipl = ipl_b / 2, opl_b = opx * size_t(pch) * 2; // bytes / halfs per guarded input plane, bytes per output plane
+    // precise form: the one-byte lo pair planes of a tensor follow its hi planes in the same allocation (kernels.h ConvArgs::lo1_off)
+    const long long in_lo_off = in_lo ? WsLayout::lo_behind(np, ipl_b) : 0, res_lo_off = res_lo ? WsLayout::lo_behind(npo, ipl_b) : 0, out_lo_off = out_lo ? WsLayout::lo_behind(npo, opl_b) : 0;
     std::vector<uint16_t> hin(size_t(np + (in_lo ? npo : 0)) * ipl, 0), hout(size_t(npo) * (out_lo ? 2 : 1) * opx * size_t(pch), 0);
     for (int ch = 0; ch < cin; ch++)
         for (size_t p = 0; p < ipx; p++) hin[size_t(ch / pch) * ipl + kGuard / 2 + p * size_t(pch) + size_t(ch % pch)] = in[size_t(ch) * ipx + p];
@@ -2516,14 +2452,14 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
         for (int ch = 0; ch < cout; ch++)
             for (size_t p = 0; p < ipx; p++) b[lo_index(ch, p, ipl_b)] = lo[size_t(ch) * ipx + p];
     };
-    if (in_lo) put_lo(hin, size_t(np) * ipl_b, in_lo);
+    if (in_lo) put_lo(hin, size_t(in_lo_off), in_lo);
     std::vector<uint16_t> hres;
     if (residual && res)
     { // planar [cout][h][w] -> guarded planes like the input
         hres.assign(size_t(npo) * (res_lo ? 2 : 1) * ipl, 0);
         for (int ch = 0; ch < cout; ch++)
             for (size_t p = 0; p < ipx; p++) hres[size_t(ch / pch) * ipl + kGuard / 2 + p * size_t(pch) + size_t(ch % pch)] = res[size_t(ch) * ipx + p];
-        if (res_lo) put_lo(hres, size_t(npo) * ipl_b, res_lo);
+        if (res_lo) put_lo(hres, size_t(res_lo_off), res_lo);
     }
     ScratchBuf d_w, d_in, d_out, d_tab, d_res;
     std::vector<WorkItem> items;
@@ -2546,7 +2482,7 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
     {
         ConvArgs a;
         std::memset(&a, 0, sizeof a);
-        a.src0 = PlaneSrc{static_cast<char*>(d_in.p) + kGuard, 0, (long long)ipx * pch * 2 + kGuard};
+        a.src0 = PlaneSrc{static_cast<char*>(d_in.p) + kGuard, 0, (long long)ipl_b};
         a.n0 = np;
         a.lvl_in = 0;
         a.lvl_out = ups ? 1 : 0;
@@ -2559,22 +2495,21 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
         { // the epilogue forms of RDB conv5 / trunk_conv (run_network)
             a.s1 = s1;
             a.precise = prec ? 1 : 0;
-            const long long res_lo_off = res_lo ? (long long)npo * (long long)ipl * 2 : 0;
             if (own_res)
             {
                 a.res1 = a.src0;
                 a.res1_kind = 1;
                 a.res1_in_acc = 1;
                 a.res1_coef = 1.f / s1;
-                a.lo1_off = in_lo ? (long long)np * (long long)ipl * 2 : 0;
+                a.lo1_off = in_lo_off;
             }
             if (res)
             {
-                const PlaneSrc rp{static_cast<char*>(d_res.p) + kGuard, 0, (long long)ipx * pch * 2 + kGuard};
+                const PlaneSrc rp{static_cast<char*>(d_res.p) + kGuard, 0, (long long)ipl_b};
                 if (own_res) { a.res2 = rp; a.res2_kind = 1; a.s2 = s2; a.lo2_off = res_lo_off; }
                 else { a.res1 = rp; a.res1_kind = 1; a.lo1_off = res_lo_off; } // trunk_conv form: v = s1*(conv+b) + res  (s2 unused)
             }
-            if (out_lo) a.out_lo_off = (long long)npo * (long long)opx * pch * 2;
+            a.out_lo_off = out_lo_off;
         }
         a.out16 = PlaneSrc{d_out.p, 0, (long long)opx * pch * 2};
         a.items = reinterpret_cast<const WorkItem*>(static_cast<const char*>(d_tab.p) + 256);
@@ -2600,7 +2535,7 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
         for (size_t p = 0; p < opx; p++)
         {
             out[size_t(ch) * opx + p] = hout[(size_t(ch / pch) * opx + p) * size_t(pch) + size_t(ch % pch)];
-            if (out_lo) out_lo[size_t(ch) * opx + p] = reinterpret_cast<const unsigned char*>(hout.data())[size_t(npo) * opl_b + lo_index(ch, p, opl_b)];
+            if (out_lo) out_lo[size_t(ch) * opx + p] = reinterpret_cast<const unsigned char*>(hout.data())[size_t(out_lo_off) + lo_index(ch, p, opl_b)];
         }
     return RSR_OK;
 }

@@ -36,6 +36,7 @@
 #include "../../include/realsr_hip.h"
 #include "kernels.h"
 #include "model.h"
+#include "workspace.h"
 
 namespace rsr {
 
@@ -97,19 +98,30 @@ struct ScratchBuf : DevBuf
     }
 };
 
-// geometry of one rsr_process call; cached per (w,h,c,T,P,tta,budget)
-struct Plan
+// What a cached plan was built for: the call's arguments and the engine state its tables and batch sizes depend on (Engine::get_plan)
+struct PlanKey
 {
     int w = 0, h = 0, c = 0, T = 0, P = 0, tta = 0;
     int nimg = 1;         // images of this geometry merged into one tile batch (kernels.h kMaxMerge); their tiles follow each other image by image
-    bool precise = false; // Engine::precise when the plan was built (the slots are larger: part of the cache key)
-    OutRatio ratio;       // Engine::out_ratio when the plan was built (part of the cache key, though no field of a Plan depends on it today: the placement tables are built alike and below 4 merely go unused)
-    bool ntw2 = false;    // flow_flags has kFlowNtw2 when the plan was built (an MFMA wave then reaches 4 planes from one base: the tile-size bound halves)
+    bool precise = false; // Engine::precise (the slots are larger)
+    OutRatio ratio;       // Engine::out_ratio (though no field of a Plan depends on it today: the placement tables are built alike and below 4 merely go unused)
+    bool ntw2 = false;    // flow_flags has kFlowNtw2 (an MFMA wave then reaches 4 planes from one base: the tile-size bound halves)
     int tile0 = 0, tile1 = 0; // tiles [tile0, tile1) of the image's tile grid, row-major (multi-GPU tile sharding)
     long long budget_mb = 0;
     bool trim = true, xcd_order = true, fold = true;
+    long long clamp = -1; // Engine::ws_clamp_bytes
+    bool operator==(const PlanKey& o) const
+    {
+        return w == o.w && h == o.h && c == o.c && T == o.T && P == o.P && tta == o.tta && nimg == o.nimg && precise == o.precise && ratio == o.ratio && ntw2 == o.ntw2 &&
+               tile0 == o.tile0 && tile1 == o.tile1 && budget_mb == o.budget_mb && trim == o.trim && xcd_order == o.xcd_order && fold == o.fold && clamp == o.clamp;
+    }
+};
+
+// geometry of one rsr_process call; cached per PlanKey
+struct Plan
+{
+    PlanKey key;
     int out_row0 = 0; // output rows are addressed relative to this one: the first row of the tile range (the device buffer of a range holds only its rows)
-    long long clamp = -1; // Engine::ws_clamp_bytes when the plan was built (part of the cache key)
     long long cap_px = 0; // slot capacity in LR pixels
     int max_tw = 0, max_th = 0;
     struct Batch
@@ -300,7 +312,7 @@ struct Engine
     std::vector<long long> sc_nonfinite;
     int selfcheck(const uint16_t* tile, int w, int h, rsr_selfcheck_report* out); // mu held
     int apply_precise_auto();                                                      // mu held, loaded: self-check on the built-in tile -> precise
-    long long bytes_per_px() const; // workspace bytes per padded LR pixel of a slot
+    long long bytes_per_px() const { return WsLayout::bytes_per_px(precise); } // workspace bytes per padded LR pixel of a slot
     int flow_flags = 0; // kFlow* bits of kernels.h
     int num_cu = 256;
     int dbg = 0; // ConvArgs::dbg ablation bits (profiling only)
@@ -334,10 +346,9 @@ struct Engine
     DevBuf blob; // packed weights on device
     DevBuf zeros;
 
-    // workspace (one allocation per buffer kind), layout = slot capacity
+    // workspace (workspace.h: one allocation per buffer), laid out for slots of ws_cap_px pixels (0: no layout)
     long long ws_cap_px = 0;
-    bool ws_precise = false; // Engine::precise the workspace was last laid out for
-    DevBuf b_in, b_fea, b_rdb[3], b_up1, b_up2, b_hr, b_out3;
+    DevBuf ws[kWsCount];
 
     // plans, most recently used first
     std::list<Plan> plans;
@@ -453,19 +464,27 @@ struct Engine
     static int ensure(DevBuf& b, size_t bytes);
     int ensure_planes(DevBuf& b, size_t bytes, long long plane_bytes, bool layout_changed, bool zero_all, hipStream_t st);
     int get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*& out);
+    // Every merged batch -- of one geometry (get_plan, nimg > 1) or of several (enqueue_mixed) -- gives its slots the capacity of a full tile: the
+    // workspace layout, hence its guards, then stays put from batch to batch whatever small images come
+    long long merged_cap_px() const { return (long long)(tilesize + 2 * prepadding) * (tilesize + 2 * prepadding); }
     long long budget_slots(long long cap_px, int w, int h, int c); // slots of cap_px LR pixels one tile batch may have: the memory policy of get_plan and enqueue_masked
     long long device_avail(int w, int h, int c);
     void free_workspace(hipStream_t st);
     int ensure_workspace(int nslots, long long cap_px, hipStream_t st);
+    WsLayout layout() const { return WsLayout{ws_cap_px, precise}; } // of the workspace as ensure_workspace left it
+    PlaneSrc ws_planes(int buf, int plane = 0) const // plane `plane` of slot 0 of a workspace buffer, with the buffer's strides
+    {
+        return PlaneSrc{static_cast<const char*>(ws[buf].p) + layout().plane_off(buf, plane), layout().slot_stride(buf), layout().plane_bytes(buf)};
+    }
     // no TTA merge / alpha channel / box reduction / YUV surface needs the planar blob (kDbgNoFusedLast: off)
     bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & kDbgNoFusedLast); }
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
-    // io: null = conv_last leaves the planar b_out3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).
+    // io: null = conv_last leaves the planar OUT3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).
     // probe: non-null = every convolution is followed by a range-probe launch on what it stored (the self-check's one-tile batch in
     // fp16 storage only; null everywhere else: the launch sequence is then exactly the one without it)
     int run_network(const Plan::Batch& b, hipStream_t st, int nslots_used, const BatchIO* io, const RangeProbe* probe);
-    int launch_batch(const Plan::Batch& b, long long cap_px, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io);
+    int launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntiles, hipStream_t st, const BatchIO& io);
     int enqueue_mixed(MergeReq* const* g, int n, hipStream_t st, hipEvent_t ev_mid); // a merged batch of images of different sizes: tables built on the fly
     int enqueue_masked(BatchIO io, const std::vector<int>& sel, hipStream_t st);     // the tiles `sel` (ascending) of the ONE image of io: tables built on the fly
     // The (image, tile) pairs `sel` (frame-major, tile = image * tiles_per_image + tile of the grid) of the io.nimg images of ONE geometry:
@@ -488,7 +507,7 @@ struct Engine
         int w = 0, h = 0;
     };
     int one_tile_upload(OneTile& t, const uint16_t* tile, int w, int h);
-    int one_tile_walk(const OneTile& t, const RangeProbe* probe); // workspace of the current storage mode, tile -> b_in, the network (never profiled)
+    int one_tile_walk(const OneTile& t, const RangeProbe* probe); // workspace of the current storage mode, tile -> IN, the network (never profiled)
     void mark_begin(hipStream_t st);
     void mark(int cls, double flops, double bytes, hipStream_t st, int conv_index = -1);
     void collect_profile(hipStream_t st);

@@ -8,6 +8,9 @@
 //   2. fill_batch: batches of 1, 7 and 60 tiles with and without TTA; every table entry is read back and range-checked.
 //   3. choose_conv_flow: which conv3x3_flow kernel, patch ring, LDS size and grid every convolution of the network and of rsr_conv3x3 gets
 //      under flow_flags 1 / 2 / 4 / 8 and in precise mode, against rows written out by hand; every plan names a row of the variant list.
+//   4. WsLayout (workspace.h): buffer sizes and the 6,048 / 6,400 B per pixel against the formulas written out by hand, no two planes or
+//      slots overlap, every plane (lo pair planes included) starts a whole number of planes behind its buffer's start in either mode; and
+//      PlanKey: keys that differ in any one field compare unequal.
 #include "../../realsr-ncnn-vulkan_amd/csrc/engine.cpp"
 
 #include <cinttypes>
@@ -328,12 +331,73 @@ static void flow_choice()
     for (int e = 0; e < kEpiCount; e++) CHECK(epi_of(epi_desc(e)) == e);
 }
 
+// WsLayout (workspace.h) against the sizes written out by hand; no overlap; the guard positions; PlanKey
+static void workspace_layout()
+{
+    const int hi[6] = {2, 4, 12, 4, 4, 4}, lo[6] = {0, 2, 2, 0, 0, 0}, level[6] = {1, 1, 1, 4, 16, 16}; // in, fea, rdb, up1, up2, hr
+    const int kind[kWsCount] = {0, 1, 2, 2, 2, 3, 4, 5, -1};                                               // of every buffer; -1: the planar output
+    for (const long long cap : {1ll, 2080ll, 2704ll, 48400ll})
+        for (const bool precise : {false, true})
+        {
+            const WsLayout L{cap, precise}, other{cap, !precise};
+            for (const long long n : {1ll, 3ll, 16ll})
+            {
+                long long sum = 0, guards = 0;
+                for (int b = 0; b < kWsCount; b++)
+                {
+                    const int k = kind[b], planes = k < 0 ? 0 : hi[k] + (precise ? lo[k] : 0);
+                    const long long want = k < 0 ? n * cap * (precise ? 192 : 96) : n * planes * (cap * level[k] * 32 + 64);
+                    CHECK(L.bytes(b, n) == want);
+                    sum += L.bytes(b, n), guards += n * planes * 64;
+                }
+                CHECK(sum - guards == n * cap * (precise ? 6400 : 6048));
+                CHECK(n * cap * WsLayout::bytes_per_px(precise) == sum - guards);
+            }
+            for (int b = 0; b < kWsCount; b++)
+            {
+                if (!WsLayout::guarded(b))
+                {
+                    CHECK(L.lo_off(b) == 0 && L.slot_stride(b) == cap * (precise ? 192 : 96));
+                    continue;
+                }
+                const int k = kind[b];
+                const long long pb = L.plane_bytes(b), px = cap * level[k] * 32;
+                CHECK(pb == other.plane_bytes(b) && pb == px + kGuard); // the plane, hence the guards' spacing, does not depend on the mode
+                CHECK((L.lo_off(b) != 0) == (precise && lo[k] != 0));
+                // the pixel ranges [start, start + px) of every plane of three slots, as the kernels address them: hi plane p at plane_off(p),
+                // lo pair plane q at plane_off(0) + lo_off + q * plane stride (conv_flow.hip lo_row), slot s at s * slot_stride
+                std::vector<long long> starts;
+                for (long long s = 0; s < 3; s++)
+                {
+                    for (int p = 0; p < hi[k]; p++) starts.push_back(s * L.slot_stride(b) + L.plane_off(b, p));
+                    for (int q = 0; q < (precise ? lo[k] : 0); q++) starts.push_back(s * L.slot_stride(b) + L.plane_off(b, 0) + L.lo_off(b) + q * pb);
+                }
+                CHECK((long long)starts.size() == 3 * L.planes_per_slot(b));
+                for (size_t i = 0; i < starts.size(); i++)
+                {
+                    // every plane starts a whole number of planes behind the buffer's start: its guard is one of those launch_zero_guards clears
+                    CHECK((starts[i] - kGuard) % pb == 0 && starts[i] >= kGuard && starts[i] + px <= L.bytes(b, 3));
+                    for (size_t j = 0; j < i; j++) CHECK(starts[i] - starts[j] >= pb || starts[j] - starts[i] >= pb); // a guard apart at least: no overlap
+                }
+            }
+        }
+    // PlanKey: equal to itself, unequal when any single field differs
+    const PlanKey k0{70, 20, 3, 32, 10, 0, 1, false, OutRatio(), false, 0, 3, 65536, true, true, true, -1};
+    PlanKey v[17];
+    for (PlanKey& k : v) k = k0;
+    v[0].w++, v[1].h++, v[2].c++, v[3].T++, v[4].P++, v[5].tta++, v[6].nimg++, v[7].precise = true, v[8].ratio = OutRatio(2, 1), v[9].ntw2 = true, v[10].tile0++, v[11].tile1++,
+        v[12].budget_mb++, v[13].trim = false, v[14].xcd_order = false, v[15].fold = false, v[16].clamp = 0;
+    CHECK(k0 == PlanKey(k0));
+    for (const PlanKey& k : v) CHECK(!(k == k0) && !(k0 == k));
+}
+
 int main()
 {
     descriptors();
     admission();
     batches();
     flow_choice();
+    workspace_layout();
     if (failures) return std::fprintf(stderr, "%d check(s) failed\n", failures), 1;
     std::puts("descriptor_check ok");
     return 0;
