@@ -63,3 +63,14 @@ def exact_area_mean(v, n, d, top=1.0):
                 out[..., X] += g * a[..., i]
         return out
     return np.swapaxes(along(np.swapaxes(along(c), -1, -2)), -1, -2) / (16.0 * d * d)
+
+
+def check_u8(gots, ds, what=""):
+    """gots: uint8 HWC outputs; ds: their float32 references m, planar.  The rule of tests/test_gpu_out_scale.py over the pooled elements."""
+    g = np.concatenate([got.transpose(2, 0, 1).reshape(-1) for got in gots])
+    want, near = u8_expected(np.concatenate([d.reshape(-1) for d in ds]))
+    print("%suint8: %d elements, %d left out (within 2^-14 of a rounding boundary), %d differ" % (what, g.size, near.sum(), ((g != want) & ~near).sum()))
+    assert g.size >= 20000, g.size
+    assert near.mean() <= 1e-3, near.mean()
+    assert np.array_equal(g[~near], want[~near])
+    assert (np.abs(g.astype(int) - want.astype(int))[near] <= 1).all()

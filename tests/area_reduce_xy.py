@@ -9,6 +9,7 @@ import numpy as np
 import yuv_ref
 import yuv_siting_ref
 from area_reduce import RATIOS, _along_x, taps  # noqa: F401  (taps: one axis is one axis, whatever the other does)
+from tile_diff_ref import out_rect
 
 F32 = np.float32
 
@@ -95,7 +96,4 @@ def encode_xy(d, siting, tile_out_x, tile_out_y, matrix=709, full=0, bits=8):
 
 def out_rect_xy(w, h, T, tile, rx, ry):
     """(x0, y0, x1, y1) of the tile's output rectangle at the pair (rx, ry)."""
-    nxt = -(-w // T)
-    yi, xi = divmod(tile, nxt)
-    (nx, dx), (ny, dy) = rx, ry
-    return (xi * T * nx // dx, yi * T * ny // dy, min((xi + 1) * T, w) * nx // dx, min((yi + 1) * T, h) * ny // dy)
+    return out_rect(w, h, T, tile, *rx, *ry)

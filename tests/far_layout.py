@@ -24,9 +24,8 @@ allocation.  Several windows share an arena at different byte columns (COLS); on
 """
 import numpy as np
 
-U8, F16, F32, NV12, P010 = 0, 1, 2, 4, 5  # RSR_FMT_* (include/realsr_hip.h)
-ES = {U8: 1, F16: 2, F32: 4, NV12: 1, P010: 2}
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16}
+from pixfmt_ref import ES, F16, F32, NP, NV12, P010, U8, image_at, is_yuv, plane_rows, shape_of  # noqa: F401  (the formats: tests/pixfmt_ref.py)
+
 W, H, T, P = 52, 44, 32, 10
 MH = 3  # rows of a layout-M image (a surface: 2)
 B31, B32 = 1 << 31, 1 << 32
@@ -44,17 +43,8 @@ SIZES = [(W * n // d, H * n // d) for n, d in RATIOS]
 KINDS = ("R", "Pn", "M")
 
 
-def is_yuv(fmt):
-    return fmt in (NV12, P010)
-
-
 def rowbytes(fmt, w, c=3):
     return w * (c if fmt == U8 else ES[fmt])
-
-
-def plane_rows(fmt, h):
-    """Rows of every plane of an h-row image: one (uint8 HWC), three (planar), Y and UV (a surface)."""
-    return [h] if fmt == U8 else ([h, h // 2] if is_yuv(fmt) else [h, h, h])
 
 
 def cols(fmt, kind="R"):
@@ -226,19 +216,7 @@ def crossings(win):
 
 
 # ---- images -------------------------------------------------------------------------------------------------------------------------------
-def image(seed, fmt, w=W, h=H, c=3):
-    """A seeded random image in the library's packed layout: uint8 (h, w, c); float (3, h, w) in [0, 1); a surface (3h / 2, w)."""
-    rng = np.random.default_rng(seed)
-    if fmt == U8:
-        return rng.integers(0, 256, size=(h, w, c), dtype=np.uint8)
-    if fmt in (F16, F32):
-        return rng.uniform(0, 1, size=(3, h, w)).astype(NP[fmt])
-    codes = rng.integers(0, 256 if fmt == NV12 else 1024, size=(h * 3 // 2, w))
-    return codes.astype(np.uint8) if fmt == NV12 else (codes << 6).astype(np.uint16)
-
-
-def shape_of(fmt, w, h, c=3):
-    return (h, w, c) if fmt == U8 else ((h * 3 // 2, w) if is_yuv(fmt) else (3, h, w))
+image = image_at(W, H)  # a seeded random image in the library's packed layout
 
 
 def raw(x):

@@ -465,7 +465,7 @@ def test_six_blocks_oracle_parity():
 
 def test_cli_loads_a_six_block_directory_and_prints_the_depth(tmp_path):
     """realsr-hip -m <a 6-block directory> -v: "6 blocks, 96 convolutions" on stderr, and the image a context of that model writes."""
-    from test_cli import CLI, read_png, write_png
+    from cli_support import CLI, read_png, write_png
     d = synth.make_model_dir(os.environ.get("RSR_MODELS", "/tmp/rsr_models"), "models-DF2K", 42, nb=6)
     img = synth.make_image(7, 50, 43)
     write_png(tmp_path / "in.png", img)

@@ -9,7 +9,6 @@ to 32 bits is shown on the CPU (tests/test_far_layout.py), and every such offset
 
 The two arenas are module-scoped (13.1 GiB together) and freed at teardown; with less than that + 4 GiB of free device memory the module
 skips, naming both figures."""
-import os
 from fractions import Fraction
 
 import numpy as np
@@ -23,47 +22,15 @@ import far_layout as fl
 import sequence_ref
 import tile_diff_ref as ref
 from far_layout import F16, F32, H, NV12, P010, T, U8, W, P
-from test_gpu_tensor_batch import ROUTES
-from test_gpu_tile_mask import DIFF_FORMATS
+from gpu_support import DIFF_FORMATS, ROUTE_IDS, ROUTES, context_fixtures, dev, out_dims, paths  # noqa: F401
+from pixfmt_ref import paste, sentinel_bytes as sentinel
 
 pytestmark = pytest.mark.gpu
 NP = fl.NP
 NT = 4  # 2 x 2 tiles
-ROUTE_IDS = ["fused", "unfused", "unfused-staged", "tta", "tta-staged"]
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, P
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0), ("dbg", 0),
-                   ("max_workspace_mb", 65536)):
-        s.set_option(key, v)
-    s.set_profiling(False)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation); everything else is an option of a call."""
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
+ctxs, ctx = context_fixtures(T, P)
 
 
 class Arenas:
@@ -93,29 +60,14 @@ def A():
 
 
 # ---- helpers ------------------------------------------------------------------------------------------------------------------------------
-def dev(x):
-    return torch.from_numpy(fl.raw(x).copy()).cuda()
-
-
 def filled_bytes(n):
     return torch.full((n,), fl.FILL, dtype=torch.uint8, device="cuda")
-
-
-def sentinel(fmt, shape):
-    """A numpy image of the format, every byte 0xCD."""
-    n = int(np.prod(shape)) * np.dtype(NP[fmt]).itemsize
-    return np.full(n, fl.FILL, dtype=np.uint8).view(NP[fmt]).reshape(shape)
 
 
 def noise(seed, fmt, shape):
     """A numpy image of the format of random BYTES: a previous output no network produces."""
     n = int(np.prod(shape)) * np.dtype(NP[fmt]).itemsize
     return np.random.default_rng(seed).integers(0, 256, size=n, dtype=np.uint8).view(NP[fmt]).reshape(shape)
-
-
-def out_dims(s, w=W, h=H):
-    r = s.out_ratio
-    return w * r.numerator // r.denominator, h * r.numerator // r.denominator
 
 
 def kind_of(fmt, kind):
@@ -183,7 +135,7 @@ def far_run(A, in_wins, xs, out_wins, wants, call, before=None):
 
 def batch_case(A, s, kind, in_fmt, out_fmt, c=3, odd=False, n=1, seed=100):
     """n images through rsr_process_device_batch: far on both sides against packed on both sides, at the options in force."""
-    ow, oh = out_dims(s)
+    ow, oh = out_dims(s, W, H)
     xs = [fl.image(seed + i, in_fmt, W, H, c) for i in range(n)]
     wants = packed_batch(s, xs, in_fmt, out_fmt, c)
     iw, ows = windows(kind, in_fmt, W, H, c, odd, n), windows(kind, out_fmt, ow, oh, c, odd, n)
@@ -295,7 +247,7 @@ def test_reduced_outputs(ctx, A, ratio, fmt, siting, kind):
     s = ctx[False]
     s.set_option("yuv_siting", siting)
     s.out_ratio = ratio
-    assert out_dims(s) in fl.SIZES
+    assert out_dims(s, W, H) in fl.SIZES
     batch_case(A, s, kind, fmt, fmt, odd=(ratio == 1), seed=170)
 
 
@@ -307,19 +259,6 @@ def test_reduced_outputs_under_tta(ctx, A, ratio, fmt, kind):
 
 
 # ---- (b) rsr_process_device_masked --------------------------------------------------------------------------------------------------------
-def paste(fmt, dst, src, rect):
-    """The output rectangle `rect` of src into dst (numpy images of format fmt)."""
-    x0, y0, x1, y1 = rect
-    if fmt == U8:
-        dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-    elif fmt in (F16, F32):
-        dst[:, y0:y1, x0:x1] = src[:, y0:y1, x0:x1]
-    else:
-        oh = dst.shape[0] * 2 // 3
-        dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-        dst[oh + y0 // 2:oh + y1 // 2, x0:x1] = src[oh + y0 // 2:oh + y1 // 2, x0:x1]
-
-
 FAR3 = [(U8, "R"), (F32, "R"), (F32, "Pn"), (NV12, "R"), (NV12, "Pn")]
 FAR3_IDS = ["u8-R", "f32-R", "f32-Pn", "nv12-R", "nv12-Pn"]
 
@@ -468,8 +407,6 @@ def test_diff_of_far_operands(ctx, A, fmtcase, kind):
     for want, m, what, col in got:
         assert m == want, (what, col)
     assert bad_in is None and bad_out is None, (bad_in, bad_out)
-
-
 
 
 @pytest.mark.parametrize("fmtcase,kind", DIFF_CASES, ids=["%s-%s" % (f[0], k) for f, k in DIFF_CASES])

@@ -4,7 +4,6 @@ The reference runs concurrent process() calls of its proc threads side by side o
 many small images"); here they share the launches.  A tile is computed the same way whoever shares its batch, so every image must come
 out BYTE-IDENTICAL to the one a lone call produces -- host and device API, RGB (conv_last writes the images itself), RGBA and TTA
 (planar blob + postproc), mixed geometries in flight at once, merging on and off."""
-import os
 import threading
 
 import numpy as np
@@ -12,13 +11,9 @@ import pytest
 
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import synth
+from gpu_support import paths  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
 
 
 def run_threads(n, fn):

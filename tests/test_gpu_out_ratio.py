@@ -22,91 +22,20 @@ import realsr_ncnn_vulkan_amd as R
 import yuv_ref
 from realsr_ncnn_vulkan_amd import torch_io
 
-from area_reduce import GENERIC, area_reduce, u8_expected
+import gpu_support as G
+from area_reduce import GENERIC, area_reduce, check_u8
+from gpu_support import context_fixtures, filled, paths, untouched  # noqa: F401
+from pixfmt_ref import F16, F32, NV12, U8, bits, halfs, u8_image as image
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW, R.RSR_FMT_NV12
-TORCH = {U8: torch.uint8, F16: torch.float16, F32: torch.float32}
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture(autouse=True)
-def back_to_defaults(ctxs):
-    yield
-    for s in ctxs.values():
-        s.out_scale = 4
-        s.set_option("precise", 0)
-        s.set_option("bgr", 0)
-        s.set_option("merge", 16)
-
-
-def image(seed, w, h, c=3):
-    return np.random.default_rng(seed).integers(0, 256, size=(h, w, c), dtype=np.uint8)
-
-
-def halfs(seed, w, h):
-    """A planar fp16 image with values the uint8 path cannot make."""
-    return np.random.default_rng(seed).random((3, h, w), dtype=np.float32).astype(np.float16)
-
-
-def filled(shape, fmt):
-    if fmt == U8:
-        return torch.full(shape, 0xCD, dtype=torch.uint8, device="cuda")
-    return torch.full(shape, float("nan"), dtype=TORCH[fmt], device="cuda")
-
-
-def untouched(t):
-    return bool((t == 0xCD).all()) if t.dtype == torch.uint8 else bool(torch.isnan(t).all())
-
-
-def geometry(x, fmt):
-    return (x.shape[1], x.shape[0], x.shape[2]) if fmt == U8 else (x.shape[2], x.shape[1], 3)
+ctxs, back_to_defaults = context_fixtures(autouse=True)
 
 
 def run(s, x, in_fmt, out_fmt, ratio):
     """One synchronous rsr_process_device_fmt call at output ratio `ratio` on the packed numpy image x; the result as a numpy array."""
-    w, h, c = geometry(x, in_fmt)
     s.out_ratio = ratio
     assert s.out_ratio == (Fraction(*ratio) if isinstance(ratio, tuple) else Fraction(ratio))
-    ow, oh = s.out_size(w, h)
-    d_in = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    d_out = filled((oh, ow, c) if out_fmt == U8 else (3, oh, ow), out_fmt)
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, c, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    got = d_out.cpu().numpy()
-    if out_fmt != U8:
-        assert not np.isnan(got).any()  # every element was written
-    return got
-
-
-def bits(a):
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
-
-
-def check_u8(gots, ds, what=""):
-    """gots: uint8 HWC outputs; ds: their float32 references m, planar.  The rule of tests/test_gpu_out_scale.py over the pooled elements."""
-    g = np.concatenate([got.transpose(2, 0, 1).reshape(-1) for got in gots])
-    want, near = u8_expected(np.concatenate([d.reshape(-1) for d in ds]))
-    print("%suint8: %d elements, %d left out (within 2^-14 of a rounding boundary), %d differ" % (what, g.size, near.sum(), ((g != want) & ~near).sum()))
-    assert g.size >= 20000, g.size
-    assert near.mean() <= 1e-3, near.mean()
-    assert np.array_equal(g[~near], want[~near])
-    assert (np.abs(g.astype(int) - want.astype(int))[near] <= 1).all()
+    return G.run(s, x, in_fmt, out_fmt, nan=True)
 
 
 def check_formats(s, n, d, w, h, seed, pool=1):
@@ -447,7 +376,7 @@ def test_integer_ratios_are_out_scale(ctxs, paths):
 
 # ---- 9. the CLI ------------------------------------------------------------------------------------------------------------------------
 def test_cli_out_ratio(ctxs, tmp_path, model_dir):
-    from test_cli import CLI, read_png, write_png
+    from cli_support import CLI, read_png, write_png
     s = ctxs[False]
     s.tilesize = 32
     img = image(8300, 40, 30)

@@ -20,13 +20,13 @@ import realsr_ncnn_vulkan_amd as R
 import yuv_ref
 
 import far_layout as fl
+import gpu_support as G
 from area_reduce_xy import area_reduce_xy, encode_xy, out_rect_xy
-from test_gpu_out_ratio import bits, check_u8
+from area_reduce import check_u8
+from gpu_support import context_fixtures, dev, paths, profile_of  # noqa: F401
+from pixfmt_ref import BITS, F16, F32, NP, NV12, P010, U8, bits, image as surface, paste, pattern, same_bits, u8_image as image
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12, P010 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW, R.RSR_FMT_NV12, R.RSR_FMT_P010
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16}
-BITS = {NV12: 8, P010: 10}
 SENTINEL = 0xCD
 # (x ratio, y ratio, w, h, tilesize)
 CASES = [((8, 3), (9, 4), 60, 44, 24),     # 160 x 99: a 3 x 2 tile grid whose last tiles are 12 wide, 20 high
@@ -41,37 +41,7 @@ RX, RY, W, H, T = CASES[0]
 HY = 40  # the height of the YUV cases at (8/3, 9/4): 160 x 90, tile rectangles of 64 x 54
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, 10
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0)):
-        s.set_option(key, v)
-    s.set_profiling(False)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation), and a second plain one for the group."""
-    made = {}
-    for key, tta in ((False, False), (True, True), ("other", False)):
-        made[key] = R.RealSR(0, tta_mode=tta)
-        made[key].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
+ctxs, ctx = context_fixtures(T, 10, others=("other",))
 
 
 def fr(r):
@@ -83,29 +53,6 @@ def set_pair(s, rx, ry, tile=None):
         s.tilesize = tile
     s.out_ratio_xy = (fr(rx), fr(ry))
     assert s.out_ratio_xy == (fr(rx), fr(ry))
-
-
-def image(seed, w, h, c=3):
-    return np.random.default_rng(seed).integers(0, 256, size=(h, w, c), dtype=np.uint8)
-
-
-def surface(seed, fmt, w, h):
-    codes = np.random.default_rng(seed).integers(0, 1 << BITS[fmt], size=(h * 3 // 2, w))
-    return codes.astype(np.uint8) if fmt == NV12 else (codes << 6).astype(np.uint16)
-
-
-def shape_of(fmt, w, h, c=3):
-    return (h, w, c) if fmt == U8 else ((h * 3 // 2, w) if fmt in BITS else (3, h, w))
-
-
-def geometry(x, fmt):
-    if fmt == U8:
-        return x.shape[1], x.shape[0], x.shape[2]
-    return (x.shape[1], x.shape[0] * 2 // 3, 3) if fmt in BITS else (x.shape[2], x.shape[1], 3)
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()
 
 
 def filled_bytes(n, fmt):
@@ -122,20 +69,7 @@ def untouched_np(a, fmt):
 
 def run(s, x, in_fmt, out_fmt):
     """One synchronous rsr_process_device_fmt call at the context's ratio or pair on the packed numpy image x; the result as a numpy array."""
-    w, h, c = geometry(x, in_fmt)
-    ow, oh = s.out_size_yuv(w, h) if out_fmt in BITS else s.out_size(w, h)
-    d_in = dev(x)
-    d_out = filled_bytes(R.image_bytes(out_fmt, ow, oh, c), out_fmt)
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, c, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    got = d_out.cpu().numpy().view(NP[out_fmt]).reshape(shape_of(out_fmt, ow, oh, c))
-    if out_fmt in (F16, F32):
-        assert not np.isnan(got).any()  # every element was written
-    return got
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+    return G.run(s, x, in_fmt, out_fmt, nan=True)
 
 
 def x4_f32(s, x, in_fmt):
@@ -278,18 +212,6 @@ def test_yuv_outputs(ctx, i):
 
 
 # ---- 4. equal axes -----------------------------------------------------------------------------------------------------------------------
-def profiled(s, fn):
-    s.set_option("merge", 1)
-    s.set_profiling(True)
-    try:
-        s.get_profile(reset=True)
-        out = fn()
-        return out, s.get_profile(reset=True)
-    finally:
-        s.set_profiling(False)
-        s.set_option("merge", 16)
-
-
 COUNTS = ("conv_launches", "post_bytes", "pre_bytes", "tiles", "calls", "conv_flops")
 STATS = ("out_scale", "out_num", "out_den", "out_num_x", "out_den_x", "out_num_y", "out_den_y")
 
@@ -304,7 +226,7 @@ def test_equal_axes_are_the_single_ratio(ctx):
         else:
             s.out_ratio = ratio
         assert tuple(s.get_stat(k) for k in STATS) == stats
-        want, p0 = profiled(s, lambda: [run(s, img, U8, U8), run(s, img, U8, F32), run(s, surf, NV12, NV12)])
+        want, p0 = profile_of(s, lambda: [run(s, img, U8, U8), run(s, img, U8, F32), run(s, surf, NV12, NV12)], merge=1)
         set_pair(s, RX, RY)  # (leave it, and come back through rsr_set_out_ratio_xy, unreduced)
         assert tuple(s.get_stat(k) for k in STATS) == (0, 0, 0, 8, 3, 9, 4)
         with pytest.raises(ValueError, match="out_ratio_xy"):
@@ -312,7 +234,7 @@ def test_equal_axes_are_the_single_ratio(ctx):
         n, d = ratio.numerator, ratio.denominator
         assert s._L.rsr_set_out_ratio_xy(s._h, 2 * n, 2 * d, 3 * n, 3 * d) == R.RSR_OK
         assert tuple(s.get_stat(k) for k in STATS) == stats and s.out_ratio == ratio
-        got, p1 = profiled(s, lambda: [run(s, img, U8, U8), run(s, img, U8, F32), run(s, surf, NV12, NV12)])
+        got, p1 = profile_of(s, lambda: [run(s, img, U8, U8), run(s, img, U8, F32), run(s, surf, NV12, NV12)], merge=1)
         for a, b in zip(got, want):
             assert same_bits(a, b)
         for key in COUNTS:
@@ -346,7 +268,7 @@ def test_default_path_guard(ctx, paths):
 
     def u8_call(s):
         s.tilesize, s.prepadding = T, 10
-        return profiled(s, lambda: run(s, img, U8, U8))
+        return profile_of(s, lambda: run(s, img, U8, U8), merge=1)
 
     fresh = R.RealSR(0)
     try:
@@ -368,9 +290,9 @@ def test_default_path_guard(ctx, paths):
         assert p1[key] == p0[key], key
     # a pair is the same conv launches and ONE post-processing launch; the byte accounting follows both axes
     set_pair(s, RX, RY)
-    _, p2 = profiled(s, lambda: run(s, img, U8, F32))
+    _, p2 = profile_of(s, lambda: run(s, img, U8, F32), merge=1)
     set_pair(s, RX, (4, 1))
-    _, p3 = profiled(s, lambda: run(s, img, U8, F32))
+    _, p3 = profile_of(s, lambda: run(s, img, U8, F32), merge=1)
     assert p2["conv_launches"] == R.NUM_CONVS and p2["post_ms"] > 0 and p2["calls"] == 1
     assert 0 < p2["post_bytes"] < p3["post_bytes"]
 
@@ -409,20 +331,6 @@ def test_batch_of_five_into_pitched_windows_equals_lone_calls(ctx, tta):
         assert untouched_np(got[~inside], out_fmt)  # the outside of every window
 
 
-def paste(dst, src, rect, fmt):
-    """The output rectangle `rect` of the image src into dst (uint8 HWC, or a surface: its Y rows and its UV rows)."""
-    x0, y0, x1, y1 = rect
-    dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-    if fmt in BITS:
-        oh = dst.shape[0] * 2 // 3
-        dst[oh + y0 // 2:oh + y1 // 2, x0:x1] = src[oh + y0 // 2:oh + y1 // 2, x0:x1]
-
-
-def pattern(fmt, shape):
-    """A previous output that is recognisably NOT a network output: a byte ramp of period 251."""
-    return (np.arange(int(np.prod(shape)), dtype=np.int64).reshape(shape) % 251).astype(NP[fmt])
-
-
 @pytest.mark.parametrize("fmt", [U8, NV12], ids=["u8", "nv12"])
 def test_masked_call_writes_exactly_the_marked_per_axis_rectangles(ctx, fmt):
     s = ctx[False]
@@ -444,7 +352,7 @@ def test_masked_call_writes_exactly_the_marked_per_axis_rectangles(ctx, fmt):
         want = before.copy()
         for t in range(nt):
             if mask[t]:
-                paste(want, plain, rects[t], fmt)
+                paste(fmt, want, plain, rects[t])
         assert same_bits(d_out.cpu().numpy().view(NP[fmt]).reshape(plain.shape), want), mask
 
 
@@ -471,7 +379,7 @@ def test_sequence_of_three_frames_with_a_previous_output(ctx, fmt):
     for k in range(n):
         want = np.full(plains[0].shape, SENTINEL, dtype=NP[fmt])
         for t in range(nt):
-            paste(want, prev if src[k, t] < 0 else plains[src[k, t]], rects[t], fmt)
+            paste(fmt, want, prev if src[k, t] < 0 else plains[src[k, t]], rects[t])
         assert sum((r[2] - r[0]) * (r[3] - r[1]) for r in rects) == 160 * (h * 9 // 4)  # the rectangles cover the window: every byte is written
         assert same_bits(d_outs[k].cpu().numpy().view(NP[fmt]).reshape(plains[0].shape), want), k
     assert same_bits(d_prev.cpu().numpy().view(NP[fmt]).reshape(prev.shape), prev)
@@ -606,7 +514,7 @@ def test_an_output_window_whose_rows_lie_beyond_2_to_32(ctx):
 
 # ---- 8. the CLI --------------------------------------------------------------------------------------------------------------------------
 def test_cli_out_ratio_xy(ctx, tmp_path, model_dir):
-    from test_cli import CLI, read_png, write_png
+    from cli_support import CLI, read_png, write_png
     s = ctx[False]
     img = image(7600, 72, 48)
     write_png(tmp_path / "a.png", img)

@@ -16,82 +16,24 @@ import torch
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import torch_io
 
+import gpu_support as G
 from box_reduce import box_reduce, u8_expected
+from gpu_support import context_fixtures, filled, paths, untouched  # noqa: F401
+from pixfmt_ref import F16, F32, U8, bits, halfs, u8_image as image
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32}
-TORCH = {U8: torch.uint8, F16: torch.float16, F32: torch.float32}
 # (w, h, tilesize) of tests/test_gpu_tensor_batch.py: partial last tiles | a folded last column | the same at tile 100 | smaller than a tile
 GEOS = [(61, 47, 32), (53, 47, 32), (121, 110, 100), (40, 30, 100)]
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture(autouse=True)
-def back_to_defaults(ctxs):
-    yield
-    for s in ctxs.values():
-        s.out_scale = 4
-        s.set_option("precise", 0)
-        s.set_option("bgr", 0)
-        s.set_option("merge", 16)
-
-
-def image(seed, w, h, c=3):
-    return np.random.default_rng(seed).integers(0, 256, size=(h, w, c), dtype=np.uint8)
-
-
-def halfs(seed, w, h):
-    """A planar fp16 image with values the uint8 path cannot make."""
-    return np.random.default_rng(seed).random((3, h, w), dtype=np.float32).astype(np.float16)
-
-
-def filled(shape, fmt):
-    if fmt == U8:
-        return torch.full(shape, 0xCD, dtype=torch.uint8, device="cuda")
-    return torch.full(shape, float("nan"), dtype=TORCH[fmt], device="cuda")
-
-
-def untouched(t):
-    return bool((t == 0xCD).all()) if t.dtype == torch.uint8 else bool(torch.isnan(t).all())
-
-
-def geometry(x, fmt):
-    return (x.shape[1], x.shape[0], x.shape[2]) if fmt == U8 else (x.shape[2], x.shape[1], 3)
+ctxs, back_to_defaults = context_fixtures(autouse=True)
 
 
 def run(s, x, in_fmt, out_fmt, scale):
     """One synchronous rsr_process_device_fmt call at out_scale `scale` on the packed numpy image x; the result as a numpy array."""
-    w, h, c = geometry(x, in_fmt)
     s.out_scale = scale
     assert s.get_stat("out_scale") == scale
-    d_in = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    d_out = filled((h * scale, w * scale, c) if out_fmt == U8 else (3, h * scale, w * scale), out_fmt)
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, c, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    got = d_out.cpu().numpy()
-    if out_fmt != U8:
-        assert not np.isnan(got).any()  # every element was written
-    return got
-
-
-def bits(a):
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint16)
+    return G.run(s, x, in_fmt, out_fmt, nan=True)
 
 
 def check_u8(got, d):
@@ -379,7 +321,7 @@ def test_device_direct_still_counts(ctxs):
 
 
 def test_cli_out_scale(ctxs, tmp_path, model_dir):
-    from test_cli import CLI, read_png, write_png
+    from cli_support import CLI, read_png, write_png
     s = ctxs[False]
     s.tilesize = 32
     img = image(9950, 40, 30)

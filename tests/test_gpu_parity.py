@@ -11,14 +11,10 @@ import pytest
 import oracle
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import synth
+from gpu_support import paths  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
 
 
 @pytest.fixture(scope="module")

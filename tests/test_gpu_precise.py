@@ -15,6 +15,7 @@ import pytest
 import oracle
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import synth
+from gpu_support import paths  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -38,11 +39,6 @@ def rand_hi_lo(rng, shape):
 
 def join(hi, lo):
     return hi.astype(np.float32) + bf8(lo) / LO
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
 
 
 @pytest.fixture(scope="module")

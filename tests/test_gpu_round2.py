@@ -16,14 +16,10 @@ import oracle
 import oracle_pool
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import synth
+from gpu_support import paths  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
 
 
 @pytest.fixture(scope="module")

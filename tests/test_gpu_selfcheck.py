@@ -355,7 +355,7 @@ def test_overflow_is_reported_not_raised():
 def test_cli_warns_about_overflow_without_verbose(tmp_path):
     """RSR_PRECISE_AUTO=1 without -v: silent on a healthy model (test_cli_precise_auto), ONE warning line per GPU when the activations
     overflow fp16; the run itself is not refused (the decision is the caller's)."""
-    from test_cli import write_png
+    from cli_support import write_png
     d = synth.make_model_dir(os.environ.get("RSR_MODELS", "/tmp/rsr_models"), "models-DF2K_sc_44hot512", 44, hot=512.0, last_gain=0.15)
     write_png(tmp_path / "in.png", synth.make_image(7, 50, 43))
     env = {k: v for k, v in os.environ.items() if k not in ("RSR_PRECISE", "RSR_PRECISE_AUTO")}
@@ -392,7 +392,7 @@ def test_two_contexts_and_a_group_member_agree(monkeypatch):
 
 # ---- 12. CLI -------------------------------------------------------------------------------------------------------------------------
 def test_cli_precise_auto(tmp_path):
-    from test_cli import read_png, write_png
+    from cli_support import read_png, write_png
     img, want = c1_image(), oracle_c1("45wide")
     mdir = os.path.dirname(model_paths("45wide")[0])
     write_png(tmp_path / "in.png", img)

@@ -20,10 +20,10 @@ from realsr_ncnn_vulkan_amd import torch_io
 
 import sequence_ref
 import tile_diff_ref as ref
+from gpu_support import DIFF_FORMATS, context_fixtures, dev, out_dims, paths, profile_of  # noqa: F401
+from pixfmt_ref import F16, F32, NP, NV12, P010, U8, image_at, paste, pattern, same_bits, sentinel, shape_of
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12, P010 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW, R.RSR_FMT_NV12, R.RSR_FMT_P010
-NP = ref.NP
 W, H, T, P = 70, 50, 32, 10
 NT, N = 6, 4
 CHECKER = [1, 0, 1, 0, 1, 0]
@@ -36,84 +36,8 @@ SEQ_STATS = ("seq_calls", "seq_frames", "seq_tiles_run", "seq_tiles_copied", "se
 MASKED_STATS = ("masked_calls", "masked_tiles_run", "masked_tiles_skipped", "masked_batches")
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    import os
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, P
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0),
-                   ("max_workspace_mb", 65536)):
-        s.set_option(key, v)
-    s.set_profiling(False)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation); everything else is an option of a call."""
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
-
-
-def shape_of(fmt, w, h, c=3):
-    return (h, w, c) if fmt == U8 else ((h * 3 // 2, w) if fmt in (NV12, P010) else (3, h, w))
-
-
-def image(seed, fmt, w=W, h=H, c=3):
-    rng = np.random.default_rng(seed)
-    if fmt == U8:
-        return rng.integers(0, 256, size=(h, w, c), dtype=np.uint8)
-    if fmt in (F16, F32):
-        return rng.uniform(0, 1, size=(3, h, w)).astype(NP[fmt])
-    codes = rng.integers(0, 256 if fmt == NV12 else 1024, size=(h * 3 // 2, w))
-    return codes.astype(np.uint8) if fmt == NV12 else (codes << 6).astype(np.uint16)
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def sentinel(fmt, shape):
-    """A numpy image of the format, filled with 0xCD bytes (float formats: NaN)."""
-    if fmt in (F16, F32):
-        return np.full(shape, np.nan, dtype=NP[fmt])
-    return np.full(shape, 0xCDCD if fmt == P010 else 0xCD, dtype=NP[fmt])
-
-
-def pattern(fmt, shape):
-    """A previous output that is recognisably NOT a network output: negative floats, P010 words with the low six bits set, a byte ramp of
-    period 251."""
-    i = np.arange(int(np.prod(shape)), dtype=np.int64).reshape(shape)
-    if fmt in (F16, F32):
-        return (-2.0 - (i % 977)).astype(NP[fmt])
-    if fmt == P010:
-        return (((i % 1021) << 6) | 0x2B).astype(np.uint16)
-    return (i % 251).astype(np.uint8)
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def out_dims(s, w, h):
-    r = s.out_ratio
-    return w * r.numerator // r.denominator, h * r.numerator // r.denominator
+ctxs, ctx = context_fixtures(T, P)
+image = image_at(W, H)
 
 
 def plain_call(s, x, in_fmt, out_fmt, w=W, h=H, c=3):
@@ -146,19 +70,6 @@ def seq_call(s, xs, in_fmt, out_fmt, masks, prev=None, w=W, h=H, c=3, in_place=F
     if prev is not None and not in_place:
         assert same_bits(d_prev.cpu().numpy().view(NP[out_fmt]).reshape(oshape), prev)
     return [d.cpu().numpy().view(NP[out_fmt]).reshape(oshape) for d in d_outs]
-
-
-def paste(fmt, dst, src, rect):
-    """The output rectangle `rect` of src into dst (numpy images of format fmt)."""
-    x0, y0, x1, y1 = rect
-    if fmt == U8:
-        dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-    elif fmt in (F16, F32):
-        dst[:, y0:y1, x0:x1] = src[:, y0:y1, x0:x1]
-    else:
-        oh = dst.shape[0] * 2 // 3
-        dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-        dst[oh + y0 // 2:oh + y1 // 2, x0:x1] = src[oh + y0 // 2:oh + y1 // 2, x0:x1]
 
 
 def expected(s, fmt, plains, masks, prev, w=W, h=H):
@@ -253,9 +164,6 @@ def video(fmt, seed, n, c=3):
         else:
             frames.append(poke(fmt, frames[-1], sp[0], sp[1], ch=(c - 1 if fmt == U8 else k % 3)))
     return frames
-
-
-DIFF_FORMATS = [("u8c3", U8, 3), ("u8c4", U8, 4), ("f16", F16, 3), ("f32", F32, 3), ("nv12", NV12, 3), ("p010", P010, 3)]
 
 
 @pytest.mark.parametrize("name,fmt,c", DIFF_FORMATS, ids=[f[0] for f in DIFF_FORMATS])
@@ -486,16 +394,6 @@ def test_a_refused_workspace_halves_this_call_and_leaves_no_clamp(ctx):
 
 
 # ---- 6. in place and the degenerate cases ---------------------------------------------------------------------------------------------------
-def profile_of(s, fn):
-    s.set_profiling(True)
-    s.get_profile(reset=True)
-    try:
-        out = fn()
-        return out, s.get_profile(reset=True)
-    finally:
-        s.set_profiling(False)
-
-
 @pytest.mark.parametrize("tta", [False, True], ids=["plain", "tta"])
 def test_in_place_degenerate_cases_stats_and_progress(ctx, tta):
     s = ctx[tta]

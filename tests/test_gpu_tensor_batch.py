@@ -7,7 +7,6 @@ tolerance appears anywhere.  Outputs are pre-filled with what no call writes (Na
 outside a window, shows.  The parity of a lone call against the oracle is tests/test_gpu_parity.py and tests/test_gpu_tensor_io.py.
 """
 import ctypes as C
-import os
 import threading
 
 import numpy as np
@@ -17,11 +16,10 @@ import torch
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import torch_io
 
-pytestmark = pytest.mark.gpu
-U8, F16, F32 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32}
-TORCH = {U8: torch.uint8, F16: torch.float16, F32: torch.float32}
+from gpu_support import ROUTE_IDS, ROUTES, TORCH, context_fixtures, filled, paths, run, untouched  # noqa: F401
+from pixfmt_ref import F16, F32, NP, U8, same_bits, sentinel, u8_image as image
 
+pytestmark = pytest.mark.gpu
 # (w, h, tilesize) of tests/test_gpu_tensor_io.py: partial last tiles both ways | a folded last column (kernels.h kFoldBit) | the same at
 # tile 100 | an image smaller than a tile
 GEOS = [(61, 47, 32), (53, 47, 32), (121, 110, 100), (40, 30, 100)]
@@ -29,25 +27,7 @@ PAIRS = [(U8, U8), (F16, F32), (F32, F16), (U8, F16)]
 FOLDED = (53, 47, 32)
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation); precise / bgr / dbg / merge are options of a call."""
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-def image(seed, w, h, c=3):
-    return np.random.default_rng(seed).integers(0, 256, size=(h, w, c), dtype=np.uint8)
+ctxs, back_to_defaults = context_fixtures(autouse=True)
 
 
 def as_fmt(img, fmt):
@@ -58,19 +38,8 @@ def as_fmt(img, fmt):
     return np.ascontiguousarray(x.transpose(2, 0, 1)).astype(NP[fmt])
 
 
-def filled(shape, fmt):
-    if fmt == U8:
-        return torch.full(shape, 0xCD, dtype=torch.uint8, device="cuda")
-    return torch.full(shape, float("nan"), dtype=TORCH[fmt], device="cuda")
-
-
 def out_buffer(fmt, w, h, c=3):
     return filled((4 * h, 4 * w, c) if fmt == U8 else (3, 4 * h, 4 * w), fmt)
-
-
-def untouched(t):
-    """Does every element of the tensor still hold its fill value?"""
-    return bool((t == 0xCD).all()) if t.dtype == torch.uint8 else bool(torch.isnan(t).all())
 
 
 def geometry(x, fmt):
@@ -79,13 +48,8 @@ def geometry(x, fmt):
 
 def single(s, x, in_fmt, out_fmt):
     """The reference: one synchronous rsr_process_device_fmt call on the packed numpy image x, as raw bytes."""
-    w, h, c = geometry(x, in_fmt)
-    d_in = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    d_out = out_buffer(out_fmt, w, h, c)
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, c, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    got = d_out.cpu().numpy()
-    assert not untouched(d_out)
+    got = run(s, x, in_fmt, out_fmt, nan=True)
+    assert not same_bits(got, sentinel(out_fmt, got.shape))
     return got.view(np.uint8)
 
 
@@ -267,11 +231,10 @@ def check_window(canvas, window, want, fmt):
 
 # plain context: the fused store, the per-pixel post kernel, the LDS-staged pre / post kernels (which must cope with, or decline, the
 # pitches); TTA context: the default (staged post kernel) and the staged pre kernel too
-ROUTES = [(False, 0), (False, 8192), (False, 8192 | 65536), (True, 0), (True, 65536)]
 
 
 @pytest.mark.parametrize("fmt", [U8, F16, F32], ids=["u8", "f16", "f32"])
-@pytest.mark.parametrize("tta,dbg", ROUTES, ids=["fused", "unfused", "unfused-staged", "tta", "tta-staged"])
+@pytest.mark.parametrize("tta,dbg", ROUTES, ids=ROUTE_IDS)
 def test_strided_crop_in_window_out(ctxs, tta, dbg, fmt):
     w, h, T = FOLDED
     s = ctxs[tta]
@@ -291,7 +254,7 @@ def test_strided_crop_in_window_out(ctxs, tta, dbg, fmt):
     check_window(canvas, window, want, fmt)
 
 
-@pytest.mark.parametrize("tta,dbg", ROUTES, ids=["fused", "unfused", "unfused-staged", "tta", "tta-staged"])
+@pytest.mark.parametrize("tta,dbg", ROUTES, ids=ROUTE_IDS)
 def test_uint8_row_pitch_of_3w_plus_1(ctxs, tta, dbg):
     """A uint8 row pitch that is no multiple of the pixel size, on both sides, three images in one batch: every pad byte stays."""
     w, h, T = FOLDED

@@ -12,7 +12,6 @@ evaluated exactly on the host and the elements where E lies within 2^-14 of an i
 < 256 move E by at most 2^-16); the test asserts that this leaves out at most 0.1 % of a frame.
 """
 import ctypes as C
-import os
 import threading
 
 import numpy as np
@@ -22,35 +21,18 @@ import torch
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import torch_io
 
-pytestmark = pytest.mark.gpu
-U8, F16, F32 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32}
+import gpu_support as G
+from gpu_support import context_fixtures, paths  # noqa: F401
+from pixfmt_ref import F16, F32, NP, U8, u8_image as image
 
+pytestmark = pytest.mark.gpu
 # (w, h, tilesize): smaller than a tile | partial last tiles in both directions at tile 32 | the same with a last tile column of 21 + 2 * 10
 # = 41 padded pixels: 9 behind a 32-column block at LR and 4 * 41 = 5 * 32 + 4 at 4x, i.e. folded last columns (kernels.h kFoldBit) |
 # tile 100 with partial last tiles both ways and a folded last column (121 = 100 + 21)
 GEOS = [(40, 30, 100), (61, 47, 32), (53, 47, 32), (121, 110, 100)]
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation); precise / bgr / dbg are options of a call."""
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-def image(seed, w, h, c=3):
-    return np.random.default_rng(seed).integers(0, 256, size=(h, w, c), dtype=np.uint8)
+ctxs, back_to_defaults = context_fixtures(autouse=True)
 
 
 def as_planar(img, fmt):
@@ -68,15 +50,7 @@ def out_buffer(fmt, w, h, c=3):
 
 def run(s, x, in_fmt, out_fmt, stream=None):
     """One synchronous rsr_process_device_fmt call on the numpy image x; returns the output as numpy."""
-    h, w = (x.shape[0], x.shape[1]) if in_fmt == U8 else (x.shape[1], x.shape[2])
-    c = x.shape[2] if in_fmt == U8 else 3
-    assert x.dtype == NP[in_fmt] and x.nbytes == R.image_bytes(in_fmt, w, h, c)
-    d_in = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    d_out = out_buffer(out_fmt, w, h, c)
-    assert d_out.numel() * d_out.element_size() == R.image_bytes(out_fmt, 4 * w, 4 * h, c)
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, c, d_out.data_ptr(), out_fmt, stream=stream)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy()
+    return G.run(s, x, in_fmt, out_fmt, nan=True, stream=stream)
 
 
 def quantise(v):
@@ -201,7 +175,7 @@ def test_sub_8_bit_input_really_arrives(ctxs):
     assert np.array_equal(quantise(snapped), run(s, np.ascontiguousarray(np.rint(x.astype(np.float32) * 255).astype(np.uint8).transpose(1, 2, 0)), U8, U8).transpose(2, 0, 1))
 
 
-def profile_of(s, x, in_fmt, out_fmt):
+def profile_and_run(s, x, in_fmt, out_fmt):
     s.get_profile(reset=True)
     out = run(s, x, in_fmt, out_fmt)
     return s.get_profile(reset=True), out
@@ -221,10 +195,10 @@ def test_fusion_is_kept_and_plans_are_shared(ctxs, precise, flow_flags):
     s.set_profiling(True)
     try:
         img = image(21, 61, 47)
-        p_u8, ref = profile_of(s, img, U8, U8)
+        p_u8, ref = profile_and_run(s, img, U8, U8)
         plans = s.get_stat("plans")
-        p_a, a = profile_of(s, img, U8, F16)
-        p_b, b = profile_of(s, as_planar(img, F16), F16, F32)
+        p_a, a = profile_and_run(s, img, U8, F16)
+        p_b, b = profile_and_run(s, as_planar(img, F16), F16, F32)
         assert s.get_stat("plans") == plans
         assert p_u8["conv_launches"] == R.NUM_CONVS and p_u8["post_ms"] == 0 and p_u8["post_bytes"] == 0
         for p in (p_a, p_b):
@@ -236,8 +210,8 @@ def test_fusion_is_kept_and_plans_are_shared(ctxs, precise, flow_flags):
         assert p_a["pre_bytes"] == p_u8["pre_bytes"] and p_b["pre_bytes"] == pytest.approx(p_u8["pre_bytes"] * (6 + 64) / (3 + 64))
         # the unfused route: one post launch, whose bytes follow the output format
         s.set_option("dbg", 8192)
-        q_u8, _ = profile_of(s, img, U8, U8)
-        q_f32, _ = profile_of(s, img, U8, F32)
+        q_u8, _ = profile_and_run(s, img, U8, U8)
+        q_f32, _ = profile_and_run(s, img, U8, F32)
         assert q_u8["post_ms"] > 0 and q_f32["post_ms"] > 0 and q_f32["conv_launches"] == q_u8["conv_launches"]
         assert q_f32["post_bytes"] == pytest.approx(q_u8["post_bytes"] * (6 + 12) / (6 + 3))  # per output pixel: the blob read + the image written
         assert s.get_stat("plans") == plans

@@ -17,85 +17,18 @@ import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import torch_io
 
 import tile_diff_ref as ref
+from gpu_support import DIFF_FORMATS, context_fixtures, dev, out_dims, paths, profile_of  # noqa: F401
+from pixfmt_ref import F16, F32, NP, NV12, NV16, P010, P210, P444, S420, S422, U8, YUV444P, YUV444P10, image_at, paste, same_bits, sentinel, shape_of
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12, P010 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW, R.RSR_FMT_NV12, R.RSR_FMT_P010
-NV16, P210, YUV444P, YUV444P10 = R.RSR_FMT_NV16, R.RSR_FMT_P210, R.RSR_FMT_YUV444P, R.RSR_FMT_YUV444P10
-S420, S422, P444 = (NV12, P010), (NV16, P210), (YUV444P, YUV444P10)  # surfaces (3h / 2, w) and (2h, w); planar (3, h, w) like the float formats
-NP = ref.NP
 W, H, T, P = 70, 50, 32, 10
 NT = 6
 CHECKER = [1, 0, 1, 0, 1, 0]
 MASKS = [[int(i == t) for i in range(NT)] for t in range(NT)] + [CHECKER, [1 - m for m in CHECKER]]
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    import os
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, P
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0),
-                   ("max_workspace_mb", 65536)):
-        s.set_option(key, v)
-    s.set_profiling(False)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation); everything else is an option of a call."""
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
-
-
-def shape_of(fmt, w, h, c=3):
-    return (h, w, c) if fmt == U8 else ((h * 3 // 2, w) if fmt in S420 else ((h * 2, w) if fmt in S422 else (3, h, w)))
-
-
-def image(seed, fmt, w=W, h=H, c=3):
-    rng = np.random.default_rng(seed)
-    if fmt == U8:
-        return rng.integers(0, 256, size=(h, w, c), dtype=np.uint8)
-    if fmt in (F16, F32):
-        return rng.uniform(0, 1, size=(3, h, w)).astype(NP[fmt])
-    codes = rng.integers(0, 256 if NP[fmt] == np.uint8 else 1024, size=shape_of(fmt, w, h))
-    return codes.astype(np.uint8) if NP[fmt] == np.uint8 else (codes << (0 if fmt in P444 else 6)).astype(np.uint16)  # (4:4:4: the code in the LOW bits)
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def sentinel(fmt, shape):
-    """A numpy image of the format, filled with 0xCD bytes (float formats: NaN)."""
-    if fmt in (F16, F32):
-        return np.full(shape, np.nan, dtype=NP[fmt])
-    return np.full(shape, 0xCDCD if fmt == P010 else 0xCD, dtype=NP[fmt])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def out_dims(s, w, h):
-    r = s.out_ratio
-    return w * r.numerator // r.denominator, h * r.numerator // r.denominator
+ctxs, ctx = context_fixtures(T, P)
+image = image_at(W, H)
 
 
 def call(s, x, in_fmt, out_fmt, mask, w=W, h=H, c=3, into=None):
@@ -111,19 +44,6 @@ def call(s, x, in_fmt, out_fmt, mask, w=W, h=H, c=3, into=None):
         s.process_device_masked(d_in.data_ptr(), in_fmt, w, h, c, d_out.data_ptr(), out_fmt, mask)
     torch.cuda.synchronize()
     return d_out.cpu().numpy().view(NP[out_fmt]).reshape(oshape)
-
-
-def paste(fmt, dst, src, rect):
-    """The output rectangle `rect` of src into dst (numpy images of format fmt)."""
-    x0, y0, x1, y1 = rect
-    if fmt == U8:
-        dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-    elif fmt in (F16, F32):
-        dst[:, y0:y1, x0:x1] = src[:, y0:y1, x0:x1]
-    else:
-        oh = dst.shape[0] * 2 // 3
-        dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-        dst[oh + y0 // 2:oh + y1 // 2, x0:x1] = src[oh + y0 // 2:oh + y1 // 2, x0:x1]
 
 
 def expected(s, fmt, plain, mask, w=W, h=H, base=None):
@@ -163,16 +83,6 @@ def test_masked_equals_plain_rectangle_by_rectangle(ctx, mode, fmtcase):
         half = call(s, x, in_fmt, out_fmt, CHECKER, c=c)
         full = call(s, x, in_fmt, out_fmt, [1 - m for m in CHECKER], c=c, into=half)
         assert same_bits(full, plain), scale
-
-
-def profile_of(s, fn):
-    s.set_profiling(True)
-    s.get_profile(reset=True)
-    try:
-        out = fn()
-        return out, s.get_profile(reset=True)
-    finally:
-        s.set_profiling(False)
 
 
 @pytest.mark.parametrize("tta", [False, True], ids=["plain", "tta"])
@@ -312,7 +222,6 @@ def poke(fmt, x, px, py, ch=0, chroma=None, h=H):
     return y
 
 
-DIFF_FORMATS = [("u8c3", U8, 3), ("u8c4", U8, 4), ("f16", F16, 3), ("f32", F32, 3), ("nv12", NV12, 3), ("p010", P010, 3)]
 # (id, fmt, c, w, h, tile): the families the feature came with on the base case; the later ones at 35 x 25 (4:4:4) and 36 x 26 (4:2:2) with
 # tile 16 -- a 3 x 2 grid again, the smallest with an interior tile, an edge tile, an odd chroma boundary and a clipped halo
 DIFF_CASES = [f + (W, H, T) for f in DIFF_FORMATS] + [("nv16", NV16, 3, 36, 26, 16), ("p210", P210, 3, 36, 26, 16), ("yuv444p", YUV444P, 3, 35, 25, 16),

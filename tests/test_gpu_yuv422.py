@@ -19,90 +19,24 @@ import torch
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import torch_io
 
+import tile_diff_ref as ref
 import yuv422_ref
 import yuv_ref
 import yuv_siting_ref
+from gpu_support import context_fixtures, dev, paths, run  # noqa: F401
+from pixfmt_ref import BITS, F16, F32, NP, NV12, NV16, P210, U8, image_at, lift, paste, place, same_bits
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12, P010, NV16, P210 = 0, 1, 2, 4, 5, 8, 9
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16, NV16: np.uint8, P210: np.uint16}
-BITS = {NV12: 8, P010: 10, NV16: 8, P210: 10}
 W, H, T, P = 36, 25, 16, 10
 CFGS = [(709, 0), (601, 1), (2020, 0), (709, 1), (601, 0), (2020, 1)]  # (yuv_matrix, yuv_range)
 SENTINEL = 0xCD
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    import os
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, P
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0)):
-        s.set_option(key, v)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
-
-
-def rows_of(fmt, h):
-    return 2 * h if fmt in (NV16, P210) else h * 3 // 2
-
-
-def surface(seed, fmt, w=W, h=H):
-    """Random codes over the whole code range -- most of them outside the RGB gamut, so the decoder's clamp acts."""
-    codes = np.random.default_rng(seed).integers(0, 1 << BITS[fmt], size=(rows_of(fmt, h), w))
-    return codes.astype(np.uint8) if BITS[fmt] == 8 else (codes << 6).astype(np.uint16)
-
-
-def rgb_image(seed, fmt, w=W, h=H):
-    rng = np.random.default_rng(seed)
-    if fmt == U8:
-        return rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
-    return rng.uniform(0, 1, size=(3, h, w)).astype(np.float16)
-
-
-def shape_of(fmt, w, h):
-    return (h, w, 3) if fmt == U8 else ((rows_of(fmt, h), w) if fmt in BITS else (3, h, w))
-
-
-def run(s, x, in_fmt, out_fmt, w=W, h=H):
-    """One synchronous rsr_process_device_fmt call on the numpy image x; the destination is pre-filled with the sentinel."""
-    ow, oh = s.out_size_fmt(out_fmt, w, h)
-    assert x.dtype == NP[in_fmt] and x.shape == shape_of(in_fmt, w, h) and x.nbytes == R.image_bytes(in_fmt, w, h)
-    d_in = torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).cuda()
-    d_out = torch.full((R.image_bytes(out_fmt, ow, oh),), SENTINEL, dtype=torch.uint8, device="cuda")
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, 3, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().view(NP[out_fmt]).reshape(shape_of(out_fmt, ow, oh))
+ctxs, ctx = context_fixtures(T, P)
+surface = rgb_image = image_at(W, H)
 
 
 def set_cfg(s, cfg):
     s.set_option("yuv_matrix", cfg[0])
     s.set_option("yuv_range", cfg[1])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def want422(d, fmt, cfg=(709, 0), siting=0, tile_w=0):
@@ -241,24 +175,6 @@ def test_end_to_end_and_cross_format(ctx, tta, precise, os_, siting):
 
 
 # ---- 4. batches, masks, sequences -------------------------------------------------------------------------------------------------
-def place(canvas, off, pitch, plane, surf):
-    """Write the 4:2:2 surface `surf` into the byte canvas: Y rows from `off`, `pitch` bytes apart, the UV rows `plane` bytes behind them.
-    Returns the mask of the bytes that belong to the surface."""
-    rows = surf.view(np.uint8).reshape(surf.shape[0], -1)
-    h = surf.shape[0] // 2
-    mask = np.zeros(canvas.shape, dtype=bool)
-    for r in range(rows.shape[0]):
-        o = off + r * pitch if r < h else off + plane + (r - h) * pitch
-        canvas[o:o + rows.shape[1]] = rows[r]
-        mask[o:o + rows.shape[1]] = True
-    return mask
-
-
-def lift(canvas, off, pitch, plane, fmt, w, h):
-    rows = [canvas[(off + r * pitch if r < h else off + plane + (r - h) * pitch):][:w * NP[fmt]().itemsize] for r in range(2 * h)]
-    return np.stack(rows).view(NP[fmt])
-
-
 @pytest.mark.parametrize("fmt", [NV16, P210], ids=["nv16", "p210"])
 @pytest.mark.parametrize("tta,os_", [(False, 4), (True, 2), (False, 1)], ids=["plain-x4", "tta-x2", "plain-x1"])
 def test_batch_of_three_pitched_windows(ctx, tta, os_, fmt):
@@ -278,7 +194,7 @@ def test_batch_of_three_pitched_windows(ctx, tta, os_, fmt):
     ins, outs, keep = [], [], []
     for x in surfs:
         canvas = np.full(ioff + ispan + 64, 0x5A, dtype=np.uint8)
-        place(canvas, ioff, ipitch, iplane, x)
+        place(canvas, ioff, ipitch, iplane, x, fmt)
         d_in = torch.from_numpy(canvas).cuda()
         d_out = torch.full((ooff + ospan + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
         keep.append((d_in, d_out))
@@ -291,31 +207,9 @@ def test_batch_of_three_pitched_windows(ctx, tta, os_, fmt):
     for (_, d_out), want in zip(keep, lone):
         got = d_out.cpu().numpy()
         assert same_bits(lift(got, ooff, opitch, oplane, fmt, W * os_, H * os_), want)
-        inside = place(np.zeros_like(got), ooff, opitch, oplane, want)
+        inside = place(np.zeros_like(got), ooff, opitch, oplane, want, fmt)
         assert (got[~inside] == SENTINEL).all()  # no byte outside the Y and UV windows is touched
         assert inside.sum() == want.nbytes
-
-
-def tile_grid(w, h, t):
-    return -(-w // t), -(-h // t)
-
-
-def out_rect(w, h, t, tile, rx=Fraction(4), ry=Fraction(4)):
-    nx, _ = tile_grid(w, h, t)
-    yi, xi = divmod(tile, nx)
-    return int(xi * t * rx), int(yi * t * ry), int(min((xi + 1) * t, w) * rx), int(min((yi + 1) * t, h) * ry)
-
-
-def paste422(dst, src, rect):
-    """The Y and the UV rectangle of one tile of a (2h, w) surface: the UV rectangle has the tile's own rows."""
-    x0, y0, x1, y1 = rect
-    oh = dst.shape[0] // 2
-    dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-    dst[oh + y0:oh + y1, x0:x1] = src[oh + y0:oh + y1, x0:x1]
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).cuda()
 
 
 @pytest.mark.parametrize("fmt,ratio", [(NV16, None), (P210, Fraction(3, 2))], ids=["nv16-x4", "p210-x3_2"])
@@ -337,7 +231,7 @@ def test_masked_tiles(ctx, fmt, ratio):
     torch.cuda.synchronize()
     want = np.full(full.shape, SENTINEL | (SENTINEL << 8) if BITS[fmt] == 10 else SENTINEL, dtype=NP[fmt])
     for t in np.flatnonzero(mask):
-        paste422(want, full, out_rect(w, h, T, t, r, r))
+        paste(fmt, want, full, ref.out_rect(w, h, T, t, r.numerator, r.denominator))
     got = d_out.cpu().numpy().view(NP[fmt]).reshape(full.shape)
     assert same_bits(got, want) and not same_bits(got, full)
 
@@ -361,39 +255,19 @@ def test_sequence_of_three_frames_with_prev_out(ctx, fmt):
     state = prev.copy()
     for k in range(3):
         for t in np.flatnonzero(masks[k]):
-            paste422(state, full[k], out_rect(W, H, T, t))
+            paste(fmt, state, full[k], ref.out_rect(W, H, T, t))
         got = d_outs[k].cpu().numpy().view(NP[fmt]).reshape(full[k].shape)
         assert same_bits(got, state), k
     assert same_bits(d_prev.cpu().numpy().view(NP[fmt]).reshape(prev.shape), prev)
 
 
 # ---- 5. the frame diff -------------------------------------------------------------------------------------------------------------
-def source_rect(w, h, t, p, tile):
-    nx, _ = tile_grid(w, h, t)
-    yi, xi = divmod(tile, nx)
-    return max(xi * t - p, 0), max(yi * t - p, 0), min(min((xi + 1) * t, w) + p, w), min(min((yi + 1) * t, h) + p, h)
-
-
-def diff_mask_ref(a, b, w, h, t, p):
-    """rsr_diff_tiles for a 4:2:2 surface, restated: the Y samples of the tile's source rectangle and the (U, V) pairs of chroma columns
-    max((sx0 >> 1) - 1, 0) .. min(((sx1 - 1) >> 1) + 1, w/2 - 1) on rows sy0 .. sy1 - 1, compared as bytes."""
-    nx, ny = tile_grid(w, h, t)
-    mask = np.zeros(nx * ny, dtype=np.uint8)
-    for tile in range(nx * ny):
-        x0, y0, x1, y1 = source_rect(w, h, t, p, tile)
-        c0, c1 = max((x0 >> 1) - 1, 0), min(((x1 - 1) >> 1) + 1, w // 2 - 1)
-        for sl in ((slice(y0, y1), slice(x0, x1)), (slice(h + y0, h + y1), slice(2 * c0, 2 * c1 + 2))):
-            if not np.array_equal(a[sl], b[sl]):
-                mask[tile] = 1
-    return mask
-
-
 def flips(w, h):
     """(row of the (2h, w) surface, column) of single samples to change: in Y, in U and in V, each at a corner of a source rectangle, one
     chroma column beyond the rectangle's own and one more (not compared by that tile), and one row below / above it."""
     out = []
     for tile in (0, 4):
-        x0, y0, x1, y1 = source_rect(w, h, T, P, tile)
+        x0, y0, x1, y1 = ref.source_rect(w, h, T, P, tile)
         c1 = min(((x1 - 1) >> 1) + 1, w // 2 - 1)
         out += [(y0, x0), (y1 - 1, x1 - 1)]
         if x1 < w:
@@ -421,7 +295,7 @@ def test_diff_tiles_and_sequence(ctx, fmt):
     for i, (r, c) in enumerate(pos):
         b = a.copy()
         b[r, c] ^= 1 if (BITS[fmt] == 8 or i % 2) else 0x40  # (P210: a bit below the code differs as well -- whole words are compared)
-        want = diff_mask_ref(a, b, W, H, T, P)
+        want = ref.diff_mask(fmt, a, b, T, P)
         d_mask = torch.full((nt,), SENTINEL, dtype=torch.uint8, device="cuda")
         s.diff_tiles(d_a.data_ptr(), dev(b).data_ptr(), fmt, W, H, 3, d_mask.data_ptr())
         torch.cuda.synchronize()
@@ -438,7 +312,7 @@ def test_diff_tiles_and_sequence(ctx, fmt):
         d_masks = torch.full((3 * nt,), SENTINEL, dtype=torch.uint8, device="cuda")
         s.diff_tiles_sequence([t.data_ptr() for t in d_f], d_a.data_ptr() if prev is not None else None, fmt, W, H, 3, d_masks.data_ptr())
         torch.cuda.synchronize()
-        want = np.stack([diff_mask_ref(p, q, W, H, T, P) for p, q in zip([a] + frames[:2], frames)])
+        want = np.stack([ref.diff_mask(fmt, p, q, T, P) for p, q in zip([a] + frames[:2], frames)])
         if prev is None:
             want[0] = 1
         assert np.array_equal(d_masks.cpu().numpy().reshape(3, nt), want)

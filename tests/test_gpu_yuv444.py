@@ -20,100 +20,27 @@ import torch
 import realsr_ncnn_vulkan_amd as R
 from realsr_ncnn_vulkan_amd import torch_io
 
+import tile_diff_ref as ref
 import yuv422_ref
 import yuv444_ref
 import yuv_ref
+from gpu_support import context_fixtures, dev, paths, run  # noqa: F401
+from pixfmt_ref import BITS, F16, F32, NP, NV12, NV16, U8, YUV444P, YUV444P10, image, image_at, lift, paste, place, same_bits
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12, P010, NV16, P210, Y444, Y444_10 = 0, 1, 2, 4, 5, 8, 9, 12, 13
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16, NV16: np.uint8, P210: np.uint16, Y444: np.uint8, Y444_10: np.uint16}
-BITS = {NV12: 8, P010: 10, NV16: 8, P210: 10, Y444: 8, Y444_10: 10}
-SEMI = (NV12, P010, NV16, P210)
+Y444, Y444_10 = YUV444P, YUV444P10
 W, H, T, P = 35, 25, 16, 10
 CFGS = [(709, 0), (601, 1), (2020, 0), (709, 1), (601, 0), (2020, 1)]  # (yuv_matrix, yuv_range)
 SENTINEL = 0xCD
 ONE_PIXEL, TWO_PIXELS = 32768, 65536  # option "dbg": the 4:4:4 post kernels make one pixel / two neighbouring pixels per thread everywhere
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    import os
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, P
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0), ("dbg", 0)):
-        s.set_option(key, v)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
-
-
-def shape_of(fmt, w, h):
-    if fmt == U8:
-        return (h, w, 3)
-    if fmt in SEMI:
-        return (2 * h if fmt in (NV16, P210) else h * 3 // 2, w)
-    return (3, h, w)
-
-
-def image444(seed, fmt, w=W, h=H):
-    """Random codes over the whole code range -- most of them outside the RGB gamut, so the decoder's clamp acts."""
-    return np.random.default_rng(seed).integers(0, 1 << BITS[fmt], size=(3, h, w)).astype(NP[fmt])
-
-
-def semi_surface(seed, fmt, w, h):
-    codes = np.random.default_rng(seed).integers(0, 1 << BITS[fmt], size=shape_of(fmt, w, h))
-    return codes.astype(np.uint8) if BITS[fmt] == 8 else (codes << 6).astype(np.uint16)
-
-
-def rgb_image(seed, fmt, w=W, h=H):
-    rng = np.random.default_rng(seed)
-    if fmt == U8:
-        return rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
-    return rng.uniform(0, 1, size=(3, h, w)).astype(np.float16)
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).cuda()
-
-
-def run(s, x, in_fmt, out_fmt, w=W, h=H):
-    """One synchronous rsr_process_device_fmt call on the numpy image x; the destination is pre-filled with the sentinel."""
-    ow, oh = s.out_size_fmt(out_fmt, w, h)
-    assert x.dtype == NP[in_fmt] and x.shape == shape_of(in_fmt, w, h) and x.nbytes == R.image_bytes(in_fmt, w, h)
-    d_in = dev(x)
-    d_out = torch.full((R.image_bytes(out_fmt, ow, oh),), SENTINEL, dtype=torch.uint8, device="cuda")
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, 3, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().view(NP[out_fmt]).reshape(shape_of(out_fmt, ow, oh))
+ctxs, ctx = context_fixtures(T, P)
+image444 = rgb_image = image_at(W, H)
+semi_surface = image
 
 
 def set_cfg(s, cfg):
     s.set_option("yuv_matrix", cfg[0])
     s.set_option("yuv_range", cfg[1])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def want444(d, fmt, cfg=(709, 0)):
@@ -258,24 +185,6 @@ def test_yuv_siting_means_nothing(ctx):
 
 
 # ---- 4. batches, masks, sequences -------------------------------------------------------------------------------------------------
-def place(canvas, off, pitch, plane, img):
-    """Write the (3, h, w) image into the byte canvas: plane q's rows from off + q * plane, `pitch` bytes apart.  Returns the mask of the
-    bytes that belong to the image."""
-    rows = img.view(np.uint8).reshape(3, img.shape[1], -1)
-    mask = np.zeros(canvas.shape, dtype=bool)
-    for q in range(3):
-        for r in range(rows.shape[1]):
-            o = off + q * plane + r * pitch
-            canvas[o:o + rows.shape[2]] = rows[q, r]
-            mask[o:o + rows.shape[2]] = True
-    return mask
-
-
-def lift(canvas, off, pitch, plane, fmt, w, h):
-    nb = w * NP[fmt]().itemsize
-    return np.stack([np.stack([canvas[off + q * plane + r * pitch:][:nb] for r in range(h)]) for q in range(3)]).view(NP[fmt])
-
-
 @pytest.mark.parametrize("fmt", [Y444, Y444_10], ids=["yuv444p", "yuv444p10"])
 @pytest.mark.parametrize("tta,os_", [(False, 4), (True, 2), (False, 1)], ids=["plain-x4", "tta-x2", "plain-x1"])
 def test_batch_of_three_pitched_windows(ctx, tta, os_, fmt):
@@ -295,7 +204,7 @@ def test_batch_of_three_pitched_windows(ctx, tta, os_, fmt):
     ins, outs, keep = [], [], []
     for x in imgs:
         canvas = np.full(ioff + ispan + 64, 0x5A, dtype=np.uint8)
-        place(canvas, ioff, ipitch, iplane, x)
+        place(canvas, ioff, ipitch, iplane, x, fmt)
         d_in = torch.from_numpy(canvas).cuda()
         d_out = torch.full((ooff + ospan + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
         keep.append((d_in, d_out))
@@ -312,25 +221,9 @@ def test_batch_of_three_pitched_windows(ctx, tta, os_, fmt):
         for (_, d_out), want in zip(keep, lone):
             got = d_out.cpu().numpy()
             assert same_bits(lift(got, ooff, opitch, oplane, fmt, W * os_, H * os_), want)
-            inside = place(np.zeros_like(got), ooff, opitch, oplane, want)
+            inside = place(np.zeros_like(got), ooff, opitch, oplane, want, fmt)
             assert (got[~inside] == SENTINEL).all()  # no byte outside the three windows is touched
             assert inside.sum() == want.nbytes
-
-
-def tile_grid(w, h, t):
-    return -(-w // t), -(-h // t)
-
-
-def out_rect(w, h, t, tile, rx=Fraction(4), ry=Fraction(4)):
-    nx, _ = tile_grid(w, h, t)
-    yi, xi = divmod(tile, nx)
-    return int(xi * t * rx), int(yi * t * ry), int(min((xi + 1) * t, w) * rx), int(min((yi + 1) * t, h) * ry)
-
-
-def paste444(dst, src, rect):
-    """The rectangle of one tile in each of the three planes."""
-    x0, y0, x1, y1 = rect
-    dst[:, y0:y1, x0:x1] = src[:, y0:y1, x0:x1]
 
 
 @pytest.mark.parametrize("fmt,ratio", [(Y444, None), (Y444_10, Fraction(3, 2))], ids=["yuv444p-x4", "yuv444p10-x3_2"])
@@ -351,7 +244,7 @@ def test_masked_tiles(ctx, fmt, ratio):
     torch.cuda.synchronize()
     want = np.full(full.shape, SENTINEL | (SENTINEL << 8) if BITS[fmt] == 10 else SENTINEL, dtype=NP[fmt])
     for t in np.flatnonzero(mask):
-        paste444(want, full, out_rect(w, h, T, t, r, r))
+        paste(fmt, want, full, ref.out_rect(w, h, T, t, r.numerator, r.denominator))
     got = d_out.cpu().numpy().view(NP[fmt]).reshape(full.shape)
     assert same_bits(got, want) and not same_bits(got, full)
 
@@ -375,37 +268,21 @@ def test_sequence_of_three_frames_with_prev_out(ctx, fmt):
     state = prev.copy()
     for k in range(3):
         for t in np.flatnonzero(masks[k]):
-            paste444(state, full[k], out_rect(W, H, T, t))
+            paste(fmt, state, full[k], ref.out_rect(W, H, T, t))
         got = d_outs[k].cpu().numpy().view(NP[fmt]).reshape(full[k].shape)
         assert same_bits(got, state), k
     assert same_bits(d_prev.cpu().numpy().view(NP[fmt]).reshape(prev.shape), prev)
 
 
 # ---- 5. the frame diff -------------------------------------------------------------------------------------------------------------
-def source_rect(w, h, t, p, tile):
-    nx, _ = tile_grid(w, h, t)
-    yi, xi = divmod(tile, nx)
-    return max(xi * t - p, 0), max(yi * t - p, 0), min(min((xi + 1) * t, w) + p, w), min(min((yi + 1) * t, h) + p, h)
-
-
-def diff_mask_ref(a, b, w, h, t, p):
-    """rsr_diff_tiles for a planar 4:4:4 image, restated: the three planes over the tile's source rectangle, nothing beyond it."""
-    nx, ny = tile_grid(w, h, t)
-    mask = np.zeros(nx * ny, dtype=np.uint8)
-    for tile in range(nx * ny):
-        x0, y0, x1, y1 = source_rect(w, h, t, p, tile)
-        mask[tile] = not np.array_equal(a[:, y0:y1, x0:x1], b[:, y0:y1, x0:x1])
-    return mask
-
-
 def pokes(w, h):
     """(plane, row, column) of single samples to change: in each plane, just inside and just outside the source rectangles of tiles 0 and 4."""
     out = []
     for q in range(3):
-        x0, y0, x1, y1 = source_rect(w, h, T, P, 0)   # (0, 0, 26, 25): the right edge is inside the image
+        x0, y0, x1, y1 = ref.source_rect(w, h, T, P, 0)   # (0, 0, 26, 25): the right edge is inside the image
         assert (x0, y0, x1, y1) == (0, 0, 26, 25)
         out += [(q, y1 - 1, x1 - 1), (q, y1 - 1, x1), (q, 0, 0)]
-        x0, y0, x1, y1 = source_rect(w, h, T, P, 4)   # (6, 6, 35, 25): the left and the upper edge are
+        x0, y0, x1, y1 = ref.source_rect(w, h, T, P, 4)   # (6, 6, 35, 25): the left and the upper edge are
         assert (x0, y0, x1, y1) == (6, 6, 35, 25)
         out += [(q, y0, x0), (q, y0 - 1, x0), (q, y0, x0 - 1), (q, y1 - 1, x1 - 1)]
     return out
@@ -422,7 +299,7 @@ def test_diff_tiles_and_sequence(ctx, fmt):
     for i, at in enumerate(pos):
         b = a.copy()
         b[at] ^= 1 if (BITS[fmt] == 8 or i % 2) else 0x800  # (YUV444P10: a bit above the code differs as well -- whole words are compared)
-        want = diff_mask_ref(a, b, W, H, T, P)
+        want = ref.diff_mask(fmt, a, b, T, P)
         d_mask = torch.full((nt,), SENTINEL, dtype=torch.uint8, device="cuda")
         s.diff_tiles(d_a.data_ptr(), dev(b).data_ptr(), fmt, W, H, 3, d_mask.data_ptr())
         torch.cuda.synchronize()
@@ -435,12 +312,12 @@ def test_diff_tiles_and_sequence(ctx, fmt):
     es = NP[fmt]().itemsize
     pitch, plane = (W + 7) * es, (H + 2) * (W + 7) * es + 10
     ca, cb = (np.full(R.image_span(fmt, W, H, 3, pitch, plane) + 8, 0x11 * (k + 1), dtype=np.uint8) for k in range(2))
-    place(ca, 2 * es, pitch, plane, a), place(cb, 4 * es, pitch, plane, b)
+    place(ca, 2 * es, pitch, plane, a, fmt), place(cb, 4 * es, pitch, plane, b, fmt)
     da, db = torch.from_numpy(ca).cuda(), torch.from_numpy(cb).cuda()
     d_mask = torch.full((nt,), SENTINEL, dtype=torch.uint8, device="cuda")
     s.diff_tiles((da.data_ptr() + 2 * es, pitch, plane), (db.data_ptr() + 4 * es, pitch, plane), fmt, W, H, 3, d_mask.data_ptr())
     torch.cuda.synchronize()
-    assert np.array_equal(d_mask.cpu().numpy(), diff_mask_ref(a, b, W, H, T, P))
+    assert np.array_equal(d_mask.cpu().numpy(), ref.diff_mask(fmt, a, b, T, P))
     # the sequence form: row k is the diff of the pair (frame k - 1, frame k), row 0 against prev; without a prev every tile of row 0 is set
     frames = [a.copy() for _ in range(3)]
     frames[1][pos[1]] ^= 1
@@ -451,7 +328,7 @@ def test_diff_tiles_and_sequence(ctx, fmt):
         d_masks = torch.full((3 * nt,), SENTINEL, dtype=torch.uint8, device="cuda")
         s.diff_tiles_sequence([t.data_ptr() for t in d_f], d_a.data_ptr() if prev is not None else None, fmt, W, H, 3, d_masks.data_ptr())
         torch.cuda.synchronize()
-        want = np.stack([diff_mask_ref(p, q, W, H, T, P) for p, q in zip([a] + frames[:2], frames)])
+        want = np.stack([ref.diff_mask(fmt, p, q, T, P) for p, q in zip([a] + frames[:2], frames)])
         if prev is None:
             want[0] = 1
         assert np.array_equal(d_masks.cpu().numpy().reshape(3, nt), want)

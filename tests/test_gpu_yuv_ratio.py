@@ -7,7 +7,6 @@ ratio in force: the surface a call writes equals
 
 bit for bit -- the F32 output itself is pinned to area_reduce of the x4 image by tests/test_gpu_out_ratio.py.  Every image is a 2 x 2 tile
 grid whose last tiles are partial, so tile-first columns and rows and short tiles are all hit.  Outputs are pre-filled with 0xCD."""
-import os
 from fractions import Fraction
 
 import numpy as np
@@ -21,11 +20,10 @@ import sequence_ref
 import tile_diff_ref
 import yuv_ref
 import yuv_siting_ref as ref
+from gpu_support import context_fixtures, dev, paths, profile_of, run  # noqa: F401
+from pixfmt_ref import BITS, F16, F32, NP, NV12, P010, U8, image_at, lift, paste, pattern, place, same_bits
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12, P010 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW, R.RSR_FMT_NV12, R.RSR_FMT_P010
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16}
-BITS = {NV12: 8, P010: 10}
 CFGS = [(709, 0), (601, 1), (2020, 0), (709, 1), (601, 0), (2020, 1)]  # (yuv_matrix, yuv_range)
 SENTINEL = 0xCD
 # (n, d, tilesize, w, h): w n / d, h n / d and tilesize n / d are even; 2 x 2 tiles, the last ones partial
@@ -35,82 +33,13 @@ OW, OH = 90, 66
 NT = 4
 
 
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, 10
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0)):
-        s.set_option(key, v)
-    s.set_profiling(False)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation); everything else is an option of a call."""
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
-
-
-def surface(seed, fmt, w=W, h=H):
-    """Random codes over the whole code range -- most of them outside the RGB gamut, so the decoder's clamp acts."""
-    codes = np.random.default_rng(seed).integers(0, 1 << BITS[fmt], size=(h * 3 // 2, w))
-    return codes.astype(np.uint8) if fmt == NV12 else (codes << 6).astype(np.uint16)
-
-
-def rgb_image(seed, fmt, w=W, h=H):
-    rng = np.random.default_rng(seed)
-    if fmt == U8:
-        return rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
-    return rng.uniform(0, 1, size=(3, h, w)).astype(NP[fmt])
-
-
-def shape_of(fmt, w, h):
-    return (h, w, 3) if fmt == U8 else ((h * 3 // 2, w) if fmt in BITS else (3, h, w))
-
-
-def out_dims(s, out_fmt, w, h):
-    return s.out_size_yuv(w, h) if out_fmt in BITS else s.out_size(w, h)
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def run(s, x, in_fmt, out_fmt, w=W, h=H):
-    """One synchronous rsr_process_device_fmt call on the numpy image x at the context's ratio; the destination is pre-filled."""
-    ow, oh = out_dims(s, out_fmt, w, h)
-    assert x.dtype == NP[in_fmt] and x.shape == shape_of(in_fmt, w, h)
-    d_in = dev(x)
-    d_out = torch.full((R.image_bytes(out_fmt, ow, oh),), SENTINEL, dtype=torch.uint8, device="cuda")
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, 3, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().view(NP[out_fmt]).reshape(shape_of(out_fmt, ow, oh))
+ctxs, ctx = context_fixtures(T, 10)
+surface = rgb_image = image_at(W, H)
 
 
 def set_cfg(s, cfg):
     s.set_option("yuv_matrix", cfg[0])
     s.set_option("yuv_range", cfg[1])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
 def encoded(d, siting, tile_out, cfg, fmt):
@@ -202,24 +131,6 @@ def test_batch_of_five_equals_lone_calls(ctx, tta):
 
 
 # ---- 4. pitched surfaces, a window inside a larger canvas ------------------------------------------------------------------------------
-def place(canvas, off, pitch, plane, surf):
-    """Write the surface `surf` into the byte canvas: Y rows from `off`, `pitch` bytes apart, the UV rows `plane` bytes behind them.
-    Returns the mask of the bytes that belong to the surface."""
-    rows = surf.view(np.uint8).reshape(surf.shape[0], -1)
-    h = surf.shape[0] * 2 // 3
-    mask = np.zeros(canvas.shape, dtype=bool)
-    for r in range(rows.shape[0]):
-        o = off + r * pitch if r < h else off + plane + (r - h) * pitch
-        canvas[o:o + rows.shape[1]] = rows[r]
-        mask[o:o + rows.shape[1]] = True
-    return mask
-
-
-def lift(canvas, off, pitch, plane, fmt, w, h):
-    rows = [canvas[(off + r * pitch if r < h else off + plane + (r - h) * pitch):][:w * NP[fmt]().itemsize] for r in range(h * 3 // 2)]
-    return np.stack(rows).view(NP[fmt])
-
-
 @pytest.mark.parametrize("fmt", [NV12, P010], ids=["nv12", "p010"])
 def test_pitched_surfaces_into_windows(ctx, fmt):
     """Two top-left-sited surfaces in ONE batch call, each inside a larger allocation (row pitch > w, the UV plane farther than h * pitch
@@ -236,7 +147,7 @@ def test_pitched_surfaces_into_windows(ctx, fmt):
     ins, outs, keep = [], [], []
     for x in surfs:
         canvas = np.full(ioff + ispan + 64, 0x5A, dtype=np.uint8)
-        place(canvas, ioff, ipitch, iplane, x)
+        place(canvas, ioff, ipitch, iplane, x, fmt)
         d_in = torch.from_numpy(canvas).cuda()
         d_out = torch.full((ooff + ospan + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
         keep.append((d_in, d_out))
@@ -247,7 +158,7 @@ def test_pitched_surfaces_into_windows(ctx, fmt):
     for (_, d_out), want in zip(keep, lone):
         got = d_out.cpu().numpy()
         assert same_bits(lift(got, ooff, opitch, oplane, fmt, OW, OH), want)
-        inside = place(np.zeros_like(got), ooff, opitch, oplane, want)
+        inside = place(np.zeros_like(got), ooff, opitch, oplane, want, fmt)
         assert (got[~inside] == SENTINEL).all()  # no byte outside the Y and UV windows is touched
         assert inside.sum() == want.nbytes
 
@@ -275,22 +186,6 @@ def test_upscale_yuv_of_a_crop_into_a_window_of_a_canvas(ctx):
 
 
 # ---- 5. masked and sequence calls -------------------------------------------------------------------------------------------------------
-def pattern(fmt, shape):
-    """A previous output that is recognisably NOT a network output: P010 words with the low six bits set, a byte ramp of period 251."""
-    i = np.arange(int(np.prod(shape)), dtype=np.int64).reshape(shape)
-    if fmt == P010:
-        return (((i % 1021) << 6) | 0x2B).astype(np.uint16)
-    return (i % 251).astype(np.uint8)
-
-
-def paste(dst, src, rect):
-    """The output rectangle `rect` of the surface src into dst: its Y rows and its UV rows."""
-    x0, y0, x1, y1 = rect
-    oh = dst.shape[0] * 2 // 3
-    dst[y0:y1, x0:x1] = src[y0:y1, x0:x1]
-    dst[oh + y0 // 2:oh + y1 // 2, x0:x1] = src[oh + y0 // 2:oh + y1 // 2, x0:x1]
-
-
 @pytest.mark.parametrize("fmt,siting", [(NV12, 0), (NV12, 2), (P010, 1)], ids=["nv12-s0", "nv12-s2", "p010-s1"])
 def test_masked_call_writes_the_plain_bytes_of_its_tiles_only(ctx, fmt, siting):
     s = ctx[False]
@@ -310,7 +205,7 @@ def test_masked_call_writes_the_plain_bytes_of_its_tiles_only(ctx, fmt, siting):
         want = before.copy()
         for t in range(NT):
             if mask[t]:
-                paste(want, plain, rects[t])
+                paste(fmt, want, plain, rects[t])
         assert same_bits(d_out.cpu().numpy().view(NP[fmt]).reshape(plain.shape), want), mask
 
 
@@ -337,7 +232,7 @@ def test_sequence_call_computes_and_propagates_reduced_rectangles(ctx, tta):
         for k in range(n):
             want = np.full(plains[0].shape, SENTINEL, dtype=np.uint8)
             for t in range(NT):
-                paste(want, pv if src[k, t] < 0 else plains[src[k, t]], rects[t])  # a propagated rectangle is identical to its source
+                paste(NV12, want, pv if src[k, t] < 0 else plains[src[k, t]], rects[t])  # a propagated rectangle is identical to its source
             assert same_bits(d_outs[k].cpu().numpy().reshape(plains[0].shape), want), (masks, k)
         if d_prev is not None:
             assert same_bits(d_prev.cpu().numpy().reshape(prev.shape), prev)
@@ -438,18 +333,6 @@ def test_errors_leave_the_output_untouched_and_launch_nothing(ctx):
 
 
 # ---- 7. the integer ratios and the default path are untouched --------------------------------------------------------------------------
-def profiled(s, fn):
-    s.set_option("merge", 1)
-    s.set_profiling(True)
-    try:
-        s.get_profile(reset=True)
-        out = fn()
-        return out, s.get_profile(reset=True)
-    finally:
-        s.set_profiling(False)
-        s.set_option("merge", 16)
-
-
 COUNTS = ("conv_launches", "post_bytes", "pre_bytes", "tiles", "calls", "conv_flops")
 
 
@@ -460,12 +343,12 @@ def test_ratios_4_2_1_are_out_scale_4_2_1(ctx, tta):
     x = surface(9950, NV12)
     for k in (4, 2, 1):
         s.out_scale = k
-        want, p0 = profiled(s, lambda: run(s, x, NV12, NV12))
+        want, p0 = profile_of(s, lambda: run(s, x, NV12, NV12), merge=1)
         s.out_ratio = Fraction(3, 2)  # (leave it, and come back through rsr_set_out_ratio)
         assert s.out_scale == 0
         s.out_ratio = (2 * k, 2)
         assert s.out_scale == k and s.out_size_yuv(W, H) == (W * k, H * k)
-        got, p1 = profiled(s, lambda: run(s, x, NV12, NV12))
+        got, p1 = profile_of(s, lambda: run(s, x, NV12, NV12), merge=1)
         assert same_bits(got, want) and got.shape == (H * k * 3 // 2, W * k)
         for key in COUNTS:
             assert p1[key] == p0[key], (k, key)
@@ -479,7 +362,7 @@ def test_default_path_guard(ctx, paths):
 
     def u8_call(s):
         s.tilesize, s.prepadding = T, 10
-        return profiled(s, lambda: run(s, img, U8, U8))
+        return profile_of(s, lambda: run(s, img, U8, U8), merge=1)
 
     fresh = R.RealSR(0)
     try:
@@ -502,8 +385,8 @@ def test_default_path_guard(ctx, paths):
     for key in COUNTS + ("post_ms",):
         assert p1[key] == p0[key], key
     # a YUV output at 3/2 is the same conv launches and ONE post-processing launch, which writes fewer bytes than the x4 surface's
-    _, p4 = profiled(s, lambda: run(s, img, U8, NV12))
+    _, p4 = profile_of(s, lambda: run(s, img, U8, NV12), merge=1)
     s.out_ratio = Fraction(3, 2)
-    _, p2 = profiled(s, lambda: run(s, img, U8, NV12))
+    _, p2 = profile_of(s, lambda: run(s, img, U8, NV12), merge=1)
     assert p2["conv_launches"] == R.NUM_CONVS and p2["post_ms"] > 0 and p2["calls"] == 1
     assert 0 < p2["post_bytes"] < p4["post_bytes"]

@@ -20,85 +20,25 @@ import realsr_ncnn_vulkan_amd as R
 
 import yuv_ref
 import yuv_siting_ref as ref
+from gpu_support import context_fixtures, paths, run as run_sized  # noqa: F401
+from pixfmt_ref import BITS, F16, F32, NP, NV12, P010, U8, image_at, lift, place, same_bits
 
 pytestmark = pytest.mark.gpu
-U8, F16, F32, NV12, P010 = R.RSR_FMT_U8_HWC, R.RSR_FMT_F16_CHW, R.RSR_FMT_F32_CHW, R.RSR_FMT_NV12, R.RSR_FMT_P010
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16}
-BITS = {NV12: 8, P010: 10}
 W, H, T = 36, 26, 16
 CFGS = [(709, 0), (601, 1), (2020, 0), (709, 1), (601, 0), (2020, 1)]  # (yuv_matrix, yuv_range)
 SENTINEL = 0xCD
-
-
-@pytest.fixture(scope="module")
-def paths(model_dir):
-    import os
-    return os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin")
-
-
-def reset(s):
-    s.tilesize, s.prepadding = T, 10
-    for key, v in (("precise", 0), ("out_scale", 4), ("yuv_matrix", 709), ("yuv_range", 0), ("yuv_siting", 0), ("merge", 16), ("bgr", 0)):
-        s.set_option(key, v)
-
-
-@pytest.fixture(scope="module")
-def ctxs(paths):
-    """One context per TTA setting (it is fixed at creation); everything else is an option of a call."""
-    made = {}
-    for tta in (False, True):
-        made[tta] = R.RealSR(0, tta_mode=tta)
-        made[tta].load(*paths)
-    yield made
-    for s in made.values():
-        s.close()
-
-
-@pytest.fixture
-def ctx(ctxs):
-    for s in ctxs.values():
-        reset(s)
-    yield ctxs
-    for s in ctxs.values():
-        reset(s)
-        assert s.yuv_siting == 0
-
-
-def surface(seed, fmt, w=W, h=H):
-    """Random codes over the whole code range -- most of them outside the RGB gamut, so the decoder's clamp acts."""
-    codes = np.random.default_rng(seed).integers(0, 1 << BITS[fmt], size=(h * 3 // 2, w))
-    return codes.astype(np.uint8) if fmt == NV12 else (codes << 6).astype(np.uint16)
-
-
-def rgb_image(seed, fmt, w=W, h=H):
-    rng = np.random.default_rng(seed)
-    if fmt == U8:
-        return rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
-    return rng.uniform(0, 1, size=(3, h, w)).astype(np.float16)
-
-
-def shape_of(fmt, w, h):
-    return (h, w, 3) if fmt == U8 else ((h * 3 // 2, w) if fmt in BITS else (3, h, w))
+ctxs, ctx = context_fixtures(T, 10)
+surface = rgb_image = image_at(W, H)
 
 
 def run(s, x, in_fmt, out_fmt, w=W, h=H):
-    """One synchronous rsr_process_device_fmt call on the numpy image x; the destination is pre-filled with a sentinel."""
-    os_ = s.out_scale
-    assert x.dtype == NP[in_fmt] and x.shape == shape_of(in_fmt, w, h) and x.nbytes == R.image_bytes(in_fmt, w, h)
-    d_in = torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).cuda()
-    d_out = torch.full((R.image_bytes(out_fmt, w * os_, h * os_),), SENTINEL, dtype=torch.uint8, device="cuda")
-    s.process_device_fmt(d_in.data_ptr(), in_fmt, w, h, 3, d_out.data_ptr(), out_fmt)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().view(NP[out_fmt]).reshape(shape_of(out_fmt, w * os_, h * os_))
+    """One synchronous rsr_process_device_fmt call on the numpy image x into w x h times out_scale."""
+    return run_sized(s, x, in_fmt, out_fmt, w, h, out_size=(w * s.out_scale, h * s.out_scale))
 
 
 def set_cfg(s, cfg):
     s.set_option("yuv_matrix", cfg[0])
     s.set_option("yuv_range", cfg[1])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def encoded(d, siting, tile_out, cfg, fmt):
@@ -228,24 +168,6 @@ def test_end_to_end_is_the_composition(ctx, siting, fmt, tta, os_):
 
 
 # ---- 6. batches, pitches, windows --------------------------------------------------------------------------------------------------
-def place(canvas, off, pitch, plane, surf):
-    """Write the surface `surf` into the byte canvas: Y rows from `off`, `pitch` bytes apart, the UV rows `plane` bytes behind them.
-    Returns the mask of the bytes that belong to the surface."""
-    rows = surf.view(np.uint8).reshape(surf.shape[0], -1)
-    h = surf.shape[0] * 2 // 3
-    mask = np.zeros(canvas.shape, dtype=bool)
-    for r in range(rows.shape[0]):
-        o = off + r * pitch if r < h else off + plane + (r - h) * pitch
-        canvas[o:o + rows.shape[1]] = rows[r]
-        mask[o:o + rows.shape[1]] = True
-    return mask
-
-
-def lift(canvas, off, pitch, plane, fmt, w, h):
-    rows = [canvas[(off + r * pitch if r < h else off + plane + (r - h) * pitch):][:w * NP[fmt]().itemsize] for r in range(h * 3 // 2)]
-    return np.stack(rows).view(NP[fmt])
-
-
 @pytest.mark.parametrize("fmt", [NV12, P010], ids=["nv12", "p010"])
 def test_batch_of_three_pitched_windows(ctx, fmt):
     """Three left-sited surfaces in ONE rsr_process_device_batch call, each inside a larger allocation (row pitch > w, UV plane farther
@@ -266,7 +188,7 @@ def test_batch_of_three_pitched_windows(ctx, fmt):
     ins, outs, keep = [], [], []
     for x in surfs:
         canvas = np.full(ioff + ispan + 64, 0x5A, dtype=np.uint8)
-        place(canvas, ioff, ipitch, iplane, x)
+        place(canvas, ioff, ipitch, iplane, x, fmt)
         d_in = torch.from_numpy(canvas).cuda()
         d_out = torch.full((ooff + ospan + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
         keep.append((d_in, d_out))
@@ -279,7 +201,7 @@ def test_batch_of_three_pitched_windows(ctx, fmt):
     for (_, d_out), want in zip(keep, lone):
         got = d_out.cpu().numpy()
         assert same_bits(lift(got, ooff, opitch, oplane, fmt, W * os_, H * os_), want)
-        inside = place(np.zeros_like(got), ooff, opitch, oplane, want)
+        inside = place(np.zeros_like(got), ooff, opitch, oplane, want, fmt)
         assert (got[~inside] == SENTINEL).all()  # no byte outside the Y and UV windows is touched
         assert inside.sum() == want.nbytes
 

@@ -15,8 +15,8 @@ from realsr_ncnn_vulkan_amd import torch_io
 import yuv422_ref
 import yuv_ref
 import yuv_siting_ref
+from pixfmt_ref import F16, F32, NV12, NV16, P010, P210, U8
 
-U8, F16, F32, NV12, P010, NV16, P210 = 0, 1, 2, 4, 5, 8, 9
 F = np.float32
 # the 67 ratios of one axis (rsr_set_out_ratio_xy): n / d in lowest terms, d in 1..8, 1 <= n / d <= 4
 RATIOS = sorted({Fraction(n, d) for d in range(1, 9) for n in range(d, 4 * d + 1) if Fraction(n, d).denominator == d})

@@ -3,9 +3,7 @@ grid, a tile's source rectangle, and, for every pixel format, the mask of tiles 
 loops over tiles; nothing here shares code with the library."""
 import numpy as np
 
-U8, F16, F32, NV12, P010 = 0, 1, 2, 4, 5
-NV16, P210, YUV444P, YUV444P10 = 8, 9, 12, 13
-NP = {U8: np.uint8, F16: np.float16, F32: np.float32, NV12: np.uint8, P010: np.uint16, NV16: np.uint8, P210: np.uint16, YUV444P: np.uint8, YUV444P10: np.uint16}
+from pixfmt_ref import F16, F32, NP, NV12, NV16, P010, P210, U8, YUV444P, YUV444P10, dims_of  # noqa: F401  (the formats: tests/pixfmt_ref.py)
 
 
 def tile_count(w, h, T):
@@ -59,14 +57,7 @@ def compared(fmt, w, h, T, P, tile, a, b):
 def diff_mask(fmt, a, b, T, P):
     """mask[t] = 1 where any compared BYTE of tile t differs between a and b, else 0 (uint8, nx * ny)."""
     assert a.shape == b.shape and a.dtype == b.dtype == NP[fmt]
-    if fmt == U8:
-        h, w = a.shape[:2]
-    elif fmt in (F16, F32, YUV444P, YUV444P10):
-        h, w = a.shape[1:]
-    elif fmt in (NV16, P210):
-        h, w = a.shape[0] // 2, a.shape[1]
-    else:
-        h, w = a.shape[0] * 2 // 3, a.shape[1]
+    w, h = dims_of(fmt, a)
     nx, ny = tile_count(w, h, T)
     mask = np.zeros(nx * ny, dtype=np.uint8)
     for t in range(nx * ny):
@@ -76,8 +67,10 @@ def diff_mask(fmt, a, b, T, P):
     return mask
 
 
-def out_rect(w, h, T, tile, num=4, den=1):
-    """(x0, y0, x1, y1) of the tile's output rectangle at output ratio num / den."""
+def out_rect(w, h, T, tile, num=4, den=1, num_y=None, den_y=None):
+    """(x0, y0, x1, y1) of the tile's output rectangle at output ratio num / den -- along y at num_y / den_y where given."""
+    if num_y is None:
+        num_y, den_y = num, den
     nx, _ = tile_count(w, h, T)
     yi, xi = divmod(tile, nx)
-    return (xi * T * num // den, yi * T * num // den, min((xi + 1) * T, w) * num // den, min((yi + 1) * T, h) * num // den)
+    return (xi * T * num // den, yi * T * num_y // den_y, min((xi + 1) * T, w) * num // den, min((yi + 1) * T, h) * num_y // den_y)
