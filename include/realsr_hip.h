@@ -180,7 +180,7 @@ int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, in
  *            skip the margin nothing reads), and computing it would widen the hot convolution launches.  The price: one chroma column (row)
  *            per tile edge -- every tilesize * out_scale output pixels, 800 at the defaults -- is filtered [0 3 1] / 4 instead of [1 2 1] / 4.
  * On the output side conv_last leaves its planar blob and one more small launch (postproc_tiles_yuv) writes the surface: the route RGBA, TTA
- * and "out_scale" below 4 take anyway.  Out of scope: host pointers (rsr_process*) and the CLI, which stay uint8 RGB(A). */
+ * and "out_scale" below 4 take anyway.  Out of scope: host pointers of rsr_process* and the CLI, which stay uint8 RGB(A) (YUV frames in host memory: "A video session" below). */
 
 /* Host-only: the fp32 constants of the definition above for yuv_matrix `matrix`, yuv_range `range` and `bits` = 8 / 10, the first n of
  * { yoff, ys, coff, cs, 2(1-Kr), 2Kb(1-Kb)/Kg, 2Kr(1-Kr)/Kg, 2(1-Kb), Kr, Kg, Kb, yscale, yoff + 0.5, cscale, coff + 0.5, 1/(2(1-Kb)),
@@ -220,9 +220,10 @@ int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
  *   Sequences.  The propagated UV rectangle of a tile has the tile's own rows.
  * One more small launch behind conv_last writes the surface, as for NV12 / P010: postproc_tiles_yuv / postproc_tiles_yuv_area with two stacked
  * 2 x 1 pairs per thread.  rsr_out_size_yuv and rsr_out_size_yuv_xy keep their exact 4:2:0 behaviour.
- * Out of scope: three-plane SUBSAMPLED layouts (yuv422p: interleave the two chroma planes first; "YUV 4:4:4" below says why rsr_image cannot
+ * Out of scope: three-plane SUBSAMPLED layouts as a format of their own (yuv422p: rsr_pack_planes interleaves the two chroma planes into an
+ * NV16 / P210 surface and rsr_unpack_planes takes one apart, "Three-plane YUV frames" below; "YUV 4:4:4" below says why rsr_image cannot
  * describe them -- planar 4:4:4 itself is RSR_FMT_YUV444P / YUV444P10), 4:1:1, a siting per side, host pointers
- * (rsr_process*), groups of GPUs and the CLI, which stay uint8 RGB(A). */
+ * of rsr_process*, groups of GPUs and the CLI, which stay uint8 RGB(A) (YUV frames in host memory: "A video session" below). */
 
 /* Host-only (no GPU): the admission rule and the size of an output in `out_fmt` at the pair of ratios and the tile size given -- *ow = w *
  * nx / dx, *oh = h * ny / dy (either pointer may be NULL).  RSR_FMT_U8_HWC / F16_CHW / F32_CHW: exactly rsr_out_size_xy.  RSR_FMT_NV12 /
@@ -264,11 +265,13 @@ int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, in
  *   Sequences.  The propagated rectangle is the tile's output rectangle in each of the three planes.
  * One more small launch behind conv_last writes the surface, as for every YUV output: postproc_tiles_yuv444 / postproc_tiles_yuv444_area, one
  * output pixel per thread and three plane stores.
- * Out of scope: the three-plane SUBSAMPLED layouts (yuv420p, yuv422p and their 10-bit forms) -- rsr_image cannot express them: its one
- * plane_pitch is the distance Y -> U AND U -> V.  Their chroma planes are smaller than the luma plane, so the two distances differ, and a
- * window of such a canvas needs a U -> V distance (and a chroma row pitch) of its own, for which the descriptor has no field -- interleave the
- * chroma planes to NV12 / NV16 first; semi-planar or packed 4:4:4 (NV24, P410, Y410, AYUV); 12- and 16-bit codes (rsr_yuv_constants keeps refusing them);
- * 4:1:1; planar RGB (GBRP); a siting per side; host pointers (rsr_process*), groups of GPUs and the CLI, which stay uint8 RGB(A). */
+ * Out of scope: the three-plane SUBSAMPLED layouts (yuv420p, yuv422p and their 10-bit forms) as a pixel format -- rsr_image cannot express
+ * them: its one plane_pitch is the distance Y -> U AND U -> V.  Their chroma planes are smaller than the luma plane, so the two distances
+ * differ, and a window of such a canvas needs a U -> V distance (and a chroma row pitch) of its own, for which the descriptor has no field --
+ * rsr_pack_planes ("Three-plane YUV frames" below) interleaves the chroma planes to NV12 / NV16 on the device, shift of the 10-bit words
+ * included, and rsr_unpack_planes is the way back; semi-planar or packed 4:4:4 (NV24, P410, Y410, AYUV); 12- and 16-bit codes (rsr_yuv_constants keeps refusing them);
+ * 4:1:1; planar RGB (GBRP); a siting per side; host pointers of rsr_process*, groups of GPUs and the CLI, which stay uint8 RGB(A) (YUV
+ * frames in host memory: "A video session" below). */
 
 /* ---- rational output scales: x3, x3/2, x4/3, x9/4 ... area-averaged on the device (no reference counterpart) --------------------------
  * Option "out_scale" (rsr_set_option) takes the x4 image down to x2 or x1 inside the library.  rsr_set_out_ratio generalises it to the
@@ -530,6 +533,89 @@ int rsr_diff_tiles_sequence(rsr_ctx* ctx, int n, const rsr_image* frames, const 
  * Out of scope: host-pointer images, groups of GPUs, the CLI, merging with concurrent calls, frames of different geometry in one call. */
 int rsr_process_device_sequence(rsr_ctx* ctx, int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt,
                                 const rsr_image* prev_out /* may be NULL */, const uint8_t* masks /* HOST, nmask bytes */, int nmask, void* stream);
+
+/* ---- Three-plane YUV frames: yuv420p / yuv422p / yuv444p and their 10-bit forms to surfaces and back (no reference counterpart) ------------
+ * Every software decoder -- ffmpeg's default pix_fmt, VapourSynth, libavfilter, YUV4MPEG2 -- emits three planes Y, U, V, each with rows of
+ * its own; the chroma planes of the subsampled layouts are smaller than the luma plane, which no rsr_image describes ("YUV 4:4:4" above).
+ * No new pixel format is made of them: rsr_pack_planes writes the SURFACE of format `fmt` the engine takes from the three planes of a frame,
+ * rsr_unpack_planes the three planes from a surface; two memory-bound launches around the calls that exist.  `fmt` fixes the chroma plane's
+ * size and the sample width:
+ *            RSR_FMT_NV12 / P010            chroma (w/2) x (h/2), samples of 8 / 16 bits   (yuv420p / yuv420p10le)
+ *            RSR_FMT_NV16 / P210            chroma (w/2) x h                               (yuv422p / yuv422p10le)
+ *            RSR_FMT_YUV444P / YUV444P10    chroma w x h                                   (yuv444p / yuv444p10le)
+ *   The definition, exact.  Y row r of the surface is Y row r of the planes; a subsampled surface has UV[r][2X] = U[r][X], UV[r][2X+1] =
+ *            V[r][X]; a 4:4:4 surface has plane 1 = U and plane 2 = V.  8-bit: bytes move unchanged.  P010 / P210, pack: every surface
+ *            word is (plane word & 1023) << 6, Y included -- planar 10-bit holds the code in the LOW bits, the surfaces hold code << 6, the
+ *            trap of doing this by hand.  P010 / P210, unpack: every plane word is surface word >> 6.  YUV444P10: words are copied verbatim
+ *            both ways (both layouts hold the code low).  unpack(pack(p)) == p wherever the planar words are codes (below 1024).
+ *   Planes.  y, u, v point at sample (0,0) of each plane, in DEVICE memory here; y_pitch and c_pitch are the bytes from one row to the
+ *            next of the Y plane and of the U and the V plane, 0 = tightly packed (w, or the chroma width, samples).
+ *   Launch.  The n frames of one geometry go in ONE launch per call, n in 1 .. RSR_SEQ_MAX (the frames one argument block carries); frame i
+ *            is src[i] -> dst[i].  Rows go to waves, lanes run along the row; 16-byte accesses where the addresses of a row allow them (a UV
+ *            piece of 16 bytes against 8 of U and 8 of V), then 4, then single samples, chosen per row; interleave and shift in registers.
+ *   Stream.  The contract of rsr_diff_tiles: asynchronous on `stream` (NULL = the context's stream, and the call waits); no host wait inside;
+ *            none of the context's workspace is used, so the call is safe next to calls of every kind.
+ *   Errors.  RSR_E_ARG before anything is launched: n outside 1 .. RSR_SEQ_MAX; a null pointer (ctx aside: src, dst, any plane, any data); an
+ *            unknown or RGB format; the parity rule of the format (rsr_image_bytes: an odd w of a 4:2:x surface, an odd h at 4:2:0); a plane
+ *            pitch below the bytes of a row; a negative pitch; for the 16-bit formats an odd plane pointer or pitch; and everything
+ *            rsr_process_device_batch refuses of the rsr_image.
+ *   Write discipline.  No byte outside the rows of the destination is written, no byte outside the rows of the source is read: pitched planes
+ *            inside a larger canvas and surfaces inside a padded allocation keep their surroundings.
+ * Out of scope: 4:1:1 and mono, 12- and 16-bit codes, NV24 / P410 / Y410 / AYUV, planes in host memory. */
+typedef struct rsr_planes
+{
+    void* y; void* u; void* v; /* the three planes of one YUV frame */
+    long long y_pitch;         /* bytes from one Y row to the next; 0 = tightly packed */
+    long long c_pitch;         /* bytes from one U (and V) row to the next; 0 = tightly packed */
+} rsr_planes;
+int rsr_pack_planes(rsr_ctx* ctx, int n, const rsr_planes* src, const rsr_image* dst, int fmt, int w, int h, void* stream);
+int rsr_unpack_planes(rsr_ctx* ctx, int n, const rsr_image* src, const rsr_planes* dst, int fmt, int w, int h, void* stream);
+
+/* ---- A video session: three-plane frames in HOST memory in, upscaled frames out (no reference counterpart) -----------------------------------
+ * What an ffmpeg filter, a VapourSynth plugin or a Y4M pipe holds are frames in host memory; rsr_process* stays uint8 RGB(A).  A session
+ * carries such frames through the diff / masked / sequence path above: rsr_video_send takes one frame, every `window` frames run as ONE
+ * sequence call, rsr_video_receive hands the results out in order.  fmt is one of the six YUV formats and names the planes' layout as in
+ * "Three-plane YUV frames" (NV12 = yuv420p, P010 = yuv420p10le -- the code in the LOW bits --, NV16 / P210 = yuv422p / yuv422p10le, YUV444P /
+ * YUV444P10); input and output have the same format; the rsr_planes point into HOST memory.
+ *   Open.    RSR_E_ARG for an RGB or unknown format, for a window outside 0 .. RSR_SEQ_MAX, for the parity rule of the input, and for what
+ *            rsr_out_size_fmt refuses at the context's output ratio and tile size -- the same message, with "YUV" in it where the parity rule
+ *            of the output bites.  window 0 means 8.  The session lowers the window, never below 1, until its device buffers -- window + 1
+ *            input and window + 1 output surfaces (the predecessor of a window stays resident) and the planar staging of one window on each
+ *            side -- fit half of the device memory that is free at open; RSR_E_NOMEM if a window of 1 does not fit.  rsr_video_info tells
+ *            the output size and the window in force (any pointer may be NULL).
+ *   States.  send stages a frame (it is copied before send returns); the window-th frame runs the window before send returns, and all its
+ *            frames are then ready.  rsr_video_ready: how many receive can hand out now.  send while ready frames remain: RSR_E_STATE;
+ *            receive with none ready: RSR_E_STATE.  flush runs what is pending (nothing pending: RSR_OK; ready frames remain:
+ *            RSR_E_STATE).  reset (a scene cut, a seek): the next frame is compared with nothing and all its tiles run; RSR_E_STATE while
+ *            frames are pending (flush first), frames that are ready stay ready.  close drops pending and ready frames; a session is closed BEFORE its context.  One thread at a
+ *            time per session; other calls on the context stay legal between the session's calls.  A change of the context's output
+ *            ratio or tile size while a session is open makes the next send (and flush) fail with RSR_E_STATE; every other option
+ *            (TTA aside: it is fixed at creation) takes effect for the next window.  Where "precise", "yuv_matrix", "yuv_range",
+ *            "yuv_siting" or the prepadding differ from the window before, the window's first frame is compared with nothing and all its
+ *            tiles run: no rectangle computed in the old mode is carried over.  After loading another model: rsr_video_reset.  A window
+ *            that fails is dropped whole (its copies are waited for), and the next frame is compared with nothing.
+ *   A window run.  The uploads (below); one rsr_pack_planes launch; rsr_diff_tiles_sequence against the last input surface of the window
+ *            before (all ones after open and reset); the one copy of the masks and the one synchronisation; rsr_process_device_sequence
+ *            with prev_out = the last output surface of the window before; one rsr_unpack_planes launch.  The download is receive's.
+ *   Host memory.  Pinned planes (rsr_host_alloc, registered memory: all three) are copied to and from the device directly, as rsr_process
+ *            copies pinned images; pageable planes go through the session's pinned staging.  Pitches as in rsr_planes, 0 = packed; what
+ *            rsr_pack_planes refuses of device planes (null, negative or short pitch, 16-bit: odd pointer or pitch) is RSR_E_ARG here.  No
+ *            byte outside the rows of a destination plane is written.
+ *   Exactness.  Output frame k is unpack(rsr_process_device_fmt(pack(frame k))) in the context's mode at the time its window runs, byte for
+ *            byte: it depends neither on the window size nor on the frames before it.
+ *   Stats    "video_frames", "video_windows", "video_tiles_run", "video_tiles_skipped" (counted once a window is enqueued); the sequence
+ *            calls count in "seq_*" as ever.
+ * Out of scope: RGB or float frames, different formats on the two sides, groups of GPUs, overlap of one window's copies with the next
+ * window's compute, interlaced material.  (The CLI runs YUV4MPEG2 streams through one such session: realsr-hip -i in.y4m -o out.y4m.) */
+typedef struct rsr_video rsr_video;
+int rsr_video_open(rsr_ctx* ctx, int fmt, int w, int h, int window, rsr_video** out);
+int rsr_video_send(rsr_video* v, const rsr_planes* host_frame);    /* one frame in */
+int rsr_video_ready(rsr_video* v);                                 /* frames receive can hand out now (negative: RSR_E_ARG) */
+int rsr_video_receive(rsr_video* v, const rsr_planes* host_frame); /* oldest ready frame out */
+int rsr_video_flush(rsr_video* v);                                 /* run the partial window */
+int rsr_video_reset(rsr_video* v);                                 /* scene cut / seek: the next frame is compared with nothing */
+int rsr_video_info(rsr_video* v, int* ow, int* oh, int* window);
+void rsr_video_close(rsr_video* v);
 
 /* Host-only: bytes from `data` to one past the last byte a w x h x c image in `fmt` with these pitches touches (0 = packed, as above: then
  * rsr_image_bytes), or RSR_E_ARG for a combination rsr_process_device_batch refuses. */

@@ -12,6 +12,7 @@ import ctypes as C
 import fractions
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -37,6 +38,9 @@ EXPORTS = [
     "rsr_tile_count", "rsr_tile_source_rect", "rsr_diff_tiles", "rsr_process_device_masked",
     "rsr_sequence_sources", "rsr_diff_tiles_sequence", "rsr_process_device_sequence",
     "rsr_out_size_fmt",
+    "rsr_pack_planes", "rsr_unpack_planes",
+    "rsr_video_open", "rsr_video_send", "rsr_video_ready", "rsr_video_receive", "rsr_video_flush", "rsr_video_reset", "rsr_video_info",
+    "rsr_video_close",
 ]
 
 NUM_CONVS = 351  # convolutions of the default-depth model (23 RRDB blocks); a loaded model's own count is RealSR.num_convs
@@ -71,6 +75,12 @@ class SelfcheckReport(C.Structure):
 class Image(C.Structure):
     """rsr_image: a device image behind its own pointer, row pitch and plane pitch (bytes; 0 = tightly packed)."""
     _fields_ = [("data", C.c_void_p), ("row_pitch", C.c_longlong), ("plane_pitch", C.c_longlong)]
+
+
+class Planes(C.Structure):
+    """rsr_planes: the three planes of one YUV frame (yuv420p / yuv422p / yuv444p and their 10-bit forms) behind their own pointers;
+    y_pitch and c_pitch in bytes, 0 = tightly packed."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_pitch", C.c_longlong), ("c_pitch", C.c_longlong)]
 
 
 class RealSRError(RuntimeError):
@@ -138,6 +148,17 @@ def lib():
     L.rsr_sequence_sources.argtypes = [ip, ip, vp, ip, C.POINTER(ip)]
     L.rsr_diff_tiles_sequence.argtypes = [vp, ip, C.POINTER(Image), C.POINTER(Image), ip, ip, ip, ip, vp, vp]
     L.rsr_process_device_sequence.argtypes = [vp, ip, C.POINTER(Image), ip, ip, ip, ip, C.POINTER(Image), ip, C.POINTER(Image), vp, ip, vp]
+    L.rsr_pack_planes.argtypes = [vp, ip, C.POINTER(Planes), C.POINTER(Image), ip, ip, ip, vp]
+    L.rsr_unpack_planes.argtypes = [vp, ip, C.POINTER(Image), C.POINTER(Planes), ip, ip, ip, vp]
+    L.rsr_video_open.argtypes = [vp, ip, ip, ip, ip, C.POINTER(vp)]
+    L.rsr_video_send.argtypes = [vp, C.POINTER(Planes)]
+    L.rsr_video_ready.argtypes = [vp]
+    L.rsr_video_receive.argtypes = [vp, C.POINTER(Planes)]
+    L.rsr_video_flush.argtypes = [vp]
+    L.rsr_video_reset.argtypes = [vp]
+    L.rsr_video_info.argtypes = [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
+    L.rsr_video_close.argtypes = [vp]
+    L.rsr_video_close.restype = None
     L.rsr_model_pack.argtypes = [cp, cp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_device_memory.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rsr_host_alloc.argtypes = [C.c_size_t]
@@ -391,6 +412,8 @@ class RealSR:
 
     def close(self):
         if getattr(self, "_h", None):
+            for v in list(getattr(self, "_videos", ())):  # open video sessions go first: they hold device memory of this context
+                v.close()
             self._L.rsr_destroy(self._h)
             self._h = None
 
@@ -527,6 +550,22 @@ class RealSR:
         self._push_params()
         self._ck(self._L.rsr_diff_tiles_sequence(self._h, len(frames), _images(frames), _images([prev]) if prev is not None else None, int(fmt), w, h, c,
                                                  C.c_void_p(int(d_masks)), C.c_void_p(int(stream)) if stream else None))
+
+    def pack_planes(self, planes, surfaces, fmt, w, h, stream=None):
+        """rsr_pack_planes: the three-plane frames planes[i] -- (y, u, v) device pointers or (y, u, v, y_pitch, c_pitch), pitches in bytes,
+        0 = packed -- into the surfaces surfaces[i] (pointers or (ptr, row_pitch, plane_pitch)) of format fmt, ONE launch for all of
+        them.  P010 / P210: every word becomes (word & 1023) << 6.  Asynchronous on `stream`; None = the context's stream, synchronously."""
+        if len(planes) != len(surfaces):
+            raise ValueError("pack_planes: %d frames for %d surfaces" % (len(planes), len(surfaces)))
+        self._ck(self._L.rsr_pack_planes(self._h, len(planes), _planes(planes), _images(surfaces), int(fmt), w, h,
+                                         C.c_void_p(int(stream)) if stream else None))
+
+    def unpack_planes(self, surfaces, planes, fmt, w, h, stream=None):
+        """rsr_unpack_planes: the way back, surfaces[i] -> planes[i]; P010 / P210: every plane word is the surface word >> 6."""
+        if len(planes) != len(surfaces):
+            raise ValueError("unpack_planes: %d surfaces for %d frames" % (len(surfaces), len(planes)))
+        self._ck(self._L.rsr_unpack_planes(self._h, len(surfaces), _images(surfaces), _planes(planes), int(fmt), w, h,
+                                           C.c_void_p(int(stream)) if stream else None))
 
     def process_device_sequence(self, srcs, in_fmt, w, h, c, dsts, out_fmt, masks, prev_out=None, stream=None):
         """rsr_process_device_sequence: the frames srcs[k] -> dsts[k] (at most RSR_SEQ_MAX) in one call.  masks: a HOST uint8 array of
@@ -707,6 +746,98 @@ class RealSR:
         return {k: getattr(p, k) for k, _ in Profile._fields_}
 
 
+_VIDEO_CHROMA = {RSR_FMT_NV12: (1, 1), RSR_FMT_P010: (1, 1), RSR_FMT_NV16: (1, 0), RSR_FMT_P210: (1, 0), RSR_FMT_YUV444P: (0, 0), RSR_FMT_YUV444P10: (0, 0)}
+
+
+class Video:
+    """rsr_video: a host video session on the loaded context sr (include/realsr_hip.h "A video session").  fmt names the layout of the
+    three planes -- RSR_FMT_NV12 = yuv420p, RSR_FMT_P010 = yuv420p10le (the code in the LOW bits), NV16 / P210 = yuv422p / yuv422p10le,
+    YUV444P / YUV444P10 --, the same on both sides.  send(y, u, v) takes numpy arrays (uint8, or uint16 for the 10-bit formats), strides
+    along the rows honoured; every `window` frames run as one sequence call; receive() returns the oldest ready frame as (y, u, v)."""
+
+    def __init__(self, sr, fmt, w, h, window=0):
+        self._sr, self._L, self._h = sr, sr._L, None
+        self.fmt, self.w, self.h = int(fmt), int(w), int(h)
+        sr._push_params()
+        hnd = C.c_void_p()
+        sr._ck(self._L.rsr_video_open(sr._h, self.fmt, self.w, self.h, int(window), C.byref(hnd)))
+        self._h = hnd
+        if not hasattr(sr, "_videos"):
+            sr._videos = weakref.WeakSet()  # RealSR.close closes the sessions that are still open
+        sr._videos.add(self)
+        ow, oh, win = C.c_int(0), C.c_int(0), C.c_int(0)
+        sr._ck(self._L.rsr_video_info(self._h, C.byref(ow), C.byref(oh), C.byref(win)))
+        self.out_size, self.window = (ow.value, oh.value), win.value
+        self._dtype = np.dtype(np.uint8 if self.fmt in (RSR_FMT_NV12, RSR_FMT_NV16, RSR_FMT_YUV444P) else np.uint16)
+
+    def _shapes(self, w, h):
+        sx, sy = _VIDEO_CHROMA[self.fmt]
+        return (h, w), (h >> sy, w >> sx), (h >> sy, w >> sx)
+
+    def _entry(self, planes, w, h, what):
+        """The rsr_planes of three numpy arrays (rows contiguous, u and v with one row stride)."""
+        es = self._dtype.itemsize
+        for a, shape in zip(planes, self._shapes(w, h)):
+            if not isinstance(a, np.ndarray) or a.dtype != self._dtype or a.shape != shape:
+                raise ValueError("%s: a plane must be a %s array of shape %s" % (what, self._dtype, shape))
+            if (a.shape[1] > 1 and a.strides[1] != es) or (a.shape[0] > 1 and a.strides[0] < a.shape[1] * es):
+                raise ValueError("%s: the rows of a plane must be contiguous and lie upwards in memory (strides %s)" % (what, a.strides))
+        y, u, v = planes
+        if u.shape[0] > 1 and u.strides[0] != v.strides[0]:
+            raise ValueError("%s: u and v must have one row stride" % what)
+        p = Planes()
+        p.y, p.u, p.v = y.ctypes.data, u.ctypes.data, v.ctypes.data
+        p.y_pitch = y.strides[0] if y.shape[0] > 1 else 0
+        p.c_pitch = u.strides[0] if u.shape[0] > 1 else 0
+        return p
+
+    def _live(self):
+        if self._h is None:
+            raise RealSRError(RSR_E_STATE, "the video session is closed")
+        return self._h
+
+    def send(self, y, u, v):
+        """One frame in; the window-th frame runs the window before this returns."""
+        h = self._live()
+        self._sr._push_params()
+        self._sr._ck(self._L.rsr_video_send(h, C.byref(self._entry((y, u, v), self.w, self.h, "send"))))
+
+    @property
+    def ready(self):
+        return int(self._L.rsr_video_ready(self._live()))
+
+    def receive(self, out=None):
+        """The oldest ready frame as (y, u, v) -- new arrays, or the three arrays `out` (views with contiguous rows are written in place)."""
+        h = self._live()
+        if out is None:
+            out = tuple(np.empty(s, dtype=self._dtype) for s in self._shapes(*self.out_size))
+        self._sr._ck(self._L.rsr_video_receive(h, C.byref(self._entry(tuple(out), self.out_size[0], self.out_size[1], "receive"))))
+        return tuple(out)
+
+    def flush(self):
+        """Run the frames that are pending as a partial window."""
+        h = self._live()
+        self._sr._push_params()
+        self._sr._ck(self._L.rsr_video_flush(h))
+
+    def reset(self):
+        """A scene cut, a seek: the next frame is compared with nothing."""
+        self._sr._ck(self._L.rsr_video_reset(self._live()))
+
+    def close(self):
+        if self._h is not None:
+            if getattr(self._sr, "_h", None):  # (RealSR.close closes its sessions first, so a live handle has a live context)
+                self._L.rsr_video_close(self._h)
+            self._h = None
+            getattr(self._sr, "_videos", set()).discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def selfcheck_tile(w=0, h=0):
     """rsr_selfcheck_tile (host-only): the self-check's built-in tile, float16 planar (3,h,w); 0, 0 = 148 x 148."""
     if w == 0 and h == 0:
@@ -776,6 +907,15 @@ def _images(entries):
     for a, e in zip(arr, entries):
         ptr, row, plane = e if isinstance(e, (tuple, list)) else (e, 0, 0)
         a.data, a.row_pitch, a.plane_pitch = int(ptr), int(row), int(plane)
+    return arr
+
+
+def _planes(entries):
+    """A ctypes array of rsr_planes from (y, u, v) or (y, u, v, y_pitch, c_pitch) tuples."""
+    arr = (Planes * max(len(entries), 1))()
+    for a, e in zip(arr, entries):
+        y, u, v, yp, cp = tuple(e) if len(e) == 5 else tuple(e) + (0, 0)
+        a.y, a.u, a.v, a.y_pitch, a.c_pitch = int(y) or None, int(u) or None, int(v) or None, int(yp), int(cp)
     return arr
 
 

@@ -240,6 +240,18 @@ int rsr_process_device_sequence(rsr_ctx* ctx, int n, const rsr_image* in, int in
     }
 }
 
+int rsr_pack_planes(rsr_ctx* ctx, int n, const rsr_planes* src, const rsr_image* dst, int fmt, int w, int h, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    return ctx->e.move_planes(true, n, src, dst, fmt, w, h, static_cast<hipStream_t>(stream));
+}
+
+int rsr_unpack_planes(rsr_ctx* ctx, int n, const rsr_image* src, const rsr_planes* dst, int fmt, int w, int h, void* stream)
+{
+    if (!ctx) return RSR_E_ARG;
+    return ctx->e.move_planes(false, n, dst, src, fmt, w, h, static_cast<hipStream_t>(stream));
+}
+
 int rsr_tile_count(int w, int h, int tilesize, int* nx, int* ny)
 {
     if (w < 1 || h < 1 || tilesize < 1 || w > (1 << 24) || h > (1 << 24) || tilesize > (1 << 24)) return Engine::fail(RSR_E_ARG, "bad image or tile size");
@@ -681,6 +693,10 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "seq_tiles_run") *value = double(e.seq_tiles_run);
     else if (k == "seq_tiles_copied") *value = double(e.seq_tiles_copied);
     else if (k == "seq_batches") *value = double(e.seq_batches);
+    else if (k == "video_frames") *value = double(e.video_frames);
+    else if (k == "video_windows") *value = double(e.video_windows);
+    else if (k == "video_tiles_run") *value = double(e.video_tiles_run);
+    else if (k == "video_tiles_skipped") *value = double(e.video_tiles_skipped);
     else if (k == "merged_batches") *value = double(e.merged_batches.load());
     else if (k == "merged_images") *value = double(e.merged_images.load());
     else if (k == "merged_widest") *value = double(e.merged_widest.load());

@@ -1609,6 +1609,46 @@ int Engine::diff_tiles(const rsr_image* a, const rsr_image* b, int fmt, int w, i
     return diff_pairs(1, r, fmt, w, h, c, d_mask, user_stream);
 }
 
+// ---- three-plane YUV frames <-> surfaces (include/realsr_hip.h rsr_pack_planes, rsr_unpack_planes) ------------------------------------------
+// Like the diff the launch touches neither the workspace nor anything of the calls in flight: it goes to the caller's stream as it is.
+int Engine::move_planes(bool pack, int n, const rsr_planes* planes, const rsr_image* surf, int fmt, int w, int h, hipStream_t user_stream)
+{
+    const char* const who = pack ? "rsr_pack_planes" : "rsr_unpack_planes";
+    if (n < 1 || n > kMaxMerge) return fail(RSR_E_ARG, std::string(who) + ": n must be 1 .. " + std::to_string(kMaxMerge));
+    if (!planes || !surf) return fail(RSR_E_ARG, std::string(who) + ": null pointer");
+    const PixFmt f = pix_fmt(fmt);
+    if (!f.bits) return fail(RSR_E_ARG, std::string(who) + ": the format must be one of the YUV formats");
+    ImageRef refs[kMaxMerge];
+    if (const int rc = image_refs(n, surf, fmt, w, h, 3, nullptr, "surface", 0, refs)) return rc;
+    PlanesArgs pa;
+    std::memset(&pa, 0, sizeof pa);
+    const long long yrow = (long long)w * f.es, crow = (long long)(w >> f.csx) * f.es;
+    for (int i = 0; i < n; i++)
+    {
+        const rsr_planes& p = planes[i];
+        const char* why = nullptr;
+        const long long yp = p.y_pitch ? p.y_pitch : yrow, cp = p.c_pitch ? p.c_pitch : crow;
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.u) | reinterpret_cast<uintptr_t>(p.v) | uintptr_t(yp) | uintptr_t(cp);
+        if (!p.y || !p.u || !p.v) why = "null plane pointer";
+        else if (p.y_pitch < 0 || p.c_pitch < 0) why = "negative pitch";
+        else if (yp < yrow || cp < crow) why = "pitch below the bytes of a row";
+        else if (bits % uintptr_t(f.es)) why = "a plane pointer or pitch is not a multiple of the sample size";
+        if (why) return fail(RSR_E_ARG, std::string(who) + ": frame " + std::to_string(i) + ": " + why);
+        PlaneFrame& d = pa.f[i];
+        d.y = static_cast<uint8_t*>(p.y), d.u = static_cast<uint8_t*>(p.u), d.v = static_cast<uint8_t*>(p.v);
+        d.surf = static_cast<uint8_t*>(const_cast<void*>(refs[i].data));
+        d.y_pitch = yp, d.c_pitch = cp, d.row = refs[i].row, d.plane = refs[i].plane;
+    }
+    pa.n = n, pa.fmt = fmt, pa.w = w, pa.h = h;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_move_planes(pa, pack, user_stream ? user_stream : stream));
+    }
+    if (!user_stream) HIP_TRY(hipStreamSynchronize(stream));
+    return RSR_OK;
+}
+
 // ---- frame sequences (include/realsr_hip.h "frame sequences") ------------------------------------------------------------------------------
 int sequence_sources(int n, int ntiles, const uint8_t* masks, int has_prev, int* src)
 {

@@ -383,6 +383,7 @@ struct Engine
     double masked_table_us = 0; // stat: host time spent building and uploading those tables
     // frame sequences (rsr_process_device_sequence); their tables travel in the rotating buffers of the masked calls
     long long seq_calls = 0, seq_frames = 0, seq_tiles_run = 0, seq_tiles_copied = 0, seq_batches = 0; // stats, under mu
+    long long video_frames = 0, video_windows = 0, video_tiles_run = 0, video_tiles_skipped = 0; // of the video sessions (video.cpp), under mu
     long long image_items(int w, int h, long long limit) const;
     int merge_width(int w, int h, int c) const; // images of this geometry one batch may take (1: not a small image / merging off)
     int submit_merged(MergeReq& r);             // returns when r's batch has been ENQUEUED (r.ev_done recorded) or failed
@@ -431,6 +432,9 @@ struct Engine
     // network as shared tile batches (enqueue_sequence); every other output rectangle is copied from the frame that computed it last, or
     // from prev_out, by one launch behind the last batch.
     int diff_tiles_sequence(int n, const rsr_image* frames, const rsr_image* prev, int fmt, int w, int h, int c, uint8_t* d_masks, hipStream_t user_stream);
+    // Three-plane YUV frames <-> surfaces (include/realsr_hip.h rsr_pack_planes / rsr_unpack_planes): n frames of one geometry, one launch on the
+    // caller's stream with the contract of diff_tiles; pack: planes -> surface.  Everything is checked before the launch.
+    int move_planes(bool pack, int n, const rsr_planes* planes, const rsr_image* surf, int fmt, int w, int h, hipStream_t user_stream);
     int process_device_sequence(int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, const rsr_image* prev_out,
                                 const uint8_t* masks, int nmask, hipStream_t user_stream, bool sync);
     // tile0/tile1: tiles [tile0, tile1) of the row-major tile grid only (tile1 < 0: all); `out` is always the full (w * out_scale x h * out_scale x c) image,

@@ -422,6 +422,28 @@ struct PropRect
 // d_rects: DEVICE table of nrects entries; max_rows: the tallest of them (sizes the grid)
 hipError_t launch_propagate_rects(const PropRect* d_rects, int nrects, int max_rows, hipStream_t st);
 
+// ---- three-plane YUV frames <-> surfaces (rsr_pack_planes, rsr_unpack_planes) -----------------------------------------------------------
+// A frame as a software decoder holds it (yuv420p, yuv422p, yuv444p and their 10-bit little-endian forms: three planes, each with rows
+// of its own) beside the surface of format `fmt` the engine takes.  Pitches in bytes, resolved; the chroma planes are (w >> csx) x
+// (h >> csy) samples.  Up to kMaxMerge frames of one geometry by value, as DiffArgs carries its pairs: ONE launch moves them all.
+struct PlaneFrame
+{
+    uint8_t *y, *u, *v; // the three planes
+    uint8_t* surf;      // Y(0,0) of the surface
+    long long y_pitch, c_pitch; // of the Y plane, of the U and V planes
+    long long row, plane;       // of the surface (ImageRef)
+};
+struct PlanesArgs
+{
+    PlaneFrame f[kMaxMerge];
+    int n; // <= kMaxMerge
+    int fmt, w, h;
+};
+// pack: planes -> surface, every P010 / P210 word (plane word & 1023) << 6; unpack: surface -> planes, every such word >> 6.  Bytes of the
+// 8-bit formats and words of YUV444P10 move unchanged.  Nothing outside the rows of the destination is written, nothing outside the rows
+// of the source read.
+hipError_t launch_move_planes(const PlanesArgs& a, bool pack, hipStream_t st);
+
 // shader-shaped standalone kernels (parity tests): device pointers
 void launch_preproc_shader(const uint8_t* bottom, int w, int h, int channels, uint16_t* const top[8], int ntop, int outw,
                            int outh, int outcstep, int pad_top, int pad_left, int crop_x, int crop_y, uint16_t* alpha,

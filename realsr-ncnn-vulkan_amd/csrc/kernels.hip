@@ -1731,6 +1731,225 @@ hipError_t launch_propagate_rects(const PropRect* d_rects, int nrects, int max_r
 }
 
 // =============================================================================================
+// three-plane YUV frames <-> surfaces (rsr_pack_planes, rsr_unpack_planes)
+// =============================================================================================
+// The idiom of propagate_rects: rows go to waves, lanes run along the row, the access is the widest the addresses of the row allow, and
+// the samples in front of the first and behind the last whole piece go one by one.  What is new is done in registers: the shift of the
+// P010 / P210 words and the interleave of a U and a V row into a UV row (and back).
+constexpr int kPlaneRows = 4; // rows per workgroup and step, one per wave: a 4320-row plane spreads over 1024 workgroups (propagate_rects has many rectangles for that; a frame has two or three planes)
+
+enum { kKeep = 0, kToHigh = 1, kToLow = 2 }; // a sample as it is | (word & 1023) << 6: planar -> P010 / P210 | word >> 6: the way back
+
+template <int OP> __device__ __forceinline__ uint32_t conv2(uint32_t x) // two 16-bit words at once
+{
+    if (OP == kToHigh) return (x & 0x03ff03ffu) << 6;
+    if (OP == kToLow) return (x >> 6) & 0x03ff03ffu;
+    return x;
+}
+template <int OP, typename E> __device__ __forceinline__ E conv1(E x) // one sample (OP != kKeep: a uint16_t)
+{
+    if (OP == kToHigh) return E((x & 1023u) << 6);
+    if (OP == kToLow) return E(x >> 6);
+    return x;
+}
+template <int OP> __device__ __forceinline__ uint4 conv(uint4 v) { return make_uint4(conv2<OP>(v.x), conv2<OP>(v.y), conv2<OP>(v.z), conv2<OP>(v.w)); }
+template <int OP> __device__ __forceinline__ uint32_t conv(uint32_t v) { return conv2<OP>(v); }
+template <int OP> __device__ __forceinline__ uint16_t conv(uint16_t v) { return conv1<OP>(v); }
+
+// copy_row for n bytes of 16-bit words that change on the way (OP != kKeep); pd, ps and n are even, so head and tail are whole words:
+// lanes 0 .. 7 and 8 .. 15 move them.
+template <typename TV, int OP>
+__device__ __forceinline__ void convert_row(uint8_t* pd, const uint8_t* ps, int n, int lane)
+{
+    constexpr int V = int(sizeof(TV));
+    const int head = min(n, int((0 - reinterpret_cast<uintptr_t>(pd)) & uintptr_t(V - 1)));
+    const int nvec = (n - head) / V, tail = n - head - nvec * V;
+    if (V > 2)
+    {
+        int e = -1;
+        if (lane < 8) e = 2 * lane < head ? 2 * lane : -1;
+        else if (lane < 16) e = 2 * (lane - 8) < tail ? n - tail + 2 * (lane - 8) : -1;
+        if (e >= 0) *reinterpret_cast<uint16_t*>(pd + e) = conv1<OP>(*reinterpret_cast<const uint16_t*>(ps + e));
+    }
+    TV* const vd = reinterpret_cast<TV*>(pd + head);
+    const TV* const vs = reinterpret_cast<const TV*>(ps + head);
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = lane; i < nvec; i += 256)
+    {
+        const bool b1 = i + 64 < nvec, b2 = i + 128 < nvec, b3 = i + 192 < nvec;
+        const TV v0 = vs[i];
+        TV v1 = v0, v2 = v0, v3 = v0;
+        if (b1) v1 = vs[i + 64];
+        if (b2) v2 = vs[i + 128];
+        if (b3) v3 = vs[i + 192];
+        vd[i] = conv<OP>(v0);
+        if (b1) vd[i + 64] = conv<OP>(v1);
+        if (b2) vd[i + 128] = conv<OP>(v2);
+        if (b3) vd[i + 192] = conv<OP>(v3);
+    }
+}
+
+// One row of a plane that keeps its layout (Y; every plane of a 4:4:4 frame): n bytes of ES-byte samples.  The width is chosen per row,
+// uniformly for the wave, as propagate_rects chooses it; 16-bit rows fall back to words, not bytes.
+template <int ES, int OP>
+__device__ __forceinline__ void move_row(uint8_t* pd, const uint8_t* ps, int n, int lane)
+{
+    const unsigned mis = __builtin_amdgcn_readfirstlane(unsigned(reinterpret_cast<uintptr_t>(pd) ^ reinterpret_cast<uintptr_t>(ps)));
+    if (OP == kKeep)
+    {
+        if (!(mis & 15)) copy_row<uint4>(pd, ps, n, lane);
+        else if (!(mis & 3)) copy_row<uint32_t>(pd, ps, n, lane);
+        else if (ES == 2) copy_row<uint16_t>(pd, ps, n, lane);
+        else copy_row<uint8_t>(pd, ps, n, lane);
+    }
+    else
+    {
+        if (!(mis & 15)) convert_row<uint4, OP>(pd, ps, n, lane);
+        else if (!(mis & 3)) convert_row<uint32_t, OP>(pd, ps, n, lane);
+        else convert_row<uint16_t, OP>(pd, ps, n, lane);
+    }
+}
+
+// Two source bytes of U and two of V (the low halves of u and v) as the four bytes of UV they make: two pairs of bytes, one pair of words.
+template <int ES> __device__ __forceinline__ uint32_t weave2(uint32_t u, uint32_t v)
+{
+    if (ES == 1) return (u & 0xffu) | ((v & 0xffu) << 8) | ((u & 0xff00u) << 8) | ((v & 0xff00u) << 16);
+    return (u & 0xffffu) | (v << 16);
+}
+template <int ES> __device__ __forceinline__ void unweave2(uint32_t d, uint32_t& u, uint32_t& v) // ... and back, into the low halves
+{
+    if (ES == 1) u = (d & 0xffu) | ((d >> 8) & 0xff00u), v = ((d >> 8) & 0xffu) | ((d >> 16) & 0xff00u);
+    else u = d & 0xffffu, v = d >> 16;
+}
+template <int ES, int OP> __device__ __forceinline__ uint4 weave(uint2 u, uint2 v)
+{
+    return make_uint4(conv2<OP>(weave2<ES>(u.x, v.x)), conv2<OP>(weave2<ES>(u.x >> 16, v.x >> 16)), conv2<OP>(weave2<ES>(u.y, v.y)),
+                      conv2<OP>(weave2<ES>(u.y >> 16, v.y >> 16)));
+}
+template <int ES, int OP> __device__ __forceinline__ uint32_t weave(uint16_t u, uint16_t v) { return conv2<OP>(weave2<ES>(u, v)); }
+template <int ES, int OP> __device__ __forceinline__ void unweave(uint4 d, uint2& u, uint2& v)
+{
+    uint32_t u0, v0, u1, v1, u2, v2, u3, v3;
+    unweave2<ES>(conv2<OP>(d.x), u0, v0), unweave2<ES>(conv2<OP>(d.y), u1, v1), unweave2<ES>(conv2<OP>(d.z), u2, v2), unweave2<ES>(conv2<OP>(d.w), u3, v3);
+    u = make_uint2(u0 | (u1 << 16), u2 | (u3 << 16)), v = make_uint2(v0 | (v1 << 16), v2 | (v3 << 16));
+}
+template <int ES, int OP> __device__ __forceinline__ void unweave(uint32_t d, uint16_t& u, uint16_t& v)
+{
+    uint32_t u0, v0;
+    unweave2<ES>(conv2<OP>(d), u0, v0);
+    u = uint16_t(u0), v = uint16_t(v0);
+}
+
+// np (U, V) pairs of ES-byte samples between a UV row and a U and a V row, one wave.  PACK: UV[2X] = U[X], UV[2X + 1] = V[X]; else the way
+// back.  A piece is one SV of U, one of V and one DV (twice as wide) of UV; the caller has seen that the three addresses reach the
+// boundaries of their pieces after the same number of pairs.  Those head pairs and the tail behind the last whole piece go sample by
+// sample (lanes 0 .. 7 and 8 .. 15: a piece has at most 8 pairs).
+template <bool PACK, int ES, int OP, typename SV, typename DV>
+__device__ __forceinline__ void pair_row(uint8_t* puv, uint8_t* pu, uint8_t* pv, int np, int lane)
+{
+    using E = std::conditional_t<ES == 1, uint8_t, uint16_t>;
+    constexpr int K = int(sizeof(SV)) / ES; // pairs per piece
+    static_assert(sizeof(DV) == 2 * sizeof(SV) && K >= 1 && K <= 8, "a UV piece is one piece of U and one of V");
+    const int head = min(np, int((0 - reinterpret_cast<uintptr_t>(pu)) & uintptr_t(sizeof(SV) - 1)) / ES);
+    const int nvec = (np - head) / K, tail = np - head - nvec * K;
+    E* const euv = reinterpret_cast<E*>(puv);
+    E* const eu = reinterpret_cast<E*>(pu);
+    E* const ev = reinterpret_cast<E*>(pv);
+    if (K > 1)
+    {
+        int e = -1;
+        if (lane < 8) e = lane < head ? lane : -1;
+        else if (lane < 16) e = lane - 8 < tail ? np - tail + lane - 8 : -1;
+        if (e >= 0)
+        {
+            if (PACK) euv[2 * e] = conv1<OP>(eu[e]), euv[2 * e + 1] = conv1<OP>(ev[e]);
+            else eu[e] = conv1<OP>(euv[2 * e]), ev[e] = conv1<OP>(euv[2 * e + 1]);
+        }
+    }
+    DV* const vuv = reinterpret_cast<DV*>(puv + head * 2 * ES);
+    SV* const vu = reinterpret_cast<SV*>(pu + head * ES);
+    SV* const vv = reinterpret_cast<SV*>(pv + head * ES);
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = lane; i < nvec; i += 64)
+    {
+        if (PACK) vuv[i] = weave<ES, OP>(vu[i], vv[i]);
+        else
+        {
+            SV su, sv;
+            unweave<ES, OP>(vuv[i], su, sv);
+            vu[i] = su, vv[i] = sv;
+        }
+    }
+}
+
+// The same at any addresses: a lane moves one pair, sample by sample.
+template <bool PACK, int ES, int OP>
+__device__ __forceinline__ void pair_row_samples(uint8_t* puv, uint8_t* pu, uint8_t* pv, int np, int lane)
+{
+    using E = std::conditional_t<ES == 1, uint8_t, uint16_t>;
+    E* const euv = reinterpret_cast<E*>(puv);
+    E* const eu = reinterpret_cast<E*>(pu);
+    E* const ev = reinterpret_cast<E*>(pv);
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = lane; i < np; i += 64)
+        if (PACK) euv[2 * i] = conv1<OP>(eu[i]), euv[2 * i + 1] = conv1<OP>(ev[i]);
+        else eu[i] = conv1<OP>(euv[2 * i]), ev[i] = conv1<OP>(euv[2 * i + 1]);
+}
+
+// grid (row chunk, plane, frame): plane 0 is Y, plane 1 the UV plane of a surface -- made of, or taken apart into, the planes U and V --
+// or, 4:4:4, U, and plane 2 V.  PACK: planes -> surface.  The UV piece is 16 bytes (8 of U, 8 of V) where the UV row starts on a whole
+// pair and half its address agrees with the U and the V address modulo 8, 4 bytes where they agree modulo 2, single samples otherwise.
+template <bool PACK, int ES, int OP>
+__global__ __launch_bounds__(256) void move_planes(const PlanesArgs a)
+{
+    const PixFmt f = pix_fmt(a.fmt);
+    const PlaneFrame& fr = a.f[blockIdx.z];
+    const int part = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int step = gridDim.x * kPlaneRows;
+    const bool pairs = f.pairs && part == 1;
+    const int rows = part ? a.h >> f.csy : a.h, n = a.w * ES;
+    uint8_t* const plane = part == 0 ? fr.y : part == 1 ? fr.u : fr.v;
+    const long long ppitch = part ? fr.c_pitch : fr.y_pitch;
+    uint8_t* const surf = fr.surf + part * fr.plane;
+#pragma unroll 1
+    for (int ys = blockIdx.x * kPlaneRows + wave; ys < rows; ys += step)
+#pragma unroll 1
+        for (int y = ys; y < min(ys - wave + kPlaneRows, rows); y += 4)
+        {
+            uint8_t* const ps = surf + (long long)y * fr.row;
+            uint8_t* const pp = plane + (long long)y * ppitch;
+            if (!pairs)
+            {
+                if (PACK) move_row<ES, OP>(ps, pp, n, lane);
+                else move_row<ES, OP>(pp, ps, n, lane);
+                continue;
+            }
+            uint8_t* const pv = fr.v + (long long)y * ppitch;
+            const uintptr_t auv = reinterpret_cast<uintptr_t>(ps), half = auv >> 1;
+            const unsigned mis = __builtin_amdgcn_readfirstlane(unsigned((half ^ reinterpret_cast<uintptr_t>(pp)) | (half ^ reinterpret_cast<uintptr_t>(pv))) |
+                                                                (unsigned(auv) & unsigned(2 * ES - 1) ? 15u : 0u));
+            if (!(mis & 7)) pair_row<PACK, ES, OP, uint2, uint4>(ps, pp, pv, a.w >> 1, lane);
+            else if (!(mis & 1)) pair_row<PACK, ES, OP, uint16_t, uint32_t>(ps, pp, pv, a.w >> 1, lane);
+            else pair_row_samples<PACK, ES, OP>(ps, pp, pv, a.w >> 1, lane);
+        }
+}
+
+hipError_t launch_move_planes(const PlanesArgs& a, bool pack, hipStream_t st)
+{
+    const PixFmt f = pix_fmt(a.fmt);
+    if (a.n <= 0 || a.h <= 0 || !f.bits) return hipSuccess;
+    const int chunks = (a.h + kPlaneRows - 1) / kPlaneRows;
+    const dim3 grid(chunks < 4096 ? chunks : 4096, f.planes, a.n), block(256); // (a taller frame: the workgroups stride over the chunks)
+    void (*k)(const PlanesArgs);
+    if (f.es == 1) k = pack ? move_planes<true, 1, kKeep> : move_planes<false, 1, kKeep>;
+    else if (!f.high) k = pack ? move_planes<true, 2, kKeep> : move_planes<false, 2, kKeep>;
+    else k = pack ? move_planes<true, 2, kToHigh> : move_planes<false, 2, kToLow>;
+    hipLaunchKernelGGL(k, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+// =============================================================================================
 // model self-check: range probe and output compare (Engine::selfcheck)
 // =============================================================================================
 constexpr int kCheckBlocks = 512; // grid-stride: at most this many workgroups of 256

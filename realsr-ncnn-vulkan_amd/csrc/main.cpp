@@ -9,7 +9,9 @@
 //     dealt image by image from the shared queue exactly like the reference (main.cpp:811-828);
 //   * codecs: stb_image / stb_image_write as in the reference (jpg, png, ... in; png, jpg out) + binary pnm; webp in / lossless
 //     webp out through the system's libwebp, bound at run time (webp_dl.h) -- without it webp files fail like a broken image;
-//   * "-j l:p:s" accepts a single proc count for several GPUs (the reference insists on one per GPU).
+//   * "-j l:p:s" accepts a single proc count for several GPUs (the reference insists on one per GPU);
+//   * video mode (no counterpart): an input that ends in .y4m, or is "-" (stdin), is a YUV4MPEG2 stream and runs through one rsr_video
+//     session to a .y4m output or "-" (stdout) -- run_video below, y4m_io.h.
 #include <dirent.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -28,14 +30,15 @@
 
 #include "image_io.h"
 #include "realsr.h"
+#include "y4m_io.h"
 
 static void print_usage()
 {
     fprintf(stderr, "Usage: realsr-hip -i infile -o outfile [options]...\n\n");
     fprintf(stderr, "  -h                   show this help\n");
     fprintf(stderr, "  -v                   verbose output\n");
-    fprintf(stderr, "  -i input-path        input image path (jpg/png/pnm) or directory\n");
-    fprintf(stderr, "  -o output-path       output image path (jpg/png) or directory\n");
+    fprintf(stderr, "  -i input-path        input image path (jpg/png/pnm) or directory; a YUV4MPEG2 stream: file.y4m, or - for stdin\n");
+    fprintf(stderr, "  -o output-path       output image path (jpg/png) or directory; for a YUV4MPEG2 input: file.y4m, or - for stdout\n");
     fprintf(stderr, "  -s scale             upscale ratio (4, default=4)\n");
     fprintf(stderr, "  -t tile-size         tile size (>=32/0=auto, default=0) can be 0,0,0 for multi-gpu\n");
     fprintf(stderr, "  -m model-path        realsr model path (default=models-DF2K_JPEG)\n");
@@ -143,6 +146,141 @@ private:
 
 static const int kEnd = -233; // same sentinel id as main.cpp:322,350
 
+// ---- video mode: a YUV4MPEG2 stream through one rsr_video session ---------------------------------------------------------------------
+static bool is_y4m_path(const std::string& p) { return p == "-" || imgio::lower_ext(p) == "y4m"; }
+
+// An integer from the environment, or `fallback` where the variable is not set (or is no number).
+static long long env_int(const char* name, long long fallback)
+{
+    const char* e = getenv(name);
+    if (!e || !*e) return fallback;
+    char* end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    return end && *end == 0 ? v : fallback;
+}
+
+// The C tag picks the format and the chroma siting, XCOLORRANGE the range; RSR_YUV_MATRIX / RSR_YUV_RANGE / RSR_YUV_SITING override
+// (matrix: the library's 709 unless said).  The context comes configured (tile size, output ratio, TTA, precise).  Every complete
+// frame of the input is written, also in front of a stream that is cut inside a frame -- which then ends with exit code 1.
+static int run_video(rsr_ctx* ctx, const std::string& inpath, const std::string& outpath, int nx, int dx, int ny, int dy, int verbose)
+{
+    FILE* fi = inpath == "-" ? stdin : fopen(inpath.c_str(), "rb");
+    if (!fi)
+    {
+        fprintf(stderr, "cannot open %s\n", inpath.c_str());
+        return 1;
+    }
+    y4m::Header hd;
+    std::string line;
+    const int lrc = y4m::read_line(fi, line);
+    std::string err = lrc == 0 ? y4m::parse_header(line, hd) : lrc == 1 ? std::string("empty input") : std::string("header line without a newline within 256 bytes");
+    if (!err.empty())
+    {
+        fprintf(stderr, "%s: %s\n", inpath.c_str(), err.c_str());
+        return 1;
+    }
+    const long long siting = env_int("RSR_YUV_SITING", hd.siting >= 0 ? hd.siting : 0), range = env_int("RSR_YUV_RANGE", hd.range >= 0 ? hd.range : 0);
+    if (rsr_set_option(ctx, "yuv_matrix", env_int("RSR_YUV_MATRIX", 709)) != RSR_OK || rsr_set_option(ctx, "yuv_range", range) != RSR_OK ||
+        rsr_set_option(ctx, "yuv_siting", siting) != RSR_OK)
+    {
+        fprintf(stderr, "invalid RSR_YUV_MATRIX / RSR_YUV_RANGE / RSR_YUV_SITING: %s\n", rsr_last_error(ctx));
+        return 1;
+    }
+    rsr_video* v = nullptr;
+    if (rsr_video_open(ctx, hd.fmt, hd.w, hd.h, int(env_int("RSR_VIDEO_WINDOW", 0)), &v) != RSR_OK)
+    {
+        fprintf(stderr, "%s: %s\n", inpath.c_str(), rsr_last_error(ctx));
+        return 1;
+    }
+    int ow = 0, oh = 0, window = 0;
+    rsr_video_info(v, &ow, &oh, &window);
+    FILE* fo = outpath == "-" ? stdout : fopen(outpath.c_str(), "wb");
+    if (!fo)
+    {
+        fprintf(stderr, "cannot open %s\n", outpath.c_str());
+        rsr_video_close(v);
+        return 1;
+    }
+    if (verbose) fprintf(stderr, "video: %d x %d -> %d x %d, windows of %d frames, yuv_range %lld, yuv_siting %lld\n", hd.w, hd.h, ow, oh, window, range, siting);
+    const std::string head = y4m::format_header(hd, ow, oh, nx, dx, ny, dy);
+    bool ok = fwrite(head.data(), 1, head.size(), fo) == head.size();
+    const size_t es = size_t(y4m::sample_bytes(hd.fmt));
+    const auto planes_of = [&](unsigned char* base, int w, int h) {
+        rsr_planes p;
+        const size_t ybytes = es * size_t(w) * size_t(h), cbytes = es * size_t(w >> y4m::chroma_shift_x(hd.fmt)) * size_t(h >> y4m::chroma_shift_y(hd.fmt));
+        p.y = base, p.u = base + ybytes, p.v = base + ybytes + cbytes, p.y_pitch = 0, p.c_pitch = 0;
+        return p;
+    };
+    std::vector<unsigned char> in, out(y4m::frame_bytes(hd.fmt, ow, oh));
+    std::queue<std::string> params; // the FRAME lines of the frames in flight, in order
+    double run0 = 0, skip0 = 0;
+    rsr_get_stat(ctx, "video_tiles_run", &run0);
+    rsr_get_stat(ctx, "video_tiles_skipped", &skip0);
+    long long frames = 0;
+    // hand out what is ready; one line per window under -v
+    const auto drain = [&]() {
+        const int n = rsr_video_ready(v);
+        if (n > 0 && verbose)
+        {
+            double run = 0, skip = 0;
+            rsr_get_stat(ctx, "video_tiles_run", &run);
+            rsr_get_stat(ctx, "video_tiles_skipped", &skip);
+            fprintf(stderr, "window: %d frames, %.0f tiles run, %.0f skipped\n", n, run - run0, skip - skip0);
+            run0 = run, skip0 = skip;
+        }
+        while (ok && rsr_video_ready(v) > 0)
+        {
+            const rsr_planes op = planes_of(out.data(), ow, oh);
+            if (rsr_video_receive(v, &op) != RSR_OK)
+            {
+                fprintf(stderr, "%s\n", rsr_last_error(ctx));
+                ok = false;
+                break;
+            }
+            ok = y4m::write_frame(fo, params.front(), out.data(), out.size());
+            if (!ok) fprintf(stderr, "write to %s failed\n", outpath.c_str());
+            params.pop();
+            frames++;
+        }
+    };
+    int rc = 0;
+    while (ok)
+    {
+        std::string fl;
+        const int fr = y4m::read_frame(fi, hd, in, fl, err);
+        if (fr <= 0)
+        { // the end, clean or not: what is pending still runs and is written
+            if (rsr_video_flush(v) != RSR_OK)
+            {
+                fprintf(stderr, "%s\n", rsr_last_error(ctx));
+                ok = false;
+            }
+            else drain();
+            if (fr < 0)
+            {
+                fprintf(stderr, "%s: %s (after %lld complete frames)\n", inpath.c_str(), err.c_str(), frames);
+                rc = 1;
+            }
+            break;
+        }
+        params.push(fl);
+        const rsr_planes ip = planes_of(in.data(), hd.w, hd.h);
+        if (rsr_video_send(v, &ip) != RSR_OK)
+        {
+            fprintf(stderr, "%s\n", rsr_last_error(ctx));
+            ok = false;
+            break;
+        }
+        drain();
+    }
+    rsr_video_close(v);
+    if (fo != stdout) ok = fclose(fo) == 0 && ok;
+    else fflush(fo);
+    if (fi != stdin) fclose(fi);
+    if (verbose) fprintf(stderr, "%s -> %s done: %lld frames\n", inpath.c_str(), outpath.c_str(), frames);
+    return ok ? rc : 1;
+}
+
 int main(int argc, char** argv)
 {
     std::string inputpath, outputpath, model = "models-DF2K_JPEG", format = "png";
@@ -239,6 +377,17 @@ int main(int argc, char** argv)
     }
     if (gpuid.empty()) gpuid.push_back(0);
     const int ngpu = int(gpuid.size());
+    const bool video = is_y4m_path(inputpath) && !is_dir(inputpath); // a YUV4MPEG2 stream: one session on one GPU
+    if (video && (!is_y4m_path(outputpath) || is_dir(outputpath)))
+    {
+        fprintf(stderr, "a YUV4MPEG2 input needs a .y4m output path or - (stdout)\n");
+        return -1;
+    }
+    if (video && ngpu > 1)
+    {
+        fprintf(stderr, "a YUV4MPEG2 stream runs on one gpu\n");
+        return -1;
+    }
     for (int g : gpuid)
         if (g < 0)
         {
@@ -273,7 +422,7 @@ int main(int argc, char** argv)
             fprintf(stderr, "invalid jobs_proc thread count argument\n");
             return -1;
         }
-    if (!is_dir(outputpath))
+    if (!video && !is_dir(outputpath))
     {
         const std::string ext = imgio::lower_ext(outputpath); // format guessed from the output path, whatever -f says
         if (ext == "png") format = "png";
@@ -298,7 +447,8 @@ int main(int argc, char** argv)
 
     // collect input and output file paths
     std::vector<std::string> input_files, output_files;
-    if (is_dir(inputpath) && is_dir(outputpath))
+    if (video) input_files.push_back(inputpath), output_files.push_back(outputpath); // (one stream: run_video opens it)
+    else if (is_dir(inputpath) && is_dir(outputpath))
     {
         std::vector<std::string> names;
         if (list_files(inputpath, names) != 0) return -1;
@@ -438,6 +588,20 @@ int main(int argc, char** argv)
                         gpuid[size_t(i)], peak, nonfinite);
         }
         realsr.push_back(std::move(r));
+    }
+    if (video)
+    { // -v prints one line per window, no per-tile percent lines
+        rsr_set_progress_callback(ctxs[0], nullptr, nullptr);
+        const RealSR& r = *realsr[0];
+        int vrc = rsr_set_params(ctxs[0], r.scale, r.tilesize, r.prepadding);
+        if (vrc == RSR_OK) vrc = r.set_ratio(ctxs[0]);
+        if (vrc != RSR_OK)
+        {
+            fprintf(stderr, "%s\n", rsr_last_error(ctxs[0]));
+            return 1;
+        }
+        const int vny = out_den_y ? out_num_y : out_num, vdy = out_den_y ? out_den_y : out_den;
+        return run_video(ctxs[0], inputpath, outputpath, out_num, out_den, vny, vdy, verbose);
     }
     // one image, several GPUs: every GPU takes a share of the tile rows
     const bool split_one_image = ngpu > 1 && input_files.size() == 1;

@@ -10,6 +10,9 @@
     sr.tilesize = 200; sr.out_ratio = Fraction(3, 2); nv12_1080 = torch_io.upscale_yuv(sr, nv12_720)   # ... or at a ratio: 720p -> 1080p
     sr.tilesize = 192; sr.out_ratio_xy = (Fraction(8, 3), Fraction(9, 4)); nv12_1080 = torch_io.upscale_yuv(sr, nv12_dvd)   # ... or one per axis: 720 x 480 -> 1920 x 1080
 
+    nv12 = torch_io.pack_planes(sr, y, u, v)   # a software decoder's yuv420p / yuv420p10le planes -> the NV12 / P010 surface above, one launch ...
+    y2, u2, v2 = torch_io.unpack_planes(sr, torch_io.upscale_yuv(sr, nv12))   # ... and the result as three planes again (chroma=422 / 444 alike)
+
     y, n = torch_io.upscale_delta(sr, frame, prev_frame, y)   # video: only the tiles whose source changed run again, y is updated in place
 
     ys, n = torch_io.upscale_sequence(sr, frames)   # video, N frames known in advance: one diff, one host wait and shared launches per 16
@@ -374,6 +377,108 @@ def upscale_yuv(sr, surface, out=None, chroma=420):
         din = _describe_yuv(packed[:h], packed[h:])
     _on_current_stream(y.device, lambda st: sr.process_device_batch([din], fmt, w, h, 3, [dout], fmt, stream=st))
     return out
+
+
+# ---- three-plane frames (yuv420p / yuv422p / yuv444p, 8 and 10 bits) to the surfaces upscale_yuv takes, and back ------------------------
+def _plane_views(sr, planes, chroma, who, what):
+    """(fmt, w, h, (y, u, v)) of a three-plane frame: 2-D tensors of one dtype on the context's GPU, u and v of the chroma's size;
+    ValueError before anything is launched."""
+    if len(planes) != 3 or not all(isinstance(t, torch.Tensor) and t.dim() == 2 for t in planes):
+        raise ValueError("%s: %s must be three 2-D tensors, the planes Y, U and V" % (who, what))
+    y, u, v = planes
+    k = _CHROMA[chroma]
+    if any(t.dtype != y.dtype or t.device != y.device for t in (u, v)):
+        raise ValueError("%s: the planes of %s must have one dtype, on one device" % (who, what))
+    if y.dtype not in k.fmt:
+        raise ValueError("%s: dtype %s is not supported (uint8; uint16 / int16 with the 10-bit code in the LOW bits)" % (who, y.dtype))
+    if y.device.type != "cuda" or y.device.index != sr.gpuid:
+        raise ValueError("%s: %s is on %s, the context runs on cuda:%d" % (who, what, y.device, sr.gpuid))
+    h, w = y.shape
+    sx, sy = (1, 1) if chroma == 420 else (1, 0) if chroma == 422 else (0, 0)
+    if h < 1 or w < 1 or w & sx or h & sy or tuple(u.shape) != (h >> sy, w >> sx) or u.shape != v.shape:
+        raise ValueError("%s: y %s with u %s and v %s is no YUV 4:%s:%s frame" % (who, tuple(y.shape), tuple(u.shape), tuple(v.shape), str(chroma)[1], str(chroma)[2]))
+    return k.fmt[y.dtype], w, h, (y, u, v)
+
+
+def _rows_fit(t):
+    """Is the 2-D view t addressable by a pointer and a row pitch (stride 1 along W, rows upwards in memory, aligned to its element)?"""
+    return (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] == 1 or t.stride(0) >= t.shape[1]) and t.data_ptr() % t.element_size() == 0
+
+
+def _planes_desc(y, u, v):
+    """The rsr_planes entry (y, u, v, y_pitch, c_pitch), in bytes, of three views, or None when none describes them: rows that are not
+    contiguous, or U and V rows that are not equally far apart."""
+    if not all(_rows_fit(t) for t in (y, u, v)) or (u.shape[0] > 1 and u.stride(0) != v.stride(0)):
+        return None
+    es = y.element_size()
+    return (y.data_ptr(), u.data_ptr(), v.data_ptr(), (y.stride(0) if y.shape[0] > 1 else y.shape[1]) * es,
+            (u.stride(0) if u.shape[0] > 1 else u.shape[1]) * es)
+
+
+def _surface_desc(sr, s, chroma, who, what, fmt, w, h):
+    """The rsr_image descriptor of the w x h surface s of format fmt -- what upscale_yuv takes: a (3h / 2, w) / (2h, w) tensor or (y, uv)
+    pair, or (3, h, w) / a (y, u, v) triple at 4:4:4 --; ValueError where it is none, of another size or dtype, or fits no descriptor."""
+    try:
+        if chroma == 444:
+            sfmt, sw, sh, d = _desc444(sr, s, what)
+        else:
+            sy, suv = _planes(sr, s, what, chroma)
+            sfmt, (sh, sw), d = _CHROMA[chroma].fmt[sy.dtype], sy.shape, _describe_yuv(sy, suv)
+    except ValueError as e:
+        raise ValueError(str(e).replace("upscale_yuv", who, 1)) from None
+    if d is None:
+        raise ValueError("%s: %s is not addressable by one row pitch and a plane pitch" % (who, what))
+    if fmt is not None and (sfmt, sw, sh) != (fmt, w, h):
+        raise ValueError("%s: %s must be a surface of %d x %d in the planes' dtype" % (who, what, w, h))
+    return sfmt, sw, sh, d
+
+
+def pack_planes(sr, y, u, v, chroma=420, out=None):
+    """The three planes of a frame as a software decoder holds it -- yuv420p / yuv422p / yuv444p: uint8; their 10-bit little-endian forms:
+    uint16 / int16 with the code in the LOW bits -- as the surface upscale_yuv takes: a (3h / 2, w) tensor (chroma=420: NV12 / P010),
+    (2h, w) (422: NV16 / P210) or (3, h, w) (444).  One launch of rsr_pack_planes on torch.cuda.current_stream(): the chroma planes are
+    interleaved on the device, and every 10-bit word of a 4:2:0 / 4:2:2 frame becomes (word & 1023) << 6 -- P010 / P210 hold the code
+    high --; 4:4:4 words are copied as they are.  y (h, w); u and v (h / 2, w / 2), (h, w / 2) or (h, w).  Views with contiguous rows are
+    read in place (a crop, a padded frame: u and v with one row stride); others are made contiguous first.  out: the surface (or, as
+    upscale_yuv takes them, the pair or triple of views) to write and return instead of a new tensor.  ValueError before anything is
+    launched."""
+    _check_chroma(chroma, "pack_planes")
+    fmt, w, h, (y, u, v) = _plane_views(sr, (y, u, v), chroma, "pack_planes", "the frame")
+    if out is not None:
+        dout = _surface_desc(sr, out, chroma, "pack_planes", "out", fmt, w, h)[3]
+    else:
+        out = _new_yuv(y, w, h, chroma)
+        dout = _surface_desc(sr, out, chroma, "pack_planes", "out", fmt, w, h)[3]
+    src = _planes_desc(y, u, v)
+    if src is None:
+        y, u, v = y.contiguous(), u.contiguous(), v.contiguous()  # (kept alive by the stream ordering, like any temporary of a torch op)
+        src = _planes_desc(y, u, v)
+    _on_current_stream(y.device, lambda st: sr.pack_planes([src], [dout], fmt, w, h, stream=st))
+    return out
+
+
+def unpack_planes(sr, surface, chroma=420, out=None):
+    """The way back: the surface upscale_yuv returns -- a (3h / 2, w) / (2h, w) tensor or (y, uv) pair, (3, h, w) or a triple at
+    chroma=444 -- as the three planes (y, u, v) of a yuv420p / yuv422p / yuv444p frame, 10-bit words with the code in the LOW bits
+    (every P010 / P210 word >> 6).  One launch of rsr_unpack_planes on torch.cuda.current_stream().  out: the (y, u, v) tensors to write
+    and return: the frame's shapes and dtype, rows contiguous, u and v with one row stride (ValueError otherwise: a result is written in
+    place or not at all).  The surface is read in place and must fit a descriptor, as an out of upscale_yuv must."""
+    _check_chroma(chroma, "unpack_planes")
+    fmt, w, h, din = _surface_desc(sr, surface, chroma, "unpack_planes", "surface", None, 0, 0)
+    first = surface[0] if isinstance(surface, (tuple, list)) else surface
+    sx, sy = (1, 1) if chroma == 420 else (1, 0) if chroma == 422 else (0, 0)
+    if out is None:
+        out = (first.new_empty((h, w)), first.new_empty((h >> sy, w >> sx)), first.new_empty((h >> sy, w >> sx)))
+    elif not isinstance(out, (tuple, list)):
+        raise ValueError("unpack_planes: out must be the three tensors (y, u, v)")
+    ofmt, ow, oh, planes = _plane_views(sr, tuple(out), chroma, "unpack_planes", "out")
+    dst = _planes_desc(*planes)
+    if (ofmt, ow, oh) != (fmt, w, h) or planes[0].device != first.device:
+        raise ValueError("unpack_planes: out must be the planes of a %d x %d frame in the surface's dtype, on %s" % (w, h, first.device))
+    if dst is None:
+        raise ValueError("unpack_planes: out is not addressable by plane pointers, one luma and one chroma row pitch")
+    _on_current_stream(first.device, lambda st: sr.unpack_planes([din], [dst], fmt, w, h, stream=st))
+    return tuple(out)
 
 
 # ---- video: run only the tiles that changed -----------------------------------------------------------------------------------------------
