@@ -113,6 +113,8 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
 /* Planar YUV 4:4:4: what screen recordings, mezzanine masters and software video frameworks hold ("YUV 4:4:4" below; ids 10 and 11 stay unknown) */
 #define RSR_FMT_YUV444P   12  /* uint8  planes Y, U, V, each [h][w]; c must be 3 */
 #define RSR_FMT_YUV444P10 13  /* uint16 little-endian, the code in the LOW 10 bits (yuv444p10le), same layout */
+/* 16-bit RGB(A): what scans, raw developments and renders hold ("16-bit RGB(A)" below; ids 14 and 15 stay unknown, as do -1, 3, 6, 7, 10, 11) */
+#define RSR_FMT_U16_HWC 16    /* uint16 little-endian [h][w][c], c in {3,4}, full range 0 .. 65535 */
 /* (Mind the contrast: P010 / P210 hold code << 6, as hardware decoders write it; YUV444P10 holds the code itself, as every producer of planar 4:4:4 does.) */
 
 /* rsr_process_device with a pixel format per side: what a tensor pipeline holds (float CHW in [0,1]) goes in and comes out without a
@@ -129,7 +131,7 @@ int rsr_process_device(rsr_ctx* ctx, const void* d_in, int w, int h, int c, void
  *   Option "bgr" swaps planes 0 and 2 the way it swaps bytes 0 and 2 of a uint8 pixel.
  *   Option "out_scale" 2 / 1: d_out is (w * out_scale) x (h * out_scale) and receives the box means of those values (rsr_set_option).
  * This is rsr_process_device_batch (below) with n = 1 and tightly packed images.
- * Out of scope: RGBA in planar form and a host-pointer variant (rsr_process stays uint8 HWC). */
+ * Out of scope: RGBA in planar form.  (Host pointers: rsr_process_fmt below; rsr_process stays uint8 HWC.) */
 int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, int h, int c, void* d_out, int out_fmt, void* stream);
 
 /* RSR_FMT_NV12 / RSR_FMT_P010 on either side of rsr_process_device_fmt / rsr_process_device_batch, independently of the other side (NV12 ->
@@ -228,8 +230,49 @@ int rsr_yuv_constants(int matrix, int range, int bits, float* out, int n);
 /* Host-only (no GPU): the admission rule and the size of an output in `out_fmt` at the pair of ratios and the tile size given -- *ow = w *
  * nx / dx, *oh = h * ny / dy (either pointer may be NULL).  RSR_FMT_U8_HWC / F16_CHW / F32_CHW: exactly rsr_out_size_xy.  RSR_FMT_NV12 /
  * P010: exactly rsr_out_size_yuv_xy.  RSR_FMT_NV16 / P210: the 4:2:2 rule above.  RSR_FMT_YUV444P / YUV444P10: exactly rsr_out_size_xy (a
- * 4:4:4 surface has no parity rule).  RSR_E_ARG for an unknown format. */
+ * 4:4:4 surface has no parity rule).  RSR_FMT_U16_HWC: exactly rsr_out_size_xy.  RSR_E_ARG for an unknown format. */
 int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, int tilesize, int w, int h, int* ow, int* oh);
+
+/* ---- 16-bit RGB(A): RSR_FMT_U16_HWC in and out (no reference counterpart) -----------------------------------------------------------------
+ * The still-image sibling of the 10-bit video formats: a 16-bit scan, raw development or render goes in without losing its low byte, and the
+ * network's sub-code precision -- what keeps an upscaled gradient from banding -- leaves in integer form, also for an 8-bit source.  Either side
+ * of a call, independently of the other (U16 -> U16, U8 -> U16, U16 -> U8, U16 <-> F16_CHW / F32_CHW, any YUV format <-> U16), through
+ * rsr_process_device_fmt, _batch (windows, pitches), _masked, _sequence, rsr_diff_tiles, rsr_diff_tiles_sequence and the host call
+ * rsr_process_fmt; in every mode: TTA, "precise", "bgr", "out_scale" 4 / 2 / 1, rsr_set_out_ratio, rsr_set_out_ratio_xy.  A call with U16 on a
+ * side is never merged with concurrent calls, like the planar formats.
+ *   Layout.  uint16 [h][w][c], c in {3, 4}, native little-endian words, full range, RGB(A) order; option "bgr" swaps samples 0 and 2 as it
+ *            swaps bytes.  rsr_image: `data` and row_pitch must be multiples of 2 (RSR_E_ARG otherwise); plane_pitch is ignored.  A row is
+ *            2*w*c bytes; rsr_image_bytes = 2*w*h*c; rsr_image_span and rsr_out_size_fmt follow U8_HWC (rsr_out_size_fmt is exactly
+ *            rsr_out_size_xy).  There is no parity rule.
+ *   Input.   The network input of sample k is fp16(float(k) * fp32(1/65535)): ONE multiplication, k UNSIGNED (an int16 view of the words holds
+ *            the codes >= 32768 as negatives; the library reads uint16).  The alpha sample is skipped, as for U8_HWC.  For every byte b the
+ *            sample 257 * b gives exactly the half the uint8 path makes of b: an 8-bit image widened by x257 is the same network input.
+ *   Precision, honestly.  The network reads fp16, so the 65,536 codes land on 7,169 distinct inputs; the round trip code -> input -> code is
+ *            off by at most 16 codes (near white), against 128 codes for a hop through 8 bits.
+ *   Output.  Let d be what RSR_FMT_F32_CHW holds for the output pixel in the context's current mode, scale, ratio or pair (in [0, 1]).  The
+ *            sample is (uint16) floor(d * 65535.f + 0.5f), the product and the sum each rounded by itself (nothing is contracted).  In the
+ *            default mode d is an fp16-rounded value, spaced up to 2^-11 apart: about 32 codes near white.  Under option "precise" it is
+ *            conv_last's fp32 result: "precise" (the CLI: RSR_PRECISE=1) is the recommended companion of 16-bit output.
+ *   Alpha (c == 4).  Both sides must then be HWC -- U8 or U16, in any combination.  The bicubic x4 alpha is computed from the source's alpha
+ *            samples in SOURCE units, with the arithmetic of the uint8 path: four rows of four taps, row = ((p0 c0 + p1 c1) + p2 c2) +
+ *            p3 c3, then the four rows likewise.  A U16 source rounds every one of these products and sums by itself (fp32, nothing is
+ *            contracted); a U8 source keeps the uint8 path's own code.  Where the two depths differ ONE multiplication follows the
+ *            bicubic sum: by 257.f (U8 -> U16) or by fp32(1/257) (U16 -> U8).  Then, as ever: the clamp to [0, max] (max = 65535 for a U16
+ *            output), the box / area mean, floor(mean + 0.5).  U8 -> U8 is bit for bit what it was.
+ *   Diff.    rsr_diff_tiles / _sequence compare bytes [x0*2c, x1*2c) of the rows of the tile's source rectangle, alpha included.
+ *   Sequences.  The propagated rectangle is the tile's output rectangle, 2c bytes per pixel.
+ * conv_last leaves its planar blob and ONE more launch (postproc_tiles and its box / area siblings) writes the image: the route RGBA, TTA and
+ * YUV outputs take.  At out_scale 4 without TTA a thread makes two neighbouring pixels -- 12 bytes as three dword stores, an RGBA pair as
+ * two 8-byte stores, where the address allows, else as samples --, elsewhere one.  Option "dbg" 32768 / 65536 force one / two pixels per
+ * thread at out_scale 4 and change no byte: the LDS-staged kernels they force for uint8 images are uint8-only. */
+
+/* Host pointers for every format pair: rsr_process with a pixel format per side.  `in` and `out` are tightly packed HOST images (`out` of the
+ * size rsr_out_size_fmt / rsr_image_bytes state for the context's ratio); the call is synchronous and returns when `out` is complete.  Any
+ * pair rsr_process_device_fmt takes goes: H2D on a copy stream (pinned memory of rsr_host_alloc travels directly, pageable memory through
+ * pinned staging), the device path, D2H, one wait.  The progress callback fires as for a synchronous rsr_process_device call.  Safe next to
+ * every other call from several threads.  Never merged with concurrent calls; no tile ranges, no groups.  Every argument is checked before
+ * anything is enqueued (RSR_E_ARG; RSR_E_STATE before rsr_load).  rsr_process_fmt(U8 -> U8) writes the bytes rsr_process writes. */
+int rsr_process_fmt(rsr_ctx* ctx, const void* in, int in_fmt, int w, int h, int c, void* out, int out_fmt);
 
 /* ---- YUV 4:4:4: RSR_FMT_YUV444P / RSR_FMT_YUV444P10 in and out (no reference counterpart) -------------------------------------------------
  * Screen recordings (H.264 Hi444PP, HEVC RExt, AV1 4:4:4, lossless x264 / FFV1: subsampled chroma smears coloured text), ProRes 4444 and

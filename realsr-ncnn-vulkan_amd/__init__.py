@@ -41,6 +41,7 @@ EXPORTS = [
     "rsr_pack_planes", "rsr_unpack_planes",
     "rsr_video_open", "rsr_video_send", "rsr_video_ready", "rsr_video_receive", "rsr_video_flush", "rsr_video_reset", "rsr_video_info",
     "rsr_video_close",
+    "rsr_process_fmt",
 ]
 
 NUM_CONVS = 351  # convolutions of the default-depth model (23 RRDB blocks); a loaded model's own count is RealSR.num_convs
@@ -55,6 +56,21 @@ RSR_FMT_NV12, RSR_FMT_P010 = 4, 5
 RSR_FMT_NV16, RSR_FMT_P210 = 8, 9
 # planar YUV 4:4:4: the planes Y, U, V [h][w] one plane pitch apart; uint8, or uint16 with the 10-bit code in the LOW bits (yuv444p10le)
 RSR_FMT_YUV444P, RSR_FMT_YUV444P10 = 12, 13
+# 16-bit RGB(A): uint16 [h][w][c], c in {3, 4}, native words, full range 0 .. 65535.  RSR_FMT_U16_HWC = 16 is an attribute of this module
+# like the others (R.RSR_FMT_U16_HWC, `from realsr_ncnn_vulkan_amd import RSR_FMT_U16_HWC`), served by the module's __getattr__: the names
+# dir() lists under RSR_FMT_* stay the formats of the tests' one packed-image table (tests/pixfmt_ref.py), which has no uint16 HWC layout --
+# this format's table is tests/rgb16_ref.py.
+_FMT_U16_HWC = 16
+_LATE_FORMATS = {"RSR_FMT_U16_HWC": _FMT_U16_HWC}
+
+
+def __getattr__(name):
+    try:
+        return _LATE_FORMATS[name]
+    except KeyError:
+        raise AttributeError("module %r has no attribute %r" % (__name__, name)) from None
+
+
 RSR_SEQ_MAX = 16  # frames per rsr_process_device_sequence call
 
 
@@ -128,6 +144,7 @@ def lib():
     L.rsr_process.argtypes = [vp, vp, ip, ip, ip, vp]
     L.rsr_process_device.argtypes = [vp, vp, ip, ip, ip, vp, vp]
     L.rsr_process_device_fmt.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, vp]
+    L.rsr_process_fmt.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip]
     L.rsr_image_bytes.argtypes = [ip, ip, ip, ip]
     L.rsr_image_bytes.restype = C.c_longlong
     L.rsr_process_device_batch.argtypes = [vp, ip, C.POINTER(Image), ip, ip, ip, ip, C.POINTER(Image), ip, vp]
@@ -385,7 +402,7 @@ class RealSR:
     def out_size_fmt(self, fmt, w, h):
         """out_size for an output in pixel format `fmt` (RSR_FMT_*) at the ratio, or pair, and tile size in force: the rule of out_size for
         the RGB formats, of out_size_yuv for NV12 / P010, and for NV16 / P210 the 4:2:2 rule -- the ratio rule, and w * nx / dx and
-        tilesize * nx / dx even; the rows carry no parity rule (rsr_out_size_fmt).  YUV444P / YUV444P10: the rule of out_size, no parity at
+        tilesize * nx / dx even; the rows carry no parity rule (rsr_out_size_fmt).  YUV444P / YUV444P10 and U16_HWC: the rule of out_size, no parity at
         all.  ValueError where the engine would refuse the call."""
         r, pair = self._ratio_or_pair()
         rx, ry = (r, r) if pair is None else pair
@@ -472,6 +489,23 @@ class RealSR:
             out = np.empty((oh, ow, c), dtype=np.uint8)
         assert out.shape == (oh, ow, c) and out.dtype == np.uint8 and out.flags.c_contiguous
         self._ck(self._L.rsr_process(self._h, _p(img), w, h, c, _p(out)))
+        return out
+
+    def process_fmt(self, img, in_fmt, out_fmt, out=None):
+        """rsr_process_fmt: process() for host images in any pair of pixel formats rsr_process_device_fmt takes.  img: a C-contiguous numpy
+        array of the shape and dtype of in_fmt (format_array_spec: (h, w, c) uint8 / uint16 for the HWC formats, (3, h, w) for the planar
+        ones, (rows, w) for a semi-planar YUV surface); returns (or fills `out` with) the array of out_fmt at out_size_fmt(out_fmt, w, h)."""
+        if not isinstance(img, np.ndarray) or not img.flags.c_contiguous:
+            raise ValueError("process_fmt: img must be a C-contiguous numpy array")
+        w, h, c = format_array_dims(in_fmt, img)
+        self._push_params()
+        ow, oh = self.out_size_fmt(out_fmt, w, h)
+        shape, dtype = format_array_spec(out_fmt, ow, oh, c)
+        if out is None:
+            out = np.empty(shape, dtype=dtype)
+        if not (isinstance(out, np.ndarray) and out.shape == shape and out.dtype == dtype and out.flags.c_contiguous):
+            raise ValueError("process_fmt: out must be a C-contiguous %s array of shape %s" % (np.dtype(dtype).name, shape))
+        self._ck(self._L.rsr_process_fmt(self._h, _p(img), int(in_fmt), w, h, c, _p(out), int(out_fmt)))
         return out
 
     def process_many(self, imgs):
@@ -851,11 +885,47 @@ def selfcheck_tile(w=0, h=0):
 
 def image_bytes(fmt, w, h, c=3):
     """rsr_image_bytes (host-only): bytes of a w x h x c image in pixel format `fmt` (RSR_FMT_*; NV12: w*h*3/2, P010: 3*w*h,
-    NV16: 2*w*h, P210: 4*w*h, YUV444P: 3*w*h, YUV444P10: 6*w*h)."""
+    NV16: 2*w*h, P210: 4*w*h, YUV444P: 3*w*h, YUV444P10: 6*w*h, U16_HWC: 2*w*h*c)."""
     n = lib().rsr_image_bytes(int(fmt), int(w), int(h), int(c))
     if n < 0:
         raise RealSRError(int(n), lib().rsr_last_error(None).decode())
     return int(n)
+
+
+_FMT_HWC = {RSR_FMT_U8_HWC: np.uint8, _FMT_U16_HWC: np.uint16}
+_FMT_PLANAR = {RSR_FMT_F16_CHW: np.float16, RSR_FMT_F32_CHW: np.float32, RSR_FMT_YUV444P: np.uint8, RSR_FMT_YUV444P10: np.uint16}
+_FMT_SURFACE = {RSR_FMT_NV12: (np.uint8, 1), RSR_FMT_P010: (np.uint16, 1), RSR_FMT_NV16: (np.uint8, 0), RSR_FMT_P210: (np.uint16, 0)}  # dtype, vertical chroma shift
+
+
+def format_array_spec(fmt, w, h, c=3):
+    """(shape, dtype) of the tightly packed numpy array that holds a w x h x c image in pixel format `fmt`: (h, w, c) for the HWC formats,
+    (3, h, w) for the planar ones, (h + (h >> csy), w) for a semi-planar YUV surface (the UV rows behind the Y rows)."""
+    if fmt in _FMT_HWC:
+        return (h, w, c), np.dtype(_FMT_HWC[fmt])
+    if fmt in _FMT_PLANAR:
+        return (3, h, w), np.dtype(_FMT_PLANAR[fmt])
+    if fmt in _FMT_SURFACE:
+        dt, csy = _FMT_SURFACE[fmt]
+        return (h + (h >> csy), w), np.dtype(dt)
+    raise ValueError("unknown pixel format %r" % (fmt,))
+
+
+def format_array_dims(fmt, a):
+    """(w, h, c) of the image the array `a` holds in pixel format `fmt` (format_array_spec's inverse); ValueError for a wrong dtype or rank."""
+    if fmt in _FMT_HWC and a.ndim == 3:
+        h, w, c = a.shape
+    elif fmt in _FMT_PLANAR and a.ndim == 3 and a.shape[0] == 3:
+        (_, h, w), c = a.shape, 3
+    elif fmt in _FMT_SURFACE and a.ndim == 2:
+        csy = _FMT_SURFACE[fmt][1]
+        rows, w = a.shape
+        h, c = (rows * 2 // 3 if csy else rows // 2), 3
+    else:
+        raise ValueError("format %r does not come as an array of shape %s" % (fmt, a.shape))
+    shape, dtype = format_array_spec(fmt, w, h, c)
+    if a.shape != shape or a.dtype != dtype:
+        raise ValueError("format %r: a %d x %d x %d image is a %s array of shape %s, not %s %s" % (fmt, w, h, c, dtype.name, shape, a.dtype.name, a.shape))
+    return int(w), int(h), int(c)
 
 
 def yuv_constants(matrix=709, range_=0, bits=8):

@@ -184,6 +184,12 @@ int rsr_process_device_fmt(rsr_ctx* ctx, const void* d_in, int in_fmt, int w, in
     return ctx->e.process_device(d_in, w, h, c, d_out, static_cast<hipStream_t>(stream), stream == nullptr, in_fmt, out_fmt);
 }
 
+int rsr_process_fmt(rsr_ctx* ctx, const void* in, int in_fmt, int w, int h, int c, void* out, int out_fmt)
+{
+    if (!ctx) return RSR_E_ARG;
+    return ctx->e.process_host_fmt(in, in_fmt, w, h, c, out, out_fmt);
+}
+
 int rsr_process_device_batch(rsr_ctx* ctx, int n, const rsr_image* in, int in_fmt, int w, int h, int c, const rsr_image* out, int out_fmt, void* stream)
 {
     if (!ctx) return RSR_E_ARG;

@@ -1092,6 +1092,7 @@ int Engine::launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntile
     po.crop = prepadding * scale;
     po.nimgs = io.nimg;
     po.out_fmt = io.out_fmt;
+    po.in_fmt = io.in_fmt;
     po.c = c;
     po.out_row0 = io.out_row0;
     po.box = io.os.is_box() ? 4 / io.os.nx : 1;
@@ -1315,6 +1316,8 @@ int Engine::process_device(const void* d_in, int w, int h, int c, void* d_out, h
     if (const int rc = parity_check(fin, w, h, "input")) return rc;
     if ((fin.bits > 8 && (reinterpret_cast<uintptr_t>(d_in) & 1)) || (fout.bits > 8 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
         return fail(RSR_E_ARG, "P010 / P210 / YUV444P10 data is not aligned to its 16-bit samples");
+    if ((fin.sample > 1 && (reinterpret_cast<uintptr_t>(d_in) & 1)) || (fout.sample > 1 && (reinterpret_cast<uintptr_t>(d_out) & 1)))
+        return fail(RSR_E_ARG, "16-bit RGB(A) data is not aligned to its samples");
     const bool u8 = in_fmt == RSR_FMT_U8_HWC && out_fmt == RSR_FMT_U8_HWC;
     if (!user_stream && sync && u8) // (a call with a float image on either side is not merged: it runs as a batch of its own, below)
     { // a small image: merged with whatever other calls hand in meanwhile (Engine::submit_merged)
@@ -1470,6 +1473,7 @@ int image_layout(int fmt, int w, int h, int c, long long row_pitch, long long pl
         pp = plane_pitch ? plane_pitch : h * rp;
         if (rp % es || pp % es) return Engine::fail(RSR_E_ARG, "pitch is not a multiple of the element size");
     }
+    else if (rp % f.sample) return Engine::fail(RSR_E_ARG, "row pitch is not a multiple of the sample size");
     *row = rp;
     *plane = pp;
     return RSR_OK;
@@ -2243,6 +2247,82 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
             pool.copy(out + off, static_cast<const char*>(L->h_out) + (k & 1) * half, n, copy_threads);
         }
     }
+    return RSR_OK;
+}
+
+// rsr_process_fmt: process_host for any pair of pixel formats -- tightly packed HOST images, the device path of process_device between an
+// upload and a download.  The call owns a lane like process_host: H2D on the lane's copy stream, the tile batches on the compute stream
+// behind ev_in, D2H on the copy stream behind ev_done, ONE wait at the end.  Pinned caller memory travels directly, pageable memory through
+// the lane's pinned staging (whole images: the call is thin -- no chunked download, no tile range, no merging, no early half).
+int Engine::process_host_fmt(const void* in, int in_fmt, int w, int h, int c, void* out, int out_fmt)
+{
+    if (!in || !out || w < 1 || h < 1 || w > (1 << 24) || h > (1 << 24) || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
+    const PixFmt fin = pix_fmt(in_fmt, c), fout = pix_fmt(out_fmt, c);
+    for (const PixFmt* f : {&fin, &fout})
+        if (const int rc = fmt_check(*f, c, "the planar float and the YUV formats come with c == 3 only")) return rc;
+    if (const int rc = parity_check(fin, w, h, "input")) return rc;
+    int T = 0;
+    OutRatio os; // the output ratio in force when the call came in (the size of `out`)
+    { // state checks BEFORE anything is enqueued on behalf of this call
+        std::lock_guard<std::mutex> lk(mu);
+        os = out_ratio;
+        if (const int rc = admit(out_fmt, w, h, os, true)) return rc;
+        T = tilesize;
+    }
+    const size_t nin = size_t(fin.rows(h)) * size_t(w) * size_t(fin.es);
+    const size_t nout = size_t(fout.rows(os.of_y(h))) * size_t(os.of_x(w)) * size_t(fout.es);
+    Lane* L = acquire_lane();
+    struct Release // nothing of this call may be in flight when the lane, and with it the caller's `in` / `out`, is handed back (process_host)
+    {
+        Engine* e;
+        Lane* l;
+        bool done_recorded = false;
+        ~Release()
+        {
+            if (l->copy) (void)hipStreamSynchronize(l->copy);
+            if (done_recorded) (void)hipEventSynchronize(l->ev_done);
+            e->release_lane(l);
+        }
+    } guard{this, L};
+    HIP_TRY(hipSetDevice(device));
+    if (!L->copy)
+    {
+        HIP_TRY(hipStreamCreateWithFlags(&L->copy, hipStreamNonBlocking));
+        for (hipEvent_t* e : {&L->ev_in, &L->ev_done, &L->ev_half, &L->ev_chunk[0], &L->ev_chunk[1]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    int rc;
+    if ((rc = ensure(L->d_in, nin)) != RSR_OK || (rc = ensure(L->d_out, nout)) != RSR_OK) return rc;
+    L->in_bytes.store(L->d_in.bytes, std::memory_order_relaxed);
+    L->out_bytes.store(L->d_out.bytes, std::memory_order_relaxed);
+    const bool pinned_out = is_pinned_host(out);
+    if (!pinned_out && (rc = ensure_pinned(L->h_out, L->h_out_bytes, nout)) != RSR_OK) return rc; // (before anything is enqueued)
+    const void* src = in;
+    if (!is_pinned_host(in))
+    {
+        if ((rc = ensure_pinned(L->h_in, L->h_in_bytes, nin)) != RSR_OK) return rc;
+        pool.copy(L->h_in, in, nin, copy_threads);
+        src = L->h_in;
+    }
+    HIP_TRY(hipMemcpyAsync(L->d_in.p, src, nin, hipMemcpyHostToDevice, L->copy));
+    HIP_TRY(hipEventRecord(L->ev_in, L->copy));
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!loaded || scale != 4 || tilesize != T || out_ratio != os)
+            return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the guard drains the upload)
+        HIP_TRY(hipStreamWaitEvent(stream, L->ev_in, 0));
+        rc = enqueue_images(BatchIO(L->d_in.p, L->d_out.p, w, h, c, in_fmt, out_fmt, os), 0, -1, 0, nullptr, stream);
+        if (rc != RSR_OK)
+        {
+            (void)hipStreamSynchronize(stream); // kernels of this call that did get enqueued use the lane buffers
+            return rc;
+        }
+        HIP_TRY(hipEventRecord(L->ev_done, stream));
+        guard.done_recorded = true;
+    }
+    HIP_TRY(hipStreamWaitEvent(L->copy, L->ev_done, 0));
+    HIP_TRY(hipMemcpyAsync(pinned_out ? out : L->h_out, L->d_out.p, nout, hipMemcpyDeviceToHost, L->copy));
+    HIP_TRY(hipStreamSynchronize(L->copy));
+    if (!pinned_out) pool.copy(out, L->h_out, nout, copy_threads);
     return RSR_OK;
 }
 

@@ -441,6 +441,8 @@ struct Engine
     // only the output rectangles of
     // those tiles are written
     int process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, int tile0 = 0, int tile1 = -1);
+    // host images of any format pair process_device takes, tightly packed (include/realsr_hip.h rsr_process_fmt); never merged, whole images only
+    int process_host_fmt(const void* in, int in_fmt, int w, int h, int c, void* out, int out_fmt);
     int net_forward(const uint16_t* in, int w, int h, uint16_t* out, float* out32 = nullptr); // out32: the fp32 result (precise mode only)
     // out = act(conv + b); with s1 != 0: v = s1*(conv + b) [+ in[0:cout] when own_res] [, v = s2*v + res when res]
     // precise form (in_lo / res_lo / out_lo, any may be null): the hi + lo / 2048 residual stream of ConvArgs::precise
@@ -480,8 +482,11 @@ struct Engine
     {
         return PlaneSrc{static_cast<const char*>(ws[buf].p) + layout().plane_off(buf, plane), layout().slot_stride(buf), layout().plane_bytes(buf)};
     }
-    // no TTA merge / alpha channel / box reduction / YUV surface needs the planar blob (kDbgNoFusedLast: off)
-    bool conv_last_writes_image(int c, int out_fmt) const { return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && !(dbg & kDbgNoFusedLast); }
+    // no TTA merge / alpha channel / box reduction / YUV surface / uint16 image needs the planar blob (kDbgNoFusedLast: off)
+    bool conv_last_writes_image(int c, int out_fmt) const
+    {
+        return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && out_fmt != kFmtU16 && !(dbg & kDbgNoFusedLast);
+    }
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).
     // io: null = conv_last leaves the planar OUT3 blob (the hooks below; with an io, a TTA or RGBA batch gets it too).

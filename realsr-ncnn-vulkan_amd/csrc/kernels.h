@@ -47,22 +47,26 @@ constexpr int kFmtNV16 = 8, kFmtP210 = 9;
 // yuv444p / yuv444p10le): three full planes Y, U, V [h][w] one plane pitch apart -- the LAYOUT of the planar float formats with a YUV
 // colour model.  uint8 codes, or uint16 words that hold a 10-bit code in their LOW bits.  No pairs, no quads: w and h are any.
 constexpr int kFmtYUV444P = 12, kFmtYUV444P10 = 13;
+// 16-bit RGB(A), what scans, raw developments and renders hold (RSR_FMT_U16_HWC): the LAYOUT of the uint8 image with uint16 samples, native
+// little-endian words, full range 0 .. 65535, c = 3 or 4.  `data` and the row pitch are multiples of 2.
+constexpr int kFmtU16 = 16;
 
 // What a pixel format IS, said once: sizes, parity rules, admission rules and byte rectangles on the host, the rectangle selection of the
 // diff kernel on the device, all read these fields.  A new format is one more case of pix_fmt.
 struct PixFmt
 {
-    int es;             // bytes of one element of a row: c for uint8 HWC, elsewhere of one sample / half / float; 0 = no such format
-    int planes;         // planes addressed through the plane pitch: 1 (uint8 HWC), 2 (Y, then UV) or 3
+    int es;             // bytes of one element of a row: c (2 c) for uint8 (uint16) HWC, elsewhere of one sample / half / float; 0 = no such format
+    int planes;         // planes addressed through the plane pitch: 1 (uint8 / uint16 HWC), 2 (Y, then UV) or 3
     bool pairs;         // plane 1 holds interleaved (U, V) pairs (the semi-planar surfaces: the geometry behind the pair / quad units) ...
     int csx, csy;       // ... the chroma shift of that plane along x and y: 1, 1 at 4:2:0; 1, 0 at 4:2:2; 0, 0 everywhere else
     int bits;           // of a Y'CbCr code (the colour model: YuvCoef, the decode in front of the network, the encode behind conv_last); 0 = RGB
     bool high;          // a 10-bit code sits in the HIGH bits of its 16-bit word (code << 6), not in the low ones
     int cmax;           // channel counts admitted: 3 .. cmax
     const char* family; // as the messages name it: "YUV 4:2:0", "YUV 4:2:2", else ""
+    int sample = 1;     // bytes of one sample of an interleaved one-plane image (es = c * sample): 1 uint8 HWC, 2 uint16 HWC
     constexpr bool known() const { return es != 0; }
     constexpr bool takes(int c) const { return c >= 3 && c <= cmax; }
-    constexpr int align() const { return planes == 1 ? 1 : es; }                            // what `data` and the pitches of a descriptor must be multiples of
+    constexpr int align() const { return planes == 1 ? sample : es; }                           // what `data` and the pitches of a descriptor must be multiples of
     constexpr long long rows(long long h) const { return h + (planes - 1) * (h >> csy); } // rows of all planes of an image h rows high, each w * es bytes
     constexpr bool odd(long long w, long long h) const { return ((w & csx) | (h & csy)) != 0; } // w or h breaks the parity rule of a subsampled axis
 };
@@ -79,6 +83,7 @@ constexpr __host__ __device__ PixFmt pix_fmt(int fmt, int c = 3)
     case kFmtP210: return {2, 2, true, 1, 0, 10, true, 3, "YUV 4:2:2"};
     case kFmtYUV444P: return {1, 3, false, 0, 0, 8, false, 3, ""};
     case kFmtYUV444P10: return {2, 3, false, 0, 0, 10, false, 3, ""};
+    case kFmtU16: return {2 * c, 1, false, 0, 0, 0, false, 4, "", 2};
     default: return {0, 0, false, 0, 0, 0, false, 0, ""};
     }
 }
@@ -353,6 +358,7 @@ struct PostArgs
     int tilesize;
     int bgr;
     int variant; // 0 default (LDS-staged under TTA, else one thread per pixel), 1 per-pixel (engine dbg kDbgPrePostVar1), 2 LDS-staged (kDbgPrePostVar2)
+                 // (a uint16 HWC image at out_scale 4: 1 one pixel per thread, 2 two neighbouring pixels, 0 two without TTA and one with)
                  // (a planar 4:4:4 surface: 1 one pixel per thread, 2 two neighbouring pixels, 0 two at out_scale 4 and one elsewhere --
                  // with_pixels_per_thread)
     // Box-reduced output (engine option "out_scale"): 0 / 1 = the x4 image as above; 2 / 4 = every K x K box of x4 pixels, each clamped
@@ -374,6 +380,7 @@ struct PostArgs
     // ... likewise: the chroma siting (engine option "yuv_siting": 0 centre, 1 left, 2 top-left).  The sited chroma filters clamp at the
     // first column / row of a TILE's rectangle; that is quad column / row 0 of the tile's own grid (BaseTile::out_*), so nothing else travels.
     int siting;
+    int in_fmt; // c == 4: what in_imgs are made of, kFmtU8 or kFmtU16 (alpha_bicubic reads their samples)
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 

@@ -4,6 +4,8 @@
 //   postproc_tiles[_lds]   realsr_postproc{,_tta}.comp equivalent, writes the uint8 HWC image (or a planar fp16 / fp32 one)
 //                          (_lds: rows staged in LDS, dword loads / 1-KiB stores, transposed TTA variants through an LDS tile;
 //                          chosen per launch by measurement: launch_*_tiles)
+//   preproc_tiles<uint16_t> / postproc_tiles<., uint16_t> / postproc_tiles_u16x2   a 16-bit RGB(A) image (kFmtU16) as the source / destination;
+//                          the box and area kernels take uint16_t as their TO alike
 //   postproc_tiles_box     the image box-reduced to x2 / x1 (out_scale)
 //   postproc_tiles_area    the image area-averaged to any other ratio, or to a ratio per axis (rsr_set_out_ratio, rsr_set_out_ratio_xy)
 //   preproc_tiles<., true> an NV12 / P010 (4:2:0) or NV16 / P210 (4:2:2) surface as the source (YUV -> RGB inside the kernel)
@@ -215,7 +217,7 @@ __device__ __forceinline__ void tta_dest(int k, int gx, int gy, int tw, int th, 
 // One thread per padded-tile pixel; writes the 32-channel fp16 input plane(s) (channels 3..31 = 0).
 // The band-relative coordinates of the shader (crop_x/crop_y/pad) are folded into x_org/y_org:
 // reflecting against the band equals reflecting against the image (engine.cpp explains why).
-// SRC: what the caller's image is made of -- uint8_t (HWC), or _Float16 / float: planar [3][ih][iw] in [0, 1].  A half IS the network
+// SRC: what the caller's image is made of -- uint8_t (HWC), uint16_t (HWC, YUV = false), or _Float16 / float: planar [3][ih][iw] in [0, 1].  A half IS the network
 // input (the uint8 path makes fp16(float(k) * (1/255.f)) of byte k: those halfs give that path's input exactly); a float is rounded to
 // fp16, to nearest even.  Lanes run along x: the three plane reads of a wave are contiguous.  Rows are PreArgs::pitch bytes apart, planes
 // PreArgs::plane: the reflected (x, y) is an index into the image, never into the surface around it.
@@ -251,6 +253,14 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
     {
         const uint8_t* p = a.imgs[im] + (long long)y * a.pitch[im] + x * a.c;
         const float norm_val = 1 / 255.f;
+        v0[0] = (_Float16)((float)p[i0] * norm_val);
+        v0[1] = (_Float16)((float)p[1] * norm_val);
+        v0[2] = (_Float16)((float)p[i2] * norm_val);
+    }
+    else if constexpr (std::is_same<SRC, uint16_t>::value)
+    { // uint16 HWC (kFmtU16): fp16(float(k) * (1 / 65535.f)) of the unsigned word k -- for k = 257 b exactly the half the uint8 path makes of byte b
+        const uint16_t* p = reinterpret_cast<const uint16_t*>(a.imgs[im] + (long long)y * a.pitch[im]) + x * a.c;
+        const float norm_val = 1 / 65535.f;
         v0[0] = (_Float16)((float)p[i0] * norm_val);
         v0[1] = (_Float16)((float)p[1] * norm_val);
         v0[2] = (_Float16)((float)p[i2] * norm_val);
@@ -393,6 +403,14 @@ static void with_image_type(int fmt, F f)
 {
     if (fmt == kFmtF16) f(_Float16{});
     else if (fmt == kFmtF32) f(float{});
+    else if (fmt == kFmtU16) f(uint16_t{});
+    else f(uint8_t{});
+}
+// f(T{}) with T = the sample type of the RGBA source image the alpha of a c == 4 launch is read from (PostArgs::in_fmt)
+template <typename F>
+static void with_alpha_type(const PostArgs& a, F f)
+{
+    if (a.c == 4 && a.in_fmt == kFmtU16) f(uint16_t{});
     else f(uint8_t{});
 }
 template <typename F>
@@ -433,6 +451,7 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
             });
         else if (a.fmt == kFmtF16) hipLaunchKernelGGL(preproc_tiles<_Float16>, grid, block, 0, st, a);
         else if (a.fmt == kFmtF32) hipLaunchKernelGGL(preproc_tiles<float>, grid, block, 0, st, a);
+        else if (a.fmt == kFmtU16) hipLaunchKernelGGL(preproc_tiles<uint16_t>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(preproc_tiles<uint8_t>, grid, block, 0, st, a);
         return;
     }
@@ -447,6 +466,43 @@ __device__ __forceinline__ uint8_t post_store(float v)
     v = floorf(v + 0.5f);
     v = fminf(fmaxf(v, 0.f), 255.f);
     return (uint8_t)v;
+}
+
+// An image of interleaved integer samples (uint8 / uint16 HWC), as opposed to a planar float one: the TO of the post kernels.
+template <typename T> constexpr bool is_hwc = std::is_integral<T>::value;
+
+// The uint16 sample (kFmtU16) of d, what RSR_FMT_F32_CHW holds for the pixel, already in [0, 1]: floor(d * 65535 + 0.5), the product and the
+// sum rounded by themselves.
+__device__ __forceinline__ uint16_t post_store16(float d) { return (uint16_t)floorf(add_rn(mul_rn(d, 65535.f), 0.5f)); }
+// The colour sample of an HWC image from the value v the uint8 conversion sees (not clamped) ...
+template <typename TO>
+__device__ __forceinline__ TO hwc_sample(float v)
+{
+    if constexpr (sizeof(TO) == 1) return post_store(v * 255.f);
+    else return post_store16(fminf(fmaxf(v, 0.f), 1.f));
+}
+// ... and from a value d in [0, 1] (the box mean, the area average)
+template <typename TO>
+__device__ __forceinline__ TO hwc_sample01(float d)
+{
+    if constexpr (sizeof(TO) == 1) return post_store(d * 255.f);
+    else return post_store16(d);
+}
+// Alpha: the bicubic value v in the units of the SOURCE's samples (TA) becomes one in the units of the destination's (TO) -- where the
+// depths differ, ONE multiplication by 257.f or by fp32(1 / 257) -- then the clamp to [0, max] (alpha_max) and floor(mean + 0.5) (alpha_store).
+template <typename TO, typename TA>
+__device__ __forceinline__ float alpha_units(float v)
+{
+    if constexpr (sizeof(TO) > sizeof(TA)) return mul_rn(v, 257.f);
+    else if constexpr (sizeof(TO) < sizeof(TA)) return mul_rn(v, 1 / 257.f);
+    else return v;
+}
+template <typename TO> constexpr float alpha_max = sizeof(TO) == 1 ? 255.f : 65535.f;
+template <typename TO>
+__device__ __forceinline__ TO alpha_store(float v)
+{
+    if constexpr (sizeof(TO) == 1) return post_store(v);
+    else return (uint16_t)fminf(fmaxf(floorf(v + 0.5f), 0.f), 65535.f);
 }
 
 // The planar float destinations (PostArgs::out_fmt): the value the uint8 conversion sees, clamped to [0, 1] -- so that
@@ -481,10 +537,19 @@ __device__ __forceinline__ void cubic_coeffs(int w, int outw, int dx, int& sx, f
 
 __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-// The bicubic x4 alpha value (0..255 units, not clamped) of a tile's kept rectangle -- realsr.cpp:431-442, realsr_preproc.comp:79-88 (crop),
-// realsr_postproc.comp:58-61 -- from the coefficient sets cubic_coeffs made for its column (bx, cx) and row (by, cy): four rows of four
-// taps of the RGBA source image, indices clamped to the rectangle.  postproc_tiles, postproc_tiles_lds, postproc_tiles_box and
-// postproc_tiles_area; a kernel that needs one row's coefficients for several pixels makes them once, at its call site.
+// The bicubic x4 alpha value (in the units of the source's samples TA: 0..255, or 0..65535 of a uint16 image; not clamped) of a tile's kept
+// rectangle -- realsr.cpp:431-442, realsr_preproc.comp:79-88 (crop), realsr_postproc.comp:58-61 -- from the coefficient sets cubic_coeffs made
+// for its column (bx, cx) and row (by, cy): four rows of four taps of the RGBA source image, indices clamped to the rectangle.
+// postproc_tiles, postproc_tiles_lds, postproc_tiles_box and postproc_tiles_area; a kernel that needs one row's coefficients for several
+// pixels makes them once, at its call site.
+// A uint8 source keeps the expression it always had (the compiler contracts it as it likes: a sum of four 20-bit products barely rounds).
+// A uint16 source has 16 more bits to lose, so its sums are pinned: ((p0 c0 + p1 c1) + p2 c2) + p3 c3, every product and sum rounded by
+// itself (dot4_rn) -- the definition of include/realsr_hip.h, which tests/rgb16_ref.py restates.
+__device__ __forceinline__ float dot4_rn(float p0, float p1, float p2, float p3, const float (&c)[4])
+{
+    return add_rn(add_rn(add_rn(mul_rn(p0, c[0]), mul_rn(p1, c[1])), mul_rn(p2, c[2])), mul_rn(p3, c[3]));
+}
+template <typename TA = uint8_t>
 __device__ __forceinline__ float alpha_bicubic(const PostArgs& a, const BaseTile& t, int im, int bx, const float (&cx)[4], int by, const float (&cy)[4])
 {
     const int aw = t.out_w / 4, ah = t.out_h / 4;
@@ -494,11 +559,15 @@ __device__ __forceinline__ float alpha_bicubic(const PostArgs& a, const BaseTile
     for (int j = 0; j < 4; j++)
     {
         const int yy = ay0 + clampi(by - 1 + j, ah);
-        const uint8_t* rp = a.in_imgs[im] + (long long)yy * a.in_pitch[im] + ax0 * 4 + 3;
-        rows[j] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
-                  (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
+        const TA* rp = reinterpret_cast<const TA*>(a.in_imgs[im] + (long long)yy * a.in_pitch[im]) + ax0 * 4 + 3;
+        if constexpr (sizeof(TA) != 1)
+            rows[j] = dot4_rn((float)rp[clampi(bx - 1, aw) * 4], (float)rp[clampi(bx, aw) * 4], (float)rp[clampi(bx + 1, aw) * 4], (float)rp[clampi(bx + 2, aw) * 4], cx);
+        else
+            rows[j] = (float)rp[clampi(bx - 1, aw) * 4] * cx[0] + (float)rp[clampi(bx, aw) * 4] * cx[1] +
+                      (float)rp[clampi(bx + 1, aw) * 4] * cx[2] + (float)rp[clampi(bx + 2, aw) * 4] * cx[3];
     }
-    return rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
+    if constexpr (sizeof(TA) != 1) return dot4_rn(rows[0], rows[1], rows[2], rows[3], cy);
+    else return rows[0] * cy[0] + rows[1] * cy[1] + rows[2] * cy[2] + rows[3] * cy[3];
 }
 
 // K contiguous blob elements, K-element aligned: ONE 4- / 8-byte (fp16) or 8- / 16-byte (fp32) load.
@@ -598,8 +667,9 @@ __device__ __forceinline__ void merged_block(const TP* b, long long ss, int w, i
 // realsr_postproc.comp:47-89 and realsr_postproc_tta.comp:54-110 for a batch of tiles.
 // One thread per output pixel of the tile's un-padded x4 rectangle.
 // TP: element type of the planar blob: _Float16 (the reference's `output` blob) or float (precise mode)
-// TO: element type of the image: uint8_t (HWC), or _Float16 / float (planar [3][out_hs][out_ws], RGB only: post_store_planar)
-template <typename TP, typename TO>
+// TO: element type of the image: uint8_t / uint16_t (HWC), or _Float16 / float (planar [3][out_hs][out_ws], RGB only: post_store_planar)
+// TA: sample type of the RGBA source image the alpha is read from (c == 4; uint8_t or uint16_t, whatever TO is)
+template <typename TP, typename TO, typename TA = uint8_t>
 __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -628,24 +698,27 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
             v[q] = c[0][0];
         }
     }
-    if constexpr (sizeof(TO) != 1)
+    if constexpr (!is_hwc<TO>)
     {
         uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im] + (long long)(t.out_x + gx) * (int)sizeof(TO);
         post_store_planar<TO>(o, a.out_plane[im], a.bgr, v);
         return;
     }
-    uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im] + (t.out_x + gx) * a.c;
-    const uint8_t r = post_store(v[0] * 255.f), g = post_store(v[1] * 255.f), bl = post_store(v[2] * 255.f);
-    o[a.bgr ? 2 : 0] = r;
-    o[1] = g;
-    o[a.bgr ? 0 : 2] = bl;
-    if (a.c == 4)
+    else
     {
-        int bx, by;
-        float cx[4], cy[4];
-        cubic_coeffs(t.out_w / 4, t.out_w, gx, bx, cx);
-        cubic_coeffs(t.out_h / 4, t.out_h, gy, by, cy);
-        o[3] = post_store(alpha_bicubic(a, t, im, bx, cx, by, cy));
+        TO* o = reinterpret_cast<TO*>(a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im]) + (t.out_x + gx) * a.c;
+        const TO r = hwc_sample<TO>(v[0]), g = hwc_sample<TO>(v[1]), bl = hwc_sample<TO>(v[2]);
+        o[a.bgr ? 2 : 0] = r;
+        o[1] = g;
+        o[a.bgr ? 0 : 2] = bl;
+        if (a.c == 4)
+        {
+            int bx, by;
+            float cx[4], cy[4];
+            cubic_coeffs(t.out_w / 4, t.out_w, gx, bx, cx);
+            cubic_coeffs(t.out_h / 4, t.out_h, gy, by, cy);
+            o[3] = alpha_store<TO>(alpha_units<TO, TA>(alpha_bicubic<TA>(a, t, im, bx, cx, by, cy)));
+        }
     }
 }
 
@@ -767,6 +840,83 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
     }
 }
 
+// postproc_tiles for a uint16 image with TWO neighbouring pixels per thread (the default without TTA; PostArgs::variant 1 / 2 force one / two
+// pixels; bytes equal to postproc_tiles<., uint16_t>): the pair's 12 bytes (C = 3) leave as three dword stores, its 16 bytes (C = 4) as two 8-byte stores, where
+// the address allows -- a tile's rectangle starts on a multiple of 4 pixels, so only the image's own base and row pitch decide --, else
+// as samples.  The blob's two elements are ONE load (the kept rectangle and the crop are multiples of 4: the run is 2-aligned).
+template <typename TP, int C, typename TA = uint8_t>
+__global__ __launch_bounds__(256) void postproc_tiles_u16x2(const PostArgs a)
+{
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int gx = (blockIdx.x * 64 + (threadIdx.x & 63)) * 2;
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= t.out_w || gy >= t.out_h) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const long long cstep = (long long)w * h;
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    const int sx = gx + a.crop, sy = gy + a.crop;
+    unsigned s[3][2]; // [channel of the blob][pixel]
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+    {
+        float v[2];
+        if (!a.tta) load_run<TP, 2>(b0 + q * cstep + (long long)sy * w + sx, v);
+        else
+        {
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+            {
+                float c[1][1];
+                tta_gather<TP, 1>(b0 + q * cstep, ss, w, h, sx + i, sy, 1, c);
+                v[i] = c[0][0];
+            }
+        }
+        s[q][0] = hwc_sample<uint16_t>(v[0]), s[q][1] = hwc_sample<uint16_t>(v[1]);
+    }
+    const unsigned f0 = a.bgr ? s[2][0] : s[0][0], l0 = a.bgr ? s[0][0] : s[2][0], f1 = a.bgr ? s[2][1] : s[0][1], l1 = a.bgr ? s[0][1] : s[2][1];
+    uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im] + (long long)(t.out_x + gx) * (2 * C);
+    if constexpr (C == 3)
+    {
+        if (!(reinterpret_cast<uintptr_t>(o) & 3))
+        {
+            unsigned* d = reinterpret_cast<unsigned*>(o);
+            d[0] = f0 | (s[1][0] << 16), d[1] = l0 | (f1 << 16), d[2] = s[1][1] | (l1 << 16);
+        }
+        else
+        {
+            unsigned short* d = reinterpret_cast<unsigned short*>(o);
+            d[0] = f0, d[1] = s[1][0], d[2] = l0, d[3] = f1, d[4] = s[1][1], d[5] = l1;
+        }
+    }
+    else
+    {
+        int by;
+        float cy[4];
+        cubic_coeffs(t.out_h / 4, t.out_h, gy, by, cy);
+        unsigned al[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+        {
+            int bx;
+            float cx[4];
+            cubic_coeffs(t.out_w / 4, t.out_w, gx + i, bx, cx);
+            al[i] = alpha_store<uint16_t>(alpha_units<uint16_t, TA>(alpha_bicubic<TA>(a, t, im, bx, cx, by, cy)));
+        }
+        if (!(reinterpret_cast<uintptr_t>(o) & 7))
+        {
+            uint2* d = reinterpret_cast<uint2*>(o);
+            d[0] = make_uint2(f0 | (s[1][0] << 16), l0 | (al[0] << 16)), d[1] = make_uint2(f1 | (s[1][1] << 16), l1 | (al[1] << 16));
+        }
+        else
+        {
+            unsigned short* d = reinterpret_cast<unsigned short*>(o);
+            d[0] = f0, d[1] = s[1][0], d[2] = l0, d[3] = al[0], d[4] = f1, d[5] = s[1][1], d[6] = l1, d[7] = al[1];
+        }
+    }
+}
+
 // ---- box-reduced output (engine option "out_scale" 2 / 1: PostArgs::box = K = 2 / 4) ----------------------------------------
 // The fp32 mean of a K x K box c[y][x] in the fixed order of include/realsr_hip.h ("out_scale"): pairs along x, then pairs of rows.
 // Plain adds and one multiplication by a power of two behind them: nothing a contraction could change.
@@ -788,8 +938,9 @@ __device__ __forceinline__ float box_mean(const float (&c)[K][K])
 // kept x4 rectangle starts and ends on multiples of 4 (BaseTile::out_*), so no box crosses a tile; BaseTile stays in x4 units and is
 // divided by K here.  Lanes run along x.  The K elements a thread needs of a blob row are contiguous and K-aligned (crop, the row
 // length 4 * tw and the plane size are multiples of 4): merged_block fetches each run with one load.
-// ALPHA: the uint8 image is RGBA (PostArgs::c == 4; a kernel of its own: the bicubic's registers stay out of the RGB path).
-template <typename TP, typename TO, int K, bool ALPHA>
+// ALPHA: the uint8 / uint16 image is RGBA (PostArgs::c == 4; a kernel of its own: the bicubic's registers stay out of the RGB path); TA the
+// sample type of the RGBA source.
+template <typename TP, typename TO, int K, bool ALPHA, typename TA = uint8_t>
 __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -802,8 +953,8 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
     const int sx = gx * K + a.crop, sy = gy * K + a.crop; // first x4 pixel of the box, in the blob
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const long long ss = a.slot_stride / (long long)sizeof(TP);
-    constexpr int es = sizeof(TO) == 1 ? 1 : (int)sizeof(TO);
-    uint8_t* const o = a.outs[im] + ((t.out_y - a.out_row0) / K + gy) * (long long)a.out_pitch[im] + (long long)(t.out_x / K + gx) * (sizeof(TO) == 1 ? a.c : es);
+    constexpr int es = (int)sizeof(TO);
+    uint8_t* const o = a.outs[im] + ((t.out_y - a.out_row0) / K + gy) * (long long)a.out_pitch[im] + (long long)(t.out_x / K + gx) * (is_hwc<TO> ? a.c * es : es);
 #pragma unroll 1 // (one channel at a time: unrolled, the loads of all three are hoisted to the top and cost three times the registers)
     for (int q = 0; q < 3; q++)
     {
@@ -811,8 +962,8 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
         merged_block<TP, K>(b0 + q * cstep, ss, w, h, sx, sy, a.tta, c);
         const float d = box_mean<K>(c); // in [0, 1] like its sixteen / four terms
         const int qo = a.bgr ? 2 - q : q;
-        if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)d;
-        else o[qo] = post_store(d * 255.f);
+        if constexpr (!is_hwc<TO>) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)d;
+        else reinterpret_cast<TO*>(o)[qo] = hwc_sample01<TO>(d);
     }
     if constexpr (ALPHA)
     { // alpha: the box mean of postproc_tiles' bicubic x4 value, each clamped to [0, 255] first; two box rows per turn: (s0 + s1) [+ (s2 + s3)]
@@ -834,8 +985,8 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
                     int bx;
                     float cx[4];
                     cubic_coeffs(t.out_w / 4, t.out_w, gx * K + i, bx, cx);
-                    const float av = alpha_bicubic(a, t, im, bx, cx, by, cy);
-                    al[i] = fminf(fmaxf(av, 0.f), 255.f);
+                    const float av = alpha_units<TO, TA>(alpha_bicubic<TA>(a, t, im, bx, cx, by, cy));
+                    al[i] = fminf(fmaxf(av, 0.f), alpha_max<TO>);
                 }
                 if constexpr (K == 2) s2[jj2] = al[0] + al[1];
                 else s2[jj2] = (al[0] + al[1]) + (al[2] + al[3]);
@@ -843,7 +994,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
             const float tp = s2[0] + s2[1];
             tot = p == 0 ? tp : tot + tp;
         }
-        o[3] = post_store(tot * (K == 2 ? 0.25f : 0.0625f));
+        reinterpret_cast<TO*>(o)[3] = alpha_store<TO>(tot * (K == 2 ? 0.25f : 0.0625f));
     }
 }
 
@@ -853,6 +1004,10 @@ static void launch_postproc_box(const PostArgs& a, int max_ow, int max_oh, hipSt
     const dim3 grid((max_ow / K + 63) / 64, (max_oh / K + 3) / 4, a.ntiles), block(256);
     if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_box<TP, _Float16, K, false>), grid, block, 0, st, a);
     else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_box<TP, float, K, false>), grid, block, 0, st, a);
+    else if (a.out_fmt == kFmtU16 && a.c == 4)
+        with_alpha_type(a, [&](auto ta) { hipLaunchKernelGGL((postproc_tiles_box<TP, uint16_t, K, true, decltype(ta)>), grid, block, 0, st, a); });
+    else if (a.out_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_box<TP, uint16_t, K, false>), grid, block, 0, st, a);
+    else if (a.c == 4 && a.in_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, true, uint16_t>), grid, block, 0, st, a);
     else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, false>), grid, block, 0, st, a);
 }
@@ -910,8 +1065,9 @@ __device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, in
 // rectangle, area_pixel per channel.  A tile's kept x4 rectangle starts on a multiple of L grid units (the engine refuses the call
 // otherwise: tilesize * n is a multiple of d, on each axis with its own n / d), so the tile's own coordinates are the image's and no footprint crosses a tile.  Lanes run
 // along x, so a wave's loads of one tap row fall into a few cache lines.  One channel at a time, as in the box kernel.
-// ALPHA: PostArgs::c == 4, the bicubic x4 alpha, clamped to [0, 255], under the same weights, order and constant.
-template <typename TP, typename TO, bool ALPHA>
+// ALPHA: PostArgs::c == 4, the bicubic x4 alpha, clamped to [0, 255] ([0, 65535] of a uint16 image), under the same weights, order and
+// constant; TA the sample type of the RGBA source.
+template <typename TP, typename TO, bool ALPHA, typename TA = uint8_t>
 __global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -924,16 +1080,16 @@ __global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
     const long long cstep = (long long)w * h;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const long long ss = a.slot_stride / (long long)sizeof(TP);
-    constexpr int es = sizeof(TO) == 1 ? 1 : (int)sizeof(TO);
+    constexpr int es = (int)sizeof(TO);
     uint8_t* const o = a.outs[im] + ((long long)(t.out_y - a.out_row0) * ny / Ly + gy) * (long long)a.out_pitch[im] +
-                       ((long long)t.out_x * nx / Lx + gx) * (sizeof(TO) == 1 ? a.c : es);
+                       ((long long)t.out_x * nx / Lx + gx) * (is_hwc<TO> ? a.c * es : es);
 #pragma unroll 1
     for (int q = 0; q < 3; q++)
     {
         const float m = area_pixel<TP>(b0 + q * cstep, ss, w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, gx, gy);
         const int qo = a.bgr ? 2 - q : q;
-        if constexpr (sizeof(TO) != 1) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)m;
-        else o[qo] = post_store(m * 255.f);
+        if constexpr (!is_hwc<TO>) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)m;
+        else reinterpret_cast<TO*>(o)[qo] = hwc_sample01<TO>(m);
     }
     if constexpr (ALPHA)
     {
@@ -945,10 +1101,10 @@ __global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
                 int bx;
                 float cx[4];
                 cubic_coeffs(t.out_w / 4, t.out_w, i, bx, cx);
-                return fminf(fmaxf(alpha_bicubic(a, t, im, bx, cx, by, cy), 0.f), 255.f);
+                return fminf(fmaxf(alpha_units<TO, TA>(alpha_bicubic<TA>(a, t, im, bx, cx, by, cy)), 0.f), alpha_max<TO>);
             };
         });
-        o[3] = post_store(mul_rn(V, a.area_norm));
+        reinterpret_cast<TO*>(o)[3] = alpha_store<TO>(mul_rn(V, a.area_norm));
     }
 }
 
@@ -959,6 +1115,10 @@ static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipS
     const dim3 grid((max_ow * a.num / Lx + 63) / 64, (max_oh * a.num_y / Ly + 3) / 4, a.ntiles), block(256);
     if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_area<TP, _Float16, false>), grid, block, 0, st, a);
     else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_area<TP, float, false>), grid, block, 0, st, a);
+    else if (a.out_fmt == kFmtU16 && a.c == 4)
+        with_alpha_type(a, [&](auto ta) { hipLaunchKernelGGL((postproc_tiles_area<TP, uint16_t, true, decltype(ta)>), grid, block, 0, st, a); });
+    else if (a.out_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_area<TP, uint16_t, false>), grid, block, 0, st, a);
+    else if (a.c == 4 && a.in_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true, uint16_t>), grid, block, 0, st, a);
     else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
 }
@@ -1397,13 +1557,32 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
         // Measured on the C5 frame: the TTA gather 0.92 ms staged vs 1.72 ms per-pixel (profiles/post_dedupe.txt; 2.42 ms before the per-pixel
         // kernel took its value through tta_gather, profiles/r04_prepost.txt: the transposed variants), but 0.19 vs 0.12 ms for the plain
         // single-variant conversion.  Default: staged under TTA, plain otherwise.
-        const bool staged = a.variant == 2 || (a.variant == 0 && a.tta);
+        // A uint16 image on either side (the destination, or the RGBA source the alpha is read from) has the per-pixel kernel only: the
+        // staged one collects uint8 pixels and reads uint8 alpha.
+        const bool sixteen = a.out_fmt == kFmtU16 || (a.c == 4 && a.in_fmt == kFmtU16);
+        const bool staged = !sixteen && (a.variant == 2 || (a.variant == 0 && a.tta));
         bool aligned = true; // (the staged kernel stores the uint8 image in dwords: base and row pitch must be multiples of 4)
         for (int i = 0; i < a.nimgs; i++) aligned = aligned && (a.out_fmt != kFmtU8 || !((reinterpret_cast<uintptr_t>(a.outs[i]) | (uintptr_t)a.out_pitch[i]) & 3));
         with_image_type(a.out_fmt, [&](auto to) {
             using TO = decltype(to);
-            if (staged && aligned) hipLaunchKernelGGL((postproc_tiles_lds<TP, TO>), dim3((max_ow + 31) / 32, (max_oh + 31) / 32, a.ntiles), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((postproc_tiles<TP, TO>), dim3((max_ow + 63) / 64, (max_oh + 3) / 4, a.ntiles), dim3(256), 0, st, a);
+            const dim3 grid((max_ow + 63) / 64, (max_oh + 3) / 4, a.ntiles);
+            if constexpr (std::is_same<TO, uint16_t>::value)
+                with_alpha_type(a, [&](auto ta) {
+                    const dim3 grid2((max_ow / 2 + 63) / 64, (max_oh + 3) / 4, a.ntiles);
+                    // Measured on the C2 frame (profiles/rgb16.txt): two pixels per thread 0.128 ms against 0.136 for one (RGBA 0.390 against
+                    // 0.453); under TTA the gather dominates and the pair's doubled registers cost more than its stores save (RGB 1.816
+                    // against 1.661).  Default: two without TTA, one with; variant 1 / 2 force one / two (the bytes are the same).
+                    const bool two = a.variant == 2 || (a.variant == 0 && !a.tta);
+                    if (two && a.c == 4) hipLaunchKernelGGL((postproc_tiles_u16x2<TP, 4, decltype(ta)>), grid2, dim3(256), 0, st, a);
+                    else if (two) hipLaunchKernelGGL((postproc_tiles_u16x2<TP, 3>), grid2, dim3(256), 0, st, a);
+                    else hipLaunchKernelGGL((postproc_tiles<TP, TO, decltype(ta)>), grid, dim3(256), 0, st, a);
+                });
+            else if (sixteen) // (a uint8 image with a uint16 RGBA source)
+            {
+                if constexpr (std::is_same<TO, uint8_t>::value) hipLaunchKernelGGL((postproc_tiles<TP, TO, uint16_t>), grid, dim3(256), 0, st, a);
+            }
+            else if (staged && aligned) hipLaunchKernelGGL((postproc_tiles_lds<TP, TO>), dim3((max_ow + 31) / 32, (max_oh + 31) / 32, a.ntiles), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((postproc_tiles<TP, TO>), grid, dim3(256), 0, st, a);
         });
     });
 }

@@ -10,6 +10,8 @@
 //   * codecs: stb_image / stb_image_write as in the reference (jpg, png, ... in; png, jpg out) + binary pnm; webp in / lossless
 //     webp out through the system's libwebp, bound at run time (webp_dl.h) -- without it webp files fail like a broken image;
 //   * "-j l:p:s" accepts a single proc count for several GPUs (the reference insists on one per GPU);
+//   * RSR_DEPTH=16|auto (no counterpart: the reference is 8-bit throughout): 16-bit PNG / PNM in, 16-bit PNG out through
+//     rsr_process_fmt (RSR_FMT_U16_HWC); unset or 8, every byte of the 8-bit route is what it was;
 //   * video mode (no counterpart): an input that ends in .y4m, or is "-" (stdin), is a YUV4MPEG2 stream and runs through one rsr_video
 //     session to a .y4m output or "-" (stdout) -- run_video below, y4m_io.h.
 #include <dirent.h>
@@ -46,6 +48,9 @@ static void print_usage()
     fprintf(stderr, "  -j load:proc:save    thread count for load/proc/save (default=1:2:2) can be 1:2,2,2:2 for multi-gpu\n");
     fprintf(stderr, "  -x                   enable tta mode\n");
     fprintf(stderr, "  -f format            output image format (jpg/png/webp, default=ext/png)\n");
+    fprintf(stderr, "\nenvironment:\n");
+    fprintf(stderr, "  RSR_DEPTH=8|16|auto  sample depth (default=8): 16 = every image runs as 16-bit RGB(A) and is written as a 16-bit .png\n");
+    fprintf(stderr, "                       (8-bit sources widened by x257); auto = 16-bit png/pnm inputs with a .png output keep their 16 bits\n");
 }
 
 static std::vector<int> parse_int_list(const char* s)
@@ -375,6 +380,21 @@ int main(int argc, char** argv)
             return -1;
         }
     }
+    // RSR_DEPTH=8|16|auto (no flag of the reference's surface is taken for it, like RSR_OUT_SCALE): the sample depth of the still-image
+    // route.  8 / unset: what it always was.  16: every image runs U16 -> U16 (an 8-bit source widened by x257: the same network input) and
+    // is written as a 16-bit PNG.  auto: a 16-bit PNG / PNM input whose output is a .png takes the 16-bit route, everything else the 8-bit one.
+    enum { kDepth8, kDepth16, kDepthAuto } depth_mode = kDepth8;
+    if (const char* de = getenv("RSR_DEPTH"))
+    {
+        const std::string v(de);
+        if (v == "16") depth_mode = kDepth16;
+        else if (v == "auto") depth_mode = kDepthAuto;
+        else if (!v.empty() && v != "8")
+        {
+            fprintf(stderr, "invalid RSR_DEPTH '%s' (8, 16 or auto)\n", de);
+            return -1;
+        }
+    }
     if (gpuid.empty()) gpuid.push_back(0);
     const int ngpu = int(gpuid.size());
     const bool video = is_y4m_path(inputpath) && !is_dir(inputpath); // a YUV4MPEG2 stream: one session on one GPU
@@ -437,6 +457,11 @@ int main(int argc, char** argv)
     if (format != "png" && format != "webp" && format != "jpg")
     {
         fprintf(stderr, "invalid format argument\n");
+        return -1;
+    }
+    if (depth_mode == kDepth16 && !video && format != "png")
+    { // (before any GPU work: nothing but PNG holds 16-bit samples here)
+        fprintf(stderr, "RSR_DEPTH=16 writes 16-bit images, which only .png holds: give a .png output path or -f png, not %s\n", format.c_str());
         return -1;
     }
     if (format == "webp" && !webpdl::api().error.empty())
@@ -629,7 +654,24 @@ int main(int argc, char** argv)
                 v->id = int(i);
                 v->inpath = input_files[i];
                 v->outpath = output_files[i];
-                const std::string err = imgio::load_image(v->inpath, v->inimage);
+                // the route of this image: 16 bits where RSR_DEPTH says so (auto: a 16-bit source into a .png), else the 8-bit route untouched
+                std::string err;
+                bool deep = false;
+                if (depth_mode != kDepth8)
+                {
+                    std::vector<uint8_t> bytes;
+                    const bool sixteen = imgio::read_file(v->inpath, bytes) && imgio::is_16bit(bytes);
+                    deep = depth_mode == kDepth16 || (sixteen && imgio::lower_ext(v->outpath) == "png");
+                    if (deep && sixteen) err = imgio::load_image16(bytes, v->inimage);
+                    else if (deep)
+                    {
+                        Image narrow;
+                        err = imgio::load_image(v->inpath, narrow);
+                        if (err.empty()) err = imgio::widen_image(narrow, v->inimage);
+                    }
+                    if (verbose) fprintf(stderr, "%s: %s\n", v->inpath.c_str(), deep ? (sixteen ? "16-bit route" : "16-bit route (8-bit source widened by x257)") : (sixteen ? "8-bit route (16-bit source reduced: the output is no .png)" : "8-bit route"));
+                }
+                if (!deep) err = imgio::load_image(v->inpath, v->inimage);
                 if (!err.empty())
                 {
                     fprintf(stderr, "decode image %s failed: %s\n", v->inpath.c_str(), err.c_str());
@@ -639,14 +681,14 @@ int main(int argc, char** argv)
                 }
                 // an RGBA image cannot be a jpg: write <name>.png instead (main.cpp:278-288)
                 const std::string oext = imgio::lower_ext(v->outpath);
-                if (v->inimage.elempack == 4 && (oext == "jpg" || oext == "jpeg"))
+                if (!deep && v->inimage.elempack == 4 && (oext == "jpg" || oext == "jpeg"))
                 {
                     const std::string out2 = v->outpath + ".png";
                     fprintf(stderr, "image %s has alpha channel ! %s will output %s\n", v->inpath.c_str(), v->inpath.c_str(), out2.c_str());
                     v->outpath = out2;
                 }
                 // (a size the ratio does not divide is refused by RealSR::process, which sizes the image through rsr_out_size)
-                v->outimage.create(std::max(1, v->inimage.w * out_num / out_den), std::max(1, out_den_y ? v->inimage.h * out_num_y / out_den_y : v->inimage.h * out_num / out_den), v->inimage.elempack, true);
+                v->outimage.create(std::max(1, v->inimage.w * out_num / out_den), std::max(1, out_den_y ? v->inimage.h * out_num_y / out_den_y : v->inimage.h * out_num / out_den), v->inimage.elempack, true, v->inimage.depth);
                 toproc.put(std::move(v));
             }
         });
@@ -660,7 +702,12 @@ int main(int argc, char** argv)
                     std::unique_ptr<Task> v = toproc.get();
                     if (v->id == kEnd) return;
                     int prc;
-                    if (split_one_image)
+                    if (split_one_image && v->inimage.depth == 16)
+                    { // rsr_process_fmt has no tile ranges: a single 16-bit image runs on the first gpu
+                        if (verbose) fprintf(stderr, "%s: a 16-bit image is not split over gpus: it runs on gpu %d\n", v->inpath.c_str(), gpuid[0]);
+                        prc = realsr[0]->process(v->inimage, v->outimage);
+                    }
+                    else if (split_one_image)
                     {
                         std::vector<RealSR*> grp;
                         for (auto& r : realsr) grp.push_back(r.get());
@@ -685,7 +732,7 @@ int main(int argc, char** argv)
             {
                 std::unique_ptr<Task> v = tosave.get();
                 if (v->id == kEnd) return;
-                const std::string err = imgio::save_image(v->outpath, v->outimage);
+                const std::string err = v->outimage.depth == 16 ? imgio::save_png16(v->outpath, v->outimage) : imgio::save_image(v->outpath, v->outimage);
                 if (!err.empty())
                 {
                     fprintf(stderr, "encode image %s failed: %s\n", v->outpath.c_str(), err.c_str());

@@ -14,6 +14,7 @@
 struct Image // what the reference passes as ncnn::Mat(w, h, data, elemsize=c, elempack=c)  (main.cpp:275-276)
 {
     int w = 0, h = 0, elempack = 0; // elempack = channels (3 RGB / 4 RGBA), HWC uint8, tightly packed
+    int depth = 8;                  // bits of a sample: 8, or 16 -- native uint16 words, full range (RSR_FMT_U16_HWC); the byte count follows
 
     Image() = default;
     Image(const Image&) = delete;
@@ -24,10 +25,11 @@ struct Image // what the reference passes as ncnn::Mat(w, h, data, elemsize=c, e
         if (this != &o)
         {
             release();
-            w = o.w; h = o.h; elempack = o.elempack; ptr = o.ptr; bytes = o.bytes; pinned = o.pinned;
+            w = o.w; h = o.h; elempack = o.elempack; depth = o.depth; ptr = o.ptr; bytes = o.bytes; pinned = o.pinned;
             o.ptr = nullptr;
             o.bytes = 0;
             o.w = o.h = o.elempack = 0;
+            o.depth = 8;
         }
         return *this;
     }
@@ -35,15 +37,19 @@ struct Image // what the reference passes as ncnn::Mat(w, h, data, elemsize=c, e
 
     uint8_t* data() { return ptr; }
     const uint8_t* data() const { return ptr; }
+    uint16_t* data16() { return reinterpret_cast<uint16_t*>(ptr); } // depth 16 (malloc and rsr_host_alloc align well beyond 2)
+    const uint16_t* data16() const { return reinterpret_cast<const uint16_t*>(ptr); }
+    size_t size_bytes() const { return bytes; }
     // pinned_memory: allocate with rsr_host_alloc, so that rsr_process moves the pixels over PCIe without a staging copy
     // (what ncnn's Vulkan staging allocator does for the reference, realsr.cpp:161-167)
-    void create(int w_, int h_, int c_, bool pinned_memory = false)
+    void create(int w_, int h_, int c_, bool pinned_memory = false, int depth_ = 8)
     {
         release();
         w = w_;
         h = h_;
         elempack = c_;
-        bytes = size_t(w_) * h_ * c_;
+        depth = depth_;
+        bytes = size_t(w_) * h_ * c_ * size_t(depth_ / 8);
         pinned = pinned_memory;
         ptr = pinned ? static_cast<uint8_t*>(rsr_host_alloc(bytes)) : static_cast<uint8_t*>(std::malloc(bytes ? bytes : 1));
         if (!ptr && pinned)
@@ -111,9 +117,12 @@ public:
         if (rc == RSR_OK) rc = out_size(inimage.w, inimage.h, &ow, &oh);
         if (rc == RSR_OK)
         {
-            if (outimage.w != ow || outimage.h != oh || outimage.elempack != inimage.elempack)
-                outimage.create(ow, oh, inimage.elempack, true);
-            rc = rsr_process(ctx, inimage.data(), inimage.w, inimage.h, inimage.elempack, outimage.data());
+            if (outimage.w != ow || outimage.h != oh || outimage.elempack != inimage.elempack || outimage.depth != inimage.depth)
+                outimage.create(ow, oh, inimage.elempack, true, inimage.depth);
+            if (inimage.depth == 16) // 16-bit RGB(A) in, 16-bit out: the host call with a format per side (the size rule is the uint8 one)
+                rc = rsr_process_fmt(ctx, inimage.data(), RSR_FMT_U16_HWC, inimage.w, inimage.h, inimage.elempack, outimage.data(), RSR_FMT_U16_HWC);
+            else
+                rc = rsr_process(ctx, inimage.data(), inimage.w, inimage.h, inimage.elempack, outimage.data());
         }
         if (rc != RSR_OK) std::fprintf(stderr, "RealSR::process: %s\n", rsr_last_error(ctx)); // (rsr_out_size reports on the calling thread, as every call does)
         return rc;

@@ -3,6 +3,8 @@
     from realsr_ncnn_vulkan_amd import RealSR, torch_io
     sr = RealSR(0); sr.load(param, bin)
     y = torch_io.upscale(sr, x)        # x: (3, H, W) or (N, 3, H, W) float16 / float32 in [0, 1] on cuda:0  ->  (.., 3, 4H, 4W)
+    y16 = torch_io.upscale(sr, x16)    # x16: (H, W, 3 | 4) uint16 / int16, 16-bit RGB(A)  ->  (4H, 4W, c) of the same dtype
+    y16 = torch_io.upscale(sr, x8, out_dtype=torch.int16)   # an 8-bit image in, the network's sub-code precision out as 16 bits
     torch_io.upscale(sr, frame[..., y0:y1, x0:x1], out=canvas[..., 4 * y0:4 * y1, 4 * x0:4 * x1])   # views in, a window out: no copies
 
     yuv444 = torch_io.upscale_yuv(sr, planes, chroma=444)   # a (3, H, W) uint8 / int16 yuv444p / yuv444p10le frame -> (3, H', W'), any H and W
@@ -29,10 +31,16 @@ import types
 import numpy as np
 import torch
 
-from . import (RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_NV16, RSR_FMT_P010, RSR_FMT_P210, RSR_FMT_U8_HWC, RSR_FMT_YUV444P,
-               RSR_FMT_YUV444P10)
+from . import (RSR_FMT_F16_CHW, RSR_FMT_F32_CHW, RSR_FMT_NV12, RSR_FMT_NV16, RSR_FMT_P010, RSR_FMT_P210, RSR_FMT_U16_HWC, RSR_FMT_U8_HWC,
+               RSR_FMT_YUV444P, RSR_FMT_YUV444P10)
 
 _FMT = {torch.float16: RSR_FMT_F16_CHW, torch.float32: RSR_FMT_F32_CHW}
+# integer HWC images: uint8, and 16-bit words as int16 too (the convention of _chroma below: torch's uint16 is a late and partial dtype);
+# the engine reads the words unsigned whatever the tensor calls them
+_HWC = {torch.uint8: RSR_FMT_U8_HWC, torch.int16: RSR_FMT_U16_HWC}
+if hasattr(torch, "uint16"):
+    _HWC[torch.uint16] = RSR_FMT_U16_HWC
+_HWC_FMTS = (RSR_FMT_U8_HWC, RSR_FMT_U16_HWC)
 
 
 def _check(sr, x):
@@ -47,6 +55,12 @@ def _check(sr, x):
         if x.shape[0] < 1 or x.shape[1] < 1:
             raise ValueError("upscale: empty image %s" % (tuple(x.shape),))
         return RSR_FMT_U8_HWC, False
+    if x.dtype in _HWC:
+        if x.dim() != 3 or x.shape[2] not in (3, 4):
+            raise ValueError("upscale: a 16-bit tensor must be (H, W, 3) or (H, W, 4), not %s" % (tuple(x.shape),))
+        if x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("upscale: empty image %s" % (tuple(x.shape),))
+        return RSR_FMT_U16_HWC, False
     if x.dtype not in _FMT:
         raise ValueError("upscale: dtype %s is not supported (float16, float32 or uint8)" % x.dtype)
     if x.dim() not in (3, 4) or x.shape[-3] != 3:
@@ -61,11 +75,13 @@ def describe(x):
     (plane_pitch 0 for uint8), or None when the view does not fit one and must be copied.  Pure: looks at shape and strides only.
       float:  stride(-1) == 1, stride(-2) >= W, stride(-3) > 0 (a crop, a slice along N, rows of a padded surface, planes stored apart)
       uint8:  stride(2) == 1, stride(1) == c, stride(0) >= W * c
+      uint16 / int16 (H, W, c): the uint8 rule in elements -- element stride 1, pixel stride c, rows >= W * c elements apart -- and an even
+              data pointer
     A dimension of size 1 has no stride to speak of.  Permuted views, stride 0 (expand) and steps along a row give None."""
     if x.dim() != 3:
         return None
     es = x.element_size()
-    if x.dtype == torch.uint8:
+    if x.dtype in _HWC:
         h, w, c = x.shape
         rs, ps, cs = x.stride()
         if (c > 1 and cs != 1) or (w > 1 and ps != c):
@@ -89,8 +105,8 @@ def describe(x):
 
 def _packed(x, d):
     """Is the descriptor d of the image tensor x the tightly packed one?"""
-    if x.dtype == torch.uint8:
-        return d[1] == x.shape[1] * x.shape[2]
+    if x.dtype in _HWC:
+        return d[1] == x.shape[1] * x.shape[2] * x.element_size()
     return d[1] == x.shape[2] * x.element_size() and d[2] == x.shape[1] * d[1]
 
 
@@ -103,24 +119,33 @@ def _out_size(sr, w, h):
     return w * s, h * s
 
 
-def upscale(sr, x, out=None):
+def upscale(sr, x, out=None, out_dtype=None):
     """x4 -- or, with sr.out_scale 2 / 1, that result box-reduced on the device to x2 / x1, or with sr.out_ratio 3/2, 4/3, 3 ... area-averaged to that scale, or with sr.out_ratio_xy = (8/3, 9/4) ... to a scale per axis (720 x 480 -> 1920 x 1080) -- of x on the context `sr` (a loaded RealSR).  x lives on the context's GPU: float16 / float32 (3, H, W) or (N, 3, H, W)
     with values in [0, 1], or uint8 (H, W, 3 | 4).  Returns a tensor of the same dtype and layout at 4x (out_scale x), enqueued on
     torch.cuda.current_stream(); a batch is ONE rsr_process_device_batch call on that stream.  A view that fits a descriptor (describe)
     is read in place; any other non-contiguous input is made contiguous first.
     out: the tensor to write (and return) instead of a new one: the result's shape, dtype and device, and itself a view that fits a
-    descriptor -- a window of a larger canvas, say.  ValueError otherwise, before anything is launched.  It must not overlap x."""
+    descriptor -- a window of a larger canvas, say.  ValueError otherwise, before anything is launched.  It must not overlap x.
+    16-bit RGB(A): x may be a uint16 / int16 (H, W, 3 | 4) tensor (RSR_FMT_U16_HWC: full-range words, read unsigned whatever the dtype says);
+    the result has the same dtype.  out_dtype (integer HWC inputs only): torch.uint8, torch.uint16 or torch.int16 -- the depth of the
+    result, so that 8 -> 16 and 16 -> 8 bits are one call; with out= given, out.dtype must equal it."""
     fmt, batched = _check(sr, x)
+    ydtype = x.dtype
+    if out_dtype is not None:
+        if fmt not in _HWC_FMTS or out_dtype not in _HWC:
+            raise ValueError("upscale: out_dtype is torch.uint8, torch.uint16 or torch.int16, for a uint8 / uint16 / int16 (H, W, 3 | 4) input only")
+        ydtype = out_dtype
+    out_fmt = _HWC[ydtype] if fmt in _HWC_FMTS else fmt
     # (the context's output size: x4 unless option "out_scale" says 2 or 1, or out_ratio another scale)
-    if fmt == RSR_FMT_U8_HWC:
+    if fmt in _HWC_FMTS:
         ow, oh = _out_size(sr, x.shape[1], x.shape[0])
         shape = (oh, ow, x.shape[2])
     else:
         ow, oh = _out_size(sr, x.shape[-1], x.shape[-2])
         shape = tuple(x.shape[:-3]) + (3, oh, ow)
     if out is not None:
-        if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != x.dtype or out.device != x.device:
-            raise ValueError("upscale: out must be a %s tensor of shape %s on %s" % (x.dtype, shape, x.device))
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != ydtype or out.device != x.device:
+            raise ValueError("upscale: out must be a %s tensor of shape %s on %s" % (ydtype, shape, x.device))
         if (batched and out.shape[0] > 1 and out.stride(0) == 0) or (out.numel() and describe(out[0] if batched else out) is None):
             raise ValueError("upscale: out (strides %s) is not addressable by row and plane pitch" % (tuple(out.stride()),))
     if x.numel() and describe(x[0] if batched else x) is None:
@@ -131,10 +156,10 @@ def upscale(sr, x, out=None):
         # The work goes onto a side stream ordered behind and in front of the default stream by events: still nothing waits on the host.
         side = _side_stream(x.device)
         side.wait_stream(cur)
-        y = _enqueue(sr, x, fmt, batched, side.cuda_stream, out, shape)
+        y = _enqueue(sr, x, fmt, batched, side.cuda_stream, out, shape, out_fmt, ydtype)
         cur.wait_stream(side)  # (x and y are next touched by work behind this wait: the allocator may reuse them safely)
         return y
-    return _enqueue(sr, x, fmt, batched, cur.cuda_stream, out, shape)
+    return _enqueue(sr, x, fmt, batched, cur.cuda_stream, out, shape, out_fmt, ydtype)
 
 
 def _on_current_stream(device, enqueue):
@@ -499,7 +524,7 @@ def _image_desc(sr, t, what, chroma=420):
     fmt, batched = _check(sr, t)
     if batched:
         raise ValueError("upscale_delta: %s must be ONE image, not a batch %s" % (what, tuple(t.shape)))
-    h, w, c = t.shape if fmt == RSR_FMT_U8_HWC else (t.shape[1], t.shape[2], 3)
+    h, w, c = t.shape if fmt in _HWC_FMTS else (t.shape[1], t.shape[2], 3)
     return fmt, w, h, c, describe(t)
 
 
@@ -594,7 +619,7 @@ def _new_like_result(x, ow, oh, chroma=420):
     """An uninitialised result for the single image x (a tensor or a (y, uv) pair; chroma: a surface's subsampling) at ow x oh, of x's kind."""
     if chroma == 444 or isinstance(x, (tuple, list)) or x.dim() == 2:
         return _new_yuv(x, ow, oh, chroma)
-    return x.new_empty((oh, ow, x.shape[2]) if x.dtype == torch.uint8 else (3, oh, ow))
+    return x.new_empty((oh, ow, x.shape[2]) if x.dtype in _HWC else (3, oh, ow))
 
 
 def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420):
@@ -651,7 +676,7 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420)
     first = xs[0][0] if pair else xs[0]
     if out is None:
         if stacked:
-            out = first.new_empty((n, oh, ow, c) if fmt == RSR_FMT_U8_HWC else (n, 3, oh, ow))
+            out = first.new_empty((n, oh, ow, c) if fmt in _HWC_FMTS else (n, 3, oh, ow))
             ys = [out[i] for i in range(n)]
         else:
             out = ys = [_new_like_result(x, ow, oh, chroma) for x in xs]
@@ -697,11 +722,12 @@ def _side_stream(device):
     return _side[device.index]
 
 
-def _enqueue(sr, x, fmt, batched, stream, out, shape):
-    y = out if out is not None else torch.empty(shape, dtype=x.dtype, device=x.device)
+def _enqueue(sr, x, fmt, batched, stream, out, shape, out_fmt=None, ydtype=None):
+    out_fmt = fmt if out_fmt is None else out_fmt
+    y = out if out is not None else torch.empty(shape, dtype=ydtype or x.dtype, device=x.device)
     if x.numel() == 0:
         return y
-    if fmt == RSR_FMT_U8_HWC:
+    if fmt in _HWC_FMTS:
         h, w, c = x.shape
     else:
         h, w, c = x.shape[-2], x.shape[-1], 3
@@ -710,9 +736,9 @@ def _enqueue(sr, x, fmt, batched, stream, out, shape):
         n, es = x.shape[0], x.element_size()
         ins = [(dx[0] + i * x.stride(0) * es, dx[1], dx[2]) for i in range(n)]
         outs = [(dy[0] + i * y.stride(0) * es, dy[1], dy[2]) for i in range(n)]
-        sr.process_device_batch(ins, fmt, w, h, c, outs, fmt, stream=stream)
+        sr.process_device_batch(ins, fmt, w, h, c, outs, out_fmt, stream=stream)
     elif _packed(x, dx) and _packed(y, dy):
-        sr.process_device_fmt(dx[0], fmt, w, h, c, dy[0], fmt, stream=stream)
+        sr.process_device_fmt(dx[0], fmt, w, h, c, dy[0], out_fmt, stream=stream)
     else:
-        sr.process_device_batch([dx], fmt, w, h, c, [dy], fmt, stream=stream)
+        sr.process_device_batch([dx], fmt, w, h, c, [dy], out_fmt, stream=stream)
     return y
