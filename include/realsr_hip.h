@@ -274,6 +274,43 @@ int rsr_out_size_fmt(int out_fmt, int num_x, int den_x, int num_y, int den_y, in
  * anything is enqueued (RSR_E_ARG; RSR_E_STATE before rsr_load).  rsr_process_fmt(U8 -> U8) writes the bytes rsr_process writes. */
 int rsr_process_fmt(rsr_ctx* ctx, const void* in, int in_fmt, int w, int h, int c, void* out, int out_fmt);
 
+/* ---- alpha through the network: option "alpha_net" (no reference counterpart) ------------------------------------------------------------
+ * Game textures, sprites, UI atlases, scans with cut-outs and logos are RGBA.  By default the colour of such an image walks the network and
+ * comes out sharp while its alpha takes ncnn's bicubic x4 and comes out soft: the two disagree along every edge, which shows as a halo.
+ * With option "alpha_net" 1 a call whose images have c == 4 (RSR_FMT_U8_HWC / RSR_FMT_U16_HWC on both sides, in any combination) sends the
+ * alpha through the same network, as a gray image, instead.  0 [default]: everything is byte for byte and launch for launch what it was.  A
+ * c == 3 call is not concerned at either value: same launches, same bytes.
+ *   The definition, exact.  Let G be the gray image of the source: c == 3, the source's sample type (uint8 or uint16), the same w x h, all
+ *            three samples of pixel (x, y) equal to the source's alpha sample there.  G enters the network as any U8 / U16 RGB image does
+ *            (fp16(b / 255); fp16(float(k) * fp32(1/65535)) for U16), with the same tiles, halo and reflect-101 as the colour.  For an
+ *            output pixel let A0, A1, A2 be what RSR_FMT_F32_CHW planes 0, 1, 2 would hold for a call on G with option "bgr" 0 in the
+ *            context's current mode, scale, ratio or pair: under TTA the eight variants merged first; under "precise" conv_last's fp32
+ *            result; below x4 the box or area mean per channel; each value in [0, 1].  Then, in this order:
+ *              1. m = min(((A0 + A1) + A2) * fp32(1/3), 1): fp32 throughout, every operation rounded by itself, the constant computed in
+ *                 double and rounded once;
+ *              2. a U8 destination stores floor(m * 255.f + 0.5f) clamped to 0 .. 255, the product and the sum each rounded by itself --
+ *                 unlike the fp16-valued colour, m * 255 is not exact in fp32, so the rule does not leave a contraction (fma) to the compiler;
+ *              3. a U16 destination stores (uint16) floor(m * 65535.f + 0.5f), likewise (the colour's own store, "16-bit RGB(A)" above).
+ *            No x257 or 1/257 step exists on this route: the depth of the source decides how G is read, the depth of the destination how m
+ *            is stored.  "bgr" does not change the alpha.  The colour samples of the call are exactly those of the same call with
+ *            "alpha_net" 0.  Nothing outside the destination window is written, as ever.
+ *   A constant alpha does not come out constant.  The network is no identity on flat images: f(255) need not be 255, and a fully opaque
+ *            image may leave with alpha 254 here and there.  The library does not look for constant tiles (that would change bytes and need
+ *            a host round trip on the device paths); a caller who knows an image to be opaque sets the option to 0 for it, as the CLI does.
+ *   Cost.    The tiles of an RGBA batch walk the network TWICE, over the same tables, plan and workspace (no workspace byte is added): expect
+ *            about twice the frame time of "alpha_net" 0 (profiles/alpha_net.txt).  The colour pass runs as ever; the alpha pass is one
+ *            more preprocessing launch, the network, and one post-processing launch that stores sample 3 alone.
+ *   Where.   Every route: rsr_process, _many, _tiles, _rows, merged concurrent calls, rsr_process_fmt, rsr_process_device, _fmt, _batch
+ *            (windows, pitches), _masked and _sequence (a tile's alpha depends on its padded source rectangle alone, and the diffs compare
+ *            the alpha bytes: masks stay valid; the rectangles are propagated behind the last batch as ever).  rsr_process_group: the
+ *            members must agree on "alpha_net" (RSR_E_ARG otherwise, like differing ratios).  The option is read when a tile batch is
+ *            enqueued.  The progress callback stays one call per tile.  Under profiling the per-class times, launch counts and
+ *            FLOPs of rsr_profile include both passes; its tile count does not.
+ *   Stats.   "alpha_net": the value in force.  "alpha_tiles": tiles run through the alpha pass since creation -- a masked call adds its
+ *            marked tiles only, a c == 3 call none.
+ * Out of scope: a per-tile decision inside the library, luma-weighted or single-channel alpha, premultiplied alpha, alpha for planar or YUV
+ * formats, one network pass shared by colour and alpha. */
+
 /* ---- YUV 4:4:4: RSR_FMT_YUV444P / RSR_FMT_YUV444P10 in and out (no reference counterpart) -------------------------------------------------
  * Screen recordings (H.264 Hi444PP, HEVC RExt, AV1 4:4:4, lossless x264 / FFV1: subsampled chroma smears coloured text), ProRes 4444 and
  * DNxHR 444 masters, and whatever was ever RGB inside libavfilter, VapourSynth or an encoder's input hold three FULL planes of integer codes:
@@ -909,6 +946,10 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *   "yuv_siting"        0 [default] = centre, 1 = left, 2 = top-left: where a chroma sample of an RSR_FMT_NV12 / RSR_FMT_P010 surface sits, on the
  *                       input and the output side alike ("Chroma siting" above); takes effect for the next call.  Any other value: RSR_E_ARG,
  *                       the value in force stays (stat "yuv_siting").  RGB formats, host pointers and the CLI are not concerned.
+ *   "alpha_net"         0 [default]: the alpha of an RGBA image is ncnn's bicubic x4.  1: it walks the network as a gray image, a second
+ *                       pass over the call's tiles at about twice the frame time ("alpha through the network" above has the exact rule);
+ *                       c == 3 calls are not concerned.  Takes effect for the next call.  Any other value: RSR_E_ARG, the value in force
+ *                       stays (stat "alpha_net"; stat "alpha_tiles": tiles run through the alpha pass since creation)
  *   "precise_auto"      1: "precise" is set by the model: on a loaded context rsr_selfcheck runs at once on the built-in tile and "precise"
  *                       becomes its recommend_precise; on a context not yet loaded the same happens at the end of the next successful
  *                       rsr_load / rsr_load_packed (which then returns the self-check's error, if it has one; the model stays loaded).

@@ -427,6 +427,18 @@ class RealSR:
     def yuv_siting(self, v):
         self.set_option("yuv_siting", int(v))  # (anything but 0, 1 or 2 raises RealSRError(RSR_E_ARG) and leaves the value alone)
 
+    @property
+    def alpha_net(self):
+        """0 (default): the alpha of an RGBA image is the bicubic x4.  1: it walks the network as a gray image -- a second pass over the
+        call's tiles, about twice the frame time -- and the mean of the three results becomes the alpha sample (option "alpha_net",
+        include/realsr_hip.h has the exact rule; a constant alpha does not come out constant).  RGB calls are not concerned.  Takes effect
+        for the next call.  Read from the engine, like yuv_siting; stat "alpha_tiles" counts the tiles that ran the alpha pass."""
+        return int(self.get_stat("alpha_net"))
+
+    @alpha_net.setter
+    def alpha_net(self, v):
+        self.set_option("alpha_net", int(v))  # (anything but 0 or 1 raises RealSRError(RSR_E_ARG) and leaves the value alone)
+
     def close(self):
         if getattr(self, "_h", None):
             for v in list(getattr(self, "_videos", ())):  # open video sessions go first: they hold device memory of this context

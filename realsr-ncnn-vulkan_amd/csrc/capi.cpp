@@ -718,6 +718,8 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "yuv_matrix") *value = double(e.yuv_matrix);
     else if (k == "yuv_range") *value = double(e.yuv_range);
     else if (k == "yuv_siting") *value = double(e.yuv_siting);
+    else if (k == "alpha_net") *value = e.alpha_net ? 1.0 : 0.0;
+    else if (k == "alpha_tiles") *value = double(e.alpha_tiles);
     else if (k == "selfcheck_runs") *value = double(e.selfcheck_runs);
     else if (k == "selfcheck_headroom") *value = e.sc_have ? double(e.sc_last.headroom) : -1.0;
     else if (k == "selfcheck_peak_abs") *value = e.sc_have ? double(e.sc_last.peak_abs) : -1.0;
@@ -780,6 +782,11 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     { // where a chroma sample of an NV12 / P010 surface sits, on both sides of a call; read when the next call is enqueued
         if (value != 0 && value != 1 && value != 2) return ctx->e.fail(RSR_E_ARG, "yuv_siting must be 0 (centre), 1 (left) or 2 (top-left)");
         ctx->e.yuv_siting = int(value);
+    }
+    else if (k == "alpha_net")
+    { // the alpha of an RGBA call through the network instead of the bicubic (include/realsr_hip.h "alpha_net"); read when the next batch is enqueued
+        if (value != 0 && value != 1) return ctx->e.fail(RSR_E_ARG, "alpha_net must be 0 (bicubic) or 1 (through the network)");
+        ctx->e.alpha_net = value != 0;
     }
     else if (k == "precise_auto")
     { // the model decides: now when one is loaded, else at the end of the next load (rsr_load / rsr_load_packed)

@@ -1081,7 +1081,19 @@ int Engine::launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntile
     pa.siting = po.siting = yuv_siting;
     launch_preproc_tiles(pa, max_tw, max_th, st);
     mark(0, 0, b.px[0] / per * BatchIO::image_px_bytes(io.in_fmt, c) + b.px[0] * 64, st);
-    const int rc = run_network(b, st, ntiles * per, &io, nullptr);
+    // Option "alpha_net" (include/realsr_hip.h): an RGBA batch walks the network twice over the same tables and workspace -- the colour pass
+    // as ever, its post launch writing the bicubic alpha too, then the alpha pass below, whose post launch overwrites sample 3 alone.  The
+    // throttle event of a merged batch belongs to the pass that runs last.
+    const bool two_pass = alpha_net && c == 4;
+    int rc;
+    if (two_pass)
+    {
+        BatchIO cio = io;
+        cio.ev_mid = nullptr;
+        rc = run_network(b, st, ntiles * per, &cio, nullptr);
+    }
+    else
+        rc = run_network(b, st, ntiles * per, &io, nullptr);
     if (rc != RSR_OK || conv_last_writes_image(c, io.out_fmt)) return rc;
     po.planar3 = ws[kWsOut3].p;
     po.f32 = precise ? 1 : 0;
@@ -1106,6 +1118,18 @@ int Engine::launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntile
     po.variant = variant;
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
     mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) * io.os.nx * io.os.ny / (16.0 * io.os.dx * io.os.dy)), st);
+    if (!two_pass) return RSR_OK;
+    // The alpha pass: the alpha sample of every source pixel into the three input planes (the gray image G of the header), the network,
+    // and the mean of the three results into sample 3.  IN and OUT3 are free again: the stream has the colour pass's launches in front.
+    pa.alpha_src = 1;
+    launch_preproc_tiles(pa, max_tw, max_th, st);
+    mark(0, 0, b.px[0] / per * (BatchIO::image_px_bytes(io.in_fmt, c) / c) + b.px[0] * 64, st);
+    rc = run_network(b, st, ntiles * per, &io, nullptr);
+    if (rc != RSR_OK) return rc;
+    po.alpha_dst = 1;
+    launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
+    mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) / c * io.os.nx * io.os.ny / (16.0 * io.os.dx * io.os.dy)), st);
+    alpha_tiles += ntiles;
     return RSR_OK;
 }
 

@@ -302,6 +302,11 @@ struct Engine
     // 2 x 2 luma quad (JPEG, MPEG-1), 1 = left (H.264 / HEVC / AV1 / MPEG-2 default), 2 = top-left (BT.2020 / UHD HEVC).  Read when a call is
     // enqueued, like the matrix; 1 and 2 launch kernels of their own (kernels.h PreArgs::siting / PostArgs::siting).
     int yuv_siting = 0;
+    // Alpha through the network (option "alpha_net"; include/realsr_hip.h "alpha_net"): an RGBA batch (c == 4) walks the network twice, once
+    // for the colour as ever and once for the gray image of its alpha samples, whose channel mean becomes sample 3 (launch_batch).  Read
+    // when a batch is enqueued, like bgr.  Both passes share the tables, the plan and the workspace: the stream orders them.
+    bool alpha_net = false;
+    long long alpha_tiles = 0; // stat: tiles that ran the alpha pass since creation, under mu
     // Model self-check (include/realsr_hip.h rsr_selfcheck): one tile through the network in both storages, compared on the device.
     bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
     long long selfcheck_runs = 0;

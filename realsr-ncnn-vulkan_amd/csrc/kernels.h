@@ -332,6 +332,8 @@ struct PreArgs
     YuvCoef yuv;    // YUV formats only
     int siting;     // ... likewise: where a chroma sample sits in its luma quad (engine option "yuv_siting"): 0 centre, 1 left, 2 top-left
                     // (a 4:2:2 surface has no vertical siting: 2 is 1 there)
+    int alpha_src;  // 1 (c == 4, uint8 / uint16 HWC): the alpha pass of engine option "alpha_net" -- sample 3 of the pixel goes into channels 0..2,
+                    // converted like a colour sample (the gray image G of include/realsr_hip.h); bgr does not apply.  Kernels of their own.
 };
 void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t st);
 
@@ -381,6 +383,10 @@ struct PostArgs
     // first column / row of a TILE's rectangle; that is quad column / row 0 of the tile's own grid (BaseTile::out_*), so nothing else travels.
     int siting;
     int in_fmt; // c == 4: what in_imgs are made of, kFmtU8 or kFmtU16 (alpha_bicubic reads their samples)
+    // 1 (c == 4, uint8 / uint16 HWC outs): the alpha pass of engine option "alpha_net" -- the blob holds the network's result for the gray
+    // image of the alpha; ONLY sample 3 of every pixel is stored, the mean of the three channel values RSR_FMT_F32_CHW would hold
+    // (postproc_tiles_alpha: x4, box and area alike).  in_imgs, in_fmt, bgr and variant are not looked at.
+    int alpha_dst;
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 

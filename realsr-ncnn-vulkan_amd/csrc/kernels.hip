@@ -227,6 +227,12 @@ __device__ __forceinline__ void tta_dest(int k, int gx, int gy, int tw, int th, 
 // VS = 0: a 4:2:2 surface (kFmtNV16 / kFmtP210), SRC its sample type likewise; the chroma row of a pixel is its own (yuv_decode).
 // VS = kVs444: a planar 4:4:4 surface (kFmtYUV444P / kFmtYUV444P10; a uint16_t holds its code in the LOW 10 bits): three plane reads at
 // the pixel's own (x, y), each contiguous over the lanes of a wave like those of the planar float sources; SITE is 0.
+// SRC = AlphaOf<uint8_t> / AlphaOf<uint16_t> (PreArgs::alpha_src, engine option "alpha_net"): the RGBA image's ALPHA sample, converted
+// like a colour sample of its type, goes into channels 0 .. 2 -- the gray image G of include/realsr_hip.h.  Instantiations of their own.
+template <typename S> struct AlphaOf { typedef S sample; };
+template <typename T> struct alpha_of { typedef void sample; };
+template <typename S> struct alpha_of<AlphaOf<S>> { typedef S sample; };
+
 template <typename SRC, bool YUV = false, int SITE = 0, int VS = 1>
 __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
 {
@@ -248,6 +254,13 @@ __global__ __launch_bounds__(256) void preproc_tiles(const PreArgs a)
         v0[0] = (_Float16)rgb[0];
         v0[1] = (_Float16)rgb[1];
         v0[2] = (_Float16)rgb[2];
+    }
+    else if constexpr (!std::is_void<typename alpha_of<SRC>::sample>::value)
+    { // the alpha pass: sample 3 of RGBA pixel (x, y), as the branches below convert a colour sample of its type
+        typedef typename alpha_of<SRC>::sample S;
+        const S k = reinterpret_cast<const S*>(a.imgs[im] + (long long)y * a.pitch[im])[x * 4 + 3];
+        const float norm_val = sizeof(S) == 1 ? 1 / 255.f : 1 / 65535.f;
+        v0[0] = v0[1] = v0[2] = (_Float16)((float)k * norm_val);
     }
     else if constexpr (sizeof(SRC) == 1)
     {
@@ -438,10 +451,15 @@ void launch_preproc_tiles(const PreArgs& a, int max_tw, int max_th, hipStream_t 
     // sectors: staging buys nothing here.  Default = the plain kernel; variant 2 forces the staged one (tests, A/B).
     bool aligned = true; // (the staged kernel reads the images in dwords, aligned down from any byte offset: only the base matters, not the pitch)
     for (int i = 0; i < a.nimgs; i++) aligned = aligned && !(reinterpret_cast<uintptr_t>(a.imgs[i]) & 3);
-    if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8) // (the staged kernel knows uint8 sources only)
+    if (a.variant != 2 || a.plane_ch != 16 || !aligned || a.fmt != kFmtU8 || a.alpha_src) // (the staged kernel knows uint8 colour sources only)
     {
         const dim3 grid((max_tw + 31) / 32, (max_th + 7) / 8, a.ntiles), block(256);
-        if (fmt_is_444(a.fmt)) // nothing is sited: one kernel per sample type whatever "yuv_siting" says
+        if (a.alpha_src) // (the engine sends c == 4 uint8 / uint16 HWC images only)
+        {
+            if (a.fmt == kFmtU16) hipLaunchKernelGGL(preproc_tiles<AlphaOf<uint16_t>>, grid, block, 0, st, a);
+            else hipLaunchKernelGGL(preproc_tiles<AlphaOf<uint8_t>>, grid, block, 0, st, a);
+        }
+        else if (fmt_is_444(a.fmt)) // nothing is sited: one kernel per sample type whatever "yuv_siting" says
             with_sample_type(a.fmt, [&](auto src) { hipLaunchKernelGGL((preproc_tiles<decltype(src), true, 0, kVs444>), grid, block, 0, st, a); });
         else if (fmt_is_yuv(a.fmt))
             with_sample_type(a.fmt, [&](auto src) {
@@ -1123,6 +1141,83 @@ static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipS
     else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
 }
 
+// A rational scale other than 4 / 2 / 1 on both axes (rsr_set_out_ratio, rsr_set_out_ratio_xy)?
+static bool generic_ratio(const PostArgs& a)
+{
+    const bool same = a.num_y == a.num && a.den_y == a.den;
+    return a.num > 0 && !(same && a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1));
+}
+
+// ---- alpha through the network (engine option "alpha_net": PostArgs::alpha_dst) --------------------------------------------------------
+// The alpha sample of include/realsr_hip.h ("alpha_net") from A0, A1, A2, what RSR_FMT_F32_CHW would hold for the pixel of the gray image:
+// m = min(((A0 + A1) + A2) * fp32(1 / 3), 1), every operation rounded by itself ...
+__device__ __forceinline__ float alpha_net_mean(float a0, float a1, float a2)
+{
+    return fminf(mul_rn(add_rn(add_rn(a0, a1), a2), (float)(1.0 / 3.0)), 1.f);
+}
+// ... and its store: floor(m * 255 + 0.5) clamped to 0 .. 255, the product and the sum rounded by themselves (m * 255 is not exact in fp32,
+// unlike the fp16-valued colour, so the definition does not leave the contraction to the compiler), or post_store16(m).
+template <typename TO>
+__device__ __forceinline__ TO alpha_net_store(float m)
+{
+    if constexpr (sizeof(TO) == 1) return (uint8_t)fminf(fmaxf(floorf(add_rn(mul_rn(m, 255.f), 0.5f)), 0.f), 255.f);
+    else return post_store16(m);
+}
+
+// The post launch of the alpha pass: one thread makes ONE output pixel of the tile's rectangle and stores ONLY its sample 3 (TO: uint8_t /
+// uint16_t, RGBA).  The three channel values come from the helpers the colour kernels use, so they ARE what RSR_FMT_F32_CHW holds:
+//   K = 1  the x4 image: merged_block<TP, 1> (postproc_tiles' value, clamped to [0, 1]);
+//   K = 2 / 4  out_scale 2 / 1: box_mean of merged_block<TP, K> (postproc_tiles_box);
+//   K = 0  a ratio or pair: area_pixel (postproc_tiles_area).
+// One channel at a time, as in the box kernel.  Lanes run along x.
+template <typename TP, typename TO, int K>
+__global__ __launch_bounds__(256) void postproc_tiles_alpha(const PostArgs a)
+{
+    const BaseTile t = a.tiles[blockIdx.z];
+    const int im = __builtin_amdgcn_readfirstlane(t.img);
+    const int nx = K ? 1 : a.num, Lx = K ? K : 4 * a.den, ny = K ? 1 : a.num_y, Ly = K ? K : 4 * a.den_y; // output pixels per x4 pixel: n / L
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= t.out_w * nx / Lx || gy >= t.out_h * ny / Ly) return;
+    const int w = t.tw * 4, h = t.th * 4;
+    const long long cstep = (long long)w * h;
+    const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
+    const long long ss = a.slot_stride / (long long)sizeof(TP);
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f; // (no array: the loop is not unrolled, and an indexed one would live in scratch)
+#pragma unroll 1
+    for (int q = 0; q < 3; q++)
+    {
+        float d;
+        if constexpr (K == 0) d = area_pixel<TP>(b0 + q * cstep, ss, w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, gx, gy);
+        else
+        {
+            float c[K][K];
+            merged_block<TP, K>(b0 + q * cstep, ss, w, h, gx * K + a.crop, gy * K + a.crop, a.tta, c);
+            if constexpr (K == 1) d = c[0][0];
+            else d = box_mean<K>(c);
+        }
+        v0 = q == 0 ? d : v0, v1 = q == 1 ? d : v1, v2 = q == 2 ? d : v2;
+    }
+    TO* const o = reinterpret_cast<TO*>(a.outs[im] + ((long long)(t.out_y - a.out_row0) * ny / Ly + gy) * (long long)a.out_pitch[im]) +
+                  ((long long)t.out_x * nx / Lx + gx) * 4;
+    o[3] = alpha_net_store<TO>(alpha_net_mean(v0, v1, v2));
+}
+
+template <typename TP>
+static void launch_postproc_alpha(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
+{
+    auto go = [&](auto k, int ow, int oh) {
+        constexpr int K = decltype(k)::value;
+        const dim3 grid((ow + 63) / 64, (oh + 3) / 4, a.ntiles), block(256);
+        if (a.out_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_alpha<TP, uint16_t, K>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((postproc_tiles_alpha<TP, uint8_t, K>), grid, block, 0, st, a);
+    };
+    if (generic_ratio(a)) go(std::integral_constant<int, 0>{}, max_ow * a.num / (4 * a.den), max_oh * a.num_y / (4 * a.den_y));
+    else if (a.box == 2) go(std::integral_constant<int, 2>{}, max_ow / 2, max_oh / 2);
+    else if (a.box > 1) go(std::integral_constant<int, 4>{}, max_ow / 4, max_oh / 4);
+    else go(std::integral_constant<int, 1>{}, max_ow, max_oh);
+}
+
 // ---- YUV 4:2:0 and 4:2:2 output (PostArgs::out_fmt kFmtNV12 / kFmtP010, kFmtNV16 / kFmtP210) ------------------------------------
 // code = floor(v * scale + add) clamped to [0, maxcode] (add = offset + 0.5f), as the sample type stores it: P010 / P210 keep it in the
 // high bits; LOW = true (planar 4:4:4) stores the code itself, the six bits above it 0
@@ -1520,18 +1615,12 @@ static void launch_postproc_yuv444(const PostArgs& a, int max_ow, int max_oh, hi
     });
 }
 
-// A rational scale other than 4 / 2 / 1 on both axes (rsr_set_out_ratio, rsr_set_out_ratio_xy)?
-static bool generic_ratio(const PostArgs& a)
-{
-    const bool same = a.num_y == a.num && a.den_y == a.den;
-    return a.num > 0 && !(same && a.den == 1 && (a.num == 4 || a.num == 2 || a.num == 1));
-}
-
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st)
 {
     if (a.ntiles <= 0) return;
     with_blob_type(a, [&](auto tp) {
         using TP = decltype(tp);
+        if (a.alpha_dst) return launch_postproc_alpha<TP>(a, max_ow, max_oh, st); // (the engine sends c == 4 uint8 / uint16 HWC images only)
         if (fmt_is_444(a.out_fmt))
         { // a planar 4:4:4 surface: one thread per pixel (or two), at every out_scale or ratio, with and without TTA
             with_sample_type(a.out_fmt, [&](auto to) {

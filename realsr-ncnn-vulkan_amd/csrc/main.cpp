@@ -12,6 +12,8 @@
 //   * "-j l:p:s" accepts a single proc count for several GPUs (the reference insists on one per GPU);
 //   * RSR_DEPTH=16|auto (no counterpart: the reference is 8-bit throughout): 16-bit PNG / PNM in, 16-bit PNG out through
 //     rsr_process_fmt (RSR_FMT_U16_HWC); unset or 8, every byte of the 8-bit route is what it was;
+//   * RSR_ALPHA=net (no counterpart): the alpha of an RGBA image walks the network as a gray image (rsr_set_option "alpha_net") instead
+//     of taking the bicubic; an image whose alpha is fully opaque keeps the bicubic and its one pass;
 //   * video mode (no counterpart): an input that ends in .y4m, or is "-" (stdin), is a YUV4MPEG2 stream and runs through one rsr_video
 //     session to a .y4m output or "-" (stdout) -- run_video below, y4m_io.h.
 #include <dirent.h>
@@ -51,6 +53,8 @@ static void print_usage()
     fprintf(stderr, "\nenvironment:\n");
     fprintf(stderr, "  RSR_DEPTH=8|16|auto  sample depth (default=8): 16 = every image runs as 16-bit RGB(A) and is written as a 16-bit .png\n");
     fprintf(stderr, "                       (8-bit sources widened by x257); auto = 16-bit png/pnm inputs with a .png output keep their 16 bits\n");
+    fprintf(stderr, "  RSR_ALPHA=net|bicubic alpha of RGBA images (default=bicubic): net = through the network as a gray image, about twice the\n");
+    fprintf(stderr, "                       time; a fully opaque alpha stays opaque and costs one pass\n");
 }
 
 static std::vector<int> parse_int_list(const char* s)
@@ -121,7 +125,28 @@ struct Task
     int id = 0;
     std::string inpath, outpath;
     Image inimage, outimage;
+    bool opaque = false; // RSR_ALPHA=net: an RGBA image whose alpha samples all hold the maximum (it runs with "alpha_net" 0)
 };
+
+// Do all alpha samples of an RGBA image hold the maximum of its depth (255 / 65535)?  One pass over the decoded image on the host.
+static bool alpha_all_max(const Image& im)
+{
+    if (im.elempack != 4) return false;
+    const size_t n = size_t(im.w) * size_t(im.h);
+    if (im.depth == 16)
+    {
+        const uint16_t* p = im.data16();
+        for (size_t i = 0; i < n; i++)
+            if (p[4 * i + 3] != 65535) return false;
+    }
+    else
+    {
+        const uint8_t* p = im.data();
+        for (size_t i = 0; i < n; i++)
+            if (p[4 * i + 3] != 255) return false;
+    }
+    return true;
+}
 
 class TaskQueue // bounded at 8 like the reference (main.cpp:141)
 {
@@ -392,6 +417,21 @@ int main(int argc, char** argv)
         else if (!v.empty() && v != "8")
         {
             fprintf(stderr, "invalid RSR_DEPTH '%s' (8, 16 or auto)\n", de);
+            return -1;
+        }
+    }
+    // RSR_ALPHA=net|bicubic (no flag of the reference's surface is taken for it): how the alpha of an RGBA image is made.  bicubic / unset:
+    // ncnn's bicubic x4, as ever.  net: the alpha walks the network as a gray image (rsr_set_option "alpha_net": a second pass over the
+    // image's tiles, about twice the time) -- except for an image whose alpha is fully opaque, the usual opaque PNG saved as RGBA, which
+    // keeps its opaque alpha and its one pass.  On the 8-bit and the RSR_DEPTH 16-bit route alike.
+    bool alpha_net = false;
+    if (const char* ae = getenv("RSR_ALPHA"))
+    {
+        const std::string v(ae);
+        if (v == "net") alpha_net = true;
+        else if (!v.empty() && v != "bicubic")
+        {
+            fprintf(stderr, "invalid RSR_ALPHA '%s' (net or bicubic)\n", ae);
             return -1;
         }
     }
@@ -679,6 +719,11 @@ int main(int argc, char** argv)
                     failures++;
                     continue;
                 }
+                if (alpha_net && v->inimage.elempack == 4)
+                {
+                    v->opaque = alpha_all_max(v->inimage);
+                    if (verbose) fprintf(stderr, "%s: %s\n", v->inpath.c_str(), v->opaque ? "alpha is fully opaque: bicubic alpha, one pass (RSR_ALPHA=net)" : "alpha through the network, two passes (RSR_ALPHA=net)");
+                }
                 // an RGBA image cannot be a jpg: write <name>.png instead (main.cpp:278-288)
                 const std::string oext = imgio::lower_ext(v->outpath);
                 if (!deep && v->inimage.elempack == 4 && (oext == "jpg" || oext == "jpeg"))
@@ -693,6 +738,10 @@ int main(int argc, char** argv)
             }
         });
 
+    // RSR_ALPHA=net: "alpha_net" is an option of the context, and the proc threads of a gpu share one: an RGBA image sets it for itself --
+    // 0 when opaque -- and keeps the other RGBA images of its gpu out until its call returns.  RGB images, which the option does not
+    // concern, run beside it as ever.
+    std::vector<std::mutex> alpha_mu(static_cast<size_t>(ngpu));
     std::vector<std::thread> procs;
     for (int g = 0; g < ngpu; g++)
         for (int j = 0; j < jobs_proc[size_t(g)]; j++)
@@ -702,6 +751,13 @@ int main(int argc, char** argv)
                     std::unique_ptr<Task> v = toproc.get();
                     if (v->id == kEnd) return;
                     int prc;
+                    std::unique_lock<std::mutex> alpha_lk;
+                    if (alpha_net && v->inimage.elempack == 4)
+                    { // (a split image is the only one there is: every context of the group gets the value)
+                        alpha_lk = std::unique_lock<std::mutex>(alpha_mu[split_one_image ? 0 : size_t(g)]);
+                        for (int k = 0; k < ngpu; k++)
+                            if (split_one_image || k == g) rsr_set_option(ctxs[size_t(k)], "alpha_net", v->opaque ? 0 : 1);
+                    }
                     if (split_one_image && v->inimage.depth == 16)
                     { // rsr_process_fmt has no tile ranges: a single 16-bit image runs on the first gpu
                         if (verbose) fprintf(stderr, "%s: a 16-bit image is not split over gpus: it runs on gpu %d\n", v->inpath.c_str(), gpuid[0]);

@@ -128,7 +128,9 @@ def upscale(sr, x, out=None, out_dtype=None):
     descriptor -- a window of a larger canvas, say.  ValueError otherwise, before anything is launched.  It must not overlap x.
     16-bit RGB(A): x may be a uint16 / int16 (H, W, 3 | 4) tensor (RSR_FMT_U16_HWC: full-range words, read unsigned whatever the dtype says);
     the result has the same dtype.  out_dtype (integer HWC inputs only): torch.uint8, torch.uint16 or torch.int16 -- the depth of the
-    result, so that 8 -> 16 and 16 -> 8 bits are one call; with out= given, out.dtype must equal it."""
+    result, so that 8 -> 16 and 16 -> 8 bits are one call; with out= given, out.dtype must equal it.
+    RGBA: the alpha of an (H, W, 4) input is the bicubic x4, or with sr.alpha_net = 1 the network's result for the gray image of the alpha
+    (option "alpha_net": a second pass over the tiles, about twice the frame time); nothing here knows the option, the engine does."""
     fmt, batched = _check(sr, x)
     ydtype = x.dtype
     if out_dtype is not None:
@@ -564,7 +566,8 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None, chroma=420):
     every launch depends on the mask, so the host has to see it: this is the only host wait, and it is what the skipped tiles are paid
     with --; the masked call.
     chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them.  chroma=444: x, prev_x, prev_y and out are
-    planar 4:4:4 images as upscale_yuv(..., chroma=444) takes them."""
+    planar 4:4:4 images as upscale_yuv(..., chroma=444) takes them.
+    sr.alpha_net = 1 holds here as in upscale: the marked tiles of an RGBA frame run both passes, and the diff compares the alpha bytes too."""
     _check_chroma(chroma, "upscale_delta")
     fmt, w, h, c, _ = _image_desc(sr, x, "x", chroma)
     if prev_x is not None and not _same_layout(x, prev_x):
@@ -636,7 +639,8 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420)
     torch.cuda.current_stream() (the side stream for the null stream, as in upscale_delta): the diff of all pairs, ONE asynchronous copy
     of the masks into pinned memory, ONE stream synchronisation, the sequence call.
     chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them.  chroma=444: every frame is a planar 4:4:4
-    image as upscale_yuv(..., chroma=444) takes it -- a list of them, or a stacked (N, 3, H, W) uint8 / int16 tensor."""
+    image as upscale_yuv(..., chroma=444) takes it -- a list of them, or a stacked (N, 3, H, W) uint8 / int16 tensor.
+    sr.alpha_net = 1 holds here as in upscale, for the tiles of RGBA frames that run."""
     _check_chroma(chroma, "upscale_sequence")
     stacked = isinstance(frames, torch.Tensor)
     if stacked:
