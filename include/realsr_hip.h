@@ -970,6 +970,16 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *   "ws_clamp_mb"       test hook: plant the workspace bound a failed allocation leaves behind (< 0 clears it; see rsr_get_stat)
  *   "ws_fail_above_mb"  test hook: workspaces above this size fail to allocate, every time (a persistently fragmented device; < 0 off);
  *                       stat "ws_failures" counts the refusals, "clamp_backoff" the calls between two attempts at the full size
+ *   "ws_poison"         test hook: 0 [default] = off; 0x10000 + p = every workspace set-up of a call first fills EVERY byte of every workspace
+ *                       buffer with the 16-bit pattern p, then zeroes exactly what a change of slot capacity inside an existing
+ *                       allocation zeroes (the 64-byte plane guards of the new layout over the whole allocation, and the input
+ *                       buffer IN) and nothing more: the worst history a workspace can have in production.  No output may depend
+ *                       on it (tests/test_gpu_ws_hygiene.py: 0xFFFF = NaN in every storage type, 0x7BFF = 65504).  Off: the calls
+ *                       made are exactly those without the hook
+ *   "test_redzone"      test hook: bytes (a multiple of 256; 0 [default] = off).  rsr_conv3x3 / rsr_conv3x3_res / rsr_conv3x3_res_precise place
+ *                       their input, residual and output buffers between two red zones of that size, filled -- like the whole output
+ *                       buffer, in place of zeros -- with the "ws_poison" pattern (0xFFFF without one); stat "test_redzone_dirty" is the
+ *                       number of red-zone bytes the last such launch changed (-1: it had none)
  *   "trace_conv"        conv index whose launch records s_memtime stamps (rsr_get_trace; -DRSR_EXPERIMENT -DRSR_FLOW_TRACE builds), -1 off
  *   "alternate_order"   1 [default]: every second conv walks its work items backwards (starts on the tiles the previous conv
  *                       touched last -> Infinity Cache hits); 0: always forwards
@@ -993,6 +1003,11 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *                       images they carried, the widest one, those whose images differed in size; "device_direct": rsr_process_device[_fmt | _batch] calls that ran on the caller's own stream
  *   "batch_calls" / "batch_images" / "batch_groups"  rsr_process_device_batch calls, the images they enqueued and the tile batches those went in (the merged_* stats count the cross-call combiner alone)
  *   "workspace_mb"      device memory the workspace holds, "ws_clamp_mb" the bound a failed allocation left behind (-1 = none)
+ *   "ws_guard_dirty"    test hook: waits for the context's streams and counts, on the host, the non-zero bytes among (a) the 64-byte guard in
+ *                       front of every plane of the current workspace layout, over the whole allocation of every guarded buffer, and
+ *                       (b) channels 3 .. 31 of the input buffer IN.  Both are invariants every convolution's zero padding rests on --
+ *                       no kernel ever writes either -- and the count is 0 after every call (tests/test_gpu_ws_hygiene.py).  -1 while the
+ *                       workspace has no layout (before the first call, after rsr_selfcheck)
  *   "lanes", "lane_in_mb", "lane_out_mb"   rsr_process lanes created so far and the device image buffers they hold (a member of
  *                       rsr_process_group allocates only the output rows of its tile range)
  *   "last_test_us"      HIP-event time of the last rsr_conv3x3 / rsr_conv3x3_res launch (with option "test_repeat" = N the

@@ -672,6 +672,15 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     }
     else if (k == "ws_clamp_mb") *value = e.ws_clamp_bytes < 0 ? -1.0 : double(e.ws_clamp_bytes) / 1048576.0;
     else if (k == "ws_failures") *value = double(e.ws_failures);
+    else if (k == "ws_poison") *value = double(e.ws_poison);
+    else if (k == "ws_guard_dirty")
+    {
+        const long long n = e.ws_guard_dirty();
+        if (n < -1) return e.fail(RSR_E_DEVICE, "ws_guard_dirty: workspace readback failed");
+        *value = double(n);
+    }
+    else if (k == "test_redzone") *value = double(e.test_redzone);
+    else if (k == "test_redzone_dirty") *value = double(e.test_redzone_dirty);
     else if (k == "pool_workers") *value = double(share_pool_stat(0));
     else if (k == "pool_inline_runs") *value = double(share_pool_stat(1));
     else if (k == "clamp_backoff") *value = double(e.clamp_backoff);
@@ -851,6 +860,17 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     }
     else if (k == "ws_fail_above_mb") // test hook: workspaces above this size fail to allocate, persistently (< 0: off)
         ctx->e.ws_fail_above_bytes = value < 0 ? -1 : value * 1048576;
+    else if (k == "ws_poison") // test hook: every workspace set-up starts from buffers full of this 16-bit pattern (bit 16 set: on; 0: off)
+    {
+        if (value != 0 && (value < 0x10000 || value > 0x1FFFF)) return ctx->e.fail(RSR_E_ARG, "ws_poison must be 0 or 0x10000 + a 16-bit pattern");
+        ctx->e.ws_poison = int(value);
+    }
+    else if (k == "test_redzone") // test hook: the one-launch entry points (rsr_conv3x3 ...) run between red zones of this many bytes (0: off)
+    {
+        if (value < 0 || value > (1 << 20) || value % 256) return ctx->e.fail(RSR_E_ARG, "test_redzone must be a multiple of 256 between 0 and 1 MiB");
+        ctx->e.test_redzone = value;
+        ctx->e.test_redzone_dirty = -1;
+    }
     else if (k == "num_cu")
     {
         if (value < 8 || value > 1024) return ctx->e.fail(RSR_E_ARG, "num_cu out of range");

@@ -633,7 +633,8 @@ int Engine::get_plan(int w, int h, int c, int tile0, int tile1, int nimg, Plan*&
 // Invariant: every guard of the CURRENT layout inside the whole allocation is zero.  A fresh allocation is zeroed
 // completely; when the layout (plane stride) changes inside an existing allocation, the guards of the new layout are
 // zeroed over the WHOLE allocation (not just the slots this call uses: a later call with more slots of the same layout
-// must not find stale pixels where its guards are).  Guards are never written afterwards.
+// must not find stale pixels where its guards are).  Guards are never written afterwards: stat "ws_guard_dirty" counts their non-zero
+// bytes, and tests/test_gpu_ws_hygiene.py finds none after any call.
 int Engine::ensure_planes(DevBuf& b, size_t bytes, long long plane_bytes, bool layout_changed, bool zero_all, hipStream_t st)
 {
     const bool grow = !(b.bytes >= bytes && b.p);
@@ -658,6 +659,27 @@ int Engine::ensure_workspace(int nslots, long long cap, hipStream_t st)
         ws_failures++;
         return fail(RSR_E_NOMEM, "workspace of " + std::to_string(total >> 20) + " MiB refused (ws_fail_above_mb test hook)");
     }
+    if (ws_poison)
+    { // test hook (option "ws_poison"): the worst history a workspace can have.  Every byte of every buffer takes the pattern; then exactly
+      // what a change of slot capacity inside an existing allocation does below -- the guards of this layout zeroed over the whole
+      // allocation, the zero_all buffers zeroed -- and nothing more.  Whatever else a call reads, it must have written itself.
+        for (int i = 0; i < kWsCount; i++)
+            if (const int rc = ensure(ws[i], size_t(lay.bytes(i, nslots)))) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        const unsigned short pat = (unsigned short)(ws_poison & 0xFFFF);
+        for (const DevBuf& b : ws)
+        {
+            if (!b.p || !b.bytes) continue;
+            HIP_TRY(hipMemsetD16Async(b.p, pat, b.bytes / 2, st));
+            if (b.bytes & 1) HIP_TRY(hipMemsetAsync(static_cast<char*>(b.p) + b.bytes - 1, pat & 0xFF, 1, st));
+        }
+        for (int i = 0; i < kWsCount; i++) // (no buffer grows any more: ensure_planes takes its layout-change branch)
+            if (WsLayout::guarded(i))
+                if (const int rc = ensure_planes(ws[i], size_t(lay.bytes(i, nslots)), lay.plane_bytes(i), true, kWsTable[i].zero_all, st)) return rc;
+        HIP_TRY(hipGetLastError());
+        ws_cap_px = cap;
+        return RSR_OK;
+    }
     if (any_grow || lc) HIP_TRY(hipStreamSynchronize(st)); // nothing in flight may use a buffer that is freed / re-laid-out
     for (int i = 0; i < kWsCount; i++)
         if (const size_t need = size_t(lay.bytes(i, nslots)); const int rc = WsLayout::guarded(i) ? ensure_planes(ws[i], need, lay.plane_bytes(i), lc, kWsTable[i].zero_all, st) : ensure(ws[i], need))
@@ -672,6 +694,39 @@ void Engine::free_workspace(hipStream_t st)
     (void)hipStreamSynchronize(st);
     for (DevBuf& wb : ws) (void)hipFree(wb.p), wb = DevBuf(); // (freeing a null pointer does nothing)
     ws_cap_px = 0;
+}
+
+// Stat "ws_guard_dirty" (test hook): the two invariants of the workspace's zeros, counted on the host.  Every guard of the current layout
+// over the whole allocation of every guarded buffer (one strided copy per buffer: 64 B at a stride of plane_bytes), and IN's channels
+// 3 .. 31 -- the bytes behind the first three halfs of a pixel of a slot's plane 0, and all of its plane 1.  Returns the number of
+// non-zero bytes, -1 without a layout, -2 when a copy failed.
+long long Engine::ws_guard_dirty()
+{
+    static_assert(kWsTable[kWsIn].planes == 2 && !kWsTable[kWsIn].lo_planes && kPlaneCh == 16, "IN: one plane of channels 0 .. 15, one of 16 .. 31");
+    if (!ws_cap_px) return -1;
+    if (hipSetDevice(device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -2; // every stream of the engine: the lanes' too
+    const WsLayout lay = layout();
+    long long dirty = 0;
+    std::vector<unsigned char> h;
+    for (int b = 0; b < kWsCount; b++)
+    {
+        if (!WsLayout::guarded(b) || !ws[b].p) continue;
+        const size_t pb = size_t(lay.plane_bytes(b)), n = ws[b].bytes / pb;
+        if (!n) continue;
+        h.assign(n * kGuard, 0);
+        if (hipMemcpy2D(h.data(), kGuard, ws[b].p, pb, kGuard, n, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+        for (const unsigned char v : h) dirty += v != 0;
+    }
+    if (const DevBuf& in = ws[kWsIn]; in.p)
+    {
+        const size_t pb = size_t(lay.plane_bytes(kWsIn)), n = in.bytes / pb;
+        h.assign(in.bytes, 0);
+        if (hipMemcpy(h.data(), in.p, in.bytes, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+        for (size_t k = 0; k < n; k++) // planes alternate: channels 0 .. 15, channels 16 .. 31
+            for (long long p = 0; p < ws_cap_px; p++)
+                for (size_t i = (k & 1) ? 0 : 6; i < size_t(WsLayout::kPxBytes); i++) dirty += h[k * pb + kGuard + size_t(p) * WsLayout::kPxBytes + i] != 0;
+    }
+    return dirty;
 }
 
 // ---- profiling ------------------------------------------------------------------------------
@@ -2606,6 +2661,21 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
         if (res_lo) put_lo(hres, size_t(res_lo_off), res_lo);
     }
     ScratchBuf d_w, d_in, d_out, d_tab, d_res;
+    // Option "test_redzone" (test hook): input, residual and output lie between two red zones of rz bytes that hold the ws_poison pattern
+    // (0xFFFF without one), and so does the whole output in place of zeros: a store outside a buffer changes a red zone, a store that is
+    // never made leaves NaN, and a read outside a buffer meets NaN where the next plane's zero guard used to be.  The kernel is handed the
+    // same pointers relative to the payload; the input's own guards and padded channels stay zero.
+    const size_t rz = size_t(test_redzone);
+    const uint16_t rz_pat = uint16_t(ws_poison ? ws_poison & 0xFFFF : 0xFFFF);
+    test_redzone_dirty = -1;
+    auto with_zones = [&](std::vector<uint16_t>& v) { // [rz | v | rz]
+        if (!rz || v.empty()) return;
+        v.insert(v.begin(), rz / 2, rz_pat);
+        v.insert(v.end(), rz / 2, rz_pat);
+    };
+    const size_t in_bytes = hin.size() * 2, res_bytes = hres.size() * 2, out_bytes = hout.size() * 2; // of the payloads
+    with_zones(hin);
+    with_zones(hres);
     std::vector<WorkItem> items;
     // test_repeat > 1 (measurement aid): the same blocks N times in ONE launch -- after the first pass every patch and every
     // output line is in the L2s, i.e. the launch shows what this conv costs when nothing goes to HBM (tools/l2_bound_probe.py)
@@ -2613,12 +2683,12 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
         append_block_items(items, 0, H, W, 0, 0, 0, 0, 0, fold_cols);
     const TileDim td{h, w};
     if ((rc = ensure(d_w, pk.size())) != RSR_OK || (rc = ensure(d_in, hin.size() * 2)) != RSR_OK ||
-        (rc = ensure(d_out, hout.size() * 2)) != RSR_OK || (rc = ensure(d_tab, 256 + items.size() * sizeof(WorkItem))) != RSR_OK ||
+        (rc = ensure(d_out, out_bytes + 2 * rz)) != RSR_OK || (rc = ensure(d_tab, 256 + items.size() * sizeof(WorkItem))) != RSR_OK ||
         (!hres.empty() && (rc = ensure(d_res, hres.size() * 2)) != RSR_OK))
         return rc;
     hipError_t he = hipMemcpy(d_w.p, pk.data(), pk.size(), hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(d_in.p, hin.data(), hin.size() * 2, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemsetAsync(d_out.p, 0, hout.size() * 2, stream);
+    if (he == hipSuccess) he = rz ? hipMemsetD16Async(d_out.p, rz_pat, (out_bytes + 2 * rz) / 2, stream) : hipMemsetAsync(d_out.p, 0, out_bytes, stream);
     if (he == hipSuccess) he = hipMemcpy(d_tab.p, &td, sizeof td, hipMemcpyHostToDevice);
     if (he == hipSuccess) he = hipMemcpy(static_cast<char*>(d_tab.p) + 256, items.data(), items.size() * sizeof(WorkItem), hipMemcpyHostToDevice);
     if (he == hipSuccess && !hres.empty()) he = hipMemcpy(d_res.p, hres.data(), hres.size() * 2, hipMemcpyHostToDevice);
@@ -2626,7 +2696,7 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
     {
         ConvArgs a;
         std::memset(&a, 0, sizeof a);
-        a.src0 = PlaneSrc{static_cast<char*>(d_in.p) + kGuard, 0, (long long)ipl_b};
+        a.src0 = PlaneSrc{static_cast<char*>(d_in.p) + rz + kGuard, 0, (long long)ipl_b};
         a.n0 = np;
         a.lvl_in = 0;
         a.lvl_out = ups ? 1 : 0;
@@ -2649,13 +2719,13 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
             }
             if (res)
             {
-                const PlaneSrc rp{static_cast<char*>(d_res.p) + kGuard, 0, (long long)ipl_b};
+                const PlaneSrc rp{static_cast<char*>(d_res.p) + rz + kGuard, 0, (long long)ipl_b};
                 if (own_res) { a.res2 = rp; a.res2_kind = 1; a.s2 = s2; a.lo2_off = res_lo_off; }
                 else { a.res1 = rp; a.res1_kind = 1; a.lo1_off = res_lo_off; } // trunk_conv form: v = s1*(conv+b) + res  (s2 unused)
             }
             a.out_lo_off = out_lo_off;
         }
-        a.out16 = PlaneSrc{d_out.p, 0, (long long)opx * pch * 2};
+        a.out16 = PlaneSrc{static_cast<char*>(d_out.p) + rz, 0, (long long)opx * pch * 2};
         a.items = reinterpret_cast<const WorkItem*>(static_cast<const char*>(d_tab.p) + 256);
         a.nitems = int(items.size());
         a.dims = static_cast<const TileDim*>(d_tab.p);
@@ -2671,7 +2741,20 @@ int Engine::conv_test(const uint16_t* in, int cin, int h, int w, int ups, const 
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         if (he == hipSuccess) he = hipGetLastError();
-        if (he == hipSuccess) he = hipMemcpy(hout.data(), d_out.p, hout.size() * 2, hipMemcpyDeviceToHost);
+        if (he == hipSuccess) he = hipMemcpy(hout.data(), static_cast<char*>(d_out.p) + rz, out_bytes, hipMemcpyDeviceToHost);
+        if (he == hipSuccess && rz)
+        { // the six red zones, byte by byte against the pattern
+            std::vector<uint16_t> z(rz / 2);
+            long long dirty = 0;
+            const std::pair<const DevBuf*, size_t> bufs[3] = {{&d_in, in_bytes}, {&d_res, res_bytes}, {&d_out, out_bytes}};
+            for (const auto& [buf, payload] : bufs)
+                for (int side = 0; side < 2 && payload && he == hipSuccess; side++)
+                {
+                    he = hipMemcpy(z.data(), static_cast<const char*>(buf->p) + (side ? rz + payload : 0), rz, hipMemcpyDeviceToHost);
+                    for (const uint16_t v : z) dirty += ((v ^ rz_pat) & 0xFF ? 1 : 0) + ((v ^ rz_pat) >> 8 ? 1 : 0);
+                }
+            if (he == hipSuccess) test_redzone_dirty = dirty;
+        }
     }
     if (he != hipSuccess) return fail(RSR_E_DEVICE, std::string("conv_test: ") + hipGetErrorString(he));
     if (rc != RSR_OK) return rc;

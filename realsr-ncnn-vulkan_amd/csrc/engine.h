@@ -338,6 +338,13 @@ struct Engine
     int clamp_calls_left = 0;
     long long ws_fail_above_bytes = -1; // test hook: workspaces above this size fail with RSR_E_NOMEM (a persistently fragmented device)
     long long ws_failures = 0;          // ... how often it fired (stat "ws_failures")
+    // Test hooks of the workspace's contents (include/realsr_hip.h "ws_poison"; tests/test_gpu_ws_hygiene.py).  ws_poison: 0 = off, else bit 16 +
+    // a 16-bit pattern that every ensure_workspace writes over every byte of every buffer before it zeroes what a change of slot capacity zeroes.
+    int ws_poison = 0;
+    long long ws_guard_dirty(); // stat: non-zero bytes in the guards of the current layout and in IN's channels 3 .. 31; -1 without a layout.  mu held
+    // conv_test inside red zones of this many bytes (option "test_redzone", 0 = off) ...
+    long long test_redzone = 0;
+    long long test_redzone_dirty = -1; // ... and how many of their bytes the last launch changed (stat; -1: the last conv_test had none)
     int tail_group_slots = 0; // slots per launch group of the 2x / 4x convs (0 = the whole batch at once), see run_network
     int max_lanes = 16; // (small images are merged across calls: the more callers in flight, the fuller the launches)
     size_t chunk_bytes = size_t(16) << 20; // download chunk for pageable destinations

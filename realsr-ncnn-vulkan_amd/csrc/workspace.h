@@ -19,7 +19,7 @@ struct WsRow
 };
 constexpr WsRow kWsRdbRow = {1, 12, 2, false, {}}; // x (4 planes) + the dense x1..x4 (4 x 2); the lo pair planes of x
 constexpr WsRow kWsTable[kWsCount] = {
-    {1, 2, 0, true, {}},        // IN: the 3-channel input padded to 32 channels; channels 3.. are never written and must stay zero
+    {1, 2, 0, true, {}},        // IN: the 3-channel input padded to 32 channels; channels 3.. are never written and must stay zero (stat "ws_guard_dirty")
     {1, 4, 2, false, {}},       // FEA: conv_first's result, the global skip; the residual stream of precise mode starts here
     kWsRdbRow, kWsRdbRow, kWsRdbRow,
     {4, 4, 0, false, {}},       // UP1 @2x

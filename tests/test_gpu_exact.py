@@ -4,7 +4,11 @@ The layer tests of tests/test_gpu_parity.py / test_gpu_precise.py use random nor
 summation order: they need a tolerance, and a tolerance lets a kernel that is wrong in a systematic way pass (round toward zero, a
 LeakyReLU slope or a bias held as fp16, a product rounded to fp16 in one step instead of through fp32).  Here the operands are chosen
 so that every partial sum is exact in fp32 in any order (tests/exact_conv.py): what is left are the epilogues' roundings, which the
-mirror restates, and every output is compared with np.array_equal."""
+mirror restates, and every output is compared with np.array_equal.
+
+The entry points behind these tests size their buffers exactly and used to pre-set the output to 0: a store past the last plane was
+invisible, a read just past a plane met the next plane's zero guard, and a store never made left a legal 0.  The module's context
+therefore runs them between red zones (option "test_redzone"), and every launch goes through launch() below."""
 import os
 
 import numpy as np
@@ -22,12 +26,28 @@ RES_COMBOS = ((0, 0, 256), (1, 0, 256), (0, 0, 8), (1, 0, 8), (0, 32, 8), (4, 0,
 PREC_COMBOS = ((0, 0, 256), (0, 0, 8), (0, 32, 8), (4, 0, 8), (1, 0, 256))
 
 
+REDZONE = 4096   # bytes; the widest swept plane row is 66 px x 32 B = 2112 B, and one store instruction moves 1 KiB
+
+
 @pytest.fixture(scope="module")
 def sr(model_dir):
+    """The one-launch entry points run between red zones (option "test_redzone"): input, residual and output buffers lie between 4 KiB
+    of NaN and the output starts as NaN, not 0 -- a store that is never made is a certain mismatch, and launch() looks at the zones."""
     s = R.RealSR(0)
     s.load(os.path.join(model_dir, "x4.param"), os.path.join(model_dir, "x4.bin"))
+    s.set_option("test_redzone", REDZONE)
     yield s
+    s.set_option("test_redzone", 0)
     s.close()
+
+
+def launch(sr, fn, *args, **kw):
+    """sr.conv3x3 / conv3x3_res / conv3x3_res_precise, and no byte of the red zones around its buffers changed."""
+    got = fn(*args, **kw)
+    assert sr.get_stat("test_redzone") == REDZONE
+    dirty = sr.get_stat("test_redzone_dirty")
+    assert dirty == 0, "%d red-zone bytes changed: a store outside the buffers" % dirty
+    return got
 
 
 def combos(sr, cs):
@@ -84,7 +104,7 @@ def test_accumulator_and_fp16_conversion_round_to_nearest_even(sr):
     wide = exact.astype(np.float16)                                           # one rounding from the exact sum
     assert not np.array_equal(want.view(np.uint16), rtz.view(np.uint16)) and not np.array_equal(want.view(np.uint16), wide.view(np.uint16))
     for c in combos(sr, LAYER_COMBOS[:2]):
-        got = sr.conv3x3(x, wt, b)
+        got = launch(sr, sr.conv3x3, x, wt, b)
         msg = same16(got, want)
         if msg:
             msg += " | equals round-toward-zero: %s, equals a single rounding of the exact sum: %s" % (
@@ -117,7 +137,7 @@ def test_fp16_subnormals_are_kept_on_both_sides(sr):
         assert sub.mean() > 0.3                                                 # subnormal results, and normal ones next to them
         flushed_out = np.where(sub, np.float16(0) * want, want).astype(np.float16)
         for c in combos(sr, LAYER_COMBOS[:2]):
-            got = sr.conv3x3(x, wt, b, lrelu=lrelu)
+            got = launch(sr, sr.conv3x3, x, wt, b, lrelu=lrelu)
             msg = same16(got, want)
             if msg:
                 msg += " | equals subnormal inputs flushed: %s, subnormal results flushed (ignoring the sign of zero): %s" % (
@@ -142,7 +162,7 @@ def _layer(sr, cin, cout, h, w, ups, lrelu, cs, seed):
     X.assert_exact(x, wt, b)
     want = X.epi1(X.conv_sum(x, wt, b, ups=ups), lrelu)
     for c in combos(sr, cs):
-        got = sr.conv3x3(x, wt, b, lrelu=lrelu, upsample2x=ups)
+        got = launch(sr, sr.conv3x3, x, wt, b, lrelu=lrelu, upsample2x=ups)
         assert got.shape == want.shape
         msg = same16(got, want)
         assert not msg, (c, msg)
@@ -194,7 +214,7 @@ def test_impulse_responses(sr, cin, cout, h, w):
         xin = X.impulse_input(cin, h, w, hits)
         want = X.epi1(X.impulse_sum(wt, b, h, w, hits), lrelu)
         for c in combos(sr, LAYER_COMBOS[:2] + LAYER_COMBOS[4:6]):
-            msg = same16(sr.conv3x3(xin, wt, b, lrelu=lrelu), want)
+            msg = same16(launch(sr, sr.conv3x3, xin, wt, b, lrelu=lrelu), want)
             assert not msg, (c, hits, msg)
 
 
@@ -220,7 +240,7 @@ def test_exact_residual_epilogues(sr, cin, h, w):
     cs = RES_COMBOS if h * w < 10000 else RES_COMBOS[:2] + RES_COMBOS[4:5]
     for c in combos(sr, cs):
         for name, ((s1, own, rr, s2), want) in forms.items():
-            msg = same16(sr.conv3x3_res(x, wt, b, s1, own_input_residual=own, res=rr, s2=s2), want)
+            msg = same16(launch(sr, sr.conv3x3_res, x, wt, b, s1, own_input_residual=own, res=rr, s2=s2), want)
             assert not msg, (name, c, msg)
 
 
@@ -251,7 +271,7 @@ def test_exact_precise_epilogues(sr, cin, h, w):
     cs = PREC_COMBOS if h * w < 10000 else PREC_COMBOS[:1] + PREC_COMBOS[2:3]
     for c in combos(sr, cs):
         for name, ((s1, own, xl, rh, rl, s2), (want_hi, want_lo)) in forms.items():
-            hi, lo = sr.conv3x3_res_precise(x, wt, b, s1, own_input_residual=own, x_lo=xl, res=rh, res_lo=rl, s2=s2)
+            hi, lo = launch(sr, sr.conv3x3_res_precise, x, wt, b, s1, own_input_residual=own, x_lo=xl, res=rh, res_lo=rl, s2=s2)
             msg = same16(hi, want_hi)
             assert not msg, (name, c, "hi", msg)
             bad = np.argwhere(lo != want_lo)

@@ -7,7 +7,8 @@ variants) is where this project gets rewritten, and a slip there worth less than
 
   A. ONE launch per kernel class on exactly summable operands (tests/exact_conv.py) at every plane width 1 .. 66 and every plane height
      1 .. 36: every residue of w % 32 with 0, 1 and 2 full blocks to its left, both sides of the fold limit kFoldMaxW = 14, every residue
-     of h % 16 and of the 4-row groups, a pair of block rows plus an unpaired one.
+     of h % 16 and of the 4-row groups, a pair of block rows plus an unpaired one.  Every launch runs between red zones (option
+     "test_redzone", tests/test_gpu_exact.py launch): no byte outside the buffers is written, and the output starts as NaN, not 0.
   B. The tile loop on the ONE-BLOCK exact model (tests/depth_ref.py; 21 convs, every kernel class present, 56 - 119 us per padded pixel in
      the numpy mirror): images smaller than the halo, single rows and columns, tiles larger than the image, padded widths on both sides
      of a block and of the fold limit, the margin rings of other prepaddings, TTA with non-square edge tiles, several batches, precise
@@ -151,11 +152,14 @@ def ctxs(nets):
 
 @pytest.fixture
 def ctx(ctxs):
+    """Part A runs between red zones (option "test_redzone", tests/test_gpu_exact.py launch): it concerns the one-launch entry points alone."""
     for s in ctxs.values():
         reset(s)
+        s.set_option("test_redzone", E.REDZONE)
     yield ctxs
     for s in ctxs.values():
         reset(s)
+        s.set_option("test_redzone", 0)
 
 
 _refs = {}
@@ -211,7 +215,7 @@ def run_class(sr, name, group):
             X.assert_exact(x, wt, b)
             want = X.epi1(X.conv_sum(x, wt, b, ups=form == "ups"), form != "plain")
             for c in E.combos(sr, CFG):
-                got = sr.conv3x3(x, wt, b, lrelu=form != "plain", upsample2x=form == "ups")
+                got = E.launch(sr, sr.conv3x3, x, wt, b, lrelu=form != "plain", upsample2x=form == "ups")
                 assert got.shape == want.shape, (name, h, w, c)
                 msg = E.same16(got, want)
                 assert not msg, (name, (h, w), c, msg)
@@ -223,13 +227,13 @@ def run_class(sr, name, group):
         if form == "res":
             want = X.epi2(acc, S, r, S)
             for c in E.combos(sr, RES_CFG):
-                msg = E.same16(sr.conv3x3_res(x, wt, b, S, own_input_residual=True, res=r, s2=S), want)
+                msg = E.same16(E.launch(sr, sr.conv3x3_res, x, wt, b, S, own_input_residual=True, res=r, s2=S), want)
                 assert not msg, (name, (h, w), c, msg)
         else:
             x_lo, r_lo = X.grid_lo(rng, x[:cout]), X.grid_lo(rng, r)
             want_hi, want_lo = X.epi_precise(acc, S, x_lo, r, r_lo, S)
             for c in E.combos(sr, PREC_CFG):
-                hi, lo = sr.conv3x3_res_precise(x, wt, b, S, own_input_residual=True, x_lo=x_lo, res=r, res_lo=r_lo, s2=S)
+                hi, lo = E.launch(sr, sr.conv3x3_res_precise, x, wt, b, S, own_input_residual=True, x_lo=x_lo, res=r, res_lo=r_lo, s2=S)
                 msg = E.same16(hi, want_hi)
                 assert not msg, (name, (h, w), c, "hi", msg)
                 bad = np.argwhere(lo != want_lo)
