@@ -295,8 +295,9 @@ int rsr_process_fmt(rsr_ctx* ctx, const void* in, int in_fmt, int w, int h, int 
  *            is stored.  "bgr" does not change the alpha.  The colour samples of the call are exactly those of the same call with
  *            "alpha_net" 0.  Nothing outside the destination window is written, as ever.
  *   A constant alpha does not come out constant.  The network is no identity on flat images: f(255) need not be 255, and a fully opaque
- *            image may leave with alpha 254 here and there.  The library does not look for constant tiles (that would change bytes and need
- *            a host round trip on the device paths); a caller who knows an image to be opaque sets the option to 0 for it, as the CLI does.
+ *            image may leave with alpha 254 here and there.  By default the library does not look for constant tiles: that changes bytes
+ *            and needs a host round trip on the device paths, so it is an option of its own, "alpha_adaptive" below.  Without it, a caller
+ *            who knows an image to be opaque sets "alpha_net" to 0 for it, as the CLI does under RSR_ALPHA=net.
  *   Cost.    The tiles of an RGBA batch walk the network TWICE, over the same tables, plan and workspace (no workspace byte is added): expect
  *            about twice the frame time of "alpha_net" 0 (profiles/alpha_net.txt).  The colour pass runs as ever; the alpha pass is one
  *            more preprocessing launch, the network, and one post-processing launch that stores sample 3 alone.
@@ -308,8 +309,35 @@ int rsr_process_fmt(rsr_ctx* ctx, const void* in, int in_fmt, int w, int h, int 
  *            FLOPs of rsr_profile include both passes; its tile count does not.
  *   Stats.   "alpha_net": the value in force.  "alpha_tiles": tiles run through the alpha pass since creation -- a masked call adds its
  *            marked tiles only, a c == 3 call none.
- * Out of scope: a per-tile decision inside the library, luma-weighted or single-channel alpha, premultiplied alpha, alpha for planar or YUV
- * formats, one network pass shared by colour and alpha. */
+ * Out of scope: luma-weighted or single-channel alpha, premultiplied alpha, alpha for planar or YUV formats, one network pass shared by
+ * colour and alpha.
+ *
+ * ---- "alpha_adaptive": skip the alpha pass on tiles of constant alpha ------------------------------------------------------------------
+ * In sprites, atlases, logos and cut-outs the alpha is constant over most of the area and interesting along silhouettes only.  Option
+ * "alpha_adaptive" 1 (0 [default]; anything else RSR_E_ARG, the value in force stays) concerns calls with c == 4 under "alpha_net" 1 and
+ * nothing else: with "alpha_net" 0, and for a c == 3 call, it is ignored -- same launches, same bytes, same stats.
+ *   The rule, exact.  A tile is FLAT when all alpha samples of its source rectangle (rsr_tile_source_rect: the padded tile clipped to the
+ *            image) are equal, compared at the source's depth: 8 bits for U8, 16 for U16 -- two U16 values that share a high byte differ.
+ *            The output rectangle of a flat tile holds, in all four samples, the bytes "alpha_net" 0 writes: its alpha is the bicubic
+ *            value, which for a constant k is k converted to the destination's depth.  Every other tile's rectangle holds the bytes
+ *            "alpha_net" 1 writes.  The colour samples are those of "alpha_net" 0 everywhere, as before.  The decision is a function of the
+ *            source rectangle alone, so masks, diffs and sequences stay valid.
+ *   THE HOST WAITS.  The library scans the alpha on the device in front of the colour pass (one launch per tile batch; under TTA once per
+ *            tile), copies one byte per tile to the host and reads them there while the colour pass runs.  So with the option on, an RGBA
+ *            call under "alpha_net" 1 performs ONE HOST WAIT PER TILE BATCH, also where the call is asynchronous (a stream argument, the
+ *            device entry points): the calling thread blocks until the caller's stream has reached the scan -- everything enqueued on it
+ *            before the call has finished by then -- and the context is held meanwhile.  Such a call must not be made under stream
+ *            capture.  The GPU has the colour pass queued behind the scan, so it does not run dry.  With the option off no call gains a
+ *            wait.
+ *   Cost.    profiles/alpha_adaptive.txt.  No tile varies: no alpha pass, no launch beyond the scan.  All vary: the alpha pass of
+ *            "alpha_net" 1 on the batch's own tables.  Otherwise the varying tiles run as a tile batch of their own, built on the fly, in a
+ *            subset of the batch's slots: no workspace byte is added.
+ *   Where.   Every route "alpha_net" takes.  rsr_process_group: the members must agree on the option (RSR_E_ARG otherwise).  Read when a
+ *            tile batch is enqueued.  The progress callback stays one call per tile.  Under profiling the scan counts in the
+ *            preprocessing class.
+ *   Stats.   "alpha_adaptive": the value in force.  "alpha_tiles_flat": tiles whose alpha pass was skipped since creation.  "alpha_tiles"
+ *            keeps its meaning, tiles run through the alpha pass: now the varying ones only.  "alpha_wait_us": host time spent in the waits.
+ * Out of scope: a device-side decision without a host wait, a tolerance ("nearly flat"), flat-colour tiles, a public scan entry point. */
 
 /* ---- YUV 4:4:4: RSR_FMT_YUV444P / RSR_FMT_YUV444P10 in and out (no reference counterpart) -------------------------------------------------
  * Screen recordings (H.264 Hi444PP, HEVC RExt, AV1 4:4:4, lossless x264 / FFV1: subsampled chroma smears coloured text), ProRes 4444 and
@@ -950,6 +978,11 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *                       pass over the call's tiles at about twice the frame time ("alpha through the network" above has the exact rule);
  *                       c == 3 calls are not concerned.  Takes effect for the next call.  Any other value: RSR_E_ARG, the value in force
  *                       stays (stat "alpha_net"; stat "alpha_tiles": tiles run through the alpha pass since creation)
+ *   "alpha_adaptive"    0 [default]: under "alpha_net" 1 every tile of an RGBA call runs the alpha pass.  1: a tile whose source rectangle
+ *                       holds one alpha value skips it and keeps the bytes of "alpha_net" 0 ("alpha_adaptive" above has the exact rule) --
+ *                       at the price of ONE HOST WAIT PER TILE BATCH, also in asynchronous calls; no such call under stream capture.
+ *                       Ignored with "alpha_net" 0 and for c == 3.  Takes effect for the next call.  Any other value: RSR_E_ARG, the value
+ *                       in force stays (stats "alpha_adaptive", "alpha_tiles_flat", "alpha_wait_us")
  *   "precise_auto"      1: "precise" is set by the model: on a loaded context rsr_selfcheck runs at once on the built-in tile and "precise"
  *                       becomes its recommend_precise; on a context not yet loaded the same happens at the end of the next successful
  *                       rsr_load / rsr_load_packed (which then returns the self-check's error, if it has one; the model stays loaded).

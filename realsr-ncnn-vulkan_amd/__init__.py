@@ -439,6 +439,20 @@ class RealSR:
     def alpha_net(self, v):
         self.set_option("alpha_net", int(v))  # (anything but 0 or 1 raises RealSRError(RSR_E_ARG) and leaves the value alone)
 
+    @property
+    def alpha_adaptive(self):
+        """0 (default): under alpha_net 1 every tile of an RGBA call runs the alpha pass.  1: a tile whose source rectangle holds ONE alpha
+        value skips it and keeps the bytes of alpha_net 0 -- that value, exactly -- while every other tile holds the bytes of alpha_net 1
+        (option "alpha_adaptive", include/realsr_hip.h).  The library scans the alpha on the device and reads the result on the host: one
+        host wait per tile batch, also in an asynchronous call, so no such call under stream capture.  Without alpha_net 1, and for RGB
+        calls, the option does nothing.  Takes effect for the next call.  Stats "alpha_tiles" / "alpha_tiles_flat": tiles that ran /
+        skipped the alpha pass."""
+        return int(self.get_stat("alpha_adaptive"))
+
+    @alpha_adaptive.setter
+    def alpha_adaptive(self, v):
+        self.set_option("alpha_adaptive", int(v))  # (anything but 0 or 1 raises RealSRError(RSR_E_ARG) and leaves the value alone)
+
     def close(self):
         if getattr(self, "_h", None):
             for v in list(getattr(self, "_videos", ())):  # open video sessions go first: they hold device memory of this context

@@ -729,6 +729,9 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "yuv_siting") *value = double(e.yuv_siting);
     else if (k == "alpha_net") *value = e.alpha_net ? 1.0 : 0.0;
     else if (k == "alpha_tiles") *value = double(e.alpha_tiles);
+    else if (k == "alpha_adaptive") *value = e.alpha_adaptive ? 1.0 : 0.0;
+    else if (k == "alpha_tiles_flat") *value = double(e.alpha_tiles_flat);
+    else if (k == "alpha_wait_us") *value = e.alpha_wait_us;
     else if (k == "selfcheck_runs") *value = double(e.selfcheck_runs);
     else if (k == "selfcheck_headroom") *value = e.sc_have ? double(e.sc_last.headroom) : -1.0;
     else if (k == "selfcheck_peak_abs") *value = e.sc_have ? double(e.sc_last.peak_abs) : -1.0;
@@ -796,6 +799,11 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     { // the alpha of an RGBA call through the network instead of the bicubic (include/realsr_hip.h "alpha_net"); read when the next batch is enqueued
         if (value != 0 && value != 1) return ctx->e.fail(RSR_E_ARG, "alpha_net must be 0 (bicubic) or 1 (through the network)");
         ctx->e.alpha_net = value != 0;
+    }
+    else if (k == "alpha_adaptive")
+    { // under alpha_net 1, skip the alpha pass on tiles whose alpha is constant (include/realsr_hip.h "alpha_adaptive"); read when the next batch is enqueued
+        if (value != 0 && value != 1) return ctx->e.fail(RSR_E_ARG, "alpha_adaptive must be 0 (every tile runs the alpha pass) or 1 (tiles of constant alpha skip it)");
+        ctx->e.alpha_adaptive = value != 0;
     }
     else if (k == "precise_auto")
     { // the model decides: now when one is loaded, else at the end of the next load (rsr_load / rsr_load_packed)

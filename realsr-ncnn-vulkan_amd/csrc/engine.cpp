@@ -101,6 +101,8 @@ Engine::~Engine()
     if (merge_done) (void)hipEventDestroy(merge_done);
     mix_ring.free();
     mask_ring.free();
+    flat_ring.free();
+    alpha_ring.free();
     if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -1134,13 +1136,16 @@ int Engine::launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntile
     if (const int bits = pix_fmt(io.in_fmt).bits; bits && !yuv_coef(yuv_matrix, yuv_range, bits, &pa.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     if (const int bits = pix_fmt(io.out_fmt).bits; bits && !yuv_coef(yuv_matrix, yuv_range, bits, &po.yuv)) return fail(RSR_E_STATE, "no such YUV matrix / range");
     pa.siting = po.siting = yuv_siting;
-    launch_preproc_tiles(pa, max_tw, max_th, st);
-    mark(0, 0, b.px[0] / per * BatchIO::image_px_bytes(io.in_fmt, c) + b.px[0] * 64, st);
     // Option "alpha_net" (include/realsr_hip.h): an RGBA batch walks the network twice over the same tables and workspace -- the colour pass
     // as ever, its post launch writing the bicubic alpha too, then the alpha pass below, whose post launch overwrites sample 3 alone.  The
     // throttle event of a merged batch belongs to the pass that runs last.
-    const bool two_pass = alpha_net && c == 4;
+    // Option "alpha_adaptive" on top: the scan goes in front of the colour pass, its bytes are read behind it (the GPU has a whole colour
+    // pass queued while the host waits), and the alpha pass runs on the tiles whose alpha varies.
+    const bool two_pass = alpha_net && c == 4, adaptive = two_pass && alpha_adaptive;
     int rc;
+    if (adaptive && (rc = enqueue_flat_scan(b, max_th, ntiles, st, io)) != RSR_OK) return rc;
+    launch_preproc_tiles(pa, max_tw, max_th, st);
+    mark(0, 0, b.px[0] / per * BatchIO::image_px_bytes(io.in_fmt, c) + b.px[0] * 64, st);
     if (two_pass)
     {
         BatchIO cio = io;
@@ -1174,17 +1179,80 @@ int Engine::launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntile
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
     mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) * io.os.nx * io.os.ny / (16.0 * io.os.dx * io.os.dy)), st);
     if (!two_pass) return RSR_OK;
+    // The tiles of the alpha pass: all of the batch on its own tables, or with "alpha_adaptive" those the scan marked.
+    const Plan::Batch* ab = &b;
+    Plan::Batch sub;
+    if (adaptive)
+    {
+        const auto t_wait = std::chrono::steady_clock::now();
+        if (flat_ring.ev[flat_ring.k]) HIP_TRY(hipEventSynchronize(flat_ring.ev[flat_ring.k])); // (no event: release waited for the stream)
+        alpha_wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_wait).count();
+        const char* const varies = flat_ring.host();
+        std::vector<int> run;
+        for (int i = 0; i < ntiles; i++)
+            if (varies[i]) run.push_back(i);
+        alpha_tiles_flat += ntiles - int(run.size());
+        if (run.empty())
+        { // no alpha pass: the colour pass ran last
+            if (io.ev_mid && hipEventRecord(io.ev_mid, st) != hipSuccess) return fail(RSR_E_DEVICE, "hipEventRecord failed");
+            return RSR_OK;
+        }
+        if (int(run.size()) < ntiles)
+        { // The varying tiles as a batch of their own: each keeps its out_x / out_y / img and gets a compact slot0, so the pass uses a subset
+          // of the batch's slots in the same workspace.  The tables travel like a masked call's: pinned image, one copy on the call's stream.
+            const size_t table_bytes = fill_batch(sub, b.tile0, int(run.size()), [&](int i) { return b.tiles[size_t(run[size_t(i)])]; }, tta != 0,
+                                                  prepadding * scale, trim_tail, fold_cols, io.out_row0);
+            if ((rc = alpha_ring.acquire(table_bytes, true)) != RSR_OK) return rc;
+            char *d = alpha_ring.dev(), *hs = alpha_ring.host();
+            (void)upload_batch(sub, d, xcd_order, &hs);
+            HIP_TRY(hipMemcpyAsync(alpha_ring.dev(), alpha_ring.host(), table_bytes, hipMemcpyHostToDevice, st));
+            ab = &sub;
+        }
+    }
+    const int an = ab == &b ? ntiles : ab->ntiles;
     // The alpha pass: the alpha sample of every source pixel into the three input planes (the gray image G of the header), the network,
     // and the mean of the three results into sample 3.  IN and OUT3 are free again: the stream has the colour pass's launches in front.
     pa.alpha_src = 1;
+    pa.tiles = po.tiles = ab->d_tiles;
+    pa.ntiles = po.ntiles = an;
     launch_preproc_tiles(pa, max_tw, max_th, st);
-    mark(0, 0, b.px[0] / per * (BatchIO::image_px_bytes(io.in_fmt, c) / c) + b.px[0] * 64, st);
-    rc = run_network(b, st, ntiles * per, &io, nullptr);
-    if (rc != RSR_OK) return rc;
-    po.alpha_dst = 1;
-    launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
-    mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) / c * io.os.nx * io.os.ny / (16.0 * io.os.dx * io.os.dy)), st);
-    alpha_tiles += ntiles;
+    mark(0, 0, ab->px[0] / per * (BatchIO::image_px_bytes(io.in_fmt, c) / c) + ab->px[0] * 64, st);
+    rc = run_network(*ab, st, an * per, &io, nullptr);
+    if (rc == RSR_OK)
+    {
+        po.alpha_dst = 1;
+        launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
+        mark(2, 0, ab->px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) / c * io.os.nx * io.os.ny / (16.0 * io.os.dx * io.os.dy)), st);
+        alpha_tiles += an;
+    }
+    if (ab == &sub) alpha_ring.release(st); // (also behind a pass that failed to launch: what it did enqueue reads the tables)
+    return rc;
+}
+
+// The scan of option "alpha_adaptive" (kernels.h FlatArgs) for the first ntiles tiles of b, in front of whatever the caller enqueues next:
+// memset, kernel, and the copy of the ntiles bytes into the pinned image of flat_ring's next slot, whose event is recorded behind the
+// copy.  Under profiling the three count as one segment of the preprocessing class.
+int Engine::enqueue_flat_scan(const Plan::Batch& b, int max_th, int ntiles, hipStream_t st, const BatchIO& io)
+{
+    if (const int rc = flat_ring.acquire(al256(size_t(ntiles)), true)) return rc;
+    FlatArgs fa;
+    std::memset(&fa, 0, sizeof fa);
+    for (int i = 0; i < io.nimg; i++)
+    {
+        fa.imgs[i] = static_cast<const uint8_t*>(io.in[i]);
+        fa.ws[i] = io.w[i];
+        fa.hs[i] = io.h[i];
+        fa.pitch[i] = io.in_pitch[i];
+    }
+    fa.tiles = b.d_tiles;
+    fa.ntiles = ntiles;
+    fa.u16 = io.in_fmt == kFmtU16 ? 1 : 0;
+    fa.flags = reinterpret_cast<uint8_t*>(flat_ring.dev());
+    const hipError_t e = launch_alpha_flat_tiles(fa, max_th, st);
+    if (e != hipSuccess) return fail(RSR_E_DEVICE, std::string("alpha_flat_tiles: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(flat_ring.host(), flat_ring.dev(), size_t(ntiles), hipMemcpyDeviceToHost, st));
+    flat_ring.release(st);
+    mark(0, 0, b.px[0] / (tta ? 8 : 1) * BatchIO::image_px_bytes(io.in_fmt, io.c), st);
     return RSR_OK;
 }
 

@@ -3,7 +3,8 @@
 // Replaces RealSR::process (/root/reference/src/realsr.cpp:145-523): instead of a row-band loop with
 // one Vulkan submit_and_wait per tile and >= 722 dispatches per tile, ALL tiles of an image (x8 under
 // TTA) are laid out as "slots" of one batch and walk the model's convolutions (351 at 23 RRDB blocks) together: one kernel launch
-// per network layer per batch, no host synchronisation inside a call.
+// per network layer per batch, no host synchronisation inside a call (the one exception is opt-in: option "alpha_adaptive" waits once
+// per tile batch for the bytes of its scan).
 //
 // Concurrency (the reference calls RealSR::process from several proc threads on one object, main.cpp:811-828,
 // with per-call allocators, realsr.cpp:161-167):
@@ -307,6 +308,17 @@ struct Engine
     // when a batch is enqueued, like bgr.  Both passes share the tables, the plan and the workspace: the stream orders them.
     bool alpha_net = false;
     long long alpha_tiles = 0; // stat: tiles that ran the alpha pass since creation, under mu
+    // Option "alpha_adaptive" (include/realsr_hip.h "alpha_adaptive"): under alpha_net, the alpha pass runs only on the tiles whose source
+    // rectangle holds more than one alpha value.  A scan in front of the colour pass (kernels.h FlatArgs) leaves one byte per tile, the host
+    // reads them while the colour pass runs -- ONE host wait per tile batch -- and launch_batch picks the alpha pass: none, the batch's own
+    // tables, or a sub-batch of the varying tiles built on the fly.  Read when a batch is enqueued, like alpha_net.
+    bool alpha_adaptive = false;
+    long long alpha_tiles_flat = 0; // stat: tiles whose alpha pass was skipped since creation, under mu
+    double alpha_wait_us = 0;       // stat: host time spent waiting for the scans' bytes
+    TableRing flat_ring;            // the scan's bytes: device and pinned, rotating like the tables
+    TableRing alpha_ring;           // the tables of the sub-batches (pinned image, one asynchronous copy on the call's stream)
+    // The scan of the first ntiles tiles of b on st, its bytes on their way to flat_ring.host(), the ring's event recorded behind them
+    int enqueue_flat_scan(const Plan::Batch& b, int max_th, int ntiles, hipStream_t st, const BatchIO& io);
     // Model self-check (include/realsr_hip.h rsr_selfcheck): one tile through the network in both storages, compared on the device.
     bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
     long long selfcheck_runs = 0;

@@ -423,6 +423,25 @@ template <int N> struct DiffArgs // N: 1 or kMaxMerge
 };
 template <int N> hipError_t launch_diff_tiles(const DiffArgs<N>& a, hipStream_t st); // the error of the memset or of the launch
 
+// ---- flat-alpha scan (engine option "alpha_adaptive") ------------------------------------------------------------------------------
+// flags[t] = 1 when the alpha samples of tile t's source rectangle are not all equal, else 0: tile t of a batch's DEVICE tile table, whose
+// rectangle is [max(x_org, 0), min(x_org + tw, w)) x [max(y_org, 0), min(y_org + th, h)) of image BaseTile::img -- what tile_source_rect
+// returns for the tile.  The images are RGBA, uint8 or uint16 HWC (u16), and travel by value as PreArgs carries them; samples are compared
+// at their own depth.  No byte outside the rectangle's rows and pixels is read.  Under TTA a tile is scanned once: the grid runs over
+// tiles, not slots.
+struct FlatArgs
+{
+    const uint8_t* imgs[kMaxMerge];
+    int ws[kMaxMerge], hs[kMaxMerge];
+    long long pitch[kMaxMerge]; // bytes from one row of image i to the next
+    const BaseTile* tiles;
+    int ntiles;
+    int u16;        // 1: uint16 samples (kFmtU16), 0: uint8
+    uint8_t* flags; // device, [ntiles]
+};
+// max_th: the tallest padded tile of the table (sizes the grid).  The error of the memset or of the launch.
+hipError_t launch_alpha_flat_tiles(const FlatArgs& a, int max_th, hipStream_t st);
+
 // One rectangle of bytes to move: `rows` rows of `width` bytes, from src to dst, each with its own pitch, at any alignment.  The rectangles
 // of one launch never overlap one another's destinations, and no source is another rectangle's destination.
 struct PropRect

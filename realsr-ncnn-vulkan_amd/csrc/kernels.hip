@@ -1924,6 +1924,78 @@ template hipError_t launch_diff_tiles<1>(const DiffArgs<1>&, hipStream_t);
 template hipError_t launch_diff_tiles<kMaxMerge>(const DiffArgs<kMaxMerge>&, hipStream_t);
 
 // =============================================================================================
+// flat-alpha scan (engine option "alpha_adaptive"): which tiles' source rectangles hold more than one alpha value
+// =============================================================================================
+// Do the alpha samples of the n RGBA pixels behind p differ from ref?  One wave, lanes along the row.  T is the sample type; a pixel is PB =
+// 4 * sizeof(T) bytes and its alpha sits in the high bits of the pixel's last dword (mask M: the top byte of a uint8 pixel's one dword, the
+// top half of a uint16 pixel's second), so ref is the alpha shifted up there and low bits zero.  A row that starts on a pixel boundary is read in
+// 16-byte pieces (4 / 2 pixels), 64 per step, behind a head of up to 3 / 1 pixels that brings it to that boundary and in front of a tail;
+// head and tail are read one pixel's alpha dword per lane (lanes 0 .. 15 and 16 .. 31).  Any other row (a uint8 pitch or base that is no
+// multiple of 4) is read one alpha sample per lane.  No byte outside [p, p + n * PB) is read.
+template <typename T>
+__device__ __forceinline__ bool row_alpha_varies(const uint8_t* p, int n, uint32_t ref, int lane)
+{
+    constexpr int PB = 4 * int(sizeof(T)), PPV = 16 / PB, SH = 32 - 8 * int(sizeof(T));
+    constexpr uint32_t M = ~uint32_t(0) << SH;
+    bool d = false;
+    if (reinterpret_cast<uintptr_t>(p) & uintptr_t(PB - 1))
+    {
+        const T* const s = reinterpret_cast<const T*>(p) + 3;
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int i = lane; i < n; i += 64) d |= (uint32_t(s[4 * i]) << SH) != ref;
+        return d;
+    }
+    const int head = min(n, int(((0 - reinterpret_cast<uintptr_t>(p)) & uintptr_t(15)) / PB));
+    const int nvec = (n - head) / PPV, tail = n - head - nvec * PPV;
+    int e = -1;
+    if (lane < 16) e = lane < head ? lane : -1;
+    else if (lane < 32) e = lane - 16 < tail ? n - tail + lane - 16 : -1;
+    if (e >= 0) d = ((reinterpret_cast<const uint32_t*>(p + (long long)e * PB)[PB / 4 - 1] ^ ref) & M) != 0;
+    const uint4* const v = reinterpret_cast<const uint4*>(p + head * PB);
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (int i = lane; i < nvec; i += 64)
+    {
+        const uint4 x = v[i];
+        const uint32_t m = sizeof(T) == 1 ? (x.x ^ ref) | (x.y ^ ref) | (x.z ^ ref) | (x.w ^ ref) : (x.y ^ ref) | (x.w ^ ref);
+        d |= (m & M) != 0;
+    }
+    return d;
+}
+
+// Grid (tile, row chunk), the rows spread as diff_tiles spreads them: kDiffRows per workgroup and step, 4 per wave.  Every sample is compared
+// with the alpha of the rectangle's first pixel; a wave that finds another value stores the 1, behind the launch function's memset.
+template <typename T> __global__ __launch_bounds__(256) void alpha_flat_tiles(const FlatArgs a)
+{
+    constexpr int PB = 4 * int(sizeof(T)), SH = 32 - 8 * int(sizeof(T));
+    const BaseTile t = a.tiles[blockIdx.x];
+    const int w = a.ws[t.img], h = a.hs[t.img];
+    const long long pitch = a.pitch[t.img];
+    const int x0 = max(t.x_org, 0), x1 = min(t.x_org + t.tw, w), y0 = max(t.y_org, 0), y1 = min(t.y_org + t.th, h);
+    const uint8_t* const base = a.imgs[t.img] + (long long)x0 * PB; // every offset from the image's base in 64 bits
+    const uint32_t ref = uint32_t(reinterpret_cast<const T*>(base + (long long)y0 * pitch)[3]) << SH;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int step = gridDim.y * kDiffRows;
+    bool d = false;
+#pragma unroll 1
+    for (int ys = y0 + blockIdx.y * kDiffRows + wave; ys < y1; ys += step)
+#pragma unroll 1
+        for (int y = ys; y < min(ys + kDiffRows, y1); y += 4) d |= row_alpha_varies<T>(base + (long long)y * pitch, x1 - x0, ref, lane);
+    if (__any(d) && lane == 0) a.flags[blockIdx.x] = 1;
+}
+
+hipError_t launch_alpha_flat_tiles(const FlatArgs& a, int max_th, hipStream_t st)
+{
+    if (a.ntiles <= 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(a.flags, 0, size_t(a.ntiles), st); // every byte is written: the kernel only ever stores ones
+    if (e != hipSuccess) return e;
+    const int chunks = (max_th + kDiffRows - 1) / kDiffRows;
+    const dim3 grid(a.ntiles, chunks < 1 ? 1 : (chunks < 1024 ? chunks : 1024)), block(256); // (taller rectangles: the kernel strides over the chunks)
+    if (a.u16) hipLaunchKernelGGL(alpha_flat_tiles<uint16_t>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(alpha_flat_tiles<uint8_t>, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+// =============================================================================================
 // frame sequences: the copy of the rectangles nobody computed
 // =============================================================================================
 // Rows of a rectangle per workgroup and step: 4 per wave.  An 800-row rectangle spreads over 50 workgroups, the 60 of a 1080p frame at x4

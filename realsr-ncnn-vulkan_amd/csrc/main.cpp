@@ -13,7 +13,8 @@
 //   * RSR_DEPTH=16|auto (no counterpart: the reference is 8-bit throughout): 16-bit PNG / PNM in, 16-bit PNG out through
 //     rsr_process_fmt (RSR_FMT_U16_HWC); unset or 8, every byte of the 8-bit route is what it was;
 //   * RSR_ALPHA=net (no counterpart): the alpha of an RGBA image walks the network as a gray image (rsr_set_option "alpha_net") instead
-//     of taking the bicubic; an image whose alpha is fully opaque keeps the bicubic and its one pass;
+//     of taking the bicubic; an image whose alpha is fully opaque keeps the bicubic and its one pass; RSR_ALPHA=adaptive: the library
+//     decides per tile (rsr_set_option "alpha_adaptive"): tiles of constant alpha keep the bicubic, the others go through the network;
 //   * video mode (no counterpart): an input that ends in .y4m, or is "-" (stdin), is a YUV4MPEG2 stream and runs through one rsr_video
 //     session to a .y4m output or "-" (stdout) -- run_video below, y4m_io.h.
 #include <dirent.h>
@@ -424,14 +425,17 @@ int main(int argc, char** argv)
     // ncnn's bicubic x4, as ever.  net: the alpha walks the network as a gray image (rsr_set_option "alpha_net": a second pass over the
     // image's tiles, about twice the time) -- except for an image whose alpha is fully opaque, the usual opaque PNG saved as RGBA, which
     // keeps its opaque alpha and its one pass.  On the 8-bit and the RSR_DEPTH 16-bit route alike.
-    bool alpha_net = false;
+    // adaptive: "alpha_net" 1 and "alpha_adaptive" 1, set ONCE per context: the library skips the alpha pass tile by tile wherever a tile's
+    // source rectangle holds one alpha value (an opaque image: everywhere), so no image needs an option of its own.
+    bool alpha_net = false, alpha_adaptive = false;
     if (const char* ae = getenv("RSR_ALPHA"))
     {
         const std::string v(ae);
         if (v == "net") alpha_net = true;
+        else if (v == "adaptive") alpha_adaptive = true;
         else if (!v.empty() && v != "bicubic")
         {
-            fprintf(stderr, "invalid RSR_ALPHA '%s' (net or bicubic)\n", ae);
+            fprintf(stderr, "invalid RSR_ALPHA '%s' (net, adaptive or bicubic)\n", ae);
             return -1;
         }
     }
@@ -604,6 +608,11 @@ int main(int argc, char** argv)
         // every proc thread of this GPU may have a call in flight (small images of concurrent calls are merged into one tile batch: the
         // reference's "-j 4:4:4 for many small images", README.md:61 -- here the more proc threads, the fuller the launches)
         rsr_set_option(ctxs[size_t(i)], "max_lanes", std::max(16, std::min(64, jobs_proc[size_t(i)])));
+        if (alpha_adaptive)
+        { // RSR_ALPHA=adaptive: the same for every image of this context
+            rsr_set_option(ctxs[size_t(i)], "alpha_net", 1);
+            rsr_set_option(ctxs[size_t(i)], "alpha_adaptive", 1);
+        }
         // no flag of the reference's surface is taken for it: RSR_PRECISE=1 keeps a byte of rounding residue per element of the residual
         // trunk (rsr_set_option "precise"; what tools/check_real_model.py recommends for weights with a wide output swing)
         // RSR_PRECISE_AUTO=1: the loaded model decides (rsr_set_option "precise_auto": one built-in tile through both storages on the
@@ -758,6 +767,22 @@ int main(int argc, char** argv)
                         for (int k = 0; k < ngpu; k++)
                             if (split_one_image || k == g) rsr_set_option(ctxs[size_t(k)], "alpha_net", v->opaque ? 0 : 1);
                     }
+                    // RSR_ALPHA=adaptive: the option is the context's, RGBA images need not keep each other out -- except under -v, where
+                    // the tiles an image sent through the alpha pass are read off the context's counters around its call
+                    const bool count_alpha = alpha_adaptive && verbose && v->inimage.elempack == 4;
+                    double ran0 = 0, flat0 = 0;
+                    if (count_alpha)
+                    {
+                        alpha_lk = std::unique_lock<std::mutex>(alpha_mu[split_one_image ? 0 : size_t(g)]);
+                        for (int k = 0; k < ngpu; k++)
+                            if (split_one_image || k == g)
+                            {
+                                double a = 0, b = 0;
+                                rsr_get_stat(ctxs[size_t(k)], "alpha_tiles", &a);
+                                rsr_get_stat(ctxs[size_t(k)], "alpha_tiles_flat", &b);
+                                ran0 += a, flat0 += b;
+                            }
+                    }
                     if (split_one_image && v->inimage.depth == 16)
                     { // rsr_process_fmt has no tile ranges: a single 16-bit image runs on the first gpu
                         if (verbose) fprintf(stderr, "%s: a 16-bit image is not split over gpus: it runs on gpu %d\n", v->inpath.c_str(), gpuid[0]);
@@ -771,6 +796,19 @@ int main(int argc, char** argv)
                     }
                     else
                         prc = realsr[size_t(g)]->process(v->inimage, v->outimage);
+                    if (count_alpha && prc == RSR_OK)
+                    {
+                        double ran = 0, flat = 0;
+                        for (int k = 0; k < ngpu; k++)
+                            if (split_one_image || k == g)
+                            {
+                                double a = 0, b = 0;
+                                rsr_get_stat(ctxs[size_t(k)], "alpha_tiles", &a);
+                                rsr_get_stat(ctxs[size_t(k)], "alpha_tiles_flat", &b);
+                                ran += a, flat += b;
+                            }
+                        fprintf(stderr, "%s: %d of %d tiles ran the alpha pass (RSR_ALPHA=adaptive)\n", v->inpath.c_str(), int(ran - ran0), int(ran - ran0 + flat - flat0));
+                    }
                     if (prc != RSR_OK)
                     {
                         std::lock_guard<std::mutex> lk(fail_mu);

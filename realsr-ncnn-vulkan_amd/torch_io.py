@@ -130,7 +130,9 @@ def upscale(sr, x, out=None, out_dtype=None):
     the result has the same dtype.  out_dtype (integer HWC inputs only): torch.uint8, torch.uint16 or torch.int16 -- the depth of the
     result, so that 8 -> 16 and 16 -> 8 bits are one call; with out= given, out.dtype must equal it.
     RGBA: the alpha of an (H, W, 4) input is the bicubic x4, or with sr.alpha_net = 1 the network's result for the gray image of the alpha
-    (option "alpha_net": a second pass over the tiles, about twice the frame time); nothing here knows the option, the engine does."""
+    (option "alpha_net": a second pass over the tiles, about twice the frame time); nothing here knows the option, the engine does.
+    With sr.alpha_adaptive = 1 on top, tiles of constant alpha skip that pass; the engine then WAITS on the host once per tile batch, until
+    the current stream has reached its scan of the alpha: the call is no longer purely asynchronous and must not run under stream capture."""
     fmt, batched = _check(sr, x)
     ydtype = x.dtype
     if out_dtype is not None:
@@ -567,7 +569,8 @@ def upscale_delta(sr, x, prev_x, prev_y, out=None, chroma=420):
     with --; the masked call.
     chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them.  chroma=444: x, prev_x, prev_y and out are
     planar 4:4:4 images as upscale_yuv(..., chroma=444) takes them.
-    sr.alpha_net = 1 holds here as in upscale: the marked tiles of an RGBA frame run both passes, and the diff compares the alpha bytes too."""
+    sr.alpha_net = 1 holds here as in upscale: the marked tiles of an RGBA frame run both passes, and the diff compares the alpha bytes too.
+    sr.alpha_adaptive = 1 likewise, with its host wait per tile batch (upscale)."""
     _check_chroma(chroma, "upscale_delta")
     fmt, w, h, c, _ = _image_desc(sr, x, "x", chroma)
     if prev_x is not None and not _same_layout(x, prev_x):
@@ -640,7 +643,8 @@ def upscale_sequence(sr, frames, prev_x=None, prev_y=None, out=None, chroma=420)
     of the masks into pinned memory, ONE stream synchronisation, the sequence call.
     chroma=422: surfaces and pairs are YUV 4:2:2 as upscale_yuv(..., chroma=422) takes them.  chroma=444: every frame is a planar 4:4:4
     image as upscale_yuv(..., chroma=444) takes it -- a list of them, or a stacked (N, 3, H, W) uint8 / int16 tensor.
-    sr.alpha_net = 1 holds here as in upscale, for the tiles of RGBA frames that run."""
+    sr.alpha_net = 1 holds here as in upscale, for the tiles of RGBA frames that run; sr.alpha_adaptive = 1 likewise, with its host wait per
+    tile batch."""
     _check_chroma(chroma, "upscale_sequence")
     stacked = isinstance(frames, torch.Tensor)
     if stacked:
