@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 
 namespace rsr {
 
@@ -86,8 +87,8 @@ Engine::~Engine()
         if (l->d_out.p) (void)hipFree(l->d_out.p);
         if (l->h_in) (void)hipHostFree(l->h_in);
         if (l->h_out) (void)hipHostFree(l->h_out);
-        for (hipEvent_t e : {l->ev_in, l->ev_done, l->ev_half, l->ev_chunk[0], l->ev_chunk[1]})
-            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t* e : l->events())
+            if (*e) (void)hipEventDestroy(*e);
         if (l->copy) (void)hipStreamDestroy(l->copy);
     }
     free_plans();
@@ -2150,13 +2151,198 @@ static int ensure_pinned(void*& p, size_t& have, size_t need)
     return RSR_OK;
 }
 
+int Lane::open()
+{
+    if (copy) return RSR_OK;
+    HIP_TRY(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+    for (hipEvent_t* e : events()) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return RSR_OK;
+}
+
+// A lane for the duration of one host call; `rc` says whether it is ready for use.
+// Whatever way the call ends, nothing of it may still be in flight when the lane -- and with it the caller's `in` / `out`
+// -- is handed back: a HIP failure half way must not turn into a use-after-free of the lane buffers by the next caller.
+struct LaneHold
+{
+    Engine* const e;
+    Lane* const l;
+    bool done_recorded = false; // ev_done was recorded on behalf of this call (lane_run, or the leader of its merged batch)
+    int rc;
+    explicit LaneHold(Engine* e_) : e(e_), l(e_->acquire_lane()) { rc = open(); }
+    LaneHold(const LaneHold&) = delete;
+    ~LaneHold()
+    {
+        if (l->copy) (void)hipStreamSynchronize(l->copy);
+        if (done_recorded) (void)hipEventSynchronize(l->ev_done);
+        e->release_lane(l);
+    }
+
+private:
+    int open()
+    {
+        HIP_TRY(hipSetDevice(e->device));
+        return l->open();
+    }
+};
+
+static int lane_reserve(DevBuf& b, std::atomic<size_t>& published, size_t bytes) // lane-private: nothing else can be using the old allocation
+{
+    const int rc = Engine::ensure(b, bytes);
+    published.store(b.bytes, std::memory_order_relaxed); // what device_avail() / rsr_get_stat read (they do not hold this lane)
+    return rc;
+}
+
+int Engine::lane_reserve_out(Lane& L, const void* out, size_t dev_bytes, size_t fetch_bytes, bool& out_pinned)
+{
+    if (const int rc = lane_reserve(L.d_out, L.out_bytes, dev_bytes)) return rc;
+    out_pinned = is_pinned_host(out);
+    return out_pinned ? RSR_OK : ensure_pinned(L.h_out, L.h_out_bytes, 2 * std::min(std::max<size_t>(chunk_bytes, 1 << 20), fetch_bytes));
+}
+
+int Engine::lane_upload(Lane& L, const void* in, size_t nin)
+{
+    if (const int rc = lane_reserve(L.d_in, L.in_bytes, nin)) return rc;
+    const void* src = in;
+    if (!is_pinned_host(in))
+    {
+        if (const int rc = ensure_pinned(L.h_in, L.h_in_bytes, nin)) return rc;
+        pool.copy(L.h_in, in, nin, copy_threads);
+        src = L.h_in;
+    }
+    HIP_TRY(hipMemcpyAsync(L.d_in.p, src, nin, hipMemcpyHostToDevice, L.copy));
+    HIP_TRY(hipEventRecord(L.ev_in, L.copy));
+    return RSR_OK;
+}
+
+int Engine::lane_run(LaneHold& hold, const BatchIO& io, int tile0, int tile1, int T, size_t* half_rows)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    if (!loaded || scale != 4 || tilesize != T || out_ratio != io.os)
+        return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the hold drains the upload)
+    HIP_TRY(hipStreamWaitEvent(stream, hold.l->ev_in, 0));
+    const int rc = enqueue_images(io, tile0, tile1, 0, half_rows, stream);
+    if (rc != RSR_OK)
+    {
+        (void)hipStreamSynchronize(stream); // kernels of this call that did get enqueued use the lane buffers
+        return rc;
+    }
+    HIP_TRY(hipEventRecord(hold.l->ev_done, stream));
+    hold.done_recorded = true;
+    return RSR_OK;
+}
+
+// What the call for tiles [tile0, tile1) of a w x h x c uint8 image downloads (tiles are independent: realsr.cpp:377-380,458-459,490).
+// A range of whole tile rows is a contiguous byte range of the output: when the engine split the 4x tail, its first `half_rows` output
+// rows are complete at ev_half and travel while the second part is still being computed.  A general range is up to three rectangles --
+// the tail of its first tile row, the head of its last row, the whole rows between.  No HIP call: tools/host_check checks it byte by byte.
+static FetchPlan fetch_plan(int w, int h, int c, int T, const OutRatio& os, int tile0, int tile1, size_t half_rows)
+{
+    const int xtiles = (w + T - 1) / T;
+    const size_t rowbytes = size_t(os.of_x(w)) * c; // one output row
+    auto yof = [&](int tr) { return size_t(os.of_y(std::min(tr * T, h))); };  // first output row of tile row tr (whole: out_admit)
+    auto xof = [&](int tc) { return size_t(os.of_x(std::min(tc * T, w))) * c; }; // byte column of tile column tc
+    const int r0 = tile0 / xtiles, c0 = tile0 % xtiles, r1 = (tile1 - 1) / xtiles, c1 = (tile1 - 1) % xtiles + 1; // last tile = (r1, c1 - 1)
+    FetchPlan p{yof(r0), yof(r1 + 1) - yof(r0), 0, {}};
+    auto add = [&](size_t y_a, size_t y_b, size_t x_a, size_t x_b, bool early) {
+        if (y_b > y_a && x_b > x_a) p.span[p.n++] = FetchSpan{y_a * rowbytes + x_a, x_b - x_a, y_b - y_a, early};
+    };
+    if (c0 == 0 && c1 == xtiles)
+    {
+        const size_t first = std::min(p.rows, half_rows);
+        add(p.row0, p.row0 + first, 0, rowbytes, true);
+        add(p.row0 + first, p.row0 + p.rows, 0, rowbytes, false);
+    }
+    else if (r0 == r1) add(yof(r0), yof(r0 + 1), xof(c0), xof(c1), false);
+    else
+    {
+        const int full0 = c0 ? r0 + 1 : r0, full1 = c1 != xtiles ? r1 : r1 + 1; // whole tile rows [full0, full1)
+        if (full0 != r0) add(yof(r0), yof(r0 + 1), xof(c0), rowbytes, false);
+        if (full1 != r1 + 1) add(yof(r1), yof(r1 + 1), 0, xof(c1), false);
+        add(yof(full0), yof(full1), 0, rowbytes, false);
+    }
+    return p;
+}
+
+// The staging chunks of a span, given the bytes of one staging slot: a contiguous span is cut by bytes (chunks of one "row" of up to
+// `slot` bytes), a rectangle by whole rows.  fetch_chunks: how many there are; fetch_chunk: chunk i.
+static int fetch_chunks(const FetchSpan& s, size_t rowbytes, size_t slot, size_t& n)
+{
+    if (s.width == rowbytes) n = (s.width * s.rows + slot - 1) / slot;
+    else if (s.width > slot) return Engine::fail(RSR_E_ARG, "chunk_mb smaller than one output row");
+    else n = (s.rows + slot / s.width - 1) / (slot / s.width);
+    return RSR_OK;
+}
+
+static FetchSpan fetch_chunk(const FetchSpan& s, size_t rowbytes, size_t slot, size_t i)
+{
+    if (s.width == rowbytes) return FetchSpan{s.off + i * slot, std::min(slot, s.width * s.rows - i * slot), 1, s.early};
+    const size_t rows_per = slot / s.width;
+    return FetchSpan{s.off + i * rows_per * rowbytes, s.width, std::min(rows_per, s.rows - i * rows_per), s.early};
+}
+
+// The download of a host call: the spans of fp from the lane's d_out -- which holds the output rows fp.row0 .. fp.row0 + fp.rows -- to
+// `out`, the full-size image, each span behind the event that completes it.  Pinned memory receives the spans directly; pageable memory
+// through the two staging slots lane_reserve_out made, so that the CPU copy of a chunk runs under the PCIe transfer of the next one.
+int Engine::lane_fetch(Lane& L, char* out, bool out_pinned, size_t rowbytes, const FetchPlan& fp)
+{
+    auto dev = [&](size_t off) { return static_cast<const char*>(L.d_out.p) + (off - fp.row0 * rowbytes); }; // device address of byte `off` of the full-size image
+    hipEvent_t waited = nullptr;
+    auto ready = [&](const FetchSpan& s) {
+        hipEvent_t ev = s.early ? L.ev_half : L.ev_done;
+        return ev == std::exchange(waited, ev) ? hipSuccess : hipStreamWaitEvent(L.copy, ev, 0);
+    };
+    if (out_pinned)
+    {
+        for (int k = 0; k < fp.n; k++)
+        {
+            const FetchSpan& s = fp.span[k];
+            HIP_TRY(ready(s));
+            if (s.width == rowbytes) HIP_TRY(hipMemcpyAsync(out + s.off, dev(s.off), s.width * s.rows, hipMemcpyDeviceToHost, L.copy));
+            else HIP_TRY(hipMemcpy2DAsync(out + s.off, rowbytes, dev(s.off), rowbytes, s.width, s.rows, hipMemcpyDeviceToHost, L.copy));
+        }
+        HIP_TRY(hipStreamSynchronize(L.copy));
+        return RSR_OK;
+    }
+    // ensure_pinned only grows h_out: a slot is half of it, but never more than chunk_mb says now, whatever an earlier call left on the lane
+    const size_t slot = std::min(L.h_out_bytes / 2, std::max<size_t>(chunk_bytes, 1 << 20));
+    size_t nch[3];
+    for (int k = 0; k < fp.n; k++) // (a refusal comes before the first copy)
+        if (const int rc = fetch_chunks(fp.span[k], rowbytes, slot, nch[k])) return rc;
+    // chunk i travels into slot i & 1 while the CPU drains chunk i - 1 from the other one
+    auto slot_of = [&](size_t i) { return static_cast<char*>(L.h_out) + (i & 1) * slot; };
+    auto drain = [&](size_t i, const FetchSpan& ch) -> int {
+        HIP_TRY(hipEventSynchronize(L.ev_chunk[i & 1]));
+        if (ch.rows == 1) pool.copy(out + ch.off, slot_of(i), ch.width, copy_threads);
+        else
+            for (size_t y = 0; y < ch.rows; y++) std::memcpy(out + ch.off + y * rowbytes, slot_of(i) + y * ch.width, ch.width);
+        return RSR_OK;
+    };
+    size_t i = 0;
+    FetchSpan prev{};
+    for (int k = 0; k < fp.n; k++)
+    {
+        HIP_TRY(ready(fp.span[k]));
+        for (size_t j = 0; j < nch[k]; j++, i++)
+        {
+            const FetchSpan ch = fetch_chunk(fp.span[k], rowbytes, slot, j);
+            // slot i & 1 was drained by the CPU copy of chunk i - 2 in the previous iteration
+            if (ch.rows == 1) HIP_TRY(hipMemcpyAsync(slot_of(i), dev(ch.off), ch.width, hipMemcpyDeviceToHost, L.copy));
+            else HIP_TRY(hipMemcpy2DAsync(slot_of(i), ch.width, dev(ch.off), rowbytes, ch.width, ch.rows, hipMemcpyDeviceToHost, L.copy));
+            HIP_TRY(hipEventRecord(L.ev_chunk[i & 1], L.copy));
+            if (i >= 1)
+                if (const int rc = drain(i - 1, prev)) return rc;
+            prev = ch;
+        }
+    }
+    return i ? drain(i - 1, prev) : RSR_OK;
+}
+
 // RealSR::process for host images.  The call owns a lane: upload on the lane's copy stream, kernels on the compute
 // stream (ordered by events), download on the copy stream again.  Pinned caller memory (rsr_host_alloc, hipHostMalloc,
 // hipHostRegister) is copied directly; pageable memory goes through the lane's pinned staging, the download in chunks so
 // that the CPU copy of chunk i overlaps the PCIe transfer of chunk i+1.
-// tile0 / tile1: only tiles [tile0, tile1) of the row-major tile grid (tiles are independent: realsr.cpp:377-380,458-459,490).
-// A range of whole tile rows is a contiguous byte range of the output; a general range is up to three rectangles -- the
-// tail of its first tile row, whole rows, the head of its last row -- fetched with 2-D copies.
+// tile0 / tile1: only tiles [tile0, tile1) of the row-major tile grid: what of the output that is, fetch_plan says.
+// The steps -- check, tile range, lane, plan, reserve, upload, merged or lane_run, lane_fetch -- are DESIGN.md 6.2.
 int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, int tile0, int tile1)
 {
     if (!in || !out || w < 1 || h < 1 || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
@@ -2174,7 +2360,6 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
         mwidth = merge_width(w, h, c);
         if (mwidth > 1) mitems = image_items(w, h, merge_target_items);
     }
-    const size_t nout_full = size_t(os.of_x(w)) * size_t(os.of_y(h)) * c;
     const int xtiles = (w + T - 1) / T, ytiles = (h + T - 1) / T;
     if (tile1 < 0) tile1 = xtiles * ytiles;
     if (tile0 < 0 || tile1 > xtiles * ytiles || tile0 >= tile1) return fail(RSR_E_ARG, "tile range outside the image");
@@ -2191,67 +2376,30 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
             n = nullptr;
         }
     } inbound{nullptr};
-    Lane* L = acquire_lane();
+    LaneHold hold(this);
+    Lane* const L = hold.l;
     if (mergeable)
     { // counted from here: a call that is still waiting for a lane is not "on its way" (lanes free up when batches complete)
         ++merge_inbound;
         inbound.n = &merge_inbound;
     }
-    // Whatever way this call ends, nothing of it may still be in flight when the lane -- and with it the caller's `in` / `out`
-    // -- is handed back: a HIP failure half way must not turn into a use-after-free of the lane buffers by the next caller.
-    struct Release
-    {
-        Engine* e;
-        Lane* l;
-        bool done_recorded = false;
-        ~Release()
-        {
-            if (l->copy) (void)hipStreamSynchronize(l->copy);
-            if (done_recorded) (void)hipEventSynchronize(l->ev_done);
-            e->release_lane(l);
-        }
-    } guard{this, L};
-    HIP_TRY(hipSetDevice(device));
-    if (!L->copy)
-    {
-        HIP_TRY(hipStreamCreateWithFlags(&L->copy, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&L->ev_in, &L->ev_done, &L->ev_half, &L->ev_chunk[0], &L->ev_chunk[1]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
-    int rc;
-    if ((rc = ensure(L->d_in, nin)) != RSR_OK) return rc;  // lane-private: nothing else can be using the old allocation
+    if (hold.rc != RSR_OK) return hold.rc;
     // The device output holds only the output ROWS of this call's tile range (a member of rsr_process_group running an eighth
-    // of a 4K frame does not allocate 398 MB for it): the kernels get the address row 0 would have and only ever write
-    // inside the rectangles of the range's tiles (conv_last / postproc_tiles place by tile), i.e. inside the allocation.
+    // of a 4K frame does not allocate 398 MB for it): the kernels get the REAL base of the allocation -- the plan of a tile range
+    // places its tiles relative to the range's first output row (Plan::out_row0, in x4 rows, is the x4 row of fp.row0: get_plan) --
+    // and only ever write inside the rectangles of the range's tiles (conv_last / postproc_tiles place by tile), i.e. inside it.
     const size_t rowbytes = size_t(os.of_x(w)) * c; // one output row
-    auto yof = [&](int tr) { return size_t(os.of_y(std::min(tr * T, h))); };  // first output row of tile row tr (whole: out_admit)
-    auto xof = [&](int tc) { return size_t(os.of_x(std::min(tc * T, w))) * c; }; // byte column of tile column tc
-    const int r0 = tile0 / xtiles, c0 = tile0 % xtiles, r1 = (tile1 - 1) / xtiles, c1 = (tile1 - 1) % xtiles + 1; // last tile = (r1, c1 - 1)
-    const size_t base_off = yof(r0) * rowbytes;
-    if ((rc = ensure(L->d_out, (yof(r1 + 1) - yof(r0)) * rowbytes)) != RSR_OK) return rc;
-    L->in_bytes.store(L->d_in.bytes, std::memory_order_relaxed); // what device_avail() / rsr_get_stat read (they do not hold this lane)
-    L->out_bytes.store(L->d_out.bytes, std::memory_order_relaxed);
-    // the kernels get the REAL base of the allocation: the plan of a tile range places its tiles relative to the range's first
-    // output row (Plan::out_row0, in x4 rows, is the x4 row of yof(r0): get_plan); dev(off) = device address of byte `off` of the full-size image
-    char* const dbase = static_cast<char*>(L->d_out.p);
-    auto dev = [&](size_t off) { return dbase + (off - base_off); };
-
-    // ---- upload ----
-    const void* src = in;
-    if (!is_pinned_host(in))
-    {
-        if ((rc = ensure_pinned(L->h_in, L->h_in_bytes, nin)) != RSR_OK) return rc;
-        pool.copy(L->h_in, in, nin, copy_threads);
-        src = L->h_in;
-    }
-    HIP_TRY(hipMemcpyAsync(L->d_in.p, src, nin, hipMemcpyHostToDevice, L->copy));
-    HIP_TRY(hipEventRecord(L->ev_in, L->copy));
+    FetchPlan fp = fetch_plan(w, h, c, T, os, tile0, tile1, 0); // (which rows are early is known once the network is enqueued)
+    int rc;
+    bool out_pinned = false;
+    if ((rc = lane_reserve_out(*L, out + fp.span[0].off, fp.rows * rowbytes, fp.bytes(), out_pinned)) != RSR_OK || (rc = lane_upload(*L, in, nin)) != RSR_OK) return rc;
 
     // ---- network ----
     size_t half_rows = 0;
     if (mergeable)
     {
         MergeReq r;
-        r.d_in = L->d_in.p; r.d_out = dbase; r.w = w; r.h = h; r.c = c; r.T = T;
+        r.d_in = L->d_in.p; r.d_out = L->d_out.p; r.w = w; r.h = h; r.c = c; r.T = T;
         r.os = os;
         r.items = mitems;
         r.width = mwidth;
@@ -2260,7 +2408,7 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
         inbound.release(); // (it is in the queue the moment submit_merged has the lock: the leader's wait ends either way)
         rc = submit_merged(r);
         if (rc != RSR_OK) return rc; // (a batch that failed half way has been drained by its leader: nothing of it is in flight)
-        guard.done_recorded = true;
+        hold.done_recorded = true;
         void (*cb)(int, int, void*) = nullptr;
         void* cb_user = nullptr;
         {
@@ -2273,134 +2421,17 @@ int Engine::process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, i
     }
     else
     {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!loaded || scale != 4 || tilesize != T || out_ratio != os)
-            return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the guard drains the upload)
-        HIP_TRY(hipStreamWaitEvent(stream, L->ev_in, 0));
-        BatchIO io(L->d_in.p, dbase, w, h, c, RSR_FMT_U8_HWC, RSR_FMT_U8_HWC, os);
+        BatchIO io(L->d_in.p, L->d_out.p, w, h, c, RSR_FMT_U8_HWC, RSR_FMT_U8_HWC, os);
         io.ev_half = L->ev_half;
-        rc = enqueue_images(io, tile0, tile1, 0, &half_rows, stream);
-        if (rc != RSR_OK)
-        {
-            (void)hipStreamSynchronize(stream); // kernels of this call that did get enqueued use the lane buffers
-            return rc;
-        }
-        HIP_TRY(hipEventRecord(L->ev_done, stream));
-        guard.done_recorded = true;
+        if ((rc = lane_run(hold, io, tile0, tile1, T, &half_rows)) != RSR_OK) return rc;
+        if (half_rows) fp = fetch_plan(w, h, c, T, os, tile0, tile1, half_rows);
     }
-
-    // ---- download ----
-    if (c0 != 0 || c1 != xtiles)
-    { // general tile range: up to three rectangles.  Pinned destinations receive them directly; pageable ones through the
-      // lane's pinned staging, in row chunks (the CPU copy of chunk i under the PCIe transfer of chunk i+1), like whole rows below
-        HIP_TRY(hipStreamWaitEvent(L->copy, L->ev_done, 0));
-        const bool pinned = is_pinned_host(out);
-        const size_t CH = std::max<size_t>(chunk_bytes, 1 << 20);
-        if (!pinned && (rc = ensure_pinned(L->h_out, L->h_out_bytes, 2 * std::min(CH, nout_full))) != RSR_OK) return rc;
-        auto rect = [&](size_t y_a, size_t y_b, size_t x_a, size_t x_b) -> int {
-            if (y_b <= y_a || x_b <= x_a) return RSR_OK;
-            const size_t wb = x_b - x_a;
-            if (pinned)
-            {
-                const size_t off = y_a * rowbytes + x_a;
-                HIP_TRY(hipMemcpy2DAsync(out + off, rowbytes, dev(off), rowbytes, wb, y_b - y_a, hipMemcpyDeviceToHost, L->copy));
-                return RSR_OK;
-            }
-            const size_t half = L->h_out_bytes / 2, rows_per = std::max<size_t>(1, half / wb);
-            if (wb > half) return fail(RSR_E_ARG, "chunk_mb smaller than one output row");
-            const size_t nch = (y_b - y_a + rows_per - 1) / rows_per;
-            for (size_t i = 0; i <= nch; i++)
-            {
-                if (i < nch)
-                {
-                    const size_t ya = y_a + i * rows_per, nr = std::min(rows_per, y_b - ya);
-                    HIP_TRY(hipMemcpy2DAsync(static_cast<char*>(L->h_out) + (i & 1) * half, wb, dev(ya * rowbytes + x_a), rowbytes, wb, nr,
-                                             hipMemcpyDeviceToHost, L->copy));
-                    HIP_TRY(hipEventRecord(L->ev_chunk[i & 1], L->copy));
-                }
-                if (i >= 1)
-                {
-                    const size_t k = i - 1, ya = y_a + k * rows_per, nr = std::min(rows_per, y_b - ya);
-                    HIP_TRY(hipEventSynchronize(L->ev_chunk[k & 1]));
-                    const char* sp = static_cast<const char*>(L->h_out) + (k & 1) * half;
-                    for (size_t y = 0; y < nr; y++) std::memcpy(out + (ya + y) * rowbytes + x_a, sp + y * wb, wb);
-                }
-            }
-            return RSR_OK;
-        };
-        if (r0 == r1) { if ((rc = rect(yof(r0), yof(r0 + 1), xof(c0), xof(c1))) != RSR_OK) return rc; }
-        else
-        {
-            int full0 = r0, full1 = r1 + 1; // whole tile rows [full0, full1)
-            if (c0 != 0)
-            {
-                if ((rc = rect(yof(r0), yof(r0 + 1), xof(c0), rowbytes)) != RSR_OK) return rc;
-                full0 = r0 + 1;
-            }
-            if (c1 != xtiles)
-            {
-                if ((rc = rect(yof(r1), yof(r1 + 1), 0, xof(c1))) != RSR_OK) return rc;
-                full1 = r1;
-            }
-            if ((rc = rect(yof(full0), yof(full1), 0, rowbytes)) != RSR_OK) return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(L->copy));
-        return RSR_OK;
-    }
-    // whole tile rows [r0, r1]: a contiguous byte range of the HWC image.  When the engine split the 4x tail, the first
-    // `half_rows` output rows are complete at ev_half: they travel while the second part is still being computed.
-    const size_t out_off = yof(r0) * rowbytes, nout = (yof(r1 + 1) - yof(r0)) * rowbytes;
-    out += out_off;
-    const size_t first = std::min(nout, half_rows * rowbytes);
-    const bool pinned_out = is_pinned_host(out);
-    if (pinned_out)
-    {
-        const char* dsrc = dev(out_off);
-        if (first)
-        {
-            HIP_TRY(hipStreamWaitEvent(L->copy, L->ev_half, 0));
-            HIP_TRY(hipMemcpyAsync(out, dsrc, first, hipMemcpyDeviceToHost, L->copy));
-        }
-        HIP_TRY(hipStreamWaitEvent(L->copy, L->ev_done, 0));
-        HIP_TRY(hipMemcpyAsync(out + first, dsrc + first, nout - first, hipMemcpyDeviceToHost, L->copy));
-        HIP_TRY(hipStreamSynchronize(L->copy));
-        return RSR_OK;
-    }
-    HIP_TRY(hipStreamWaitEvent(L->copy, first ? L->ev_half : L->ev_done, 0));
-    const size_t CH = std::max<size_t>(chunk_bytes, 1 << 20);
-    if ((rc = ensure_pinned(L->h_out, L->h_out_bytes, 2 * std::min(CH, nout))) != RSR_OK) return rc;
-    const size_t half = L->h_out_bytes / 2;
-    const size_t nchunks = (nout + half - 1) / half;
-    const char* dsrc = dev(out_off);
-    bool waited_done = false;
-    for (size_t i = 0; i <= nchunks; i++)
-    {
-        if (i < nchunks)
-        {
-            const size_t off = i * half, n = std::min(half, nout - off);
-            if (first && !waited_done && off + n > first)
-            { // this chunk reaches into the rows of the second part
-                HIP_TRY(hipStreamWaitEvent(L->copy, L->ev_done, 0));
-                waited_done = true;
-            }
-            // slot i&1 was drained by the CPU copy of chunk i-2 in the previous iteration
-            HIP_TRY(hipMemcpyAsync(static_cast<char*>(L->h_out) + (i & 1) * half, dsrc + off, n, hipMemcpyDeviceToHost, L->copy));
-            HIP_TRY(hipEventRecord(L->ev_chunk[i & 1], L->copy));
-        }
-        if (i >= 1)
-        {
-            const size_t k = i - 1, off = k * half, n = std::min(half, nout - off);
-            HIP_TRY(hipEventSynchronize(L->ev_chunk[k & 1]));
-            pool.copy(out + off, static_cast<const char*>(L->h_out) + (k & 1) * half, n, copy_threads);
-        }
-    }
-    return RSR_OK;
+    return lane_fetch(*L, reinterpret_cast<char*>(out), out_pinned, rowbytes, fp);
 }
 
 // rsr_process_fmt: process_host for any pair of pixel formats -- tightly packed HOST images, the device path of process_device between an
-// upload and a download.  The call owns a lane like process_host: H2D on the lane's copy stream, the tile batches on the compute stream
-// behind ev_in, D2H on the copy stream behind ev_done, ONE wait at the end.  Pinned caller memory travels directly, pageable memory through
-// the lane's pinned staging (whole images: the call is thin -- no chunked download, no tile range, no merging, no early half).
+// upload and a download.  The same steps on a lane as process_host, for whole images: no tile range, no merging, no early
+// half; the output -- every plane of it -- is ONE contiguous span.
 int Engine::process_host_fmt(const void* in, int in_fmt, int w, int h, int c, void* out, int out_fmt)
 {
     if (!in || !out || w < 1 || h < 1 || w > (1 << 24) || h > (1 << 24) || (c != 3 && c != 4)) return fail(RSR_E_ARG, "bad image arguments");
@@ -2417,60 +2448,15 @@ int Engine::process_host_fmt(const void* in, int in_fmt, int w, int h, int c, vo
         T = tilesize;
     }
     const size_t nin = size_t(fin.rows(h)) * size_t(w) * size_t(fin.es);
-    const size_t nout = size_t(fout.rows(os.of_y(h))) * size_t(os.of_x(w)) * size_t(fout.es);
-    Lane* L = acquire_lane();
-    struct Release // nothing of this call may be in flight when the lane, and with it the caller's `in` / `out`, is handed back (process_host)
-    {
-        Engine* e;
-        Lane* l;
-        bool done_recorded = false;
-        ~Release()
-        {
-            if (l->copy) (void)hipStreamSynchronize(l->copy);
-            if (done_recorded) (void)hipEventSynchronize(l->ev_done);
-            e->release_lane(l);
-        }
-    } guard{this, L};
-    HIP_TRY(hipSetDevice(device));
-    if (!L->copy)
-    {
-        HIP_TRY(hipStreamCreateWithFlags(&L->copy, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&L->ev_in, &L->ev_done, &L->ev_half, &L->ev_chunk[0], &L->ev_chunk[1]}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
-    int rc;
-    if ((rc = ensure(L->d_in, nin)) != RSR_OK || (rc = ensure(L->d_out, nout)) != RSR_OK) return rc;
-    L->in_bytes.store(L->d_in.bytes, std::memory_order_relaxed);
-    L->out_bytes.store(L->d_out.bytes, std::memory_order_relaxed);
-    const bool pinned_out = is_pinned_host(out);
-    if (!pinned_out && (rc = ensure_pinned(L->h_out, L->h_out_bytes, nout)) != RSR_OK) return rc; // (before anything is enqueued)
-    const void* src = in;
-    if (!is_pinned_host(in))
-    {
-        if ((rc = ensure_pinned(L->h_in, L->h_in_bytes, nin)) != RSR_OK) return rc;
-        pool.copy(L->h_in, in, nin, copy_threads);
-        src = L->h_in;
-    }
-    HIP_TRY(hipMemcpyAsync(L->d_in.p, src, nin, hipMemcpyHostToDevice, L->copy));
-    HIP_TRY(hipEventRecord(L->ev_in, L->copy));
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!loaded || scale != 4 || tilesize != T || out_ratio != os)
-            return fail(RSR_E_STATE, "context parameters changed while the call was in flight"); // (the guard drains the upload)
-        HIP_TRY(hipStreamWaitEvent(stream, L->ev_in, 0));
-        rc = enqueue_images(BatchIO(L->d_in.p, L->d_out.p, w, h, c, in_fmt, out_fmt, os), 0, -1, 0, nullptr, stream);
-        if (rc != RSR_OK)
-        {
-            (void)hipStreamSynchronize(stream); // kernels of this call that did get enqueued use the lane buffers
-            return rc;
-        }
-        HIP_TRY(hipEventRecord(L->ev_done, stream));
-        guard.done_recorded = true;
-    }
-    HIP_TRY(hipStreamWaitEvent(L->copy, L->ev_done, 0));
-    HIP_TRY(hipMemcpyAsync(pinned_out ? out : L->h_out, L->d_out.p, nout, hipMemcpyDeviceToHost, L->copy));
-    HIP_TRY(hipStreamSynchronize(L->copy));
-    if (!pinned_out) pool.copy(out, L->h_out, nout, copy_threads);
-    return RSR_OK;
+    const size_t rowbytes = size_t(os.of_x(w)) * size_t(fout.es); // (a UV row has as many bytes as a Y row)
+    const FetchPlan fp{0, size_t(fout.rows(os.of_y(h))), 1, {FetchSpan{0, rowbytes, size_t(fout.rows(os.of_y(h))), false}}};
+    LaneHold hold(this);
+    Lane* const L = hold.l;
+    int rc = hold.rc;
+    bool out_pinned = false;
+    if (rc != RSR_OK || (rc = lane_reserve_out(*L, out, fp.bytes(), fp.bytes(), out_pinned)) != RSR_OK || (rc = lane_upload(*L, in, nin)) != RSR_OK) return rc;
+    if ((rc = lane_run(hold, BatchIO(L->d_in.p, L->d_out.p, w, h, c, in_fmt, out_fmt, os), 0, -1, T, nullptr)) != RSR_OK) return rc;
+    return lane_fetch(*L, static_cast<char*>(out), out_pinned, rowbytes, fp);
 }
 
 // The one-tile batch of the hooks below: one slot of exactly w x h pixels, nothing trimmed; its tables and the planar fp16

@@ -24,6 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -268,6 +269,8 @@ struct Lane
 {
     hipStream_t copy = nullptr;
     hipEvent_t ev_in = nullptr, ev_done = nullptr, ev_half = nullptr, ev_chunk[2] = {nullptr, nullptr};
+    std::array<hipEvent_t*, 5> events() { return {&ev_in, &ev_done, &ev_half, &ev_chunk[0], &ev_chunk[1]}; } // THE list: open() creates them, ~Engine destroys them
+    int open(); // the copy stream and the events, on the lane's first use
     DevBuf d_in, d_out;
     std::atomic<size_t> in_bytes{0}, out_bytes{0}; // sizes of d_in / d_out for readers that do not own the lane (device_avail, rsr_get_stat)
     void* h_in = nullptr;
@@ -275,6 +278,27 @@ struct Lane
     void* h_out = nullptr; // two download chunks
     size_t h_out_bytes = 0;
     bool busy = false;
+};
+struct LaneHold; // engine.cpp: a lane for the duration of one host call
+
+// What a host call downloads (engine.cpp fetch_plan; Engine::lane_fetch): spans of the full-size, tightly packed output image.  A span is
+// `rows` pieces of `width` bytes, one per output row from byte `off` on; width == the bytes of a row: ONE contiguous byte range.
+struct FetchSpan
+{
+    size_t off, width, rows;
+    bool early; // complete at the lane's ev_half already (the first part of a split 4x tail); else at ev_done
+};
+struct FetchPlan
+{
+    size_t row0, rows; // the output rows the spans lie in: what the lane's d_out holds (a member of a group allocates the rows of its range, not the frame)
+    int n;
+    FetchSpan span[3];
+    size_t bytes() const
+    {
+        size_t b = 0;
+        for (int i = 0; i < n; i++) b += span[i].width * span[i].rows;
+        return b;
+    }
 };
 
 struct Engine
@@ -467,6 +491,13 @@ struct Engine
     int process_host(const uint8_t* in, int w, int h, int c, uint8_t* out, int tile0 = 0, int tile1 = -1);
     // host images of any format pair process_device takes, tightly packed (include/realsr_hip.h rsr_process_fmt); never merged, whole images only
     int process_host_fmt(const void* in, int in_fmt, int w, int h, int c, void* out, int out_fmt);
+    // The steps of a host entry point behind its checks, each on the lane the call holds:
+    // d_out of dev_bytes; out_pinned: `out` is pinned memory and receives the copies directly, else the two staging slots of a download of fetch_bytes are made
+    int lane_reserve_out(Lane& L, const void* out, size_t dev_bytes, size_t fetch_bytes, bool& out_pinned);
+    int lane_upload(Lane& L, const void* in, size_t nin);                                 // d_in <- in on the copy stream (pageable memory through h_in), ev_in behind it
+    // the tiles [tile0, tile1) of io on the compute stream behind ev_in, ev_done behind them; refuses when the context is no longer what the call's checks saw (T, io.os)
+    int lane_run(LaneHold& hold, const BatchIO& io, int tile0, int tile1, int T, size_t* half_rows);
+    int lane_fetch(Lane& L, char* out, bool out_pinned, size_t rowbytes, const FetchPlan& fp); // the spans of fp: d_out -> out, each behind its event; returns when they have arrived
     int net_forward(const uint16_t* in, int w, int h, uint16_t* out, float* out32 = nullptr); // out32: the fp32 result (precise mode only)
     // out = act(conv + b); with s1 != 0: v = s1*(conv + b) [+ in[0:cout] when own_res] [, v = s2*v + res when res]
     // precise form (in_lo / res_lo / out_lo, any may be null): the hi + lo / 2048 residual stream of ConvArgs::precise

@@ -77,6 +77,28 @@ def test_pinned_and_pageable_buffers(ctx):
         pin_out.free()
 
 
+def test_pageable_output_in_several_chunks(ctx):
+    """chunk_mb 1: the download into pageable memory goes through the two staging slots in chunks of 1 MiB -- a slot is never larger than
+    chunk_mb says at the time of the call, whatever staging an earlier call left on the lane (Engine::lane_fetch), and never smaller
+    than 1 MiB.  800 x 480 x 6 B = 2.3 MB of 16-bit RGB is three chunks.  The NV12 surface of the same size is 576,000 B, ONE chunk; the
+    1200 x 960 surface of a 300 x 240 image is 1.73 MB, two: the boundary, at 1 MiB, lies inside the Y plane of 1.15 MB."""
+    s = ctx[False]
+    for w, h, out_fmt, chunks in ((200, 120, U16, 3), (200, 120, NV12, 1), (300, 240, NV12, 2)):
+        img = Z.image16(270, w, h)
+        nbytes = R.image_bytes(out_fmt, 4 * w, 4 * h, 3)
+        assert -(-nbytes // (1 << 20)) == chunks and (out_fmt != NV12 or chunks == 1 or 1 << 20 < 4 * w * 4 * h)  # what the docstring says
+        pin = R.PinnedArray((nbytes,))
+        try:
+            spec = s.process_fmt(img, U16, out_fmt)  # chunk_mb 16, pageable: one chunk
+            pinned = s.process_fmt(img, U16, out_fmt, out=pin.array.view(spec.dtype).reshape(spec.shape))
+            s.set_option("chunk_mb", 1)
+            got = s.process_fmt(img, U16, out_fmt, out=np.full_like(spec, 0xCD))
+            assert spec.nbytes == nbytes and np.array_equal(got, spec) and np.array_equal(got, pinned)
+        finally:
+            s.set_option("chunk_mb", 16)
+            pin.free()
+
+
 def test_four_threads_on_one_context(ctx):
     """Four threads, each its own images and format pair, next to one another and next to rsr_process on the same context."""
     s = ctx[False]

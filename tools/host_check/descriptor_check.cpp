@@ -11,6 +11,9 @@
 //   4. WsLayout (workspace.h): buffer sizes and the 6,048 / 6,400 B per pixel against the formulas written out by hand, no two planes or
 //      slots overlap, every plane (lo pair planes included) starts a whole number of planes behind its buffer's start in either mode; and
 //      PlanKey: keys that differ in any one field compare unequal.
+//   5. fetch_plan / fetch_chunks (the download of a host call): for five tile grids, RGB and RGBA, x4, x2 and x3/2, EVERY tile range and every
+//      early half, the spans cover the union of the range's output rectangles byte for byte, each byte once, inside the rows the device
+//      buffer holds; and the staging chunks of every span tile it in order, slot by slot, a rectangle narrower than a row being refused.
 #include "../../realsr-ncnn-vulkan_amd/csrc/engine.cpp"
 
 #include <cinttypes>
@@ -391,6 +394,81 @@ static void workspace_layout()
     for (const PlanKey& k : v) CHECK(!(k == k0) && !(k0 == k));
 }
 
+// fetch_chunks / fetch_chunk: the chunks tile the span exactly and in order, none larger than a staging slot, a rectangle's are whole rows
+static void span_chunks(const FetchSpan& s, size_t rowbytes)
+{
+    const bool flat = s.width == rowbytes;
+    size_t n = 0;
+    for (const size_t slot : {s.width, s.width + 1, size_t(4096), size_t(1) << 20})
+    {
+        if (!flat && s.width > slot) continue; // (refused: below)
+        CHECK(fetch_chunks(s, rowbytes, slot, n) == RSR_OK && n >= 1);
+        size_t next = s.off;
+        for (size_t i = 0; i < n; i++)
+        {
+            const FetchSpan ch = fetch_chunk(s, rowbytes, slot, i);
+            CHECK(ch.off == next && ch.early == s.early && ch.width >= 1 && ch.rows >= 1 && ch.width * ch.rows <= slot);
+            CHECK(flat ? ch.rows == 1 : ch.width == s.width);
+            next += flat ? ch.width : ch.rows * rowbytes;
+        }
+        CHECK(next == s.off + (flat ? s.width * s.rows : s.rows * rowbytes));
+    }
+    if (!flat)
+        for (const size_t slot : {s.width - 1, size_t(1)})
+            CHECK(fetch_chunks(s, rowbytes, slot, n) == RSR_E_ARG && !std::strcmp(last_error(), "chunk_mb smaller than one output row"));
+}
+
+// fetch_plan: the spans of every tile range against the union of the range's output rectangles, written out from min(t * T, extent) and
+// OutRatio::of_x / of_y alone; every byte exactly once, none outside (the maps have the exact size of the output: an overrun is ASan's)
+static void fetch_plans()
+{
+    const int geo[][3] = {{70, 150, 32}, {45, 100, 32}, {33, 32, 32}, {32, 32, 32}, {96, 33, 32}};
+    for (const auto& g : geo)
+        for (const int c : {3, 4})
+            for (const OutRatio os : {OutRatio(), OutRatio(2, 1), OutRatio(3, 2)})
+            {
+                const int w = g[0], h = g[1], T = g[2];
+                if (out_admit(pix_fmt(RSR_FMT_U8_HWC), w, h, T, os, kWhoEngine) != RSR_OK) continue;
+                const int xt = (w + T - 1) / T, yt = (h + T - 1) / T;
+                const size_t rowbytes = size_t(os.of_x(w)) * c, orows = size_t(os.of_y(h));
+                auto edge_x = [&](int t) { return size_t(os.of_x(std::min(t * T, w))) * c; };
+                auto edge_y = [&](int t) { return size_t(os.of_y(std::min(t * T, h))); };
+                for (int tile0 = 0; tile0 < xt * yt; tile0++)
+                    for (int tile1 = tile0 + 1; tile1 <= xt * yt; tile1++)
+                    {
+                        std::vector<uint8_t> want(rowbytes * orows, 0);
+                        for (int t = tile0; t < tile1; t++)
+                            for (size_t y = edge_y(t / xt); y < edge_y(t / xt + 1); y++)
+                                for (size_t x = edge_x(t % xt); x < edge_x(t % xt + 1); x++) want[y * rowbytes + x] = 1;
+                        const int r0 = tile0 / xt, r1 = (tile1 - 1) / xt;
+                        const bool whole = tile0 % xt == 0 && tile1 % xt == 0;
+                        const size_t first_row = edge_y(r0), nrows = edge_y(r1 + 1) - first_row;
+                        std::vector<size_t> halves = {0, nrows + 1}; // (rows of the range: what enqueue_images reports)
+                        for (int tr = r0 + 1; tr <= r1; tr++) halves.push_back(edge_y(tr) - first_row);
+                        for (const size_t half : halves)
+                        {
+                            const FetchPlan p = fetch_plan(w, h, c, T, os, tile0, tile1, half);
+                            CHECK(p.n >= 1 && p.n <= (whole ? 2 : 3) && p.row0 == first_row && p.rows == nrows);
+                            std::vector<uint8_t> got(rowbytes * orows, 0);
+                            size_t bytes = 0;
+                            for (int k = 0; k < p.n; k++)
+                            {
+                                const FetchSpan& s = p.span[k];
+                                CHECK(s.width >= 1 && s.width <= rowbytes && s.rows >= 1 && s.off % rowbytes + s.width <= rowbytes);
+                                CHECK(s.off >= p.row0 * rowbytes && s.off + (s.rows - 1) * rowbytes + s.width <= (p.row0 + p.rows) * rowbytes);
+                                if (s.early) CHECK(whole && k == 0 && s.width == rowbytes && s.off == first_row * rowbytes && s.rows <= half);
+                                for (size_t y = 0; y < s.rows; y++)
+                                    for (size_t x = 0; x < s.width; x++) got[s.off + y * rowbytes + x]++;
+                                bytes += s.width * s.rows;
+                                span_chunks(s, rowbytes);
+                            }
+                            CHECK(got == want && bytes == p.bytes());
+                            if (whole && half) CHECK(p.span[0].early && p.span[0].rows == std::min(half, nrows));
+                        }
+                    }
+            }
+}
+
 int main()
 {
     descriptors();
@@ -398,6 +476,7 @@ int main()
     batches();
     flow_choice();
     workspace_layout();
+    fetch_plans();
     if (failures) return std::fprintf(stderr, "%d check(s) failed\n", failures), 1;
     std::puts("descriptor_check ok");
     return 0;

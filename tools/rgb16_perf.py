@@ -10,7 +10,8 @@ All variants alternate inside every repetition, on ONE torch stream, each timed 
 gate is printed per line: the native path must not be slower than its detour by more than the detour's own spread over the repetitions.
 Then, reported without a gate: post_ms of the U16 launch next to the unfused uint8 launch (engine option "dbg" 8192) and the F16 one, with
 one / two pixels per thread forced (engine option "dbg" 32768 / 65536), the same under TTA (C5), the host call rsr_process_fmt U16 -> U16
-from pinned buffers next to rsr_process u8, and the command line tool on one 1080p 16-bit PNG end to end.
+from pinned buffers next to rsr_process u8 (and either into a pageable array; every host row is max(reps, 20) calls behind 3 warm-up passes --
+the two pinned rows of profiles/rgb16.txt are from `reps` calls behind one), and the command line tool on one 1080p 16-bit PNG end to end.
     python tools/rgb16_perf.py [reps=5] [frames=4] [out=profiles/rgb16.txt]
 """
 import os
@@ -157,14 +158,19 @@ pins = [R.PinnedArray(s) for s in ((h, w, 6), (4 * h, 4 * w, 6), (h, w, 3), (4 *
 a16, o16 = pins[0].array.view(np.uint16).reshape(h, w, 3), pins[1].array.view(np.uint16).reshape(4 * h, 4 * w, 3)
 a8, o8 = pins[2].array, pins[3].array
 a16[:], a8[:] = img16, img8
-host = {"process_fmt u16->u16": [], "process u8": []}
-for rep in range(reps + 1):
-    for n, f in (("process_fmt u16->u16", lambda: sr.process_fmt(a16, U16, U16, out=o16)), ("process u8", lambda: sr.process(a8, out=o8))):
+p16, p8 = np.empty_like(o16), np.empty_like(o8)  # pageable destinations: the download goes through the lane's two staging slots
+host_calls = (("process_fmt u16->u16", lambda: sr.process_fmt(a16, U16, U16, out=o16)), ("process u8", lambda: sr.process(a8, out=o8)),
+              ("process_fmt u16->u16, pageable out", lambda: sr.process_fmt(a16, U16, U16, out=p16)), ("process u8, pageable out", lambda: sr.process(a8, out=p8)))
+host = {n: [] for n, _ in host_calls}
+host_warm, host_reps = 3, max(reps, 20)
+for rep in range(host_warm + host_reps):
+    for n, f in host_calls:
         t0 = time.perf_counter()
         f()
-        if rep:  # (the first pass warms the lanes up)
+        if rep >= host_warm:  # (the first passes warm the lanes up and touch the pageable arrays)
             host[n].append((time.perf_counter() - t0) * 1e3)
 same_as_device = bool(np.array_equal(o16.view(np.int16), outs["u16->u16 x4"].cpu().numpy()))
+pageable_same = bool(np.array_equal(p16, o16) and np.array_equal(p8, o8))
 for p in pins:
     p.free()
 
@@ -219,10 +225,11 @@ for n, _ in shapes:
 lines.append("C5: the same frame under TTA (no gate):")
 for n, _ in tta_shapes:
     lines.append("%-34s pre_ms %.3f post_ms %.3f" % (n, tta_prof[n]["pre_ms"], tta_prof[n]["post_ms"]))
-lines.append("host -> host from pinned buffers, wall clock per call, %d calls each, alternating (no gate); process_fmt moves twice the bytes over PCIe:" % reps)
+lines.append("host -> host from a pinned input, into a pinned or a pageable output, wall clock per call, %d calls each after %d warm-up passes, alternating (no gate);" % (host_reps, host_warm))
+lines.append("process_fmt moves twice the bytes over PCIe:")
 for n, t in host.items():
     lines.append("%-34s median %.2f ms, min %.2f, max %.2f" % (n, np.median(t), min(t), max(t)))
-lines.append("process_fmt u16->u16 equals the device call byte for byte: %s" % same_as_device)
+lines.append("process_fmt u16->u16 equals the device call byte for byte: %s; the pageable outputs equal the pinned ones: %s" % (same_as_device, pageable_same))
 lines += cli_lines
 text = "\n".join(lines)
 print(text)
