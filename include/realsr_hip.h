@@ -763,6 +763,53 @@ int rsr_model_pack(const char* parampath, const char* modelpath, void* dst, size
  * pointer on this context's GPU (is_device=1). */
 int rsr_load_packed(rsr_ctx* ctx, const void* blob, size_t bytes, int is_device);
 
+/* ---- network interpolation: a strength between two loaded models (no reference counterpart) ---------------------------------------------
+ * The reference ships two x4 networks of one architecture, models-DF2K (sharp, keeps compression artefacts) and models-DF2K_JPEG (removes
+ * them, softer), and its user picks one with -m.  ESRGAN's own answer to "too sharp / too smooth" is network interpolation,
+ * w = (1 - t) w_A + t w_B over the weights of two networks with one graph (Real-ESRGAN's -dn, the denoise strength).  Every model the
+ * loader accepts is the one canonical graph, so any two models of one depth can be blended.
+ *
+ * THE RULE.  A and B are packed blobs (rsr_model_pack) whose header and conv table are BYTE-IDENTICAL -- the conv count and, per
+ * convolution, cin / cout / act / nplanes / nt / slope and the three offsets; anything else is RSR_E_GRAPH, rsr_last_error() naming the
+ * first convolution and field that differ (or the two depths).  t is an fp32 in [0, 1], u = fp32(1) - t.  The blend C holds
+ *   - A's header, A's table and every byte of A outside the segments below (the padding behind a segment);
+ *   - for every convolution, every half c of its fp16 weight image, and of the aux image where it has one:
+ *         c = fp16_rne((u * float(a)) + (t * float(b)));
+ *   - for every fp32 bias:  c = (u * a) + (t * b);
+ *   - every operation rounded by itself in fp32, round to nearest even, NO fused multiply-add;
+ *   - t == 0 is A's bytes verbatim and t == 1 B's: copies, not arithmetic;
+ *   - zero padding stays zero by the arithmetic itself; inf and NaN among the weights get no special treatment (IEEE decides).
+ * The blend is of the PACKED halves: a raw-fp32 .bin has been rounded to fp16 by the packing, as for every other use, and the blend
+ * rounds once more -- against blending the fp32 sources that is a second rounding, at most one fp16 ulp.
+ *
+ * rsr_model_blend is the rule in host code (no GPU): check of both blobs (RSR_E_FORMAT), comparison of the tables (RSR_E_GRAPH), then
+ * dst = the blend.  *need (may be NULL) receives its size, a_bytes; dst == NULL only reports it; cap < *need, a NULL blob, NaN or a t
+ * outside [0, 1] are RSR_E_ARG.  dst must not overlap a or b.  The result loads with rsr_load_packed and serves rsr_create_group users
+ * through a model of their own making. */
+int rsr_model_blend(const void* a, size_t a_bytes, const void* b, size_t b_bytes, float t, void* dst, size_t cap, size_t* need);
+
+/* On the device: a context takes a SECOND model beside the one it has loaded and then holds three blobs -- A, B and the active one the
+ * kernels read, which starts as a device-to-device copy of A (strength 0).  A context without a second model holds one blob, as ever.
+ * rsr_load_second / rsr_load_second_packed: RSR_E_STATE before a first model is loaded; everything is validated (and every allocation
+ * made: RSR_E_NOMEM) before the context changes, so a failed call leaves it as it was.  Loading another second model keeps the strength
+ * and blends again; rsr_load / rsr_load_packed of a new FIRST model drop the second and set the strength to 0.
+ * rsr_set_blend: RSR_E_STATE without a second model, RSR_E_ARG for NaN or a t outside [0, 1].  The contract of rsr_load: it waits for
+ * the context's stream, must not run concurrently with processing calls on this context nor under stream capture, and returns when the
+ * active blob is complete (one kernel launch over all segments; a copy at 0 and 1).  The model has then changed hands as behind a
+ * load: the self-check's report and ranges, a `precise` that option "precise_auto" switched on and the per-convolution times are
+ * dropped (under "precise_auto" the self-check runs again on the blended model); plans and workspace stay.
+ * Stats "blend" (the fp32 strength) and "second_loaded".  rsr_process_group: the members must agree on both (the strength by its bits),
+ * RSR_E_ARG before any launch otherwise; rsr_create_group takes no pair -- load the second model per member, or make the group's model
+ * with rsr_model_blend / rsr_model_export. */
+int rsr_load_second(rsr_ctx* ctx, const char* parampath, const char* modelpath);
+int rsr_load_second_packed(rsr_ctx* ctx, const void* blob, size_t bytes, int is_device);
+int rsr_set_blend(rsr_ctx* ctx, float t);
+
+/* The active blob -> host memory: for a plainly loaded context the bytes of rsr_model_pack, behind rsr_set_blend the bytes of
+ * rsr_model_blend.  Keeps a chosen blend for a later rsr_load_packed.  *need (may be NULL) receives the size; dst == NULL only reports
+ * it.  RSR_E_STATE before a load, RSR_E_ARG when cap is too small.  Waits for the context's stream. */
+int rsr_model_export(rsr_ctx* ctx, void* dst, size_t cap, size_t* need);
+
 /* ---- several GPUs of one node ------------------------------------------------ */
 /* What main.cpp:778-791 does per GPU (construct, load), for n GPUs at once: the model is parsed and packed once, uploaded to
  * gpuids[0] and broadcast to the other devices with ONE RCCL collective over xGMI (librccl is dlopen'ed; when it is not
@@ -1048,7 +1095,9 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value);
  *   "precise_active"    0 / 1: the storage mode the next call runs in (option "precise", whoever set it); "out_scale": the output scale in force (0: a ratio other than 4 / 2 / 1, "out_num" / "out_den": rsr_set_out_ratio; 0 / 0 while the axes differ, "out_num_x" / "out_den_x" / "out_num_y" / "out_den_y": rsr_set_out_ratio_xy); "yuv_matrix" / "yuv_range" / "yuv_siting": likewise
  *   "selfcheck_runs"    self-checks run on the context; of the last one: "selfcheck_headroom", "selfcheck_peak_abs", "selfcheck_ms",
  *                       "selfcheck_overflow" (-1 before the first run)
- *   "model_blocks" / "model_convs"  RRDB blocks and convolutions (15 blocks + 6) of the loaded model; 0 before a load */
+ *   "model_blocks" / "model_convs"  RRDB blocks and convolutions (15 blocks + 6) of the loaded model; 0 before a load
+ *   "second_loaded" / "blend"       0 / 1: a second model is loaded (rsr_load_second); the strength of rsr_set_blend, the fp32 value exactly;
+ *                       "blend_us": HIP-event time of the last rsr_set_blend's one launch (or copy), taken while rsr_set_profiling is on, else -1 */
 int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value);
 
 const char* rsr_last_error(const rsr_ctx* ctx); /* ctx may be NULL: last global (create/pack) error */

@@ -42,6 +42,7 @@ EXPORTS = [
     "rsr_video_open", "rsr_video_send", "rsr_video_ready", "rsr_video_receive", "rsr_video_flush", "rsr_video_reset", "rsr_video_info",
     "rsr_video_close",
     "rsr_process_fmt",
+    "rsr_model_blend", "rsr_load_second", "rsr_load_second_packed", "rsr_set_blend", "rsr_model_export",
 ]
 
 NUM_CONVS = 351  # convolutions of the default-depth model (23 RRDB blocks); a loaded model's own count is RealSR.num_convs
@@ -184,6 +185,11 @@ def lib():
     L.rsr_host_free.restype = None
     L.rsr_set_progress_callback.argtypes = [vp, vp, vp]
     L.rsr_load_packed.argtypes = [vp, vp, C.c_size_t, ip]
+    L.rsr_model_blend.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_float, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rsr_load_second.argtypes = [vp, cp, cp]
+    L.rsr_load_second_packed.argtypes = [vp, vp, C.c_size_t, ip]
+    L.rsr_set_blend.argtypes = [vp, C.c_float]
+    L.rsr_model_export.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rsr_model_info.argtypes = [cp, cp, C.POINTER(ip), C.POINTER(ip), C.POINTER(C.c_longlong),
                                  C.POINTER(C.c_longlong), C.POINTER(ip)]
     L.rsr_preproc.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, ip, ip, ip, vp, ip, ip]
@@ -247,6 +253,23 @@ def model_pack(param_path, bin_path):
     if rc != 0:
         raise RealSRError(rc, L.rsr_last_error(None).decode())
     return buf
+
+
+def model_blend(blob_a, blob_b, t):
+    """Host-only network interpolation (rsr_model_blend): the blob (1 - t) * blob_a + t * blob_b of two packed models of one depth,
+    t in [0, 1]; returns bytes.  The rule, rounding by rounding, is in include/realsr_hip.h; the result loads with load_packed."""
+    L = lib()
+    a = np.ascontiguousarray(np.frombuffer(blob_a, dtype=np.uint8) if isinstance(blob_a, (bytes, bytearray, memoryview)) else blob_a, dtype=np.uint8)
+    b = np.ascontiguousarray(np.frombuffer(blob_b, dtype=np.uint8) if isinstance(blob_b, (bytes, bytearray, memoryview)) else blob_b, dtype=np.uint8)
+    need = C.c_size_t()
+    rc = L.rsr_model_blend(_p(a), a.size, _p(b), b.size, float(t), None, 0, need)
+    if rc != 0:
+        raise RealSRError(rc, L.rsr_last_error(None).decode())
+    buf = np.empty(need.value, dtype=np.uint8)
+    rc = L.rsr_model_blend(_p(a), a.size, _p(b), b.size, float(t), _p(buf), buf.size, need)
+    if rc != 0:
+        raise RealSRError(rc, L.rsr_last_error(None).decode())
+    return buf.tobytes()
 
 
 class PinnedArray:
@@ -481,6 +504,36 @@ class RealSR:
         else:
             blob = np.ascontiguousarray(blob, dtype=np.uint8)
             self._ck(self._L.rsr_load_packed(self._h, _p(blob), blob.size, 0))
+
+    def load_second(self, parampath, modelpath):
+        """A second model of the same depth beside the loaded one (rsr_load_second); `blend` then moves the weights between the two."""
+        self._ck(self._L.rsr_load_second(self._h, str(parampath).encode(), str(modelpath).encode()))
+
+    def load_second_packed(self, blob, device_ptr=None):
+        """load_second from a packed blob: np.uint8 array or bytes (host), or pass device_ptr (int) + blob = nbytes."""
+        if device_ptr is not None:
+            self._ck(self._L.rsr_load_second_packed(self._h, C.c_void_p(int(device_ptr)), int(blob), 1))
+        else:
+            blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8)
+            self._ck(self._L.rsr_load_second_packed(self._h, _p(blob), blob.size, 0))
+
+    @property
+    def blend(self):
+        """The strength t of the network interpolation, the weights being (1 - t) * first + t * second model (stat "blend"; 0 without a
+        second model).  Setting it rewrites the context's active weights on the device (rsr_set_blend): not while calls are in flight."""
+        return self.get_stat("blend")
+
+    @blend.setter
+    def blend(self, t):
+        self._ck(self._L.rsr_set_blend(self._h, float(t)))
+
+    def export_model(self):
+        """The packed blob the kernels read, as bytes (rsr_model_export): model_pack's for a plain load, model_blend's behind `blend`."""
+        need = C.c_size_t()
+        self._ck(self._L.rsr_model_export(self._h, None, 0, need))
+        buf = np.empty(need.value, dtype=np.uint8)
+        self._ck(self._L.rsr_model_export(self._h, _p(buf), buf.size, need))
+        return buf.tobytes()
 
     @property
     def num_blocks(self):

@@ -403,6 +403,46 @@ int rsr_load_packed(rsr_ctx* ctx, const void* blob, size_t bytes, int is_device)
     return (rc == RSR_OK && ctx->e.precise_auto) ? ctx->e.apply_precise_auto() : rc;
 }
 
+// ---- network interpolation ------------------------------------------------------------------------------------------------------------
+int rsr_model_blend(const void* a, size_t a_bytes, const void* b, size_t b_bytes, float t, void* dst, size_t cap, size_t* need)
+{
+    std::string err;
+    const int rc = rsr::blend_packed(a, a_bytes, b, b_bytes, t, dst, cap, need, err);
+    return rc == RSR_OK ? RSR_OK : Engine::fail(rc, err);
+}
+
+int rsr_load_second(rsr_ctx* ctx, const char* parampath, const char* modelpath)
+{
+    if (!ctx) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    const int rc = ctx->e.load_second_files(parampath, modelpath);
+    // (a strength other than 0 was in force: the active blob changed, and with it what option "precise_auto" decides from)
+    return (rc == RSR_OK && ctx->e.precise_auto && ctx->e.blend_t != 0.f) ? ctx->e.apply_precise_auto() : rc;
+}
+
+int rsr_load_second_packed(rsr_ctx* ctx, const void* blob, size_t bytes, int is_device)
+{
+    if (!ctx || !blob) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    const int rc = ctx->e.load_second_blob(blob, bytes, is_device != 0);
+    return (rc == RSR_OK && ctx->e.precise_auto && ctx->e.blend_t != 0.f) ? ctx->e.apply_precise_auto() : rc;
+}
+
+int rsr_set_blend(rsr_ctx* ctx, float t)
+{
+    if (!ctx) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    const int rc = ctx->e.set_blend(t);
+    return (rc == RSR_OK && ctx->e.precise_auto) ? ctx->e.apply_precise_auto() : rc; // as behind a load: the model is another one
+}
+
+int rsr_model_export(rsr_ctx* ctx, void* dst, size_t cap, size_t* need)
+{
+    if (!ctx) return RSR_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->e.mu);
+    return ctx->e.export_model(dst, cap, need);
+}
+
 int rsr_model_info(const char* parampath, const char* modelpath, int* n_layers, int* n_convs, long long* n_weights,
                    long long* n_biases, int* bin_encoding)
 {
@@ -739,6 +779,9 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "selfcheck_overflow") *value = e.sc_have ? double(e.sc_last.fp16_overflow) : -1.0;
     else if (k == "model_blocks") *value = double(e.nb);
     else if (k == "model_convs") *value = double(e.nconv);
+    else if (k == "blend") *value = double(e.blend_t); // (the fp32 strength, exactly)
+    else if (k == "second_loaded") *value = e.second ? 1.0 : 0.0;
+    else if (k == "blend_us") *value = e.last_blend_us;
     else return e.fail(RSR_E_ARG, "unknown stat " + k);
     return RSR_OK;
 }

@@ -92,7 +92,7 @@ Engine::~Engine()
         if (l->copy) (void)hipStreamDestroy(l->copy);
     }
     free_plans();
-    for (DevBuf* b : {&blob, &zeros, &trace_buf})
+    for (DevBuf* b : {&blob, &blob_a, &blob_b, &blend_tab, &zeros, &trace_buf})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf& b : ws)
         if (b.p) (void)hipFree(b.p);
@@ -233,6 +233,13 @@ void Engine::adopt_model(const unsigned char* head)
     nconv = int(H.nconv);
     nb = depth_of_convs(H.nconv);
     nrdb = 3 * nb;
+    model_head.assign(head, head + packed_table_bytes(H.nconv));
+    drop_model_state();
+    loaded = true;
+}
+
+void Engine::drop_model_state()
+{
     sc_peak.assign(size_t(nconv), 0.f);
     sc_nonfinite.assign(size_t(nconv), 0);
     conv_ms_by_index.assign(size_t(nconv), 0.0);
@@ -240,7 +247,6 @@ void Engine::adopt_model(const unsigned char* head)
     sc_have = false;
     if (precise_by_auto) precise = false;
     precise_by_auto = false;
-    loaded = true;
 }
 
 int Engine::load_blob_host(const void* data, size_t bytes)
@@ -261,6 +267,7 @@ int Engine::load_blob_host(const void* data, size_t bytes)
     }
     if (blob.p) (void)hipFree(blob.p);
     blob = fresh;
+    drop_second(); // a new first model: the pair is gone, the strength back at 0
     adopt_model(static_cast<const unsigned char*>(data));
     return RSR_OK;
 }
@@ -289,6 +296,7 @@ int Engine::load_blob_device(const void* data, size_t bytes)
     }
     if (blob.p) (void)hipFree(blob.p);
     blob = fresh;
+    drop_second(); // a new first model: the pair is gone, the strength back at 0
     adopt_model(head.data());
     return RSR_OK;
 }
@@ -304,6 +312,145 @@ int Engine::load_files(const char* param, const char* bin)
     rc = pack_model(m, buf.data(), buf.size(), e);
     if (rc != RSR_OK) return fail(rc, e);
     return load_blob_host(buf.data(), buf.size());
+}
+
+// ---- network interpolation ----------------------------------------------------------------
+void Engine::drop_second()
+{
+    for (DevBuf* b : {&blob_a, &blob_b, &blend_tab})
+    {
+        if (b->p) (void)hipFree(b->p);
+        *b = DevBuf();
+    }
+    blend_chunks = 0;
+    second = false;
+    blend_t = 0.f;
+}
+
+int Engine::load_second_files(const char* param, const char* bin)
+{
+    if (!param || !bin) return fail(RSR_E_ARG, "null path");
+    if (!loaded) return fail(RSR_E_STATE, "rsr_load_second: no first model is loaded");
+    Model m;
+    std::string e;
+    int rc = load_model(param, bin, m, e);
+    if (rc != RSR_OK) return fail(rc, e);
+    std::vector<unsigned char> buf(packed_size(m));
+    rc = pack_model(m, buf.data(), buf.size(), e);
+    if (rc != RSR_OK) return fail(rc, e);
+    return load_second_blob(buf.data(), buf.size(), false);
+}
+
+// Everything that can fail happens on fresh allocations; the context changes hands only in the last lines, which cannot fail.
+int Engine::load_second_blob(const void* data, size_t bytes, bool is_device)
+{
+    if (!loaded) return fail(RSR_E_STATE, "rsr_load_second: no first model is loaded");
+    if (!data || bytes < sizeof(PackedHeader)) return fail(RSR_E_FORMAT, "packed blob too small");
+    HIP_TRY(hipSetDevice(device));
+    std::vector<unsigned char> fetched; // header + table of a device blob (load_blob_device)
+    const unsigned char* head = static_cast<const unsigned char*>(data);
+    size_t head_bytes = bytes;
+    if (is_device)
+    {
+        PackedHeader H;
+        HIP_TRY(hipMemcpy(&H, data, sizeof H, hipMemcpyDeviceToHost));
+        if (depth_of_convs(H.nconv) == 0 || packed_table_bytes(H.nconv) > bytes) return fail(RSR_E_FORMAT, "packed blob header mismatch (conv count / size)");
+        fetched.resize(packed_table_bytes(H.nconv));
+        HIP_TRY(hipMemcpy(fetched.data(), data, fetched.size(), hipMemcpyDeviceToHost));
+        head = fetched.data(), head_bytes = fetched.size();
+    }
+    int rc = adopt_table(head, head_bytes, bytes);
+    if (rc != RSR_OK) return rc;
+    std::string e;
+    if ((rc = compare_tables(model_head.data(), head, e)) != RSR_OK) return fail(rc, "second model: " + e);
+    HIP_TRY(hipStreamSynchronize(stream));
+
+    // the chunks of the segments: the table is the first model's, so a pair that is already loaded keeps its own
+    std::vector<BlendChunk> chunks;
+    if (!second)
+    {
+        std::vector<BlendSeg> segs;
+        blend_segments(convs.data(), uint32_t(nconv), segs);
+        for (const BlendSeg& s : segs)
+            for (uint64_t o = 0; o < s.bytes; o += uint64_t(kBlendChunkUnits) * 16)
+                chunks.push_back(BlendChunk{s.off + o, uint32_t(std::min<uint64_t>(s.bytes - o, uint64_t(kBlendChunkUnits) * 16) / 16), s.f32 ? 1u : 0u});
+    }
+    DevBuf fresh_b, fresh_active, fresh_tab;
+    auto give_up = [&](int code) {
+        for (DevBuf* b : {&fresh_b, &fresh_active, &fresh_tab})
+            if (b->p) (void)hipFree(b->p);
+        return code;
+    };
+    if ((rc = ensure(fresh_b, bytes)) != RSR_OK) return give_up(rc);
+    if (!second && ((rc = ensure(fresh_active, bytes)) != RSR_OK || (rc = ensure(fresh_tab, chunks.size() * sizeof(BlendChunk))) != RSR_OK)) return give_up(rc);
+    hipError_t he = hipMemcpy(fresh_b.p, data, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+    if (he == hipSuccess && !second)
+    { // the active blob starts as ONE device-to-device copy of A -- under the test hook "ws_poison" over a buffer full of its pattern
+        if (ws_poison) he = hipMemsetD16(fresh_active.p, (unsigned short)(ws_poison & 0xffff), bytes / 2);
+        if (he == hipSuccess) he = hipMemcpy(fresh_active.p, blob.p, bytes, hipMemcpyDeviceToDevice);
+        if (he == hipSuccess) he = hipMemcpy(fresh_tab.p, chunks.data(), chunks.size() * sizeof(BlendChunk), hipMemcpyHostToDevice);
+    }
+    if (he != hipSuccess) return give_up(fail(RSR_E_DEVICE, std::string("second model upload: ") + hipGetErrorString(he)));
+
+    if (second)
+        (void)hipFree(blob_b.p);
+    else
+    {
+        blob_a = blob;
+        blob = fresh_active;
+        blend_tab = fresh_tab;
+        blend_chunks = int(chunks.size());
+    }
+    blob_b = fresh_b;
+    second = true;
+    // a new second model under a strength that was already chosen: the active blob follows (at 0 it is A's copy and stays)
+    return blend_t != 0.f ? apply_blend() : RSR_OK;
+}
+
+int Engine::apply_blend()
+{
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamSynchronize(stream));
+    // under rsr_set_profiling the one launch (or copy) is bracketed with HIP events: stat "blend_us" (tools/blend_perf.py)
+    hipEvent_t e0 = profiling ? take_event_timed() : nullptr, e1 = profiling ? take_event_timed() : nullptr;
+    if (e0 && e1) (void)hipEventRecord(e0, stream);
+    hipError_t he;
+    if (blend_t == 0.f || blend_t == 1.f) // copies, not arithmetic
+        he = hipMemcpyAsync(blob.p, blend_t == 0.f ? blob_a.p : blob_b.p, blob_a.bytes, hipMemcpyDeviceToDevice, stream);
+    else
+        he = launch_blend_blob(static_cast<const BlendChunk*>(blend_tab.p), blend_chunks, blob_a.p, blob_b.p, blob.p, blend_t, num_cu, stream);
+    if (e0 && e1 && he == hipSuccess) (void)hipEventRecord(e1, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    float ms = 0.f;
+    last_blend_us = (e0 && e1 && he == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? double(ms) * 1e3 : -1.0;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (he != hipSuccess) return fail(RSR_E_DEVICE, std::string("blend: ") + hipGetErrorString(he));
+    drop_model_state(); // the weights changed hands: what a self-check said about the old ones, and the times of their convolutions, go
+    return RSR_OK;
+}
+
+int Engine::set_blend(float t)
+{
+    if (!second) return fail(RSR_E_STATE, "rsr_set_blend: no second model is loaded (rsr_load_second)");
+    if (!(t >= 0.f && t <= 1.f)) return fail(RSR_E_ARG, "rsr_set_blend: the strength must be a number in [0, 1]");
+    const float before = blend_t;
+    blend_t = t == 0.f ? 0.f : t; // (-0 is 0: the members of a group compare their strengths by the bits)
+    const int rc = apply_blend();
+    if (rc != RSR_OK) blend_t = before; // (a device error: the active blob may hold either)
+    return rc;
+}
+
+int Engine::export_model(void* dst, size_t cap, size_t* need)
+{
+    if (!loaded) return fail(RSR_E_STATE, "rsr_model_export: no model is loaded");
+    if (need) *need = blob.bytes;
+    if (!dst) return RSR_OK;
+    if (cap < blob.bytes) return fail(RSR_E_ARG, "rsr_model_export: buffer too small");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(dst, blob.p, blob.bytes, hipMemcpyDeviceToHost));
+    return RSR_OK;
 }
 
 // ---- plan ---------------------------------------------------------------------------------

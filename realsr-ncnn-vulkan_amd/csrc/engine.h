@@ -391,8 +391,25 @@ struct Engine
     // model: depth of the loaded RRDBNet (0 before a load) -- nb RRDB blocks, nrdb = 3 nb dense blocks, nconv = 15 nb + 6 convolutions
     int nb = 0, nrdb = 0, nconv = 0;
     std::vector<PackedConv> convs;
-    DevBuf blob; // packed weights on device
+    DevBuf blob; // packed weights on device: THE blob the kernels read (run_network)
     DevBuf zeros;
+    std::vector<unsigned char> model_head; // header + table of `blob` as it was validated (adopt_model): what a second model's table is compared with
+    // Network interpolation (include/realsr_hip.h "network interpolation"; rsr_load_second, rsr_set_blend).  Without a second model the
+    // context holds `blob` alone, as ever.  With one it holds three blobs of one table: blob_a (the first model: the allocation that was
+    // `blob`), blob_b (the second) and `blob`, the ACTIVE one, = (1 - blend_t) * A + blend_t * B as launch_blend_blob wrote it over the
+    // chunks of blend_tab (a copy of A at 0, of B at 1).  A load of a new first model drops all of it (drop_second).
+    bool second = false;
+    float blend_t = 0.f;
+    DevBuf blob_a, blob_b, blend_tab; // blend_tab: BlendChunk[blend_chunks], built once per second model's first load (the table is A's)
+    int blend_chunks = 0;
+    double last_blend_us = -1.0; // stat "blend_us": HIP-event time of the last blend launch or copy, taken under rsr_set_profiling only (-1: not taken)
+    int load_second_files(const char* param, const char* bin);
+    int load_second_blob(const void* data, size_t bytes, bool is_device);
+    int set_blend(float t);                                  // mu held; returns when the active blob is complete
+    int apply_blend();                                       // active <- blend_t of A and B on the compute stream, waited for; then drop_model_state
+    int export_model(void* dst, size_t cap, size_t* need);   // the active blob -> host
+    void drop_second();                                      // back to one blob (the active one stays `blob`); blend_t = 0
+    void drop_model_state();                                 // what described the model whose weights just changed: see adopt_model
 
     // workspace (workspace.h: one allocation per buffer), laid out for slots of ws_cap_px pixels (0: no layout)
     long long ws_cap_px = 0;

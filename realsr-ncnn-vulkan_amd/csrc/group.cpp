@@ -396,13 +396,14 @@ int rsr_process_group(rsr_ctx* const* ctx, int n, const uint8_t* in, int w, int 
         if (!ctx[i]) return Engine::fail(RSR_E_ARG, "null context in group");
     // every member maps a tile range to pixels with its OWN parameters: they must agree, or rectangles are written twice / never
     int T = 0, P = 0, S = 0, tta = 0, NB = 0;
-    bool AN = false, AA = false;
+    bool AN = false, AA = false, SEC = false;
+    float BT = 0.f; // compared by its bits: members blended at strengths that differ in the last place hold different weights
     rsr::OutRatio OS;
     for (int i = 0; i < n; i++)
     {
         std::lock_guard<std::mutex> lk(ctx[i]->e.mu);
         const Engine& e = ctx[i]->e;
-        if (i == 0) { T = e.tilesize; P = e.prepadding; S = e.scale; OS = e.out_ratio; tta = e.tta; NB = e.nb; AN = e.alpha_net; AA = e.alpha_adaptive; }
+        if (i == 0) { T = e.tilesize; P = e.prepadding; S = e.scale; OS = e.out_ratio; tta = e.tta; NB = e.nb; AN = e.alpha_net; AA = e.alpha_adaptive; SEC = e.second; BT = e.blend_t; }
         else if (e.tilesize != T || e.prepadding != P || e.scale != S || e.out_ratio != OS || e.tta != tta)
             return Engine::fail(RSR_E_ARG, "group members carry different parameters (tilesize / prepadding / scale / out_scale or output ratio / tta)");
         else if (e.alpha_net != AN) // one image, one kind of alpha
@@ -411,6 +412,8 @@ int rsr_process_group(rsr_ctx* const* ctx, int n, const uint8_t* in, int w, int 
             return Engine::fail(RSR_E_ARG, "group members carry different alpha_adaptive options");
         else if (e.nb != NB) // the shares of one image must come from one network
             return Engine::fail(RSR_E_ARG, "group members hold models of different depth (" + std::to_string(NB) + " and " + std::to_string(e.nb) + " RRDB blocks)");
+        else if (e.second != SEC || std::memcmp(&e.blend_t, &BT, sizeof BT)) // ... blended alike (rsr_load_second, rsr_set_blend)
+            return Engine::fail(RSR_E_ARG, "group members differ in their second model or blend strength (" + std::to_string(BT) + " and " + std::to_string(e.blend_t) + ")");
     }
     if (const int rrc = out_admit(pix_fmt(RSR_FMT_U8_HWC), w, h, T, OS, kWhoEngine)) return rrc; // (before any share has written a rectangle)
     const int xtiles = (w + T - 1) / T, ytiles = (h + T - 1) / T, ntiles = xtiles * ytiles;

@@ -476,6 +476,21 @@ struct PlanesArgs
 // of the source read.
 hipError_t launch_move_planes(const PlanesArgs& a, bool pack, hipStream_t st);
 
+// ---- network interpolation: the active blob from two resident ones (rsr_set_blend) --------------------------------------------------------
+// One piece of a blend segment (model.h BlendSeg): `units` 16-byte units from byte `off` of the blobs on, at most kBlendChunkUnits of
+// them, never across the end of its segment.  A workgroup takes whole chunks, so which segment a unit belongs to is never searched for.
+constexpr int kBlendChunkUnits = 1024; // 16 KiB: four units per thread of a 256-thread workgroup, all loads of both blobs in flight in front of the stores
+struct BlendChunk
+{
+    uint64_t off;   // from the start of the blob; a multiple of 16 (segments start 256-byte aligned, chunks are multiples of 16 bytes)
+    uint32_t units; // 1 .. kBlendChunkUnits
+    uint32_t f32;   // fp32 elements (biases), else fp16
+};
+// c = (u * a) + (t * b) over every chunk of the DEVICE table, u = 1 - t: fp16 elements converted to fp32, blended and rounded to nearest
+// even; every operation rounded by itself (no fused multiply-add).  a, b, c: three blobs of one table, 16-byte aligned, c neither a nor
+// b.  Nothing outside the chunks is read or written.  One launch.
+hipError_t launch_blend_blob(const BlendChunk* d_chunks, int nchunks, const void* a, const void* b, void* c, float t, int num_cu, hipStream_t st);
+
 // shader-shaped standalone kernels (parity tests): device pointers
 void launch_preproc_shader(const uint8_t* bottom, int w, int h, int channels, uint16_t* const top[8], int ntop, int outw,
                            int outh, int outcstep, int pad_top, int pad_left, int crop_x, int crop_y, uint16_t* alpha,

@@ -2386,4 +2386,83 @@ void launch_output_compare(const uint16_t* a, const float* b, long long n, unsig
     hipLaunchKernelGGL(output_compare, dim3(grid), dim3(256), 0, st, a, b, nvec, res, ndiff);
 }
 
+// =============================================================================================
+// network interpolation: the active blob from two resident ones (rsr_set_blend)
+// =============================================================================================
+// (u * a) + (t * b), three roundings.  hipcc contracts a product and a sum into one fused multiply-add by default -- also through
+// __fmul_rn / __fadd_rn, which are a plain * and + in this toolchain's headers -- so the two operators stand under the pragma that
+// forbids it: the rule of include/realsr_hip.h is the unfused one, what numpy and the host function compute.
+__device__ __forceinline__ float blend1(float u, float a, float t, float b)
+{
+#pragma clang fp contract(off)
+    const float p = u * a;
+    const float q = t * b;
+    return p + q;
+}
+
+// One 16-byte unit: four fp32 biases, or eight fp16 weights through fp32 and back (round to nearest even: the conversion's default).
+__device__ __forceinline__ uint4 blend_unit(uint4 qa, uint4 qb, float t, float u, bool f32)
+{
+    uint4 r;
+    if (f32)
+    {
+        f32x4 a, b, c;
+        __builtin_memcpy(&a, &qa, 16);
+        __builtin_memcpy(&b, &qb, 16);
+#pragma unroll
+        for (int k = 0; k < 4; k++) c[k] = blend1(u, a[k], t, b[k]);
+        __builtin_memcpy(&r, &c, 16);
+    }
+    else
+    {
+        half8 a, b, c;
+        __builtin_memcpy(&a, &qa, 16);
+        __builtin_memcpy(&b, &qb, 16);
+#pragma unroll
+        for (int k = 0; k < 8; k++) c[k] = (_Float16)blend1(u, (float)a[k], t, (float)b[k]);
+        __builtin_memcpy(&r, &c, 16);
+    }
+    return r;
+}
+
+// A workgroup takes whole chunks, grid-stride: thread i of it the units i, i + 256, i + 512, i + 768 of the chunk -- a wave-instruction
+// moves 1 KiB contiguously.  The eight loads of a thread (four per blob) are issued in front of the arithmetic and the stores; a unit
+// beyond the chunk's end is neither loaded nor stored.  The chunk's three words are the same for the whole workgroup (scalar loads).
+__global__ __launch_bounds__(256) void blend_blob(const BlendChunk* __restrict__ chunks, int nchunks, const char* __restrict__ a, const char* __restrict__ b,
+                                                  char* __restrict__ c, float t, float u)
+{
+#pragma unroll 1
+    for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x)
+    {
+        const BlendChunk k = chunks[ch];
+        const int units = int(k.units), i = threadIdx.x;
+        const bool f32 = k.f32 != 0;
+        const uint4* const va = reinterpret_cast<const uint4*>(a + k.off);
+        const uint4* const vb = reinterpret_cast<const uint4*>(b + k.off);
+        uint4* const vc = reinterpret_cast<uint4*>(c + k.off);
+        const bool b0 = i < units, b1 = i + 256 < units, b2 = i + 512 < units, b3 = i + 768 < units;
+        uint4 a0 = {}, a1 = {}, a2 = {}, a3 = {}, c0 = {}, c1 = {}, c2 = {}, c3 = {};
+        if (b0) a0 = va[i], c0 = vb[i];
+        if (b1) a1 = va[i + 256], c1 = vb[i + 256];
+        if (b2) a2 = va[i + 512], c2 = vb[i + 512];
+        if (b3) a3 = va[i + 768], c3 = vb[i + 768];
+        if (b0) vc[i] = blend_unit(a0, c0, t, u, f32);
+        if (b1) vc[i + 256] = blend_unit(a1, c1, t, u, f32);
+        if (b2) vc[i + 512] = blend_unit(a2, c2, t, u, f32);
+        if (b3) vc[i + 768] = blend_unit(a3, c3, t, u, f32);
+    }
+}
+static_assert(kBlendChunkUnits == 4 * 256, "blend_blob: four units per thread of a 256-thread workgroup");
+
+hipError_t launch_blend_blob(const BlendChunk* d_chunks, int nchunks, const void* a, const void* b, void* c, float t, int num_cu, hipStream_t st)
+{
+    if (nchunks <= 0) return hipSuccess;
+    // a pass that only waits for memory: eight workgroups per CU (eight waves per SIMD) cover the device, the chunks beyond are strided over
+    const int cap = (num_cu > 0 ? num_cu : 256) * 8;
+    const unsigned grid = unsigned(nchunks < cap ? nchunks : cap);
+    hipLaunchKernelGGL(blend_blob, dim3(grid), dim3(256), 0, st, d_chunks, nchunks, static_cast<const char*>(a), static_cast<const char*>(b),
+                       static_cast<char*>(c), t, 1.f - t);
+    return hipGetLastError();
+}
+
 } // namespace rsr

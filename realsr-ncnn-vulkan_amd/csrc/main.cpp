@@ -15,6 +15,9 @@
 //   * RSR_ALPHA=net (no counterpart): the alpha of an RGBA image walks the network as a gray image (rsr_set_option "alpha_net") instead
 //     of taking the bicubic; an image whose alpha is fully opaque keeps the bicubic and its one pass; RSR_ALPHA=adaptive: the library
 //     decides per tile (rsr_set_option "alpha_adaptive"): tiles of constant alpha keep the bicubic, the others go through the network;
+//   * RSR_BLEND=<model-dir>:<t> (no counterpart): beside -m, a second model of the same depth and a strength t in [0, 1]; every context
+//     loads it (rsr_load_second) and runs on the weights (1 - t) * <-m model> + t * <model-dir> (rsr_set_blend): network interpolation,
+//     e.g. -m models-DF2K with RSR_BLEND=models-DF2K_JPEG:0.4;
 //   * video mode (no counterpart): an input that ends in .y4m, or is "-" (stdin), is a YUV4MPEG2 stream and runs through one rsr_video
 //     session to a .y4m output or "-" (stdout) -- run_video below, y4m_io.h.
 #include <dirent.h>
@@ -56,6 +59,8 @@ static void print_usage()
     fprintf(stderr, "                       (8-bit sources widened by x257); auto = 16-bit png/pnm inputs with a .png output keep their 16 bits\n");
     fprintf(stderr, "  RSR_ALPHA=net|bicubic alpha of RGBA images (default=bicubic): net = through the network as a gray image, about twice the\n");
     fprintf(stderr, "                       time; a fully opaque alpha stays opaque and costs one pass\n");
+    fprintf(stderr, "  RSR_BLEND=dir:t      a second model directory of the same depth and a strength t in [0, 1]: the weights are\n");
+    fprintf(stderr, "                       (1 - t) * the -m model + t * the model of dir (network interpolation)\n");
 }
 
 static std::vector<int> parse_int_list(const char* s)
@@ -439,6 +444,34 @@ int main(int argc, char** argv)
             return -1;
         }
     }
+    // RSR_BLEND=<model-dir>:<t> (no flag of the reference's surface is taken for it): network interpolation between the -m model and the
+    // one of <model-dir>, t a plain decimal in [0, 1] behind the LAST colon (digits with at most one point: no sign, no exponent, no blanks).
+    std::string blend_dir, blend_text;
+    float blend_t = 0.f;
+    const char* be = getenv("RSR_BLEND");
+    if (be && *be) // (empty is unset, as for RSR_ALPHA)
+    {
+        const std::string v(be);
+        const size_t colon = v.rfind(':');
+        bool ok = colon != std::string::npos && colon > 0 && colon + 1 < v.size();
+        if (ok)
+        {
+            blend_dir = v.substr(0, colon), blend_text = v.substr(colon + 1);
+            size_t digits = 0, points = 0;
+            for (char ch : blend_text)
+                if (ch >= '0' && ch <= '9') digits++;
+                else if (ch == '.') points++;
+                else ok = false;
+            ok = ok && digits >= 1 && points <= 1 && blend_text.size() <= 32;
+            if (ok) blend_t = std::strtof(blend_text.c_str(), nullptr);
+            ok = ok && blend_t >= 0.f && blend_t <= 1.f;
+        }
+        if (!ok)
+        {
+            fprintf(stderr, "invalid RSR_BLEND '%s' (<model-dir>:<t>, t a decimal in [0, 1], e.g. models-DF2K_JPEG:0.4)\n", be);
+            return -1;
+        }
+    }
     if (gpuid.empty()) gpuid.push_back(0);
     const int ngpu = int(gpuid.size());
     const bool video = is_y4m_path(inputpath) && !is_dir(inputpath); // a YUV4MPEG2 stream: one session on one GPU
@@ -561,6 +594,30 @@ int main(int argc, char** argv)
     }
     const std::string parampath = sanitize_filepath(model + "/x4.param");
     const std::string modelpath = sanitize_filepath(model + "/x4.bin");
+    // RSR_BLEND: both models are read on the host first -- a missing directory, a file that is no model, two depths: refused before any GPU work
+    const std::string blend_param = blend_dir.empty() ? std::string() : sanitize_filepath(blend_dir + "/x4.param");
+    const std::string blend_model = blend_dir.empty() ? std::string() : sanitize_filepath(blend_dir + "/x4.bin");
+    int blend_blocks = 0;
+    if (!blend_dir.empty())
+    {
+        int convs_a = 0, convs_b = 0;
+        if (!is_dir(blend_dir) || rsr_model_info(blend_param.c_str(), blend_model.c_str(), nullptr, &convs_b, nullptr, nullptr, nullptr) != RSR_OK)
+        {
+            fprintf(stderr, "RSR_BLEND: %s holds no model: %s\n", blend_dir.c_str(), is_dir(blend_dir) ? rsr_last_error(nullptr) : "no such directory");
+            return -1;
+        }
+        if (rsr_model_info(parampath.c_str(), modelpath.c_str(), nullptr, &convs_a, nullptr, nullptr, nullptr) != RSR_OK)
+        {
+            fprintf(stderr, "model load failed: %s\n", rsr_last_error(nullptr));
+            return -1;
+        }
+        if (convs_a != convs_b)
+        {
+            fprintf(stderr, "RSR_BLEND: %s has %d RRDB blocks, %s has %d: only models of one depth can be blended\n", blend_dir.c_str(), (convs_b - 6) / 15, model.c_str(), (convs_a - 6) / 15);
+            return -1;
+        }
+        blend_blocks = (convs_b - 6) / 15;
+    }
 
     if (jobs_proc.empty()) jobs_proc.assign(size_t(ngpu), 2);
     if (tilesize.empty()) tilesize.assign(size_t(ngpu), 0);
@@ -585,6 +642,16 @@ int main(int argc, char** argv)
         return -1;
     }
     if (verbose && ngpu > 1) fprintf(stderr, "weights reached %d gpus by: %s\n", ngpu, rsr_group_transport());
+    if (!blend_dir.empty())
+    { // every context gets the pair and the strength (rsr_process_group insists that they agree)
+        for (int i = 0; i < ngpu; i++)
+            if (rsr_load_second(ctxs[size_t(i)], blend_param.c_str(), blend_model.c_str()) != RSR_OK || rsr_set_blend(ctxs[size_t(i)], blend_t) != RSR_OK)
+            {
+                fprintf(stderr, "RSR_BLEND: gpu %d: %s\n", gpuid[size_t(i)], rsr_last_error(ctxs[size_t(i)]));
+                return -1;
+            }
+        if (verbose) fprintf(stderr, "blend %s of %s (%d blocks)\n", blend_text.c_str(), blend_dir.c_str(), blend_blocks);
+    }
     std::vector<std::unique_ptr<RealSR>> realsr;
     for (int i = 0; i < ngpu; i++)
     {

@@ -619,4 +619,128 @@ int check_packed(const void* head, size_t head_bytes, size_t total_bytes, std::s
     return RSR_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// blending two packed blobs
+// ------------------------------------------------------------------------------------------
+void blend_segments(const PackedConv* T, uint32_t nconv, std::vector<BlendSeg>& out)
+{
+    for (uint32_t i = 0; i < nconv; i++)
+    {
+        PackedConv c;
+        std::memcpy(&c, reinterpret_cast<const unsigned char*>(T) + size_t(i) * sizeof(PackedConv), sizeof c);
+        const uint64_t np = c.nplanes, nt = c.nt; // (the sizes check_packed held the offsets to)
+        out.push_back(BlendSeg{c.b_off, nt * 32 * 4, true});
+        out.push_back(BlendSeg{c.w16_off, 2 * np * 9 * nt * 32 * 32, false});
+        if (c.aux_off) out.push_back(BlendSeg{c.aux_off, 2 * np * 3 * 32 * 32, false});
+    }
+}
+
+int compare_tables(const void* head_a, const void* head_b, std::string& err)
+{
+    PackedHeader A, B;
+    std::memcpy(&A, head_a, sizeof A);
+    std::memcpy(&B, head_b, sizeof B);
+    if (A.nconv != B.nconv)
+    {
+        err = "the two models differ in depth: " + std::to_string(depth_of_convs(A.nconv)) + " and " + std::to_string(depth_of_convs(B.nconv)) +
+              " RRDB blocks (" + std::to_string(A.nconv) + " and " + std::to_string(B.nconv) + " convolutions)";
+        return RSR_E_GRAPH;
+    }
+    const unsigned char* ta = static_cast<const unsigned char*>(head_a) + sizeof(PackedHeader);
+    const unsigned char* tb = static_cast<const unsigned char*>(head_b) + sizeof(PackedHeader);
+    for (uint32_t i = 0; i < A.nconv; i++)
+    {
+        PackedConv a, b;
+        std::memcpy(&a, ta + size_t(i) * sizeof a, sizeof a);
+        std::memcpy(&b, tb + size_t(i) * sizeof b, sizeof b);
+        if (!std::memcmp(&a, &b, sizeof a)) continue;
+        const char* field = a.cin != b.cin ? "cin" : a.cout != b.cout ? "cout" : a.act != b.act ? "act" : a.nplanes != b.nplanes ? "nplanes" : a.nt != b.nt ? "nt" :
+                            std::memcmp(&a.slope, &b.slope, sizeof a.slope) ? "slope" : a.b_off != b.b_off ? "b_off" : a.w16_off != b.w16_off ? "w16_off" : "aux_off";
+        err = std::string("the two models differ at convolution ") + std::to_string(i) + ", field " + field;
+        if (!std::strcmp(field, "slope")) err += " (" + std::to_string(a.slope) + " and " + std::to_string(b.slope) + ")";
+        return RSR_E_GRAPH;
+    }
+    if (std::memcmp(&A, &B, sizeof A))
+    { // (equal tables and both sizes checked against their own blob: nothing of a header that check_packed passed is left to differ)
+        err = "the two models differ in their blob headers";
+        return RSR_E_GRAPH;
+    }
+    return RSR_OK;
+}
+
+namespace {
+// One rounding each: a product and a sum behind calls the compiler does not look through cannot be contracted into a fused multiply-add,
+// whatever -ffp-contract says and whatever the target has.
+#if defined(__GNUC__)
+#define RSR_NOINLINE __attribute__((noinline))
+#else
+#define RSR_NOINLINE
+#endif
+RSR_NOINLINE float mul_rn(float x, float y) { return x * y; }
+RSR_NOINLINE float add_rn(float x, float y) { return x + y; }
+float blend1(float u, float a, float t, float b) { return add_rn(mul_rn(u, a), mul_rn(t, b)); }
+} // namespace
+
+int blend_packed(const void* a, size_t a_bytes, const void* b, size_t b_bytes, float t, void* dst, size_t cap, size_t* need, std::string& err)
+{
+    if (!a || !b)
+    {
+        err = "null blob";
+        return RSR_E_ARG;
+    }
+    if (!(t >= 0.f && t <= 1.f)) // (NaN compares false)
+    {
+        err = "blend strength must be a number in [0, 1]";
+        return RSR_E_ARG;
+    }
+    int rc = check_packed(a, a_bytes, a_bytes, err);
+    if (rc != RSR_OK) { err = "first model: " + err; return rc; }
+    rc = check_packed(b, b_bytes, b_bytes, err);
+    if (rc != RSR_OK) { err = "second model: " + err; return rc; }
+    rc = compare_tables(a, b, err);
+    if (rc != RSR_OK) return rc;
+    if (need) *need = a_bytes;
+    if (!dst) return RSR_OK;
+    if (cap < a_bytes)
+    {
+        err = "blended blob buffer too small";
+        return RSR_E_ARG;
+    }
+    const unsigned char* pa = static_cast<const unsigned char*>(a);
+    const unsigned char* pb = static_cast<const unsigned char*>(b);
+    unsigned char* pc = static_cast<unsigned char*>(dst);
+    if (t == 1.f)
+    { // B's bytes verbatim (its header and table are A's)
+        std::memcpy(pc, pb, a_bytes);
+        return RSR_OK;
+    }
+    std::memcpy(pc, pa, a_bytes);
+    if (t == 0.f) return RSR_OK;
+    PackedHeader H;
+    std::memcpy(&H, a, sizeof H);
+    std::vector<BlendSeg> segs;
+    blend_segments(reinterpret_cast<const PackedConv*>(pa + sizeof(PackedHeader)), H.nconv, segs);
+    const float u = 1.f - t;
+    for (const BlendSeg& s : segs) // (any byte buffer: elements travel through memcpy)
+        if (s.f32)
+            for (uint64_t o = s.off; o < s.off + s.bytes; o += 4)
+            {
+                float x, y;
+                std::memcpy(&x, pa + o, 4);
+                std::memcpy(&y, pb + o, 4);
+                const float z = blend1(u, x, t, y);
+                std::memcpy(pc + o, &z, 4);
+            }
+        else
+            for (uint64_t o = s.off; o < s.off + s.bytes; o += 2)
+            {
+                uint16_t x, y;
+                std::memcpy(&x, pa + o, 2);
+                std::memcpy(&y, pb + o, 2);
+                const uint16_t z = f32_to_f16(blend1(u, f16_to_f32(x), t, f16_to_f32(y)));
+                std::memcpy(pc + o, &z, 2);
+            }
+    return RSR_OK;
+}
+
 } // namespace rsr

@@ -112,6 +112,26 @@ void canonical_conv(int index, int& cin, int& cout, int& act);
 // ... and at depth nb (index 0 .. num_convs(nb) - 1)
 void canonical_conv(int nb, int index, int& cin, int& cout, int& act);
 
+// ---- blending two packed blobs (include/realsr_hip.h "network interpolation") ------------------------------------------------------------
+// What a blend computes: the segments of a blob that hold numbers.  Per convolution, in table order: the fp32 biases, the fp16 w16
+// image, and the fp16 aux image where aux_off != 0.  Every segment starts 256-byte aligned and is a multiple of 16 bytes (nt * 128,
+// np * nt * 18432, np * 6144).  Everything else of a blob -- header, table, the padding behind a segment -- is not a number.
+struct BlendSeg
+{
+    uint64_t off, bytes;
+    bool f32; // fp32 elements (biases), else fp16
+};
+// The segments of the table T of nconv entries (a table check_packed has passed), appended to out
+void blend_segments(const PackedConv* T, uint32_t nconv, std::vector<BlendSeg>& out);
+// Are header + table of two checked blobs byte-identical (head_a, head_b: at least packed_table_bytes of their nconv)?  RSR_E_GRAPH
+// otherwise, err naming the depths, or the first convolution and field that differ.
+int compare_tables(const void* head_a, const void* head_b, std::string& err);
+// THE rule in C++ (rsr_model_blend): check_packed of both, compare_tables, then dst = a outside the segments and
+// fp16_rne((u * a) + (t * b)) / (u * a) + (t * b) inside, u = 1 - t, every operation rounded by itself in fp32.  t == 0 / t == 1 copy
+// a / b.  *need (may be null) = the size of the result whenever the two blobs passed; dst == null only reports it.  dst must not
+// overlap a or b.
+int blend_packed(const void* a, size_t a_bytes, const void* b, size_t b_bytes, float t, void* dst, size_t cap, size_t* need, std::string& err);
+
 uint16_t f32_to_f16(float f);
 float f16_to_f32(uint16_t h);
 
