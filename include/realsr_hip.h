@@ -339,6 +339,49 @@ int rsr_process_fmt(rsr_ctx* ctx, const void* in, int in_fmt, int w, int h, int 
  *            keeps its meaning, tiles run through the alpha pass: now the varying ones only.  "alpha_wait_us": host time spent in the waits.
  * Out of scope: a device-side decision without a host wait, a tolerance ("nearly flat"), flat-colour tiles, a public scan entry point. */
 
+/* ---- "dither": position-keyed ordered dither for integer outputs (no reference counterpart) ------------------------------------------------
+ * Every integer the library writes is floor(d * M + 0.5) of a value d it holds far more finely than one code.  An upscaler makes large smooth
+ * gradients -- sky, vignettes, anime backgrounds, out-of-focus areas -- and rounding each pixel to the nearest code turns them into steps
+ * several pixels wide: the banding "16-bit RGB(A)" above exists to avoid.  Most callers cannot take 16 bits (an 8-bit encoder wants NV12, a
+ * 10-bit one P010, a PNG for the web is 8 bits); the library is the one place that still has the unquantised value at the moment of the store.
+ * Option "dither" 1 (0 [default]; anything else RSR_E_ARG, the value in force stays): every COLOUR sample of every INTEGER output format is
+ * rounded against a position-dependent threshold instead of 0.5.  With 0 every launch, byte and stat is what it was.
+ *   The rule, exact.  For the sample at column x, row y of its own plane, in the coordinates of the output image -- (0, 0) is the sample
+ *            rsr_image::data points at (the window's own origin for a window of a canvas):
+ *              h     = (x * 0xC13FA9A9u + y * 0x91E10DA5u) mod 2^32      (uint32 wrap-around)
+ *              k     = h >> 25                                            0 .. 127
+ *              theta = (2k + 1) * 2^-8                                    1/256 .. 255/256, exact in fp32
+ *            the R2 low-discrepancy lattice in integer form: no table, blue-noise-like on gradients, the 128 values equally frequent.  For
+ *            a sample of a subsampled plane (UV of NV12 / P010 / NV16 / P210) x and y are the chroma sample's own indices (X, Y).  The three
+ *            colour samples of an interleaved HWC pixel share the pixel's theta, U and V of one chroma sample share theirs: no chroma noise.
+ *   RGB codes (U8_HWC: M = 255; U16_HWC: M = 65535).  The code is floor(add_rn(mul_rn(d, M), theta)), every operation rounded by itself, d
+ *            what RSR_FMT_F32_CHW holds for that pixel in the same context: clamped to [0, 1], TTA merged, the box or area mean taken,
+ *            fp16-rounded in the default mode and fp32 under "precise".
+ *   YUV codes.  floor(v * scale + (offset + 0.5f)) clamped to [0, maxcode] becomes floor(add_rn(mul_rn(v, scale), add_rn(offset, theta))) with
+ *            the same clamp.  P010 / P210 still store code << 6, YUV444P10 the code low.  The value v that is quantised is the one of
+ *            "dither" 0: the quad mean, the sited filters and their tile-first clamp are untouched.
+ *   Not touched.  Alpha samples are those of "dither" 0, the bicubic alpha and the "alpha_net" alpha alike.  RSR_FMT_F16_CHW / F32_CHW outputs
+ *            are not concerned (same launches, same bytes).  "bgr" swaps samples, not thresholds.
+ *   What follows.  theta is a multiple of 2^-8 below 1, so n + theta is exact for every integer n < 2^16: a d that is exactly a code keeps
+ *            its code -- black stays 0, white stays M, an 8-bit-exact image passes unchanged -- and no clamp can be hit for d in [0, 1].
+ *            The pattern is static and keyed to image coordinates, so a tile's output rectangle is still a function of its padded source
+ *            rectangle alone: masked calls, sequences, propagated rectangles, the video session's reuse of prev_out, tile ranges
+ *            (rsr_process_tiles, _rows), batches, merged concurrent calls and group sharding all give the bytes of the plain call.  An
+ *            `out` window of a canvas carries the pattern from the window's own origin.
+ *   Depths, honestly.  At 8 bits the default mode has about eight fp16 steps per code near white: the dither has something to work with.
+ *            At 10 bits fp16 has two steps per code near white, at 16 bits none to spare: for P010 / P210 / YUV444P10 / U16_HWC the option
+ *            is accepted and follows the same rule, and "precise" is its recommended companion.
+ *   Route.   The rounding lives in the post-processing launch.  A U8_HWC RGB call without TTA at out_scale 4, whose bytes conv_last writes
+ *            itself by default, takes the planar blob and ONE postproc_tiles launch while the option is on -- the route U16, RGBA, TTA and
+ *            YUV calls take anyway -- and the host calls' early download of the first half of the image (the split tail, which hangs on the
+ *            fused store) is off, as for U16.  profiles/dither.txt has the cost.
+ *   Where.   Every route.  rsr_process_group: the members must agree on the option (RSR_E_ARG otherwise).  Read when a tile batch is
+ *            enqueued.  The CLI: RSR_DITHER=1.
+ *   Stats.   "dither": the value in force.
+ * Out of scope: error diffusion, a temporally varying pattern (it would break the masked / sequence invariant and is hostile to encoders),
+ * a table-based blue-noise mask, dithered alpha, a strength, a per-side or per-format switch, a dithering epilogue fused into conv_last,
+ * dither of the fp16 float output. */
+
 /* ---- YUV 4:4:4: RSR_FMT_YUV444P / RSR_FMT_YUV444P10 in and out (no reference counterpart) -------------------------------------------------
  * Screen recordings (H.264 Hi444PP, HEVC RExt, AV1 4:4:4, lossless x264 / FFV1: subsampled chroma smears coloured text), ProRes 4444 and
  * DNxHR 444 masters, and whatever was ever RGB inside libavfilter, VapourSynth or an encoder's input hold three FULL planes of integer codes:
@@ -1030,6 +1073,11 @@ int rsr_get_trace(rsr_ctx* ctx, unsigned long long* out, int n);
  *                       at the price of ONE HOST WAIT PER TILE BATCH, also in asynchronous calls; no such call under stream capture.
  *                       Ignored with "alpha_net" 0 and for c == 3.  Takes effect for the next call.  Any other value: RSR_E_ARG, the value
  *                       in force stays (stats "alpha_adaptive", "alpha_tiles_flat", "alpha_wait_us")
+ *   "dither"            0 [default]: every integer sample is rounded to the nearest code.  1: every colour sample of every integer output
+ *                       format (U8 / U16 RGB(A), the Y / U / V codes of the YUV formats) is rounded against a threshold keyed to its place in
+ *                       the output image ("dither" above has the exact rule); alpha and the float formats are not touched.  A U8 RGB call
+ *                       then leaves conv_last's fused store for one post launch.  Takes effect for the next call.  Any other value:
+ *                       RSR_E_ARG, the value in force stays (stat "dither")
  *   "precise_auto"      1: "precise" is set by the model: on a loaded context rsr_selfcheck runs at once on the built-in tile and "precise"
  *                       becomes its recommend_precise; on a context not yet loaded the same happens at the end of the next successful
  *                       rsr_load / rsr_load_packed (which then returns the self-check's error, if it has one; the model stays loaded).

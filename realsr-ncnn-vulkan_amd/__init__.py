@@ -476,6 +476,23 @@ class RealSR:
     def alpha_adaptive(self, v):
         self.set_option("alpha_adaptive", int(v))  # (anything but 0 or 1 raises RealSRError(RSR_E_ARG) and leaves the value alone)
 
+    @property
+    def dither(self):
+        """0 (default): every integer sample is floor(d * M + 0.5) of the value d the library holds.  1: every COLOUR sample of every integer
+        output format -- uint8 / uint16 RGB(A), the Y / U / V codes of NV12, P010, NV16, P210, YUV444P, YUV444P10 -- is rounded against a
+        threshold keyed to its position in the output image instead (option "dither", include/realsr_hip.h has the rule): smooth gradients
+        come out as fine static noise, not as bands.  A value that is exactly a code keeps it; alpha samples and the float formats are not
+        touched; masked calls, sequences, tile ranges and batches give the bytes of the plain call.  A uint8 RGB call then leaves conv_last's
+        fused store for one post-processing launch.  At 10 and 16 bits `precise` is its companion: fp16 has no steps to spare there.  Takes
+        effect for the next call.  Read from the engine, like alpha_net."""
+        return int(self.get_stat("dither"))
+
+    @dither.setter
+    def dither(self, v):
+        if int(v) != v:  # (the C ABI takes an integer: a fraction must not be truncated into a valid value on its way there)
+            raise RealSRError(RSR_E_ARG, "dither must be 0 (round to nearest) or 1 (ordered dither of integer outputs)")
+        self.set_option("dither", int(v))  # (anything but 0 or 1 raises RealSRError(RSR_E_ARG) and leaves the value alone)
+
     def close(self):
         if getattr(self, "_h", None):
             for v in list(getattr(self, "_videos", ())):  # open video sessions go first: they hold device memory of this context

@@ -772,6 +772,7 @@ int rsr_get_stat(rsr_ctx* ctx, const char* key, double* value)
     else if (k == "alpha_adaptive") *value = e.alpha_adaptive ? 1.0 : 0.0;
     else if (k == "alpha_tiles_flat") *value = double(e.alpha_tiles_flat);
     else if (k == "alpha_wait_us") *value = e.alpha_wait_us;
+    else if (k == "dither") *value = e.dither ? 1.0 : 0.0;
     else if (k == "selfcheck_runs") *value = double(e.selfcheck_runs);
     else if (k == "selfcheck_headroom") *value = e.sc_have ? double(e.sc_last.headroom) : -1.0;
     else if (k == "selfcheck_peak_abs") *value = e.sc_have ? double(e.sc_last.peak_abs) : -1.0;
@@ -847,6 +848,11 @@ int rsr_set_option(rsr_ctx* ctx, const char* key, long long value)
     { // under alpha_net 1, skip the alpha pass on tiles whose alpha is constant (include/realsr_hip.h "alpha_adaptive"); read when the next batch is enqueued
         if (value != 0 && value != 1) return ctx->e.fail(RSR_E_ARG, "alpha_adaptive must be 0 (every tile runs the alpha pass) or 1 (tiles of constant alpha skip it)");
         ctx->e.alpha_adaptive = value != 0;
+    }
+    else if (k == "dither")
+    { // the colour samples of integer outputs rounded against the position-keyed threshold (include/realsr_hip.h "dither"); read when the next batch is enqueued
+        if (value != 0 && value != 1) return ctx->e.fail(RSR_E_ARG, "dither must be 0 (round to nearest) or 1 (ordered dither of integer outputs)");
+        ctx->e.dither = value != 0;
     }
     else if (k == "precise_auto")
     { // the model decides: now when one is loaded, else at the end of the next load (rsr_load / rsr_load_packed)

@@ -1324,6 +1324,7 @@ int Engine::launch_batch(const Plan::Batch& b, int max_tw, int max_th, int ntile
     po.tilesize = tilesize;
     po.bgr = bgr ? 1 : 0;
     po.variant = variant;
+    po.dither = dither && io.out_fmt != kFmtF16 && io.out_fmt != kFmtF32 ? 1 : 0; // (the alpha pass below does not look at it)
     launch_postproc_tiles(po, (max_tw - 2 * prepadding) * scale, (max_th - 2 * prepadding) * scale, st);
     mark(2, 0, b.px[2] / per * (6.0 * per + BatchIO::image_px_bytes(io.out_fmt, c) * io.os.nx * io.os.ny / (16.0 * io.os.dx * io.os.dy)), st);
     if (!two_pass) return RSR_OK;

@@ -343,6 +343,14 @@ struct Engine
     TableRing alpha_ring;           // the tables of the sub-batches (pinned image, one asynchronous copy on the call's stream)
     // The scan of the first ntiles tiles of b on st, its bytes on their way to flat_ring.host(), the ring's event recorded behind them
     int enqueue_flat_scan(const Plan::Batch& b, int max_th, int ntiles, hipStream_t st, const BatchIO& io);
+    // Option "dither" (include/realsr_hip.h "dither"): the colour samples of every integer output format are rounded against a threshold
+    // keyed to the sample's position in the output image instead of 0.5 (kernels.h PostArgs::dither).  Read when a batch is enqueued, like
+    // alpha_adaptive.  The rounding lives in the post launch alone, so while it is on conv_last never writes the image itself
+    // (conv_last_writes_image): a uint8 RGB call without TTA takes the planar blob and one postproc_tiles launch, the route uint16, RGBA, TTA
+    // and YUV calls take anyway, and the split tail of the host calls' early download, which hangs on the fused store, is off as for uint16.
+    // No table of a plan depends on the route (the placement fields of the 4x work items are made for every non-TTA plan and merely go
+    // unread), so one cached plan serves a context that alternates between the two settings.
+    bool dither = false;
     // Model self-check (include/realsr_hip.h rsr_selfcheck): one tile through the network in both storages, compared on the device.
     bool precise_auto = false;    // option "precise_auto": `precise` follows the self-check's recommendation (now when loaded, else at the next load)
     long long selfcheck_runs = 0;
@@ -554,10 +562,12 @@ struct Engine
     {
         return PlaneSrc{static_cast<const char*>(ws[buf].p) + layout().plane_off(buf, plane), layout().slot_stride(buf), layout().plane_bytes(buf)};
     }
-    // no TTA merge / alpha channel / box reduction / YUV surface / uint16 image needs the planar blob (kDbgNoFusedLast: off)
+    // no TTA merge / alpha channel / box reduction / YUV surface / uint16 image needs the planar blob (kDbgNoFusedLast: off); nor does a
+    // dithered uint8 image (the planar float formats are not dithered and keep the fused store)
     bool conv_last_writes_image(int c, int out_fmt) const
     {
-        return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && out_fmt != kFmtU16 && !(dbg & kDbgNoFusedLast);
+        return !tta && c == 3 && out_ratio == OutRatio() && !fmt_is_yuv(out_fmt) && out_fmt != kFmtU16 && !(dbg & kDbgNoFusedLast) &&
+               !(dither && out_fmt == kFmtU8);
     }
     int check_tile_px(long long cap_px) const; // RSR_E_ARG when the 32-bit plane offsets of the kernels cannot address a slot of cap_px LR pixels
     // The first nslots_used slots of the batch through the network (a merged batch narrower than its plan: fewer than b.nslots).

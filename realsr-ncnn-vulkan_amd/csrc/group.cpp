@@ -396,20 +396,22 @@ int rsr_process_group(rsr_ctx* const* ctx, int n, const uint8_t* in, int w, int 
         if (!ctx[i]) return Engine::fail(RSR_E_ARG, "null context in group");
     // every member maps a tile range to pixels with its OWN parameters: they must agree, or rectangles are written twice / never
     int T = 0, P = 0, S = 0, tta = 0, NB = 0;
-    bool AN = false, AA = false, SEC = false;
+    bool AN = false, AA = false, DI = false, SEC = false;
     float BT = 0.f; // compared by its bits: members blended at strengths that differ in the last place hold different weights
     rsr::OutRatio OS;
     for (int i = 0; i < n; i++)
     {
         std::lock_guard<std::mutex> lk(ctx[i]->e.mu);
         const Engine& e = ctx[i]->e;
-        if (i == 0) { T = e.tilesize; P = e.prepadding; S = e.scale; OS = e.out_ratio; tta = e.tta; NB = e.nb; AN = e.alpha_net; AA = e.alpha_adaptive; SEC = e.second; BT = e.blend_t; }
+        if (i == 0) { T = e.tilesize; P = e.prepadding; S = e.scale; OS = e.out_ratio; tta = e.tta; NB = e.nb; AN = e.alpha_net; AA = e.alpha_adaptive; DI = e.dither; SEC = e.second; BT = e.blend_t; }
         else if (e.tilesize != T || e.prepadding != P || e.scale != S || e.out_ratio != OS || e.tta != tta)
             return Engine::fail(RSR_E_ARG, "group members carry different parameters (tilesize / prepadding / scale / out_scale or output ratio / tta)");
         else if (e.alpha_net != AN) // one image, one kind of alpha
             return Engine::fail(RSR_E_ARG, "group members carry different alpha_net options");
         else if (e.alpha_adaptive != AA) // ... and one rule for its flat tiles
             return Engine::fail(RSR_E_ARG, "group members carry different alpha_adaptive options");
+        else if (e.dither != DI) // one image, one rounding: the shares of a dithered image carry one pattern
+            return Engine::fail(RSR_E_ARG, "group members carry different dither options");
         else if (e.nb != NB) // the shares of one image must come from one network
             return Engine::fail(RSR_E_ARG, "group members hold models of different depth (" + std::to_string(NB) + " and " + std::to_string(e.nb) + " RRDB blocks)");
         else if (e.second != SEC || std::memcmp(&e.blend_t, &BT, sizeof BT)) // ... blended alike (rsr_load_second, rsr_set_blend)

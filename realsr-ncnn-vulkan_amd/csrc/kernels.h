@@ -387,6 +387,11 @@ struct PostArgs
     // image of the alpha; ONLY sample 3 of every pixel is stored, the mean of the three channel values RSR_FMT_F32_CHW would hold
     // (postproc_tiles_alpha: x4, box and area alike).  in_imgs, in_fmt, bgr and variant are not looked at.
     int alpha_dst;
+    // 1 (engine option "dither"; an integer out_fmt: uint8 / uint16 HWC, every YUV surface): every colour sample is rounded against the
+    // threshold theta(x, y) of include/realsr_hip.h ("dither") instead of 0.5 -- x, y the sample's own indices in its plane of the output
+    // image, made from BaseTile::out_x / out_y (NOT relative to out_row0: a tile range carries the image's pattern).  Kernels of their own:
+    // the instantiations of 0 are untouched.  Alpha samples (the bicubic, and the whole alpha_dst launch) and the float formats ignore it.
+    int dither;
 };
 void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_t st);
 

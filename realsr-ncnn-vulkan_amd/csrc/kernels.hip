@@ -433,6 +433,13 @@ static void with_siting(int siting, F f)
     else if (siting == 2) f(std::integral_constant<int, 2>{});
     else f(std::integral_constant<int, 0>{});
 }
+// f(bool_constant DI): the dithering instantiation of a post kernel (PostArgs::dither) or the plain one
+template <typename F>
+static void with_dither(const PostArgs& a, F f)
+{
+    if (a.dither) f(std::true_type{});
+    else f(std::false_type{});
+}
 // f(siting, vertical chroma shift VS) of a YUV surface: VS 1 = 4:2:0 with its three sitings; VS 0 = 4:2:2, left or centre -- top-left has no
 // vertical meaning there and IS left (the same kernels, the same bytes).  (Semi-planar surfaces: a planar 4:4:4 one has nothing to site.)
 template <typename F>
@@ -492,18 +499,45 @@ template <typename T> constexpr bool is_hwc = std::is_integral<T>::value;
 // The uint16 sample (kFmtU16) of d, what RSR_FMT_F32_CHW holds for the pixel, already in [0, 1]: floor(d * 65535 + 0.5), the product and the
 // sum rounded by themselves.
 __device__ __forceinline__ uint16_t post_store16(float d) { return (uint16_t)floorf(add_rn(mul_rn(d, 65535.f), 0.5f)); }
-// The colour sample of an HWC image from the value v the uint8 conversion sees (not clamped) ...
-template <typename TO>
-__device__ __forceinline__ TO hwc_sample(float v)
+
+// ---- ordered dither (engine option "dither": PostArgs::dither) -------------------------------------------------------------------------
+// The threshold theta of include/realsr_hip.h ("dither") for the sample at column x, row y of its plane of the OUTPUT IMAGE: the R2 lattice
+// in integers, h = x * 0xC13FA9A9 + y * 0x91E10DA5 mod 2^32, k = h >> 25, theta = (2k + 1) / 256 -- two 32-bit multiplications and an add
+// per pixel, shared by the pixel's samples; no table, no LDS.  Every post kernel has the template argument DI: false = the kernel as it
+// always was (theta_at folds to the 0.5f nobody reads), true = an instantiation of its own that makes theta from the output coordinates
+// the thread already holds and hands it to the sample helpers below.
+__device__ __forceinline__ float dither_theta(int x, int y)
 {
-    if constexpr (sizeof(TO) == 1) return post_store(v * 255.f);
+    const unsigned h = (unsigned)x * 0xC13FA9A9u + (unsigned)y * 0x91E10DA5u;
+    return (float)(2u * (h >> 25) + 1u) * (1.f / 256.f); // (an integer below 256 times 2^-8: exact)
+}
+template <bool DI>
+__device__ __forceinline__ float theta_at(int x, int y)
+{
+    if constexpr (DI) return dither_theta(x, y);
+    else return 0.5f;
+}
+// The dithered colour sample of d in [0, 1]: floor(d * M + theta), the product and the sum rounded by themselves.  n + theta is exact for
+// every integer n <= M, so a d that is a code keeps it, and d <= 1 gives at most M + 255/256: no clamp is needed.
+template <typename TO>
+__device__ __forceinline__ TO hwc_dither(float d, float theta)
+{
+    return (TO)floorf(add_rn(mul_rn(d, sizeof(TO) == 1 ? 255.f : 65535.f), theta));
+}
+// The colour sample of an HWC image from the value v the uint8 conversion sees (not clamped) ...
+template <typename TO, bool DI = false>
+__device__ __forceinline__ TO hwc_sample(float v, [[maybe_unused]] float theta = 0.5f)
+{
+    if constexpr (DI) return hwc_dither<TO>(fminf(fmaxf(v, 0.f), 1.f), theta);
+    else if constexpr (sizeof(TO) == 1) return post_store(v * 255.f);
     else return post_store16(fminf(fmaxf(v, 0.f), 1.f));
 }
 // ... and from a value d in [0, 1] (the box mean, the area average)
-template <typename TO>
-__device__ __forceinline__ TO hwc_sample01(float d)
+template <typename TO, bool DI = false>
+__device__ __forceinline__ TO hwc_sample01(float d, [[maybe_unused]] float theta = 0.5f)
 {
-    if constexpr (sizeof(TO) == 1) return post_store(d * 255.f);
+    if constexpr (DI) return hwc_dither<TO>(d, theta);
+    else if constexpr (sizeof(TO) == 1) return post_store(d * 255.f);
     else return post_store16(d);
 }
 // Alpha: the bicubic value v in the units of the SOURCE's samples (TA) becomes one in the units of the destination's (TO) -- where the
@@ -687,7 +721,8 @@ __device__ __forceinline__ void merged_block(const TP* b, long long ss, int w, i
 // TP: element type of the planar blob: _Float16 (the reference's `output` blob) or float (precise mode)
 // TO: element type of the image: uint8_t / uint16_t (HWC), or _Float16 / float (planar [3][out_hs][out_ws], RGB only: post_store_planar)
 // TA: sample type of the RGBA source image the alpha is read from (c == 4; uint8_t or uint16_t, whatever TO is)
-template <typename TP, typename TO, typename TA = uint8_t>
+// DI: the colour samples of an HWC image are dithered (theta_at; the pixel's three share one threshold, the alpha has none)
+template <typename TP, typename TO, typename TA = uint8_t, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -725,7 +760,8 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
     else
     {
         TO* o = reinterpret_cast<TO*>(a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im]) + (t.out_x + gx) * a.c;
-        const TO r = hwc_sample<TO>(v[0]), g = hwc_sample<TO>(v[1]), bl = hwc_sample<TO>(v[2]);
+        const float th = theta_at<DI>(t.out_x + gx, t.out_y + gy);
+        const TO r = hwc_sample<TO, DI>(v[0], th), g = hwc_sample<TO, DI>(v[1], th), bl = hwc_sample<TO, DI>(v[2], th);
         o[a.bgr ? 2 : 0] = r;
         o[1] = g;
         o[a.bgr ? 0 : 2] = bl;
@@ -749,7 +785,8 @@ __global__ __launch_bounds__(256) void postproc_tiles(const PostArgs a)
 // (a 32-pixel row segment of the HWC image = 96 or 128 contiguous bytes).
 // TO != uint8_t (planar float image): lanes run along x, so the values leave straight from the registers, 32 contiguous elements per
 // channel row, and the uint8 staging at the end is not needed.
-template <typename TP, typename TO>
+// DI (uint8 image): the colour bytes are dithered on their way into the staging rows.
+template <typename TP, typename TO, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
 {
     __shared__ TP T[32][sizeof(TP) == 2 ? 34 : 33]; // pitch: conflict-free column reads for 2- and 4-byte elements
@@ -835,9 +872,19 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
             continue;
         }
         unsigned char* o = &ob[gyl][lx * a.c];
-        o[a.bgr ? 2 : 0] = post_store(v[0] * 255.f);
-        o[1] = post_store(v[1] * 255.f);
-        o[a.bgr ? 0 : 2] = post_store(v[2] * 255.f);
+        if constexpr (DI)
+        {
+            const float th = dither_theta(t.out_x + gx0 + lx, t.out_y + gy0 + gyl);
+            o[a.bgr ? 2 : 0] = hwc_sample<uint8_t, true>(v[0], th);
+            o[1] = hwc_sample<uint8_t, true>(v[1], th);
+            o[a.bgr ? 0 : 2] = hwc_sample<uint8_t, true>(v[2], th);
+        }
+        else
+        {
+            o[a.bgr ? 2 : 0] = post_store(v[0] * 255.f);
+            o[1] = post_store(v[1] * 255.f);
+            o[a.bgr ? 0 : 2] = post_store(v[2] * 255.f);
+        }
         if (a.c == 4)
         {
             int bx, by;
@@ -862,7 +909,8 @@ __global__ __launch_bounds__(256) void postproc_tiles_lds(const PostArgs a)
 // pixels; bytes equal to postproc_tiles<., uint16_t>): the pair's 12 bytes (C = 3) leave as three dword stores, its 16 bytes (C = 4) as two 8-byte stores, where
 // the address allows -- a tile's rectangle starts on a multiple of 4 pixels, so only the image's own base and row pitch decide --, else
 // as samples.  The blob's two elements are ONE load (the kept rectangle and the crop are multiples of 4: the run is 2-aligned).
-template <typename TP, int C, typename TA = uint8_t>
+// DI: each of the two pixels has its own threshold.
+template <typename TP, int C, typename TA = uint8_t, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_u16x2(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -876,6 +924,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_u16x2(const PostArgs a)
     const long long ss = a.slot_stride / (long long)sizeof(TP);
     const int sx = gx + a.crop, sy = gy + a.crop;
     unsigned s[3][2]; // [channel of the blob][pixel]
+    const float th0 = theta_at<DI>(t.out_x + gx, t.out_y + gy), th1 = theta_at<DI>(t.out_x + gx + 1, t.out_y + gy);
 #pragma unroll
     for (int q = 0; q < 3; q++)
     {
@@ -891,7 +940,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_u16x2(const PostArgs a)
                 v[i] = c[0][0];
             }
         }
-        s[q][0] = hwc_sample<uint16_t>(v[0]), s[q][1] = hwc_sample<uint16_t>(v[1]);
+        s[q][0] = hwc_sample<uint16_t, DI>(v[0], th0), s[q][1] = hwc_sample<uint16_t, DI>(v[1], th1);
     }
     const unsigned f0 = a.bgr ? s[2][0] : s[0][0], l0 = a.bgr ? s[0][0] : s[2][0], f1 = a.bgr ? s[2][1] : s[0][1], l1 = a.bgr ? s[0][1] : s[2][1];
     uint8_t* o = a.outs[im] + (long long)(t.out_y - a.out_row0 + gy) * a.out_pitch[im] + (long long)(t.out_x + gx) * (2 * C);
@@ -957,8 +1006,8 @@ __device__ __forceinline__ float box_mean(const float (&c)[K][K])
 // divided by K here.  Lanes run along x.  The K elements a thread needs of a blob row are contiguous and K-aligned (crop, the row
 // length 4 * tw and the plane size are multiples of 4): merged_block fetches each run with one load.
 // ALPHA: the uint8 / uint16 image is RGBA (PostArgs::c == 4; a kernel of its own: the bicubic's registers stay out of the RGB path); TA the
-// sample type of the RGBA source.
-template <typename TP, typename TO, int K, bool ALPHA, typename TA = uint8_t>
+// sample type of the RGBA source.  DI: the colour samples are dithered at the pixel's place (t.out_x / K + gx, t.out_y / K + gy) of the reduced image.
+template <typename TP, typename TO, int K, bool ALPHA, typename TA = uint8_t, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -973,6 +1022,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
     const long long ss = a.slot_stride / (long long)sizeof(TP);
     constexpr int es = (int)sizeof(TO);
     uint8_t* const o = a.outs[im] + ((t.out_y - a.out_row0) / K + gy) * (long long)a.out_pitch[im] + (long long)(t.out_x / K + gx) * (is_hwc<TO> ? a.c * es : es);
+    [[maybe_unused]] const float th = theta_at<DI>(t.out_x / K + gx, t.out_y / K + gy);
 #pragma unroll 1 // (one channel at a time: unrolled, the loads of all three are hoisted to the top and cost three times the registers)
     for (int q = 0; q < 3; q++)
     {
@@ -981,7 +1031,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_box(const PostArgs a)
         const float d = box_mean<K>(c); // in [0, 1] like its sixteen / four terms
         const int qo = a.bgr ? 2 - q : q;
         if constexpr (!is_hwc<TO>) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)d;
-        else reinterpret_cast<TO*>(o)[qo] = hwc_sample01<TO>(d);
+        else reinterpret_cast<TO*>(o)[qo] = hwc_sample01<TO, DI>(d, th);
     }
     if constexpr (ALPHA)
     { // alpha: the box mean of postproc_tiles' bicubic x4 value, each clamped to [0, 255] first; two box rows per turn: (s0 + s1) [+ (s2 + s3)]
@@ -1022,12 +1072,16 @@ static void launch_postproc_box(const PostArgs& a, int max_ow, int max_oh, hipSt
     const dim3 grid((max_ow / K + 63) / 64, (max_oh / K + 3) / 4, a.ntiles), block(256);
     if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_box<TP, _Float16, K, false>), grid, block, 0, st, a);
     else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_box<TP, float, K, false>), grid, block, 0, st, a);
-    else if (a.out_fmt == kFmtU16 && a.c == 4)
-        with_alpha_type(a, [&](auto ta) { hipLaunchKernelGGL((postproc_tiles_box<TP, uint16_t, K, true, decltype(ta)>), grid, block, 0, st, a); });
-    else if (a.out_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_box<TP, uint16_t, K, false>), grid, block, 0, st, a);
-    else if (a.c == 4 && a.in_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, true, uint16_t>), grid, block, 0, st, a);
-    else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, false>), grid, block, 0, st, a);
+    else
+        with_dither(a, [&](auto di) {
+            constexpr bool DI = decltype(di)::value;
+            if (a.out_fmt == kFmtU16 && a.c == 4)
+                with_alpha_type(a, [&](auto ta) { hipLaunchKernelGGL((postproc_tiles_box<TP, uint16_t, K, true, decltype(ta), DI>), grid, block, 0, st, a); });
+            else if (a.out_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_box<TP, uint16_t, K, false, uint8_t, DI>), grid, block, 0, st, a);
+            else if (a.c == 4 && a.in_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, true, uint16_t, DI>), grid, block, 0, st, a);
+            else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, true, uint8_t, DI>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((postproc_tiles_box<TP, uint8_t, K, false, uint8_t, DI>), grid, block, 0, st, a);
+        });
 }
 
 // ---- area-averaged output at a rational scale (rsr_set_out_ratio: PostArgs::num / den, e.g. 3/2, 4/3, 9/4, 3/1) -------------------------
@@ -1084,8 +1138,8 @@ __device__ __forceinline__ float area_pixel(const TP* b, long long ss, int w, in
 // otherwise: tilesize * n is a multiple of d, on each axis with its own n / d), so the tile's own coordinates are the image's and no footprint crosses a tile.  Lanes run
 // along x, so a wave's loads of one tap row fall into a few cache lines.  One channel at a time, as in the box kernel.
 // ALPHA: PostArgs::c == 4, the bicubic x4 alpha, clamped to [0, 255] ([0, 65535] of a uint16 image), under the same weights, order and
-// constant; TA the sample type of the RGBA source.
-template <typename TP, typename TO, bool ALPHA, typename TA = uint8_t>
+// constant; TA the sample type of the RGBA source.  DI: the colour samples are dithered at the pixel's place in the output image.
+template <typename TP, typename TO, bool ALPHA, typename TA = uint8_t, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -1101,13 +1155,14 @@ __global__ __launch_bounds__(256) void postproc_tiles_area(const PostArgs a)
     constexpr int es = (int)sizeof(TO);
     uint8_t* const o = a.outs[im] + ((long long)(t.out_y - a.out_row0) * ny / Ly + gy) * (long long)a.out_pitch[im] +
                        ((long long)t.out_x * nx / Lx + gx) * (is_hwc<TO> ? a.c * es : es);
+    [[maybe_unused]] const float th = theta_at<DI>(int((long long)t.out_x * nx / Lx) + gx, int((long long)t.out_y * ny / Ly) + gy);
 #pragma unroll 1
     for (int q = 0; q < 3; q++)
     {
         const float m = area_pixel<TP>(b0 + q * cstep, ss, w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, gx, gy);
         const int qo = a.bgr ? 2 - q : q;
         if constexpr (!is_hwc<TO>) *reinterpret_cast<TO*>(o + qo * a.out_plane[im]) = (TO)m;
-        else reinterpret_cast<TO*>(o)[qo] = hwc_sample01<TO>(m);
+        else reinterpret_cast<TO*>(o)[qo] = hwc_sample01<TO, DI>(m, th);
     }
     if constexpr (ALPHA)
     {
@@ -1133,12 +1188,16 @@ static void launch_postproc_area(const PostArgs& a, int max_ow, int max_oh, hipS
     const dim3 grid((max_ow * a.num / Lx + 63) / 64, (max_oh * a.num_y / Ly + 3) / 4, a.ntiles), block(256);
     if (a.out_fmt == kFmtF16) hipLaunchKernelGGL((postproc_tiles_area<TP, _Float16, false>), grid, block, 0, st, a);
     else if (a.out_fmt == kFmtF32) hipLaunchKernelGGL((postproc_tiles_area<TP, float, false>), grid, block, 0, st, a);
-    else if (a.out_fmt == kFmtU16 && a.c == 4)
-        with_alpha_type(a, [&](auto ta) { hipLaunchKernelGGL((postproc_tiles_area<TP, uint16_t, true, decltype(ta)>), grid, block, 0, st, a); });
-    else if (a.out_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_area<TP, uint16_t, false>), grid, block, 0, st, a);
-    else if (a.c == 4 && a.in_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true, uint16_t>), grid, block, 0, st, a);
-    else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false>), grid, block, 0, st, a);
+    else
+        with_dither(a, [&](auto di) {
+            constexpr bool DI = decltype(di)::value;
+            if (a.out_fmt == kFmtU16 && a.c == 4)
+                with_alpha_type(a, [&](auto ta) { hipLaunchKernelGGL((postproc_tiles_area<TP, uint16_t, true, decltype(ta), DI>), grid, block, 0, st, a); });
+            else if (a.out_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_area<TP, uint16_t, false, uint8_t, DI>), grid, block, 0, st, a);
+            else if (a.c == 4 && a.in_fmt == kFmtU16) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true, uint16_t, DI>), grid, block, 0, st, a);
+            else if (a.c == 4) hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, true, uint8_t, DI>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((postproc_tiles_area<TP, uint8_t, false, uint8_t, DI>), grid, block, 0, st, a);
+        });
 }
 
 // A rational scale other than 4 / 2 / 1 on both axes (rsr_set_out_ratio, rsr_set_out_ratio_xy)?
@@ -1221,12 +1280,23 @@ static void launch_postproc_alpha(const PostArgs& a, int max_ow, int max_oh, hip
 // ---- YUV 4:2:0 and 4:2:2 output (PostArgs::out_fmt kFmtNV12 / kFmtP010, kFmtNV16 / kFmtP210) ------------------------------------
 // code = floor(v * scale + add) clamped to [0, maxcode] (add = offset + 0.5f), as the sample type stores it: P010 / P210 keep it in the
 // high bits; LOW = true (planar 4:4:4) stores the code itself, the six bits above it 0
-template <typename TO, bool LOW = false>
-__device__ __forceinline__ unsigned yuv_code(float v, float scale, float add, float maxcode)
+// DI (option "dither"): code = floor(v * scale + (offset + theta)), the same clamp -- `add` is then the offset ALONE (YuvAdd), the sum in
+// the brackets rounded by itself like the other two operations (exact: an integer offset below 2^16 plus a multiple of 2^-8)
+template <typename TO, bool LOW = false, bool DI = false>
+__device__ __forceinline__ unsigned yuv_code(float v, float scale, float add, float maxcode, [[maybe_unused]] float theta = 0.5f)
 {
+    if constexpr (DI) add = add_rn(add, theta);
     const float q = fminf(fmaxf(floorf(add_rn(mul_rn(v, scale), add)), 0.f), maxcode);
     return sizeof(TO) == 1 || LOW ? (unsigned)q : (unsigned)q << 6;
 }
+// The `add` of yuv_code for the luma (y) and the chroma (c) codes: offset + 0.5f as YuvCoef carries it, or under DI the offset itself (the
+// decode's yoff / coff are the very numbers yadd / cadd were made from: engine.cpp yuv_coef)
+template <bool DI>
+struct YuvAdd
+{
+    float y, c;
+    __device__ __forceinline__ YuvAdd(const YuvCoef& k) : y(DI ? k.yoff : k.yadd), c(DI ? k.coff : k.cadd) {}
+};
 
 // Two neighbouring samples of a surface row (lo in front) as ONE store of twice the sample size where the address allows it.
 template <typename TO>
@@ -1350,7 +1420,11 @@ struct QuadArea
 // is filtered vertically, so no row clamp exists.  rows = the luma rows of this quad that exist: 2, or 1 where the tile's rectangle ends on
 // an odd row (no parity rule holds for a 4:2:2 surface's rows) -- then nothing of row 1 is gathered (unless SRC::whole_quads says it cannot
 // happen) or stored.
-template <typename TO, int SITE, int VS, typename SRC, typename TP>
+//
+// DI (option "dither"): every code is rounded against theta of its own place in its own plane of the output image -- a luma sample at
+// (X + i, Yi + j), Yi the quad's first row in the IMAGE (not in the buffer of a tile range), the (U, V) pair, which shares one threshold,
+// at its chroma indices (X / 2, Yi / 2) or, 4:2:2, (X / 2, Yi + n).  The values that are quantised are untouched.
+template <typename TO, int SITE, int VS, bool DI, typename SRC, typename TP>
 __device__ __forceinline__ void yuv_quad(const PostArgs& a, const BaseTile& t, int im, int gx, int gy, const SRC& src, const TP* b0, long long cstep, int rows = 2)
 {
     constexpr int NC = VS ? 1 : 2; // chroma rows of the quad
@@ -1408,17 +1482,22 @@ __device__ __forceinline__ void yuv_quad(const PostArgs& a, const BaseTile& t, i
     const long long pitch = a.out_pitch[im];
     const int X = src.out_x(t.out_x) + 2 * gx, Y = src.out_y(t.out_y - a.out_row0) + 2 * gy; // the quad's first luma sample
     uint8_t* const oy = a.outs[im] + Y * pitch + (long long)X * (int)sizeof(TO);
+    const YuvAdd<DI> add(k);
+    [[maybe_unused]] const int Yi = src.out_y(t.out_y) + 2 * gy; // the quad's first luma row in the image
 #pragma unroll
     for (int j = 0; j < 2; j++)
         if (VS || j < rows)
-            store_pair<TO>(oy + j * pitch, yuv_code<TO>(yq[j][0], k.yscale, k.yadd, k.maxcode), yuv_code<TO>(yq[j][1], k.yscale, k.yadd, k.maxcode));
+            store_pair<TO>(oy + j * pitch, yuv_code<TO, false, DI>(yq[j][0], k.yscale, add.y, k.maxcode, theta_at<DI>(X, Yi + j)),
+                           yuv_code<TO, false, DI>(yq[j][1], k.yscale, add.y, k.maxcode, theta_at<DI>(X + 1, Yi + j)));
     // the (U, V) pairs: a UV row is as long as a Y row, a pair as wide as two luma samples; 4:2:0 has one for the quad, on UV row Y / 2
     uint8_t* const ouv = a.outs[im] + a.out_plane[im] + (VS ? Y >> 1 : Y) * pitch + (long long)X * (int)sizeof(TO);
 #pragma unroll
     for (int n = 0; n < NC; n++)
     {
         const float cb = mul_rn(sub_rn(bm[n], ym[n]), k.icb), cr = mul_rn(sub_rn(rm[n], ym[n]), k.icr);
-        if (VS || n < rows) store_pair<TO>(ouv + n * pitch, yuv_code<TO>(cb, k.cscale, k.cadd, k.maxcode), yuv_code<TO>(cr, k.cscale, k.cadd, k.maxcode));
+        const float th = theta_at<DI>(X >> 1, VS ? Yi >> 1 : Yi + n);
+        if (VS || n < rows)
+            store_pair<TO>(ouv + n * pitch, yuv_code<TO, false, DI>(cb, k.cscale, add.c, k.maxcode, th), yuv_code<TO, false, DI>(cr, k.cscale, add.c, k.maxcode, th));
     }
 }
 
@@ -1428,7 +1507,7 @@ __device__ __forceinline__ void yuv_quad(const PostArgs& a, const BaseTile& t, i
 // TP: element type of the blob (_Float16, or float in precise mode); TO: sample type of the surface, uint8_t (NV12) or uint16_t (P010).
 // VS = 0: a 4:2:2 surface (TO: uint8_t NV16, uint16_t P210), two stacked luma pairs per thread.  Its rectangles start and end on even
 // COLUMNS only; where one has an odd number of rows (out_scale 1) the threads of its last quad row make one pair (yuv_quad, rows).
-template <typename TP, typename TO, int OS, int SITE = 0, int VS = 1>
+template <typename TP, typename TO, int OS, int SITE = 0, int VS = 1, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
 {
     constexpr int K = 4 / OS, Q = 2 * K; // x4 pixels per output pixel / per quad, along an axis
@@ -1441,7 +1520,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
     const int w = t.tw * 4, h = t.th * 4;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const QuadBox<TP, OS> src{a.slot_stride / (long long)sizeof(TP), w, h, gx * Q + a.crop, gy * Q + a.crop, a.tta};
-    yuv_quad<TO, SITE, VS>(a, t, im, gx, gy, src, b0, (long long)w * h, min(2, oh - 2 * gy));
+    yuv_quad<TO, SITE, VS, DI>(a, t, im, gx, gy, src, b0, (long long)w * h, min(2, oh - 2 * gy));
 }
 
 // The sibling of postproc_tiles_yuv for the scales n / d that are not 4, 2 or 1: yuv_quad over QuadArea.  A tile's rectangle is
@@ -1449,7 +1528,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv(const PostArgs a)
 // admits the call only where those, w * nx / dx and h * ny / dy are even (out_admit), so no quad crosses a tile or the image's edge.
 // Lanes run along x.
 // VS = 0: a 4:2:2 surface -- w * nx / dx and tilesize * nx / dx are even, the two row counts are any (yuv_quad, rows).
-template <typename TP, typename TO, int SITE, int VS = 1>
+template <typename TP, typename TO, int SITE, int VS = 1, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -1462,7 +1541,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv_area(const PostArgs a)
     const int w = t.tw * 4, h = t.th * 4;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const QuadArea<TP> src{a.slot_stride / (long long)sizeof(TP), w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, 2 * gx, 2 * gy};
-    yuv_quad<TO, SITE, VS>(a, t, im, gx, gy, src, b0, (long long)w * h, min(2, oh - 2 * gy));
+    yuv_quad<TO, SITE, VS, DI>(a, t, im, gx, gy, src, b0, (long long)w * h, min(2, oh - 2 * gy));
 }
 
 template <typename TP, typename TO>
@@ -1471,7 +1550,9 @@ static void launch_postproc_yuv_area(const PostArgs& a, int max_ow, int max_oh, 
     const int Lx = 4 * a.den, Ly = 4 * a.den_y; // (ow_tile / 2) x (oh_tile / 2) quads per tile (4:2:2: the last quad row may be half a quad)
     const dim3 grid((max_ow * a.num / Lx / 2 + 63) / 64, ((max_oh * a.num_y / Ly + 1) / 2 + 3) / 4, a.ntiles), block(256);
     with_chroma(a.out_fmt, a.siting, [&](auto site, auto vs) {
-        hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, decltype(site)::value, decltype(vs)::value>), grid, block, 0, st, a);
+        with_dither(a, [&](auto di) {
+            hipLaunchKernelGGL((postproc_tiles_yuv_area<TP, TO, decltype(site)::value, decltype(vs)::value, decltype(di)::value>), grid, block, 0, st, a);
+        });
     });
 }
 
@@ -1482,9 +1563,12 @@ static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipSt
     const dim3 grid((max_ow / q + 63) / 64, ((max_oh / (q / 2) + 1) / 2 + 3) / 4, a.ntiles), block(256); // (4:2:2: the last quad row may be half a quad)
     with_chroma(a.out_fmt, a.siting, [&](auto site, auto vs) {
         constexpr int SITE = decltype(site)::value, VS = decltype(vs)::value;
-        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1, SITE, VS>), grid, block, 0, st, a);
-        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2, SITE, VS>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4, SITE, VS>), grid, block, 0, st, a);
+        with_dither(a, [&](auto di) {
+            constexpr bool DI = decltype(di)::value;
+            if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 1, SITE, VS, DI>), grid, block, 0, st, a);
+            else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 2, SITE, VS, DI>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((postproc_tiles_yuv<TP, TO, 4, SITE, VS, DI>), grid, block, 0, st, a);
+        });
     });
 }
 
@@ -1495,7 +1579,8 @@ static void launch_postproc_yuv(const PostArgs& a, int max_ow, int max_oh, hipSt
 // at a time: the three never hold registers together), Cb = (B - Y') * icb, Cr = (R - Y') * icr; nothing is filtered, so no siting and no
 // tile-first clamp exist.  Three plane stores finish it, the planes out_plane apart; a 10-bit code is stored as it is (the high six bits
 // 0).  n = how many of the NP pixels exist: a rectangle may have an odd width, and nothing of a pixel beyond it is gathered or stored.
-template <typename TO, int NP, typename SRC, typename TP>
+// DI (option "dither"): the three codes of a pixel sit at the same (x, y) of their planes and share theta(x, y).
+template <typename TO, int NP, bool DI, typename SRC, typename TP>
 __device__ __forceinline__ void yuv_pixels(const PostArgs& a, const BaseTile& t, int im, int gx, int gy, const SRC& src, const TP* b0, long long cstep, int n)
 {
     const YuvCoef& k = a.yuv;
@@ -1517,14 +1602,17 @@ __device__ __forceinline__ void yuv_pixels(const PostArgs& a, const BaseTile& t,
         }
     }
     unsigned cy[NP], cu[NP], cv[NP];
+    const int X = src.out_x(t.out_x) + NP * gx, Y = src.out_y(t.out_y - a.out_row0) + gy;
+    const YuvAdd<DI> add(k);
+    [[maybe_unused]] const int Yi = src.out_y(t.out_y) + gy; // the row in the image (Y: in the buffer of a tile range)
 #pragma unroll
     for (int i = 0; i < NP; i++)
     {
-        cy[i] = yuv_code<TO, true>(y[i], k.yscale, k.yadd, k.maxcode);
-        cu[i] = yuv_code<TO, true>(mul_rn(sub_rn(bl[i], y[i]), k.icb), k.cscale, k.cadd, k.maxcode);
-        cv[i] = yuv_code<TO, true>(mul_rn(sub_rn(r[i], y[i]), k.icr), k.cscale, k.cadd, k.maxcode);
+        const float th = theta_at<DI>(X + i, Yi);
+        cy[i] = yuv_code<TO, true, DI>(y[i], k.yscale, add.y, k.maxcode, th);
+        cu[i] = yuv_code<TO, true, DI>(mul_rn(sub_rn(bl[i], y[i]), k.icb), k.cscale, add.c, k.maxcode, th);
+        cv[i] = yuv_code<TO, true, DI>(mul_rn(sub_rn(r[i], y[i]), k.icr), k.cscale, add.c, k.maxcode, th);
     }
-    const int X = src.out_x(t.out_x) + NP * gx, Y = src.out_y(t.out_y - a.out_row0) + gy;
     uint8_t* const o = a.outs[im] + Y * (long long)a.out_pitch[im] + (long long)X * (int)sizeof(TO);
     const long long plane = a.out_plane[im];
     if constexpr (NP == 2)
@@ -1545,7 +1633,7 @@ __device__ __forceinline__ void yuv_pixels(const PostArgs& a, const BaseTile& t,
 // The 4:4:4 sibling of postproc_tiles_yuv: one thread makes NP pixels of one row (yuv_pixels over QuadBox) at the context's out_scale OS (4,
 // 2 or 1).  The rectangle of a tile is out_w / K x out_h / K output pixels, of any parity.  Lanes run along x: every plane store of a wave
 // is one contiguous run.  TP: element type of the blob; TO: uint8_t (YUV444P) or uint16_t (YUV444P10).
-template <typename TP, typename TO, int OS, int NP>
+template <typename TP, typename TO, int OS, int NP, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv444(const PostArgs a)
 {
     constexpr int K = 4 / OS; // x4 pixels per output pixel, along an axis
@@ -1558,12 +1646,12 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv444(const PostArgs a)
     const int w = t.tw * 4, h = t.th * 4;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const QuadBox<TP, OS> src{a.slot_stride / (long long)sizeof(TP), w, h, NP * gx * K + a.crop, gy * K + a.crop, a.tta};
-    yuv_pixels<TO, NP>(a, t, im, gx, gy, src, b0, (long long)w * h, min(NP, ow - NP * gx));
+    yuv_pixels<TO, NP, DI>(a, t, im, gx, gy, src, b0, (long long)w * h, min(NP, ow - NP * gx));
 }
 
 // ... and of postproc_tiles_yuv_area, for every other ratio or pair: yuv_pixels over QuadArea.  The engine admits the call where the ratio
 // rule holds (w, h and tilesize times the ratios whole); the quotients may be odd.
-template <typename TP, typename TO, int NP>
+template <typename TP, typename TO, int NP, bool DI = false>
 __global__ __launch_bounds__(256) void postproc_tiles_yuv444_area(const PostArgs a)
 {
     const BaseTile t = a.tiles[blockIdx.z];
@@ -1576,7 +1664,7 @@ __global__ __launch_bounds__(256) void postproc_tiles_yuv444_area(const PostArgs
     const int w = t.tw * 4, h = t.th * 4;
     const TP* b0 = reinterpret_cast<const TP*>(static_cast<const char*>(a.planar3) + (long long)t.slot0 * a.slot_stride);
     const QuadArea<TP> src{a.slot_stride / (long long)sizeof(TP), w, h, a.crop, a.tta, nx, Lx, ny, Ly, a.area_norm, NP * gx, gy};
-    yuv_pixels<TO, NP>(a, t, im, gx, gy, src, b0, (long long)w * h, min(NP, ow - NP * gx));
+    yuv_pixels<TO, NP, DI>(a, t, im, gx, gy, src, b0, (long long)w * h, min(NP, ow - NP * gx));
 }
 
 // f(integral_constant NP): pixels per thread of the 4:4:4 kernels.  Chosen by the compiler's resource report and by measurement (DESIGN.md
@@ -1598,7 +1686,7 @@ static void launch_postproc_yuv444_area(const PostArgs& a, int max_ow, int max_o
     with_pixels_per_thread(a, false, [&](auto np) {
         constexpr int NP = decltype(np)::value;
         const dim3 grid(((ow + NP - 1) / NP + 63) / 64, (oh + 3) / 4, a.ntiles), block(256);
-        hipLaunchKernelGGL((postproc_tiles_yuv444_area<TP, TO, NP>), grid, block, 0, st, a);
+        with_dither(a, [&](auto di) { hipLaunchKernelGGL((postproc_tiles_yuv444_area<TP, TO, NP, decltype(di)::value>), grid, block, 0, st, a); });
     });
 }
 
@@ -1609,9 +1697,12 @@ static void launch_postproc_yuv444(const PostArgs& a, int max_ow, int max_oh, hi
     with_pixels_per_thread(a, K == 1, [&](auto np) {
         constexpr int NP = decltype(np)::value;
         const dim3 grid(((ow + NP - 1) / NP + 63) / 64, (oh + 3) / 4, a.ntiles), block(256);
-        if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 1, NP>), grid, block, 0, st, a);
-        else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 2, NP>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 4, NP>), grid, block, 0, st, a);
+        with_dither(a, [&](auto di) {
+            constexpr bool DI = decltype(di)::value;
+            if (a.box == 4) hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 1, NP, DI>), grid, block, 0, st, a);
+            else if (a.box == 2) hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 2, NP, DI>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((postproc_tiles_yuv444<TP, TO, 4, NP, DI>), grid, block, 0, st, a);
+        });
     });
 }
 
@@ -1655,23 +1746,27 @@ void launch_postproc_tiles(const PostArgs& a, int max_ow, int max_oh, hipStream_
         with_image_type(a.out_fmt, [&](auto to) {
             using TO = decltype(to);
             const dim3 grid((max_ow + 63) / 64, (max_oh + 3) / 4, a.ntiles);
-            if constexpr (std::is_same<TO, uint16_t>::value)
-                with_alpha_type(a, [&](auto ta) {
-                    const dim3 grid2((max_ow / 2 + 63) / 64, (max_oh + 3) / 4, a.ntiles);
-                    // Measured on the C2 frame (profiles/rgb16.txt): two pixels per thread 0.128 ms against 0.136 for one (RGBA 0.390 against
-                    // 0.453); under TTA the gather dominates and the pair's doubled registers cost more than its stores save (RGB 1.816
-                    // against 1.661).  Default: two without TTA, one with; variant 1 / 2 force one / two (the bytes are the same).
-                    const bool two = a.variant == 2 || (a.variant == 0 && !a.tta);
-                    if (two && a.c == 4) hipLaunchKernelGGL((postproc_tiles_u16x2<TP, 4, decltype(ta)>), grid2, dim3(256), 0, st, a);
-                    else if (two) hipLaunchKernelGGL((postproc_tiles_u16x2<TP, 3>), grid2, dim3(256), 0, st, a);
-                    else hipLaunchKernelGGL((postproc_tiles<TP, TO, decltype(ta)>), grid, dim3(256), 0, st, a);
-                });
-            else if (sixteen) // (a uint8 image with a uint16 RGBA source)
-            {
-                if constexpr (std::is_same<TO, uint8_t>::value) hipLaunchKernelGGL((postproc_tiles<TP, TO, uint16_t>), grid, dim3(256), 0, st, a);
-            }
-            else if (staged && aligned) hipLaunchKernelGGL((postproc_tiles_lds<TP, TO>), dim3((max_ow + 31) / 32, (max_oh + 31) / 32, a.ntiles), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((postproc_tiles<TP, TO>), grid, dim3(256), 0, st, a);
+            with_dither(a, [&](auto di) {
+                constexpr bool DI = decltype(di)::value && is_hwc<TO>; // (a planar float image is never dithered: no instantiation for it)
+                if constexpr (std::is_same<TO, uint16_t>::value)
+                    with_alpha_type(a, [&](auto ta) {
+                        const dim3 grid2((max_ow / 2 + 63) / 64, (max_oh + 3) / 4, a.ntiles);
+                        // Measured on the C2 frame (profiles/rgb16.txt): two pixels per thread 0.128 ms against 0.136 for one (RGBA 0.390 against
+                        // 0.453); under TTA the gather dominates and the pair's doubled registers cost more than its stores save (RGB 1.816
+                        // against 1.661).  Default: two without TTA, one with; variant 1 / 2 force one / two (the bytes are the same).
+                        const bool two = a.variant == 2 || (a.variant == 0 && !a.tta);
+                        if (two && a.c == 4) hipLaunchKernelGGL((postproc_tiles_u16x2<TP, 4, decltype(ta), DI>), grid2, dim3(256), 0, st, a);
+                        else if (two) hipLaunchKernelGGL((postproc_tiles_u16x2<TP, 3, uint8_t, DI>), grid2, dim3(256), 0, st, a);
+                        else hipLaunchKernelGGL((postproc_tiles<TP, TO, decltype(ta), DI>), grid, dim3(256), 0, st, a);
+                    });
+                else if (sixteen) // (a uint8 image with a uint16 RGBA source)
+                {
+                    if constexpr (std::is_same<TO, uint8_t>::value) hipLaunchKernelGGL((postproc_tiles<TP, TO, uint16_t, DI>), grid, dim3(256), 0, st, a);
+                }
+                else if (staged && aligned)
+                    hipLaunchKernelGGL((postproc_tiles_lds<TP, TO, DI>), dim3((max_ow + 31) / 32, (max_oh + 31) / 32, a.ntiles), dim3(256), 0, st, a);
+                else hipLaunchKernelGGL((postproc_tiles<TP, TO, uint8_t, DI>), grid, dim3(256), 0, st, a);
+            });
         });
     });
 }

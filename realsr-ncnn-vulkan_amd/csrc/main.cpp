@@ -18,6 +18,8 @@
 //   * RSR_BLEND=<model-dir>:<t> (no counterpart): beside -m, a second model of the same depth and a strength t in [0, 1]; every context
 //     loads it (rsr_load_second) and runs on the weights (1 - t) * <-m model> + t * <model-dir> (rsr_set_blend): network interpolation,
 //     e.g. -m models-DF2K with RSR_BLEND=models-DF2K_JPEG:0.4;
+//   * RSR_DITHER=1 (no counterpart): the colour samples of every integer output -- 8- and 16-bit images, Y4M frames -- are rounded against
+//     the library's position-keyed threshold instead of 0.5 (rsr_set_option "dither"): gradients leave as fine static noise, not as bands;
 //   * video mode (no counterpart): an input that ends in .y4m, or is "-" (stdin), is a YUV4MPEG2 stream and runs through one rsr_video
 //     session to a .y4m output or "-" (stdout) -- run_video below, y4m_io.h.
 #include <dirent.h>
@@ -59,6 +61,8 @@ static void print_usage()
     fprintf(stderr, "                       (8-bit sources widened by x257); auto = 16-bit png/pnm inputs with a .png output keep their 16 bits\n");
     fprintf(stderr, "  RSR_ALPHA=net|bicubic alpha of RGBA images (default=bicubic): net = through the network as a gray image, about twice the\n");
     fprintf(stderr, "                       time; a fully opaque alpha stays opaque and costs one pass\n");
+    fprintf(stderr, "  RSR_DITHER=0|1       ordered dither of the integer outputs (default=0): 1 = colour samples of 8- / 16-bit images and Y4M\n");
+    fprintf(stderr, "                       frames are rounded against a position-keyed threshold, so smooth gradients do not band\n");
     fprintf(stderr, "  RSR_BLEND=dir:t      a second model directory of the same depth and a strength t in [0, 1]: the weights are\n");
     fprintf(stderr, "                       (1 - t) * the -m model + t * the model of dir (network interpolation)\n");
 }
@@ -444,6 +448,19 @@ int main(int argc, char** argv)
             return -1;
         }
     }
+    // RSR_DITHER=0|1 (no flag of the reference's surface is taken for it): option "dither" of every context, set ONCE below -- the 8-bit and
+    // the RSR_DEPTH 16-bit image routes and the Y4M route alike.  Anything else is refused here, before any GPU work.
+    bool dither = false;
+    if (const char* di = getenv("RSR_DITHER"))
+    {
+        const std::string v(di);
+        if (v == "1") dither = true;
+        else if (!v.empty() && v != "0")
+        {
+            fprintf(stderr, "invalid RSR_DITHER '%s' (0 or 1)\n", di);
+            return -1;
+        }
+    }
     // RSR_BLEND=<model-dir>:<t> (no flag of the reference's surface is taken for it): network interpolation between the -m model and the
     // one of <model-dir>, t a plain decimal in [0, 1] behind the LAST colon (digits with at most one point: no sign, no exponent, no blanks).
     std::string blend_dir, blend_text;
@@ -679,6 +696,11 @@ int main(int argc, char** argv)
         { // RSR_ALPHA=adaptive: the same for every image of this context
             rsr_set_option(ctxs[size_t(i)], "alpha_net", 1);
             rsr_set_option(ctxs[size_t(i)], "alpha_adaptive", 1);
+        }
+        if (dither)
+        { // RSR_DITHER=1: the same for every image and frame of this context
+            rsr_set_option(ctxs[size_t(i)], "dither", 1);
+            if (verbose) fprintf(stderr, "gpu %d: ordered dither of the integer outputs (RSR_DITHER)\n", gpuid[size_t(i)]);
         }
         // no flag of the reference's surface is taken for it: RSR_PRECISE=1 keeps a byte of rounding residue per element of the residual
         // trunk (rsr_set_option "precise"; what tools/check_real_model.py recommends for weights with a wide output swing)

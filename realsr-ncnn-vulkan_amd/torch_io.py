@@ -132,7 +132,10 @@ def upscale(sr, x, out=None, out_dtype=None):
     RGBA: the alpha of an (H, W, 4) input is the bicubic x4, or with sr.alpha_net = 1 the network's result for the gray image of the alpha
     (option "alpha_net": a second pass over the tiles, about twice the frame time); nothing here knows the option, the engine does.
     With sr.alpha_adaptive = 1 on top, tiles of constant alpha skip that pass; the engine then WAITS on the host once per tile batch, until
-    the current stream has reached its scan of the alpha: the call is no longer purely asynchronous and must not run under stream capture."""
+    the current stream has reached its scan of the alpha: the call is no longer purely asynchronous and must not run under stream capture.
+    Dither: with sr.dither = 1 the colour samples of an integer result (uint8, uint16 / int16) are rounded against a threshold keyed to their
+    place in the result (option "dither": gradients leave as fine static noise, not as bands; an out= window carries the pattern from its own
+    origin); alpha and float results are not touched.  Nothing here knows the option, the engine does."""
     fmt, batched = _check(sr, x)
     ydtype = x.dtype
     if out_dtype is not None:
@@ -380,7 +383,9 @@ def upscale_yuv(sr, surface, out=None, chroma=420):
     hold) -- a (3, H, W) tensor of the planes Y, U, V, uint8 or uint16 / int16 with the 10-bit code in the LOW bits (yuv444p10le), or a
     (y, u, v) triple of (H, W) views.  Any H and W >= 1, odd ones included: no parity rule exists.  The view needs stride 1 along W, one row
     stride for all planes and equally spaced planes -- a crop, a window of a canvas -- and is then taken without a copy; ValueError
-    otherwise.  The result is (3, H', W') of the same dtype (or a triple), sized by sr.out_size_fmt; out= takes a window."""
+    otherwise.  The result is (3, H', W') of the same dtype (or a triple), sized by sr.out_size_fmt; out= takes a window.
+    sr.dither = 1 (option "dither") holds here as in upscale: every Y, U and V code is rounded against the threshold of its own place in its
+    own plane, the (U, V) pair of a chroma sample against one; at 10 bits sr.set_option("precise", 1) is its companion."""
     _check_chroma(chroma, "upscale_yuv")
     if chroma == 444:
         return _upscale_yuv444(sr, surface, out)

@@ -5,7 +5,8 @@
 
 Prints every kernel of the first report whose VGPRs, AGPRs, scratch, occupancy or LDS differ in the second, then the kernels only the
 second has, with their registers, scratch and occupancy.  Kernels are matched by their mangled names; a post kernel that gained the
-defaulted alpha-source template argument (a trailing `h` = unsigned char in front of the closing E) is matched with its old name."""
+defaulted alpha-source template argument (a trailing `h` = unsigned char in front of the closing E) is matched with its old name, and so is one that gained the defaulted dither
+argument (a trailing `Lb0E`)."""
 import re
 import sys
 
@@ -27,6 +28,9 @@ def parse(path):
 
 
 def parent_name(n):
+    # a post kernel that gained the defaulted dither template argument (a trailing `Lb0E` = false) is matched with its old name
+    if re.match(r"_ZN3rsr\d+postproc_tiles\w*I", n) and n.endswith("Lb0EEEvNS_8PostArgsE"):
+        return n[:-len("Lb0EEEvNS_8PostArgsE")] + "EEvNS_8PostArgsE"
     if re.match(r"_ZN3rsr(14postproc_tiles|18postproc_tiles_box|19postproc_tiles_area)I", n) and n.endswith("hEEvNS_8PostArgsE"):
         return n[:-len("hEEvNS_8PostArgsE")] + "EEvNS_8PostArgsE"
     return n
